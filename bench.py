@@ -25,6 +25,10 @@ class against that class's first GOP), and -- labelled extras, never `value` -- 
 frame's pictures uploaded and its results downloaded, overlapped with the compute), `g_sweep` (throughput against the number of
 GOPs in flight), `clip_600` (BASELINE config 3's 600 frames as closed GOPs of --keyint frames: wall time of the whole clip) and
 `config4_literal` (8 closed GOPs).
+
+--dump-outputs DIR: after the timed steps, what a caller holds when the last of them is done -- pass-1 records, embedding vectors,
+final motion vectors and (closed loop) the deblocked pictures of a fixed seeded choice of GOPs -- as DIR/<name>.npy, for comparing
+two builds of the library output for output (dump_outputs below).
 """
 import argparse
 import hashlib
@@ -35,6 +39,7 @@ import subprocess
 import sys
 import threading
 import time
+import zlib
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, "video-steganography-pcamv_amd"))
@@ -43,6 +48,8 @@ B_SEARCH = 1920.0       # algorithmic bytes per macroblock of one a
 B_WHOLE = 5888.0        # ... of both passes of the closed loop: 2 x (1920 + 1024)
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md
 MB_RECORD = 236         # sizeof(pcamv_mb_t)
+DUMP_GOPS = 8           # --dump-outputs: GOPs sampled
+DUMP_BYTES = 64000000   # ... and the most it writes, the .npy headers included
 
 
 def parse_args():
@@ -68,6 +75,7 @@ def parse_args():
     ap.add_argument("--g-sweep", default="1,8,20,64,256,1024,2048", help="GOP counts of the low-G sweep ('' = skip; rank 0, N=1 only)")
     ap.add_argument("--cpu-frames", type=int, default=24, help="1080p P frames timed for the CPU baseline (0 = skip the CPU baseline)")
     ap.add_argument("--cpu-cif-frames", type=int, default=200, help="CIF P frames timed through the reference itself (oracle/_ref) and through the port (0 = skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed (a fixed seeded sample of it, at most 64 MB) as DIR/<name>.npy (rank 0)")
     return ap.parse_args()
 
 
@@ -122,6 +130,48 @@ class Gops:
         self.batch.close()
         for e in self.encs:
             e.close()
+
+
+def dump_outputs(path, run, closed_loop):
+    """--dump-outputs: the results of the step the device ran last, as a caller of the C ABI receives them, for DUMP_GOPS GOPs drawn
+    with a fixed seed out of all that are in flight: <name>.npy = that output of the drawn GOPs, stacked in GOP order (mb_<field>: the
+    pass-1 records; final_mv: the motion vectors pass 2 coded; embed_<vector>: the GOPs' vectors one after the other, embed_n / embed_m
+    / embed_num_flip their lengths; recon_y/u/v: the deblocked picture).  Two members of the record are no output and are left out:
+    `pad`, and `ref` -- the library takes one reference frame (pcamv_gpu_open refuses more), so every inter block's reference index is 0.  Integers of up to 16 bits and floats are written as float32,
+    wider integers as float64 (both exact).  Above DUMP_BYTES in all, every array keeps the same fraction of its elements, drawn with a
+    seed made of its name.  Nothing here depends on anything but the arguments, so two runs of the same command compare file by file."""
+    import numpy as np
+    G = len(run.encs)
+    gops = sorted(np.random.default_rng(20).choice(G, size=min(G, DUMP_GOPS), replace=False).tolist())
+    per_gop = []
+    for k in gops:
+        mbs, emb = run.encs[k].fetch_results(want_embed=True)
+        o = {"mb_" + f: mbs[f] for f in mbs.dtype.names if f not in ("pad", "ref")}
+        o["final_mv"] = run.encs[k].final_mvs(mbs)["mv"]
+        for v in ("cover", "rho", "message", "stego", "flip"):
+            o["embed_" + v] = np.asarray(emb[v])
+        for c in ("n", "m", "num_flip"):
+            o["embed_" + c] = np.array([emb[c]], np.int64)
+        if closed_loop:
+            o.update(zip(("recon_y", "recon_u", "recon_v"), run.encs[k].fetch_recon()))
+        per_gop.append(o)
+    arrays = {}
+    for name in per_gop[0]:
+        a = [o[name] for o in per_gop]
+        a = np.concatenate(a) if name.startswith("embed_") else np.stack(a)
+        arrays[name] = a.astype(np.float32 if a.dtype.kind == "f" or a.dtype.itemsize <= 2 else np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    keep = min(1.0, (DUMP_BYTES - 256 * len(arrays)) / total)      # (an .npy header of these shapes is 128 bytes)
+    os.makedirs(path, exist_ok=True)
+    written = 0
+    for name, a in arrays.items():
+        if keep < 1.0:
+            idx = np.random.default_rng(zlib.crc32(name.encode())).choice(a.size, size=int(a.size * keep), replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(path, name + ".npy"), a)
+        written += os.path.getsize(os.path.join(path, name + ".npy"))
+    assert written <= DUMP_BYTES
+    return {"dir": path, "gops": gops, "arrays": len(arrays), "bytes": written, "fraction_of_elements_kept": keep}
 
 
 def main():
@@ -255,6 +305,7 @@ def main():
     if ber is not None:
         ber /= ber_bits
     mbs, emb = chk[0][0], chk[0][1]
+    dumped = dump_outputs(args.dump_outputs, run, closed_loop) if args.dump_outputs and rank == 0 else None
 
     # ---- parity at scale: what the timed loop computed (4 waves per SIMD, eight queues, work stealing, second-pass tasks of 8
     # macroblocks) against the CPU port on the same chained frames.  The port runs in threads (ctypes releases the GIL) while the
@@ -382,6 +433,8 @@ def main():
     }
     if gathered is not None:
         out["gathered_payloads"] = gathered
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
 
     solo = rank == 0 and world == 1
     # ---- PCIe-inclusive pipeline (extra): every step's source pictures go host -> device and its records + flip maps device -> host,

@@ -51,6 +51,34 @@ def test_content_classes_are_compared_within_class():
     assert j["parity_at_scale"]["content_classes"] == 4 and j["parity_at_scale"]["gops_identical_within_class"] is True and j["parity_at_scale"]["ok"] is True
 
 
+def test_dump_outputs_repeat_and_follow_the_timed_steps(tmp_path):
+    """--dump-outputs: float32 / float64 .npy files, at most 64 MB in all, the same from run to run of one command; and --steps is the
+    number of timed steps: the dump after 1 warm-up + 2 timed steps is that after 2 + 1 (the same three chained frames), not that after 1 + 3"""
+    import numpy as np
+    quiet = ("--cpu-frames", "0", "--host-io-steps", "0", "--g-sweep", "", "--clip-keyints", "", "--parity-gops", "0")
+
+    def dump(tag, warmup, steps):
+        d = tmp_path / tag
+        j = _run("--warmup", str(warmup), "--steps", str(steps), "--dump-outputs", str(d), *quiet)
+        assert j["steps"] == steps and j["warmup"] == warmup and j["dumped_outputs"]["gops"] == [0, 1, 2, 3, 4, 5]
+        files = sorted(os.listdir(d))
+        assert files and all(f.endswith(".npy") for f in files)
+        assert sum(os.path.getsize(d / f) for f in files) == j["dumped_outputs"]["bytes"] <= 64000000
+        out = {f[:-4]: np.load(d / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) and a.size > 0 for a in out.values())
+        return out
+
+    a, again, b, c = dump("a", 1, 2), dump("again", 1, 2), dump("b", 2, 1), dump("c", 1, 3)
+    for name in ("mb_mv", "mb_inter_stego_cost", "final_mv", "embed_flip", "embed_rho", "recon_y", "recon_u", "recon_v"):
+        assert name in a, name
+    assert a["recon_y"].shape == (6, 288, 352) and a["mb_mv"].shape == (6, 396, 16, 2) and a["embed_n"].sum() == len(a["embed_flip"]) > 0
+    for other in (again, b):
+        assert sorted(other) == sorted(a)
+        for name in a:
+            assert np.array_equal(a[name], other[name], equal_nan=True), name
+    assert not np.array_equal(a["recon_y"], c["recon_y"]) and not np.array_equal(a["mb_mv"], c["mb_mv"])
+
+
 def test_strong_mode_gathers_payloads_and_two_ranks_agree():
     """--strong on one rank, then the N > 1 path as the driver launches it -- two ranks through torch.distributed.run (bench.py starts
     them itself, before anything touches the GPU), sharded GOPs, all_reduce of the time, all_gather + gather of the payloads -- on the
