@@ -25,6 +25,8 @@
  *   pcamv_gpu_embed_pframe      cover/cost assembly + message + stc_embed + flip map,
  *                               encoder.c:1561-1855, embed.h:309-548
  *   pcamv_gpu_stc_extract       (no reference counterpart: extractor defined in SURVEY 8(c))
+ *   pcamv_gpu_set_payload*      the message source, encoder.c:1838-1840 (rand() there: a caller's payload here)
+ *   pcamv_gpu_*extract_*, rx_*  (no reference counterpart: the extractor is absent from the reference)
  *   pcamv_gpu_close             x264_encoder_close's frees
  *
  * All functions return 0 on success and a negative PCAMV_E* code on error; the message is
@@ -36,6 +38,7 @@
 #ifndef PCAMV_GPU_H
 #define PCAMV_GPU_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -145,7 +148,8 @@ int pcamv_gpu_analyse_pframe(pcamv_ctx_t *ctx, int qp, int embed, pcamv_mb_t *ou
 /* Embedding stage on the records of the last analyse call.  emrate as x264's --emrate
  * (encoder.c:1828-1836): 0 < r <= 1 bits per MV, r > 1 bits per frame.  message == NULL
  * draws the bits from the context's glibc-compatible rand() stream (seed 1 at open, as the
- * reference never calls srand, encoder.c:1838-1840); otherwise message[0..m) is used. */
+ * reference never calls srand, encoder.c:1838-1840) -- or, with a payload attached (pcamv_gpu_set_payload below), the
+ * payload's next m bits; otherwise message[0..m) is used. */
 int pcamv_gpu_embed_pframe(pcamv_ctx_t *ctx, float emrate, const uint8_t *message, int message_len,
                            pcamv_embed_t *out);
 
@@ -221,6 +225,7 @@ int pcamv_gpu_fetch_results(pcamv_ctx_t *ctx, pcamv_mb_t *out_mb, pcamv_embed_t 
 int  pcamv_gpu_batch_create(pcamv_ctx_t *const *ctxs, int n, pcamv_batch_t **batch);
 void pcamv_gpu_batch_destroy(pcamv_batch_t *batch);
 int  pcamv_gpu_batch_step(pcamv_batch_t *batch, int qp, float emrate, void *stream);
+/* kernel: the dominant kernel's name (below), or one of "k_embed_prepare", "k_extract_prepare", "k_extract_bits", "k_payload_check" */
 int  pcamv_gpu_batch_kernel_time(pcamv_batch_t *batch, const char *kernel, double *avg_ms, int *launches, int reset);
 const char *pcamv_gpu_batch_last_error(const pcamv_batch_t *batch);
 /* Closed loop on the device: with on != 0 every batch step ends with pass 2 + the loop filter (embedding must be
@@ -272,6 +277,51 @@ int pcamv_gpu_debug_state_hash(pcamv_ctx_t *ctx, int enable);
 int pcamv_gpu_debug_state_hash_fetch(pcamv_ctx_t *ctx, uint32_t *out);
 
 int pcamv_gpu_abi_version(void);
+/* What the library can do beyond the calls of its ABI version: a mask of PCAMV_FEATURE_* (additions keep the version). */
+#define PCAMV_FEATURE_PAYLOAD 0x1u      /* the payload path below */
+unsigned pcamv_gpu_features(void);
+
+/* ---- Payload path: the caller's bits through the device-resident entry points, and back out on the device ----
+ *
+ * Sender.  The reference takes every frame's message from rand() (encoder.c:1838-1840), and so do embed_pframe(message == NULL),
+ * step_device and batch_step.  A payload attached to a context replaces that source: packed bytes, 8 bits per byte, most
+ * significant bit first, n_bits long.  A frame that embeds m bits takes payload bits cursor .. cursor + m - 1 (zeros past the
+ * payload's end) and the cursor -- a device word, so closed-loop steps need no host round trip although m is only known on the
+ * device -- advances by m whatever stc_ok turns out to be, like the rand() stream does: a frame whose embedding failed costs its
+ * own m bits and nothing after them, sender and receiver offsets stay aligned.  Attaching sets the cursor to 0.  While a payload
+ * is attached the rand() state does not move; attaching NULL / 0 detaches, and the context embeds the rand() stream again from
+ * where it stood.  An explicit `message` of pcamv_gpu_embed_pframe still wins and does not move the cursor.
+ * set_payload copies host bytes; set_payload_device borrows a device buffer the caller keeps alive while attached.
+ * payload_tell synchronises: bits consumed so far, bits of the attached payload. */
+int pcamv_gpu_set_payload(pcamv_ctx_t *ctx, const uint8_t *bytes, int64_t n_bits);
+int pcamv_gpu_set_payload_device(pcamv_ctx_t *ctx, const void *device_bytes, int64_t n_bits);
+int pcamv_gpu_payload_tell(pcamv_ctx_t *ctx, int64_t *consumed_bits, int64_t *payload_bits);
+
+/* Receiver (kernels k_extract_prepare, k_extract_bits; the reference has no extractor).  A frame's message is read
+ * from its FINAL motion the way a decoder sees it: carriers in embedding order (encoder.c:1566-1647) of every coded macroblock
+ * (i_type != PCAMV_P_SKIP), stego bit = LSB(mvx + mvy), m from n and emrate as the embedding stage computes it, the two
+ * sub-matrices from a receive-side column generator of the context's own (initialised like the sender's, advanced the same way:
+ * see pcamv_gpu_stc_extract_lcg), one thread per message bit.  The bits are packed like the payload and appended to the context's
+ * received stream at a device-side write cursor that moves by m; a frame with m > n, or with sub-matrices that cannot be built,
+ * appends m zero bits.
+ * rx_reserve makes room for n_bits (0 releases) and empties the stream; rx_reset empties it (cursor 0, generator at its initial
+ * state).  A frame that runs past the reservation sets a device flag, its bits beyond are dropped (nothing is written out of
+ * bounds), and the next synchronising call of this group reports PCAMV_ENOMEM once.  rx_tell / rx_fetch synchronise. */
+int pcamv_gpu_rx_reserve(pcamv_ctx_t *ctx, int64_t n_bits);
+int pcamv_gpu_rx_reset(pcamv_ctx_t *ctx);
+int pcamv_gpu_rx_tell(pcamv_ctx_t *ctx, int64_t *received_bits, int64_t *reserved_bits);
+int pcamv_gpu_rx_fetch(pcamv_ctx_t *ctx, uint8_t *bytes, int64_t n_bits);
+/* Every context's last step (its records and the flip map of its embedding stage, on the device: final MV = mv_stego where the map
+ * says so, what pcamv_gpu_final_mvs returns) through the receiver, on `stream`, without a host synchronisation; call it after a
+ * batch_step with the same emrate, between closed-loop steps or after the last.  Every context needs a reservation. */
+int pcamv_gpu_batch_extract_step(pcamv_batch_t *batch, float emrate, void *stream);
+/* One frame from host records that hold final motion (pcamv_gpu_parse_pslice_*): uploaded, same kernels.  bits_out (optional, room
+ * for 16 * mb_count) receives the message bits one per byte, n / m (optional) the frame's carriers and message bits; with a
+ * reservation the bits are appended to the received stream too.  Synchronises. */
+int pcamv_gpu_extract_pframe(pcamv_ctx_t *ctx, const pcamv_mb_t *mbs, float emrate, uint8_t *bits_out, int32_t *n, int32_t *m);
+/* diff[i] = number of bits in which context i's received stream differs from its attached payload, payload bits past its end
+ * counting as zeros: the BER numerator of every chain from one kernel and one small copy.  Synchronises. */
+int pcamv_gpu_batch_payload_check(pcamv_batch_t *batch, int64_t *diff);
 
 #ifdef __cplusplus
 }

@@ -22,6 +22,9 @@
 #define PCAMV_SPEC2_MAX_CHAINS 704
 #define NEV 32
 #define NRING 8
+#define NKEV 16                /* launches a timer of the smaller kernels remembers between two kernel_time calls */
+enum { KT_EMBED_PREPARE, KT_EXTRACT_PREPARE, KT_EXTRACT_BITS, KT_PAYLOAD_CHECK, KT_N };
+#define PCAMV_FEATURES PCAMV_FEATURE_PAYLOAD
 
 struct pcamv_ctx;
 /* A batch = the set of independent closed-GOP contexts whose frames advance together: every kernel
@@ -42,8 +45,14 @@ struct pcamv_batch {
     int b_mbrd, b_tesa;         /* instance of the analysis kernel the batch's contexts need (fixed at creation) */
     unsigned *d_flow;
     FlowDev fl, fl2;          /* queue descriptors of the analysis and of the second pass */
+    /* payload path: descriptors of the receiving side (their own ring, made by the first extraction), the per-context counts of
+     * payload_check, and the timers of the kernels besides the dominant one */
+    ExtractDev *h_X, *d_X; long long *d_chk;
+    hipEvent_t xslot_done[NRING]; int xslot_used[NRING], xhead;
+    struct KTimer { hipEvent_t e0[NKEV], e1[NKEV]; int made, n, head, launches; double ms; } kt[KT_N];
     char err[256];
 };
+static const char *const kt_names[KT_N] = {"k_embed_prepare", "k_extract_prepare", "k_extract_bits", "k_payload_check"};
 
 struct pcamv_ctx {
     pcamv_params_t p;
@@ -64,6 +73,10 @@ struct pcamv_ctx {
     uint8_t *d_cover, *d_stego, *d_message, *d_user_msg; unsigned *d_colinfo;
     float *d_rho; int8_t *d_flip; int *d_hdr, *d_rnd; unsigned *d_cols, *d_path; long long *d_lcg;
     int cap;
+    /* payload path: the attached payload (own copy, or the caller's device buffer), the cursors (PST_*), the received stream and the
+     * receiver's scratch (made by pcamv_gpu_rx_reserve / the first extraction) */
+    uint8_t *d_payload_own; size_t payload_own_bytes; long long *d_pstate;
+    ExtractDev X; unsigned *d_rx; uint8_t *d_rx_stego, *d_rx_bits; int *d_rx_hdr; unsigned *d_rx_cols; pcamv_mb_t *d_rx_mbs;
     int *d_trace;
     uint16_t *d_nnz; int *d_car_base; int8_t *d_flip_user;     /* pass 2 */
     uint8_t *d_mbflip;         /* [n_mb] per macroblock: a carrier of it is flipped in d_flip */
@@ -87,6 +100,7 @@ static int bfail(pcamv_batch *b, int code, const char *fmt, ...)
 #define HIPCHKB(b, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return bfail(b, PCAMV_EHIP, "%s: %s", #call, hipGetErrorString(e_)); } while (0)
 
 extern "C" int pcamv_gpu_abi_version(void) { return PCAMV_ABI_VERSION; }
+extern "C" unsigned pcamv_gpu_features(void) { return PCAMV_FEATURES; }
 #ifdef PCAMV_PROF
 int pcamv_rd_prof_fetch(unsigned long long *out, int reset);
 int pcamv_rd_prof_fetch_lo(unsigned long long *out, int reset);
@@ -155,6 +169,10 @@ extern "C" void pcamv_gpu_batch_destroy(pcamv_batch_t *b)
     if (b->h_E) hipHostFree(b->h_E);
     hipFree(b->d_F); hipFree(b->d_E);
     if (b->d_flow) hipFree(b->d_flow);
+    if (b->h_X) hipHostFree(b->h_X);
+    hipFree(b->d_X); hipFree(b->d_chk);
+    for (int i = 0; i < NRING; i++) if (b->xslot_done[i]) hipEventDestroy(b->xslot_done[i]);
+    for (int k = 0; k < KT_N; k++) for (int i = 0; i < NKEV; i++) { if (b->kt[k].e0[i]) hipEventDestroy(b->kt[k].e0[i]); if (b->kt[k].e1[i]) hipEventDestroy(b->kt[k].e1[i]); }
     for (int i = 0; i < NRING; i++) if (b->slot_done[i]) hipEventDestroy(b->slot_done[i]);
     for (int i = 0; i < NEV; i++) { if (b->ev0[i]) hipEventDestroy(b->ev0[i]); if (b->ev1[i]) hipEventDestroy(b->ev1[i]); }
     free(b->ctx);
@@ -388,6 +406,8 @@ static int open_impl(pcamv_ctx *c, const pcamv_params_t *p, int device)
     int rnd[40]; memset(rnd, 0, sizeof(rnd)); glibc_srand_state(rnd, 1);
     HIPCHK(c, hipMemcpy(c->d_rnd, rnd, sizeof(rnd), hipMemcpyHostToDevice));
     long long lcg = 1; HIPCHK(c, hipMemcpy(c->d_lcg, &lcg, sizeof(lcg), hipMemcpyHostToDevice));
+    const long long pstate[PST_WORDS] = {0, 0, 0, 1};       /* cursors at 0; the receiver's column generator starts like the sender's */
+    HIPCHK(c, dalloc(&c->d_pstate, PST_WORDS)); HIPCHK(c, hipMemcpy(c->d_pstate, pstate, sizeof(pstate), hipMemcpyHostToDevice));
     for (int i = 0; i < 3; i++) { F.fenc[i] = c->d_fenc[i]; F.rec[i] = c->d_rec[i]; F.raw[i] = c->d_raw[i]; }
     F.luma_base = c->d_luma; F.chroma_base[0] = c->d_chroma[0]; F.chroma_base[1] = c->d_chroma[1];
     F.luma_raster = c->d_luma_raster;
@@ -401,6 +421,8 @@ static int open_impl(pcamv_ctx *c, const pcamv_params_t *p, int device)
     E.mbflip = c->d_mbflip;
     E.flip = c->d_flip; E.hdr = c->d_hdr; E.cols = c->d_cols; E.path = c->d_path; E.rnd = c->d_rnd;
     E.lcg = c->d_lcg; E.colinfo = c->d_colinfo; E.cap = c->cap; E.car_base = c->d_car_base; E.user_message = NULL; E.user_message_len = 0; E.emrate = 0;
+    E.payload = NULL; E.payload_bits = 0; E.pstate = c->d_pstate;
+    c->X.n_mb = F.n_mb; c->X.cap = c->cap; c->X.pstate = c->d_pstate;
     pcamv_ctx *one[1] = {c};
     return pcamv_gpu_batch_create(one, 1, &c->self);
 }
@@ -422,6 +444,8 @@ extern "C" void pcamv_gpu_close(pcamv_ctx_t *c)
     for (int q = 0; q < 52; q++) if (c->d_cost_mv[q]) hipFree(c->d_cost_mv[q]);
     hipFree(c->d_cover); hipFree(c->d_stego); hipFree(c->d_message); hipFree(c->d_colinfo); hipFree(c->d_user_msg); hipFree(c->d_rho);
     hipFree(c->d_flip); hipFree(c->d_hdr); hipFree(c->d_rnd); hipFree(c->d_cols); hipFree(c->d_lcg); hipFree(c->d_path);
+    hipFree(c->d_payload_own); hipFree(c->d_pstate); hipFree(c->d_rx); hipFree(c->d_rx_stego); hipFree(c->d_rx_bits); hipFree(c->d_rx_hdr);
+    hipFree(c->d_rx_cols); hipFree(c->d_rx_mbs);
     if (c->d_trace) hipFree(c->d_trace);
     hipFree(c->d_nnz); hipFree(c->d_car_base); hipFree(c->d_flip_user); hipFree(c->d_mbflip);
     hipFree(c->d_nb_nz); hipFree(c->d_nb_cbp); hipFree(c->d_nb_mvd); hipFree(c->d_cabac); hipFree(c->d_cabac_tab); hipFree(c->d_dbg_hash);
@@ -513,6 +537,27 @@ static int batch_release_slot(pcamv_batch *b, int slot, hipStream_t st)
     return 0;
 }
 
+/* hipEvents around a launch of one of the smaller kernels (pcamv_gpu_batch_kernel_time reports them under their names); the events
+ * of a timer are made the first time its kernel is launched through the batch */
+static int kt_begin(pcamv_batch *b, int k, hipStream_t st)
+{
+    pcamv_batch::KTimer &T = b->kt[k];
+    if (T.made < 0) return -1;
+    if (!T.made) {
+        for (int i = 0; i < NKEV; i++) if (hipEventCreate(&T.e0[i]) != hipSuccess || hipEventCreate(&T.e1[i]) != hipSuccess) { T.made = -1; return -1; }
+        T.made = 1;
+    }
+    hipEventRecord(T.e0[T.head], st);
+    return T.head;
+}
+static void kt_end(pcamv_batch *b, int k, int ev, hipStream_t st)
+{
+    pcamv_batch::KTimer &T = b->kt[k];
+    if (ev < 0) return;
+    hipEventRecord(T.e1[ev], st);
+    T.head = (T.head + 1) % NKEV; if (T.n < NKEV) T.n++;
+}
+
 /* what: bit0 plane production, bit1 analysis (search+RCA+encode), bit2 embedding */
 static int batch_launch(pcamv_batch *b, int what, hipStream_t st, int timed)
 {
@@ -574,7 +619,9 @@ static int batch_launch(pcamv_batch *b, int what, hipStream_t st, int timed)
         }
     }
     if (what & 4) {
+        const int ev = timed ? kt_begin(b, KT_EMBED_PREPARE, st) : -1;
         hipLaunchKernelGGL(k_embed_prepare, dim3(G), dim3(1024), 0, st, dE);
+        kt_end(b, KT_EMBED_PREPARE, ev, st);
         /* 2 trellis states per thread: measured 3.25 / 2.89 / 2.90 ms per 1080p frame for 1 / 2 / 4 */
         /* (one frame alone: 2 trellis states per thread is the fastest chain; thousands of frames: 4 states per thread = 4 waves per frame, so
          * that a CU holds eight frames' trellises instead of four and the batch needs half the rounds: 18.6 -> 13.3 ms per 4096-frame step) */
@@ -841,6 +888,234 @@ extern "C" int pcamv_gpu_fetch_results(pcamv_ctx_t *c, pcamv_mb_t *out_mb, pcamv
     return 0;
 }
 
+/* ------------------------------------------------------------------ payload path
+ * Sender: a payload attached to a context is what its frames embed wherever no caller's message is given (embed_pframe(NULL),
+ * step_device, batch_step in open and closed loop) -- the reference draws those bits from rand() (encoder.c:1838-1840); the cursor
+ * lives on the device and moves by each frame's m there, so closed-loop steps need no host round trip. */
+static int payload_attach(pcamv_ctx *c, const uint8_t *d_bytes, int64_t n_bits)
+{
+    c->E.payload = n_bits > 0 ? d_bytes : NULL; c->E.payload_bits = n_bits > 0 ? n_bits : 0;
+    c->X.payload = c->E.payload; c->X.payload_bits = c->E.payload_bits;
+    HIPCHK(c, hipMemset(c->d_pstate + PST_TX, 0, sizeof(long long)));
+    return 0;
+}
+extern "C" int pcamv_gpu_set_payload(pcamv_ctx_t *c, const uint8_t *bytes, int64_t n_bits)
+{
+    if (!c || n_bits < 0 || (n_bits > 0 && !bytes)) return PCAMV_EINVAL;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipDeviceSynchronize());          /* frames in flight still read the payload attached so far */
+    const size_t nb = bytes ? (size_t)((n_bits + 7) >> 3) : 0;
+    if (nb > c->payload_own_bytes) {
+        hipFree(c->d_payload_own); c->d_payload_own = NULL; c->payload_own_bytes = 0;
+        HIPCHK(c, dalloc(&c->d_payload_own, nb));
+        c->payload_own_bytes = nb;
+    }
+    if (nb) HIPCHK(c, hipMemcpy(c->d_payload_own, bytes, nb, hipMemcpyHostToDevice));
+    return payload_attach(c, nb ? c->d_payload_own : NULL, nb ? n_bits : 0);
+}
+extern "C" int pcamv_gpu_set_payload_device(pcamv_ctx_t *c, const void *d_bytes, int64_t n_bits)
+{
+    if (!c || n_bits < 0 || (n_bits > 0 && !d_bytes)) return PCAMV_EINVAL;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipDeviceSynchronize());
+    return payload_attach(c, d_bytes ? (const uint8_t *)d_bytes : NULL, d_bytes ? n_bits : 0);
+}
+/* after a synchronisation: did a frame run past the reserved received buffer?  (reported once, like flow_check) */
+static int rx_check(pcamv_ctx *c, long long *pstate_out)
+{
+    long long st[PST_WORDS];
+    HIPCHK(c, hipMemcpy(st, c->d_pstate, sizeof(st), hipMemcpyDeviceToHost));
+    if (pstate_out) memcpy(pstate_out, st, sizeof(st));
+    if (st[PST_OVERRUN]) {
+        hipMemset(c->d_pstate + PST_OVERRUN, 0, sizeof(long long));
+        return fail(c, PCAMV_ENOMEM, "received stream: %lld bits extracted, %lld reserved (the bits beyond were dropped)", st[PST_RX], c->X.rx_cap_bits);
+    }
+    return 0;
+}
+extern "C" int pcamv_gpu_payload_tell(pcamv_ctx_t *c, int64_t *consumed_bits, int64_t *payload_bits)
+{
+    if (!c) return PCAMV_EINVAL;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipDeviceSynchronize());
+    long long tx = 0;
+    HIPCHK(c, hipMemcpy(&tx, c->d_pstate + PST_TX, sizeof(tx), hipMemcpyDeviceToHost));
+    if (consumed_bits) *consumed_bits = tx;
+    if (payload_bits) *payload_bits = c->E.payload_bits;
+    return 0;
+}
+
+/* Receiver.  rx_reserve: room for n_bits of received stream (0 releases it) and the per-frame scratch; the stream starts empty, the
+ * receiver's column generator at its initial state. */
+static int rx_scratch(pcamv_ctx *c)
+{
+    if (c->d_rx_stego) return 0;
+    HIPCHK(c, dalloc(&c->d_rx_stego, (size_t)c->cap)); HIPCHK(c, dalloc(&c->d_rx_bits, (size_t)c->cap));
+    HIPCHK(c, dalloc(&c->d_rx_hdr, 8)); HIPCHK(c, dalloc(&c->d_rx_cols, 2 * STC_MAXW));
+    HIPCHK(c, hipMemset(c->d_rx_hdr, 0, 8 * sizeof(int)));
+    c->X.stego = c->d_rx_stego; c->X.hdr = c->d_rx_hdr; c->X.cols = c->d_rx_cols;
+    return 0;
+}
+extern "C" int pcamv_gpu_rx_reset(pcamv_ctx_t *c)
+{
+    if (!c) return PCAMV_EINVAL;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipDeviceSynchronize());
+    const long long st[3] = {0, 0, 1};          /* PST_RX, PST_OVERRUN, PST_RX_LCG */
+    HIPCHK(c, hipMemcpy(c->d_pstate + PST_RX, st, sizeof(st), hipMemcpyHostToDevice));
+    if (c->d_rx) HIPCHK(c, hipMemset(c->d_rx, 0, (size_t)((c->X.rx_cap_bits + 31) >> 5) * 4));
+    return 0;
+}
+extern "C" int pcamv_gpu_rx_reserve(pcamv_ctx_t *c, int64_t n_bits)
+{
+    if (!c || n_bits < 0) return PCAMV_EINVAL;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipDeviceSynchronize());
+    hipFree(c->d_rx); c->d_rx = NULL; c->X.rx = NULL; c->X.rx_cap_bits = 0;
+    if (n_bits) {
+        int rc = rx_scratch(c);
+        if (rc) return rc;
+        HIPCHK(c, dalloc(&c->d_rx, (size_t)((n_bits + 31) >> 5)));
+        c->X.rx = c->d_rx; c->X.rx_cap_bits = n_bits;
+    }
+    return pcamv_gpu_rx_reset(c);
+}
+extern "C" int pcamv_gpu_rx_tell(pcamv_ctx_t *c, int64_t *received_bits, int64_t *reserved_bits)
+{
+    if (!c) return PCAMV_EINVAL;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipDeviceSynchronize());
+    long long st[PST_WORDS];
+    const int rc = rx_check(c, st);
+    if (received_bits) *received_bits = st[PST_RX];
+    if (reserved_bits) *reserved_bits = c->X.rx_cap_bits;
+    return rc;
+}
+extern "C" int pcamv_gpu_rx_fetch(pcamv_ctx_t *c, uint8_t *bytes, int64_t n_bits)
+{
+    if (!c || !bytes || n_bits < 0 || n_bits > c->X.rx_cap_bits) return PCAMV_EINVAL;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipDeviceSynchronize());
+    int rc = rx_check(c, NULL);
+    if (rc) return rc;
+    if (n_bits) HIPCHK(c, hipMemcpy(bytes, c->d_rx, (size_t)((n_bits + 7) >> 3), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+/* the two kernels of the receiving side for nx frames whose descriptors are at dX; emrate bounds the message bits of a frame */
+static void extract_launch(pcamv_batch *b, const ExtractDev *dX, int nx, int cap, float emrate, hipStream_t st)
+{
+    int ev = b ? kt_begin(b, KT_EXTRACT_PREPARE, st) : -1;
+    hipLaunchKernelGGL(k_extract_prepare, dim3(nx), dim3(1024), 0, st, dX);
+    if (b) kt_end(b, KT_EXTRACT_PREPARE, ev, st);
+    /* workgroups per frame: enough for the most bits a frame of this rate can hold (+ the 63 positions in front of a frame's first
+     * bit); the kernel strides if a frame has more (it cannot) */
+    double most = emrate > 1.0f ? (double)(int)emrate : ceil((double)emrate * cap) + 1;
+    if (most > cap) most = cap;
+    const int groups = (int)((most + 63 + 255) / 256) > 0 ? (int)((most + 63 + 255) / 256) : 1;
+    ev = b ? kt_begin(b, KT_EXTRACT_BITS, st) : -1;
+    hipLaunchKernelGGL(k_extract_bits, dim3(groups, nx), dim3(256), 0, st, dX);
+    if (b) kt_end(b, KT_EXTRACT_BITS, ev, st);
+}
+/* descriptors of the batch's contexts as they stand, into the next slot of the receiving side's ring */
+static int batch_push_xdescs(pcamv_batch *b, hipStream_t st, const ExtractDev **dX, int *slot_out)
+{
+    if (!b->d_X) {
+        HIPCHKB(b, hipHostMalloc((void **)&b->h_X, sizeof(ExtractDev) * b->n * NRING, hipHostMallocDefault));
+        HIPCHKB(b, dalloc(&b->d_X, (size_t)b->n * NRING));
+        HIPCHKB(b, dalloc(&b->d_chk, (size_t)b->n));
+        for (int i = 0; i < NRING; i++) HIPCHKB(b, hipEventCreateWithFlags(&b->xslot_done[i], hipEventDisableTiming));
+    }
+    const int slot = b->xhead;
+    b->xhead = (b->xhead + 1) % NRING;
+    if (b->xslot_used[slot]) HIPCHKB(b, hipEventSynchronize(b->xslot_done[slot]));
+    ExtractDev *hX = b->h_X + (size_t)slot * b->n;
+    for (int i = 0; i < b->n; i++) hX[i] = b->ctx[i]->X;
+    HIPCHKB(b, hipMemcpyAsync(b->d_X + (size_t)slot * b->n, hX, sizeof(ExtractDev) * b->n, hipMemcpyHostToDevice, st));
+    *dX = b->d_X + (size_t)slot * b->n; *slot_out = slot;
+    return 0;
+}
+static int batch_release_xslot(pcamv_batch *b, int slot, hipStream_t st)
+{
+    HIPCHKB(b, hipEventRecord(b->xslot_done[slot], st));
+    b->xslot_used[slot] = 1;
+    return 0;
+}
+/* Every context's last step -- its records and the flip map of its embedding stage, both still on the device -- through the
+ * receiving side, on `stream`, without a host synchronisation: between two closed-loop steps, or after the last one. */
+extern "C" int pcamv_gpu_batch_extract_step(pcamv_batch_t *b, float emrate, void *stream)
+{
+    if (!b || emrate <= 0) return PCAMV_EINVAL;
+    HIPCHKB(b, hipSetDevice(b->device));
+    for (int i = 0; i < b->n; i++) {
+        pcamv_ctx *c = b->ctx[i];
+        if (!c) return bfail(b, PCAMV_EINVAL, "context %d of the batch was closed", i);
+        if (!c->d_rx) return bfail(b, PCAMV_EINVAL, "context %d has no received buffer (pcamv_gpu_rx_reserve)", i);
+        c->X.mbs = c->d_rec_mb; c->X.flip = c->d_flip; c->X.bits = NULL; c->X.emrate = emrate;
+    }
+    hipStream_t st = stream ? (hipStream_t)stream : b->ctx[0]->stream;
+    const ExtractDev *dX; int slot;
+    int rc = batch_push_xdescs(b, st, &dX, &slot);
+    if (rc) return rc;
+    extract_launch(b, dX, b->n, b->ctx[0]->cap, emrate, st);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return bfail(b, PCAMV_EHIP, "kernel launch: %s", hipGetErrorString(e));
+    return batch_release_xslot(b, slot, st);
+}
+/* One frame from host records holding FINAL motion (what pcamv_gpu_parse_pslice_* reads out of a stream): uploaded, then the same
+ * kernels.  bits_out (optional, 16 * mb_count bytes) receives the frame's message bits, one per byte; n / m its carriers and bits.
+ * With a received buffer reserved the bits are appended to it as well. */
+extern "C" int pcamv_gpu_extract_pframe(pcamv_ctx_t *c, const pcamv_mb_t *mbs, float emrate, uint8_t *bits_out, int32_t *n_out, int32_t *m_out)
+{
+    if (!c || !mbs || emrate <= 0) return PCAMV_EINVAL;
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = rx_scratch(c);
+    if (rc) return rc;
+    if (!c->d_rx_mbs) HIPCHK(c, dalloc(&c->d_rx_mbs, (size_t)c->F.n_mb));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(c->d_rx_mbs, mbs, (size_t)c->F.n_mb * sizeof(pcamv_mb_t), hipMemcpyHostToDevice));
+    c->X.mbs = c->d_rx_mbs; c->X.flip = NULL; c->X.bits = c->d_rx_bits; c->X.emrate = emrate;
+    pcamv_batch *b = c->self;
+    const ExtractDev *dX; int slot;
+    if ((rc = batch_push_xdescs(b, c->stream, &dX, &slot))) return fail(c, rc, "%s", b->err);
+    extract_launch(b, dX, 1, c->cap, emrate, c->stream);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(c, PCAMV_EHIP, "kernel launch: %s", hipGetErrorString(e));
+    if ((rc = batch_release_xslot(b, slot, c->stream))) return fail(c, rc, "%s", b->err);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    int hdr[8];
+    HIPCHK(c, hipMemcpy(hdr, c->d_rx_hdr, sizeof(hdr), hipMemcpyDeviceToHost));
+    if (hdr[0] < 0 || hdr[0] > c->cap || hdr[1] < 0) return fail(c, PCAMV_EHIP, "extract header corrupt");
+    if (n_out) *n_out = hdr[0];
+    if (m_out) *m_out = hdr[1];
+    const int m_copy = hdr[1] < c->cap ? hdr[1] : c->cap;
+    if (bits_out && m_copy) HIPCHK(c, hipMemcpy(bits_out, c->d_rx_bits, (size_t)m_copy, hipMemcpyDeviceToHost));
+    return rx_check(c, NULL);
+}
+/* diff[i] = bits in which context i's received stream differs from its attached payload (payload bits past its end are zeros): the
+ * BER numerator of every chain, one kernel over the batch and one copy.  Synchronises. */
+extern "C" int pcamv_gpu_batch_payload_check(pcamv_batch_t *b, int64_t *diff)
+{
+    if (!b || !diff) return PCAMV_EINVAL;
+    HIPCHKB(b, hipSetDevice(b->device));
+    for (int i = 0; i < b->n; i++) if (!b->ctx[i]) return bfail(b, PCAMV_EINVAL, "context %d of the batch was closed", i);
+    hipStream_t st = b->ctx[0]->stream;
+    HIPCHKB(b, hipDeviceSynchronize());
+    const ExtractDev *dX; int slot;
+    int rc = batch_push_xdescs(b, st, &dX, &slot);
+    if (rc) return rc;
+    int ev = kt_begin(b, KT_PAYLOAD_CHECK, st);
+    hipLaunchKernelGGL(k_payload_check, dim3(b->n), dim3(256), 0, st, dX, b->d_chk);
+    kt_end(b, KT_PAYLOAD_CHECK, ev, st);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return bfail(b, PCAMV_EHIP, "kernel launch: %s", hipGetErrorString(e));
+    if ((rc = batch_release_xslot(b, slot, st))) return rc;
+    HIPCHKB(b, hipStreamSynchronize(st));
+    static_assert(sizeof(long long) == sizeof(int64_t), "payload_check copies the counts as they are");
+    HIPCHKB(b, hipMemcpy(diff, b->d_chk, sizeof(int64_t) * b->n, hipMemcpyDeviceToHost));
+    for (int i = 0; i < b->n; i++) if ((rc = rx_check(b->ctx[i], NULL))) return bfail(b, rc, "context %d: %s", i, b->ctx[i]->err);
+    return 0;
+}
+
 static int batch_kernel_time(pcamv_batch *b, double *avg_ms, int *launches, int reset)
 {
     HIPCHKB(b, hipSetDevice(b->device));
@@ -858,7 +1133,23 @@ static int batch_kernel_time(pcamv_batch *b, double *avg_ms, int *launches, int 
 }
 extern "C" int pcamv_gpu_batch_kernel_time(pcamv_batch_t *b, const char *kernel, double *avg_ms, int *launches, int reset)
 {
-    if (!b || !kernel || strcmp(kernel, dominant_kernel(b))) return PCAMV_EINVAL;
+    if (!b || !kernel) return PCAMV_EINVAL;
+    for (int k = 0; k < KT_N; k++) {
+        if (strcmp(kernel, kt_names[k])) continue;
+        pcamv_batch::KTimer &T = b->kt[k];
+        HIPCHKB(b, hipSetDevice(b->device));
+        HIPCHKB(b, hipDeviceSynchronize());
+        for (int i = 0; i < T.n; i++) {         /* (a full ring holds the last NKEV launches, in any order: an average does not care) */
+            float ms = 0;
+            if (hipEventElapsedTime(&ms, T.e0[i], T.e1[i]) == hipSuccess) { T.ms += ms; T.launches++; }
+        }
+        T.n = 0; T.head = 0;
+        if (avg_ms) *avg_ms = T.launches ? T.ms / T.launches : 0;
+        if (launches) *launches = T.launches;
+        if (reset) { T.ms = 0; T.launches = 0; }
+        return 0;
+    }
+    if (strcmp(kernel, dominant_kernel(b))) return PCAMV_EINVAL;
     return batch_kernel_time(b, avg_ms, launches, reset);
 }
 extern "C" int pcamv_gpu_kernel_time(pcamv_ctx_t *c, const char *kernel, double *avg_ms, int *launches, int reset)
@@ -975,29 +1266,8 @@ extern "C" int pcamv_gpu_final_mvs(pcamv_ctx_t *c, pcamv_mb_t *mbs)
     return 0;
 }
 
-/* sub-matrix columns as the embedder gets them (embed.h:141-199): the published tables for widths 2..20, columns drawn from the
- * code's own LCG (embed.h:134-139) outside that range */
-static int host_stc_matrix(int width, int height, unsigned *cols, long long *lcg)
-{
-    if (width >= 2 && width <= 20 && height >= 7 && height <= 12) {
-        for (int i = 0; i < width; i++) cols[i] = pcamv_stc_mats[(height - 7) * 400 + (width - 1) * 20 + i];
-        return 1;
-    }
-    if (!lcg || width < 1 || width > STC_MAXW || (1 << (height - 2)) < width) return 0;
-    unsigned mask = (1u << (height - 2)) - 1, bop = (1u << (height - 1)) + 1;
-    long hold = (long)*lcg;
-    for (int i = 0; i < width; i++) {
-        unsigned r = 0; int j;
-        for (j = -1; j < i;) {
-            hold = hold * 214013L + 2531011L;
-            r = (((unsigned)(hold >> 16) & 0x7fff & mask) << 1) + bop;
-            for (j = 0; j < i; j++) if (cols[j] == r) break;
-        }
-        cols[i] = r;
-    }
-    *lcg = hold;
-    return 1;
-}
+/* (sub-matrix columns as the embedder gets them: pcamv_stc_matrix_host, pcamv_stc_extract.h) */
+static int host_stc_matrix(int width, int height, unsigned *cols, long long *lcg) { return pcamv_stc_matrix_host(pcamv_stc_mats, width, height, cols, lcg); }
 /* syndrome-trellis extractor: H*y over GF(2) with stc_embed's sub-matrix schedule (embed.h:340-393).  lcg: state of the
  * column generator before this frame's embedding (in) / after it (out); NULL = only the tabulated widths */
 extern "C" int pcamv_gpu_stc_extract_lcg(const uint8_t *stego, int n, int m, int hgt, int64_t *lcg, uint8_t *message)

@@ -10,6 +10,8 @@
  *   k_encode          phase C, one wavefront per macroblock
  *   k_embed_prepare   cover / cost assembly + MVC adjustment + message (encoder.c:1561-1840)
  *   k_stc_forward/backward  syndrome-trellis Viterbi (embed.h:309-548), 1024 states = 1024 lanes
+ *   k_extract_prepare / k_extract_bits / k_payload_check   the receiving side: carriers of the final motion -> syndrome ->
+ *                     packed bytes appended to the context's received stream, and its comparison with the attached payload
  */
 #ifndef PCAMV_KERNELS_HIP_H
 #define PCAMV_KERNELS_HIP_H
@@ -17,6 +19,7 @@
 #include "pcamv_prims_gpu.h"
 #include "pcamv_mbkernels.h"
 #include "stc_mats.h"
+#include "pcamv_stc_extract.h"
 
 /* The kernels every instance of the library shares (plane production, the second pass, the embedding stage, the common analysis
  * kernel, the probes) are compiled by ONE translation unit, pcamv_gpu.hip; the units of the --me tesa and RD instances take only the
@@ -982,7 +985,6 @@ static __global__ void __launch_bounds__(64) k_rd_probe(const FrameDev *__restri
 #endif
 
 /* ------------------------------------------------------------------ embedding stage */
-#define STC_MAXW 256
 struct EmbedDev {
     const pcamv_mb_t *mbs; int n_mb;
     uint8_t *cover, *stego, *message; float *rho; int8_t *flip;
@@ -994,12 +996,38 @@ struct EmbedDev {
     long long *lcg;           /* STC column LCG state (embed.h:134) */
     float emrate;
     const uint8_t *user_message; int user_message_len;
+    /* payload attached to the context (pcamv_gpu_set_payload*): packed bytes, most significant bit first; NULL = the rand() stream.
+     * A frame without a caller's message takes the bits pstate[PST_TX] .. + m and moves that cursor by m on the device. */
+    const uint8_t *payload; long long payload_bits;
+    long long *pstate;        /* [PST_*] cursors of the payload path (below) */
     int cap;                  /* capacity of the per-carrier arrays */
     int *car_base;            /* [n_mb] index of each macroblock's first carrier (pass 2 finds its flips there) */
     uint8_t *mbflip;          /* [n_mb] 1 = one of the macroblock's carriers is flipped (k_mb_flips, after the backward pass) */
     unsigned *colinfo;        /* per trellis column, what both Viterbi passes need of it in one word: the (shortened)
                                * matrix column as the forward pass uses it [9:0] and as the backward pass does [22:13], cover bit [10], "last column of its message bit" [11], that
                                * message bit [12] */
+};
+
+/* per-context device words of the payload path */
+enum { PST_TX = 0,            /* payload bits the sender has consumed */
+       PST_RX = 1,            /* bits appended to the received stream */
+       PST_OVERRUN = 2,       /* != 0: a frame did not fit the reserved received buffer (its tail was dropped, never written) */
+       PST_RX_LCG = 3,        /* the receiver's own STC column generator (embed.h:134), started like the sender's */
+       PST_WORDS = 4 };
+
+/* The receiving side of one frame (k_extract_prepare -> k_extract_bits), and the comparison of the received stream with the payload. */
+struct ExtractDev {
+    const pcamv_mb_t *mbs; int n_mb, cap;
+    const int8_t *flip;       /* flip map in carrier order: the final MV of carrier k is mv_stego where flip[k] == 1 (what
+                               * pcamv_gpu_final_mvs applies); NULL: the records hold final MVs already (parsed from a stream) */
+    float emrate;
+    uint8_t *stego;           /* [cap] LSB(mvx + mvy) of every carrier's final MV */
+    uint8_t *bits;            /* [cap] the frame's message bits, one per byte, or NULL */
+    int *hdr;                 /* [0]=n [1]=m [2]=sub-matrices built [6..7]=(long long) bit offset of the frame in the received stream */
+    unsigned *cols;           /* [2][STC_MAXW] */
+    long long *pstate;
+    unsigned *rx; long long rx_cap_bits;          /* received stream: packed, zeroed when reserved / reset; NULL = nothing is appended */
+    const uint8_t *payload; long long payload_bits;
 };
 
 __device__ __forceinline__ int dev_is01(int d) { return d == 0 || d == 1; }
@@ -1036,18 +1064,20 @@ __device__ int dev_stc_matrix(int width, int height, unsigned *cols, long long *
     return 1;
 }
 
-#ifdef PCAMV_MAIN_TU
-static __global__ void __launch_bounds__(1024) k_embed_prepare(const EmbedDev *__restrict__ Es)
+/* Carriers of a frame's records in embedding order (encoder.c:1566-1647), for a workgroup of 1024: every thread takes a run of
+ * macroblocks [*lo, *hi), and gets the index of its first carrier in *base; returns the frame's carrier count.  Sender and
+ * receiver share the walk; they differ in what tells a carrying macroblock: the record's own flag (sender), or -- all a decoder
+ * knows -- that the macroblock is coded (DECODER: i_type != P_SKIP; the same set, encoder.c:1566). */
+template <bool DECODER>
+__device__ __forceinline__ int dev_carrier_scan(const pcamv_mb_t *__restrict__ mbs, int n_mb, int *s_cnt, int *lo_out, int *hi_out, int *base_out)
 {
-    const EmbedDev E = Es[blockIdx.x];
-    __shared__ int s_cnt[1024];
     const int t = threadIdx.x;
-    const int chunk = (E.n_mb + 1023) / 1024;
-    const int lo = t * chunk, hi = min(E.n_mb, lo + chunk);
+    const int chunk = (n_mb + 1023) / 1024;
+    const int lo = t * chunk, hi = min(n_mb, lo + chunk);
     int cnt = 0, slots[16];
     for (int xy = lo; xy < hi; xy++) {
-        const pcamv_mb_t *mb = &E.mbs[xy];
-        cnt += carrier_slots(mb->i_type, mb->i_partition, mb->i_sub_partition, mb->used, slots);
+        const pcamv_mb_t *mb = &mbs[xy];
+        cnt += carrier_slots(mb->i_type, mb->i_partition, mb->i_sub_partition, DECODER ? mb->i_type != PCAMV_P_SKIP : mb->used, slots);
     }
     s_cnt[t] = cnt;
     __syncthreads();
@@ -1057,8 +1087,18 @@ static __global__ void __launch_bounds__(1024) k_embed_prepare(const EmbedDev *_
         s_cnt[t] += v;
         __syncthreads();
     }
-    int base = s_cnt[t] - cnt;
-    const int n = s_cnt[1023];
+    *lo_out = lo; *hi_out = hi; *base_out = s_cnt[t] - cnt;
+    return s_cnt[1023];
+}
+
+#ifdef PCAMV_MAIN_TU
+static __global__ void __launch_bounds__(1024) k_embed_prepare(const EmbedDev *__restrict__ Es)
+{
+    const EmbedDev E = Es[blockIdx.x];
+    __shared__ int s_cnt[1024];
+    const int t = threadIdx.x;
+    int lo, hi, base, slots[16];
+    const int n = dev_carrier_scan<false>(E.mbs, E.n_mb, s_cnt, &lo, &hi, &base);
     const float mvc_c1 = 2, mvc_c2 = 0.7f;
     for (int xy = lo; xy < hi; xy++) {
         const pcamv_mb_t *mb = &E.mbs[xy];
@@ -1113,8 +1153,7 @@ static __global__ void __launch_bounds__(1024) k_embed_prepare(const EmbedDev *_
     __shared__ unsigned s_rnd[64];
     __shared__ unsigned s_cols[2 * STC_MAXW];
     __shared__ int s_ok;
-    int m = E.emrate > 1.0f ? (int)E.emrate : (int)__fmul_rn(E.emrate, (float)n);
-    if (m < 0) m = 0;
+    const int m = pcamv_stc_frame_bits(E.emrate, n);
     const bool sched = m > 0 && m <= n;
     const double invalpha = sched ? (double)n / m : 0.0;
     const int shorter = (int)floor(invalpha), longer = (int)ceil(invalpha);
@@ -1136,7 +1175,7 @@ static __global__ void __launch_bounds__(1024) k_embed_prepare(const EmbedDev *_
     if (t < 64) {
         if (E.user_message) {
             for (int i = t; i < imin(m, E.cap); i += 64) E.message[i] = i < E.user_message_len ? E.user_message[i] : 0;     /* m > n (> cap) fails in stc_embed like the reference's; never write past the arrays */
-        } else {
+        } else if (!E.payload) {
             /* glibc TYPE_3 rand(): x[k] = x[k-31] + x[k-3], output x[k] >> 1.  Three outputs are independent of each
              * other, so lanes 0..2 make three per round on a 64-entry ring in LDS.  The stored state is a 31-entry
              * ring with the oldest value at st[31] (f): x[-31 + j] = st[(f + j) % 31]. */
@@ -1156,7 +1195,15 @@ static __global__ void __launch_bounds__(1024) k_embed_prepare(const EmbedDev *_
             if (t == 0) { E.rnd[31] = (f + m) % 31; E.rnd[32] = (E.rnd[32] + m) % 31; }
         }
     }
+    /* an attached payload: bit cursor + i of it to message bit i, zeros past its end; one bit per lane, the whole workgroup (nothing
+     * serial to wait for, and the rand() state does not move).  The cursor advances by m whatever becomes of the frame -- the
+     * rule of the rand() stream -- so a frame whose embedding fails costs its own m bits and nothing after them. */
+    const bool from_payload = !E.user_message && E.payload;
+    const long long cursor = from_payload ? E.pstate[PST_TX] : 0;
+    if (from_payload)
+        for (int i = t; i < imin(m, E.cap); i += 1024) E.message[i] = cursor + i < E.payload_bits ? (uint8_t)pcamv_packed_bit(E.payload, cursor + i) : 0;
     __syncthreads();
+    if (from_payload && t == 0) E.pstate[PST_TX] = cursor + m;          /* (every thread has read the cursor: the barrier above) */
     if (!s_ok) return;
     for (int i = t; i < m; i += 1024) {
         const int start = STC_BEFORE(i);
@@ -1320,6 +1367,124 @@ static __global__ void __launch_bounds__(256) k_mb_flips(const EmbedDev *__restr
     int any = 0;
     for (int i = a; i < b && i < n; i++) any |= E.flip[i] == 1;
     E.mbflip[xy] = (uint8_t)any;
+}
+/* ------------------------------------------------------------------ receiving side
+ * (the reference has no extractor; this is the library's own, pcamv_gpu_stc_extract_lcg, on the device)
+ * k_extract_prepare, one workgroup per frame: the carriers of the frame as a decoder finds them, the LSB of each one's final MV,
+ * the frame's n and m, the two sub-matrices from the receiver's own column generator (shorter then longer, as the host extractor
+ * calls them), and the frame's place in the received stream: the write cursor moves by m whatever the frame turns out to be, so
+ * that the offsets of sender and receiver stay aligned (m > n, or no matrix for the width: m zero bits -- the stream is zeroed
+ * when reserved, so nothing is written for them). */
+static __global__ void __launch_bounds__(1024) k_extract_prepare(const ExtractDev *__restrict__ Xs)
+{
+    const ExtractDev X = Xs[blockIdx.x];
+    __shared__ int s_cnt[1024];
+    __shared__ unsigned s_cols[2 * STC_MAXW];
+    const int t = threadIdx.x;
+    int lo, hi, base, slots[16];
+    const int n = dev_carrier_scan<true>(X.mbs, X.n_mb, s_cnt, &lo, &hi, &base);
+    for (int xy = lo; xy < hi; xy++) {
+        const pcamv_mb_t *mb = &X.mbs[xy];
+        const int k = carrier_slots(mb->i_type, mb->i_partition, mb->i_sub_partition, mb->i_type != PCAMV_P_SKIP, slots);
+        for (int i = 0; i < k && base + i < X.cap; i++) {
+            const int16_t *mv = X.flip && X.flip[base + i] == 1 ? mb->mv_stego[slots[i]] : mb->mv[slots[i]];
+            X.stego[base + i] = (uint8_t)((mv[0] + mv[1]) & 1);
+        }
+        base += k;
+    }
+    if (t == 64) {
+        const int m = pcamv_stc_frame_bits(X.emrate, n);
+        const bool sched = m > 0 && m <= n;
+        const double invalpha = sched ? (double)n / m : 0.0;
+        const int shorter = (int)floor(invalpha), longer = (int)ceil(invalpha);
+        const int ok = sched && dev_stc_matrix(shorter, PCAMV_STC_HEIGHT, s_cols, X.pstate + PST_RX_LCG) &&
+                       dev_stc_matrix(longer, PCAMV_STC_HEIGHT, s_cols + STC_MAXW, X.pstate + PST_RX_LCG);
+        if (ok) {
+            for (int k = 0; k < shorter; k++) X.cols[k] = s_cols[k];
+            for (int k = 0; k < longer; k++) X.cols[STC_MAXW + k] = s_cols[STC_MAXW + k];
+        }
+        X.hdr[0] = n; X.hdr[1] = m; X.hdr[2] = ok;
+        const long long at = X.pstate[PST_RX];
+        *(long long *)(X.hdr + 6) = at;
+        if (X.rx) {
+            X.pstate[PST_RX] = at + m;
+            if (at + m > X.rx_cap_bits) X.pstate[PST_OVERRUN] = 1;
+        }
+    }
+}
+
+/* k_extract_bits: one thread per message bit (pcamv_stc_extract_bit, shared with the host), the sub-matrices in LDS, the stego
+ * columns a workgroup's 256 bits reach staged through LDS when they fit (265 blocks of up to EXTRACT_WIN / 265 = 30 columns; wider
+ * sub-matrices mean few message bits, those read global memory).  Threads are laid over the received stream from a 64-bit
+ * boundary below the frame's first bit, so a wave's ballot is eight whole bytes of the stream: reversed to most-significant-bit
+ * first and OR-ed in as two words (a frame's first and last byte may be shared with its neighbours'; the stream is zeroed when
+ * reserved).  Bits at or beyond the reserved capacity are dropped here, never written. */
+#define EXTRACT_WIN 8192
+static __global__ void __launch_bounds__(256) k_extract_bits(const ExtractDev *__restrict__ Xs)
+{
+    const ExtractDev X = Xs[blockIdx.y];
+    __shared__ unsigned s_cols[2 * STC_MAXW];
+    __shared__ uint8_t s_win[EXTRACT_WIN];
+    const int t = threadIdx.x, lane = t & 63;
+    const int n = X.hdr[0], ok = X.hdr[2];
+    const int m = imin(X.hdr[1], X.cap);                /* (ok: m <= n <= cap; else only the zeros of `bits` are left to write) */
+    if (!ok) {
+        if (X.bits) for (int j = blockIdx.x * 256 + t; j < m; j += gridDim.x * 256) X.bits[j] = 0;
+        return;
+    }
+    const long long at = *(const long long *)(X.hdr + 6);
+    const int lead = (int)(at & 63);                    /* positions between the 64-bit boundary and the frame's first bit */
+    const long long pos0 = at - lead;
+    const double invalpha = (double)n / m;
+    const int shorter = (int)floor(invalpha), longer = (int)ceil(invalpha);
+    for (int k = t; k < shorter; k += 256) s_cols[k] = X.cols[k];
+    for (int k = t; k < longer; k += 256) s_cols[STC_MAXW + k] = X.cols[STC_MAXW + k];
+    for (int g0 = blockIdx.x * 256; g0 < lead + m; g0 += gridDim.x * 256) {        /* (workgroup-uniform: barriers inside) */
+        const int j = g0 + t - lead;
+        int wlo, whi;
+        pcamv_stc_window(imax(g0 - lead, 0), g0 - lead + 256, n, m, invalpha, PCAMV_STC_HEIGHT, &wlo, &whi);
+        const bool staged = whi - wlo <= EXTRACT_WIN;
+        __syncthreads();                                /* s_cols written / the last round's window read */
+        if (staged) {
+            for (int k = t; k < whi - wlo; k += 256) s_win[k] = X.stego[wlo + k];
+            __syncthreads();
+        }
+        const unsigned bit = j >= 0 && j < m ? pcamv_stc_extract_bit(staged ? s_win : X.stego, staged ? wlo : 0, n, m, invalpha, shorter, longer,
+                                                                      s_cols, s_cols + STC_MAXW, PCAMV_STC_HEIGHT, j) : 0u;
+        if (X.bits && j >= 0 && j < m) X.bits[j] = (uint8_t)bit;
+        const long long pos = pos0 + g0 + t;
+        const unsigned long long bal = __ballot(bit && X.rx && pos < X.rx_cap_bits);
+        if (lane < 2) {
+            const unsigned w = __builtin_bswap32(__brev((unsigned)(bal >> (32 * lane))));          /* bit-reversed inside every byte */
+            const long long word = ((pos - lane) >> 5) + lane;
+            if (w && word < ((X.rx_cap_bits + 31) >> 5)) atomicOr(&X.rx[word], w);
+        }
+    }
+}
+
+/* bits in which a context's received stream differs from its attached payload (the BER numerator), over the bits received so far;
+ * payload bits past its end count as zeros.  One workgroup per context. */
+static __global__ void __launch_bounds__(256) k_payload_check(const ExtractDev *__restrict__ Xs, long long *__restrict__ out)
+{
+    const ExtractDev X = Xs[blockIdx.x];
+    __shared__ int s_sum[4];
+    const int t = threadIdx.x;
+    long long got = X.rx ? X.pstate[PST_RX] : 0;
+    if (got > X.rx_cap_bits) got = X.rx_cap_bits;
+    const uint8_t *rx = (const uint8_t *)X.rx;
+    const long long nbytes = (got + 7) >> 3, pbytes = X.payload ? (X.payload_bits + 7) >> 3 : 0;
+    int diff = 0;
+    for (long long b = t; b < nbytes; b += 256) {
+        unsigned p = b < pbytes ? X.payload[b] : 0u;
+        if (b == pbytes - 1 && (X.payload_bits & 7)) p &= 0xff00u >> (X.payload_bits & 7);         /* what the caller's last byte holds beyond the payload */
+        unsigned d = rx[b] ^ p;
+        if (b == nbytes - 1 && (got & 7)) d &= 0xff00u >> (got & 7);
+        diff += __popc(d & 0xffu);
+    }
+    diff = wave_sum_all(diff);
+    if ((t & 63) == 0) s_sum[t >> 6] = diff;
+    __syncthreads();
+    if (t == 0) out[blockIdx.x] = (long long)s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
 }
 #endif
 #endif

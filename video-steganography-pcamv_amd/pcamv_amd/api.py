@@ -246,6 +246,35 @@ def stc_extract(stego, m, height=10, lcg=None):
     return msg
 
 
+FEATURE_PAYLOAD = 0x1
+
+
+def features():
+    """pcamv_gpu_features: mask of FEATURE_* the loaded library has"""
+    lib = load_library()
+    lib.pcamv_gpu_features.restype = C.c_uint
+    return lib.pcamv_gpu_features()
+
+
+def pack_bits(bits):
+    """bits (0 / 1, one per element) -> (packed bytes, 8 per byte, most significant bit first, the last byte zero-filled; number of bits):
+    the layout of payloads and of the received stream"""
+    bits = np.ascontiguousarray(bits, np.uint8) & 1
+    return np.packbits(bits, bitorder="big"), len(bits)
+
+
+def unpack_bits(packed, n_bits):
+    """the first n_bits of a packed buffer, one bit per element"""
+    packed = np.ascontiguousarray(packed, np.uint8)
+    if n_bits > 8 * len(packed):
+        raise PcamvError(f"{n_bits} bits asked of {len(packed)} bytes")
+    return np.unpackbits(packed, bitorder="big")[:n_bits]
+
+
+def _is_device_tensor(x):
+    return hasattr(x, "data_ptr") and hasattr(x, "is_cuda")
+
+
 class Encoder:
     """One analysis context = one x264_t's worth of P-frame analysis state on one GPU."""
 
@@ -331,6 +360,71 @@ class Encoder:
         self._chk(self.lib.pcamv_gpu_embed_pframe(self.ctx, C.c_float(emrate), _p(message),
                                                   0 if message is None else len(message), C.byref(e)), "embed_pframe")
         return self._embed_out(arr, e)
+
+    # payload path: the caller's bits through embed_pframe(None) / step_device / Batch.step, and back out on the device
+    def set_payload(self, payload, n_bits=None):
+        """attach a payload: packed bytes (pack_bits) as a numpy array / bytes (copied), or a torch uint8 device tensor (borrowed: kept
+        referenced here while attached); n_bits defaults to all of it.  None detaches: the rand() stream again, from where it stood"""
+        self.lib.pcamv_gpu_set_payload.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+        self.lib.pcamv_gpu_set_payload_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+        self._payload_keep = None
+        if payload is None:
+            return self._chk(self.lib.pcamv_gpu_set_payload(self.ctx, None, 0), "set_payload")
+        if _is_device_tensor(payload):
+            if not payload.is_cuda or payload.element_size() != 1 or not payload.is_contiguous():
+                raise PcamvError("a borrowed payload is a contiguous uint8 tensor on the device")
+            n_bits = 8 * payload.numel() if n_bits is None else n_bits
+            if n_bits > 8 * payload.numel():
+                raise PcamvError("n_bits beyond the tensor")
+            self._payload_keep = payload
+            return self._chk(self.lib.pcamv_gpu_set_payload_device(self.ctx, C.c_void_p(payload.data_ptr()), n_bits), "set_payload_device")
+        data = np.frombuffer(payload, np.uint8) if isinstance(payload, (bytes, bytearray)) else np.ascontiguousarray(payload, np.uint8)
+        n_bits = 8 * len(data) if n_bits is None else n_bits
+        if n_bits > 8 * len(data):
+            raise PcamvError("n_bits beyond the buffer")
+        self._chk(self.lib.pcamv_gpu_set_payload(self.ctx, _p(data), n_bits), "set_payload")
+
+    def payload_tell(self):
+        """(payload bits consumed so far, bits of the attached payload); synchronises"""
+        used, total = C.c_int64(), C.c_int64()
+        self._chk(self.lib.pcamv_gpu_payload_tell(self.ctx, C.byref(used), C.byref(total)), "payload_tell")
+        return used.value, total.value
+
+    def rx_reserve(self, n_bits):
+        """room for n_bits of received stream (0 releases it); the stream starts empty"""
+        self.lib.pcamv_gpu_rx_reserve.argtypes = [C.c_void_p, C.c_int64]
+        self._chk(self.lib.pcamv_gpu_rx_reserve(self.ctx, n_bits), "rx_reserve")
+
+    def rx_reset(self):
+        self._chk(self.lib.pcamv_gpu_rx_reset(self.ctx), "rx_reset")
+
+    def rx_tell(self):
+        """(bits received so far, bits reserved); synchronises; raises once after a frame ran past the reservation"""
+        got, cap = C.c_int64(), C.c_int64()
+        self._chk(self.lib.pcamv_gpu_rx_tell(self.ctx, C.byref(got), C.byref(cap)), "rx_tell")
+        return got.value, cap.value
+
+    def received(self, n_bits=None, packed=False):
+        """the received stream so far (or its first n_bits): one bit per element, or the packed bytes"""
+        self.lib.pcamv_gpu_rx_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+        if n_bits is None:
+            got, cap = self.rx_tell()
+            n_bits = min(got, cap)
+        out = np.zeros((n_bits + 7) // 8, np.uint8)
+        self._chk(self.lib.pcamv_gpu_rx_fetch(self.ctx, _p(out), n_bits), "rx_fetch")
+        return out if packed else unpack_bits(out, n_bits)
+
+    def extract_pframe(self, mbs, emrate):
+        """message bits of one frame out of records that hold its FINAL motion (parse_pslice_*), extracted on the device:
+        dict(bits, n, m); appended to the received stream too when one is reserved"""
+        mbs = np.ascontiguousarray(mbs, MB_DTYPE)
+        if len(mbs) != self.n_mb:
+            raise PcamvError(f"{len(mbs)} records for a picture of {self.n_mb} macroblocks")
+        bits = np.zeros(16 * self.n_mb, np.uint8)
+        n, m = C.c_int32(), C.c_int32()
+        self.lib.pcamv_gpu_extract_pframe.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        self._chk(self.lib.pcamv_gpu_extract_pframe(self.ctx, _p(mbs), emrate, _p(bits), C.byref(n), C.byref(m)), "extract_pframe")
+        return dict(bits=bits[:min(m.value, len(bits))].copy(), n=n.value, m=m.value)
 
     def final_mvs(self, mbs):
         out = mbs.copy()
@@ -457,6 +551,20 @@ class Batch:
                                                          C.c_size_t(flip_stride), C.c_void_p(stream or None))
         if rc:
             raise PcamvError(f"batch_copy_results_async failed ({rc}): {self.lib.pcamv_gpu_batch_last_error(self.b).decode()}")
+
+    def extract_step(self, emrate, stream=0):
+        """every context's last step through the receiver, on the device, without a host sync (each needs rx_reserve)"""
+        rc = self.lib.pcamv_gpu_batch_extract_step(self.b, C.c_float(emrate), C.c_void_p(stream or None))
+        if rc:
+            raise PcamvError(f"batch_extract_step failed ({rc}): {self.lib.pcamv_gpu_batch_last_error(self.b).decode()}")
+
+    def payload_check(self):
+        """per context: bits in which its received stream differs from its attached payload (zeros past the payload's end)"""
+        out = np.zeros(len(self.encs), np.int64)
+        rc = self.lib.pcamv_gpu_batch_payload_check(self.b, _p(out))
+        if rc:
+            raise PcamvError(f"batch_payload_check failed ({rc}): {self.lib.pcamv_gpu_batch_last_error(self.b).decode()}")
+        return out
 
     def dominant_kernel(self):
         self.lib.pcamv_gpu_batch_dominant_kernel.restype = C.c_char_p
