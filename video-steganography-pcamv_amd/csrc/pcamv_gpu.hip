@@ -13,18 +13,36 @@
 #include "pcamv_kernels.hip.h"
 #include "pcamv_host_tables.h"
 #include "pcamv_mvsyntax.h"
+#include "pcamv_rd_select.h"
 
 #define PCAMV_ABI_VERSION 3
-/* chains in a batch up to which the speculative raster schedule is used, and up to which its 1 / 2 waves-per-SIMD builds (measured:
- * pcamv_gpu_batch_create) */
-#define PCAMV_SPEC_MAX_CHAINS 3584
-#define PCAMV_SPEC1_MAX_CHAINS 320
-#define PCAMV_SPEC2_MAX_CHAINS 704
 #define NEV 32
 #define NRING 8
 #define NKEV 16                /* launches a timer of the smaller kernels remembers between two kernel_time calls */
 enum { KT_EMBED_PREPARE, KT_EXTRACT_PREPARE, KT_EXTRACT_BITS, KT_PAYLOAD_CHECK, KT_N };
 #define PCAMV_FEATURES PCAMV_FEATURE_PAYLOAD
+
+/* The builds of the RD instance of the analysis kernel (pcamv_rd.hip RD_NAME: one translation unit each), a row per entry of
+ * PCAMV_RD_BUILDS in the order of rd_select's result; the phase timers are per translation unit (PCAMV_PROF) */
+struct RdBuild {
+    int spec;                   /* waves per SIMD of the speculative raster chain, 0: plain chain */
+    void (*launch)(unsigned waves, hipStream_t st, const FrameDev *dF, const FlowDev &fl);
+    int (*waves_per_cu)(void);
+    int (*prof_fetch)(unsigned long long *out, int reset);      /* NULL without PCAMV_PROF */
+};
+#ifdef PCAMV_PROF
+#define RD_PROF_FN(sfx) pcamv_rd_prof_fetch##sfx
+#else
+#define RD_PROF_FN(sfx) NULL
+#endif
+#define RD_DECL(id, sfx, spec) void pcamv_launch_flow_rd##sfx(unsigned, hipStream_t, const FrameDev *, const FlowDev &); \
+    int pcamv_flow_rd_waves_per_cu##sfx(void); int pcamv_rd_prof_fetch##sfx(unsigned long long *, int);
+#define RD_ROW(id, sfx, spec) {spec, pcamv_launch_flow_rd##sfx, pcamv_flow_rd_waves_per_cu##sfx, RD_PROF_FN(sfx)},
+PCAMV_RD_BUILDS(RD_DECL)
+static const RdBuild rd_builds[RD_N_BUILDS] = {PCAMV_RD_BUILDS(RD_ROW)};
+
+/* one ring of NRING descriptor slots: a slot is written again only after the work that read it last (its event) is done */
+struct DescRing { int head, used[NRING]; hipEvent_t done[NRING]; };
 
 struct pcamv_ctx;
 /* A batch = the set of independent closed-GOP contexts whose frames advance together: every kernel
@@ -35,20 +53,20 @@ struct pcamv_batch {
     pcamv_ctx **ctx;
     FrameDev *h_F, *d_F;        /* NRING slots of n descriptors (pinned host / device) */
     EmbedDev *h_E, *d_E;
-    hipEvent_t slot_done[NRING];
-    int slot_used[NRING], head;
+    DescRing ring;
     hipEvent_t ev0[NEV], ev1[NEV];
     int ev_n, ev_head;
     double t_search_ms; int t_search_launches;
     /* dataflow schedule (k_analyse_flow): queue + dependency counters, one persistent launch per step */
-    int sched_flow, flow_waves, flow2_waves, closed_loop, rd_lo, rd_spec, stc_ns;
+    int sched_flow, flow_waves, flow2_waves, closed_loop, stc_ns;
     int b_mbrd, b_tesa;         /* instance of the analysis kernel the batch's contexts need (fixed at creation) */
+    const RdBuild *rd;          /* ... and which build of the RD instance (b_mbrd) */
     unsigned *d_flow;
     FlowDev fl, fl2;          /* queue descriptors of the analysis and of the second pass */
     /* payload path: descriptors of the receiving side (their own ring, made by the first extraction), the per-context counts of
      * payload_check, and the timers of the kernels besides the dominant one */
     ExtractDev *h_X, *d_X; long long *d_chk;
-    hipEvent_t xslot_done[NRING]; int xslot_used[NRING], xhead;
+    DescRing xring;
     struct KTimer { hipEvent_t e0[NKEV], e1[NKEV]; int made, n, head, launches; double ms; } kt[KT_N];
     char err[256];
 };
@@ -102,29 +120,15 @@ static int bfail(pcamv_batch *b, int code, const char *fmt, ...)
 extern "C" int pcamv_gpu_abi_version(void) { return PCAMV_ABI_VERSION; }
 extern "C" unsigned pcamv_gpu_features(void) { return PCAMV_FEATURES; }
 #ifdef PCAMV_PROF
-int pcamv_rd_prof_fetch(unsigned long long *out, int reset);
-int pcamv_rd_prof_fetch_lo(unsigned long long *out, int reset);
-int pcamv_rd_prof_fetch_spec(unsigned long long *out, int reset);
-int pcamv_rd_prof_fetch_spec2(unsigned long long *out, int reset);
-int pcamv_rd_prof_fetch_tesa(unsigned long long *out, int reset);
-int pcamv_rd_prof_fetch_spec4(unsigned long long *out, int reset);
 extern "C" int pcamv_gpu_prof_fetch(unsigned long long *out, int reset)
 {
     unsigned long long rd[PCAMV_PROF_N];
     if (hipMemcpyFromSymbol(out, HIP_SYMBOL(pcamv_prof), sizeof(unsigned long long) * PCAMV_PROF_N) != hipSuccess) return -1;
     if (reset) { unsigned long long z[PCAMV_PROF_N] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(pcamv_prof), z, sizeof(z)) != hipSuccess) return -1; }
-    if (pcamv_rd_prof_fetch(rd, reset)) return -1;
-    for (int i = 0; i < PCAMV_PROF_N; i++) out[i] += rd[i];
-    if (pcamv_rd_prof_fetch_lo(rd, reset)) return -1;
-    for (int i = 0; i < PCAMV_PROF_N; i++) out[i] += rd[i];
-    if (pcamv_rd_prof_fetch_spec(rd, reset)) return -1;
-    for (int i = 0; i < PCAMV_PROF_N; i++) out[i] += rd[i];
-    if (pcamv_rd_prof_fetch_spec2(rd, reset)) return -1;
-    for (int i = 0; i < PCAMV_PROF_N; i++) out[i] += rd[i];
-    if (pcamv_rd_prof_fetch_spec4(rd, reset)) return -1;
-    for (int i = 0; i < PCAMV_PROF_N; i++) out[i] += rd[i];
-    if (pcamv_rd_prof_fetch_tesa(rd, reset)) return -1;
-    for (int i = 0; i < PCAMV_PROF_N; i++) out[i] += rd[i];
+    for (const RdBuild &r : rd_builds) {
+        if (r.prof_fetch(rd, reset)) return -1;
+        for (int i = 0; i < PCAMV_PROF_N; i++) out[i] += rd[i];
+    }
     return 0;
 }
 #endif
@@ -171,9 +175,9 @@ extern "C" void pcamv_gpu_batch_destroy(pcamv_batch_t *b)
     if (b->d_flow) hipFree(b->d_flow);
     if (b->h_X) hipHostFree(b->h_X);
     hipFree(b->d_X); hipFree(b->d_chk);
-    for (int i = 0; i < NRING; i++) if (b->xslot_done[i]) hipEventDestroy(b->xslot_done[i]);
+    for (int i = 0; i < NRING; i++) if (b->xring.done[i]) hipEventDestroy(b->xring.done[i]);
     for (int k = 0; k < KT_N; k++) for (int i = 0; i < NKEV; i++) { if (b->kt[k].e0[i]) hipEventDestroy(b->kt[k].e0[i]); if (b->kt[k].e1[i]) hipEventDestroy(b->kt[k].e1[i]); }
-    for (int i = 0; i < NRING; i++) if (b->slot_done[i]) hipEventDestroy(b->slot_done[i]);
+    for (int i = 0; i < NRING; i++) if (b->ring.done[i]) hipEventDestroy(b->ring.done[i]);
     for (int i = 0; i < NEV; i++) { if (b->ev0[i]) hipEventDestroy(b->ev0[i]); if (b->ev1[i]) hipEventDestroy(b->ev1[i]); }
     free(b->ctx);
     delete b;
@@ -203,7 +207,7 @@ extern "C" int pcamv_gpu_batch_create(pcamv_ctx_t *const *ctxs, int n, pcamv_bat
     if (e == hipSuccess) e = hipHostMalloc((void **)&b->h_E, sizeof(EmbedDev) * n * NRING, hipHostMallocDefault);
     if (e == hipSuccess) e = dalloc(&b->d_F, (size_t)n * NRING);
     if (e == hipSuccess) e = dalloc(&b->d_E, (size_t)n * NRING);
-    for (int i = 0; i < NRING && e == hipSuccess; i++) e = hipEventCreateWithFlags(&b->slot_done[i], hipEventDisableTiming);
+    for (int i = 0; i < NRING && e == hipSuccess; i++) e = hipEventCreateWithFlags(&b->ring.done[i], hipEventDisableTiming);
     for (int i = 0; i < NEV && e == hipSuccess; i++) { e = hipEventCreate(&b->ev0[i]); if (e == hipSuccess) e = hipEventCreate(&b->ev1[i]); }
     /* schedule: PCAMV_SCHED=diag keeps one launch per anti-diagonal (+ separate RCA / encode launches);
      * the default is the dataflow kernel.  Both are the same per-macroblock code. */
@@ -231,30 +235,11 @@ extern "C" int pcamv_gpu_batch_create(pcamv_ctx_t *const *ctxs, int n, pcamv_bat
         if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_analyse_flow, 64, 0);
         if (e == hipSuccess) e = hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, b->device);
         if (e == hipSuccess && F.b_mbrd) {
-            /* which build of the RD instance (pcamv_rd.hip): one wave per SIMD while the chains fit that anyway */
-            const char *inst = getenv("PCAMV_RD_INSTANCE");
-            /* measured (1080p umh subme 7, MB/s lo / hi): 256 chains 2.31 / 2.21 M, 512: 4.43 / 4.19 M, 1024: 6.84 / 7.77 M -- with one
-             * wave per SIMD the lo build has no free wave left at 1024 chains to take the RCA steps off the chains */
-            /* Five builds (pcamv_rd*.hip).  With CABAC (raster chains) the ones that hand a chain on speculatively after the 16x16
-             * search -- ~3 waves work on a chain then --, at 1, 2 or 4 waves per SIMD by the number of chains; measured (1080p umh
-             * subme 7, M MB/s, plain / spec1 / spec2 / spec4): 256 chains 2.51 / 4.60 / - / -, 512: 4.81 / 6.77 / 8.17 / 7.90,
-             * 1024: 8.40 / 7.31 / 11.9 / 14.0, 2048: 14.3 / 7.30 / 12.5 / 18.3, 3072: 18.4 / - / - / 19.0, 4096: 19.5 / - / - / 19.3.
-             * Without a chain (CAVLC: wavefront order) and for thousands of chains the plain builds: "lo" (1 wave per SIMD) while the
-             * chains fit that anyway, else "hi" (4).  PCAMV_RD_INSTANCE=lo|hi|spec|spec2|spec4 and PCAMV_FLOW_SPEC=0|1 override.
-             * The speculative chain needs pictures >= FLOW_SPEC_MIN_MBW macroblocks wide. */
-            const char *sp = getenv("PCAMV_FLOW_SPEC");
-            const int can_spec = b->fl.raster && F.mb_w >= FLOW_SPEC_MIN_MBW;
-            int want_spec = inst ? !strncmp(inst, "spec", 4) : (sp ? atoi(sp) != 0 : n <= PCAMV_SPEC_MAX_CHAINS);
-            b->rd_spec = can_spec && want_spec ? (inst && !strcmp(inst, "spec") ? 1 : inst && !strcmp(inst, "spec2") ? 2 : inst && !strcmp(inst, "spec4") ? 4 :
-                                                   n <= PCAMV_SPEC1_MAX_CHAINS ? 1 : n <= PCAMV_SPEC2_MAX_CHAINS ? 2 : 4) : 0;
-            b->rd_lo = !b->rd_spec && (inst && strncmp(inst, "spec", 4) ? !strcmp(inst, "lo") : (b->fl.raster && n <= 2 * n_cu));
-            /* sub-8x8 partitions at this level (x264_rd_cost_part): compiled into the two one-wave-per-SIMD builds only */
-            if (ctxs[0]->p.inter & PCAMV_ANALYSE_PSUB8x8) { if (b->rd_spec) b->rd_spec = 1; else b->rd_lo = 1; }
-            /* --me tesa: its own build (pcamv_rd_tesa.hip), plain chain */
-            if (b->b_tesa) { b->rd_spec = 0; b->rd_lo = 0; }
-            b->fl.spec = b->rd_spec != 0;
-            per_cu = b->b_tesa ? pcamv_flow_rd_waves_per_cu_tesa() : b->rd_spec == 1 ? pcamv_flow_rd_waves_per_cu_spec() : b->rd_spec == 2 ? pcamv_flow_rd_waves_per_cu_spec2() :
-                     b->rd_spec == 4 ? pcamv_flow_rd_waves_per_cu_spec4() : b->rd_lo ? pcamv_flow_rd_waves_per_cu_lo() : pcamv_flow_rd_waves_per_cu();
+            /* which build of the RD instance (pcamv_rd_select.h: the rules and what was measured) */
+            b->rd = &rd_builds[rd_select(n, n_cu, b->fl.raster, F.mb_w, (ctxs[0]->p.inter & PCAMV_ANALYSE_PSUB8x8) != 0, b->b_tesa,
+                                         getenv("PCAMV_RD_INSTANCE"), getenv("PCAMV_FLOW_SPEC"))];
+            b->fl.spec = b->rd->spec != 0;
+            per_cu = b->rd->waves_per_cu();
             if (per_cu < 0) e = hipErrorUnknown;
         }
         const char *wv = getenv("PCAMV_FLOW_WAVES");
@@ -517,12 +502,27 @@ extern "C" int pcamv_gpu_set_fenc_device(pcamv_ctx_t *c, const void *y, const vo
 }
 
 /* ------------------------------------------------------------------ batched launches */
+/* the ring's next slot, once its descriptors are no longer in flight */
+static int ring_take(pcamv_batch *b, DescRing &r, int *slot_out)
+{
+    const int slot = r.head;
+    r.head = (r.head + 1) % NRING;
+    if (r.used[slot]) HIPCHKB(b, hipEventSynchronize(r.done[slot]));
+    *slot_out = slot;
+    return 0;
+}
+/* ... and what was queued on `st` so far is what reads them */
+static int ring_release(pcamv_batch *b, DescRing &r, int slot, hipStream_t st)
+{
+    HIPCHKB(b, hipEventRecord(r.done[slot], st));
+    r.used[slot] = 1;
+    return 0;
+}
 /* take the next descriptor slot, fill it from the contexts' current FrameDev/EmbedDev and queue its upload */
 static int batch_push_descs(pcamv_batch *b, hipStream_t st, const FrameDev **dF, const EmbedDev **dE, int *slot_out)
 {
-    int slot = b->head;
-    b->head = (b->head + 1) % NRING;
-    if (b->slot_used[slot]) HIPCHKB(b, hipEventSynchronize(b->slot_done[slot]));    /* descriptors of this slot no longer in flight */
+    int slot;
+    { const int rc = ring_take(b, b->ring, &slot); if (rc) return rc; }
     FrameDev *hF = b->h_F + (size_t)slot * b->n; EmbedDev *hE = b->h_E + (size_t)slot * b->n;
     for (int i = 0; i < b->n; i++) { hF[i] = b->ctx[i]->F; hE[i] = b->ctx[i]->E; }
     HIPCHKB(b, hipMemcpyAsync(b->d_F + (size_t)slot * b->n, hF, sizeof(FrameDev) * b->n, hipMemcpyHostToDevice, st));
@@ -530,11 +530,17 @@ static int batch_push_descs(pcamv_batch *b, hipStream_t st, const FrameDev **dF,
     *dF = b->d_F + (size_t)slot * b->n; *dE = b->d_E + (size_t)slot * b->n; *slot_out = slot;
     return 0;
 }
-static int batch_release_slot(pcamv_batch *b, int slot, hipStream_t st)
+
+/* one launch per anti-diagonal d = x + 2 y of the macroblock grid (left / top / top-right dependency): launch(macroblocks on it, d) */
+template <class Launch> static void diag_launch(int n_diag, const FrameDev &F, Launch launch)
 {
-    HIPCHKB(b, hipEventRecord(b->slot_done[slot], st));
-    b->slot_used[slot] = 1;
-    return 0;
+    for (int d = 0; d < n_diag; d++) {
+        int y_lo = d - (F.mb_w - 1); y_lo = y_lo > 0 ? (y_lo + 1) >> 1 : 0;
+        int y_hi = d / 2; if (y_hi > F.mb_h - 1) y_hi = F.mb_h - 1;
+        int cnt = y_hi - y_lo + 1;
+        if (cnt <= 0) continue;
+        launch(cnt, d);
+    }
 }
 
 /* hipEvents around a launch of one of the smaller kernels (pcamv_gpu_batch_kernel_time reports them under their names); the events
@@ -587,32 +593,18 @@ static int batch_launch(pcamv_batch *b, int what, hipStream_t st, int timed)
         hipLaunchKernelGGL(k_chroma_pad, gc, dim3(256), 0, st, dF);
     }
     if (what & 2) {
-        int ev = -1, tesa = 0;
-        for (int i = 0; i < b->n; i++) tesa |= b->ctx[i]->F.me_method == PCAMV_ME_TESA;       /* the kernel instance with --me tesa compiled in */
+        int ev = -1;
         if (timed && !b->sched_flow) { ev = b->ev_head; hipEventRecord(b->ev0[ev], st); }
         for (int i = 0; i < b->n; i++) b->ctx[i]->last = b;
         if (b->sched_flow) {
             hipLaunchKernelGGL(k_flow_init, dim3((b->fl.total + 255) / 256), dim3(256), 0, st, b->fl);
             if (timed) { ev = b->ev_head; hipEventRecord(b->ev0[ev], st); }
-            if (F.b_mbrd) {
-                if (b->b_tesa) pcamv_launch_flow_rd_tesa((unsigned)b->flow_waves, st, dF, b->fl);
-                else if (b->rd_spec == 1) pcamv_launch_flow_rd_spec((unsigned)b->flow_waves, st, dF, b->fl);
-                else if (b->rd_spec == 2) pcamv_launch_flow_rd_spec2((unsigned)b->flow_waves, st, dF, b->fl);
-                else if (b->rd_spec == 4) pcamv_launch_flow_rd_spec4((unsigned)b->flow_waves, st, dF, b->fl);
-                else if (b->rd_lo) pcamv_launch_flow_rd_lo((unsigned)b->flow_waves, st, dF, b->fl);
-                else pcamv_launch_flow_rd((unsigned)b->flow_waves, st, dF, b->fl);
-            }
-            else if (tesa) pcamv_launch_flow_tesa((unsigned)b->flow_waves, st, dF, b->fl);
+            if (b->b_mbrd) b->rd->launch((unsigned)b->flow_waves, st, dF, b->fl);
+            else if (b->b_tesa) pcamv_launch_flow_tesa((unsigned)b->flow_waves, st, dF, b->fl);
             else hipLaunchKernelGGL(k_analyse_flow, dim3(b->flow_waves), dim3(64), 0, st, dF, b->fl);
             if (timed) { hipEventRecord(b->ev1[ev], st); b->ev_head = (b->ev_head + 1) % NEV; if (b->ev_n < NEV) b->ev_n++; }
         } else {
-            for (int d = 0; d < b->n_diag; d++) {
-                int y_lo = d - (F.mb_w - 1); y_lo = y_lo > 0 ? (y_lo + 1) >> 1 : 0;
-                int y_hi = d / 2; if (y_hi > F.mb_h - 1) y_hi = F.mb_h - 1;
-                int cnt = y_hi - y_lo + 1;
-                if (cnt <= 0) continue;
-                hipLaunchKernelGGL(k_search_diag<0>, dim3(cnt, G), dim3(64), 0, st, dF, d);
-            }
+            diag_launch(b->n_diag, F, [&](int cnt, int d) { hipLaunchKernelGGL(k_search_diag<0>, dim3(cnt, G), dim3(64), 0, st, dF, d); });
             if (timed) { hipEventRecord(b->ev1[ev], st); b->ev_head = (b->ev_head + 1) % NEV; if (b->ev_n < NEV) b->ev_n++; }
             hipLaunchKernelGGL(k_rca, dim3(F.n_mb * b->slots_per_mb, G), dim3(64), 0, st, dF, b->slots_per_mb);
             hipLaunchKernelGGL(k_encode, dim3(F.n_mb, G), dim3(64), 0, st, dF);
@@ -635,18 +627,12 @@ static int batch_launch(pcamv_batch *b, int what, hipStream_t st, int timed)
             hipLaunchKernelGGL(k_flow_init, dim3((b->fl2.total + 255) / 256), dim3(256), 0, st, b->fl2);
             hipLaunchKernelGGL(k_pass2_deblock_flow, dim3(b->flow2_waves), dim3(64), 0, st, dF, b->fl2);
         } else {
-            for (int d = 0; d < b->n_diag; d++) {
-                int y_lo = d - (F.mb_w - 1); y_lo = y_lo > 0 ? (y_lo + 1) >> 1 : 0;
-                int y_hi = d / 2; if (y_hi > F.mb_h - 1) y_hi = F.mb_h - 1;
-                int cnt = y_hi - y_lo + 1;
-                if (cnt <= 0) continue;
-                hipLaunchKernelGGL(k_pass2_deblock_diag, dim3(cnt, G), dim3(64), 0, st, dF, d);
-            }
+            diag_launch(b->n_diag, F, [&](int cnt, int d) { hipLaunchKernelGGL(k_pass2_deblock_diag, dim3(cnt, G), dim3(64), 0, st, dF, d); });
         }
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return bfail(b, PCAMV_EHIP, "kernel launch: %s", hipGetErrorString(e));
-    return batch_release_slot(b, slot, st);
+    return ring_release(b, b->ring, slot, st);
 }
 /* after a synchronisation: did the dataflow kernel of the last step give up on a bounded spin? */
 static int flow_check(pcamv_batch *b)
@@ -816,21 +802,15 @@ extern "C" int pcamv_gpu_pass2_pframe(pcamv_ctx_t *c, const uint8_t *flips, int 
         if (rc) return fail(c, rc, "%s", b->err);
         const FrameDev &F = c->F;
         for (int pass = 0; pass < 2; pass++) {
-            for (int d = 0; d < b->n_diag; d++) {
-                int y_lo = d - (F.mb_w - 1); y_lo = y_lo > 0 ? (y_lo + 1) >> 1 : 0;
-                int y_hi = d / 2; if (y_hi > F.mb_h - 1) y_hi = F.mb_h - 1;
-                int cnt = y_hi - y_lo + 1;
-                if (cnt <= 0) continue;
-                if (pass == 0) hipLaunchKernelGGL(k_pass2_diag, dim3(cnt, 1), dim3(64), 0, c->stream, dF, d);
-                else hipLaunchKernelGGL(k_deblock_diag, dim3(cnt, 1), dim3(64), 0, c->stream, dF, d);
-            }
+            if (pass == 0) diag_launch(b->n_diag, F, [&](int cnt, int d) { hipLaunchKernelGGL(k_pass2_diag, dim3(cnt, 1), dim3(64), 0, c->stream, dF, d); });
+            else diag_launch(b->n_diag, F, [&](int cnt, int d) { hipLaunchKernelGGL(k_deblock_diag, dim3(cnt, 1), dim3(64), 0, c->stream, dF, d); });
             HIPCHK(c, hipStreamSynchronize(c->stream));
             uint8_t *const *dst = pass == 0 ? recon : deblocked;
             if (dst)
                 for (int i = 0; i < 3; i++)
                     if (dst[i]) HIPCHK(c, hipMemcpy(dst[i], c->d_rec[i], i ? ysz / 4 : ysz, hipMemcpyDeviceToHost));
         }
-        rc = batch_release_slot(b, slot, c->stream);
+        rc = ring_release(b, b->ring, slot, c->stream);
         if (rc) return fail(c, rc, "%s", b->err);
     }
     if (out_final) {
@@ -1023,21 +1003,14 @@ static int batch_push_xdescs(pcamv_batch *b, hipStream_t st, const ExtractDev **
         HIPCHKB(b, hipHostMalloc((void **)&b->h_X, sizeof(ExtractDev) * b->n * NRING, hipHostMallocDefault));
         HIPCHKB(b, dalloc(&b->d_X, (size_t)b->n * NRING));
         HIPCHKB(b, dalloc(&b->d_chk, (size_t)b->n));
-        for (int i = 0; i < NRING; i++) HIPCHKB(b, hipEventCreateWithFlags(&b->xslot_done[i], hipEventDisableTiming));
+        for (int i = 0; i < NRING; i++) HIPCHKB(b, hipEventCreateWithFlags(&b->xring.done[i], hipEventDisableTiming));
     }
-    const int slot = b->xhead;
-    b->xhead = (b->xhead + 1) % NRING;
-    if (b->xslot_used[slot]) HIPCHKB(b, hipEventSynchronize(b->xslot_done[slot]));
+    int slot;
+    { const int rc = ring_take(b, b->xring, &slot); if (rc) return rc; }
     ExtractDev *hX = b->h_X + (size_t)slot * b->n;
     for (int i = 0; i < b->n; i++) hX[i] = b->ctx[i]->X;
     HIPCHKB(b, hipMemcpyAsync(b->d_X + (size_t)slot * b->n, hX, sizeof(ExtractDev) * b->n, hipMemcpyHostToDevice, st));
     *dX = b->d_X + (size_t)slot * b->n; *slot_out = slot;
-    return 0;
-}
-static int batch_release_xslot(pcamv_batch *b, int slot, hipStream_t st)
-{
-    HIPCHKB(b, hipEventRecord(b->xslot_done[slot], st));
-    b->xslot_used[slot] = 1;
     return 0;
 }
 /* Every context's last step -- its records and the flip map of its embedding stage, both still on the device -- through the
@@ -1059,7 +1032,7 @@ extern "C" int pcamv_gpu_batch_extract_step(pcamv_batch_t *b, float emrate, void
     extract_launch(b, dX, b->n, b->ctx[0]->cap, emrate, st);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return bfail(b, PCAMV_EHIP, "kernel launch: %s", hipGetErrorString(e));
-    return batch_release_xslot(b, slot, st);
+    return ring_release(b, b->xring, slot, st);
 }
 /* One frame from host records holding FINAL motion (what pcamv_gpu_parse_pslice_* reads out of a stream): uploaded, then the same
  * kernels.  bits_out (optional, 16 * mb_count bytes) receives the frame's message bits, one per byte; n / m its carriers and bits.
@@ -1080,7 +1053,7 @@ extern "C" int pcamv_gpu_extract_pframe(pcamv_ctx_t *c, const pcamv_mb_t *mbs, f
     extract_launch(b, dX, 1, c->cap, emrate, c->stream);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(c, PCAMV_EHIP, "kernel launch: %s", hipGetErrorString(e));
-    if ((rc = batch_release_xslot(b, slot, c->stream))) return fail(c, rc, "%s", b->err);
+    if ((rc = ring_release(b, b->xring, slot, c->stream))) return fail(c, rc, "%s", b->err);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     int hdr[8];
     HIPCHK(c, hipMemcpy(hdr, c->d_rx_hdr, sizeof(hdr), hipMemcpyDeviceToHost));
@@ -1108,7 +1081,7 @@ extern "C" int pcamv_gpu_batch_payload_check(pcamv_batch_t *b, int64_t *diff)
     kt_end(b, KT_PAYLOAD_CHECK, ev, st);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return bfail(b, PCAMV_EHIP, "kernel launch: %s", hipGetErrorString(e));
-    if ((rc = batch_release_xslot(b, slot, st))) return rc;
+    if ((rc = ring_release(b, b->xring, slot, st))) return rc;
     HIPCHKB(b, hipStreamSynchronize(st));
     static_assert(sizeof(long long) == sizeof(int64_t), "payload_check copies the counts as they are");
     HIPCHKB(b, hipMemcpy(diff, b->d_chk, sizeof(int64_t) * b->n, hipMemcpyDeviceToHost));

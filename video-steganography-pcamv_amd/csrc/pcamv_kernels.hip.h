@@ -614,8 +614,8 @@ struct FlowDev {
 #define FLOW_ERR 512
 #define FLOW_CTR_WORDS 576
 #define FLOW_RDONE_STRIDE 32          /* words between two chains' counters: a 128-byte line each */
-#define FLOW_SPEC_AHEAD 4             /* a macroblock is handed on only once the one FLOW_SPEC_AHEAD before it is final */
-#define FLOW_SPEC_MIN_MBW 8           /* (so that its top / top-right neighbours, mb_w - 1 .. mb_w + 1 back, always are) */
+#define FLOW_SPEC_AHEAD 4             /* a macroblock is handed on only once the one FLOW_SPEC_AHEAD before it is final (so that its top / top-right
+                                       * neighbours, mb_w - 1 .. mb_w + 1 back, always are: FLOW_SPEC_MIN_MBW, pcamv_rd_select.h) */
 
 #ifdef PCAMV_MAIN_TU
 static __global__ void __launch_bounds__(256) k_flow_init(FlowDev fl)
@@ -781,14 +781,10 @@ __device__ __forceinline__ void flow_loop(const FrameDev *__restrict__ Fs, const
         if (!item) { if (lane == 0) __hip_atomic_store(&fl.ctr[FLOW_ERR], 1u, RLX_AGENT); break; }
         if (MODE == 0) PROF_ADD(14, t_item);
         const unsigned long long t_f = PROF_T();
-#ifdef PCAMV_FLOW_ACQUIRE
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");         /* drop this CU's stale L1 lines of the neighbours' motion */
-#else
         /* no agent-scope acquire: the only data of other waves read here is the neighbours' motion, and every such
          * load is itself an agent-scope load (NB_LD*, `sc1`) issued after the queue entry was seen -- so this CU's L1
          * keeps its lines of the reference planes instead of losing them once per macroblock and wave */
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#endif
         const int g = (int)((item - 1u) >> 16), xy = (int)((item - 1u) & 0xffffu);
         const FrameDev F = Fs[g];
         const int y = xy / fl.mb_w, x = xy - y * fl.mb_w;
@@ -881,18 +877,7 @@ static __global__ void __launch_bounds__(64, PCAMV_RD_OCC) k_analyse_flow_rd(con
     flow_loop<0, PCAMV_RD_VARIANT>(Fs, fl, L, &A, nullptr);
 }
 #endif
-void pcamv_launch_flow_rd(unsigned waves, hipStream_t st, const FrameDev *dF, const FlowDev &fl);
-int pcamv_flow_rd_waves_per_cu(void);
-void pcamv_launch_flow_rd_lo(unsigned waves, hipStream_t st, const FrameDev *dF, const FlowDev &fl);
-int pcamv_flow_rd_waves_per_cu_lo(void);
-void pcamv_launch_flow_rd_spec(unsigned waves, hipStream_t st, const FrameDev *dF, const FlowDev &fl);
-int pcamv_flow_rd_waves_per_cu_spec(void);
-void pcamv_launch_flow_rd_tesa(unsigned waves, hipStream_t st, const FrameDev *dF, const FlowDev &fl);
-int pcamv_flow_rd_waves_per_cu_tesa(void);
-void pcamv_launch_flow_rd_spec2(unsigned waves, hipStream_t st, const FrameDev *dF, const FlowDev &fl);
-int pcamv_flow_rd_waves_per_cu_spec2(void);
-void pcamv_launch_flow_rd_spec4(unsigned waves, hipStream_t st, const FrameDev *dF, const FlowDev &fl);
-int pcamv_flow_rd_waves_per_cu_spec4(void);
+/* (its builds' launchers are declared with the library's table of them, pcamv_gpu.hip) */
 
 /* pass 2 + loop filter through the same queue: the tasks are short (~5 us), which only works because the hand-off
  * costs no cache maintenance -- final motion and reconstructed pixels are stored write-through (NB_ST*) and the

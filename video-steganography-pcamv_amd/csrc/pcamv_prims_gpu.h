@@ -415,33 +415,12 @@ __device__ __forceinline__ EvalRes eval_list_body(const EvalEnv &F, MBLocal *L, 
     return res;
 }
 
-__device__ __forceinline__ uint64_t rfl64(uint64_t v) { return (uint64_t)(uint32_t)rfl((int)(uint32_t)v) | (uint64_t)(uint32_t)rfl((int)(uint32_t)(v >> 32)) << 32; }
-#ifdef PCAMV_EVAL_CALL
-/* -DPCAMV_EVAL_CALL (off; kept for measurements): the list primitive as ONE real function (flags at run time; the descriptor
- * fields it reads arrive as values and are made scalar again) instead of an inlined copy per call site (7 KB against ~600 KB
- * of the kernel).  Measured slower both ways: a lone wave with every register 356 k against 282 k cycles per macroblock, the
- * 4-waves-per-SIMD build 12.7 against 14.2 M MB/s at 4096 chains (fewer spills, 128 instead of 149, but 40 calls per macroblock
- * each pay the callee-saved registers' round trip through scratch).  The CABAC residual walk, 2 calls per macroblock, is the
- * opposite case (pcamv_prims_rd_gpu.h). */
-static __device__ __noinline__ EvalRes eval_list_fn(EvalEnv E, MBLocal *L, const uint8_t *enc, int ip, int xoff, int yoff, int n, int flags, int mvp0, int mvp1)
-{
-    EvalEnv U;
-    U.cost_mv = (const int16_t *)rfl64((uint64_t)E.cost_mv); U.luma_base = (const uint8_t *)rfl64((uint64_t)E.luma_base); U.chroma_base = (const uint8_t *)rfl64((uint64_t)E.chroma_base);
-    U.plane_size = (long long)rfl64((uint64_t)E.plane_size); U.cplane_size = (long long)rfl64((uint64_t)E.cplane_size);
-    U.lskip = rfl(E.lskip); U.cstride = rfl(E.cstride); U.trace = (int *)rfl64((uint64_t)E.trace); U.trace_mb = rfl(E.trace_mb);
-    return eval_list_body(U, L, enc, ip, xoff, yoff, n, flags, mvp0, mvp1);
-}
-#endif
 __device__ __forceinline__ EvalRes prim_eval_list(const FrameDev &F, MBLocal *L, const uint8_t *enc, int ip, int xoff, int yoff, int n, int flags, int mvp0, int mvp1)
 {
     EvalEnv E;
     E.cost_mv = F.cost_mv; E.luma_base = F.luma_base; E.chroma_base = F.chroma_base[0]; E.plane_size = F.plane_size; E.cplane_size = F.cplane_size;
     E.lskip = F.lskip; E.cstride = F.cstride; E.trace = F.trace; E.trace_mb = F.trace_mb;
-#ifdef PCAMV_EVAL_CALL
-    return eval_list_fn(E, L, enc, ip, xoff, yoff, n, flags, mvp0, mvp1);
-#else
     return eval_list_body(E, L, enc, ip, xoff, yoff, n, flags, mvp0, mvp1);
-#endif
 }
 
 /* Exhaustive search window (me.c:489-622 without the ADS skip, see pcamv_logic.h): SAD + MV bits of every
@@ -896,90 +875,28 @@ __device__ __forceinline__ int quad_had2x2(int v, int q)
     int a = v0 + v1, b = v2 + v3, c = v0 - v1, e = v2 - v3;      /* d0, d1, d2, d3 of the reference */
     return q == 0 ? a + b : q == 1 ? a - b : q == 2 ? c + e : c - e;
 }
-/* Transform stage of x264_macroblock_encode for an inter macroblock (encoder/macroblock.c:277-372,
- * 696-753): residual transform + quantisation, luma 8x8 / macroblock decimation, chroma DC 2x2 and the
- * chroma decimation rule, dequantisation, inverse transform added to the prediction in L->pred.
- * One 4x4 block per lane (0..15 luma in x264 block order = quads of lanes are 8x8 blocks, 16..19 U,
- * 20..23 V), levels stay in registers, every decision is a quad / row DPP reduction:
- *   - the reference's saturating `if (dec8 < 6) dec8 += score` only ever compares against 4 and 6, so
- *     plain sums decide identically. */
-/* lv: also leave the quantised levels in scan order (L->coef per block, L->cdc chroma DC in zigzag_scan_2x2_dc order) and the
- * per-block non-zero flags as the entropy coder sees them (L->nzc: zero where an 8x8 / the macroblock / a chroma plane was dropped) */
-__device__ __forceinline__ void prim_mb_transform_v1(const FrameDev &F, MBLocal *L, int lv_ = 0)
-{
-    PCAMV_WAVE_SYNC();
-    const int lv = rfl(lv_);
-    const int lane = LANE();
-    const bool is_l = lane < 16, is_c = lane >= 16 && lane < 24;
-    const int ch = (lane - 16) >> 2, ci = (lane - 16) & 3;
-    const int px = is_l ? 4 * blk_x_of(lane) : ch * 8 + (ci & 1) * 4;
-    const int py = is_l ? 4 * blk_y_of(lane) : 16 + (ci >> 1) * 4;
-    int16_t d[16];
-    int nz = 0, score = 0, rawdc = 0;
-    if (is_l || is_c) residual_block(F, L, px, py, is_l, d, &nz, &score, &rawdc, lv ? L->coef[lane < 24 ? lane : 0] : nullptr);
-    /* luma: 8x8 sums over quads, macroblock sum over the row of 16 lanes */
-    const int sc = (nz && F.b_dct_decimate) ? score : 0;
-    int q8 = sc + dpp_qp1(sc); q8 += dpp_qp2(q8);
-    int any8 = nz | dpp_qp1(nz); any8 |= dpp_qp2(any8);
-    int row = q8 + dpp_hmir(q8); row += dpp_mir(row);            /* the four quad sums of the 16-lane row together */
-    bool keep = F.b_dct_decimate ? (q8 >= 4 && row >= 6) : any8 != 0;
-    /* chroma: per plane (quad) AC score, DC 2x2 transform, quantisation, dequantisation */
-    const int cdc = quad_had2x2(rawdc, lane & 3);
-    int dcq;
-    { const int mf = F.q_mf[1][0] >> 1, bias = F.q_bias[1][0] << 1;
-      dcq = cdc > 0 ? ((bias + cdc) * mf >> 16) : -((bias - cdc) * mf >> 16); }
-    int nzdc = dcq != 0; nzdc |= dpp_qp1(nzdc); nzdc |= dpp_qp2(nzdc);
-    int dmf = F.dq_mf_c[0], qbits = F.chroma_qp / 6 - 5;
-    if (qbits > 0) { dmf <<= qbits; qbits = 0; }
-    const int rdc = (int16_t)(quad_had2x2(dcq, lane & 3) * dmf >> -qbits);
-    const int cmode = (q8 < 7 && F.b_dct_decimate) || !any8 ? (nzdc ? 1 : 0) : 2;     /* on chroma lanes q8 / any8 are the plane's */
-    const unsigned long long keep_mask = __ballot(is_l && keep), ac_mask = __ballot(is_c && cmode == 2);
-    uint8_t *dst = L->pred + py * 16 + px;
-    if (is_l) {
-        if (keep && nz) idct4x4_add(dst, d);
-    } else if (is_c) {
-        if (cmode == 2) { if (nzdc) d[0] = (int16_t)rdc; idct4x4_add(dst, d); }
-        else if (cmode == 1) {
-            const int v = (rdc + 32) >> 6;
-#pragma unroll
-            for (int y = 0; y < 4; y++) {
-                uint32_t p = lds4(dst + y * 16), o = 0;
-#pragma unroll
-                for (int x = 0; x < 4; x++) o |= (uint32_t)clip3i((int)((p >> (8 * x)) & 255) + v, 0, 255) << (8 * x);
-                sts4(dst + y * 16, o);
-            }
-        }
-    }
-    L->nnz_mask = (int)(__ballot(is_l && keep && nz) & 0xffffu);
-    L->cbp_luma = (int)((keep_mask & 1) | ((keep_mask >> 3) & 2) | ((keep_mask >> 6) & 4) | ((keep_mask >> 9) & 8));
-    const unsigned long long dc_mask = __ballot(is_c && nzdc);
-    L->cbp_chroma = ac_mask ? 2 : dc_mask ? 1 : 0;                 /* encoder/macroblock.c:364-372: DC-only chroma */
-    if (lv) {
-        if (is_l) L->nzc[scan8_of(lane)] = (uint8_t)(keep && nz);
-        else if (is_c) {
-            L->nzc[scan8_all_of(lane)] = (uint8_t)(cmode == 2 && nz);
-            const int q = lane & 3;
-            L->cdc[ch][q == 1 ? 2 : q == 2 ? 1 : q] = (int16_t)dcq;     /* zigzag_scan_2x2_dc: d[0][0], d[1][0], d[0][1], d[1][1] */
-            if (q == 0) L->nzc[scan8_all_of(25 + ch)] = (uint8_t)(nzdc != 0);
-        }
-        if (lane == 0) L->nzc[scan8_all_of(24)] = 0;
-    }
-    PCAMV_WAVE_SYNC();
-}
 /* lane ^ 4 inside a row of 16: two row shifts, each written to the banks (quads) it is right for */
 __device__ __forceinline__ int dpp_x4(int v)
 {
     const int a = __builtin_amdgcn_update_dpp(0, v, 0x104, 0xf, 0x5, false);
     return __builtin_amdgcn_update_dpp(a, v, 0x114, 0xf, 0xa, false);
 }
-/* The same stage with TWO lanes per 4x4 block (round 3): a lone macroblock has 24 blocks, one per lane left 40 lanes idle through ~900
+/* Transform stage of x264_macroblock_encode for an inter macroblock (encoder/macroblock.c:277-372,
+ * 696-753): residual transform + quantisation, luma 8x8 / macroblock decimation, chroma DC 2x2 and the
+ * chroma decimation rule, dequantisation, inverse transform added to the prediction in L->pred.
+ * Levels stay in registers, every decision is a DPP reduction:
+ *   - the reference's saturating `if (dec8 < 6) dec8 += score` only ever compares against 4 and 6, so
+ *     plain sums decide identically.
+ * TWO lanes per 4x4 block (round 3): a lone macroblock has 24 blocks, one per lane left 40 lanes idle through ~900
  * instructions.  Lane 2 b + h (luma, b in x264 block order: an 8x8 is eight lanes) and 32 + 2 cb + h (chroma, a plane is eight lanes)
  * holds rows 0 and 3 (h = 0) or 1 and 2 (h = 1) of its block: the horizontal transform and the first vertical butterfly (row A +- row B)
  * are in-lane, the second one exchanges with the partner lane (h = 0 ends with the coefficients of vertical frequency 0 and 1, h = 1 with
  * 2 and 3, all four horizontal frequencies each); quantisation, scan masks and dequantisation work on eight coefficients instead of
  * sixteen; the inverse transform runs the other way round (horizontal pass in-lane per vertical frequency, one exchange, and h = 0 ends
- * with rows 0 and 3, h = 1 with rows 1 and 2 -- the rows it loaded).  Same results as prim_mb_transform_v1, the arithmetic is the
- * reference's (dct.c:122-170, quant.c, macroblock.c) value for value. */
+ * with rows 0 and 3, h = 1 with rows 1 and 2 -- the rows it loaded).  The arithmetic is the reference's (dct.c:122-170, quant.c,
+ * macroblock.c) value for value. */
+/* lv: also leave the quantised levels in scan order (L->coef per block, L->cdc chroma DC in zigzag_scan_2x2_dc order) and the
+ * per-block non-zero flags as the entropy coder sees them (L->nzc: zero where an 8x8 / the macroblock / a chroma plane was dropped) */
 __device__ __forceinline__ void prim_mb_transform(const FrameDev &F, MBLocal *L, int lv_ = 0)
 {
     PCAMV_WAVE_SYNC();

@@ -698,62 +698,6 @@ PCAMV_RESIDUAL_FN CabBits cab_residual_walk(MBLocal *L, int commit_, int part_)
     }
     PROF_ADD(25, t_2);
     const unsigned long long t_3 = PROF_T();
-#ifdef PCAMV_RESIDUAL_V1
-    /* ---- 3 */
-    for (int pass = 0; pass < 3; pass++) {
-        const unsigned catm = pass == 0 ? 0xffffu : pass == 1 ? 0x3000000u : 0xff0000u;
-        unsigned bm = flagm & catm;
-        if (!bm) continue;
-        const int cnt = pass == 0 ? 16 : pass == 1 ? 4 : 15;
-        const int sig_off = pass == 0 ? 134 : pass == 1 ? 149 : 152, last_off = pass == 0 ? 195 : pass == 1 ? 210 : 213, lvl_off = pass == 0 ? 247 : pass == 1 ? 257 : 266;
-        int sigS = lane < cnt - 1 ? S[sig_off + lane] : 0, lastS = lane < cnt - 1 ? S[last_off + lane] : 0, lvlS = lane < 10 ? S[lvl_off + lane] : 0;
-        unsigned long long lvlQ = 0; int lvlN = 0, lvl_tot = 0;
-        for (; bm; bm &= bm - 1) {
-            const int b = __builtin_ctz(bm);
-            const unsigned nz = (unsigned)__builtin_amdgcn_readlane((int)nzm, b), g1 = (unsigned)__builtin_amdgcn_readlane((int)gt1, b);
-            const unsigned n0 = (unsigned)__builtin_amdgcn_readlane((int)nib0, b), n1 = (unsigned)__builtin_amdgcn_readlane((int)nib1, b);
-            const int last = 31 - __builtin_clz(nz);
-            if (lane < imin(last + 1, cnt - 1)) {
-                const int sb = (int)((nz >> lane) & 1u);
-                const uint32_t w1 = T[2 * sigS + sb], w2 = T[2 * lastS + (lane == last)];
-                bits += (int)(w1 >> 8); sigS = (int)(w1 & 255u);
-                if (sb) { bits += (int)(w2 >> 8); lastS = (int)(w2 & 255u); }
-            }
-            /* levels from the last non-zero one down: node = min(#(|l| = 1) so far, 3) until a level above 1 was seen, then
-             * min(3 + #(|l| > 1), 7); the decisions go to the queues of the lanes that own the level contexts (lane k < 10) */
-            int neq1 = 0, ngt1 = 0;
-            for (unsigned m = nz; m;) {
-                const int i = 31 - __builtin_clz(m);
-                m &= ~(1u << i);
-                const int node = ngt1 ? imin(3 + ngt1, 7) : imin(neq1, 3);
-                const int c1 = node < 4 ? node + 1 : 0, c2 = node < 4 ? 5 : imin(node + 2, 9);
-                if (lvl_tot > 64 - 16) { bits += cabq_resolve(T, lvlS, lvlQ, lvlN); lvl_tot = 0; }     /* no queue may pass 64 bins */
-                if ((g1 >> i) & 1u) {
-                    int a = (int)(((i < 8 ? n0 : n1) >> (4 * (i & 7))) & 15u);
-                    if (a == 15) {          /* 15 or more: the exact magnitude (escape suffix) from the block's levels */
-                        const int16_t *l = b < 16 ? L->coef[b] : b < 24 ? L->coef[b] + 1 : L->cdc[b - 24];
-                        a = rfl(iabs((int)l[i]));
-                    }
-                    const int am1 = a - 1, prefix = imin(am1, 14);
-                    cabq_push(lvlQ, lvlN, c1, 1);
-                    cabq_push_run(lvlQ, lvlN, c2, prefix - 1, prefix < 14);
-                    if (prefix >= 14) sbits += size_ue_of((unsigned)(am1 - 14)) << 8;
-                    lvl_tot += 1 + prefix;
-                    ngt1++;
-                } else {
-                    cabq_push(lvlQ, lvlN, c1, 0);
-                    lvl_tot++;
-                    neq1++;
-                }
-            }
-            sbits += 256 * __builtin_popcount(nz);       /* signs */
-            PROF_CNT(30, __builtin_popcount(nz));
-        }
-        bits += cabq_resolve(T, lvlS, lvlQ, lvlN);
-        if (lane < cnt - 1) { D[sig_off + lane] = (uint8_t)sigS; D[last_off + lane] = (uint8_t)lastS; }
-        if (lane < 10) D[lvl_off + lane] = (uint8_t)lvlS;
-    }
-#else
     /* ---- 3 (round 3): nothing per level or per block on the scalar side any more.
      * 3a. Every block with levels (its own lane) describes, in ten words, what it contributes to each context, in closed form: with
      *     n levels, `last` the highest position, h the highest position of a level above 1 and t the number of levels above h
@@ -872,7 +816,6 @@ PCAMV_RESIDUAL_FN CabBits cab_residual_walk(MBLocal *L, int commit_, int part_)
         if (live) D[ctx] = (uint8_t)st;
     }
     (void)sbits;
-#endif
     PROF_ADD(26, t_3);
     out.vbits = bits; out.bits = sbits;
     return out;

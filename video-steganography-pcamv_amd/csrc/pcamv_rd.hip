@@ -19,9 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #define PCAMV_RD_TU 1
-#ifndef PCAMV_NO_RESIDUAL_CALL
 #define PCAMV_RESIDUAL_CALL 1      /* pcamv_prims_rd_gpu.h: the CABAC residual walk as a function of its own */
-#endif
 /* variant mask of the control code (pcamv_logic.h): 2 = RD mode decision, 4 = speculative raster chain, 8 = sub-8x8 partitions priced by
  * x264_rd_cost_part -- only in the two one-wave-per-SIMD builds, which have the registers for it (compiled into the 4-waves-per-SIMD
  * build it cost 22 spilled VGPRs); batches with --partitions p4x4 at --subme >= 6 run on those (pcamv_gpu_batch_create) */

@@ -5,7 +5,5 @@
  * context states share LDS (pcamv_mbkernels.h mbk_search).
  */
 #define PCAMV_RD_TESA 1
-#ifndef PCAMV_RD_TESA_INLINE
 #define PCAMV_SEARCH_CALL 1          /* the search of a partition as a function of its own (pcamv_logic.h): inlined at every call site this unit took 8 minutes to compile */
-#endif
 #include "pcamv_rd.hip"

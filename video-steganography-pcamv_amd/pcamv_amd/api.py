@@ -131,9 +131,13 @@ def lib_path():
     return os.environ.get("PCAMV_GPU_LIB") or os.path.join(_PKG, "libpcamv_gpu.so")
 
 
+# the library's translation units (csrc/<unit>.hip): the host side with the common kernels, the --me tesa instance of the analysis kernel,
+# and the six builds of its --subme 6 / 7 instance
+UNITS = ("pcamv_gpu", "pcamv_tesa", "pcamv_rd", "pcamv_rd_lo", "pcamv_rd_spec", "pcamv_rd_spec2", "pcamv_rd_spec4", "pcamv_rd_tesa")
+
+
 def build_library(force=False):
-    """hipcc --offload-arch=gfx950 of csrc/pcamv_gpu.hip (+ csrc/pcamv_tesa.hip, the --me tesa instance, and csrc/pcamv_rd.hip + csrc/pcamv_rd_lo.hip
-    + csrc/pcamv_rd_spec{,2,4}.hip + csrc/pcamv_rd_tesa.hip, the six builds of the --subme 6 / 7 instance, compiled side by side) into the in-tree libpcamv_gpu.so."""
+    """hipcc --offload-arch=gfx950 of UNITS, compiled side by side, into the in-tree libpcamv_gpu.so."""
     out = lib_path()
     srcs = [os.path.join(_CSRC, f) for f in sorted(os.listdir(_CSRC)) if not f.endswith(".o")]
     srcs.append(os.path.join(os.path.dirname(_PKG), "include", "pcamv_gpu.h"))
@@ -141,7 +145,7 @@ def build_library(force=False):
         return out
     flags = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-std=c++17", "-Wno-unused-value", "-Wno-unused-result"]
     objs, procs = [], []
-    for unit in ("pcamv_gpu", "pcamv_tesa", "pcamv_rd", "pcamv_rd_lo", "pcamv_rd_spec", "pcamv_rd_spec2", "pcamv_rd_spec4", "pcamv_rd_tesa"):
+    for unit in UNITS:
         obj = os.path.join(_CSRC, unit + ".o")
         objs.append(obj)
         procs.append(subprocess.Popen(["hipcc", *flags, "-c", "-o", obj, os.path.join(_CSRC, unit + ".hip")]))
