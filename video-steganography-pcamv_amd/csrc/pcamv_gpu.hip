@@ -16,11 +16,19 @@
 #include "pcamv_rd_select.h"
 
 #define PCAMV_ABI_VERSION 3
-#define NEV 32
+#define NEV 32                 /* launches the analysis kernel's timer remembers between two kernel_time calls ... */
 #define NRING 8
-#define NKEV 16                /* launches a timer of the smaller kernels remembers between two kernel_time calls */
-enum { KT_EMBED_PREPARE, KT_EXTRACT_PREPARE, KT_EXTRACT_BITS, KT_PAYLOAD_CHECK, KT_N };
+#define NKEV 16                /* ... and a timer of the smaller kernels */
+enum { KT_ANALYSE, KT_EMBED_PREPARE, KT_EXTRACT_PREPARE, KT_EXTRACT_BITS, KT_PAYLOAD_CHECK, KT_N };
 #define PCAMV_FEATURES PCAMV_FEATURE_PAYLOAD
+/* the stages of a step (batch_launch's `what`): plane production, analysis (search + RCA + encode), embedding, second pass */
+enum { ST_PLANES = 1, ST_ANALYSE = 2, ST_EMBED = 4, ST_PASS2 = 8 };
+
+/* what device code assumes of constants it cannot see side by side (this unit includes both headers) */
+static_assert(sizeof(pcamv_mb_t) == 59 * 4, "p2_unit_load copies a record as 59 dwords: a field added to pcamv_mb_t truncates or misaligns the second pass' LDS copy");
+static_assert(P2_LSLOTS <= 64 * 11 && P2_CSLOTS <= 64 * 7 && 8 * 59 <= 64 * 8,
+              "p2_unit_load's fixed unroll counts (11 / 7 / 8 rounds of 64 lanes) no longer cover the luma tile, the chroma tile or the 8 records of a run");
+static_assert(FLOW_SPEC_MIN_MBW - 1 > FLOW_SPEC_AHEAD + 1, "speculative chain: a macroblock would be handed on before its top / top-right neighbours are final");
 
 /* The builds of the RD instance of the analysis kernel (pcamv_rd.hip RD_NAME: one translation unit each), a row per entry of
  * PCAMV_RD_BUILDS in the order of rd_select's result; the phase timers are per translation unit (PCAMV_PROF) */
@@ -43,6 +51,9 @@ static const RdBuild rd_builds[RD_N_BUILDS] = {PCAMV_RD_BUILDS(RD_ROW)};
 
 /* one ring of NRING descriptor slots: a slot is written again only after the work that read it last (its event) is done */
 struct DescRing { int head, used[NRING]; hipEvent_t done[NRING]; };
+/* hipEvents around the launches of one kernel, summed when pcamv_gpu_batch_kernel_time asks for it by name: a ring of the last `cap`
+ * launches; one pair of events stands for `weight` launches (the anti-diagonals of PCAMV_SCHED=diag share a pair) */
+struct KTimer { hipEvent_t e0[NEV], e1[NEV]; int cap, weight, made, n, head, launches; double ms; };
 
 struct pcamv_ctx;
 /* A batch = the set of independent closed-GOP contexts whose frames advance together: every kernel
@@ -54,24 +65,21 @@ struct pcamv_batch {
     FrameDev *h_F, *d_F;        /* NRING slots of n descriptors (pinned host / device) */
     EmbedDev *h_E, *d_E;
     DescRing ring;
-    hipEvent_t ev0[NEV], ev1[NEV];
-    int ev_n, ev_head;
-    double t_search_ms; int t_search_launches;
     /* dataflow schedule (k_analyse_flow): queue + dependency counters, one persistent launch per step */
     int sched_flow, flow_waves, flow2_waves, closed_loop, stc_ns;
     int b_mbrd, b_tesa;         /* instance of the analysis kernel the batch's contexts need (fixed at creation) */
     const RdBuild *rd;          /* ... and which build of the RD instance (b_mbrd) */
     unsigned *d_flow;
     FlowDev fl, fl2;          /* queue descriptors of the analysis and of the second pass */
-    /* payload path: descriptors of the receiving side (their own ring, made by the first extraction), the per-context counts of
-     * payload_check, and the timers of the kernels besides the dominant one */
+    /* payload path: descriptors of the receiving side (their own ring, made by the first extraction) and the per-context counts of
+     * payload_check */
     ExtractDev *h_X, *d_X; long long *d_chk;
     DescRing xring;
-    struct KTimer { hipEvent_t e0[NKEV], e1[NKEV]; int made, n, head, launches; double ms; } kt[KT_N];
+    KTimer kt[KT_N];            /* the timed kernels; the events of a timer are made by its first launch */
     char err[256];
 };
-static const char *const kt_names[KT_N] = {"k_embed_prepare", "k_extract_prepare", "k_extract_bits", "k_payload_check"};
 
+#define CTX_NBUF 168            /* device buffers a context can own: the two per-QP tables of 52 and the ~55 buffers with a name */
 struct pcamv_ctx {
     pcamv_params_t p;
     int device;
@@ -80,42 +88,51 @@ struct pcamv_ctx {
     pcamv_batch *last;          /* batch that ran this context's most recent analysis */
     FrameDev F;
     EmbedDev E;
-    /* device allocations */
-    uint8_t *d_fenc[3], *d_raw[3], *d_luma, *d_luma_raster, *d_chroma[2], *d_rec[3];
-    int8_t *d_mb_type, *d_ref8, *d_prev_ref, *d_ref8_b;
-    int16_t *d_mv, *d_mvr, *d_prev_mv, *d_mvp_aux, *d_mv_b;
+    /* device memory: every buffer is one hipMalloc of ctx_alloc, which notes it here for pcamv_gpu_close.  Most live in the member of
+     * F / E / X that the kernels read; a field below is what such a member is pointed at and away from while the context lives */
+    void *owned[CTX_NBUF]; int n_owned;
+    uint8_t *d_fenc[3], *d_raw[3];
+    int8_t *d_ref8, *d_prev_ref, *d_ref8_b;
+    int16_t *d_mv, *d_prev_mv, *d_mv_b;
     int last_field, prev_internal;   /* ping-pong of the motion field for device-resident chains: which of d_mv (0) / d_mv_b (1) the last analysis wrote */
     pcamv_batch *member_of[16]; int n_member;    /* batches this context belongs to (its own included): told when it closes */
-    pcamv_mb_t *d_rec_mb;
     int16_t *d_cost_mv[52];
-    uint8_t *d_cover, *d_stego, *d_message, *d_user_msg; unsigned *d_colinfo;
-    float *d_rho; int8_t *d_flip; int *d_hdr, *d_rnd; unsigned *d_cols, *d_path; long long *d_lcg;
+    uint8_t *d_user_msg;
+    int8_t *d_flip;
     int cap;
-    /* payload path: the attached payload (own copy, or the caller's device buffer), the cursors (PST_*), the received stream and the
-     * receiver's scratch (made by pcamv_gpu_rx_reserve / the first extraction) */
-    uint8_t *d_payload_own; size_t payload_own_bytes; long long *d_pstate;
-    ExtractDev X; unsigned *d_rx; uint8_t *d_rx_stego, *d_rx_bits; int *d_rx_hdr; unsigned *d_rx_cols; pcamv_mb_t *d_rx_mbs;
+    /* payload path: the attached payload (own copy, or the caller's device buffer), the received stream and the receiver's scratch (made
+     * by pcamv_gpu_rx_reserve / the first extraction); the cursors (PST_*) are E.pstate */
+    uint8_t *d_payload_own; size_t payload_own_bytes;
+    ExtractDev X; unsigned *d_rx; uint8_t *d_rx_bits; pcamv_mb_t *d_rx_mbs;
     int *d_trace;
-    uint16_t *d_nnz; int *d_car_base; int8_t *d_flip_user;     /* pass 2 */
+    int8_t *d_flip_user;       /* pass 2 */
     uint8_t *d_mbflip;         /* [n_mb] per macroblock: a carrier of it is flipped in d_flip */
-    int rec_pristine;          /* d_rec / d_nnz hold the first pass' reconstruction of the frame last analysed (no second pass has run over it) */
+    int rec_pristine;          /* F.rec / F.nnz hold the first pass' reconstruction of the frame last analysed (no second pass has run over it) */
     /* --subme >= 6 */
-    uint8_t *d_nb_nz, *d_cabac, *d_cabac_init[52]; int16_t *d_nb_cbp, *d_nb_mvd; uint32_t *d_cabac_tab, *d_dbg_hash;
+    uint8_t *d_cabac_init[52]; uint32_t *d_dbg_hash;
     char err[256];
 };
 
-static int fail(pcamv_ctx *c, int code, const char *fmt, ...)
+/* the error text of a context or of a batch */
+template <class Owner> static int fail(Owner *o, int code, const char *fmt, ...)
 {
-    if (c) { va_list ap; va_start(ap, fmt); vsnprintf(c->err, sizeof(c->err), fmt, ap); va_end(ap); }
+    if (o) { va_list ap; va_start(ap, fmt); vsnprintf(o->err, sizeof(o->err), fmt, ap); va_end(ap); }
     return code;
 }
-static int bfail(pcamv_batch *b, int code, const char *fmt, ...)
+#define HIPCHK(o, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(o, PCAMV_EHIP, "%s: %s", #call, hipGetErrorString(e_)); } while (0)
+#define TRY(call) do { const int rc_ = (call); if (rc_) return rc_; } while (0)
+/* rc of a call the batch made on behalf of context c: its error text becomes the context's */
+static int on_behalf(pcamv_ctx *c, const pcamv_batch *b, int rc)
 {
-    if (b) { va_list ap; va_start(ap, fmt); vsnprintf(b->err, sizeof(b->err), fmt, ap); va_end(ap); }
-    return code;
+    if (rc) snprintf(c->err, sizeof(c->err), "%s", b->err);
+    return rc;
 }
-#define HIPCHK(c, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(c, PCAMV_EHIP, "%s: %s", #call, hipGetErrorString(e_)); } while (0)
-#define HIPCHKB(b, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return bfail(b, PCAMV_EHIP, "%s: %s", #call, hipGetErrorString(e_)); } while (0)
+/* a batch can run only while all its contexts are open */
+static int batch_live(pcamv_batch *b)
+{
+    for (int i = 0; i < b->n; i++) if (!b->ctx[i]) return fail(b, PCAMV_EINVAL, "context %d of the batch was closed", i);
+    return 0;
+}
 
 extern "C" int pcamv_gpu_abi_version(void) { return PCAMV_ABI_VERSION; }
 extern "C" unsigned pcamv_gpu_features(void) { return PCAMV_FEATURES; }
@@ -135,6 +152,33 @@ extern "C" int pcamv_gpu_prof_fetch(unsigned long long *out, int reset)
 extern "C" const char *pcamv_gpu_last_error(const pcamv_ctx_t *c) { return c ? c->err : "no context"; }
 
 template <class T> static hipError_t dalloc(T **p, size_t n) { return hipMalloc((void **)p, n * sizeof(T)); }
+/* device memory of a context: `count` elements in one allocation of its own, every byte set to `fill` if that is >= 0; released by
+ * pcamv_gpu_close, whichever way the context got there, or before that by ctx_free */
+template <class T> static int ctx_alloc(pcamv_ctx *c, T **p, size_t count, int fill = -1)
+{
+    if (c->n_owned >= CTX_NBUF) return fail(c, PCAMV_ENOMEM, "a context owns at most %d device buffers", CTX_NBUF);
+    HIPCHK(c, dalloc(p, count));
+    c->owned[c->n_owned++] = (void *)*p;
+    if (fill >= 0) HIPCHK(c, hipMemset((void *)*p, fill, count * sizeof(T)));
+    return 0;
+}
+template <class T> static void ctx_free(pcamv_ctx *c, T **p)
+{
+    for (int i = 0; i < c->n_owned; i++) if (c->owned[i] == (void *)*p) { c->owned[i] = c->owned[--c->n_owned]; break; }
+    hipFree((void *)*p); *p = NULL;
+}
+/* temporaries released when their scope ends, on every return path: a device allocation and a host block */
+template <class T> struct DevTmp {
+    T *p = NULL;
+    DevTmp() {} DevTmp(const DevTmp &) = delete; ~DevTmp() { hipFree(p); }
+    hipError_t alloc(size_t n) { return dalloc(&p, n); }
+    operator T *() const { return p; }
+};
+template <class T> struct HostTmp {      /* NULL when there is no memory */
+    T *p;
+    explicit HostTmp(size_t n) : p((T *)malloc(n * sizeof(T))) {} HostTmp(const HostTmp &) = delete; ~HostTmp() { free(p); }
+    operator T *() const { return p; }
+};
 
 /* glibc srand(seed) state (random_r TYPE_3): the reference draws message bits from rand() with the
  * default seed 1 (encoder.c:1838-1840) */
@@ -158,6 +202,15 @@ static void glibc_srand_state(int *st, unsigned seed)
 }
 
 /* ------------------------------------------------------------------ batches */
+static hipError_t ring_create(DescRing &r)
+{
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < NRING && e == hipSuccess; i++) e = hipEventCreateWithFlags(&r.done[i], hipEventDisableTiming);
+    return e;
+}
+static void ring_destroy(DescRing &r) { for (int i = 0; i < NRING; i++) if (r.done[i]) hipEventDestroy(r.done[i]); }
+static void kt_destroy(KTimer &T) { for (int i = 0; i < NEV; i++) { if (T.e0[i]) hipEventDestroy(T.e0[i]); if (T.e1[i]) hipEventDestroy(T.e1[i]); } }
+
 extern "C" void pcamv_gpu_batch_destroy(pcamv_batch_t *b)
 {
     if (!b) return;
@@ -171,16 +224,34 @@ extern "C" void pcamv_gpu_batch_destroy(pcamv_batch_t *b)
     }
     if (b->h_F) hipHostFree(b->h_F);
     if (b->h_E) hipHostFree(b->h_E);
-    hipFree(b->d_F); hipFree(b->d_E);
-    if (b->d_flow) hipFree(b->d_flow);
     if (b->h_X) hipHostFree(b->h_X);
-    hipFree(b->d_X); hipFree(b->d_chk);
-    for (int i = 0; i < NRING; i++) if (b->xring.done[i]) hipEventDestroy(b->xring.done[i]);
-    for (int k = 0; k < KT_N; k++) for (int i = 0; i < NKEV; i++) { if (b->kt[k].e0[i]) hipEventDestroy(b->kt[k].e0[i]); if (b->kt[k].e1[i]) hipEventDestroy(b->kt[k].e1[i]); }
-    for (int i = 0; i < NRING; i++) if (b->ring.done[i]) hipEventDestroy(b->ring.done[i]);
-    for (int i = 0; i < NEV; i++) { if (b->ev0[i]) hipEventDestroy(b->ev0[i]); if (b->ev1[i]) hipEventDestroy(b->ev1[i]); }
+    hipFree(b->d_F); hipFree(b->d_E); hipFree(b->d_flow); hipFree(b->d_X); hipFree(b->d_chk);
+    ring_destroy(b->ring); ring_destroy(b->xring);
+    for (KTimer &T : b->kt) kt_destroy(T);
     free(b->ctx);
     delete b;
+}
+
+/* knobs of the environment, read when a batch is made: is `name` set to `value`; an integer within [lo, hi], else dflt */
+static int env_is(const char *name, const char *value) { const char *v = getenv(name); return v && !strcmp(v, value); }
+static int env_int(const char *name, int lo, int hi, int dflt) { const char *v = getenv(name); return v && atoi(v) >= lo && atoi(v) <= hi ? atoi(v) : dflt; }
+/* waves of a persistent dataflow kernel: as many as the device holds at once (or PCAMV_FLOW_WAVES), at least one, at most one per task */
+static int flow_wave_count(int per_cu, int n_cu, size_t tasks)
+{
+    const char *wv = getenv("PCAMV_FLOW_WAVES");
+    long waves = wv ? atol(wv) : (long)per_cu * n_cu;
+    if (waves < 1) waves = 1;
+    if ((size_t)waves > tasks) waves = (long)tasks;
+    return (int)waves;
+}
+/* the n chains of a batch over the fl.nq queues, whole chains each (fl.n_mb tasks per chain) */
+static void flow_split_queues(FlowDev &fl, int n)
+{
+    unsigned qb = 0;
+    for (int q = 0; q < 8; q++) {
+        const unsigned ng = q < fl.nq ? ((unsigned)n + (unsigned)(fl.nq - 1 - q)) / (unsigned)fl.nq : 0u;
+        fl.qbase[q] = qb; fl.qcount[q] = ng * (unsigned)fl.n_mb; qb += fl.qcount[q];
+    }
 }
 
 extern "C" int pcamv_gpu_batch_create(pcamv_ctx_t *const *ctxs, int n, pcamv_batch_t **out)
@@ -199,75 +270,65 @@ extern "C" int pcamv_gpu_batch_create(pcamv_ctx_t *const *ctxs, int n, pcamv_bat
     b->ctx = (pcamv_ctx **)malloc(sizeof(pcamv_ctx *) * n);
     for (int i = 0; i < n; i++) b->ctx[i] = ctxs[i];
     const FrameDev &F = ctxs[0]->F;
+    const int sub8x8 = (ctxs[0]->p.inter & PCAMV_ANALYSE_PSUB8x8) != 0;
     b->n_diag = F.mb_w + 2 * (F.mb_h - 1);
     b->max_diag = (F.mb_w + 1) / 2 < F.mb_h ? (F.mb_w + 1) / 2 : F.mb_h;
-    b->slots_per_mb = (ctxs[0]->p.inter & PCAMV_ANALYSE_PSUB8x8) ? 16 : 2;
+    b->slots_per_mb = sub8x8 ? 16 : 2;
+    /* schedule: PCAMV_SCHED=diag keeps one launch per anti-diagonal (+ separate RCA / encode launches);
+     * the default is the dataflow kernel.  Both are the same per-macroblock code. */
+    b->sched_flow = !env_is("PCAMV_SCHED", "diag") && F.n_mb <= 65535 && n <= 65535;
+    { const int ns = env_int("PCAMV_STC_STATES", 2, 4, 0); b->stc_ns = ns == 2 || ns == 4 ? ns : (n >= 1024 ? 4 : 2); }      /* trellis states per thread of the forward Viterbi */
+    for (int k = 0; k < KT_N; k++) { b->kt[k].cap = k == KT_ANALYSE ? NEV : NKEV; b->kt[k].weight = 1; }
+    if (!b->sched_flow) b->kt[KT_ANALYSE].weight = b->n_diag;
     hipError_t e = hipSetDevice(b->device);
     if (e == hipSuccess) e = hipHostMalloc((void **)&b->h_F, sizeof(FrameDev) * n * NRING, hipHostMallocDefault);
     if (e == hipSuccess) e = hipHostMalloc((void **)&b->h_E, sizeof(EmbedDev) * n * NRING, hipHostMallocDefault);
     if (e == hipSuccess) e = dalloc(&b->d_F, (size_t)n * NRING);
     if (e == hipSuccess) e = dalloc(&b->d_E, (size_t)n * NRING);
-    for (int i = 0; i < NRING && e == hipSuccess; i++) e = hipEventCreateWithFlags(&b->ring.done[i], hipEventDisableTiming);
-    for (int i = 0; i < NEV && e == hipSuccess; i++) { e = hipEventCreate(&b->ev0[i]); if (e == hipSuccess) e = hipEventCreate(&b->ev1[i]); }
-    /* schedule: PCAMV_SCHED=diag keeps one launch per anti-diagonal (+ separate RCA / encode launches);
-     * the default is the dataflow kernel.  Both are the same per-macroblock code. */
-    const char *sched = getenv("PCAMV_SCHED");
-    b->sched_flow = !(sched && !strcmp(sched, "diag")) && F.n_mb <= 65535 && n <= 65535;
-    { const char *v = getenv("PCAMV_STC_STATES"); b->stc_ns = v && (atoi(v) == 2 || atoi(v) == 4) ? atoi(v) : (n >= 1024 ? 4 : 2); }      /* trellis states per thread of the forward Viterbi */
+    if (e == hipSuccess) e = ring_create(b->ring);
     if (e == hipSuccess && b->sched_flow) {
         const size_t total = (size_t)n * F.n_mb;
         e = dalloc(&b->d_flow, FLOW_CTR_WORDS + 2 * total + (size_t)FLOW_RDONE_STRIDE * n);
-        b->fl.ctr = b->d_flow; b->fl.queue = b->d_flow + FLOW_CTR_WORDS; b->fl.dep = (int *)(b->d_flow + FLOW_CTR_WORDS + total);
-        b->fl.rdone = b->d_flow + FLOW_CTR_WORDS + 2 * total; b->fl.spec = 0;
-        const char *aff = getenv("PCAMV_FLOW_AFFINITY");
-        b->fl.nq = (aff && !strcmp(aff, "0")) || n < 8 ? 1 : 8;
-        unsigned qb = 0;
-        for (int q = 0; q < 8; q++) {
-            unsigned ng = q < b->fl.nq ? ((unsigned)n + (unsigned)(b->fl.nq - 1 - q)) / (unsigned)b->fl.nq : 0u;
-            b->fl.qbase[q] = qb; b->fl.qcount[q] = ng * (unsigned)F.n_mb; qb += b->fl.qcount[q];
-        }
-        b->fl.total = (unsigned)total; b->fl.spin_limit = 4u << 20;
-        b->fl.n_gop = n; b->fl.n_mb = F.n_mb; b->fl.mb_w = F.mb_w; b->fl.mb_h = F.mb_h; b->fl.fused = 1; b->fl.unit = 1;
+        /* the analysis: its queues, which build of it, how many waves */
+        FlowDev &fl = b->fl;
+        fl.ctr = b->d_flow; fl.queue = b->d_flow + FLOW_CTR_WORDS; fl.dep = (int *)(b->d_flow + FLOW_CTR_WORDS + total);
+        fl.rdone = b->d_flow + FLOW_CTR_WORDS + 2 * total; fl.spec = 0;
+        fl.total = (unsigned)total; fl.spin_limit = 4u << 20;
+        fl.n_gop = n; fl.n_mb = F.n_mb; fl.mb_w = F.mb_w; fl.mb_h = F.mb_h; fl.fused = 1; fl.unit = 1;
+        fl.nq = env_is("PCAMV_FLOW_AFFINITY", "0") || n < 8 ? 1 : 8;
+        flow_split_queues(fl, n);
         /* one chain per frame: the context states (CABAC), or -- sub-8x8 partitions priced by x264_rd_cost_part -- the non-zero counts
          * / MV differences the macroblock coded before this one leaves in the cache (PCAMV_CHAIN_NZ) */
-        b->fl.raster = F.b_mbrd && (F.b_cabac || (ctxs[0]->p.inter & PCAMV_ANALYSE_PSUB8x8));
+        fl.raster = F.b_mbrd && (F.b_cabac || sub8x8);
         int per_cu = 0, n_cu = 0;
         if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_analyse_flow, 64, 0);
         if (e == hipSuccess) e = hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, b->device);
         if (e == hipSuccess && F.b_mbrd) {
             /* which build of the RD instance (pcamv_rd_select.h: the rules and what was measured) */
-            b->rd = &rd_builds[rd_select(n, n_cu, b->fl.raster, F.mb_w, (ctxs[0]->p.inter & PCAMV_ANALYSE_PSUB8x8) != 0, b->b_tesa,
-                                         getenv("PCAMV_RD_INSTANCE"), getenv("PCAMV_FLOW_SPEC"))];
-            b->fl.spec = b->rd->spec != 0;
+            b->rd = &rd_builds[rd_select(n, n_cu, fl.raster, F.mb_w, sub8x8, b->b_tesa, getenv("PCAMV_RD_INSTANCE"), getenv("PCAMV_FLOW_SPEC"))];
+            fl.spec = b->rd->spec != 0;
             per_cu = b->rd->waves_per_cu();
             if (per_cu < 0) e = hipErrorUnknown;
         }
-        const char *wv = getenv("PCAMV_FLOW_WAVES");
-        long waves = wv ? atol(wv) : (long)per_cu * n_cu;
-        if (waves < 1) waves = 1;
-        if ((size_t)waves > total) waves = (long)total;
-        b->flow_waves = (int)waves;
-        if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_pass2_deblock_flow, 64, 0);
-        waves = wv ? atol(wv) : (long)per_cu * n_cu;
-        if (waves < 1) waves = 1;
-        if ((size_t)waves > total) waves = (long)total;
+        b->flow_waves = flow_wave_count(per_cu, n_cu, total);
         /* the second pass can take `unit` macroblocks of a row per task (PCAMV_PASS2_UNIT; the dependency graph is the
          * same on the coarser grid).  Measured at G=256: 115.1 / 114.7 / 116.9 / 122.6 ms per step for 1 / 2 / 4 / 8 --
          * its queue traffic is not what bounds it any more.  With thousands of GOPs in flight it is again: 4096 GOPs 2300 / 2277 /
          * 2264 / 2253 ms per step.  Round 3: a task's macroblocks are one LDS tile (P2Unit: one memory round trip, whole cache lines), which is
          * what the run is for now -- 1080p, ms per step for 1 / 8: 1 GOP 316 / 319, 256 GOPs 354 / 353, 512 GOPs 391 / 382, 4096 GOPs: the
          * kernel alone 106 (macroblock by macroblock) -> 65.  Default: 8 from 256 GOPs on, else 1.  Same buffers: the two kernels never overlap. */
-        { const char *u = getenv("PCAMV_PASS2_UNIT"); const int unit = u && atoi(u) >= 1 && atoi(u) <= 8 ? atoi(u) : (n >= 256 ? 8 : 1);
-          b->fl2 = b->fl; b->fl2.unit = unit; b->fl2.raster = 0; b->fl2.spec = 0; b->fl2.mb_w = (F.mb_w + unit - 1) / unit; b->fl2.n_mb = b->fl2.mb_w * F.mb_h;
-          b->fl2.total = (unsigned)n * (unsigned)b->fl2.n_mb;
-          unsigned qb2 = 0;
-          for (int q = 0; q < 8; q++) { b->fl2.qbase[q] = qb2; b->fl2.qcount[q] = b->fl.qcount[q] / (unsigned)F.n_mb * (unsigned)b->fl2.n_mb; qb2 += b->fl2.qcount[q]; }
-          b->fl2.dep = (int *)(b->d_flow + FLOW_CTR_WORDS + b->fl2.total); }
-        if ((size_t)waves > b->fl2.total) waves = (long)b->fl2.total;
-        b->flow2_waves = (int)waves;
+        const int unit = env_int("PCAMV_PASS2_UNIT", 1, 8, n >= 256 ? 8 : 1);
+        FlowDev &fl2 = b->fl2;      /* the analysis' queues on the coarser grid */
+        fl2 = fl; fl2.unit = unit; fl2.raster = 0; fl2.spec = 0; fl2.mb_w = (F.mb_w + unit - 1) / unit; fl2.n_mb = fl2.mb_w * F.mb_h;
+        fl2.total = (unsigned)n * (unsigned)fl2.n_mb;
+        flow_split_queues(fl2, n);
+        fl2.dep = (int *)(b->d_flow + FLOW_CTR_WORDS + fl2.total);
+        if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_pass2_deblock_flow, 64, 0);
+        b->flow2_waves = flow_wave_count(per_cu, n_cu, fl2.total);
         if (e == hipSuccess) e = hipMemset(b->d_flow, 0, FLOW_CTR_WORDS * sizeof(unsigned));
     }
     if (e != hipSuccess) { pcamv_gpu_batch_destroy(b); return PCAMV_EHIP; }
+    /* the contexts learn of the batch */
     for (int i = 0; i < n; i++) if (ctxs[i]->n_member >= 16) { pcamv_gpu_batch_destroy(b); return PCAMV_EINVAL; }
     for (int i = 0; i < n; i++) ctxs[i]->member_of[ctxs[i]->n_member++] = b;
     for (int i = 0; i < n; i++)         /* the kernel instance with --me tesa compiled in exists for the dataflow schedule only */
@@ -283,16 +344,16 @@ extern "C" int pcamv_gpu_fetch_recon(pcamv_ctx_t *c, uint8_t *const planes[3])
     if (!c || !planes) return PCAMV_EINVAL;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipDeviceSynchronize());
-    if (c->last) { int rc = flow_check(c->last); if (rc) return fail(c, rc, "%s", c->last->err); }
+    TRY(on_behalf(c, c->last, flow_check(c->last)));
     const size_t ysz = (size_t)c->F.w * c->F.h;
     for (int i = 0; i < 3; i++)
-        if (planes[i]) HIPCHK(c, hipMemcpy(planes[i], c->d_rec[i], i ? ysz / 4 : ysz, hipMemcpyDeviceToHost));
+        if (planes[i]) HIPCHK(c, hipMemcpy(planes[i], c->F.rec[i], i ? ysz / 4 : ysz, hipMemcpyDeviceToHost));
     return 0;
 }
 extern "C" int pcamv_gpu_recon_device(pcamv_ctx_t *c, void *planes[3])
 {
     if (!c || !planes) return PCAMV_EINVAL;
-    for (int i = 0; i < 3; i++) planes[i] = c->d_rec[i];
+    for (int i = 0; i < 3; i++) planes[i] = c->F.rec[i];
     return 0;
 }
 static const char *dominant_kernel(const pcamv_batch *b)
@@ -303,18 +364,23 @@ static const char *dominant_kernel(const pcamv_batch *b)
     return "k_analyse_flow";
 }
 extern "C" const char *pcamv_gpu_batch_dominant_kernel(const pcamv_batch_t *b) { return dominant_kernel(b); }
+static const char *kt_name(const pcamv_batch *b, int k)      /* what pcamv_gpu_batch_kernel_time knows timer k by */
+{
+    static const char *const small[KT_N] = {NULL, "k_embed_prepare", "k_extract_prepare", "k_extract_bits", "k_payload_check"};
+    return k == KT_ANALYSE ? dominant_kernel(b) : small[k];
+}
 extern "C" int pcamv_gpu_batch_copy_results_async(pcamv_batch_t *b, void *dst_mb, size_t mb_stride, void *dst_flip, size_t flip_stride, void *stream)
 {
     if (!b || !dst_mb) return PCAMV_EINVAL;
-    HIPCHKB(b, hipSetDevice(b->device));
+    HIPCHK(b, hipSetDevice(b->device));
     hipStream_t st = (hipStream_t)stream;
-    for (int i = 0; i < b->n; i++) if (!b->ctx[i]) return bfail(b, PCAMV_EINVAL, "context %d of the batch was closed", i);
+    TRY(batch_live(b));
     for (int i = 0; i < b->n; i++) {
         pcamv_ctx *c = b->ctx[i];
         const size_t nb = (size_t)c->F.n_mb * sizeof(pcamv_mb_t);
         if (mb_stride < nb || (dst_flip && flip_stride < (size_t)c->cap)) return PCAMV_EINVAL;
-        HIPCHKB(b, hipMemcpyAsync((char *)dst_mb + (size_t)i * mb_stride, c->d_rec_mb, nb, hipMemcpyDefault, st));
-        if (dst_flip) HIPCHKB(b, hipMemcpyAsync((char *)dst_flip + (size_t)i * flip_stride, c->d_flip, (size_t)c->cap, hipMemcpyDefault, st));
+        HIPCHK(b, hipMemcpyAsync((char *)dst_mb + (size_t)i * mb_stride, c->F.rec_mb, nb, hipMemcpyDefault, st));
+        if (dst_flip) HIPCHK(b, hipMemcpyAsync((char *)dst_flip + (size_t)i * flip_stride, c->d_flip, (size_t)c->cap, hipMemcpyDefault, st));
     }
     return 0;
 }
@@ -349,65 +415,51 @@ static int open_impl(pcamv_ctx *c, const pcamv_params_t *p, int device)
     HIPCHK(c, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     FrameDev &F = c->F;
     pcamv_frame_set_params(&F, p);
-    const size_t ysz = (size_t)F.w * F.h, lsz = (size_t)F.plane_size, csz = (size_t)F.cstride * F.clines;
+    const size_t ysz = (size_t)F.w * F.h, lsz = (size_t)F.plane_size, csz = (size_t)F.cstride * F.clines, n_mb = (size_t)F.n_mb;
+    EmbedDev &E = c->E;
     for (int i = 0; i < 3; i++) {
-        HIPCHK(c, dalloc(&c->d_fenc[i], i ? ysz / 4 : ysz));
-        HIPCHK(c, dalloc(&c->d_raw[i], i ? ysz / 4 : ysz));
-        HIPCHK(c, dalloc(&c->d_rec[i], i ? ysz / 4 : ysz));
+        TRY(ctx_alloc(c, &c->d_fenc[i], i ? ysz / 4 : ysz));
+        TRY(ctx_alloc(c, &c->d_raw[i], i ? ysz / 4 : ysz));
+        TRY(ctx_alloc(c, &F.rec[i], i ? ysz / 4 : ysz));
+        F.fenc[i] = c->d_fenc[i]; F.raw[i] = c->d_raw[i];
     }
-    HIPCHK(c, dalloc(&c->d_luma, 4 * lsz + 64));
-    HIPCHK(c, hipMemset(c->d_luma, 0, 4 * lsz + 64));      /* the repeated columns of each plane's last strip are never written */
-    if (F.me_method == PCAMV_ME_ESA || F.me_method == PCAMV_ME_TESA) HIPCHK(c, dalloc(&c->d_luma_raster, (size_t)F.stride * F.lines + 64));
-    HIPCHK(c, dalloc(&c->d_chroma[0], 2 * (csz + 64))); c->d_chroma[1] = c->d_chroma[0] + csz + 64;   /* one allocation: 32-bit offsets reach both */
+    TRY(ctx_alloc(c, &F.luma_base, 4 * lsz + 64, 0));      /* the repeated columns of each plane's last strip are never written */
+    if (F.me_method == PCAMV_ME_ESA || F.me_method == PCAMV_ME_TESA) TRY(ctx_alloc(c, &F.luma_raster, (size_t)F.stride * F.lines + 64));
+    TRY(ctx_alloc(c, &F.chroma_base[0], 2 * (csz + 64))); F.chroma_base[1] = F.chroma_base[0] + csz + 64;   /* one allocation: 32-bit offsets reach both */
     F.cplane_size = (long long)(csz + 64);
-    HIPCHK(c, dalloc(&c->d_mb_type, (size_t)F.n_mb)); HIPCHK(c, dalloc(&c->d_ref8, (size_t)F.n_mb * 4)); HIPCHK(c, dalloc(&c->d_prev_ref, (size_t)F.n_mb * 4));
-    HIPCHK(c, dalloc(&c->d_mv, (size_t)F.n_mb * 32)); HIPCHK(c, dalloc(&c->d_prev_mv, (size_t)F.n_mb * 32));
-    HIPCHK(c, dalloc(&c->d_mv_b, (size_t)F.n_mb * 32)); HIPCHK(c, dalloc(&c->d_ref8_b, (size_t)F.n_mb * 4));
-    HIPCHK(c, hipMemset(c->d_mv_b, 0, (size_t)F.n_mb * 64)); HIPCHK(c, hipMemset(c->d_ref8_b, 0xff, (size_t)F.n_mb * 4));
-    HIPCHK(c, dalloc(&c->d_mvr, (size_t)F.n_mb * 2)); HIPCHK(c, dalloc(&c->d_mvp_aux, (size_t)F.n_mb * 32));
-    HIPCHK(c, dalloc(&c->d_rec_mb, (size_t)F.n_mb));
-    HIPCHK(c, hipMemset(c->d_rec_mb, 0, (size_t)F.n_mb * sizeof(pcamv_mb_t)));
-    HIPCHK(c, hipMemset(c->d_mv, 0, (size_t)F.n_mb * 64)); HIPCHK(c, hipMemset(c->d_mvr, 0, (size_t)F.n_mb * 4));
-    HIPCHK(c, hipMemset(c->d_mvp_aux, 0, (size_t)F.n_mb * 64));
+    for (int k = 0; k < 2; k++) F.chroma[k] = F.chroma_base[k] + (size_t)F.cstride * PCAMV_CPAD + PCAMV_CPAD;
+    TRY(ctx_alloc(c, &F.mb_type, n_mb)); TRY(ctx_alloc(c, &c->d_ref8, n_mb * 4)); TRY(ctx_alloc(c, &c->d_prev_ref, n_mb * 4));
+    TRY(ctx_alloc(c, &c->d_mv, n_mb * 32, 0)); TRY(ctx_alloc(c, &c->d_prev_mv, n_mb * 32));
+    TRY(ctx_alloc(c, &c->d_mv_b, n_mb * 32, 0)); TRY(ctx_alloc(c, &c->d_ref8_b, n_mb * 4, 0xff));
+    TRY(ctx_alloc(c, &F.mvr, n_mb * 2, 0)); TRY(ctx_alloc(c, &F.mvp_aux, n_mb * 32, 0));
+    TRY(ctx_alloc(c, &F.rec_mb, n_mb, 0));
+    F.mv = c->d_mv; F.ref8 = c->d_ref8; F.prev_mv = c->d_prev_mv; F.prev_ref = c->d_prev_ref; F.have_prev = 0;
     c->cap = 16 * F.n_mb;
-    HIPCHK(c, dalloc(&c->d_cover, (size_t)c->cap)); HIPCHK(c, dalloc(&c->d_stego, (size_t)c->cap)); HIPCHK(c, dalloc(&c->d_message, (size_t)c->cap));
-    HIPCHK(c, dalloc(&c->d_user_msg, (size_t)c->cap)); HIPCHK(c, dalloc(&c->d_colinfo, (size_t)c->cap));
-    HIPCHK(c, dalloc(&c->d_rho, (size_t)c->cap)); HIPCHK(c, dalloc(&c->d_flip, (size_t)c->cap));
-    HIPCHK(c, dalloc(&c->d_hdr, 8)); HIPCHK(c, dalloc(&c->d_rnd, 40)); HIPCHK(c, dalloc(&c->d_cols, 2 * STC_MAXW + 8)); HIPCHK(c, dalloc(&c->d_lcg, 1));
-    HIPCHK(c, dalloc(&c->d_path, (size_t)c->cap * 32));
-    HIPCHK(c, dalloc(&c->d_nnz, (size_t)F.n_mb)); HIPCHK(c, dalloc(&c->d_car_base, (size_t)F.n_mb)); HIPCHK(c, dalloc(&c->d_flip_user, (size_t)c->cap));
-    HIPCHK(c, dalloc(&c->d_mbflip, (size_t)F.n_mb)); HIPCHK(c, hipMemset(c->d_mbflip, 1, (size_t)F.n_mb));
-    HIPCHK(c, hipMemset(c->d_nnz, 0, (size_t)F.n_mb * 2)); HIPCHK(c, hipMemset(c->d_car_base, 0, (size_t)F.n_mb * 4));
-    HIPCHK(c, hipMemset(c->d_hdr, 0, 8 * sizeof(int)));
+    const size_t cap = (size_t)c->cap;
+    TRY(ctx_alloc(c, &E.cover, cap)); TRY(ctx_alloc(c, &E.stego, cap)); TRY(ctx_alloc(c, &E.message, cap));
+    TRY(ctx_alloc(c, &c->d_user_msg, cap)); TRY(ctx_alloc(c, &E.colinfo, cap));
+    TRY(ctx_alloc(c, &E.rho, cap)); TRY(ctx_alloc(c, &c->d_flip, cap));
+    TRY(ctx_alloc(c, &E.hdr, 8, 0)); TRY(ctx_alloc(c, &E.rnd, 40)); TRY(ctx_alloc(c, &E.cols, 2 * STC_MAXW + 8)); TRY(ctx_alloc(c, &E.lcg, 1));
+    TRY(ctx_alloc(c, &E.path, cap * 32));
+    TRY(ctx_alloc(c, &F.nnz, n_mb, 0)); TRY(ctx_alloc(c, &E.car_base, n_mb, 0)); TRY(ctx_alloc(c, &c->d_flip_user, cap));
+    TRY(ctx_alloc(c, &c->d_mbflip, n_mb, 1));
     if (F.b_mbrd) {
-        HIPCHK(c, dalloc(&c->d_nb_nz, (size_t)F.n_mb * 16)); HIPCHK(c, dalloc(&c->d_nb_cbp, (size_t)F.n_mb)); HIPCHK(c, dalloc(&c->d_nb_mvd, (size_t)F.n_mb * 16));
-        HIPCHK(c, dalloc(&c->d_cabac, PCAMV_CHAIN_BYTES)); HIPCHK(c, dalloc(&c->d_cabac_tab, 256));
-        HIPCHK(c, hipMemset(c->d_nb_nz, 0, (size_t)F.n_mb * 16)); HIPCHK(c, hipMemset(c->d_nb_cbp, 0, (size_t)F.n_mb * 2)); HIPCHK(c, hipMemset(c->d_nb_mvd, 0, (size_t)F.n_mb * 32));
-        HIPCHK(c, hipMemset(c->d_cabac, 0, PCAMV_CHAIN_BYTES));
+        uint32_t *d_tab;
+        TRY(ctx_alloc(c, &F.nb_nz, n_mb * 16, 0)); TRY(ctx_alloc(c, &F.nb_cbp, n_mb, 0)); TRY(ctx_alloc(c, &F.nb_mvd, n_mb * 16, 0));
+        TRY(ctx_alloc(c, &F.cabac, PCAMV_CHAIN_BYTES, 0)); TRY(ctx_alloc(c, &d_tab, 256));
         uint32_t tab[256]; pcamv_build_cabac_tab(tab);
-        HIPCHK(c, hipMemcpy(c->d_cabac_tab, tab, sizeof(tab), hipMemcpyHostToDevice));
-        F.nb_nz = c->d_nb_nz; F.nb_cbp = c->d_nb_cbp; F.nb_mvd = c->d_nb_mvd; F.cabac = c->d_cabac; F.cabac_tab = c->d_cabac_tab;
+        HIPCHK(c, hipMemcpy(d_tab, tab, sizeof(tab), hipMemcpyHostToDevice));
+        F.cabac_tab = d_tab;
     }
     int rnd[40]; memset(rnd, 0, sizeof(rnd)); glibc_srand_state(rnd, 1);
-    HIPCHK(c, hipMemcpy(c->d_rnd, rnd, sizeof(rnd), hipMemcpyHostToDevice));
-    long long lcg = 1; HIPCHK(c, hipMemcpy(c->d_lcg, &lcg, sizeof(lcg), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(E.rnd, rnd, sizeof(rnd), hipMemcpyHostToDevice));
+    long long lcg = 1; HIPCHK(c, hipMemcpy(E.lcg, &lcg, sizeof(lcg), hipMemcpyHostToDevice));
     const long long pstate[PST_WORDS] = {0, 0, 0, 1};       /* cursors at 0; the receiver's column generator starts like the sender's */
-    HIPCHK(c, dalloc(&c->d_pstate, PST_WORDS)); HIPCHK(c, hipMemcpy(c->d_pstate, pstate, sizeof(pstate), hipMemcpyHostToDevice));
-    for (int i = 0; i < 3; i++) { F.fenc[i] = c->d_fenc[i]; F.rec[i] = c->d_rec[i]; F.raw[i] = c->d_raw[i]; }
-    F.luma_base = c->d_luma; F.chroma_base[0] = c->d_chroma[0]; F.chroma_base[1] = c->d_chroma[1];
-    F.luma_raster = c->d_luma_raster;
-    for (int k = 0; k < 2; k++) F.chroma[k] = c->d_chroma[k] + (size_t)F.cstride * PCAMV_CPAD + PCAMV_CPAD;
-    F.mb_type = c->d_mb_type; F.mv = c->d_mv; F.ref8 = c->d_ref8; F.mvr = c->d_mvr;
-    F.prev_mv = c->d_prev_mv; F.prev_ref = c->d_prev_ref; F.have_prev = 0;
-    F.rec_mb = c->d_rec_mb; F.mvp_aux = c->d_mvp_aux;
-    F.nnz = c->d_nnz; F.car_base = c->d_car_base; F.flip = c->d_flip; F.mbflip = c->d_mbflip;
-    EmbedDev &E = c->E;
-    E.mbs = c->d_rec_mb; E.n_mb = F.n_mb; E.cover = c->d_cover; E.stego = c->d_stego; E.message = c->d_message; E.rho = c->d_rho;
-    E.mbflip = c->d_mbflip;
-    E.flip = c->d_flip; E.hdr = c->d_hdr; E.cols = c->d_cols; E.path = c->d_path; E.rnd = c->d_rnd;
-    E.lcg = c->d_lcg; E.colinfo = c->d_colinfo; E.cap = c->cap; E.car_base = c->d_car_base; E.user_message = NULL; E.user_message_len = 0; E.emrate = 0;
-    E.payload = NULL; E.payload_bits = 0; E.pstate = c->d_pstate;
-    c->X.n_mb = F.n_mb; c->X.cap = c->cap; c->X.pstate = c->d_pstate;
+    TRY(ctx_alloc(c, &E.pstate, PST_WORDS)); HIPCHK(c, hipMemcpy(E.pstate, pstate, sizeof(pstate), hipMemcpyHostToDevice));
+    F.car_base = E.car_base; F.flip = c->d_flip; F.mbflip = c->d_mbflip;
+    E.mbs = F.rec_mb; E.n_mb = F.n_mb; E.mbflip = c->d_mbflip; E.flip = c->d_flip; E.cap = c->cap;
+    E.user_message = NULL; E.user_message_len = 0; E.emrate = 0; E.payload = NULL; E.payload_bits = 0;
+    c->X.n_mb = F.n_mb; c->X.cap = c->cap; c->X.pstate = E.pstate;
     pcamv_ctx *one[1] = {c};
     return pcamv_gpu_batch_create(one, 1, &c->self);
 }
@@ -422,19 +474,7 @@ extern "C" void pcamv_gpu_close(pcamv_ctx_t *c)
         pcamv_batch *b = c->member_of[k];
         for (int i = 0; i < b->n; i++) if (b->ctx[i] == c) b->ctx[i] = NULL;
     }
-    for (int i = 0; i < 3; i++) { hipFree(c->d_fenc[i]); hipFree(c->d_raw[i]); hipFree(c->d_rec[i]); }
-    hipFree(c->d_luma); hipFree(c->d_luma_raster); hipFree(c->d_chroma[0]);
-    hipFree(c->d_mb_type); hipFree(c->d_ref8); hipFree(c->d_prev_ref); hipFree(c->d_mv); hipFree(c->d_prev_mv); hipFree(c->d_mvr);
-    hipFree(c->d_mvp_aux); hipFree(c->d_rec_mb); hipFree(c->d_mv_b); hipFree(c->d_ref8_b);
-    for (int q = 0; q < 52; q++) if (c->d_cost_mv[q]) hipFree(c->d_cost_mv[q]);
-    hipFree(c->d_cover); hipFree(c->d_stego); hipFree(c->d_message); hipFree(c->d_colinfo); hipFree(c->d_user_msg); hipFree(c->d_rho);
-    hipFree(c->d_flip); hipFree(c->d_hdr); hipFree(c->d_rnd); hipFree(c->d_cols); hipFree(c->d_lcg); hipFree(c->d_path);
-    hipFree(c->d_payload_own); hipFree(c->d_pstate); hipFree(c->d_rx); hipFree(c->d_rx_stego); hipFree(c->d_rx_bits); hipFree(c->d_rx_hdr);
-    hipFree(c->d_rx_cols); hipFree(c->d_rx_mbs);
-    if (c->d_trace) hipFree(c->d_trace);
-    hipFree(c->d_nnz); hipFree(c->d_car_base); hipFree(c->d_flip_user); hipFree(c->d_mbflip);
-    hipFree(c->d_nb_nz); hipFree(c->d_nb_cbp); hipFree(c->d_nb_mvd); hipFree(c->d_cabac); hipFree(c->d_cabac_tab); hipFree(c->d_dbg_hash);
-    for (int q = 0; q < 52; q++) if (c->d_cabac_init[q]) hipFree(c->d_cabac_init[q]);
+    for (int i = 0; i < c->n_owned; i++) hipFree(c->owned[i]);
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
 }
@@ -443,13 +483,11 @@ static int ensure_qp(pcamv_ctx *c, int qp)
 {
     if (qp < 0 || qp > 51) return fail(c, PCAMV_EINVAL, "qp %d out of range", qp);
     if (!c->d_cost_mv[qp]) {
-        int16_t *h = (int16_t *)malloc(PCAMV_COST_MV_LEN * sizeof(int16_t));
+        HostTmp<int16_t> h(PCAMV_COST_MV_LEN);
         if (!h) return fail(c, PCAMV_ENOMEM, "cost table");
         pcamv_build_cost_mv(qp, h);
-        hipError_t e = dalloc(&c->d_cost_mv[qp], (size_t)PCAMV_COST_MV_LEN + 1);      /* + 1: prim_mv_cost fetches the dword that holds an entry */
-        if (e == hipSuccess) e = hipMemcpy(c->d_cost_mv[qp], h, PCAMV_COST_MV_LEN * sizeof(int16_t), hipMemcpyHostToDevice);
-        free(h);
-        if (e != hipSuccess) return fail(c, PCAMV_EHIP, "cost table upload: %s", hipGetErrorString(e));
+        TRY(ctx_alloc(c, &c->d_cost_mv[qp], (size_t)PCAMV_COST_MV_LEN + 1));      /* + 1: prim_mv_cost fetches the dword that holds an entry */
+        HIPCHK(c, hipMemcpy(c->d_cost_mv[qp], h, PCAMV_COST_MV_LEN * sizeof(int16_t), hipMemcpyHostToDevice));
     }
     pcamv_frame_set_qp(&c->F, &c->p, qp);
     c->F.cost_mv = c->d_cost_mv[qp] + PCAMV_COST_MV_CENTRE;
@@ -457,9 +495,8 @@ static int ensure_qp(pcamv_ctx *c, int qp)
         if (!c->d_cabac_init[qp]) {
             uint8_t init[PCAMV_CHAIN_BYTES] = {0};       /* states, then nothing left over from an earlier macroblock */
             pcamv_build_cabac_init(qp, init);
-            hipError_t e = dalloc(&c->d_cabac_init[qp], (size_t)PCAMV_CHAIN_BYTES);
-            if (e == hipSuccess) e = hipMemcpy(c->d_cabac_init[qp], init, PCAMV_CHAIN_BYTES, hipMemcpyHostToDevice);
-            if (e != hipSuccess) return fail(c, PCAMV_EHIP, "context initialisation upload: %s", hipGetErrorString(e));
+            TRY(ctx_alloc(c, &c->d_cabac_init[qp], (size_t)PCAMV_CHAIN_BYTES));
+            HIPCHK(c, hipMemcpy(c->d_cabac_init[qp], init, PCAMV_CHAIN_BYTES, hipMemcpyHostToDevice));
         }
         c->F.cabac_init = c->d_cabac_init[qp];
     }
@@ -470,7 +507,7 @@ extern "C" int pcamv_gpu_debug_state_hash(pcamv_ctx_t *c, int enable)
 {
     if (!c) return PCAMV_EINVAL;
     HIPCHK(c, hipSetDevice(c->device));
-    if (enable && !c->d_dbg_hash) { HIPCHK(c, dalloc(&c->d_dbg_hash, (size_t)c->F.n_mb)); HIPCHK(c, hipMemset(c->d_dbg_hash, 0, (size_t)c->F.n_mb * 4)); }
+    if (enable && !c->d_dbg_hash) TRY(ctx_alloc(c, &c->d_dbg_hash, (size_t)c->F.n_mb, 0));
     c->F.dbg_hash = enable ? c->d_dbg_hash : NULL;
     return 0;
 }
@@ -507,14 +544,14 @@ static int ring_take(pcamv_batch *b, DescRing &r, int *slot_out)
 {
     const int slot = r.head;
     r.head = (r.head + 1) % NRING;
-    if (r.used[slot]) HIPCHKB(b, hipEventSynchronize(r.done[slot]));
+    if (r.used[slot]) HIPCHK(b, hipEventSynchronize(r.done[slot]));
     *slot_out = slot;
     return 0;
 }
 /* ... and what was queued on `st` so far is what reads them */
 static int ring_release(pcamv_batch *b, DescRing &r, int slot, hipStream_t st)
 {
-    HIPCHKB(b, hipEventRecord(r.done[slot], st));
+    HIPCHK(b, hipEventRecord(r.done[slot], st));
     r.used[slot] = 1;
     return 0;
 }
@@ -522,11 +559,11 @@ static int ring_release(pcamv_batch *b, DescRing &r, int slot, hipStream_t st)
 static int batch_push_descs(pcamv_batch *b, hipStream_t st, const FrameDev **dF, const EmbedDev **dE, int *slot_out)
 {
     int slot;
-    { const int rc = ring_take(b, b->ring, &slot); if (rc) return rc; }
+    TRY(ring_take(b, b->ring, &slot));
     FrameDev *hF = b->h_F + (size_t)slot * b->n; EmbedDev *hE = b->h_E + (size_t)slot * b->n;
     for (int i = 0; i < b->n; i++) { hF[i] = b->ctx[i]->F; hE[i] = b->ctx[i]->E; }
-    HIPCHKB(b, hipMemcpyAsync(b->d_F + (size_t)slot * b->n, hF, sizeof(FrameDev) * b->n, hipMemcpyHostToDevice, st));
-    HIPCHKB(b, hipMemcpyAsync(b->d_E + (size_t)slot * b->n, hE, sizeof(EmbedDev) * b->n, hipMemcpyHostToDevice, st));
+    HIPCHK(b, hipMemcpyAsync(b->d_F + (size_t)slot * b->n, hF, sizeof(FrameDev) * b->n, hipMemcpyHostToDevice, st));
+    HIPCHK(b, hipMemcpyAsync(b->d_E + (size_t)slot * b->n, hE, sizeof(EmbedDev) * b->n, hipMemcpyHostToDevice, st));
     *dF = b->d_F + (size_t)slot * b->n; *dE = b->d_E + (size_t)slot * b->n; *slot_out = slot;
     return 0;
 }
@@ -543,14 +580,13 @@ template <class Launch> static void diag_launch(int n_diag, const FrameDev &F, L
     }
 }
 
-/* hipEvents around a launch of one of the smaller kernels (pcamv_gpu_batch_kernel_time reports them under their names); the events
- * of a timer are made the first time its kernel is launched through the batch */
+/* the events of timer k around what is queued on `st` between kt_begin and kt_end; a timer whose events cannot be made stays off */
 static int kt_begin(pcamv_batch *b, int k, hipStream_t st)
 {
-    pcamv_batch::KTimer &T = b->kt[k];
+    KTimer &T = b->kt[k];
     if (T.made < 0) return -1;
     if (!T.made) {
-        for (int i = 0; i < NKEV; i++) if (hipEventCreate(&T.e0[i]) != hipSuccess || hipEventCreate(&T.e1[i]) != hipSuccess) { T.made = -1; return -1; }
+        for (int i = 0; i < T.cap; i++) if (hipEventCreate(&T.e0[i]) != hipSuccess || hipEventCreate(&T.e1[i]) != hipSuccess) { T.made = -1; return -1; }
         T.made = 1;
     }
     hipEventRecord(T.e0[T.head], st);
@@ -558,60 +594,65 @@ static int kt_begin(pcamv_batch *b, int k, hipStream_t st)
 }
 static void kt_end(pcamv_batch *b, int k, int ev, hipStream_t st)
 {
-    pcamv_batch::KTimer &T = b->kt[k];
+    KTimer &T = b->kt[k];
     if (ev < 0) return;
     hipEventRecord(T.e1[ev], st);
-    T.head = (T.head + 1) % NKEV; if (T.n < NKEV) T.n++;
+    T.head = (T.head + 1) % T.cap; if (T.n < T.cap) T.n++;
 }
 
-/* what: bit0 plane production, bit1 analysis (search+RCA+encode), bit2 embedding */
-static int batch_launch(pcamv_batch *b, int what, hipStream_t st, int timed)
+/* the second pass takes the frame's reconstruction as it stands: the first pass' own, once (then it has been filtered in place) */
+static void pass2_takes_rec(pcamv_ctx *c)
 {
-    HIPCHKB(b, hipSetDevice(b->device));
+    c->F.rec_is_pass1 = c->rec_pristine;
+    c->rec_pristine = 0;
+}
+
+/* the stages `what` (ST_*) of one step of every context of the batch, queued on `st` */
+static int batch_launch(pcamv_batch *b, int what, hipStream_t st)
+{
+    HIPCHK(b, hipSetDevice(b->device));
+    TRY(batch_live(b));
     for (int i = 0; i < b->n; i++) {
         pcamv_ctx *c = b->ctx[i];
-        if (!c) return bfail(b, PCAMV_EINVAL, "context %d of the batch was closed", i);
-        if ((what & 2) && c->prev_internal) {      /* this frame writes the field the last analysis did not write, and reads that one */
+        if ((what & ST_ANALYSE) && c->prev_internal) {      /* this frame writes the field the last analysis did not write, and reads that one */
             const int wr = !c->last_field;
             c->F.mv = wr ? c->d_mv_b : c->d_mv; c->F.ref8 = wr ? c->d_ref8_b : c->d_ref8;
             c->F.prev_mv = wr ? c->d_mv : c->d_mv_b; c->F.prev_ref = wr ? c->d_ref8 : c->d_ref8_b;
         }
-        if (what & 2) c->last_field = c->F.mv == c->d_mv_b;
-        if (what & 2) c->rec_pristine = 1;         /* the analysis leaves the first pass' reconstruction + non-zero flags in rec / nnz ... */
-        c->F.rec_is_pass1 = (what & 8) ? c->rec_pristine : 0;
-        if (what & 8) c->rec_pristine = 0;         /* ... until a second pass has filtered the picture in place */
+        if (what & ST_ANALYSE) c->last_field = c->F.mv == c->d_mv_b;
+        if (what & ST_ANALYSE) c->rec_pristine = 1;         /* the analysis leaves the first pass' reconstruction + non-zero flags in rec / nnz ... */
+        if (what & ST_PASS2) pass2_takes_rec(c);            /* ... until a second pass has filtered the picture in place */
+        else c->F.rec_is_pass1 = 0;
     }
     const FrameDev *dF; const EmbedDev *dE; int slot;
-    int rc = batch_push_descs(b, st, &dF, &dE, &slot);
-    if (rc) return rc;
+    TRY(batch_push_descs(b, st, &dF, &dE, &slot));
     const FrameDev &F = b->ctx[0]->F;
     const unsigned G = (unsigned)b->n;
-    if (what & 1) {
+    if (what & ST_PLANES) {
         dim3 g((F.stride / 4 + HP_THREADS - 1) / HP_THREADS, (F.lines + HP_ROWS - 1) / HP_ROWS, G);
         hipLaunchKernelGGL(k_hpel, g, dim3(HP_THREADS), 0, st, dF);
         dim3 gc((F.cstride / 4 + 255) / 256, F.clines, 2 * G);
         hipLaunchKernelGGL(k_chroma_pad, gc, dim3(256), 0, st, dF);
     }
-    if (what & 2) {
-        int ev = -1;
-        if (timed && !b->sched_flow) { ev = b->ev_head; hipEventRecord(b->ev0[ev], st); }
+    if (what & ST_ANALYSE) {
         for (int i = 0; i < b->n; i++) b->ctx[i]->last = b;
-        if (b->sched_flow) {
+        if (b->sched_flow) {        /* timed: the analysis kernel without k_flow_init */
             hipLaunchKernelGGL(k_flow_init, dim3((b->fl.total + 255) / 256), dim3(256), 0, st, b->fl);
-            if (timed) { ev = b->ev_head; hipEventRecord(b->ev0[ev], st); }
+            const int ev = kt_begin(b, KT_ANALYSE, st);
             if (b->b_mbrd) b->rd->launch((unsigned)b->flow_waves, st, dF, b->fl);
             else if (b->b_tesa) pcamv_launch_flow_tesa((unsigned)b->flow_waves, st, dF, b->fl);
             else hipLaunchKernelGGL(k_analyse_flow, dim3(b->flow_waves), dim3(64), 0, st, dF, b->fl);
-            if (timed) { hipEventRecord(b->ev1[ev], st); b->ev_head = (b->ev_head + 1) % NEV; if (b->ev_n < NEV) b->ev_n++; }
-        } else {
+            kt_end(b, KT_ANALYSE, ev, st);
+        } else {                    /* timed: the n_diag launches of the search (one pair of events, KTimer::weight), without k_rca / k_encode */
+            const int ev = kt_begin(b, KT_ANALYSE, st);
             diag_launch(b->n_diag, F, [&](int cnt, int d) { hipLaunchKernelGGL(k_search_diag<0>, dim3(cnt, G), dim3(64), 0, st, dF, d); });
-            if (timed) { hipEventRecord(b->ev1[ev], st); b->ev_head = (b->ev_head + 1) % NEV; if (b->ev_n < NEV) b->ev_n++; }
+            kt_end(b, KT_ANALYSE, ev, st);
             hipLaunchKernelGGL(k_rca, dim3(F.n_mb * b->slots_per_mb, G), dim3(64), 0, st, dF, b->slots_per_mb);
             hipLaunchKernelGGL(k_encode, dim3(F.n_mb, G), dim3(64), 0, st, dF);
         }
     }
-    if (what & 4) {
-        const int ev = timed ? kt_begin(b, KT_EMBED_PREPARE, st) : -1;
+    if (what & ST_EMBED) {
+        const int ev = kt_begin(b, KT_EMBED_PREPARE, st);
         hipLaunchKernelGGL(k_embed_prepare, dim3(G), dim3(1024), 0, st, dE);
         kt_end(b, KT_EMBED_PREPARE, ev, st);
         /* 2 trellis states per thread: measured 3.25 / 2.89 / 2.90 ms per 1080p frame for 1 / 2 / 4 */
@@ -622,7 +663,7 @@ static int batch_launch(pcamv_batch *b, int what, hipStream_t st, int timed)
         hipLaunchKernelGGL(k_stc_backward, dim3(G), dim3(64), 0, st, dE);
         hipLaunchKernelGGL(k_mb_flips, dim3((F.n_mb + 255) / 256, G), dim3(256), 0, st, dE);
     }
-    if (what & 8) {      /* pass 2: final MVs -> reconstruction -> loop filter, same dependency as the search */
+    if (what & ST_PASS2) {      /* final MVs -> reconstruction -> loop filter, same dependency as the search */
         if (b->sched_flow) {
             hipLaunchKernelGGL(k_flow_init, dim3((b->fl2.total + 255) / 256), dim3(256), 0, st, b->fl2);
             hipLaunchKernelGGL(k_pass2_deblock_flow, dim3(b->flow2_waves), dim3(64), 0, st, dF, b->fl2);
@@ -631,7 +672,7 @@ static int batch_launch(pcamv_batch *b, int what, hipStream_t st, int timed)
         }
     }
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return bfail(b, PCAMV_EHIP, "kernel launch: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(b, PCAMV_EHIP, "kernel launch: %s", hipGetErrorString(e));
     return ring_release(b, b->ring, slot, st);
 }
 /* after a synchronisation: did the dataflow kernel of the last step give up on a bounded spin? */
@@ -639,19 +680,14 @@ static int flow_check(pcamv_batch *b)
 {
     if (!b || !b->sched_flow) return 0;
     unsigned bad = 0;
-    HIPCHKB(b, hipMemcpy(&bad, b->fl.ctr + FLOW_ERR, sizeof(bad), hipMemcpyDeviceToHost));
+    HIPCHK(b, hipMemcpy(&bad, b->fl.ctr + FLOW_ERR, sizeof(bad), hipMemcpyDeviceToHost));
     if (bad) {
         hipMemset(b->fl.ctr + FLOW_ERR, 0, sizeof(unsigned));
-        return bfail(b, PCAMV_EHIP, "dataflow kernel: queue wait timed out (results of the last step are incomplete)");
+        return fail(b, PCAMV_EHIP, "dataflow kernel: queue wait timed out (results of the last step are incomplete)");
     }
     return 0;
 }
-static int ctx_launch(pcamv_ctx *c, int what)
-{
-    int rc = batch_launch(c->self, what, c->stream, 1);
-    if (rc) { snprintf(c->err, sizeof(c->err), "%s", c->self->err); return rc; }
-    return 0;
-}
+static int ctx_launch(pcamv_ctx *c, int what) { return on_behalf(c, c->self, batch_launch(c->self, what, c->stream)); }
 
 extern "C" int pcamv_gpu_set_ref(pcamv_ctx_t *c, const uint8_t *const plane[3], const int stride[3], const int16_t *prev_mv, const int8_t *prev_ref)
 {
@@ -671,8 +707,7 @@ extern "C" int pcamv_gpu_set_ref(pcamv_ctx_t *c, const uint8_t *const plane[3], 
         HIPCHK(c, hipMemcpy(c->d_prev_mv, prev_mv, (size_t)c->F.n_mb * 64, hipMemcpyHostToDevice));
         HIPCHK(c, hipMemcpy(c->d_prev_ref, prev_ref, (size_t)c->F.n_mb * 4, hipMemcpyHostToDevice));
     }
-    int rc = ctx_launch(c, 1);
-    if (rc) return rc;
+    TRY(ctx_launch(c, ST_PLANES));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -696,15 +731,13 @@ extern "C" int pcamv_gpu_get_ref_planes(pcamv_ctx_t *c, uint8_t *out, int *strid
     HIPCHK(c, hipDeviceSynchronize());
     /* the device keeps the planes in strips (pcamv_common.h); the caller gets x264's raster planes */
     const size_t psz = (size_t)c->F.plane_size;
-    uint8_t *tmp = (uint8_t *)malloc(4 * psz);
+    HostTmp<uint8_t> tmp(4 * psz);
     if (!tmp) return fail(c, PCAMV_EHIP, "out of host memory");
-    hipError_t e = hipMemcpy(tmp, c->d_luma, 4 * psz, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { free(tmp); HIPCHK(c, e); }
+    HIPCHK(c, hipMemcpy(tmp, c->F.luma_base, 4 * psz, hipMemcpyDeviceToHost));
     for (int k = 0; k < 4; k++)
         for (int y = 0; y < c->F.lines; y++)
             for (int x = 0; x < c->F.stride; x++)
                 out[((size_t)k * c->F.lines + y) * c->F.stride + x] = tmp[k * psz + (size_t)y * PCAMV_LROW + x + (size_t)(x / PCAMV_LSW) * c->F.lskip];
-    free(tmp);
     if (stride) *stride = c->F.stride;
     if (lines) *lines = c->F.lines;
     return 0;
@@ -714,16 +747,15 @@ extern "C" int pcamv_gpu_analyse_pframe(pcamv_ctx_t *c, int qp, int embed, pcamv
 {
     if (!c || !out_mb) return PCAMV_EINVAL;
     HIPCHK(c, hipSetDevice(c->device));
-    int rc = ensure_qp(c, qp);
-    if (rc) return rc;
+    TRY(ensure_qp(c, qp));
     c->F.embed = embed;
-    if ((rc = ctx_launch(c, 2))) return rc;
+    TRY(ctx_launch(c, ST_ANALYSE));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if ((rc = flow_check(c->self))) return fail(c, rc, "%s", c->self->err);
-    HIPCHK(c, hipMemcpy(out_mb, c->d_rec_mb, (size_t)c->F.n_mb * sizeof(pcamv_mb_t), hipMemcpyDeviceToHost));
+    TRY(on_behalf(c, c->self, flow_check(c->self)));
+    HIPCHK(c, hipMemcpy(out_mb, c->F.rec_mb, (size_t)c->F.n_mb * sizeof(pcamv_mb_t), hipMemcpyDeviceToHost));
     if (recon)
         for (int i = 0; i < 3; i++)
-            if (recon[i]) HIPCHK(c, hipMemcpy(recon[i], c->d_rec[i], ((size_t)c->F.w * c->F.h) >> (i ? 2 : 0), hipMemcpyDeviceToHost));
+            if (recon[i]) HIPCHK(c, hipMemcpy(recon[i], c->F.rec[i], ((size_t)c->F.w * c->F.h) >> (i ? 2 : 0), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -731,15 +763,15 @@ static int fetch_embed(pcamv_ctx *c, pcamv_embed_t *out)
 {
     int hdr[8];
     HIPCHK(c, hipDeviceSynchronize());
-    HIPCHK(c, hipMemcpy(hdr, c->d_hdr, sizeof(hdr), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(hdr, c->E.hdr, sizeof(hdr), hipMemcpyDeviceToHost));
     out->n = hdr[0]; out->m = hdr[1]; out->stc_ok = hdr[2]; out->num_flip = hdr[3];
     if (out->n < 0 || out->m < 0 || out->n > c->cap) return fail(c, PCAMV_EHIP, "embed header corrupt");
     const int m_copy = out->m < c->cap ? out->m : c->cap;          /* a bits-per-frame rate above the capacity: stc_embed failed (m > n), the message array holds cap bits */
-    if (out->cover && out->n) HIPCHK(c, hipMemcpy(out->cover, c->d_cover, out->n, hipMemcpyDeviceToHost));
-    if (out->rho && out->n) HIPCHK(c, hipMemcpy(out->rho, c->d_rho, (size_t)out->n * 4, hipMemcpyDeviceToHost));
-    if (out->stego && out->n) HIPCHK(c, hipMemcpy(out->stego, c->d_stego, out->n, hipMemcpyDeviceToHost));
+    if (out->cover && out->n) HIPCHK(c, hipMemcpy(out->cover, c->E.cover, out->n, hipMemcpyDeviceToHost));
+    if (out->rho && out->n) HIPCHK(c, hipMemcpy(out->rho, c->E.rho, (size_t)out->n * 4, hipMemcpyDeviceToHost));
+    if (out->stego && out->n) HIPCHK(c, hipMemcpy(out->stego, c->E.stego, out->n, hipMemcpyDeviceToHost));
     if (out->flip && out->n) HIPCHK(c, hipMemcpy(out->flip, c->d_flip, out->n, hipMemcpyDeviceToHost));
-    if (out->message && m_copy) HIPCHK(c, hipMemcpy(out->message, c->d_message, m_copy, hipMemcpyDeviceToHost));
+    if (out->message && m_copy) HIPCHK(c, hipMemcpy(out->message, c->E.message, m_copy, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -753,9 +785,29 @@ extern "C" int pcamv_gpu_embed_pframe(pcamv_ctx_t *c, float emrate, const uint8_
         c->E.user_message = c->d_user_msg; c->E.user_message_len = message_len;
     } else { c->E.user_message = NULL; c->E.user_message_len = 0; }
     c->E.emrate = emrate;
-    int rc = ctx_launch(c, 4);
-    if (rc) return rc;
+    TRY(ctx_launch(c, ST_EMBED));
     return fetch_embed(c, out);
+}
+
+/* the carrier MVs of a record in embedding order (encoder.c:1566-1647; the device's carrier_slots): their slots in mv[], and how many */
+static int mb_carrier_slots(const pcamv_mb_t *mb, int slots[16])
+{
+    int n = 0;
+    if (!mb->used) return 0;
+    if (mb->i_type == PCAMV_P_8x8) {
+        for (int i = 0; i < 4; i++)
+            switch (mb->i_sub_partition[i]) {
+            case PCAMV_D_L0_8x8: slots[n++] = i * 4; break;
+            case PCAMV_D_L0_4x8: slots[n++] = i * 4; slots[n++] = i * 4 + 1; break;
+            case PCAMV_D_L0_8x4: slots[n++] = i * 4; slots[n++] = i * 4 + 2; break;
+            default: for (int j = 0; j < 4; j++) slots[n++] = i * 4 + j; break;
+            }
+    } else if (mb->i_type == PCAMV_P_L0) {
+        slots[n++] = 0;
+        if (mb->i_partition == PCAMV_D_8x16) slots[n++] = 4;
+        else if (mb->i_partition == PCAMV_D_16x8) slots[n++] = 8;
+    }
+    return n;
 }
 
 /* Pass 2 of the frame last analysed: final MVs (the record with mv_stego where the flip map says so; the flip
@@ -767,39 +819,30 @@ extern "C" int pcamv_gpu_pass2_pframe(pcamv_ctx_t *c, const uint8_t *flips, int 
 {
     if (!c) return PCAMV_EINVAL;
     HIPCHK(c, hipSetDevice(c->device));
+    const size_t n_mb = (size_t)c->F.n_mb;
     if (flips) {
         if (n_flips < 0 || n_flips > c->cap) return fail(c, PCAMV_EINVAL, "n_flips");
         HIPCHK(c, hipMemset(c->d_flip_user, 0, (size_t)c->cap));
         if (n_flips) HIPCHK(c, hipMemcpy(c->d_flip_user, flips, n_flips, hipMemcpyHostToDevice));
         c->F.flip = c->d_flip_user; c->F.mbflip = nullptr;          /* a caller's map: the per-macroblock summary belongs to the embedding stage's own */
         /* carrier index of every macroblock from the record (the embedding stage may not have run) */
-        pcamv_mb_t *h = (pcamv_mb_t *)malloc((size_t)c->F.n_mb * sizeof(pcamv_mb_t));
-        int *base = (int *)malloc((size_t)c->F.n_mb * sizeof(int));
-        if (!h || !base) { free(h); free(base); return fail(c, PCAMV_ENOMEM, "pass2"); }
-        HIPCHK(c, hipMemcpy(h, c->d_rec_mb, (size_t)c->F.n_mb * sizeof(pcamv_mb_t), hipMemcpyDeviceToHost));
-        int k = 0;
-        for (int xy = 0; xy < c->F.n_mb; xy++) {
-            base[xy] = k;
-            if (!h[xy].used) continue;
-            if (h[xy].i_type == PCAMV_P_8x8)
-                for (int i = 0; i < 4; i++) k += h[xy].i_sub_partition[i] == PCAMV_D_L0_8x8 ? 1 : h[xy].i_sub_partition[i] == PCAMV_D_L0_4x4 ? 4 : 2;
-            else k += h[xy].i_partition == PCAMV_D_16x16 ? 1 : 2;
-        }
-        hipError_t e = hipMemcpy(c->d_car_base, base, (size_t)c->F.n_mb * sizeof(int), hipMemcpyHostToDevice);
-        free(h); free(base);
-        if (e != hipSuccess) return fail(c, PCAMV_EHIP, "pass2: %s", hipGetErrorString(e));
+        HostTmp<pcamv_mb_t> h(n_mb);
+        HostTmp<int> base(n_mb);
+        if (!h || !base) return fail(c, PCAMV_ENOMEM, "pass2");
+        HIPCHK(c, hipMemcpy(h, c->F.rec_mb, n_mb * sizeof(pcamv_mb_t), hipMemcpyDeviceToHost));
+        int k = 0, slots[16];
+        for (size_t xy = 0; xy < n_mb; xy++) { base[xy] = k; k += mb_carrier_slots(&h[xy], slots); }
+        HIPCHK(c, hipMemcpy(c->E.car_base, base, n_mb * sizeof(int), hipMemcpyHostToDevice));
         if (k > n_flips) return fail(c, PCAMV_EINVAL, "flip map has %d entries, the record has %d carriers", n_flips, k);
     } else { c->F.flip = c->d_flip; c->F.mbflip = c->d_mbflip; }
     const size_t ysz = (size_t)c->F.w * c->F.h;
     /* pass-2 reconstruction first (for callers that want it before the loop filter), then the filter */
     pcamv_batch *b = c->self;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->F.rec_is_pass1 = c->rec_pristine;
-    c->rec_pristine = 0;
+    pass2_takes_rec(c);
     {   /* pass 2 only */
         const FrameDev *dF; const EmbedDev *dE; int slot;
-        int rc = batch_push_descs(b, c->stream, &dF, &dE, &slot);
-        if (rc) return fail(c, rc, "%s", b->err);
+        TRY(on_behalf(c, b, batch_push_descs(b, c->stream, &dF, &dE, &slot)));
         const FrameDev &F = c->F;
         for (int pass = 0; pass < 2; pass++) {
             if (pass == 0) diag_launch(b->n_diag, F, [&](int cnt, int d) { hipLaunchKernelGGL(k_pass2_diag, dim3(cnt, 1), dim3(64), 0, c->stream, dF, d); });
@@ -808,17 +851,15 @@ extern "C" int pcamv_gpu_pass2_pframe(pcamv_ctx_t *c, const uint8_t *flips, int 
             uint8_t *const *dst = pass == 0 ? recon : deblocked;
             if (dst)
                 for (int i = 0; i < 3; i++)
-                    if (dst[i]) HIPCHK(c, hipMemcpy(dst[i], c->d_rec[i], i ? ysz / 4 : ysz, hipMemcpyDeviceToHost));
+                    if (dst[i]) HIPCHK(c, hipMemcpy(dst[i], c->F.rec[i], i ? ysz / 4 : ysz, hipMemcpyDeviceToHost));
         }
-        rc = ring_release(b, b->ring, slot, c->stream);
-        if (rc) return fail(c, rc, "%s", b->err);
+        TRY(on_behalf(c, b, ring_release(b, b->ring, slot, c->stream)));
     }
     if (out_final) {
-        HIPCHK(c, hipMemcpy(out_final, c->d_rec_mb, (size_t)c->F.n_mb * sizeof(pcamv_mb_t), hipMemcpyDeviceToHost));
-        int16_t *mv = (int16_t *)malloc((size_t)c->F.n_mb * 64);
+        HIPCHK(c, hipMemcpy(out_final, c->F.rec_mb, n_mb * sizeof(pcamv_mb_t), hipMemcpyDeviceToHost));
+        HostTmp<int16_t> mv(n_mb * 32);
         if (!mv) return fail(c, PCAMV_ENOMEM, "pass2");
-        hipError_t e = hipMemcpy(mv, c->F.mv, (size_t)c->F.n_mb * 64, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { free(mv); return fail(c, PCAMV_EHIP, "pass2: %s", hipGetErrorString(e)); }
+        HIPCHK(c, hipMemcpy(mv, c->F.mv, n_mb * 64, hipMemcpyDeviceToHost));
         const int s4 = 4 * c->F.mb_w;
         static const int bx[16] = {0, 1, 0, 1, 2, 3, 2, 3, 0, 1, 0, 1, 2, 3, 2, 3}, by[16] = {0, 0, 1, 1, 0, 0, 1, 1, 2, 2, 3, 3, 2, 2, 3, 3};
         for (int xy = 0; xy < c->F.n_mb; xy++) {
@@ -828,7 +869,6 @@ extern "C" int pcamv_gpu_pass2_pframe(pcamv_ctx_t *c, const uint8_t *flips, int 
                 out_final[xy].mv[i][0] = s[0]; out_final[xy].mv[i][1] = s[1]; out_final[xy].ref[i] = 0;
             }
         }
-        free(mv);
     }
     return 0;
 }
@@ -837,33 +877,31 @@ extern "C" int pcamv_gpu_pass2_pframe(pcamv_ctx_t *c, const uint8_t *flips, int 
 extern "C" int pcamv_gpu_batch_step(pcamv_batch_t *b, int qp, float emrate, void *stream)
 {
     if (!b) return PCAMV_EINVAL;
-    HIPCHKB(b, hipSetDevice(b->device));
+    HIPCHK(b, hipSetDevice(b->device));
+    TRY(batch_live(b));
     for (int i = 0; i < b->n; i++) {
         pcamv_ctx *c = b->ctx[i];
-        if (!c) return bfail(b, PCAMV_EINVAL, "context %d of the batch was closed", i);
         int rc = ensure_qp(c, qp);
-        if (rc) return bfail(b, rc, "%s", c->err);
-        if (!c->F.raw[0]) return bfail(b, PCAMV_EINVAL, "context %d has no reference", i);
+        if (rc) return fail(b, rc, "%s", c->err);
+        if (!c->F.raw[0]) return fail(b, PCAMV_EINVAL, "context %d has no reference", i);
         c->F.embed = emrate > 0; c->E.emrate = emrate; c->E.user_message = NULL; c->E.user_message_len = 0;
         c->F.flip = c->d_flip; c->F.mbflip = c->d_mbflip;        /* a closed-loop step applies the flip map of its own embedding stage, never a caller's map left by pass2_pframe */
     }
     hipStream_t st = stream ? (hipStream_t)stream : b->ctx[0]->stream;
-    return batch_launch(b, (emrate > 0 ? 7 : 3) | (b->closed_loop ? 8 : 0), st, 1);
+    return batch_launch(b, ST_PLANES | ST_ANALYSE | (emrate > 0 ? ST_EMBED : 0) | (b->closed_loop ? ST_PASS2 : 0), st);
 }
 extern "C" int pcamv_gpu_step_device(pcamv_ctx_t *c, int qp, float emrate, void *stream)
 {
     if (!c) return PCAMV_EINVAL;
-    int rc = pcamv_gpu_batch_step(c->self, qp, emrate, stream ? stream : (void *)c->stream);
-    if (rc) snprintf(c->err, sizeof(c->err), "%s", c->self->err);
-    return rc;
+    return on_behalf(c, c->self, pcamv_gpu_batch_step(c->self, qp, emrate, stream ? stream : (void *)c->stream));
 }
 extern "C" int pcamv_gpu_fetch_results(pcamv_ctx_t *c, pcamv_mb_t *out_mb, pcamv_embed_t *out)
 {
     if (!c) return PCAMV_EINVAL;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipDeviceSynchronize());
-    if (c->last) { int rc = flow_check(c->last); if (rc) return fail(c, rc, "%s", c->last->err); }
-    if (out_mb) HIPCHK(c, hipMemcpy(out_mb, c->d_rec_mb, (size_t)c->F.n_mb * sizeof(pcamv_mb_t), hipMemcpyDeviceToHost));
+    TRY(on_behalf(c, c->last, flow_check(c->last)));
+    if (out_mb) HIPCHK(c, hipMemcpy(out_mb, c->F.rec_mb, (size_t)c->F.n_mb * sizeof(pcamv_mb_t), hipMemcpyDeviceToHost));
     if (out) return fetch_embed(c, out);
     return 0;
 }
@@ -876,7 +914,7 @@ static int payload_attach(pcamv_ctx *c, const uint8_t *d_bytes, int64_t n_bits)
 {
     c->E.payload = n_bits > 0 ? d_bytes : NULL; c->E.payload_bits = n_bits > 0 ? n_bits : 0;
     c->X.payload = c->E.payload; c->X.payload_bits = c->E.payload_bits;
-    HIPCHK(c, hipMemset(c->d_pstate + PST_TX, 0, sizeof(long long)));
+    HIPCHK(c, hipMemset(c->E.pstate + PST_TX, 0, sizeof(long long)));
     return 0;
 }
 extern "C" int pcamv_gpu_set_payload(pcamv_ctx_t *c, const uint8_t *bytes, int64_t n_bits)
@@ -886,8 +924,8 @@ extern "C" int pcamv_gpu_set_payload(pcamv_ctx_t *c, const uint8_t *bytes, int64
     HIPCHK(c, hipDeviceSynchronize());          /* frames in flight still read the payload attached so far */
     const size_t nb = bytes ? (size_t)((n_bits + 7) >> 3) : 0;
     if (nb > c->payload_own_bytes) {
-        hipFree(c->d_payload_own); c->d_payload_own = NULL; c->payload_own_bytes = 0;
-        HIPCHK(c, dalloc(&c->d_payload_own, nb));
+        ctx_free(c, &c->d_payload_own); c->payload_own_bytes = 0;
+        TRY(ctx_alloc(c, &c->d_payload_own, nb));
         c->payload_own_bytes = nb;
     }
     if (nb) HIPCHK(c, hipMemcpy(c->d_payload_own, bytes, nb, hipMemcpyHostToDevice));
@@ -904,10 +942,10 @@ extern "C" int pcamv_gpu_set_payload_device(pcamv_ctx_t *c, const void *d_bytes,
 static int rx_check(pcamv_ctx *c, long long *pstate_out)
 {
     long long st[PST_WORDS];
-    HIPCHK(c, hipMemcpy(st, c->d_pstate, sizeof(st), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(st, c->E.pstate, sizeof(st), hipMemcpyDeviceToHost));
     if (pstate_out) memcpy(pstate_out, st, sizeof(st));
     if (st[PST_OVERRUN]) {
-        hipMemset(c->d_pstate + PST_OVERRUN, 0, sizeof(long long));
+        hipMemset(c->E.pstate + PST_OVERRUN, 0, sizeof(long long));
         return fail(c, PCAMV_ENOMEM, "received stream: %lld bits extracted, %lld reserved (the bits beyond were dropped)", st[PST_RX], c->X.rx_cap_bits);
     }
     return 0;
@@ -918,7 +956,7 @@ extern "C" int pcamv_gpu_payload_tell(pcamv_ctx_t *c, int64_t *consumed_bits, in
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipDeviceSynchronize());
     long long tx = 0;
-    HIPCHK(c, hipMemcpy(&tx, c->d_pstate + PST_TX, sizeof(tx), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&tx, c->E.pstate + PST_TX, sizeof(tx), hipMemcpyDeviceToHost));
     if (consumed_bits) *consumed_bits = tx;
     if (payload_bits) *payload_bits = c->E.payload_bits;
     return 0;
@@ -928,11 +966,9 @@ extern "C" int pcamv_gpu_payload_tell(pcamv_ctx_t *c, int64_t *consumed_bits, in
  * receiver's column generator at its initial state. */
 static int rx_scratch(pcamv_ctx *c)
 {
-    if (c->d_rx_stego) return 0;
-    HIPCHK(c, dalloc(&c->d_rx_stego, (size_t)c->cap)); HIPCHK(c, dalloc(&c->d_rx_bits, (size_t)c->cap));
-    HIPCHK(c, dalloc(&c->d_rx_hdr, 8)); HIPCHK(c, dalloc(&c->d_rx_cols, 2 * STC_MAXW));
-    HIPCHK(c, hipMemset(c->d_rx_hdr, 0, 8 * sizeof(int)));
-    c->X.stego = c->d_rx_stego; c->X.hdr = c->d_rx_hdr; c->X.cols = c->d_rx_cols;
+    if (c->X.stego) return 0;
+    TRY(ctx_alloc(c, &c->X.stego, (size_t)c->cap)); TRY(ctx_alloc(c, &c->d_rx_bits, (size_t)c->cap));
+    TRY(ctx_alloc(c, &c->X.hdr, 8, 0)); TRY(ctx_alloc(c, &c->X.cols, 2 * STC_MAXW));
     return 0;
 }
 extern "C" int pcamv_gpu_rx_reset(pcamv_ctx_t *c)
@@ -941,7 +977,7 @@ extern "C" int pcamv_gpu_rx_reset(pcamv_ctx_t *c)
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipDeviceSynchronize());
     const long long st[3] = {0, 0, 1};          /* PST_RX, PST_OVERRUN, PST_RX_LCG */
-    HIPCHK(c, hipMemcpy(c->d_pstate + PST_RX, st, sizeof(st), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->E.pstate + PST_RX, st, sizeof(st), hipMemcpyHostToDevice));
     if (c->d_rx) HIPCHK(c, hipMemset(c->d_rx, 0, (size_t)((c->X.rx_cap_bits + 31) >> 5) * 4));
     return 0;
 }
@@ -950,11 +986,10 @@ extern "C" int pcamv_gpu_rx_reserve(pcamv_ctx_t *c, int64_t n_bits)
     if (!c || n_bits < 0) return PCAMV_EINVAL;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipDeviceSynchronize());
-    hipFree(c->d_rx); c->d_rx = NULL; c->X.rx = NULL; c->X.rx_cap_bits = 0;
+    ctx_free(c, &c->d_rx); c->X.rx = NULL; c->X.rx_cap_bits = 0;
     if (n_bits) {
-        int rc = rx_scratch(c);
-        if (rc) return rc;
-        HIPCHK(c, dalloc(&c->d_rx, (size_t)((n_bits + 31) >> 5)));
+        TRY(rx_scratch(c));
+        TRY(ctx_alloc(c, &c->d_rx, (size_t)((n_bits + 31) >> 5)));
         c->X.rx = c->d_rx; c->X.rx_cap_bits = n_bits;
     }
     return pcamv_gpu_rx_reset(c);
@@ -975,8 +1010,7 @@ extern "C" int pcamv_gpu_rx_fetch(pcamv_ctx_t *c, uint8_t *bytes, int64_t n_bits
     if (!c || !bytes || n_bits < 0 || n_bits > c->X.rx_cap_bits) return PCAMV_EINVAL;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipDeviceSynchronize());
-    int rc = rx_check(c, NULL);
-    if (rc) return rc;
+    TRY(rx_check(c, NULL));
     if (n_bits) HIPCHK(c, hipMemcpy(bytes, c->d_rx, (size_t)((n_bits + 7) >> 3), hipMemcpyDeviceToHost));
     return 0;
 }
@@ -984,32 +1018,32 @@ extern "C" int pcamv_gpu_rx_fetch(pcamv_ctx_t *c, uint8_t *bytes, int64_t n_bits
 /* the two kernels of the receiving side for nx frames whose descriptors are at dX; emrate bounds the message bits of a frame */
 static void extract_launch(pcamv_batch *b, const ExtractDev *dX, int nx, int cap, float emrate, hipStream_t st)
 {
-    int ev = b ? kt_begin(b, KT_EXTRACT_PREPARE, st) : -1;
+    int ev = kt_begin(b, KT_EXTRACT_PREPARE, st);
     hipLaunchKernelGGL(k_extract_prepare, dim3(nx), dim3(1024), 0, st, dX);
-    if (b) kt_end(b, KT_EXTRACT_PREPARE, ev, st);
+    kt_end(b, KT_EXTRACT_PREPARE, ev, st);
     /* workgroups per frame: enough for the most bits a frame of this rate can hold (+ the 63 positions in front of a frame's first
      * bit); the kernel strides if a frame has more (it cannot) */
     double most = emrate > 1.0f ? (double)(int)emrate : ceil((double)emrate * cap) + 1;
     if (most > cap) most = cap;
     const int groups = (int)((most + 63 + 255) / 256) > 0 ? (int)((most + 63 + 255) / 256) : 1;
-    ev = b ? kt_begin(b, KT_EXTRACT_BITS, st) : -1;
+    ev = kt_begin(b, KT_EXTRACT_BITS, st);
     hipLaunchKernelGGL(k_extract_bits, dim3(groups, nx), dim3(256), 0, st, dX);
-    if (b) kt_end(b, KT_EXTRACT_BITS, ev, st);
+    kt_end(b, KT_EXTRACT_BITS, ev, st);
 }
 /* descriptors of the batch's contexts as they stand, into the next slot of the receiving side's ring */
 static int batch_push_xdescs(pcamv_batch *b, hipStream_t st, const ExtractDev **dX, int *slot_out)
 {
     if (!b->d_X) {
-        HIPCHKB(b, hipHostMalloc((void **)&b->h_X, sizeof(ExtractDev) * b->n * NRING, hipHostMallocDefault));
-        HIPCHKB(b, dalloc(&b->d_X, (size_t)b->n * NRING));
-        HIPCHKB(b, dalloc(&b->d_chk, (size_t)b->n));
-        for (int i = 0; i < NRING; i++) HIPCHKB(b, hipEventCreateWithFlags(&b->xring.done[i], hipEventDisableTiming));
+        HIPCHK(b, hipHostMalloc((void **)&b->h_X, sizeof(ExtractDev) * b->n * NRING, hipHostMallocDefault));
+        HIPCHK(b, dalloc(&b->d_X, (size_t)b->n * NRING));
+        HIPCHK(b, dalloc(&b->d_chk, (size_t)b->n));
+        HIPCHK(b, ring_create(b->xring));
     }
     int slot;
-    { const int rc = ring_take(b, b->xring, &slot); if (rc) return rc; }
+    TRY(ring_take(b, b->xring, &slot));
     ExtractDev *hX = b->h_X + (size_t)slot * b->n;
     for (int i = 0; i < b->n; i++) hX[i] = b->ctx[i]->X;
-    HIPCHKB(b, hipMemcpyAsync(b->d_X + (size_t)slot * b->n, hX, sizeof(ExtractDev) * b->n, hipMemcpyHostToDevice, st));
+    HIPCHK(b, hipMemcpyAsync(b->d_X + (size_t)slot * b->n, hX, sizeof(ExtractDev) * b->n, hipMemcpyHostToDevice, st));
     *dX = b->d_X + (size_t)slot * b->n; *slot_out = slot;
     return 0;
 }
@@ -1018,20 +1052,19 @@ static int batch_push_xdescs(pcamv_batch *b, hipStream_t st, const ExtractDev **
 extern "C" int pcamv_gpu_batch_extract_step(pcamv_batch_t *b, float emrate, void *stream)
 {
     if (!b || emrate <= 0) return PCAMV_EINVAL;
-    HIPCHKB(b, hipSetDevice(b->device));
+    HIPCHK(b, hipSetDevice(b->device));
+    TRY(batch_live(b));
     for (int i = 0; i < b->n; i++) {
         pcamv_ctx *c = b->ctx[i];
-        if (!c) return bfail(b, PCAMV_EINVAL, "context %d of the batch was closed", i);
-        if (!c->d_rx) return bfail(b, PCAMV_EINVAL, "context %d has no received buffer (pcamv_gpu_rx_reserve)", i);
-        c->X.mbs = c->d_rec_mb; c->X.flip = c->d_flip; c->X.bits = NULL; c->X.emrate = emrate;
+        if (!c->d_rx) return fail(b, PCAMV_EINVAL, "context %d has no received buffer (pcamv_gpu_rx_reserve)", i);
+        c->X.mbs = c->F.rec_mb; c->X.flip = c->d_flip; c->X.bits = NULL; c->X.emrate = emrate;
     }
     hipStream_t st = stream ? (hipStream_t)stream : b->ctx[0]->stream;
     const ExtractDev *dX; int slot;
-    int rc = batch_push_xdescs(b, st, &dX, &slot);
-    if (rc) return rc;
+    TRY(batch_push_xdescs(b, st, &dX, &slot));
     extract_launch(b, dX, b->n, b->ctx[0]->cap, emrate, st);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return bfail(b, PCAMV_EHIP, "kernel launch: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(b, PCAMV_EHIP, "kernel launch: %s", hipGetErrorString(e));
     return ring_release(b, b->xring, slot, st);
 }
 /* One frame from host records holding FINAL motion (what pcamv_gpu_parse_pslice_* reads out of a stream): uploaded, then the same
@@ -1041,22 +1074,21 @@ extern "C" int pcamv_gpu_extract_pframe(pcamv_ctx_t *c, const pcamv_mb_t *mbs, f
 {
     if (!c || !mbs || emrate <= 0) return PCAMV_EINVAL;
     HIPCHK(c, hipSetDevice(c->device));
-    int rc = rx_scratch(c);
-    if (rc) return rc;
-    if (!c->d_rx_mbs) HIPCHK(c, dalloc(&c->d_rx_mbs, (size_t)c->F.n_mb));
+    TRY(rx_scratch(c));
+    if (!c->d_rx_mbs) TRY(ctx_alloc(c, &c->d_rx_mbs, (size_t)c->F.n_mb));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(c->d_rx_mbs, mbs, (size_t)c->F.n_mb * sizeof(pcamv_mb_t), hipMemcpyHostToDevice));
     c->X.mbs = c->d_rx_mbs; c->X.flip = NULL; c->X.bits = c->d_rx_bits; c->X.emrate = emrate;
     pcamv_batch *b = c->self;
     const ExtractDev *dX; int slot;
-    if ((rc = batch_push_xdescs(b, c->stream, &dX, &slot))) return fail(c, rc, "%s", b->err);
+    TRY(on_behalf(c, b, batch_push_xdescs(b, c->stream, &dX, &slot)));
     extract_launch(b, dX, 1, c->cap, emrate, c->stream);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(c, PCAMV_EHIP, "kernel launch: %s", hipGetErrorString(e));
-    if ((rc = ring_release(b, b->xring, slot, c->stream))) return fail(c, rc, "%s", b->err);
+    TRY(on_behalf(c, b, ring_release(b, b->xring, slot, c->stream)));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     int hdr[8];
-    HIPCHK(c, hipMemcpy(hdr, c->d_rx_hdr, sizeof(hdr), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(hdr, c->X.hdr, sizeof(hdr), hipMemcpyDeviceToHost));
     if (hdr[0] < 0 || hdr[0] > c->cap || hdr[1] < 0) return fail(c, PCAMV_EHIP, "extract header corrupt");
     if (n_out) *n_out = hdr[0];
     if (m_out) *m_out = hdr[1];
@@ -1069,66 +1101,50 @@ extern "C" int pcamv_gpu_extract_pframe(pcamv_ctx_t *c, const pcamv_mb_t *mbs, f
 extern "C" int pcamv_gpu_batch_payload_check(pcamv_batch_t *b, int64_t *diff)
 {
     if (!b || !diff) return PCAMV_EINVAL;
-    HIPCHKB(b, hipSetDevice(b->device));
-    for (int i = 0; i < b->n; i++) if (!b->ctx[i]) return bfail(b, PCAMV_EINVAL, "context %d of the batch was closed", i);
+    HIPCHK(b, hipSetDevice(b->device));
+    TRY(batch_live(b));
     hipStream_t st = b->ctx[0]->stream;
-    HIPCHKB(b, hipDeviceSynchronize());
+    HIPCHK(b, hipDeviceSynchronize());
     const ExtractDev *dX; int slot;
-    int rc = batch_push_xdescs(b, st, &dX, &slot);
-    if (rc) return rc;
+    TRY(batch_push_xdescs(b, st, &dX, &slot));
     int ev = kt_begin(b, KT_PAYLOAD_CHECK, st);
     hipLaunchKernelGGL(k_payload_check, dim3(b->n), dim3(256), 0, st, dX, b->d_chk);
     kt_end(b, KT_PAYLOAD_CHECK, ev, st);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return bfail(b, PCAMV_EHIP, "kernel launch: %s", hipGetErrorString(e));
-    if ((rc = ring_release(b, b->xring, slot, st))) return rc;
-    HIPCHKB(b, hipStreamSynchronize(st));
+    if (e != hipSuccess) return fail(b, PCAMV_EHIP, "kernel launch: %s", hipGetErrorString(e));
+    TRY(ring_release(b, b->xring, slot, st));
+    HIPCHK(b, hipStreamSynchronize(st));
     static_assert(sizeof(long long) == sizeof(int64_t), "payload_check copies the counts as they are");
-    HIPCHKB(b, hipMemcpy(diff, b->d_chk, sizeof(int64_t) * b->n, hipMemcpyDeviceToHost));
-    for (int i = 0; i < b->n; i++) if ((rc = rx_check(b->ctx[i], NULL))) return bfail(b, rc, "context %d: %s", i, b->ctx[i]->err);
+    HIPCHK(b, hipMemcpy(diff, b->d_chk, sizeof(int64_t) * b->n, hipMemcpyDeviceToHost));
+    for (int i = 0; i < b->n; i++) { const int rc = rx_check(b->ctx[i], NULL); if (rc) return fail(b, rc, "context %d: %s", i, b->ctx[i]->err); }
     return 0;
 }
 
-static int batch_kernel_time(pcamv_batch *b, double *avg_ms, int *launches, int reset)
-{
-    HIPCHKB(b, hipSetDevice(b->device));
-    HIPCHKB(b, hipDeviceSynchronize());
-    { int rc = flow_check(b); if (rc) return rc; }
-    for (int i = 0; i < b->ev_n; i++) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, b->ev0[i], b->ev1[i]) == hipSuccess) { b->t_search_ms += ms; b->t_search_launches += b->sched_flow ? 1 : b->n_diag; }
-    }
-    b->ev_n = 0; b->ev_head = 0;
-    if (avg_ms) *avg_ms = b->t_search_launches ? b->t_search_ms / b->t_search_launches : 0;
-    if (launches) *launches = b->t_search_launches;
-    if (reset) { b->t_search_ms = 0; b->t_search_launches = 0; }
-    return 0;
-}
+/* the time of one of the batch's timed kernels by its name: the launches since the last call, added to the running average */
 extern "C" int pcamv_gpu_batch_kernel_time(pcamv_batch_t *b, const char *kernel, double *avg_ms, int *launches, int reset)
 {
     if (!b || !kernel) return PCAMV_EINVAL;
-    for (int k = 0; k < KT_N; k++) {
-        if (strcmp(kernel, kt_names[k])) continue;
-        pcamv_batch::KTimer &T = b->kt[k];
-        HIPCHKB(b, hipSetDevice(b->device));
-        HIPCHKB(b, hipDeviceSynchronize());
-        for (int i = 0; i < T.n; i++) {         /* (a full ring holds the last NKEV launches, in any order: an average does not care) */
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, T.e0[i], T.e1[i]) == hipSuccess) { T.ms += ms; T.launches++; }
-        }
-        T.n = 0; T.head = 0;
-        if (avg_ms) *avg_ms = T.launches ? T.ms / T.launches : 0;
-        if (launches) *launches = T.launches;
-        if (reset) { T.ms = 0; T.launches = 0; }
-        return 0;
+    int k = 0;
+    while (k < KT_N && strcmp(kernel, kt_name(b, k))) k++;
+    if (k == KT_N) return PCAMV_EINVAL;
+    KTimer &T = b->kt[k];
+    HIPCHK(b, hipSetDevice(b->device));
+    HIPCHK(b, hipDeviceSynchronize());
+    if (k == KT_ANALYSE) TRY(flow_check(b));
+    for (int i = 0; i < T.n; i++) {         /* (a full ring holds the last T.cap launches, in any order: an average does not care) */
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, T.e0[i], T.e1[i]) == hipSuccess) { T.ms += ms; T.launches += T.weight; }
     }
-    if (strcmp(kernel, dominant_kernel(b))) return PCAMV_EINVAL;
-    return batch_kernel_time(b, avg_ms, launches, reset);
+    T.n = 0; T.head = 0;
+    if (avg_ms) *avg_ms = T.launches ? T.ms / T.launches : 0;
+    if (launches) *launches = T.launches;
+    if (reset) { T.ms = 0; T.launches = 0; }
+    return 0;
 }
 extern "C" int pcamv_gpu_kernel_time(pcamv_ctx_t *c, const char *kernel, double *avg_ms, int *launches, int reset)
 {
     if (!c || !kernel || strcmp(kernel, dominant_kernel(c->self))) return PCAMV_EINVAL;
-    return batch_kernel_time(c->self, avg_ms, launches, reset);
+    return pcamv_gpu_batch_kernel_time(c->self, kernel, avg_ms, launches, reset);
 }
 
 /* diagnostics: log every block-cost evaluation made for macroblock mb during the next analyse call
@@ -1141,7 +1157,7 @@ extern "C" int pcamv_gpu_trace_mb(pcamv_ctx_t *c, int mb)
 #endif
     HIPCHK(c, hipSetDevice(c->device));
     if (mb < 0) { c->F.trace = NULL; return 0; }
-    if (!c->d_trace) HIPCHK(c, dalloc(&c->d_trace, (size_t)1 + 8 * 4000));
+    if (!c->d_trace) TRY(ctx_alloc(c, &c->d_trace, (size_t)1 + 8 * 4000));
     HIPCHK(c, hipMemset(c->d_trace, 0, (1 + 8 * 4000) * sizeof(int)));
     c->F.trace = c->d_trace; c->F.trace_mb = mb;
     return 0;
@@ -1165,16 +1181,14 @@ extern "C" int pcamv_gpu_block_costs(pcamv_ctx_t *c, int qp, int n, const int32_
         int px = r[0] * 16 + r[3] + (r[5] >> 2), py = r[1] * 16 + r[4] + (r[6] >> 2);    /* stay inside the 32-pixel padding */
         if (px < -28 || py < -28 || px + 20 > c->F.w + 28 || py + 20 > c->F.h + 28) return fail(c, PCAMV_EINVAL, "request %d leaves the padded plane", i);
     }
-    int rc = ensure_qp(c, qp);
-    if (rc) return rc;
-    int *d_req = NULL, *d_out = NULL; FrameDev *d_F = NULL;
-    HIPCHK(c, dalloc(&d_req, (size_t)n * 8)); HIPCHK(c, dalloc(&d_out, (size_t)n * 3)); HIPCHK(c, dalloc(&d_F, 1));
+    TRY(ensure_qp(c, qp));
+    DevTmp<int> d_req, d_out; DevTmp<FrameDev> d_F;
+    HIPCHK(c, d_req.alloc((size_t)n * 8)); HIPCHK(c, d_out.alloc((size_t)n * 3)); HIPCHK(c, d_F.alloc(1));
     HIPCHK(c, hipMemcpy(d_req, req, (size_t)n * 8 * sizeof(int), hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(d_F, &c->F, sizeof(FrameDev), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_block_costs, dim3(n), dim3(64), 0, c->stream, (const FrameDev *)d_F, (const int *)d_req, d_out);
+    hipLaunchKernelGGL(k_block_costs, dim3(n), dim3(64), 0, c->stream, (const FrameDev *)d_F, (const int *)d_req, (int *)d_out);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(out, d_out, (size_t)n * 3 * sizeof(int), hipMemcpyDeviceToHost));
-    hipFree(d_req); hipFree(d_out); hipFree(d_F);
     return 0;
 }
 
@@ -1182,21 +1196,14 @@ extern "C" int pcamv_gpu_rd_probe(pcamv_ctx_t *c, int qp, int n, const uint8_t *
 {
     if (!c || !req || !out || n <= 0) return PCAMV_EINVAL;
     HIPCHK(c, hipSetDevice(c->device));
-    int rc = ensure_qp(c, qp);
-    if (rc) return rc;
-    uint8_t *d_req = NULL; int *d_out = NULL; FrameDev *d_F = NULL;
-    hipError_t e = dalloc(&d_req, (size_t)n * 1024);
-    if (e == hipSuccess) e = dalloc(&d_out, (size_t)n * 32);
-    if (e == hipSuccess) e = dalloc(&d_F, 1);
-    if (e == hipSuccess) e = hipMemcpy(d_req, req, (size_t)n * 1024, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_F, &c->F, sizeof(FrameDev), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_rd_probe, dim3(n), dim3(64), 0, c->stream, (const FrameDev *)d_F, (const uint8_t *)d_req, d_out);
-        e = hipStreamSynchronize(c->stream);
-    }
-    if (e == hipSuccess) e = hipMemcpy(out, d_out, (size_t)n * 32 * sizeof(int), hipMemcpyDeviceToHost);
-    hipFree(d_req); hipFree(d_out); hipFree(d_F);
-    if (e != hipSuccess) return fail(c, PCAMV_EHIP, "rd_probe: %s", hipGetErrorString(e));
+    TRY(ensure_qp(c, qp));
+    DevTmp<uint8_t> d_req; DevTmp<int> d_out; DevTmp<FrameDev> d_F;
+    HIPCHK(c, d_req.alloc((size_t)n * 1024)); HIPCHK(c, d_out.alloc((size_t)n * 32)); HIPCHK(c, d_F.alloc(1));
+    HIPCHK(c, hipMemcpy(d_req, req, (size_t)n * 1024, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_F, &c->F, sizeof(FrameDev), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_rd_probe, dim3(n), dim3(64), 0, c->stream, (const FrameDev *)d_F, (const uint8_t *)d_req, (int *)d_out);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out, d_out, (size_t)n * 32 * sizeof(int), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -1206,36 +1213,18 @@ extern "C" int pcamv_gpu_final_mvs(pcamv_ctx_t *c, pcamv_mb_t *mbs)
     if (!c || !mbs) return PCAMV_EINVAL;
     HIPCHK(c, hipSetDevice(c->device));
     int hdr[8];
-    HIPCHK(c, hipMemcpy(hdr, c->d_hdr, sizeof(hdr), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(hdr, c->E.hdr, sizeof(hdr), hipMemcpyDeviceToHost));
     int n = hdr[0];
     if (n < 0 || n > c->cap) return fail(c, PCAMV_EHIP, "embed header corrupt");
-    int8_t *flip = (int8_t *)malloc(n ? n : 1);
+    HostTmp<int8_t> flip(n ? n : 1);
     if (!flip) return fail(c, PCAMV_ENOMEM, "flip");
-    hipError_t e = hipMemcpy(flip, c->d_flip, n, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { free(flip); return fail(c, PCAMV_EHIP, "flip download"); }
-    int k = 0;
+    HIPCHK(c, hipMemcpy(flip, c->d_flip, n, hipMemcpyDeviceToHost));
+    int k = 0, slots[16];
     for (int xy = 0; xy < c->F.n_mb; xy++) {
-        int slots[16], cs = 0;
-        const pcamv_mb_t *mb = &mbs[xy];
-        if (mb->used) {
-            if (mb->i_type == PCAMV_P_8x8) {
-                for (int i = 0; i < 4; i++)
-                    switch (mb->i_sub_partition[i]) {
-                    case PCAMV_D_L0_8x8: slots[cs++] = i * 4; break;
-                    case PCAMV_D_L0_4x8: slots[cs++] = i * 4; slots[cs++] = i * 4 + 1; break;
-                    case PCAMV_D_L0_8x4: slots[cs++] = i * 4; slots[cs++] = i * 4 + 2; break;
-                    default: for (int j = 0; j < 4; j++) slots[cs++] = i * 4 + j; break;
-                    }
-            } else if (mb->i_type == PCAMV_P_L0) {
-                slots[cs++] = 0;
-                if (mb->i_partition == PCAMV_D_8x16) slots[cs++] = 4;
-                else if (mb->i_partition == PCAMV_D_16x8) slots[cs++] = 8;
-            }
-        }
+        const int cs = mb_carrier_slots(&mbs[xy], slots);
         for (int i = 0; i < cs && k < n; i++, k++)
             if (flip[k] == 1) { mbs[xy].mv[slots[i]][0] = mbs[xy].mv_stego[slots[i]][0]; mbs[xy].mv[slots[i]][1] = mbs[xy].mv_stego[slots[i]][1]; }
     }
-    free(flip);
     return 0;
 }
 
