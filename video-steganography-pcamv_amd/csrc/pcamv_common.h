@@ -179,6 +179,14 @@ struct MBLocal {
     int16_t snap_cmvd[48][2];
     int snap_cbp_luma, snap_cbp_chroma, snap_nnz_mask;
     int snap_part, snap_cost;      /* partition (PCAMV_D_*) of the kept trial, -1 = none; its RD cost */
+    /* ... and what a later trial with the same motion takes over from it instead of computing it again (rd_trial): the 16 per-4x4 MVs
+     * it was made with (block order), its distortion (SSD + psy term), the size of its residual (CABAC, 8.8 fixed point) */
+    uint32_t snap_mv[16];
+    int snap_ssd, snap_f8r;
+#if defined(PCAMV_PROF)            /* counters build: the MVs of every trial made so far (COUNT rd trials ..., tools/dbg/prof_phases.py) */
+    uint32_t prof_mv[4][16];
+    int prof_ntrial;
+#endif
 #ifdef PCAMV_SEARCH_CALL           /* the motion search as a callee (pcamv_logic.h): its arguments pass through here */
     const struct FrameDev *fdesc;  /* this macroblock's frame descriptor in the descriptor array (constant memory) */
     int me_tmp[10];                /* MEState */
@@ -186,6 +194,8 @@ struct MBLocal {
 #endif
 };
 #define PCAMV_PASS2_LDS ((int)offsetof(MBLocal, coef))       /* everything up to and including pred */
+/* 16 waves per CU of 160 KB: a wave's MBLocal + Analysis (pcamv_kernels.hip.h asserts the sum) must stay within this */
+#define PCAMV_WAVE_LDS_MAX 10240
 /* the second-pass kernel allocates PCAMV_PASS2_LDS bytes of an MBLocal: what it touches must lie below the cut, and two users count on
  * neighbours staying neighbours (the residual walk's rows run from cxy into ccost; the Hadamard exhaustive search's survivor list and the
  * intra analysis' picture run from recb on) */
@@ -304,7 +314,8 @@ struct MEState {
 };
 
 
-/* diagnostics build (-DPCAMV_PROF): wave cycles per phase of k_analyse_flow, summed in pcamv_prof[] (tools/dbg/prof_phases.py) */
+/* diagnostics build (-DPCAMV_PROF): wave cycles per phase of k_analyse_flow, summed in pcamv_prof[] (tools/dbg/prof_phases.py); slots 43..46 count
+ * the RD trials: all, with the kept trial's motion, with an earlier trial's, reusing and cheaper than the kept one (tools/dbg/rd_reuse_count.py) */
 #if defined(PCAMV_PROF) && !defined(PCAMV_HOST_EMU)
 #define PCAMV_PROF_N 48
 static __device__ unsigned long long pcamv_prof[PCAMV_PROF_N];

@@ -841,6 +841,9 @@ __device__ __forceinline__ void flow_loop(const FrameDev *__restrict__ Fs, const
     PROF_FLUSH();
 }
 
+#ifndef PCAMV_PROF                 /* (the counters build keeps its sums and a trial log in LDS as well) */
+static_assert(sizeof(MBLocal) + sizeof(Analysis) <= PCAMV_WAVE_LDS_MAX, "the analysis kernels' LDS per wave (MBLocal + Analysis) no longer allows 16 waves per CU");
+#endif
 #ifdef PCAMV_MAIN_TU
 static __global__ void __launch_bounds__(64, PCAMV_FLOW_OCC) k_analyse_flow(const FrameDev *__restrict__ Fs, FlowDev fl)
 {

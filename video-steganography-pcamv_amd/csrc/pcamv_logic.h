@@ -798,15 +798,23 @@ PCAMV_DEV void cabac_mb_header(const FrameDev &F, MBLocal *L, CabWalk &C)
     (void)F;
 }
 /* x264_rd_cost_mb (rdo.c:139-171) of the macroblock as the cache describes it: distortion (SSD + psy-RD) + lambda2 * bits */
-PCAMV_DEV int rd_cost_mb(const FrameDev &F, MBLocal *L)
+/* the two terms a later trial with the same motion takes over (rd_trial): the distortion, and with CABAC the size of the residual */
+struct RdParts { int ssd, f8r; };
+/* reuse: the motion is the kept trial's, whose terms `parts` holds -- only the header is walked (rd_trial); else `parts` is filled */
+PCAMV_DEV int rd_cost_mb(const FrameDev &F, MBLocal *L, RdParts *parts, int reuse)
 {
     L->b_skip_mc = 0;
-    const unsigned long long t_e = PROF_T();
-    mb_encode(F, L, 0, 1);
-    PROF_ADD(18, t_e);
-    const unsigned long long t_s = PROF_T();
-    const int ssd = prim_ssd_mb(F, L);
-    PROF_ADD(19, t_s);
+    if (!reuse) {
+        const unsigned long long t_e = PROF_T();
+        mb_encode(F, L, 0, 1);
+        PROF_ADD(18, t_e);
+        const unsigned long long t_s = PROF_T();
+        parts->ssd = prim_ssd_mb(F, L); parts->f8r = 0;
+        PROF_ADD(19, t_s);
+    }
+#ifndef PCAMV_HOST_EMU
+    else prim_rd_reuse_begin(L);
+#endif
     int bits;
     if (F.b_cabac) {
         const unsigned long long t_h = PROF_T();
@@ -815,13 +823,24 @@ PCAMV_DEV int rd_cost_mb(const FrameDev &F, MBLocal *L)
         cabac_mb_header(F, L, C);
         PROF_ADD(20, t_h);
         const unsigned long long t_r = PROF_T();
+        int f8;
+#if !defined(PCAMV_HOST_EMU) && !defined(PCAMV_RD_NO_REUSE)
+        if (reuse) f8 = prim_cab_end(L, C, 0) + parts->f8r;
+        else {
+            const int f8h = prim_cab_bits_so_far(L, C);
+            prim_cab_residual(F, L, C, 0);
+            f8 = prim_cab_end(L, C, 0);
+            parts->f8r = f8 - f8h;
+        }
+#else
         prim_cab_residual(F, L, C, 0);
-        const int f8 = prim_cab_end(L, C, 0);
+        f8 = prim_cab_end(L, C, 0);
+#endif
         PROF_ADD(21, t_r);
         bits = (int)(((unsigned long long)(unsigned)f8 * (unsigned long long)F.lambda2 + 32768ull) >> 16);
     } else
         bits = (int)((unsigned)prim_cavlc_mb(F, L) * (unsigned)F.lambda2 + 128u) >> 8;       /* int arithmetic in the reference */
-    return ssd + bits;
+    return parts->ssd + bits;
 }
 /* x264_rd_cost_part for one 8x8 of a P_8x8 macroblock (rdo.c:202-245, i_pixel = PIXEL_8x8): x264_macroblock_encode_p8x8 of that
  * 8x8 with the sub-partition the cache describes (encoder/macroblock.c:929-1052), SSD + psy of its luma 8x8 and plain SSD of its two
@@ -860,10 +879,37 @@ PCAMV_DEV unsigned long long rd_cost_part8(const FrameDev &F, MBLocal *L, int i8
  * strict <), so the one that is the cheapest so far is the decision's winner as far as it has come: its products are kept
  * (prim_rd_keep), and the macroblock as decided is not encoded and walked a second time when it is the kept one (mbk_search).
  * counts = 0: a trial the decision will not look at (P_8x8 while nothing is embedded, analyse.c:2841). */
+/* Reuse: a trial whose 16 per-4x4 MVs are those of the kept trial encodes to the same macroblock.  The prediction reads nothing but
+ * these MVs (prim_predict_mb; x264_mb_mc, common/macroblock.c), the transform stage nothing but source, prediction and the quantiser
+ * (prim_mb_transform: encoder/macroblock.c:605-754 -- the type only tells P_SKIP apart, and the decimation rules are those of every
+ * inter type), the distortion nothing but source and reconstruction (prim_ssd_mb: rdo.c:106-137), and the residual's decisions
+ * nothing but the levels and the neighbours' flags, on contexts (85 and up) no header decision touches (encoder/cabac.c:671-757
+ * against 1000-1018).  A size is a sum over decisions, so with the kept trial's distortion and residual size (RdParts)
+ *     cost = ssd(kept) + ((f8 header(this) + f8 residual(kept)) * lambda2 + 32768 >> 16)       (rdo.c:139-171)
+ * is what the full trial returns, bit for bit, for one header walk.  If that is the cheapest so far, this mode becomes the kept
+ * trial with its own header's products and the old one's everything else (prim_rd_keep_header).  CABAC only: CAVLC makes every trial
+ * in full.  The CPU emulation makes every trial in full as well and stays an independent check of the rule. */
 PCAMV_DEV int rd_trial(const FrameDev &F, MBLocal *L, int counts)
 {
-    const int cost = rd_cost_mb(F, L);
-    if (counts && cost < L->snap_cost) { L->snap_cost = cost; L->snap_part = L->i_partition; prim_rd_keep(F, L); }
+    RdParts parts;
+    int reuse = 0;
+#if !defined(PCAMV_HOST_EMU) && (!defined(PCAMV_RD_NO_REUSE) || defined(PCAMV_PROF))
+    const bool same = rfl(L->snap_part) >= 0 && prim_rd_same_motion(L);
+#ifdef PCAMV_PROF
+    prim_rd_prof_trial(L, same);
+#endif
+#ifndef PCAMV_RD_NO_REUSE
+    if (same && F.b_cabac) { reuse = 1; parts.ssd = L->snap_ssd; parts.f8r = L->snap_f8r; }
+#endif
+#endif
+    const int cost = rd_cost_mb(F, L, &parts, reuse);
+    if (counts && cost < L->snap_cost) {
+        L->snap_cost = cost; L->snap_part = L->i_partition;
+#ifndef PCAMV_HOST_EMU
+        if (reuse) { PROF_CNT(46, 1); prim_rd_keep_header(L); } else
+#endif
+        { L->snap_ssd = parts.ssd; L->snap_f8r = parts.f8r; prim_rd_keep(F, L); }
+    }
     return cost;
 }
 template <int TESA>
@@ -1186,6 +1232,9 @@ PCAMV_DEV int analyse_s16(const FrameDev &F, MBLocal *L, Analysis *a)
     for (int i = 0; i < 4; i++) a->cost4x4[i] = a->cost8x4[i] = a->cost4x8[i] = PCAMV_COST_MAX;      /* (read by the RD stage whether analysed or not) */
     a->rd16_early = 0;
     L->snap_part = -1; L->snap_cost = PCAMV_COST_MAX;
+#if defined(PCAMV_PROF) && !defined(PCAMV_HOST_EMU)
+    L->prof_ntrial = 0;
+#endif
     if (F.b_fast_pskip) {
         if (F.subme >= 3) b_try_pskip = 1;
         else if (L->type_left == PCAMV_P_SKIP || L->type_top == PCAMV_P_SKIP || L->type_topleft == PCAMV_P_SKIP || L->type_topright == PCAMV_P_SKIP)

@@ -600,6 +600,12 @@ __device__ __forceinline__ void prim_cb_run(MBLocal *L, CabWalk &C, int ctx_, in
     C.tot += ones + zero;
 }
 __device__ __forceinline__ void prim_cb_bypass(CabWalk &C, int f8) { C.bits += rfl(f8); }
+/* the size of everything walked so far (8.8 fixed point), the walk going on: what a macroblock's header costs apart from its residual */
+__device__ __forceinline__ int prim_cab_bits_so_far(MBLocal *L, CabWalk &C)
+{
+    prim_cab_flush(L, C);
+    return rfl(C.bits) + wave_sum_all(C.vbits);
+}
 __device__ __forceinline__ int prim_cab_end(MBLocal *L, CabWalk &C, int commit_)
 {
     const int lane = LANE();
@@ -1026,8 +1032,54 @@ __device__ __forceinline__ void prim_rd_keep(const FrameDev &F, MBLocal *L)
         d[lane] = s[lane]; if (lane < PCAMV_CAB_USED / 4 - 64) d[64 + lane] = s[64 + lane];
     }
     if (lane == 0) { L->snap_cbp_luma = L->cbp_luma; L->snap_cbp_chroma = L->cbp_chroma; L->snap_nnz_mask = L->nnz_mask; }
+    if (lane < 16) L->snap_mv[lane] = ((const uint32_t *)L->cmv)[scan8_of(lane)];
     PCAMV_WAVE_SYNC();
 }
+/* Reuse of the kept trial by a trial with the same motion (rd_trial, pcamv_logic.h).  Is the motion the cache describes -- its 16
+ * per-4x4 MVs, all the prediction reads -- that of the kept trial? */
+__device__ __forceinline__ bool prim_rd_same_motion(MBLocal *L)
+{
+    PCAMV_WAVE_SYNC();
+    const int lane = LANE();
+    const bool differs = lane < 16 && ((const uint32_t *)L->cmv)[scan8_of(lane)] != L->snap_mv[lane];
+    return __builtin_amdgcn_ballot_w64(differs) == 0ull;
+}
+/* ... then encoding it would leave what the kept trial left: the coded block pattern (which the header walk reads) and the non-zero
+ * flags / counts go where the encode would have put them; pixels and levels are not needed by a header walk and stay in the snapshot */
+__device__ __forceinline__ void prim_rd_reuse_begin(MBLocal *L)
+{
+    PCAMV_WAVE_SYNC();
+    const int lane = LANE();
+    if (lane < 12) ((uint32_t *)L->nzc)[lane] = ((const uint32_t *)L->snap_nzc)[lane];
+    if (lane == 0) { L->cbp_luma = L->snap_cbp_luma; L->cbp_chroma = L->snap_cbp_chroma; L->nnz_mask = L->snap_nnz_mask; }
+    PCAMV_WAVE_SYNC();
+}
+/* ... and if its header makes it the cheaper one it becomes the kept trial: its MV differences, and of the context states this walk's
+ * for the contexts a header owns (cab_hdr_ctx: 0..23, 36..63, 73..84 -- the trial copy holds the slice's states for those it did not
+ * touch, as the kept copy does) beside the kept trial's for all others (the residual's, 85 and up) */
+__device__ __forceinline__ void prim_rd_keep_header(MBLocal *L)
+{
+    PCAMV_WAVE_SYNC();
+    const int lane = LANE();
+    if (lane < 48) ((uint32_t *)L->snap_cmvd)[lane] = ((const uint32_t *)L->cmvd)[lane];
+    L_CABK(L)[cab_hdr_ctx(lane)] = L_CABT(L)[cab_hdr_ctx(lane)];
+    PCAMV_WAVE_SYNC();
+}
+#ifdef PCAMV_PROF
+/* counters build: one RD trial is about to be made; same_kept: its motion is the kept trial's */
+__device__ __forceinline__ void prim_rd_prof_trial(MBLocal *L, bool same_kept)
+{
+    PCAMV_WAVE_SYNC();
+    const int lane = LANE(), n = rfl(L->prof_ntrial);
+    const uint32_t mv = lane < 16 ? ((const uint32_t *)L->cmv)[scan8_of(lane)] : 0u;
+    int same_other = 0;
+    for (int k = 0; k < n; k++) same_other |= __builtin_amdgcn_ballot_w64(lane < 16 && mv != L->prof_mv[k][lane]) == 0ull;
+    PROF_CNT(43, 1); PROF_CNT(44, same_kept ? 1 : 0); PROF_CNT(45, !same_kept && same_other ? 1 : 0);
+    if (lane < 16 && n < 4) L->prof_mv[n][lane] = mv;
+    if (lane == 0) L->prof_ntrial = n + 1;
+    PCAMV_WAVE_SYNC();
+}
+#endif
 /* the kept trial is the macroblock as decided: put its products where the final encode + walk would have left them (the context
  * states become the slice's; the mb_skip_flag decision, which a size trial does not contain, is the caller's) */
 __device__ __forceinline__ void prim_rd_restore(const FrameDev &F, MBLocal *L)
