@@ -12,8 +12,9 @@
 #include "pcamv_mbkernels.h"
 #include "pcamv_host_tables.h"
 
-/* the instance the library would run: the --me tesa one (variant bit 0) only for that method; bit 1 the RD mode decision, bit 3 x264_rd_cost_part */
-#define EMU_SEARCH(F, L, a, x, y) do { if ((F).me_method == PCAMV_ME_TESA) mbk_search<11>(F, L, a, x, y); else mbk_search<10>(F, L, a, x, y); } while (0)
+/* the instance the library would run (pcamv_variant.h): the --me tesa one only for that method */
+#define EMU_SEARCH(F, L, a, x, y) do { if ((F).me_method == PCAMV_ME_TESA) mbk_search<V_TESA | V_RD | V_RD_PSUB>(F, L, a, x, y); \
+                                       else mbk_search<V_RD | V_RD_PSUB>(F, L, a, x, y); } while (0)
 extern "C" int emu_analyse_pframe(const pcamv_params_t *p, int qp, int embed,
                                   const uint8_t *fy, const uint8_t *fu, const uint8_t *fv,
                                   uint8_t *luma4, uint8_t *cu, uint8_t *cv,

@@ -106,6 +106,9 @@ def driver(tmp_path_factory):
     lib.rdsel_build_name.restype = C.c_char_p
     lib.rdsel_build_name.argtypes = [C.c_int]
     lib.rdsel_build_spec.argtypes = [C.c_int]
+    lib.rdsel_build_occ.argtypes = [C.c_int]
+    lib.rdsel_build_variant.argtypes = [C.c_int]
+    lib.rdsel_variant_bit.argtypes = [C.c_char_p]
     return lib
 
 
@@ -118,6 +121,16 @@ def test_rows_of_the_table(driver):
     assert tuple(driver.rdsel_build_name(i).decode() for i in range(len(BUILDS))) == BUILDS
     # waves per SIMD of the speculative chain; 0 = plain chain (FlowDev::spec derives from it)
     assert [driver.rdsel_build_spec(i) for i in range(len(BUILDS))] == [0, 0, 1, 2, 4, 0]
+    # what each build is: waves per SIMD its registers are held to, and what its control code has compiled in
+    V = {name: driver.rdsel_variant_bit(name.encode()) for name in ("V_TESA", "V_RD", "V_SPEC", "V_RD_PSUB")}
+    assert sorted(V.values()) == [1, 2, 4, 8]
+    assert [driver.rdsel_build_occ(i) for i in range(len(BUILDS))] == [4, 1, 1, 2, 4, 1]
+    assert [driver.rdsel_build_variant(i) for i in range(len(BUILDS))] == [
+        V["V_RD"], V["V_RD"] | V["V_RD_PSUB"], V["V_RD"] | V["V_SPEC"] | V["V_RD_PSUB"], V["V_RD"] | V["V_SPEC"], V["V_RD"] | V["V_SPEC"],
+        V["V_TESA"] | V["V_RD"] | V["V_RD_PSUB"]]
+    for i in range(len(BUILDS)):        # the derived column: a speculative build's waves per SIMD
+        spec = driver.rdsel_build_variant(i) & V["V_SPEC"]
+        assert driver.rdsel_build_spec(i) == (driver.rdsel_build_occ(i) if spec else 0)
 
 
 def test_rd_select(driver):
@@ -129,4 +142,29 @@ def test_rd_select(driver):
         if got != want:
             wrong.append(f"n={n} CUs={n_cu} raster={raster} mb_w={mb_w} sub8x8={sub8x8} tesa={tesa} PCAMV_RD_INSTANCE={inst!r} "
                          f"PCAMV_FLOW_SPEC={flow_spec!r}: {got}, expected {want}")
+    assert not wrong, "\n".join(wrong)
+
+
+def test_rd_select_against_the_table(driver):
+    """What rd_select relies on is in the row it returns: every build is an RD build; sub-8x8 partitions go to a build that prices
+    them; --me tesa gets the build with that search, and nothing else does; a speculative build only where the chain can be
+    speculative (a raster chain, a picture wide enough)."""
+    V = {name: driver.rdsel_variant_bit(name.encode()) for name in ("V_TESA", "V_RD", "V_SPEC", "V_RD_PSUB")}
+    min_mbw = driver.rdsel_spec_min_mbw()
+    wrong = []
+    for args, _ in CASES:
+        n, n_cu, raster, mb_w, sub8x8, tesa, inst, flow_spec = args
+        row = BUILDS.index(driver.rdsel_name(n, n_cu, raster, mb_w, sub8x8, tesa, _enc(inst), _enc(flow_spec)).decode())
+        variant = driver.rdsel_build_variant(row)
+        bad = []
+        if not variant & V["V_RD"]:
+            bad.append("not an RD build")
+        if sub8x8 and not variant & V["V_RD_PSUB"]:
+            bad.append("sub-8x8 partitions on a build without V_RD_PSUB")
+        if bool(variant & V["V_TESA"]) != bool(tesa):
+            bad.append("V_TESA set exactly for --me tesa")
+        if variant & V["V_SPEC"] and not (raster and mb_w >= min_mbw):
+            bad.append("a speculative build without a raster chain or on a narrow picture")
+        if bad:
+            wrong.append(f"{args} -> {BUILDS[row]}: " + "; ".join(bad))
     assert not wrong, "\n".join(wrong)

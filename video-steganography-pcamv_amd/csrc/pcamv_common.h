@@ -16,6 +16,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include "../../include/pcamv_gpu.h"
+#include "pcamv_variant.h"
 
 #ifdef PCAMV_HOST_EMU
 #define PCAMV_DEV static inline
@@ -194,7 +195,7 @@ struct MBLocal {
 #endif
 };
 #define PCAMV_PASS2_LDS ((int)offsetof(MBLocal, coef))       /* everything up to and including pred */
-/* 16 waves per CU of 160 KB: a wave's MBLocal + Analysis (pcamv_kernels.hip.h asserts the sum) must stay within this */
+/* 16 waves per CU of 160 KB: a wave's MBLocal + Analysis (pcamv_flow.hip.h asserts the sum) must stay within this */
 #define PCAMV_WAVE_LDS_MAX 10240
 /* the second-pass kernel allocates PCAMV_PASS2_LDS bytes of an MBLocal: what it touches must lie below the cut, and two users count on
  * neighbours staying neighbours (the residual walk's rows run from cxy into ccost; the Hadamard exhaustive search's survivor list and the

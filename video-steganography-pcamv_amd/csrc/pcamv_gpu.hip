@@ -1,6 +1,7 @@
 /*
  * pcamv_gpu.hip -- host side of libpcamv_gpu.so: the C ABI of include/pcamv_gpu.h over the
- * gfx950 kernels of pcamv_kernels.hip.h.  There is no CPU path: every entry point needs a HIP
+ * gfx950 kernels of pcamv_planes.hip.h, pcamv_kernels.hip.h and pcamv_embed.hip.h, which this unit alone compiles, and the launchers
+ * of the other instances of the analysis kernel (pcamv_flow.hip.h).  There is no CPU path: every entry point needs a HIP
  * device and fails with PCAMV_ENODEV / PCAMV_EHIP otherwise.
  */
 #include <hip/hip_runtime.h>
@@ -10,7 +11,9 @@
 #include <stdlib.h>
 #include <string.h>
 #include <new>
+#include "pcamv_planes.hip.h"
 #include "pcamv_kernels.hip.h"
+#include "pcamv_embed.hip.h"
 #include "pcamv_host_tables.h"
 #include "pcamv_mvsyntax.h"
 #include "pcamv_rd_select.h"
@@ -30,7 +33,7 @@ static_assert(P2_LSLOTS <= 64 * 11 && P2_CSLOTS <= 64 * 7 && 8 * 59 <= 64 * 8,
               "p2_unit_load's fixed unroll counts (11 / 7 / 8 rounds of 64 lanes) no longer cover the luma tile, the chroma tile or the 8 records of a run");
 static_assert(FLOW_SPEC_MIN_MBW - 1 > FLOW_SPEC_AHEAD + 1, "speculative chain: a macroblock would be handed on before its top / top-right neighbours are final");
 
-/* The builds of the RD instance of the analysis kernel (pcamv_rd.hip RD_NAME: one translation unit each), a row per entry of
+/* The builds of the RD instance of the analysis kernel (one translation unit each, pcamv_rd.hip), a row per entry of
  * PCAMV_RD_BUILDS in the order of rd_select's result; the phase timers are per translation unit (PCAMV_PROF) */
 struct RdBuild {
     int spec;                   /* waves per SIMD of the speculative raster chain, 0: plain chain */
@@ -39,14 +42,11 @@ struct RdBuild {
     int (*prof_fetch)(unsigned long long *out, int reset);      /* NULL without PCAMV_PROF */
 };
 #ifdef PCAMV_PROF
-#define RD_PROF_FN(sfx) pcamv_rd_prof_fetch##sfx
+#define RD_PROF_FN(id) pcamv_rd_prof_fetch<RD_##id>
 #else
-#define RD_PROF_FN(sfx) NULL
+#define RD_PROF_FN(id) NULL
 #endif
-#define RD_DECL(id, sfx, spec) void pcamv_launch_flow_rd##sfx(unsigned, hipStream_t, const FrameDev *, const FlowDev &); \
-    int pcamv_flow_rd_waves_per_cu##sfx(void); int pcamv_rd_prof_fetch##sfx(unsigned long long *, int);
-#define RD_ROW(id, sfx, spec) {spec, pcamv_launch_flow_rd##sfx, pcamv_flow_rd_waves_per_cu##sfx, RD_PROF_FN(sfx)},
-PCAMV_RD_BUILDS(RD_DECL)
+#define RD_ROW(id, occ, variant) {rd_build_spec(RD_##id), pcamv_launch_flow_rd<RD_##id>, pcamv_flow_rd_waves_per_cu<RD_##id>, RD_PROF_FN(id)},
 static const RdBuild rd_builds[RD_N_BUILDS] = {PCAMV_RD_BUILDS(RD_ROW)};
 
 /* one ring of NRING descriptor slots: a slot is written again only after the work that read it last (its event) is done */

@@ -215,24 +215,23 @@ PCAMV_DEV EvalRes eval_cands(const FrameDev &F, MBLocal *L, MEState *me, const u
 {
     return prim_eval_list(F, L, enc, me->i_pixel, me->xoff, me->yoff, n, flags, me->mvp[0], me->mvp[1]);
 }
-/* The functions of the search are templates on TESA: 1 = the instance that can run --me tesa (its own kernel), 0 = the
- * instance every other method runs, with that method's code and -- more important -- its run-time choice of the
- * full-pel metric compiled out (the primitives are specialised on constant flags; with the flags a run-time value the
- * other methods lost 11 %).
+/* The functions of the search are templates on VARIANT, a mask of what the instance has compiled in (pcamv_variant.h).  V_TESA:
+ * the instance that can run --me tesa (its own kernel); without it, the instance every other method runs, with that method's
+ * code and -- more important -- its run-time choice of the full-pel metric compiled out (the primitives are specialised on
+ * constant flags; with the flags a run-time value the other methods lost 11 %).  V_RD: the RD mode decision of --subme >= 6
+ * (a kernel of its own as well: its code would otherwise cost the search kernel registers).
  * encoder.c mbcmp_init: with --me tesa and subme > 1 the "full-pel" comparisons of the search (fpelcmp: COST_MV,
  * COST_MV_HPEL, the half-pel rounds of refine_subpel) are SATD instead of SAD.  FPEL_LIST: flags of a list of full-pel
  * candidates, FPEL_SAD: flags of a quarter-pel list scored with that metric. */
-/* The template parameter is a variant mask: bit 0 = the --me tesa instance, bit 1 = the instance with the RD mode decision of
- * --subme >= 6 compiled in (a kernel of its own as well: its code would otherwise cost the search kernel registers). */
-#define FPEL_SATD ((TESA & 1) && F.me_method == PCAMV_ME_TESA && F.subme > 1)
-#define MBRD_ON ((TESA & 2) && F.b_mbrd)
-/* bit 3: the instance that prices sub-8x8 partitions with x264_rd_cost_part (a build of its own: compiled into the others its code costs
+#define FPEL_SATD ((VARIANT & V_TESA) && F.me_method == PCAMV_ME_TESA && F.subme > 1)
+#define MBRD_ON ((VARIANT & V_RD) && F.b_mbrd)
+/* V_RD_PSUB: the instance that prices sub-8x8 partitions with x264_rd_cost_part (a build of its own: compiled into the others its code costs
  * them registers -- 22 spilled VGPRs and 135 more parked scalars in the 4-waves-per-SIMD build) */
-#define RD_PSUB_ON ((TESA & 8) && (F.inter & PCAMV_ANALYSE_PSUB8x8))
+#define RD_PSUB_ON ((VARIANT & V_RD_PSUB) && (F.inter & PCAMV_ANALYSE_PSUB8x8))
 #define FPEL_LIST (FPEL_SATD ? EV_SATD : EV_FPEL)
 #define FPEL_SAD (FPEL_SATD ? EV_SATD : 0)
 /* the n listed full-pel candidates folded into the running best, in list order (strict <) */
-template <int TESA>
+template <int VARIANT>
 PCAMV_DEV int fpel_fold(const FrameDev &F, MBLocal *L, MEState *me, int &bmx, int &bmy, int &bcost, int n)
 {
     EvalRes r = eval_cands(F, L, me, L->fenc, n, FPEL_LIST);
@@ -242,14 +241,14 @@ PCAMV_DEV int fpel_fold(const FrameDev &F, MBLocal *L, MEState *me, int &bmx, in
 #define FSET(c, X, Y) (L->cxy[c] = CAND_PACK((X) * 4, (Y) * 4))
 #define TRY4(ox, oy, a0, a1, b0, b1, c0, c1, d0, d1) { \
         FSET(0, (ox) + (a0), (oy) + (a1)); FSET(1, (ox) + (b0), (oy) + (b1)); FSET(2, (ox) + (c0), (oy) + (c1)); FSET(3, (ox) + (d0), (oy) + (d1)); \
-        fpel_fold<TESA>(F, L, me, bmx, bmy, bcost, 4); }
+        fpel_fold<VARIANT>(F, L, me, bmx, bmy, bcost, 4); }
 #define TRY8(ox, oy, a0, a1, b0, b1, c0, c1, d0, d1, e0, e1, f0, f1, g0, g1, h0, h1) { \
         FSET(0, (ox) + (a0), (oy) + (a1)); FSET(1, (ox) + (b0), (oy) + (b1)); FSET(2, (ox) + (c0), (oy) + (c1)); FSET(3, (ox) + (d0), (oy) + (d1)); \
         FSET(4, (ox) + (e0), (oy) + (e1)); FSET(5, (ox) + (f0), (oy) + (f1)); FSET(6, (ox) + (g0), (oy) + (g1)); FSET(7, (ox) + (h0), (oy) + (h1)); \
-        fpel_fold<TESA>(F, L, me, bmx, bmy, bcost, 8); }
+        fpel_fold<VARIANT>(F, L, me, bmx, bmy, bcost, 8); }
 #define CHECK_MVRANGE(mx, my) ((mx) >= mv_x_min && (mx) <= mv_x_max && (my) >= mv_y_min && (my) <= mv_y_max)
 
-template <int TESA>
+template <int VARIANT>
 PCAMV_DEV void refine_subpel(const FrameDev &F, MBLocal *L, MEState *me, int hpel_iters, int qpel_iters, int b_refine_qpel)
 {
     const int ip = me->i_pixel;
@@ -315,7 +314,7 @@ PCAMV_DEV void refine_subpel(const FrameDev &F, MBLocal *L, MEState *me, int hpe
 
 /* the two arms of the UMH cross (me.c:331-357 CROSS): +i, -i for i = start, start+2, .. < max, first
  * along x then along y; candidates beyond the search window are skipped */
-template <int TESA>
+template <int VARIANT>
 PCAMV_DEV void cross_search(const FrameDev &F, MBLocal *L, MEState *me, int &bmx, int &bmy, int &bcost,
                             int omx, int omy, int start, int x_max, int y_max,
                             int mv_x_min, int mv_x_max, int mv_y_min, int mv_y_max)
@@ -332,11 +331,11 @@ PCAMV_DEV void cross_search(const FrameDev &F, MBLocal *L, MEState *me, int &bmx
             int ok = isy ? (neg ? y >= mv_y_min : y <= mv_y_max) : (neg ? x >= mv_x_min : x <= mv_x_max);
             L->cxy[c] = ok ? CAND_PACK(x * 4, y * 4) : CAND_NONE;
         }
-        fpel_fold<TESA>(F, L, me, bmx, bmy, bcost, n);
+        fpel_fold<VARIANT>(F, L, me, bmx, bmy, bcost, n);
     }
 }
 
-template <int TESA>
+template <int VARIANT>
 PCAMV_DEV void hex_search(const FrameDev &F, MBLocal *L, MEState *me, int &bmx, int &bmy, int &bcost, int i_me_range,
                           int mv_x_min, int mv_x_max, int mv_y_min, int mv_y_max)
 {
@@ -365,7 +364,7 @@ PCAMV_DEV void hex_search(const FrameDev &F, MBLocal *L, MEState *me, int &bmx, 
 /* Hadamard exhaustive search (me.c:525-600): the window of ESA, but a position is only remembered when its ADS and
  * then its SAD pass thresholds relative to the best SAD so far; the list is pruned to me_range / 2 entries and those
  * are scored with the search's comparison function (SATD above subme 1).  */
-template <int TESA>
+template <int VARIANT>
 PCAMV_DEV void tesa_search(const FrameDev &F, MBLocal *L, MEState *me, int &bmx, int &bmy, int &bcost, int i_me_range,
                                       int mv_x_min, int mv_x_max, int mv_y_min, int mv_y_max)
 {
@@ -387,11 +386,11 @@ PCAMV_DEV void tesa_search(const FrameDev &F, MBLocal *L, MEState *me, int &bmx,
             bsad += ycost;
         }
         n = prim_tesa_select(L, n, i_me_range / 2, bsad, sad_thresh, min_x, min_y);
-        if (n > 0) fpel_fold<TESA>(F, L, me, bmx, bmy, bcost, n);
+        if (n > 0) fpel_fold<VARIANT>(F, L, me, bmx, bmy, bcost, n);
     }
 }
 
-template <int TESA>
+template <int VARIANT>
 PCAMV_DEV void me_search_body(const FrameDev &F, MBLocal *L, MEState *me, int (*mvc)[2], int i_mvc);
 #if defined(PCAMV_SEARCH_CALL) && !defined(PCAMV_HOST_EMU)
 /* -DPCAMV_SEARCH_CALL (off; kept for measurements): the search of one partition as a REAL function -- 5 to 9 calls per
@@ -399,7 +398,7 @@ PCAMV_DEV void me_search_body(const FrameDev &F, MBLocal *L, MEState *me, int (*
  * again from constant memory (a reference to the caller's copy would pin that copy in scratch).  Measured in the
  * 4-waves-per-SIMD build of the RD kernel: 13.7 against 14.4 M MB/s at 4096 chains -- the callee spills as much as the inlined
  * code did (195 against 149 registers over caller + callee), and the descriptor reload and the LDS hand-over are new. */
-template <int TESA>
+template <int VARIANT>
 static __device__ __noinline__ void me_search_fn(MBLocal *L, int i_mvc_)
 {
     const unsigned long long fp = (unsigned long long)L->fdesc;
@@ -410,9 +409,9 @@ static __device__ __noinline__ void me_search_fn(MBLocal *L, int i_mvc_)
 #pragma unroll
     for (int i = 0; i < (int)(sizeof(FrameDev) / 4); i++) dst[i] = src[i];
     const FrameDev &F = Fm;
-    me_search_body<TESA>(F, L, (MEState *)L->me_tmp, L->mvc_tmp, __builtin_amdgcn_readfirstlane(i_mvc_));
+    me_search_body<VARIANT>(F, L, (MEState *)L->me_tmp, L->mvc_tmp, __builtin_amdgcn_readfirstlane(i_mvc_));
 }
-template <int TESA>
+template <int VARIANT>
 PCAMV_DEV void me_search(const FrameDev &F, MBLocal *L, MEState *me, int (*mvc)[2], int i_mvc)
 {
     (void)F;
@@ -420,15 +419,15 @@ PCAMV_DEV void me_search(const FrameDev &F, MBLocal *L, MEState *me, int (*mvc)[
     *(MEState *)L->me_tmp = *me;
     for (int i = 0; i < i_mvc; i++) { L->mvc_tmp[i][0] = mvc[i][0]; L->mvc_tmp[i][1] = mvc[i][1]; }
     PCAMV_WAVE_SYNC();
-    me_search_fn<TESA>(L, i_mvc);
+    me_search_fn<VARIANT>(L, i_mvc);
     PCAMV_WAVE_SYNC();
     *me = *(MEState *)L->me_tmp;
 }
 #else
-template <int TESA>
-PCAMV_DEV void me_search(const FrameDev &F, MBLocal *L, MEState *me, int (*mvc)[2], int i_mvc) { me_search_body<TESA>(F, L, me, mvc, i_mvc); }
+template <int VARIANT>
+PCAMV_DEV void me_search(const FrameDev &F, MBLocal *L, MEState *me, int (*mvc)[2], int i_mvc) { me_search_body<VARIANT>(F, L, me, mvc, i_mvc); }
 #endif
-template <int TESA>
+template <int VARIANT>
 PCAMV_DEV void me_search_body(const FrameDev &F, MBLocal *L, MEState *me, int (*mvc)[2], int i_mvc)
 {
     const int ip = me->i_pixel;
@@ -461,11 +460,11 @@ PCAMV_DEV void me_search_body(const FrameDev &F, MBLocal *L, MEState *me, int (*
             int n = 6;
             FSET(2, pmx, pmy - 1); FSET(3, pmx, pmy + 1); FSET(4, pmx - 1, pmy); FSET(5, pmx + 1, pmy);
             if (pmx | pmy) { FSET(6, 0, -1); FSET(7, 0, 1); FSET(8, -1, 0); FSET(9, 1, 0); n = 10; }
-            fpel_fold<TESA>(F, L, me, bmx, bmy, bcost, n);
+            fpel_fold<VARIANT>(F, L, me, bmx, bmy, bcost, n);
             umh_ucost1 = imin(L->ccost[0], L->ccost[1]);
             umh_diamonds_done = 1;
         } else
-            fpel_fold<TESA>(F, L, me, bmx, bmy, bcost, 2);
+            fpel_fold<VARIANT>(F, L, me, bmx, bmy, bcost, 2);
     } else {
         /* full-pel test: the predictor (its MV bits not charged), then the candidates, then (0,0).
          * Candidates equal to the running best are listed too: their cost cannot be smaller. */
@@ -491,7 +490,7 @@ PCAMV_DEV void me_search_body(const FrameDev &F, MBLocal *L, MEState *me, int (*
             if (!CHECK_MVRANGE(bmx, bmy)) break;
         } while (++i < i_me_range);
     } else if (F.me_method == PCAMV_ME_HEX) {
-        hex_search<TESA>(F, L, me, bmx, bmy, bcost, i_me_range, mv_x_min, mv_x_max, mv_y_min, mv_y_max);
+        hex_search<VARIANT>(F, L, me, bmx, bmy, bcost, i_me_range, mv_x_min, mv_x_max, mv_y_min, mv_y_max);
     } else if (F.me_method == PCAMV_ME_ESA) {
         /* exhaustive search (me.c:489-622).  The reference walks the window row by row, drops
          * positions whose sum-of-block-DC difference (ADS, a lower bound of the SAD) plus MV bits
@@ -506,8 +505,8 @@ PCAMV_DEV void me_search_body(const FrameDev &F, MBLocal *L, MEState *me, int (*
             EvalRes r = prim_esa_window(F, L, ip, me->xoff, me->yoff, min_x, min_y, width, max_y - min_y + 1, me->mvp[0], me->mvp[1]);
             if (r.cost < bcost) { bcost = r.cost; bmx = min_x + r.idx % width; bmy = min_y + r.idx / width; }
         }
-    } else if ((TESA & 1) && F.me_method == PCAMV_ME_TESA) {
-        tesa_search<TESA>(F, L, me, bmx, bmy, bcost, i_me_range, mv_x_min, mv_x_max, mv_y_min, mv_y_max);
+    } else if ((VARIANT & V_TESA) && F.me_method == PCAMV_ME_TESA) {
+        tesa_search<VARIANT>(F, L, me, bmx, bmy, bcost, i_me_range, mv_x_min, mv_x_max, mv_y_min, mv_y_max);
     } else { /* UMH */
         int ucost1, ucost2, cross_start = 1, do_hex = 1, done = 0;
 #define SAD_THRESH(v) (bcost < ((v) >> size_shift_of(ip)))
@@ -527,7 +526,7 @@ PCAMV_DEV void me_search_body(const FrameDev &F, MBLocal *L, MEState *me, int (*
                 if (bcost == ucost1 && SAD_THRESH(500)) { done = 1; do_hex = 0; }
                 else if (bcost == ucost2) {
                     int range = (i_me_range >> 1) | 1;
-                    cross_search<TESA>(F, L, me, bmx, bmy, bcost, omx, omy, 3, range, range, mv_x_min, mv_x_max, mv_y_min, mv_y_max);
+                    cross_search<VARIANT>(F, L, me, bmx, bmy, bcost, omx, omy, 3, range, range, mv_x_min, mv_x_max, mv_y_min, mv_y_max);
                     TRY8(omx, omy, -1, -2, 1, -2, -2, -1, 2, -1, -2, 1, 2, 1, -1, 2, 1, 2);
                     if (bcost == ucost2) { done = 1; do_hex = 0; }
                     cross_start = range + 2;
@@ -548,7 +547,7 @@ PCAMV_DEV void me_search_body(const FrameDev &F, MBLocal *L, MEState *me, int (*
                     mvd_ctx = mvd < 10 * denom ? 0 : mvd < 20 * denom ? 1 : mvd < 40 * denom ? 2 : 3;
                     i_me_range = i_me_range * range_mul_of(mvd_ctx, sad_ctx) / 4;
                 }
-                cross_search<TESA>(F, L, me, bmx, bmy, bcost, omx, omy, cross_start, i_me_range, i_me_range / 2, mv_x_min, mv_x_max, mv_y_min, mv_y_max);
+                cross_search<VARIANT>(F, L, me, bmx, bmy, bcost, omx, omy, cross_start, i_me_range, i_me_range / 2, mv_x_min, mv_x_max, mv_y_min, mv_y_max);
                 TRY4(omx, omy, -2, -2, -2, 2, 2, -2, 2, 2);
                 /* 16-point hexagons at radii 4, 8, .. around the (fixed) cross result, me.c:404-457 */
                 omx = bmx; omy = bmy;
@@ -560,12 +559,12 @@ PCAMV_DEV void me_search_body(const FrameDev &F, MBLocal *L, MEState *me, int (*
                         int mx = omx + hex4_x(j) * i, my = omy + hex4_y(j) * i;
                         L->cxy[c] = CHECK_MVRANGE(mx, my) ? CAND_PACK(mx * 4, my * 4) : CAND_NONE;
                     }
-                    fpel_fold<TESA>(F, L, me, bmx, bmy, bcost, n);
+                    fpel_fold<VARIANT>(F, L, me, bmx, bmy, bcost, n);
                 }
                 if (!(bmy <= mv_y_max)) do_hex = 0;
             }
         }
-        if (do_hex) hex_search<TESA>(F, L, me, bmx, bmy, bcost, i_me_range, mv_x_min, mv_x_max, mv_y_min, mv_y_max);
+        if (do_hex) hex_search<VARIANT>(F, L, me, bmx, bmy, bcost, i_me_range, mv_x_min, mv_x_max, mv_y_min, mv_y_max);
 #undef SAD_THRESH
     }
 
@@ -573,14 +572,14 @@ PCAMV_DEV void me_search_body(const FrameDev &F, MBLocal *L, MEState *me, int (*
     else { me->mv[0] = bmx * 4; me->mv[1] = bmy * 4; me->cost = bcost; }
     me->cost_mv = MVCOSTX(me->mv[0]) + MVCOSTY(me->mv[1]);
     if (bmx == pmx && bmy == pmy && F.subme < 3) me->cost += me->cost_mv;
-    if (F.subme >= 2) refine_subpel<TESA>(F, L, me, subpel_iter_of(F.subme, 2), subpel_iter_of(F.subme, 3), 0);
+    if (F.subme >= 2) refine_subpel<VARIANT>(F, L, me, subpel_iter_of(F.subme, 2), subpel_iter_of(F.subme, 3), 0);
     else if (me->mv[1] > L->mv_max_spel[1]) me->mv[1] = L->mv_max_spel[1];
 }
 
-template <int TESA>
+template <int VARIANT>
 PCAMV_DEV void me_refine_qpel(const FrameDev &F, MBLocal *L, MEState *me)
 {
-    refine_subpel<TESA>(F, L, me, subpel_iter_of(F.subme, 0), subpel_iter_of(F.subme, 1), 1);
+    refine_subpel<VARIANT>(F, L, me, subpel_iter_of(F.subme, 0), subpel_iter_of(F.subme, 1), 1);
 }
 
 /* ---------------------------------------------------------------- macroblock (re-)encode */
@@ -912,7 +911,7 @@ PCAMV_DEV int rd_trial(const FrameDev &F, MBLocal *L, int counts)
     }
     return cost;
 }
-template <int TESA>
+template <int VARIANT>
 PCAMV_DEV void analyse_p_rd(const FrameDev &F, MBLocal *L, struct Analysis *a, int i_satd)
 {
     const int thresh = i_satd * 5 / 4;
@@ -930,7 +929,7 @@ PCAMV_DEV void analyse_p_rd(const FrameDev &F, MBLocal *L, struct Analysis *a, i
 #ifndef PCAMV_HOST_EMU
         asm volatile("" : "+s"(inter_now));
 #endif
-        if ((TESA & 8) && (inter_now & PCAMV_ANALYSE_PSUB8x8)) {
+        if ((VARIANT & V_RD_PSUB) && (inter_now & PCAMV_ANALYSE_PSUB8x8)) {
             /* analyse.c:2150-2180: per 8x8 the sub-partition shapes whose SATD cost is within 5/4 of the best are priced with
              * x264_rd_cost_part, the 8x8 shape itself only if another one was.  No update of the whole cache here: it holds what the
              * last trial / search left, and the trials of one 8x8 see what the others' left behind (non-zero flags, MV differences) */
@@ -971,7 +970,7 @@ PCAMV_DEV void entropy_commit(const FrameDev &F, MBLocal *L, int walked)
     prim_rd_commit(F, L, skip);
 }
 
-template <int TESA>
+template <int VARIANT>
 PCAMV_DEV int analyse_p16x16(const FrameDev &F, MBLocal *L, Analysis *a, int b_try_pskip)
 {
     MEState me;
@@ -979,7 +978,7 @@ PCAMV_DEV int analyse_p16x16(const FrameDev &F, MBLocal *L, Analysis *a, int b_t
     predict_mv_16x16(L, 0, me.mvp);
     for (int i = 0; i < 9; i++) { L->mvc16[i][0] = 0; L->mvc16[i][1] = 0; }
     int i_mvc = predict_mv_ref16x16(F, L, L->mvc16);
-    me_search<TESA>(F, L, &me, L->mvc16, i_mvc);
+    me_search<VARIANT>(F, L, &me, L->mvc16, i_mvc);
     if (b_try_pskip && me.cost - me.cost_mv < 300 * F.lambda &&
         iabs(me.mv[0] - L->pskip_mv[0]) + iabs(me.mv[1] - L->pskip_mv[1]) <= 1 && probe_pskip(F, L)) {
         L->i_type = PCAMV_P_SKIP;
@@ -1001,7 +1000,7 @@ PCAMV_DEV int analyse_p16x16(const FrameDev &F, MBLocal *L, Analysis *a, int b_t
     }
     return 0;
 }
-template <int TESA>
+template <int VARIANT>
 PCAMV_DEV void analyse_p8x8(const FrameDev &F, MBLocal *L, Analysis *a)
 {
     int i_mvc = 1;
@@ -1012,7 +1011,7 @@ PCAMV_DEV void analyse_p8x8(const FrameDev &F, MBLocal *L, Analysis *a)
         int x8 = i % 2, y8 = i / 2;
         me_setup(me, PIX_8x8, 8 * x8, 8 * y8);
         predict_mv(L, 4 * i, 2, me->mvp);
-        me_search<TESA>(F, L, me, a->mvc, i_mvc);
+        me_search<VARIANT>(F, L, me, a->mvc, i_mvc);
         cache_mv_set(L, 2 * x8, 2 * y8, 2, 2, me->mv[0], me->mv[1]);
         a->mvc[i_mvc][0] = me->mv[0]; a->mvc[i_mvc][1] = me->mv[1]; i_mvc++;
         me->cost += F.lambda * 1;
@@ -1020,7 +1019,7 @@ PCAMV_DEV void analyse_p8x8(const FrameDev &F, MBLocal *L, Analysis *a)
     a->cost8x8 = a->me8x8[0].cost + a->me8x8[1].cost + a->me8x8[2].cost + a->me8x8[3].cost;
     for (int i = 0; i < 4; i++) L->sub_part[i] = PCAMV_D_L0_8x8;
 }
-template <int TESA>
+template <int VARIANT>
 PCAMV_DEV void analyse_p16x8(const FrameDev &F, MBLocal *L, Analysis *a)
 {
     L->i_partition = PCAMV_D_16x8;
@@ -1032,13 +1031,13 @@ PCAMV_DEV void analyse_p16x8(const FrameDev &F, MBLocal *L, Analysis *a)
         mvc[2][0] = a->mvc[2 * i + 2][0]; mvc[2][1] = a->mvc[2 * i + 2][1];
         cache_ref_set(L, 0, 2 * i, 4, 2, 0);
         predict_mv(L, 8 * i, 4, me.mvp);
-        me_search<TESA>(F, L, &me, mvc, 3);
+        me_search<VARIANT>(F, L, &me, mvc, 3);
         a->me16x8[i] = me;
         cache_mv_set(L, 0, 2 * i, 4, 2, me.mv[0], me.mv[1]);
     }
     a->cost16x8 = a->me16x8[0].cost + a->me16x8[1].cost;
 }
-template <int TESA>
+template <int VARIANT>
 PCAMV_DEV void analyse_p8x16(const FrameDev &F, MBLocal *L, Analysis *a)
 {
     L->i_partition = PCAMV_D_8x16;
@@ -1050,13 +1049,13 @@ PCAMV_DEV void analyse_p8x16(const FrameDev &F, MBLocal *L, Analysis *a)
         mvc[2][0] = a->mvc[i + 3][0]; mvc[2][1] = a->mvc[i + 3][1];
         cache_ref_set(L, 2 * i, 0, 2, 4, 0);
         predict_mv(L, 4 * i, 2, me.mvp);
-        me_search<TESA>(F, L, &me, mvc, 3);
+        me_search<VARIANT>(F, L, &me, mvc, 3);
         a->me8x16[i] = me;
         cache_mv_set(L, 2 * i, 0, 2, 4, me.mv[0], me.mv[1]);
     }
     a->cost8x16 = a->me8x16[0].cost + a->me8x16[1].cost;
 }
-template <int TESA>
+template <int VARIANT>
 PCAMV_DEV void analyse_sub8x8(const FrameDev &F, MBLocal *L, Analysis *a, int i8, int pixel)
 {
     L->i_partition = PCAMV_D_8x8;
@@ -1069,7 +1068,7 @@ PCAMV_DEV void analyse_sub8x8(const FrameDev &F, MBLocal *L, Analysis *a, int i8
         int mvc[1][2];
         const MEState *cand = pixel == PIX_4x4 ? &a->me8x8[i8] : &a->me4x4[i8][0];
         mvc[0][0] = cand->mv[0]; mvc[0][1] = cand->mv[1];
-        me_search<TESA>(F, L, me, mvc, k == 0);
+        me_search<VARIANT>(F, L, me, mvc, k == 0);
         cache_mv_set(L, blk_x_of(idx), blk_y_of(idx), pixel == PIX_8x4 ? 2 : 1, pixel == PIX_4x8 ? 2 : 1, me->mv[0], me->mv[1]);
         cost += me->cost;
     }
@@ -1217,12 +1216,12 @@ PCAMV_DEV int carrier_of_block(int i_type, int i_partition, const uint8_t *sub, 
  * motion to the frame arrays its right/lower neighbours read.  Writes the record without the
  * RCA fields; the search-time mvp of every carrier slot goes to mvp_aux for phase B.
  * Three stages, so that a schedule can hand the macroblock's successor its motion as early as it is known (the speculative
- * raster schedule of the RD instance, pcamv_kernels.hip.h):
+ * raster schedule of the RD instance, pcamv_flow.hip.h):
  *   analyse_s16     early P_SKIP, else the 16x16 search (returns 1 for a skipped macroblock: nothing else follows)
  *   analyse_s_rest  the other partitions' searches and the decision by SATD cost
  *   analyse_decide  quarter-pel refinement of the decided partition, or -- --subme >= 6 -- the intra thresholds and the RD trials:
  *                   the only stage that reads what the entropy coder left behind in the macroblock coded before this one */
-template <int TESA>
+template <int VARIANT>
 PCAMV_DEV int analyse_s16(const FrameDev &F, MBLocal *L, Analysis *a)
 {
     int b_skip = 0, b_try_pskip = 0;
@@ -1241,16 +1240,16 @@ PCAMV_DEV int analyse_s16(const FrameDev &F, MBLocal *L, Analysis *a)
             b_skip = probe_pskip(F, L);
     }
     if (b_skip) { L->i_type = PCAMV_P_SKIP; L->i_partition = PCAMV_D_16x16; return 1; }
-    return analyse_p16x16<TESA>(F, L, a, b_try_pskip);
+    return analyse_p16x16<VARIANT>(F, L, a, b_try_pskip);
 }
-template <int TESA>
+template <int VARIANT>
 PCAMV_DEV void analyse_s_rest(const FrameDev &F, MBLocal *L, Analysis *a)
 {
     int i_cost;
     const unsigned flags = F.inter;
     int i_type = PCAMV_P_L0, i_partition = PCAMV_D_16x16;
     const unsigned long long t_b = PROF_T();
-    if (flags & PCAMV_ANALYSE_PSUB16x16) analyse_p8x8<TESA>(F, L, a);
+    if (flags & PCAMV_ANALYSE_PSUB16x16) analyse_p8x8<VARIANT>(F, L, a);
     PROF_ADD(7, t_b);
     const unsigned long long t_c = PROF_T();
     i_cost = a->me16x16.cost;
@@ -1258,13 +1257,13 @@ PCAMV_DEV void analyse_s_rest(const FrameDev &F, MBLocal *L, Analysis *a)
         if (flags & PCAMV_ANALYSE_PSUB8x8) {
             i_type = PCAMV_P_8x8; i_partition = PCAMV_D_8x8; i_cost = a->cost8x8;
             for (int i = 0; i < 4; i++) {
-                analyse_sub8x8<TESA>(F, L, a, i, PIX_4x4);
+                analyse_sub8x8<VARIANT>(F, L, a, i, PIX_4x4);
                 if (a->cost4x4[i] < a->me8x8[i].cost) {
                     int c8 = a->cost4x4[i];
                     L->sub_part[i] = PCAMV_D_L0_4x4;
-                    analyse_sub8x8<TESA>(F, L, a, i, PIX_8x4);
+                    analyse_sub8x8<VARIANT>(F, L, a, i, PIX_8x4);
                     if (a->cost8x4[i] < c8) { c8 = a->cost8x4[i]; L->sub_part[i] = PCAMV_D_L0_8x4; }
-                    analyse_sub8x8<TESA>(F, L, a, i, PIX_4x8);
+                    analyse_sub8x8<VARIANT>(F, L, a, i, PIX_4x8);
                     if (a->cost4x8[i] < c8) { c8 = a->cost4x8[i]; L->sub_part[i] = PCAMV_D_L0_4x8; }
                     i_cost += c8 - a->me8x8[i].cost;
                 }
@@ -1274,16 +1273,16 @@ PCAMV_DEV void analyse_s_rest(const FrameDev &F, MBLocal *L, Analysis *a)
         }
     }
     if ((flags & PCAMV_ANALYSE_PSUB16x16) && a->cost8x8 < a->me16x16.cost + a->me8x8[1].cost_mv + a->me8x8[2].cost_mv) {
-        analyse_p16x8<TESA>(F, L, a);
+        analyse_p16x8<VARIANT>(F, L, a);
         if (a->cost16x8 < i_cost) { i_cost = a->cost16x8; i_type = PCAMV_P_L0; i_partition = PCAMV_D_16x8; }
-        analyse_p8x16<TESA>(F, L, a);
+        analyse_p8x16<VARIANT>(F, L, a);
         if (a->cost8x16 < i_cost) { i_cost = a->cost8x16; i_type = PCAMV_P_L0; i_partition = PCAMV_D_8x16; }
     }
     L->i_partition = i_partition;
     a->sel_type = i_type; a->sel_part = i_partition; a->sel_cost = i_cost;
     PROF_ADD(8, t_c);
 }
-template <int TESA>
+template <int VARIANT>
 PCAMV_DEV void analyse_decide(const FrameDev &F, MBLocal *L, Analysis *a)
 {
     int i_type = a->sel_type, i_partition = a->sel_part, i_cost = a->sel_cost;
@@ -1315,7 +1314,7 @@ PCAMV_DEV void analyse_decide(const FrameDev &F, MBLocal *L, Analysis *a)
         } else intra_analyse(F, L, i_cost, &i16, &i4);
         PROF_ADD(16, t_i);
         const unsigned long long t_rd = PROF_T();
-        analyse_p_rd<TESA>(F, L, a, imin(i_cost, imin(i16, i4)));
+        analyse_p_rd<VARIANT>(F, L, a, imin(i_cost, imin(i16, i4)));
         PROF_ADD(17, t_rd);
         i_type = PCAMV_P_L0; i_partition = PCAMV_D_16x16; i_cost = a->me16x16.cost;
         if (a->cost16x8 < i_cost) { i_cost = a->cost16x8; i_partition = PCAMV_D_16x8; }
@@ -1323,29 +1322,29 @@ PCAMV_DEV void analyse_decide(const FrameDev &F, MBLocal *L, Analysis *a)
         if (F.embed && a->cost8x8 < i_cost) { i_cost = a->cost8x8; i_partition = PCAMV_D_8x8; i_type = PCAMV_P_8x8; }
         L->i_partition = i_partition;
     } else
-    if (i_partition == PCAMV_D_16x16) me_refine_qpel<TESA>(F, L, &a->me16x16);
-    else if (i_partition == PCAMV_D_16x8) { me_refine_qpel<TESA>(F, L, &a->me16x8[0]); me_refine_qpel<TESA>(F, L, &a->me16x8[1]); }
-    else if (i_partition == PCAMV_D_8x16) { me_refine_qpel<TESA>(F, L, &a->me8x16[0]); me_refine_qpel<TESA>(F, L, &a->me8x16[1]); }
+    if (i_partition == PCAMV_D_16x16) me_refine_qpel<VARIANT>(F, L, &a->me16x16);
+    else if (i_partition == PCAMV_D_16x8) { me_refine_qpel<VARIANT>(F, L, &a->me16x8[0]); me_refine_qpel<VARIANT>(F, L, &a->me16x8[1]); }
+    else if (i_partition == PCAMV_D_8x16) { me_refine_qpel<VARIANT>(F, L, &a->me8x16[0]); me_refine_qpel<VARIANT>(F, L, &a->me8x16[1]); }
     else
         for (int i = 0; i < 4; i++)
             switch (L->sub_part[i]) {
-            case PCAMV_D_L0_8x8: me_refine_qpel<TESA>(F, L, &a->me8x8[i]); break;
-            case PCAMV_D_L0_8x4: me_refine_qpel<TESA>(F, L, &a->me8x4[i][0]); me_refine_qpel<TESA>(F, L, &a->me8x4[i][1]); break;
-            case PCAMV_D_L0_4x8: me_refine_qpel<TESA>(F, L, &a->me4x8[i][0]); me_refine_qpel<TESA>(F, L, &a->me4x8[i][1]); break;
-            default: for (int k = 0; k < 4; k++) me_refine_qpel<TESA>(F, L, &a->me4x4[i][k]); break;
+            case PCAMV_D_L0_8x8: me_refine_qpel<VARIANT>(F, L, &a->me8x8[i]); break;
+            case PCAMV_D_L0_8x4: me_refine_qpel<VARIANT>(F, L, &a->me8x4[i][0]); me_refine_qpel<VARIANT>(F, L, &a->me8x4[i][1]); break;
+            case PCAMV_D_L0_4x8: me_refine_qpel<VARIANT>(F, L, &a->me4x8[i][0]); me_refine_qpel<VARIANT>(F, L, &a->me4x8[i][1]); break;
+            default: for (int k = 0; k < 4; k++) me_refine_qpel<VARIANT>(F, L, &a->me4x4[i][k]); break;
             }
     L->i_type = i_type;
     PROF_ADD(9, t_d);
 }
-template <int TESA>
+template <int VARIANT>
 PCAMV_DEV void analyse_mb_search(const FrameDev &F, MBLocal *L, Analysis *a)
 {
     const unsigned long long t_a = PROF_T();
-    const int skip = analyse_s16<TESA>(F, L, a);
+    const int skip = analyse_s16<VARIANT>(F, L, a);
     PROF_ADD(6, t_a);
     if (!skip) {
-        analyse_s_rest<TESA>(F, L, a);
-        analyse_decide<TESA>(F, L, a);
+        analyse_s_rest<VARIANT>(F, L, a);
+        analyse_decide<VARIANT>(F, L, a);
     }
     update_cache(L, a);
 }

@@ -23,11 +23,12 @@
  * the whole launch -- in scratch, reloaded at ~800 sites of the RD instance, every reload a memory round trip of its own in front
  * of the instruction that needs it.  Recomputing them where they are used is one or two VALU instructions. */
 __device__ __forceinline__ int pcamv_lane_id(void) { int l = (int)(threadIdx.x & 63); asm volatile("" : "+v"(l)); return l; }
-#ifdef PCAMV_RD_LO      /* the one-wave-per-SIMD build has the registers to keep them (183 in use): hoisted is 1-2 % faster there */
-#define LANE() ((int)(threadIdx.x & 63))
-#else
-#define LANE() pcamv_lane_id()
+/* PCAMV_RD_LO, a compile-time constant: a build for one wave per SIMD (pcamv_rd.hip sets it from the build's row of PCAMV_RD_BUILDS)
+ * has the registers to keep them (183 in use): hoisted is 1-2 % faster there */
+#ifndef PCAMV_RD_LO
+#define PCAMV_RD_LO 0
 #endif
+#define LANE() (PCAMV_RD_LO ? (int)(threadIdx.x & 63) : pcamv_lane_id())
 /* clamp to [0,255] of an already shifted value.  The empty asm keeps hipcc (ROCm 7.2) from fusing
  * shift + clamp of two neighbours into v_ashr_pk_u8_i32: the code it emits around that gfx950
  * instruction ORs further bytes into the destination assuming bits [31:16] come back zero, but

@@ -7,8 +7,10 @@
  * code costs the search of --subme <= 5 registers (141 spilled VGPRs, 552 bytes of scratch per lane when it was), and in a
  * translation unit of its own so that the library's instances compile side by side.
  *
- * Two builds of it (this file, and pcamv_rd_lo.hip which includes it with PCAMV_RD_LO defined), differing in the register
- * budget only.  With CABAC a frame is ONE chain of macroblocks (the context states), so a batch of G GOPs keeps G waves busy
+ * Six builds of it, one translation unit each: this file is the 4-waves-per-SIMD build "hi", and pcamv_rd_lo.hip, pcamv_rd_spec*.hip
+ * and pcamv_rd_tesa.hip include it with PCAMV_RD_BUILD naming their row of PCAMV_RD_BUILDS (pcamv_rd_select.h), which says what a
+ * build is: the waves per SIMD its registers are held to and the variant of the control code.  The two plain ones differ in the
+ * register budget only.  With CABAC a frame is ONE chain of macroblocks (the context states), so a batch of G GOPs keeps G waves busy
  * (+ the RCA work they hand off to whoever is free):
  *   - "lo", 1 wave per SIMD, every register (342 VGPRs in use, lane-derived constants hoisted out of the macroblock loop):
  *     the fastest macroblock.  Used while the chains are few (G <= 2 x CUs): G=64 874 ms per 1080p step, 512: 943 ms = 4.43 M MB/s;
@@ -18,46 +20,37 @@
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#define PCAMV_RD_TU 1
+#include "pcamv_rd_select.h"
+#ifndef PCAMV_RD_BUILD
+#define PCAMV_RD_BUILD hi
+#endif
+#define RD_ID_(id) RD_##id
+#define RD_ID(id) RD_ID_(id)
+static constexpr int RD_BUILD = RD_ID(PCAMV_RD_BUILD);         /* this unit's row of PCAMV_RD_BUILDS */
+#ifdef PCAMV_RD_OCC                 /* development: the registers of the hi build re-budgeted for an experiment (tools/dbg/build_fast.sh, EXTRA=-DPCAMV_RD_OCC=n) */
+static constexpr int RD_OCC = RD_BUILD == RD_hi ? PCAMV_RD_OCC : rd_build_defs[RD_BUILD].occ;
+#else
+static constexpr int RD_OCC = rd_build_defs[RD_BUILD].occ;
+#endif
+static constexpr int RD_VARIANT = rd_build_defs[RD_BUILD].variant;
+/* pcamv_prims_gpu.h LANE(): a build for one wave per SIMD has the registers to keep what is computed from the lane number */
+static constexpr bool RD_ONE_WAVE = rd_build_defs[RD_BUILD].occ == 1;
+#define PCAMV_RD_LO RD_ONE_WAVE
 #define PCAMV_RESIDUAL_CALL 1      /* pcamv_prims_rd_gpu.h: the CABAC residual walk as a function of its own */
-/* variant mask of the control code (pcamv_logic.h): 2 = RD mode decision, 4 = speculative raster chain, 8 = sub-8x8 partitions priced by
- * x264_rd_cost_part -- only in the two one-wave-per-SIMD builds, which have the registers for it (compiled into the 4-waves-per-SIMD
- * build it cost 22 spilled VGPRs); batches with --partitions p4x4 at --subme >= 6 run on those (pcamv_gpu_batch_create) */
-#if defined(PCAMV_RD_SPEC)          /* pcamv_rd_spec*.hip: the speculative raster chain, PCAMV_RD_SPEC = waves per SIMD (1, 2 or 4) */
-#if PCAMV_RD_SPEC == 1
-#define PCAMV_RD_LO 1
-#define RD_NAME(x) x##_spec
-#define PCAMV_RD_VARIANT 14
-#elif PCAMV_RD_SPEC == 2
-#define RD_NAME(x) x##_spec2
-#define PCAMV_RD_VARIANT 6
-#else
-#define RD_NAME(x) x##_spec4
-#define PCAMV_RD_VARIANT 6
-#endif
-#define PCAMV_RD_OCC PCAMV_RD_SPEC
-#elif defined(PCAMV_RD_TESA)        /* pcamv_rd_tesa.hip: the RD mode decision after the Hadamard exhaustive search (--me tesa), one wave per SIMD */
-#define PCAMV_RD_LO 1
-#define PCAMV_RD_OCC 1
-#define PCAMV_RD_VARIANT 11
-#define RD_NAME(x) x##_tesa
-#elif defined(PCAMV_RD_LO)
-#define PCAMV_RD_OCC 1
-#define PCAMV_RD_VARIANT 10
-#define RD_NAME(x) x##_lo
-#else
-#ifndef PCAMV_RD_OCC
-#define PCAMV_RD_OCC 4
-#endif
-#define RD_NAME(x) x
-#endif
-#include "pcamv_kernels.hip.h"
+#include "pcamv_flow.hip.h"
 
-void RD_NAME(pcamv_launch_flow_rd)(unsigned waves, hipStream_t st, const FrameDev *dF, const FlowDev &fl)
+static __global__ void __launch_bounds__(64, RD_OCC) k_analyse_flow_rd(const FrameDev *__restrict__ Fs, FlowDev fl)
+{
+    __shared__ MBLocal L;
+    __shared__ Analysis A;
+    flow_loop<0, RD_VARIANT>(Fs, fl, L, &A, nullptr);
+}
+
+template <> void pcamv_launch_flow_rd<RD_BUILD>(unsigned waves, hipStream_t st, const FrameDev *dF, const FlowDev &fl)
 {
     hipLaunchKernelGGL(k_analyse_flow_rd, dim3(waves), dim3(64), 0, st, dF, fl);
 }
-int RD_NAME(pcamv_flow_rd_waves_per_cu)(void)
+template <> int pcamv_flow_rd_waves_per_cu<RD_BUILD>(void)
 {
     int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_analyse_flow_rd, 64, 0) != hipSuccess) return -1;
@@ -65,7 +58,7 @@ int RD_NAME(pcamv_flow_rd_waves_per_cu)(void)
 }
 #ifdef PCAMV_PROF
 /* the phase timers are per translation unit (static __device__): this instance's */
-int RD_NAME(pcamv_rd_prof_fetch)(unsigned long long *out, int reset)
+template <> int pcamv_rd_prof_fetch<RD_BUILD>(unsigned long long *out, int reset)
 {
     if (hipMemcpyFromSymbol(out, HIP_SYMBOL(pcamv_prof), sizeof(unsigned long long) * PCAMV_PROF_N) != hipSuccess) return -1;
     if (reset) { unsigned long long z[PCAMV_PROF_N] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(pcamv_prof), z, sizeof(z)) != hipSuccess) return -1; }

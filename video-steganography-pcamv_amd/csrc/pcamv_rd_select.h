@@ -8,13 +8,32 @@
 #define PCAMV_RD_SELECT_H
 #include <stdlib.h>
 #include <string.h>
+#include "pcamv_variant.h"
 
-/* X(id, suffix of the build's host entry points (pcamv_rd.hip RD_NAME), waves per SIMD of the speculative chain or 0: plain chain);
+/* What each build is, stated here only: X(id, waves per SIMD its registers are held to, variant of the control code).  The unit of
+ * a build (pcamv_rd*.hip) names its row and compiles the kernel from it, pcamv_gpu.hip makes its table of launchers from the list;
  * PCAMV_RD_INSTANCE names a build by its id */
-#define PCAMV_RD_BUILDS(X) X(hi, , 0) X(lo, _lo, 0) X(spec, _spec, 1) X(spec2, _spec2, 2) X(spec4, _spec4, 4) X(tesa, _tesa, 0)
-#define PCAMV_RD_ENUM(id, sfx, spec) RD_##id,
+#define PCAMV_RD_BUILDS(X) \
+    X(hi,    4, V_RD) \
+    X(lo,    1, V_RD | V_RD_PSUB) \
+    X(spec,  1, V_RD | V_SPEC | V_RD_PSUB) \
+    X(spec2, 2, V_RD | V_SPEC) \
+    X(spec4, 4, V_RD | V_SPEC) \
+    X(tesa,  1, V_TESA | V_RD | V_RD_PSUB)
+#define PCAMV_RD_ENUM(id, occ, variant) RD_##id,
 enum { PCAMV_RD_BUILDS(PCAMV_RD_ENUM) RD_N_BUILDS };
 #undef PCAMV_RD_ENUM
+struct RdBuildDef { int occ, variant; };
+#define PCAMV_RD_DEF(id, occ, variant) {occ, variant},
+static constexpr RdBuildDef rd_build_defs[RD_N_BUILDS] = {PCAMV_RD_BUILDS(PCAMV_RD_DEF)};
+#undef PCAMV_RD_DEF
+/* waves per SIMD of a build's speculative raster chain, 0: plain chain */
+static constexpr int rd_build_spec(int build) { return rd_build_defs[build].variant & V_SPEC ? rd_build_defs[build].occ : 0; }
+static constexpr bool rd_build_has(int build, int bits) { return (rd_build_defs[build].variant & bits) == bits; }
+/* what rd_select (below) takes for granted of the rows it returns */
+static_assert(rd_build_has(RD_tesa, V_TESA | V_RD_PSUB) && rd_build_has(RD_spec, V_SPEC | V_RD_PSUB) && rd_build_has(RD_lo, V_RD_PSUB) &&
+              !rd_build_spec(RD_tesa) && !rd_build_spec(RD_lo) && !rd_build_spec(RD_hi),
+              "rd_select sends --me tesa and sub-8x8 partitions to builds that have them compiled in, and takes tesa, lo and hi for plain chains");
 
 /* chains in a batch up to which the speculative raster schedule is used, and up to which its 1 / 2 waves-per-SIMD builds (measured:
  * below) */
@@ -22,7 +41,7 @@ enum { PCAMV_RD_BUILDS(PCAMV_RD_ENUM) RD_N_BUILDS };
 #define PCAMV_SPEC1_MAX_CHAINS 320
 #define PCAMV_SPEC2_MAX_CHAINS 704
 /* narrowest picture, in macroblocks, that takes the speculative chain: a macroblock is handed on once the one FLOW_SPEC_AHEAD
- * (pcamv_kernels.hip.h) before it is final, and its top / top-right neighbours, mb_w - 1 .. mb_w + 1 back, must be final by then */
+ * (pcamv_flow.hip.h) before it is final, and its top / top-right neighbours, mb_w - 1 .. mb_w + 1 back, must be final by then */
 #define FLOW_SPEC_MIN_MBW 8
 
 /* Which build of the RD instance (pcamv_rd.hip) a batch runs: one wave per SIMD while the chains fit that anyway.
@@ -45,7 +64,7 @@ static inline int rd_select(int n, int n_cu, int raster, int mb_w, int sub8x8, i
     const int can_spec = raster && mb_w >= FLOW_SPEC_MIN_MBW;
     const int inst_spec = inst && !strncmp(inst, "spec", 4);
     const int want_spec = inst ? inst_spec : flow_spec ? atoi(flow_spec) != 0 : n <= PCAMV_SPEC_MAX_CHAINS;
-    /* sub-8x8 partitions at this level (x264_rd_cost_part): compiled into the two one-wave-per-SIMD builds only, spec and lo */
+    /* sub-8x8 partitions at this level (x264_rd_cost_part, V_RD_PSUB): compiled into the one-wave-per-SIMD builds only */
     if (can_spec && want_spec) {
         if (sub8x8 || (inst && !strcmp(inst, "spec"))) return RD_spec;
         if (inst && !strcmp(inst, "spec2")) return RD_spec2;

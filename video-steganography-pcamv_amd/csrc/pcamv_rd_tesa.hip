@@ -4,6 +4,6 @@
  * search itself is what takes the time); the RD stage's inputs are fetched after the searches because the survivor list and the
  * context states share LDS (pcamv_mbkernels.h mbk_search).
  */
-#define PCAMV_RD_TESA 1
+#define PCAMV_RD_BUILD tesa
 #define PCAMV_SEARCH_CALL 1          /* the search of a partition as a function of its own (pcamv_logic.h): inlined at every call site this unit took 8 minutes to compile */
 #include "pcamv_rd.hip"
