@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- 1080p macroblocks/s of the P-frame hot path (embedding on) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 The workload is BASELINE.json's configuration 3 as written: 1920x1088 synthetic I420, --me umh --subme 7 (RD mode decision,
 CABAC, psy-RD: the reference's defaults at that level) --qp 26 --emrate 0.5, closed loop.
@@ -18,13 +18,18 @@ the environment, bench.py launches its N ranks itself).  Weak scaling (default):
 collective.  --strong: --gops is the size of ONE fixed set of GOPs, sharded round-robin over the ranks (pcamv_amd.shard), and
 after the timed region payloads are gathered to rank 0 in GOP order with tensor collectives over RCCL.
 
-Prints ONE JSON line (rank 0): metric/value/unit per BASELINE.json, `roofline` for the dominant kernel, `cpu_baseline` (the
-oracle port on a bounded 1080p sample + the reference itself, oracle/_ref, on CIF with the port beside it), `parity_at_scale`
-(after the timed loop: the first GOP of every XCD queue against the port run over the same chained frames, every GOP of a content
-class against that class's first GOP), and -- labelled extras, never `value` -- `pcie_inclusive` (the same steps with every
-frame's pictures uploaded and its results downloaded, overlapped with the compute), `g_sweep` (throughput against the number of
-GOPs in flight), `clip_600` (BASELINE config 3's 600 frames as closed GOPs of --keyint frames: wall time of the whole clip) and
-`config4_literal` (8 closed GOPs).
+Prints ONE JSON line (rank 0): metric/value/unit per BASELINE.json and `roofline` for the dominant kernel (its launches are timed
+with events inside the timed steps; no run of its own).  A plain run does that and no more: set-up, warm-up, the timed steps, the
+dump if asked for, the line.
+
+--full: everything else the benchmark measures or checks, after the timed steps, each block sized by an option of its own: the
+payload read back out of the final motion vectors (`extracted_payload_BER`), `cpu_baseline` (the oracle port on a bounded 1080p
+sample + the reference itself, oracle/_ref, on CIF with the port beside it), `parity_at_scale` (the first GOP of every XCD queue
+against the port run over the same chained frames, every GOP of a content class against that class's first GOP), and -- labelled
+extras, never `value` -- `pcie_inclusive` (the same steps with every frame's pictures uploaded and its results downloaded,
+overlapped with the compute), `g_sweep` (throughput against the number of GOPs in flight), `clip_600` (BASELINE config 3's 600
+frames as closed GOPs of --keyint frames: wall time of the whole clip) and `config4_literal` (8 closed GOPs).  Without --full
+those options are read and nothing of theirs runs.
 
 --dump-outputs DIR: after the timed steps, what a caller holds when the last of them is done -- pass-1 records, embedding vectors,
 final motion vectors and (closed loop) the deblocked pictures of a fixed seeded choice of GOPs -- as DIR/<name>.npy, for comparing
@@ -52,7 +57,7 @@ DUMP_GOPS = 8           # --dump-outputs: GOPs sampled
 DUMP_BYTES = 64000000   # ... and the most it writes, the .npy headers included
 
 
-def parse_args():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -67,16 +72,18 @@ def parse_args():
     ap.add_argument("--qp", type=int, default=26)
     ap.add_argument("--emrate", type=float, default=0.5)
     ap.add_argument("--open-loop", action="store_true", help="pass 1 only: no pass 2 / loop filter, the reference is the previous source frame")
-    ap.add_argument("--host-io-steps", type=int, default=6, help="steps of the PCIe-inclusive pipeline (0 = skip; rank 0, N=1 only)")
     ap.add_argument("--classes", type=int, default=64, help="distinct content classes: GOP g starts at frame g mod classes of a synthetic clip that long")
-    ap.add_argument("--parity-gops", type=int, default=8, help="GOPs compared with the CPU port after the timed loop (the first of every XCD queue; 0 = skip)")
-    ap.add_argument("--clip-keyints", default="30,8", help="keyint values of the 600-frame clip block ('' = skip; rank 0, N=1 only)")
-    ap.add_argument("--clip-frames", type=int, default=600)
-    ap.add_argument("--g-sweep", default="1,8,20,64,256,1024,2048", help="GOP counts of the low-G sweep ('' = skip; rank 0, N=1 only)")
-    ap.add_argument("--cpu-frames", type=int, default=24, help="1080p P frames timed for the CPU baseline (0 = skip the CPU baseline)")
-    ap.add_argument("--cpu-cif-frames", type=int, default=200, help="CIF P frames timed through the reference itself (oracle/_ref) and through the port (0 = skip)")
     ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed (a fixed seeded sample of it, at most 64 MB) as DIR/<name>.npy (rank 0)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run the checks and the other measurements (the options below size them)")
+    fx = ap.add_argument_group("blocks of --full", "read always, used with --full only")
+    fx.add_argument("--host-io-steps", type=int, default=6, help="steps of the PCIe-inclusive pipeline (0 = skip; rank 0, N=1 only)")
+    fx.add_argument("--parity-gops", type=int, default=8, help="GOPs compared with the CPU port after the timed loop (the first of every XCD queue; 0 = skip)")
+    fx.add_argument("--clip-keyints", default="30,8", help="keyint values of the 600-frame clip block ('' = skip; rank 0, N=1 only)")
+    fx.add_argument("--clip-frames", type=int, default=600)
+    fx.add_argument("--g-sweep", default="1,8,20,64,256,1024,2048", help="GOP counts of the low-G sweep ('' = skip; rank 0, N=1 only)")
+    fx.add_argument("--cpu-frames", type=int, default=24, help="1080p P frames timed for the CPU baseline (0 = skip the CPU baseline)")
+    fx.add_argument("--cpu-cif-frames", type=int, default=200, help="CIF P frames timed through the reference itself (oracle/_ref) and through the port (0 = skip)")
+    return ap.parse_args(argv)
 
 
 def self_launch(args):
@@ -130,6 +137,14 @@ class Gops:
         self.batch.close()
         for e in self.encs:
             e.close()
+
+    def leave_to_exit(self):
+        """instead of close() when the process is about to end: a context's device memory is about a hundred allocations, and freeing
+        those of 4096 contexts one by one takes 26 s, while the driver takes all of it back at once when the process exits.  The
+        wrappers forget their handles, so that nothing is freed when they are collected either."""
+        self.batch.b = None
+        for e in self.encs:
+            e.ctx = None
 
 
 def dump_outputs(path, run, closed_loop):
@@ -285,33 +300,37 @@ def main():
     n_diag = (W // 16) + 2 * (H // 16 - 1)
     flow = dom.startswith("k_analyse_flow")
 
-    # the embedded payload comes back out of the final motion vectors (the first GOPs of this rank: one per XCD queue)
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import helpers
-    from helpers import carrier_lsbs
+    # --full: the embedded payload comes back out of the final motion vectors (the first GOPs of this rank: one per XCD queue)
     T_done = args.warmup + args.steps
-    n_chk = max(1, min(args.parity_gops if args.parity_gops > 0 else 1, G, 8))
-    ber, ber_bits, chk = None, 0, []
-    for k in range(n_chk):
-        mbs_k, emb_k = run.encs[k].fetch_results(want_embed=True)
-        rec_k = run.encs[k].fetch_recon() if closed_loop else None
-        chk.append((mbs_k, emb_k, rec_k))
-        if emb_k["m"] > 0:
-            if emb_k["stc_ok"] != 1:
-                sys.exit(f"bench.py: the syndrome-trellis embedding of GOP {k} failed")
-            ext = pcamv_amd.stc_extract(carrier_lsbs(run.encs[k].final_mvs(mbs_k)), emb_k["m"])
-            ber = (0.0 if ber is None else ber) + float((ext != emb_k["message"]).sum())
-            ber_bits += int(emb_k["m"])
-    if ber is not None:
-        ber /= ber_bits
-    mbs, emb = chk[0][0], chk[0][1]
+    checked, chk = {}, []
+    if args.full:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import helpers
+        from helpers import carrier_lsbs
+        n_chk = max(1, min(args.parity_gops if args.parity_gops > 0 else 1, G, 8))
+        ber, ber_bits = None, 0
+        for k in range(n_chk):
+            mbs_k, emb_k = run.encs[k].fetch_results(want_embed=True)
+            rec_k = run.encs[k].fetch_recon() if closed_loop else None
+            chk.append((mbs_k, emb_k, rec_k))
+            if emb_k["m"] > 0:
+                if emb_k["stc_ok"] != 1:
+                    sys.exit(f"bench.py: the syndrome-trellis embedding of GOP {k} failed")
+                ext = pcamv_amd.stc_extract(carrier_lsbs(run.encs[k].final_mvs(mbs_k)), emb_k["m"])
+                ber = (0.0 if ber is None else ber) + float((ext != emb_k["message"]).sum())
+                ber_bits += int(emb_k["m"])
+        if ber is not None:
+            ber /= ber_bits
+        checked = {"extracted_payload_BER": ber, "BER_checked": {"gops": n_chk, "bits": ber_bits},
+                   "carriers_per_frame": int(chk[0][1]["n"]), "bits_per_frame": int(chk[0][1]["m"])}
     dumped = dump_outputs(args.dump_outputs, run, closed_loop) if args.dump_outputs and rank == 0 else None
+    solo = args.full and rank == 0 and world == 1      # the blocks of --full below run on one GPU alone
 
     # ---- parity at scale: what the timed loop computed (4 waves per SIMD, eight queues, work stealing, second-pass tasks of 8
     # macroblocks) against the CPU port on the same chained frames.  The port runs in threads (ctypes releases the GIL) while the
     # extras below keep the GPU busy; joined before the CPU baseline is timed.
     parity, par_threads, par_res = None, [], {}
-    if rank == 0 and world == 1 and args.parity_gops > 0 and closed_loop and T_done > 0:
+    if solo and args.parity_gops > 0 and closed_loop and T_done > 0:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import orc
         op_par = orc.make_params(W, H, me=args.me, subme=args.subme, mv_range=p.i_mv_range, tscale=256, inter=p.inter, cabac=p.b_cabac)
@@ -359,13 +378,8 @@ def main():
             sys.exit("bench.py: GOPs of the same content class ended the timed loop with different records / flip maps")
         parity = {"gops_identical_within_class": True, "content_classes": len(first_of), "gops": G}
 
-    # N > 1: per-rank summary to every rank, and (--strong) the payloads of the set's first GOPs to rank 0 in GOP order;
-    # tensor collectives over RCCL, after the timed region
-    summary = torch.tensor([emb["n"], emb["m"], emb["num_flip"]], device=cdev, dtype=torch.int64)
+    # --strong: the payloads of the set's first GOPs to rank 0 in GOP order; tensor collectives over RCCL, after the timed region
     gathered = None
-    if dist is not None:
-        allsum = [torch.zeros_like(summary) for _ in range(world)]
-        dist.all_gather(allsum, summary)
     if args.strong:
         n_gather = min(args.gops, 64)
         local_payload = {}
@@ -420,9 +434,8 @@ def main():
                                f"{' --no-cabac' if args.no_cabac else ''}, " + ("closed loop (pass 2 + loop filter on the GPU)" if closed_loop else "open-loop reference")
                                + (f", {args.gops} closed GOPs in total sharded over the ranks" if args.strong else f", {args.gops} closed GOPs in flight per GPU"),
                    "mb_per_frame": n_mb, "gops_per_gpu": G, "frames_per_step": total_gops, "content_classes": min(2 * nfr - 2, total_gops),
-                   "value_is": "inputs resident in HBM when the timed region starts; pcie_inclusive is the host-fed pipeline"},
-        "extracted_payload_BER": ber, "BER_checked": {"gops": n_chk, "bits": ber_bits},
-        "carriers_per_frame": int(emb["n"]), "bits_per_frame": int(emb["m"]),
+                   "value_is": "inputs resident in HBM when the timed region starts; pcie_inclusive (--full) is the host-fed pipeline"},
+        **checked,
         "hbm_algorithmic_GBps_whole_path": (B_WHOLE if closed_loop else B_WHOLE / 2) * value / 1e9,
         "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": traffic_src,
@@ -436,7 +449,6 @@ def main():
     if dumped is not None:
         out["dumped_outputs"] = dumped
 
-    solo = rank == 0 and world == 1
     # ---- PCIe-inclusive pipeline (extra): every step's source pictures go host -> device and its records + flip maps device -> host,
     # double-buffered and overlapped with the compute: uploads of step k+1 and downloads of step k run on a copy stream during the compute
     if solo and args.host_io_steps > 0:
@@ -673,7 +685,7 @@ def main():
     if rank == 0:
         print(json.dumps(out))
     if run is not None:
-        run.close()
+        run.leave_to_exit()
     if dist is not None:
         dist.destroy_process_group()
 

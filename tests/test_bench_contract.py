@@ -10,9 +10,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
 
 
+# --full at this size: every block of it, each cut down to a few frames
+FULL = ("--full", "--cpu-frames", "2", "--cpu-cif-frames", "3", "--g-sweep", "1,2", "--host-io-steps", "3", "--clip-frames", "24", "--clip-keyints", "4")
+
+
 def _run(*extra, env=None):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--width", "352", "--height", "288", "--gops", "6", "--steps", "2", "--warmup", "1",
-           "--cpu-frames", "2", "--cpu-cif-frames", "3", "--g-sweep", "1,2", "--host-io-steps", "3", "--clip-frames", "24", "--clip-keyints", "4", *extra]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--width", "352", "--height", "288", "--gops", "6", "--steps", "2", "--warmup", "1", *extra]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=dict(os.environ, **(env or {})))
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -20,8 +23,8 @@ def _run(*extra, env=None):
     return json.loads(lines[0])
 
 
-def test_bench_line_has_the_contract_fields():
-    j = _run()
+def test_full_bench_line_has_the_contract_fields():
+    j = _run(*FULL)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
               "roofline", "cpu_baseline"):
         assert k in j, k
@@ -45,9 +48,29 @@ def test_bench_line_has_the_contract_fields():
     assert j["roofline"]["valu_issue_frac"] is None or j["roofline"]["valu_issue_frac"]["frac"] > 0
 
 
-def test_content_classes_are_compared_within_class():
+def test_a_plain_run_prints_the_headline_alone(tmp_path):
+    """without --full: the contract's fields and the roofline of the timed steps' own launches, none of the checks and measurements
+    that --full adds -- whatever their options say -- and the same dump as with --full (the blocks of --full run after it is written)"""
+    import numpy as np
+    j = _run("--dump-outputs", str(tmp_path / "plain"), *FULL[1:])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "roofline"):
+        assert k in j, k
+    assert j["metric"] == "1080p macroblocks/s (embed on)" and j["unit"] == "MB/s" and j["higher_is_better"] is True and j["dtype"] == "u8"
+    assert j["steps"] == 2 and j["warmup"] == 1 and j["value"] > 0 and abs(j["value"] - 6 * 396 * 2 / (j["ms_per_step"] * 2e-3)) < 1e-6 * j["value"]
+    assert j["roofline"]["kernel"] == "k_analyse_flow_rd" and j["roofline"]["avg_launch_ms"] > 0 and j["roofline"]["launches_timed"] == 2
+    for k in ("cpu_baseline", "parity_at_scale", "pcie_inclusive", "g_sweep", "other_workloads", "clip_600", "config4_literal", "extracted_payload_BER", "BER_checked"):
+        assert k not in j, k
+    jf = _run("--dump-outputs", str(tmp_path / "full"), *FULL)
+    assert jf["metric"] == j["metric"] and jf["unit"] == j["unit"] and jf["dtype"] == j["dtype"] and jf["config"] == j["config"] and "cpu_baseline" in jf
+    files = sorted(os.listdir(tmp_path / "plain"))
+    assert files and files == sorted(os.listdir(tmp_path / "full"))
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "plain" / f), np.load(tmp_path / "full" / f), equal_nan=True), f
+
+
+def test_full_compares_content_classes_within_class():
     """more GOPs than content classes: GOPs 0 and 4, 1 and 5 see the same pictures and must end with the same records"""
-    j = _run("--classes", "4", "--cpu-frames", "0", "--host-io-steps", "0", "--g-sweep", "", "--clip-keyints", "")
+    j = _run("--full", "--classes", "4", "--cpu-frames", "0", "--host-io-steps", "0", "--g-sweep", "", "--clip-keyints", "")
     assert j["parity_at_scale"]["content_classes"] == 4 and j["parity_at_scale"]["gops_identical_within_class"] is True and j["parity_at_scale"]["ok"] is True
 
 

@@ -1,5 +1,5 @@
 """bench.py --dump-outputs, the part that needs no GPU: the size cap and the seeded sample, on stand-ins for the device contexts
-(the dump of a real run is checked by tests/test_bench_contract.py)."""
+(the dump of a real run is checked by tests/test_bench_contract.py); and --full as an option."""
 import os
 
 import numpy as np
@@ -57,3 +57,9 @@ def test_dump_is_whole_below_the_cap_and_a_repeatable_sample_above_it(tmp_path, 
     for name in a:
         assert np.array_equal(a[name], b[name]) and a[name].dtype == whole[name].dtype
         assert a[name].size == int(whole[name].size * cut[0]["fraction_of_elements_kept"]) and np.isin(a[name], whole[name]).all()
+
+
+def test_full_is_off_unless_asked_for_and_its_blocks_keep_their_options():
+    plain, full = bench.parse_args(["--gpus", "1", "--steps", "5", "--warmup", "2"]), bench.parse_args(["--full", "--g-sweep", "1,2", "--cpu-frames", "0"])
+    assert plain.full is False and (plain.gpus, plain.steps, plain.warmup, plain.dump_outputs) == (1, 5, 2, None)
+    assert full.full is True and full.g_sweep == "1,2" and full.cpu_frames == 0 and (full.host_io_steps, full.parity_gops, full.clip_keyints) == (6, 8, "30,8")
