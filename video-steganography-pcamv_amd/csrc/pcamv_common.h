@@ -100,7 +100,38 @@ struct FrameDev {
     uint32_t *dbg_hash;            /* diagnostics: [n_mb] FNV-1a of the context states after each macroblock, or NULL */
     int rec_is_pass1;              /* pass 2: rec / nnz still hold what this frame's first pass left (nothing has filtered them yet) */
     const uint8_t *mbflip;         /* pass 2: [n_mb] 1 = some carrier of the macroblock is flipped in `flip` (k_mb_flips), or NULL: look at the carriers */
+    const struct FrameDev *self;   /* where this descriptor lies in device memory: set by the host as it uploads one (FD below) */
 };
+
+/* A macroblock kernel works on a copy of its frame's descriptor, and the compiler keeps every field of that copy which the
+ * kernel reads as `F.field` in a register for the whole macroblock.  A four-waves-per-SIMD build does not have ~140 scalar
+ * registers for that: it parked them in VGPR lanes (334 spilled SGPRs in the RD instance) and paid a v_readlane, a VALU
+ * instruction with a hazard slot in front of it, at every use.  So only what the list passes read stays `F.field` (cost_mv,
+ * luma_base, chroma_base, plane_size, cplane_size, lskip, cstride, stride, lambda, subme, me_method, me_range, b_chroma_me,
+ * mb_w) and the switches the RD stage tests at every turn (b_mbrd, b_cabac, inter, embed, psy_rd, lambda2, trace); everything else -- the quantiser sets, the once-per-macroblock pointers, parameters of one stage -- is read as
+ * FD(F).field: a scalar load from the descriptor in constant memory at the place of use, off the vector pipe.  The empty asm
+ * makes each read a load of its own; without it the compiler hoists them all back to the top of the macroblock loop.
+ * A one-wave-per-SIMD build (PCAMV_RD_LO) has the registers and keeps the copy; -DPCAMV_NO_DESC_RELOAD is the A side of the A/B. */
+#ifdef PCAMV_HOST_EMU
+#define FD(F) (F)
+#else
+#define PCAMV_AS4 __attribute__((address_space(4)))
+PCAMV_DEV const PCAMV_AS4 FrameDev &fd_reload(const FrameDev &F)
+{
+    /* (the pointer is wave-uniform, but a speculative build may hold it in a vector register: the two halves go through
+     * v_readfirstlane, which costs nothing where they are in scalar registers already) */
+    const uint64_t a = (uint64_t)F.self;
+    uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(a >> 32));
+    asm volatile("" : "+s"(lo), "+s"(hi));
+    return *(const PCAMV_AS4 FrameDev *)((uint64_t)hi << 32 | lo);
+}
+template <bool KEEP> PCAMV_DEV const auto &fd_pick(const FrameDev &F) { if constexpr (KEEP) return F; else return fd_reload(F); }
+#ifdef PCAMV_NO_DESC_RELOAD
+#define FD(F) (F)
+#else
+#define FD(F) fd_pick<PCAMV_RD_LO>(F)          /* (PCAMV_RD_LO: pcamv_prims_gpu.h) */
+#endif
+#endif
 
 /* Small lookup tables live in registers as packed constants: a table in memory costs one global
  * load round trip per use, and these sit on the serial chain of the search (me.c tables, block

@@ -89,10 +89,10 @@ __device__ __forceinline__ bool spec_inputs_final(const FrameDev &F, MBLocal *L)
 {
     if (!(L->neighbour & NB_LEFT)) return true;
     const int xy = L->mb_xy, s4 = 4 * F.mb_w, b4 = 4 * (L->mb_y * s4 + L->mb_x);
-    const uint32_t m0 = NB_LD32(&F.mv[2 * (b4 - 1)]), m1 = NB_LD32(&F.mv[2 * (b4 - 1 + s4)]);
-    const uint32_t m2 = NB_LD32(&F.mv[2 * (b4 - 1 + 2 * s4)]), m3 = NB_LD32(&F.mv[2 * (b4 - 1 + 3 * s4)]);
-    const uint32_t r = NB_LD32(&F.mvr[2 * (xy - 1)]);
-    const int t = NB_LD8(&F.mb_type[xy - 1]);
+    const uint32_t m0 = NB_LD32(&FD(F).mv[2 * (b4 - 1)]), m1 = NB_LD32(&FD(F).mv[2 * (b4 - 1 + s4)]);
+    const uint32_t m2 = NB_LD32(&FD(F).mv[2 * (b4 - 1 + 2 * s4)]), m3 = NB_LD32(&FD(F).mv[2 * (b4 - 1 + 3 * s4)]);
+    const uint32_t r = NB_LD32(&FD(F).mvr[2 * (xy - 1)]);
+    const int t = NB_LD8(&FD(F).mb_type[xy - 1]);
     PCAMV_WAVE_SYNC();
     const int16_t (*c)[2] = L->cmv;
     bool ok = m0 == NB_PACK16(c[SCAN8_0 - 1][0], c[SCAN8_0 - 1][1]) && m1 == NB_PACK16(c[SCAN8_0 - 1 + 8][0], c[SCAN8_0 - 1 + 8][1]) &&
@@ -116,8 +116,8 @@ __device__ __forceinline__ bool mbk_search_spec(const FrameDev &F, MBLocal *L, A
             /* what the successor's searches start from: a skipped macroblock's motion is final as it stands (as far as this
              * macroblock's own inputs are), a coded one is announced as 16x16 with the search's result */
             const uint32_t w = skip ? NB_PACK16(L->pskip_mv[0], L->pskip_mv[1]) : NB_PACK16(a->me16x16.mv[0], a->me16x16.mv[1]);
-            if (lane < 16) NB_ST32(&F.mv[2 * (b4 + (lane >> 2) * s4 + (lane & 3))], w);
-            if (lane == 0) { NB_ST8(&F.mb_type[xy], skip ? PCAMV_P_SKIP : PCAMV_P_L0); NB_ST16(&F.ref8[b8], 0); NB_ST16(&F.ref8[b8 + s8], 0); }
+            if (lane < 16) NB_ST32(&FD(F).mv[2 * (b4 + (lane >> 2) * s4 + (lane & 3))], w);
+            if (lane == 0) { NB_ST8(&FD(F).mb_type[xy], skip ? PCAMV_P_SKIP : PCAMV_P_L0); NB_ST16(&FD(F).ref8[b8], 0); NB_ST16(&FD(F).ref8[b8 + s8], 0); }
             if (xy + 1 < fl.n_mb) {
                 if (!flow_wait_rdone(fl, g, xy + 1 > FLOW_SPEC_AHEAD ? (unsigned)(xy + 1 - FLOW_SPEC_AHEAD) : 0u)) return false;
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

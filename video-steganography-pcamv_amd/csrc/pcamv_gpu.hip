@@ -561,7 +561,7 @@ static int batch_push_descs(pcamv_batch *b, hipStream_t st, const FrameDev **dF,
     int slot;
     TRY(ring_take(b, b->ring, &slot));
     FrameDev *hF = b->h_F + (size_t)slot * b->n; EmbedDev *hE = b->h_E + (size_t)slot * b->n;
-    for (int i = 0; i < b->n; i++) { hF[i] = b->ctx[i]->F; hE[i] = b->ctx[i]->E; }
+    for (int i = 0; i < b->n; i++) { hF[i] = b->ctx[i]->F; hF[i].self = b->d_F + (size_t)slot * b->n + i; hE[i] = b->ctx[i]->E; }
     HIPCHK(b, hipMemcpyAsync(b->d_F + (size_t)slot * b->n, hF, sizeof(FrameDev) * b->n, hipMemcpyHostToDevice, st));
     HIPCHK(b, hipMemcpyAsync(b->d_E + (size_t)slot * b->n, hE, sizeof(EmbedDev) * b->n, hipMemcpyHostToDevice, st));
     *dF = b->d_F + (size_t)slot * b->n; *dE = b->d_E + (size_t)slot * b->n; *slot_out = slot;
@@ -1185,7 +1185,8 @@ extern "C" int pcamv_gpu_block_costs(pcamv_ctx_t *c, int qp, int n, const int32_
     DevTmp<int> d_req, d_out; DevTmp<FrameDev> d_F;
     HIPCHK(c, d_req.alloc((size_t)n * 8)); HIPCHK(c, d_out.alloc((size_t)n * 3)); HIPCHK(c, d_F.alloc(1));
     HIPCHK(c, hipMemcpy(d_req, req, (size_t)n * 8 * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(d_F, &c->F, sizeof(FrameDev), hipMemcpyHostToDevice));
+    FrameDev hF = c->F; hF.self = d_F;
+    HIPCHK(c, hipMemcpy(d_F, &hF, sizeof(FrameDev), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_block_costs, dim3(n), dim3(64), 0, c->stream, (const FrameDev *)d_F, (const int *)d_req, (int *)d_out);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(out, d_out, (size_t)n * 3 * sizeof(int), hipMemcpyDeviceToHost));
@@ -1200,7 +1201,8 @@ extern "C" int pcamv_gpu_rd_probe(pcamv_ctx_t *c, int qp, int n, const uint8_t *
     DevTmp<uint8_t> d_req; DevTmp<int> d_out; DevTmp<FrameDev> d_F;
     HIPCHK(c, d_req.alloc((size_t)n * 1024)); HIPCHK(c, d_out.alloc((size_t)n * 32)); HIPCHK(c, d_F.alloc(1));
     HIPCHK(c, hipMemcpy(d_req, req, (size_t)n * 1024, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(d_F, &c->F, sizeof(FrameDev), hipMemcpyHostToDevice));
+    FrameDev hF = c->F; hF.self = d_F;
+    HIPCHK(c, hipMemcpy(d_F, &hF, sizeof(FrameDev), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_rd_probe, dim3(n), dim3(64), 0, c->stream, (const FrameDev *)d_F, (const uint8_t *)d_req, (int *)d_out);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(out, d_out, (size_t)n * 32 * sizeof(int), hipMemcpyDeviceToHost));

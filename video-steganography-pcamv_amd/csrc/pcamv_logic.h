@@ -89,28 +89,28 @@ PCAMV_DEV int predict_mv_ref16x16(const FrameDev &F, MBLocal *L, int (*mvc)[2])
     const int use_t = (L->neighbour & NB_TOP) && L->type_top != PCAMV_P_SKIP;
     const int use_tl = (L->neighbour & NB_TOP) && (L->neighbour & NB_TOPLEFT) && L->type_topleft != PCAMV_P_SKIP;
     const int use_tr = (L->neighbour & NB_TOP) && L->mb_x < F.mb_w - 1 && L->type_topright != PCAMV_P_SKIP;
-    const uint32_t w_l = NB_LD32(&F.mvr[2 * (use_l ? xy - 1 : xy)]), w_t = NB_LD32(&F.mvr[2 * (use_t ? top : xy)]);
-    const uint32_t w_tl = NB_LD32(&F.mvr[2 * (use_tl ? top - 1 : xy)]), w_tr = NB_LD32(&F.mvr[2 * (use_tr ? top + 1 : xy)]);
+    const uint32_t w_l = NB_LD32(&FD(F).mvr[2 * (use_l ? xy - 1 : xy)]), w_t = NB_LD32(&FD(F).mvr[2 * (use_t ? top : xy)]);
+    const uint32_t w_tl = NB_LD32(&FD(F).mvr[2 * (use_tl ? top - 1 : xy)]), w_tr = NB_LD32(&FD(F).mvr[2 * (use_tr ? top + 1 : xy)]);
 #define SETMV(w_) { mvc[i][0] = (int16_t)((w_) & 0xffff); mvc[i][1] = (int16_t)((w_) >> 16); i++; }
     if (use_l) SETMV(w_l);
     if (use_t) SETMV(w_t);
     if (use_tl) SETMV(w_tl);
     if (use_tr) SETMV(w_tr);
 #undef SETMV
-    if (F.have_prev) {
+    if (FD(F).have_prev) {
         int ok[3], rf[3]; uint32_t mw[3];
         for (int k = 0; k < 3; k++) {
             const int dx = k == 1, dy = k == 2;
-            ok[k] = !(k == 1 && !(L->mb_x < F.mb_w - 1)) && !(k == 2 && !(L->mb_y < F.mb_h - 1));
+            ok[k] = !(k == 1 && !(L->mb_x < F.mb_w - 1)) && !(k == 2 && !(L->mb_y < FD(F).mb_h - 1));
             const int b4 = 4 * (L->mb_y * 4 * F.mb_w + L->mb_x) + (ok[k] ? dx * 4 + dy * 4 * (4 * F.mb_w) : 0);
             const int b8 = 2 * (L->mb_y * 2 * F.mb_w + L->mb_x) + (ok[k] ? dx * 2 + dy * 2 * (2 * F.mb_w) : 0);
-            rf[k] = F.prev_ref[b8];
-            mw[k] = *(const uint32_t *)&F.prev_mv[2 * b4];
+            rf[k] = FD(F).prev_ref[b8];
+            mw[k] = *(const uint32_t *)&FD(F).prev_mv[2 * b4];
         }
         for (int k = 0; k < 3; k++)
             if (ok[k] && rf[k] >= 0) {
-                mvc[i][0] = (int16_t)(((int)(int16_t)(mw[k] & 0xffff) * F.tscale + 128) >> 8);
-                mvc[i][1] = (int16_t)(((int)(int16_t)(mw[k] >> 16) * F.tscale + 128) >> 8);
+                mvc[i][0] = (int16_t)(((int)(int16_t)(mw[k] & 0xffff) * FD(F).tscale + 128) >> 8);
+                mvc[i][1] = (int16_t)(((int)(int16_t)(mw[k] >> 16) * FD(F).tscale + 128) >> 8);
                 i++;
             }
     }
@@ -132,8 +132,8 @@ PCAMV_DEV void mb_load(const FrameDev &F, MBLocal *L, int mb_x, int mb_y, int li
     const int nb = (mb_y > 0 ? NB_TOP : 0) | (mb_x > 0 ? NB_LEFT : 0) | (mb_x < F.mb_w - 1 && mb_y > 0 ? NB_TOPRIGHT : 0) | (mb_x > 0 && mb_y > 0 ? NB_TOPLEFT : 0);
     /* (unconditional loads: a neighbour that does not exist reads this macroblock's own slot and is ignored -- a load inside an `if`
      * is a branch of its own with its own s_waitcnt, i.e. one memory round trip per neighbour instead of one for all) */
-    int t_top = NB_LD8(&F.mb_type[(nb & NB_TOP) ? top : L->mb_xy]), t_left = NB_LD8(&F.mb_type[(nb & NB_LEFT) ? L->mb_xy - 1 : L->mb_xy]);
-    int t_tr = NB_LD8(&F.mb_type[(nb & NB_TOPRIGHT) ? top + 1 : L->mb_xy]), t_tl = NB_LD8(&F.mb_type[(nb & NB_TOPLEFT) ? top - 1 : L->mb_xy]);
+    int t_top = NB_LD8(&FD(F).mb_type[(nb & NB_TOP) ? top : L->mb_xy]), t_left = NB_LD8(&FD(F).mb_type[(nb & NB_LEFT) ? L->mb_xy - 1 : L->mb_xy]);
+    int t_tr = NB_LD8(&FD(F).mb_type[(nb & NB_TOPRIGHT) ? top + 1 : L->mb_xy]), t_tl = NB_LD8(&FD(F).mb_type[(nb & NB_TOPLEFT) ? top - 1 : L->mb_xy]);
     const int s4 = 4 * F.mb_w, s8 = 2 * F.mb_w;
     const int b4 = 4 * (mb_y * s4 + mb_x), b8 = 2 * (mb_y * s8 + mb_x);
     const int t4 = (4 * (mb_y - 1) + 3) * s4 + 4 * mb_x, t8 = (2 * (mb_y - 1) + 1) * s8 + 2 * mb_x;
@@ -146,7 +146,7 @@ PCAMV_DEV void mb_load(const FrameDev &F, MBLocal *L, int mb_x, int mb_y, int li
         else if (i == 5) { ok = nb & NB_TOPRIGHT; c8 = SCAN8_0 + 4 - 8; m4 = t4 + 4; r8 = t8 + 2; }
         else { ok = nb & NB_LEFT; c8 = SCAN8_0 - 1 + 8 * (i - 6); m4 = b4 - 1 + (i - 6) * s4; r8 = b8 - 1 + ((i - 6) >> 1) * s8; }
         nb_c8[NB_SLOT(i)] = ok ? c8 : -1;
-        nb_w[NB_SLOT(i)] = NB_LD32(&F.mv[2 * (ok ? m4 : b4)]); nb_r[NB_SLOT(i)] = NB_LD8(&F.ref8[ok ? r8 : b8]);
+        nb_w[NB_SLOT(i)] = NB_LD32(&FD(F).mv[2 * (ok ? m4 : b4)]); nb_r[NB_SLOT(i)] = NB_LD8(&FD(F).ref8[ok ? r8 : b8]);
     }
     prim_mb_fetch(F, mb_x, mb_y, nb, rd, pf);
     /* ---- from here on the loaded values are used */
@@ -172,7 +172,7 @@ PCAMV_DEV void mb_load(const FrameDev &F, MBLocal *L, int mb_x, int mb_y, int li
     L->type_left = L->type_top = L->type_topleft = L->type_topright = -1;
     }
 
-    int fmv = 4 * F.mv_range;
+    int fmv = 4 * FD(F).mv_range;
     L->mv_min[0] = 4 * (-16 * mb_x - 24);
     L->mv_max[0] = 4 * (16 * (F.mb_w - mb_x - 1) + 24);
     L->mv_min_spel[0] = clip3i(L->mv_min[0], -fmv, fmv - 1);
@@ -180,7 +180,7 @@ PCAMV_DEV void mb_load(const FrameDev &F, MBLocal *L, int mb_x, int mb_y, int li
     L->mv_min_fpel[0] = (L->mv_min_spel[0] >> 2) + 5;
     L->mv_max_fpel[0] = (L->mv_max_spel[0] >> 2) - 5;
     L->mv_min[1] = 4 * (-16 * mb_y - 24);
-    L->mv_max[1] = 4 * (16 * (F.mb_h - mb_y - 1) + 24);
+    L->mv_max[1] = 4 * (16 * (FD(F).mb_h - mb_y - 1) + 24);
     L->mv_min_spel[1] = clip3i(L->mv_min[1], imax(4 * (-512 + 8), -fmv), fmv);
     L->mv_max_spel[1] = clip3i(L->mv_max[1], -fmv, fmv - 1);
     L->mv_max_spel[1] = imin(L->mv_max_spel[1], fmv * 4);
@@ -610,14 +610,14 @@ PCAMV_DEV int probe_pskip(const FrameDev &F, MBLocal *L)
     prim_residual(F, L, 1, 0);
     int decimate = 0;
     for (int idx = 0; idx < 16; idx++) if (L->blk_nz[idx]) { decimate += L->blk_score[idx]; if (decimate >= 6) return 0; }
-    int thresh = (F.lambda2_chroma + 32) >> 6;
+    int thresh = (FD(F).lambda2_chroma + 32) >> 6;
     prim_predict_16x16(F, L, mvx, mvy, 2);
     int need[2];
     for (int ch = 0; ch < 2; ch++) need[ch] = !(prim_chroma_ssd(F, L, ch) < thresh);
     if (need[0] | need[1]) prim_residual(F, L, 0, 1);
     for (int ch = 0; ch < 2; ch++) {
         if (!need[ch]) continue;
-        int mf = F.q_mf[1][0] >> 1, bias = F.q_bias[1][0] << 1, nz = 0;
+        int mf = FD(F).q_mf[1][0] >> 1, bias = FD(F).q_bias[1][0] << 1, nz = 0;
         for (int k = 0; k < 4; k++) {
             int c = L->cdc[ch][k];
             nz |= c > 0 ? ((bias + c) * mf >> 16) : -((bias - c) * mf >> 16);
@@ -1234,7 +1234,7 @@ PCAMV_DEV int analyse_s16(const FrameDev &F, MBLocal *L, Analysis *a)
 #if defined(PCAMV_PROF) && !defined(PCAMV_HOST_EMU)
     L->prof_ntrial = 0;
 #endif
-    if (F.b_fast_pskip) {
+    if (FD(F).b_fast_pskip) {
         if (F.subme >= 3) b_try_pskip = 1;
         else if (L->type_left == PCAMV_P_SKIP || L->type_top == PCAMV_P_SKIP || L->type_topleft == PCAMV_P_SKIP || L->type_topright == PCAMV_P_SKIP)
             b_skip = probe_pskip(F, L);

@@ -43,7 +43,7 @@ PCAMV_DEV void mbk_search_finish(const FrameDev &F, MBLocal *L, Analysis *a, int
 #else
         prim_store_rec(F, L, true);
 #endif
-        if (PCAMV_LANE0 && F.nnz) F.nnz[L->mb_xy] = (uint16_t)L->nnz_mask;      /* with the pixels: what pass 2 takes over for a macroblock the embedding leaves alone */
+        if (PCAMV_LANE0 && FD(F).nnz) FD(F).nnz[L->mb_xy] = (uint16_t)L->nnz_mask;      /* with the pixels: what pass 2 takes over for a macroblock the embedding leaves alone */
         entropy_commit(F, L, kept);
         PROF_ADD(22, t_c);
     }
@@ -52,7 +52,7 @@ PCAMV_DEV void mbk_search_finish(const FrameDev &F, MBLocal *L, Analysis *a, int
     int *slots = L->slots;
     const int used = F.embed && L->i_type != PCAMV_P_SKIP;
     const int n = carrier_slots(L->i_type, L->i_partition, L->sub_part, used, slots);
-    pcamv_mb_t *r = &F.rec_mb[xy];
+    pcamv_mb_t *r = &FD(F).rec_mb[xy];
     const int s4 = 4 * F.mb_w, s8 = 2 * F.mb_w, b4 = 4 * (mb_y * s4 + mb_x), b8 = 2 * (mb_y * s8 + mb_x);
     PCAMV_WAVE_SYNC();
     /* the 16 per-4x4 entries of the record and of the frame's motion field (x264_macroblock_cache_save,
@@ -62,10 +62,10 @@ PCAMV_DEV void mbk_search_finish(const FrameDev &F, MBLocal *L, Analysis *a, int
         r->ref[i] = L->cref[i8]; r->mv[i][0] = L->cmv[i8][0]; r->mv[i][1] = L->cmv[i8][1];
         r->mv_stego[i][0] = r->mv_stego[i][1] = 0; r->inter_stego_cost[i] = 0;
         int x = i & 3, y = i >> 2;
-        NB_ST32(&F.mv[2 * (b4 + y * s4 + x)], NB_PACK16(L->cmv[SCAN8_0 + x + 8 * y][0], L->cmv[SCAN8_0 + x + 8 * y][1]));
+        NB_ST32(&FD(F).mv[2 * (b4 + y * s4 + x)], NB_PACK16(L->cmv[SCAN8_0 + x + 8 * y][0], L->cmv[SCAN8_0 + x + 8 * y][1]));
     }
     if (PCAMV_LANE0) {
-        r->i_type = L->i_type; r->i_partition = L->i_partition; r->i_qp = F.qp;
+        r->i_type = L->i_type; r->i_partition = L->i_partition; r->i_qp = FD(F).qp;
         for (int i = 0; i < 4; i++) r->i_sub_partition[i] = L->i_type == PCAMV_P_8x8 ? L->sub_part[i] : PCAMV_D_L0_8x8;
         r->pskip_mv[0] = L->pskip_mv[0]; r->pskip_mv[1] = L->pskip_mv[1];
         if (L->i_type != PCAMV_P_SKIP) { r->mvr16[0] = L->mvr_own[0]; r->mvr16[1] = L->mvr_own[1]; }
@@ -73,12 +73,12 @@ PCAMV_DEV void mbk_search_finish(const FrameDev &F, MBLocal *L, Analysis *a, int
         r->used = (uint8_t)used; r->pad[0] = r->pad[1] = r->pad[2] = 0;
         for (int k = 0; k < n; k++) {
             MEState *me = slot_me(L, a, slots[k]);
-            F.mvp_aux[(xy * 16 + slots[k]) * 2] = (int16_t)me->mvp[0];
-            F.mvp_aux[(xy * 16 + slots[k]) * 2 + 1] = (int16_t)me->mvp[1];
+            FD(F).mvp_aux[(xy * 16 + slots[k]) * 2] = (int16_t)me->mvp[0];
+            FD(F).mvp_aux[(xy * 16 + slots[k]) * 2 + 1] = (int16_t)me->mvp[1];
         }
-        NB_ST8(&F.mb_type[xy], L->i_type);
-        NB_ST16(&F.ref8[b8], (uint16_t)(uint8_t)L->cref[scan8_of(0)] | (uint16_t)(uint8_t)L->cref[scan8_of(4)] << 8);
-        NB_ST16(&F.ref8[b8 + s8], (uint16_t)(uint8_t)L->cref[scan8_of(8)] | (uint16_t)(uint8_t)L->cref[scan8_of(12)] << 8);
+        NB_ST8(&FD(F).mb_type[xy], L->i_type);
+        NB_ST16(&FD(F).ref8[b8], (uint16_t)(uint8_t)L->cref[scan8_of(0)] | (uint16_t)(uint8_t)L->cref[scan8_of(4)] << 8);
+        NB_ST16(&FD(F).ref8[b8 + s8], (uint16_t)(uint8_t)L->cref[scan8_of(8)] | (uint16_t)(uint8_t)L->cref[scan8_of(12)] << 8);
     }
     PROF_ADD(12, t_w);
 }
@@ -108,7 +108,7 @@ PCAMV_DEV void mbk_search(const FrameDev &F, MBLocal *L, Analysis *a, int mb_x, 
 /* rebuild the decided partitioning (types, MVs, search-time mvp) from the record */
 PCAMV_DEV int analysis_from_record(const FrameDev &F, MBLocal *L, Analysis *a, int xy, int *slots)
 {
-    const pcamv_mb_t *r = &F.rec_mb[xy];
+    const pcamv_mb_t *r = &FD(F).rec_mb[xy];
     mb_load(F, L, xy % F.mb_w, xy / F.mb_w);
     L->i_type = r->i_type; L->i_partition = r->i_partition;
     for (int i = 0; i < 4; i++) L->sub_part[i] = r->i_sub_partition[i];
@@ -119,14 +119,14 @@ PCAMV_DEV int analysis_from_record(const FrameDev &F, MBLocal *L, Analysis *a, i
         slot_geometry(L->i_type, L->i_partition, L->sub_part, s, &ip, &xo, &yo);
         me_setup(me, ip, xo, yo);
         me->mv[0] = r->mv[s][0]; me->mv[1] = r->mv[s][1];
-        me->mvp[0] = F.mvp_aux[(xy * 16 + s) * 2]; me->mvp[1] = F.mvp_aux[(xy * 16 + s) * 2 + 1];
+        me->mvp[0] = FD(F).mvp_aux[(xy * 16 + s) * 2]; me->mvp[1] = FD(F).mvp_aux[(xy * 16 + s) * 2 + 1];
     }
     return n;
 }
 
 PCAMV_DEV void mbk_rca(const FrameDev &F, MBLocal *L, Analysis *a, int xy, int k)
 {
-    if (!F.rec_mb[xy].used) return;
+    if (!FD(F).rec_mb[xy].used) return;
     int *slots = L->slots;
     const int n = analysis_from_record(F, L, a, xy, slots);
     if (k >= n) return;
@@ -135,7 +135,7 @@ PCAMV_DEV void mbk_rca(const FrameDev &F, MBLocal *L, Analysis *a, int xy, int k
     const int bx = me->mv[0], by = me->mv[1];
     const int cost = rca_mv_cost(F, L, a, me, &dx, &dy, 0);
     if (PCAMV_LANE0) {
-        pcamv_mb_t *r = &F.rec_mb[xy];
+        pcamv_mb_t *r = &FD(F).rec_mb[xy];
         r->mv_stego[slots[k]][0] = (int16_t)(bx + dx); r->mv_stego[slots[k]][1] = (int16_t)(by + dy);
         r->inter_stego_cost[slots[k]] = cost;
     }
@@ -163,14 +163,14 @@ PCAMV_DEV int mbk_recon(const FrameDev &F, MBLocal *L, Analysis *a, int xy, int 
     }
     mb_encode(F, L);
     prim_store_rec(F, L);
-    if (PCAMV_LANE0 && F.nnz) F.nnz[xy] = (uint16_t)L->nnz_mask;
+    if (PCAMV_LANE0 && FD(F).nnz) FD(F).nnz[xy] = (uint16_t)L->nnz_mask;
     PROF_ADD(10, t_e);
     return n;
 }
 PCAMV_DEV void mbk_rca_all(const FrameDev &F, MBLocal *L, Analysis *a, int xy, int n)
 {
     int *slots = L->slots;
-    if (F.rec_mb[xy].used && n > 0) {
+    if (FD(F).rec_mb[xy].used && n > 0) {
         const unsigned long long t_w = PROF_T();
         PROF_CNT(42, n);
         prim_copy_pred(L, L->recb0);
@@ -188,7 +188,7 @@ PCAMV_DEV void mbk_rca_all(const FrameDev &F, MBLocal *L, Analysis *a, int xy, i
             const int bx = me->mv[0], by = me->mv[1];
             const int cost = rca_mv_cost(F, L, a, me, &dx, &dy, 1, win);
             if (PCAMV_LANE0) {
-                pcamv_mb_t *r = &F.rec_mb[xy];
+                pcamv_mb_t *r = &FD(F).rec_mb[xy];
                 r->mv_stego[slots[k]][0] = (int16_t)(bx + dx); r->mv_stego[slots[k]][1] = (int16_t)(by + dy);
                 r->inter_stego_cost[slots[k]] = cost;
             }
@@ -228,19 +228,19 @@ PCAMV_DEV int mbk_pass2(const FrameDev &F, MBLocal *L, int mb_x, int mb_y, int s
     if (unit) any_flip = unit->any_flip;
     else {
         const int lane = LANE();
-        if (F.rec_is_pass1) {
-            pre_y = *(const uint32_t *)(F.rec[0] + (size_t)(mb_y * 16 + (lane >> 2)) * F.w + mb_x * 16 + (lane & 3) * 4);
-            if (lane < 32) pre_c = *(const uint32_t *)(((lane >> 4) ? F.rec[2] : F.rec[1]) + (size_t)(mb_y * 8 + ((lane & 15) >> 1)) * (F.w >> 1) + mb_x * 8 + (lane & 1) * 4);
+        if (FD(F).rec_is_pass1) {
+            pre_y = *(const uint32_t *)(FD(F).rec[0] + (size_t)(mb_y * 16 + (lane >> 2)) * FD(F).w + mb_x * 16 + (lane & 3) * 4);
+            if (lane < 32) pre_c = *(const uint32_t *)(((lane >> 4) ? FD(F).rec[2] : FD(F).rec[1]) + (size_t)(mb_y * 8 + ((lane & 15) >> 1)) * (FD(F).w >> 1) + mb_x * 8 + (lane & 1) * 4);
         }
-        if (F.mbflip) any_flip = F.mbflip[xy];
+        if (FD(F).mbflip) any_flip = FD(F).mbflip[xy];
     }
 #else
     const int any_flip = 1;
 #endif
     if (!unit) {
         FOR_CAND(i, (int)(sizeof(pcamv_mb_t) / 4) + 1) {
-            if (i < (int)(sizeof(pcamv_mb_t) / 4)) ((uint32_t *)L->ccost)[i] = ((const uint32_t *)&F.rec_mb[xy])[i];
-            else L->ccost[191] = F.car_base ? F.car_base[xy] : 0;
+            if (i < (int)(sizeof(pcamv_mb_t) / 4)) ((uint32_t *)L->ccost)[i] = ((const uint32_t *)&FD(F).rec_mb[xy])[i];
+            else L->ccost[191] = FD(F).car_base ? FD(F).car_base[xy] : 0;
         }
     }
     PCAMV_WAVE_SYNC();
@@ -265,7 +265,7 @@ PCAMV_DEV int mbk_pass2(const FrameDev &F, MBLocal *L, int mb_x, int mb_y, int s
         const int base = unit ? unit->base : L->ccost[191];
         PCAMV_WAVE_SYNC();
         /* its carriers' flip flags: one more round trip, for the macroblocks that have a flipped carrier at all */
-        if (PCAMV_RFL(any_flip)) { FOR_CAND(j, n) L->cxy[j] = F.flip ? (uint32_t)(F.flip[base + j] == 1) : 0u; }
+        if (PCAMV_RFL(any_flip)) { FOR_CAND(j, n) L->cxy[j] = FD(F).flip ? (uint32_t)(FD(F).flip[base + j] == 1) : 0u; }
         else { FOR_CAND(j, n) L->cxy[j] = 0u; }
         PCAMV_WAVE_SYNC();
         FOR_CAND(i, 16) {
@@ -282,12 +282,12 @@ PCAMV_DEV int mbk_pass2(const FrameDev &F, MBLocal *L, int mb_x, int mb_y, int s
     /* A macroblock whose motion is what the first pass decided -- no carrier of it flipped; skipped with the same skip prediction --
      * reconstructs to what the first pass stored (same type, motion, source, reference and quantiser): pixels and non-zero flags
      * are taken from there instead of being made again.  (~7 of 8 macroblocks at half a bit per carrier.) */
-    const int reuse = same && F.rec_is_pass1;
+    const int reuse = same && FD(F).rec_is_pass1;
     if (reuse) {
 #ifdef PCAMV_HOST_EMU
-        L->nnz_mask = F.nnz[xy];
+        L->nnz_mask = FD(F).nnz[xy];
 #else
-        L->nnz_mask = unit ? unit->nnz1 : rfl((int)F.nnz[xy]);
+        L->nnz_mask = unit ? unit->nnz1 : rfl((int)FD(F).nnz[xy]);
         if (!unit) {   /* (the layout of prim_store_rec) */
             const int lane = LANE();
             PCAMV_WAVE_SYNC();
@@ -311,12 +311,12 @@ PCAMV_DEV int mbk_pass2(const FrameDev &F, MBLocal *L, int mb_x, int mb_y, int s
     PCAMV_WAVE_SYNC();
     FOR_CAND(i, 16) {
         int x = i & 3, y = i >> 2;
-        NB_ST32(&F.mv[2 * (b4 + y * s4 + x)], NB_PACK16(L->cmv[SCAN8_0 + x + 8 * y][0], L->cmv[SCAN8_0 + x + 8 * y][1]));
+        NB_ST32(&FD(F).mv[2 * (b4 + y * s4 + x)], NB_PACK16(L->cmv[SCAN8_0 + x + 8 * y][0], L->cmv[SCAN8_0 + x + 8 * y][1]));
     }
     if (PCAMV_LANE0) {
-        NB_ST8(&F.mb_type[xy], L->i_type);
-        NB_ST16(&F.ref8[b8], 0); NB_ST16(&F.ref8[b8 + s8], 0);
-        NB_ST16(&F.nnz[xy], L->nnz_mask);
+        NB_ST8(&FD(F).mb_type[xy], L->i_type);
+        NB_ST16(&FD(F).ref8[b8], 0); NB_ST16(&FD(F).ref8[b8 + s8], 0);
+        NB_ST16(&FD(F).nnz[xy], L->nnz_mask);
     }
     return !reuse;
 }
@@ -327,6 +327,6 @@ PCAMV_DEV void mbk_encode(const FrameDev &F, MBLocal *L, Analysis *a, int xy)
     update_cache(L, a);
     mb_encode(F, L);
     prim_store_rec(F, L);
-    if (PCAMV_LANE0 && F.nnz) F.nnz[xy] = (uint16_t)L->nnz_mask;
+    if (PCAMV_LANE0 && FD(F).nnz) FD(F).nnz[xy] = (uint16_t)L->nnz_mask;
 }
 #endif

@@ -621,14 +621,15 @@ __device__ __forceinline__ int prim_chroma4x4_cost(const FrameDev &F, MBLocal *L
 
 __device__ __forceinline__ void prim_load_fenc(const FrameDev &F, MBLocal *L)
 {
+    const auto &D = FD(F);
     PCAMV_WAVE_SYNC();
     const int lane = LANE();
     { int row = lane >> 2, c4 = lane & 3;
-      sts4(L->fenc + row * 16 + c4 * 4, *(const uint32_t *)(F.fenc[0] + (size_t)(L->mb_y * 16 + row) * F.w + L->mb_x * 16 + c4 * 4)); }
+      sts4(L->fenc + row * 16 + c4 * 4, *(const uint32_t *)(D.fenc[0] + (size_t)(L->mb_y * 16 + row) * D.w + L->mb_x * 16 + c4 * 4)); }
     if (lane < 32) {
         int plane = lane >> 4, row = (lane & 15) >> 1, c4 = lane & 1;
         sts4(L->fenc + 256 + row * 16 + plane * 8 + c4 * 4,
-             *(const uint32_t *)((plane ? F.fenc[2] : F.fenc[1]) + (size_t)(L->mb_y * 8 + row) * (F.w >> 1) + L->mb_x * 8 + c4 * 4));
+             *(const uint32_t *)((plane ? D.fenc[2] : D.fenc[1]) + (size_t)(L->mb_y * 8 + row) * (D.w >> 1) + L->mb_x * 8 + c4 * 4));
     }
     PCAMV_WAVE_SYNC();
 }
@@ -711,11 +712,12 @@ __device__ __forceinline__ void quant_score_dequant(const FrameDev &F, bool is_l
 {
     *rawdc = d[0];
     if (!is_l) d[0] = 0;
-    const int qp = is_l ? F.qp : F.chroma_qp;
+    const auto &Q = FD(F);          /* one read of the descriptor for the whole quantiser set: wide scalar loads, asked for before the arithmetic */
+    const int qp = is_l ? Q.qp : Q.chroma_qp;
     /* the three position classes of the flat quantiser, picked once (no indexing of F inside the loops) */
-    const int mf0 = is_l ? F.q_mf[0][0] : F.q_mf[1][0], mf1 = is_l ? F.q_mf[0][1] : F.q_mf[1][1], mf2 = is_l ? F.q_mf[0][2] : F.q_mf[1][2];
-    const int bs0 = is_l ? F.q_bias[0][0] : F.q_bias[1][0], bs1 = is_l ? F.q_bias[0][1] : F.q_bias[1][1], bs2 = is_l ? F.q_bias[0][2] : F.q_bias[1][2];
-    const int dq0 = is_l ? F.dq_mf[0] : F.dq_mf_c[0], dq1 = is_l ? F.dq_mf[1] : F.dq_mf_c[1], dq2 = is_l ? F.dq_mf[2] : F.dq_mf_c[2];
+    const int mf0 = is_l ? Q.q_mf[0][0] : Q.q_mf[1][0], mf1 = is_l ? Q.q_mf[0][1] : Q.q_mf[1][1], mf2 = is_l ? Q.q_mf[0][2] : Q.q_mf[1][2];
+    const int bs0 = is_l ? Q.q_bias[0][0] : Q.q_bias[1][0], bs1 = is_l ? Q.q_bias[0][1] : Q.q_bias[1][1], bs2 = is_l ? Q.q_bias[0][2] : Q.q_bias[1][2];
+    const int dq0 = is_l ? Q.dq_mf[0] : Q.dq_mf_c[0], dq1 = is_l ? Q.dq_mf[1] : Q.dq_mf_c[1], dq2 = is_l ? Q.dq_mf[2] : Q.dq_mf_c[2];
     /* quantise (quant.c:33-48: c > 0 ? (bias + c) * mf >> 16 : -((bias - c) * mf >> 16)) as ONE signed multiply-add and an arithmetic
      * shift per coefficient: with bm = bias * mf (< 2^16, so c = 0 stays 0) the positive arm is (c * mf + bm) >> 16, and the negative one,
      * -floor(x / 2^16) with x = |c| * mf + bm, is (c * mf - bm + 65535) >> 16; |c| < 2^14, mf < 2^16.  The non-zero mask in zigzag order
@@ -900,6 +902,7 @@ __device__ __forceinline__ int dpp_x4(int v)
  * per-block non-zero flags as the entropy coder sees them (L->nzc: zero where an 8x8 / the macroblock / a chroma plane was dropped) */
 __device__ __forceinline__ void prim_mb_transform(const FrameDev &F, MBLocal *L, int lv_ = 0)
 {
+    const auto &Q = FD(F);          /* the quantiser set and the decimation switch: one read of the descriptor, asked for before the pixels */
     PCAMV_WAVE_SYNC();
     const int lv = rfl(lv_);
     const int lane = LANE();
@@ -936,9 +939,9 @@ __device__ __forceinline__ void prim_mb_transform(const FrameDev &F, MBLocal *L,
     if (!is_l && !h) c[0] = 0;
     {
         /* quantiser and dequantiser of the lane's eight positions: class (j & 1) + (vertical frequency & 1) -- c[0..3]: 0 1 0 1, c[4..7]: 1 2 1 2 */
-        const int mf0 = is_l ? F.q_mf[0][0] : F.q_mf[1][0], mf1 = is_l ? F.q_mf[0][1] : F.q_mf[1][1], mf2 = is_l ? F.q_mf[0][2] : F.q_mf[1][2];
-        const int bs0 = is_l ? F.q_bias[0][0] : F.q_bias[1][0], bs1 = is_l ? F.q_bias[0][1] : F.q_bias[1][1], bs2 = is_l ? F.q_bias[0][2] : F.q_bias[1][2];
-        const int dq0 = is_l ? F.dq_mf[0] : F.dq_mf_c[0], dq1 = is_l ? F.dq_mf[1] : F.dq_mf_c[1], dq2 = is_l ? F.dq_mf[2] : F.dq_mf_c[2];
+        const int mf0 = is_l ? Q.q_mf[0][0] : Q.q_mf[1][0], mf1 = is_l ? Q.q_mf[0][1] : Q.q_mf[1][1], mf2 = is_l ? Q.q_mf[0][2] : Q.q_mf[1][2];
+        const int bs0 = is_l ? Q.q_bias[0][0] : Q.q_bias[1][0], bs1 = is_l ? Q.q_bias[0][1] : Q.q_bias[1][1], bs2 = is_l ? Q.q_bias[0][2] : Q.q_bias[1][2];
+        const int dq0 = is_l ? Q.dq_mf[0] : Q.dq_mf_c[0], dq1 = is_l ? Q.dq_mf[1] : Q.dq_mf_c[1], dq2 = is_l ? Q.dq_mf[2] : Q.dq_mf_c[2];
         const int bm0 = (int)mul24u((uint32_t)bs0, (uint32_t)mf0), bm1 = (int)mul24u((uint32_t)bs1, (uint32_t)mf1), bm2 = (int)mul24u((uint32_t)bs2, (uint32_t)mf2);
         /* scan positions (inverse zigzag of raster index 4 j + vertical frequency): vf 0: 0 1 5 6, 1: 2 4 7 12, 2: 3 8 11 13, 3: 9 10 14 15 */
         int mx = 0, mn = 0;
@@ -968,7 +971,7 @@ __device__ __forceinline__ void prim_mb_transform(const FrameDev &F, MBLocal *L,
             const unsigned zr = is_l ? zm << 1 : zm, z = zr | 1u;
             const unsigned s1 = z << 1, s3 = s1 | s1 << 1 | z << 3, s6 = s3 | s3 << 3;
             score = big ? 9 : __builtin_popcount(zr & s1) + __builtin_popcount(zr & s3) + __builtin_popcount(zr & s6);
-            const int qbits = (is_l ? F.qp : F.chroma_qp) / 6 - 4;
+            const int qbits = (is_l ? Q.qp : Q.chroma_qp) / 6 - 4;
 #pragma unroll
             for (int k = 0; k < 8; k++) {
                 const int cls = (k & 1) + (k >> 2), dqv = cls == 0 ? dq0 : cls == 1 ? dq1 : dq2;
@@ -977,12 +980,12 @@ __device__ __forceinline__ void prim_mb_transform(const FrameDev &F, MBLocal *L,
         }
     }
     /* luma: 8x8 sums over the eight lanes of an 8x8, macroblock sum over lanes 0..31; chroma: the plane's eight lanes */
-    const int sc = (nz && F.b_dct_decimate && !h) ? score : 0;
+    const int sc = (nz && Q.b_dct_decimate && !h) ? score : 0;
     int q8 = sc + dpp_qp1(sc); q8 += dpp_qp2(q8); q8 += dpp_hmir(q8);
     int any8 = nz | dpp_qp2(nz); any8 |= dpp_hmir(any8);
     const int r16 = q8 + dpp_mir(q8);
     const int row = __builtin_amdgcn_readlane(r16, 0) + __builtin_amdgcn_readlane(r16, 16);
-    const bool keep = F.b_dct_decimate ? (q8 >= 4 && row >= 6) : any8 != 0;
+    const bool keep = Q.b_dct_decimate ? (q8 >= 4 && row >= 6) : any8 != 0;
     /* chroma DC: 2x2 transform over the plane's four blocks (their h = 0 lanes, two apart): butterflies with lane ^ 2, then lane ^ 4; the
      * network leaves coefficient (k & 1) * 2 + (k >> 1) in the lane of block k -- zigzag_scan_2x2_dc's place k -- and, run again on the
      * quantised values, block k's reconstructed DC in the lane of block k */
@@ -990,11 +993,11 @@ __device__ __forceinline__ void prim_mb_transform(const FrameDev &F, MBLocal *L,
     int cdc = mad24s(rawdc, s2, dpp_qp2(rawdc));
     cdc = mad24s(cdc, s4, dpp_x4(cdc));
     int dcq;
-    { const int mf = F.q_mf[1][0] >> 1, bias = F.q_bias[1][0] << 1;
+    { const int mf = Q.q_mf[1][0] >> 1, bias = Q.q_bias[1][0] << 1;
       dcq = cdc > 0 ? ((bias + cdc) * mf >> 16) : -((bias - cdc) * mf >> 16); }
     if (h || !is_c) dcq = 0;
     int nzdc = dcq != 0; nzdc |= dpp_qp1(nzdc); nzdc |= dpp_qp2(nzdc); nzdc |= dpp_hmir(nzdc);
-    int dmf = F.dq_mf_c[0], qbits = F.chroma_qp / 6 - 5;
+    int dmf = Q.dq_mf_c[0], qbits = Q.chroma_qp / 6 - 5;
     if (qbits > 0) { dmf <<= qbits; qbits = 0; }
     int idc = mad24s(dcq, s2, dpp_qp2(dcq));
     idc = mad24s(idc, s4, dpp_x4(idc));
@@ -1004,7 +1007,7 @@ __device__ __forceinline__ void prim_mb_transform(const FrameDev &F, MBLocal *L,
         const int other = dpp_qp1(rdc);
         rdc = h ? other : rdc;
     }
-    const int cmode = (q8 < 7 && F.b_dct_decimate) || !any8 ? (nzdc ? 1 : 0) : 2;
+    const int cmode = (q8 < 7 && Q.b_dct_decimate) || !any8 ? (nzdc ? 1 : 0) : 2;
     const unsigned long long keep_mask = __ballot(is_l && keep), ac_mask = __ballot(is_c && cmode == 2);
     const bool inv = is_l ? keep && nz : is_c && cmode == 2;
     if (is_c && cmode == 2 && nzdc && !h) c[0] = (int16_t)rdc;
@@ -1088,6 +1091,7 @@ __device__ __forceinline__ void prim_predict_win16(const FrameDev &F, MBLocal *L
  * (macroblock j = lane / 8, plane = quad) */
 __device__ __forceinline__ void prim_mb_transform4(const FrameDev &F, MBLocal *L)
 {
+    const auto &Q = FD(F);
     PCAMV_WAVE_SYNC();
     const int lane = LANE();
     {
@@ -1095,11 +1099,11 @@ __device__ __forceinline__ void prim_mb_transform4(const FrameDev &F, MBLocal *L
         uint8_t *pr = L->pred4[j];
         int16_t d[16]; int nz, score, rawdc;
         residual_block_at(F, L, pr, px, py, true, d, &nz, &score, &rawdc);
-        const int sc = (nz && F.b_dct_decimate) ? score : 0;
+        const int sc = (nz && Q.b_dct_decimate) ? score : 0;
         int q8 = sc + dpp_qp1(sc); q8 += dpp_qp2(q8);
         int any8 = nz | dpp_qp1(nz); any8 |= dpp_qp2(any8);
         int row = q8 + dpp_hmir(q8); row += dpp_mir(row);
-        const bool keep = F.b_dct_decimate ? (q8 >= 4 && row >= 6) : any8 != 0;
+        const bool keep = Q.b_dct_decimate ? (q8 >= 4 && row >= 6) : any8 != 0;
         if (keep && nz) idct4x4_add(pr + py * 16 + px, d);
     }
     if (lane < 32) {
@@ -1107,18 +1111,18 @@ __device__ __forceinline__ void prim_mb_transform4(const FrameDev &F, MBLocal *L
         uint8_t *pr = L->pred4[j];
         int16_t d[16]; int nz, score, rawdc;
         residual_block_at(F, L, pr, px, py, false, d, &nz, &score, &rawdc);
-        const int sc = (nz && F.b_dct_decimate) ? score : 0;
+        const int sc = (nz && Q.b_dct_decimate) ? score : 0;
         int q8 = sc + dpp_qp1(sc); q8 += dpp_qp2(q8);
         int any8 = nz | dpp_qp1(nz); any8 |= dpp_qp2(any8);
         const int cdc = quad_had2x2(rawdc, ci);
         int dcq;
-        { const int mf = F.q_mf[1][0] >> 1, bias = F.q_bias[1][0] << 1;
+        { const int mf = Q.q_mf[1][0] >> 1, bias = Q.q_bias[1][0] << 1;
           dcq = cdc > 0 ? ((bias + cdc) * mf >> 16) : -((bias - cdc) * mf >> 16); }
         int nzdc = dcq != 0; nzdc |= dpp_qp1(nzdc); nzdc |= dpp_qp2(nzdc);
-        int dmf = F.dq_mf_c[0], qbits = F.chroma_qp / 6 - 5;
+        int dmf = Q.dq_mf_c[0], qbits = Q.chroma_qp / 6 - 5;
         if (qbits > 0) { dmf <<= qbits; qbits = 0; }
         const int rdc = (int16_t)(quad_had2x2(dcq, ci) * dmf >> -qbits);
-        const int cmode = (q8 < 7 && F.b_dct_decimate) || !any8 ? (nzdc ? 1 : 0) : 2;
+        const int cmode = (q8 < 7 && Q.b_dct_decimate) || !any8 ? (nzdc ? 1 : 0) : 2;
         uint8_t *dst = pr + py * 16 + px;
         if (cmode == 2) { if (nzdc) d[0] = (int16_t)rdc; idct4x4_add(dst, d); }
         else if (cmode == 1) {
@@ -1161,15 +1165,16 @@ __device__ __forceinline__ void prim_copy_pred(MBLocal *L, uint8_t *dst)
 /* wt: store write-through (agent scope), for pixels another wave reads in the same launch (pass 2 -> loop filter) */
 __device__ __forceinline__ void prim_store_rec(const FrameDev &F, MBLocal *L, bool wt = false)
 {
+    const auto &D = FD(F);
     PCAMV_WAVE_SYNC();
     const int lane = LANE();
     { int row = lane >> 2, c4 = lane & 3;
-      uint32_t *d = (uint32_t *)(F.rec[0] + (size_t)(L->mb_y * 16 + row) * F.w + L->mb_x * 16 + c4 * 4);
+      uint32_t *d = (uint32_t *)(D.rec[0] + (size_t)(L->mb_y * 16 + row) * D.w + L->mb_x * 16 + c4 * 4);
       const uint32_t v = lds4(L->pred + row * 16 + c4 * 4);
       if (wt) NB_ST32(d, v); else *d = v; }
     if (lane < 32) {
         int plane = lane >> 4, row = (lane & 15) >> 1, c4 = lane & 1;
-        uint32_t *d = (uint32_t *)((plane ? F.rec[2] : F.rec[1]) + (size_t)(L->mb_y * 8 + row) * (F.w >> 1) + L->mb_x * 8 + c4 * 4);
+        uint32_t *d = (uint32_t *)((plane ? D.rec[2] : D.rec[1]) + (size_t)(L->mb_y * 8 + row) * (D.w >> 1) + L->mb_x * 8 + c4 * 4);
         const uint32_t v = lds4(L->pred + 256 + row * 16 + plane * 8 + c4 * 4);
         if (wt) NB_ST32(d, v); else *d = v;
     }
@@ -1178,19 +1183,20 @@ __device__ __forceinline__ void prim_store_rec(const FrameDev &F, MBLocal *L, bo
  * reconstruction IS its final one) */
 __device__ __forceinline__ void prim_load_rec(const FrameDev &F, MBLocal *L)
 {
+    const auto &D = FD(F);
     PCAMV_WAVE_SYNC();
     const int lane = LANE();
     { int row = lane >> 2, c4 = lane & 3;
-      sts4(L->pred + row * 16 + c4 * 4, *(const uint32_t *)(F.rec[0] + (size_t)(L->mb_y * 16 + row) * F.w + L->mb_x * 16 + c4 * 4)); }
+      sts4(L->pred + row * 16 + c4 * 4, *(const uint32_t *)(D.rec[0] + (size_t)(L->mb_y * 16 + row) * D.w + L->mb_x * 16 + c4 * 4)); }
     if (lane < 32) {
         int plane = lane >> 4, row = (lane & 15) >> 1, c4 = lane & 1;
-        sts4(L->pred + 256 + row * 16 + plane * 8 + c4 * 4, *(const uint32_t *)((plane ? F.rec[2] : F.rec[1]) + (size_t)(L->mb_y * 8 + row) * (F.w >> 1) + L->mb_x * 8 + c4 * 4));
+        sts4(L->pred + 256 + row * 16 + plane * 8 + c4 * 4, *(const uint32_t *)((plane ? D.rec[2] : D.rec[1]) + (size_t)(L->mb_y * 8 + row) * (D.w >> 1) + L->mb_x * 8 + c4 * 4));
     }
     PCAMV_WAVE_SYNC();
 }
 __device__ __forceinline__ void prim_store_mvr(const FrameDev &F, MBLocal *L, int mvx, int mvy)
 {
-    if (LANE() == 0) NB_ST32(&F.mvr[2 * L->mb_xy], NB_PACK16(mvx, mvy));
+    if (LANE() == 0) NB_ST32(&FD(F).mvr[2 * L->mb_xy], NB_PACK16(mvx, mvy));
 }
 PCAMV_DEV void predict_mv(MBLocal *L, int idx, int width, int mvp[2]);      /* pcamv_logic.h */
 #include "pcamv_prims_rd_gpu.h"

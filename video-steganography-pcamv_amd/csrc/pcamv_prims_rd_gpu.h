@@ -31,11 +31,11 @@ __device__ __forceinline__ void prim_mb_fetch(const FrameDev &F, int mb_x_, int 
     const int lane = LANE();
     const int xy = mb_y * F.mb_w + mb_x, top = xy - F.mb_w;
     { const int row = lane >> 2, c4 = lane & 3;
-      P.fy = *(const uint32_t *)(F.fenc[0] + (size_t)(mb_y * 16 + row) * F.w + mb_x * 16 + c4 * 4); }
+      P.fy = *(const uint32_t *)(FD(F).fenc[0] + (size_t)(mb_y * 16 + row) * FD(F).w + mb_x * 16 + c4 * 4); }
     P.fc = 0;
     if (lane < 32) {
         const int plane = lane >> 4, row = (lane & 15) >> 1, c4 = lane & 1;
-        P.fc = *(const uint32_t *)((plane ? F.fenc[2] : F.fenc[1]) + (size_t)(mb_y * 8 + row) * (F.w >> 1) + mb_x * 8 + c4 * 4);
+        P.fc = *(const uint32_t *)((plane ? FD(F).fenc[2] : FD(F).fenc[1]) + (size_t)(mb_y * 8 + row) * (FD(F).w >> 1) + mb_x * 8 + c4 * 4);
     }
     P.role = 0; P.b0 = P.b1 = 0; P.s0 = P.s1 = P.s2 = P.t0 = P.t1 = P.t2 = P.t3 = 0;
     if (!rd) return;
@@ -45,9 +45,9 @@ __device__ __forceinline__ void prim_mb_fetch(const FrameDev &F, int mb_x_, int 
         const int k8 = lane & 7, l8 = (lane >> 3) & 1, ok8 = lane < 16 && (l8 ? (nb & NB_LEFT) : (nb & NB_TOP));
         const int k32 = (lane - 16) & 7, l32 = k32 >> 2, ok32 = lane >= 16 && lane < 24 && (l32 ? (nb & NB_LEFT) : (nb & NB_TOP));
         const int ok16 = (lane == 24 && (nb & NB_TOP)) || (lane == 25 && (nb & NB_LEFT));
-        const uint32_t v8 = (uint8_t)NB_LD8(&F.nb_nz[(ok8 ? (l8 ? xy - 1 : top) : xy) * 16 + 8 * l8 + k8]);
-        const uint32_t v32 = NB_LD32(&F.nb_mvd[((ok32 ? (l32 ? xy - 1 : top) : xy) * 8 + k32) * 2]);
-        const uint32_t v16 = (uint32_t)(int)(int16_t)NB_LD16(&F.nb_cbp[ok16 ? (lane == 24 ? top : xy - 1) : xy]);
+        const uint32_t v8 = (uint8_t)NB_LD8(&FD(F).nb_nz[(ok8 ? (l8 ? xy - 1 : top) : xy) * 16 + 8 * l8 + k8]);
+        const uint32_t v32 = NB_LD32(&FD(F).nb_mvd[((ok32 ? (l32 ? xy - 1 : top) : xy) * 8 + k32) * 2]);
+        const uint32_t v16 = (uint32_t)(int)(int16_t)NB_LD16(&FD(F).nb_cbp[ok16 ? (lane == 24 ? top : xy - 1) : xy]);
         P.role = lane < 16 ? (ok8 ? v8 : 0x80u) : ok32 ? v32 : ok16 ? v16 : 0u;
     }
     /* borders: luma 25 + 16, chroma 2 x (9 + 8) = 75 bytes, agent-scope loads (the neighbours stored them write-through) */
@@ -57,21 +57,21 @@ __device__ __forceinline__ void prim_mb_fetch(const FrameDev &F, int mb_x_, int 
         int c, is_left, k;
         if (i < 41) { c = 0; is_left = i >= 25; k = is_left ? i - 25 : i - 1; }
         else { const int j = (i - 41) % 17; c = 1 + (i - 41) / 17; is_left = j >= 9; k = is_left ? j - 9 : j - 1; }
-        const int w = c ? 8 : 16, pw = c ? F.w >> 1 : F.w, x0 = mb_x * w, y0 = mb_y * w;
-        const uint8_t *pl = c == 0 ? F.rec[0] : c == 1 ? F.rec[1] : F.rec[2];
+        const int w = c ? 8 : 16, pw = c ? FD(F).w >> 1 : FD(F).w, x0 = mb_x * w, y0 = mb_y * w;
+        const uint8_t *pl = c == 0 ? FD(F).rec[0] : c == 1 ? FD(F).rec[1] : FD(F).rec[2];
         const bool ok = lane + 64 * r < 75 && (is_left ? mb_x > 0 : mb_y > 0);
         const size_t o = !ok ? (size_t)y0 * pw + x0 : is_left ? (size_t)(y0 + k) * pw + x0 - 1 : (size_t)(y0 - 1) * pw + clip3i(x0 + k, 0, pw - 1);
         const int v = (uint8_t)NB_LD8((const int8_t *)pl + o);
         if (r == 0) P.b0 = ok ? v : 0; else P.b1 = ok ? v : 0;
     }
     if (F.b_cabac) {
-        const uint32_t *src = (const uint32_t *)(xy == 0 ? F.cabac_init : F.cabac);
+        const uint32_t *src = (const uint32_t *)(xy == 0 ? FD(F).cabac_init : FD(F).cabac);
         if (xy == 0) { P.s0 = src[lane]; if (lane < 52) P.s1 = src[64 + lane]; }
         else { P.s0 = NB_LD32(src + lane); if (lane < 52) P.s1 = NB_LD32(src + 64 + lane); }
-        P.t0 = F.cabac_tab[lane]; P.t1 = F.cabac_tab[64 + lane]; P.t2 = F.cabac_tab[128 + lane]; P.t3 = F.cabac_tab[192 + lane];
+        P.t0 = FD(F).cabac_tab[lane]; P.t1 = FD(F).cabac_tab[64 + lane]; P.t2 = FD(F).cabac_tab[128 + lane]; P.t3 = FD(F).cabac_tab[192 + lane];
     }
     if (F.inter & PCAMV_ANALYSE_PSUB8x8) {       /* the macroblock's own non-zero / mvd entries as the macroblock coded before it left them (PCAMV_CHAIN_NZ / _MVD) */
-        const uint32_t *src = (const uint32_t *)(xy == 0 ? F.cabac_init : F.cabac) + PCAMV_CHAIN_NZ / 4;
+        const uint32_t *src = (const uint32_t *)(xy == 0 ? FD(F).cabac_init : FD(F).cabac) + PCAMV_CHAIN_NZ / 4;
         if (lane < 22) P.s2 = xy == 0 ? src[lane] : NB_LD32(src + lane);
     }
 }
@@ -107,7 +107,7 @@ __device__ __forceinline__ void prim_mb_fetch_store(const FrameDev &F, MBLocal *
             }
         } else if (lane == 24) L->cbp_top = (nb & NB_TOP) ? (int)P.role : -1;
         else if (lane == 25) L->cbp_left = (nb & NB_LEFT) ? (int)P.role : -1;
-        else if (lane == 26) L->b_fast_intra = xy > 4 && F.ref_is_inter;          /* analyse.c:363-378 */
+        else if (lane == 26) L->b_fast_intra = xy > 4 && FD(F).ref_is_inter;          /* analyse.c:363-378 */
 #pragma unroll
         for (int r = 0; r < 2; r++) {
             const int i = lane + 64 * r;
@@ -341,13 +341,14 @@ __device__ __forceinline__ void prim_intra4_encode(const FrameDev &F, MBLocal *L
         d[i * 4 + 0] = s03 + s12; d[i * 4 + 1] = 2 * d03 + d12; d[i * 4 + 2] = s03 - s12; d[i * 4 + 3] = d03 - 2 * d12;
     }
     int nz = 0;
-    const int qbits = F.qp / 6 - 4;
+    const auto &Q = FD(F);
+    const int qbits = Q.qp / 6 - 4;
     int16_t c[16];
 #pragma unroll
     for (int i = 0; i < 16; i++) {
         const int cls = (i & 1) + ((i >> 2) & 1);
-        const int mf = cls == 0 ? F.q_mf_i[0] : cls == 1 ? F.q_mf_i[1] : F.q_mf_i[2], bias = cls == 0 ? F.q_bias_i[0] : cls == 1 ? F.q_bias_i[1] : F.q_bias_i[2];
-        const int dq = cls == 0 ? F.dq_mf[0] : cls == 1 ? F.dq_mf[1] : F.dq_mf[2];
+        const int mf = cls == 0 ? Q.q_mf_i[0] : cls == 1 ? Q.q_mf_i[1] : Q.q_mf_i[2], bias = cls == 0 ? Q.q_bias_i[0] : cls == 1 ? Q.q_bias_i[1] : Q.q_bias_i[2];
+        const int dq = cls == 0 ? Q.dq_mf[0] : cls == 1 ? Q.dq_mf[1] : Q.dq_mf[2];
         int v = d[i];
         const int qa = (int)(mul24u((uint32_t)(bias + iabs(v)), (uint32_t)mf) >> 16);      /* branch-free form, see quant_score_dequant */
         v = v < 0 ? -qa : qa;
@@ -968,10 +969,10 @@ __device__ __forceinline__ void prim_encode_p8x8(const FrameDev &F, MBLocal *L, 
     int16_t d[16];
     int nz = 0, score = 0, rawdc = 0;
     if (is_l || is_c) residual_block(F, L, px, py, lane < 16, d, &nz, &score, &rawdc, L->coef[lane < 24 ? lane : 0]);
-    const int sc = (is_l && nz && F.b_dct_decimate) ? score : 0, nzl = is_l ? nz : 0;
+    const int sc = (is_l && nz && FD(F).b_dct_decimate) ? score : 0, nzl = is_l ? nz : 0;
     int q8 = sc + dpp_qp1(sc); q8 += dpp_qp2(q8);
     int any8 = nzl | dpp_qp1(nzl); any8 |= dpp_qp2(any8);
-    const bool keep = any8 != 0 && !(F.b_dct_decimate && q8 < 4);
+    const bool keep = any8 != 0 && !(FD(F).b_dct_decimate && q8 < 4);
     uint8_t *dst = L->pred + py * 16 + px;
     if (is_l) { if (keep && nz) idct4x4_add(dst, d); L->nzc[scan8_of(lane)] = (uint8_t)(keep && nz); }
     else if (is_c) { if (nz) idct4x4_add(dst, d); L->nzc[scan8_all_of(lane)] = (uint8_t)nz; }
@@ -1105,26 +1106,26 @@ __device__ __forceinline__ void prim_rd_commit(const FrameDev &F, MBLocal *L, in
     if (lane < 16) {
         const int k = lane & 7, is_right = lane >> 3;
         const int blk = is_right ? (k < 4 ? (k == 0 ? 5 : k == 1 ? 7 : k == 2 ? 13 : 15) : 17 + 2 * (k - 4)) : (k < 4 ? (k == 0 ? 10 : k == 1 ? 11 : k == 2 ? 14 : 15) : k < 6 ? 18 + (k - 4) : 22 + (k - 6));
-        NB_ST8(&F.nb_nz[xy * 16 + lane], skip ? 0 : L->nzc[scan8_all_of(blk)]);
+        NB_ST8(&FD(F).nb_nz[xy * 16 + lane], skip ? 0 : L->nzc[scan8_all_of(blk)]);
     } else if (lane < 24) {
         const int k = lane - 16, pos = k < 4 ? SCAN8_0 + k + 8 * 3 : SCAN8_0 + 3 + 8 * (k - 4);
-        NB_ST32(&F.nb_mvd[(xy * 8 + k) * 2], skip ? 0u : ((const uint32_t *)L->cmvd)[pos]);
+        NB_ST32(&FD(F).nb_mvd[(xy * 8 + k) * 2], skip ? 0u : ((const uint32_t *)L->cmvd)[pos]);
     } else if (lane == 24) {
         const int cbp = skip ? 0 : ((F.b_cabac ? (L->nzc[scan8_all_of(25)] << 9 | L->nzc[scan8_all_of(26)] << 10) : 0) | L->cbp_chroma << 4 | L->cbp_luma);
-        NB_ST16(&F.nb_cbp[xy], cbp);
+        NB_ST16(&FD(F).nb_cbp[xy], cbp);
     }
     if (F.b_cabac) {
         const uint32_t *src = (const uint32_t *)L_CAB(L, 0);
-        NB_ST32((uint32_t *)F.cabac + lane, src[lane]);
-        if (lane < 52) NB_ST32((uint32_t *)F.cabac + 64 + lane, src[64 + lane]);
-        if (F.dbg_hash && lane == 0) {
+        NB_ST32((uint32_t *)FD(F).cabac + lane, src[lane]);
+        if (lane < 52) NB_ST32((uint32_t *)FD(F).cabac + 64 + lane, src[64 + lane]);
+        if (FD(F).dbg_hash && lane == 0) {
             uint32_t h = 2166136261u;
             for (int i = 0; i < 460; i++) h = (h ^ L_CAB(L, 0)[i]) * 16777619u;
-            F.dbg_hash[xy] = h;
+            FD(F).dbg_hash[xy] = h;
         }
     }
     if (F.inter & PCAMV_ANALYSE_PSUB8x8) {
-        uint32_t *dst = (uint32_t *)F.cabac + PCAMV_CHAIN_NZ / 4;
+        uint32_t *dst = (uint32_t *)FD(F).cabac + PCAMV_CHAIN_NZ / 4;
         if (lane < 6) {
             uint32_t w = 0;
 #pragma unroll
