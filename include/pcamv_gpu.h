@@ -27,6 +27,8 @@
  *   pcamv_gpu_stc_extract       (no reference counterpart: extractor defined in SURVEY 8(c))
  *   pcamv_gpu_set_payload*      the message source, encoder.c:1838-1840 (rand() there: a caller's payload here)
  *   pcamv_gpu_*extract_*, rx_*  (no reference counterpart: the extractor is absent from the reference)
+ *   pcamv_gpu_*_slices*,        (no reference counterpart) the receiver fed from stream bytes: CABAC P slices parsed on the
+ *   parse_pslice_cabac_device   device, one wavefront per slice (k_parse_pslice), straight into the extractor
  *   pcamv_gpu_close             x264_encoder_close's frees
  *
  * All functions return 0 on success and a negative PCAMV_E* code on error; the message is
@@ -226,7 +228,7 @@ int  pcamv_gpu_batch_create(pcamv_ctx_t *const *ctxs, int n, pcamv_batch_t **bat
 void pcamv_gpu_batch_destroy(pcamv_batch_t *batch);
 int  pcamv_gpu_batch_step(pcamv_batch_t *batch, int qp, float emrate, void *stream);
 /* kernel: the dominant kernel's name (below), or one of "k_embed_prepare", "k_extract_prepare", "k_extract_bits", "k_payload_check" */
-int  pcamv_gpu_batch_kernel_time(pcamv_batch_t *batch, const char *kernel, double *avg_ms, int *launches, int reset);
+int  pcamv_gpu_batch_kernel_time(pcamv_batch_t *batch, const char *kernel, double *avg_ms, int *launches, int reset);    /* ... or "k_parse_pslice" */
 const char *pcamv_gpu_batch_last_error(const pcamv_batch_t *batch);
 /* Closed loop on the device: with on != 0 every batch step ends with pass 2 + the loop filter (embedding must be
  * on: the flip map comes from it), leaving each context's deblocked reconstruction in its device planes
@@ -279,6 +281,7 @@ int pcamv_gpu_debug_state_hash_fetch(pcamv_ctx_t *ctx, uint32_t *out);
 int pcamv_gpu_abi_version(void);
 /* What the library can do beyond the calls of its ABI version: a mask of PCAMV_FEATURE_* (additions keep the version). */
 #define PCAMV_FEATURE_PAYLOAD 0x1u      /* the payload path below */
+#define PCAMV_FEATURE_SLICE_PARSER 0x2u /* CABAC P slices parsed on the device (the receiver from a stream, at the end of this file) */
 unsigned pcamv_gpu_features(void);
 
 /* ---- Payload path: the caller's bits through the device-resident entry points, and back out on the device ----
@@ -322,6 +325,42 @@ int pcamv_gpu_extract_pframe(pcamv_ctx_t *ctx, const pcamv_mb_t *mbs, float emra
 /* diff[i] = number of bits in which context i's received stream differs from its attached payload, payload bits past its end
  * counting as zeros: the BER numerator of every chain from one kernel and one small copy.  Synchronises. */
 int pcamv_gpu_batch_payload_check(pcamv_batch_t *batch, int64_t *diff);
+
+/* ---- Receiver from a stream: CABAC P slices parsed on the device (kernel k_parse_pslice, one wavefront per slice) ----
+ *
+ * What a receiver holds is a stream.  These calls take RBSP bytes (pcamv_gpu_nal_to_rbsp stays the front end; the caller gives the
+ * bit behind the slice header and the slice QP, as for pcamv_gpu_parse_pslice_cabac_at) and parse them where the extractor runs: no
+ * host parse, no upload of records, no synchronisation per frame.  Scope and return codes per slice are the host parser's: frame
+ * macroblocks, one reference, 4x4 transform, cabac_init_idc 0; PCAMV_EUNSUP for an intra macroblock, PCAMV_EINVAL for a slice that
+ * ends in the wrong place, runs out of bytes or has bad alignment bits.  The host parser is the independent check of this one
+ * (tests/test_slice_parse_emu.py, test_slice_parse_fuzz.py, test_gpu_slice_parser.py).  A slice is at most 2^30 bytes.
+ * Contexts opened with b_cabac == 0 are refused with PCAMV_EUNSUP: CAVLC slices keep the host parser.
+ *
+ * parse_pslice_cabac_device: the parity probe.  One slice from host bytes, parsed on the device, the mb_count records copied back;
+ * the picture size is the context's.  Synchronises. */
+int pcamv_gpu_parse_pslice_cabac_device(pcamv_ctx_t *ctx, const uint8_t *rbsp, size_t len, size_t start_bit, int slice_qp, pcamv_mb_t *out_mb);
+/* One slice per context of the batch: staged into one device buffer with one copy on `stream`, parsed by one launch into every
+ * context's receive-side records, then the receiver's kernels as in pcamv_gpu_batch_extract_step (the records hold final motion:
+ * no flip map).  No host synchronisation: the bits are appended at each context's device-side cursor.  Every context needs a
+ * reservation (pcamv_gpu_rx_reserve), else PCAMV_EINVAL.  A slice that fails to parse sets its context's status word on the
+ * device and that context appends NOTHING in this call: cursor and receive-side column generator are untouched. */
+typedef struct pcamv_slice_t { const uint8_t *rbsp; size_t len; size_t start_bit; int32_t slice_qp; } pcamv_slice_t;
+int pcamv_gpu_batch_extract_slices(pcamv_batch_t *batch, const pcamv_slice_t *slices, float emrate, void *stream);
+/* the same on bytes that are on the device already (a torch uint8 tensor, say): slice i is bytes[off[i] .. off[i] + len[i]) of a
+ * borrowed buffer of bytes_size bytes; off / len / start_bit (int64) and slice_qp (int32) are device arrays of one entry per
+ * context, kept alive and unchanged until the work queued on `stream` is done.  Entries that do not fit the buffer fail as
+ * PCAMV_EINVAL slices; nothing outside it is read.
+ * Ordering is the caller's.  The parser is queued on `stream` -- NULL: the first context's own stream, which is non-blocking and
+ * waits for no other stream -- and reads the buffer and the arrays there: whatever produced them must be complete on that
+ * stream's timeline before this call (produced on `stream` itself, `stream` made to wait for the producer's event, or a host
+ * synchronisation), and nothing may rewrite them until the work queued here is done.  The library adds no synchronisation. */
+int pcamv_gpu_batch_extract_slices_device(pcamv_batch_t *batch, const void *bytes, size_t bytes_size, const int64_t *off, const int64_t *len,
+                                          const int64_t *start_bit, const int32_t *slice_qp, float emrate, void *stream);
+/* synchronises; status[i] = return code of context i's slice in the last extract_slices call (0, PCAMV_EINVAL or PCAMV_EUNSUP) */
+int pcamv_gpu_batch_slice_status(pcamv_batch_t *batch, int32_t *status);
+/* Diagnostics for the parity tests: the records the context's last slice parsed to (mb_count of them; synchronises), and whether
+ * the guard region the library keeps behind that buffer still holds its pattern (*guard_intact, optional). */
+int pcamv_gpu_debug_slice_records(pcamv_ctx_t *ctx, pcamv_mb_t *out_mb, int *guard_intact);
 
 #ifdef __cplusplus
 }

@@ -59,6 +59,8 @@ struct ExtractDev {
     long long *pstate;
     unsigned *rx; long long rx_cap_bits;          /* received stream: packed, zeroed when reserved / reset; NULL = nothing is appended */
     const uint8_t *payload; long long payload_bits;
+    int *slice_status;        /* records parsed from a slice on the device (k_parse_pslice): the parser's return code; != 0: the frame
+                               * appends nothing, cursor and column generator stay as they are.  NULL: not from a slice */
 };
 
 __device__ __forceinline__ int dev_is01(int d) { return d == 0 || d == 1; }
@@ -409,6 +411,10 @@ static __global__ void __launch_bounds__(1024) k_extract_prepare(const ExtractDe
     __shared__ int s_cnt[1024];
     __shared__ unsigned s_cols[2 * STC_MAXW];
     const int t = threadIdx.x;
+    if (X.slice_status && *X.slice_status) {            /* (the whole workgroup: no barrier was reached) the slice did not parse: no bits */
+        if (t == 64) { X.hdr[0] = 0; X.hdr[1] = 0; X.hdr[2] = 0; *(long long *)(X.hdr + 6) = X.pstate[PST_RX]; }
+        return;
+    }
     int lo, hi, base, slots[16];
     const int n = dev_carrier_scan<true>(X.mbs, X.n_mb, s_cnt, &lo, &hi, &base);
     for (int xy = lo; xy < hi; xy++) {

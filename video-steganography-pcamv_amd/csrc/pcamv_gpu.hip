@@ -14,6 +14,7 @@
 #include "pcamv_planes.hip.h"
 #include "pcamv_kernels.hip.h"
 #include "pcamv_embed.hip.h"
+#include "pcamv_slice.hip.h"
 #include "pcamv_host_tables.h"
 #include "pcamv_mvsyntax.h"
 #include "pcamv_rd_select.h"
@@ -22,8 +23,10 @@
 #define NEV 32                 /* launches the analysis kernel's timer remembers between two kernel_time calls ... */
 #define NRING 8
 #define NKEV 16                /* ... and a timer of the smaller kernels */
-enum { KT_ANALYSE, KT_EMBED_PREPARE, KT_EXTRACT_PREPARE, KT_EXTRACT_BITS, KT_PAYLOAD_CHECK, KT_N };
-#define PCAMV_FEATURES PCAMV_FEATURE_PAYLOAD
+enum { KT_ANALYSE, KT_EMBED_PREPARE, KT_EXTRACT_PREPARE, KT_EXTRACT_BITS, KT_PAYLOAD_CHECK, KT_PARSE_PSLICE, KT_N };
+#define PCAMV_FEATURES (PCAMV_FEATURE_PAYLOAD | PCAMV_FEATURE_SLICE_PARSER)
+#define SLICE_GUARD_MBS 4       /* records behind a context's receive-side records that nothing may write (pcamv_gpu_debug_slice_records) */
+#define NSTAGE 2                /* staging buffers of extract_slices: a call waits for the one before the last */
 /* the stages of a step (batch_launch's `what`): plane production, analysis (search + RCA + encode), embedding, second pass */
 enum { ST_PLANES = 1, ST_ANALYSE = 2, ST_EMBED = 4, ST_PASS2 = 8 };
 
@@ -75,6 +78,11 @@ struct pcamv_batch {
      * payload_check */
     ExtractDev *h_X, *d_X; long long *d_chk;
     DescRing xring;
+    /* receiver from a stream (k_parse_pslice): per-context status words, the tables, the row buffers of pictures too wide for LDS, and
+     * the staging of host slices -- descriptor arrays then bytes in one block, pinned host and device, NSTAGE of them in turn */
+    int *d_sstat; uint8_t *d_sp_tab, *d_sp_scratch;
+    int sp_lds_cols;            /* pictures up to this many macroblocks wide keep the parser's row buffer in LDS (SP_LDS_COLS; PCAMV_SLICE_LDS_COLS lowers it) */
+    uint8_t *h_stage[NSTAGE], *d_stage[NSTAGE]; size_t stage_cap[NSTAGE]; hipEvent_t stage_done[NSTAGE]; int stage_used[NSTAGE], stage_head;
     KTimer kt[KT_N];            /* the timed kernels; the events of a timer are made by its first launch */
     char err[256];
 };
@@ -226,6 +234,8 @@ extern "C" void pcamv_gpu_batch_destroy(pcamv_batch_t *b)
     if (b->h_E) hipHostFree(b->h_E);
     if (b->h_X) hipHostFree(b->h_X);
     hipFree(b->d_F); hipFree(b->d_E); hipFree(b->d_flow); hipFree(b->d_X); hipFree(b->d_chk);
+    hipFree(b->d_sstat); hipFree(b->d_sp_tab); hipFree(b->d_sp_scratch);
+    for (int k = 0; k < NSTAGE; k++) { if (b->h_stage[k]) hipHostFree(b->h_stage[k]); hipFree(b->d_stage[k]); if (b->stage_done[k]) hipEventDestroy(b->stage_done[k]); }
     ring_destroy(b->ring); ring_destroy(b->xring);
     for (KTimer &T : b->kt) kt_destroy(T);
     free(b->ctx);
@@ -278,6 +288,7 @@ extern "C" int pcamv_gpu_batch_create(pcamv_ctx_t *const *ctxs, int n, pcamv_bat
      * the default is the dataflow kernel.  Both are the same per-macroblock code. */
     b->sched_flow = !env_is("PCAMV_SCHED", "diag") && F.n_mb <= 65535 && n <= 65535;
     { const int ns = env_int("PCAMV_STC_STATES", 2, 4, 0); b->stc_ns = ns == 2 || ns == 4 ? ns : (n >= 1024 ? 4 : 2); }      /* trellis states per thread of the forward Viterbi */
+    b->sp_lds_cols = env_int("PCAMV_SLICE_LDS_COLS", 0, SP_LDS_COLS, SP_LDS_COLS);      /* (tests: 0 sends every picture through the global scratch rows) */
     for (int k = 0; k < KT_N; k++) { b->kt[k].cap = k == KT_ANALYSE ? NEV : NKEV; b->kt[k].weight = 1; }
     if (!b->sched_flow) b->kt[KT_ANALYSE].weight = b->n_diag;
     hipError_t e = hipSetDevice(b->device);
@@ -366,7 +377,7 @@ static const char *dominant_kernel(const pcamv_batch *b)
 extern "C" const char *pcamv_gpu_batch_dominant_kernel(const pcamv_batch_t *b) { return dominant_kernel(b); }
 static const char *kt_name(const pcamv_batch *b, int k)      /* what pcamv_gpu_batch_kernel_time knows timer k by */
 {
-    static const char *const small[KT_N] = {NULL, "k_embed_prepare", "k_extract_prepare", "k_extract_bits", "k_payload_check"};
+    static const char *const small[KT_N] = {NULL, "k_embed_prepare", "k_extract_prepare", "k_extract_bits", "k_payload_check", "k_parse_pslice"};
     return k == KT_ANALYSE ? dominant_kernel(b) : small[k];
 }
 extern "C" int pcamv_gpu_batch_copy_results_async(pcamv_batch_t *b, void *dst_mb, size_t mb_stride, void *dst_flip, size_t flip_stride, void *stream)
@@ -971,6 +982,14 @@ static int rx_scratch(pcamv_ctx *c)
     TRY(ctx_alloc(c, &c->X.hdr, 8, 0)); TRY(ctx_alloc(c, &c->X.cols, 2 * STC_MAXW));
     return 0;
 }
+/* the records of the receiving side that do not come from an analysis (host records, parsed slices), with a guard behind them */
+static int rx_mbs(pcamv_ctx *c)
+{
+    if (c->d_rx_mbs) return 0;
+    TRY(ctx_alloc(c, &c->d_rx_mbs, (size_t)c->F.n_mb + SLICE_GUARD_MBS));
+    HIPCHK(c, hipMemset(c->d_rx_mbs + c->F.n_mb, 0xA5, SLICE_GUARD_MBS * sizeof(pcamv_mb_t)));
+    return 0;
+}
 extern "C" int pcamv_gpu_rx_reset(pcamv_ctx_t *c)
 {
     if (!c) return PCAMV_EINVAL;
@@ -1057,7 +1076,7 @@ extern "C" int pcamv_gpu_batch_extract_step(pcamv_batch_t *b, float emrate, void
     for (int i = 0; i < b->n; i++) {
         pcamv_ctx *c = b->ctx[i];
         if (!c->d_rx) return fail(b, PCAMV_EINVAL, "context %d has no received buffer (pcamv_gpu_rx_reserve)", i);
-        c->X.mbs = c->F.rec_mb; c->X.flip = c->d_flip; c->X.bits = NULL; c->X.emrate = emrate;
+        c->X.mbs = c->F.rec_mb; c->X.flip = c->d_flip; c->X.bits = NULL; c->X.emrate = emrate; c->X.slice_status = NULL;
     }
     hipStream_t st = stream ? (hipStream_t)stream : b->ctx[0]->stream;
     const ExtractDev *dX; int slot;
@@ -1075,10 +1094,10 @@ extern "C" int pcamv_gpu_extract_pframe(pcamv_ctx_t *c, const pcamv_mb_t *mbs, f
     if (!c || !mbs || emrate <= 0) return PCAMV_EINVAL;
     HIPCHK(c, hipSetDevice(c->device));
     TRY(rx_scratch(c));
-    if (!c->d_rx_mbs) TRY(ctx_alloc(c, &c->d_rx_mbs, (size_t)c->F.n_mb));
+    TRY(rx_mbs(c));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(c->d_rx_mbs, mbs, (size_t)c->F.n_mb * sizeof(pcamv_mb_t), hipMemcpyHostToDevice));
-    c->X.mbs = c->d_rx_mbs; c->X.flip = NULL; c->X.bits = c->d_rx_bits; c->X.emrate = emrate;
+    c->X.mbs = c->d_rx_mbs; c->X.flip = NULL; c->X.bits = c->d_rx_bits; c->X.emrate = emrate; c->X.slice_status = NULL;
     pcamv_batch *b = c->self;
     const ExtractDev *dX; int slot;
     TRY(on_behalf(c, b, batch_push_xdescs(b, c->stream, &dX, &slot)));
@@ -1095,6 +1114,175 @@ extern "C" int pcamv_gpu_extract_pframe(pcamv_ctx_t *c, const pcamv_mb_t *mbs, f
     const int m_copy = hdr[1] < c->cap ? hdr[1] : c->cap;
     if (bits_out && m_copy) HIPCHK(c, hipMemcpy(bits_out, c->d_rx_bits, (size_t)m_copy, hipMemcpyDeviceToHost));
     return rx_check(c, NULL);
+}
+/* ------------------------------------------------------------------ receiver from a stream (k_parse_pslice, pcamv_slice.hip.h) */
+/* what every launch of the parser needs of the batch: status words, the tables, scratch rows for pictures too wide for LDS */
+static int slice_setup(pcamv_batch *b)
+{
+    const FrameDev &F = b->ctx[0]->F;
+    if (!b->d_sstat) HIPCHK(b, dalloc(&b->d_sstat, (size_t)b->n));
+    if (!b->d_sp_tab) {
+        uint8_t tab[SP_TAB_BYTES];
+        memcpy(tab + SP_TAB_INIT, pcamv_cabac_init_p, 2 * SP_NCTX); memcpy(tab + SP_TAB_TRANS, pcamv_cabac_transition, 256);
+        memcpy(tab + SP_TAB_RLPS, pcamv_cabac_range_lps, 512);
+        HIPCHK(b, dalloc(&b->d_sp_tab, (size_t)SP_TAB_BYTES));
+        HIPCHK(b, hipMemcpy(b->d_sp_tab, tab, sizeof(tab), hipMemcpyHostToDevice));
+    }
+    if (F.mb_w > b->sp_lds_cols && !b->d_sp_scratch) HIPCHK(b, dalloc(&b->d_sp_scratch, (size_t)b->n * SP_ROW_BYTES * F.mb_w));
+    return 0;
+}
+/* the contexts can take parsed slices: CABAC, and (want_rx) a reservation each; their descriptors then point at the receive-side records */
+static int slice_contexts(pcamv_batch *b, int want_rx, float emrate)
+{
+    for (int i = 0; i < b->n; i++) {
+        pcamv_ctx *c = b->ctx[i];
+        if (!c->F.b_cabac) return fail(b, PCAMV_EUNSUP, "context %d was opened with --no-cabac: CAVLC slices keep the host parser (pcamv_gpu_parse_pslice_cavlc*)", i);
+        if (want_rx && !c->d_rx) return fail(b, PCAMV_EINVAL, "context %d has no received buffer (pcamv_gpu_rx_reserve)", i);
+    }
+    for (int i = 0; i < b->n; i++) {
+        pcamv_ctx *c = b->ctx[i];
+        TRY(rx_scratch(c)); TRY(rx_mbs(c));
+        c->X.mbs = c->d_rx_mbs; c->X.flip = NULL; c->X.bits = NULL; c->X.emrate = emrate; c->X.slice_status = b->d_sstat + i;
+    }
+    return 0;
+}
+static void slice_launch(pcamv_batch *b, const ExtractDev *dX, SliceJobs J, hipStream_t st)
+{
+    const FrameDev &F = b->ctx[0]->F;
+    J.tab = b->d_sp_tab; J.scratch = b->d_sp_scratch; J.scratch_stride = (long long)SP_ROW_BYTES * F.mb_w; J.mb_w = F.mb_w; J.mb_h = F.mb_h; J.lds_cols = b->sp_lds_cols;
+    const int ev = kt_begin(b, KT_PARSE_PSLICE, st);
+    hipLaunchKernelGGL(k_parse_pslice, dim3(b->n), dim3(64), 0, st, dX, J);
+    kt_end(b, KT_PARSE_PSLICE, ev, st);
+}
+/* parse (slices described by J, one per context) and, with extract != 0, the receiver's kernels behind it, all on `st` */
+static int slices_run(pcamv_batch *b, SliceJobs J, int extract, float emrate, hipStream_t st)
+{
+    const ExtractDev *dX; int slot;
+    TRY(batch_push_xdescs(b, st, &dX, &slot));
+    slice_launch(b, dX, J, st);
+    if (extract) extract_launch(b, dX, b->n, b->ctx[0]->cap, emrate, st);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(b, PCAMV_EHIP, "kernel launch: %s", hipGetErrorString(e));
+    return ring_release(b, b->xring, slot, st);
+}
+/* host slices into the next staging buffer: [off n][len n][start_bit n] int64, [qp n] int32, then the bytes, every slice at a multiple
+ * of 4; one copy on `st`.  *stage_out: the buffer's index, to be released (stage_release) once the kernels that read it are queued */
+static int slices_stage(pcamv_batch *b, const pcamv_slice_t *sl, hipStream_t st, SliceJobs *J, int *stage_out)
+{
+    const size_t n = (size_t)b->n, hdr = (n * (3 * 8 + 4) + 15) & ~(size_t)15;
+    size_t total = hdr;
+    for (size_t i = 0; i < n; i++) {
+        if (!sl[i].rbsp || sl[i].len > (size_t)SP_MAX_LEN) return fail(b, PCAMV_EINVAL, "slice %d: no bytes, or more than 2^30 of them", (int)i);
+        if (sl[i].start_bit > ((size_t)1 << 40)) return fail(b, PCAMV_EINVAL, "slice %d: start bit %zu is beyond any slice", (int)i, sl[i].start_bit);
+        total += (sl[i].len + 3) & ~(size_t)3;
+    }
+    const int k = b->stage_head;
+    b->stage_head = (k + 1) % NSTAGE;
+    if (!b->stage_done[k]) HIPCHK(b, hipEventCreateWithFlags(&b->stage_done[k], hipEventDisableTiming));
+    if (b->stage_used[k]) HIPCHK(b, hipEventSynchronize(b->stage_done[k]));
+    if (total > b->stage_cap[k]) {
+        if (b->h_stage[k]) hipHostFree(b->h_stage[k]);
+        hipFree(b->d_stage[k]); b->h_stage[k] = NULL; b->d_stage[k] = NULL; b->stage_cap[k] = 0;
+        const size_t cap = total + total / 4;
+        HIPCHK(b, hipHostMalloc((void **)&b->h_stage[k], cap, hipHostMallocDefault));
+        HIPCHK(b, dalloc(&b->d_stage[k], cap));
+        b->stage_cap[k] = cap;
+    }
+    uint8_t *h = b->h_stage[k];
+    long long *off = (long long *)h, *len = off + n, *start = len + n; int *qp = (int *)(start + n);
+    size_t at = 0;
+    for (size_t i = 0; i < n; i++) {
+        off[i] = (long long)at; len[i] = (long long)sl[i].len; start[i] = (long long)sl[i].start_bit; qp[i] = sl[i].slice_qp;
+        memcpy(h + hdr + at, sl[i].rbsp, sl[i].len);
+        at += (sl[i].len + 3) & ~(size_t)3;
+    }
+    HIPCHK(b, hipMemcpyAsync(b->d_stage[k], h, total, hipMemcpyHostToDevice, st));
+    /* from here on the buffer is in flight whatever happens to the kernels: the event stands for the copy until stage_release moves it
+     * behind the kernels that read the device side */
+    HIPCHK(b, hipEventRecord(b->stage_done[k], st));
+    b->stage_used[k] = 1;
+    const uint8_t *d = b->d_stage[k];
+    J->bytes = d + hdr; J->bytes_size = (long long)(total - hdr);
+    J->off = (const long long *)d; J->len = J->off + n; J->start_bit = J->len + n; J->qp = (const int *)(J->start_bit + n);
+    *stage_out = k;
+    return 0;
+}
+static int stage_release(pcamv_batch *b, int k, hipStream_t st)
+{
+    HIPCHK(b, hipEventRecord(b->stage_done[k], st));
+    b->stage_used[k] = 1;
+    return 0;
+}
+static int slices_checked(pcamv_batch *b, float emrate, int want_rx)
+{
+    if (!b || emrate <= 0) return PCAMV_EINVAL;
+    HIPCHK(b, hipSetDevice(b->device));
+    TRY(batch_live(b));
+    TRY(slice_setup(b));
+    return slice_contexts(b, want_rx, emrate);
+}
+extern "C" int pcamv_gpu_batch_extract_slices(pcamv_batch_t *b, const pcamv_slice_t *slices, float emrate, void *stream)
+{
+    if (!slices) return PCAMV_EINVAL;
+    TRY(slices_checked(b, emrate, 1));
+    hipStream_t st = stream ? (hipStream_t)stream : b->ctx[0]->stream;
+    SliceJobs J; int k;
+    TRY(slices_stage(b, slices, st, &J, &k));
+    const int rc = slices_run(b, J, 1, emrate, st), rc2 = stage_release(b, k, st);      /* released on every path */
+    return rc ? rc : rc2;
+}
+extern "C" int pcamv_gpu_batch_extract_slices_device(pcamv_batch_t *b, const void *bytes, size_t bytes_size, const int64_t *off, const int64_t *len,
+                                                     const int64_t *start_bit, const int32_t *slice_qp, float emrate, void *stream)
+{
+    if (!bytes || !off || !len || !start_bit || !slice_qp || bytes_size > ((size_t)1 << 62)) return PCAMV_EINVAL;
+    TRY(slices_checked(b, emrate, 1));
+    static_assert(sizeof(long long) == sizeof(int64_t), "the caller's int64 arrays are read as they are");
+    SliceJobs J;
+    J.bytes = (const uint8_t *)bytes; J.bytes_size = (long long)bytes_size;
+    J.off = (const long long *)off; J.len = (const long long *)len; J.start_bit = (const long long *)start_bit; J.qp = slice_qp;
+    return slices_run(b, J, 1, emrate, stream ? (hipStream_t)stream : b->ctx[0]->stream);
+}
+extern "C" int pcamv_gpu_batch_slice_status(pcamv_batch_t *b, int32_t *status)
+{
+    if (!b || !status) return PCAMV_EINVAL;
+    HIPCHK(b, hipSetDevice(b->device));
+    if (!b->d_sstat) return fail(b, PCAMV_EINVAL, "no slices were handed to this batch yet");
+    HIPCHK(b, hipDeviceSynchronize());
+    HIPCHK(b, hipMemcpy(status, b->d_sstat, sizeof(int32_t) * b->n, hipMemcpyDeviceToHost));
+    return 0;
+}
+/* the parity probe: one slice from host bytes through k_parse_pslice, its records back */
+extern "C" int pcamv_gpu_parse_pslice_cabac_device(pcamv_ctx_t *c, const uint8_t *rbsp, size_t len, size_t start_bit, int slice_qp, pcamv_mb_t *out_mb)
+{
+    if (!c || !rbsp || !out_mb) return PCAMV_EINVAL;
+    pcamv_batch *b = c->self;
+    TRY(on_behalf(c, b, slices_checked(b, 1.0f, 0)));
+    const pcamv_slice_t sl = {rbsp, len, start_bit, slice_qp};
+    SliceJobs J; int k, rc = 0;
+    TRY(on_behalf(c, b, slices_stage(b, &sl, c->stream, &J, &k)));
+    rc = slices_run(b, J, 0, 1.0f, c->stream);
+    const int rc2 = stage_release(b, k, c->stream);                                     /* released on every path */
+    TRY(on_behalf(c, b, rc ? rc : rc2));
+    rc = 0;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(&rc, b->d_sstat, sizeof(rc), hipMemcpyDeviceToHost));
+    if (rc) return fail(c, rc, rc == PCAMV_EUNSUP ? "the slice holds an intra macroblock" : "the slice does not parse (ends in the wrong place, runs out of bytes, or bad alignment bits)");
+    HIPCHK(c, hipMemcpy(out_mb, c->d_rx_mbs, (size_t)c->F.n_mb * sizeof(pcamv_mb_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+extern "C" int pcamv_gpu_debug_slice_records(pcamv_ctx_t *c, pcamv_mb_t *out_mb, int *guard_intact)
+{
+    if (!c || !out_mb || !c->d_rx_mbs) return PCAMV_EINVAL;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipDeviceSynchronize());
+    HIPCHK(c, hipMemcpy(out_mb, c->d_rx_mbs, (size_t)c->F.n_mb * sizeof(pcamv_mb_t), hipMemcpyDeviceToHost));
+    if (guard_intact) {
+        uint8_t g[SLICE_GUARD_MBS * sizeof(pcamv_mb_t)];
+        HIPCHK(c, hipMemcpy(g, c->d_rx_mbs + c->F.n_mb, sizeof(g), hipMemcpyDeviceToHost));
+        *guard_intact = 1;
+        for (size_t i = 0; i < sizeof(g); i++) if (g[i] != 0xA5) *guard_intact = 0;
+    }
+    return 0;
 }
 /* diff[i] = bits in which context i's received stream differs from its attached payload (payload bits past its end are zeros): the
  * BER numerator of every chain, one kernel over the batch and one copy.  Synchronises. */

@@ -251,6 +251,7 @@ def stc_extract(stego, m, height=10, lcg=None):
 
 
 FEATURE_PAYLOAD = 0x1
+FEATURE_SLICE_PARSER = 0x2      # CABAC P slices parsed on the device: Encoder.parse_pslice_device, Batch.extract_slices
 
 
 def features():
@@ -430,6 +431,22 @@ class Encoder:
         self._chk(self.lib.pcamv_gpu_extract_pframe(self.ctx, _p(mbs), emrate, _p(bits), C.byref(n), C.byref(m)), "extract_pframe")
         return dict(bits=bits[:min(m.value, len(bits))].copy(), n=n.value, m=m.value)
 
+    def parse_pslice_device(self, rbsp, hdr_bits, qp):
+        """pcamv_gpu_parse_pslice_cabac_device: the records of one CABAC P slice (RBSP bytes, slice data behind bit hdr_bits, slice
+        QP) parsed on the device by k_parse_pslice -- the parity probe of Batch.extract_slices; raises like parse_pslice_at"""
+        data = np.frombuffer(bytes(rbsp), np.uint8)
+        mbs = np.zeros(self.n_mb, MB_DTYPE)
+        self.lib.pcamv_gpu_parse_pslice_cabac_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p]
+        self._chk(self.lib.pcamv_gpu_parse_pslice_cabac_device(self.ctx, _p(data), len(data), hdr_bits, qp, _p(mbs)), "parse_pslice_cabac_device")
+        return mbs
+
+    def slice_records(self):
+        """diagnostics: (the records this context's last slice parsed to on the device, whether the guard behind them is intact)"""
+        mbs = np.zeros(self.n_mb, MB_DTYPE)
+        ok = C.c_int()
+        self._chk(self.lib.pcamv_gpu_debug_slice_records(self.ctx, _p(mbs), C.byref(ok)), "debug_slice_records")
+        return mbs, bool(ok.value)
+
     def final_mvs(self, mbs):
         out = mbs.copy()
         self._chk(self.lib.pcamv_gpu_final_mvs(self.ctx, _p(out)), "final_mvs")
@@ -561,6 +578,45 @@ class Batch:
         rc = self.lib.pcamv_gpu_batch_extract_step(self.b, C.c_float(emrate), C.c_void_p(stream or None))
         if rc:
             raise PcamvError(f"batch_extract_step failed ({rc}): {self.lib.pcamv_gpu_batch_last_error(self.b).decode()}")
+
+    def _slice_chk(self, rc, what):
+        if rc:
+            names = {-1: "invalid argument", -5: "unsupported"}
+            raise PcamvError(f"{what} failed ({names.get(rc, rc)}): {self.lib.pcamv_gpu_batch_last_error(self.b).decode()}")
+
+    def extract_slices(self, slices, emrate, stream=0):
+        """one CABAC P slice per context, a list of (rbsp bytes, hdr_bits, qp): staged with one copy, parsed on the device
+        (k_parse_pslice, one wavefront per slice) and sent through the receiver, without a host sync.  Every context needs
+        rx_reserve; a slice that does not parse appends nothing for its context (slice_status)"""
+        if len(slices) != len(self.encs):
+            raise PcamvError(f"{len(slices)} slices for a batch of {len(self.encs)} contexts")
+        class _Slice(C.Structure):
+            _fields_ = [("rbsp", C.c_void_p), ("len", C.c_size_t), ("start_bit", C.c_size_t), ("slice_qp", C.c_int32)]
+        keep = [np.frombuffer(bytes(s[0]), np.uint8) if len(s[0]) else np.zeros(1, np.uint8) for s in slices]
+        arr = (_Slice * len(slices))(*[_Slice(k.ctypes.data, len(s[0]), int(s[1]), int(s[2])) for k, s in zip(keep, slices)])
+        self.lib.pcamv_gpu_batch_extract_slices.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
+        self._slice_chk(self.lib.pcamv_gpu_batch_extract_slices(self.b, arr, emrate, C.c_void_p(stream or None)), "batch_extract_slices")
+
+    def extract_slices_device(self, data, off, length, hdr_bits, qp, emrate, stream=0):
+        """the same on bytes already on the device: `data` a contiguous uint8 device tensor (borrowed, no copy), off / length /
+        hdr_bits int64 and qp int32 device tensors of one entry per context; the caller keeps them alive until the work is done.
+        Ordering is the caller's: the work is queued on `stream` (0: the first context's own non-blocking stream, which waits for
+        no other stream), so the tensors must be complete before the call -- produced on `stream`, or that stream made to wait
+        for their producer (an event), or torch.cuda.synchronize() -- and must not be rewritten before the queued work is done"""
+        for t, size, what in ((data, 1, "data: uint8"), (off, 8, "off: int64"), (length, 8, "length: int64"), (hdr_bits, 8, "hdr_bits: int64"), (qp, 4, "qp: int32")):
+            if not _is_device_tensor(t) or not t.is_cuda or t.element_size() != size or not t.is_contiguous():
+                raise PcamvError(f"{what}, contiguous, on the device")
+        if any(t.numel() != len(self.encs) for t in (off, length, hdr_bits, qp)):
+            raise PcamvError(f"one entry per context ({len(self.encs)}) in off / length / hdr_bits / qp")
+        self.lib.pcamv_gpu_batch_extract_slices_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
+        self._slice_chk(self.lib.pcamv_gpu_batch_extract_slices_device(self.b, data.data_ptr(), data.numel(), off.data_ptr(), length.data_ptr(), hdr_bits.data_ptr(),
+                                                                       qp.data_ptr(), emrate, C.c_void_p(stream or None)), "batch_extract_slices_device")
+
+    def slice_status(self):
+        """per context: the parser's code for its slice of the last extract_slices call (0, -1 invalid, -5 unsupported); synchronises"""
+        out = np.zeros(len(self.encs), np.int32)
+        self._slice_chk(self.lib.pcamv_gpu_batch_slice_status(self.b, _p(out)), "batch_slice_status")
+        return out
 
     def payload_check(self):
         """per context: bits in which its received stream differs from its attached payload (zeros past the payload's end)"""
