@@ -70,7 +70,7 @@ typedef struct pcamv_params_t {
     int32_t i_me_range;               /* analyse.i_me_range   (default 16, common.c:121); <= 16 with PCAMV_ME_TESA */
     int32_t i_subpel_refine;          /* analyse.i_subpel_refine, 1..7 (6 and 7 are the same for P frames: RD mode decision, incl.
                                          x264_rd_cost_part for sub-8x8 partitions); 8 / 9 (RD refinement of MVs: off in the fork's P frames) PCAMV_EUNSUP */
-    int32_t i_mv_range;               /* analyse.i_mv_range after level lookup, encoder.c:558    */
+    int32_t i_mv_range;               /* analyse.i_mv_range after level lookup, encoder.c:558; >= 16 */
     int32_t b_chroma_me;              /* analyse.b_chroma_me  (default 1)                        */
     int32_t b_fast_pskip;             /* analyse.b_fast_pskip (default 1)                        */
     int32_t b_dct_decimate;           /* analyse.b_dct_decimate (default 1)                      */

@@ -17,6 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(ROOT, "video-steganography-pcamv_amd"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 import refh  # noqa: E402
 import orc  # noqa: E402  (only for level_mv_range / block tables, no oracle compute)
 from pcamv_amd.synth import make_clip  # noqa: E402
@@ -39,9 +40,13 @@ def mv_field(mbs, mbw, mbh):
     return mvf, np.zeros((mbh * 2, mbw * 2), np.int8)
 
 
-def analysis_fixture(name, W, H, me, subme, qp, inter, seed, static_cols, me_range=16, noise=6, frames=2, cabac=1, psy_rd=1.0, embed=1):
-    clip = make_clip(W, H, frames + 1, seed=seed, static_cols=static_cols, noise=noise)
-    mvr = orc.level_mv_range(W, H)
+def analysis_fixture(name, W, H, me, subme, qp, inter, seed, static_cols, me_range=16, noise=6, frames=2, cabac=1, psy_rd=1.0, embed=1,
+                     clip=None, mv_range=None):
+    """clip: frames + 1 pictures (Y, U, V) to use instead of the synthetic clip (seed / static_cols / noise then mean nothing);
+    mv_range: an explicit --mvrange instead of the level's"""
+    if clip is None:
+        clip = make_clip(W, H, frames + 1, seed=seed, static_cols=static_cols, noise=noise)
+    mvr = orc.level_mv_range(W, H) if mv_range is None else mv_range
     r = refh.Ref(W, H, qp=qp, me=me, subme=subme, mv_range=mvr, embed=embed, inter_flags=inter | 0x1 | 0x100, me_range=me_range,
                  cabac=cabac, psy_rd=psy_rd)
     hashes = r.debug_state_hash() if subme >= 6 and cabac else None
@@ -251,6 +256,13 @@ if __name__ == "__main__":
         pslice_fixture("pslice_cavlc_cif_umh_subme7_final", 352, 288, "umh", 7, 26, 0x1 | 0x100, 6, 96, final=True, cabac=0)
         pslice_fixture("pslice_cavlc_cif_hex_subme5_p4x4_qp10", 352, 288, "hex", 5, 10, 0x31, 22, 160, noise=40, cabac=0)
         pslice_fixture("pslice_cavlc_qcif_hex_subme6_qp34", 176, 144, "hex", 6, 34, 0x11, 9, 0, noise=30, cabac=0)
+        sys.exit(0)
+    if "--hostile-only" in sys.argv:           # tests/hostile_cases.py: saturated pixels, motion out of reach, cuts, MVs on the clip limits; QP 0 and 51
+        import hostile_cases as hc
+        analysis_fixture("hostile_sat_umh_subme7_qp0", 176, 144, "umh", 7, 0, 0x10, 0, 0, clip=hc.sat())
+        analysis_fixture("hostile_fastpan_hex_subme5_qp51", 176, 144, "hex", 5, 51, 0x10, 0, 0, clip=hc.fastpan())
+        analysis_fixture("hostile_cut_hex_subme6_cavlc_psub8_qp0", 176, 144, "hex", 6, 0, 0x30, 0, 0, cabac=0, clip=hc.cut())
+        analysis_fixture("hostile_limit_umh_subme7_qp26_mvr16", 176, 144, "umh", 7, 26, 0x10, 0, 0, clip=hc.limit(16), mv_range=16)
         sys.exit(0)
     if "--rd-psub8-only" in sys.argv:          # x264_rd_cost_part: sub-8x8 partitions at --subme 6 / 7 (round 3)
         analysis_fixture("qcif_hex_subme6_psub8", 176, 144, "hex", 6, 26, 0x30, 61, 0, noise=30)

@@ -11,6 +11,9 @@ ANALYSIS_FIXTURES = ["qcif_hex_subme5", "qcif_dia_subme2", "qcif_umh_subme4_psub
 RD_FIXTURES = ["qcif_hex_subme6", "qcif_umh_subme7_cavlc", "qcif_dia_subme6_nopsy_noisy", "qcif_esa_subme6_noembed", "cif_umh_subme7",
                # sub-8x8 partitions priced by x264_rd_cost_part (rdo.c:202-245)
                "qcif_hex_subme6_psub8", "qcif_hex_subme7_psub8_cavlc", "qcif_umh_subme6_psub8", "qcif_tesa_subme6"]
+# tests/hostile_cases.py's pictures (saturated pixels, motion out of reach, cuts, MVs on the clip limit of an explicit --mvrange) at QP 0 / 51
+HOSTILE_ANALYSIS_FIXTURES = ["hostile_fastpan_hex_subme5_qp51"]
+HOSTILE_RD_FIXTURES = ["hostile_sat_umh_subme7_qp0", "hostile_cut_hex_subme6_cavlc_psub8_qp0", "hostile_limit_umh_subme7_qp26_mvr16"]
 
 
 def fixture_params(g, make_params, **over):

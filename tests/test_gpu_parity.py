@@ -45,7 +45,7 @@ def _fixture_params(pc, g):
 GPU_FIXTURES = ["qcif_hex_subme5", "qcif_dia_subme2", "qcif_umh_subme4_psub8", "qcif_esa_subme3", "qcif_tesa_subme5_psub8", "qcif_hex_noisy_partitions", "cif_umh_subme5"]
 
 
-@pytest.mark.parametrize("name", GPU_FIXTURES + helpers.RD_FIXTURES)
+@pytest.mark.parametrize("name", GPU_FIXTURES + helpers.RD_FIXTURES + helpers.HOSTILE_ANALYSIS_FIXTURES + helpers.HOSTILE_RD_FIXTURES)
 def test_pframe_analysis_matches_reference_fixture(pc, name):
     """every field of the pass-1 record, the reconstruction and the half-pel planes against what the reference's own code
     computed; for --subme 6 / 7 with CABAC also the context states after every macroblock"""
@@ -620,7 +620,7 @@ def test_pass2_and_loop_filter_match_oracle(pc, cfg):
     enc.close(); o.close(); o2.close()
 
 
-def _closed_loop_vs_oracle(pc, W, H, me, subme, qp, n_gops, steps, seed0, emrate=0.5, statics=(0, 64, 128), noise=6, hashes=False, inter=0x10):
+def _closed_loop_vs_oracle(pc, W, H, me, subme, qp, n_gops, steps, seed0, emrate=0.5, statics=(0, 64, 128), noise=6, hashes=False, inter=0x10, clips=None):
     """GOPs advanced together through closed-loop steps (dataflow analysis, embedding, then pass 2 + loop filter through the same
     dataflow queue; every later step's reference is the step's own deblocked picture and final motion field, both taken from the
     device): records, embedding vectors, deblocked pictures vs the oracle, and the payload back out of the final motion vectors
@@ -628,7 +628,8 @@ def _closed_loop_vs_oracle(pc, W, H, me, subme, qp, n_gops, steps, seed0, emrate
     import torch
     import orc
     from pcamv_amd.synth import make_clip
-    clips = [make_clip(W, H, steps + 1, seed=seed0 + g, static_cols=statics[g % len(statics)], noise=noise) for g in range(n_gops)]
+    if clips is None:       # (clips: one list of steps + 1 pictures per GOP to use instead of the synthetic ones)
+        clips = [make_clip(W, H, steps + 1, seed=seed0 + g, static_cols=statics[g % len(statics)], noise=noise) for g in range(n_gops)]
     orc.lib().orc_stc_lcg_reset(1)          # fresh contexts: the column generator's initial state on both sides (it is process-wide in the oracle)
     dev = torch.device("cuda", 0)
     d = [[[torch.from_numpy(np.ascontiguousarray(pl)).to(dev) for pl in fr] for fr in clip] for clip in clips]

@@ -14,7 +14,7 @@ FIX = ["qcif_hex_subme5", "qcif_dia_subme2", "qcif_umh_subme4_psub8", "qcif_esa_
 
 
 @pytest.mark.parametrize("order", [1, 2], ids=["diagonal_phases", "dataflow_fused"])
-@pytest.mark.parametrize("name", FIX)
+@pytest.mark.parametrize("name", FIX + helpers.HOSTILE_ANALYSIS_FIXTURES)
 def test_control_logic_matches_reference(name, order):
     g = helpers.load(name)
     W, H = int(g["width"]), int(g["height"])
@@ -35,7 +35,7 @@ def test_control_logic_matches_reference(name, order):
 # --subme 6 / 7: the RD mode decision in the shared control code.  With CABAC the context states chain the macroblocks of a
 # frame in raster order (order 3: raster, fused); CAVLC sizes depend on the left / top neighbours only, so the dataflow
 # schedule's orders apply as well.
-RD = [(n, o) for n in helpers.RD_FIXTURES for o in ((3,) if "cavlc" not in n else (1, 2, 3))]
+RD = [(n, o) for n in helpers.RD_FIXTURES + helpers.HOSTILE_RD_FIXTURES for o in ((3,) if "cavlc" not in n else (1, 2, 3))]
 
 
 @pytest.mark.parametrize("name,order", RD, ids=[f"{n}-order{o}" for n, o in RD])

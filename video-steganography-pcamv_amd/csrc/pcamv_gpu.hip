@@ -408,7 +408,9 @@ extern "C" int pcamv_gpu_open(const pcamv_params_t *p, int device, pcamv_ctx_t *
     if (p->i_subpel_refine < 1 || p->i_subpel_refine > 7) return PCAMV_EUNSUP;   /* 8, 9: RD refinement of the MVs (disabled in the fork's P frames anyway, analyse.c:3112) */
     if (p->i_me_method < PCAMV_ME_DIA || p->i_me_method > PCAMV_ME_TESA) return PCAMV_EUNSUP;
     if (p->i_me_method == PCAMV_ME_TESA && p->i_me_range > TESA_MAX_RANGE) return PCAMV_EUNSUP;      /* the survivor list lives in LDS: 32 x 33 positions */
-    if (p->i_me_range < 4 || p->i_me_range > 64 || p->i_mv_range < 32) return PCAMV_EINVAL;
+    /* x264_validate_parameters leaves 32 .. 512 here (encoder.c:561), but the analysis is defined for smaller ranges as well (the clip bounds of
+     * analyse.c:271-317 only move inwards) and the parity tests drive it at 16, where the bounds are easiest to reach: refused below that */
+    if (p->i_me_range < 4 || p->i_me_range > 64 || p->i_mv_range < 16) return PCAMV_EINVAL;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return PCAMV_ENODEV;
     pcamv_ctx *c = new (std::nothrow) pcamv_ctx();
@@ -1366,8 +1368,13 @@ extern "C" int pcamv_gpu_block_costs(pcamv_ctx_t *c, int qp, int n, const int32_
     for (int i = 0; i < n; i++) {
         const int32_t *r = req + 8 * i;
         if (r[0] < 0 || r[0] >= c->F.mb_w || r[1] < 0 || r[1] >= c->F.mb_h || r[2] < 0 || r[2] > 6) return fail(c, PCAMV_EINVAL, "request %d", i);
-        int px = r[0] * 16 + r[3] + (r[5] >> 2), py = r[1] * 16 + r[4] + (r[6] >> 2);    /* stay inside the 32-pixel padding */
-        if (px < -28 || py < -28 || px + 20 > c->F.w + 28 || py + 20 > c->F.h + 28) return fail(c, PCAMV_EINVAL, "request %d leaves the padded plane", i);
+        /* stay inside the 32-pixel padding: the BLOCK (not a 16x16 at its origin) within 24 pixels of the picture, which is as far as the
+         * analysis' own MVs take any partition (mv_min / mv_max, pcamv_logic.h); the fetches read one column and two rows more, batch mode
+         * one pixel more, and the chroma rows 8 bytes from the block's first sample: all inside the 32 (chroma 16) */
+        static const int bw[7] = {16, 16, 8, 8, 8, 4, 4}, bh[7] = {16, 8, 16, 8, 4, 8, 4};
+        int px = r[0] * 16 + r[3] + (r[5] >> 2), py = r[1] * 16 + r[4] + (r[6] >> 2);
+        if (r[3] < 0 || r[4] < 0 || r[3] + bw[r[2]] > 16 || r[4] + bh[r[2]] > 16) return fail(c, PCAMV_EINVAL, "request %d: block outside its macroblock", i);
+        if (px < -28 || py < -28 || px + bw[r[2]] > c->F.w + 24 || py + bh[r[2]] > c->F.h + 24) return fail(c, PCAMV_EINVAL, "request %d leaves the padded plane", i);
     }
     TRY(ensure_qp(c, qp));
     DevTmp<int> d_req, d_out; DevTmp<FrameDev> d_F;
