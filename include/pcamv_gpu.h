@@ -27,8 +27,8 @@
  *   pcamv_gpu_stc_extract       (no reference counterpart: extractor defined in SURVEY 8(c))
  *   pcamv_gpu_set_payload*      the message source, encoder.c:1838-1840 (rand() there: a caller's payload here)
  *   pcamv_gpu_*extract_*, rx_*  (no reference counterpart: the extractor is absent from the reference)
- *   pcamv_gpu_*_slices*,        (no reference counterpart) the receiver fed from stream bytes: CABAC P slices parsed on the
- *   parse_pslice_cabac_device   device, one wavefront per slice (k_parse_pslice), straight into the extractor
+ *   pcamv_gpu_*_slices*,        (no reference counterpart) the receiver fed from stream bytes: CABAC and CAVLC P slices parsed on
+ *   parse_pslice_*_device       the device, one wavefront per slice (k_parse_pslice, k_parse_pslice_cavlc), straight into the extractor
  *   pcamv_gpu_close             x264_encoder_close's frees
  *
  * All functions return 0 on success and a negative PCAMV_E* code on error; the message is
@@ -228,7 +228,7 @@ int  pcamv_gpu_batch_create(pcamv_ctx_t *const *ctxs, int n, pcamv_batch_t **bat
 void pcamv_gpu_batch_destroy(pcamv_batch_t *batch);
 int  pcamv_gpu_batch_step(pcamv_batch_t *batch, int qp, float emrate, void *stream);
 /* kernel: the dominant kernel's name (below), or one of "k_embed_prepare", "k_extract_prepare", "k_extract_bits", "k_payload_check" */
-int  pcamv_gpu_batch_kernel_time(pcamv_batch_t *batch, const char *kernel, double *avg_ms, int *launches, int reset);    /* ... or "k_parse_pslice" */
+int  pcamv_gpu_batch_kernel_time(pcamv_batch_t *batch, const char *kernel, double *avg_ms, int *launches, int reset);    /* ... or "k_parse_pslice", "k_parse_pslice_cavlc" */
 const char *pcamv_gpu_batch_last_error(const pcamv_batch_t *batch);
 /* Closed loop on the device: with on != 0 every batch step ends with pass 2 + the loop filter (embedding must be
  * on: the flip map comes from it), leaving each context's deblocked reconstruction in its device planes
@@ -282,6 +282,7 @@ int pcamv_gpu_abi_version(void);
 /* What the library can do beyond the calls of its ABI version: a mask of PCAMV_FEATURE_* (additions keep the version). */
 #define PCAMV_FEATURE_PAYLOAD 0x1u      /* the payload path below */
 #define PCAMV_FEATURE_SLICE_PARSER 0x2u /* CABAC P slices parsed on the device (the receiver from a stream, at the end of this file) */
+#define PCAMV_FEATURE_SLICE_PARSER_CAVLC 0x4u   /* ... and CAVLC P slices (the *_cavlc calls there) */
 unsigned pcamv_gpu_features(void);
 
 /* ---- Payload path: the caller's bits through the device-resident entry points, and back out on the device ----
@@ -334,7 +335,8 @@ int pcamv_gpu_batch_payload_check(pcamv_batch_t *batch, int64_t *diff);
  * macroblocks, one reference, 4x4 transform, cabac_init_idc 0; PCAMV_EUNSUP for an intra macroblock, PCAMV_EINVAL for a slice that
  * ends in the wrong place, runs out of bytes or has bad alignment bits.  The host parser is the independent check of this one
  * (tests/test_slice_parse_emu.py, test_slice_parse_fuzz.py, test_gpu_slice_parser.py).  A slice is at most 2^30 bytes.
- * Contexts opened with b_cabac == 0 are refused with PCAMV_EUNSUP: CAVLC slices keep the host parser.
+ * The stream's entropy mode is stated by the call: these calls take CABAC slices and refuse contexts opened with b_cabac == 0 with
+ * PCAMV_EUNSUP; --no-cabac streams go through the *_cavlc calls below.
  *
  * parse_pslice_cabac_device: the parity probe.  One slice from host bytes, parsed on the device, the mb_count records copied back;
  * the picture size is the context's.  Synchronises. */
@@ -361,6 +363,22 @@ int pcamv_gpu_batch_slice_status(pcamv_batch_t *batch, int32_t *status);
 /* Diagnostics for the parity tests: the records the context's last slice parsed to (mb_count of them; synchronises), and whether
  * the guard region the library keeps behind that buffer still holds its pattern (*guard_intact, optional). */
 int pcamv_gpu_debug_slice_records(pcamv_ctx_t *ctx, pcamv_mb_t *out_mb, int *guard_intact);
+
+/* ---- The same for --no-cabac streams: CAVLC P slices parsed on the device (kernel k_parse_pslice_cavlc, one wavefront per slice) ----
+ *
+ * What changes is the syntax read (mb_skip_run, Exp-Golomb header, residual_block_cavlc, rbsp_slice_trailing_bits) and that there is
+ * no slice QP: the slice data begins at bit start_bit of the RBSP, which need not be a byte boundary, as for
+ * pcamv_gpu_parse_pslice_cavlc_at.  Return codes per slice are that host parser's on every input: PCAMV_EUNSUP for an intra
+ * macroblock, PCAMV_EINVAL for a code no table has, a slice whose bits run out or are left over, or a start bit at or behind the
+ * end (tests/test_slice_parse_cavlc_emu.py, test_slice_parse_cavlc_fuzz.py, test_gpu_slice_parser_cavlc.py).
+ * These calls require contexts opened with b_cabac == 0 and refuse CABAC contexts with PCAMV_EUNSUP (those go through the calls
+ * above).  Everything else is shared with them: staging with one copy, borrowed device buffers and their ordering rule, the
+ * per-context status (pcamv_gpu_batch_slice_status), pcamv_gpu_debug_slice_records and its guard, a failed slice appending nothing,
+ * no host synchronisation. */
+int pcamv_gpu_parse_pslice_cavlc_device(pcamv_ctx_t *ctx, const uint8_t *rbsp, size_t len, size_t start_bit, pcamv_mb_t *out_mb);
+int pcamv_gpu_batch_extract_slices_cavlc(pcamv_batch_t *batch, const pcamv_slice_t *slices, float emrate, void *stream);      /* slice_qp is not read */
+int pcamv_gpu_batch_extract_slices_cavlc_device(pcamv_batch_t *batch, const void *bytes, size_t bytes_size, const int64_t *off,
+                                                const int64_t *len, const int64_t *start_bit, float emrate, void *stream);
 
 #ifdef __cplusplus
 }

@@ -23,8 +23,8 @@
 #define NEV 32                 /* launches the analysis kernel's timer remembers between two kernel_time calls ... */
 #define NRING 8
 #define NKEV 16                /* ... and a timer of the smaller kernels */
-enum { KT_ANALYSE, KT_EMBED_PREPARE, KT_EXTRACT_PREPARE, KT_EXTRACT_BITS, KT_PAYLOAD_CHECK, KT_PARSE_PSLICE, KT_N };
-#define PCAMV_FEATURES (PCAMV_FEATURE_PAYLOAD | PCAMV_FEATURE_SLICE_PARSER)
+enum { KT_ANALYSE, KT_EMBED_PREPARE, KT_EXTRACT_PREPARE, KT_EXTRACT_BITS, KT_PAYLOAD_CHECK, KT_PARSE_PSLICE, KT_PARSE_PSLICE_CAVLC, KT_N };
+#define PCAMV_FEATURES (PCAMV_FEATURE_PAYLOAD | PCAMV_FEATURE_SLICE_PARSER | PCAMV_FEATURE_SLICE_PARSER_CAVLC)
 #define SLICE_GUARD_MBS 4       /* records behind a context's receive-side records that nothing may write (pcamv_gpu_debug_slice_records) */
 #define NSTAGE 2                /* staging buffers of extract_slices: a call waits for the one before the last */
 /* the stages of a step (batch_launch's `what`): plane production, analysis (search + RCA + encode), embedding, second pass */
@@ -78,7 +78,7 @@ struct pcamv_batch {
      * payload_check */
     ExtractDev *h_X, *d_X; long long *d_chk;
     DescRing xring;
-    /* receiver from a stream (k_parse_pslice): per-context status words, the tables, the row buffers of pictures too wide for LDS, and
+    /* receiver from a stream (k_parse_pslice, k_parse_pslice_cavlc; a batch is of one entropy mode): per-context status words, the tables, the row buffers of pictures too wide for LDS, and
      * the staging of host slices -- descriptor arrays then bytes in one block, pinned host and device, NSTAGE of them in turn */
     int *d_sstat; uint8_t *d_sp_tab, *d_sp_scratch;
     int sp_lds_cols;            /* pictures up to this many macroblocks wide keep the parser's row buffer in LDS (SP_LDS_COLS; PCAMV_SLICE_LDS_COLS lowers it) */
@@ -377,7 +377,7 @@ static const char *dominant_kernel(const pcamv_batch *b)
 extern "C" const char *pcamv_gpu_batch_dominant_kernel(const pcamv_batch_t *b) { return dominant_kernel(b); }
 static const char *kt_name(const pcamv_batch *b, int k)      /* what pcamv_gpu_batch_kernel_time knows timer k by */
 {
-    static const char *const small[KT_N] = {NULL, "k_embed_prepare", "k_extract_prepare", "k_extract_bits", "k_payload_check", "k_parse_pslice"};
+    static const char *const small[KT_N] = {NULL, "k_embed_prepare", "k_extract_prepare", "k_extract_bits", "k_payload_check", "k_parse_pslice", "k_parse_pslice_cavlc"};
     return k == KT_ANALYSE ? dominant_kernel(b) : small[k];
 }
 extern "C" int pcamv_gpu_batch_copy_results_async(pcamv_batch_t *b, void *dst_mb, size_t mb_stride, void *dst_flip, size_t flip_stride, void *stream)
@@ -1117,12 +1117,29 @@ extern "C" int pcamv_gpu_extract_pframe(pcamv_ctx_t *c, const pcamv_mb_t *mbs, f
     if (bits_out && m_copy) HIPCHK(c, hipMemcpy(bits_out, c->d_rx_bits, (size_t)m_copy, hipMemcpyDeviceToHost));
     return rx_check(c, NULL);
 }
-/* ------------------------------------------------------------------ receiver from a stream (k_parse_pslice, pcamv_slice.hip.h) */
-/* what every launch of the parser needs of the batch: status words, the tables, scratch rows for pictures too wide for LDS */
-static int slice_setup(pcamv_batch *b)
+/* ------------------------------------------------------------------ receiver from a stream (k_parse_pslice, k_parse_pslice_cavlc, pcamv_slice.hip.h) */
+/* The stream's entropy mode is stated by the call (cavlc = 0 / 1) and has to be the contexts': looked at before anything is set up,
+ * so that a batch never holds the other mode's tables */
+static int slice_mode(pcamv_batch *b, int cavlc)
+{
+    for (int i = 0; i < b->n; i++) {
+        pcamv_ctx *c = b->ctx[i];
+        if (!cavlc && !c->F.b_cabac) return fail(b, PCAMV_EUNSUP, "context %d was opened with --no-cabac: its slices are CAVLC, which pcamv_gpu_batch_extract_slices_cavlc* and pcamv_gpu_parse_pslice_cavlc_device parse", i);
+        if (cavlc && c->F.b_cabac) return fail(b, PCAMV_EUNSUP, "context %d was opened with CABAC: its slices are CABAC, which pcamv_gpu_batch_extract_slices* and pcamv_gpu_parse_pslice_cabac_device parse", i);
+    }
+    return 0;
+}
+/* what every launch of the parser needs of the batch: status words, the tables of its mode, scratch rows for pictures too wide for LDS */
+static int slice_setup(pcamv_batch *b, int cavlc)
 {
     const FrameDev &F = b->ctx[0]->F;
     if (!b->d_sstat) HIPCHK(b, dalloc(&b->d_sstat, (size_t)b->n));
+    if (!b->d_sp_tab && cavlc) {
+        uint8_t tab[SV_TAB_BYTES];
+        if (sv_build_tables(tab)) return fail(b, PCAMV_EINVAL, "a CAVLC code of pcamv_entropy_tables.h does not fit the parser's table entry");
+        HIPCHK(b, dalloc(&b->d_sp_tab, (size_t)SV_TAB_BYTES));
+        HIPCHK(b, hipMemcpy(b->d_sp_tab, tab, sizeof(tab), hipMemcpyHostToDevice));
+    }
     if (!b->d_sp_tab) {
         uint8_t tab[SP_TAB_BYTES];
         memcpy(tab + SP_TAB_INIT, pcamv_cabac_init_p, 2 * SP_NCTX); memcpy(tab + SP_TAB_TRANS, pcamv_cabac_transition, 256);
@@ -1130,15 +1147,14 @@ static int slice_setup(pcamv_batch *b)
         HIPCHK(b, dalloc(&b->d_sp_tab, (size_t)SP_TAB_BYTES));
         HIPCHK(b, hipMemcpy(b->d_sp_tab, tab, sizeof(tab), hipMemcpyHostToDevice));
     }
-    if (F.mb_w > b->sp_lds_cols && !b->d_sp_scratch) HIPCHK(b, dalloc(&b->d_sp_scratch, (size_t)b->n * SP_ROW_BYTES * F.mb_w));
+    if (F.mb_w > b->sp_lds_cols && !b->d_sp_scratch) HIPCHK(b, dalloc(&b->d_sp_scratch, (size_t)b->n * (cavlc ? SV_ROW_BYTES : SP_ROW_BYTES) * F.mb_w));
     return 0;
 }
-/* the contexts can take parsed slices: CABAC, and (want_rx) a reservation each; their descriptors then point at the receive-side records */
+/* the contexts can take parsed slices: (want_rx) a reservation each; their descriptors then point at the receive-side records */
 static int slice_contexts(pcamv_batch *b, int want_rx, float emrate)
 {
     for (int i = 0; i < b->n; i++) {
         pcamv_ctx *c = b->ctx[i];
-        if (!c->F.b_cabac) return fail(b, PCAMV_EUNSUP, "context %d was opened with --no-cabac: CAVLC slices keep the host parser (pcamv_gpu_parse_pslice_cavlc*)", i);
         if (want_rx && !c->d_rx) return fail(b, PCAMV_EINVAL, "context %d has no received buffer (pcamv_gpu_rx_reserve)", i);
     }
     for (int i = 0; i < b->n; i++) {
@@ -1148,28 +1164,31 @@ static int slice_contexts(pcamv_batch *b, int want_rx, float emrate)
     }
     return 0;
 }
-static void slice_launch(pcamv_batch *b, const ExtractDev *dX, SliceJobs J, hipStream_t st)
+static void slice_launch(pcamv_batch *b, const ExtractDev *dX, SliceJobs J, int cavlc, hipStream_t st)
 {
     const FrameDev &F = b->ctx[0]->F;
-    J.tab = b->d_sp_tab; J.scratch = b->d_sp_scratch; J.scratch_stride = (long long)SP_ROW_BYTES * F.mb_w; J.mb_w = F.mb_w; J.mb_h = F.mb_h; J.lds_cols = b->sp_lds_cols;
-    const int ev = kt_begin(b, KT_PARSE_PSLICE, st);
-    hipLaunchKernelGGL(k_parse_pslice, dim3(b->n), dim3(64), 0, st, dX, J);
-    kt_end(b, KT_PARSE_PSLICE, ev, st);
+    const int kt = cavlc ? KT_PARSE_PSLICE_CAVLC : KT_PARSE_PSLICE;
+    J.tab = b->d_sp_tab; J.scratch = b->d_sp_scratch; J.scratch_stride = (long long)(cavlc ? SV_ROW_BYTES : SP_ROW_BYTES) * F.mb_w;
+    J.mb_w = F.mb_w; J.mb_h = F.mb_h; J.lds_cols = b->sp_lds_cols;
+    const int ev = kt_begin(b, kt, st);
+    if (cavlc) hipLaunchKernelGGL(k_parse_pslice_cavlc, dim3(b->n), dim3(64), 0, st, dX, J);
+    else hipLaunchKernelGGL(k_parse_pslice, dim3(b->n), dim3(64), 0, st, dX, J);
+    kt_end(b, kt, ev, st);
 }
 /* parse (slices described by J, one per context) and, with extract != 0, the receiver's kernels behind it, all on `st` */
-static int slices_run(pcamv_batch *b, SliceJobs J, int extract, float emrate, hipStream_t st)
+static int slices_run(pcamv_batch *b, SliceJobs J, int cavlc, int extract, float emrate, hipStream_t st)
 {
     const ExtractDev *dX; int slot;
     TRY(batch_push_xdescs(b, st, &dX, &slot));
-    slice_launch(b, dX, J, st);
+    slice_launch(b, dX, J, cavlc, st);
     if (extract) extract_launch(b, dX, b->n, b->ctx[0]->cap, emrate, st);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(b, PCAMV_EHIP, "kernel launch: %s", hipGetErrorString(e));
     return ring_release(b, b->xring, slot, st);
 }
-/* host slices into the next staging buffer: [off n][len n][start_bit n] int64, [qp n] int32, then the bytes, every slice at a multiple
- * of 4; one copy on `st`.  *stage_out: the buffer's index, to be released (stage_release) once the kernels that read it are queued */
-static int slices_stage(pcamv_batch *b, const pcamv_slice_t *sl, hipStream_t st, SliceJobs *J, int *stage_out)
+/* host slices into the next staging buffer: [off n][len n][start_bit n] int64, [qp n] int32 (zeros with cavlc: slice_qp is not read),
+ * then the bytes, every slice at a multiple of 4; one copy on `st`.  *stage_out: the buffer's index, to be released (stage_release) once the kernels that read it are queued */
+static int slices_stage(pcamv_batch *b, const pcamv_slice_t *sl, int cavlc, hipStream_t st, SliceJobs *J, int *stage_out)
 {
     const size_t n = (size_t)b->n, hdr = (n * (3 * 8 + 4) + 15) & ~(size_t)15;
     size_t total = hdr;
@@ -1194,7 +1213,7 @@ static int slices_stage(pcamv_batch *b, const pcamv_slice_t *sl, hipStream_t st,
     long long *off = (long long *)h, *len = off + n, *start = len + n; int *qp = (int *)(start + n);
     size_t at = 0;
     for (size_t i = 0; i < n; i++) {
-        off[i] = (long long)at; len[i] = (long long)sl[i].len; start[i] = (long long)sl[i].start_bit; qp[i] = sl[i].slice_qp;
+        off[i] = (long long)at; len[i] = (long long)sl[i].len; start[i] = (long long)sl[i].start_bit; qp[i] = cavlc ? 0 : sl[i].slice_qp;
         memcpy(h + hdr + at, sl[i].rbsp, sl[i].len);
         at += (sl[i].len + 3) & ~(size_t)3;
     }
@@ -1215,34 +1234,54 @@ static int stage_release(pcamv_batch *b, int k, hipStream_t st)
     b->stage_used[k] = 1;
     return 0;
 }
-static int slices_checked(pcamv_batch *b, float emrate, int want_rx)
+static int slices_checked(pcamv_batch *b, float emrate, int want_rx, int cavlc)
 {
     if (!b || emrate <= 0) return PCAMV_EINVAL;
     HIPCHK(b, hipSetDevice(b->device));
     TRY(batch_live(b));
-    TRY(slice_setup(b));
+    TRY(slice_mode(b, cavlc));
+    TRY(slice_setup(b, cavlc));
     return slice_contexts(b, want_rx, emrate);
 }
-extern "C" int pcamv_gpu_batch_extract_slices(pcamv_batch_t *b, const pcamv_slice_t *slices, float emrate, void *stream)
+static int extract_slices_host(pcamv_batch *b, const pcamv_slice_t *slices, int cavlc, float emrate, void *stream)
 {
     if (!slices) return PCAMV_EINVAL;
-    TRY(slices_checked(b, emrate, 1));
+    TRY(slices_checked(b, emrate, 1, cavlc));
     hipStream_t st = stream ? (hipStream_t)stream : b->ctx[0]->stream;
     SliceJobs J; int k;
-    TRY(slices_stage(b, slices, st, &J, &k));
-    const int rc = slices_run(b, J, 1, emrate, st), rc2 = stage_release(b, k, st);      /* released on every path */
+    TRY(slices_stage(b, slices, cavlc, st, &J, &k));
+    const int rc = slices_run(b, J, cavlc, 1, emrate, st), rc2 = stage_release(b, k, st);      /* released on every path */
     return rc ? rc : rc2;
 }
-extern "C" int pcamv_gpu_batch_extract_slices_device(pcamv_batch_t *b, const void *bytes, size_t bytes_size, const int64_t *off, const int64_t *len,
-                                                     const int64_t *start_bit, const int32_t *slice_qp, float emrate, void *stream)
+static int extract_slices_device(pcamv_batch *b, const void *bytes, size_t bytes_size, const int64_t *off, const int64_t *len, const int64_t *start_bit,
+                                 const int32_t *slice_qp, int cavlc, float emrate, void *stream)
 {
-    if (!bytes || !off || !len || !start_bit || !slice_qp || bytes_size > ((size_t)1 << 62)) return PCAMV_EINVAL;
-    TRY(slices_checked(b, emrate, 1));
+    if (!bytes || !off || !len || !start_bit || (!cavlc && !slice_qp) || bytes_size > ((size_t)1 << 62)) return PCAMV_EINVAL;
+    TRY(slices_checked(b, emrate, 1, cavlc));
     static_assert(sizeof(long long) == sizeof(int64_t), "the caller's int64 arrays are read as they are");
     SliceJobs J;
     J.bytes = (const uint8_t *)bytes; J.bytes_size = (long long)bytes_size;
     J.off = (const long long *)off; J.len = (const long long *)len; J.start_bit = (const long long *)start_bit; J.qp = slice_qp;
-    return slices_run(b, J, 1, emrate, stream ? (hipStream_t)stream : b->ctx[0]->stream);
+    return slices_run(b, J, cavlc, 1, emrate, stream ? (hipStream_t)stream : b->ctx[0]->stream);
+}
+extern "C" int pcamv_gpu_batch_extract_slices(pcamv_batch_t *b, const pcamv_slice_t *slices, float emrate, void *stream)
+{
+    return extract_slices_host(b, slices, 0, emrate, stream);
+}
+extern "C" int pcamv_gpu_batch_extract_slices_cavlc(pcamv_batch_t *b, const pcamv_slice_t *slices, float emrate, void *stream)
+{
+    return extract_slices_host(b, slices, 1, emrate, stream);
+}
+extern "C" int pcamv_gpu_batch_extract_slices_device(pcamv_batch_t *b, const void *bytes, size_t bytes_size, const int64_t *off, const int64_t *len,
+                                                     const int64_t *start_bit, const int32_t *slice_qp, float emrate, void *stream)
+{
+    if (!slice_qp) return PCAMV_EINVAL;
+    return extract_slices_device(b, bytes, bytes_size, off, len, start_bit, slice_qp, 0, emrate, stream);
+}
+extern "C" int pcamv_gpu_batch_extract_slices_cavlc_device(pcamv_batch_t *b, const void *bytes, size_t bytes_size, const int64_t *off, const int64_t *len,
+                                                           const int64_t *start_bit, float emrate, void *stream)
+{
+    return extract_slices_device(b, bytes, bytes_size, off, len, start_bit, NULL, 1, emrate, stream);
 }
 extern "C" int pcamv_gpu_batch_slice_status(pcamv_batch_t *b, int32_t *status)
 {
@@ -1253,24 +1292,33 @@ extern "C" int pcamv_gpu_batch_slice_status(pcamv_batch_t *b, int32_t *status)
     HIPCHK(b, hipMemcpy(status, b->d_sstat, sizeof(int32_t) * b->n, hipMemcpyDeviceToHost));
     return 0;
 }
-/* the parity probe: one slice from host bytes through k_parse_pslice, its records back */
-extern "C" int pcamv_gpu_parse_pslice_cabac_device(pcamv_ctx_t *c, const uint8_t *rbsp, size_t len, size_t start_bit, int slice_qp, pcamv_mb_t *out_mb)
+/* the parity probe: one slice from host bytes through k_parse_pslice (k_parse_pslice_cavlc), its records back */
+static int parse_pslice_device(pcamv_ctx_t *c, const uint8_t *rbsp, size_t len, size_t start_bit, int slice_qp, int cavlc, pcamv_mb_t *out_mb)
 {
     if (!c || !rbsp || !out_mb) return PCAMV_EINVAL;
     pcamv_batch *b = c->self;
-    TRY(on_behalf(c, b, slices_checked(b, 1.0f, 0)));
+    TRY(on_behalf(c, b, slices_checked(b, 1.0f, 0, cavlc)));
     const pcamv_slice_t sl = {rbsp, len, start_bit, slice_qp};
     SliceJobs J; int k, rc = 0;
-    TRY(on_behalf(c, b, slices_stage(b, &sl, c->stream, &J, &k)));
-    rc = slices_run(b, J, 0, 1.0f, c->stream);
+    TRY(on_behalf(c, b, slices_stage(b, &sl, cavlc, c->stream, &J, &k)));
+    rc = slices_run(b, J, cavlc, 0, 1.0f, c->stream);
     const int rc2 = stage_release(b, k, c->stream);                                     /* released on every path */
     TRY(on_behalf(c, b, rc ? rc : rc2));
     rc = 0;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(&rc, b->d_sstat, sizeof(rc), hipMemcpyDeviceToHost));
-    if (rc) return fail(c, rc, rc == PCAMV_EUNSUP ? "the slice holds an intra macroblock" : "the slice does not parse (ends in the wrong place, runs out of bytes, or bad alignment bits)");
+    if (rc) return fail(c, rc, rc == PCAMV_EUNSUP ? "the slice holds an intra macroblock" : cavlc ? "the slice does not parse (a code no table has, bits left over or missing, or a bad start bit)" :
+                        "the slice does not parse (ends in the wrong place, runs out of bytes, or bad alignment bits)");
     HIPCHK(c, hipMemcpy(out_mb, c->d_rx_mbs, (size_t)c->F.n_mb * sizeof(pcamv_mb_t), hipMemcpyDeviceToHost));
     return 0;
+}
+extern "C" int pcamv_gpu_parse_pslice_cabac_device(pcamv_ctx_t *c, const uint8_t *rbsp, size_t len, size_t start_bit, int slice_qp, pcamv_mb_t *out_mb)
+{
+    return parse_pslice_device(c, rbsp, len, start_bit, slice_qp, 0, out_mb);
+}
+extern "C" int pcamv_gpu_parse_pslice_cavlc_device(pcamv_ctx_t *c, const uint8_t *rbsp, size_t len, size_t start_bit, pcamv_mb_t *out_mb)
+{
+    return parse_pslice_device(c, rbsp, len, start_bit, 0, 1, out_mb);
 }
 extern "C" int pcamv_gpu_debug_slice_records(pcamv_ctx_t *c, pcamv_mb_t *out_mb, int *guard_intact)
 {

@@ -1,5 +1,5 @@
 /*
- * pcamv_slice.hip.h -- k_parse_pslice: CABAC P slices parsed on the device, one wavefront per slice (gfx950).
+ * pcamv_slice.hip.h -- k_parse_pslice, k_parse_pslice_cavlc: P slices parsed on the device, one wavefront per slice (gfx950).
  *
  * A CABAC slice is serial, like a CABAC frame in the analysis kernel; the answer is the same: one wave per slice, thousands of
  * slices in flight.  The parser itself is pcamv_slice_parse.h (shared with the host test drivers); this file gives it its working
@@ -11,19 +11,25 @@
  * No spin-wait, no dependency between waves: a slice that fails writes its status word and the wave is done.  Nothing depends on
  * a slice being well-formed: the slice's place in the byte buffer is checked against the buffer here, everything inside it by the
  * parser.  Records and status leave through ordinary vector stores.
+ *
+ * k_parse_pslice_cavlc is the same for --no-cabac streams (pcamv_slice_parse_cavlc.h).  A CAVLC slice has no context states and
+ * no arithmetic decoder: the wave keeps the byte window, the VLC tables (one 16-bit entry per code), the macroblock cache and a row
+ * buffer of 24 bytes per column -- 5044 bytes, so that LDS admits the 32 waves per CU the registers do.
  */
 #ifndef PCAMV_SLICE_HIP_H
 #define PCAMV_SLICE_HIP_H
 #include "pcamv_embed.hip.h"
 #include "pcamv_slice_parse.h"
+#include "pcamv_slice_parse_cavlc.h"
 
 #define SP_LDS_COLS 128
 
 /* the slices of one launch: slice i is bytes[off[i] .. off[i] + len[i]), its slice data starts behind bit start_bit[i], slice QP qp[i] */
 struct SliceJobs {
     const uint8_t *bytes; long long bytes_size;
-    const long long *off, *len, *start_bit; const int *qp;
-    const uint8_t *tab;                 /* SP_TAB_BYTES: pcamv_entropy_tables.h in the block form of pcamv_slice_parse.h */
+    const long long *off, *len, *start_bit; const int *qp;     /* (CAVLC reads no QP: qp is NULL there) */
+    const uint8_t *tab;                 /* pcamv_entropy_tables.h in the block form of the parser: SP_TAB_BYTES of pcamv_slice_parse.h, or
+                                         * SV_TAB_BYTES of pcamv_slice_parse_cavlc.h */
     uint8_t *scratch; long long scratch_stride;     /* row buffers of pictures wider than SP_LDS_COLS macroblocks, one per slice */
     int mb_w, mb_h;
     int lds_cols;                       /* <= SP_LDS_COLS: pictures wider than this many macroblocks use `scratch` */
@@ -48,6 +54,30 @@ static __global__ void __launch_bounds__(64) k_parse_pslice(const ExtractDev *__
     int rc = PCAMV_EINVAL;
     if (off >= 0 && len >= 0 && len <= J.bytes_size && off <= J.bytes_size - len && X.n_mb == J.mb_w * J.mb_h && (J.mb_w <= lds_cols || J.scratch))
         rc = pcamv_slice_parse(S, T, J.bytes + off, len, J.start_bit[i], J.qp[i], J.mb_w, J.mb_h, (pcamv_mb_t *)X.mbs);
+    if (lane == 0) *X.slice_status = rc;
+}
+
+/* the same for a CAVLC slice: J.tab is the SV_TAB_BYTES block, J.qp is not read, the scratch rows are SV_ROW_BYTES per column */
+static __global__ void __launch_bounds__(64) k_parse_pslice_cavlc(const ExtractDev *__restrict__ Xs, const SliceJobs J)
+{
+    __shared__ uint32_t s_win[64], s_mv[48], s_tl[1], s_tab[SV_TAB_BYTES / 4], s_row[SP_LDS_COLS * SV_ROW_BYTES / 4];
+    __shared__ uint8_t s_nz[48];
+    __shared__ int8_t s_ref[48];
+    static_assert(SV_TAB_BYTES % 4 == 0 && SV_T_CBP % 4 == 0, "the table block is copied and addressed in dwords");
+    const int i = blockIdx.x, lane = threadIdx.x;
+    const ExtractDev X = Xs[i];
+    for (int k = lane; k < SV_TAB_BYTES / 4; k += 64) s_tab[k] = ((const uint32_t *)J.tab)[k];
+    SP_SYNC();
+    const int lds_cols = J.lds_cols < SP_LDS_COLS ? J.lds_cols : SP_LDS_COLS;
+    SvState S;
+    S.win = s_win; S.cmv = s_mv; S.cref = s_ref; S.cnz = s_nz; S.tl = s_tl;
+    S.ctx = nullptr; S.cmvd = nullptr; S.trans = nullptr; S.rlps = nullptr;
+    S.vlc = (const uint16_t *)s_tab; S.cbp_of = (const uint8_t *)s_tab + SV_T_CBP;
+    S.row = J.mb_w <= lds_cols ? (uint8_t *)s_row : J.scratch + (long long)i * J.scratch_stride;
+    const long long off = J.off[i], len = J.len[i];
+    int rc = PCAMV_EINVAL;
+    if (off >= 0 && len >= 0 && len <= J.bytes_size && off <= J.bytes_size - len && X.n_mb == J.mb_w * J.mb_h && (J.mb_w <= lds_cols || J.scratch))
+        rc = pcamv_slice_parse_cavlc(S, J.bytes + off, len, J.start_bit[i], J.mb_w, J.mb_h, (pcamv_mb_t *)X.mbs);
     if (lane == 0) *X.slice_status = rc;
 }
 #endif

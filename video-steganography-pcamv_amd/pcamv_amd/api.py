@@ -252,6 +252,7 @@ def stc_extract(stego, m, height=10, lcg=None):
 
 FEATURE_PAYLOAD = 0x1
 FEATURE_SLICE_PARSER = 0x2      # CABAC P slices parsed on the device: Encoder.parse_pslice_device, Batch.extract_slices
+FEATURE_SLICE_PARSER_CAVLC = 0x4    # CAVLC P slices too: Encoder.parse_pslice_cavlc_device, Batch.extract_slices_cavlc
 
 
 def features():
@@ -440,6 +441,16 @@ class Encoder:
         self._chk(self.lib.pcamv_gpu_parse_pslice_cabac_device(self.ctx, _p(data), len(data), hdr_bits, qp, _p(mbs)), "parse_pslice_cabac_device")
         return mbs
 
+    def parse_pslice_cavlc_device(self, rbsp, hdr_bits):
+        """pcamv_gpu_parse_pslice_cavlc_device: the records of one CAVLC P slice (RBSP bytes, slice data from bit hdr_bits on; the
+        context was opened with b_cabac = 0) parsed on the device by k_parse_pslice_cavlc -- the parity probe of
+        Batch.extract_slices_cavlc; raises like parse_pslice_at"""
+        data = np.frombuffer(bytes(rbsp), np.uint8) if len(rbsp) else np.zeros(1, np.uint8)
+        mbs = np.zeros(self.n_mb, MB_DTYPE)
+        self.lib.pcamv_gpu_parse_pslice_cavlc_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
+        self._chk(self.lib.pcamv_gpu_parse_pslice_cavlc_device(self.ctx, _p(data), len(rbsp), hdr_bits, _p(mbs)), "parse_pslice_cavlc_device")
+        return mbs
+
     def slice_records(self):
         """diagnostics: (the records this context's last slice parsed to on the device, whether the guard behind them is intact)"""
         mbs = np.zeros(self.n_mb, MB_DTYPE)
@@ -611,6 +622,29 @@ class Batch:
         self.lib.pcamv_gpu_batch_extract_slices_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
         self._slice_chk(self.lib.pcamv_gpu_batch_extract_slices_device(self.b, data.data_ptr(), data.numel(), off.data_ptr(), length.data_ptr(), hdr_bits.data_ptr(),
                                                                        qp.data_ptr(), emrate, C.c_void_p(stream or None)), "batch_extract_slices_device")
+
+    def extract_slices_cavlc(self, slices, emrate, stream=0):
+        """extract_slices for --no-cabac contexts: one CAVLC P slice per context, a list of (rbsp bytes, hdr_bits), parsed by
+        k_parse_pslice_cavlc; CABAC contexts are refused (unsupported)"""
+        if len(slices) != len(self.encs):
+            raise PcamvError(f"{len(slices)} slices for a batch of {len(self.encs)} contexts")
+        class _Slice(C.Structure):
+            _fields_ = [("rbsp", C.c_void_p), ("len", C.c_size_t), ("start_bit", C.c_size_t), ("slice_qp", C.c_int32)]
+        keep = [np.frombuffer(bytes(s[0]), np.uint8) if len(s[0]) else np.zeros(1, np.uint8) for s in slices]
+        arr = (_Slice * len(slices))(*[_Slice(k.ctypes.data, len(s[0]), int(s[1]), 0) for k, s in zip(keep, slices)])
+        self.lib.pcamv_gpu_batch_extract_slices_cavlc.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
+        self._slice_chk(self.lib.pcamv_gpu_batch_extract_slices_cavlc(self.b, arr, emrate, C.c_void_p(stream or None)), "batch_extract_slices_cavlc")
+
+    def extract_slices_cavlc_device(self, data, off, length, hdr_bits, emrate, stream=0):
+        """extract_slices_device for --no-cabac contexts: the same tensors without the QPs, the same ordering rule"""
+        for t, size, what in ((data, 1, "data: uint8"), (off, 8, "off: int64"), (length, 8, "length: int64"), (hdr_bits, 8, "hdr_bits: int64")):
+            if not _is_device_tensor(t) or not t.is_cuda or t.element_size() != size or not t.is_contiguous():
+                raise PcamvError(f"{what}, contiguous, on the device")
+        if any(t.numel() != len(self.encs) for t in (off, length, hdr_bits)):
+            raise PcamvError(f"one entry per context ({len(self.encs)}) in off / length / hdr_bits")
+        self.lib.pcamv_gpu_batch_extract_slices_cavlc_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
+        self._slice_chk(self.lib.pcamv_gpu_batch_extract_slices_cavlc_device(self.b, data.data_ptr(), data.numel(), off.data_ptr(), length.data_ptr(), hdr_bits.data_ptr(),
+                                                                             emrate, C.c_void_p(stream or None)), "batch_extract_slices_cavlc_device")
 
     def slice_status(self):
         """per context: the parser's code for its slice of the last extract_slices call (0, -1 invalid, -5 unsupported); synchronises"""
