@@ -834,3 +834,13 @@ def test_pass2_task_sizes_match_oracle(pc, monkeypatch, unit):
     monkeypatch.setenv("PCAMV_PASS2_UNIT", str(unit))
     assert _closed_loop_vs_oracle(pc, 352, 288, "hex", 5, 30, 3, 2, 81) > 0
     assert _closed_loop_vs_oracle(pc, 352, 288, "umh", 7, 26, 2, 2, 83) > 0
+
+
+@pytest.mark.parametrize("W,H", [(176, 144), (96, 176)])
+def test_closed_loop_per_diagonal_schedule_matches_oracle(pc, monkeypatch, W, H):
+    """PCAMV_SCHED=diag against the oracle directly (elsewhere it is only compared with the dataflow schedule): its batched second
+    pass is one launch per anti-diagonal, a block per macroblock and GOP, each macroblock a run of one through the second pass' tile.
+    96x176 = 6x11 macroblocks, taller than wide: the first diagonals hold one block, the last ones start below row 0; three GOPs:
+    the per-GOP descriptor; p4x4: the loop filter's strength rule inside 8x8 blocks that can be split."""
+    monkeypatch.setenv("PCAMV_SCHED", "diag")
+    assert _closed_loop_vs_oracle(pc, W, H, "hex", 5, 30, 3, 2, 131, statics=(0, 32, 64), inter=0x30) > 0

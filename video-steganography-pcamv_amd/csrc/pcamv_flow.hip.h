@@ -110,7 +110,7 @@ __device__ __forceinline__ bool mbk_search_spec(const FrameDev &F, MBLocal *L, A
     bool handed_on = false;
     int skip;
     for (int round = 0;; round++) {
-        mb_load(F, L, mb_x, mb_y, 0, 0);                 /* neighbours' motion + source pixels; nothing of the entropy coder yet */
+        mb_load(F, L, mb_x, mb_y, false, 0);                 /* neighbours' motion + source pixels; nothing of the entropy coder yet */
         skip = analyse_s16<VARIANT>(F, L, a);
         if (!handed_on) {
             /* what the successor's searches start from: a skipped macroblock's motion is final as it stands (as far as this
@@ -212,9 +212,7 @@ __device__ __forceinline__ void flow_loop(const FrameDev *__restrict__ Fs, const
             const int x0 = fl.unit * x, n = imin(fl.unit, F.mb_w - x0);
             p2_unit_load(F, Up, x0, y, n);
             for (int k = 0; k < n; k++) {
-                P2Pre pre;
-                pre.r = &Up->rec[k]; pre.base = Up->car_base[k]; pre.any_flip = Up->mbflip[k]; pre.nnz1 = Up->nnz1[k]; pre.drain = k > 0;
-                if (mbk_pass2(F, &L, x0 + k, y, 0, &pre)) p2_put_mb(Up, &L, k);
+                if (mbk_pass2(F, &L, x0 + k, y, p2_pre(Up, k))) p2_put_mb(Up, &L, k);
                 mbk_deblock_unit(F, Up, &L, k, x0 + k, y);
             }
             p2_unit_store(F, Up, x0, y, n);
@@ -257,6 +255,18 @@ __device__ __forceinline__ void flow_loop(const FrameDev *__restrict__ Fs, const
 static_assert(sizeof(MBLocal) + sizeof(Analysis) <= PCAMV_WAVE_LDS_MAX, "the analysis kernels' LDS per wave (MBLocal + Analysis) no longer allows 16 waves per CU");
 #endif
 
+/* the macroblock of block blockIdx.x of a launch for the anti-diagonal x + 2y = d (the host's diag_launch sizes the grid); false: none */
+__device__ __forceinline__ bool diag_pos(const FrameDev &F, int d, int *x, int *y)
+{
+    int y_lo = d - (F.mb_w - 1); y_lo = y_lo > 0 ? (y_lo + 1) >> 1 : 0;
+    *y = y_lo + (int)blockIdx.x; *x = d - 2 * *y;
+    return *y < F.mb_h && *x >= 0 && *x < F.mb_w;
+}
+
+/* the second pass and the loop filter one anti-diagonal per launch (PCAMV_SCHED=diag, pcamv_gpu_pass2_pframe) are a unit of their own,
+ * pcamv_pass2_diag.hip, so that the unit of k_pass2_deblock_flow holds no other user of the tile's functions; stages: P2D_* */
+enum { P2D_PASS2 = 1, P2D_DEBLOCK = 2 };
+void pcamv_launch_pass2_diag(int stages, unsigned blocks, unsigned gops, hipStream_t st, const FrameDev *dF, int d);
 /* The instances of k_analyse_flow with --me tesa or the RD mode decision of --subme 6 / 7 compiled in are kernels of their own
  * (pcamv_logic.h: the control code is a template on the variant), each in a translation unit of its own, built in parallel with
  * the main one; the library calls them through these launchers.  pcamv_tesa.hip: */

@@ -32,8 +32,7 @@ enum { ST_PLANES = 1, ST_ANALYSE = 2, ST_EMBED = 4, ST_PASS2 = 8 };
 
 /* what device code assumes of constants it cannot see side by side (this unit includes both headers) */
 static_assert(sizeof(pcamv_mb_t) == 59 * 4, "p2_unit_load copies a record as 59 dwords: a field added to pcamv_mb_t truncates or misaligns the second pass' LDS copy");
-static_assert(P2_LSLOTS <= 64 * 11 && P2_CSLOTS <= 64 * 7 && 8 * 59 <= 64 * 8,
-              "p2_unit_load's fixed unroll counts (11 / 7 / 8 rounds of 64 lanes) no longer cover the luma tile, the chroma tile or the 8 records of a run");
+static_assert(4 * P2_LROW(8) <= P2_TW && 4 * P2_CROW(8) <= P2_CW, "a tile row of the longest run (8 macroblocks and the four columns left of it) no longer fits the tile's pitch");
 static_assert(FLOW_SPEC_MIN_MBW - 1 > FLOW_SPEC_AHEAD + 1, "speculative chain: a macroblock would be handed on before its top / top-right neighbours are final");
 
 /* The builds of the RD instance of the analysis kernel (one translation unit each, pcamv_rd.hip), a row per entry of
@@ -681,7 +680,7 @@ static int batch_launch(pcamv_batch *b, int what, hipStream_t st)
             hipLaunchKernelGGL(k_flow_init, dim3((b->fl2.total + 255) / 256), dim3(256), 0, st, b->fl2);
             hipLaunchKernelGGL(k_pass2_deblock_flow, dim3(b->flow2_waves), dim3(64), 0, st, dF, b->fl2);
         } else {
-            diag_launch(b->n_diag, F, [&](int cnt, int d) { hipLaunchKernelGGL(k_pass2_deblock_diag, dim3(cnt, G), dim3(64), 0, st, dF, d); });
+            diag_launch(b->n_diag, F, [&](int cnt, int d) { pcamv_launch_pass2_diag(P2D_PASS2 | P2D_DEBLOCK, cnt, G, st, dF, d); });
         }
     }
     hipError_t e = hipGetLastError();
@@ -858,8 +857,7 @@ extern "C" int pcamv_gpu_pass2_pframe(pcamv_ctx_t *c, const uint8_t *flips, int 
         TRY(on_behalf(c, b, batch_push_descs(b, c->stream, &dF, &dE, &slot)));
         const FrameDev &F = c->F;
         for (int pass = 0; pass < 2; pass++) {
-            if (pass == 0) diag_launch(b->n_diag, F, [&](int cnt, int d) { hipLaunchKernelGGL(k_pass2_diag, dim3(cnt, 1), dim3(64), 0, c->stream, dF, d); });
-            else diag_launch(b->n_diag, F, [&](int cnt, int d) { hipLaunchKernelGGL(k_deblock_diag, dim3(cnt, 1), dim3(64), 0, c->stream, dF, d); });
+            diag_launch(b->n_diag, F, [&](int cnt, int d) { pcamv_launch_pass2_diag(pass == 0 ? P2D_PASS2 : P2D_DEBLOCK, cnt, 1, c->stream, dF, d); });
             HIPCHK(c, hipStreamSynchronize(c->stream));
             uint8_t *const *dst = pass == 0 ? recon : deblocked;
             if (dst)

@@ -4,7 +4,7 @@
  *
  *   k_search_diag / k_rca / k_encode     PCAMV_SCHED=diag: phase A for one anti-diagonal, one wavefront per macroblock; phase B,
  *                     one wavefront per (macroblock, carrier slot); phase C, one wavefront per macroblock
- *   k_pass2_diag / k_deblock_diag / k_pass2_deblock_diag   the second pass and the loop filter of one anti-diagonal
+ *                     (the second pass and the loop filter of one anti-diagonal: pcamv_pass2_diag.hip)
  *   k_flow_init       queue and dependency counters of a persistent launch
  *   k_analyse_flow    the dataflow schedule of the analysis, common instance (the --me tesa and RD instances: pcamv_tesa.hip, pcamv_rd.hip)
  *   k_pass2_deblock_flow   second pass + loop filter through the same queue, a run of macroblocks per task
@@ -21,10 +21,8 @@ __global__ void __launch_bounds__(64) k_search_diag(const FrameDev *__restrict__
     __shared__ MBLocal L;
     __shared__ Analysis A;
     const FrameDev F = Fs[blockIdx.y];
-    /* MBs of the anti-diagonal x + 2y = d */
-    int y_lo = d - (F.mb_w - 1); y_lo = y_lo > 0 ? (y_lo + 1) >> 1 : 0;
-    int y = y_lo + (int)blockIdx.x, x = d - 2 * y;
-    if (y >= F.mb_h || x < 0 || x >= F.mb_w) return;
+    int x, y;
+    if (!diag_pos(F, d, &x, &y)) return;
     mbk_search<VARIANT>(F, &L, &A, x, y);
 }
 static __global__ void __launch_bounds__(64) k_rca(const FrameDev *__restrict__ Fs, int slots_per_mb)
@@ -44,42 +42,6 @@ static __global__ void __launch_bounds__(64) k_encode(const FrameDev *__restrict
     const FrameDev F = Fs[blockIdx.y];
     if ((int)blockIdx.x >= F.n_mb) return;
     mbk_encode(F, &L, &A, blockIdx.x);
-}
-
-/* ------------------------------------------------------------------ pass 2 + loop filter */
-static __global__ void __launch_bounds__(64) k_pass2_diag(const FrameDev *__restrict__ Fs, int d)
-{
-    __shared__ MBLocal L;
-    const FrameDev F = Fs[blockIdx.y];
-    int y_lo = d - (F.mb_w - 1); y_lo = y_lo > 0 ? (y_lo + 1) >> 1 : 0;
-    int y = y_lo + (int)blockIdx.x, x = d - 2 * y;
-    if (y >= F.mb_h || x < 0 || x >= F.mb_w) return;
-    mbk_pass2(F, &L, x, y);
-}
-static __global__ void __launch_bounds__(64) k_deblock_diag(const FrameDev *__restrict__ Fs, int d)
-{
-    __shared__ DeblockLDS D;
-    const FrameDev F = Fs[blockIdx.y];
-    int y_lo = d - (F.mb_w - 1); y_lo = y_lo > 0 ? (y_lo + 1) >> 1 : 0;
-    const int my = y_lo + (int)blockIdx.x, mx = d - 2 * my;
-    if (my >= F.mb_h || mx < 0 || mx >= F.mb_w) return;
-    mbk_deblock(F, &D, mx, my);
-}
-
-/* both stages of one anti-diagonal in one launch: the filter of (x,y) only needs the pass-2 reconstruction of
- * (x,y) itself and the filtered neighbours of earlier diagonals, and only modifies macroblocks of earlier diagonals */
-static __global__ void __launch_bounds__(64) k_pass2_deblock_diag(const FrameDev *__restrict__ Fs, int d)
-{
-    __shared__ MBLocal L;
-    __shared__ DeblockLDS D;
-    const FrameDev F = Fs[blockIdx.y];
-    int y_lo = d - (F.mb_w - 1); y_lo = y_lo > 0 ? (y_lo + 1) >> 1 : 0;
-    const int y = y_lo + (int)blockIdx.x, x = d - 2 * y;
-    if (y >= F.mb_h || x < 0 || x >= F.mb_w) return;
-    mbk_pass2(F, &L, x, y);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        /* the reconstruction just stored is read back by the filter */
-    __syncthreads();
-    mbk_deblock(F, &D, x, y);
 }
 
 /* ------------------------------------------------------------------ the persistent kernels (pcamv_flow.hip.h) */
@@ -115,8 +77,7 @@ static __global__ void __launch_bounds__(64, PCAMV_FLOW_OCC) k_analyse_flow(cons
 static __global__ void __launch_bounds__(64, PCAMV_PASS2_OCC) k_pass2_deblock_flow(const FrameDev *__restrict__ Fs, FlowDev fl)
 {
     /* only the head of the per-macroblock storage (PCAMV_PASS2_LDS: the fields the second pass touches come first in MBLocal): 4.3 instead
-     * of 8.9 KB per wave with the filter's staging area, so the CU holds the six waves per SIMD the kernel's 83 VGPRs allow -- it
-     * waits for memory three quarters of its time, more waves in flight is what it can use */
+     * of 8.9 KB per wave */
     __shared__ __attribute__((aligned(16))) uint8_t Lraw[PCAMV_PASS2_LDS];
     __shared__ __attribute__((aligned(16))) P2Unit U;
     flow_loop<1, 0>(Fs, fl, *reinterpret_cast<MBLocal *>(Lraw), nullptr, &U);

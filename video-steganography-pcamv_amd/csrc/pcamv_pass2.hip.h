@@ -1,11 +1,12 @@
 /*
- * pcamv_pass2.hip.h -- the loop filter and the second pass' tile of a run of macroblocks (gfx950): types and __device__ functions
- * only.  Every unit of the library sees this header through pcamv_flow.hip.h (flow_loop's second-pass arm names P2Unit), so it
- * holds no kernel; the kernels that use it are the main unit's (pcamv_kernels.hip.h).
+ * pcamv_pass2.hip.h -- the second pass and the loop filter of a run of macroblocks of a row, held as one tile in LDS (gfx950): types
+ * and __device__ functions only.  Every unit of the library sees this header through pcamv_flow.hip.h (flow_loop's second-pass arm
+ * is made of these functions), so it holds no kernel; the kernels that use it are k_pass2_deblock_flow (main unit, pcamv_kernels.hip.h) with
+ * runs of up to eight macroblocks and the per-diagonal kernels (pcamv_pass2_diag.hip) with runs of one.
  *
- *   mbk_deblock         the loop filter of one macroblock in a staging area of its own (the per-diagonal kernels)
- *   p2_unit_load / p2_put_mb / mbk_deblock_unit / p2_unit_store   the same for a run of up to eight macroblocks of a row held as
- *                       one tile in LDS (P2Unit; k_pass2_deblock_flow)
+ *   p2_unit_load / p2_unit_store   the tile (P2Unit) in from the frame and back
+ *   mbk_pass2 / p2_put_mb          the second pass of one macroblock of the run; its new reconstruction into the tile
+ *   mbk_deblock_unit               the loop filter of one macroblock, in the tile -- the only loop filter of the library
  */
 #ifndef PCAMV_PASS2_HIP_H
 #define PCAMV_PASS2_HIP_H
@@ -25,139 +26,7 @@ __device__ static const int8_t dbk_tc0_dev[52][3] = {
     {2, 3, 4}, {3, 3, 5}, {3, 4, 6}, {3, 4, 6}, {4, 5, 7}, {4, 5, 8}, {4, 6, 9}, {5, 7, 10}, {6, 8, 11}, {6, 8, 13}, {7, 10, 14}, {8, 11, 16},
     {9, 12, 18}, {10, 13, 20}, {11, 15, 23}, {13, 17, 25}};
 
-/* Loop filter of one macroblock (x264_frame_deblock_row, common/frame.c:627-798, inter macroblocks, 4x4
- * transform, one QP): the macroblock and the 4 pixels left of / above it are staged in LDS, the 32
- * boundary strengths are computed one per lane, then the four vertical and the four horizontal edges are
- * filtered in order (one line per lane: 16 luma, 8 + 8 chroma on even edges) and the touched pixels go back.
- * Needs (x-1,y), (x,y-1) and (x+1,y-1) filtered: same anti-diagonal order as the search. */
-struct DeblockLDS { uint8_t sy[20][24]; uint8_t sc[2][12][16]; uint8_t sbs[2][4][4]; };
-/* Lo: the MBLocal pass 2 of this macroblock has just run in (same wave): its unfiltered reconstruction (pred), type, final
- * motion and non-zero flags are taken from there; nullptr: everything is in memory like the neighbours' */
-__device__ __forceinline__ void mbk_deblock(const FrameDev &F, DeblockLDS *D, int mx, int my, const MBLocal *Lo = nullptr)
-{
-    const uint8_t *own = Lo ? Lo->pred : nullptr;
-    uint8_t (*sy)[24] = D->sy;              /* rows / cols -4..15 of the macroblock at [r + 4][c + 4] */
-    uint8_t (*sc)[12][16] = D->sc;          /* chroma rows / cols -4..7 */
-    uint8_t (*sbs)[4][4] = D->sbs;
-    const int lane = LANE(), xy = my * F.mb_w + mx, W = F.w, CW = F.w >> 1;
-    const int gx = 16 * mx, gy = 16 * my, cgx = 8 * mx, cgy = 8 * my;
-    /* stage: 20 rows x 5 dwords of luma, 2 x 12 rows x 3 dwords of chroma (nothing outside the picture) */
-    for (int i = lane; i < 100; i += 64) {
-        const int r = i / 5 - 4, c = (i % 5) * 4 - 4;
-        if (own && r >= 0 && c >= 0) *(uint32_t *)&sy[r + 4][c + 4] = lds4(own + r * 16 + c);
-        else if (gy + r >= 0 && gx + c >= 0) *(uint32_t *)&sy[r + 4][c + 4] = NB_LD32(F.rec[0] + (size_t)(gy + r) * W + gx + c);
-    }
-    for (int i = lane; i < 72; i += 64) {
-        const int pl = i / 36, j = i % 36, r = j / 3 - 4, c = (j % 3) * 4 - 4;
-        if (own && r >= 0 && c >= 0) *(uint32_t *)&sc[pl][r + 4][c + 4] = lds4(own + 256 + r * 16 + pl * 8 + c);
-        else if (cgy + r >= 0 && cgx + c >= 0) *(uint32_t *)&sc[pl][r + 4][c + 4] = NB_LD32((pl ? F.rec[2] : F.rec[1]) + (size_t)(cgy + r) * CW + cgx + c);
-    }
-    /* boundary strengths */
-    const int type = Lo ? Lo->i_type : (int)NB_LD8(&F.mb_type[xy]), qp = F.qp;
-    const int qp_thresh = 15 - (F.chroma_qp_offset > 0 ? F.chroma_qp_offset : 0);
-    const int edge_end = (type == PCAMV_P_SKIP || qp <= qp_thresh) ? 1 : 4;
-    const int no_sub8x8 = type != PCAMV_P_8x8 || !(F.inter & PCAMV_ANALYSE_PSUB8x8);
-    if (lane < 32) {
-        const int dir = lane >> 4, edge = (lane >> 2) & 3, i = lane & 3;
-        int bs = 0;
-        const bool on = edge < edge_end && !(edge == 0 && (dir ? my == 0 : mx == 0));
-        if (on) {
-            const int x = dir == 0 ? edge : i, y = dir == 0 ? i : edge;
-            const int xn = dir == 0 ? (x - 1) & 3 : x, yn = dir == 0 ? y : (y - 1) & 3;
-            const int nxy = edge ? xy : (dir ? xy - F.mb_w : xy - 1);
-            const int bi = (x & 1) + 2 * (y & 1) + 4 * (x >> 1) + 8 * (y >> 1), bn = (xn & 1) + 2 * (yn & 1) + 4 * (xn >> 1) + 8 * (yn >> 1);
-            const int s4 = 4 * F.mb_w, s8 = 2 * F.mb_w;
-            const int fx = 4 * mx + x, fy = 4 * my + y, fxn = dir == 0 ? fx - 1 : fx, fyn = dir == 0 ? fy : fy - 1;
-            /* both sides of the edge: flags, motion, reference -- this macroblock's from LDS when it has just been made
-             * here, the rest in one round of loads (not one per test) */
-            const bool nb_local = Lo && edge;
-            const int c8a = SCAN8_0 + x + 8 * y, c8b = SCAN8_0 + xn + 8 * yn;
-            const unsigned nz_a = Lo ? (unsigned)Lo->nnz_mask : (unsigned)NB_LD16(&F.nnz[xy]);
-            const unsigned nz_b = nb_local ? (unsigned)Lo->nnz_mask : (unsigned)NB_LD16(&F.nnz[nxy]);
-            const uint32_t wa = Lo ? NB_PACK16(Lo->cmv[c8a][0], Lo->cmv[c8a][1]) : NB_LD32(F.mv + 2 * (fy * s4 + fx));
-            const uint32_t wb = nb_local ? NB_PACK16(Lo->cmv[c8b][0], Lo->cmv[c8b][1]) : NB_LD32(F.mv + 2 * (fyn * s4 + fxn));
-            const int ra = Lo ? (int)Lo->cref[c8a] : (int)NB_LD8(&F.ref8[(fy >> 1) * s8 + (fx >> 1)]);
-            const int rb = nb_local ? (int)Lo->cref[c8b] : (int)NB_LD8(&F.ref8[(fyn >> 1) * s8 + (fxn >> 1)]);
-            if (((nz_a >> bi) & 1) || ((nz_b >> bn) & 1)) bs = 2;
-            else if (!(edge & no_sub8x8)) {
-                const int a0 = (int16_t)(wa & 0xffff), a1 = (int16_t)(wa >> 16), b0 = (int16_t)(wb & 0xffff), b1 = (int16_t)(wb >> 16);
-                if (ra != rb || iabs(a0 - b0) >= 4 || iabs(a1 - b1) >= 4) bs = 1;
-                bs |= 0x10;              /* marks "decided by the motion test" for the copy rule below */
-            }
-        }
-        sbs[dir][edge][i] = (uint8_t)bs;
-    }
-    __syncthreads();
-    {   /* frame.c:735-737: inside an 8x8 that cannot be split, the odd 4-pixel group repeats its left/upper
-         * neighbour's strength unless that one is 2 */
-        const int dir = (lane >> 4) & 1, edge = (lane >> 2) & 3, i = lane & 3;
-        int bs = sbs[dir][edge][i];
-        const int prev = i ? sbs[dir][edge][i - 1] & 0xf : 0;
-        __syncthreads();
-        if (lane < 32) {
-            if ((bs & 0x10) && (i & no_sub8x8) && prev != 2) bs = prev;
-            sbs[dir][edge][i] = (uint8_t)(bs & 0xf);
-        }
-    }
-    __syncthreads();
-    const int qpc = F.chroma_qp;
-    const int alpha = dbk_alpha_dev[qp], beta = dbk_beta_dev[qp], calpha = dbk_alpha_dev[qpc], cbeta = dbk_beta_dev[qpc];
-    /* tc0 of the three strengths, looked up once (a per-edge table load would sit on the chain of eight dependent edges) */
-    const int tl1 = dbk_tc0_dev[qp][0], tl2 = dbk_tc0_dev[qp][1], tl3 = dbk_tc0_dev[qp][2];
-    const int tc1 = dbk_tc0_dev[qpc][0], tc2 = dbk_tc0_dev[qpc][1], tc3 = dbk_tc0_dev[qpc][2];
-    for (int dir = 0; dir < 2; dir++)
-        for (int edge = 0; edge < 4; edge++) {
-            const uint32_t any = *(const uint32_t *)sbs[dir][edge];
-            if (any) {
-                if (lane < 16 && alpha && beta) {
-                    const int bs = sbs[dir][edge][lane >> 2];
-                    if (bs) {
-                        const int tc0 = bs == 1 ? tl1 : bs == 2 ? tl2 : tl3;
-                        uint8_t *q = dir == 0 ? &sy[lane + 4][4 * edge + 4] : &sy[4 * edge + 4][lane + 4];
-                        const int xs = dir == 0 ? 1 : 24;
-                        const int p2 = q[-3 * xs], p1 = q[-2 * xs], p0 = q[-xs], q0 = q[0], q1 = q[xs], q2 = q[2 * xs];
-                        if (iabs(p0 - q0) < alpha && iabs(p1 - p0) < beta && iabs(q1 - q0) < beta) {
-                            int tc = tc0;
-                            if (iabs(p2 - p0) < beta) { q[-2 * xs] = (uint8_t)(p1 + clip3i(((p2 + ((p0 + q0 + 1) >> 1)) >> 1) - p1, -tc0, tc0)); tc++; }
-                            if (iabs(q2 - q0) < beta) { q[xs] = (uint8_t)(q1 + clip3i(((q2 + ((p0 + q0 + 1) >> 1)) >> 1) - q1, -tc0, tc0)); tc++; }
-                            const int delta = clip3i((((q0 - p0) * 4) + (p1 - q1) + 4) >> 3, -tc, tc);
-                            q[-xs] = (uint8_t)clip3i(p0 + delta, 0, 255); q[0] = (uint8_t)clip3i(q0 - delta, 0, 255);
-                        }
-                    }
-                } else if (lane >= 16 && lane < 32 && !(edge & 1) && calpha && cbeta) {
-                    const int pl = (lane - 16) >> 3, l = (lane - 16) & 7, bs = sbs[dir][edge][l >> 1];
-                    if (bs) {
-                        const int tc = (bs == 1 ? tc1 : bs == 2 ? tc2 : tc3) + 1;
-                        uint8_t *q = dir == 0 ? &sc[pl][l + 4][2 * edge + 4] : &sc[pl][2 * edge + 4][l + 4];
-                        const int xs = dir == 0 ? 1 : 16;
-                        const int p1 = q[-2 * xs], p0 = q[-xs], q0 = q[0], q1 = q[xs];
-                        if (iabs(p0 - q0) < calpha && iabs(p1 - p0) < cbeta && iabs(q1 - q0) < cbeta) {
-                            const int delta = clip3i((((q0 - p0) * 4) + (p1 - q1) + 4) >> 3, -tc, tc);
-                            q[-xs] = (uint8_t)clip3i(p0 + delta, 0, 255); q[0] = (uint8_t)clip3i(q0 - delta, 0, 255);
-                        }
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    /* write back: the macroblock, the 4 columns left of it (rows 0..15), the 4 rows above it (cols 0..15) */
-    { const int r = lane >> 2, c = (lane & 3) * 4;
-      NB_ST32(F.rec[0] + (size_t)(gy + r) * W + gx + c, *(const uint32_t *)&sy[r + 4][c + 4]); }
-    if (lane < 16 && mx > 0) NB_ST32(F.rec[0] + (size_t)(gy + lane) * W + gx - 4, *(const uint32_t *)&sy[lane + 4][0]);
-    if (lane >= 16 && lane < 32 && my > 0) { const int r = (lane - 16) >> 2, c = ((lane - 16) & 3) * 4;
-      NB_ST32(F.rec[0] + (size_t)(gy - 4 + r) * W + gx + c, *(const uint32_t *)&sy[r][c + 4]); }
-    if (lane >= 32) {
-        const int pl = (lane - 32) >> 4, j = (lane - 32) & 15, r = j >> 1, c = (j & 1) * 4;
-        uint8_t *dst = pl ? F.rec[2] : F.rec[1];
-        NB_ST32(dst + (size_t)(cgy + r) * CW + cgx + c, *(const uint32_t *)&sc[pl][r + 4][c + 4]);
-    }
-    __syncthreads();
-    if (lane < 16 && mx > 0) { const int pl = lane >> 3, r = lane & 7; uint8_t *dst = pl ? F.rec[2] : F.rec[1];
-      NB_ST32(dst + (size_t)(cgy + r) * CW + cgx - 4, *(const uint32_t *)&sc[pl][r + 4][0]); }
-    if (lane >= 16 && lane < 32 && my > 0) { const int pl = (lane - 16) >> 3, j = (lane - 16) & 7, r = j >> 1, c = (j & 1) * 4; uint8_t *dst = pl ? F.rec[2] : F.rec[1];
-      NB_ST32(dst + (size_t)(cgy - 4 + r) * CW + cgx + c, *(const uint32_t *)&sc[pl][r][c + 4]); }
-}
-/* ------------------------------------------------------------------ the second pass of a RUN of macroblocks of a row (k_pass2_deblock_flow)
+/* ------------------------------------------------------------------ the second pass of a RUN of macroblocks of a row (k_pass2_deblock_flow; runs of one: pcamv_pass2_diag.hip)
  * A task of the second-pass kernel is up to eight macroblocks of a row.  Taken one by one, each cost two or three memory round trips (record,
  * pixels, the filter's borders), fetched 4 KB for its 0.6 KB (a macroblock's sixteen 16-byte rows are sixteen cache lines, which its seven
  * neighbours in the run fetch again) and stored its rows as partial lines.  Here the run is ONE tile in LDS: its pixels with the four
@@ -175,46 +44,53 @@ struct P2Unit {
     unsigned l_nnz; uint32_t l_mv[4]; int l_ref[4];                 /* the left neighbour's right column: of the run's first macroblock from memory, then handed on */
     uint8_t sbs[2][4][4];
 };
-#define P2_LSLOTS (20 * 33)             /* luma dwords of the tile: row r = i / 33 - 4, column c = 4 * (i % 33) - 4 */
-#define P2_CSLOTS (2 * 12 * 17)         /* chroma: plane i / 204, row (i % 204) / 17 - 4, column 4 * (i % 17) - 4 */
+/* NMAX: the longest run the caller hands in (8: a task of k_pass2_deblock_flow; 1: the per-diagonal kernels) -- the tile's dwords are walked
+ * 64 at a time, and only as many of them as a run of NMAX has */
+#define P2_LROW(NMAX) (4 * (NMAX) + 1)              /* luma dwords of a tile row: row r = i / P2_LROW - 4, column c = 4 * (i % P2_LROW) - 4 */
+#define P2_CROW(NMAX) (2 * (NMAX) + 1)              /* chroma: plane i / (12 * P2_CROW), row (i % (12 * P2_CROW)) / P2_CROW - 4, column 4 * (i % P2_CROW) - 4 */
+#define P2_LITER(NMAX) ((20 * P2_LROW(NMAX) + 63) / 64)
+#define P2_CITER(NMAX) ((2 * 12 * P2_CROW(NMAX) + 63) / 64)
+#define P2_RITER(NMAX) ((59 * (NMAX) + 63) / 64)    /* the records: 59 words each */
+template <int NMAX>
 __device__ __forceinline__ bool p2_slot(const FrameDev &F, int i, bool chroma, int x0, int y, int n, int *pl, int *r, int *c, size_t *goff)
 {
     if (!chroma) {
-        if (i >= P2_LSLOTS) return false;
-        *pl = 0; *r = i / 33 - 4; *c = 4 * (i % 33) - 4;
+        if (i >= 20 * P2_LROW(NMAX)) return false;
+        *pl = 0; *r = i / P2_LROW(NMAX) - 4; *c = 4 * (i % P2_LROW(NMAX)) - 4;
         const int gx = 16 * x0 + *c, gy = 16 * y + *r;
         if (gx < 0 || gy < 0 || *c >= 16 * n) return false;
         *goff = (size_t)gy * F.w + gx;
     } else {
-        if (i >= P2_CSLOTS) return false;
-        const int j = i % 204;
-        *pl = 1 + i / 204; *r = j / 17 - 4; *c = 4 * (j % 17) - 4;
+        if (i >= 2 * 12 * P2_CROW(NMAX)) return false;
+        const int j = i % (12 * P2_CROW(NMAX));
+        *pl = 1 + i / (12 * P2_CROW(NMAX)); *r = j / P2_CROW(NMAX) - 4; *c = 4 * (j % P2_CROW(NMAX)) - 4;
         const int gx = 8 * x0 + *c, gy = 8 * y + *r;
         if (gx < 0 || gy < 0 || *c >= 8 * n) return false;
         *goff = (size_t)gy * (F.w >> 1) + gx;
     }
     return true;
 }
+template <int NMAX = 8>
 __device__ __forceinline__ void p2_unit_load(const FrameDev &F, P2Unit *U, int x0, int y, int n)
 {
     const int lane = LANE(), xy0 = y * F.mb_w + x0;
     /* every load first, then the stores to LDS: one round trip for the run */
-    uint32_t vl[11], vc[7], vr[8];
+    uint32_t vl[P2_LITER(NMAX)], vc[P2_CITER(NMAX)], vr[P2_RITER(NMAX)];
 #pragma unroll
-    for (int t = 0; t < 11; t++) {
+    for (int t = 0; t < P2_LITER(NMAX); t++) {
         int pl, r, c; size_t o;
-        vl[t] = p2_slot(F, lane + 64 * t, false, x0, y, n, &pl, &r, &c, &o) ? NB_LD32(F.rec[0] + o) : 0u;
+        vl[t] = p2_slot<NMAX>(F, lane + 64 * t, false, x0, y, n, &pl, &r, &c, &o) ? NB_LD32(F.rec[0] + o) : 0u;
     }
 #pragma unroll
-    for (int t = 0; t < 7; t++) {
+    for (int t = 0; t < P2_CITER(NMAX); t++) {
         int pl, r, c; size_t o;
         vc[t] = 0u;
-        if (p2_slot(F, lane + 64 * t, true, x0, y, n, &pl, &r, &c, &o)) vc[t] = NB_LD32((pl == 2 ? F.rec[2] : F.rec[1]) + o);
+        if (p2_slot<NMAX>(F, lane + 64 * t, true, x0, y, n, &pl, &r, &c, &o)) vc[t] = NB_LD32((pl == 2 ? F.rec[2] : F.rec[1]) + o);
     }
 #pragma unroll
-    for (int t = 0; t < 8; t++) {
+    for (int t = 0; t < P2_RITER(NMAX); t++) {
         const int i = lane + 64 * t, k = i / 59, w = i - 59 * k;
-        vr[t] = (i < 8 * 59 && k < n) ? ((const uint32_t *)&F.rec_mb[xy0 + k])[w] : 0u;
+        vr[t] = (i < NMAX * 59 && k < n) ? ((const uint32_t *)&F.rec_mb[xy0 + k])[w] : 0u;
     }
     int cb = 0, mf = 1, n1 = 0;
     if (lane < n) { cb = F.car_base ? F.car_base[xy0 + lane] : 0; mf = F.mbflip ? (int)F.mbflip[xy0 + lane] : 1; n1 = (int)F.nnz[xy0 + lane]; }
@@ -230,19 +106,19 @@ __device__ __forceinline__ void p2_unit_load(const FrameDev &F, P2Unit *U, int x
     }
     PCAMV_WAVE_SYNC();
 #pragma unroll
-    for (int t = 0; t < 11; t++) {
+    for (int t = 0; t < P2_LITER(NMAX); t++) {
         int pl, r, c; size_t o;
-        if (p2_slot(F, lane + 64 * t, false, x0, y, n, &pl, &r, &c, &o)) *(uint32_t *)&U->ty[r + 4][c + 4] = vl[t];
+        if (p2_slot<NMAX>(F, lane + 64 * t, false, x0, y, n, &pl, &r, &c, &o)) *(uint32_t *)&U->ty[r + 4][c + 4] = vl[t];
     }
 #pragma unroll
-    for (int t = 0; t < 7; t++) {
+    for (int t = 0; t < P2_CITER(NMAX); t++) {
         int pl, r, c; size_t o;
-        if (p2_slot(F, lane + 64 * t, true, x0, y, n, &pl, &r, &c, &o)) *(uint32_t *)&U->tc[pl - 1][r + 4][c + 4] = vc[t];
+        if (p2_slot<NMAX>(F, lane + 64 * t, true, x0, y, n, &pl, &r, &c, &o)) *(uint32_t *)&U->tc[pl - 1][r + 4][c + 4] = vc[t];
     }
 #pragma unroll
-    for (int t = 0; t < 8; t++) {
+    for (int t = 0; t < P2_RITER(NMAX); t++) {
         const int i = lane + 64 * t;
-        if (i < 8 * 59) ((uint32_t *)U->rec)[i] = vr[t];
+        if (i < NMAX * 59) ((uint32_t *)U->rec)[i] = vr[t];
     }
     if (lane < 8) { U->car_base[lane] = cb; U->mbflip[lane] = mf; U->nnz1[lane] = n1; }
     if (lane < 32) { U->t_mv[lane >> 2][lane & 3] = tm; U->t_ref[lane >> 2][lane & 3] = tr; if ((lane & 3) == 0) U->t_nnz[lane >> 2] = tn; }
@@ -258,7 +134,88 @@ __device__ __forceinline__ void p2_put_mb(P2Unit *U, const MBLocal *L, int k)
     if (lane < 32) *(uint32_t *)&U->tc[lane >> 4][((lane & 15) >> 1) + 4][8 * k + 4 + 4 * (lane & 1)] = lds4(L->pred + 256 + ((lane & 15) >> 1) * 16 + (lane >> 4) * 8 + (lane & 1) * 4);
     PCAMV_WAVE_SYNC();
 }
-/* the loop filter of macroblock k of the run, in the tile (what mbk_deblock does in its staging area; same strengths, same arithmetic) */
+/* pass 2 of one macroblock of the run (analyse.c:2870-3107 + x264_macroblock_encode, semantics of DESIGN.md 5b): the
+ * pass-1 type / partition, the record's MVs with mv_stego where the flip map says so, for a P_SKIP
+ * macroblock the skip prediction from the FINAL neighbours; reconstruction; final motion + non-zero flags
+ * for the loop filter and for the next frame's temporal candidates.  Same left / top / top-right
+ * dependency as the search. */
+/* What the macroblock needs of memory came in with the tile (P2Pre, out of P2Unit): the record, the index of the first carrier, "any
+ * carrier flipped", the first pass' non-zero flags; and the pixels of a macroblock the embedding left alone are already where the loop
+ * filter works -- nothing is loaded here then.  Returns 1 when the macroblock was reconstructed anew (L->pred holds its pixels, for
+ * p2_put_mb), 0 when the first pass' reconstruction stands. */
+struct P2Pre { const pcamv_mb_t *r; int base, any_flip, nnz1, drain; };
+__device__ __forceinline__ P2Pre p2_pre(const P2Unit *U, int k)
+{
+    P2Pre pre;
+    pre.r = &U->rec[k]; pre.base = U->car_base[k]; pre.any_flip = U->mbflip[k]; pre.nnz1 = U->nnz1[k]; pre.drain = k > 0;
+    return pre;
+}
+__device__ __forceinline__ int mbk_pass2(const FrameDev &F, MBLocal *L, int mb_x, int mb_y, const P2Pre &unit)
+{
+    const int xy = mb_y * F.mb_w + mb_x;
+    const pcamv_mb_t *r = unit.r;
+    PCAMV_WAVE_SYNC();
+    /* (a later macroblock of the run: the skip prediction reads the left neighbour's final motion from memory, where this wave stored it a moment ago) */
+    if (unit.drain && r->i_type == PCAMV_P_SKIP) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    /* only a skipped macroblock needs its neighbours (skip prediction); the source pixels only a macroblock that is re-encoded (below) */
+    const bool coded = r->i_type != PCAMV_P_SKIP;
+    mb_load(F, L, mb_x, mb_y, coded);
+    L->i_type = r->i_type; L->i_partition = r->i_partition;
+    for (int i = 0; i < 4; i++) L->sub_part[i] = r->i_sub_partition[i];
+    cache_ref_set(L, 0, 0, 4, 4, 0);
+    int same;
+    if (L->i_type == PCAMV_P_SKIP) {
+        L->i_partition = PCAMV_D_16x16;
+        cache_mv_set(L, 0, 0, 4, 4, L->pskip_mv[0], L->pskip_mv[1]);
+        same = L->pskip_mv[0] == r->pskip_mv[0] && L->pskip_mv[1] == r->pskip_mv[1];
+    } else {
+        int *slots = L->slots;
+        const int n = carrier_slots(L->i_type, L->i_partition, L->sub_part, r->used, slots);
+        const int base = unit.base;
+        PCAMV_WAVE_SYNC();
+        /* its carriers' flip flags: one more round trip, for the macroblocks that have a flipped carrier at all */
+        if (rfl(unit.any_flip)) { FOR_CAND(j, n) L->cxy[j] = FD(F).flip ? (uint32_t)(FD(F).flip[base + j] == 1) : 0u; }
+        else { FOR_CAND(j, n) L->cxy[j] = 0u; }
+        PCAMV_WAVE_SYNC();
+        FOR_CAND(i, 16) {
+            const int s = carrier_of_block(L->i_type, L->i_partition, L->sub_part, i);
+            int flipped = 0;
+            for (int j = 0; j < n; j++) if (slots[j] == s) flipped = (int)L->cxy[j];
+            L->cmv[scan8_of(i)][0] = flipped ? r->mv_stego[s][0] : r->mv[i][0];
+            L->cmv[scan8_of(i)][1] = flipped ? r->mv_stego[s][1] : r->mv[i][1];
+        }
+        PCAMV_WAVE_SYNC();
+        same = 1;
+        for (int j = 0; j < n; j++) if (L->cxy[j]) same = 0;
+    }
+    /* A macroblock whose motion is what the first pass decided -- no carrier of it flipped; skipped with the same skip prediction --
+     * reconstructs to what the first pass stored (same type, motion, source, reference and quantiser): pixels and non-zero flags
+     * are taken from there instead of being made again.  (~7 of 8 macroblocks at half a bit per carrier.) */
+    const int reuse = same && FD(F).rec_is_pass1;
+    if (reuse) L->nnz_mask = unit.nnz1;
+    else {
+        if (coded) prim_load_fenc(F, L);
+        mb_encode(F, L);
+    }
+    /* final motion, type and non-zero flags: read by the neighbours' skip prediction and loop filter in the same
+     * launch, so stored write-through like the search's hand-off */
+    const int s4 = 4 * F.mb_w, s8 = 2 * F.mb_w, b4 = 4 * (mb_y * s4 + mb_x), b8 = 2 * (mb_y * s8 + mb_x);
+    PCAMV_WAVE_SYNC();
+    FOR_CAND(i, 16) {
+        int x = i & 3, y = i >> 2;
+        NB_ST32(&FD(F).mv[2 * (b4 + y * s4 + x)], NB_PACK16(L->cmv[SCAN8_0 + x + 8 * y][0], L->cmv[SCAN8_0 + x + 8 * y][1]));
+    }
+    if (LANE() == 0) {
+        NB_ST8(&FD(F).mb_type[xy], L->i_type);
+        NB_ST16(&FD(F).ref8[b8], 0); NB_ST16(&FD(F).ref8[b8 + s8], 0);
+        NB_ST16(&FD(F).nnz[xy], L->nnz_mask);
+    }
+    return !reuse;
+}
+/* The loop filter of macroblock k of the run, in the tile (x264_frame_deblock_row, common/frame.c:627-798, inter macroblocks, 4x4
+ * transform, one QP): the 32 boundary strengths are computed one per lane, then the four vertical and the four horizontal edges are
+ * filtered in order, one line per lane.  Needs (x-1,y), (x,y-1) and (x+1,y-1) filtered: same anti-diagonal order as the search.
+ * Of Lo -- the MBLocal pass 2 of this macroblock has just run in -- it reads type, final motion (cmv, cref) and non-zero flags. */
 __device__ __forceinline__ void mbk_deblock_unit(const FrameDev &F, P2Unit *U, const MBLocal *Lo, int k, int mx, int my)
 {
     uint8_t (*sbs)[4][4] = U->sbs;
@@ -287,13 +244,14 @@ __device__ __forceinline__ void mbk_deblock_unit(const FrameDev &F, P2Unit *U, c
             else if (!(edge & no_sub8x8)) {
                 const int a0 = (int16_t)(wa & 0xffff), a1 = (int16_t)(wa >> 16), b0 = (int16_t)(wb & 0xffff), b1 = (int16_t)(wb >> 16);
                 if (ra != rb || iabs(a0 - b0) >= 4 || iabs(a1 - b1) >= 4) bs = 1;
-                bs |= 0x10;
+                bs |= 0x10;              /* marks "decided by the motion test" for the copy rule below */
             }
         }
         sbs[dir][edge][i] = (uint8_t)bs;
     }
     __syncthreads();
-    {
+    {   /* frame.c:735-737: inside an 8x8 that cannot be split, the odd 4-pixel group repeats its left/upper
+         * neighbour's strength unless that one is 2 */
         const int dir = (lane >> 4) & 1, edge = (lane >> 2) & 3, i = lane & 3;
         int bs = sbs[dir][edge][i];
         const int prev = i ? sbs[dir][edge][i - 1] & 0xf : 0;
@@ -306,6 +264,7 @@ __device__ __forceinline__ void mbk_deblock_unit(const FrameDev &F, P2Unit *U, c
     __syncthreads();
     const int qpc = F.chroma_qp;
     const int alpha = dbk_alpha_dev[qp], beta = dbk_beta_dev[qp], calpha = dbk_alpha_dev[qpc], cbeta = dbk_beta_dev[qpc];
+    /* tc0 of the three strengths, looked up once (a per-edge table load would sit on the chain of eight dependent edges) */
     const int tl1 = dbk_tc0_dev[qp][0], tl2 = dbk_tc0_dev[qp][1], tl3 = dbk_tc0_dev[qp][2];
     const int tc1 = dbk_tc0_dev[qpc][0], tc2 = dbk_tc0_dev[qpc][1], tc3 = dbk_tc0_dev[qpc][2];
     /* luma lines in lanes 0..15, the chroma lines of the even edges in lanes 16..31 (plane, line), ONE instruction stream for both: the chroma
@@ -345,19 +304,20 @@ __device__ __forceinline__ void mbk_deblock_unit(const FrameDev &F, P2Unit *U, c
 }
 /* the tile back to the frame: the run's rows 0..15 with the four columns left of it (the left neighbour's, touched by the first
  * macroblock's left edge), and the four rows above it */
+template <int NMAX = 8>
 __device__ __forceinline__ void p2_unit_store(const FrameDev &F, P2Unit *U, int x0, int y, int n)
 {
     const int lane = LANE();
     PCAMV_WAVE_SYNC();
 #pragma unroll
-    for (int t = 0; t < 11; t++) {
+    for (int t = 0; t < P2_LITER(NMAX); t++) {
         int pl, r, c; size_t o;
-        if (p2_slot(F, lane + 64 * t, false, x0, y, n, &pl, &r, &c, &o) && (r < 0 ? c >= 0 : true)) NB_ST32(F.rec[0] + o, *(const uint32_t *)&U->ty[r + 4][c + 4]);
+        if (p2_slot<NMAX>(F, lane + 64 * t, false, x0, y, n, &pl, &r, &c, &o) && (r < 0 ? c >= 0 : true)) NB_ST32(F.rec[0] + o, *(const uint32_t *)&U->ty[r + 4][c + 4]);
     }
 #pragma unroll
-    for (int t = 0; t < 7; t++) {
+    for (int t = 0; t < P2_CITER(NMAX); t++) {
         int pl, r, c; size_t o;
-        if (p2_slot(F, lane + 64 * t, true, x0, y, n, &pl, &r, &c, &o) && (r < 0 ? c >= 0 : true)) NB_ST32((pl == 2 ? F.rec[2] : F.rec[1]) + o, *(const uint32_t *)&U->tc[pl - 1][r + 4][c + 4]);
+        if (p2_slot<NMAX>(F, lane + 64 * t, true, x0, y, n, &pl, &r, &c, &o) && (r < 0 ? c >= 0 : true)) NB_ST32((pl == 2 ? F.rec[2] : F.rec[1]) + o, *(const uint32_t *)&U->tc[pl - 1][r + 4][c + 4]);
     }
 }
 #endif

@@ -1162,7 +1162,7 @@ __device__ __forceinline__ void prim_copy_pred(MBLocal *L, uint8_t *dst)
     if (lane < 32) ((uint32_t *)dst)[64 + lane] = ((const uint32_t *)L->pred)[64 + lane];
     PCAMV_WAVE_SYNC();
 }
-/* wt: store write-through (agent scope), for pixels another wave reads in the same launch (pass 2 -> loop filter) */
+/* wt: store write-through (agent scope), for pixels another wave reads in the same launch (--subme >= 6: the neighbours' intra thresholds) */
 __device__ __forceinline__ void prim_store_rec(const FrameDev &F, MBLocal *L, bool wt = false)
 {
     const auto &D = FD(F);
@@ -1178,21 +1178,6 @@ __device__ __forceinline__ void prim_store_rec(const FrameDev &F, MBLocal *L, bo
         const uint32_t v = lds4(L->pred + 256 + row * 16 + plane * 8 + c4 * 4);
         if (wt) NB_ST32(d, v); else *d = v;
     }
-}
-/* the macroblock's reconstruction back out of the frame (pass 2 of a macroblock whose motion the embedding left alone: its first-pass
- * reconstruction IS its final one) */
-__device__ __forceinline__ void prim_load_rec(const FrameDev &F, MBLocal *L)
-{
-    const auto &D = FD(F);
-    PCAMV_WAVE_SYNC();
-    const int lane = LANE();
-    { int row = lane >> 2, c4 = lane & 3;
-      sts4(L->pred + row * 16 + c4 * 4, *(const uint32_t *)(D.rec[0] + (size_t)(L->mb_y * 16 + row) * D.w + L->mb_x * 16 + c4 * 4)); }
-    if (lane < 32) {
-        int plane = lane >> 4, row = (lane & 15) >> 1, c4 = lane & 1;
-        sts4(L->pred + 256 + row * 16 + plane * 8 + c4 * 4, *(const uint32_t *)((plane ? D.rec[2] : D.rec[1]) + (size_t)(L->mb_y * 8 + row) * (D.w >> 1) + L->mb_x * 8 + c4 * 4));
-    }
-    PCAMV_WAVE_SYNC();
 }
 __device__ __forceinline__ void prim_store_mvr(const FrameDev &F, MBLocal *L, int mvx, int mvy)
 {

@@ -132,8 +132,8 @@ def lib_path():
 
 
 # the library's translation units (csrc/<unit>.hip): the host side with the common kernels, the --me tesa instance of the analysis kernel,
-# and the six builds of its --subme 6 / 7 instance
-UNITS = ("pcamv_gpu", "pcamv_tesa", "pcamv_rd", "pcamv_rd_lo", "pcamv_rd_spec", "pcamv_rd_spec2", "pcamv_rd_spec4", "pcamv_rd_tesa")
+# the per-diagonal second pass, and the six builds of the analysis kernel's --subme 6 / 7 instance
+UNITS = ("pcamv_gpu", "pcamv_pass2_diag", "pcamv_tesa", "pcamv_rd", "pcamv_rd_lo", "pcamv_rd_spec", "pcamv_rd_spec2", "pcamv_rd_spec4", "pcamv_rd_tesa")
 
 
 def build_library(force=False):
