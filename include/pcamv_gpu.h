@@ -29,6 +29,8 @@
  *   pcamv_gpu_*extract_*, rx_*  (no reference counterpart: the extractor is absent from the reference)
  *   pcamv_gpu_*_slices*,        (no reference counterpart) the receiver fed from stream bytes: CABAC and CAVLC P slices parsed on
  *   parse_pslice_*_device       the device, one wavefront per slice (k_parse_pslice, k_parse_pslice_cavlc), straight into the extractor
+ *   pcamv_gpu_*write_*          the second pass' x264_macroblock_write_cabac + x264_cabac_encode_flush (encoder/cabac.c:781, common/cabac.c:908)
+ *                               and x264_nal_encode (common/common.c:658): the P slice of a step written on the device (k_write_pslice)
  *   pcamv_gpu_close             x264_encoder_close's frees
  *
  * All functions return 0 on success and a negative PCAMV_E* code on error; the message is
@@ -283,6 +285,7 @@ int pcamv_gpu_abi_version(void);
 #define PCAMV_FEATURE_PAYLOAD 0x1u      /* the payload path below */
 #define PCAMV_FEATURE_SLICE_PARSER 0x2u /* CABAC P slices parsed on the device (the receiver from a stream, at the end of this file) */
 #define PCAMV_FEATURE_SLICE_PARSER_CAVLC 0x4u   /* ... and CAVLC P slices (the *_cavlc calls there) */
+#define PCAMV_FEATURE_SLICE_WRITER 0x8u /* CABAC P slices written on the device (the sender to a stream, at the end of this file) */
 unsigned pcamv_gpu_features(void);
 
 /* ---- Payload path: the caller's bits through the device-resident entry points, and back out on the device ----
@@ -379,6 +382,44 @@ int pcamv_gpu_parse_pslice_cavlc_device(pcamv_ctx_t *ctx, const uint8_t *rbsp, s
 int pcamv_gpu_batch_extract_slices_cavlc(pcamv_batch_t *batch, const pcamv_slice_t *slices, float emrate, void *stream);      /* slice_qp is not read */
 int pcamv_gpu_batch_extract_slices_cavlc_device(pcamv_batch_t *batch, const void *bytes, size_t bytes_size, const int64_t *off,
                                                 const int64_t *len, const int64_t *start_bit, float emrate, void *stream);
+
+/* ---- Sender to a stream: CABAC P slices written on the device (kernel k_write_pslice, one wavefront per slice) ----
+ *
+ * A step leaves each context's final motion on the device (the records and the flip map); these calls turn it into the bytes a
+ * receiver needs without a trip through the host: slice data as encoder/cabac.c writes it (cabac_init_idc 0, the states of the
+ * slice QP, mb_qp_delta 0, one reference, 4x4 transform), the levels made again from the final motion with the step's source and
+ * reference planes and the context's quantisers.  A P_SKIP macroblock's motion is inferred as a decoder infers it; a macroblock the
+ * record calls coded is written as coded whatever it codes, since the receiver counts carriers per coded macroblock.
+ * The slice header is the caller's, opaque here (its fields come from the SPS / PPS, the host's control plane): n_bits bits, most
+ * significant first, behind which the writer puts cabac_alignment_one_bits and the slice data -- the RBSP form; with n_bits == 0
+ * (or no header) the output is the bare slice data.  As a NAL unit: long start code, the header byte from nal_ref_idc and
+ * nal_unit_type, the RBSP with emulation prevention as x264_nal_encode inserts it.  i_frame chooses the bit x264_cabac_encode_flush
+ * takes from the frame counter (0x35a4e4f5 >> (i_frame & 31) & 1).
+ * Contexts opened with b_cabac == 0 are refused with PCAMV_EUNSUP: there is no CAVLC writer yet.  SPS, PPS, slice headers, I frames
+ * and several slices per picture stay the host's. */
+typedef struct pcamv_slice_hdr_t { const uint8_t *bits; int32_t n_bits; int32_t i_frame; int32_t nal_ref_idc; int32_t nal_unit_type; } pcamv_slice_hdr_t;
+/* The parity probe; synchronises.  mbs == NULL: the context's last frame -- final == 0 the first-pass records as they are, final != 0
+ * the records with the embedding stage's flip map (what the second pass reconstructed).  mbs != NULL: host records that hold final
+ * motion already (what a parser returns), uploaded; only type, partition, sub-partition and mv are read.  hdr may be NULL (no header
+ * bits, i_frame 0, nal_ref_idc 2, nal_unit_type 1).  out[cap] receives *len bytes; a slice that does not fit is PCAMV_ENOMEM. */
+int pcamv_gpu_write_pslice(pcamv_ctx_t *ctx, const pcamv_slice_hdr_t *hdr, int final, const pcamv_mb_t *mbs, int as_nal, uint8_t *out, size_t cap, size_t *len);
+/* Every context's last step with final motion, from one launch on `stream`, no host synchronisation.  hdrs: n_hdr == 1 (one header
+ * for all contexts) or the batch size (NULL and 0: none), staged with one copy.  bytes is a borrowed device buffer of bytes_size
+ * bytes; off and cap (in) and len (out) are device arrays of int64, one entry per context: slice i goes to bytes[off[i] .. off[i] +
+ * cap[i]) and is len[i] long.  Nothing is written at or beyond a slice's capacity; a slice that does not fit sets its context's
+ * status to PCAMV_ENOMEM and its len to 0.  With as_nal == 0, (bytes, off, len) is what pcamv_gpu_batch_extract_slices_device takes.
+ * Ordering is the caller's, by the rule of that call; and this call belongs after the batch_step whose frame it writes and before the
+ * next one, whose plane stage is the first thing to overwrite what the writer reads (that step's source planes, padded reference
+ * planes, records and flip map). */
+int pcamv_gpu_batch_write_step(pcamv_batch_t *batch, const pcamv_slice_hdr_t *hdrs, int n_hdr, int as_nal, void *bytes, size_t bytes_size,
+                               const int64_t *off, const int64_t *cap, int64_t *len, void *stream);
+/* synchronises; status[i] = 0 or PCAMV_ENOMEM for context i's slice of the last write call (PCAMV_EINVAL: its place is not inside the buffer) */
+int pcamv_gpu_batch_write_status(pcamv_batch_t *batch, int32_t *status);
+/* a capacity under which no slice of the context's picture size fails, for a header of hdr_bits bits, as RBSP or as a NAL unit */
+int64_t pcamv_gpu_slice_bound(const pcamv_ctx_t *ctx, int32_t hdr_bits, int as_nal);
+/* Host code, the inverse of pcamv_gpu_nal_to_rbsp: long start code, header byte, the RBSP with emulation prevention bytes as
+ * x264_nal_encode inserts them (common/common.c:658-695).  nal[cap] receives *nal_len bytes (at most 5 + len + len / 2 + 1). */
+int pcamv_gpu_rbsp_to_nal(const uint8_t *rbsp, size_t len, int nal_ref_idc, int nal_unit_type, uint8_t *nal, size_t cap, size_t *nal_len);
 
 #ifdef __cplusplus
 }

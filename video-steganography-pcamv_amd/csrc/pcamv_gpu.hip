@@ -23,8 +23,8 @@
 #define NEV 32                 /* launches the analysis kernel's timer remembers between two kernel_time calls ... */
 #define NRING 8
 #define NKEV 16                /* ... and a timer of the smaller kernels */
-enum { KT_ANALYSE, KT_EMBED_PREPARE, KT_EXTRACT_PREPARE, KT_EXTRACT_BITS, KT_PAYLOAD_CHECK, KT_PARSE_PSLICE, KT_PARSE_PSLICE_CAVLC, KT_N };
-#define PCAMV_FEATURES (PCAMV_FEATURE_PAYLOAD | PCAMV_FEATURE_SLICE_PARSER | PCAMV_FEATURE_SLICE_PARSER_CAVLC)
+enum { KT_ANALYSE, KT_EMBED_PREPARE, KT_EXTRACT_PREPARE, KT_EXTRACT_BITS, KT_PAYLOAD_CHECK, KT_PARSE_PSLICE, KT_PARSE_PSLICE_CAVLC, KT_WRITE_PSLICE, KT_N };
+#define PCAMV_FEATURES (PCAMV_FEATURE_PAYLOAD | PCAMV_FEATURE_SLICE_PARSER | PCAMV_FEATURE_SLICE_PARSER_CAVLC | PCAMV_FEATURE_SLICE_WRITER)
 #define SLICE_GUARD_MBS 4       /* records behind a context's receive-side records that nothing may write (pcamv_gpu_debug_slice_records) */
 #define NSTAGE 2                /* staging buffers of extract_slices: a call waits for the one before the last */
 /* the stages of a step (batch_launch's `what`): plane production, analysis (search + RCA + encode), embedding, second pass */
@@ -33,6 +33,7 @@ enum { ST_PLANES = 1, ST_ANALYSE = 2, ST_EMBED = 4, ST_PASS2 = 8 };
 /* what device code assumes of constants it cannot see side by side (this unit includes both headers) */
 static_assert(sizeof(pcamv_mb_t) == 59 * 4, "p2_unit_load copies a record as 59 dwords: a field added to pcamv_mb_t truncates or misaligns the second pass' LDS copy");
 static_assert(4 * P2_LROW(8) <= P2_TW && 4 * P2_CROW(8) <= P2_CW, "a tile row of the longest run (8 macroblocks and the four columns left of it) no longer fits the tile's pitch");
+static_assert(SW_LDS_COLS == SP_LDS_COLS, "the writer's row buffer in LDS is the parsers' (one PCAMV_SLICE_LDS_COLS lowers both)");
 static_assert(FLOW_SPEC_MIN_MBW - 1 > FLOW_SPEC_AHEAD + 1, "speculative chain: a macroblock would be handed on before its top / top-right neighbours are final");
 
 /* The builds of the RD instance of the analysis kernel (one translation unit each, pcamv_rd.hip), a row per entry of
@@ -82,6 +83,10 @@ struct pcamv_batch {
     int *d_sstat; uint8_t *d_sp_tab, *d_sp_scratch;
     int sp_lds_cols;            /* pictures up to this many macroblocks wide keep the parser's row buffer in LDS (SP_LDS_COLS; PCAMV_SLICE_LDS_COLS lowers it) */
     uint8_t *h_stage[NSTAGE], *d_stage[NSTAGE]; size_t stage_cap[NSTAGE]; hipEvent_t stage_done[NSTAGE]; int stage_used[NSTAGE], stage_head;
+    /* sender to a stream (k_write_pslice): per-context status words, the tables, the row buffers of pictures too wide for LDS, and the
+     * staging of the callers' slice headers (pinned host and device, NSTAGE in turn) */
+    int *d_wstat; uint8_t *d_sw_tab, *d_sw_scratch;
+    uint8_t *h_wstage[NSTAGE], *d_wstage[NSTAGE]; size_t wstage_cap[NSTAGE]; hipEvent_t wstage_done[NSTAGE]; int wstage_used[NSTAGE], wstage_head;
     KTimer kt[KT_N];            /* the timed kernels; the events of a timer are made by its first launch */
     char err[256];
 };
@@ -235,6 +240,8 @@ extern "C" void pcamv_gpu_batch_destroy(pcamv_batch_t *b)
     hipFree(b->d_F); hipFree(b->d_E); hipFree(b->d_flow); hipFree(b->d_X); hipFree(b->d_chk);
     hipFree(b->d_sstat); hipFree(b->d_sp_tab); hipFree(b->d_sp_scratch);
     for (int k = 0; k < NSTAGE; k++) { if (b->h_stage[k]) hipHostFree(b->h_stage[k]); hipFree(b->d_stage[k]); if (b->stage_done[k]) hipEventDestroy(b->stage_done[k]); }
+    hipFree(b->d_wstat); hipFree(b->d_sw_tab); hipFree(b->d_sw_scratch);
+    for (int k = 0; k < NSTAGE; k++) { if (b->h_wstage[k]) hipHostFree(b->h_wstage[k]); hipFree(b->d_wstage[k]); if (b->wstage_done[k]) hipEventDestroy(b->wstage_done[k]); }
     ring_destroy(b->ring); ring_destroy(b->xring);
     for (KTimer &T : b->kt) kt_destroy(T);
     free(b->ctx);
@@ -376,7 +383,7 @@ static const char *dominant_kernel(const pcamv_batch *b)
 extern "C" const char *pcamv_gpu_batch_dominant_kernel(const pcamv_batch_t *b) { return dominant_kernel(b); }
 static const char *kt_name(const pcamv_batch *b, int k)      /* what pcamv_gpu_batch_kernel_time knows timer k by */
 {
-    static const char *const small[KT_N] = {NULL, "k_embed_prepare", "k_extract_prepare", "k_extract_bits", "k_payload_check", "k_parse_pslice", "k_parse_pslice_cavlc"};
+    static const char *const small[KT_N] = {NULL, "k_embed_prepare", "k_extract_prepare", "k_extract_bits", "k_payload_check", "k_parse_pslice", "k_parse_pslice_cavlc", "k_write_pslice"};
     return k == KT_ANALYSE ? dominant_kernel(b) : small[k];
 }
 extern "C" int pcamv_gpu_batch_copy_results_async(pcamv_batch_t *b, void *dst_mb, size_t mb_stride, void *dst_flip, size_t flip_stride, void *stream)
@@ -1353,6 +1360,206 @@ extern "C" int pcamv_gpu_batch_payload_check(pcamv_batch_t *b, int64_t *diff)
     static_assert(sizeof(long long) == sizeof(int64_t), "payload_check copies the counts as they are");
     HIPCHK(b, hipMemcpy(diff, b->d_chk, sizeof(int64_t) * b->n, hipMemcpyDeviceToHost));
     for (int i = 0; i < b->n; i++) { const int rc = rx_check(b->ctx[i], NULL); if (rc) return fail(b, rc, "context %d: %s", i, b->ctx[i]->err); }
+    return 0;
+}
+
+/* ------------------------------------------------------------------ sender to a stream (k_write_pslice, pcamv_slice.hip.h) */
+static int write_header_ok(const pcamv_slice_hdr_t *h)
+{
+    return h->n_bits >= 0 && h->n_bits <= (1 << 24) && (!h->n_bits || h->bits) && h->nal_ref_idc >= 0 && h->nal_ref_idc <= 3 && h->nal_unit_type >= 0 && h->nal_unit_type <= 31;
+}
+/* what every launch of the writer needs of the batch; the contexts' entropy mode is looked at before anything is set up */
+static int write_setup(pcamv_batch *b)
+{
+    for (int i = 0; i < b->n; i++) {
+        pcamv_ctx *c = b->ctx[i];
+        if (!c->F.b_cabac) return fail(b, PCAMV_EUNSUP, "context %d was opened with --no-cabac: the slice writer writes CABAC slices only (a CAVLC writer does not exist yet)", i);
+        if (!c->last) return fail(b, PCAMV_EINVAL, "context %d has analysed no frame yet: there is nothing to write", i);
+    }
+    const FrameDev &F = b->ctx[0]->F;
+    if (!b->d_wstat) HIPCHK(b, dalloc(&b->d_wstat, (size_t)b->n));
+    if (!b->d_sw_tab) {
+        uint8_t tab[SW_TAB_BYTES];
+        memcpy(tab + SW_TAB_INIT, pcamv_cabac_init_p, 2 * SW_NCTX); memcpy(tab + SW_TAB_TRANS, pcamv_cabac_transition, 256);
+        memcpy(tab + SW_TAB_RLPS, pcamv_cabac_range_lps, 512);
+        HIPCHK(b, dalloc(&b->d_sw_tab, (size_t)SW_TAB_BYTES));
+        HIPCHK(b, hipMemcpy(b->d_sw_tab, tab, sizeof(tab), hipMemcpyHostToDevice));
+    }
+    if (F.mb_w > b->sp_lds_cols && !b->d_sw_scratch) HIPCHK(b, dalloc(&b->d_sw_scratch, (size_t)b->n * SP_ROW_BYTES * F.mb_w));
+    return 0;
+}
+/* the callers' headers into the next staging buffer -- n_hdr entries of SW_HDR_WORDS words, then the bits of each at a multiple of
+ * 4 -- with one copy on `st`; *stage_out is released (write_stage_release) once the kernel that reads it is queued */
+static int write_stage(pcamv_batch *b, const pcamv_slice_hdr_t *hdrs, int n_hdr, hipStream_t st, const int **d_hdr, int *stage_out)
+{
+    static const pcamv_slice_hdr_t none = {NULL, 0, 0, 2, 1};
+    if (!hdrs) { hdrs = &none; n_hdr = 1; }
+    size_t total = (size_t)n_hdr * SW_HDR_WORDS * 4;
+    for (int i = 0; i < n_hdr; i++) {
+        if (!write_header_ok(&hdrs[i])) return fail(b, PCAMV_EINVAL, "slice header %d: bits missing, n_bits, nal_ref_idc or nal_unit_type out of range", i);
+        total += ((size_t)(hdrs[i].n_bits + 7) / 8 + 3) & ~(size_t)3;
+    }
+    const int k = b->wstage_head;
+    b->wstage_head = (k + 1) % NSTAGE;
+    if (!b->wstage_done[k]) HIPCHK(b, hipEventCreateWithFlags(&b->wstage_done[k], hipEventDisableTiming));
+    if (b->wstage_used[k]) HIPCHK(b, hipEventSynchronize(b->wstage_done[k]));
+    if (total > b->wstage_cap[k]) {
+        if (b->h_wstage[k]) hipHostFree(b->h_wstage[k]);
+        hipFree(b->d_wstage[k]); b->h_wstage[k] = NULL; b->d_wstage[k] = NULL; b->wstage_cap[k] = 0;
+        const size_t cap = total + total / 4;
+        HIPCHK(b, hipHostMalloc((void **)&b->h_wstage[k], cap, hipHostMallocDefault));
+        HIPCHK(b, dalloc(&b->d_wstage[k], cap));
+        b->wstage_cap[k] = cap;
+    }
+    uint8_t *h = b->h_wstage[k];
+    int *w = (int *)h;
+    size_t at = (size_t)n_hdr * SW_HDR_WORDS * 4;
+    for (int i = 0; i < n_hdr; i++) {
+        const size_t nb = (size_t)(hdrs[i].n_bits + 7) / 8;
+        w[SW_HDR_WORDS * i] = (int)at; w[SW_HDR_WORDS * i + 1] = hdrs[i].n_bits; w[SW_HDR_WORDS * i + 2] = hdrs[i].i_frame;
+        w[SW_HDR_WORDS * i + 3] = hdrs[i].nal_ref_idc << 5 | hdrs[i].nal_unit_type;
+        if (nb) memcpy(h + at, hdrs[i].bits, nb);
+        at += (nb + 3) & ~(size_t)3;
+    }
+    HIPCHK(b, hipMemcpyAsync(b->d_wstage[k], h, total, hipMemcpyHostToDevice, st));
+    HIPCHK(b, hipEventRecord(b->wstage_done[k], st));
+    b->wstage_used[k] = 1;
+    *d_hdr = (const int *)b->d_wstage[k]; *stage_out = k;
+    return 0;
+}
+static int write_stage_release(pcamv_batch *b, int k, hipStream_t st)
+{
+    HIPCHK(b, hipEventRecord(b->wstage_done[k], st));
+    b->wstage_used[k] = 1;
+    return 0;
+}
+/* one launch over the batch's contexts as they stand: J brings the destination and the mode */
+static int write_run(pcamv_batch *b, WriteJobs J, const pcamv_slice_hdr_t *hdrs, int n_hdr, hipStream_t st)
+{
+    const FrameDev &F0 = b->ctx[0]->F;
+    int k;
+    TRY(write_stage(b, hdrs, n_hdr, st, &J.hdr, &k));
+    J.n_hdr = hdrs ? n_hdr : 1;
+    J.status = b->d_wstat; J.tab = b->d_sw_tab; J.scratch = b->d_sw_scratch; J.scratch_stride = (long long)SP_ROW_BYTES * F0.mb_w;
+    J.lds_cols = b->sp_lds_cols;
+    const FrameDev *dF; const EmbedDev *dE; int slot;
+    int rc = batch_push_descs(b, st, &dF, &dE, &slot);
+    if (!rc) {
+        const int ev = kt_begin(b, KT_WRITE_PSLICE, st);
+        pcamv_launch_write_pslice((unsigned)b->n, st, dF, J);
+        kt_end(b, KT_WRITE_PSLICE, ev, st);
+        const hipError_t e = hipGetLastError();
+        rc = e != hipSuccess ? fail(b, PCAMV_EHIP, "kernel launch: %s", hipGetErrorString(e)) : ring_release(b, b->ring, slot, st);
+    }
+    const int rc2 = write_stage_release(b, k, st);                  /* released on every path */
+    return rc ? rc : rc2;
+}
+/* Every context's last step as a CABAC P slice, final motion (the records with the flip map of the step's embedding stage), from one
+ * launch on `stream`, no host synchronisation.
+ * Ordering is the caller's, as for pcamv_gpu_batch_extract_slices_device (the borrowed buffer and the three arrays belong to `stream`'s
+ * timeline), and the call belongs after the batch_step whose frame it writes and before the next one: the kernel reads that step's
+ * source planes (fenc), padded reference planes, records, flip map and carrier index.  Within a step the stages run in the order
+ * planes, analysis, embedding, second pass (batch_launch); the analysis writes records, reconstruction and motion field, the
+ * embedding the flip map, the second pass reconstruction, motion field and non-zero flags in place -- none of which the writer reads
+ * but the records and the flip map, both complete when the step is.  The first thing of the NEXT step to overwrite anything read here is
+ * its plane stage (k_hpel / k_chroma_pad: the padded planes), then its analysis (the records); the source planes are the caller's and
+ * stay until the caller replaces them. */
+extern "C" int pcamv_gpu_batch_write_step(pcamv_batch_t *b, const pcamv_slice_hdr_t *hdrs, int n_hdr, int as_nal, void *bytes, size_t bytes_size,
+                                          const int64_t *off, const int64_t *cap, int64_t *len, void *stream)
+{
+    if (!b || !bytes || !off || !cap || !len || bytes_size > ((size_t)1 << 62)) return PCAMV_EINVAL;
+    if (hdrs ? (n_hdr != 1 && n_hdr != b->n) : n_hdr != 0) return fail(b, PCAMV_EINVAL, "n_hdr is 1 or the batch size (0 with no header)");
+    HIPCHK(b, hipSetDevice(b->device));
+    TRY(batch_live(b));
+    TRY(write_setup(b));
+    static_assert(sizeof(long long) == sizeof(int64_t), "the caller's int64 arrays are read as they are");
+    WriteJobs J = {};
+    J.bytes = (uint8_t *)bytes; J.bytes_size = (long long)bytes_size;
+    J.off = (const long long *)off; J.cap = (const long long *)cap; J.len = (long long *)len;
+    J.mbs = NULL; J.as_nal = as_nal != 0; J.final = 1;
+    return write_run(b, J, hdrs, n_hdr, stream ? (hipStream_t)stream : b->ctx[0]->stream);
+}
+/* synchronises; status[i] = return code of context i's slice in the last write call (0 or PCAMV_ENOMEM; PCAMV_EINVAL for a place
+ * outside the buffer) */
+extern "C" int pcamv_gpu_batch_write_status(pcamv_batch_t *b, int32_t *status)
+{
+    if (!b || !status) return PCAMV_EINVAL;
+    HIPCHK(b, hipSetDevice(b->device));
+    if (!b->d_wstat) return fail(b, PCAMV_EINVAL, "this batch has written no slices yet");
+    HIPCHK(b, hipDeviceSynchronize());
+    HIPCHK(b, hipMemcpy(status, b->d_wstat, sizeof(int32_t) * b->n, hipMemcpyDeviceToHost));
+    return 0;
+}
+/* A capacity under which no slice of the context's picture size fails: SW_MB_BOUND bytes per macroblock (derived in
+ * pcamv_slice_write.h from the most bits a decision, a level and an mvd can take), the header's bytes, the flush; as a NAL unit
+ * start code and header byte, and one emulation prevention byte for every two bytes of RBSP at the worst (each takes two zeros
+ * before it and resets the count). */
+extern "C" int64_t pcamv_gpu_slice_bound(const pcamv_ctx_t *c, int32_t hdr_bits, int as_nal)
+{
+    if (!c || hdr_bits < 0) return PCAMV_EINVAL;
+    const int64_t rbsp = (int64_t)SW_MB_BOUND * c->F.n_mb + (hdr_bits + 7) / 8 + SW_TAIL_BOUND;
+    return as_nal ? 5 + rbsp + rbsp / 2 + 1 : rbsp;
+}
+/* the parity probe: one slice of the context's last frame (mbs == NULL; final: with the embedding stage's flip map) or of uploaded
+ * records that hold final motion, written on the device, copied back.  Synchronises. */
+extern "C" int pcamv_gpu_write_pslice(pcamv_ctx_t *c, const pcamv_slice_hdr_t *hdr, int final, const pcamv_mb_t *mbs, int as_nal, uint8_t *out, size_t cap,
+                                      size_t *len)
+{
+    if (!c || !out || !len || cap > ((size_t)1 << 40)) return PCAMV_EINVAL;
+    *len = 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    pcamv_batch *b = c->self;
+    TRY(on_behalf(c, b, batch_live(b)));
+    TRY(on_behalf(c, b, write_setup(b)));
+    if (mbs) {
+        TRY(rx_mbs(c));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipMemcpy(c->d_rx_mbs, mbs, (size_t)c->F.n_mb * sizeof(pcamv_mb_t), hipMemcpyHostToDevice));
+    }
+    uint8_t *d_out = NULL;
+    const size_t arr = 3 * sizeof(long long);
+    HIPCHK(c, hipMalloc((void **)&d_out, arr + (cap ? cap : 1)));
+    const long long h_arr[3] = {0, (long long)cap, 0};
+    int rc = 0, st = 0;
+    long long n = 0;
+    hipError_t e = hipMemcpy(d_out, h_arr, arr, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        WriteJobs J = {};
+        J.bytes = d_out + arr; J.bytes_size = (long long)cap;
+        J.off = (const long long *)d_out; J.cap = J.off + 1; J.len = (long long *)d_out + 2;
+        J.mbs = mbs ? c->d_rx_mbs : NULL; J.as_nal = as_nal != 0; J.final = final != 0;
+        rc = on_behalf(c, b, write_run(b, J, hdr, hdr ? 1 : 0, c->stream));
+        if (!rc) e = hipStreamSynchronize(c->stream);
+        if (!rc && e == hipSuccess) e = hipMemcpy(&st, b->d_wstat, sizeof(st), hipMemcpyDeviceToHost);
+        if (!rc && e == hipSuccess) e = hipMemcpy(&n, d_out + 2 * sizeof(long long), sizeof(n), hipMemcpyDeviceToHost);
+        if (!rc && e == hipSuccess && !st && n >= 0 && (size_t)n <= cap && n) e = hipMemcpy(out, d_out + arr, (size_t)n, hipMemcpyDeviceToHost);
+    }
+    hipFree(d_out);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(c, PCAMV_EHIP, "write_pslice: %s", hipGetErrorString(e));
+    if (st) return fail(c, st, st == PCAMV_ENOMEM ? "the slice does not fit %zu bytes (pcamv_gpu_slice_bound gives a capacity that always does)" :
+                        "the records are no P macroblocks of this path (type, partition or sub-partition out of range)", cap);
+    if (n < 0 || (size_t)n > cap) return fail(c, PCAMV_EHIP, "write_pslice: length corrupt");
+    *len = (size_t)n;
+    return 0;
+}
+/* the inverse of pcamv_gpu_nal_to_rbsp, as x264_nal_encode writes a unit (common/common.c:658-695): long start code, header byte, the
+ * RBSP with an emulation prevention byte before every byte <= 3 that follows two zeros.  Host code. */
+extern "C" int pcamv_gpu_rbsp_to_nal(const uint8_t *rbsp, size_t len, int nal_ref_idc, int nal_unit_type, uint8_t *nal, size_t cap, size_t *nal_len)
+{
+    if ((!rbsp && len) || !nal || !nal_len || nal_ref_idc < 0 || nal_ref_idc > 3 || nal_unit_type < 0 || nal_unit_type > 31) return PCAMV_EINVAL;
+    size_t n = 0;
+    int zeros = 0;
+    const uint8_t head[5] = {0, 0, 0, 1, (uint8_t)(nal_ref_idc << 5 | nal_unit_type)};
+    *nal_len = 0;
+    for (int i = 0; i < 5; i++) { if (n >= cap) return PCAMV_ENOMEM; nal[n++] = head[i]; }
+    for (size_t i = 0; i < len; i++) {
+        if (zeros == 2 && rbsp[i] <= 3) { if (n >= cap) return PCAMV_ENOMEM; nal[n++] = 3; zeros = 0; }
+        zeros = rbsp[i] == 0 ? zeros + 1 : 0;
+        if (n >= cap) return PCAMV_ENOMEM;
+        nal[n++] = rbsp[i];
+    }
+    *nal_len = n;
     return 0;
 }
 

@@ -15,12 +15,16 @@
  * k_parse_pslice_cavlc is the same for --no-cabac streams (pcamv_slice_parse_cavlc.h).  A CAVLC slice has no context states and
  * no arithmetic decoder: the wave keeps the byte window, the VLC tables (one 16-bit entry per code), the macroblock cache and a row
  * buffer of 24 bytes per column -- 5044 bytes, so that LDS admits the 32 waves per CU the registers do.
+ *
+ * k_write_pslice (pcamv_slice_write.hip) is the other direction: a CABAC P slice of every context's last step written on the device, one
+ * wavefront per slice (pcamv_slice_write.h, which also describes a launch: WriteJobs).
  */
 #ifndef PCAMV_SLICE_HIP_H
 #define PCAMV_SLICE_HIP_H
 #include "pcamv_embed.hip.h"
 #include "pcamv_slice_parse.h"
 #include "pcamv_slice_parse_cavlc.h"
+#include "pcamv_slice_write.h"
 
 #define SP_LDS_COLS 128
 
@@ -80,4 +84,7 @@ static __global__ void __launch_bounds__(64) k_parse_pslice_cavlc(const ExtractD
         rc = pcamv_slice_parse_cavlc(S, J.bytes + off, len, J.start_bit[i], J.mb_w, J.mb_h, (pcamv_mb_t *)X.mbs);
     if (lane == 0) *X.slice_status = rc;
 }
+/* the writer's kernel is a unit of its own (pcamv_slice_write.hip): it inlines the analysis' prediction and transform primitives, and what
+ * the compiler makes of the kernels of this unit depends on what else in the unit calls them */
+void pcamv_launch_write_pslice(unsigned slices, hipStream_t st, const FrameDev *dF, const WriteJobs &J);
 #endif

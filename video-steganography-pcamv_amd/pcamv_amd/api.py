@@ -132,8 +132,8 @@ def lib_path():
 
 
 # the library's translation units (csrc/<unit>.hip): the host side with the common kernels, the --me tesa instance of the analysis kernel,
-# the per-diagonal second pass, and the six builds of the analysis kernel's --subme 6 / 7 instance
-UNITS = ("pcamv_gpu", "pcamv_pass2_diag", "pcamv_tesa", "pcamv_rd", "pcamv_rd_lo", "pcamv_rd_spec", "pcamv_rd_spec2", "pcamv_rd_spec4", "pcamv_rd_tesa")
+# the per-diagonal second pass, the slice writer, and the six builds of the analysis kernel's --subme 6 / 7 instance
+UNITS = ("pcamv_gpu", "pcamv_pass2_diag", "pcamv_slice_write", "pcamv_tesa", "pcamv_rd", "pcamv_rd_lo", "pcamv_rd_spec", "pcamv_rd_spec2", "pcamv_rd_spec4", "pcamv_rd_tesa")
 
 
 def build_library(force=False):
@@ -216,6 +216,33 @@ def nal_to_rbsp(nal):
     return out[:n.value].tobytes(), ref_idc.value, typ.value
 
 
+def rbsp_to_nal(rbsp, nal_ref_idc=2, nal_unit_type=1):
+    """pcamv_gpu_rbsp_to_nal: the NAL unit of an RBSP as x264_nal_encode writes it (long start code, header byte, emulation
+    prevention); the inverse of nal_to_rbsp"""
+    data = np.frombuffer(bytes(rbsp), np.uint8)
+    out = np.zeros(5 + len(data) + len(data) // 2 + 1, np.uint8)
+    n = C.c_size_t()
+    lib = load_library()
+    lib.pcamv_gpu_rbsp_to_nal.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    rc = lib.pcamv_gpu_rbsp_to_nal(_p(data) if len(data) else None, len(data), nal_ref_idc, nal_unit_type, _p(out), len(out), C.byref(n))
+    if rc:
+        raise PcamvError(f"pcamv_gpu_rbsp_to_nal failed: {rc}")
+    return out[:n.value].tobytes()
+
+
+class _SliceHdr(C.Structure):
+    _fields_ = [("bits", C.c_void_p), ("n_bits", C.c_int32), ("i_frame", C.c_int32), ("nal_ref_idc", C.c_int32), ("nal_unit_type", C.c_int32)]
+
+
+def _slice_hdr(hdr):
+    """pcamv_slice_hdr_t of a header given as a sequence of bits, or as dict(bits=..., i_frame=0, nal_ref_idc=2, nal_unit_type=1);
+    returns (struct, the array that keeps its bits alive)"""
+    d = hdr if isinstance(hdr, dict) else dict(bits=hdr)
+    bits = np.asarray(d.get("bits", ()), np.uint8)
+    packed = np.packbits(bits & 1, bitorder="big") if len(bits) else np.zeros(1, np.uint8)
+    return _SliceHdr(packed.ctypes.data, len(bits), int(d.get("i_frame", 0)), int(d.get("nal_ref_idc", 2)), int(d.get("nal_unit_type", 1))), packed
+
+
 def parse_pslice_at(rbsp, start_bit, mb_w, mb_h, qp=None):
     """pcamv_gpu_parse_pslice_cabac_at (qp given) / _cavlc_at: the slice data behind a slice header that ends at bit start_bit of the RBSP"""
     data = np.frombuffer(bytes(rbsp), np.uint8)
@@ -253,6 +280,7 @@ def stc_extract(stego, m, height=10, lcg=None):
 FEATURE_PAYLOAD = 0x1
 FEATURE_SLICE_PARSER = 0x2      # CABAC P slices parsed on the device: Encoder.parse_pslice_device, Batch.extract_slices
 FEATURE_SLICE_PARSER_CAVLC = 0x4    # CAVLC P slices too: Encoder.parse_pslice_cavlc_device, Batch.extract_slices_cavlc
+FEATURE_SLICE_WRITER = 0x8      # CABAC P slices written on the device: Encoder.write_pslice, Batch.write_step
 
 
 def features():
@@ -451,6 +479,36 @@ class Encoder:
         self._chk(self.lib.pcamv_gpu_parse_pslice_cavlc_device(self.ctx, _p(data), len(rbsp), hdr_bits, _p(mbs)), "parse_pslice_cavlc_device")
         return mbs
 
+    def slice_bound(self, hdr_bits=0, as_nal=False):
+        """pcamv_gpu_slice_bound: a capacity under which no slice of this picture size fails to be written"""
+        self.lib.pcamv_gpu_slice_bound.restype = C.c_int64
+        self.lib.pcamv_gpu_slice_bound.argtypes = [C.c_void_p, C.c_int32, C.c_int]
+        n = self.lib.pcamv_gpu_slice_bound(self.ctx, int(hdr_bits), int(as_nal))
+        if n < 0:
+            raise PcamvError(f"slice_bound failed ({n})")
+        return int(n)
+
+    def write_pslice(self, hdr=None, final=True, mbs=None, as_nal=False, cap=None):
+        """pcamv_gpu_write_pslice: the CABAC P slice of this context's last frame written on the device by k_write_pslice, as bytes --
+        final=True with the embedding stage's flip map (the motion the second pass reconstructed), final=False the first-pass
+        records as they are; mbs: host records that hold final motion instead (type, partition, sub-partition and mv are read).
+        hdr: the slice header's bits (a sequence, or dict(bits, i_frame, nal_ref_idc, nal_unit_type)), behind which come the
+        alignment ones and the slice data; none: the bare slice data.  as_nal: the NAL unit with start code and emulation
+        prevention.  cap: the capacity offered (default: slice_bound); a slice that does not fit raises (-3)"""
+        h, keep = _slice_hdr(hdr if hdr is not None else ())
+        if cap is None:
+            cap = self.slice_bound(h.n_bits, as_nal)
+        if mbs is not None:
+            mbs = np.ascontiguousarray(mbs, MB_DTYPE)
+            if len(mbs) != self.n_mb:
+                raise PcamvError(f"{len(mbs)} records for a picture of {self.n_mb} macroblocks")
+        out = np.zeros(max(int(cap), 1), np.uint8)
+        n = C.c_size_t()
+        self.lib.pcamv_gpu_write_pslice.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        self._chk(self.lib.pcamv_gpu_write_pslice(self.ctx, C.byref(h) if hdr is not None else None, int(bool(final)), _p(mbs), int(bool(as_nal)), _p(out), int(cap),
+                                                  C.byref(n)), "write_pslice")
+        return out[:n.value].tobytes()
+
     def slice_records(self):
         """diagnostics: (the records this context's last slice parsed to on the device, whether the guard behind them is intact)"""
         mbs = np.zeros(self.n_mb, MB_DTYPE)
@@ -645,6 +703,33 @@ class Batch:
         self.lib.pcamv_gpu_batch_extract_slices_cavlc_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
         self._slice_chk(self.lib.pcamv_gpu_batch_extract_slices_cavlc_device(self.b, data.data_ptr(), data.numel(), off.data_ptr(), length.data_ptr(), hdr_bits.data_ptr(),
                                                                              emrate, C.c_void_p(stream or None)), "batch_extract_slices_cavlc_device")
+
+    def write_step(self, hdr, data, off, cap, length, as_nal=False, stream=0):
+        """pcamv_gpu_batch_write_step: every context's last step written as a CABAC P slice (final motion) by one launch of
+        k_write_pslice, without a host sync.  hdr: None, one header for all contexts or a list of one per context (as for
+        Encoder.write_pslice).  `data` a contiguous uint8 device tensor (borrowed), off / cap (in) and length (out) int64 device
+        tensors of one entry per context: slice i goes to data[off[i] : off[i] + cap[i]] and is length[i] long; one that does not
+        fit gets length 0 and write_status() -3.  With as_nal=False (data, off, length) is what extract_slices_device takes.
+        Ordering is the caller's, as for extract_slices_device; the call belongs after the step it writes and before the next"""
+        for t, size, what in ((data, 1, "data: uint8"), (off, 8, "off: int64"), (cap, 8, "cap: int64"), (length, 8, "length: int64")):
+            if not _is_device_tensor(t) or not t.is_cuda or t.element_size() != size or not t.is_contiguous():
+                raise PcamvError(f"{what}, contiguous, on the device")
+        if any(t.numel() != len(self.encs) for t in (off, cap, length)):
+            raise PcamvError(f"one entry per context ({len(self.encs)}) in off / cap / length")
+        hdrs = [] if hdr is None else list(hdr) if isinstance(hdr, list) and hdr and isinstance(hdr[0], (dict, list, tuple, np.ndarray)) else [hdr]
+        if len(hdrs) not in (0, 1, len(self.encs)):
+            raise PcamvError(f"{len(hdrs)} headers for a batch of {len(self.encs)} contexts (none, one, or one each)")
+        made = [_slice_hdr(h) for h in hdrs]
+        arr = (_SliceHdr * max(len(made), 1))(*[m[0] for m in made])
+        self.lib.pcamv_gpu_batch_write_step.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._slice_chk(self.lib.pcamv_gpu_batch_write_step(self.b, arr if made else None, len(made), int(bool(as_nal)), data.data_ptr(), data.numel(), off.data_ptr(),
+                                                            cap.data_ptr(), length.data_ptr(), C.c_void_p(stream or None)), "batch_write_step")
+
+    def write_status(self):
+        """per context: 0, or -3 where its slice of the last write_step did not fit its capacity; synchronises"""
+        out = np.zeros(len(self.encs), np.int32)
+        self._slice_chk(self.lib.pcamv_gpu_batch_write_status(self.b, _p(out)), "batch_write_status")
+        return out
 
     def slice_status(self):
         """per context: the parser's code for its slice of the last extract_slices call (0, -1 invalid, -5 unsupported); synchronises"""
