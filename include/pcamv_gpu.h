@@ -30,7 +30,8 @@
  *   pcamv_gpu_*_slices*,        (no reference counterpart) the receiver fed from stream bytes: CABAC and CAVLC P slices parsed on
  *   parse_pslice_*_device       the device, one wavefront per slice (k_parse_pslice, k_parse_pslice_cavlc), straight into the extractor
  *   pcamv_gpu_*write_*          the second pass' x264_macroblock_write_cabac + x264_cabac_encode_flush (encoder/cabac.c:781, common/cabac.c:908)
- *                               and x264_nal_encode (common/common.c:658): the P slice of a step written on the device (k_write_pslice)
+ *                               and x264_nal_encode (common/common.c:658): the P slice of a step written on the device (k_write_pslice);
+ *                               the *_cavlc calls x264_macroblock_write_cavlc (encoder/cavlc.c:288) instead (k_write_pslice_cavlc)
  *   pcamv_gpu_close             x264_encoder_close's frees
  *
  * All functions return 0 on success and a negative PCAMV_E* code on error; the message is
@@ -286,6 +287,7 @@ int pcamv_gpu_abi_version(void);
 #define PCAMV_FEATURE_SLICE_PARSER 0x2u /* CABAC P slices parsed on the device (the receiver from a stream, at the end of this file) */
 #define PCAMV_FEATURE_SLICE_PARSER_CAVLC 0x4u   /* ... and CAVLC P slices (the *_cavlc calls there) */
 #define PCAMV_FEATURE_SLICE_WRITER 0x8u /* CABAC P slices written on the device (the sender to a stream, at the end of this file) */
+#define PCAMV_FEATURE_SLICE_WRITER_CAVLC 0x10u  /* ... and CAVLC P slices (the *_cavlc calls there) */
 unsigned pcamv_gpu_features(void);
 
 /* ---- Payload path: the caller's bits through the device-resident entry points, and back out on the device ----
@@ -417,6 +419,15 @@ int pcamv_gpu_batch_write_step(pcamv_batch_t *batch, const pcamv_slice_hdr_t *hd
 int pcamv_gpu_batch_write_status(pcamv_batch_t *batch, int32_t *status);
 /* a capacity under which no slice of the context's picture size fails, for a header of hdr_bits bits, as RBSP or as a NAL unit */
 int64_t pcamv_gpu_slice_bound(const pcamv_ctx_t *ctx, int32_t hdr_bits, int as_nal);
+/* The same for contexts opened with --no-cabac (b_cabac = 0): CAVLC P slices, written by k_write_pslice_cavlc.  The slice data
+ * follows the header's last bit directly (CAVLC has no alignment bits), hdr's i_frame is not read, and with as_nal = 0 the batch
+ * call's (bytes, off, len) and the header's bit count are what pcamv_gpu_batch_extract_slices_cavlc_device takes as (bytes, off, len,
+ * start_bit).  pcamv_gpu_batch_write_status and pcamv_gpu_slice_bound serve both modes.  Each pair of calls refuses the other entropy
+ * mode's contexts with PCAMV_EUNSUP. */
+int pcamv_gpu_write_pslice_cavlc(pcamv_ctx_t *ctx, const pcamv_slice_hdr_t *hdr, int final, const pcamv_mb_t *mbs, int as_nal, uint8_t *out, size_t cap,
+                                 size_t *len);
+int pcamv_gpu_batch_write_step_cavlc(pcamv_batch_t *batch, const pcamv_slice_hdr_t *hdrs, int n_hdr, int as_nal, void *bytes, size_t bytes_size,
+                                     const int64_t *off, const int64_t *cap, int64_t *len, void *stream);
 /* Host code, the inverse of pcamv_gpu_nal_to_rbsp: long start code, header byte, the RBSP with emulation prevention bytes as
  * x264_nal_encode inserts them (common/common.c:658-695).  nal[cap] receives *nal_len bytes (at most 5 + len + len / 2 + 1). */
 int pcamv_gpu_rbsp_to_nal(const uint8_t *rbsp, size_t len, int nal_ref_idc, int nal_unit_type, uint8_t *nal, size_t cap, size_t *nal_len);

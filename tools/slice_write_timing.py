@@ -3,10 +3,12 @@ CIF chains (--me hex --subme 6, QP 26, half a bit per carrier) with 1, 64, 1024 
 workload -- 1920x1088, --me umh --subme 7, QP 26, 64 content classes -- at 256 chains.  For every point: k_write_pslice alone
 (hipEvents around the launch, pcamv_gpu_batch_kernel_time), slices/s and macroblocks/s, bytes per slice, and beside it the same
 batch's step (host clock around Batch.step + synchronisation, the benchmark's way) with the writer's share of it.  Every written
-slice is checked by the device parser's status through Batch.extract_slices_device.  Prints one JSON line and writes it to --out.
+slice is checked by the device parser's status through Batch.extract_slices_device.  --cavlc: the same chains opened with
+--no-cabac, written by k_write_pslice_cavlc and checked through Batch.extract_slices_cavlc_device.  Prints one JSON line and keeps
+it in --out under the key of its entropy mode ("cabac" / "cavlc"), beside the other mode's last run.
 Needs a GPU.
 
-    python tools/slice_write_timing.py [--counts 1,64,1024,4096] [--hd-chains 256] [--reps 3] [--out profiles/slice_write_timing.json]
+    python tools/slice_write_timing.py [--cavlc] [--counts 1,64,1024,4096] [--hd-chains 256] [--reps 3] [--out profiles/slice_write_timing.json]
 """
 import argparse
 import json
@@ -25,7 +27,7 @@ def tri(i, n):
     return i if i < n else period - i
 
 
-def point(pcamv_amd, torch, np, W, H, me, subme, qp, n, reps, classes):
+def point(pcamv_amd, torch, np, W, H, me, subme, qp, n, reps, classes, cavlc):
     from pcamv_amd.synth import make_clip
     dev = torch.device("cuda", 0)
     nfr = max(classes, reps + 3)
@@ -34,6 +36,8 @@ def point(pcamv_amd, torch, np, W, H, me, subme, qp, n, reps, classes):
     p = pcamv_amd.param_default(W, H)
     pcamv_amd.param_parse(p, "me", me)
     pcamv_amd.param_parse(p, "subme", subme)
+    p.b_cabac = 0 if cavlc else 1
+    kernel = "k_write_pslice_cavlc" if cavlc else "k_write_pslice"
     encs = [pcamv_amd.Encoder(p) for _ in range(n)]
     n_mb = encs[0].n_mb
     for e in encs:
@@ -66,11 +70,15 @@ def point(pcamv_amd, torch, np, W, H, me, subme, qp, n, reps, classes):
         torch.cuda.synchronize()
         if t:
             step_s.append(time.perf_counter() - w0)
-        batch.write_step(None, data, off, cap, length, as_nal=False, stream=0)
-        batch.extract_slices_device(data, off, length, zero, qps, 0.5, 0)
+        if cavlc:
+            batch.write_step_cavlc(None, data, off, cap, length, as_nal=False, stream=0)
+            batch.extract_slices_cavlc_device(data, off, length, zero, 0.5, 0)
+        else:
+            batch.write_step(None, data, off, cap, length, as_nal=False, stream=0)
+            batch.extract_slices_device(data, off, length, zero, qps, 0.5, 0)
         if not t:
-            batch.kernel_time("k_write_pslice", reset=True)
-    ms, launches = batch.kernel_time("k_write_pslice", reset=True)
+            batch.kernel_time(kernel, reset=True)
+    ms, launches = batch.kernel_time(kernel, reset=True)
     if (batch.write_status() != 0).any() or (batch.slice_status() != 0).any() or launches != reps:
         sys.exit("slice_write_timing.py: a slice did not fit %d bytes per macroblock, or did not parse" % BYTES_PER_MB)
     lens = length.cpu().numpy()
@@ -86,6 +94,7 @@ def point(pcamv_amd, torch, np, W, H, me, subme, qp, n, reps, classes):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--cavlc", action="store_true", help="--no-cabac chains: k_write_pslice_cavlc")
     ap.add_argument("--counts", default="1,64,1024,4096", help="CIF slices in flight ('' = skip)")
     ap.add_argument("--hd-chains", type=int, default=256, help="chains of the benchmark's 1080p workload (0 = skip)")
     ap.add_argument("--reps", type=int, default=3)
@@ -97,17 +106,23 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("slice_write_timing.py needs a GPU: the HIP path has no CPU fallback")
     torch.cuda.init()
-    out = dict(kernel="k_write_pslice", reps=args.reps, capacity_bytes_per_mb=BYTES_PER_MB, cif=[], hd=None)
+    out = dict(kernel="k_write_pslice_cavlc" if args.cavlc else "k_write_pslice", reps=args.reps, capacity_bytes_per_mb=BYTES_PER_MB, cif=[], hd=None)
     for n in [int(v) for v in args.counts.split(",") if v]:
-        out["cif"].append(point(pcamv_amd, torch, np, 352, 288, "hex", 6, 26, n, args.reps, 16))
+        out["cif"].append(point(pcamv_amd, torch, np, 352, 288, "hex", 6, 26, n, args.reps, 16, args.cavlc))
         print(json.dumps(out["cif"][-1]), flush=True)
     if args.hd_chains:
-        out["hd"] = point(pcamv_amd, torch, np, 1920, 1088, "umh", 7, 26, args.hd_chains, args.reps, 64)
-    line = json.dumps(out)
-    print(line)
+        out["hd"] = point(pcamv_amd, torch, np, 1920, 1088, "umh", 7, 26, args.hd_chains, args.reps, 64, args.cavlc)
+    print(json.dumps(out))
     if args.out:
+        both = {}
+        if os.path.exists(args.out):
+            with open(args.out) as f:
+                both = json.load(f)
+            if "kernel" in both:                        # a file of before the modes had keys: one CABAC run
+                both = {"cabac": both}
+        both["cavlc" if args.cavlc else "cabac"] = out
         with open(args.out, "w") as f:
-            f.write(line + "\n")
+            f.write(json.dumps(both) + "\n")
 
 
 if __name__ == "__main__":

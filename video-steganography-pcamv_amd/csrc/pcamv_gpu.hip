@@ -23,8 +23,9 @@
 #define NEV 32                 /* launches the analysis kernel's timer remembers between two kernel_time calls ... */
 #define NRING 8
 #define NKEV 16                /* ... and a timer of the smaller kernels */
-enum { KT_ANALYSE, KT_EMBED_PREPARE, KT_EXTRACT_PREPARE, KT_EXTRACT_BITS, KT_PAYLOAD_CHECK, KT_PARSE_PSLICE, KT_PARSE_PSLICE_CAVLC, KT_WRITE_PSLICE, KT_N };
-#define PCAMV_FEATURES (PCAMV_FEATURE_PAYLOAD | PCAMV_FEATURE_SLICE_PARSER | PCAMV_FEATURE_SLICE_PARSER_CAVLC | PCAMV_FEATURE_SLICE_WRITER)
+enum { KT_ANALYSE, KT_EMBED_PREPARE, KT_EXTRACT_PREPARE, KT_EXTRACT_BITS, KT_PAYLOAD_CHECK, KT_PARSE_PSLICE, KT_PARSE_PSLICE_CAVLC, KT_WRITE_PSLICE, KT_WRITE_PSLICE_CAVLC, KT_N };
+#define PCAMV_FEATURES (PCAMV_FEATURE_PAYLOAD | PCAMV_FEATURE_SLICE_PARSER | PCAMV_FEATURE_SLICE_PARSER_CAVLC | PCAMV_FEATURE_SLICE_WRITER | \
+                        PCAMV_FEATURE_SLICE_WRITER_CAVLC)
 #define SLICE_GUARD_MBS 4       /* records behind a context's receive-side records that nothing may write (pcamv_gpu_debug_slice_records) */
 #define NSTAGE 2                /* staging buffers of extract_slices: a call waits for the one before the last */
 /* the stages of a step (batch_launch's `what`): plane production, analysis (search + RCA + encode), embedding, second pass */
@@ -383,7 +384,8 @@ static const char *dominant_kernel(const pcamv_batch *b)
 extern "C" const char *pcamv_gpu_batch_dominant_kernel(const pcamv_batch_t *b) { return dominant_kernel(b); }
 static const char *kt_name(const pcamv_batch *b, int k)      /* what pcamv_gpu_batch_kernel_time knows timer k by */
 {
-    static const char *const small[KT_N] = {NULL, "k_embed_prepare", "k_extract_prepare", "k_extract_bits", "k_payload_check", "k_parse_pslice", "k_parse_pslice_cavlc", "k_write_pslice"};
+    static const char *const small[KT_N] = {NULL, "k_embed_prepare", "k_extract_prepare", "k_extract_bits", "k_payload_check", "k_parse_pslice", "k_parse_pslice_cavlc", "k_write_pslice",
+                                            "k_write_pslice_cavlc"};
     return k == KT_ANALYSE ? dominant_kernel(b) : small[k];
 }
 extern "C" int pcamv_gpu_batch_copy_results_async(pcamv_batch_t *b, void *dst_mb, size_t mb_stride, void *dst_flip, size_t flip_stride, void *stream)
@@ -1363,21 +1365,29 @@ extern "C" int pcamv_gpu_batch_payload_check(pcamv_batch_t *b, int64_t *diff)
     return 0;
 }
 
-/* ------------------------------------------------------------------ sender to a stream (k_write_pslice, pcamv_slice.hip.h) */
+/* ------------------------------------------------------------------ sender to a stream (k_write_pslice, k_write_pslice_cavlc; pcamv_slice.hip.h) */
 static int write_header_ok(const pcamv_slice_hdr_t *h)
 {
     return h->n_bits >= 0 && h->n_bits <= (1 << 24) && (!h->n_bits || h->bits) && h->nal_ref_idc >= 0 && h->nal_ref_idc <= 3 && h->nal_unit_type >= 0 && h->nal_unit_type <= 31;
 }
-/* what every launch of the writer needs of the batch; the contexts' entropy mode is looked at before anything is set up */
-static int write_setup(pcamv_batch *b)
+/* What every launch of a writer needs of the batch.  The stream's entropy mode is stated by the call (cavlc = 0 / 1) and has to be the
+ * contexts' (a batch is of one mode): looked at before anything is set up. */
+static int write_setup(pcamv_batch *b, int cavlc)
 {
     for (int i = 0; i < b->n; i++) {
         pcamv_ctx *c = b->ctx[i];
-        if (!c->F.b_cabac) return fail(b, PCAMV_EUNSUP, "context %d was opened with --no-cabac: the slice writer writes CABAC slices only (a CAVLC writer does not exist yet)", i);
+        if (!cavlc && !c->F.b_cabac) return fail(b, PCAMV_EUNSUP, "context %d was opened with --no-cabac: its slices are CAVLC, which pcamv_gpu_write_pslice_cavlc and pcamv_gpu_batch_write_step_cavlc write", i);
+        if (cavlc && c->F.b_cabac) return fail(b, PCAMV_EUNSUP, "context %d was opened with CABAC: its slices are CABAC, which pcamv_gpu_write_pslice and pcamv_gpu_batch_write_step write", i);
         if (!c->last) return fail(b, PCAMV_EINVAL, "context %d has analysed no frame yet: there is nothing to write", i);
     }
     const FrameDev &F = b->ctx[0]->F;
     if (!b->d_wstat) HIPCHK(b, dalloc(&b->d_wstat, (size_t)b->n));
+    if (!b->d_sw_tab && cavlc) {
+        uint8_t tab[SV_TAB_BYTES];
+        if (sv_build_tables(tab)) return fail(b, PCAMV_EINVAL, "a CAVLC code of pcamv_entropy_tables.h does not fit the table entry");
+        HIPCHK(b, dalloc(&b->d_sw_tab, (size_t)SV_TAB_BYTES));
+        HIPCHK(b, hipMemcpy(b->d_sw_tab, tab, sizeof(tab), hipMemcpyHostToDevice));
+    }
     if (!b->d_sw_tab) {
         uint8_t tab[SW_TAB_BYTES];
         memcpy(tab + SW_TAB_INIT, pcamv_cabac_init_p, 2 * SW_NCTX); memcpy(tab + SW_TAB_TRANS, pcamv_cabac_transition, 256);
@@ -1385,7 +1395,7 @@ static int write_setup(pcamv_batch *b)
         HIPCHK(b, dalloc(&b->d_sw_tab, (size_t)SW_TAB_BYTES));
         HIPCHK(b, hipMemcpy(b->d_sw_tab, tab, sizeof(tab), hipMemcpyHostToDevice));
     }
-    if (F.mb_w > b->sp_lds_cols && !b->d_sw_scratch) HIPCHK(b, dalloc(&b->d_sw_scratch, (size_t)b->n * SP_ROW_BYTES * F.mb_w));
+    if (F.mb_w > b->sp_lds_cols && !b->d_sw_scratch) HIPCHK(b, dalloc(&b->d_sw_scratch, (size_t)b->n * (cavlc ? SV_ROW_BYTES : SP_ROW_BYTES) * F.mb_w));
     return 0;
 }
 /* the callers' headers into the next staging buffer -- n_hdr entries of SW_HDR_WORDS words, then the bits of each at a multiple of
@@ -1434,27 +1444,29 @@ static int write_stage_release(pcamv_batch *b, int k, hipStream_t st)
     return 0;
 }
 /* one launch over the batch's contexts as they stand: J brings the destination and the mode */
-static int write_run(pcamv_batch *b, WriteJobs J, const pcamv_slice_hdr_t *hdrs, int n_hdr, hipStream_t st)
+static int write_run(pcamv_batch *b, WriteJobs J, const pcamv_slice_hdr_t *hdrs, int n_hdr, int cavlc, hipStream_t st)
 {
     const FrameDev &F0 = b->ctx[0]->F;
     int k;
     TRY(write_stage(b, hdrs, n_hdr, st, &J.hdr, &k));
     J.n_hdr = hdrs ? n_hdr : 1;
-    J.status = b->d_wstat; J.tab = b->d_sw_tab; J.scratch = b->d_sw_scratch; J.scratch_stride = (long long)SP_ROW_BYTES * F0.mb_w;
+    J.status = b->d_wstat; J.tab = b->d_sw_tab; J.scratch = b->d_sw_scratch; J.scratch_stride = (long long)(cavlc ? SV_ROW_BYTES : SP_ROW_BYTES) * F0.mb_w;
     J.lds_cols = b->sp_lds_cols;
     const FrameDev *dF; const EmbedDev *dE; int slot;
     int rc = batch_push_descs(b, st, &dF, &dE, &slot);
     if (!rc) {
-        const int ev = kt_begin(b, KT_WRITE_PSLICE, st);
-        pcamv_launch_write_pslice((unsigned)b->n, st, dF, J);
-        kt_end(b, KT_WRITE_PSLICE, ev, st);
+        const int kt = cavlc ? KT_WRITE_PSLICE_CAVLC : KT_WRITE_PSLICE;
+        const int ev = kt_begin(b, kt, st);
+        if (cavlc) pcamv_launch_write_pslice_cavlc((unsigned)b->n, st, dF, J);
+        else pcamv_launch_write_pslice((unsigned)b->n, st, dF, J);
+        kt_end(b, kt, ev, st);
         const hipError_t e = hipGetLastError();
         rc = e != hipSuccess ? fail(b, PCAMV_EHIP, "kernel launch: %s", hipGetErrorString(e)) : ring_release(b, b->ring, slot, st);
     }
     const int rc2 = write_stage_release(b, k, st);                  /* released on every path */
     return rc ? rc : rc2;
 }
-/* Every context's last step as a CABAC P slice, final motion (the records with the flip map of the step's embedding stage), from one
+/* Every context's last step as a CABAC (cavlc: CAVLC) P slice, final motion (the records with the flip map of the step's embedding stage), from one
  * launch on `stream`, no host synchronisation.
  * Ordering is the caller's, as for pcamv_gpu_batch_extract_slices_device (the borrowed buffer and the three arrays belong to `stream`'s
  * timeline), and the call belongs after the batch_step whose frame it writes and before the next one: the kernel reads that step's
@@ -1464,20 +1476,31 @@ static int write_run(pcamv_batch *b, WriteJobs J, const pcamv_slice_hdr_t *hdrs,
  * but the records and the flip map, both complete when the step is.  The first thing of the NEXT step to overwrite anything read here is
  * its plane stage (k_hpel / k_chroma_pad: the padded planes), then its analysis (the records); the source planes are the caller's and
  * stay until the caller replaces them. */
-extern "C" int pcamv_gpu_batch_write_step(pcamv_batch_t *b, const pcamv_slice_hdr_t *hdrs, int n_hdr, int as_nal, void *bytes, size_t bytes_size,
-                                          const int64_t *off, const int64_t *cap, int64_t *len, void *stream)
+static int batch_write_step(pcamv_batch_t *b, const pcamv_slice_hdr_t *hdrs, int n_hdr, int as_nal, void *bytes, size_t bytes_size,
+                            const int64_t *off, const int64_t *cap, int64_t *len, int cavlc, void *stream)
 {
     if (!b || !bytes || !off || !cap || !len || bytes_size > ((size_t)1 << 62)) return PCAMV_EINVAL;
     if (hdrs ? (n_hdr != 1 && n_hdr != b->n) : n_hdr != 0) return fail(b, PCAMV_EINVAL, "n_hdr is 1 or the batch size (0 with no header)");
     HIPCHK(b, hipSetDevice(b->device));
     TRY(batch_live(b));
-    TRY(write_setup(b));
+    TRY(write_setup(b, cavlc));
     static_assert(sizeof(long long) == sizeof(int64_t), "the caller's int64 arrays are read as they are");
     WriteJobs J = {};
     J.bytes = (uint8_t *)bytes; J.bytes_size = (long long)bytes_size;
     J.off = (const long long *)off; J.cap = (const long long *)cap; J.len = (long long *)len;
     J.mbs = NULL; J.as_nal = as_nal != 0; J.final = 1;
-    return write_run(b, J, hdrs, n_hdr, stream ? (hipStream_t)stream : b->ctx[0]->stream);
+    return write_run(b, J, hdrs, n_hdr, cavlc, stream ? (hipStream_t)stream : b->ctx[0]->stream);
+}
+extern "C" int pcamv_gpu_batch_write_step(pcamv_batch_t *b, const pcamv_slice_hdr_t *hdrs, int n_hdr, int as_nal, void *bytes, size_t bytes_size,
+                                          const int64_t *off, const int64_t *cap, int64_t *len, void *stream)
+{
+    return batch_write_step(b, hdrs, n_hdr, as_nal, bytes, bytes_size, off, cap, len, 0, stream);
+}
+/* the same as a CAVLC P slice (k_write_pslice_cavlc), for contexts opened with --no-cabac */
+extern "C" int pcamv_gpu_batch_write_step_cavlc(pcamv_batch_t *b, const pcamv_slice_hdr_t *hdrs, int n_hdr, int as_nal, void *bytes, size_t bytes_size,
+                                                const int64_t *off, const int64_t *cap, int64_t *len, void *stream)
+{
+    return batch_write_step(b, hdrs, n_hdr, as_nal, bytes, bytes_size, off, cap, len, 1, stream);
 }
 /* synchronises; status[i] = return code of context i's slice in the last write call (0 or PCAMV_ENOMEM; PCAMV_EINVAL for a place
  * outside the buffer) */
@@ -1502,15 +1525,15 @@ extern "C" int64_t pcamv_gpu_slice_bound(const pcamv_ctx_t *c, int32_t hdr_bits,
 }
 /* the parity probe: one slice of the context's last frame (mbs == NULL; final: with the embedding stage's flip map) or of uploaded
  * records that hold final motion, written on the device, copied back.  Synchronises. */
-extern "C" int pcamv_gpu_write_pslice(pcamv_ctx_t *c, const pcamv_slice_hdr_t *hdr, int final, const pcamv_mb_t *mbs, int as_nal, uint8_t *out, size_t cap,
-                                      size_t *len)
+static int write_pslice(pcamv_ctx_t *c, const pcamv_slice_hdr_t *hdr, int final, const pcamv_mb_t *mbs, int as_nal, uint8_t *out, size_t cap, size_t *len,
+                        int cavlc)
 {
     if (!c || !out || !len || cap > ((size_t)1 << 40)) return PCAMV_EINVAL;
     *len = 0;
     HIPCHK(c, hipSetDevice(c->device));
     pcamv_batch *b = c->self;
     TRY(on_behalf(c, b, batch_live(b)));
-    TRY(on_behalf(c, b, write_setup(b)));
+    TRY(on_behalf(c, b, write_setup(b, cavlc)));
     if (mbs) {
         TRY(rx_mbs(c));
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1528,7 +1551,7 @@ extern "C" int pcamv_gpu_write_pslice(pcamv_ctx_t *c, const pcamv_slice_hdr_t *h
         J.bytes = d_out + arr; J.bytes_size = (long long)cap;
         J.off = (const long long *)d_out; J.cap = J.off + 1; J.len = (long long *)d_out + 2;
         J.mbs = mbs ? c->d_rx_mbs : NULL; J.as_nal = as_nal != 0; J.final = final != 0;
-        rc = on_behalf(c, b, write_run(b, J, hdr, hdr ? 1 : 0, c->stream));
+        rc = on_behalf(c, b, write_run(b, J, hdr, hdr ? 1 : 0, cavlc, c->stream));
         if (!rc) e = hipStreamSynchronize(c->stream);
         if (!rc && e == hipSuccess) e = hipMemcpy(&st, b->d_wstat, sizeof(st), hipMemcpyDeviceToHost);
         if (!rc && e == hipSuccess) e = hipMemcpy(&n, d_out + 2 * sizeof(long long), sizeof(n), hipMemcpyDeviceToHost);
@@ -1542,6 +1565,16 @@ extern "C" int pcamv_gpu_write_pslice(pcamv_ctx_t *c, const pcamv_slice_hdr_t *h
     if (n < 0 || (size_t)n > cap) return fail(c, PCAMV_EHIP, "write_pslice: length corrupt");
     *len = (size_t)n;
     return 0;
+}
+extern "C" int pcamv_gpu_write_pslice(pcamv_ctx_t *c, const pcamv_slice_hdr_t *hdr, int final, const pcamv_mb_t *mbs, int as_nal, uint8_t *out, size_t cap,
+                                      size_t *len)
+{
+    return write_pslice(c, hdr, final, mbs, as_nal, out, cap, len, 0);
+}
+extern "C" int pcamv_gpu_write_pslice_cavlc(pcamv_ctx_t *c, const pcamv_slice_hdr_t *hdr, int final, const pcamv_mb_t *mbs, int as_nal, uint8_t *out, size_t cap,
+                                            size_t *len)
+{
+    return write_pslice(c, hdr, final, mbs, as_nal, out, cap, len, 1);
 }
 /* the inverse of pcamv_gpu_nal_to_rbsp, as x264_nal_encode writes a unit (common/common.c:658-695): long start code, header byte, the
  * RBSP with an emulation prevention byte before every byte <= 3 that follows two zeros.  Host code. */

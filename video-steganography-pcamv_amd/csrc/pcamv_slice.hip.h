@@ -87,4 +87,5 @@ static __global__ void __launch_bounds__(64) k_parse_pslice_cavlc(const ExtractD
 /* the writer's kernel is a unit of its own (pcamv_slice_write.hip): it inlines the analysis' prediction and transform primitives, and what
  * the compiler makes of the kernels of this unit depends on what else in the unit calls them */
 void pcamv_launch_write_pslice(unsigned slices, hipStream_t st, const FrameDev *dF, const WriteJobs &J);
+void pcamv_launch_write_pslice_cavlc(unsigned slices, hipStream_t st, const FrameDev *dF, const WriteJobs &J);   /* pcamv_slice_write_cavlc.hip */
 #endif

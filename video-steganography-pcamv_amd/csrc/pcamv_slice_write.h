@@ -33,25 +33,13 @@
  */
 #ifndef PCAMV_SLICE_WRITE_H
 #define PCAMV_SLICE_WRITE_H
-#include "pcamv_slice_parse.h"
+#include "pcamv_slice_write_common.h"
 
 #define SW_NCTX 460
 #define SW_CTX_BYTES 464
-#define SW_OBUF 256
 /* the tables as one block: context initialisers (m, n) of all 460 contexts (the state hash covers them all), transitions, rangeTabLPS */
 enum { SW_TAB_INIT = 0, SW_TAB_TRANS = 2 * SW_NCTX, SW_TAB_RLPS = SW_TAB_TRANS + 256, SW_TAB_BYTES = SW_TAB_RLPS + 512 };
-/* A capacity no slice exceeds, per macroblock.  A decision shifts out at most 6 bits (rangeTabLPS >= 6: renorm shift <= 6), a bypass
- * bin 1.  |level| < 4096 (|residual| <= 255, the core transform's gain is 36, the quantiser's factor at QP 0 is 0.4; chroma DC
- * 16320 * 0.2), so a coefficient is at most significant + last + 14 prefix decisions, 25 bins of Exp-Golomb 0 and a sign: 16 * 6 +
- * 26 = 122 bits, 384 coefficients; 27 coded_block_flags; an mvd component (|mvd| < 2^16) 9 decisions + 33 bins of Exp-Golomb 3 +
- * sign = 88 bits, 32 of them; mb_skip_flag, mb_type 3, sub_mb_type 12, coded_block_pattern 6, mb_qp_delta 1 decisions; the
- * terminal bin 1 bit: 46848 + 162 + 2816 + 23 * 6 + 1 = 49965 bits = 6246 bytes.  (The reference's densest slice seen, QP 0 on
- * saturated noise, has 538 per macroblock: the bound is far from tight, and is no function of the raw picture size.) */
-#define SW_MB_BOUND 6272
-#define SW_TAIL_BOUND 16        /* the flush: 10 bits and the pending byte */
-
-struct SwHeader { const uint8_t *bits; int n_bits, i_frame, nal_byte; };       /* bits: most significant first; nal_byte: nal_ref_idc << 5 | nal_unit_type */
-
+/* (SW_OBUF, SW_MB_BOUND, SW_TAIL_BOUND, SwHeader and the output path -- sw_emit -- are pcamv_slice_write_common.h's) */
 struct SwState {
     SpState S;                          /* the neighbourhood (S.ctx: SW_CTX_BYTES here; S.win is not used) */
     uint32_t low, range; int queue, outstanding, pend;      /* pend: the last byte put, not final yet (-1: none) */
@@ -60,42 +48,6 @@ struct SwState {
     long long abase;
     int as_nal, zeros, bad;
 };
-
-/* ---------------------------------------------------------------- output */
-/* what the buffer holds to the destination: whole dwords where all four bytes are the slice's and below cap, single bytes at the ends */
-PCAMV_DEV void sw_flush(SwState &W)
-{
-    uint8_t *d0 = W.dst + W.abase;                   /* 4-byte aligned */
-    const long long room = W.cap - W.abase;          /* buffer positions below this may be stored */
-    const int lo = W.abase < 0 ? (int)-W.abase : 0, hi = (long long)W.fill < room ? W.fill : (int)(room < 0 ? 0 : room);
-    SP_SYNC();
-    SP_LANES(l) {
-        const int a = 4 * l;
-        if (a >= lo && a + 4 <= hi) sp_st32(d0 + a, W.obuf[l]);
-        else for (int k = 0; k < 4; k++) if (a + k >= lo && a + k < hi) d0[a + k] = (uint8_t)(W.obuf[l] >> (8 * k));
-    }
-    SP_SYNC();
-    W.abase += W.fill;
-    W.fill = 0;
-}
-PCAMV_DEV void sw_raw(SwState &W, uint32_t b)
-{
-    if (W.n < W.cap) {
-        ((uint8_t *)W.obuf)[W.fill] = (uint8_t)b;
-        if (++W.fill == SW_OBUF) sw_flush(W);
-    }
-    W.n++;
-}
-/* one final byte of the RBSP */
-PCAMV_DEV void sw_emit(SwState &W, uint32_t b)
-{
-    b &= 255u;
-    if (W.as_nal) {
-        if (W.zeros == 2 && b <= 3u) { sw_raw(W, 3u); W.zeros = 0; }
-        W.zeros = b == 0 ? W.zeros + 1 : 0;
-    }
-    sw_raw(W, b);
-}
 
 /* ---------------------------------------------------------------- arithmetic coder (common/cabac.c:807-926) */
 PCAMV_DEV void sw_putbyte(SwState &W)
@@ -233,28 +185,6 @@ PCAMV_DEV void sw_residual(SwState &W, int cat, const int16_t *l, int count, int
     }
 }
 
-/* the carrier slot (= first block of the partition) that owns block i, and that slot's place among the macroblock's carriers in
- * embedding order: carrier_of_block and carrier_slots of pcamv_logic.h on the four sub-partitions packed in one word, so that a lane
- * indexes no array */
-PCAMV_DEV int sw_block_slot(int type, int partition, uint32_t sub, int i)
-{
-    if (type == PCAMV_P_8x8) {
-        const int t = (int)((sub >> (8 * (i >> 2))) & 255u), j = i & 3;
-        return (i & 12) + (t == PCAMV_D_L0_8x8 ? 0 : t == PCAMV_D_L0_4x8 ? (j & 1) : t == PCAMV_D_L0_8x4 ? (j & 2) : j);
-    }
-    if (partition == PCAMV_D_8x16) return sp_blk_x(i) < 2 ? 0 : 4;
-    if (partition == PCAMV_D_16x8) return sp_blk_y(i) < 2 ? 0 : 8;
-    return 0;
-}
-PCAMV_DEV int sw_slot_rank(int type, uint32_t sub, int s)
-{
-    if (type != PCAMV_P_8x8) return s != 0;
-    int n = 0;
-    for (int k = 0; k < (s >> 2); k++) { const int t = (int)((sub >> (8 * k)) & 255u); n += t == PCAMV_D_L0_8x8 ? 1 : t == PCAMV_D_L0_4x4 ? 4 : 2; }
-    const int t = (int)((sub >> (8 * (s >> 2))) & 255u), j = s & 3;
-    return n + (t == PCAMV_D_L0_4x4 ? j : j != 0);
-}
-
 /* Every macroblock of the picture.  mbs: the records; flip / car_base: the embedding stage's flip map in carrier order and each
  * macroblock's first carrier in it (flip == NULL: the records' mv are final); n_car: entries of flip.  hash (optional): FNV-1a of
  * the 460 states after each macroblock. */
@@ -293,33 +223,12 @@ PCAMV_DEV int sw_run(SwState &W, const FrameDev &F, MBLocal *L, const pcamv_mb_t
 
             /* the record: type, partition, sub-partitions; anything else is not a P macroblock of this path */
             const pcamv_mb_t *r = mbs + xy;
-            int type = (int)SP_UNI(r->i_type), partition = (int)SP_UNI(r->i_partition);
-            const uint32_t sub = SP_UNI((uint32_t)r->i_sub_partition[0] | (uint32_t)r->i_sub_partition[1] << 8 | (uint32_t)r->i_sub_partition[2] << 16 |
-                                        (uint32_t)r->i_sub_partition[3] << 24);
-            const int used = (int)SP_UNI(r->used);
-            if (type == PCAMV_P_8x8) { partition = PCAMV_D_8x8; if (sub & 0xfcfcfcfcu) return PCAMV_EINVAL; }
-            else if (type == PCAMV_P_L0) { if (partition != PCAMV_D_16x16 && partition != PCAMV_D_16x8 && partition != PCAMV_D_8x16) return PCAMV_EINVAL; }
-            else if (type != PCAMV_P_SKIP) return PCAMV_EUNSUP;
+            SW_READ_RECORD(r, type, partition, sub, used);
             S.partition = type == PCAMV_P_SKIP ? PCAMV_D_16x16 : partition;
             int cbp_luma = 0, cbp_chroma = 0, dcf = 0;
             if (type != PCAMV_P_SKIP) {
-                /* final motion of the sixteen blocks, one per lane: into the neighbourhood and into the primitives' cache */
-                const int base = flip && car_base ? (int)SP_UNI(car_base[xy]) : 0;
-                SP_SYNC();
-                SP_LANES(i) if (i < 16) {
-                    const int s = sw_block_slot(type, partition, sub, i), k = base + sw_slot_rank(type, sub, s);
-                    const int flipped = flip && used && (unsigned)k < (unsigned)n_car && flip[k] == 1;
-                    const int16_t *m = flipped ? r->mv_stego[s] : r->mv[s];
-                    S.cmv[sp_s8(i)] = sp_pack(m[0], m[1]); S.cref[sp_s8(i)] = 0;
-                    L->cmv[scan8_of(i)][0] = m[0]; L->cmv[scan8_of(i)][1] = m[1];
-                }
-                SP_SYNC();
-                /* levels: prediction from that motion, transform and quantisation as the second pass makes them (mbk_pass2) */
-                mb_load(F, L, mx, my, true);
-                L->i_type = type; L->i_partition = partition;
-                for (int i = 0; i < 4; i++) L->sub_part[i] = (uint8_t)(sub >> (8 * i));
-                prim_load_fenc(F, L);
-                mb_encode(F, L, 0, 1);
+                /* final motion of the sixteen blocks and the levels made from it */
+                sw_motion_levels(S, F, L, r, type, partition, sub, used, flip, car_base, n_car, xy, mx, my);
                 cbp_luma = (int)SP_UNI(L->cbp_luma) & 15; cbp_chroma = (int)SP_UNI(L->cbp_chroma) & 3;
             }
             const int skip = type == PCAMV_P_SKIP;
@@ -455,18 +364,5 @@ PCAMV_DEV int pcamv_slice_write(SwState &W, const SpTables &T, const FrameDev &F
     return 0;
 }
 
-/* the slices of one launch of the writer: slice i goes to bytes[off[i] .. off[i] + cap[i]), its length to len[i], its return code to status[i] */
-#define SW_HDR_WORDS 4
-#define SW_LDS_COLS 128         /* SP_LDS_COLS of the parsers: pictures up to this many macroblocks wide keep the row buffer in LDS */
-struct WriteJobs {
-    uint8_t *bytes; long long bytes_size;
-    const long long *off, *cap; long long *len; int *status;
-    const int *hdr;                     /* n_hdr (1: one for all, or one per slice) entries of SW_HDR_WORDS words {byte offset of the bits behind this
-                                         * array's start, n_bits, i_frame, NAL header byte}, then the bits */
-    int n_hdr;
-    const pcamv_mb_t *mbs;              /* records that hold final motion, uploaded by the caller (a launch of one slice), or NULL: the contexts' own */
-    const uint8_t *tab;                 /* SW_TAB_BYTES of pcamv_slice_write.h */
-    uint8_t *scratch; long long scratch_stride;
-    int lds_cols, as_nal, final;        /* final: the records with the embedding stage's flip map (else as they are) */
-};
+/* (a launch is described by WriteJobs of pcamv_slice_write_common.h) */
 #endif

@@ -132,8 +132,8 @@ def lib_path():
 
 
 # the library's translation units (csrc/<unit>.hip): the host side with the common kernels, the --me tesa instance of the analysis kernel,
-# the per-diagonal second pass, the slice writer, and the six builds of the analysis kernel's --subme 6 / 7 instance
-UNITS = ("pcamv_gpu", "pcamv_pass2_diag", "pcamv_slice_write", "pcamv_tesa", "pcamv_rd", "pcamv_rd_lo", "pcamv_rd_spec", "pcamv_rd_spec2", "pcamv_rd_spec4", "pcamv_rd_tesa")
+# the per-diagonal second pass, the two slice writers, and the six builds of the analysis kernel's --subme 6 / 7 instance
+UNITS = ("pcamv_gpu", "pcamv_pass2_diag", "pcamv_slice_write", "pcamv_slice_write_cavlc", "pcamv_tesa", "pcamv_rd", "pcamv_rd_lo", "pcamv_rd_spec", "pcamv_rd_spec2", "pcamv_rd_spec4", "pcamv_rd_tesa")
 
 
 def build_library(force=False):
@@ -281,6 +281,7 @@ FEATURE_PAYLOAD = 0x1
 FEATURE_SLICE_PARSER = 0x2      # CABAC P slices parsed on the device: Encoder.parse_pslice_device, Batch.extract_slices
 FEATURE_SLICE_PARSER_CAVLC = 0x4    # CAVLC P slices too: Encoder.parse_pslice_cavlc_device, Batch.extract_slices_cavlc
 FEATURE_SLICE_WRITER = 0x8      # CABAC P slices written on the device: Encoder.write_pslice, Batch.write_step
+FEATURE_SLICE_WRITER_CAVLC = 0x10   # CAVLC P slices too: Encoder.write_pslice_cavlc, Batch.write_step_cavlc
 
 
 def features():
@@ -495,6 +496,15 @@ class Encoder:
         hdr: the slice header's bits (a sequence, or dict(bits, i_frame, nal_ref_idc, nal_unit_type)), behind which come the
         alignment ones and the slice data; none: the bare slice data.  as_nal: the NAL unit with start code and emulation
         prevention.  cap: the capacity offered (default: slice_bound); a slice that does not fit raises (-3)"""
+        return self._write_pslice("pcamv_gpu_write_pslice", hdr, final, mbs, as_nal, cap)
+
+    def write_pslice_cavlc(self, hdr=None, final=True, mbs=None, as_nal=False, cap=None):
+        """pcamv_gpu_write_pslice_cavlc: the same for a context opened with b_cabac = 0 -- the CAVLC P slice of its last frame written
+        by k_write_pslice_cavlc.  The slice data follows the header's last bit directly (no alignment bits); hdr's i_frame is not read"""
+        return self._write_pslice("pcamv_gpu_write_pslice_cavlc", hdr, final, mbs, as_nal, cap)
+
+    def _write_pslice(self, call, hdr, final, mbs, as_nal, cap):
+        """what write_pslice and write_pslice_cavlc share: `call` names the library's entry point"""
         h, keep = _slice_hdr(hdr if hdr is not None else ())
         if cap is None:
             cap = self.slice_bound(h.n_bits, as_nal)
@@ -504,9 +514,10 @@ class Encoder:
                 raise PcamvError(f"{len(mbs)} records for a picture of {self.n_mb} macroblocks")
         out = np.zeros(max(int(cap), 1), np.uint8)
         n = C.c_size_t()
-        self.lib.pcamv_gpu_write_pslice.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
-        self._chk(self.lib.pcamv_gpu_write_pslice(self.ctx, C.byref(h) if hdr is not None else None, int(bool(final)), _p(mbs), int(bool(as_nal)), _p(out), int(cap),
-                                                  C.byref(n)), "write_pslice")
+        fn = getattr(self.lib, call)
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        self._chk(fn(self.ctx, C.byref(h) if hdr is not None else None, int(bool(final)), _p(mbs), int(bool(as_nal)), _p(out), int(cap), C.byref(n)),
+                  call[len("pcamv_gpu_"):])
         return out[:n.value].tobytes()
 
     def slice_records(self):
@@ -711,6 +722,16 @@ class Batch:
         tensors of one entry per context: slice i goes to data[off[i] : off[i] + cap[i]] and is length[i] long; one that does not
         fit gets length 0 and write_status() -3.  With as_nal=False (data, off, length) is what extract_slices_device takes.
         Ordering is the caller's, as for extract_slices_device; the call belongs after the step it writes and before the next"""
+        self._write_step("pcamv_gpu_batch_write_step", hdr, data, off, cap, length, as_nal, stream)
+
+    def write_step_cavlc(self, hdr, data, off, cap, length, as_nal=False, stream=0):
+        """pcamv_gpu_batch_write_step_cavlc: the same for contexts opened with b_cabac = 0 -- CAVLC P slices by one launch of
+        k_write_pslice_cavlc.  With as_nal=False (data, off, length) and the header's bit count are what extract_slices_cavlc_device
+        takes as (data, off, length, hdr_bits)"""
+        self._write_step("pcamv_gpu_batch_write_step_cavlc", hdr, data, off, cap, length, as_nal, stream)
+
+    def _write_step(self, call, hdr, data, off, cap, length, as_nal, stream):
+        """what write_step and write_step_cavlc share: `call` names the library's entry point"""
         for t, size, what in ((data, 1, "data: uint8"), (off, 8, "off: int64"), (cap, 8, "cap: int64"), (length, 8, "length: int64")):
             if not _is_device_tensor(t) or not t.is_cuda or t.element_size() != size or not t.is_contiguous():
                 raise PcamvError(f"{what}, contiguous, on the device")
@@ -721,9 +742,10 @@ class Batch:
             raise PcamvError(f"{len(hdrs)} headers for a batch of {len(self.encs)} contexts (none, one, or one each)")
         made = [_slice_hdr(h) for h in hdrs]
         arr = (_SliceHdr * max(len(made), 1))(*[m[0] for m in made])
-        self.lib.pcamv_gpu_batch_write_step.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        self._slice_chk(self.lib.pcamv_gpu_batch_write_step(self.b, arr if made else None, len(made), int(bool(as_nal)), data.data_ptr(), data.numel(), off.data_ptr(),
-                                                            cap.data_ptr(), length.data_ptr(), C.c_void_p(stream or None)), "batch_write_step")
+        fn = getattr(self.lib, call)
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._slice_chk(fn(self.b, arr if made else None, len(made), int(bool(as_nal)), data.data_ptr(), data.numel(), off.data_ptr(), cap.data_ptr(),
+                           length.data_ptr(), C.c_void_p(stream or None)), call[len("pcamv_gpu_"):])
 
     def write_status(self):
         """per context: 0, or -3 where its slice of the last write_step did not fit its capacity; synchronises"""
