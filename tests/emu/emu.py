@@ -1,27 +1,14 @@
 """TEST-ONLY: build + bind tests/emu/libpcamv_emu.so (the product's control code with scalar prims)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
-LIB = os.path.join(HERE, "libpcamv_emu.so")
-CSRC = os.path.join(ROOT, "video-steganography-pcamv_amd", "csrc")
+from emu._build import FLAGS, build_so, csrc, here
 
 
 def build(sanitize=False):
-    srcs = [os.path.join(HERE, "emu_driver.cpp")]
-    deps = srcs + [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "pcamv_prims_emu.h")]
-    if os.path.exists(LIB) and all(os.path.getmtime(LIB) > os.path.getmtime(d) for d in deps):
-        return LIB
-    cmd = ["g++", "-O1", "-g", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unused-function",
-           "-Wno-unused-variable", "-I", CSRC, "-I", HERE, "-o", LIB] + srcs
-    if sanitize:
-        cmd[1:1] = ["-fsanitize=address,undefined"]
-    subprocess.check_call(cmd)
-    return LIB
+    return build_so("libpcamv_emu.so", ["emu_driver.cpp"], csrc() + here("pcamv_prims_emu.h"),
+                    (("-fsanitize=address,undefined",) if sanitize else ()) + FLAGS)
 
 
 def analyse_pframe(orc_mod, params, qp, embed, fenc, ref_planes4, ref_u, ref_v, prev_mv=None, prev_ref=None, diag=1, trace_mb=-1, state_hash=None):

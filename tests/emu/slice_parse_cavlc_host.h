@@ -9,6 +9,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "pcamv_slice_parse_cavlc.h"
+#include "slice_host.h"
 
 static inline int sv_host_parse(const uint8_t *rbsp, long long len, long long start_bit, int mb_w, int mb_h, pcamv_mb_t *out)
 {
@@ -22,13 +23,11 @@ static inline int sv_host_parse(const uint8_t *rbsp, long long len, long long st
     uint8_t *cbp_of = (uint8_t *)malloc(48);
     memcpy(vlc, tab, 2 * SV_T_N); memcpy(cbp_of, tab + SV_T_CBP, 48);
     S.vlc = vlc; S.cbp_of = cbp_of;
-    S.win = (uint32_t *)malloc(64 * 4);
-    S.cmv = (uint32_t *)malloc(48 * 4); S.cref = (int8_t *)malloc(48); S.cnz = (uint8_t *)malloc(48);
-    S.row = (uint8_t *)malloc((size_t)SV_ROW_BYTES * mb_w); S.tl = (uint32_t *)malloc(4);
-    memset(S.win, 0, 256); memset(S.cmv, 0, 192); memset(S.cref, 0, 48); memset(S.cnz, 0, 48);
-    memset(S.row, 0, (size_t)SV_ROW_BYTES * mb_w); S.tl[0] = 0;
+    S.win = (uint32_t *)calloc(64, 4);
+    slice_host_alloc(S, (size_t)SV_ROW_BYTES * mb_w, 1);
     const int rc = pcamv_slice_parse_cavlc(S, rbsp, len, start_bit, mb_w, mb_h, out);
-    free(S.win); free(S.cmv); free(S.cref); free(S.cnz); free(S.row); free(S.tl);
+    slice_host_free(S);
+    free(S.win);
     free(vlc); free(cbp_of);
     return rc;
 }

@@ -9,6 +9,7 @@
 #include <string.h>
 #include "pcamv_entropy_tables.h"
 #include "pcamv_slice_parse.h"
+#include "slice_host.h"
 
 static inline int sp_host_parse(const uint8_t *rbsp, long long len, long long start_bit, int qp, int mb_w, int mb_h, pcamv_mb_t *out)
 {
@@ -20,13 +21,11 @@ static inline int sp_host_parse(const uint8_t *rbsp, long long len, long long st
     uint8_t *trans = (uint8_t *)malloc(256), *rlps = (uint8_t *)malloc(512);
     memcpy(init_p, pcamv_cabac_init_p, 2 * SP_NCTX); memcpy(trans, pcamv_cabac_transition, 256); memcpy(rlps, pcamv_cabac_range_lps, 512);
     const SpTables T = {init_p, trans, rlps};
-    S.win = (uint32_t *)malloc(64 * 4); S.ctx = (uint8_t *)malloc(SP_NCTX);
-    S.cmv = (uint32_t *)malloc(48 * 4); S.cmvd = (uint32_t *)malloc(48 * 4); S.cref = (int8_t *)malloc(48); S.cnz = (uint8_t *)malloc(48);
-    S.row = (uint8_t *)malloc((size_t)SP_ROW_BYTES * mb_w); S.tl = (uint32_t *)malloc(4);
-    memset(S.win, 0, 256); memset(S.cmv, 0, 192); memset(S.cmvd, 0, 192); memset(S.cref, 0, 48); memset(S.cnz, 0, 48);
-    memset(S.row, 0, (size_t)SP_ROW_BYTES * mb_w); S.tl[0] = 0;
+    S.win = (uint32_t *)calloc(64, 4); S.ctx = (uint8_t *)malloc(SP_NCTX); S.cmvd = (uint32_t *)calloc(48, 4);
+    slice_host_alloc(S, (size_t)SP_ROW_BYTES * mb_w, 1);
     const int rc = pcamv_slice_parse(S, T, rbsp, len, start_bit, qp, mb_w, mb_h, out);
-    free(S.win); free(S.ctx); free(S.cmv); free(S.cmvd); free(S.cref); free(S.cnz); free(S.row); free(S.tl);
+    slice_host_free(S);
+    free(S.win); free(S.ctx); free(S.cmvd);
     free(init_p); free(trans); free(rlps);
     return rc;
 }

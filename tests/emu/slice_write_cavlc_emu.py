@@ -1,28 +1,17 @@
 """TEST-ONLY: build + bind tests/emu/libpcamv_slice_write_cavlc_emu.so (the device CAVLC slice writer's control code with scalar primitives)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
+from emu._build import ABI, build_so, csrc, here
 from emu.slice_write_emu import padded_planes  # noqa: F401  (the same padded reference planes)
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
-LIB = os.path.join(HERE, "libpcamv_slice_write_cavlc_emu.so")
-CSRC = os.path.join(ROOT, "video-steganography-pcamv_amd", "csrc")
 ENOMEM = -3
 
 
 def build():
-    src = os.path.join(HERE, "slice_write_cavlc_driver.cpp")
-    deps = [src, os.path.join(HERE, "slice_write_cavlc_host.h"), os.path.join(HERE, "pcamv_prims_emu.h"), os.path.join(ROOT, "include", "pcamv_gpu.h")]
-    deps += [os.path.join(CSRC, f) for f in os.listdir(CSRC)]
-    if os.path.exists(LIB) and all(os.path.getmtime(LIB) > os.path.getmtime(d) for d in deps):
-        return LIB
-    subprocess.check_call(["g++", "-O1", "-g", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unused-function",
-                           "-Wno-unused-variable", "-I", CSRC, "-I", HERE, "-o", LIB, src])
-    return LIB
+    return build_so("libpcamv_slice_write_cavlc_emu.so", ["slice_write_cavlc_driver.cpp"],
+                    here("slice_write_cavlc_host.h", "slice_host.h", "pcamv_prims_emu.h") + [ABI] + csrc())
 
 
 def lib():

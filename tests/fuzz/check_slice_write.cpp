@@ -4,53 +4,15 @@
  * must receive the expected bytes; a shorter one must give PCAMV_ENOMEM and length 0.  Built and run by
  * tests/test_slice_write_sanitize.py, which writes the cases (tests/slice_write_cases.py: write_case_file).
  *
- * usage: check_slice_write <cases.bin>     cases.bin: int32 count, then per case int32 {qp, n_hdr_bits, as_nal, short, nal_byte, blobs}
- * and `blobs` (10) blocks of int64 length + bytes: parameters, source Y U V, the padded reference planes (luma x 4, U, V), records,
- * header bits (packed), expected bytes.
+ * usage: check_slice_write <cases.bin>     (the case file and what a case must give: check_slice_write_common.h)
  * prints one line per case "<index> <rc> <len> <expected len> <short>" and a summary; exit status 1 on any failure. */
-#include <stdio.h>
-#include <vector>
 #include "slice_write_host.h"
-
-static bool read_blob(FILE *f, std::vector<uint8_t> &b)
-{
-    int64_t n = 0;
-    if (fread(&n, 8, 1, f) != 1 || n < 0 || n > ((int64_t)1 << 31)) return false;
-    b.resize((size_t)n);
-    return !n || fread(b.data(), 1, (size_t)n, f) == (size_t)n;
-}
+#include "check_slice_write_common.h"
 
 int main(int argc, char **argv)
 {
     if (argc < 2) return 2;
-    FILE *f = fopen(argv[1], "rb");
-    if (!f) return 2;
-    int32_t count = 0;
-    if (fread(&count, 4, 1, f) != 1 || count < 0) return 2;
-    long bad = 0, fit = 0, refused = 0;
-    for (int k = 0; k < count; k++) {
-        int32_t h[6];
-        if (fread(h, 4, 6, f) != 6 || h[5] != 10) return 2;
-        std::vector<uint8_t> blob[10];
-        for (int i = 0; i < 10; i++) if (!read_blob(f, blob[i])) return 2;
-        if (blob[0].size() != sizeof(pcamv_params_t)) return 2;
-        pcamv_params_t p;
-        memcpy(&p, blob[0].data(), sizeof(p));
-        const size_t n_mb = (size_t)(p.i_width / 16) * (p.i_height / 16);
-        if (blob[7].size() != n_mb * sizeof(pcamv_mb_t) || blob[1].size() != (size_t)p.i_width * p.i_height) return 2;
-        const SwHostFrame in = {&p, h[0], {blob[1].data(), blob[2].data(), blob[3].data()}, blob[4].data(), blob[5].data(), blob[6].data(),
-                                (const pcamv_mb_t *)blob[7].data(), NULL, 0};
-        const long long want = (long long)blob[9].size(), cap = want - h[3];
-        if (cap < 0) return 2;
-        uint8_t *out = (uint8_t *)malloc(cap ? (size_t)cap : 1);        /* exact size: any store past the capacity is caught */
-        long long len = -1;
-        const int rc = sw_host_write(in, blob[8].data(), h[1], 0, h[4], h[2], out, cap, &len, NULL);
-        printf("%d %d %lld %lld %d\n", k, rc, len, want, h[3]);
-        if (h[3] == 0) { if (rc || len != want || memcmp(out, blob[9].data(), (size_t)want)) bad++; else fit++; }
-        else { if (rc != PCAMV_ENOMEM || len != 0) bad++; else refused++; }
-        free(out);
-    }
-    fclose(f);
-    printf("fit %ld refused %ld bad %ld\n", fit, refused, bad);
-    return bad ? 1 : 0;
+    return sw_check_cases(argv[1], [](const SliceHostFrame &in, const uint8_t *hdr_bits, int n_bits, int nal_byte, int as_nal, uint8_t *out, long long cap, long long *len) {
+        return sw_host_write(in, hdr_bits, n_bits, 0, nal_byte, as_nal, out, cap, len, NULL);
+    });
 }

@@ -142,6 +142,39 @@ def test_received_bits_from_stream_bytes(pc, name):
         e.close()
 
 
+def test_staging_ring_wraps_and_regrows(pc):
+    """five extract_slices calls of one batch from host slices, no synchronisation between them: the ring of two staging buffers
+    wraps twice, and the third call's slices sit behind 4096 more bytes of header, so that its buffer is regrown while the call
+    before it is still in flight.  Every call appends what a single call gives"""
+    g = helpers.load(next(n for n in sc.FINAL_FIXTURES if "qcif" in n))
+    (w, h), qp, m = sc.dims(g), int(g["qp"]), int(g["m"])
+    rbsp, _, _ = pc.nal_to_rbsp(g["nal"].tobytes())
+    hb = int(g["nal_hdr_bits"])
+    longer = 4096
+    calls = [(rbsp, hb, qp)] * 2 + [(b"\xff" * longer + rbsp, 8 * longer + hb, qp)] + [(rbsp, hb, qp)] * 2
+    one = pc.Encoder(_params(pc, 16 * w, 16 * h))
+    one.rx_reserve(2 * m)
+    b1 = pc.Batch([one])
+    b1.extract_slices([calls[0]], 0.5)
+    assert b1.slice_status().tolist() == [0]
+    once = one.received()
+    assert len(once) == m and np.array_equal(once, g["message"])
+    b1.close(); one.close()
+    encs = [pc.Encoder(_params(pc, 16 * w, 16 * h)) for _ in range(2)]
+    for e in encs:
+        e.rx_reserve(len(calls) * m + 64)
+    batch = pc.Batch(encs)
+    for c in calls:
+        batch.extract_slices([c] * len(encs), 0.5)
+    assert batch.slice_status().tolist() == [0] * len(encs)
+    for e in encs:
+        assert e.rx_tell()[0] == len(calls) * m
+        assert np.array_equal(e.received(), np.tile(once, len(calls)))
+    batch.close()
+    for e in encs:
+        e.close()
+
+
 def test_refusals(pc):
     g = helpers.load("pslice_qcif_hex_subme5_final")
     data, qp = g["slice_data"].tobytes(), int(g["qp"])

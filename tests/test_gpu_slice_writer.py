@@ -266,6 +266,52 @@ def test_batch_closes_the_loop_on_the_device(pc):
         enc.close()
 
 
+def test_staging_ring_wraps_and_regrows(pc):
+    """five write_step calls of one batch back to back on one stream, no synchronisation between them: the ring of two staging
+    buffers wraps twice, and a buffer is regrown (the header grows from 21 bits to 21 + 8 * 256 and to 21 + 8 * 4096) while the call
+    before the last is still in flight.  Every call's region holds what the single-context probe writes behind the same header"""
+    import torch
+    from pcamv_amd.synth import make_clip
+    W, H, qp, n = 176, 144, 28, 2
+    hdr_lens = [21, 21 + 8 * 256, 21 + 8 * 4096, 21, 21 + 8 * 64]
+    dev = torch.device("cuda", 0)
+    clips = [make_clip(W, H, 2, seed=730 + g, static_cols=32 * g, noise=6) for g in range(n)]
+    d = [[[torch.from_numpy(np.ascontiguousarray(pl)).to(dev) for pl in fr] for fr in clip] for clip in clips]
+    p = pc.param_default(W, H)
+    pc.param_parse(p, "subme", 6)
+    encs = [pc.Encoder(p) for _ in range(n)]
+    batch = pc.Batch(encs)
+    rng = np.random.default_rng(31)
+    hdrs = [dict(bits=rng.integers(0, 2, k).astype(np.uint8), nal_ref_idc=swc.NAL_REF_IDC, nal_unit_type=swc.NAL_UNIT_TYPE) for k in hdr_lens]
+    calls = len(hdrs)
+    bound = encs[0].slice_bound(max(hdr_lens), False)
+    stride = bound + 3                                  # slices at odd offsets of one tensor
+    data = torch.full((calls * n * stride,), 0xA5, dtype=torch.uint8, device=dev)
+    off = (torch.arange(calls * n, dtype=torch.int64, device=dev) * stride).reshape(calls, n)
+    cap = torch.full((n,), bound, dtype=torch.int64, device=dev)
+    length = torch.full((calls, n), -7, dtype=torch.int64, device=dev)
+    for g, enc in enumerate(encs):
+        enc.set_ref_device(*[pl.data_ptr() for pl in d[g][0]])
+        enc.set_fenc_device(*[pl.data_ptr() for pl in d[g][1]])
+    torch.cuda.synchronize()            # the contract: the tensors are complete before the library's stream touches them
+    batch.step(qp, 0.5, 0)
+    for k in range(calls):
+        batch.write_step(hdrs[k], data, off[k], cap, length[k], as_nal=False, stream=0)
+    torch.cuda.synchronize()
+    assert batch.write_status().tolist() == [0] * n
+    lens, blob = length.cpu().numpy(), data.cpu().numpy()
+    for k in range(calls):
+        for g, enc in enumerate(encs):
+            want = enc.write_pslice(hdr=hdrs[k])
+            at = (k * n + g) * stride
+            assert len(want) > hdr_lens[k] // 8 and lens[k, g] == len(want), f"call {k}, chain {g}: {lens[k, g]} bytes against {len(want)}"
+            assert blob[at:at + len(want)].tobytes() == want, f"call {k}, chain {g}"
+            assert (blob[at + len(want):at + stride] == 0xA5).all(), f"call {k}, chain {g}: bytes behind its slice were written"
+    batch.close()
+    for enc in encs:
+        enc.close()
+
+
 def test_refusals(pc):
     assert pc.features() & pc.FEATURE_SLICE_WRITER
     import torch

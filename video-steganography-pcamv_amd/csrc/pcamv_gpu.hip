@@ -58,6 +58,9 @@ struct DescRing { int head, used[NRING]; hipEvent_t done[NRING]; };
 /* hipEvents around the launches of one kernel, summed when pcamv_gpu_batch_kernel_time asks for it by name: a ring of the last `cap`
  * launches; one pair of events stands for `weight` launches (the anti-diagonals of PCAMV_SCHED=diag share a pair) */
 struct KTimer { hipEvent_t e0[NEV], e1[NEV]; int cap, weight, made, n, head, launches; double ms; };
+/* NSTAGE staging buffers taken in turn, each a pinned host block and its device copy made by the calls themselves (stage_take): a buffer
+ * is filled again only after the work that read it last (its event) is done, so a call waits for the one before the last */
+struct StageRing { uint8_t *h[NSTAGE], *d[NSTAGE]; size_t cap[NSTAGE]; hipEvent_t done[NSTAGE]; int used[NSTAGE], head; };
 
 struct pcamv_ctx;
 /* A batch = the set of independent closed-GOP contexts whose frames advance together: every kernel
@@ -80,14 +83,14 @@ struct pcamv_batch {
     ExtractDev *h_X, *d_X; long long *d_chk;
     DescRing xring;
     /* receiver from a stream (k_parse_pslice, k_parse_pslice_cavlc; a batch is of one entropy mode): per-context status words, the tables, the row buffers of pictures too wide for LDS, and
-     * the staging of host slices -- descriptor arrays then bytes in one block, pinned host and device, NSTAGE of them in turn */
+     * the staging of host slices -- descriptor arrays then bytes in one block */
     int *d_sstat; uint8_t *d_sp_tab, *d_sp_scratch;
     int sp_lds_cols;            /* pictures up to this many macroblocks wide keep the parser's row buffer in LDS (SP_LDS_COLS; PCAMV_SLICE_LDS_COLS lowers it) */
-    uint8_t *h_stage[NSTAGE], *d_stage[NSTAGE]; size_t stage_cap[NSTAGE]; hipEvent_t stage_done[NSTAGE]; int stage_used[NSTAGE], stage_head;
-    /* sender to a stream (k_write_pslice): per-context status words, the tables, the row buffers of pictures too wide for LDS, and the
-     * staging of the callers' slice headers (pinned host and device, NSTAGE in turn) */
+    StageRing rx_stage;
+    /* sender to a stream (k_write_pslice, k_write_pslice_cavlc): the same of its own, and the staging of the callers' slice headers -- a
+     * ring apart from the receiver's, since a write and a parse of one batch may be in flight on different streams */
     int *d_wstat; uint8_t *d_sw_tab, *d_sw_scratch;
-    uint8_t *h_wstage[NSTAGE], *d_wstage[NSTAGE]; size_t wstage_cap[NSTAGE]; hipEvent_t wstage_done[NSTAGE]; int wstage_used[NSTAGE], wstage_head;
+    StageRing tx_stage;
     KTimer kt[KT_N];            /* the timed kernels; the events of a timer are made by its first launch */
     char err[256];
 };
@@ -134,6 +137,12 @@ template <class Owner> static int fail(Owner *o, int code, const char *fmt, ...)
 }
 #define HIPCHK(o, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(o, PCAMV_EHIP, "%s: %s", #call, hipGetErrorString(e_)); } while (0)
 #define TRY(call) do { const int rc_ = (call); if (rc_) return rc_; } while (0)
+/* behind the launches of an entry point: did the runtime take them all? */
+template <class Owner> static int launched(Owner *o)
+{
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? fail(o, PCAMV_EHIP, "kernel launch: %s", hipGetErrorString(e)) : 0;
+}
 /* rc of a call the batch made on behalf of context c: its error text becomes the context's */
 static int on_behalf(pcamv_ctx *c, const pcamv_batch *b, int rc)
 {
@@ -222,6 +231,10 @@ static hipError_t ring_create(DescRing &r)
     return e;
 }
 static void ring_destroy(DescRing &r) { for (int i = 0; i < NRING; i++) if (r.done[i]) hipEventDestroy(r.done[i]); }
+static void stage_destroy(StageRing &R)
+{
+    for (int k = 0; k < NSTAGE; k++) { if (R.h[k]) hipHostFree(R.h[k]); hipFree(R.d[k]); if (R.done[k]) hipEventDestroy(R.done[k]); }
+}
 static void kt_destroy(KTimer &T) { for (int i = 0; i < NEV; i++) { if (T.e0[i]) hipEventDestroy(T.e0[i]); if (T.e1[i]) hipEventDestroy(T.e1[i]); } }
 
 extern "C" void pcamv_gpu_batch_destroy(pcamv_batch_t *b)
@@ -240,9 +253,9 @@ extern "C" void pcamv_gpu_batch_destroy(pcamv_batch_t *b)
     if (b->h_X) hipHostFree(b->h_X);
     hipFree(b->d_F); hipFree(b->d_E); hipFree(b->d_flow); hipFree(b->d_X); hipFree(b->d_chk);
     hipFree(b->d_sstat); hipFree(b->d_sp_tab); hipFree(b->d_sp_scratch);
-    for (int k = 0; k < NSTAGE; k++) { if (b->h_stage[k]) hipHostFree(b->h_stage[k]); hipFree(b->d_stage[k]); if (b->stage_done[k]) hipEventDestroy(b->stage_done[k]); }
+    stage_destroy(b->rx_stage);
     hipFree(b->d_wstat); hipFree(b->d_sw_tab); hipFree(b->d_sw_scratch);
-    for (int k = 0; k < NSTAGE; k++) { if (b->h_wstage[k]) hipHostFree(b->h_wstage[k]); hipFree(b->d_wstage[k]); if (b->wstage_done[k]) hipEventDestroy(b->wstage_done[k]); }
+    stage_destroy(b->tx_stage);
     ring_destroy(b->ring); ring_destroy(b->xring);
     for (KTimer &T : b->kt) kt_destroy(T);
     free(b->ctx);
@@ -576,6 +589,38 @@ static int ring_release(pcamv_batch *b, DescRing &r, int slot, hipStream_t st)
     r.used[slot] = 1;
     return 0;
 }
+/* the staging ring's next buffer with room for `total` bytes (regrown with a quarter to spare), once it is no longer in flight */
+static int stage_take(pcamv_batch *b, StageRing &R, size_t total, int *k_out)
+{
+    const int k = R.head;
+    R.head = (k + 1) % NSTAGE;
+    if (!R.done[k]) HIPCHK(b, hipEventCreateWithFlags(&R.done[k], hipEventDisableTiming));
+    if (R.used[k]) HIPCHK(b, hipEventSynchronize(R.done[k]));
+    if (total > R.cap[k]) {
+        if (R.h[k]) hipHostFree(R.h[k]);
+        hipFree(R.d[k]); R.h[k] = NULL; R.d[k] = NULL; R.cap[k] = 0;
+        const size_t cap = total + total / 4;
+        HIPCHK(b, hipHostMalloc((void **)&R.h[k], cap, hipHostMallocDefault));
+        HIPCHK(b, dalloc(&R.d[k], cap));
+        R.cap[k] = cap;
+    }
+    *k_out = k;
+    return 0;
+}
+/* what was queued on `st` so far is what reads buffer k: called once the kernels that read its device side are queued */
+static int stage_release(pcamv_batch *b, StageRing &R, int k, hipStream_t st)
+{
+    HIPCHK(b, hipEventRecord(R.done[k], st));
+    R.used[k] = 1;
+    return 0;
+}
+/* the first `total` bytes of buffer k to the device, one copy on `st`.  From here on the buffer is in flight whatever happens to the
+ * kernels: the event stands for the copy until stage_release moves it behind the kernels that read the device side */
+static int stage_send(pcamv_batch *b, StageRing &R, int k, size_t total, hipStream_t st)
+{
+    HIPCHK(b, hipMemcpyAsync(R.d[k], R.h[k], total, hipMemcpyHostToDevice, st));
+    return stage_release(b, R, k, st);
+}
 /* take the next descriptor slot, fill it from the contexts' current FrameDev/EmbedDev and queue its upload */
 static int batch_push_descs(pcamv_batch *b, hipStream_t st, const FrameDev **dF, const EmbedDev **dE, int *slot_out)
 {
@@ -692,8 +737,7 @@ static int batch_launch(pcamv_batch *b, int what, hipStream_t st)
             diag_launch(b->n_diag, F, [&](int cnt, int d) { pcamv_launch_pass2_diag(P2D_PASS2 | P2D_DEBLOCK, cnt, G, st, dF, d); });
         }
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(b, PCAMV_EHIP, "kernel launch: %s", hipGetErrorString(e));
+    TRY(launched(b));
     return ring_release(b, b->ring, slot, st);
 }
 /* after a synchronisation: did the dataflow kernel of the last step give up on a bounded spin? */
@@ -1091,8 +1135,7 @@ extern "C" int pcamv_gpu_batch_extract_step(pcamv_batch_t *b, float emrate, void
     const ExtractDev *dX; int slot;
     TRY(batch_push_xdescs(b, st, &dX, &slot));
     extract_launch(b, dX, b->n, b->ctx[0]->cap, emrate, st);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(b, PCAMV_EHIP, "kernel launch: %s", hipGetErrorString(e));
+    TRY(launched(b));
     return ring_release(b, b->xring, slot, st);
 }
 /* One frame from host records holding FINAL motion (what pcamv_gpu_parse_pslice_* reads out of a stream): uploaded, then the same
@@ -1111,8 +1154,7 @@ extern "C" int pcamv_gpu_extract_pframe(pcamv_ctx_t *c, const pcamv_mb_t *mbs, f
     const ExtractDev *dX; int slot;
     TRY(on_behalf(c, b, batch_push_xdescs(b, c->stream, &dX, &slot)));
     extract_launch(b, dX, 1, c->cap, emrate, c->stream);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(c, PCAMV_EHIP, "kernel launch: %s", hipGetErrorString(e));
+    TRY(launched(c));
     TRY(on_behalf(c, b, ring_release(b, b->xring, slot, c->stream)));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     int hdr[8];
@@ -1124,39 +1166,60 @@ extern "C" int pcamv_gpu_extract_pframe(pcamv_ctx_t *c, const pcamv_mb_t *mbs, f
     if (bits_out && m_copy) HIPCHK(c, hipMemcpy(bits_out, c->d_rx_bits, (size_t)m_copy, hipMemcpyDeviceToHost));
     return rx_check(c, NULL);
 }
-/* ------------------------------------------------------------------ receiver from a stream (k_parse_pslice, k_parse_pslice_cavlc, pcamv_slice.hip.h) */
-/* The stream's entropy mode is stated by the call (cavlc = 0 / 1) and has to be the contexts': looked at before anything is set up,
- * so that a batch never holds the other mode's tables */
-static int slice_mode(pcamv_batch *b, int cavlc)
+/* ------------------------------------------------------------------ slice streams: what the receiver from one and the sender to one share */
+/* The stream's entropy mode is stated by the call (cavlc = 0 / 1) and has to be the contexts' (a batch is of one mode): looked at before
+ * anything is set up, so that a batch never holds the other mode's tables.
+ * for_cavlc / for_cabac: the caller's entry points of either mode and what they do, for the message */
+static int entropy_mode(pcamv_batch *b, int cavlc, const char *for_cavlc, const char *for_cabac)
 {
     for (int i = 0; i < b->n; i++) {
         pcamv_ctx *c = b->ctx[i];
-        if (!cavlc && !c->F.b_cabac) return fail(b, PCAMV_EUNSUP, "context %d was opened with --no-cabac: its slices are CAVLC, which pcamv_gpu_batch_extract_slices_cavlc* and pcamv_gpu_parse_pslice_cavlc_device parse", i);
-        if (cavlc && c->F.b_cabac) return fail(b, PCAMV_EUNSUP, "context %d was opened with CABAC: its slices are CABAC, which pcamv_gpu_batch_extract_slices* and pcamv_gpu_parse_pslice_cabac_device parse", i);
+        if (!cavlc && !c->F.b_cabac) return fail(b, PCAMV_EUNSUP, "context %d was opened with --no-cabac: its slices are CAVLC, which %s", i, for_cavlc);
+        if (cavlc && c->F.b_cabac) return fail(b, PCAMV_EUNSUP, "context %d was opened with CABAC: its slices are CABAC, which %s", i, for_cabac);
     }
     return 0;
 }
-/* what every launch of the parser needs of the batch: status words, the tables of its mode, scratch rows for pictures too wide for LDS */
-static int slice_setup(pcamv_batch *b, int cavlc)
+/* the tables of a mode as the one block its kernels read, made once: the SV_TAB_BYTES of sv_build_tables, or the standard's CABAC tables
+ * init_p[2 * nctx] | transition[256] | range_lps[512] for the nctx contexts the kernel keeps */
+static_assert(SP_TAB_INIT == 0 && SP_TAB_TRANS == 2 * SP_NCTX && SP_TAB_RLPS == 2 * SP_NCTX + 256 && SP_TAB_BYTES == 2 * SP_NCTX + 768, "k_parse_pslice reads another table block than entropy_tab makes");
+static_assert(SW_TAB_INIT == 0 && SW_TAB_TRANS == 2 * SW_NCTX && SW_TAB_RLPS == 2 * SW_NCTX + 256 && SW_TAB_BYTES == 2 * SW_NCTX + 768, "k_write_pslice reads another table block than entropy_tab makes");
+static int entropy_tab(pcamv_batch *b, uint8_t **d_tab, int cavlc, int nctx)
 {
-    const FrameDev &F = b->ctx[0]->F;
-    if (!b->d_sstat) HIPCHK(b, dalloc(&b->d_sstat, (size_t)b->n));
-    if (!b->d_sp_tab && cavlc) {
-        uint8_t tab[SV_TAB_BYTES];
-        if (sv_build_tables(tab)) return fail(b, PCAMV_EINVAL, "a CAVLC code of pcamv_entropy_tables.h does not fit the parser's table entry");
-        HIPCHK(b, dalloc(&b->d_sp_tab, (size_t)SV_TAB_BYTES));
-        HIPCHK(b, hipMemcpy(b->d_sp_tab, tab, sizeof(tab), hipMemcpyHostToDevice));
-    }
-    if (!b->d_sp_tab) {
-        uint8_t tab[SP_TAB_BYTES];
-        memcpy(tab + SP_TAB_INIT, pcamv_cabac_init_p, 2 * SP_NCTX); memcpy(tab + SP_TAB_TRANS, pcamv_cabac_transition, 256);
-        memcpy(tab + SP_TAB_RLPS, pcamv_cabac_range_lps, 512);
-        HIPCHK(b, dalloc(&b->d_sp_tab, (size_t)SP_TAB_BYTES));
-        HIPCHK(b, hipMemcpy(b->d_sp_tab, tab, sizeof(tab), hipMemcpyHostToDevice));
-    }
-    if (F.mb_w > b->sp_lds_cols && !b->d_sp_scratch) HIPCHK(b, dalloc(&b->d_sp_scratch, (size_t)b->n * (cavlc ? SV_ROW_BYTES : SP_ROW_BYTES) * F.mb_w));
+    uint8_t tab[SV_TAB_BYTES > SW_TAB_BYTES ? SV_TAB_BYTES : SW_TAB_BYTES];
+    static_assert(SP_NCTX <= SW_NCTX, "entropy_tab's block is sized for the writer's contexts");
+    if (*d_tab) return 0;
+    if (cavlc && sv_build_tables(tab)) return fail(b, PCAMV_EINVAL, "a CAVLC code of pcamv_entropy_tables.h does not fit the %stable entry", d_tab == &b->d_sp_tab ? "parser's " : "");
+    if (!cavlc) { memcpy(tab, pcamv_cabac_init_p, 2 * nctx); memcpy(tab + 2 * nctx, pcamv_cabac_transition, 256); memcpy(tab + 2 * nctx + 256, pcamv_cabac_range_lps, 512); }
+    const size_t bytes = cavlc ? (size_t)SV_TAB_BYTES : (size_t)2 * nctx + 768;
+    HIPCHK(b, dalloc(d_tab, bytes));
+    HIPCHK(b, hipMemcpy(*d_tab, tab, bytes, hipMemcpyHostToDevice));
     return 0;
 }
+/* the row buffers of a launch, one per slice: the bytes of each, and the allocation for pictures too wide for LDS */
+static size_t row_bytes(const pcamv_batch *b, int cavlc) { return (size_t)(cavlc ? SV_ROW_BYTES : SP_ROW_BYTES) * b->ctx[0]->F.mb_w; }
+static int scratch_rows(pcamv_batch *b, uint8_t **d_scratch, int cavlc)
+{
+    if (b->ctx[0]->F.mb_w > b->sp_lds_cols && !*d_scratch) HIPCHK(b, dalloc(d_scratch, (size_t)b->n * row_bytes(b, cavlc)));
+    return 0;
+}
+/* what every launch of a parser or a writer needs of the batch: status words, the tables of its mode, scratch rows */
+static int entropy_setup(pcamv_batch *b, int **d_stat, uint8_t **d_tab, uint8_t **d_scratch, int cavlc, int nctx)
+{
+    if (!*d_stat) HIPCHK(b, dalloc(d_stat, (size_t)b->n));
+    TRY(entropy_tab(b, d_tab, cavlc, nctx));
+    return scratch_rows(b, d_scratch, cavlc);
+}
+/* synchronises; the status words of the batch's last parse or write call */
+static int status_fetch(pcamv_batch *b, int *pcamv_batch::*d_stat, int32_t *status, const char *none_yet)
+{
+    if (!b || !status) return PCAMV_EINVAL;
+    HIPCHK(b, hipSetDevice(b->device));
+    if (!(b->*d_stat)) return fail(b, PCAMV_EINVAL, "%s", none_yet);
+    HIPCHK(b, hipDeviceSynchronize());
+    HIPCHK(b, hipMemcpy(status, b->*d_stat, sizeof(int32_t) * b->n, hipMemcpyDeviceToHost));
+    return 0;
+}
+/* ------------------------------------------------------------------ receiver from a stream (k_parse_pslice, k_parse_pslice_cavlc, pcamv_slice.hip.h) */
 /* the contexts can take parsed slices: (want_rx) a reservation each; their descriptors then point at the receive-side records */
 static int slice_contexts(pcamv_batch *b, int want_rx, float emrate)
 {
@@ -1175,7 +1238,7 @@ static void slice_launch(pcamv_batch *b, const ExtractDev *dX, SliceJobs J, int 
 {
     const FrameDev &F = b->ctx[0]->F;
     const int kt = cavlc ? KT_PARSE_PSLICE_CAVLC : KT_PARSE_PSLICE;
-    J.tab = b->d_sp_tab; J.scratch = b->d_sp_scratch; J.scratch_stride = (long long)(cavlc ? SV_ROW_BYTES : SP_ROW_BYTES) * F.mb_w;
+    J.tab = b->d_sp_tab; J.scratch = b->d_sp_scratch; J.scratch_stride = (long long)row_bytes(b, cavlc);
     J.mb_w = F.mb_w; J.mb_h = F.mb_h; J.lds_cols = b->sp_lds_cols;
     const int ev = kt_begin(b, kt, st);
     if (cavlc) hipLaunchKernelGGL(k_parse_pslice_cavlc, dim3(b->n), dim3(64), 0, st, dX, J);
@@ -1189,8 +1252,7 @@ static int slices_run(pcamv_batch *b, SliceJobs J, int cavlc, int extract, float
     TRY(batch_push_xdescs(b, st, &dX, &slot));
     slice_launch(b, dX, J, cavlc, st);
     if (extract) extract_launch(b, dX, b->n, b->ctx[0]->cap, emrate, st);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(b, PCAMV_EHIP, "kernel launch: %s", hipGetErrorString(e));
+    TRY(launched(b));
     return ring_release(b, b->xring, slot, st);
 }
 /* host slices into the next staging buffer: [off n][len n][start_bit n] int64, [qp n] int32 (zeros with cavlc: slice_qp is not read),
@@ -1204,19 +1266,9 @@ static int slices_stage(pcamv_batch *b, const pcamv_slice_t *sl, int cavlc, hipS
         if (sl[i].start_bit > ((size_t)1 << 40)) return fail(b, PCAMV_EINVAL, "slice %d: start bit %zu is beyond any slice", (int)i, sl[i].start_bit);
         total += (sl[i].len + 3) & ~(size_t)3;
     }
-    const int k = b->stage_head;
-    b->stage_head = (k + 1) % NSTAGE;
-    if (!b->stage_done[k]) HIPCHK(b, hipEventCreateWithFlags(&b->stage_done[k], hipEventDisableTiming));
-    if (b->stage_used[k]) HIPCHK(b, hipEventSynchronize(b->stage_done[k]));
-    if (total > b->stage_cap[k]) {
-        if (b->h_stage[k]) hipHostFree(b->h_stage[k]);
-        hipFree(b->d_stage[k]); b->h_stage[k] = NULL; b->d_stage[k] = NULL; b->stage_cap[k] = 0;
-        const size_t cap = total + total / 4;
-        HIPCHK(b, hipHostMalloc((void **)&b->h_stage[k], cap, hipHostMallocDefault));
-        HIPCHK(b, dalloc(&b->d_stage[k], cap));
-        b->stage_cap[k] = cap;
-    }
-    uint8_t *h = b->h_stage[k];
+    int k;
+    TRY(stage_take(b, b->rx_stage, total, &k));
+    uint8_t *h = b->rx_stage.h[k];
     long long *off = (long long *)h, *len = off + n, *start = len + n; int *qp = (int *)(start + n);
     size_t at = 0;
     for (size_t i = 0; i < n; i++) {
@@ -1224,21 +1276,11 @@ static int slices_stage(pcamv_batch *b, const pcamv_slice_t *sl, int cavlc, hipS
         memcpy(h + hdr + at, sl[i].rbsp, sl[i].len);
         at += (sl[i].len + 3) & ~(size_t)3;
     }
-    HIPCHK(b, hipMemcpyAsync(b->d_stage[k], h, total, hipMemcpyHostToDevice, st));
-    /* from here on the buffer is in flight whatever happens to the kernels: the event stands for the copy until stage_release moves it
-     * behind the kernels that read the device side */
-    HIPCHK(b, hipEventRecord(b->stage_done[k], st));
-    b->stage_used[k] = 1;
-    const uint8_t *d = b->d_stage[k];
+    TRY(stage_send(b, b->rx_stage, k, total, st));
+    const uint8_t *d = b->rx_stage.d[k];
     J->bytes = d + hdr; J->bytes_size = (long long)(total - hdr);
     J->off = (const long long *)d; J->len = J->off + n; J->start_bit = J->len + n; J->qp = (const int *)(J->start_bit + n);
     *stage_out = k;
-    return 0;
-}
-static int stage_release(pcamv_batch *b, int k, hipStream_t st)
-{
-    HIPCHK(b, hipEventRecord(b->stage_done[k], st));
-    b->stage_used[k] = 1;
     return 0;
 }
 static int slices_checked(pcamv_batch *b, float emrate, int want_rx, int cavlc)
@@ -1246,8 +1288,8 @@ static int slices_checked(pcamv_batch *b, float emrate, int want_rx, int cavlc)
     if (!b || emrate <= 0) return PCAMV_EINVAL;
     HIPCHK(b, hipSetDevice(b->device));
     TRY(batch_live(b));
-    TRY(slice_mode(b, cavlc));
-    TRY(slice_setup(b, cavlc));
+    TRY(entropy_mode(b, cavlc, "pcamv_gpu_batch_extract_slices_cavlc* and pcamv_gpu_parse_pslice_cavlc_device parse", "pcamv_gpu_batch_extract_slices* and pcamv_gpu_parse_pslice_cabac_device parse"));
+    TRY(entropy_setup(b, &b->d_sstat, &b->d_sp_tab, &b->d_sp_scratch, cavlc, SP_NCTX));
     return slice_contexts(b, want_rx, emrate);
 }
 static int extract_slices_host(pcamv_batch *b, const pcamv_slice_t *slices, int cavlc, float emrate, void *stream)
@@ -1257,7 +1299,7 @@ static int extract_slices_host(pcamv_batch *b, const pcamv_slice_t *slices, int 
     hipStream_t st = stream ? (hipStream_t)stream : b->ctx[0]->stream;
     SliceJobs J; int k;
     TRY(slices_stage(b, slices, cavlc, st, &J, &k));
-    const int rc = slices_run(b, J, cavlc, 1, emrate, st), rc2 = stage_release(b, k, st);      /* released on every path */
+    const int rc = slices_run(b, J, cavlc, 1, emrate, st), rc2 = stage_release(b, b->rx_stage, k, st);      /* released on every path */
     return rc ? rc : rc2;
 }
 static int extract_slices_device(pcamv_batch *b, const void *bytes, size_t bytes_size, const int64_t *off, const int64_t *len, const int64_t *start_bit,
@@ -1292,12 +1334,7 @@ extern "C" int pcamv_gpu_batch_extract_slices_cavlc_device(pcamv_batch_t *b, con
 }
 extern "C" int pcamv_gpu_batch_slice_status(pcamv_batch_t *b, int32_t *status)
 {
-    if (!b || !status) return PCAMV_EINVAL;
-    HIPCHK(b, hipSetDevice(b->device));
-    if (!b->d_sstat) return fail(b, PCAMV_EINVAL, "no slices were handed to this batch yet");
-    HIPCHK(b, hipDeviceSynchronize());
-    HIPCHK(b, hipMemcpy(status, b->d_sstat, sizeof(int32_t) * b->n, hipMemcpyDeviceToHost));
-    return 0;
+    return status_fetch(b, &pcamv_batch::d_sstat, status, "no slices were handed to this batch yet");
 }
 /* the parity probe: one slice from host bytes through k_parse_pslice (k_parse_pslice_cavlc), its records back */
 static int parse_pslice_device(pcamv_ctx_t *c, const uint8_t *rbsp, size_t len, size_t start_bit, int slice_qp, int cavlc, pcamv_mb_t *out_mb)
@@ -1309,7 +1346,7 @@ static int parse_pslice_device(pcamv_ctx_t *c, const uint8_t *rbsp, size_t len, 
     SliceJobs J; int k, rc = 0;
     TRY(on_behalf(c, b, slices_stage(b, &sl, cavlc, c->stream, &J, &k)));
     rc = slices_run(b, J, cavlc, 0, 1.0f, c->stream);
-    const int rc2 = stage_release(b, k, c->stream);                                     /* released on every path */
+    const int rc2 = stage_release(b, b->rx_stage, k, c->stream);                                     /* released on every path */
     TRY(on_behalf(c, b, rc ? rc : rc2));
     rc = 0;
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1355,8 +1392,7 @@ extern "C" int pcamv_gpu_batch_payload_check(pcamv_batch_t *b, int64_t *diff)
     int ev = kt_begin(b, KT_PAYLOAD_CHECK, st);
     hipLaunchKernelGGL(k_payload_check, dim3(b->n), dim3(256), 0, st, dX, b->d_chk);
     kt_end(b, KT_PAYLOAD_CHECK, ev, st);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(b, PCAMV_EHIP, "kernel launch: %s", hipGetErrorString(e));
+    TRY(launched(b));
     TRY(ring_release(b, b->xring, slot, st));
     HIPCHK(b, hipStreamSynchronize(st));
     static_assert(sizeof(long long) == sizeof(int64_t), "payload_check copies the counts as they are");
@@ -1370,36 +1406,16 @@ static int write_header_ok(const pcamv_slice_hdr_t *h)
 {
     return h->n_bits >= 0 && h->n_bits <= (1 << 24) && (!h->n_bits || h->bits) && h->nal_ref_idc >= 0 && h->nal_ref_idc <= 3 && h->nal_unit_type >= 0 && h->nal_unit_type <= 31;
 }
-/* What every launch of a writer needs of the batch.  The stream's entropy mode is stated by the call (cavlc = 0 / 1) and has to be the
- * contexts' (a batch is of one mode): looked at before anything is set up. */
+/* what every launch of a writer needs of the batch, once its mode is the contexts' and each of them has a frame to write (a batch is of
+ * one mode, pcamv_gpu_batch_create: the first context decides the mode check, so it may run for all before the frames are looked at) */
 static int write_setup(pcamv_batch *b, int cavlc)
 {
-    for (int i = 0; i < b->n; i++) {
-        pcamv_ctx *c = b->ctx[i];
-        if (!cavlc && !c->F.b_cabac) return fail(b, PCAMV_EUNSUP, "context %d was opened with --no-cabac: its slices are CAVLC, which pcamv_gpu_write_pslice_cavlc and pcamv_gpu_batch_write_step_cavlc write", i);
-        if (cavlc && c->F.b_cabac) return fail(b, PCAMV_EUNSUP, "context %d was opened with CABAC: its slices are CABAC, which pcamv_gpu_write_pslice and pcamv_gpu_batch_write_step write", i);
-        if (!c->last) return fail(b, PCAMV_EINVAL, "context %d has analysed no frame yet: there is nothing to write", i);
-    }
-    const FrameDev &F = b->ctx[0]->F;
-    if (!b->d_wstat) HIPCHK(b, dalloc(&b->d_wstat, (size_t)b->n));
-    if (!b->d_sw_tab && cavlc) {
-        uint8_t tab[SV_TAB_BYTES];
-        if (sv_build_tables(tab)) return fail(b, PCAMV_EINVAL, "a CAVLC code of pcamv_entropy_tables.h does not fit the table entry");
-        HIPCHK(b, dalloc(&b->d_sw_tab, (size_t)SV_TAB_BYTES));
-        HIPCHK(b, hipMemcpy(b->d_sw_tab, tab, sizeof(tab), hipMemcpyHostToDevice));
-    }
-    if (!b->d_sw_tab) {
-        uint8_t tab[SW_TAB_BYTES];
-        memcpy(tab + SW_TAB_INIT, pcamv_cabac_init_p, 2 * SW_NCTX); memcpy(tab + SW_TAB_TRANS, pcamv_cabac_transition, 256);
-        memcpy(tab + SW_TAB_RLPS, pcamv_cabac_range_lps, 512);
-        HIPCHK(b, dalloc(&b->d_sw_tab, (size_t)SW_TAB_BYTES));
-        HIPCHK(b, hipMemcpy(b->d_sw_tab, tab, sizeof(tab), hipMemcpyHostToDevice));
-    }
-    if (F.mb_w > b->sp_lds_cols && !b->d_sw_scratch) HIPCHK(b, dalloc(&b->d_sw_scratch, (size_t)b->n * (cavlc ? SV_ROW_BYTES : SP_ROW_BYTES) * F.mb_w));
-    return 0;
+    TRY(entropy_mode(b, cavlc, "pcamv_gpu_write_pslice_cavlc and pcamv_gpu_batch_write_step_cavlc write", "pcamv_gpu_write_pslice and pcamv_gpu_batch_write_step write"));
+    for (int i = 0; i < b->n; i++) if (!b->ctx[i]->last) return fail(b, PCAMV_EINVAL, "context %d has analysed no frame yet: there is nothing to write", i);
+    return entropy_setup(b, &b->d_wstat, &b->d_sw_tab, &b->d_sw_scratch, cavlc, SW_NCTX);
 }
 /* the callers' headers into the next staging buffer -- n_hdr entries of SW_HDR_WORDS words, then the bits of each at a multiple of
- * 4 -- with one copy on `st`; *stage_out is released (write_stage_release) once the kernel that reads it is queued */
+ * 4 -- with one copy on `st`; *stage_out is released (stage_release) once the kernel that reads it is queued */
 static int write_stage(pcamv_batch *b, const pcamv_slice_hdr_t *hdrs, int n_hdr, hipStream_t st, const int **d_hdr, int *stage_out)
 {
     static const pcamv_slice_hdr_t none = {NULL, 0, 0, 2, 1};
@@ -1409,19 +1425,9 @@ static int write_stage(pcamv_batch *b, const pcamv_slice_hdr_t *hdrs, int n_hdr,
         if (!write_header_ok(&hdrs[i])) return fail(b, PCAMV_EINVAL, "slice header %d: bits missing, n_bits, nal_ref_idc or nal_unit_type out of range", i);
         total += ((size_t)(hdrs[i].n_bits + 7) / 8 + 3) & ~(size_t)3;
     }
-    const int k = b->wstage_head;
-    b->wstage_head = (k + 1) % NSTAGE;
-    if (!b->wstage_done[k]) HIPCHK(b, hipEventCreateWithFlags(&b->wstage_done[k], hipEventDisableTiming));
-    if (b->wstage_used[k]) HIPCHK(b, hipEventSynchronize(b->wstage_done[k]));
-    if (total > b->wstage_cap[k]) {
-        if (b->h_wstage[k]) hipHostFree(b->h_wstage[k]);
-        hipFree(b->d_wstage[k]); b->h_wstage[k] = NULL; b->d_wstage[k] = NULL; b->wstage_cap[k] = 0;
-        const size_t cap = total + total / 4;
-        HIPCHK(b, hipHostMalloc((void **)&b->h_wstage[k], cap, hipHostMallocDefault));
-        HIPCHK(b, dalloc(&b->d_wstage[k], cap));
-        b->wstage_cap[k] = cap;
-    }
-    uint8_t *h = b->h_wstage[k];
+    int k;
+    TRY(stage_take(b, b->tx_stage, total, &k));
+    uint8_t *h = b->tx_stage.h[k];
     int *w = (int *)h;
     size_t at = (size_t)n_hdr * SW_HDR_WORDS * 4;
     for (int i = 0; i < n_hdr; i++) {
@@ -1431,26 +1437,17 @@ static int write_stage(pcamv_batch *b, const pcamv_slice_hdr_t *hdrs, int n_hdr,
         if (nb) memcpy(h + at, hdrs[i].bits, nb);
         at += (nb + 3) & ~(size_t)3;
     }
-    HIPCHK(b, hipMemcpyAsync(b->d_wstage[k], h, total, hipMemcpyHostToDevice, st));
-    HIPCHK(b, hipEventRecord(b->wstage_done[k], st));
-    b->wstage_used[k] = 1;
-    *d_hdr = (const int *)b->d_wstage[k]; *stage_out = k;
-    return 0;
-}
-static int write_stage_release(pcamv_batch *b, int k, hipStream_t st)
-{
-    HIPCHK(b, hipEventRecord(b->wstage_done[k], st));
-    b->wstage_used[k] = 1;
+    TRY(stage_send(b, b->tx_stage, k, total, st));
+    *d_hdr = (const int *)b->tx_stage.d[k]; *stage_out = k;
     return 0;
 }
 /* one launch over the batch's contexts as they stand: J brings the destination and the mode */
 static int write_run(pcamv_batch *b, WriteJobs J, const pcamv_slice_hdr_t *hdrs, int n_hdr, int cavlc, hipStream_t st)
 {
-    const FrameDev &F0 = b->ctx[0]->F;
     int k;
     TRY(write_stage(b, hdrs, n_hdr, st, &J.hdr, &k));
     J.n_hdr = hdrs ? n_hdr : 1;
-    J.status = b->d_wstat; J.tab = b->d_sw_tab; J.scratch = b->d_sw_scratch; J.scratch_stride = (long long)(cavlc ? SV_ROW_BYTES : SP_ROW_BYTES) * F0.mb_w;
+    J.status = b->d_wstat; J.tab = b->d_sw_tab; J.scratch = b->d_sw_scratch; J.scratch_stride = (long long)row_bytes(b, cavlc);
     J.lds_cols = b->sp_lds_cols;
     const FrameDev *dF; const EmbedDev *dE; int slot;
     int rc = batch_push_descs(b, st, &dF, &dE, &slot);
@@ -1460,10 +1457,10 @@ static int write_run(pcamv_batch *b, WriteJobs J, const pcamv_slice_hdr_t *hdrs,
         if (cavlc) pcamv_launch_write_pslice_cavlc((unsigned)b->n, st, dF, J);
         else pcamv_launch_write_pslice((unsigned)b->n, st, dF, J);
         kt_end(b, kt, ev, st);
-        const hipError_t e = hipGetLastError();
-        rc = e != hipSuccess ? fail(b, PCAMV_EHIP, "kernel launch: %s", hipGetErrorString(e)) : ring_release(b, b->ring, slot, st);
+        rc = launched(b);
+        if (!rc) rc = ring_release(b, b->ring, slot, st);
     }
-    const int rc2 = write_stage_release(b, k, st);                  /* released on every path */
+    const int rc2 = stage_release(b, b->tx_stage, k, st);                  /* released on every path */
     return rc ? rc : rc2;
 }
 /* Every context's last step as a CABAC (cavlc: CAVLC) P slice, final motion (the records with the flip map of the step's embedding stage), from one
@@ -1506,12 +1503,7 @@ extern "C" int pcamv_gpu_batch_write_step_cavlc(pcamv_batch_t *b, const pcamv_sl
  * outside the buffer) */
 extern "C" int pcamv_gpu_batch_write_status(pcamv_batch_t *b, int32_t *status)
 {
-    if (!b || !status) return PCAMV_EINVAL;
-    HIPCHK(b, hipSetDevice(b->device));
-    if (!b->d_wstat) return fail(b, PCAMV_EINVAL, "this batch has written no slices yet");
-    HIPCHK(b, hipDeviceSynchronize());
-    HIPCHK(b, hipMemcpy(status, b->d_wstat, sizeof(int32_t) * b->n, hipMemcpyDeviceToHost));
-    return 0;
+    return status_fetch(b, &pcamv_batch::d_wstat, status, "this batch has written no slices yet");
 }
 /* A capacity under which no slice of the context's picture size fails: SW_MB_BOUND bytes per macroblock (derived in
  * pcamv_slice_write.h from the most bits a decision, a level and an mvd can take), the header's bytes, the flush; as a NAL unit

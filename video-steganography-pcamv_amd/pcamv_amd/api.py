@@ -230,6 +230,11 @@ def rbsp_to_nal(rbsp, nal_ref_idc=2, nal_unit_type=1):
     return out[:n.value].tobytes()
 
 
+class _Slice(C.Structure):
+    """pcamv_slice_t"""
+    _fields_ = [("rbsp", C.c_void_p), ("len", C.c_size_t), ("start_bit", C.c_size_t), ("slice_qp", C.c_int32)]
+
+
 class _SliceHdr(C.Structure):
     _fields_ = [("bits", C.c_void_p), ("n_bits", C.c_int32), ("i_frame", C.c_int32), ("nal_ref_idc", C.c_int32), ("nal_unit_type", C.c_int32)]
 
@@ -465,19 +470,22 @@ class Encoder:
         """pcamv_gpu_parse_pslice_cabac_device: the records of one CABAC P slice (RBSP bytes, slice data behind bit hdr_bits, slice
         QP) parsed on the device by k_parse_pslice -- the parity probe of Batch.extract_slices; raises like parse_pslice_at"""
         data = np.frombuffer(bytes(rbsp), np.uint8)
-        mbs = np.zeros(self.n_mb, MB_DTYPE)
-        self.lib.pcamv_gpu_parse_pslice_cabac_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p]
-        self._chk(self.lib.pcamv_gpu_parse_pslice_cabac_device(self.ctx, _p(data), len(data), hdr_bits, qp, _p(mbs)), "parse_pslice_cabac_device")
-        return mbs
+        return self._parse_pslice_device("pcamv_gpu_parse_pslice_cabac_device", data, len(data), hdr_bits, qp)
 
     def parse_pslice_cavlc_device(self, rbsp, hdr_bits):
         """pcamv_gpu_parse_pslice_cavlc_device: the records of one CAVLC P slice (RBSP bytes, slice data from bit hdr_bits on; the
         context was opened with b_cabac = 0) parsed on the device by k_parse_pslice_cavlc -- the parity probe of
         Batch.extract_slices_cavlc; raises like parse_pslice_at"""
         data = np.frombuffer(bytes(rbsp), np.uint8) if len(rbsp) else np.zeros(1, np.uint8)
+        return self._parse_pslice_device("pcamv_gpu_parse_pslice_cavlc_device", data, len(rbsp), hdr_bits)
+
+    def _parse_pslice_device(self, call, data, n, hdr_bits, *qp):
+        """what parse_pslice_device and parse_pslice_cavlc_device share: `call` names the library's entry point, which takes the
+        slice QP (CABAC) or none; data: the slice's n bytes"""
         mbs = np.zeros(self.n_mb, MB_DTYPE)
-        self.lib.pcamv_gpu_parse_pslice_cavlc_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
-        self._chk(self.lib.pcamv_gpu_parse_pslice_cavlc_device(self.ctx, _p(data), len(rbsp), hdr_bits, _p(mbs)), "parse_pslice_cavlc_device")
+        fn = getattr(self.lib, call)
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t] + [C.c_int] * len(qp) + [C.c_void_p]
+        self._chk(fn(self.ctx, _p(data), n, hdr_bits, *qp, _p(mbs)), call[len("pcamv_gpu_"):])
         return mbs
 
     def slice_bound(self, hdr_bits=0, as_nal=False):
@@ -668,14 +676,7 @@ class Batch:
         """one CABAC P slice per context, a list of (rbsp bytes, hdr_bits, qp): staged with one copy, parsed on the device
         (k_parse_pslice, one wavefront per slice) and sent through the receiver, without a host sync.  Every context needs
         rx_reserve; a slice that does not parse appends nothing for its context (slice_status)"""
-        if len(slices) != len(self.encs):
-            raise PcamvError(f"{len(slices)} slices for a batch of {len(self.encs)} contexts")
-        class _Slice(C.Structure):
-            _fields_ = [("rbsp", C.c_void_p), ("len", C.c_size_t), ("start_bit", C.c_size_t), ("slice_qp", C.c_int32)]
-        keep = [np.frombuffer(bytes(s[0]), np.uint8) if len(s[0]) else np.zeros(1, np.uint8) for s in slices]
-        arr = (_Slice * len(slices))(*[_Slice(k.ctypes.data, len(s[0]), int(s[1]), int(s[2])) for k, s in zip(keep, slices)])
-        self.lib.pcamv_gpu_batch_extract_slices.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
-        self._slice_chk(self.lib.pcamv_gpu_batch_extract_slices(self.b, arr, emrate, C.c_void_p(stream or None)), "batch_extract_slices")
+        self._extract_slices("pcamv_gpu_batch_extract_slices", slices, emrate, stream, lambda s: int(s[2]))
 
     def extract_slices_device(self, data, off, length, hdr_bits, qp, emrate, stream=0):
         """the same on bytes already on the device: `data` a contiguous uint8 device tensor (borrowed, no copy), off / length /
@@ -683,37 +684,39 @@ class Batch:
         Ordering is the caller's: the work is queued on `stream` (0: the first context's own non-blocking stream, which waits for
         no other stream), so the tensors must be complete before the call -- produced on `stream`, or that stream made to wait
         for their producer (an event), or torch.cuda.synchronize() -- and must not be rewritten before the queued work is done"""
-        for t, size, what in ((data, 1, "data: uint8"), (off, 8, "off: int64"), (length, 8, "length: int64"), (hdr_bits, 8, "hdr_bits: int64"), (qp, 4, "qp: int32")):
-            if not _is_device_tensor(t) or not t.is_cuda or t.element_size() != size or not t.is_contiguous():
-                raise PcamvError(f"{what}, contiguous, on the device")
-        if any(t.numel() != len(self.encs) for t in (off, length, hdr_bits, qp)):
-            raise PcamvError(f"one entry per context ({len(self.encs)}) in off / length / hdr_bits / qp")
-        self.lib.pcamv_gpu_batch_extract_slices_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
-        self._slice_chk(self.lib.pcamv_gpu_batch_extract_slices_device(self.b, data.data_ptr(), data.numel(), off.data_ptr(), length.data_ptr(), hdr_bits.data_ptr(),
-                                                                       qp.data_ptr(), emrate, C.c_void_p(stream or None)), "batch_extract_slices_device")
+        self._extract_slices_device("pcamv_gpu_batch_extract_slices_device", data, off, length, hdr_bits, emrate, stream, qp)
 
     def extract_slices_cavlc(self, slices, emrate, stream=0):
         """extract_slices for --no-cabac contexts: one CAVLC P slice per context, a list of (rbsp bytes, hdr_bits), parsed by
         k_parse_pslice_cavlc; CABAC contexts are refused (unsupported)"""
-        if len(slices) != len(self.encs):
-            raise PcamvError(f"{len(slices)} slices for a batch of {len(self.encs)} contexts")
-        class _Slice(C.Structure):
-            _fields_ = [("rbsp", C.c_void_p), ("len", C.c_size_t), ("start_bit", C.c_size_t), ("slice_qp", C.c_int32)]
-        keep = [np.frombuffer(bytes(s[0]), np.uint8) if len(s[0]) else np.zeros(1, np.uint8) for s in slices]
-        arr = (_Slice * len(slices))(*[_Slice(k.ctypes.data, len(s[0]), int(s[1]), 0) for k, s in zip(keep, slices)])
-        self.lib.pcamv_gpu_batch_extract_slices_cavlc.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
-        self._slice_chk(self.lib.pcamv_gpu_batch_extract_slices_cavlc(self.b, arr, emrate, C.c_void_p(stream or None)), "batch_extract_slices_cavlc")
+        self._extract_slices("pcamv_gpu_batch_extract_slices_cavlc", slices, emrate, stream, lambda s: 0)
 
     def extract_slices_cavlc_device(self, data, off, length, hdr_bits, emrate, stream=0):
         """extract_slices_device for --no-cabac contexts: the same tensors without the QPs, the same ordering rule"""
-        for t, size, what in ((data, 1, "data: uint8"), (off, 8, "off: int64"), (length, 8, "length: int64"), (hdr_bits, 8, "hdr_bits: int64")):
+        self._extract_slices_device("pcamv_gpu_batch_extract_slices_cavlc_device", data, off, length, hdr_bits, emrate, stream)
+
+    def _extract_slices(self, call, slices, emrate, stream, qp):
+        """what extract_slices and extract_slices_cavlc share: `call` names the library's entry point, qp(slice) gives a slice's QP"""
+        if len(slices) != len(self.encs):
+            raise PcamvError(f"{len(slices)} slices for a batch of {len(self.encs)} contexts")
+        keep = [np.frombuffer(bytes(s[0]), np.uint8) if len(s[0]) else np.zeros(1, np.uint8) for s in slices]
+        arr = (_Slice * len(slices))(*[_Slice(k.ctypes.data, len(s[0]), int(s[1]), qp(s)) for k, s in zip(keep, slices)])
+        fn = getattr(self.lib, call)
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
+        self._slice_chk(fn(self.b, arr, emrate, C.c_void_p(stream or None)), call[len("pcamv_gpu_"):])
+
+    def _extract_slices_device(self, call, data, off, length, hdr_bits, emrate, stream, *qp):
+        """what extract_slices_device and extract_slices_cavlc_device share: `call` names the library's entry point, which takes
+        the QPs (CABAC) or none"""
+        per_ctx = [(off, 8, "off: int64"), (length, 8, "length: int64"), (hdr_bits, 8, "hdr_bits: int64")] + [(t, 4, "qp: int32") for t in qp]
+        for t, size, what in [(data, 1, "data: uint8")] + per_ctx:
             if not _is_device_tensor(t) or not t.is_cuda or t.element_size() != size or not t.is_contiguous():
                 raise PcamvError(f"{what}, contiguous, on the device")
-        if any(t.numel() != len(self.encs) for t in (off, length, hdr_bits)):
-            raise PcamvError(f"one entry per context ({len(self.encs)}) in off / length / hdr_bits")
-        self.lib.pcamv_gpu_batch_extract_slices_cavlc_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
-        self._slice_chk(self.lib.pcamv_gpu_batch_extract_slices_cavlc_device(self.b, data.data_ptr(), data.numel(), off.data_ptr(), length.data_ptr(), hdr_bits.data_ptr(),
-                                                                             emrate, C.c_void_p(stream or None)), "batch_extract_slices_cavlc_device")
+        if any(t.numel() != len(self.encs) for t, _, _ in per_ctx):
+            raise PcamvError(f"one entry per context ({len(self.encs)}) in {' / '.join(what.split(':')[0] for _, _, what in per_ctx)}")
+        fn = getattr(self.lib, call)
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * len(per_ctx) + [C.c_float, C.c_void_p]
+        self._slice_chk(fn(self.b, data.data_ptr(), data.numel(), *[t.data_ptr() for t, _, _ in per_ctx], emrate, C.c_void_p(stream or None)), call[len("pcamv_gpu_"):])
 
     def write_step(self, hdr, data, off, cap, length, as_nal=False, stream=0):
         """pcamv_gpu_batch_write_step: every context's last step written as a CABAC P slice (final motion) by one launch of
