@@ -264,6 +264,11 @@ if __name__ == "__main__":
         analysis_fixture("hostile_cut_hex_subme6_cavlc_psub8_qp0", 176, 144, "hex", 6, 0, 0x30, 0, 0, cabac=0, clip=hc.cut())
         analysis_fixture("hostile_limit_umh_subme7_qp26_mvr16", 176, 144, "umh", 7, 26, 0x10, 0, 0, clip=hc.limit(16), mv_range=16)
         sys.exit(0)
+    if "--geometry-only" in sys.argv:          # tests/geometry_cases.py: one macroblock, one column, one row (that module's seed)
+        analysis_fixture("tiny_1x1_hex_subme5", 16, 16, "hex", 5, 26, 0x10, 77, 0, noise=20)
+        analysis_fixture("col_1x9_umh_subme7", 16, 144, "umh", 7, 26, 0x10, 77, 0, noise=20)
+        analysis_fixture("row_11x1_hex_subme6_cavlc", 176, 16, "hex", 6, 26, 0x10, 77, 48, cabac=0, noise=12)
+        sys.exit(0)
     if "--rd-psub8-only" in sys.argv:          # x264_rd_cost_part: sub-8x8 partitions at --subme 6 / 7 (round 3)
         analysis_fixture("qcif_hex_subme6_psub8", 176, 144, "hex", 6, 26, 0x30, 61, 0, noise=30)
         analysis_fixture("qcif_hex_subme7_psub8_cavlc", 176, 144, "hex", 7, 20, 0x30, 62, 32, cabac=0, noise=40)

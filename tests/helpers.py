@@ -14,6 +14,10 @@ RD_FIXTURES = ["qcif_hex_subme6", "qcif_umh_subme7_cavlc", "qcif_dia_subme6_nops
 # tests/hostile_cases.py's pictures (saturated pixels, motion out of reach, cuts, MVs on the clip limit of an explicit --mvrange) at QP 0 / 51
 HOSTILE_ANALYSIS_FIXTURES = ["hostile_fastpan_hex_subme5_qp51"]
 HOSTILE_RD_FIXTURES = ["hostile_sat_umh_subme7_qp0", "hostile_cut_hex_subme6_cavlc_psub8_qp0", "hostile_limit_umh_subme7_qp26_mvr16"]
+# tests/geometry_cases.py's extremes, so that the device is compared with the reference's own output there too: one macroblock, one
+# column of 9 (CABAC, context states), one row of 11 (CAVLC sizes)
+GEOMETRY_ANALYSIS_FIXTURES = ["tiny_1x1_hex_subme5"]
+GEOMETRY_RD_FIXTURES = ["col_1x9_umh_subme7", "row_11x1_hex_subme6_cavlc"]
 
 
 def fixture_params(g, make_params, **over):

@@ -13,6 +13,8 @@ CABAC_FIXTURES = ["pslice_qcif_hex_subme5_final", "pslice_cif_umh_subme7_final",
                   "pslice_qcif_hex_subme6_qp34", "pslice_cif_dia_subme4_p4x4_qp16"]
 FINAL_FIXTURES = [n for n in CABAC_FIXTURES if n.endswith("_final")]
 LIVE_SHAPES = [(1056, 96), (96, 1056), (528, 192)]
+# one macroblock, one column, one row: the row buffers hold one column, or no macroblock has a top / top-left / top-right neighbour
+TINY_SHAPES = [(16, 16), (16, 144), (176, 16)]
 FIELDS = (("type", "i_type"), ("partition", "i_partition"), ("sub_partition", "i_sub_partition"), ("mv", "mv"))
 
 
@@ -81,15 +83,21 @@ def live_available():
     return refh.available()
 
 
-def live_slices(qp=22, noise=20):
-    """two chained P frames of each LIVE_SHAPES picture as the reference's own CABAC coder writes them:
+def live_clip(W, H, k, noise=20):
+    """the three pictures of the k-th shape of a list; the motionless columns on the left (P_SKIP) are 32 wide, 16 in a picture
+    32 wide, and absent in one 16 wide"""
+    from pcamv_amd.synth import make_clip
+    return make_clip(W, H, 3, seed=51 + k, static_cols=32 if W > 32 else 16 if W > 16 else 0, noise=noise)
+
+
+def live_slices(qp=22, noise=20, shapes=LIVE_SHAPES):
+    """two chained P frames of each picture of `shapes` as the reference's own CABAC coder writes them:
     yields (W, H, t, qp, slice bytes, the reference's records)"""
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
     import orc
     import refh
-    from pcamv_amd.synth import make_clip
-    for k, (W, H) in enumerate(LIVE_SHAPES):
-        clip = make_clip(W, H, 3, seed=51 + k, static_cols=32, noise=noise)
+    for k, (W, H) in enumerate(shapes):
+        clip = live_clip(W, H, k, noise)
         r = refh.Ref(W, H, qp=qp, me="hex", subme=6, mv_range=orc.level_mv_range(W, H), cabac=1, embed=1, inter_flags=0x31)
         ref, prev = clip[0], (None, None)
         for t in (1, 2):

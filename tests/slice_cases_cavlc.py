@@ -40,9 +40,8 @@ def live_slices(qp=22, noise=20, shapes=sc.LIVE_SHAPES):
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
     import orc
     import refh
-    from pcamv_amd.synth import make_clip
     for k, (W, H) in enumerate(shapes):
-        clip = make_clip(W, H, 3, seed=51 + k, static_cols=32, noise=noise)
+        clip = sc.live_clip(W, H, k, noise)
         r = refh.Ref(W, H, qp=qp, me="hex", subme=6, mv_range=orc.level_mv_range(W, H), cabac=0, embed=1, inter_flags=0x31)
         ref, prev = clip[0], (None, None)
         for t in (1, 2):

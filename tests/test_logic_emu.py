@@ -14,7 +14,7 @@ FIX = ["qcif_hex_subme5", "qcif_dia_subme2", "qcif_umh_subme4_psub8", "qcif_esa_
 
 
 @pytest.mark.parametrize("order", [1, 2], ids=["diagonal_phases", "dataflow_fused"])
-@pytest.mark.parametrize("name", FIX + helpers.HOSTILE_ANALYSIS_FIXTURES)
+@pytest.mark.parametrize("name", FIX + helpers.HOSTILE_ANALYSIS_FIXTURES + helpers.GEOMETRY_ANALYSIS_FIXTURES)
 def test_control_logic_matches_reference(name, order):
     g = helpers.load(name)
     W, H = int(g["width"]), int(g["height"])
@@ -35,7 +35,7 @@ def test_control_logic_matches_reference(name, order):
 # --subme 6 / 7: the RD mode decision in the shared control code.  With CABAC the context states chain the macroblocks of a
 # frame in raster order (order 3: raster, fused); CAVLC sizes depend on the left / top neighbours only, so the dataflow
 # schedule's orders apply as well.
-RD = [(n, o) for n in helpers.RD_FIXTURES + helpers.HOSTILE_RD_FIXTURES for o in ((3,) if "cavlc" not in n else (1, 2, 3))]
+RD = [(n, o) for n in helpers.RD_FIXTURES + helpers.HOSTILE_RD_FIXTURES + helpers.GEOMETRY_RD_FIXTURES for o in ((3,) if "cavlc" not in n else (1, 2, 3))]
 
 
 @pytest.mark.parametrize("name,order", RD, ids=[f"{n}-order{o}" for n, o in RD])
@@ -62,14 +62,15 @@ def test_rd_mode_decision_logic_matches_reference(name, order):
 
 def test_strip_layout_arithmetic():
     """Device layout of the luma reference planes (pcamv_common.h): the multiply-shift strip index is x / 28 for every x a
-    padded plane can have (up to 8K widths and beyond), a 4-byte fetch at any x -- and at x + 1 -- stays inside one strip's row, distinct
+    padded plane can have (from a 16-pixel picture, whose padding is four times its width, and 48 pixels, whose padded stride of 112 is
+    four strips exactly, up to 8K widths and beyond), a 4-byte fetch at any x -- and at x + 1 -- stays inside one strip's row, distinct
     pixels of a plane (up to the four repeated columns) never share a byte, and every byte lies inside the plane's allocation."""
     import ctypes as C
     lib = C.CDLL(emu.build())
     lib.emu_strip_offset.restype = C.c_longlong
     lib.emu_strip_plane_size.restype = C.c_longlong
     assert lib.emu_strip_index_first_bad(40000) == -1
-    for w, h in ((176, 144), (1920, 1088), (3840, 2160), (7680, 4320)):
+    for w, h in ((16, 16), (32, 16), (48, 48), (176, 144), (1920, 1088), (3840, 2160), (7680, 4320)):
         stride, lines = (w + 64 + 15) & ~15, h + 64
         psz = lib.emu_strip_plane_size(stride, lines)
         seen = {}

@@ -148,7 +148,8 @@ def test_sa8d_and_hadamard_ac_match_reference(prim_rd):
             assert L.orc_sa8d(ip, C.c_void_p(pix.ctypes.data), 32, C.c_void_p(other.ctypes.data), 16) == int(prim_rd["sa8d_res"][i, k])
 
 
-@pytest.mark.parametrize("name", helpers.ANALYSIS_FIXTURES + helpers.RD_FIXTURES + helpers.HOSTILE_ANALYSIS_FIXTURES + helpers.HOSTILE_RD_FIXTURES)
+@pytest.mark.parametrize("name", helpers.ANALYSIS_FIXTURES + helpers.RD_FIXTURES + helpers.HOSTILE_ANALYSIS_FIXTURES + helpers.HOSTILE_RD_FIXTURES +
+                         helpers.GEOMETRY_ANALYSIS_FIXTURES + helpers.GEOMETRY_RD_FIXTURES)
 def test_pframe_analysis_matches_reference(name):
     g = helpers.load(name)
     W, H = int(g["width"]), int(g["height"])
