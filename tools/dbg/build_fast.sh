@@ -5,7 +5,7 @@
 #   [EXTRA=<flags>] [OUT=<library>] tools/dbg/build_fast.sh [units...] [--prof]
 set -e
 cd "$(dirname "$0")/../../video-steganography-pcamv_amd"
-ALL="gpu pass2_diag tesa rd rd_lo rd_spec rd_spec2 rd_spec4 rd_tesa"        # csrc/pcamv_<unit>.hip: pcamv_amd/api.py UNITS
+ALL="gpu pass2_diag slice_write slice_write_cavlc tesa rd rd_lo rd_spec rd_spec2 rd_spec4 rd_tesa"        # csrc/pcamv_<unit>.hip: pcamv_amd/api.py UNITS
 FLAGS="--offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -std=c++17 -Wno-unused-value -Wno-unused-result"
 UNITS=""; PROF=0
 for a in "$@"; do if [ "$a" = "--prof" ]; then PROF=1; else UNITS="$UNITS $a"; fi; done

@@ -884,6 +884,155 @@ __device__ __forceinline__ int dpp_x4(int v)
     const int a = __builtin_amdgcn_update_dpp(0, v, 0x104, 0xf, 0x5, false);
     return __builtin_amdgcn_update_dpp(a, v, 0x114, 0xf, 0xa, false);
 }
+/* ---- the per-lane body of the two-lanes-per-block layout (h = 0: rows 0 and 3, h = 1: rows 1 and 2 of the 4x4 block at (px,py)),
+ * shared by prim_mb_transform and the chroma pass of prim_mb_transform4.  Both lanes of a block must be active together: the
+ * partner exchange is a DPP, and a DPP read of a lane that is switched off returns 0. ---- */
+/* load two rows of fenc - pred, horizontal + split vertical transform, quantise / scan mask / score / dequantise the lane's eight
+ * coefficients: c[j] = (horizontal frequency j, vertical frequency 2 h), c[4 + j] = (j, 2 h + 1); zm, nz and score are the block's
+ * (both lanes), *rawdc the unquantised DC in the h = 0 lane (chroma: cleared before quantisation).  lv: also leave the quantised
+ * levels in scan order in lv_out (h->dct.luma4x4), for the entropy coder's size walk */
+template <class QT>
+__device__ __forceinline__ void half4x4_forward(const QT &Q, const uint8_t *fenc, const uint8_t *pred, int px, int py, int h, bool is_l, bool act,
+                                                int lv, int16_t *lv_out, int c[8], int *nz_out, int *score_out, int *rawdc_out)
+{
+    const int ra = h ? 1 : 0, rb = h ? 2 : 3;                                      /* this lane's two rows */
+    const int sgn = h ? -1 : 1;
+    int nz = 0, score = 0, big = 0;
+    unsigned zm = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) c[k] = 0;
+    if (act) {
+        int t[2][4];
+#pragma unroll
+        for (int k = 0; k < 2; k++) {
+            const int y = k ? rb : ra;
+            const uint32_t e = lds4(fenc + (py + y) * 16 + px), p = lds4(pred + (py + y) * 16 + px);
+            const int d0 = (int)(e & 255) - (int)(p & 255), d1 = (int)((e >> 8) & 255) - (int)((p >> 8) & 255);
+            const int d2 = (int)((e >> 16) & 255) - (int)((p >> 16) & 255), d3 = (int)(e >> 24) - (int)(p >> 24);
+            const int s03 = d0 + d3, s12 = d1 + d2, d03 = d0 - d3, d12 = d1 - d2;
+            t[k][0] = s03 + s12; t[k][1] = 2 * d03 + d12; t[k][2] = s03 - s12; t[k][3] = d03 - 2 * d12;
+        }
+        /* vertical: rows (0, 3) / (1, 2) in-lane, then with the partner: h = 0: s03 + s12, 2 d03 + d12; h = 1: s03 - s12, d03 - 2 d12 */
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int s = t[0][j] + t[1][j], d = t[0][j] - t[1][j];
+            c[j] = mad24s(s, sgn, dpp_qp1(s));
+            c[4 + j] = mad24s(d, 2 * sgn, dpp_qp1(d));
+        }
+    }
+    *rawdc_out = h ? 0 : c[0];
+    if (!is_l && !h) c[0] = 0;
+    {
+        /* quantiser and dequantiser of the lane's eight positions: class (j & 1) + (vertical frequency & 1) -- c[0..3]: 0 1 0 1, c[4..7]: 1 2 1 2 */
+        const int mf0 = is_l ? Q.q_mf[0][0] : Q.q_mf[1][0], mf1 = is_l ? Q.q_mf[0][1] : Q.q_mf[1][1], mf2 = is_l ? Q.q_mf[0][2] : Q.q_mf[1][2];
+        const int bs0 = is_l ? Q.q_bias[0][0] : Q.q_bias[1][0], bs1 = is_l ? Q.q_bias[0][1] : Q.q_bias[1][1], bs2 = is_l ? Q.q_bias[0][2] : Q.q_bias[1][2];
+        const int dq0 = is_l ? Q.dq_mf[0] : Q.dq_mf_c[0], dq1 = is_l ? Q.dq_mf[1] : Q.dq_mf_c[1], dq2 = is_l ? Q.dq_mf[2] : Q.dq_mf_c[2];
+        const int bm0 = (int)mul24u((uint32_t)bs0, (uint32_t)mf0), bm1 = (int)mul24u((uint32_t)bs1, (uint32_t)mf1), bm2 = (int)mul24u((uint32_t)bs2, (uint32_t)mf2);
+        /* scan positions (inverse zigzag of raster index 4 j + vertical frequency): vf 0: 0 1 5 6, 1: 2 4 7 12, 2: 3 8 11 13, 3: 9 10 14 15 */
+        int mx = 0, mn = 0;
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const int j = k & 3, odd = k >> 2, cls = (j & 1) + odd;
+            const int mf = cls == 0 ? mf0 : cls == 1 ? mf1 : mf2, bm = cls == 0 ? bm0 : cls == 1 ? bm1 : bm2;
+            constexpr int pos0[8] = {0, 1, 5, 6, 2, 4, 7, 12}, pos1[8] = {3, 8, 11, 13, 9, 10, 14, 15};
+            const int q = mad24s(c[k], mf, c[k] < 0 ? 65535 - bm : bm) >> 16;
+            c[k] = q;
+            zm |= q != 0 ? (h ? 1u << pos1[k] : 1u << pos0[k]) : 0u;
+            mx = imax(mx, q); mn = imin(mn, q);
+        }
+        big = mx > 1 || mn < -1;
+        zm |= (unsigned)dpp_qp1((int)zm);
+        big |= dpp_qp1(big);
+        nz = zm != 0;
+        if (lv && nz && act) {          /* the quantised levels in scan order (h->dct.luma4x4), for the entropy coder's size walk */
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                constexpr int pos0[8] = {0, 1, 5, 6, 2, 4, 7, 12}, pos1[8] = {3, 8, 11, 13, 9, 10, 14, 15};
+                lv_out[h ? pos1[k] : pos0[k]] = (int16_t)c[k];
+            }
+        }
+        if (nz) {
+            const unsigned zr = is_l ? zm << 1 : zm, z = zr | 1u;
+            const unsigned s1 = z << 1, s3 = s1 | s1 << 1 | z << 3, s6 = s3 | s3 << 3;
+            score = big ? 9 : __builtin_popcount(zr & s1) + __builtin_popcount(zr & s3) + __builtin_popcount(zr & s6);
+            const int qbits = (is_l ? Q.qp : Q.chroma_qp) / 6 - 4;
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                const int cls = (k & 1) + (k >> 2), dqv = cls == 0 ? dq0 : cls == 1 ? dq1 : dq2;
+                c[k] = qbits >= 0 ? (int16_t)(mul24s(c[k], dqv) << qbits) : (int16_t)((mul24s(c[k], dqv) + (1 << (-qbits - 1))) >> (-qbits));
+            }
+        }
+    }
+    *nz_out = nz; *score_out = score;
+}
+/* chroma DC of a plane whose four blocks sit in eight consecutive lanes (block k in lanes 2 k + h of the eight): 2x2 transform over
+ * the h = 0 lanes, two apart -- butterflies with lane ^ 2, then lane ^ 4; the network leaves coefficient (k & 1) * 2 + (k >> 1) in
+ * the lane of block k -- zigzag_scan_2x2_dc's place k -- and, run again on the quantised values, block k's reconstructed DC in the
+ * lane of block k.  *dcq: the quantised coefficient of that place (h = 0 lanes), *nzdc: some DC of the plane survives, *rdc: the
+ * block's reconstructed DC in both of its lanes */
+template <class QT>
+__device__ __forceinline__ void half4x4_chroma_dc(const QT &Q, int lane, int h, bool is_c, int rawdc, int *dcq_out, int *nzdc_out, int *rdc_out)
+{
+    const int s2 = lane & 2 ? -1 : 1, s4 = lane & 4 ? -1 : 1;
+    int cdc = mad24s(rawdc, s2, dpp_qp2(rawdc));
+    cdc = mad24s(cdc, s4, dpp_x4(cdc));
+    int dcq;
+    { const int mf = Q.q_mf[1][0] >> 1, bias = Q.q_bias[1][0] << 1;
+      dcq = cdc > 0 ? ((bias + cdc) * mf >> 16) : -((bias - cdc) * mf >> 16); }
+    if (h || !is_c) dcq = 0;
+    int nzdc = dcq != 0; nzdc |= dpp_qp1(nzdc); nzdc |= dpp_qp2(nzdc); nzdc |= dpp_hmir(nzdc);
+    int dmf = Q.dq_mf_c[0], qbits = Q.chroma_qp / 6 - 5;
+    if (qbits > 0) { dmf <<= qbits; qbits = 0; }
+    int idc = mad24s(dcq, s2, dpp_qp2(dcq));
+    idc = mad24s(idc, s4, dpp_x4(idc));
+    int rdc = (int16_t)(idc * dmf >> -qbits);
+    {   /* both lanes of the block (the exchange made by all lanes, THEN the choice: inside `h ? dpp : x` only the odd lanes would
+         * execute it, and a DPP read of a lane that is switched off returns 0) */
+        const int other = dpp_qp1(rdc);
+        rdc = h ? other : rdc;
+    }
+    *dcq_out = dcq; *nzdc_out = nzdc; *rdc_out = rdc;
+}
+/* inverse of the dequantised coefficients added to the lane's two rows of pred: per vertical frequency the horizontal pass
+ * (in-lane), then the vertical one with the partner */
+__device__ __forceinline__ void half4x4_inverse_add(uint8_t *pred, int px, int py, int h, const int c[8])
+{
+    const int ra = h ? 1 : 0, rb = h ? 2 : 3, sgn = h ? -1 : 1;
+    int u[2][4];
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+        const int c0 = c[4 * k], c1 = c[4 * k + 1], c2 = c[4 * k + 2], c3 = c[4 * k + 3];
+        const int s02 = c0 + c2, d02 = c0 - c2, s13 = c1 + (c3 >> 1), d13 = (c1 >> 1) - c3;
+        u[k][0] = (int16_t)(s02 + s13); u[k][1] = (int16_t)(d02 + d13); u[k][2] = (int16_t)(d02 - d13); u[k][3] = (int16_t)(s02 - s13);
+    }
+    uint32_t oa = 0, ob = 0;
+    uint8_t *pa = pred + (py + ra) * 16 + px, *pb = pred + (py + rb) * 16 + px;
+    const uint32_t va = lds4(pa), vb = lds4(pb);
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        /* h = 0 holds t[0][i], t[1][i] and makes s02, s13; h = 1 holds t[2][i], t[3][i] and makes d02, d13 */
+        const int x = mad24s(u[0][i], sgn, dpp_qp1(u[0][i])) + 32;
+        const int y = mad24s(u[1][i], sgn, dpp_qp1(u[1][i]) >> 1);
+        const int r_a = (int16_t)((x + y) >> 6), r_b = (int16_t)((x - y) >> 6);      /* rows 0 / 3 (h = 0), 1 / 2 (h = 1) */
+        oa |= (uint32_t)clip3i((int)((va >> (8 * i)) & 255) + r_a, 0, 255) << (8 * i);
+        ob |= (uint32_t)clip3i((int)((vb >> (8 * i)) & 255) + r_b, 0, 255) << (8 * i);
+    }
+    sts4(pa, oa); sts4(pb, ob);
+}
+/* DC-only chroma block: the reconstructed DC added to the lane's two rows */
+__device__ __forceinline__ void half4x4_add_dc(uint8_t *pred, int px, int py, int h, int rdc)
+{
+    const int ra = h ? 1 : 0, rb = h ? 2 : 3;
+    const int v = (rdc + 32) >> 6;
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+        uint8_t *dst = pred + (py + (k ? rb : ra)) * 16 + px;
+        uint32_t p = lds4(dst), o = 0;
+#pragma unroll
+        for (int x = 0; x < 4; x++) o |= (uint32_t)clip3i((int)((p >> (8 * x)) & 255) + v, 0, 255) << (8 * x);
+        sts4(dst, o);
+    }
+}
 /* Transform stage of x264_macroblock_encode for an inter macroblock (encoder/macroblock.c:277-372,
  * 696-753): residual transform + quantisation, luma 8x8 / macroblock decimation, chroma DC 2x2 and the
  * chroma decimation rule, dequantisation, inverse transform added to the prediction in L->pred.
@@ -911,74 +1060,9 @@ __device__ __forceinline__ void prim_mb_transform(const FrameDev &F, MBLocal *L,
     const int cb = (lane - 32) >> 1, ch = cb >> 2, ci = cb & 3;
     const int px = is_l ? 4 * blk_x_of(blk) : ch * 8 + (ci & 1) * 4;
     const int py = is_l ? 4 * blk_y_of(blk) : 16 + (ci >> 1) * 4;
-    const int ra = h ? 1 : 0, rb = h ? 2 : 3;                                      /* this lane's two rows */
-    const int sgn = h ? -1 : 1;
-    int c[8] = {0, 0, 0, 0, 0, 0, 0, 0};           /* coefficients: c[j] = (horizontal frequency j, vertical frequency 2 h), c[4 + j] = (j, 2 h + 1) */
-    int nz = 0, score = 0, rawdc = 0, big = 0;
-    unsigned zm = 0;
-    if (is_l || is_c) {
-        int t[2][4];
-#pragma unroll
-        for (int k = 0; k < 2; k++) {
-            const int y = k ? rb : ra;
-            const uint32_t e = lds4(L->fenc + (py + y) * 16 + px), p = lds4(L->pred + (py + y) * 16 + px);
-            const int d0 = (int)(e & 255) - (int)(p & 255), d1 = (int)((e >> 8) & 255) - (int)((p >> 8) & 255);
-            const int d2 = (int)((e >> 16) & 255) - (int)((p >> 16) & 255), d3 = (int)(e >> 24) - (int)(p >> 24);
-            const int s03 = d0 + d3, s12 = d1 + d2, d03 = d0 - d3, d12 = d1 - d2;
-            t[k][0] = s03 + s12; t[k][1] = 2 * d03 + d12; t[k][2] = s03 - s12; t[k][3] = d03 - 2 * d12;
-        }
-        /* vertical: rows (0, 3) / (1, 2) in-lane, then with the partner: h = 0: s03 + s12, 2 d03 + d12; h = 1: s03 - s12, d03 - 2 d12 */
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int s = t[0][j] + t[1][j], d = t[0][j] - t[1][j];
-            c[j] = mad24s(s, sgn, dpp_qp1(s));
-            c[4 + j] = mad24s(d, 2 * sgn, dpp_qp1(d));
-        }
-    }
-    rawdc = h ? 0 : c[0];
-    if (!is_l && !h) c[0] = 0;
-    {
-        /* quantiser and dequantiser of the lane's eight positions: class (j & 1) + (vertical frequency & 1) -- c[0..3]: 0 1 0 1, c[4..7]: 1 2 1 2 */
-        const int mf0 = is_l ? Q.q_mf[0][0] : Q.q_mf[1][0], mf1 = is_l ? Q.q_mf[0][1] : Q.q_mf[1][1], mf2 = is_l ? Q.q_mf[0][2] : Q.q_mf[1][2];
-        const int bs0 = is_l ? Q.q_bias[0][0] : Q.q_bias[1][0], bs1 = is_l ? Q.q_bias[0][1] : Q.q_bias[1][1], bs2 = is_l ? Q.q_bias[0][2] : Q.q_bias[1][2];
-        const int dq0 = is_l ? Q.dq_mf[0] : Q.dq_mf_c[0], dq1 = is_l ? Q.dq_mf[1] : Q.dq_mf_c[1], dq2 = is_l ? Q.dq_mf[2] : Q.dq_mf_c[2];
-        const int bm0 = (int)mul24u((uint32_t)bs0, (uint32_t)mf0), bm1 = (int)mul24u((uint32_t)bs1, (uint32_t)mf1), bm2 = (int)mul24u((uint32_t)bs2, (uint32_t)mf2);
-        /* scan positions (inverse zigzag of raster index 4 j + vertical frequency): vf 0: 0 1 5 6, 1: 2 4 7 12, 2: 3 8 11 13, 3: 9 10 14 15 */
-        int mx = 0, mn = 0;
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const int j = k & 3, odd = k >> 2, cls = (j & 1) + odd;
-            const int mf = cls == 0 ? mf0 : cls == 1 ? mf1 : mf2, bm = cls == 0 ? bm0 : cls == 1 ? bm1 : bm2;
-            constexpr int pos0[8] = {0, 1, 5, 6, 2, 4, 7, 12}, pos1[8] = {3, 8, 11, 13, 9, 10, 14, 15};
-            const int q = mad24s(c[k], mf, c[k] < 0 ? 65535 - bm : bm) >> 16;
-            c[k] = q;
-            zm |= q != 0 ? (h ? 1u << pos1[k] : 1u << pos0[k]) : 0u;
-            mx = imax(mx, q); mn = imin(mn, q);
-        }
-        big = mx > 1 || mn < -1;
-        zm |= (unsigned)dpp_qp1((int)zm);
-        big |= dpp_qp1(big);
-        nz = zm != 0;
-        if (lv && nz && (is_l || is_c)) {          /* the quantised levels in scan order (h->dct.luma4x4), for the entropy coder's size walk */
-            int16_t *lv_out = L->coef[blk];
-#pragma unroll
-            for (int k = 0; k < 8; k++) {
-                constexpr int pos0[8] = {0, 1, 5, 6, 2, 4, 7, 12}, pos1[8] = {3, 8, 11, 13, 9, 10, 14, 15};
-                lv_out[h ? pos1[k] : pos0[k]] = (int16_t)c[k];
-            }
-        }
-        if (nz) {
-            const unsigned zr = is_l ? zm << 1 : zm, z = zr | 1u;
-            const unsigned s1 = z << 1, s3 = s1 | s1 << 1 | z << 3, s6 = s3 | s3 << 3;
-            score = big ? 9 : __builtin_popcount(zr & s1) + __builtin_popcount(zr & s3) + __builtin_popcount(zr & s6);
-            const int qbits = (is_l ? Q.qp : Q.chroma_qp) / 6 - 4;
-#pragma unroll
-            for (int k = 0; k < 8; k++) {
-                const int cls = (k & 1) + (k >> 2), dqv = cls == 0 ? dq0 : cls == 1 ? dq1 : dq2;
-                c[k] = qbits >= 0 ? (int16_t)(mul24s(c[k], dqv) << qbits) : (int16_t)((mul24s(c[k], dqv) + (1 << (-qbits - 1))) >> (-qbits));
-            }
-        }
-    }
+    int c[8];
+    int nz, score, rawdc;
+    half4x4_forward(Q, L->fenc, L->pred, px, py, h, is_l, is_l || is_c, lv, L->coef[blk], c, &nz, &score, &rawdc);
     /* luma: 8x8 sums over the eight lanes of an 8x8, macroblock sum over lanes 0..31; chroma: the plane's eight lanes */
     const int sc = (nz && Q.b_dct_decimate && !h) ? score : 0;
     int q8 = sc + dpp_qp1(sc); q8 += dpp_qp2(q8); q8 += dpp_hmir(q8);
@@ -986,64 +1070,14 @@ __device__ __forceinline__ void prim_mb_transform(const FrameDev &F, MBLocal *L,
     const int r16 = q8 + dpp_mir(q8);
     const int row = __builtin_amdgcn_readlane(r16, 0) + __builtin_amdgcn_readlane(r16, 16);
     const bool keep = Q.b_dct_decimate ? (q8 >= 4 && row >= 6) : any8 != 0;
-    /* chroma DC: 2x2 transform over the plane's four blocks (their h = 0 lanes, two apart): butterflies with lane ^ 2, then lane ^ 4; the
-     * network leaves coefficient (k & 1) * 2 + (k >> 1) in the lane of block k -- zigzag_scan_2x2_dc's place k -- and, run again on the
-     * quantised values, block k's reconstructed DC in the lane of block k */
-    const int s2 = lane & 2 ? -1 : 1, s4 = lane & 4 ? -1 : 1;
-    int cdc = mad24s(rawdc, s2, dpp_qp2(rawdc));
-    cdc = mad24s(cdc, s4, dpp_x4(cdc));
-    int dcq;
-    { const int mf = Q.q_mf[1][0] >> 1, bias = Q.q_bias[1][0] << 1;
-      dcq = cdc > 0 ? ((bias + cdc) * mf >> 16) : -((bias - cdc) * mf >> 16); }
-    if (h || !is_c) dcq = 0;
-    int nzdc = dcq != 0; nzdc |= dpp_qp1(nzdc); nzdc |= dpp_qp2(nzdc); nzdc |= dpp_hmir(nzdc);
-    int dmf = Q.dq_mf_c[0], qbits = Q.chroma_qp / 6 - 5;
-    if (qbits > 0) { dmf <<= qbits; qbits = 0; }
-    int idc = mad24s(dcq, s2, dpp_qp2(dcq));
-    idc = mad24s(idc, s4, dpp_x4(idc));
-    int rdc = (int16_t)(idc * dmf >> -qbits);
-    {   /* both lanes of the block (the exchange made by all lanes, THEN the choice: inside `h ? dpp : x` only the odd lanes would
-         * execute it, and a DPP read of a lane that is switched off returns 0) */
-        const int other = dpp_qp1(rdc);
-        rdc = h ? other : rdc;
-    }
+    int dcq, nzdc, rdc;
+    half4x4_chroma_dc(Q, lane, h, is_c, rawdc, &dcq, &nzdc, &rdc);
     const int cmode = (q8 < 7 && Q.b_dct_decimate) || !any8 ? (nzdc ? 1 : 0) : 2;
     const unsigned long long keep_mask = __ballot(is_l && keep), ac_mask = __ballot(is_c && cmode == 2);
     const bool inv = is_l ? keep && nz : is_c && cmode == 2;
     if (is_c && cmode == 2 && nzdc && !h) c[0] = (int16_t)rdc;
-    if (inv) {
-        /* inverse: per vertical frequency the horizontal pass (in-lane), then the vertical one with the partner */
-        int u[2][4];
-#pragma unroll
-        for (int k = 0; k < 2; k++) {
-            const int c0 = c[4 * k], c1 = c[4 * k + 1], c2 = c[4 * k + 2], c3 = c[4 * k + 3];
-            const int s02 = c0 + c2, d02 = c0 - c2, s13 = c1 + (c3 >> 1), d13 = (c1 >> 1) - c3;
-            u[k][0] = (int16_t)(s02 + s13); u[k][1] = (int16_t)(d02 + d13); u[k][2] = (int16_t)(d02 - d13); u[k][3] = (int16_t)(s02 - s13);
-        }
-        uint32_t oa = 0, ob = 0;
-        const uint8_t *pa = L->pred + (py + ra) * 16 + px, *pb = L->pred + (py + rb) * 16 + px;
-        const uint32_t va = lds4(pa), vb = lds4(pb);
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            /* h = 0 holds t[0][i], t[1][i] and makes s02, s13; h = 1 holds t[2][i], t[3][i] and makes d02, d13 */
-            const int x = mad24s(u[0][i], sgn, dpp_qp1(u[0][i])) + 32;
-            const int y = mad24s(u[1][i], sgn, dpp_qp1(u[1][i]) >> 1);
-            const int r_a = (int16_t)((x + y) >> 6), r_b = (int16_t)((x - y) >> 6);      /* rows 0 / 3 (h = 0), 1 / 2 (h = 1) */
-            oa |= (uint32_t)clip3i((int)((va >> (8 * i)) & 255) + r_a, 0, 255) << (8 * i);
-            ob |= (uint32_t)clip3i((int)((vb >> (8 * i)) & 255) + r_b, 0, 255) << (8 * i);
-        }
-        sts4((uint8_t *)pa, oa); sts4((uint8_t *)pb, ob);
-    } else if (is_c && cmode == 1) {
-        const int v = (rdc + 32) >> 6;
-#pragma unroll
-        for (int k = 0; k < 2; k++) {
-            uint8_t *dst = L->pred + (py + (k ? rb : ra)) * 16 + px;
-            uint32_t p = lds4(dst), o = 0;
-#pragma unroll
-            for (int x = 0; x < 4; x++) o |= (uint32_t)clip3i((int)((p >> (8 * x)) & 255) + v, 0, 255) << (8 * x);
-            sts4(dst, o);
-        }
-    }
+    if (inv) half4x4_inverse_add(L->pred, px, py, h, c);
+    else if (is_c && cmode == 1) half4x4_add_dc(L->pred, px, py, h, rdc);
     {
         /* one bit per block out of the even lanes' bits */
         unsigned m = (unsigned)__ballot(is_l && keep && nz && !h);
@@ -1087,8 +1121,8 @@ __device__ __forceinline__ void prim_predict_win16(const FrameDev &F, MBLocal *L
     PCAMV_WAVE_SYNC();
 }
 /* transform stage of the four predictions in pred4 (same rules as prim_mb_transform): pass A, every lane
- * one luma block (macroblock j = lane / 16: a DPP row each); pass B, lanes 0..31 one chroma block each
- * (macroblock j = lane / 8, plane = quad) */
+ * one luma block (macroblock j = lane / 16: a DPP row each); pass B, the 32 chroma blocks two lanes each as in
+ * prim_mb_transform: lane = 16 j + 8 plane + 2 block + h, a prediction's plane is eight consecutive lanes of a DPP row */
 __device__ __forceinline__ void prim_mb_transform4(const FrameDev &F, MBLocal *L)
 {
     const auto &Q = FD(F);
@@ -1106,35 +1140,20 @@ __device__ __forceinline__ void prim_mb_transform4(const FrameDev &F, MBLocal *L
         const bool keep = Q.b_dct_decimate ? (q8 >= 4 && row >= 6) : any8 != 0;
         if (keep && nz) idct4x4_add(pr + py * 16 + px, d);
     }
-    if (lane < 32) {
-        const int j = lane >> 3, ch = (lane >> 2) & 1, ci = lane & 3, px = ch * 8 + (ci & 1) * 4, py = 16 + (ci >> 1) * 4;
+    {
+        const int j = lane >> 4, ch = (lane >> 3) & 1, ci = (lane >> 1) & 3, h = lane & 1, px = ch * 8 + (ci & 1) * 4, py = 16 + (ci >> 1) * 4;
         uint8_t *pr = L->pred4[j];
-        int16_t d[16]; int nz, score, rawdc;
-        residual_block_at(F, L, pr, px, py, false, d, &nz, &score, &rawdc);
-        const int sc = (nz && Q.b_dct_decimate) ? score : 0;
-        int q8 = sc + dpp_qp1(sc); q8 += dpp_qp2(q8);
-        int any8 = nz | dpp_qp1(nz); any8 |= dpp_qp2(any8);
-        const int cdc = quad_had2x2(rawdc, ci);
-        int dcq;
-        { const int mf = Q.q_mf[1][0] >> 1, bias = Q.q_bias[1][0] << 1;
-          dcq = cdc > 0 ? ((bias + cdc) * mf >> 16) : -((bias - cdc) * mf >> 16); }
-        int nzdc = dcq != 0; nzdc |= dpp_qp1(nzdc); nzdc |= dpp_qp2(nzdc);
-        int dmf = Q.dq_mf_c[0], qbits = Q.chroma_qp / 6 - 5;
-        if (qbits > 0) { dmf <<= qbits; qbits = 0; }
-        const int rdc = (int16_t)(quad_had2x2(dcq, ci) * dmf >> -qbits);
-        const int cmode = (q8 < 7 && Q.b_dct_decimate) || !any8 ? (nzdc ? 1 : 0) : 2;
-        uint8_t *dst = pr + py * 16 + px;
-        if (cmode == 2) { if (nzdc) d[0] = (int16_t)rdc; idct4x4_add(dst, d); }
-        else if (cmode == 1) {
-            const int v = (rdc + 32) >> 6;
-#pragma unroll
-            for (int y = 0; y < 4; y++) {
-                uint32_t p = lds4(dst + y * 16), o = 0;
-#pragma unroll
-                for (int x = 0; x < 4; x++) o |= (uint32_t)clip3i((int)((p >> (8 * x)) & 255) + v, 0, 255) << (8 * x);
-                sts4(dst + y * 16, o);
-            }
-        }
+        int c[8];
+        int nz, score, rawdc;
+        half4x4_forward(Q, L->fenc, pr, px, py, h, false, true, 0, (int16_t *)nullptr, c, &nz, &score, &rawdc);
+        const int sc = (nz && Q.b_dct_decimate && !h) ? score : 0;
+        int q8 = sc + dpp_qp1(sc); q8 += dpp_qp2(q8); q8 += dpp_hmir(q8);
+        int any8 = nz | dpp_qp2(nz); any8 |= dpp_hmir(any8);
+        int dcq, nzdc, rdc;
+        half4x4_chroma_dc(Q, lane, h, true, rawdc, &dcq, &nzdc, &rdc);
+        const int cmode = (q8 < 7 && Q.b_dct_decimate) || !any8 ? (nzdc ? 1 : 0) : 2;      /* the same in the plane's eight lanes */
+        if (cmode == 2) { if (nzdc && !h) c[0] = (int16_t)rdc; half4x4_inverse_add(pr, px, py, h, c); }
+        else if (cmode == 1) half4x4_add_dc(pr, px, py, h, rdc);
     }
     PCAMV_WAVE_SYNC();
 }
