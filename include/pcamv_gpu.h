@@ -176,8 +176,9 @@ int pcamv_gpu_pass2_pframe(pcamv_ctx_t *ctx, const uint8_t *flips, int n_flips, 
  * reference draws the columns from a process-wide LCG (embed.h:134-139) that every such frame advances, so the extractor needs
  * the generator's state: *lcg = state before this frame's embedding (1 for the first P frame of a process -- of a closed GOP
  * under the per-GOP parity definition; a context starts there), updated to the state after it, to be carried to the next frame
- * exactly as the reference's own extractor process carries it.  pcamv_gpu_stc_extract = the same with lcg == NULL: tabulated
- * widths only, PCAMV_EUNSUP otherwise. */
+ * exactly as the reference's own extractor process carries it -- also by a call that returns PCAMV_EUNSUP because a sub-matrix would be
+ * wider than 256 columns: the embedder draws the shorter one (width 256) before the longer one fails, and so does this.
+ * pcamv_gpu_stc_extract = the same with lcg == NULL: tabulated widths only, PCAMV_EUNSUP otherwise. */
 int pcamv_gpu_stc_extract(const uint8_t *stego, int n, int m, int matrixheight, uint8_t *message);
 int pcamv_gpu_stc_extract_lcg(const uint8_t *stego, int n, int m, int matrixheight, int64_t *lcg, uint8_t *message);
 
@@ -270,6 +271,14 @@ int pcamv_gpu_block_costs(pcamv_ctx_t *ctx, int qp, int n, const int32_t *req, i
  * 4 / 5 fenc_satd_sum / fenc_sa8d_sum of the source, 6..9 intra 16x16 V, H, DC (variant by avail), P, 10..13 intra chroma DC
  * (variant), H, V, P over both planes, 14..25 the twelve 4x4 modes on block 0 (x264's I_PRED_4x4 order); unavailable = 1 << 28. */
 int pcamv_gpu_rd_probe(pcamv_ctx_t *ctx, int qp, int n, const uint8_t *req, int32_t *out);
+
+/* Probe of the embedding stage on a caller's records, for parity tests of the cover / cost assembly and the syndrome-trellis kernels
+ * at inputs no analysis produces: mbs[mb_count] is copied into the context's record buffer, then the stage runs exactly as
+ * pcamv_gpu_embed_pframe runs it (same kernels and outputs; the rand() stream, the payload cursor and the column generator move the
+ * same way).  Afterwards the context stands as after an analysis that produced those records: pcamv_gpu_final_mvs,
+ * pcamv_gpu_batch_extract_step and the slice writers' final motion see them and the new flip map.  Synchronises. */
+int pcamv_gpu_embed_records(pcamv_ctx_t *ctx, const pcamv_mb_t *mbs, float emrate,
+                            const uint8_t *message, int message_len, pcamv_embed_t *out);
 
 /* Diagnostics: record every block-cost evaluation {ip,xoff,yoff,mvx,mvy,flags,cost,cost2} made for
  * macroblock mb by the next analyse call (mb < 0: off); out holds 1 + 8*4000 int32, out[0] = count. */

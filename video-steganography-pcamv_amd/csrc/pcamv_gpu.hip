@@ -840,10 +840,9 @@ static int fetch_embed(pcamv_ctx *c, pcamv_embed_t *out)
     return 0;
 }
 
-extern "C" int pcamv_gpu_embed_pframe(pcamv_ctx_t *c, float emrate, const uint8_t *message, int message_len, pcamv_embed_t *out)
+/* the embedding stage on the records that stand in the context's record buffer (F.rec_mb = E.mbs): what embed_pframe and embed_records share */
+static int embed_stage(pcamv_ctx *c, float emrate, const uint8_t *message, int message_len, pcamv_embed_t *out)
 {
-    if (!c || !out || emrate <= 0) return PCAMV_EINVAL;
-    HIPCHK(c, hipSetDevice(c->device));
     if (message) {
         if (message_len < 0 || message_len > c->cap) return fail(c, PCAMV_EINVAL, "message_len");
         HIPCHK(c, hipMemcpy(c->d_user_msg, message, message_len, hipMemcpyHostToDevice));
@@ -852,6 +851,23 @@ extern "C" int pcamv_gpu_embed_pframe(pcamv_ctx_t *c, float emrate, const uint8_
     c->E.emrate = emrate;
     TRY(ctx_launch(c, ST_EMBED));
     return fetch_embed(c, out);
+}
+extern "C" int pcamv_gpu_embed_pframe(pcamv_ctx_t *c, float emrate, const uint8_t *message, int message_len, pcamv_embed_t *out)
+{
+    if (!c || !out || emrate <= 0) return PCAMV_EINVAL;
+    HIPCHK(c, hipSetDevice(c->device));
+    return embed_stage(c, emrate, message, message_len, out);
+}
+/* The probe of the embedding stage: a caller's records take the place an analysis would have written them to, then the stage as
+ * embed_pframe runs it.  Afterwards the context stands as after an analysis that produced them (final_mvs, batch_extract_step and
+ * the writers' final motion read the record buffer and the new flip map). */
+extern "C" int pcamv_gpu_embed_records(pcamv_ctx_t *c, const pcamv_mb_t *mbs, float emrate, const uint8_t *message, int message_len, pcamv_embed_t *out)
+{
+    if (!c || !mbs || !out || emrate <= 0) return PCAMV_EINVAL;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipDeviceSynchronize());          /* work in flight (a receiver's launch on another stream) may still read the records */
+    HIPCHK(c, hipMemcpy(c->F.rec_mb, mbs, (size_t)c->F.n_mb * sizeof(pcamv_mb_t), hipMemcpyHostToDevice));
+    return embed_stage(c, emrate, message, message_len, out);
 }
 
 /* the carrier MVs of a record in embedding order (encoder.c:1566-1647; the device's carrier_slots): their slots in mv[], and how many */
@@ -1712,12 +1728,14 @@ extern "C" int pcamv_gpu_stc_extract_lcg(const uint8_t *stego, int n, int m, int
     if (!stego || !message || n <= 0 || m <= 0 || m > n || hgt < 7 || hgt > 12) return PCAMV_EINVAL;
     double invalpha = (double)n / m;
     int shorter = (int)floor(invalpha), longer = (int)ceil(invalpha);
-    if (longer > STC_MAXW) return PCAMV_EUNSUP;
     unsigned *cs = (unsigned *)malloc(2 * (size_t)STC_MAXW * sizeof(unsigned)), *cl = cs + STC_MAXW;
     if (!cs) return PCAMV_ENOMEM;
     long long st = lcg ? (long long)*lcg : 0;
-    if (!host_stc_matrix(shorter, hgt, cs, lcg ? &st : NULL) || !host_stc_matrix(longer, hgt, cl, lcg ? &st : NULL)) { free(cs); return PCAMV_EUNSUP; }
+    /* (host_stc_matrix refuses widths above STC_MAXW.)  The embedder draws the shorter sub-matrix before it finds that the longer one
+     * cannot be built (widths 256 / 257), so the generator moves on a frame that fails, too: here as in the embedder and in k_extract_prepare */
+    const int built = host_stc_matrix(shorter, hgt, cs, lcg ? &st : NULL) && host_stc_matrix(longer, hgt, cl, lcg ? &st : NULL);
     if (lcg) *lcg = (int64_t)st;
+    if (!built) { free(cs); return PCAMV_EUNSUP; }
     memset(message, 0, m);
     int worm = 0, index = 0;
     for (int i = 0; i < m; i++) {

@@ -401,6 +401,21 @@ class Encoder:
                                                   0 if message is None else len(message), C.byref(e)), "embed_pframe")
         return self._embed_out(arr, e)
 
+    def embed_records(self, mbs, emrate, message=None):
+        """pcamv_gpu_embed_records: the embedding stage on the caller's records instead of an analysis' -- the probe of the cover /
+        cost assembly and the syndrome-trellis kernels; the result of embed_pframe, and the context stands as after an analysis that
+        produced `mbs` (final_mvs, Batch.extract_step, the writers' final=True)"""
+        mbs = np.ascontiguousarray(mbs, MB_DTYPE)
+        if len(mbs) != self.n_mb:
+            raise PcamvError(f"{len(mbs)} records for a picture of {self.n_mb} macroblocks")
+        arr, e = self._embed_bufs()
+        if message is not None:
+            message = np.ascontiguousarray(message, np.uint8)
+        self.lib.pcamv_gpu_embed_records.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_void_p]
+        self._chk(self.lib.pcamv_gpu_embed_records(self.ctx, _p(mbs), emrate, _p(message), 0 if message is None else len(message), C.byref(e)),
+                  "embed_records")
+        return self._embed_out(arr, e)
+
     # payload path: the caller's bits through embed_pframe(None) / step_device / Batch.step, and back out on the device
     def set_payload(self, payload, n_bits=None):
         """attach a payload: packed bytes (pack_bits) as a numpy array / bytes (copied), or a torch uint8 device tensor (borrowed: kept
