@@ -144,6 +144,11 @@ int pcamv_gpu_set_ref(pcamv_ctx_t *ctx, const uint8_t *const plane[3], const int
  * (DESIGN.md section 3), which this call undoes. */
 int pcamv_gpu_get_ref_planes(pcamv_ctx_t *ctx, uint8_t *out, int *stride, int *lines);
 
+/* Diagnostics: the same planes exactly as they lie in device memory -- the four luma planes in the strip layout, repeated
+ * columns included (*luma_bytes = 4 * strips * 32 * lines), then the two padded chroma planes in raster rows (*chroma_bytes
+ * = 2 * ALIGN(width/2+32,16) * (height/2+32)).  out may be NULL to ask for the sizes; else cap must be their sum. */
+int pcamv_gpu_get_ref_strips(pcamv_ctx_t *ctx, uint8_t *out, size_t cap, size_t *luma_bytes, size_t *chroma_bytes);
+
 /* Pass-1 analysis of the whole P frame at luma QP qp.  out_mb[mb_count] receives the record
  * (with embed != 0 also used / mv_stego / inter_stego_cost).  recon[3] (optional, tightly
  * packed w*h, w/2*h/2 x2) receives the pass-1 reconstruction before deblocking. */

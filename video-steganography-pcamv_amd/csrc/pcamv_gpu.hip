@@ -695,10 +695,11 @@ static int batch_launch(pcamv_batch *b, int what, hipStream_t st)
     const FrameDev &F = b->ctx[0]->F;
     const unsigned G = (unsigned)b->n;
     if (what & ST_PLANES) {
-        dim3 g((F.stride / 4 + HP_THREADS - 1) / HP_THREADS, (F.lines + HP_ROWS - 1) / HP_ROWS, G);
+        /* a wave = 8 strips (those that begin inside the stride) x HP_ROWS lines; lines is a multiple of 16 */
+        dim3 g(((F.stride + PCAMV_LSW - 1) / PCAMV_LSW + 7) / 8, (F.lines + HP_ROWS - 1) / HP_ROWS, G);
         hipLaunchKernelGGL(k_hpel, g, dim3(HP_THREADS), 0, st, dF);
-        dim3 gc((F.cstride / 4 + 255) / 256, F.clines, 2 * G);
-        hipLaunchKernelGGL(k_chroma_pad, gc, dim3(256), 0, st, dF);
+        dim3 gc((F.cstride / 16 * CP_ROWS + CP_THREADS - 1) / CP_THREADS, (F.clines + CP_ROWS - 1) / CP_ROWS, 2 * G);
+        hipLaunchKernelGGL(k_chroma_pad, gc, dim3(CP_THREADS), 0, st, dF);
     }
     if (what & ST_ANALYSE) {
         for (int i = 0; i < b->n; i++) b->ctx[i]->last = b;
@@ -805,6 +806,23 @@ extern "C" int pcamv_gpu_get_ref_planes(pcamv_ctx_t *c, uint8_t *out, int *strid
                 out[((size_t)k * c->F.lines + y) * c->F.stride + x] = tmp[k * psz + (size_t)y * PCAMV_LROW + x + (size_t)(x / PCAMV_LSW) * c->F.lskip];
     if (stride) *stride = c->F.stride;
     if (lines) *lines = c->F.lines;
+    return 0;
+}
+
+/* diagnostics (layout tests): the four luma planes as they lie in device memory, strips and repeated columns included, then the
+ * two padded chroma planes */
+extern "C" int pcamv_gpu_get_ref_strips(pcamv_ctx_t *c, uint8_t *out, size_t cap, size_t *luma_bytes, size_t *chroma_bytes)
+{
+    if (!c) return PCAMV_EINVAL;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipDeviceSynchronize());
+    const size_t lb = 4 * (size_t)c->F.plane_size, csz = (size_t)c->F.cstride * c->F.clines;
+    if (luma_bytes) *luma_bytes = lb;
+    if (chroma_bytes) *chroma_bytes = 2 * csz;
+    if (!out) return 0;                                     /* sizes only */
+    if (cap < lb + 2 * csz) return fail(c, PCAMV_EINVAL, "get_ref_strips: %zu bytes offered, %zu needed", cap, lb + 2 * csz);
+    HIPCHK(c, hipMemcpy(out, c->F.luma_base, lb, hipMemcpyDeviceToHost));
+    for (int k = 0; k < 2; k++) HIPCHK(c, hipMemcpy(out + lb + k * csz, c->F.chroma_base[k], csz, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -12,43 +12,65 @@
 #include "pcamv_prims_gpu.h"
 
 /* ------------------------------------------------------------------ plane production */
+/* stores go out as global_store (address space 1), not flat: 16 bytes a lane, whole 128-byte lines a wave */
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(1))) u32x4 *gp128w;
+typedef __attribute__((address_space(1))) uint32_t *gp32w;
+typedef const __attribute__((address_space(1))) uint32_t *gp32;
 /* Every kernel is batched over independent closed GOPs: blockIdx.z (plane kernels) or blockIdx.y
  * (macroblock kernels) selects the GOP's FrameDev in a device array.  One launch then carries
  * the same dependency step of all GOPs, which is what fills the 256 CUs (a single 1080p frame
  * exposes at most 60 independent macroblocks at a time). */
-static __global__ void __launch_bounds__(256) k_chroma_pad(const FrameDev *__restrict__ Fs)
+/* One thread = 16 horizontally adjacent bytes of a padded chroma row (cstride is a multiple of 16; the pad and the width are
+ * multiples of 4, so each of the four dwords is inside the picture or one replicated pixel), CP_ROWS rows per block: a wave's store
+ * instruction covers whole 128-byte lines. */
+#define CP_ROWS 4
+#define CP_THREADS 256
+static __global__ void __launch_bounds__(CP_THREADS) k_chroma_pad(const FrameDev *__restrict__ Fs)
 {
     const FrameDev &F = Fs[blockIdx.z >> 1];
     const int pl = blockIdx.z & 1;
     const uint8_t *__restrict__ src = F.raw[1 + pl];
     uint8_t *__restrict__ dst = F.chroma_base[pl];
     const int w = F.w >> 1, h = F.h >> 1, cstride = F.cstride, clines = F.clines;
-    /* 4 pixels per thread; pad and width are multiples of 4, so a group is inside the picture or one replicated pixel */
-    const int x = 4 * (blockIdx.x * blockDim.x + threadIdx.x), y = blockIdx.y;
-    if (x >= cstride || y >= clines) return;
+    const int per_row = cstride >> 4;                        /* threads a row takes */
+    const int i = blockIdx.x * CP_THREADS + threadIdx.x;
+    const int y = blockIdx.y * CP_ROWS + i / per_row, x = 16 * (i % per_row);
+    if (i >= per_row * CP_ROWS || y >= clines) return;
     const uint8_t *rowp = src + (size_t)clip3i(y - PCAMV_CPAD, 0, h - 1) * w;
-    const int gx = x - PCAMV_CPAD;
-    uint32_t v;
-    if (gx < 0 || gx >= w) v = rowp[gx < 0 ? 0 : w - 1] * 0x01010101u;
-    else if (((uintptr_t)src & 3) == 0) v = *(const uint32_t *)(rowp + gx);
-    else v = rowp[gx] | rowp[gx + 1] << 8 | rowp[gx + 2] << 16 | (uint32_t)rowp[gx + 3] << 24;
-    *(uint32_t *)(dst + (size_t)y * cstride + x) = v;
+    const bool aligned = ((uintptr_t)src & 3) == 0;
+    uint32_t v[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int gx = x + 4 * k - PCAMV_CPAD;
+        if (gx < 0 || gx >= w) v[k] = rowp[gx < 0 ? 0 : w - 1] * 0x01010101u;
+        else if (aligned) v[k] = *(const uint32_t *)(rowp + gx);
+        else v[k] = rowp[gx] | rowp[gx + 1] << 8 | rowp[gx + 2] << 16 | (uint32_t)rowp[gx + 3] << 24;
+    }
+    *(gp128w)(dst + (size_t)y * cstride + x) = u32x4{v[0], v[1], v[2], v[3]};
 }
 
 /* (clamp_u8: pcamv_prims_gpu.h) */
 /* The four luma planes full / H / V / HV of the reference frame, padded (x264_frame_filter + expand_border,
  * common/mc.c:455-507, frame.c:246-300; the filtered planes are defined 4 columns / 8 rows beyond the picture and
- * replicated from there).  One thread = 4 horizontally adjacent output pixels, walking HP_ROWS rows down: it keeps
- * the 6 source rows x 12 source columns its filters need in registers (three dwords a row, one new row per output
- * row), so a source byte is fetched once per thread and never goes through LDS; every store is a full dword and a
- * wave's stores are contiguous.  The output pixel groups are aligned with the picture (pad and width are multiples
- * of 4), so a group is either inside the filtered domain or entirely replicated from its edge pixel. */
+ * replicated from there).  One thread = one dword of a strip (pcamv_common.h): 4 horizontally adjacent output pixels
+ * of the padded columns 28 s + 4 d .. + 3, d = 0 .. 7, walking HP_ROWS rows down.  It keeps the 6 source rows x 12
+ * source columns its filters need in registers (three dwords a row, one new row per output row), so a source byte is
+ * fetched once per thread.  A strip's last dword (d = 7) shows the same columns as the next strip's first: it is an
+ * output group like any other (the filter is closed-form in x), there is no second store.  The output pixel groups are
+ * aligned with the picture (pad, width and 28 are multiples of 4), so a group is either inside the filtered domain or
+ * entirely replicated from its edge pixel.
+ * Stores: a 128-byte line of the layout is rows 4 q .. 4 q + 3 of one strip.  A wave (8 strips x 8 dwords) parks four
+ * finished rows of the four planes in LDS (4 planes x 8 strips x 128 bytes, the strips HP_TILE dwords apart so that
+ * the 64 lanes of a row write hit 64 banks), then every lane takes 16 bytes of its own strip's line back and the
+ * wave's global_store_dwordx4 covers eight whole lines per plane. */
 #define HP_ROWS 16
-#define HP_THREADS 128
+#define HP_THREADS 64
+#define HP_TILE 40
 __device__ __forceinline__ void hpel_load_row(const uint8_t *__restrict__ rowp, int eg0, int W, bool fast, uint32_t d[3])
 {
     if (fast) {
-        const uint32_t *q = (const uint32_t *)(rowp + eg0 - 4);
+        const gp32 q = (gp32)(rowp + eg0 - 4);
         d[0] = q[0]; d[1] = q[1]; d[2] = q[2];
     } else {
 #pragma unroll
@@ -62,20 +84,23 @@ __device__ __forceinline__ void hpel_load_row(const uint8_t *__restrict__ rowp, 
 }
 static __global__ void __launch_bounds__(HP_THREADS) k_hpel(const FrameDev *__restrict__ Fs)
 {
+    __shared__ uint32_t tile[4][8][HP_TILE];
     const FrameDev &F = Fs[blockIdx.z];
     const uint8_t *__restrict__ src = F.raw[0];
     uint8_t *__restrict__ planes = F.luma_base;
     const int W = F.w, H = F.h, stride = F.stride, lines = F.lines;
-    const int x0 = 4 * (blockIdx.x * HP_THREADS + threadIdx.x), yb = blockIdx.y * HP_ROWS;
-    if (x0 >= stride) return;
+    const int t = threadIdx.x >> 3, d = threadIdx.x & 7;
+    const int strip = blockIdx.x * 8 + t, yb = blockIdx.y * HP_ROWS;
+    if (strip * PCAMV_LSW >= stride) return;             /* (strips that begin beyond the stride are never read) */
+    const int x0 = strip * PCAMV_LSW + 4 * d;
     /* first picture column of the group whose values this group shows, and which of its bytes when replicated */
     const int gx = x0 - PCAMV_PAD, eg0 = clip3i(gx, -4, W);
     const int rep = gx < -4 ? 0 : gx > W ? 3 : -1;
     const bool fast = eg0 >= 4 && eg0 + 8 <= W && ((uintptr_t)src & 3) == 0;
     const size_t psz = (size_t)F.plane_size;
-    const unsigned strip = PCAMV_LSTRIP_OF(x0);
-    const size_t strip_o = (size_t)x0 + (size_t)strip * (size_t)F.lskip;
-    const bool dup = strip > 0 && (unsigned)x0 == strip * PCAMV_LSW;
+    /* the lane's 16 bytes of its strip's line: row d / 2 of the four, half d % 2 */
+    uint8_t *const line0 = planes + (size_t)strip * PCAMV_LROW * (size_t)lines + 16 * d;
+    const bool raster = F.luma_raster && d < 7 && x0 < stride;
     uint32_t w[6][3];
     uint32_t of = 0, oh = 0, ov = 0, oc = 0;
     int ey_prev = 0;
@@ -116,20 +141,19 @@ static __global__ void __launch_bounds__(HP_THREADS) k_hpel(const FrameDev *__re
                 ov = (ov >> sh & 255) * 0x01010101u; oc = (oc >> sh & 255) * 0x01010101u;
             }
         }
-        /* strip layout (pcamv_common.h): the group's place in its own strip and, for a strip's first group, the repeat at the end
-         * of the strip before it */
-        const size_t o = (size_t)y * PCAMV_LROW + strip_o;
-        *(uint32_t *)(planes + o) = of;
-        if (F.luma_raster) *(uint32_t *)(F.luma_raster + (size_t)y * stride + x0) = of;
-        *(uint32_t *)(planes + psz + o) = oh;
-        *(uint32_t *)(planes + 2 * psz + o) = ov;
-        *(uint32_t *)(planes + 3 * psz + o) = oc;
-        if (dup) {
-            const size_t o2 = o - (size_t)F.lskip;
-            *(uint32_t *)(planes + o2) = of;
-            *(uint32_t *)(planes + psz + o2) = oh;
-            *(uint32_t *)(planes + 2 * psz + o2) = ov;
-            *(uint32_t *)(planes + 3 * psz + o2) = oc;
+        if (raster) *(gp32w)(F.luma_raster + (size_t)y * stride + x0) = of;
+        /* (yb and lines are multiples of 4: a walk is made of whole lines) */
+        const int r = y & 3;
+        tile[0][t][8 * r + d] = of; tile[1][t][8 * r + d] = oh; tile[2][t][8 * r + d] = ov; tile[3][t][8 * r + d] = oc;
+        if (r == 3) {
+            PCAMV_WAVE_SYNC();
+            u32x4 ln[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) ln[k] = *(const u32x4 *)&tile[k][t][4 * d];
+            PCAMV_WAVE_SYNC();
+            uint8_t *const o = line0 + (size_t)(y - 3) * PCAMV_LROW;
+#pragma unroll
+            for (int k = 0; k < 4; k++) *(gp128w)(o + k * psz) = ln[k];
         }
     }
 }

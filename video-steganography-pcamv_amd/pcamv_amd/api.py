@@ -371,6 +371,18 @@ class Encoder:
         assert st.value == stride and ln.value == self.h + 64
         return out
 
+    def ref_strips(self):
+        """(luma, chroma): the four luma planes as they lie in device memory, [4, strips, lines, 32] with each strip's four
+        repeated columns, and the two padded chroma planes [2, h/2 + 32, cstride]"""
+        fn = self.lib.pcamv_gpu_get_ref_strips
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+        lb, cb = C.c_size_t(), C.c_size_t()
+        self._chk(fn(self.ctx, None, 0, C.byref(lb), C.byref(cb)), "get_ref_strips")
+        out = np.zeros(lb.value + cb.value, np.uint8)
+        self._chk(fn(self.ctx, _p(out), out.size, C.byref(lb), C.byref(cb)), "get_ref_strips")
+        lines, clines = self.h + 64, self.h // 2 + 32
+        return out[:lb.value].reshape(4, -1, lines, 32), out[lb.value:].reshape(2, clines, -1)
+
     def analyse_pframe(self, qp, embed=1, want_recon=True):
         mbs = np.zeros(self.n_mb, MB_DTYPE)
         rec = [np.zeros((self.h, self.w), np.uint8), np.zeros((self.h // 2, self.w // 2), np.uint8),
