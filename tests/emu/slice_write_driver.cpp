@@ -34,3 +34,12 @@ extern "C" int swx_carrier_arithmetic_differs(void)
     }
     return bad;
 }
+
+/* sp_partition of pcamv_slice_parse.h (the partition walk of all four slice coders) as it is, and the embedding stage's carrier_slots
+ * of the same macroblock shape (sub: the four sub-partitions, one byte each; returns the count), for the test to set side by side */
+extern "C" int swx_partition(int type, int partition, uint32_t sub, int k) { return sp_partition(type, partition, sub, k); }
+extern "C" int swx_carrier_slots(int type, int partition, uint32_t sub, int slots[16])
+{
+    const uint8_t s[4] = {(uint8_t)sub, (uint8_t)(sub >> 8), (uint8_t)(sub >> 16), (uint8_t)(sub >> 24)};
+    return carrier_slots(type, partition, s, 1, slots);
+}

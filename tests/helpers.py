@@ -52,6 +52,12 @@ def compare_records(golden_mbs, got, what=""):
                                  f"expected {a[bad[0]].tolist()} got {b[bad[0]].tolist()}")
 
 
+def same_records(a, b, what):
+    """every field of two arrays of parsed records equal"""
+    for f in a.dtype.names:
+        assert np.array_equal(a[f], b[f]), f"{what}: record field {f} differs"
+
+
 def mv_field(mbs_mv, mbw, mbh):
     """the record's MVs (x264 block order per macroblock) as the frame's 4x4 motion field + its (all zero) reference field"""
     mv = np.asarray(mbs_mv, np.int16).reshape(mbh, mbw, 16, 2)

@@ -187,11 +187,6 @@ def test_control_code_matches_oracle(c):
 TINY_CASES = [c for c in gc.by_shape({(w // 16, h // 16) for w, h in sc.TINY_SHAPES})]
 
 
-def _same_records(a, b, what):
-    for f in a.dtype.names:
-        assert np.array_equal(a[f], b[f]), f"{what}: record field {f} differs"
-
-
 @pytest.mark.parametrize("cabac", [1, 0], ids=["cabac", "cavlc"])
 @pytest.mark.parametrize("c", TINY_CASES, ids=[gc.case_id(c) for c in TINY_CASES])
 def test_tiny_slices_round_trip_in_emulation(c, cabac):
@@ -212,7 +207,7 @@ def test_tiny_slices_round_trip_in_emulation(c, cabac):
             host = pcamv_amd.parse_pslice_at(data, 0, c.mbw, c.mbh, qp=None)
             rc, dev = slice_parse_cavlc_emu.parse_at(data, 0, c.mbw, c.mbh)
         assert rc == 0
-        _same_records(host, dev, f"{gc.case_id(c)} frame {t}")
+        helpers.same_records(host, dev, f"{gc.case_id(c)} frame {t}")
         for _, fld in sc.FIELDS:
             assert np.array_equal(dev[fld], f.final[fld]), (t, fld)
 
@@ -251,7 +246,7 @@ def test_tiny_slices_equal_the_reference(cabac):
             host = pcamv_amd.parse_pslice_at(bytes(data), 0, w, h, qp=None)
             rc, dev = slice_parse_cavlc_emu.parse_at(bytes(data), 0, w, h)
         assert rc == 0
-        _same_records(host, dev, f"{W}x{H} frame {t}")
+        helpers.same_records(host, dev, f"{W}x{H} frame {t}")
         for a, b in sc.FIELDS:
             assert np.array_equal(mbs[a], dev[b]), (W, H, t, a)
         seen |= set(np.unique(dev["i_type"]).tolist())

@@ -29,23 +29,18 @@ def _params(pc, W, H, cabac=1):
     return p
 
 
-def _same_records(a, b, what):
-    for f in a.dtype.names:
-        assert np.array_equal(a[f], b[f]), f"{what}: record field {f} differs"
-
-
 @pytest.mark.parametrize("name", sc.CABAC_FIXTURES)
 def test_device_parser_equals_the_host_parser(pc, name):
     g = helpers.load(name)
     (w, h), qp = sc.dims(g), int(g["qp"])
     enc = pc.Encoder(_params(pc, 16 * w, 16 * h))
     got = enc.parse_pslice_device(g["slice_data"].tobytes(), 0, qp)
-    _same_records(pc.parse_pslice_cabac(g["slice_data"].tobytes(), w, h, qp), got, name)
+    helpers.same_records(pc.parse_pslice_cabac(g["slice_data"].tobytes(), w, h, qp), got, name)
     for a, b in sc.FIELDS:
         assert np.array_equal(g[a], got[b]), (name, a)
     rbsp, _, _ = pc.nal_to_rbsp(g["nal"].tobytes())
     got = enc.parse_pslice_device(rbsp, int(g["nal_hdr_bits"]), qp)
-    _same_records(pc.parse_pslice_at(rbsp, int(g["nal_hdr_bits"]), w, h, qp), got, name + " (rbsp)")
+    helpers.same_records(pc.parse_pslice_at(rbsp, int(g["nal_hdr_bits"]), w, h, qp), got, name + " (rbsp)")
     assert enc.slice_records()[1], "the guard behind the records was written"
     with pytest.raises(pc.PcamvError):                  # alignment bits that are not ones: the host parser's error
         enc.parse_pslice_device(rbsp, int(g["nal_hdr_bits"]) - 3, qp)
@@ -64,7 +59,7 @@ def test_device_parser_on_live_wide_and_tall_pictures(pc):
         got = enc.parse_pslice_device(data, 0, qp)
         for a, b in sc.FIELDS:
             assert np.array_equal(mbs[a], got[b]), (W, H, t, a)
-        _same_records(pc.parse_pslice_cabac(data, W // 16, H // 16, qp), got, f"{W}x{H} frame {t}")
+        helpers.same_records(pc.parse_pslice_cabac(data, W // 16, H // 16, qp), got, f"{W}x{H} frame {t}")
     for enc in encs.values():
         enc.close()
 
@@ -79,7 +74,7 @@ def test_row_buffer_in_global_scratch(pc, monkeypatch):
     data = g["slice_data"].tobytes()
     want = pc.parse_pslice_cabac(data, w, h, qp)
     encs = [pc.Encoder(_params(pc, 16 * w, 16 * h)) for _ in range(5)]
-    _same_records(want, encs[0].parse_pslice_device(data, 0, qp), "probe, scratch rows")
+    helpers.same_records(want, encs[0].parse_pslice_device(data, 0, qp), "probe, scratch rows")
     for e in encs:
         e.rx_reserve(16 * w * h)
     batch = pc.Batch(encs)
@@ -89,7 +84,7 @@ def test_row_buffer_in_global_scratch(pc, monkeypatch):
     assert status.tolist() == [0, sc.host_parse(dict(data=bytes(bad), start_bit=0, qp=qp, mb_w=w, mb_h=h))[0], 0, -1, 0]
     for k in (0, 2, 4):
         got, guard_ok = encs[k].slice_records()
-        _same_records(want, got, f"slice {k}, scratch rows")
+        helpers.same_records(want, got, f"slice {k}, scratch rows")
         assert guard_ok
     batch.close()
     for e in encs:
@@ -97,7 +92,7 @@ def test_row_buffer_in_global_scratch(pc, monkeypatch):
     if sc.live_available():
         for W, H, t, qp, data, mbs in sc.live_slices():
             enc = pc.Encoder(_params(pc, W, H))
-            _same_records(pc.parse_pslice_cabac(data, W // 16, H // 16, qp), enc.parse_pslice_device(data, 0, qp), f"{W}x{H} frame {t}, scratch rows")
+            helpers.same_records(pc.parse_pslice_cabac(data, W // 16, H // 16, qp), enc.parse_pslice_device(data, 0, qp), f"{W}x{H} frame {t}, scratch rows")
             enc.close()
 
 
@@ -216,7 +211,7 @@ def test_damaged_slices_in_one_launch(pc):
         got, guard_ok = e.slice_records()
         assert guard_ok, "the guard behind the records was written"
         if rc == 0:
-            _same_records(mbs, got, "a slice that parses")
+            helpers.same_records(mbs, got, "a slice that parses")
             bits = ref.extract_pframe(mbs, 0.5)
             assert e.rx_tell()[0] == bits["m"] and np.array_equal(e.received(), bits["bits"])
         else:

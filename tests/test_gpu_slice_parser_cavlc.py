@@ -28,11 +28,6 @@ def _params(pc, W, H, cabac=0):
     return p
 
 
-def _same_records(a, b, what):
-    for f in a.dtype.names:
-        assert np.array_equal(a[f], b[f]), f"{what}: record field {f} differs"
-
-
 def test_feature_bit(pc):
     assert pc.features() & pc.FEATURE_SLICE_PARSER_CAVLC
     assert pc.features() & pc.FEATURE_SLICE_PARSER and pc.FEATURE_SLICE_PARSER_CAVLC == 0x4
@@ -44,13 +39,13 @@ def test_device_parser_equals_the_host_parser(pc, name):
     w, h = scv.dims(g)
     enc = pc.Encoder(_params(pc, 16 * w, 16 * h))
     got = enc.parse_pslice_cavlc_device(g["slice_data"].tobytes(), 0)
-    _same_records(pc.parse_pslice_cavlc(g["slice_data"].tobytes(), w, h), got, name)
+    helpers.same_records(pc.parse_pslice_cavlc(g["slice_data"].tobytes(), w, h), got, name)
     for a, b in scv.FIELDS:
         assert np.array_equal(g[a], got[b]), (name, a)
     rbsp, _, _ = pc.nal_to_rbsp(g["nal"].tobytes())
     hb = int(g["nal_hdr_bits"])
     got = enc.parse_pslice_cavlc_device(rbsp, hb)
-    _same_records(pc.parse_pslice_at(rbsp, hb, w, h), got, name + " (rbsp)")
+    helpers.same_records(pc.parse_pslice_at(rbsp, hb, w, h), got, name + " (rbsp)")
     for a, b in scv.FIELDS:
         assert np.array_equal(g[a], got[b]), (name, a, "rbsp")
     assert enc.slice_records()[1], "the guard behind the records was written"
@@ -71,7 +66,7 @@ def test_row_buffer_in_global_scratch(pc, monkeypatch):
     hb = int(g["nal_hdr_bits"])
     want = pc.parse_pslice_at(rbsp, hb, w, h)
     encs = [pc.Encoder(_params(pc, 16 * w, 16 * h)) for _ in range(5)]
-    _same_records(want, encs[0].parse_pslice_cavlc_device(rbsp, hb), "probe, scratch rows")
+    helpers.same_records(want, encs[0].parse_pslice_cavlc_device(rbsp, hb), "probe, scratch rows")
     for e in encs:
         e.rx_reserve(16 * w * h)
     batch = pc.Batch(encs)
@@ -83,7 +78,7 @@ def test_row_buffer_in_global_scratch(pc, monkeypatch):
     assert batch.slice_status().tolist() == codes
     for k in (0, 2, 4):
         got, guard_ok = encs[k].slice_records()
-        _same_records(want, got, f"slice {k}, scratch rows")
+        helpers.same_records(want, got, f"slice {k}, scratch rows")
         assert guard_ok
     for k in (1, 3):
         assert encs[k].slice_records()[1]
@@ -94,7 +89,7 @@ def test_row_buffer_in_global_scratch(pc, monkeypatch):
         for W, H, t, data, mbs in scv.live_slices():
             enc = pc.Encoder(_params(pc, W, H))
             got = enc.parse_pslice_cavlc_device(data, 0)
-            _same_records(pc.parse_pslice_cavlc(data, W // 16, H // 16), got, f"{W}x{H} frame {t}, scratch rows")
+            helpers.same_records(pc.parse_pslice_cavlc(data, W // 16, H // 16), got, f"{W}x{H} frame {t}, scratch rows")
             for a, b in scv.FIELDS:
                 assert np.array_equal(mbs[a], got[b]), (W, H, t, a)
             enc.close()
@@ -192,7 +187,7 @@ def test_damaged_slices_in_one_launch(pc):
         got, guard_ok = e.slice_records()
         assert guard_ok, "the guard behind the records was written"
         if rc == 0:
-            _same_records(mbs, got, "a slice that parses")
+            helpers.same_records(mbs, got, "a slice that parses")
             bits = ref.extract_pframe(mbs, 0.5)
             assert e.rx_tell()[0] == bits["m"] and np.array_equal(e.received(), bits["bits"])
         else:

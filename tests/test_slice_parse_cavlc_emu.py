@@ -10,11 +10,6 @@ import slice_cases_cavlc as scv
 from emu import slice_parse_cavlc_emu as emu
 
 
-def _same_records(a, b, what):
-    for f in a.dtype.names:
-        assert np.array_equal(a[f], b[f]), f"{what}: record field {f} differs"
-
-
 @pytest.mark.parametrize("name", scv.CAVLC_FIXTURES)
 def test_device_control_code_reads_the_fixtures(name):
     import pcamv_amd
@@ -23,7 +18,7 @@ def test_device_control_code_reads_the_fixtures(name):
     # through slice_data, from bit 0
     rc, got = emu.parse_at(g["slice_data"].tobytes(), 0, w, h)
     assert rc == 0
-    _same_records(pcamv_amd.parse_pslice_cavlc(g["slice_data"].tobytes(), w, h), got, name)
+    helpers.same_records(pcamv_amd.parse_pslice_cavlc(g["slice_data"].tobytes(), w, h), got, name)
     for a, b in scv.FIELDS:
         assert np.array_equal(g[a], got[b]), (name, a)
     assert (got["ref"] == 0).all()
@@ -33,8 +28,8 @@ def test_device_control_code_reads_the_fixtures(name):
     assert hb % 8
     rc, got2 = emu.parse_at(rbsp, hb, w, h)
     assert rc == 0
-    _same_records(pcamv_amd.parse_pslice_at(rbsp, hb, w, h), got2, name + " (rbsp)")
-    _same_records(got, got2, name + " (rbsp vs slice_data)")
+    helpers.same_records(pcamv_amd.parse_pslice_at(rbsp, hb, w, h), got2, name + " (rbsp)")
+    helpers.same_records(got, got2, name + " (rbsp vs slice_data)")
 
 
 def test_return_codes_of_bad_starts_and_sizes():
@@ -58,7 +53,7 @@ def test_return_codes_of_bad_starts_and_sizes():
     want, mbs = scv.host_parse(c)
     rc, got = emu.parse_at(c["data"], 0, 3, 3)
     assert want == 0 and rc == 0 and (got["i_type"] == pcamv_amd.P_SKIP).all()
-    _same_records(mbs, got, "nine skipped macroblocks")
+    helpers.same_records(mbs, got, "nine skipped macroblocks")
 
 
 def test_live_wide_and_tall_pictures():
@@ -74,6 +69,6 @@ def test_live_wide_and_tall_pictures():
             assert rc == 0, (W, H, t, rc, kw)
             for a, b in scv.FIELDS:
                 assert np.array_equal(mbs[a], got[b]), (W, H, t, a, kw)
-            _same_records(pcamv_amd.parse_pslice_cavlc(data, W // 16, H // 16), got, f"{W}x{H} frame {t} {kw}")
+            helpers.same_records(pcamv_amd.parse_pslice_cavlc(data, W // 16, H // 16), got, f"{W}x{H} frame {t} {kw}")
             seen |= set(np.unique(got["i_type"]).tolist())
     assert seen == {pcamv_amd.P_L0, pcamv_amd.P_8x8, pcamv_amd.P_SKIP}, seen

@@ -10,11 +10,6 @@ import slice_cases as sc
 from emu import slice_parse_emu
 
 
-def _same_records(a, b, what):
-    for f in a.dtype.names:
-        assert np.array_equal(a[f], b[f]), f"{what}: record field {f} differs"
-
-
 @pytest.mark.parametrize("name", sc.CABAC_FIXTURES)
 def test_device_control_code_reads_the_fixtures(name):
     import pcamv_amd
@@ -24,7 +19,7 @@ def test_device_control_code_reads_the_fixtures(name):
     # through slice_data
     rc, got = slice_parse_emu.parse_at(g["slice_data"].tobytes(), 0, w, h, qp)
     assert rc == 0
-    _same_records(pcamv_amd.parse_pslice_cabac(g["slice_data"].tobytes(), w, h, qp), got, name)
+    helpers.same_records(pcamv_amd.parse_pslice_cabac(g["slice_data"].tobytes(), w, h, qp), got, name)
     for a, b in sc.FIELDS:
         assert np.array_equal(g[a], got[b]), (name, a)
     assert (got["ref"] == 0).all()
@@ -32,8 +27,8 @@ def test_device_control_code_reads_the_fixtures(name):
     rbsp, _, _ = pcamv_amd.nal_to_rbsp(g["nal"].tobytes())
     rc, got2 = slice_parse_emu.parse_at(rbsp, int(g["nal_hdr_bits"]), w, h, qp)
     assert rc == 0
-    _same_records(pcamv_amd.parse_pslice_at(rbsp, int(g["nal_hdr_bits"]), w, h, qp), got2, name + " (rbsp)")
-    _same_records(got, got2, name + " (rbsp vs slice_data)")
+    helpers.same_records(pcamv_amd.parse_pslice_at(rbsp, int(g["nal_hdr_bits"]), w, h, qp), got2, name + " (rbsp)")
+    helpers.same_records(got, got2, name + " (rbsp vs slice_data)")
 
 
 def test_return_codes_of_bad_starts_and_sizes():
@@ -64,6 +59,6 @@ def test_live_wide_and_tall_pictures():
         assert rc == 0, (W, H, t, rc)
         for a, b in sc.FIELDS:
             assert np.array_equal(mbs[a], got[b]), (W, H, t, a)
-        _same_records(pcamv_amd.parse_pslice_cabac(data, W // 16, H // 16, qp), got, f"{W}x{H} frame {t}")
+        helpers.same_records(pcamv_amd.parse_pslice_cabac(data, W // 16, H // 16, qp), got, f"{W}x{H} frame {t}")
         seen |= set(np.unique(got["i_type"]).tolist())
     assert seen == {pcamv_amd.P_L0, pcamv_amd.P_8x8, pcamv_amd.P_SKIP}, seen

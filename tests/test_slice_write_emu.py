@@ -63,6 +63,39 @@ def test_carrier_arithmetic_is_the_embedding_stage_s():
     assert C.CDLL(swe.build()).swx_carrier_arithmetic_differs() == 0
 
 
+def test_partition_walk_tiles_every_partitioning():
+    """sp_partition, the one partition walk of the four slice coders, over 16x16, 16x8, 8x16 and all 256 P_8x8 partitionings: the
+    partitions come in ascending first block, tile the sixteen 4x4 blocks exactly once, start at the embedding stage's carrier
+    slots, and behind the last one (and at k = 16) the walk ends"""
+    import ctypes as C
+    lib = C.CDLL(swe.build())
+    P_L0, P_8x8, D_8x8 = 4, 5, 13
+    shapes = [(P_L0, d, 0x03030303) for d in (16, 14, 15)]
+    shapes += [(P_8x8, D_8x8, (c & 3) | (c >> 2 & 3) << 8 | (c >> 4 & 3) << 16 | (c >> 6 & 3) << 24) for c in range(256)]
+    assert len(set(shapes)) == 259
+    sizes = set()
+    for type_, partition, sub in shapes:
+        what = (type_, partition, hex(sub))
+        firsts, covered = [], []
+        for k in range(17):
+            pt = lib.swx_partition(type_, partition, sub, k)
+            if pt < 0:
+                break
+            first, w, h = pt & 255, pt >> 8 & 255, pt >> 16
+            assert w in (1, 2, 4) and h in (1, 2, 4), what
+            x0, y0 = helpers.BX[first], helpers.BY[first]
+            covered += [(x0 + dx, y0 + dy) for dy in range(h) for dx in range(w)]
+            firsts.append(first)
+            sizes.add((w, h))
+        n = len(firsts)
+        assert 1 <= n <= 16 and firsts == sorted(firsts), what
+        assert sorted(covered) == [(x, y) for x in range(4) for y in range(4)], what
+        slots = (C.c_int * 16)()
+        assert lib.swx_carrier_slots(type_, partition, sub, slots) == n and list(slots[:n]) == firsts, what
+        assert lib.swx_partition(type_, partition, sub, n) == -1 and lib.swx_partition(type_, partition, sub, 16) == -1, what
+    assert sizes == {(4, 4), (4, 2), (2, 4), (2, 2), (2, 1), (1, 2), (1, 1)}
+
+
 @pytest.mark.parametrize("name", sc.FINAL_FIXTURES)
 def test_first_pass_records_and_flip_map_give_the_final_slice(name):
     """the way the device gets a frame's final motion: the first-pass records (the CPU restatement's, from the fixture's pictures)

@@ -34,7 +34,6 @@ enum { ST_PLANES = 1, ST_ANALYSE = 2, ST_EMBED = 4, ST_PASS2 = 8 };
 /* what device code assumes of constants it cannot see side by side (this unit includes both headers) */
 static_assert(sizeof(pcamv_mb_t) == 59 * 4, "p2_unit_load copies a record as 59 dwords: a field added to pcamv_mb_t truncates or misaligns the second pass' LDS copy");
 static_assert(4 * P2_LROW(8) <= P2_TW && 4 * P2_CROW(8) <= P2_CW, "a tile row of the longest run (8 macroblocks and the four columns left of it) no longer fits the tile's pitch");
-static_assert(SW_LDS_COLS == SP_LDS_COLS, "the writer's row buffer in LDS is the parsers' (one PCAMV_SLICE_LDS_COLS lowers both)");
 static_assert(FLOW_SPEC_MIN_MBW - 1 > FLOW_SPEC_AHEAD + 1, "speculative chain: a macroblock would be handed on before its top / top-right neighbours are final");
 
 /* The builds of the RD instance of the analysis kernel (one translation unit each, pcamv_rd.hip), a row per entry of

@@ -26,8 +26,6 @@
 #include "pcamv_slice_parse_cavlc.h"
 #include "pcamv_slice_write.h"
 
-#define SP_LDS_COLS 128
-
 /* the slices of one launch: slice i is bytes[off[i] .. off[i] + len[i]), its slice data starts behind bit start_bit[i], slice QP qp[i] */
 struct SliceJobs {
     const uint8_t *bytes; long long bytes_size;

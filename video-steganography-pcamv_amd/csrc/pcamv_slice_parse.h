@@ -24,9 +24,13 @@
  *   ctx   the SP_NCTX context states a P slice of this path touches
  *   cmv / cmvd / cref / cnz   one macroblock's neighbourhood in x264's cache layout (8 columns; row 0 = the line above, column 3 =
  *         the column to the left), 48 positions each
- *   row   what the macroblocks of the next row read of this one, SP_ROW_BYTES per macroblock column -- the bottom row's four MVs
- *         and mvds, its coded_block_flags (luma 4, Cb 2, Cr 2), cbp, type -- overwritten column by column as the slice advances;
- *         the macroblock to the left is still in the cache when its neighbour is gathered.  No whole-picture field.
+ *   row   what the macroblocks of the next row read of this one, SP_ROW_BYTES per macroblock column -- the bottom row's four MVs,
+ *         its coded_block_flags (luma 4, Cb 2, Cr 2), its mvds, cbp, type: the SP_ROW_* layout -- overwritten column by column as the
+ *         slice advances; the macroblock to the left is still in the cache when its neighbour is gathered.  No whole-picture field.
+ *
+ * Stated here once: the row layout and SP_LDS_COLS for all four slice coders; for the CABAC pair (this parser, pcamv_slice_write.h)
+ * sp_gather, sp_hand_on, sp_fill_pskip and sp_init_contexts; for the writer sp_partition.  The CAVLC coders keep their own gather and
+ * hand-on (DESIGN.md 3g gives the measurement).  Each coder keeps its own syntax and entropy code.
  */
 #ifndef PCAMV_SLICE_PARSE_H
 #define PCAMV_SLICE_PARSE_H
@@ -58,7 +62,17 @@
 
 #define SP_NCTX 276             /* contexts 0..275 (PCAMV_CAB_USED): coeff_abs_level_minus1 of category 4 ends at 275 */
 #define SP_CTX_BYTES 320
+/* One column of the row buffer.  A CAVLC coder keeps the first SV_ROW_BYTES of it (cnz then holds total_coeffs), a CABAC coder all. */
+enum { SP_ROW_MV = 0,           /* the bottom row's four MVs */
+       SP_ROW_NZ = 16,          /* its flags or counts: luma 4, Cb 2, Cr 2 */
+       SP_ROW_MVD = 24,         /* its four mvds */
+       SP_ROW_CBP = 40,         /* cbp_luma | cbp_chroma << 4 | chroma DC flags << 8, two bytes */
+       SP_ROW_TYPE = 42 };
 #define SP_ROW_BYTES 48
+#define SV_ROW_BYTES 24
+static_assert(SV_ROW_BYTES == SP_ROW_MVD, "the CAVLC column is the prefix of the CABAC column that ends where the mvds begin");
+static_assert(SP_ROW_TYPE < SP_ROW_BYTES && SP_ROW_MV % 4 == 0 && SP_ROW_MVD % 4 == 0, "MVs and mvds are stored as dwords");
+#define SP_LDS_COLS 128         /* pictures up to this many macroblocks wide keep the row buffer in LDS (the kernels of all four coders) */
 #define SP_MAX_LEN (1 << 30)    /* bytes of one slice (positions are ints) */
 /* the standard's tables as one block, the form the device gets them in: context initialisers (m, n) of the first SP_NCTX contexts,
  * the state transitions, rangeTabLPS in the 128-state form */
@@ -73,7 +87,7 @@ struct SpState {
     uint32_t *cmv, *cmvd;               /* mvx | mvy << 16 */
     int8_t *cref;                       /* 0 = predicted from the one reference, -2 = not available */
     uint8_t *cnz;                       /* coded_block_flags: luma in the motion layout, chroma at sp_nzc_pos */
-    uint8_t *row;                       /* [mb_w][SP_ROW_BYTES], 4-byte aligned */
+    uint8_t *row;                       /* [mb_w][SP_ROW_BYTES] (CAVLC: SV_ROW_BYTES), 4-byte aligned */
     uint32_t *tl;                       /* [1] the MV above-left of the next macroblock (its row entry is overwritten before it is read) */
     uint32_t range, offset, cache;      /* cache: the low cbits bits are slice bits not yet consumed */
     int cbits, pos, overrun, partition, last_dqp, cbp_left, type_left;
@@ -203,6 +217,90 @@ SP_HD void sp_predict_pskip(const SpState &S, int mv[2])          /* 8.4.1.1 */
     sp_predict_from3(refa, refb, refc, a, b, c, mv);
 }
 
+/* ---------------------------------------------------------------- the neighbourhood of the CABAC coders (this parser, pcamv_slice_write.h) */
+/* The gather, one cache position per lane: the column to the left out of the cache as the last macroblock left it, the line above out
+ * of column rt of the row buffer, above-left from tl; everything else not available (MV, mvd and flag 0, reference -2) */
+SP_HD void sp_gather(SpState &S, const uint8_t *rt, bool left, bool top, bool topright)
+{
+    uint32_t g_mv[SP_SLOTS], g_mvd[SP_SLOTS], g_nz[SP_SLOTS]; int g_ref[SP_SLOTS];
+    SP_SYNC();
+    SP_LANES(q) if (q < 48) {
+        uint32_t mv = 0, mvd = 0, nz = 0; int ref = -2;
+        const int col = q & 7, r = q >> 3;
+        if (left && col == 3 && r >= 1 && r <= 4) { mv = S.cmv[q + 4]; mvd = S.cmvd[q + 4]; nz = S.cnz[q + 4]; ref = 0; }
+        if (left && (q == 8 || q == 16 || q == 32 || q == 40)) nz = S.cnz[q + 2];
+        if (top && q >= 4 && q < 8) { mv = sp_ld32(rt + SP_ROW_MV + 4 * (q - 4)); mvd = sp_ld32(rt + SP_ROW_MVD + 4 * (q - 4)); nz = rt[SP_ROW_NZ + q - 4]; ref = 0; }
+        if (top && (q == 1 || q == 2)) nz = rt[SP_ROW_NZ + 4 + q - 1];
+        if (top && (q == 25 || q == 26)) nz = rt[SP_ROW_NZ + 6 + q - 25];
+        if (left && top && q == 3) { mv = S.tl[0]; ref = 0; }
+        if (topright && q == 8) { mv = sp_ld32(rt + SP_ROW_BYTES + SP_ROW_MV); ref = 0; }
+        g_mv[SP_SLOT(q)] = mv; g_mvd[SP_SLOT(q)] = mvd; g_nz[SP_SLOT(q)] = nz; g_ref[SP_SLOT(q)] = ref;
+    }
+    SP_SYNC();
+    SP_LANES(q) if (q < 48) { S.cmv[q] = g_mv[SP_SLOT(q)]; S.cmvd[q] = g_mvd[SP_SLOT(q)]; S.cnz[q] = (uint8_t)g_nz[SP_SLOT(q)]; S.cref[q] = (int8_t)g_ref[SP_SLOT(q)]; }
+    SP_SYNC();
+}
+/* The hand-on to the next row: the macroblock's bottom row, cbp and type into column rt once the MV above-left of the next macroblock is
+ * out of it.  rec (the parser's; NULL in the writer): the macroblock's record leaves in the same pass, one dword per lane -- type,
+ * S.partition, sub, the sixteen MVs of the cache, skip_mv */
+SP_HD void sp_hand_on(SpState &S, uint8_t *rt, bool top, int cbp, int type, uint32_t *rec, uint32_t sub, uint32_t skip_mv)
+{
+    const uint32_t next_tl = top ? sp_ld32(rt + SP_ROW_MV + 12) : 0u;
+    SP_SYNC();
+    SP_LANES(l) {
+        if (rec && l < 59)
+            rec[l] = l == 0 ? (uint32_t)type : l == 1 ? (uint32_t)S.partition : l == 3 ? sub : l >= 8 && l < 24 ? S.cmv[sp_s8(l - 8)] : l == 56 ? skip_mv : 0u;
+        if (l < 4) { sp_st32(rt + SP_ROW_MV + 4 * l, S.cmv[36 + l]); sp_st32(rt + SP_ROW_MVD + 4 * l, S.cmvd[36 + l]); rt[SP_ROW_NZ + l] = S.cnz[36 + l]; }
+        else if (l < 8) rt[SP_ROW_NZ + l] = S.cnz[l < 6 ? 17 + (l - 4) : 41 + (l - 6)];
+        else if (l == 8) { rt[SP_ROW_CBP] = (uint8_t)(cbp & 255); rt[SP_ROW_CBP + 1] = (uint8_t)(cbp >> 8); rt[SP_ROW_TYPE] = (uint8_t)type; }
+    }
+    SP_SYNC();
+    S.tl[0] = next_tl;
+}
+/* a P_SKIP macroblock's motion: the prediction of 8.4.1.1 (returned in mv) into its sixteen blocks */
+SP_HD void sp_fill_pskip(SpState &S, int mv[2])
+{
+    sp_predict_pskip(S, mv);
+    const uint32_t p = SP_UNI(sp_pack(mv[0], mv[1]));
+    SP_SYNC();
+    SP_LANES(l) if (l < 16) { S.cmv[sp_s8(l)] = p; S.cref[sp_s8(l)] = 0; }
+    SP_SYNC();
+}
+/* Partition k of a macroblock in syntax order as first block | width << 8 | height << 16 (in 4x4 blocks), -1 behind the last: the
+ * writer's walk is ONE loop around ONE call of its mvd coder, where fifteen call sites had that coder inlined fifteen times.  sub: the
+ * four sub-partitions, one byte each, 0..3 (read for P_8x8 only).  Straight-line code: a slice is one wave's serial walk, and what
+ * does not depend on k leaves the loop. */
+static_assert(PCAMV_D_L0_4x4 == 0 && PCAMV_D_L0_8x4 == 1 && PCAMV_D_L0_4x8 == 2 && PCAMV_D_L0_8x8 == 3, "sp_partition computes with the sub-types' values");
+SP_HD int sp_partition(int type, int partition, uint32_t sub, int k)
+{
+    if (type != PCAMV_P_8x8) {
+        const int n = partition == PCAMV_D_16x16 ? 1 : partition == PCAMV_D_16x8 || partition == PCAMV_D_8x16 ? 2 : 0;
+        if ((unsigned)k >= (unsigned)n) return -1;
+        return (partition == PCAMV_D_16x8 ? 8 * k : 4 * k) | (partition == PCAMV_D_8x16 ? 2 : 4) << 8 | (partition == PCAMV_D_16x8 ? 2 : 4) << 16;
+    }
+    /* an 8x8 of sub-type t has 4 >> ((t + 1) >> 1) = 4, 2, 2, 1 partitions; ends: the running totals behind each 8x8, one byte each */
+    uint32_t ends = 0, n = 0;
+    for (int i = 0; i < 4; i++) { n += 4u >> ((((sub >> (8 * i)) & 3u) + 1u) >> 1); ends |= n << (8 * i); }
+    if ((unsigned)k >= n) return -1;
+    const int i = (k >= (int)(ends & 255u)) + (k >= (int)((ends >> 8) & 255u)) + (k >= (int)((ends >> 16) & 255u));
+    const int t = (int)((sub >> (8 * i)) & 3u), j = k - (int)(((ends << 8) >> (8 * i)) & 255u);      /* j: its place inside 8x8 i */
+    return (4 * i + (t == PCAMV_D_L0_8x4 ? 2 * j : j)) | (1 + (t & 1)) << 8 | (1 + (t >> 1)) << 16;
+}
+/* the first n_ctx context states at the slice start from the slice QP (pcamv_build_cabac_init), one per lane per pass */
+SP_HD void sp_init_contexts(SpState &S, const SpTables &T, int qp, int n_ctx)
+{
+    SP_SYNC();
+    for (int p = 0; p < (n_ctx + 63) / 64; p++)
+        SP_LANES(l) {
+            const int i = 64 * p + l;
+            if (i < n_ctx) {
+                const int v = ((T.init_p[2 * i] * qp) >> 4) + T.init_p[2 * i + 1];
+                S.ctx[i] = (uint8_t)(v < 1 ? 1 : v > 126 ? 126 : v);
+            }
+        }
+    SP_SYNC();
+}
+
 /* ---------------------------------------------------------------- macroblock layer */
 SP_HD int sp_mvd_cpn(SpState &S, int idx, int l)
 {
@@ -266,29 +364,11 @@ SP_HD int sp_run(SpState &S, int mb_w, int mb_h, pcamv_mb_t *out)
     for (int my = 0; my < mb_h; my++)
         for (int mx = 0; mx < mb_w; mx++) {
             const int xy = my * mb_w + mx;
-            const bool left = mx > 0, top = my > 0, topleft = left && top, topright = top && mx < mb_w - 1;
+            const bool left = mx > 0, top = my > 0;
             uint8_t *rt = S.row + (size_t)SP_ROW_BYTES * mx;
-            /* the neighbourhood, one cache position per lane: the column to the left out of the cache as the last macroblock left
-             * it, the line above out of the row buffer; everything else not available */
-            uint32_t g_mv[SP_SLOTS], g_mvd[SP_SLOTS], g_nz[SP_SLOTS]; int g_ref[SP_SLOTS];
-            SP_SYNC();
-            SP_LANES(q) if (q < 48) {
-                uint32_t mv = 0, mvd = 0, nz = 0; int ref = -2;
-                const int col = q & 7, r = q >> 3;
-                if (left && col == 3 && r >= 1 && r <= 4) { mv = S.cmv[q + 4]; mvd = S.cmvd[q + 4]; nz = S.cnz[q + 4]; ref = 0; }
-                if (left && (q == 8 || q == 16 || q == 32 || q == 40)) nz = S.cnz[q + 2];
-                if (top && q >= 4 && q < 8) { mv = sp_ld32(rt + 4 * (q - 4)); mvd = sp_ld32(rt + 16 + 4 * (q - 4)); nz = rt[32 + q - 4]; ref = 0; }
-                if (top && (q == 1 || q == 2)) nz = rt[36 + q - 1];
-                if (top && (q == 25 || q == 26)) nz = rt[38 + q - 25];
-                if (topleft && q == 3) { mv = S.tl[0]; ref = 0; }
-                if (topright && q == 8) { mv = sp_ld32(rt + SP_ROW_BYTES); ref = 0; }
-                g_mv[SP_SLOT(q)] = mv; g_mvd[SP_SLOT(q)] = mvd; g_nz[SP_SLOT(q)] = nz; g_ref[SP_SLOT(q)] = ref;
-            }
-            SP_SYNC();
-            SP_LANES(q) if (q < 48) { S.cmv[q] = g_mv[SP_SLOT(q)]; S.cmvd[q] = g_mvd[SP_SLOT(q)]; S.cnz[q] = (uint8_t)g_nz[SP_SLOT(q)]; S.cref[q] = (int8_t)g_ref[SP_SLOT(q)]; }
-            SP_SYNC();
-            const int cl = left ? S.cbp_left : -1, ct = top ? (int)(rt[40] | rt[41] << 8) : -1;
-            const int tl = left ? S.type_left : -1, tt = top ? (int)rt[42] : -1;
+            sp_gather(S, rt, left, top, top && mx < mb_w - 1);
+            const int cl = left ? S.cbp_left : -1, ct = top ? (int)(rt[SP_ROW_CBP] | rt[SP_ROW_CBP + 1] << 8) : -1;
+            const int tl = left ? S.type_left : -1, tt = top ? (int)rt[SP_ROW_TYPE] : -1;
 
             int type = PCAMV_P_L0, partition = PCAMV_D_16x16, skip_mv[2] = {0, 0};
             uint32_t sub = PCAMV_D_L0_8x8 * 0x01010101u;               /* i_sub_partition[4], one byte each */
@@ -296,11 +376,7 @@ SP_HD int sp_run(SpState &S, int mb_w, int mb_h, pcamv_mb_t *out)
             S.partition = PCAMV_D_16x16;
             const int skip = sp_decision(S, 11 + (tl >= 0 && tl != PCAMV_P_SKIP) + (tt >= 0 && tt != PCAMV_P_SKIP));
             if (skip) {
-                sp_predict_pskip(S, skip_mv);
-                const uint32_t mv = sp_pack(skip_mv[0], skip_mv[1]);
-                SP_SYNC();
-                SP_LANES(l) if (l < 16) { S.cmv[sp_s8(l)] = mv; S.cref[sp_s8(l)] = 0; }
-                SP_SYNC();
+                sp_fill_pskip(S, skip_mv);
                 type = PCAMV_P_SKIP;
                 S.last_dqp = 0;
             } else {
@@ -317,6 +393,7 @@ SP_HD int sp_run(SpState &S, int mb_w, int mb_h, pcamv_mb_t *out)
                         else t = sp_decision(S, 23) ? PCAMV_D_L0_4x8 : PCAMV_D_L0_4x4;
                         sub |= (uint32_t)t << (8 * i);
                     }
+                    /* (its own walk: the loop over sp_partition cost k_parse_pslice 1.2 %, 15.785 against 15.599 ms) */
                     for (int i = 0; i < 4; i++) {
                         const int t = (int)((sub >> (8 * i)) & 255u);
                         if (t == PCAMV_D_L0_8x8) sp_mvd(S, 4 * i, 2, 2);
@@ -358,28 +435,9 @@ SP_HD int sp_run(SpState &S, int mb_w, int mb_h, pcamv_mb_t *out)
                     }
                 } else S.last_dqp = 0;
             }
-            /* the record, one dword per lane; what the next macroblocks read: the bottom row into the row buffer once the MV
-             * above-left of the next macroblock is out of it */
-            const uint32_t next_tl = top ? sp_ld32(rt + 12) : 0u;
+            /* the record, and what the next macroblocks read */
             const int cbp = cbp_luma | cbp_chroma << 4 | dcf << 8;
-            uint32_t *o = (uint32_t *)(void *)(out + xy);
-            SP_SYNC();
-            SP_LANES(l) {
-                if (l < 59) {
-                    uint32_t v = 0;
-                    if (l == 0) v = (uint32_t)type;
-                    else if (l == 1) v = (uint32_t)partition;
-                    else if (l == 3) v = sub;
-                    else if (l >= 8 && l < 24) v = S.cmv[sp_s8(l - 8)];
-                    else if (l == 56) v = sp_pack(skip_mv[0], skip_mv[1]);
-                    o[l] = v;
-                }
-                if (l < 4) { sp_st32(rt + 4 * l, S.cmv[36 + l]); sp_st32(rt + 16 + 4 * l, S.cmvd[36 + l]); rt[32 + l] = S.cnz[36 + l]; }
-                else if (l < 8) rt[36 + l - 4] = S.cnz[l < 6 ? 17 + (l - 4) : 41 + (l - 6)];
-                else if (l == 8) { rt[40] = (uint8_t)(cbp & 255); rt[41] = (uint8_t)(cbp >> 8); rt[42] = (uint8_t)type; }
-            }
-            SP_SYNC();
-            S.tl[0] = next_tl;
+            sp_hand_on(S, rt, top, cbp, type, (uint32_t *)(void *)(out + xy), sub, sp_pack(skip_mv[0], skip_mv[1]));
             S.cbp_left = cbp; S.type_left = type;
             const int end = sp_terminal(S);
             if (end != (xy == mb_w * mb_h - 1)) return PCAMV_EINVAL;        /* end_of_slice_flag in the wrong place */
@@ -404,16 +462,7 @@ SP_HD int pcamv_slice_parse(SpState &S, const SpTables &T, const uint8_t *rbsp, 
     S.src = rbsp + (start_bit >> 3); S.len = (int)(len - (start_bit >> 3));
     if (S.len < 2) return PCAMV_EINVAL;
     S.trans = T.trans; S.rlps = T.rlps;
-    SP_SYNC();
-    for (int p = 0; p < (SP_NCTX + 63) / 64; p++)          /* context states at the slice start (pcamv_build_cabac_init), one per lane per pass */
-        SP_LANES(l) {
-            const int i = 64 * p + l;
-            if (i < SP_NCTX) {
-                const int v = ((T.init_p[2 * i] * qp) >> 4) + T.init_p[2 * i + 1];
-                S.ctx[i] = (uint8_t)(v < 1 ? 1 : v > 126 ? 126 : v);
-            }
-        }
-    SP_SYNC();
+    sp_init_contexts(S, T, qp, SP_NCTX);
     S.pos = 0; S.win_base = -1024; S.cache = 0; S.cbits = 0; S.overrun = 0;
     S.range = 510; S.offset = sp_bits(S, 9);
     return sp_run(S, mb_w, mb_h, out);

@@ -32,8 +32,8 @@
  *   cmv / cref / cnz   one macroblock's neighbourhood in x264's cache layout, 48 positions each; cnz holds total_coeff,
  *         0x80 = not available
  *   row   what the macroblocks of the next row read of this one, SV_ROW_BYTES per macroblock column: the bottom row's four MVs
- *         and its eight total_coeffs (luma 4, Cb 2, Cr 2).  The type of the macroblock above is not kept: no CAVLC syntax element
- *         of a P slice depends on it (a skipped macroblock above counts through its total_coeffs, which are 0).
+ *         (SP_ROW_MV) and its eight total_coeffs (SP_ROW_NZ: luma 4, Cb 2, Cr 2).  The type of the macroblock above is not kept:
+ *         no CAVLC syntax element of a P slice depends on it (a skipped macroblock above counts through its total_coeffs, 0).
  */
 #ifndef PCAMV_SLICE_PARSE_CAVLC_H
 #define PCAMV_SLICE_PARSE_CAVLC_H
@@ -46,7 +46,6 @@
 #define SV_BALLOT(hit, l) ((uint64_t)((hit) ? 1 : 0) << (l))               /* ... or adds its bit, SP_LANES being a loop */
 #endif
 
-#define SV_ROW_BYTES 24
 /* The VLC tables as one block, the form the device gets them in.  One 16-bit entry per code: len | code << 5 (len 0: no such
  * code).  coeff_token: 5 classes (nC 0-1, 2-3, 4-7, 8+, chroma DC) of 64 entries, entry 4 (total_coeff - 1) + trailing_ones, and
  * entry 3 -- a slot no token has -- the class's total_coeff = 0 code.  total_zeros: 15 rows of 16; for chroma DC 3 rows of 4;
@@ -218,11 +217,11 @@ SP_HD int sv_run(SvState &S, int mb_w, int mb_h, pcamv_mb_t *out)
                 const int col = q & 7, r = q >> 3;
                 if (left && col == 3 && r >= 1 && r <= 4) { mv = S.cmv[q + 4]; nz = S.cnz[q + 4]; ref = 0; }
                 if (left && (q == 8 || q == 16 || q == 32 || q == 40)) nz = S.cnz[q + 2];
-                if (top && q >= 4 && q < 8) { mv = sp_ld32(rt + 4 * (q - 4)); nz = rt[16 + q - 4]; ref = 0; }
-                if (top && (q == 1 || q == 2)) nz = rt[20 + q - 1];
-                if (top && (q == 25 || q == 26)) nz = rt[22 + q - 25];
+                if (top && q >= 4 && q < 8) { mv = sp_ld32(rt + SP_ROW_MV + 4 * (q - 4)); nz = rt[SP_ROW_NZ + q - 4]; ref = 0; }
+                if (top && (q == 1 || q == 2)) nz = rt[SP_ROW_NZ + 4 + q - 1];
+                if (top && (q == 25 || q == 26)) nz = rt[SP_ROW_NZ + 6 + q - 25];
                 if (topleft && q == 3) { mv = S.tl[0]; ref = 0; }
-                if (topright && q == 8) { mv = sp_ld32(rt + SV_ROW_BYTES); ref = 0; }
+                if (topright && q == 8) { mv = sp_ld32(rt + SV_ROW_BYTES + SP_ROW_MV); ref = 0; }
                 if (col >= 4 && r >= 1 && r <= 4) nz = 0;
                 if ((col == 1 || col == 2) && (r == 1 || r == 2 || r == 4 || r == 5)) nz = 0;
                 g_mv[SP_SLOT(q)] = mv; g_nz[SP_SLOT(q)] = nz; g_ref[SP_SLOT(q)] = ref;
@@ -291,7 +290,7 @@ SP_HD int sv_run(SvState &S, int mb_w, int mb_h, pcamv_mb_t *out)
             }
             /* the record, one dword per lane; what the next macroblocks read: the bottom row into the row buffer once the MV
              * above-left of the next macroblock is out of it */
-            const uint32_t next_tl = top ? sp_ld32(rt + 12) : 0u;
+            const uint32_t next_tl = top ? sp_ld32(rt + SP_ROW_MV + 12) : 0u;
             uint32_t *o = (uint32_t *)(void *)(out + xy);
             SP_SYNC();
             SP_LANES(l) {
@@ -304,8 +303,8 @@ SP_HD int sv_run(SvState &S, int mb_w, int mb_h, pcamv_mb_t *out)
                     else if (l == 56) v = sp_pack(skip_mv[0], skip_mv[1]);
                     o[l] = v;
                 }
-                if (l < 4) { sp_st32(rt + 4 * l, S.cmv[36 + l]); rt[16 + l] = S.cnz[36 + l]; }
-                else if (l < 8) rt[20 + l - 4] = S.cnz[l < 6 ? 17 + (l - 4) : 41 + (l - 6)];
+                if (l < 4) { sp_st32(rt + SP_ROW_MV + 4 * l, S.cmv[36 + l]); rt[SP_ROW_NZ + l] = S.cnz[36 + l]; }
+                else if (l < 8) rt[SP_ROW_NZ + l] = S.cnz[l < 6 ? 17 + (l - 4) : 41 + (l - 6)];
             }
             SP_SYNC();
             S.tl[0] = next_tl;

@@ -20,10 +20,10 @@
  * (k_extract_prepare), so a P_L0 16x16 without residual whose MV equals the skip prediction is NOT folded into P_SKIP as
  * x264_macroblock_encode would (macroblock.c:783-794); the analysis' own walk of the coded macroblock (entropy_commit) does not either.
  *
- * What is shared with the parser (pcamv_slice_parse.h, unchanged): the working memory of the neighbourhood (SpState: cmv, cmvd,
- * cref, cnz, the row buffer with its SP_ROW_BYTES layout, tl), the MV prediction (sp_predict_mv, sp_predict_pskip), the cache
- * geometry (sp_s8, sp_nzc_pos), SP_LANES / SP_SYNC / SP_UNI.  The gather and the hand-on to the next row are restated here, since
- * the parser keeps them inside sp_run.
+ * What is shared with the parser (pcamv_slice_parse.h): the working memory of the neighbourhood (SpState: cmv, cmvd, cref, cnz, the
+ * row buffer with its SP_ROW_* layout, tl) and its mechanics (sp_gather, sp_hand_on, sp_fill_pskip, sp_partition), the context
+ * initialisation (sp_init_contexts), the MV prediction (sp_predict_mv, sp_predict_pskip), the cache geometry (sp_s8, sp_nzc_pos),
+ * SP_LANES / SP_SYNC / SP_UNI.
  *
  * Output.  Final bytes go through sw_emit: with as_nal, emulation prevention runs there, on each byte as it becomes final (the rule
  * of x264_nal_encode, common/common.c:679-691, needs the count of zeros before the byte and nothing else: two bits of state, and no
@@ -197,29 +197,12 @@ PCAMV_DEV int sw_run(SwState &W, const FrameDev &F, MBLocal *L, const pcamv_mb_t
     for (int my = 0; my < mb_h; my++)
         for (int mx = 0; mx < mb_w; mx++) {
             const int xy = my * mb_w + mx;
-            const bool left = mx > 0, top = my > 0, topleft = left && top, topright = top && mx < mb_w - 1;
+            const bool left = mx > 0, top = my > 0;
             uint8_t *rt = S.row + (size_t)SP_ROW_BYTES * mx;
             if (xy) sw_terminal0(W);                                        /* end_of_slice_flag 0 of the macroblock before */
-            /* the neighbourhood, one cache position per lane (the parser's gather: pcamv_slice_parse.h, sp_run) */
-            uint32_t g_mv[SP_SLOTS], g_mvd[SP_SLOTS], g_nz[SP_SLOTS]; int g_ref[SP_SLOTS];
-            SP_SYNC();
-            SP_LANES(q) if (q < 48) {
-                uint32_t mv = 0, mvd = 0, nz = 0; int ref = -2;
-                const int col = q & 7, r = q >> 3;
-                if (left && col == 3 && r >= 1 && r <= 4) { mv = S.cmv[q + 4]; mvd = S.cmvd[q + 4]; nz = S.cnz[q + 4]; ref = 0; }
-                if (left && (q == 8 || q == 16 || q == 32 || q == 40)) nz = S.cnz[q + 2];
-                if (top && q >= 4 && q < 8) { mv = sp_ld32(rt + 4 * (q - 4)); mvd = sp_ld32(rt + 16 + 4 * (q - 4)); nz = rt[32 + q - 4]; ref = 0; }
-                if (top && (q == 1 || q == 2)) nz = rt[36 + q - 1];
-                if (top && (q == 25 || q == 26)) nz = rt[38 + q - 25];
-                if (topleft && q == 3) { mv = S.tl[0]; ref = 0; }
-                if (topright && q == 8) { mv = sp_ld32(rt + SP_ROW_BYTES); ref = 0; }
-                g_mv[SP_SLOT(q)] = mv; g_mvd[SP_SLOT(q)] = mvd; g_nz[SP_SLOT(q)] = nz; g_ref[SP_SLOT(q)] = ref;
-            }
-            SP_SYNC();
-            SP_LANES(q) if (q < 48) { S.cmv[q] = g_mv[SP_SLOT(q)]; S.cmvd[q] = g_mvd[SP_SLOT(q)]; S.cnz[q] = (uint8_t)g_nz[SP_SLOT(q)]; S.cref[q] = (int8_t)g_ref[SP_SLOT(q)]; }
-            SP_SYNC();
-            const int cl = left ? S.cbp_left : -1, ct = top ? (int)(rt[40] | rt[41] << 8) : -1;
-            const int tl = left ? S.type_left : -1, tt = top ? (int)rt[42] : -1;
+            sp_gather(S, rt, left, top, top && mx < mb_w - 1);
+            const int cl = left ? S.cbp_left : -1, ct = top ? (int)(rt[SP_ROW_CBP] | rt[SP_ROW_CBP + 1] << 8) : -1;
+            const int tl = left ? S.type_left : -1, tt = top ? (int)rt[SP_ROW_TYPE] : -1;
 
             /* the record: type, partition, sub-partitions; anything else is not a P macroblock of this path */
             const pcamv_mb_t *r = mbs + xy;
@@ -234,12 +217,7 @@ PCAMV_DEV int sw_run(SwState &W, const FrameDev &F, MBLocal *L, const pcamv_mb_t
             const int skip = type == PCAMV_P_SKIP;
             sw_decision(W, 11 + (tl >= 0 && tl != PCAMV_P_SKIP) + (tt >= 0 && tt != PCAMV_P_SKIP), skip);
             if (skip) {
-                int pm[2];
-                sp_predict_pskip(S, pm);
-                const uint32_t mv = SP_UNI(sp_pack(pm[0], pm[1]));
-                SP_SYNC();
-                SP_LANES(l) if (l < 16) { S.cmv[sp_s8(l)] = mv; S.cref[sp_s8(l)] = 0; }
-                SP_SYNC();
+                int pm[2]; sp_fill_pskip(S, pm);
             } else {
                 sw_decision(W, 14, 0);
                 if (type == PCAMV_P_8x8) { sw_decision(W, 15, 0); sw_decision(W, 16, 1); }
@@ -251,16 +229,8 @@ PCAMV_DEV int sw_run(SwState &W, const FrameDev &F, MBLocal *L, const pcamv_mb_t
                         sw_decision(W, 21, t == PCAMV_D_L0_8x8);
                         if (t != PCAMV_D_L0_8x8) { sw_decision(W, 22, t != PCAMV_D_L0_8x4); if (t != PCAMV_D_L0_8x4) sw_decision(W, 23, t == PCAMV_D_L0_4x8); }
                     }
-                    for (int i = 0; i < 4; i++) {
-                        const int t = (int)((sub >> (8 * i)) & 255u);
-                        if (t == PCAMV_D_L0_8x8) sw_mvd(W, 4 * i, 2, 2);
-                        else if (t == PCAMV_D_L0_8x4) { sw_mvd(W, 4 * i, 2, 1); sw_mvd(W, 4 * i + 2, 2, 1); }
-                        else if (t == PCAMV_D_L0_4x8) { sw_mvd(W, 4 * i, 1, 2); sw_mvd(W, 4 * i + 1, 1, 2); }
-                        else for (int k = 0; k < 4; k++) sw_mvd(W, 4 * i + k, 1, 1);
-                    }
-                } else if (partition == PCAMV_D_16x16) sw_mvd(W, 0, 4, 4);
-                else if (partition == PCAMV_D_16x8) { sw_mvd(W, 0, 4, 2); sw_mvd(W, 8, 4, 2); }
-                else { sw_mvd(W, 0, 2, 4); sw_mvd(W, 4, 2, 4); }
+                }
+                for (int k = 0, pt; (pt = sp_partition(type, partition, sub, k)) >= 0; k++) sw_mvd(W, pt & 255, (pt >> 8) & 255, pt >> 16);
                 /* coded_block_pattern */
                 sw_decision(W, 76 - ((cl >> 1) & 1) - ((ct >> 1) & 2), cbp_luma & 1);
                 sw_decision(W, 76 - (cbp_luma & 1) - ((ct >> 2) & 2), (cbp_luma >> 1) & 1);
@@ -301,17 +271,9 @@ PCAMV_DEV int sw_run(SwState &W, const FrameDev &F, MBLocal *L, const pcamv_mb_t
             }
             if (W.bad) return PCAMV_EINVAL;
             if (W.n > W.cap) return PCAMV_ENOMEM;
-            /* what the next macroblocks read: the bottom row into the row buffer once the MV above-left of the next macroblock is out of it */
-            const uint32_t next_tl = top ? sp_ld32(rt + 12) : 0u;
+            /* what the next macroblocks read */
             const int cbp = cbp_luma | cbp_chroma << 4 | dcf << 8;
-            SP_SYNC();
-            SP_LANES(l) {
-                if (l < 4) { sp_st32(rt + 4 * l, S.cmv[36 + l]); sp_st32(rt + 16 + 4 * l, S.cmvd[36 + l]); rt[32 + l] = S.cnz[36 + l]; }
-                else if (l < 8) rt[36 + l - 4] = S.cnz[l < 6 ? 17 + (l - 4) : 41 + (l - 6)];
-                else if (l == 8) { rt[40] = (uint8_t)(cbp & 255); rt[41] = (uint8_t)(cbp >> 8); rt[42] = (uint8_t)type; }
-            }
-            SP_SYNC();
-            S.tl[0] = next_tl;
+            sp_hand_on(S, rt, top, cbp, type, nullptr, 0, 0);
             S.cbp_left = cbp; S.type_left = type;
             if (hash) {
                 uint32_t h = 2166136261u;
@@ -337,20 +299,11 @@ PCAMV_DEV int pcamv_slice_write(SwState &W, const SpTables &T, const FrameDev &F
     if (qp < 0 || qp > 51) return PCAMV_EINVAL;
     SpState &S = W.S;
     S.trans = T.trans; S.rlps = T.rlps;
-    SP_SYNC();
-    for (int p = 0; p < (SW_NCTX + 63) / 64; p++)
-        SP_LANES(l) {
-            const int i = 64 * p + l;
-            if (i < SW_NCTX) {
-                const int v = ((T.init_p[2 * i] * qp) >> 4) + T.init_p[2 * i + 1];
-                S.ctx[i] = (uint8_t)(v < 1 ? 1 : v > 126 ? 126 : v);
-            }
-        }
+    sp_init_contexts(S, T, qp, SW_NCTX);
     SP_LANES(l) { if (l < 48) { S.cmv[l] = 0; S.cmvd[l] = 0; S.cnz[l] = 0; S.cref[l] = -2; } if (l == 0) S.tl[0] = 0; }
     SP_SYNC();
-    W.low = 0; W.range = 0x1FE; W.queue = -1; W.outstanding = 0; W.pend = -1;
-    W.dst = dst; W.cap = cap; W.n = 0; W.fill = (int)((uintptr_t)dst & 3u); W.abase = -(long long)W.fill;
-    W.as_nal = 0; W.zeros = 0; W.bad = 0;
+    W.low = 0; W.range = 0x1FE; W.queue = -1; W.outstanding = 0; W.pend = -1; W.bad = 0;
+    sw_out_begin(W, dst, cap);
     if (as_nal) { sw_raw(W, 0); sw_raw(W, 0); sw_raw(W, 0); sw_raw(W, 1); sw_raw(W, (uint32_t)H.nal_byte & 255u); W.as_nal = 1; }
     for (int k = 0; k < (H.n_bits + 7) >> 3; k++) {
         uint32_t b = SP_UNI(H.bits[k]);

@@ -3,7 +3,7 @@
  * (gfx950).  The writer itself is pcamv_slice_write.h (shared with the host test drivers); this unit gives it its working memory --
  * LDS of the wave: the parser's neighbourhood memory and row buffer, all 460 context states, the two tables of the serial chain, an
  * output buffer of SW_OBUF bytes and a whole MBLocal, since a macroblock's levels are made here from its final motion with the
- * analysis' primitives -- and the slice's place in the batch.  Pictures wider than SW_LDS_COLS macroblocks keep the row buffer in
+ * analysis' primitives -- and the slice's place in the batch.  Pictures wider than SP_LDS_COLS macroblocks keep the row buffer in
  * the wave's slot of a global scratch buffer.
  *
  * A CABAC slice is serial; as for the parsers the answer is one wave per slice and thousands of slices in flight.  No spin-wait, no
@@ -20,7 +20,7 @@
 static __global__ void __launch_bounds__(64) k_write_pslice(const FrameDev *__restrict__ Fs, const WriteJobs J)
 {
     __shared__ MBLocal L;
-    __shared__ uint32_t s_mv[48], s_mvd[48], s_tl[1], s_tab[(256 + 512) / 4], s_row[SW_LDS_COLS * SP_ROW_BYTES / 4], s_obuf[SW_OBUF / 4], s_ctx[SW_CTX_BYTES / 4];
+    __shared__ uint32_t s_mv[48], s_mvd[48], s_tl[1], s_tab[(256 + 512) / 4], s_row[SP_LDS_COLS * SP_ROW_BYTES / 4], s_obuf[SW_OBUF / 4], s_ctx[SW_CTX_BYTES / 4];
     __shared__ uint8_t s_nz[48];
     __shared__ int8_t s_ref[48];
     static_assert(SW_TAB_TRANS % 4 == 0, "the table block is copied in dwords");
@@ -28,7 +28,7 @@ static __global__ void __launch_bounds__(64) k_write_pslice(const FrameDev *__re
     const FrameDev F = Fs[i];
     for (int k = lane; k < (256 + 512) / 4; k += 64) s_tab[k] = ((const uint32_t *)(J.tab + SW_TAB_TRANS))[k];
     SP_SYNC();
-    const int lds_cols = J.lds_cols < SW_LDS_COLS ? J.lds_cols : SW_LDS_COLS;
+    const int lds_cols = J.lds_cols < SP_LDS_COLS ? J.lds_cols : SP_LDS_COLS;
     SwState W;
     SpState &S = W.S;
     S.win = nullptr; S.ctx = (uint8_t *)s_ctx; S.cmv = s_mv; S.cmvd = s_mvd; S.cref = s_ref; S.cnz = s_nz; S.tl = s_tl;

@@ -209,7 +209,7 @@ PCAMV_DEV int swv_run(SwvState &W, const FrameDev &F, MBLocal *L, const pcamv_mb
             const int xy = my * mb_w + mx;
             const bool left = mx > 0, top = my > 0, topleft = left && top, topright = top && mx < mb_w - 1;
             uint8_t *rt = S.row + (size_t)SV_ROW_BYTES * mx;
-            /* the neighbourhood, one cache position per lane (the parser's gather: pcamv_slice_parse_cavlc.h, sv_run) */
+            /* the neighbourhood, one cache position per lane (the CAVLC parser's gather: pcamv_slice_parse_cavlc.h, sv_run) */
             uint32_t g_mv[SP_SLOTS], g_nz[SP_SLOTS]; int g_ref[SP_SLOTS];
             SP_SYNC();
             SP_LANES(q) if (q < 48) {
@@ -217,11 +217,11 @@ PCAMV_DEV int swv_run(SwvState &W, const FrameDev &F, MBLocal *L, const pcamv_mb
                 const int col = q & 7, r = q >> 3;
                 if (left && col == 3 && r >= 1 && r <= 4) { mv = S.cmv[q + 4]; nz = S.cnz[q + 4]; ref = 0; }
                 if (left && (q == 8 || q == 16 || q == 32 || q == 40)) nz = S.cnz[q + 2];
-                if (top && q >= 4 && q < 8) { mv = sp_ld32(rt + 4 * (q - 4)); nz = rt[16 + q - 4]; ref = 0; }
-                if (top && (q == 1 || q == 2)) nz = rt[20 + q - 1];
-                if (top && (q == 25 || q == 26)) nz = rt[22 + q - 25];
+                if (top && q >= 4 && q < 8) { mv = sp_ld32(rt + SP_ROW_MV + 4 * (q - 4)); nz = rt[SP_ROW_NZ + q - 4]; ref = 0; }
+                if (top && (q == 1 || q == 2)) nz = rt[SP_ROW_NZ + 4 + q - 1];
+                if (top && (q == 25 || q == 26)) nz = rt[SP_ROW_NZ + 6 + q - 25];
                 if (topleft && q == 3) { mv = S.tl[0]; ref = 0; }
-                if (topright && q == 8) { mv = sp_ld32(rt + SV_ROW_BYTES); ref = 0; }
+                if (topright && q == 8) { mv = sp_ld32(rt + SV_ROW_BYTES + SP_ROW_MV); ref = 0; }
                 if (col >= 4 && r >= 1 && r <= 4) nz = 0;
                 if ((col == 1 || col == 2) && (r == 1 || r == 2 || r == 4 || r == 5)) nz = 0;
                 g_mv[SP_SLOT(q)] = mv; g_nz[SP_SLOT(q)] = nz; g_ref[SP_SLOT(q)] = ref;
@@ -309,11 +309,11 @@ PCAMV_DEV int swv_run(SwvState &W, const FrameDev &F, MBLocal *L, const pcamv_mb
             }
             if (W.n > W.cap) return PCAMV_ENOMEM;
             /* what the next macroblocks read: the bottom row into the row buffer once the MV above-left of the next macroblock is out of it */
-            const uint32_t next_tl = top ? sp_ld32(rt + 12) : 0u;
+            const uint32_t next_tl = top ? sp_ld32(rt + SP_ROW_MV + 12) : 0u;
             SP_SYNC();
             SP_LANES(l) {
-                if (l < 4) { sp_st32(rt + 4 * l, S.cmv[36 + l]); rt[16 + l] = S.cnz[36 + l]; }
-                else if (l < 8) rt[20 + l - 4] = S.cnz[l < 6 ? 17 + (l - 4) : 41 + (l - 6)];
+                if (l < 4) { sp_st32(rt + SP_ROW_MV + 4 * l, S.cmv[36 + l]); rt[SP_ROW_NZ + l] = S.cnz[36 + l]; }
+                else if (l < 8) rt[SP_ROW_NZ + l] = S.cnz[l < 6 ? 17 + (l - 4) : 41 + (l - 6)];
             }
             SP_SYNC();
             S.tl[0] = next_tl;

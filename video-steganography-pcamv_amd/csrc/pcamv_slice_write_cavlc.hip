@@ -3,7 +3,7 @@
  * wavefront per slice (gfx950).  The writer itself is pcamv_slice_write_cavlc.h (shared with the host test drivers); this unit gives
  * it its working memory -- LDS of the wave: a whole MBLocal, since a macroblock's levels are made here from its final motion with the
  * analysis' primitives, the CAVLC parser's neighbourhood and row buffer, the table block, the 26 per-lane block strings with their
- * lengths, an output buffer of SW_OBUF bytes -- and the slice's place in the batch.  Pictures wider than SW_LDS_COLS macroblocks keep
+ * lengths, an output buffer of SW_OBUF bytes -- and the slice's place in the batch.  Pictures wider than SP_LDS_COLS macroblocks keep
  * the row buffer in the wave's slot of a global scratch buffer.
  *
  * One wave per slice and thousands of slices in flight, as for k_write_pslice; inside a macroblock the 26 residual blocks are coded
@@ -21,7 +21,7 @@
 static __global__ void __launch_bounds__(64) k_write_pslice_cavlc(const FrameDev *__restrict__ Fs, const WriteJobs J)
 {
     __shared__ MBLocal L;
-    __shared__ uint32_t s_mv[48], s_tl[1], s_tab[SV_TAB_BYTES / 4], s_row[SW_LDS_COLS * SV_ROW_BYTES / 4], s_obuf[SW_OBUF / 4];
+    __shared__ uint32_t s_mv[48], s_tl[1], s_tab[SV_TAB_BYTES / 4], s_row[SP_LDS_COLS * SV_ROW_BYTES / 4], s_obuf[SW_OBUF / 4];
     __shared__ uint32_t s_blk[SWV_NBLK * SWV_BLK_DWORDS], s_blen[SWV_NBLK];
     __shared__ uint8_t s_nz[48];
     __shared__ int8_t s_ref[48];
@@ -30,7 +30,7 @@ static __global__ void __launch_bounds__(64) k_write_pslice_cavlc(const FrameDev
     const FrameDev F = Fs[i];
     for (int k = lane; k < SV_TAB_BYTES / 4; k += 64) s_tab[k] = ((const uint32_t *)J.tab)[k];
     SP_SYNC();
-    const int lds_cols = J.lds_cols < SW_LDS_COLS ? J.lds_cols : SW_LDS_COLS;
+    const int lds_cols = J.lds_cols < SP_LDS_COLS ? J.lds_cols : SP_LDS_COLS;
     SwvState W;
     SvState &S = W.S;
     S.win = nullptr; S.ctx = nullptr; S.cmvd = nullptr; S.cmv = s_mv; S.cref = s_ref; S.cnz = s_nz; S.tl = s_tl;

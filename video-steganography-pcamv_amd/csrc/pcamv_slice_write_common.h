@@ -103,9 +103,8 @@ PCAMV_DEV int sw_slot_rank(int type, uint32_t sub, int s)
 }
 
 /* The record r as the writers read it: declares type, partition, sub (the four sub-partitions, one byte each) and used, and makes the
- * calling function return PCAMV_EINVAL / PCAMV_EUNSUP where the record is no P macroblock of this path.  A macro and not a function
- * so that k_write_pslice compiles to the instructions it had before the CAVLC writer shared this: with the checks behind a call the
- * compiler laid the kernel's registers out differently. */
+ * calling function return PCAMV_EINVAL / PCAMV_EUNSUP where the record is no P macroblock of this path.  A macro because it declares
+ * the caller's four values and returns from the caller. */
 #define SW_READ_RECORD(r, type, partition, sub, used) \
     int type = (int)SP_UNI((r)->i_type), partition = (int)SP_UNI((r)->i_partition); \
     const uint32_t sub = SP_UNI((uint32_t)(r)->i_sub_partition[0] | (uint32_t)(r)->i_sub_partition[1] << 8 | (uint32_t)(r)->i_sub_partition[2] << 16 | \
@@ -141,7 +140,6 @@ PCAMV_DEV void sw_motion_levels(SpState &S, const FrameDev &F, MBLocal *L, const
 
 /* the slices of one launch of a writer: slice i goes to bytes[off[i] .. off[i] + cap[i]), its length to len[i], its return code to status[i] */
 #define SW_HDR_WORDS 4
-#define SW_LDS_COLS 128         /* SP_LDS_COLS of the parsers: pictures up to this many macroblocks wide keep the row buffer in LDS */
 struct WriteJobs {
     uint8_t *bytes; long long bytes_size;
     const long long *off, *cap; long long *len; int *status;
