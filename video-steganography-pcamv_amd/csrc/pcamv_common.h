@@ -347,7 +347,9 @@ struct MEState {
 
 
 /* diagnostics build (-DPCAMV_PROF): wave cycles per phase of k_analyse_flow, summed in pcamv_prof[] (tools/dbg/prof_phases.py); slots 43..46 count
- * the RD trials: all, with the kept trial's motion, with an earlier trial's, reusing and cheaper than the kept one (tools/dbg/rd_reuse_count.py) */
+ * the RD trials: all, with the kept trial's motion, with an earlier trial's, reusing and cheaper than the kept one (tools/dbg/rd_reuse_count.py);
+ * slots 39 and 47 count the luma and the chroma passes of the SATD lists, slot 31 the luma passes that run on the matrix core and
+ * slot 23 those of them that read the LDS window (tools/dbg/satd_pass_count.py) */
 #if defined(PCAMV_PROF) && !defined(PCAMV_HOST_EMU)
 #define PCAMV_PROF_N 48
 static __device__ unsigned long long pcamv_prof[PCAMV_PROF_N];

@@ -29,6 +29,13 @@ __device__ __forceinline__ int pcamv_lane_id(void) { int l = (int)(threadIdx.x &
 #define PCAMV_RD_LO 0
 #endif
 #define LANE() (PCAMV_RD_LO ? (int)(threadIdx.x & 63) : pcamv_lane_id())
+/* PCAMV_SATD_MAT, a compile-time constant: the SATD lists of 16x16 blocks run on the matrix core (satd16x16_rows_mat).  The --me tesa
+ * instances set it to 0 (pcamv_tesa.hip, pcamv_rd.hip by the build's variant): their full-pel lists are SATD lists, the RD one runs a
+ * single wave per SIMD with nobody to fill the waits for the matrix results, and it measured 0.37 % slower with the matrix path
+ * (continued) */
+#ifndef PCAMV_SATD_MAT
+#define PCAMV_SATD_MAT 1
+#endif
 /* clamp to [0,255] of an already shifted value.  The empty asm keeps hipcc (ROCm 7.2) from fusing
  * shift + clamp of two neighbours into v_ashr_pk_u8_i32: the code it emits around that gfx950
  * instruction ORs further bytes into the destination assuming bits [31:16] come back zero, but
@@ -179,6 +186,41 @@ __device__ __forceinline__ int satd4x4_half(const uint32_t ec[8], const uint32_t
     return (int)acc.x + (int)acc.y;
 }
 
+/* ---- the same metric on the matrix core (the SATD lists of 16x16 blocks) ----
+ * The 4x4 Hadamard transform is a product with the constant +-1 matrix H16 = H4 (x) H4.  Every pixel byte XORed with 0x80 is the
+ * signed byte p - 128; one v_mfma_i32_16x16x32_i8 takes as A (16 rows of K = 32) the 16 source and the 16 reference pixels of
+ * sixteen 4x4 blocks, lane (m = lane & 15, g = lane >> 4) supplying row g of block m (source dword low, reference dword high), and
+ * as B the constant [H16 ; -H16].  D[m][n] = coefficient n of H16 (e - r) of block m: the two offsets cancel, |D| <= 16 * 255, i32
+ * sums are exact.  Lane (n, g) receives coefficient n of the blocks 4g .. 4g+3.  The accumulator is preset to SATD_BIAS, so every
+ * D is in [28688, 36848] with a zero high half and v_sad_u16(D, SATD_BIAS, acc) = |coefficient| + acc in one instruction. */
+typedef int v4i32 __attribute__((ext_vector_type(4)));
+#define SATD_BIAS 32768
+/* the lane's 8 bytes of B: column n = coefficient (a, b) = (n >> 2, n & 3), k = 8g .. 8g+7 = the source pixels of row g (x = 0..3),
+ * then the reference pixels of that row with the opposite sign */
+__device__ __forceinline__ long satd_mat_operand(int lane)
+{
+    const int n = lane & 15, g = lane >> 4, a = n >> 2, b = n & 3;
+    uint32_t pat = b == 0 ? 0x01010101u : b == 1 ? 0xff01ff01u : b == 2 ? 0xffff0101u : 0x01ffff01u;
+    if (__builtin_popcount(a & g) & 1) pat ^= 0xfefefefeu;        /* +1 <-> -1 in every byte */
+    return (long)(((uint64_t)(pat ^ 0xfefefefeu) << 32) | pat);
+}
+/* Four instructions = the 16 blocks of four 16x16 candidates: block m = 4 * candidate + block column, instruction j = block row.
+ * e[j] (XORed with 0x80808080 already) and r[j] are row g of block (m, j).  Every lane of lane row g gets candidate g's SATD
+ * (x264's: half the sum of the absolute coefficients, which is even per block as all 16 have the parity of the pixel sum). */
+__device__ __forceinline__ int satd16x16_rows_mat(const uint32_t e[4], const uint32_t r[4], long hb)
+{
+    const v4i32 bias = {SATD_BIAS, SATD_BIAS, SATD_BIAS, SATD_BIAS};
+    uint32_t s = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const long a = (long)(((uint64_t)(r[j] ^ 0x80808080u) << 32) | e[j]);
+        const v4i32 d = __builtin_amdgcn_mfma_i32_16x16x32_i8(a, hb, bias, 0, 0, 0);
+#pragma unroll
+        for (int i = 0; i < 4; i++) s = __builtin_amdgcn_sad_u16((uint32_t)d[i], (uint32_t)SATD_BIAS, s);
+    }
+    return group_sum((int)s, 16) >> 1;
+}
+
 /* mc_chroma (mc.c:246-277) of a 4x4 block: rows as 8-byte loads, the bilinear weights as one
  * v_dot4_u32_u8 per output pixel over the bytes {A[i], A[i+1], B[i], B[i+1]} */
 __device__ __forceinline__ void chroma_rows_load(gp8 cb, uint32_t cstride, uint32_t off, uint64_t row[5])
@@ -273,9 +315,13 @@ __device__ __forceinline__ void chroma_block4_win(const MBLocal *L, int b, int m
  *           fetches its 4x4 reference pixels (one or two planes, v_lerp_u8), SAD (v_sad_u8) or the
  *           packed Hadamard, DPP butterfly over the nblk lanes, MV bits looked up per lane, the
  *           group's first lane stores the total to ccost[c];
+ *           the SATD list of a 16x16 block (PCAMV_SATD_MAT): lane = 16 g + m fetches ROW g of the four blocks of block column
+ *           m & 3 of candidate m >> 2, four candidates per pass, v_mfma_i32_16x16x32_i8 (satd16x16_rows_mat) leaves candidate
+ *           g's total in lane row g, lane 20 g stores it (the MAT side of the `luma` lambda below);
  *   chroma: (partitions >= 8x8) lane = slot * 2nb + plane * nb + blk, both planes of 128/nblk
  *           candidates per pass, group totals added to ccost[c] with an LDS atomic;
  *   result: lane c reads ccost[c], key = cost << 6 | c, wave minimum -> smallest cost, first index. */
+template <bool B> struct BoolC { static constexpr bool value = B; };
 /* what a list evaluation reads of the frame descriptor */
 struct EvalEnv { const int16_t *cost_mv; const uint8_t *luma_base, *chroma_base; long long plane_size, cplane_size; int lskip, cstride; int *trace; int trace_mb; };
 __device__ __forceinline__ EvalRes eval_list_body(const EvalEnv &F, MBLocal *L, const uint8_t *enc, int ip_, int xoff_, int yoff_,
@@ -290,20 +336,35 @@ __device__ __forceinline__ EvalRes eval_list_body(const EvalEnv &F, MBLocal *L, 
     const unsigned long long t_ev = PROF_T();
     PROF_CNT(32, 1); PROF_CNT(33, n);
     int key_acc = 0x7fffffff;
-    {
-        const int slot = lane >> lgn, blk = lane & (nblk - 1);
-        const int px = xoff + 4 * (blk & ((1 << lgw) - 1)), py = yoff + 4 * (blk >> lgw);
+    /* MAT (the SATD list of a 16x16 block, on the matrix core): lane (m = lane & 15, g = lane >> 4) fetches ROW g of the four blocks
+     * of block column m & 3 of the pass's candidate m >> 2 (rows RS = 4 apart), satd16x16_rows_mat leaves candidate g's sum in lane
+     * row g, and of that row the lane that fetched for candidate g (m = 4g: it has looked up that candidate's MV bits) stores it */
+    auto luma = [&](auto mat) __attribute__((always_inline)) {
+        constexpr bool MAT = decltype(mat)::value;
+        /* what the two mappings differ in: the candidate slot the lane fetches for, blk == 0 in the lane that stores a candidate's
+         * total, the lane's first row and column, the step between its four rows, the candidates per pass */
+        constexpr int RS = MAT ? 4 : 1;
+        int slot, blk, px, py, cpp;
+        if (MAT) {
+            const int m = lane & 15, g = lane >> 4;
+            slot = m >> 2; blk = lane ^ mul24s(g, 20); px = xoff + 4 * (m & 3); py = yoff + g; cpp = 4;
+        } else {
+            slot = lane >> lgn; blk = lane & (nblk - 1); px = xoff + 4 * (blk & ((1 << lgw) - 1)); py = yoff + 4 * (blk >> lgw); cpp = 64 >> lgn;
+        }
         uint32_t e[4], ec[8];
         const uint8_t *encl = (flags & EV_SRC4) ? enc + (slot & 3) * 384 : enc;       /* the slot's source stays the same in every pass */
 #pragma unroll
-        for (int k = 0; k < 4; k++) e[k] = lds4(encl + (py + k) * 16 + px);
-        if (satd) pk_cols(e, ec);
+        for (int k = 0; k < 4; k++) e[k] = lds4(encl + (py + k * RS) * 16 + px) ^ (MAT ? 0x80808080u : 0u);
+        if (!MAT && satd) pk_cols(e, ec);
+        const long hb = MAT ? satd_mat_operand(lane) : 0;
         const gp8 lb = (gp8)F.luma_base;
         const uint32_t stride = PCAMV_LROW, psz = (uint32_t)F.plane_size, lskip = (uint32_t)F.lskip;
-        const gp8 lb1 = lb + stride, lb2 = lb1 + stride, lb3 = lb2 + stride;
+        const gp8 lb1 = lb + RS * stride, lb2 = lb1 + RS * stride, lb3 = lb2 + RS * stride;
         const uint32_t rowbase = (uint32_t)(L->mb_y * 16 + py + PCAMV_PAD) * stride, colbase = (uint32_t)(L->mb_x * 16 + px + PCAMV_PAD);
-        const int cpp = 64 >> lgn;
         for (int p0 = 0; p0 < n; p0 += cpp) {
+            if (MAT || satd) PROF_CNT(39, 1);
+            if (MAT) PROF_CNT(31, 1);
+            if (MAT && (flags & EV_WIN)) PROF_CNT(23, 1);
             const int c = p0 + slot;
             const uint32_t xy = L->cxy[c < n ? c : 0];
             const bool act = c < n && xy != CAND_NONE;
@@ -320,11 +381,11 @@ __device__ __forceinline__ EvalRes eval_list_body(const EvalEnv &F, MBLocal *L, 
                 const int wb = (L->mb_y * 16 + py + PCAMV_PAD + (mvy >> 2) - L->win_y0) * WIN_LW + (L->mb_x * 16 + px + PCAMV_PAD + (mvx >> 2) - L->win_x0);
                 const int ba = wb + ((dx != 0) + 2 * (dy == 2)) * WIN_LP + (dy == 3 ? WIN_LW : 0);
 #pragma unroll
-                for (int k = 0; k < 4; k++) r[k] = wld4(L, ba + k * WIN_LW);
+                for (int k = 0; k < 4; k++) r[k] = wld4(L, ba + k * RS * WIN_LW);
                 if ((dx | dy) & 1) {
                     const int bb = wb + (dy ? (2 + (dx == 2)) * WIN_LP : 0) + (dx == 3);
 #pragma unroll
-                    for (int k = 0; k < 4; k++) r[k] = avg4(r[k], wld4(L, bb + k * WIN_LW));
+                    for (int k = 0; k < 4; k++) r[k] = avg4(r[k], wld4(L, bb + k * RS * WIN_LW));
                 }
             } else if (flags & EV_FPEL) {
                 r[0] = gld4(lb, o); r[1] = gld4(lb1, o); r[2] = gld4(lb2, o); r[3] = gld4(lb3, o);
@@ -341,18 +402,20 @@ __device__ __forceinline__ EvalRes eval_list_body(const EvalEnv &F, MBLocal *L, 
             }
             asm volatile("" : "+v"(mvb0), "+v"(mvb1), "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]));
             int v;
-            if (satd) v = satd4x4_half(ec, r);
+            if (MAT) v = satd16x16_rows_mat(e, r, hb);
+            else if (satd) v = satd4x4_half(ec, r);
             else {
                 uint32_t sa = 0;
 #pragma unroll
                 for (int k = 0; k < 4; k++) sa = __builtin_amdgcn_sad_u8(e[k], r[k], sa);
                 v = (int)sa;
             }
-            v = group_sum(v, nblk) + mvb0 + mvb1;
+            v = (MAT ? v : group_sum(v, nblk)) + mvb0 + mvb1;
             if (blk == 0 && c < n) L->ccost[c] = act ? v : PCAMV_COST_MAX;
             if (blk == 0 && act) key_acc = imin(key_acc, (v << 6) | c);
         }
-    }
+    };
+    if (PCAMV_SATD_MAT && satd && ip == PIX_16x16) luma(BoolC<true>()); else luma(BoolC<false>());
     PCAMV_WAVE_SYNC();
     if ((flags & EV_CHROMA) && ip <= PIX_8x8) {
         const int lgnb = lgn - 2, nb = 1 << lgnb, lgcw = lgw - 1;          /* chroma 4x4 blocks per plane: 4,2,2,1 */
@@ -368,6 +431,7 @@ __device__ __forceinline__ EvalRes eval_list_body(const EvalEnv &F, MBLocal *L, 
         const uint32_t rowbase = (plane ? (uint32_t)F.cplane_size : 0u) + mul24u((uint32_t)(L->mb_y * 8 + py + PCAMV_CPAD), cstride) + (uint32_t)(L->mb_x * 8 + px + PCAMV_CPAD);
         const int cpp = 64 >> (lgnb + 1);
         for (int p0 = 0; p0 < n; p0 += cpp) {
+            if (satd) PROF_CNT(47, 1);
             const int c = p0 + slot;
             const uint32_t xy = L->cxy[c < n ? c : 0];
             const bool act = c < n && xy != CAND_NONE;

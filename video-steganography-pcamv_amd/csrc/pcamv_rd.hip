@@ -36,6 +36,7 @@ static constexpr int RD_VARIANT = rd_build_defs[RD_BUILD].variant;
 /* pcamv_prims_gpu.h LANE(): a build for one wave per SIMD has the registers to keep what is computed from the lane number */
 static constexpr bool RD_ONE_WAVE = rd_build_defs[RD_BUILD].occ == 1;
 #define PCAMV_RD_LO RD_ONE_WAVE
+#define PCAMV_SATD_MAT (!(RD_VARIANT & V_TESA))       /* pcamv_prims_gpu.h: the --me tesa build keeps the packed SATD for its 16x16 lists */
 #define PCAMV_RESIDUAL_CALL 1      /* pcamv_prims_rd_gpu.h: the CABAC residual walk as a function of its own */
 #include "pcamv_flow.hip.h"
 

@@ -9,6 +9,7 @@
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#define PCAMV_SATD_MAT 0         /* pcamv_prims_gpu.h: the --me tesa instances keep the packed SATD for their 16x16 lists */
 #include "pcamv_flow.hip.h"
 
 static __global__ void __launch_bounds__(64, PCAMV_FLOW_OCC) k_analyse_flow_tesa(const FrameDev *__restrict__ Fs, FlowDev fl)
