@@ -29,6 +29,8 @@
  *   pcamv_gpu_*extract_*, rx_*  (no reference counterpart: the extractor is absent from the reference)
  *   pcamv_gpu_*_slices*,        (no reference counterpart) the receiver fed from stream bytes: CABAC and CAVLC P slices parsed on
  *   parse_pslice_*_device       the device, one wavefront per slice (k_parse_pslice, k_parse_pslice_cavlc), straight into the extractor
+ *   pcamv_gpu_*_nals*,          the same fed NAL units: what a decoder's NAL layer undoes of x264_nal_encode (common/common.c:658-690), on
+ *   nal_to_rbsp_device          the device, one wavefront per unit (k_nal_to_rbsp), in front of either parser
  *   pcamv_gpu_*write_*          the second pass' x264_macroblock_write_cabac + x264_cabac_encode_flush (encoder/cabac.c:781, common/cabac.c:908)
  *                               and x264_nal_encode (common/common.c:658): the P slice of a step written on the device (k_write_pslice);
  *                               the *_cavlc calls x264_macroblock_write_cavlc (encoder/cavlc.c:288) instead (k_write_pslice_cavlc)
@@ -302,6 +304,7 @@ int pcamv_gpu_abi_version(void);
 #define PCAMV_FEATURE_SLICE_PARSER_CAVLC 0x4u   /* ... and CAVLC P slices (the *_cavlc calls there) */
 #define PCAMV_FEATURE_SLICE_WRITER 0x8u /* CABAC P slices written on the device (the sender to a stream, at the end of this file) */
 #define PCAMV_FEATURE_SLICE_WRITER_CAVLC 0x10u  /* ... and CAVLC P slices (the *_cavlc calls there) */
+#define PCAMV_FEATURE_NAL_DEVICE 0x20u  /* the receiver takes NAL units: emulation prevention undone on the device (the *_nals* calls) */
 unsigned pcamv_gpu_features(void);
 
 /* ---- Payload path: the caller's bits through the device-resident entry points, and back out on the device ----
@@ -348,7 +351,7 @@ int pcamv_gpu_batch_payload_check(pcamv_batch_t *batch, int64_t *diff);
 
 /* ---- Receiver from a stream: CABAC P slices parsed on the device (kernel k_parse_pslice, one wavefront per slice) ----
  *
- * What a receiver holds is a stream.  These calls take RBSP bytes (pcamv_gpu_nal_to_rbsp stays the front end; the caller gives the
+ * What a receiver holds is a stream.  These calls take RBSP bytes (the *_nals* calls further down take NAL units; the caller gives the
  * bit behind the slice header and the slice QP, as for pcamv_gpu_parse_pslice_cabac_at) and parse them where the extractor runs: no
  * host parse, no upload of records, no synchronisation per frame.  Scope and return codes per slice are the host parser's: frame
  * macroblocks, one reference, 4x4 transform, cabac_init_idc 0; PCAMV_EUNSUP for an intra macroblock, PCAMV_EINVAL for a slice that
@@ -398,6 +401,34 @@ int pcamv_gpu_parse_pslice_cavlc_device(pcamv_ctx_t *ctx, const uint8_t *rbsp, s
 int pcamv_gpu_batch_extract_slices_cavlc(pcamv_batch_t *batch, const pcamv_slice_t *slices, float emrate, void *stream);      /* slice_qp is not read */
 int pcamv_gpu_batch_extract_slices_cavlc_device(pcamv_batch_t *batch, const void *bytes, size_t bytes_size, const int64_t *off,
                                                 const int64_t *len, const int64_t *start_bit, float emrate, void *stream);
+
+/* ---- The receiver on NAL units: emulation prevention undone on the device (kernel k_nal_to_rbsp, one wavefront per unit) ----
+ *
+ * The extract_slices* calls above with NAL units in place of RBSPs -- what a stream carries and what the writers below produce with
+ * as_nal = 1: optional Annex B start code (long or short), header byte, payload with emulation_prevention_three_bytes.  One launch of
+ * k_nal_to_rbsp in front of the parser undoes that layer for every context's unit, with the semantics of pcamv_gpu_nal_to_rbsp on every
+ * input: a unit with nothing behind its start code, with forbidden_zero_bit set, with 00 00 0{0,1,2} behind its header byte or with
+ * 00 00 03 xx, xx > 03, is a PCAMV_EINVAL slice (it appends nothing; pcamv_gpu_batch_slice_status); nal_unit_type is not looked at.
+ * The RBSPs go to a buffer of the library's, taken in turn with a second one like the staging buffers: the caller's bytes are read
+ * only.  One unit per context per call.
+ * start_bit counts bits of the RBSP, from the first byte behind the NAL header byte: the number the RBSP calls take.  The units of
+ * one call must not overlap one another in `bytes`: unit i's RBSP is written at [off[i], off[i] + len[i]) of the library's buffer, so
+ * an overlap is never a memory error, but what overlapping units unescape to is unspecified.
+ * nal_header (optional): an int32 device array of one entry per context that receives each unit's header byte, -1 for a unit
+ * without one; it belongs to `stream` like the other arrays.  Borrowed buffers and their ordering rule, staging with one copy, the
+ * refusal of the other entropy mode's contexts (PCAMV_EUNSUP) and the per-context status are those of the calls above. */
+int pcamv_gpu_batch_extract_nals(pcamv_batch_t *batch, const pcamv_slice_t *units, float emrate, void *stream);        /* rbsp / len: the unit */
+int pcamv_gpu_batch_extract_nals_cavlc(pcamv_batch_t *batch, const pcamv_slice_t *units, float emrate, void *stream);
+int pcamv_gpu_batch_extract_nals_device(pcamv_batch_t *batch, const void *bytes, size_t bytes_size, const int64_t *off, const int64_t *len,
+                                        const int64_t *start_bit, const int32_t *slice_qp, int32_t *nal_header, float emrate, void *stream);
+int pcamv_gpu_batch_extract_nals_cavlc_device(pcamv_batch_t *batch, const void *bytes, size_t bytes_size, const int64_t *off, const int64_t *len,
+                                              const int64_t *start_bit, int32_t *nal_header, float emrate, void *stream);
+/* The parity probe; synchronises.  n units of one host buffer, unit i at bytes[off[i] .. off[i] + len[i]), unescaped by one launch on
+ * the context's device and stream (nothing else of the context is used).  out[bytes_size] receives unit i's RBSP at off[i] and is
+ * otherwise returned as it came (a caller's guard pattern survives); out_len[i] its length or -1, status[i] its return code,
+ * nal_header[i] (optional) its header byte or -1.  Entries that do not fit the buffer are PCAMV_EINVAL units. */
+int pcamv_gpu_nal_to_rbsp_device(pcamv_ctx_t *ctx, const uint8_t *bytes, size_t bytes_size, const int64_t *off, const int64_t *len, int n,
+                                 uint8_t *out, int64_t *out_len, int32_t *status, int32_t *nal_header);
 
 /* ---- Sender to a stream: CABAC P slices written on the device (kernel k_write_pslice, one wavefront per slice) ----
  *

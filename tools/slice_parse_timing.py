@@ -6,7 +6,13 @@ core, and 16 threads.  With --cavlc the same sweep for --no-cabac streams: tests
 k_parse_pslice_cavlc, Batch.extract_slices_cavlc, pcamv_gpu_parse_pslice_cavlc_at.  Prints one JSON line and writes it to --out, which
 holds one line per mode: the line of the mode that ran is replaced, the other one kept.  Needs a GPU.
 
+With --nal the receiver on NAL units instead: the same fixture wrapped by rbsp_to_nal, every context with its own copy
+in one device tensor, 256 and 4096 units in flight -- k_nal_to_rbsp's time next to the parser's of the same run (the same hipEvents),
+and the wall time of Batch.extract_nals_device against Batch.extract_slices_device on the same content.  Written to
+profiles/nal_unescape_timing.json, one line per entropy mode.
+
     python tools/slice_parse_timing.py [--cavlc] [--counts 1,64,1024,4096] [--reps 5] [--out profiles/slice_parse_timing.json]
+    python tools/slice_parse_timing.py --nal [--cavlc] [--counts 256,4096] [--reps 5] [--out profiles/nal_unescape_timing.json]
 """
 import argparse
 import ctypes as C
@@ -20,14 +26,79 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "video-steganography-pcamv_amd")]
 
 
+def nal_sweep(args, pcamv_amd, np, torch, out, rbsp, hb, qp, m, want):
+    """--nal: out["device"] gets one entry per count; `want`: the host parser's records of the slice"""
+    dev = torch.device("cuda", 0)
+    nal = pcamv_amd.rbsp_to_nal(rbsp, 2, 1)
+    assert pcamv_amd.nal_to_rbsp(nal)[0] == rbsp
+    out.update(kernel="k_nal_to_rbsp", parser=out["kernel"], unit_bytes=len(nal), escapes=len(nal) - 5 - len(rbsp))
+    p = pcamv_amd.param_default(out["width"], out["height"])
+    pcamv_amd.param_parse(p, "subme", 5)
+    p.b_cabac = 0 if args.cavlc else 1
+    encs = []
+    for n in [int(v) for v in args.counts.split(",")]:
+        while len(encs) < n:
+            e = pcamv_amd.Encoder(p)
+            e.rx_reserve((3 * args.reps + 3) * m)
+            encs.append(e)
+        batch = pcamv_amd.Batch(encs[:n])
+        for e in encs[:n]:
+            e.rx_reset()
+        stride = (len(nal) + 3) | 1                         # every context its own copy, at odd offsets
+        off = torch.arange(n, dtype=torch.int64, device=dev) * stride
+        hdr = torch.full((n,), hb, dtype=torch.int64, device=dev)
+        qps = [] if args.cavlc else [torch.full((n,), qp, dtype=torch.int32, device=dev)]
+        forms = {}
+        for name, blob in (("nal", nal), ("rbsp", rbsp)):
+            forms[name] = (torch.from_numpy(np.tile(np.frombuffer(blob + bytes(stride - len(blob)), np.uint8), n)).to(dev), off,
+                           torch.full((n,), len(blob), dtype=torch.int64, device=dev), hdr, *qps, 0.5)
+        calls = dict(nal=batch.extract_nals_cavlc_device if args.cavlc else batch.extract_nals_device,
+                     rbsp=batch.extract_slices_cavlc_device if args.cavlc else batch.extract_slices_device)
+        torch.cuda.synchronize()                            # the tensors are complete before the library's stream reads them
+        for name in ("nal", "rbsp"):
+            calls[name](*forms[name])                       # first launch: allocations, code load
+        torch.cuda.synchronize()
+        # the two kernels of the same launches
+        batch.kernel_time("k_nal_to_rbsp", reset=True); batch.kernel_time(out["parser"], reset=True)
+        for _ in range(args.reps):
+            calls["nal"](*forms["nal"])
+        torch.cuda.synchronize()
+        ms, launches = batch.kernel_time("k_nal_to_rbsp", reset=True)
+        parser_ms, parser_launches = batch.kernel_time(out["parser"], reset=True)
+        if launches != args.reps or parser_launches != args.reps:
+            sys.exit("slice_parse_timing.py: a launch was not timed")
+        # the two calls in turn, each between two synchronisations: neither form has the quieter half of the run
+        wall = dict(nal=0.0, rbsp=0.0)
+        for _ in range(args.reps):
+            for name in ("nal", "rbsp"):
+                w0 = time.perf_counter()
+                calls[name](*forms[name])
+                torch.cuda.synchronize()
+                wall[name] += (time.perf_counter() - w0) / args.reps
+                if (batch.slice_status() != 0).any():
+                    sys.exit("slice_parse_timing.py: a unit failed on the device")
+        got = encs[n - 1].slice_records()[0]
+        if any(not np.array_equal(got[f], want[f]) for f in got.dtype.names) or encs[n - 1].rx_tell()[0] != (3 * args.reps + 2) * m:
+            sys.exit("slice_parse_timing.py: the device's records differ from the host parser's")
+        out["device"].append(dict(units=n, unescape_kernel_ms=ms, parser_kernel_ms=parser_ms, unescape_share_of_parser=ms / parser_ms,
+                                  unescape_gb_per_s=n * len(nal) / (ms * 1e-3) / 1e9, extract_nals_device_wall_ms=wall["nal"] * 1e3,
+                                  extract_slices_device_wall_ms=wall["rbsp"] * 1e3, wall_ratio=wall["nal"] / wall["rbsp"]))
+        batch.close()
+    for e in encs:
+        e.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cavlc", action="store_true", help="CAVLC slices on --no-cabac contexts instead of CABAC ones")
-    ap.add_argument("--counts", default="1,64,1024,4096")
+    ap.add_argument("--nal", action="store_true", help="the receiver on NAL units: k_nal_to_rbsp next to the parser (profiles/nal_unescape_timing.json)")
+    ap.add_argument("--counts", default=None, help="default 1,64,1024,4096; with --nal 256,4096")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--host-threads", type=int, default=16)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "slice_parse_timing.json"))
+    ap.add_argument("--out", default=None, help="default profiles/slice_parse_timing.json; with --nal profiles/nal_unescape_timing.json")
     args = ap.parse_args()
+    args.counts = args.counts or ("256,4096" if args.nal else "1,64,1024,4096")
+    args.out = args.out if args.out is not None else os.path.join(ROOT, "profiles", "nal_unescape_timing.json" if args.nal else "slice_parse_timing.json")
     import numpy as np
     import torch
     import pcamv_amd
@@ -58,6 +129,9 @@ def main():
         return mbs
 
     want = host_parse(20)
+    if args.nal:
+        nal_sweep(args, pcamv_amd, np, torch, out, rbsp, hb, qp, m, want)
+        return write_line(args, out, mode)
     w0 = time.perf_counter(); host_parse(200); one = (time.perf_counter() - w0) / 200
     with ThreadPoolExecutor(args.host_threads) as ex:
         list(ex.map(host_parse, [20] * args.host_threads))
@@ -99,6 +173,10 @@ def main():
         batch.close()
     for e in encs:
         e.close()
+    write_line(args, out, mode)
+
+
+def write_line(args, out, mode):
     line = json.dumps(out)
     print(line)
     if args.out:

@@ -23,9 +23,9 @@
 #define NEV 32                 /* launches the analysis kernel's timer remembers between two kernel_time calls ... */
 #define NRING 8
 #define NKEV 16                /* ... and a timer of the smaller kernels */
-enum { KT_ANALYSE, KT_EMBED_PREPARE, KT_EXTRACT_PREPARE, KT_EXTRACT_BITS, KT_PAYLOAD_CHECK, KT_PARSE_PSLICE, KT_PARSE_PSLICE_CAVLC, KT_WRITE_PSLICE, KT_WRITE_PSLICE_CAVLC, KT_N };
+enum { KT_ANALYSE, KT_EMBED_PREPARE, KT_EXTRACT_PREPARE, KT_EXTRACT_BITS, KT_PAYLOAD_CHECK, KT_PARSE_PSLICE, KT_PARSE_PSLICE_CAVLC, KT_WRITE_PSLICE, KT_WRITE_PSLICE_CAVLC, KT_NAL_TO_RBSP, KT_N };
 #define PCAMV_FEATURES (PCAMV_FEATURE_PAYLOAD | PCAMV_FEATURE_SLICE_PARSER | PCAMV_FEATURE_SLICE_PARSER_CAVLC | PCAMV_FEATURE_SLICE_WRITER | \
-                        PCAMV_FEATURE_SLICE_WRITER_CAVLC)
+                        PCAMV_FEATURE_SLICE_WRITER_CAVLC | PCAMV_FEATURE_NAL_DEVICE)
 #define SLICE_GUARD_MBS 4       /* records behind a context's receive-side records that nothing may write (pcamv_gpu_debug_slice_records) */
 #define NSTAGE 2                /* staging buffers of extract_slices: a call waits for the one before the last */
 /* the stages of a step (batch_launch's `what`): plane production, analysis (search + RCA + encode), embedding, second pass */
@@ -58,7 +58,8 @@ struct DescRing { int head, used[NRING]; hipEvent_t done[NRING]; };
  * launches; one pair of events stands for `weight` launches (the anti-diagonals of PCAMV_SCHED=diag share a pair) */
 struct KTimer { hipEvent_t e0[NEV], e1[NEV]; int cap, weight, made, n, head, launches; double ms; };
 /* NSTAGE staging buffers taken in turn, each a pinned host block and its device copy made by the calls themselves (stage_take): a buffer
- * is filled again only after the work that read it last (its event) is done, so a call waits for the one before the last */
+ * is filled again only after the work that read it last (its event) is done, so a call waits for the one before the last.  A ring
+ * that only kernels fill (nal_stage) has no host blocks */
 struct StageRing { uint8_t *h[NSTAGE], *d[NSTAGE]; size_t cap[NSTAGE]; hipEvent_t done[NSTAGE]; int used[NSTAGE], head; };
 
 struct pcamv_ctx;
@@ -86,6 +87,8 @@ struct pcamv_batch {
     int *d_sstat; uint8_t *d_sp_tab, *d_sp_scratch;
     int sp_lds_cols;            /* pictures up to this many macroblocks wide keep the parser's row buffer in LDS (SP_LDS_COLS; PCAMV_SLICE_LDS_COLS lowers it) */
     StageRing rx_stage;
+    /* ... handed NAL units (k_nal_to_rbsp): the RBSPs, their lengths and header bytes, which the parser of the same call reads */
+    StageRing nal_stage;
     /* sender to a stream (k_write_pslice, k_write_pslice_cavlc): the same of its own, and the staging of the callers' slice headers -- a
      * ring apart from the receiver's, since a write and a parse of one batch may be in flight on different streams */
     int *d_wstat; uint8_t *d_sw_tab, *d_sw_scratch;
@@ -252,7 +255,7 @@ extern "C" void pcamv_gpu_batch_destroy(pcamv_batch_t *b)
     if (b->h_X) hipHostFree(b->h_X);
     hipFree(b->d_F); hipFree(b->d_E); hipFree(b->d_flow); hipFree(b->d_X); hipFree(b->d_chk);
     hipFree(b->d_sstat); hipFree(b->d_sp_tab); hipFree(b->d_sp_scratch);
-    stage_destroy(b->rx_stage);
+    stage_destroy(b->rx_stage); stage_destroy(b->nal_stage);
     hipFree(b->d_wstat); hipFree(b->d_sw_tab); hipFree(b->d_sw_scratch);
     stage_destroy(b->tx_stage);
     ring_destroy(b->ring); ring_destroy(b->xring);
@@ -397,7 +400,7 @@ extern "C" const char *pcamv_gpu_batch_dominant_kernel(const pcamv_batch_t *b) {
 static const char *kt_name(const pcamv_batch *b, int k)      /* what pcamv_gpu_batch_kernel_time knows timer k by */
 {
     static const char *const small[KT_N] = {NULL, "k_embed_prepare", "k_extract_prepare", "k_extract_bits", "k_payload_check", "k_parse_pslice", "k_parse_pslice_cavlc", "k_write_pslice",
-                                            "k_write_pslice_cavlc"};
+                                            "k_write_pslice_cavlc", "k_nal_to_rbsp"};
     return k == KT_ANALYSE ? dominant_kernel(b) : small[k];
 }
 extern "C" int pcamv_gpu_batch_copy_results_async(pcamv_batch_t *b, void *dst_mb, size_t mb_stride, void *dst_flip, size_t flip_stride, void *stream)
@@ -588,8 +591,9 @@ static int ring_release(pcamv_batch *b, DescRing &r, int slot, hipStream_t st)
     r.used[slot] = 1;
     return 0;
 }
-/* the staging ring's next buffer with room for `total` bytes (regrown with a quarter to spare), once it is no longer in flight */
-static int stage_take(pcamv_batch *b, StageRing &R, size_t total, int *k_out)
+/* the staging ring's next buffer with room for `total` bytes (regrown with a quarter to spare), once it is no longer in flight;
+ * host == 0: the device side alone */
+static int stage_take(pcamv_batch *b, StageRing &R, size_t total, int *k_out, int host = 1)
 {
     const int k = R.head;
     R.head = (k + 1) % NSTAGE;
@@ -599,7 +603,7 @@ static int stage_take(pcamv_batch *b, StageRing &R, size_t total, int *k_out)
         if (R.h[k]) hipHostFree(R.h[k]);
         hipFree(R.d[k]); R.h[k] = NULL; R.d[k] = NULL; R.cap[k] = 0;
         const size_t cap = total + total / 4;
-        HIPCHK(b, hipHostMalloc((void **)&R.h[k], cap, hipHostMallocDefault));
+        if (host) HIPCHK(b, hipHostMalloc((void **)&R.h[k], cap, hipHostMallocDefault));
         HIPCHK(b, dalloc(&R.d[k], cap));
         R.cap[k] = cap;
     }
@@ -1325,18 +1329,49 @@ static int slices_checked(pcamv_batch *b, float emrate, int want_rx, int cavlc)
     TRY(entropy_setup(b, &b->d_sstat, &b->d_sp_tab, &b->d_sp_scratch, cavlc, SP_NCTX));
     return slice_contexts(b, want_rx, emrate);
 }
-static int extract_slices_host(pcamv_batch *b, const pcamv_slice_t *slices, int cavlc, float emrate, void *stream)
+/* Unescape first (k_nal_to_rbsp, one wavefront per unit, queued on `st`): the n NAL units J describes into the next buffer of nal_stage
+ * -- [rbsp_len n] int64, [nal_header n] int32, then J->bytes_size bytes in which unit i's RBSP begins at off[i] -- their return codes into
+ * d_status.  J then describes the RBSPs: bytes and len are the library's, off / start_bit / qp stay as they were, and a unit that failed
+ * has len -1, which the parsers refuse.  The buffer is taken like a staging buffer: not before the call before the last, whose parser
+ * read it, is done.  nal_header (optional): the caller's device array instead of the library's; preload (the probe): host bytes the
+ * RBSP buffer holds before the launch.  *stage_out: the buffer, to be released once the kernels that read it are queued */
+static int nals_unescape(pcamv_batch *b, int n, SliceJobs *J, int *d_status, int32_t *nal_header, const uint8_t *preload, hipStream_t st, int *stage_out)
+{
+    const size_t hdr = ((size_t)n * (8 + 4) + 15) & ~(size_t)15;
+    int k;
+    TRY(stage_take(b, b->nal_stage, hdr + (size_t)J->bytes_size, &k, 0));
+    uint8_t *d = b->nal_stage.d[k];
+    NalJobs N;
+    N.bytes = J->bytes; N.bytes_size = J->bytes_size; N.off = J->off; N.len = J->len;
+    N.rbsp_len = (long long *)d; N.nal_header = nal_header ? nal_header : (int *)(N.rbsp_len + n); N.rbsp = d + hdr; N.status = d_status;
+    if (preload) HIPCHK(b, hipMemcpyAsync(N.rbsp, preload, (size_t)J->bytes_size, hipMemcpyHostToDevice, st));
+    const int ev = kt_begin(b, KT_NAL_TO_RBSP, st);
+    hipLaunchKernelGGL(k_nal_to_rbsp, dim3(n), dim3(64), 0, st, N);
+    kt_end(b, KT_NAL_TO_RBSP, ev, st);
+    J->bytes = N.rbsp; J->len = N.rbsp_len;
+    *stage_out = k;
+    return 0;
+}
+/* what the extract_slices* and extract_nals* calls are: J's slices (nal != 0: NAL units, unescaped first) parsed and sent through the receiver */
+static int extract_run(pcamv_batch *b, SliceJobs J, int cavlc, int nal, int32_t *nal_header, float emrate, hipStream_t st)
+{
+    int kn = -1;
+    if (nal) TRY(nals_unescape(b, b->n, &J, b->d_sstat, nal_header, NULL, st, &kn));
+    const int rc = slices_run(b, J, cavlc, 1, emrate, st), rc2 = kn >= 0 ? stage_release(b, b->nal_stage, kn, st) : 0;       /* released on every path */
+    return rc ? rc : rc2;
+}
+static int extract_slices_host(pcamv_batch *b, const pcamv_slice_t *slices, int cavlc, int nal, float emrate, void *stream)
 {
     if (!slices) return PCAMV_EINVAL;
     TRY(slices_checked(b, emrate, 1, cavlc));
     hipStream_t st = stream ? (hipStream_t)stream : b->ctx[0]->stream;
     SliceJobs J; int k;
     TRY(slices_stage(b, slices, cavlc, st, &J, &k));
-    const int rc = slices_run(b, J, cavlc, 1, emrate, st), rc2 = stage_release(b, b->rx_stage, k, st);      /* released on every path */
+    const int rc = extract_run(b, J, cavlc, nal, NULL, emrate, st), rc2 = stage_release(b, b->rx_stage, k, st);      /* released on every path */
     return rc ? rc : rc2;
 }
 static int extract_slices_device(pcamv_batch *b, const void *bytes, size_t bytes_size, const int64_t *off, const int64_t *len, const int64_t *start_bit,
-                                 const int32_t *slice_qp, int cavlc, float emrate, void *stream)
+                                 const int32_t *slice_qp, int cavlc, int nal, int32_t *nal_header, float emrate, void *stream)
 {
     if (!bytes || !off || !len || !start_bit || (!cavlc && !slice_qp) || bytes_size > ((size_t)1 << 62)) return PCAMV_EINVAL;
     TRY(slices_checked(b, emrate, 1, cavlc));
@@ -1344,26 +1379,72 @@ static int extract_slices_device(pcamv_batch *b, const void *bytes, size_t bytes
     SliceJobs J;
     J.bytes = (const uint8_t *)bytes; J.bytes_size = (long long)bytes_size;
     J.off = (const long long *)off; J.len = (const long long *)len; J.start_bit = (const long long *)start_bit; J.qp = slice_qp;
-    return slices_run(b, J, cavlc, 1, emrate, stream ? (hipStream_t)stream : b->ctx[0]->stream);
+    return extract_run(b, J, cavlc, nal, nal_header, emrate, stream ? (hipStream_t)stream : b->ctx[0]->stream);
 }
 extern "C" int pcamv_gpu_batch_extract_slices(pcamv_batch_t *b, const pcamv_slice_t *slices, float emrate, void *stream)
 {
-    return extract_slices_host(b, slices, 0, emrate, stream);
+    return extract_slices_host(b, slices, 0, 0, emrate, stream);
 }
 extern "C" int pcamv_gpu_batch_extract_slices_cavlc(pcamv_batch_t *b, const pcamv_slice_t *slices, float emrate, void *stream)
 {
-    return extract_slices_host(b, slices, 1, emrate, stream);
+    return extract_slices_host(b, slices, 1, 0, emrate, stream);
 }
 extern "C" int pcamv_gpu_batch_extract_slices_device(pcamv_batch_t *b, const void *bytes, size_t bytes_size, const int64_t *off, const int64_t *len,
                                                      const int64_t *start_bit, const int32_t *slice_qp, float emrate, void *stream)
 {
     if (!slice_qp) return PCAMV_EINVAL;
-    return extract_slices_device(b, bytes, bytes_size, off, len, start_bit, slice_qp, 0, emrate, stream);
+    return extract_slices_device(b, bytes, bytes_size, off, len, start_bit, slice_qp, 0, 0, NULL, emrate, stream);
 }
 extern "C" int pcamv_gpu_batch_extract_slices_cavlc_device(pcamv_batch_t *b, const void *bytes, size_t bytes_size, const int64_t *off, const int64_t *len,
                                                            const int64_t *start_bit, float emrate, void *stream)
 {
-    return extract_slices_device(b, bytes, bytes_size, off, len, start_bit, NULL, 1, emrate, stream);
+    return extract_slices_device(b, bytes, bytes_size, off, len, start_bit, NULL, 1, 0, NULL, emrate, stream);
+}
+/* the same four on NAL units */
+extern "C" int pcamv_gpu_batch_extract_nals(pcamv_batch_t *b, const pcamv_slice_t *units, float emrate, void *stream)
+{
+    return extract_slices_host(b, units, 0, 1, emrate, stream);
+}
+extern "C" int pcamv_gpu_batch_extract_nals_cavlc(pcamv_batch_t *b, const pcamv_slice_t *units, float emrate, void *stream)
+{
+    return extract_slices_host(b, units, 1, 1, emrate, stream);
+}
+extern "C" int pcamv_gpu_batch_extract_nals_device(pcamv_batch_t *b, const void *bytes, size_t bytes_size, const int64_t *off, const int64_t *len,
+                                                   const int64_t *start_bit, const int32_t *slice_qp, int32_t *nal_header, float emrate, void *stream)
+{
+    if (!slice_qp) return PCAMV_EINVAL;
+    return extract_slices_device(b, bytes, bytes_size, off, len, start_bit, slice_qp, 0, 1, nal_header, emrate, stream);
+}
+extern "C" int pcamv_gpu_batch_extract_nals_cavlc_device(pcamv_batch_t *b, const void *bytes, size_t bytes_size, const int64_t *off, const int64_t *len,
+                                                         const int64_t *start_bit, int32_t *nal_header, float emrate, void *stream)
+{
+    return extract_slices_device(b, bytes, bytes_size, off, len, start_bit, NULL, 1, 1, nal_header, emrate, stream);
+}
+/* the parity probe of k_nal_to_rbsp: n units of one host buffer through one launch, everything copied back */
+extern "C" int pcamv_gpu_nal_to_rbsp_device(pcamv_ctx_t *c, const uint8_t *bytes, size_t bytes_size, const int64_t *off, const int64_t *len, int n,
+                                            uint8_t *out, int64_t *out_len, int32_t *status, int32_t *nal_header)
+{
+    if (!c || !bytes || !off || !len || !out || !out_len || !status || n < 0 || bytes_size > ((size_t)1 << 40)) return PCAMV_EINVAL;
+    if (!n) return 0;
+    pcamv_batch *b = c->self;
+    HIPCHK(c, hipSetDevice(c->device));
+    DevTmp<uint8_t> d_bytes; DevTmp<long long> d_at; DevTmp<int> d_status;
+    HIPCHK(c, d_bytes.alloc(bytes_size ? bytes_size : 1)); HIPCHK(c, d_at.alloc(2 * (size_t)n)); HIPCHK(c, d_status.alloc((size_t)n));
+    HIPCHK(c, hipMemcpy(d_bytes, bytes, bytes_size, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_at, off, sizeof(int64_t) * n, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_at + n, len, sizeof(int64_t) * n, hipMemcpyHostToDevice));
+    SliceJobs J;
+    J.bytes = d_bytes; J.bytes_size = (long long)bytes_size; J.off = d_at; J.len = d_at + n;
+    int k;
+    TRY(on_behalf(c, b, nals_unescape(b, n, &J, d_status, NULL, out, c->stream, &k)));
+    const int rc = launched(b), rc2 = stage_release(b, b->nal_stage, k, c->stream);                  /* released on every path */
+    TRY(on_behalf(c, b, rc ? rc : rc2));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out, J.bytes, bytes_size, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(out_len, J.len, sizeof(int64_t) * n, hipMemcpyDeviceToHost));
+    if (nal_header) HIPCHK(c, hipMemcpy(nal_header, J.len + n, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(status, d_status, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+    return 0;
 }
 extern "C" int pcamv_gpu_batch_slice_status(pcamv_batch_t *b, int32_t *status)
 {

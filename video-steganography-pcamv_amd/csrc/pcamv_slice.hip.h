@@ -16,6 +16,9 @@
  * no arithmetic decoder: the wave keeps the byte window, the VLC tables (one 16-bit entry per code), the macroblock cache and a row
  * buffer of 24 bytes per column -- 5044 bytes, so that LDS admits the 32 waves per CU the registers do.
  *
+ * k_nal_to_rbsp is what runs in front of either parser when the receiver is handed NAL units: one wavefront per unit, lane-parallel
+ * (pcamv_nal_unescape.h), the RBSP of unit i at the unit's own offset of a buffer of the library's.  The parsers do not know of it.
+ *
  * k_write_pslice (pcamv_slice_write.hip) is the other direction: a CABAC P slice of every context's last step written on the device, one
  * wavefront per slice (pcamv_slice_write.h, which also describes a launch: WriteJobs).
  */
@@ -24,6 +27,7 @@
 #include "pcamv_embed.hip.h"
 #include "pcamv_slice_parse.h"
 #include "pcamv_slice_parse_cavlc.h"
+#include "pcamv_nal_unescape.h"
 #include "pcamv_slice_write.h"
 
 /* the slices of one launch: slice i is bytes[off[i] .. off[i] + len[i]), its slice data starts behind bit start_bit[i], slice QP qp[i] */
@@ -81,6 +85,27 @@ static __global__ void __launch_bounds__(64) k_parse_pslice_cavlc(const ExtractD
     if (off >= 0 && len >= 0 && len <= J.bytes_size && off <= J.bytes_size - len && X.n_mb == J.mb_w * J.mb_h && (J.mb_w <= lds_cols || J.scratch))
         rc = pcamv_slice_parse_cavlc(S, J.bytes + off, len, J.start_bit[i], J.mb_w, J.mb_h, (pcamv_mb_t *)X.mbs);
     if (lane == 0) *X.slice_status = rc;
+}
+
+/* the NAL units of one launch: unit i is bytes[off[i] .. off[i] + len[i]); its RBSP goes to rbsp[off[i] ..) (a buffer of bytes_size bytes
+ * too: an RBSP is shorter than its unit, so units that do not overlap give RBSPs that do not), the RBSP's length to rbsp_len[i] (-1: the
+ * unit is invalid), its header byte to nal_header[i] (-1: it has none), its return code to status[i] */
+struct NalJobs {
+    const uint8_t *bytes; long long bytes_size;
+    const long long *off, *len;
+    uint8_t *rbsp; long long *rbsp_len; int *nal_header, *status;
+};
+static __global__ void __launch_bounds__(64) k_nal_to_rbsp(const NalJobs J)
+{
+    __shared__ uint32_t s_win[NU_WIN_DWORDS], s_out[NU_OUT_DWORDS];
+    const int i = blockIdx.x, lane = threadIdx.x;
+    const NuWork W = {s_win, s_out};
+    const long long off = J.off[i], len = J.len[i];
+    int rc = PCAMV_EINVAL;
+    if (off >= 0 && len >= 0 && len <= J.bytes_size && off <= J.bytes_size - len)
+        rc = pcamv_nal_unescape(W, J.bytes + off, len, J.rbsp + off, J.rbsp_len + i, J.nal_header + i);
+    else if (lane == 0) { J.rbsp_len[i] = -1; J.nal_header[i] = -1; }
+    if (lane == 0) J.status[i] = rc;
 }
 /* the writer's kernel is a unit of its own (pcamv_slice_write.hip): it inlines the analysis' prediction and transform primitives, and what
  * the compiler makes of the kernels of this unit depends on what else in the unit calls them */

@@ -287,6 +287,7 @@ FEATURE_SLICE_PARSER = 0x2      # CABAC P slices parsed on the device: Encoder.p
 FEATURE_SLICE_PARSER_CAVLC = 0x4    # CAVLC P slices too: Encoder.parse_pslice_cavlc_device, Batch.extract_slices_cavlc
 FEATURE_SLICE_WRITER = 0x8      # CABAC P slices written on the device: Encoder.write_pslice, Batch.write_step
 FEATURE_SLICE_WRITER_CAVLC = 0x10   # CAVLC P slices too: Encoder.write_pslice_cavlc, Batch.write_step_cavlc
+FEATURE_NAL_DEVICE = 0x20       # the receiver takes NAL units, unescaped on the device: Batch.extract_nals*, Encoder.nal_to_rbsp_device
 
 
 def features():
@@ -515,6 +516,32 @@ class Encoder:
         self._chk(fn(self.ctx, _p(data), n, hdr_bits, *qp, _p(mbs)), call[len("pcamv_gpu_"):])
         return mbs
 
+    def nal_to_rbsp_device(self, units):
+        """pcamv_gpu_nal_to_rbsp_device: NAL units (a list of bytes) unescaped on the device by one launch of k_nal_to_rbsp -- the
+        parity probe of Batch.extract_nals*; a list of (return code, RBSP bytes or None, header byte or -1), to be compared with
+        nal_to_rbsp"""
+        off = np.cumsum([0] + [len(u) for u in units[:-1]], dtype=np.int64) if units else np.zeros(0, np.int64)
+        length = np.array([len(u) for u in units], np.int64)
+        rc, n, hdr, out = self.nal_to_rbsp_device_packed(np.frombuffer(b"".join(bytes(u) for u in units), np.uint8), off, length)
+        return [(int(r), out[o:o + k].tobytes() if r == 0 else None, int(h)) for r, k, h, o in zip(rc, n, hdr, off)]
+
+    def nal_to_rbsp_device_packed(self, data, off, length, out=None):
+        """the same on units packed by the caller: unit i is data[off[i] : off[i] + length[i]] (uint8; int64).  Returns (return codes,
+        RBSP lengths or -1, header bytes or -1, out): unit i's RBSP is out[off[i] :] and every other byte of `out` (default: zeros)
+        is as it was handed in"""
+        data, off, length = np.ascontiguousarray(data, np.uint8), np.ascontiguousarray(off, np.int64), np.ascontiguousarray(length, np.int64)
+        out = np.zeros(len(data), np.uint8) if out is None else np.ascontiguousarray(out, np.uint8).copy()
+        if len(off) != len(length) or len(out) != len(data):
+            raise PcamvError("one offset per length, and as many bytes of output as of input")
+        n = len(off)
+        rc, out_len, hdr = np.zeros(n, np.int32), np.zeros(n, np.int64), np.zeros(n, np.int32)
+        pad = np.zeros(1, np.uint8)
+        fn = self.lib.pcamv_gpu_nal_to_rbsp_device
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4
+        self._chk(fn(self.ctx, _p(data if len(data) else pad), len(data), _p(off), _p(length), n, _p(out if len(out) else pad), _p(out_len), _p(rc), _p(hdr)),
+                  "nal_to_rbsp_device")
+        return rc, out_len, hdr, out
+
     def slice_bound(self, hdr_bits=0, as_nal=False):
         """pcamv_gpu_slice_bound: a capacity under which no slice of this picture size fails to be written"""
         self.lib.pcamv_gpu_slice_bound.restype = C.c_int64
@@ -722,6 +749,26 @@ class Batch:
         """extract_slices_device for --no-cabac contexts: the same tensors without the QPs, the same ordering rule"""
         self._extract_slices_device("pcamv_gpu_batch_extract_slices_cavlc_device", data, off, length, hdr_bits, emrate, stream)
 
+    def extract_nals(self, units, emrate, stream=0):
+        """extract_slices on NAL units: a list of (unit bytes, hdr_bits, qp), each unit with or without a start code, hdr_bits
+        counting bits of its RBSP (from the first byte behind the NAL header byte).  k_nal_to_rbsp undoes the emulation prevention on
+        the device in front of the parser; a unit that is not valid counts as a slice that does not parse (slice_status -1)"""
+        self._extract_slices("pcamv_gpu_batch_extract_nals", units, emrate, stream, lambda s: int(s[2]))
+
+    def extract_nals_cavlc(self, units, emrate, stream=0):
+        """extract_nals for --no-cabac contexts: a list of (unit bytes, hdr_bits)"""
+        self._extract_slices("pcamv_gpu_batch_extract_nals_cavlc", units, emrate, stream, lambda s: 0)
+
+    def extract_nals_device(self, data, off, length, hdr_bits, qp, emrate, stream=0, nal_header=None):
+        """extract_slices_device on NAL units, e.g. what write_step(as_nal=True) wrote: the same tensors and the same ordering rule;
+        `data` is only read (the RBSPs go to a buffer of the library's), and the units must not overlap one another.  nal_header
+        (optional): an int32 device tensor of one entry per context that receives each unit's header byte (-1: the unit has none)"""
+        self._extract_slices_device("pcamv_gpu_batch_extract_nals_device", data, off, length, hdr_bits, emrate, stream, qp, nal_header=(nal_header,))
+
+    def extract_nals_cavlc_device(self, data, off, length, hdr_bits, emrate, stream=0, nal_header=None):
+        """extract_nals_device for --no-cabac contexts: the same without the QPs"""
+        self._extract_slices_device("pcamv_gpu_batch_extract_nals_cavlc_device", data, off, length, hdr_bits, emrate, stream, nal_header=(nal_header,))
+
     def _extract_slices(self, call, slices, emrate, stream, qp):
         """what extract_slices and extract_slices_cavlc share: `call` names the library's entry point, qp(slice) gives a slice's QP"""
         if len(slices) != len(self.encs):
@@ -732,18 +779,20 @@ class Batch:
         fn.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
         self._slice_chk(fn(self.b, arr, emrate, C.c_void_p(stream or None)), call[len("pcamv_gpu_"):])
 
-    def _extract_slices_device(self, call, data, off, length, hdr_bits, emrate, stream, *qp):
-        """what extract_slices_device and extract_slices_cavlc_device share: `call` names the library's entry point, which takes
-        the QPs (CABAC) or none"""
+    def _extract_slices_device(self, call, data, off, length, hdr_bits, emrate, stream, *qp, nal_header=()):
+        """what the extract_slices*_device and extract_nals*_device calls share: `call` names the library's entry point, which takes
+        the QPs (CABAC) or none, and (the NAL calls) an optional array for the header bytes: nal_header = (tensor or None,)"""
         per_ctx = [(off, 8, "off: int64"), (length, 8, "length: int64"), (hdr_bits, 8, "hdr_bits: int64")] + [(t, 4, "qp: int32") for t in qp]
+        per_ctx += [(t, 4, "nal_header: int32") for t in nal_header if t is not None]
         for t, size, what in [(data, 1, "data: uint8")] + per_ctx:
             if not _is_device_tensor(t) or not t.is_cuda or t.element_size() != size or not t.is_contiguous():
                 raise PcamvError(f"{what}, contiguous, on the device")
         if any(t.numel() != len(self.encs) for t, _, _ in per_ctx):
             raise PcamvError(f"one entry per context ({len(self.encs)}) in {' / '.join(what.split(':')[0] for _, _, what in per_ctx)}")
         fn = getattr(self.lib, call)
-        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * len(per_ctx) + [C.c_float, C.c_void_p]
-        self._slice_chk(fn(self.b, data.data_ptr(), data.numel(), *[t.data_ptr() for t, _, _ in per_ctx], emrate, C.c_void_p(stream or None)), call[len("pcamv_gpu_"):])
+        ptrs = [t.data_ptr() for t, _, _ in per_ctx] + [None for t in nal_header if t is None]
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * len(ptrs) + [C.c_float, C.c_void_p]
+        self._slice_chk(fn(self.b, data.data_ptr(), data.numel(), *ptrs, emrate, C.c_void_p(stream or None)), call[len("pcamv_gpu_"):])
 
     def write_step(self, hdr, data, off, cap, length, as_nal=False, stream=0):
         """pcamv_gpu_batch_write_step: every context's last step written as a CABAC P slice (final motion) by one launch of
