@@ -31,6 +31,8 @@
  *   parse_pslice_*_device       the device, one wavefront per slice (k_parse_pslice, k_parse_pslice_cavlc), straight into the extractor
  *   pcamv_gpu_*_nals*,          the same fed NAL units: what a decoder's NAL layer undoes of x264_nal_encode (common/common.c:658-690), on
  *   nal_to_rbsp_device          the device, one wavefront per unit (k_nal_to_rbsp), in front of either parser
+ *   pcamv_gpu_*_stream*,        the same fed a byte stream per context: Annex B start codes found (k_stream_scan, k_stream_place), the P slices'
+ *   annexb_index, slice_header  headers read (k_slice_header: what x264_slice_header_write wrote, encoder.c:174-305), one slice unit per call
  *   pcamv_gpu_*write_*          the second pass' x264_macroblock_write_cabac + x264_cabac_encode_flush (encoder/cabac.c:781, common/cabac.c:908)
  *                               and x264_nal_encode (common/common.c:658): the P slice of a step written on the device (k_write_pslice);
  *                               the *_cavlc calls x264_macroblock_write_cavlc (encoder/cavlc.c:288) instead (k_write_pslice_cavlc)
@@ -57,6 +59,7 @@ extern "C" {
 #define PCAMV_ENOMEM  (-3)
 #define PCAMV_EHIP    (-4)
 #define PCAMV_EUNSUP  (-5)
+#define PCAMV_EEOF    (-6)        /* a context's byte stream has no further slice unit (the receiver on byte streams) */
 
 /* enum values are the reference's own (x264.h:106-111, common/macroblock.h mb_class_e / mb_partition_e) */
 enum { PCAMV_ME_DIA = 0, PCAMV_ME_HEX = 1, PCAMV_ME_UMH = 2, PCAMV_ME_ESA = 3, PCAMV_ME_TESA = 4 };
@@ -203,12 +206,46 @@ int pcamv_gpu_parse_pslice_cabac(const uint8_t *slice_data, size_t len, int mb_w
 int pcamv_gpu_parse_pslice_cavlc(const uint8_t *slice_data, size_t len, int mb_w, int mb_h, pcamv_mb_t *out_mb);
 /* The same on what a stream really holds.  pcamv_gpu_nal_to_rbsp undoes x264_nal_encode (common/common.c:658-690): optional Annex-B
  * start code, the NAL header byte (returned), emulation_prevention_three_bytes removed; rbsp must hold len bytes.  The _at forms
- * start at bit start_bit of the RBSP, i.e. right behind a slice header of any length (the caller parses or skips the header:
- * it depends on the SPS / PPS in use): CAVLC slice data begins at that bit, CABAC slice data after the cabac_alignment_one_bits
- * that fill up the byte. */
+ * start at bit start_bit of the RBSP, i.e. right behind a slice header of any length (pcamv_gpu_parse_slice_header below reads
+ * one, given what it needs of the SPS / PPS in use): CAVLC slice data begins at that bit, CABAC slice data after the
+ * cabac_alignment_one_bits that fill up the byte. */
 int pcamv_gpu_nal_to_rbsp(const uint8_t *nal, size_t len, uint8_t *rbsp, size_t *rbsp_len, int *nal_ref_idc, int *nal_unit_type);
 int pcamv_gpu_parse_pslice_cabac_at(const uint8_t *rbsp, size_t len, size_t start_bit, int mb_w, int mb_h, int slice_qp, pcamv_mb_t *out_mb);
 int pcamv_gpu_parse_pslice_cavlc_at(const uint8_t *rbsp, size_t len, size_t start_bit, int mb_w, int mb_h, pcamv_mb_t *out_mb);
+/* The layer above a unit, host code: an Annex B byte stream cut into its NAL units.  A start code prefix is any 00 00 01; unit i
+ * begins behind the i-th prefix and ends in front of the next one, or at len, without its trailing 00 bytes (trailing_zero_8bits, or
+ * the zero_byte of a long start code).  Bytes in front of the first prefix belong to no unit; a unit may be empty (len 0,
+ * nal_header -1).  off counts from bytes[0]; nal_header is the unit's first byte; kind comes from nal_unit_type and, for type 1, from
+ * the first payload byte alone (its first bit is first_mb_in_slice == 0, slice_type is the ue behind it; emulation prevention cannot
+ * touch that byte):
+ *   PCAMV_UNIT_PSLICE  type 1, first_mb_in_slice 0, slice_type 0 or 5
+ *   PCAMV_UNIT_UNSUP   type 1 with first_mb_in_slice != 0 (a second slice of a picture), slice_type B / SP / SI or none there is, or
+ *                      without a payload byte; types 2, 3, 4 (data partitions)
+ *   PCAMV_UNIT_OTHER   everything else: parameter sets, SEI, delimiters, IDR units, a type-1 I slice (it carries nothing)
+ * forbidden_zero_bit is not judged here (pcamv_gpu_nal_to_rbsp fails such a unit).  units[cap] receives the first cap units,
+ * *n_units counts all of them, *n_slices the stream's "slice units": those of kind PSLICE or UNSUP, in stream order. */
+enum { PCAMV_UNIT_OTHER = 0, PCAMV_UNIT_PSLICE = 1, PCAMV_UNIT_UNSUP = 2 };
+typedef struct pcamv_unit_t { int64_t off, len; int32_t nal_header, kind; } pcamv_unit_t;
+int pcamv_gpu_annexb_index(const uint8_t *bytes, size_t len, pcamv_unit_t *units, size_t cap, int64_t *n_units, int64_t *n_slices);
+/* What slice_header() (7.3.3) needs of the active SPS / PPS: the host's control plane, filled in by the caller.  Assumed beyond it:
+ * frame_mbs_only_flag 1, one slice group.  log2_* 4 .. 16, poc_type 0 .. 2, num_ref_idx_l0_default (the count, not minus 1) 1 .. 32,
+ * pic_init_qp 0 .. 51 (26 + pic_init_qp_minus26), pps_id 0 .. 255; anything else is PCAMV_EINVAL for every header. */
+typedef struct pcamv_stream_params_t {
+    int32_t log2_max_frame_num, poc_type, log2_max_poc_lsb, delta_pic_order_always_zero, pic_order_present, redundant_pic_cnt_present;
+    int32_t num_ref_idx_l0_default, weighted_pred, entropy_cabac, pic_init_qp, deblocking_filter_control_present, pps_id;
+} pcamv_stream_params_t;
+/* The header of a P slice as x264_slice_header_write writes it (encoder/encoder.c:174-305), host code: rbsp[0, len) is the unit
+ * behind its header byte, unescaped (pcamv_gpu_nal_to_rbsp).  *start_bit: the bit behind the header, the number the *_at calls take
+ * (cabac_alignment_one_bits stay the parser's); *slice_qp = pic_init_qp + slice_qp_delta; *frame_num.  All three are -1 on failure.
+ * In syntax order: nal_unit_type != 1, first_mb_in_slice != 0, slice_type not 0 or 5, pps_id != params->pps_id: PCAMV_EUNSUP;
+ * frame_num; the POC fields of poc_type 0 / 1 / 2; redundant_pic_cnt; num_ref_idx_active_override_flag and its ue -- more than one
+ * active reference, by it or by the default: EUNSUP; ref_pic_list_reordering walked to its 3 -- an idc above 3: PCAMV_EINVAL;
+ * weighted_pred set: EUNSUP; with nal_ref_idc != 0 adaptive_ref_pic_marking_mode_flag 1: EUNSUP; with entropy_cabac cabac_init_idc
+ * != 0: EUNSUP; slice_qp_delta -- a QP outside 0 .. 51: EINVAL; with deblocking control the idc (above 2: EINVAL) and its offsets.
+ * A ue with more than 31 leading zeros, a read at or past bit 8 * len, and a start_bit at or past the end are EINVAL, found before
+ * the element is judged.  Nothing outside rbsp[0, len) is read. */
+int pcamv_gpu_parse_slice_header(const uint8_t *rbsp, size_t len, int nal_header, const pcamv_stream_params_t *params, int64_t *start_bit,
+                                 int32_t *slice_qp, int32_t *frame_num);
 
 /* Device-resident variants used by bench.py and the multi-frame pipeline: planes are raw
  * device pointers (hipMalloc / torch storage), tightly packed like recon[] above. */
@@ -305,6 +342,7 @@ int pcamv_gpu_abi_version(void);
 #define PCAMV_FEATURE_SLICE_WRITER 0x8u /* CABAC P slices written on the device (the sender to a stream, at the end of this file) */
 #define PCAMV_FEATURE_SLICE_WRITER_CAVLC 0x10u  /* ... and CAVLC P slices (the *_cavlc calls there) */
 #define PCAMV_FEATURE_NAL_DEVICE 0x20u  /* the receiver takes NAL units: emulation prevention undone on the device (the *_nals* calls) */
+#define PCAMV_FEATURE_STREAM_DEVICE 0x40u       /* the receiver takes Annex B byte streams: units found and slice headers read on the device */
 unsigned pcamv_gpu_features(void);
 
 /* ---- Payload path: the caller's bits through the device-resident entry points, and back out on the device ----
@@ -429,6 +467,61 @@ int pcamv_gpu_batch_extract_nals_cavlc_device(pcamv_batch_t *batch, const void *
  * nal_header[i] (optional) its header byte or -1.  Entries that do not fit the buffer are PCAMV_EINVAL units. */
 int pcamv_gpu_nal_to_rbsp_device(pcamv_ctx_t *ctx, const uint8_t *bytes, size_t bytes_size, const int64_t *off, const int64_t *len, int n,
                                  uint8_t *out, int64_t *out_len, int32_t *status, int32_t *nal_header);
+
+/* ---- The receiver on byte streams: NAL units found and slice headers read on the device ----
+ *
+ * What a receiver really has: one Annex B byte stream per chain -- start codes, parameter sets, SEI, delimiters, an IDR picture, then
+ * P slices whose headers carry frame_num, the POC bits and slice_qp_delta.  index_streams cuts every context's stream into its units
+ * once; extract_stream_step then feeds one slice unit per context and call through unescape -> header -> parse -> extract with no host
+ * synchronisation and no per-frame array from the caller.  The semantics are those of pcamv_gpu_annexb_index and
+ * pcamv_gpu_parse_slice_header on every input.
+ *
+ * The scan is data-parallel over bytes: a wavefront takes one chunk of PCAMV_STREAM_CHUNK bytes of one stream (k_stream_scan: the
+ * prefixes and slice units a chunk starts, its last non-zero byte and last prefix), one wavefront per stream makes the exclusive prefix
+ * over its chunks (k_stream_prefix), and a second scan writes every unit at its place (k_stream_place): nothing depends on the order
+ * in which wavefronts finish.  Each context's table keeps its first max_units slice units (kinds PSLICE and UNSUP, in stream order);
+ * the count returned is the full count.
+ *
+ * index_streams_device: context i's stream is bytes[off[i] .. off[i] + len[i]) of a borrowed device buffer; off / len are device int64
+ * arrays of one entry per context, read by this call alone (the library keeps its own copy).  The streams of one call must not
+ * overlap: the library's working memory is sized for bytes_size bytes in all, and a stream that no longer fits it gets n_slices_out
+ * PCAMV_EINVAL (like one that does not fit the buffer) and an empty table; every step of such a context is PCAMV_EINVAL too, and
+ * stream_tell gives its total as PCAMV_EINVAL.  The call builds the tables, sets every context's unit
+ * cursor to 0, synchronises ONCE, returns each context's slice-unit count in n_slices_out[i] (host, optional) and sizes the RBSP slots
+ * of the steps by the longest slice unit of the tables -- not by bytes_size.  The buffer stays borrowed until the next index call;
+ * ordering on `stream` is the caller's, as for pcamv_gpu_batch_extract_slices_device.  Handing over complete units is the caller's
+ * job: a stream cut inside a unit ends in a unit that fails in its step.  index_streams: the same from host bytes, one copy.
+ *
+ * extract_stream_step, for every context: the slice unit at the cursor is taken and the cursor moves on by one, whatever then happens
+ * to the unit; a table at its end (or at max_units) gives PCAMV_EEOF and the cursor stays; a unit of kind UNSUP gives PCAMV_EUNSUP;
+ * else the unit is unescaped (k_stream_unit, the control code of k_nal_to_rbsp), its header is read with `params` (k_slice_header:
+ * start_bit and slice QP go where the parser reads them), it is parsed and extracted as by the *_nals* calls.  A context whose unit
+ * failed at any stage appends nothing.  pcamv_gpu_batch_slice_status reports the code of the first stage that failed.
+ * params->entropy_cabac chooses the parser; contexts of the other mode are refused with PCAMV_EUNSUP before anything is queued.
+ * Before any index call: PCAMV_EINVAL.  nal_header (optional): device int32 array, one per context, receives the unit's header byte
+ * (-1 where no unit was taken).  stream_tell synchronises: next[i] the cursor = slice units taken so far (a failed take at the end
+ * does not count), total[i] the slice units of the stream. */
+#define PCAMV_STREAM_CHUNK 2048
+int pcamv_gpu_stream_chunk(void);               /* PCAMV_STREAM_CHUNK of the library in use */
+int pcamv_gpu_batch_index_streams_device(pcamv_batch_t *batch, const void *bytes, size_t bytes_size, const int64_t *off, const int64_t *len,
+                                         int64_t max_units, int64_t *n_slices_out, void *stream);
+typedef struct pcamv_stream_t { const uint8_t *bytes; size_t len; } pcamv_stream_t;
+int pcamv_gpu_batch_index_streams(pcamv_batch_t *batch, const pcamv_stream_t *streams, int64_t max_units, int64_t *n_slices_out, void *stream);
+int pcamv_gpu_batch_extract_stream_step(pcamv_batch_t *batch, const pcamv_stream_params_t *params, float emrate, int32_t *nal_header, void *stream);
+int pcamv_gpu_batch_stream_tell(pcamv_batch_t *batch, int64_t *next, int64_t *total);
+/* The parity probes; they synchronise.  index_streams_probe: n streams of one host buffer through the three kernels, ALL units listed
+ * (what pcamv_gpu_annexb_index lists).  units_out holds n tables of cap_per_stream + PCAMV_UNIT_GUARD entries each: the library fills
+ * them with bytes 0xA5 on the device, the kernels write the first min(count, cap_per_stream) entries of each, and everything comes
+ * back as the device left it (the guard entries behind a table must still hold the pattern).  n_units / n_slices: the full counts,
+ * PCAMV_EINVAL for a stream that does not fit.  Fails with PCAMV_EHIP if the device copy of `bytes` was changed.
+ * slice_headers_device: n RBSPs of one host buffer through k_slice_header, one lane each: rc / start_bit / slice_qp / frame_num as
+ * pcamv_gpu_parse_slice_header gives them. */
+#define PCAMV_UNIT_GUARD 4
+int pcamv_gpu_index_streams_probe(pcamv_ctx_t *ctx, const uint8_t *bytes, size_t bytes_size, const int64_t *off, const int64_t *len, int n,
+                                  pcamv_unit_t *units_out, int64_t cap_per_stream, int64_t *n_units, int64_t *n_slices);
+int pcamv_gpu_slice_headers_device(pcamv_ctx_t *ctx, const uint8_t *bytes, size_t bytes_size, const int64_t *off, const int64_t *len,
+                                   const int32_t *nal_header, int n, const pcamv_stream_params_t *params, int32_t *rc, int64_t *start_bit,
+                                   int32_t *slice_qp, int32_t *frame_num);
 
 /* ---- Sender to a stream: CABAC P slices written on the device (kernel k_write_pslice, one wavefront per slice) ----
  *

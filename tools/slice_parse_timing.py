@@ -11,8 +11,16 @@ in one device tensor, 256 and 4096 units in flight -- k_nal_to_rbsp's time next 
 and the wall time of Batch.extract_nals_device against Batch.extract_slices_device on the same content.  Written to
 profiles/nal_unescape_timing.json, one line per entropy mode.
 
+With --stream the receiver on byte streams: every context with its own Annex B stream of 8 frames -- a delimiter and
+the same fixture's slice data behind a real slice header, per frame -- in one device tensor, 256 and 4096 streams.  The index kernels
+(k_stream_plan, k_stream_scan, k_stream_prefix, k_stream_place) and the wall time of Batch.index_streams_device against the library's
+host function pcamv_gpu_annexb_index on the same streams, one core and 16 threads; then k_stream_unit, k_slice_header and k_stream_status
+next to the parser of the same launches, and the wall time of Batch.extract_stream_step against Batch.extract_nals_device on the same
+unit.  Written to profiles/stream_index_timing.json, one line per entropy mode.
+
     python tools/slice_parse_timing.py [--cavlc] [--counts 1,64,1024,4096] [--reps 5] [--out profiles/slice_parse_timing.json]
     python tools/slice_parse_timing.py --nal [--cavlc] [--counts 256,4096] [--reps 5] [--out profiles/nal_unescape_timing.json]
+    python tools/slice_parse_timing.py --stream [--cavlc] [--counts 256,4096] [--reps 5] [--out profiles/stream_index_timing.json]
 """
 import argparse
 import ctypes as C
@@ -88,17 +96,143 @@ def nal_sweep(args, pcamv_amd, np, torch, out, rbsp, hb, qp, m, want):
         e.close()
 
 
+def write_header_bits(sp, qp, frame_num):
+    """a P slice header for the parameter sets `sp` as x264 writes one: first_mb 0, slice_type 5, pps_id, frame_num, POC lsb, no
+    override, no reordering, adaptive_ref_pic_marking_mode_flag 0 (nal_ref_idc 2), cabac_init_idc 0, slice_qp_delta, deblocking idc 0
+    and two zero offsets.  (The one header form this tool times; the full writer, over every element of the syntax, is
+    tests/stream_cases.py's write_header: a change to the syntax belongs in both)"""
+    bits = []
+
+    def ue(v):
+        n = (v + 1).bit_length()
+        bits.extend([0] * (n - 1) + [(v + 1) >> (n - 1 - k) & 1 for k in range(n)])
+
+    def se(v):
+        ue(2 * v - 1 if v > 0 else -2 * v)
+    ue(0); ue(5); ue(sp.pps_id)
+    bits.extend((frame_num >> (sp.log2_max_frame_num - 1 - k)) & 1 for k in range(sp.log2_max_frame_num))
+    bits.extend(((2 * frame_num) >> (sp.log2_max_poc_lsb - 1 - k)) & 1 for k in range(sp.log2_max_poc_lsb))
+    bits.extend([0, 0, 0])
+    if sp.entropy_cabac:
+        ue(0)
+    se(qp - sp.pic_init_qp)
+    ue(0); se(0); se(0)
+    return bits
+
+
+def stream_sweep(args, pcamv_amd, np, torch, out, slice_data, qp, m, want):
+    """--stream: out["device"] gets one entry per count; `want`: the host parser's records of the slice"""
+    dev = torch.device("cuda", 0)
+    frames = 8
+    sp = pcamv_amd.StreamParams(log2_max_frame_num=8, log2_max_poc_lsb=8, entropy_cabac=0 if args.cavlc else 1, deblocking_filter_control_present=1)
+    units = []
+    for k in range(frames):
+        bits = write_header_bits(sp, qp, k + 1)
+        if args.cavlc:
+            tail = np.unpackbits(np.frombuffer(slice_data, np.uint8))
+            tail = tail[:int(np.nonzero(tail)[0][-1]) + 1]
+            allbits = np.concatenate([np.array(bits, np.uint8), tail])
+        else:
+            allbits = np.concatenate([np.array(bits + [1] * (-len(bits) % 8), np.uint8), np.unpackbits(np.frombuffer(slice_data, np.uint8))])
+        rbsp = np.packbits(np.concatenate([allbits, np.zeros(-len(allbits) % 8, np.uint8)])).tobytes()
+        units.append((pcamv_amd.rbsp_to_nal(rbsp, 2, 1), len(bits)))
+    stream = b"".join(b"\x00\x00\x00\x01\x09\x30" + u for u, _ in units)
+    u_list, n_units, n_slices = pcamv_amd.annexb_index(stream)
+    if (n_units, n_slices) != (2 * frames, frames):
+        sys.exit("slice_parse_timing.py: the stream is not what it was assembled from")
+    out.update(kernel="k_stream_scan", parser=out["kernel"], stream_bytes=len(stream), frames=frames, chunk=pcamv_amd.stream_chunk())
+    lib = pcamv_amd.load_library()
+    lib.pcamv_gpu_annexb_index.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    sdata = np.frombuffer(stream, np.uint8)
+
+    def host_index(k):
+        table = np.zeros(64, pcamv_amd.UNIT_DTYPE)
+        a, b = C.c_int64(), C.c_int64()
+        for _ in range(k):
+            if lib.pcamv_gpu_annexb_index(sdata.ctypes.data, len(sdata), table.ctypes.data, 64, C.byref(a), C.byref(b)) or b.value != frames:
+                sys.exit("slice_parse_timing.py: the host index failed")
+
+    host_index(20)
+    w0 = time.perf_counter(); host_index(400); one = (time.perf_counter() - w0) / 400
+    with ThreadPoolExecutor(args.host_threads) as ex:
+        list(ex.map(host_index, [20] * args.host_threads))
+        w0 = time.perf_counter(); list(ex.map(host_index, [400] * args.host_threads)); many = (time.perf_counter() - w0) / (400 * args.host_threads)
+    out["host_index"] = dict(one_core_streams_per_s=1 / one, one_core_gb_per_s=len(stream) / one / 1e9, threads=args.host_threads,
+                             threads_streams_per_s=1 / many, threads_gb_per_s=len(stream) / many / 1e9)
+    p = pcamv_amd.param_default(out["width"], out["height"])
+    pcamv_amd.param_parse(p, "subme", 5)
+    p.b_cabac = 0 if args.cavlc else 1
+    index_kernels = ("k_stream_plan", "k_stream_scan", "k_stream_prefix", "k_stream_place")
+    step_kernels = ("k_stream_unit", "k_slice_header", "k_stream_status")
+    encs = []
+    for n in [int(v) for v in args.counts.split(",")]:
+        while len(encs) < n:
+            e = pcamv_amd.Encoder(p)
+            e.rx_reserve((4 * args.reps + 6) * m)
+            encs.append(e)
+        batch = pcamv_amd.Batch(encs[:n])
+        for e in encs[:n]:
+            e.rx_reset()
+        stride = (len(stream) + 3) | 1                      # every context its own copy, at odd offsets
+        data = torch.from_numpy(np.tile(np.frombuffer(stream + bytes(stride - len(stream)), np.uint8), n)).to(dev)
+        off = torch.arange(n, dtype=torch.int64, device=dev) * stride
+        length = torch.full((n,), len(stream), dtype=torch.int64, device=dev)
+        first = int(u_list[1]["off"]) - 4                   # the first slice unit with its start code, as extract_nals_device takes it
+        nal_args = [data, off + first, torch.full((n,), len(units[0][0]), dtype=torch.int64, device=dev), torch.full((n,), units[0][1], dtype=torch.int64, device=dev)]
+        nal_args += [] if args.cavlc else [torch.full((n,), qp, dtype=torch.int32, device=dev)]
+        nal_call = batch.extract_nals_cavlc_device if args.cavlc else batch.extract_nals_device
+        torch.cuda.synchronize()                            # the tensors are complete before the library's stream reads them
+        if batch.index_streams_device(data, off, length, max_units=16).tolist() != [frames] * n:
+            sys.exit("slice_parse_timing.py: the device's index differs from the host's")
+        batch.extract_stream_step(sp, 0.5); nal_call(*nal_args, 0.5)        # first launches: allocations, code load
+        torch.cuda.synchronize()
+        for k in index_kernels + step_kernels + (out["parser"],):
+            batch.kernel_time(k, reset=True)
+        wall = dict(index=0.0, stream=0.0, nal=0.0)
+        for _ in range(args.reps):
+            w0 = time.perf_counter()
+            batch.index_streams_device(data, off, length, max_units=16)     # (synchronises itself)
+            wall["index"] += (time.perf_counter() - w0) / args.reps
+            for name, call in (("stream", lambda: batch.extract_stream_step(sp, 0.5)), ("nal", lambda: nal_call(*nal_args, 0.5))):
+                w0 = time.perf_counter()
+                call()
+                torch.cuda.synchronize()
+                wall[name] += (time.perf_counter() - w0) / args.reps
+                if (batch.slice_status() != 0).any():
+                    sys.exit("slice_parse_timing.py: a unit failed on the device")
+        ms = {}
+        for k in index_kernels + step_kernels + (out["parser"],):
+            ms[k], launches = batch.kernel_time(k, reset=True)
+            if launches != (2 * args.reps if k == out["parser"] else args.reps):
+                sys.exit("slice_parse_timing.py: a launch was not timed")
+        got = encs[n - 1].slice_records()[0]
+        if any(not np.array_equal(got[f], want[f]) for f in got.dtype.names) or encs[n - 1].rx_tell()[0] != (2 * args.reps + 2) * m:
+            sys.exit("slice_parse_timing.py: the device's records differ from the host parser's")
+        index_ms, extra_ms = sum(ms[k] for k in index_kernels), sum(ms[k] for k in step_kernels)
+        out["device"].append(dict(streams=n, index_kernels_ms={k: ms[k] for k in index_kernels}, index_kernels_total_ms=index_ms,
+                                  index_gb_per_s=n * len(stream) / (index_ms * 1e-3) / 1e9, index_streams_device_wall_ms=wall["index"] * 1e3,
+                                  host_one_core_ms=n * one * 1e3, host_threads_ms=n * many * 1e3,
+                                  step_kernels_ms={k: ms[k] for k in step_kernels}, step_extra_kernels_ms=extra_ms, parser_kernel_ms=ms[out["parser"]],
+                                  step_extra_share_of_parser=extra_ms / ms[out["parser"]], extract_stream_step_wall_ms=wall["stream"] * 1e3,
+                                  extract_nals_device_wall_ms=wall["nal"] * 1e3, wall_ratio=wall["stream"] / wall["nal"]))
+        batch.close()
+    for e in encs:
+        e.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cavlc", action="store_true", help="CAVLC slices on --no-cabac contexts instead of CABAC ones")
     ap.add_argument("--nal", action="store_true", help="the receiver on NAL units: k_nal_to_rbsp next to the parser (profiles/nal_unescape_timing.json)")
-    ap.add_argument("--counts", default=None, help="default 1,64,1024,4096; with --nal 256,4096")
+    ap.add_argument("--stream", action="store_true", help="the receiver on byte streams: the index kernels, and a stream step next to a NAL step (profiles/stream_index_timing.json)")
+    ap.add_argument("--counts", default=None, help="default 1,64,1024,4096; with --nal or --stream 256,4096")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--host-threads", type=int, default=16)
     ap.add_argument("--out", default=None, help="default profiles/slice_parse_timing.json; with --nal profiles/nal_unescape_timing.json")
     args = ap.parse_args()
-    args.counts = args.counts or ("256,4096" if args.nal else "1,64,1024,4096")
-    args.out = args.out if args.out is not None else os.path.join(ROOT, "profiles", "nal_unescape_timing.json" if args.nal else "slice_parse_timing.json")
+    args.counts = args.counts or ("256,4096" if args.nal or args.stream else "1,64,1024,4096")
+    args.out = args.out if args.out is not None else os.path.join(ROOT, "profiles", "stream_index_timing.json" if args.stream else "nal_unescape_timing.json" if args.nal else
+                                                                  "slice_parse_timing.json")
     import numpy as np
     import torch
     import pcamv_amd
@@ -131,6 +265,9 @@ def main():
     want = host_parse(20)
     if args.nal:
         nal_sweep(args, pcamv_amd, np, torch, out, rbsp, hb, qp, m, want)
+        return write_line(args, out, mode)
+    if args.stream:
+        stream_sweep(args, pcamv_amd, np, torch, out, g["slice_data"].tobytes(), qp, m, want)
         return write_line(args, out, mode)
     w0 = time.perf_counter(); host_parse(200); one = (time.perf_counter() - w0) / 200
     with ThreadPoolExecutor(args.host_threads) as ex:

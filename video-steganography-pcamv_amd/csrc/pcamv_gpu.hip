@@ -23,9 +23,10 @@
 #define NEV 32                 /* launches the analysis kernel's timer remembers between two kernel_time calls ... */
 #define NRING 8
 #define NKEV 16                /* ... and a timer of the smaller kernels */
-enum { KT_ANALYSE, KT_EMBED_PREPARE, KT_EXTRACT_PREPARE, KT_EXTRACT_BITS, KT_PAYLOAD_CHECK, KT_PARSE_PSLICE, KT_PARSE_PSLICE_CAVLC, KT_WRITE_PSLICE, KT_WRITE_PSLICE_CAVLC, KT_NAL_TO_RBSP, KT_N };
+enum { KT_ANALYSE, KT_EMBED_PREPARE, KT_EXTRACT_PREPARE, KT_EXTRACT_BITS, KT_PAYLOAD_CHECK, KT_PARSE_PSLICE, KT_PARSE_PSLICE_CAVLC, KT_WRITE_PSLICE, KT_WRITE_PSLICE_CAVLC, KT_NAL_TO_RBSP,
+       KT_STREAM_PLAN, KT_STREAM_SCAN, KT_STREAM_PREFIX, KT_STREAM_PLACE, KT_STREAM_UNIT, KT_SLICE_HEADER, KT_STREAM_STATUS, KT_N };
 #define PCAMV_FEATURES (PCAMV_FEATURE_PAYLOAD | PCAMV_FEATURE_SLICE_PARSER | PCAMV_FEATURE_SLICE_PARSER_CAVLC | PCAMV_FEATURE_SLICE_WRITER | \
-                        PCAMV_FEATURE_SLICE_WRITER_CAVLC | PCAMV_FEATURE_NAL_DEVICE)
+                        PCAMV_FEATURE_SLICE_WRITER_CAVLC | PCAMV_FEATURE_NAL_DEVICE | PCAMV_FEATURE_STREAM_DEVICE)
 #define SLICE_GUARD_MBS 4       /* records behind a context's receive-side records that nothing may write (pcamv_gpu_debug_slice_records) */
 #define NSTAGE 2                /* staging buffers of extract_slices: a call waits for the one before the last */
 /* the stages of a step (batch_launch's `what`): plane production, analysis (search + RCA + encode), embedding, second pass */
@@ -62,6 +63,17 @@ struct KTimer { hipEvent_t e0[NEV], e1[NEV]; int cap, weight, made, n, head, lau
  * that only kernels fill (nal_stage) has no host blocks */
 struct StageRing { uint8_t *h[NSTAGE], *d[NSTAGE]; size_t cap[NSTAGE]; hipEvent_t done[NSTAGE]; int used[NSTAGE], head; };
 
+/* the index of n byte streams (k_stream_plan .. k_stream_place): the library's copy of their placement, the working memory of the
+ * scan, the tables; for a batch also what its steps need -- the borrowed buffer and the size of an RBSP slot */
+struct StreamIndex {
+    int n, ready;
+    long long max_units, stride, max_chunks;
+    long long *d_at;            /* [off n][len n][chunk_base n][n_units n][n_slices n][cursor n] */
+    int *d_bad; unsigned long long *d_longest; SiChunk *d_chunks; pcamv_unit_t *d_table; uint8_t *d_own;
+    size_t cap_n, cap_chunks, cap_table, cap_own;
+    const uint8_t *bytes; long long bytes_size, slot;
+};
+
 struct pcamv_ctx;
 /* A batch = the set of independent closed-GOP contexts whose frames advance together: every kernel
  * launch carries the same dependency step of all of them (descriptor arrays in device memory). */
@@ -89,6 +101,9 @@ struct pcamv_batch {
     StageRing rx_stage;
     /* ... handed NAL units (k_nal_to_rbsp): the RBSPs, their lengths and header bytes, which the parser of the same call reads */
     StageRing nal_stage;
+    /* ... handed byte streams: the index of every context's stream, and the job arrays and RBSP slots of a step, sized by index calls */
+    StreamIndex sx;
+    StageRing su_stage;
     /* sender to a stream (k_write_pslice, k_write_pslice_cavlc): the same of its own, and the staging of the callers' slice headers -- a
      * ring apart from the receiver's, since a write and a parse of one batch may be in flight on different streams */
     int *d_wstat; uint8_t *d_sw_tab, *d_sw_scratch;
@@ -237,6 +252,11 @@ static void stage_destroy(StageRing &R)
 {
     for (int k = 0; k < NSTAGE; k++) { if (R.h[k]) hipHostFree(R.h[k]); hipFree(R.d[k]); if (R.done[k]) hipEventDestroy(R.done[k]); }
 }
+static void stream_index_free(StreamIndex &S)
+{
+    hipFree(S.d_at); hipFree(S.d_bad); hipFree(S.d_longest); hipFree(S.d_chunks); hipFree(S.d_table); hipFree(S.d_own);
+    S = StreamIndex();
+}
 static void kt_destroy(KTimer &T) { for (int i = 0; i < NEV; i++) { if (T.e0[i]) hipEventDestroy(T.e0[i]); if (T.e1[i]) hipEventDestroy(T.e1[i]); } }
 
 extern "C" void pcamv_gpu_batch_destroy(pcamv_batch_t *b)
@@ -255,7 +275,8 @@ extern "C" void pcamv_gpu_batch_destroy(pcamv_batch_t *b)
     if (b->h_X) hipHostFree(b->h_X);
     hipFree(b->d_F); hipFree(b->d_E); hipFree(b->d_flow); hipFree(b->d_X); hipFree(b->d_chk);
     hipFree(b->d_sstat); hipFree(b->d_sp_tab); hipFree(b->d_sp_scratch);
-    stage_destroy(b->rx_stage); stage_destroy(b->nal_stage);
+    stage_destroy(b->rx_stage); stage_destroy(b->nal_stage); stage_destroy(b->su_stage);
+    stream_index_free(b->sx);
     hipFree(b->d_wstat); hipFree(b->d_sw_tab); hipFree(b->d_sw_scratch);
     stage_destroy(b->tx_stage);
     ring_destroy(b->ring); ring_destroy(b->xring);
@@ -400,7 +421,8 @@ extern "C" const char *pcamv_gpu_batch_dominant_kernel(const pcamv_batch_t *b) {
 static const char *kt_name(const pcamv_batch *b, int k)      /* what pcamv_gpu_batch_kernel_time knows timer k by */
 {
     static const char *const small[KT_N] = {NULL, "k_embed_prepare", "k_extract_prepare", "k_extract_bits", "k_payload_check", "k_parse_pslice", "k_parse_pslice_cavlc", "k_write_pslice",
-                                            "k_write_pslice_cavlc", "k_nal_to_rbsp"};
+                                            "k_write_pslice_cavlc", "k_nal_to_rbsp", "k_stream_plan", "k_stream_scan", "k_stream_prefix", "k_stream_place", "k_stream_unit",
+                                            "k_slice_header", "k_stream_status"};
     return k == KT_ANALYSE ? dominant_kernel(b) : small[k];
 }
 extern "C" int pcamv_gpu_batch_copy_results_async(pcamv_batch_t *b, void *dst_mb, size_t mb_stride, void *dst_flip, size_t flip_stride, void *stream)
@@ -624,6 +646,8 @@ static int stage_send(pcamv_batch *b, StageRing &R, int k, size_t total, hipStre
     HIPCHK(b, hipMemcpyAsync(R.d[k], R.h[k], total, hipMemcpyHostToDevice, st));
     return stage_release(b, R, k, st);
 }
+/* the job arrays in front of a stream step's RBSP slots: [off n][len n][start_bit n] int64, [qp n][first n][frame_num n][nal_header n] int32 */
+static size_t stream_step_hdr(int n) { return ((size_t)n * (3 * 8 + 4 * 4) + 15) & ~(size_t)15; }
 /* take the next descriptor slot, fill it from the contexts' current FrameDev/EmbedDev and queue its upload */
 static int batch_push_descs(pcamv_batch *b, hipStream_t st, const FrameDev **dF, const EmbedDev **dE, int *slot_out)
 {
@@ -1477,6 +1501,236 @@ extern "C" int pcamv_gpu_parse_pslice_cabac_device(pcamv_ctx_t *c, const uint8_t
 extern "C" int pcamv_gpu_parse_pslice_cavlc_device(pcamv_ctx_t *c, const uint8_t *rbsp, size_t len, size_t start_bit, pcamv_mb_t *out_mb)
 {
     return parse_pslice_device(c, rbsp, len, start_bit, 0, 1, out_mb);
+}
+/* ------------------------------------------------------------------ receiver on byte streams (k_stream_*, k_slice_header, pcamv_slice.hip.h) */
+extern "C" int pcamv_gpu_stream_chunk(void) { return SI_CHUNK; }
+/* the device memory of an index of n streams in bytes_size bytes, tables of max_units entries and `guard` more behind each: grown, never
+ * shrunk (a hipFree waits for the device: only a call that may synchronise gets here) */
+template <class T> static int grow(pcamv_batch *b, T **p, size_t *cap, size_t want)
+{
+    if (want <= *cap && *p) return 0;
+    hipFree(*p); *p = NULL; *cap = 0;
+    HIPCHK(b, dalloc(p, want ? want : 1));
+    *cap = want;
+    return 0;
+}
+static int stream_index_room(pcamv_batch *b, StreamIndex &S, int n, long long max_units, int guard, size_t bytes_size)
+{
+    S.ready = 0;
+    S.n = n; S.max_units = max_units; S.stride = max_units + guard;
+    S.max_chunks = (long long)(bytes_size / SI_CHUNK) + 2LL * n + 2;
+    if ((size_t)n > S.cap_n || !S.d_at) {
+        size_t c1 = 0, c2 = 0;
+        TRY(grow(b, &S.d_at, &c1, 6 * (size_t)n)); TRY(grow(b, &S.d_bad, &c2, (size_t)n));
+        S.cap_n = (size_t)n;
+    }
+    if (!S.d_longest) HIPCHK(b, dalloc(&S.d_longest, 1));
+    TRY(grow(b, &S.d_chunks, &S.cap_chunks, (size_t)S.max_chunks));
+    return grow(b, &S.d_table, &S.cap_table, (size_t)n * (size_t)S.stride);
+}
+/* the four kernels on `st`: streams (d_off[i], d_len[i]) of d_bytes; all != 0: every unit into the tables, else the slice units */
+static int stream_index_run(pcamv_batch *b, StreamIndex &S, const uint8_t *d_bytes, size_t bytes_size, const long long *d_off, const long long *d_len, int all, hipStream_t st)
+{
+    const size_t n = (size_t)S.n;
+    HIPCHK(b, hipMemcpyAsync(S.d_at, d_off, 8 * n, hipMemcpyDeviceToDevice, st));
+    HIPCHK(b, hipMemcpyAsync(S.d_at + n, d_len, 8 * n, hipMemcpyDeviceToDevice, st));
+    HIPCHK(b, hipMemsetAsync(S.d_longest, 0, 8, st));
+    StreamJobs J;
+    J.bytes = d_bytes; J.bytes_size = (long long)bytes_size; J.off = S.d_at; J.len = S.d_at + n;
+    J.chunk_base = S.d_at + 2 * n; J.bad = S.d_bad; J.chunks = S.d_chunks; J.max_chunks = S.max_chunks;
+    J.table = S.d_table; J.max_units = S.max_units; J.stride = S.stride; J.all = all;
+    J.n_units = S.d_at + 3 * n; J.n_slices = S.d_at + 4 * n; J.cursor = S.d_at + 5 * n; J.longest = S.d_longest; J.n = S.n;
+    const unsigned chunks = (unsigned)S.max_chunks;
+    int ev = kt_begin(b, KT_STREAM_PLAN, st);
+    hipLaunchKernelGGL(k_stream_plan, dim3(1), dim3(64), 0, st, J);
+    kt_end(b, KT_STREAM_PLAN, ev, st);
+    ev = kt_begin(b, KT_STREAM_SCAN, st);
+    hipLaunchKernelGGL(k_stream_scan, dim3(chunks), dim3(64), 0, st, J);
+    kt_end(b, KT_STREAM_SCAN, ev, st);
+    ev = kt_begin(b, KT_STREAM_PREFIX, st);
+    hipLaunchKernelGGL(k_stream_prefix, dim3(S.n), dim3(64), 0, st, J);
+    kt_end(b, KT_STREAM_PREFIX, ev, st);
+    ev = kt_begin(b, KT_STREAM_PLACE, st);
+    hipLaunchKernelGGL(k_stream_place, dim3(chunks), dim3(64), 0, st, J);
+    kt_end(b, KT_STREAM_PLACE, ev, st);
+    return launched(b);
+}
+static int stream_index_checked(pcamv_batch *b, const void *bytes, size_t bytes_size, long long max_units)
+{
+    if (!b || !bytes || max_units < 1 || max_units > (1LL << 24) || bytes_size > ((size_t)1 << 40)) return PCAMV_EINVAL;
+    HIPCHK(b, hipSetDevice(b->device));
+    return batch_live(b);
+}
+/* behind the kernels: the one synchronisation of an index call, the counts to the host, the RBSP slots of the steps to come */
+static int stream_index_finish(pcamv_batch *b, const uint8_t *d_bytes, size_t bytes_size, int64_t *n_slices_out)
+{
+    StreamIndex &S = b->sx;
+    HIPCHK(b, hipDeviceSynchronize());
+    unsigned long long longest = 0;
+    HIPCHK(b, hipMemcpy(&longest, S.d_longest, 8, hipMemcpyDeviceToHost));
+    static_assert(sizeof(long long) == sizeof(int64_t), "the counts are copied as they are");
+    if (n_slices_out) HIPCHK(b, hipMemcpy(n_slices_out, S.d_at + 4 * (size_t)S.n, 8 * (size_t)S.n, hipMemcpyDeviceToHost));
+    /* an RBSP is shorter than its unit by the header byte at least; slots at multiples of 4 */
+    S.slot = (long long)((longest + 3) & ~3ULL); if (S.slot < 4) S.slot = 4;
+    const size_t total = stream_step_hdr(S.n) + (size_t)S.n * (size_t)S.slot;
+    StageRing &R = b->su_stage;
+    for (int k = 0; k < NSTAGE; k++)
+        if (total > R.cap[k]) {
+            hipFree(R.d[k]); R.d[k] = NULL; R.cap[k] = 0;
+            HIPCHK(b, dalloc(&R.d[k], total));
+            R.cap[k] = total;
+        }
+    S.bytes = d_bytes; S.bytes_size = (long long)bytes_size; S.ready = 1;
+    return 0;
+}
+extern "C" int pcamv_gpu_batch_index_streams_device(pcamv_batch_t *b, const void *bytes, size_t bytes_size, const int64_t *off, const int64_t *len,
+                                                    int64_t max_units, int64_t *n_slices_out, void *stream)
+{
+    if (!off || !len) return PCAMV_EINVAL;
+    TRY(stream_index_checked(b, bytes, bytes_size, max_units));
+    hipStream_t st = stream ? (hipStream_t)stream : b->ctx[0]->stream;
+    TRY(stream_index_room(b, b->sx, b->n, max_units, 0, bytes_size));
+    TRY(stream_index_run(b, b->sx, (const uint8_t *)bytes, bytes_size, (const long long *)off, (const long long *)len, 0, st));
+    return stream_index_finish(b, (const uint8_t *)bytes, bytes_size, n_slices_out);
+}
+/* host streams into a buffer of the index's own -- [off n][len n] int64, then the bytes, every stream at a multiple of 4 -- with one copy */
+extern "C" int pcamv_gpu_batch_index_streams(pcamv_batch_t *b, const pcamv_stream_t *streams, int64_t max_units, int64_t *n_slices_out, void *stream)
+{
+    if (!streams) return PCAMV_EINVAL;
+    TRY(stream_index_checked(b, streams, 0, max_units));
+    const size_t n = (size_t)b->n, hdr = (16 * n + 15) & ~(size_t)15;
+    size_t total = hdr;
+    for (size_t i = 0; i < n; i++) {
+        if ((!streams[i].bytes && streams[i].len) || streams[i].len > ((size_t)1 << 36)) return fail(b, PCAMV_EINVAL, "stream %d: no bytes, or more than 2^36 of them", (int)i);
+        total += (streams[i].len + 3) & ~(size_t)3;
+    }
+    HostTmp<uint8_t> h(total);
+    if (!h) return fail(b, PCAMV_ENOMEM, "no memory to stage %zu bytes of streams", total);
+    long long *off = (long long *)h.p, *len = off + n;
+    size_t at = 0;
+    for (size_t i = 0; i < n; i++) {
+        off[i] = (long long)at; len[i] = (long long)streams[i].len;
+        if (streams[i].len) memcpy(h.p + hdr + at, streams[i].bytes, streams[i].len);
+        at += (streams[i].len + 3) & ~(size_t)3;
+    }
+    StreamIndex &S = b->sx;
+    S.ready = 0;
+    HIPCHK(b, hipDeviceSynchronize());              /* (steps on the buffer that is replaced may be in flight) */
+    TRY(grow(b, &S.d_own, &S.cap_own, total));
+    hipStream_t st = stream ? (hipStream_t)stream : b->ctx[0]->stream;
+    HIPCHK(b, hipMemcpy(S.d_own, h.p, total, hipMemcpyHostToDevice));       /* (complete on return: the host block does not outlive this call) */
+    TRY(stream_index_room(b, S, b->n, max_units, 0, total - hdr));
+    TRY(stream_index_run(b, S, S.d_own + hdr, total - hdr, (const long long *)S.d_own, (const long long *)S.d_own + n, 0, st));
+    return stream_index_finish(b, S.d_own + hdr, total - hdr, n_slices_out);
+}
+extern "C" int pcamv_gpu_batch_extract_stream_step(pcamv_batch_t *b, const pcamv_stream_params_t *params, float emrate, int32_t *nal_header, void *stream)
+{
+    if (!b || !params) return PCAMV_EINVAL;
+    const int cavlc = !params->entropy_cabac;
+    TRY(slices_checked(b, emrate, 1, cavlc));
+    StreamIndex &S = b->sx;
+    if (!S.ready) return fail(b, PCAMV_EINVAL, "no byte streams were handed to this batch yet (pcamv_gpu_batch_index_streams*)");
+    hipStream_t st = stream ? (hipStream_t)stream : b->ctx[0]->stream;
+    const size_t n = (size_t)b->n, hdr = stream_step_hdr(b->n);
+    int k;
+    TRY(stage_take(b, b->su_stage, hdr + n * (size_t)S.slot, &k, 0));     /* (never regrown here: the index call sized every buffer) */
+    uint8_t *d = b->su_stage.d[k];
+    StreamStep J;
+    J.bytes = S.bytes; J.bytes_size = S.bytes_size; J.soff = S.d_at; J.slen = S.d_at + n; J.bad = S.d_bad;
+    J.table = S.d_table; J.max_units = S.max_units; J.stride = S.stride; J.n_slices = S.d_at + 4 * n; J.cursor = S.d_at + 5 * n;
+    J.rbsp = d + hdr; J.slot = S.slot; J.rbsp_size = (long long)n * S.slot;
+    J.off = (long long *)d; J.len = J.off + n; J.start_bit = J.len + n;
+    J.qp = (int *)(J.start_bit + n); J.first = J.qp + n; J.frame_num = J.first + n; J.nal_header = nal_header ? nal_header : J.frame_num + n;
+    J.P = *params; J.n = b->n;
+    int ev = kt_begin(b, KT_STREAM_UNIT, st);
+    hipLaunchKernelGGL(k_stream_unit, dim3(b->n), dim3(64), 0, st, J);
+    kt_end(b, KT_STREAM_UNIT, ev, st);
+    ev = kt_begin(b, KT_SLICE_HEADER, st);
+    hipLaunchKernelGGL(k_slice_header, dim3((b->n + 63) / 64), dim3(64), 0, st, J);
+    kt_end(b, KT_SLICE_HEADER, ev, st);
+    SliceJobs SJ;
+    SJ.bytes = J.rbsp; SJ.bytes_size = J.rbsp_size; SJ.off = J.off; SJ.len = J.len; SJ.start_bit = J.start_bit; SJ.qp = cavlc ? NULL : J.qp;
+    const int rc = slices_run(b, SJ, cavlc, 1, emrate, st);
+    /* the parser refused what an earlier stage had failed (len -1) with its own code: the first stage's code takes its place */
+    ev = kt_begin(b, KT_STREAM_STATUS, st);
+    hipLaunchKernelGGL(k_stream_status, dim3((b->n + 63) / 64), dim3(64), 0, st, J.first, b->d_sstat, b->n);
+    kt_end(b, KT_STREAM_STATUS, ev, st);
+    const int rc1 = launched(b), rc2 = stage_release(b, b->su_stage, k, st);        /* released on every path */
+    return rc ? rc : rc1 ? rc1 : rc2;
+}
+extern "C" int pcamv_gpu_batch_stream_tell(pcamv_batch_t *b, int64_t *next, int64_t *total)
+{
+    if (!b) return PCAMV_EINVAL;
+    HIPCHK(b, hipSetDevice(b->device));
+    const StreamIndex &S = b->sx;
+    if (!S.ready) return fail(b, PCAMV_EINVAL, "no byte streams were handed to this batch yet (pcamv_gpu_batch_index_streams*)");
+    HIPCHK(b, hipDeviceSynchronize());
+    if (total) HIPCHK(b, hipMemcpy(total, S.d_at + 4 * (size_t)S.n, 8 * (size_t)S.n, hipMemcpyDeviceToHost));
+    if (next) HIPCHK(b, hipMemcpy(next, S.d_at + 5 * (size_t)S.n, 8 * (size_t)S.n, hipMemcpyDeviceToHost));
+    return 0;
+}
+/* the parity probe of the index kernels: n streams of one host buffer, all units listed, tables and guards back as the device left them */
+extern "C" int pcamv_gpu_index_streams_probe(pcamv_ctx_t *c, const uint8_t *bytes, size_t bytes_size, const int64_t *off, const int64_t *len, int n,
+                                             pcamv_unit_t *units_out, int64_t cap_per_stream, int64_t *n_units, int64_t *n_slices)
+{
+    if (!c || (!bytes && bytes_size) || !off || !len || !units_out || !n_units || !n_slices || n < 1 || cap_per_stream < 0 || cap_per_stream > (1LL << 24) ||
+        bytes_size > ((size_t)1 << 40)) return PCAMV_EINVAL;
+    pcamv_batch *b = c->self;
+    HIPCHK(c, hipSetDevice(c->device));
+    DevTmp<uint8_t> d_bytes; DevTmp<long long> d_at;
+    HIPCHK(c, d_bytes.alloc(bytes_size ? bytes_size : 1)); HIPCHK(c, d_at.alloc(2 * (size_t)n));
+    if (bytes_size) HIPCHK(c, hipMemcpy(d_bytes, bytes, bytes_size, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_at, off, sizeof(int64_t) * n, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_at + n, len, sizeof(int64_t) * n, hipMemcpyHostToDevice));
+    StreamIndex S = StreamIndex();
+    int rc = stream_index_room(b, S, n, cap_per_stream, PCAMV_UNIT_GUARD, bytes_size);
+    const size_t entries = (size_t)n * (size_t)(cap_per_stream + PCAMV_UNIT_GUARD);
+    hipError_t e = hipSuccess;
+    if (!rc) e = hipMemsetAsync(S.d_table, 0xA5, entries * sizeof(pcamv_unit_t), c->stream);
+    if (!rc && e == hipSuccess) rc = stream_index_run(b, S, d_bytes, bytes_size, d_at, d_at + n, 1, c->stream);
+    if (!rc && e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (!rc && e == hipSuccess) e = hipMemcpy(units_out, S.d_table, entries * sizeof(pcamv_unit_t), hipMemcpyDeviceToHost);
+    if (!rc && e == hipSuccess) e = hipMemcpy(n_units, S.d_at + 3 * (size_t)n, 8 * (size_t)n, hipMemcpyDeviceToHost);
+    if (!rc && e == hipSuccess) e = hipMemcpy(n_slices, S.d_at + 4 * (size_t)n, 8 * (size_t)n, hipMemcpyDeviceToHost);
+    HostTmp<uint8_t> back(bytes_size ? bytes_size : 1);
+    if (!rc && e == hipSuccess && back && bytes_size) {
+        e = hipMemcpy(back.p, d_bytes, bytes_size, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && memcmp(back.p, bytes, bytes_size)) rc = fail(b, PCAMV_EHIP, "the index kernels changed the streams' bytes");
+    }
+    stream_index_free(S);
+    if (e != hipSuccess) return fail(c, PCAMV_EHIP, "index_streams_probe: %s", hipGetErrorString(e));
+    return on_behalf(c, b, rc);
+}
+/* the parity probe of k_slice_header: n RBSPs of one host buffer, one lane each */
+extern "C" int pcamv_gpu_slice_headers_device(pcamv_ctx_t *c, const uint8_t *bytes, size_t bytes_size, const int64_t *off, const int64_t *len,
+                                              const int32_t *nal_header, int n, const pcamv_stream_params_t *params, int32_t *rc_out, int64_t *start_bit,
+                                              int32_t *slice_qp, int32_t *frame_num)
+{
+    if (!c || (!bytes && bytes_size) || !off || !len || !nal_header || !params || !rc_out || !start_bit || !slice_qp || !frame_num || n < 1 ||
+        bytes_size > ((size_t)1 << 40)) return PCAMV_EINVAL;
+    pcamv_batch *b = c->self;
+    HIPCHK(c, hipSetDevice(c->device));
+    DevTmp<uint8_t> d_bytes; DevTmp<long long> d_at; DevTmp<int> d_int;
+    HIPCHK(c, d_bytes.alloc(bytes_size ? bytes_size : 1)); HIPCHK(c, d_at.alloc(3 * (size_t)n)); HIPCHK(c, d_int.alloc(4 * (size_t)n));
+    if (bytes_size) HIPCHK(c, hipMemcpy(d_bytes, bytes, bytes_size, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_at, off, sizeof(int64_t) * n, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_at + n, len, sizeof(int64_t) * n, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemset(d_int, 0, sizeof(int) * 4 * (size_t)n));
+    HIPCHK(c, hipMemcpy(d_int + 2 * (size_t)n, nal_header, sizeof(int32_t) * n, hipMemcpyHostToDevice));
+    StreamStep J = StreamStep();
+    J.rbsp = d_bytes; J.rbsp_size = (long long)bytes_size; J.off = d_at; J.len = d_at + n; J.start_bit = d_at + 2 * (size_t)n;
+    J.qp = d_int; J.first = d_int + n; J.nal_header = d_int + 2 * (size_t)n; J.frame_num = d_int + 3 * (size_t)n;
+    J.P = *params; J.n = n;
+    const int ev = kt_begin(b, KT_SLICE_HEADER, c->stream);
+    hipLaunchKernelGGL(k_slice_header, dim3((n + 63) / 64), dim3(64), 0, c->stream, J);
+    kt_end(b, KT_SLICE_HEADER, ev, c->stream);
+    TRY(on_behalf(c, b, launched(b)));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(start_bit, J.start_bit, sizeof(int64_t) * n, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(slice_qp, J.qp, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(rc_out, J.first, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(frame_num, J.frame_num, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+    return 0;
 }
 extern "C" int pcamv_gpu_debug_slice_records(pcamv_ctx_t *c, pcamv_mb_t *out_mb, int *guard_intact)
 {

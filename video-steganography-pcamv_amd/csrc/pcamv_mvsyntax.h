@@ -577,4 +577,140 @@ static int parse_pslice_cavlc_bits(const uint8_t *data, size_t len, size_t start
     free(P.fmv); free(P.fnz); free(P.ftype);
     return rc;
 }
+/* The layer above a unit: an Annex B byte stream (H.264 annex B) cut into its NAL units, and the header of a P slice read
+ * (slice_header(), 7.3.3, as x264_slice_header_write writes it, encoder/encoder.c:174-305).  These two define what the device does
+ * (pcamv_stream_index.h) on every input, valid or not.
+ * A start code prefix is any 00 00 01; unit i begins behind the i-th prefix and ends in front of the next one or at len, without its
+ * trailing 00 bytes (trailing_zero_8bits, or the zero_byte of a long start code).  units[cap] receives the first cap units, *n_units
+ * counts them all, *n_slices those of kind PSLICE or UNSUP.  The kind is read from nal_unit_type and, for type 1, from the first
+ * payload byte, which emulation prevention cannot touch: first_mb_in_slice == 0 is its first bit, slice_type the ue behind it. */
+static inline int pcamv_unit_kind(int nal_header, int payload0)
+{
+    if (nal_header < 0) return PCAMV_UNIT_OTHER;
+    const int type = nal_header & 31;
+    if (type >= 2 && type <= 4) return PCAMV_UNIT_UNSUP;        /* data partitions */
+    if (type != 1) return PCAMV_UNIT_OTHER;
+    if (payload0 < 0 || !(payload0 & 0x80)) return PCAMV_UNIT_UNSUP;    /* no payload, or first_mb_in_slice != 0 */
+    int zeros = 0;
+    while (zeros < 7 && !((payload0 << (1 + zeros)) & 0x80)) zeros++;
+    if (zeros > 3) return PCAMV_UNIT_UNSUP;                     /* no slice_type there is */
+    const int slice_type = (1 << zeros) - 1 + ((payload0 >> (6 - 2 * zeros)) & ((1 << zeros) - 1));
+    if (slice_type == 0 || slice_type == 5) return PCAMV_UNIT_PSLICE;
+    return slice_type == 2 || slice_type == 7 ? PCAMV_UNIT_OTHER : PCAMV_UNIT_UNSUP;     /* an I slice carries nothing */
+}
+extern "C" int pcamv_gpu_annexb_index(const uint8_t *bytes, size_t len, pcamv_unit_t *units, size_t cap, int64_t *n_units, int64_t *n_slices)
+{
+    if ((!bytes && len) || (!units && cap) || !n_units || !n_slices) return PCAMV_EINVAL;
+    int64_t nu = 0, ns = 0;
+    size_t i = 0, begin = 0;
+    int open = 0;
+    for (;;) {
+        while (i + 2 < len && !(bytes[i] == 0 && bytes[i + 1] == 0 && bytes[i + 2] == 1)) i++;
+        const size_t stop = i + 2 < len ? i : len;              /* the next prefix, or the end */
+        if (open) {
+            size_t end = stop;
+            while (end > begin && bytes[end - 1] == 0) end--;
+            pcamv_unit_t u;
+            u.off = (int64_t)begin; u.len = (int64_t)(end - begin);
+            u.nal_header = end > begin ? bytes[begin] : -1;
+            u.kind = pcamv_unit_kind(u.nal_header, end > begin + 1 ? bytes[begin + 1] : -1);
+            if ((size_t)nu < cap) units[nu] = u;
+            nu++;
+            if (u.kind != PCAMV_UNIT_OTHER) ns++;
+        }
+        if (stop == len) break;
+        i += 3; begin = i; open = 1;
+    }
+    *n_units = nu; *n_slices = ns;
+    return 0;
+}
+namespace mvsyntax {
+struct HdrBits {                /* the RBSP bit by bit; past its end every read fails */
+    const uint8_t *d; uint64_t nbits, pos; int bad;
+    unsigned get1()
+    {
+        if (pos >= nbits) { bad = 1; return 0; }
+        const unsigned b = (d[pos >> 3] >> (7 - (pos & 7))) & 1u;
+        pos++;
+        return b;
+    }
+    uint32_t u(int n) { uint32_t v = 0; while (n--) v = v << 1 | get1(); return v; }
+    uint64_t ue()
+    {
+        int zeros = 0;
+        while (!bad && !get1()) if (++zeros > 31) bad = 1;
+        if (bad) return 0;
+        return ((uint64_t)1 << zeros) - 1 + u(zeros);
+    }
+    int64_t se() { const uint64_t k = ue(); return k & 1 ? (int64_t)((k + 1) >> 1) : -(int64_t)(k >> 1); }
+};
+}
+static inline int pcamv_stream_params_ok(const pcamv_stream_params_t *p)
+{
+    return p && p->log2_max_frame_num >= 4 && p->log2_max_frame_num <= 16 && p->poc_type >= 0 && p->poc_type <= 2 && p->log2_max_poc_lsb >= 4 &&
+           p->log2_max_poc_lsb <= 16 && p->num_ref_idx_l0_default >= 1 && p->num_ref_idx_l0_default <= 32 && p->pic_init_qp >= 0 && p->pic_init_qp <= 51 &&
+           p->pps_id >= 0 && p->pps_id <= 255;
+}
+/* the header of a P slice in rbsp[0, len) (the bytes behind the NAL header byte, unescaped): *start_bit the bit behind it, the number
+ * the *_at parsers take; -1 in all three outputs on failure */
+extern "C" int pcamv_gpu_parse_slice_header(const uint8_t *rbsp, size_t len, int nal_header, const pcamv_stream_params_t *params, int64_t *start_bit,
+                                            int32_t *slice_qp, int32_t *frame_num)
+{
+    if (start_bit) *start_bit = -1;
+    if (slice_qp) *slice_qp = -1;
+    if (frame_num) *frame_num = -1;
+    if ((!rbsp && len) || !start_bit || !slice_qp || !frame_num || !pcamv_stream_params_ok(params) || len > ((size_t)1 << 40)) return PCAMV_EINVAL;
+    if (nal_header < 0 || (nal_header & 31) != 1) return PCAMV_EUNSUP;          /* not a coded slice of a non-IDR picture */
+    const pcamv_stream_params_t &P = *params;
+    mvsyntax::HdrBits b = {rbsp, (uint64_t)len * 8, 0, 0};
+    /* a read past the end is PCAMV_EINVAL wherever it happens: looked at after every element, before the element is judged */
+#define HDR_EOF() do { if (b.bad) return PCAMV_EINVAL; } while (0)
+    if (b.ue() != 0) { HDR_EOF(); return PCAMV_EUNSUP; }                        /* first_mb_in_slice */
+    HDR_EOF();
+    const uint64_t slice_type = b.ue(); HDR_EOF();
+    if (slice_type != 0 && slice_type != 5) return PCAMV_EUNSUP;
+    const uint64_t pps_id = b.ue(); HDR_EOF();
+    if (pps_id != (uint64_t)P.pps_id) return PCAMV_EUNSUP;
+    const uint32_t fn = b.u(P.log2_max_frame_num); HDR_EOF();
+    if (P.poc_type == 0) {
+        b.u(P.log2_max_poc_lsb); HDR_EOF();
+        if (P.pic_order_present) { b.se(); HDR_EOF(); }                         /* delta_pic_order_cnt_bottom */
+    } else if (P.poc_type == 1 && !P.delta_pic_order_always_zero) {
+        b.se(); HDR_EOF();
+        if (P.pic_order_present) { b.se(); HDR_EOF(); }
+    }
+    if (P.redundant_pic_cnt_present) { b.ue(); HDR_EOF(); }
+    uint64_t n_ref = (uint64_t)P.num_ref_idx_l0_default;
+    const unsigned over = b.get1(); HDR_EOF();
+    if (over) { n_ref = b.ue() + 1; HDR_EOF(); }
+    if (n_ref > 1) return PCAMV_EUNSUP;
+    const unsigned reorder = b.get1(); HDR_EOF();
+    if (reorder)
+        for (;;) {
+            const uint64_t idc = b.ue(); HDR_EOF();
+            if (idc == 3) break;
+            if (idc > 3) return PCAMV_EINVAL;
+            b.ue(); HDR_EOF();                                                  /* abs_diff_pic_num_minus1 / long_term_pic_num */
+        }
+    if (P.weighted_pred) return PCAMV_EUNSUP;                                   /* pred_weight_table */
+    if ((nal_header >> 5) & 3) {
+        const unsigned adaptive = b.get1(); HDR_EOF();
+        if (adaptive) return PCAMV_EUNSUP;                                      /* memory management control operations */
+    }
+    if (P.entropy_cabac) {
+        const uint64_t idc = b.ue(); HDR_EOF();
+        if (idc != 0) return PCAMV_EUNSUP;                                      /* cabac_init_idc: the parser keeps one table */
+    }
+    const int64_t qp = P.pic_init_qp + b.se(); HDR_EOF();
+    if (qp < 0 || qp > 51) return PCAMV_EINVAL;
+    if (P.deblocking_filter_control_present) {
+        const uint64_t idc = b.ue(); HDR_EOF();
+        if (idc > 2) return PCAMV_EINVAL;
+        if (idc != 1) { b.se(); HDR_EOF(); b.se(); HDR_EOF(); }
+    }
+#undef HDR_EOF
+    if (b.pos >= b.nbits) return PCAMV_EINVAL;                                  /* no slice data behind the header */
+    *start_bit = (int64_t)b.pos; *slice_qp = (int32_t)qp; *frame_num = (int32_t)fn;
+    return 0;
+}
 #endif

@@ -19,6 +19,11 @@
  * k_nal_to_rbsp is what runs in front of either parser when the receiver is handed NAL units: one wavefront per unit, lane-parallel
  * (pcamv_nal_unescape.h), the RBSP of unit i at the unit's own offset of a buffer of the library's.  The parsers do not know of it.
  *
+ * k_stream_plan, k_stream_scan, k_stream_prefix, k_stream_place cut every context's Annex B byte stream into its NAL units, a wavefront
+ * per chunk of a stream (pcamv_stream_index.h); k_stream_unit then takes one slice unit per context and call from the table and
+ * unescapes it with k_nal_to_rbsp's control code, k_slice_header reads its slice header, one lane per context, into the job arrays the
+ * parsers read, and k_stream_status puts the code of the first stage that failed where the parser put its own.
+ *
  * k_write_pslice (pcamv_slice_write.hip) is the other direction: a CABAC P slice of every context's last step written on the device, one
  * wavefront per slice (pcamv_slice_write.h, which also describes a launch: WriteJobs).
  */
@@ -28,6 +33,7 @@
 #include "pcamv_slice_parse.h"
 #include "pcamv_slice_parse_cavlc.h"
 #include "pcamv_nal_unescape.h"
+#include "pcamv_stream_index.h"
 #include "pcamv_slice_write.h"
 
 /* the slices of one launch: slice i is bytes[off[i] .. off[i] + len[i]), its slice data starts behind bit start_bit[i], slice QP qp[i] */
@@ -106,6 +112,144 @@ static __global__ void __launch_bounds__(64) k_nal_to_rbsp(const NalJobs J)
         rc = pcamv_nal_unescape(W, J.bytes + off, len, J.rbsp + off, J.rbsp_len + i, J.nal_header + i);
     else if (lane == 0) { J.rbsp_len[i] = -1; J.nal_header[i] = -1; }
     if (lane == 0) J.status[i] = rc;
+}
+
+/* ---- byte streams.  The index of n streams: stream i is bytes[off[i] .. off[i] + len[i]); its chunks' summaries are chunks[chunk_base[i]
+ * .. chunk_base[i + 1]) (k_stream_plan: room for max_chunks in all; a stream that does not fit the buffer or the room has bad[i] set and
+ * no chunk); its table is table[i * stride .. + max_units) */
+struct StreamJobs {
+    const uint8_t *bytes; long long bytes_size;
+    const long long *off, *len;
+    long long *chunk_base; int *bad; SiChunk *chunks; long long max_chunks;
+    pcamv_unit_t *table; long long max_units, stride; int all;
+    long long *n_units, *n_slices, *cursor; unsigned long long *longest;
+    int n;
+};
+SP_HD SiTable stream_table(const StreamJobs &J, int i) { const SiTable T = {J.table + (long long)i * J.stride, J.max_units, J.all, J.longest}; return T; }
+/* one wavefront: the chunks of every stream, their exclusive prefix.  Lane l owns streams [l * seg, (l + 1) * seg) and walks them one
+ * after the other, so the kernel's time grows linearly with n (0.04 ms at 4096 streams): beyond some 10^5 streams of one call a scan over
+ * several waves would be the next step */
+static __global__ void __launch_bounds__(64) k_stream_plan(const StreamJobs J)
+{
+    __shared__ long long s_sum[64];
+    const int lane = threadIdx.x, seg = (J.n + 63) / 64, i0 = lane * seg, i1 = i0 + seg < J.n ? i0 + seg : J.n;
+    long long sum = 0;
+    for (int i = i0; i < i1; i++) {
+        const long long off = J.off[i], len = J.len[i];
+        if (off >= 0 && len >= 0 && len <= J.bytes_size && off <= J.bytes_size - len) sum += si_chunks(J.bytes + off, len);
+    }
+    s_sum[lane] = sum;
+    __syncthreads();
+    long long base = 0;
+    for (int j = 0; j < lane; j++) base += s_sum[j];
+    for (int i = i0; i < i1; i++) {
+        const long long off = J.off[i], len = J.len[i];
+        const int fits = off >= 0 && len >= 0 && len <= J.bytes_size && off <= J.bytes_size - len;
+        const long long c = fits ? si_chunks(J.bytes + off, len) : 0;
+        const int bad = !fits || base + c > J.max_chunks;
+        J.chunk_base[i] = base; J.bad[i] = bad;
+        if (!bad) base += c;
+        if (bad) { J.n_units[i] = PCAMV_EINVAL; J.n_slices[i] = PCAMV_EINVAL; }
+        J.cursor[i] = 0;
+    }
+    /* (chunk_base[i + 1] is read as stream i's end only where stream i is not bad: stream_chunks) */
+}
+/* the stream flat chunk f belongs to and its number there; -1: none (the grid is sized for the most chunks there can be).  Streams
+ * without chunks (empty, or bad) share their base with the stream behind them, and the walk down over them is one step per such
+ * stream: a long run of empty streams in front of a long one costs every wave of the long one that many steps */
+static __device__ int stream_of_chunk(const StreamJobs &J, long long f, long long *c)
+{
+    int lo = 0, hi = J.n - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (J.chunk_base[mid] <= f) lo = mid; else hi = mid - 1; }
+    /* streams without chunks share their base with the next one: the last stream at or below f that has chunk f is the one */
+    while (lo >= 0) {
+        if (!J.bad[lo]) {
+            const long long n = si_chunks(J.bytes + J.off[lo], J.len[lo]);
+            if (f >= J.chunk_base[lo] && f < J.chunk_base[lo] + n) { *c = f - J.chunk_base[lo]; return lo; }
+            if (n > 0) return -1;
+        }
+        lo--;
+    }
+    return -1;
+}
+static __global__ void __launch_bounds__(64) k_stream_scan(const StreamJobs J)
+{
+    __shared__ uint32_t s_win[SI_WIN_DWORDS];
+    long long c = 0;
+    const int i = stream_of_chunk(J, blockIdx.x, &c);
+    if (i < 0) return;
+    const SiWork W = {s_win, nullptr};
+    si_scan(W, J.bytes + J.off[i], J.len[i], c, 0, J.chunks + blockIdx.x, stream_table(J, i));
+}
+static __global__ void __launch_bounds__(64) k_stream_prefix(const StreamJobs J)
+{
+    __shared__ SiChunk s_sc[64];
+    const int i = blockIdx.x;
+    if (J.bad[i]) return;
+    const SiWork W = {nullptr, s_sc};
+    const uint8_t *src = J.bytes + J.off[i];
+    si_prefix(W, src, J.len[i], J.chunks + J.chunk_base[i], si_chunks(src, J.len[i]), stream_table(J, i), J.n_units + i, J.n_slices + i);
+}
+static __global__ void __launch_bounds__(64) k_stream_place(const StreamJobs J)
+{
+    __shared__ uint32_t s_win[SI_WIN_DWORDS];
+    long long c = 0;
+    const int i = stream_of_chunk(J, blockIdx.x, &c);
+    if (i < 0) return;
+    const SiWork W = {s_win, nullptr};
+    si_scan(W, J.bytes + J.off[i], J.len[i], c, 1, J.chunks + blockIdx.x, stream_table(J, i));
+}
+
+/* one step of the stream receiver: context i's next slice unit (table[i * max_units + cursor[i]], a unit of its stream bytes[soff[i] ..
+ * + slen[i])) unescaped to rbsp[i * slot ..), then what the parsers read: off / len / start_bit / qp.  first[i]: the code of the first
+ * stage that failed */
+struct StreamStep {
+    const uint8_t *bytes; long long bytes_size;
+    const long long *soff, *slen; const int *bad;
+    const pcamv_unit_t *table; long long max_units, stride; const long long *n_slices; long long *cursor;
+    uint8_t *rbsp; long long slot, rbsp_size;       /* (the header probe: any buffer of rbsp_size bytes, off / len the caller's) */
+    long long *off, *len, *start_bit; int *qp, *first, *nal_header, *frame_num;
+    pcamv_stream_params_t P;
+    int n;
+};
+static __global__ void __launch_bounds__(64) k_stream_unit(const StreamStep J)
+{
+    __shared__ uint32_t s_win[NU_WIN_DWORDS], s_out[NU_OUT_DWORDS];
+    const int i = blockIdx.x, lane = threadIdx.x;
+    const NuWork W = {s_win, s_out};
+    const long long cur = J.cursor[i], total = J.bad[i] ? 0 : J.n_slices[i], have = total < J.max_units ? total : J.max_units;
+    int rc = J.bad[i] ? PCAMV_EINVAL : PCAMV_EEOF, done = 0;      /* (a stream the index call refused has no end to be at) */
+    if (cur >= 0 && cur < have) {
+        const pcamv_unit_t u = J.table[(long long)i * J.stride + cur];
+        const long long soff = J.soff[i], slen = J.slen[i];
+        if (lane == 0) J.cursor[i] = cur + 1;
+        rc = u.kind == PCAMV_UNIT_PSLICE ? PCAMV_EINVAL : PCAMV_EUNSUP;
+        if (u.kind == PCAMV_UNIT_PSLICE && u.off >= 0 && u.len >= 0 && u.len <= slen && u.off <= slen - u.len && u.len <= J.slot + 1 && soff >= 0 &&
+            slen <= J.bytes_size && soff <= J.bytes_size - slen) {
+            rc = pcamv_nal_unescape(W, J.bytes + soff + u.off, u.len, J.rbsp + (long long)i * J.slot, J.len + i, J.nal_header + i);
+            done = 1;
+        }
+    }
+    if (lane == 0) {
+        if (!done) { J.len[i] = -1; J.nal_header[i] = -1; }
+        J.off[i] = (long long)i * J.slot; J.first[i] = rc; J.start_bit[i] = 0; J.qp[i] = 0; J.frame_num[i] = -1;
+    }
+}
+/* one lane per slice: the header of RBSP i (bytes[off[i] .. + len[i]) of the buffer the parser will read) */
+static __global__ void __launch_bounds__(64) k_slice_header(const StreamStep J)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= J.n || J.first[i]) return;
+    const long long off = J.off[i], len = J.len[i];
+    long long sb = -1; int qp = -1, fn = -1, rc = PCAMV_EINVAL;
+    if (off >= 0 && len >= 0 && len <= J.rbsp_size && off <= J.rbsp_size - len) rc = pcamv_slice_header_read(J.rbsp + off, len, J.nal_header[i], J.P, &sb, &qp, &fn);
+    J.start_bit[i] = sb; J.qp[i] = qp; J.frame_num[i] = fn;
+    if (rc) { J.first[i] = rc; J.len[i] = -1; }         /* as the unescaper marks a unit that failed: the parser refuses it */
+}
+static __global__ void __launch_bounds__(64) k_stream_status(const int *__restrict__ first, int *__restrict__ status, int n)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i < n && first[i]) status[i] = first[i];
 }
 /* the writer's kernel is a unit of its own (pcamv_slice_write.hip): it inlines the analysis' prediction and transform primitives, and what
  * the compiler makes of the kernels of this unit depends on what else in the unit calls them */

@@ -235,6 +235,11 @@ class _Slice(C.Structure):
     _fields_ = [("rbsp", C.c_void_p), ("len", C.c_size_t), ("start_bit", C.c_size_t), ("slice_qp", C.c_int32)]
 
 
+class _Stream(C.Structure):
+    """pcamv_stream_t"""
+    _fields_ = [("bytes", C.c_void_p), ("len", C.c_size_t)]
+
+
 class _SliceHdr(C.Structure):
     _fields_ = [("bits", C.c_void_p), ("n_bits", C.c_int32), ("i_frame", C.c_int32), ("nal_ref_idc", C.c_int32), ("nal_unit_type", C.c_int32)]
 
@@ -288,6 +293,54 @@ FEATURE_SLICE_PARSER_CAVLC = 0x4    # CAVLC P slices too: Encoder.parse_pslice_c
 FEATURE_SLICE_WRITER = 0x8      # CABAC P slices written on the device: Encoder.write_pslice, Batch.write_step
 FEATURE_SLICE_WRITER_CAVLC = 0x10   # CAVLC P slices too: Encoder.write_pslice_cavlc, Batch.write_step_cavlc
 FEATURE_NAL_DEVICE = 0x20       # the receiver takes NAL units, unescaped on the device: Batch.extract_nals*, Encoder.nal_to_rbsp_device
+FEATURE_STREAM_DEVICE = 0x40    # the receiver takes Annex B byte streams: Batch.index_streams*, Batch.extract_stream_step
+EINVAL, EUNSUP, EEOF = -1, -5, -6       # EEOF: a context's byte stream has no further slice unit
+UNIT_OTHER, UNIT_PSLICE, UNIT_UNSUP = 0, 1, 2
+UNIT_GUARD = 4                  # PCAMV_UNIT_GUARD: guard entries behind each table of Encoder.index_streams_device
+UNIT_DTYPE = np.dtype([("off", np.int64), ("len", np.int64), ("nal_header", np.int32), ("kind", np.int32)])        # pcamv_unit_t
+
+
+class StreamParams(C.Structure):
+    """pcamv_stream_params_t: what slice_header() needs of the active SPS / PPS (frame macroblocks only, one slice group)"""
+    _fields_ = [(n, C.c_int32) for n in ("log2_max_frame_num", "poc_type", "log2_max_poc_lsb", "delta_pic_order_always_zero", "pic_order_present",
+                                         "redundant_pic_cnt_present", "num_ref_idx_l0_default", "weighted_pred", "entropy_cabac", "pic_init_qp",
+                                         "deblocking_filter_control_present", "pps_id")]
+
+    def __init__(self, **kw):
+        d = dict(log2_max_frame_num=4, poc_type=0, log2_max_poc_lsb=4, num_ref_idx_l0_default=1, entropy_cabac=1, pic_init_qp=26)
+        d.update(kw)
+        super().__init__(**d)
+
+
+def stream_chunk():
+    """PCAMV_STREAM_CHUNK: the bytes of a stream one wavefront of the index kernels scans"""
+    return int(load_library().pcamv_gpu_stream_chunk())
+
+
+def annexb_index(data, cap=None):
+    """pcamv_gpu_annexb_index: (the first `cap` NAL units of an Annex B byte stream as a UNIT_DTYPE array, the number of units, the
+    number of slice units -- kinds PSLICE and UNSUP)"""
+    buf = np.frombuffer(bytes(data), np.uint8) if len(data) else np.zeros(1, np.uint8)
+    cap = len(data) // 3 + 1 if cap is None else int(cap)
+    units = np.zeros(max(cap, 1), UNIT_DTYPE)
+    nu, ns = C.c_int64(), C.c_int64()
+    fn = load_library().pcamv_gpu_annexb_index
+    fn.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    rc = fn(_p(buf), len(data), _p(units), cap, C.byref(nu), C.byref(ns))
+    if rc:
+        raise PcamvError(f"pcamv_gpu_annexb_index failed: {rc}")
+    return units[:min(cap, nu.value)], nu.value, ns.value
+
+
+def parse_slice_header(rbsp, nal_header, params):
+    """pcamv_gpu_parse_slice_header: (return code, start_bit, slice QP, frame_num) of the P slice header at the start of an RBSP; the
+    last three are -1 when the code is not 0"""
+    buf = np.frombuffer(bytes(rbsp), np.uint8) if len(rbsp) else np.zeros(1, np.uint8)
+    sb, qp, fn_ = C.c_int64(), C.c_int32(), C.c_int32()
+    fn = load_library().pcamv_gpu_parse_slice_header
+    fn.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    rc = fn(_p(buf), len(rbsp), int(nal_header), C.byref(params), C.byref(sb), C.byref(qp), C.byref(fn_))
+    return rc, sb.value, qp.value, fn_.value
 
 
 def features():
@@ -542,6 +595,36 @@ class Encoder:
                   "nal_to_rbsp_device")
         return rc, out_len, hdr, out
 
+    def index_streams_device(self, data, off, length, cap):
+        """pcamv_gpu_index_streams_probe: the byte streams data[off[i] : off[i] + length[i]] cut into their NAL units by the index
+        kernels, ALL units listed -- the parity probe of Batch.index_streams*, to be compared with annexb_index.  Returns (tables,
+        n_units, n_slices): tables a UNIT_DTYPE array of shape (n, cap + UNIT_GUARD) as the device left it (filled with bytes 0xA5
+        beforehand: entries past min(n_units, cap), the guard among them, still hold that).  Raises if the device changed `data`"""
+        data, off, length = np.ascontiguousarray(data, np.uint8), np.ascontiguousarray(off, np.int64), np.ascontiguousarray(length, np.int64)
+        n = len(off)
+        tables = np.zeros((n, int(cap) + UNIT_GUARD), UNIT_DTYPE)
+        nu, ns = np.zeros(n, np.int64), np.zeros(n, np.int64)
+        pad = np.zeros(1, np.uint8)
+        fn = self.lib.pcamv_gpu_index_streams_probe
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        self._chk(fn(self.ctx, _p(data if len(data) else pad), len(data), _p(off), _p(length), n, _p(tables), int(cap), _p(nu), _p(ns)), "index_streams_probe")
+        return tables, nu, ns
+
+    def slice_headers_device(self, data, off, length, nal_header, params):
+        """pcamv_gpu_slice_headers_device: the P slice headers of the RBSPs data[off[i] : off[i] + length[i]] read by k_slice_header,
+        one lane each -- the parity probe of Batch.extract_stream_step's header stage; (return codes, start bits, QPs, frame_nums) as
+        parse_slice_header gives them"""
+        data, off, length = np.ascontiguousarray(data, np.uint8), np.ascontiguousarray(off, np.int64), np.ascontiguousarray(length, np.int64)
+        nal_header = np.ascontiguousarray(nal_header, np.int32)
+        n = len(off)
+        rc, sb, qp, fnum = np.zeros(n, np.int32), np.zeros(n, np.int64), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        pad = np.zeros(1, np.uint8)
+        fn = self.lib.pcamv_gpu_slice_headers_device
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p] + [C.c_void_p] * 4
+        self._chk(fn(self.ctx, _p(data if len(data) else pad), len(data), _p(off), _p(length), _p(nal_header), n, C.byref(params), _p(rc), _p(sb), _p(qp), _p(fnum)),
+                  "slice_headers_device")
+        return rc, sb, qp, fnum
+
     def slice_bound(self, hdr_bits=0, as_nal=False):
         """pcamv_gpu_slice_bound: a capacity under which no slice of this picture size fails to be written"""
         self.lib.pcamv_gpu_slice_bound.restype = C.c_int64
@@ -768,6 +851,58 @@ class Batch:
     def extract_nals_cavlc_device(self, data, off, length, hdr_bits, emrate, stream=0, nal_header=None):
         """extract_nals_device for --no-cabac contexts: the same without the QPs"""
         self._extract_slices_device("pcamv_gpu_batch_extract_nals_cavlc_device", data, off, length, hdr_bits, emrate, stream, nal_header=(nal_header,))
+
+    def index_streams(self, streams, max_units=64, stream=0):
+        """pcamv_gpu_batch_index_streams: one Annex B byte stream per context (a list of bytes), staged with one copy and cut into NAL
+        units on the device; each context's table keeps its first max_units slice units and its cursor is set to 0.  Synchronises once;
+        returns every context's slice-unit count (int64; -1: the stream did not fit)"""
+        if len(streams) != len(self.encs):
+            raise PcamvError(f"{len(streams)} streams for a batch of {len(self.encs)} contexts")
+        keep = [np.frombuffer(bytes(s), np.uint8) if len(s) else np.zeros(1, np.uint8) for s in streams]
+        arr = (_Stream * len(streams))(*[_Stream(k.ctypes.data, len(s)) for k, s in zip(keep, streams)])
+        out = np.zeros(len(self.encs), np.int64)
+        fn = self.lib.pcamv_gpu_batch_index_streams
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        self._slice_chk(fn(self.b, arr, int(max_units), _p(out), C.c_void_p(stream or None)), "batch_index_streams")
+        return out
+
+    def index_streams_device(self, data, off, length, max_units=64, stream=0):
+        """the same on bytes already on the device: context i's stream is data[off[i] : off[i] + length[i]] of a contiguous uint8
+        device tensor, borrowed until the next index call; off / length int64 device tensors, read by this call alone.  The ordering
+        rule is extract_slices_device's; the streams must not overlap"""
+        for t, size, what in ((data, 1, "data: uint8"), (off, 8, "off: int64"), (length, 8, "length: int64")):
+            if not _is_device_tensor(t) or not t.is_cuda or t.element_size() != size or not t.is_contiguous():
+                raise PcamvError(f"{what}, contiguous, on the device")
+        if off.numel() != len(self.encs) or length.numel() != len(self.encs):
+            raise PcamvError(f"one entry per context ({len(self.encs)}) in off / length")
+        out = np.zeros(len(self.encs), np.int64)
+        fn = self.lib.pcamv_gpu_batch_index_streams_device
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        self._slice_chk(fn(self.b, data.data_ptr(), data.numel(), off.data_ptr(), length.data_ptr(), int(max_units), _p(out), C.c_void_p(stream or None)),
+                        "batch_index_streams_device")
+        return out
+
+    def extract_stream_step(self, params, emrate, stream=0, nal_header=None):
+        """pcamv_gpu_batch_extract_stream_step: every context's next slice unit of its indexed stream unescaped, its slice header read
+        with `params` (a StreamParams), parsed and sent through the receiver, without a host sync and without per-frame arrays.
+        slice_status() afterwards: 0, EEOF (no further slice unit), EUNSUP, EINVAL -- the code of the first stage that failed; such a
+        context appends nothing.  nal_header (optional): int32 device tensor receiving each unit's header byte"""
+        if nal_header is not None and (not _is_device_tensor(nal_header) or not nal_header.is_cuda or nal_header.element_size() != 4 or
+                                       not nal_header.is_contiguous() or nal_header.numel() != len(self.encs)):
+            raise PcamvError(f"nal_header: int32, contiguous, on the device, one entry per context ({len(self.encs)})")
+        fn = self.lib.pcamv_gpu_batch_extract_stream_step
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
+        self._slice_chk(fn(self.b, C.byref(params), emrate, nal_header.data_ptr() if nal_header is not None else None, C.c_void_p(stream or None)),
+                        "batch_extract_stream_step")
+
+    def stream_tell(self):
+        """(next, total) per context: slice units taken so far (a take at the end does not count), slice units of the stream;
+        synchronises"""
+        nxt, total = np.zeros(len(self.encs), np.int64), np.zeros(len(self.encs), np.int64)
+        fn = self.lib.pcamv_gpu_batch_stream_tell
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        self._slice_chk(fn(self.b, _p(nxt), _p(total)), "batch_stream_tell")
+        return nxt, total
 
     def _extract_slices(self, call, slices, emrate, stream, qp):
         """what extract_slices and extract_slices_cavlc share: `call` names the library's entry point, qp(slice) gives a slice's QP"""
