@@ -343,6 +343,7 @@ int pcamv_gpu_abi_version(void);
 #define PCAMV_FEATURE_SLICE_WRITER_CAVLC 0x10u  /* ... and CAVLC P slices (the *_cavlc calls there) */
 #define PCAMV_FEATURE_NAL_DEVICE 0x20u  /* the receiver takes NAL units: emulation prevention undone on the device (the *_nals* calls) */
 #define PCAMV_FEATURE_STREAM_DEVICE 0x40u       /* the receiver takes Annex B byte streams: units found and slice headers read on the device */
+#define PCAMV_FEATURE_STREAM_WRITER 0x80u       /* the sender writes Annex B byte streams: slice headers and unit placement on the device */
 unsigned pcamv_gpu_features(void);
 
 /* ---- Payload path: the caller's bits through the device-resident entry points, and back out on the device ----
@@ -535,8 +536,9 @@ int pcamv_gpu_slice_headers_device(pcamv_ctx_t *ctx, const uint8_t *bytes, size_
  * (or no header) the output is the bare slice data.  As a NAL unit: long start code, the header byte from nal_ref_idc and
  * nal_unit_type, the RBSP with emulation prevention as x264_nal_encode inserts it.  i_frame chooses the bit x264_cabac_encode_flush
  * takes from the frame counter (0x35a4e4f5 >> (i_frame & 31) & 1).
- * Contexts opened with b_cabac == 0 are refused with PCAMV_EUNSUP: there is no CAVLC writer yet.  SPS, PPS, slice headers, I frames
- * and several slices per picture stay the host's. */
+ * Contexts opened with b_cabac == 0 are refused with PCAMV_EUNSUP (they go through the *_cavlc calls below).  SPS, PPS, I frames and
+ * several slices per picture stay the host's; so does the slice header in these calls -- the stream calls at the end of this file make
+ * it on the device. */
 typedef struct pcamv_slice_hdr_t { const uint8_t *bits; int32_t n_bits; int32_t i_frame; int32_t nal_ref_idc; int32_t nal_unit_type; } pcamv_slice_hdr_t;
 /* The parity probe; synchronises.  mbs == NULL: the context's last frame -- final == 0 the first-pass records as they are, final != 0
  * the records with the embedding stage's flip map (what the second pass reconstructed).  mbs != NULL: host records that hold final
@@ -569,6 +571,81 @@ int pcamv_gpu_batch_write_step_cavlc(pcamv_batch_t *batch, const pcamv_slice_hdr
 /* Host code, the inverse of pcamv_gpu_nal_to_rbsp: long start code, header byte, the RBSP with emulation prevention bytes as
  * x264_nal_encode inserts them (common/common.c:658-695).  nal[cap] receives *nal_len bytes (at most 5 + len + len / 2 + 1). */
 int pcamv_gpu_rbsp_to_nal(const uint8_t *rbsp, size_t len, int nal_ref_idc, int nal_unit_type, uint8_t *nal, size_t cap, size_t *nal_len);
+
+/* ---- The sender writes byte streams: slice headers written and units placed on the device ----
+ *
+ * The write_step* calls above take the slice header and every unit's place from the caller, per frame.  These calls need neither: a
+ * batch is given one region of a device buffer per context once (stream_open), and every write_stream_step appends each context's last
+ * step to its stream as [access unit delimiter +] P slice unit, the header made on the device from the step's QP, a picture counter
+ * and the parameter sets.  Closed-loop contexts run step -> write_stream_step N times, then index_streams_device -> extract_stream_step
+ * N times on the same (bytes, off, len): nothing per frame passes through the host on either side, and the bytes in between are a
+ * well-formed Annex B stream.  Out of scope, the caller's as before: writing and parsing SPS / PPS, I frames (the stream's `head`, opaque
+ * here), several slices per picture.
+ *
+ * write_slice_header: host code, no GPU; the semantics of the device's header writer on every input (csrc/pcamv_stream_write.h), and the
+ * inverse of pcamv_gpu_parse_slice_header.  slice_header() (7.3.3) of a P slice for `params`, element by element as
+ * x264_slice_header_write emits it (encoder/encoder.c:174-305): first_mb_in_slice 0, slice_type, pps_id, frame_num, the POC elements of
+ * poc_type (0: poc_lsb [, delta_pic_order_cnt_bottom]; 1 and not delta_pic_order_always_zero: delta_pic_order_cnt[0] [, [1]]; the second
+ * of each with pic_order_present), redundant_pic_cnt if present, num_ref_idx_active_override_flag (0 if num_ref_idx_l0_default is 1, else
+ * 1 and num_ref_idx_l0_active_minus1 = 0: the stream says one active reference), ref_pic_list_reordering_flag_l0 0,
+ * adaptive_ref_pic_marking_mode_flag 0 if nal_ref_idc != 0, cabac_init_idc 0 with CABAC, slice_qp_delta = slice_qp - pic_init_qp, and
+ * with deblocking control disable_deblocking_filter_idc and, unless it is 1, the two offsets.  bits[cap] receives (*n_bits + 7) / 8
+ * bytes, most significant bit first, the last byte zero-filled: what pcamv_slice_hdr_t takes.  At most PCAMV_SLICE_HDR_MAX_BITS bits.
+ * Refused before anything is written, every member judged whether `params` has its element written or not -- PCAMV_EINVAL: params
+ * outside the ranges stated at pcamv_stream_params_t, frame_num or poc_lsb not below 2^log2_max_*, slice_qp outside 0 .. 51, slice_type
+ * not 0 or 5, an idc outside 0 .. 2, an offset outside -6 .. 6, nal_ref_idc outside 0 .. 3, redundant_pic_cnt outside 0 .. 127, a POC
+ * delta with |v| > 2^30 (the longest Exp-Golomb code the readers take); then PCAMV_EUNSUP: weighted_pred.  PCAMV_ENOMEM: cap too small. */
+#define PCAMV_SLICE_HDR_MAX_BITS 215    /* derived in csrc/pcamv_stream_write.h */
+#define PCAMV_SLICE_HDR_BYTES 28        /* a header's slot in the probe's output: the longest header, whole dwords */
+typedef struct pcamv_slice_fields_t {
+    int32_t nal_ref_idc, slice_type, frame_num, poc_lsb;
+    int32_t delta_pic_order_cnt_bottom, delta_pic_order_cnt[2];
+    int32_t redundant_pic_cnt, slice_qp;
+    int32_t disable_deblocking_filter_idc;
+    int32_t slice_alpha_c0_offset_div2, slice_beta_offset_div2;
+} pcamv_slice_fields_t;
+int pcamv_gpu_write_slice_header(const pcamv_stream_params_t *params, const pcamv_slice_fields_t *fields, uint8_t *bits, size_t cap, int32_t *n_bits);
+/* What every picture of a batch's streams shares.  nal_ref_idc 1 .. 3 (0 is refused: in this path a chain's P frame is the next one's
+ * reference); slice_type 0 or 5; first_pic >= 0; disable_deblocking_filter_idc 0 .. 2, or -1 for the reference's rule per picture
+ * (encoder.c:159-169: 0 if 15 < qp + 2 * min(alpha, beta) of the two offsets below, else 1); aud 0 or 1.
+ * Picture k of a stream (k = 0: the first write_stream_step after stream_open) has frame_num = (first_pic + k) mod 2^log2_max_frame_num,
+ * poc_lsb = 2 (first_pic + k) mod 2^log2_max_poc_lsb, all POC deltas and redundant_pic_cnt 0 (encoder.c:1153-1158, 2282, 2306 for a
+ * stream without B frames) and, for the CABAC writer's flush, i_frame = first_i_frame + k. */
+typedef struct pcamv_stream_write_t {
+    int32_t nal_ref_idc, slice_type, first_pic, first_i_frame;
+    int32_t disable_deblocking_filter_idc;
+    int32_t slice_alpha_c0_offset_div2, slice_beta_offset_div2, aud;
+} pcamv_stream_write_t;
+/* stream_open: context i's stream is bytes[off[i] .. off[i] + cap[i]) of a borrowed device buffer of bytes_size bytes.  off / cap are
+ * device int64 arrays of one entry per context, read by this call alone (the library keeps its own copy); len is a borrowed device int64
+ * array that the library keeps current until the next open: len[i] = bytes of context i's stream so far, so that (bytes, off, len) is
+ * at any time what pcamv_gpu_batch_index_streams_device takes.  head (optional: NULL / 0; host bytes, opaque, at most 2^24) -- the
+ * caller's parameter sets and IDR picture -- is copied to the start of every stream (kernel k_stream_open, one lane per context, queued
+ * on `stream`).  The call waits once for `stream`, for its copies of off, cap and head; the kernel is not waited for.  A context whose region does not lie inside the buffer, or does not hold head, gets len 0
+ * and PCAMV_EINVAL in every step, and nothing is ever written for it.  The regions must not overlap.  params / wr out of range:
+ * PCAMV_EINVAL, weighted_pred: PCAMV_EUNSUP, nothing is opened.
+ *
+ * write_stream_step follows write_step's ordering rule (after the batch_step it writes, before the next) and queues three launches on
+ * `stream`, without host synchronisation: k_stream_slot, one lane per context (the picture's header into a header table of the
+ * library's, the delimiter 00 00 00 01 09 30 at the stream's end if wr->aud, the place the writer gets; the QP is the step's, read from
+ * the frame descriptor the writer reads it from), then k_write_pslice / k_write_pslice_cavlc unchanged with as_nal = 1 and that table,
+ * then k_stream_commit, one lane per context.  params->entropy_cabac chooses the writer; contexts of the other mode are refused with
+ * PCAMV_EUNSUP before anything is queued.  Before any open: PCAMV_EINVAL.
+ * The picture counter moves on in every step for every context, whether the unit fits or not: a receiver sees the gap in frame_num.  The
+ * delimiter and the unit succeed or fail together.  A picture that does not fit leaves the stream and len[i] where they were and sets
+ * the context's status to PCAMV_ENOMEM (pcamv_gpu_batch_write_status serves: 0, PCAMV_ENOMEM, PCAMV_EINVAL); bytes between the stream's
+ * end and the end of its region are then unspecified.  Nothing outside [off[i], off[i] + cap[i]) is ever written.
+ * stream_written synchronises; each output is optional, one int64 per context: the stream's bytes (= len[i]), the steps since the open,
+ * the slice units among them that are in the stream. */
+int pcamv_gpu_batch_stream_open(pcamv_batch_t *batch, void *bytes, size_t bytes_size, const int64_t *off, const int64_t *cap, int64_t *len,
+                                const pcamv_stream_params_t *params, const pcamv_stream_write_t *wr, const uint8_t *head, size_t head_len, void *stream);
+int pcamv_gpu_batch_write_stream_step(pcamv_batch_t *batch, void *stream);
+int pcamv_gpu_batch_stream_written(pcamv_batch_t *batch, int64_t *bytes, int64_t *pictures, int64_t *units);
+/* The parity probe of the device's header writer; synchronises.  n cases, one parameter set and one pcamv_slice_fields_t per case, one
+ * lane each (k_slice_headers_write): rc[i] and n_bits[i] as pcamv_gpu_write_slice_header gives them, the bits of case i in
+ * bits[i * PCAMV_SLICE_HDR_BYTES ..), bytes of a slot behind a header's last byte 0. */
+int pcamv_gpu_slice_headers_write_device(pcamv_ctx_t *ctx, const pcamv_stream_params_t *params, const pcamv_slice_fields_t *fields, int n,
+                                         int32_t *rc, int32_t *n_bits, uint8_t *bits);
 
 #ifdef __cplusplus
 }

@@ -21,6 +21,14 @@ unit.  Written to profiles/stream_index_timing.json, one line per entropy mode.
     python tools/slice_parse_timing.py [--cavlc] [--counts 1,64,1024,4096] [--reps 5] [--out profiles/slice_parse_timing.json]
     python tools/slice_parse_timing.py --nal [--cavlc] [--counts 256,4096] [--reps 5] [--out profiles/nal_unescape_timing.json]
     python tools/slice_parse_timing.py --stream [--cavlc] [--counts 256,4096] [--reps 5] [--out profiles/stream_index_timing.json]
+
+With --write-stream the sender's byte streams: 256 and 4096 closed-loop CIF chains (--me hex --subme 6, QP 26) that step
+and then write the same frame twice in turn -- Batch.write_step*(as_nal=True) with one host-made header, and Batch.write_stream_step,
+which makes that header on the device and places the unit itself -- each call between two synchronisations on the host clock, with the
+writer's kernel time of each form and the times of k_stream_slot and k_stream_commit (hipEvents around the launches).  The two units
+must be the same bytes.  Written to profiles/stream_write_timing.json, one line per entropy mode.
+
+    python tools/slice_parse_timing.py --write-stream [--cavlc] [--counts 256,4096] [--reps 5] [--out profiles/stream_write_timing.json]
 """
 import argparse
 import ctypes as C
@@ -220,19 +228,111 @@ def stream_sweep(args, pcamv_amd, np, torch, out, slice_data, qp, m, want):
         e.close()
 
 
+def write_stream_sweep(args, pcamv_amd, np, torch, mode):
+    """--write-stream: one entry per count of chains.  Every round steps the chains, then writes the same frame twice in turn, each call
+    between two synchronisations: Batch.write_step*(as_nal=True) with one host-made header, and Batch.write_stream_step on streams opened
+    for that round -- the same header made on the device, so the two units must be the same bytes.  The writer's kernel is read after
+    each call, so that each form has its own"""
+    from pcamv_amd.synth import make_clip
+    dev = torch.device("cuda", 0)
+    W, H, qp, classes, per_mb = 352, 288, 26, 16, 768       # (the chains and the capacity per macroblock of tools/slice_write_timing.py)
+    cavlc = mode == "cavlc"
+    writer = "k_write_pslice_cavlc" if cavlc else "k_write_pslice"
+    sp = pcamv_amd.StreamParams(log2_max_frame_num=8, log2_max_poc_lsb=8, entropy_cabac=0 if cavlc else 1, deblocking_filter_control_present=1)
+    first_pic = 5
+    wr = pcamv_amd.StreamWrite(nal_ref_idc=2, slice_type=5, first_pic=first_pic, first_i_frame=first_pic)
+    hdr = dict(bits=write_header_bits(sp, qp, first_pic), i_frame=first_pic, nal_ref_idc=2, nal_unit_type=1)
+    if pcamv_amd.write_slice_header(sp, pcamv_amd.SliceFields(frame_num=first_pic, poc_lsb=2 * first_pic, slice_qp=qp)) != hdr["bits"]:
+        sys.exit("slice_parse_timing.py: the library's header differs from the one this tool writes")
+    out = dict(mode=mode, kernel="k_stream_slot", writer=writer, width=W, height=H, qp=qp, reps=args.reps, header_bits=len(hdr["bits"]), device=[])
+    nfr = max(classes, args.reps + 3)
+    clip = make_clip(W, H, nfr, seed=13)
+    d = [[torch.from_numpy(np.ascontiguousarray(pl)).to(dev) for pl in fr] for fr in clip]
+    p = pcamv_amd.param_default(W, H)
+    pcamv_amd.param_parse(p, "me", "hex")
+    pcamv_amd.param_parse(p, "subme", 6)
+    p.b_cabac = 0 if cavlc else 1
+    encs = []
+    for n in [int(v) for v in args.counts.split(",")]:
+        while len(encs) < n:
+            encs.append(pcamv_amd.Encoder(p))
+        batch = pcamv_amd.Batch(encs[:n])
+        batch.set_closed_loop(True)
+        stride = per_mb * encs[0].n_mb
+        off = torch.arange(n, dtype=torch.int64, device=dev) * stride
+        cap = torch.full((n,), stride, dtype=torch.int64, device=dev)
+        data = {k: torch.zeros(n * stride, dtype=torch.uint8, device=dev) for k in ("step", "stream")}
+        length = {k: torch.zeros(n, dtype=torch.int64, device=dev) for k in ("step", "stream")}
+        recon = [e.recon_device() for e in encs[:n]]
+        write_step = batch.write_step_cavlc if cavlc else batch.write_step
+        calls = dict(step=lambda: write_step(hdr, data["step"], off, cap, length["step"], as_nal=True, stream=0), stream=lambda: batch.write_stream_step(0))
+        wall, kernel_ms, small = dict(step=[], stream=[]), dict(step=[], stream=[]), dict(k_stream_slot=[], k_stream_commit=[])
+        torch.cuda.synchronize()
+        for t in range(args.reps + 1):                      # the first round is not timed: allocations, code load
+            for k, e in enumerate(encs[:n]):
+                ph = k % classes
+                if t:
+                    e.set_ref_device(recon[k][0], recon[k][1], recon[k][2], e.PREV_INTERNAL, e.PREV_INTERNAL)
+                else:
+                    a = d[ph]
+                    e.set_ref_device(a[0].data_ptr(), a[1].data_ptr(), a[2].data_ptr(), 0, 0)
+                b = d[(t + ph + 1) % nfr]
+                e.set_fenc_device(b[0].data_ptr(), b[1].data_ptr(), b[2].data_ptr())
+            batch.step(qp, 0.5, 0)
+            batch.stream_open(data["stream"], off, cap, length["stream"], sp, wr)       # every round's picture is a stream's first
+            torch.cuda.synchronize()
+            for k in (writer, "k_stream_slot", "k_stream_commit"):
+                batch.kernel_time(k, reset=True)
+            for name in (("step", "stream"), ("stream", "step"))[t & 1]:        # the two forms take turns at going first
+                w0 = time.perf_counter()
+                calls[name]()
+                torch.cuda.synchronize()
+                w = time.perf_counter() - w0
+                if (batch.write_status() != 0).any():
+                    sys.exit("slice_parse_timing.py: a unit did not fit %d bytes per macroblock" % per_mb)
+                ms, launches = batch.kernel_time(writer, reset=True)
+                if launches != 1:
+                    sys.exit("slice_parse_timing.py: a launch was not timed")
+                if t:
+                    wall[name].append(w * 1e3); kernel_ms[name].append(ms)
+            for k in small:
+                ms, launches = batch.kernel_time(k, reset=True)
+                if launches != 1:
+                    sys.exit("slice_parse_timing.py: a launch was not timed")
+                if t:
+                    small[k].append(ms)
+            if not torch.equal(length["step"], length["stream"]) or not torch.equal(data["step"], data["stream"]):
+                sys.exit("slice_parse_timing.py: the stream's unit is not the unit write_step wrote behind the host-made header")
+        med = lambda v: sorted(v)[len(v) // 2]              # noqa: E731
+        lens = length["stream"].cpu().numpy()
+        out["device"].append(dict(chains=n, unit_bytes_mean=float(lens.mean()), write_step_wall_ms=med(wall["step"]), write_step_wall_ms_min=min(wall["step"]),
+                                  write_step_wall_ms_max=max(wall["step"]), write_stream_step_wall_ms=med(wall["stream"]),
+                                  write_stream_step_wall_ms_min=min(wall["stream"]), write_stream_step_wall_ms_max=max(wall["stream"]),
+                                  wall_difference_ms=med(wall["stream"]) - med(wall["step"]), write_step_spread_ms=max(wall["step"]) - min(wall["step"]),
+                                  writer_kernel_ms_in_write_step=med(kernel_ms["step"]), writer_kernel_ms_in_write_stream_step=med(kernel_ms["stream"]),
+                                  k_stream_slot_ms=med(small["k_stream_slot"]), k_stream_commit_ms=med(small["k_stream_commit"]),
+                                  slot_and_commit_share_of_writer=(med(small["k_stream_slot"]) + med(small["k_stream_commit"])) / med(kernel_ms["stream"])))
+        print(json.dumps(out["device"][-1]), flush=True)
+        batch.close()
+    for e in encs:
+        e.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cavlc", action="store_true", help="CAVLC slices on --no-cabac contexts instead of CABAC ones")
     ap.add_argument("--nal", action="store_true", help="the receiver on NAL units: k_nal_to_rbsp next to the parser (profiles/nal_unescape_timing.json)")
     ap.add_argument("--stream", action="store_true", help="the receiver on byte streams: the index kernels, and a stream step next to a NAL step (profiles/stream_index_timing.json)")
-    ap.add_argument("--counts", default=None, help="default 1,64,1024,4096; with --nal or --stream 256,4096")
+    ap.add_argument("--write-stream", action="store_true", help="the sender's byte streams: write_stream_step next to write_step (profiles/stream_write_timing.json)")
+    ap.add_argument("--counts", default=None, help="default 1,64,1024,4096; with --nal, --stream or --write-stream 256,4096")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--host-threads", type=int, default=16)
     ap.add_argument("--out", default=None, help="default profiles/slice_parse_timing.json; with --nal profiles/nal_unescape_timing.json")
     args = ap.parse_args()
-    args.counts = args.counts or ("256,4096" if args.nal or args.stream else "1,64,1024,4096")
-    args.out = args.out if args.out is not None else os.path.join(ROOT, "profiles", "stream_index_timing.json" if args.stream else "nal_unescape_timing.json" if args.nal else
-                                                                  "slice_parse_timing.json")
+    args.counts = args.counts or ("256,4096" if args.nal or args.stream or args.write_stream else "1,64,1024,4096")
+    args.out = args.out if args.out is not None else os.path.join(ROOT, "profiles", "stream_write_timing.json" if args.write_stream else "stream_index_timing.json" if args.stream else
+                                                                  "nal_unescape_timing.json" if args.nal else "slice_parse_timing.json")
     import numpy as np
     import torch
     import pcamv_amd
@@ -240,6 +340,8 @@ def main():
         sys.exit("slice_parse_timing.py needs a GPU: the HIP path has no CPU fallback")
     torch.cuda.init()
     mode = "cavlc" if args.cavlc else "cabac"
+    if args.write_stream:
+        return write_line(args, write_stream_sweep(args, pcamv_amd, np, torch, mode), mode)
     fixture, kernel = ("pslice_cavlc_cif_umh_subme7_final", "k_parse_pslice_cavlc") if args.cavlc else ("pslice_cif_umh_subme7_final", "k_parse_pslice")
     g = np.load(os.path.join(ROOT, "tests", "golden", fixture + ".npz"))
     W, H, qp, m = int(g["width"]), int(g["height"]), int(g["qp"]), int(g["m"])

@@ -24,9 +24,10 @@
 #define NRING 8
 #define NKEV 16                /* ... and a timer of the smaller kernels */
 enum { KT_ANALYSE, KT_EMBED_PREPARE, KT_EXTRACT_PREPARE, KT_EXTRACT_BITS, KT_PAYLOAD_CHECK, KT_PARSE_PSLICE, KT_PARSE_PSLICE_CAVLC, KT_WRITE_PSLICE, KT_WRITE_PSLICE_CAVLC, KT_NAL_TO_RBSP,
-       KT_STREAM_PLAN, KT_STREAM_SCAN, KT_STREAM_PREFIX, KT_STREAM_PLACE, KT_STREAM_UNIT, KT_SLICE_HEADER, KT_STREAM_STATUS, KT_N };
+       KT_STREAM_PLAN, KT_STREAM_SCAN, KT_STREAM_PREFIX, KT_STREAM_PLACE, KT_STREAM_UNIT, KT_SLICE_HEADER, KT_STREAM_STATUS,
+       KT_STREAM_OPEN, KT_STREAM_SLOT, KT_STREAM_COMMIT, KT_N };
 #define PCAMV_FEATURES (PCAMV_FEATURE_PAYLOAD | PCAMV_FEATURE_SLICE_PARSER | PCAMV_FEATURE_SLICE_PARSER_CAVLC | PCAMV_FEATURE_SLICE_WRITER | \
-                        PCAMV_FEATURE_SLICE_WRITER_CAVLC | PCAMV_FEATURE_NAL_DEVICE | PCAMV_FEATURE_STREAM_DEVICE)
+                        PCAMV_FEATURE_SLICE_WRITER_CAVLC | PCAMV_FEATURE_NAL_DEVICE | PCAMV_FEATURE_STREAM_DEVICE | PCAMV_FEATURE_STREAM_WRITER)
 #define SLICE_GUARD_MBS 4       /* records behind a context's receive-side records that nothing may write (pcamv_gpu_debug_slice_records) */
 #define NSTAGE 2                /* staging buffers of extract_slices: a call waits for the one before the last */
 /* the stages of a step (batch_launch's `what`): plane production, analysis (search + RCA + encode), embedding, second pass */
@@ -74,6 +75,17 @@ struct StreamIndex {
     const uint8_t *bytes; long long bytes_size, slot;
 };
 
+/* the byte streams a batch writes (pcamv_gpu_batch_stream_open): the borrowed buffer and length array, the settings every picture shares,
+ * and in one block of the library's per context the stream's state, the header table the slice writer reads, and what passes between
+ * k_stream_slot, the writer and k_stream_commit */
+struct StreamOut {
+    int ready;
+    uint8_t *bytes; long long bytes_size; long long *len;
+    SwsSetup S;
+    uint8_t *d_own; size_t cap_own;     /* [SwsCtx n][w_off n][w_cap n][w_len n][off n][cap n][first n][table: n entries, n slots] */
+    uint8_t *d_head; size_t cap_head;
+};
+
 struct pcamv_ctx;
 /* A batch = the set of independent closed-GOP contexts whose frames advance together: every kernel
  * launch carries the same dependency step of all of them (descriptor arrays in device memory). */
@@ -108,6 +120,8 @@ struct pcamv_batch {
      * ring apart from the receiver's, since a write and a parse of one batch may be in flight on different streams */
     int *d_wstat; uint8_t *d_sw_tab, *d_sw_scratch;
     StageRing tx_stage;
+    /* ... that writes byte streams (k_stream_open, k_stream_slot, k_stream_commit): what stream_open was given and the library's own of it */
+    StreamOut so;
     KTimer kt[KT_N];            /* the timed kernels; the events of a timer are made by its first launch */
     char err[256];
 };
@@ -279,6 +293,7 @@ extern "C" void pcamv_gpu_batch_destroy(pcamv_batch_t *b)
     stream_index_free(b->sx);
     hipFree(b->d_wstat); hipFree(b->d_sw_tab); hipFree(b->d_sw_scratch);
     stage_destroy(b->tx_stage);
+    hipFree(b->so.d_own); hipFree(b->so.d_head);
     ring_destroy(b->ring); ring_destroy(b->xring);
     for (KTimer &T : b->kt) kt_destroy(T);
     free(b->ctx);
@@ -422,7 +437,7 @@ static const char *kt_name(const pcamv_batch *b, int k)      /* what pcamv_gpu_b
 {
     static const char *const small[KT_N] = {NULL, "k_embed_prepare", "k_extract_prepare", "k_extract_bits", "k_payload_check", "k_parse_pslice", "k_parse_pslice_cavlc", "k_write_pslice",
                                             "k_write_pslice_cavlc", "k_nal_to_rbsp", "k_stream_plan", "k_stream_scan", "k_stream_prefix", "k_stream_place", "k_stream_unit",
-                                            "k_slice_header", "k_stream_status"};
+                                            "k_slice_header", "k_stream_status", "k_stream_open", "k_stream_slot", "k_stream_commit"};
     return k == KT_ANALYSE ? dominant_kernel(b) : small[k];
 }
 extern "C" int pcamv_gpu_batch_copy_results_async(pcamv_batch_t *b, void *dst_mb, size_t mb_stride, void *dst_flip, size_t flip_stride, void *stream)
@@ -1809,26 +1824,41 @@ static int write_stage(pcamv_batch *b, const pcamv_slice_hdr_t *hdrs, int n_hdr,
     *d_hdr = (const int *)b->tx_stage.d[k]; *stage_out = k;
     return 0;
 }
-/* one launch over the batch's contexts as they stand: J brings the destination and the mode */
-static int write_run(pcamv_batch *b, WriteJobs J, const pcamv_slice_hdr_t *hdrs, int n_hdr, int cavlc, hipStream_t st)
+/* one launch over the batch's contexts as they stand: J brings the destination and the mode.  The headers are the host's (hdrs, staged
+ * here), or with sw a header table on the device that k_stream_slot fills in front of the writer from the descriptors the writer reads;
+ * k_stream_commit then follows the writer */
+static int write_run(pcamv_batch *b, WriteJobs J, const pcamv_slice_hdr_t *hdrs, int n_hdr, int cavlc, hipStream_t st, const StreamWrite *sw = NULL)
 {
-    int k;
-    TRY(write_stage(b, hdrs, n_hdr, st, &J.hdr, &k));
-    J.n_hdr = hdrs ? n_hdr : 1;
+    int k = -1;
+    if (sw) { J.hdr = sw->table; J.n_hdr = b->n; }
+    else {
+        TRY(write_stage(b, hdrs, n_hdr, st, &J.hdr, &k));
+        J.n_hdr = hdrs ? n_hdr : 1;
+    }
     J.status = b->d_wstat; J.tab = b->d_sw_tab; J.scratch = b->d_sw_scratch; J.scratch_stride = (long long)row_bytes(b, cavlc);
     J.lds_cols = b->sp_lds_cols;
     const FrameDev *dF; const EmbedDev *dE; int slot;
     int rc = batch_push_descs(b, st, &dF, &dE, &slot);
     if (!rc) {
+        if (sw) {
+            const int ev = kt_begin(b, KT_STREAM_SLOT, st);
+            hipLaunchKernelGGL(k_stream_slot, dim3((b->n + 63) / 64), dim3(64), 0, st, dF, *sw);
+            kt_end(b, KT_STREAM_SLOT, ev, st);
+        }
         const int kt = cavlc ? KT_WRITE_PSLICE_CAVLC : KT_WRITE_PSLICE;
         const int ev = kt_begin(b, kt, st);
         if (cavlc) pcamv_launch_write_pslice_cavlc((unsigned)b->n, st, dF, J);
         else pcamv_launch_write_pslice((unsigned)b->n, st, dF, J);
         kt_end(b, kt, ev, st);
+        if (sw) {
+            const int ev2 = kt_begin(b, KT_STREAM_COMMIT, st);
+            hipLaunchKernelGGL(k_stream_commit, dim3((b->n + 63) / 64), dim3(64), 0, st, *sw);
+            kt_end(b, KT_STREAM_COMMIT, ev2, st);
+        }
         rc = launched(b);
         if (!rc) rc = ring_release(b, b->ring, slot, st);
     }
-    const int rc2 = stage_release(b, b->tx_stage, k, st);                  /* released on every path */
+    const int rc2 = k >= 0 ? stage_release(b, b->tx_stage, k, st) : 0;     /* released on every path */
     return rc ? rc : rc2;
 }
 /* Every context's last step as a CABAC (cavlc: CAVLC) P slice, final motion (the records with the flip map of the step's embedding stage), from one
@@ -1953,6 +1983,122 @@ extern "C" int pcamv_gpu_rbsp_to_nal(const uint8_t *rbsp, size_t len, int nal_re
         nal[n++] = rbsp[i];
     }
     *nal_len = n;
+    return 0;
+}
+
+/* ------------------------------------------------------------------ sender to byte streams (k_stream_open, k_stream_slot, k_stream_commit; pcamv_stream_write.h) */
+extern "C" int pcamv_gpu_write_slice_header(const pcamv_stream_params_t *params, const pcamv_slice_fields_t *fields, uint8_t *bits, size_t cap, int32_t *n_bits)
+{
+    if (n_bits) *n_bits = 0;
+    if (!params || !fields || !n_bits || (!bits && cap)) return PCAMV_EINVAL;
+    int n = 0;
+    TRY(pcamv_slice_header_write(*params, *fields, NULL, &n));          /* judged and counted; nothing stored */
+    if ((size_t)(n + 7) / 8 > cap) return PCAMV_ENOMEM;
+    const int rc = pcamv_slice_header_write(*params, *fields, bits, &n);
+    *n_bits = n;
+    return rc;
+}
+/* the arrays of the library's block for n contexts (StreamOut::d_own), every one at a multiple of 8 */
+static size_t stream_out_bytes(int n) { return (size_t)n * (sizeof(SwsCtx) + 5 * 8 + 4 + SWS_HDR_WORDS * 4 + PCAMV_SLICE_HDR_BYTES) + 8; }
+static StreamWrite stream_out_jobs(const pcamv_batch *b)
+{
+    const StreamOut &O = b->so;
+    const size_t n = (size_t)b->n;
+    static_assert(sizeof(SwsCtx) % 8 == 0, "the int64 arrays follow the contexts' states");
+    StreamWrite J = StreamWrite();
+    J.bytes = O.bytes; J.bytes_size = O.bytes_size; J.len = O.len;
+    J.ctx = (SwsCtx *)O.d_own;
+    J.w_off = (long long *)(J.ctx + n); J.w_cap = J.w_off + n; J.w_len = J.w_cap + n;
+    long long *at = J.w_len + n;
+    J.off = at; J.cap = at + n;
+    J.first = (int *)(at + 2 * n); J.table = J.first + ((n + 1) & ~(size_t)1);
+    J.status = b->d_wstat; J.head = O.d_head; J.S = O.S; J.n = b->n;
+    return J;
+}
+extern "C" int pcamv_gpu_batch_stream_open(pcamv_batch_t *b, void *bytes, size_t bytes_size, const int64_t *off, const int64_t *cap, int64_t *len,
+                                           const pcamv_stream_params_t *params, const pcamv_stream_write_t *wr, const uint8_t *head, size_t head_len, void *stream)
+{
+    if (!b || !bytes || !off || !cap || !len || !params || !wr || (!head && head_len) || head_len > ((size_t)1 << 24) || bytes_size > ((size_t)1 << 62)) return PCAMV_EINVAL;
+    HIPCHK(b, hipSetDevice(b->device));
+    TRY(batch_live(b));
+    SwsSetup S; S.P = *params; S.W = *wr;
+    const int ok = sws_setup_ok(S);
+    if (ok == PCAMV_EUNSUP) return fail(b, ok, "weighted prediction: the header writer has no pred_weight_table");
+    if (ok) return fail(b, ok, wr->nal_ref_idc == 0 ? "nal_ref_idc 0: in this path a chain's P frame is the next one's reference" :
+                               "stream_open: parameter sets or stream settings out of range");
+    StreamOut &O = b->so;
+    O.ready = 0;
+    hipStream_t st = stream ? (hipStream_t)stream : b->ctx[0]->stream;
+    const size_t total = stream_out_bytes(b->n);
+    if (total > O.cap_own || head_len > O.cap_head) HIPCHK(b, hipDeviceSynchronize());        /* (steps on the blocks that are replaced may be in flight) */
+    TRY(grow(b, &O.d_own, &O.cap_own, total));
+    TRY(grow(b, &O.d_head, &O.cap_head, head_len));
+    O.bytes = (uint8_t *)bytes; O.bytes_size = (long long)bytes_size; O.len = (long long *)len; O.S = S;
+    StreamWrite J = stream_out_jobs(b);
+    static_assert(sizeof(long long) == sizeof(int64_t), "the caller's int64 arrays are read as they are");
+    HIPCHK(b, hipMemcpyAsync((void *)J.off, off, 8 * (size_t)b->n, hipMemcpyDeviceToDevice, st));
+    HIPCHK(b, hipMemcpyAsync((void *)J.cap, cap, 8 * (size_t)b->n, hipMemcpyDeviceToDevice, st));
+    if (head_len) HIPCHK(b, hipMemcpyAsync(O.d_head, head, head_len, hipMemcpyHostToDevice, st));
+    HIPCHK(b, hipStreamSynchronize(st));                                /* off, cap and head are read by this call alone: copied on return */
+    J.head_len = (long long)head_len;
+    const int ev = kt_begin(b, KT_STREAM_OPEN, st);
+    hipLaunchKernelGGL(k_stream_open, dim3((b->n + 63) / 64), dim3(64), 0, st, J);
+    kt_end(b, KT_STREAM_OPEN, ev, st);
+    TRY(launched(b));
+    O.ready = 1;
+    return 0;
+}
+extern "C" int pcamv_gpu_batch_write_stream_step(pcamv_batch_t *b, void *stream)
+{
+    if (!b) return PCAMV_EINVAL;
+    HIPCHK(b, hipSetDevice(b->device));
+    TRY(batch_live(b));
+    if (!b->so.ready) return fail(b, PCAMV_EINVAL, "no byte streams were opened on this batch yet (pcamv_gpu_batch_stream_open)");
+    const int cavlc = !b->so.S.P.entropy_cabac;
+    TRY(write_setup(b, cavlc));
+    const StreamWrite SJ = stream_out_jobs(b);
+    WriteJobs J = {};
+    J.bytes = SJ.bytes; J.bytes_size = SJ.bytes_size;
+    J.off = SJ.w_off; J.cap = SJ.w_cap; J.len = SJ.w_len;
+    J.mbs = NULL; J.as_nal = 1; J.final = 1;
+    return write_run(b, J, NULL, 0, cavlc, stream ? (hipStream_t)stream : b->ctx[0]->stream, &SJ);
+}
+/* synchronises */
+extern "C" int pcamv_gpu_batch_stream_written(pcamv_batch_t *b, int64_t *bytes, int64_t *pictures, int64_t *units)
+{
+    if (!b) return PCAMV_EINVAL;
+    HIPCHK(b, hipSetDevice(b->device));
+    if (!b->so.ready) return fail(b, PCAMV_EINVAL, "no byte streams were opened on this batch yet (pcamv_gpu_batch_stream_open)");
+    HIPCHK(b, hipDeviceSynchronize());
+    HostTmp<SwsCtx> h((size_t)b->n);
+    if (!h) return fail(b, PCAMV_ENOMEM, "no memory for %d stream states", b->n);
+    HIPCHK(b, hipMemcpy(h.p, b->so.d_own, sizeof(SwsCtx) * (size_t)b->n, hipMemcpyDeviceToHost));
+    for (int i = 0; i < b->n; i++) {
+        if (bytes) bytes[i] = h.p[i].cur;
+        if (pictures) pictures[i] = h.p[i].pic;
+        if (units) units[i] = h.p[i].units;
+    }
+    return 0;
+}
+/* the parity probe of the header writer: n cases, one lane each */
+extern "C" int pcamv_gpu_slice_headers_write_device(pcamv_ctx_t *c, const pcamv_stream_params_t *params, const pcamv_slice_fields_t *fields, int n,
+                                                    int32_t *rc_out, int32_t *n_bits, uint8_t *bits)
+{
+    if (!c || !params || !fields || !rc_out || !n_bits || !bits || n < 1 || n > (1 << 24)) return PCAMV_EINVAL;
+    HIPCHK(c, hipSetDevice(c->device));
+    DevTmp<pcamv_stream_params_t> d_p; DevTmp<pcamv_slice_fields_t> d_f; DevTmp<int> d_int; DevTmp<uint8_t> d_bits;
+    const size_t slots = (size_t)n * PCAMV_SLICE_HDR_BYTES;
+    HIPCHK(c, d_p.alloc((size_t)n)); HIPCHK(c, d_f.alloc((size_t)n)); HIPCHK(c, d_int.alloc(2 * (size_t)n)); HIPCHK(c, d_bits.alloc(slots));
+    HIPCHK(c, hipMemcpy(d_p, params, sizeof(*params) * (size_t)n, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_f, fields, sizeof(*fields) * (size_t)n, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemset(d_int, 0xA5, sizeof(int) * 2 * (size_t)n));
+    HIPCHK(c, hipMemset(d_bits, 0, slots));
+    hipLaunchKernelGGL(k_slice_headers_write, dim3((n + 63) / 64), dim3(64), 0, c->stream, d_p, d_f, n, d_int, d_int + n, d_bits);
+    TRY(launched(c));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(rc_out, d_int, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(n_bits, d_int + n, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(bits, d_bits, slots, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -26,6 +26,10 @@
  *
  * k_write_pslice (pcamv_slice_write.hip) is the other direction: a CABAC P slice of every context's last step written on the device, one
  * wavefront per slice (pcamv_slice_write.h, which also describes a launch: WriteJobs).
+ *
+ * k_stream_open, k_stream_slot, k_stream_commit put that writer's units into one Annex B byte stream per context (pcamv_stream_write.h), one
+ * lane per context: k_stream_slot in front of the writer makes each picture's slice header in the header table the writer reads and gives
+ * the writer its place at the stream's end, k_stream_commit behind it moves the stream's end over what was written.
  */
 #ifndef PCAMV_SLICE_HIP_H
 #define PCAMV_SLICE_HIP_H
@@ -35,6 +39,7 @@
 #include "pcamv_nal_unescape.h"
 #include "pcamv_stream_index.h"
 #include "pcamv_slice_write.h"
+#include "pcamv_stream_write.h"
 
 /* the slices of one launch: slice i is bytes[off[i] .. off[i] + len[i]), its slice data starts behind bit start_bit[i], slice QP qp[i] */
 struct SliceJobs {
@@ -250,6 +255,54 @@ static __global__ void __launch_bounds__(64) k_stream_status(const int *__restri
 {
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (i < n && first[i]) status[i] = first[i];
+}
+
+/* ---- the sender's byte streams (pcamv_stream_write.h), one lane per context.  ctx, table, slot, w_len are the library's; bytes and len
+ * the caller's (stream_open).  table is the header table the slice writer reads (WriteJobs::hdr, n entries), slot / w_len / status what
+ * it reads as off, cap and writes as len, status */
+static_assert(SWS_HDR_WORDS == SW_HDR_WORDS, "k_stream_slot writes the table the slice writers read");
+struct StreamWrite {
+    uint8_t *bytes; long long bytes_size;
+    SwsCtx *ctx; int *table;
+    long long *w_off, *w_cap, *w_len, *len; int *first, *status;
+    const long long *off, *cap; const uint8_t *head; long long head_len;       /* k_stream_open alone */
+    SwsSetup S;
+    int n;
+};
+static __global__ void __launch_bounds__(64) k_stream_open(const StreamWrite J)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= J.n) return;
+    SwsCtx c;
+    long long len = 0;
+    sws_open(c, J.bytes, J.bytes_size, J.off[i], J.cap[i], J.head, J.head_len, &len);
+    J.ctx[i] = c; J.len[i] = len;
+}
+static __global__ void __launch_bounds__(64) k_stream_slot(const FrameDev *__restrict__ Fs, const StreamWrite J)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= J.n) return;
+    const SwsSlot s = sws_slot(J.S, J.ctx[i], J.bytes, Fs[i].qp, J.table, J.n, i);
+    J.w_off[i] = s.off; J.w_cap[i] = s.cap; J.first[i] = s.first;
+}
+static __global__ void __launch_bounds__(64) k_stream_commit(const StreamWrite J)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= J.n) return;
+    SwsCtx c = J.ctx[i];
+    long long len = 0; int rc = 0;
+    sws_commit(J.S, c, J.first[i], J.w_len[i], J.status[i], &len, &rc);
+    J.ctx[i] = c; J.len[i] = len; J.status[i] = rc;
+}
+/* the parity probe of the header writer: case i's parameter set and members, its slot of PCAMV_SLICE_HDR_BYTES bytes (zeros beforehand) */
+static __global__ void __launch_bounds__(64) k_slice_headers_write(const pcamv_stream_params_t *__restrict__ P, const pcamv_slice_fields_t *__restrict__ f,
+                                                                   int n, int *__restrict__ rc, int *__restrict__ n_bits, uint8_t *__restrict__ bits)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    int nb = 0;
+    rc[i] = pcamv_slice_header_write(P[i], f[i], bits + (long long)i * PCAMV_SLICE_HDR_BYTES, &nb);
+    n_bits[i] = nb;
 }
 /* the writer's kernel is a unit of its own (pcamv_slice_write.hip): it inlines the analysis' prediction and transform primitives, and what
  * the compiler makes of the kernels of this unit depends on what else in the unit calls them */

@@ -343,6 +343,51 @@ def parse_slice_header(rbsp, nal_header, params):
     return rc, sb.value, qp.value, fn_.value
 
 
+FEATURE_STREAM_WRITER = 0x80    # the sender writes Annex B byte streams: Batch.stream_open, Batch.write_stream_step, write_slice_header
+SLICE_HDR_MAX_BITS = 215        # PCAMV_SLICE_HDR_MAX_BITS
+SLICE_HDR_BYTES = 28            # PCAMV_SLICE_HDR_BYTES: a header's slot in the output of Encoder.slice_headers_write_device
+
+
+class SliceFields(C.Structure):
+    """pcamv_slice_fields_t: what a P slice header says beyond the parameter sets"""
+    _fields_ = [("nal_ref_idc", C.c_int32), ("slice_type", C.c_int32), ("frame_num", C.c_int32), ("poc_lsb", C.c_int32), ("delta_pic_order_cnt_bottom", C.c_int32),
+                ("delta_pic_order_cnt", C.c_int32 * 2), ("redundant_pic_cnt", C.c_int32), ("slice_qp", C.c_int32), ("disable_deblocking_filter_idc", C.c_int32),
+                ("slice_alpha_c0_offset_div2", C.c_int32), ("slice_beta_offset_div2", C.c_int32)]
+
+    def __init__(self, **kw):
+        d = dict(nal_ref_idc=2, slice_type=5, slice_qp=26)
+        d.update(kw)
+        if "delta_pic_order_cnt" in d:
+            d["delta_pic_order_cnt"] = (C.c_int32 * 2)(*d["delta_pic_order_cnt"])
+        super().__init__(**d)
+
+
+class StreamWrite(C.Structure):
+    """pcamv_stream_write_t: what every picture of the streams a batch writes shares.  disable_deblocking_filter_idc -1: the
+    reference's rule per picture (0 if 15 < qp + 2 * min(alpha, beta), else 1)"""
+    _fields_ = [(n, C.c_int32) for n in ("nal_ref_idc", "slice_type", "first_pic", "first_i_frame", "disable_deblocking_filter_idc",
+                                         "slice_alpha_c0_offset_div2", "slice_beta_offset_div2", "aud")]
+
+    def __init__(self, **kw):
+        d = dict(nal_ref_idc=2, slice_type=5)
+        d.update(kw)
+        super().__init__(**d)
+
+
+def write_slice_header(params, fields):
+    """pcamv_gpu_write_slice_header: the bits (a list of 0 / 1) of the P slice header for a StreamParams and a SliceFields, the inverse of
+    parse_slice_header; what Encoder.write_pslice and Batch.write_step take as hdr.  Raises PcamvError with the library's code (-1: a
+    value out of range, -5: weighted prediction)"""
+    out = np.zeros(SLICE_HDR_BYTES, np.uint8)
+    n = C.c_int32()
+    fn = load_library().pcamv_gpu_write_slice_header
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32)]
+    rc = fn(C.byref(params), C.byref(fields), _p(out), len(out), C.byref(n))
+    if rc:
+        raise PcamvError(f"pcamv_gpu_write_slice_header failed: {rc}")
+    return np.unpackbits(out, bitorder="big")[:n.value].tolist()
+
+
 def features():
     """pcamv_gpu_features: mask of FEATURE_* the loaded library has"""
     lib = load_library()
@@ -624,6 +669,20 @@ class Encoder:
         self._chk(fn(self.ctx, _p(data if len(data) else pad), len(data), _p(off), _p(length), _p(nal_header), n, C.byref(params), _p(rc), _p(sb), _p(qp), _p(fnum)),
                   "slice_headers_device")
         return rc, sb, qp, fnum
+
+    def slice_headers_write_device(self, cases):
+        """pcamv_gpu_slice_headers_write_device: the P slice headers of `cases`, a list of (StreamParams, SliceFields), written by
+        k_slice_headers_write, one lane each -- the parity probe of Batch.write_stream_step's header stage.  Returns (return codes,
+        bit counts, an (n, SLICE_HDR_BYTES) uint8 array of the packed bits, zeros behind each header) as write_slice_header gives
+        them"""
+        n = len(cases)
+        ps = (StreamParams * n)(*[c[0] for c in cases])
+        fs = (SliceFields * n)(*[c[1] for c in cases])
+        rc, nb, bits = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros((n, SLICE_HDR_BYTES), np.uint8)
+        fn = self.lib.pcamv_gpu_slice_headers_write_device
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._chk(fn(self.ctx, ps, fs, n, _p(rc), _p(nb), _p(bits)), "slice_headers_write_device")
+        return rc, nb, bits
 
     def slice_bound(self, hdr_bits=0, as_nal=False):
         """pcamv_gpu_slice_bound: a capacity under which no slice of this picture size fails to be written"""
@@ -960,6 +1019,44 @@ class Batch:
         fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         self._slice_chk(fn(self.b, arr if made else None, len(made), int(bool(as_nal)), data.data_ptr(), data.numel(), off.data_ptr(), cap.data_ptr(),
                            length.data_ptr(), C.c_void_p(stream or None)), call[len("pcamv_gpu_"):])
+
+    def stream_open(self, data, off, cap, length, params, wr, head=b"", stream=0):
+        """pcamv_gpu_batch_stream_open: context i's Annex B byte stream is data[off[i] : off[i] + cap[i]] of a contiguous uint8 device
+        tensor (borrowed); off / cap int64 device tensors read by this call alone; `length` an int64 device tensor (borrowed) that the
+        library keeps current: length[i] = bytes of stream i so far, so that (data, off, length) is at any time what
+        index_streams_device takes.  params: the StreamParams of the streams, wr: a StreamWrite, head: bytes copied to the start of
+        every stream (the caller's parameter sets and IDR picture).  A context whose region does not lie inside `data` or does not
+        hold `head` gets length 0 and write_status() -1 in every step.  Ordering is the caller's, as for extract_slices_device"""
+        for t, size, what in ((data, 1, "data: uint8"), (off, 8, "off: int64"), (cap, 8, "cap: int64"), (length, 8, "length: int64")):
+            if not _is_device_tensor(t) or not t.is_cuda or t.element_size() != size or not t.is_contiguous():
+                raise PcamvError(f"{what}, contiguous, on the device")
+        if any(t.numel() != len(self.encs) for t in (off, cap, length)):
+            raise PcamvError(f"one entry per context ({len(self.encs)}) in off / cap / length")
+        keep = np.frombuffer(bytes(head), np.uint8) if len(head) else None
+        fn = self.lib.pcamv_gpu_batch_stream_open
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        self._slice_chk(fn(self.b, data.data_ptr(), data.numel(), off.data_ptr(), cap.data_ptr(), length.data_ptr(), C.byref(params), C.byref(wr),
+                           _p(keep), len(head), C.c_void_p(stream or None)), "batch_stream_open")
+
+    def write_stream_step(self, stream=0):
+        """pcamv_gpu_batch_write_stream_step: every context's last step appended to its stream as [access unit delimiter +] P slice
+        unit -- the slice header made on the device from the step's QP, the stream's picture counter and the parameter sets
+        (k_stream_slot), the slice by k_write_pslice / k_write_pslice_cavlc as the StreamParams' entropy_cabac says, the stream's
+        end moved on by k_stream_commit -- without a host sync and without per-frame arrays.  After the step it writes and before
+        the next.  write_status() afterwards: 0, -3 (the picture does not fit what is left of the region: the stream stays as it
+        was, the picture counter moves on), -1 (the region was refused by stream_open)"""
+        fn = self.lib.pcamv_gpu_batch_write_stream_step
+        fn.argtypes = [C.c_void_p, C.c_void_p]
+        self._slice_chk(fn(self.b, C.c_void_p(stream or None)), "batch_write_stream_step")
+
+    def stream_written(self):
+        """(bytes, pictures, units) per context: the stream's length, the steps since stream_open, the slice units in the stream;
+        synchronises"""
+        out = [np.zeros(len(self.encs), np.int64) for _ in range(3)]
+        fn = self.lib.pcamv_gpu_batch_stream_written
+        fn.argtypes = [C.c_void_p] * 4
+        self._slice_chk(fn(self.b, *[_p(o) for o in out]), "batch_stream_written")
+        return tuple(out)
 
     def write_status(self):
         """per context: 0, or -3 where its slice of the last write_step did not fit its capacity; synchronises"""
