@@ -344,6 +344,7 @@ int pcamv_gpu_abi_version(void);
 #define PCAMV_FEATURE_NAL_DEVICE 0x20u  /* the receiver takes NAL units: emulation prevention undone on the device (the *_nals* calls) */
 #define PCAMV_FEATURE_STREAM_DEVICE 0x40u       /* the receiver takes Annex B byte streams: units found and slice headers read on the device */
 #define PCAMV_FEATURE_STREAM_WRITER 0x80u       /* the sender writes Annex B byte streams: slice headers and unit placement on the device */
+#define PCAMV_FEATURE_STREAM_WINDOW 0x100u      /* the receiver on byte streams takes a window of slice units per context in one call */
 unsigned pcamv_gpu_features(void);
 
 /* ---- Payload path: the caller's bits through the device-resident entry points, and back out on the device ----
@@ -510,6 +511,40 @@ typedef struct pcamv_stream_t { const uint8_t *bytes; size_t len; } pcamv_stream
 int pcamv_gpu_batch_index_streams(pcamv_batch_t *batch, const pcamv_stream_t *streams, int64_t max_units, int64_t *n_slices_out, void *stream);
 int pcamv_gpu_batch_extract_stream_step(pcamv_batch_t *batch, const pcamv_stream_params_t *params, float emrate, int32_t *nal_header, void *stream);
 int pcamv_gpu_batch_stream_tell(pcamv_batch_t *batch, int64_t *next, int64_t *total);
+/* A window of slice units per context in one call (PCAMV_FEATURE_STREAM_WINDOW).  A slice is one serial chain on one wavefront, so a
+ * step costs the latency of one slice however few contexts the batch has; the frames of one stream are independent in everything that
+ * is expensive (a P slice parses on its own; carriers, stego bits and n of a frame depend on its records alone), and only the write
+ * cursor of the received stream and the receiver's column generator chain from frame to frame, both cheap once every frame's n is
+ * known.  So k units per context go through unescape (k_stream_window_unit), header, parser and carrier scan (k_extract_count) as
+ * n * k independent jobs, one lane per context then walks its k slots in order (k_extract_chain), and k_extract_bits writes all of
+ * them.  The rule: a window call of k is observationally k extract_stream_step calls.
+ *
+ * stream_window(k), 1 <= k <= PCAMV_STREAM_WINDOW_MAX, reserves per context x slot what a step keeps per context: receive-side records
+ * (with the guard behind them), stego, hdr, cols, a status word, a row-scratch slot where the picture is wider than the parser's LDS
+ * limit, and an RBSP slot sized as the index call sizes the steps'.  The memory is k times the step path's and k is the caller's
+ * choice: a 1080p slot is about 2 MB (8160 records of 236 bytes, 128 KB of stego bytes), so 256 contexts x 8 slots take 4 GB.  k = 0
+ * releases it.  The call synchronises and allocates, as an index call may; it belongs behind an index call (PCAMV_EINVAL before), and
+ * an index call made later that needs longer RBSP slots regrows them.  The window call below never allocates.
+ *
+ * extract_stream_window(params, emrate, k): refused with PCAMV_EINVAL for k < 1 or k above the reserved count; every other refusal is
+ * extract_stream_step's.  Slot w < k of context i takes the unit at cursor[i] + w if that lies within min(n_slices, max_units), else
+ * its status is PCAMV_EEOF and it takes nothing; the cursor moves on by the number of slots that took a unit (a unit of kind UNSUP
+ * counts as taken and gives PCAMV_EUNSUP; a context whose index failed gives PCAMV_EINVAL in every slot).  Each taken unit goes
+ * through the step's stages with the step's codes.  Within a context the slots are appended to the received stream in slot order: a
+ * slot with a non-zero status appends nothing and leaves write cursor and column generator where they were, the slots behind it go on
+ * from there; m > n or sub-matrices that cannot be built append m zero bits and draw from the generator what a step draws; a slot
+ * that runs past the reservation drops its bits beyond it and the next synchronising call reports PCAMV_ENOMEM once.  nal_header
+ * (optional): device int32[n * k], context-major (i * k + w), the header byte or -1 where no unit was taken.  No host synchronisation
+ * and no per-frame host arrays; a call waits on the device for the window call before it, whichever stream that was on.  Afterwards
+ * pcamv_gpu_batch_slice_status returns slot k - 1's status of every context, pcamv_gpu_debug_slice_records the records of the last slot
+ * that took a unit, stream_tell the cursor as moved: what k steps would have left.
+ *
+ * window_status synchronises: host int32[n * k] of the last window call, context-major. */
+#define PCAMV_STREAM_WINDOW_MAX 64
+int pcamv_gpu_batch_stream_window(pcamv_batch_t *batch, int k);
+int pcamv_gpu_batch_extract_stream_window(pcamv_batch_t *batch, const pcamv_stream_params_t *params, float emrate, int k,
+                                          int32_t *nal_header, void *stream);
+int pcamv_gpu_batch_window_status(pcamv_batch_t *batch, int32_t *status);
 /* The parity probes; they synchronise.  index_streams_probe: n streams of one host buffer through the three kernels, ALL units listed
  * (what pcamv_gpu_annexb_index lists).  units_out holds n tables of cap_per_stream + PCAMV_UNIT_GUARD entries each: the library fills
  * them with bytes 0xA5 on the device, the kernels write the first min(count, cap_per_stream) entries of each, and everything comes

@@ -18,9 +18,16 @@ host function pcamv_gpu_annexb_index on the same streams, one core and 16 thread
 next to the parser of the same launches, and the wall time of Batch.extract_stream_step against Batch.extract_nals_device on the same
 unit.  Written to profiles/stream_index_timing.json, one line per entropy mode.
 
+With --window a window of units per stream: 256 of the same streams of 8 frames, and in one run, in turn within every
+repetition, the wall time of (a) 8 x Batch.extract_stream_step, (b) one Batch.extract_stream_window(k=8), (c) the floor: one
+Batch.extract_stream_step of a batch of 2048 contexts -- the same slices through the step's kernels in one launch -- with the times of
+k_stream_window_unit, k_extract_count and k_extract_chain next to the parser's in each form.  (a) and (b) must receive the same bits.
+Written to profiles/stream_window_timing.json, one line per entropy mode.
+
     python tools/slice_parse_timing.py [--cavlc] [--counts 1,64,1024,4096] [--reps 5] [--out profiles/slice_parse_timing.json]
     python tools/slice_parse_timing.py --nal [--cavlc] [--counts 256,4096] [--reps 5] [--out profiles/nal_unescape_timing.json]
     python tools/slice_parse_timing.py --stream [--cavlc] [--counts 256,4096] [--reps 5] [--out profiles/stream_index_timing.json]
+    python tools/slice_parse_timing.py --window [--cavlc] [--counts 256] [--reps 5] [--out profiles/stream_window_timing.json]
 
 With --write-stream the sender's byte streams: 256 and 4096 closed-loop CIF chains (--me hex --subme 6, QP 26) that step
 and then write the same frame twice in turn -- Batch.write_step*(as_nal=True) with one host-made header, and Batch.write_stream_step,
@@ -128,10 +135,9 @@ def write_header_bits(sp, qp, frame_num):
     return bits
 
 
-def stream_sweep(args, pcamv_amd, np, torch, out, slice_data, qp, m, want):
-    """--stream: out["device"] gets one entry per count; `want`: the host parser's records of the slice"""
-    dev = torch.device("cuda", 0)
-    frames = 8
+def frames_stream(args, pcamv_amd, np, slice_data, qp, frames=8):
+    """(parameter sets, [(unit, header bits)], stream, the host's unit list): `frames` pictures of the fixture's slice data, each
+    behind an access unit delimiter and a header of its own"""
     sp = pcamv_amd.StreamParams(log2_max_frame_num=8, log2_max_poc_lsb=8, entropy_cabac=0 if args.cavlc else 1, deblocking_filter_control_present=1)
     units = []
     for k in range(frames):
@@ -148,6 +154,14 @@ def stream_sweep(args, pcamv_amd, np, torch, out, slice_data, qp, m, want):
     u_list, n_units, n_slices = pcamv_amd.annexb_index(stream)
     if (n_units, n_slices) != (2 * frames, frames):
         sys.exit("slice_parse_timing.py: the stream is not what it was assembled from")
+    return sp, units, stream, u_list
+
+
+def stream_sweep(args, pcamv_amd, np, torch, out, slice_data, qp, m, want):
+    """--stream: out["device"] gets one entry per count; `want`: the host parser's records of the slice"""
+    dev = torch.device("cuda", 0)
+    frames = 8
+    sp, units, stream, u_list = frames_stream(args, pcamv_amd, np, slice_data, qp, frames)
     out.update(kernel="k_stream_scan", parser=out["kernel"], stream_bytes=len(stream), frames=frames, chunk=pcamv_amd.stream_chunk())
     lib = pcamv_amd.load_library()
     lib.pcamv_gpu_annexb_index.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
@@ -224,6 +238,83 @@ def stream_sweep(args, pcamv_amd, np, torch, out, slice_data, qp, m, want):
                                   step_extra_share_of_parser=extra_ms / ms[out["parser"]], extract_stream_step_wall_ms=wall["stream"] * 1e3,
                                   extract_nals_device_wall_ms=wall["nal"] * 1e3, wall_ratio=wall["stream"] / wall["nal"]))
         batch.close()
+    for e in encs:
+        e.close()
+
+
+def window_sweep(args, pcamv_amd, np, torch, out, slice_data, qp, m, want):
+    """--window: per count n of streams of 8 frames, in one run and in turn within every repetition, each between two synchronisations:
+    (a) 8 x extract_stream_step, (b) one extract_stream_window(k=8) on the same batch, (c) the floor -- one extract_stream_step of a
+    batch of 8 n contexts, the same number of slices through the step's kernels in one launch.  The index call in front of each (it
+    puts the cursors back) is not timed.  (a) and (b) must leave the same received bits"""
+    dev = torch.device("cuda", 0)
+    frames = 8
+    sp, units, stream, _ = frames_stream(args, pcamv_amd, np, slice_data, qp, frames)
+    parser = out["kernel"]
+    window_kernels = ("k_stream_window_unit", "k_extract_count", "k_extract_chain")
+    out.update(kernel="k_stream_window_unit", parser=parser, stream_bytes=len(stream), frames=frames)
+    p = pcamv_amd.param_default(out["width"], out["height"])
+    pcamv_amd.param_parse(p, "subme", 5)
+    p.b_cabac = 0 if args.cavlc else 1
+    encs = []
+    for n in [int(v) for v in args.counts.split(",")]:
+        while len(encs) < frames * n:
+            e = pcamv_amd.Encoder(p)
+            e.rx_reserve(frames * m + 64)
+            encs.append(e)
+        few, many = pcamv_amd.Batch(encs[:n]), pcamv_amd.Batch(encs[:frames * n])
+        stride = (len(stream) + 3) | 1                      # every context its own copy, at odd offsets
+        data = torch.from_numpy(np.tile(np.frombuffer(stream + bytes(stride - len(stream)), np.uint8), frames * n)).to(dev)
+        off = torch.arange(frames * n, dtype=torch.int64, device=dev) * stride
+        length = torch.full((frames * n,), len(stream), dtype=torch.int64, device=dev)
+        torch.cuda.synchronize()                            # the tensors are complete before the library's stream reads them
+
+        def fresh(batch, count):
+            for e in encs[:count]:
+                e.rx_reset()
+            if batch.index_streams_device(data, off[:count], length[:count], max_units=16).tolist() != [frames] * count:
+                sys.exit("slice_parse_timing.py: the device's index differs from the host's")
+
+        def steps():
+            for _ in range(frames):
+                few.extract_stream_step(sp, 0.5)
+
+        fresh(few, n)
+        few.stream_window(frames)
+        runs = (("steps", few, n, steps), ("window", few, n, lambda: few.extract_stream_window(sp, 0.5, frames)),
+                ("floor", many, frames * n, lambda: many.extract_stream_step(sp, 0.5)))
+        wall, ms, received = dict(steps=0.0, window=0.0, floor=0.0), {}, {}
+        for rep in range(args.reps + 1):                    # the first round is not timed: allocations, code load
+            for name, batch, count, call in runs:
+                fresh(batch, count)
+                for k in window_kernels + (parser,):
+                    batch.kernel_time(k, reset=True)
+                w0 = time.perf_counter()
+                call()
+                torch.cuda.synchronize()
+                if rep:
+                    wall[name] += (time.perf_counter() - w0) / args.reps
+                if (batch.slice_status() != 0).any() or (name == "window" and (batch.window_status() != 0).any()):
+                    sys.exit("slice_parse_timing.py: a unit failed on the device")
+                got = {k: batch.kernel_time(k, reset=True) for k in window_kernels + (parser,)}
+                if got[parser][1] != (frames if name == "steps" else 1) or any(got[k][1] != (name == "window") for k in window_kernels):
+                    sys.exit("slice_parse_timing.py: a launch was not timed")
+                if rep:
+                    for k, (v, _) in got.items():
+                        ms[name, k] = ms.get((name, k), 0.0) + v / args.reps
+                if name != "floor":
+                    received[name] = [encs[0].received(packed=True).tobytes(), encs[n - 1].received(packed=True).tobytes(), encs[n - 1].rx_tell()[0]]
+                    rec = encs[n - 1].slice_records()[0]
+                    if any(not np.array_equal(rec[f], want[f]) for f in rec.dtype.names) or received[name][2] != frames * m:
+                        sys.exit("slice_parse_timing.py: the device's records differ from the host parser's")
+            if received["steps"] != received["window"]:
+                sys.exit("slice_parse_timing.py: the window received other bits than the steps")
+        out["device"].append(dict(streams=n, frames=frames, slices=frames * n,
+                                  steps_wall_ms=wall["steps"] * 1e3, window_wall_ms=wall["window"] * 1e3, floor_wall_ms=wall["floor"] * 1e3,
+                                  steps_over_window=wall["steps"] / wall["window"], window_over_floor=wall["window"] / wall["floor"],
+                                  parser_kernel_ms=dict(steps_each=ms["steps", parser], window=ms["window", parser], floor=ms["floor", parser]),
+                                  window_kernels_ms={k: ms["window", k] for k in window_kernels}))
+        few.close(); many.close()
     for e in encs:
         e.close()
 
@@ -324,14 +415,16 @@ def main():
     ap.add_argument("--cavlc", action="store_true", help="CAVLC slices on --no-cabac contexts instead of CABAC ones")
     ap.add_argument("--nal", action="store_true", help="the receiver on NAL units: k_nal_to_rbsp next to the parser (profiles/nal_unescape_timing.json)")
     ap.add_argument("--stream", action="store_true", help="the receiver on byte streams: the index kernels, and a stream step next to a NAL step (profiles/stream_index_timing.json)")
+    ap.add_argument("--window", action="store_true", help="a window of 8 units per stream next to 8 stream steps and to one step of 8 times the streams (profiles/stream_window_timing.json)")
     ap.add_argument("--write-stream", action="store_true", help="the sender's byte streams: write_stream_step next to write_step (profiles/stream_write_timing.json)")
     ap.add_argument("--counts", default=None, help="default 1,64,1024,4096; with --nal, --stream or --write-stream 256,4096")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--host-threads", type=int, default=16)
     ap.add_argument("--out", default=None, help="default profiles/slice_parse_timing.json; with --nal profiles/nal_unescape_timing.json")
     args = ap.parse_args()
-    args.counts = args.counts or ("256,4096" if args.nal or args.stream or args.write_stream else "1,64,1024,4096")
+    args.counts = args.counts or ("256" if args.window else "256,4096" if args.nal or args.stream or args.write_stream else "1,64,1024,4096")
     args.out = args.out if args.out is not None else os.path.join(ROOT, "profiles", "stream_write_timing.json" if args.write_stream else "stream_index_timing.json" if args.stream else
+                                                                  "stream_window_timing.json" if args.window else
                                                                   "nal_unescape_timing.json" if args.nal else "slice_parse_timing.json")
     import numpy as np
     import torch
@@ -370,6 +463,9 @@ def main():
         return write_line(args, out, mode)
     if args.stream:
         stream_sweep(args, pcamv_amd, np, torch, out, g["slice_data"].tobytes(), qp, m, want)
+        return write_line(args, out, mode)
+    if args.window:
+        window_sweep(args, pcamv_amd, np, torch, out, g["slice_data"].tobytes(), qp, m, want)
         return write_line(args, out, mode)
     w0 = time.perf_counter(); host_parse(200); one = (time.perf_counter() - w0) / 200
     with ThreadPoolExecutor(args.host_threads) as ex:

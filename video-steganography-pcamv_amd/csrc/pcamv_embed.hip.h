@@ -6,6 +6,7 @@
  *   k_mb_flips        per macroblock: is one of its carriers flipped (what the second pass asks)
  *   k_extract_prepare / k_extract_bits / k_payload_check   the receiving side: carriers of the final motion -> syndrome ->
  *                     packed bytes appended to the context's received stream, and its comparison with the attached payload
+ *   k_extract_count / k_extract_chain   k_extract_prepare for a window of frames per context: the carriers of all of them, then the chain
  */
 #ifndef PCAMV_EMBED_HIP_H
 #define PCAMV_EMBED_HIP_H
@@ -39,12 +40,7 @@ struct EmbedDev {
                                * message bit [12] */
 };
 
-/* per-context device words of the payload path */
-enum { PST_TX = 0,            /* payload bits the sender has consumed */
-       PST_RX = 1,            /* bits appended to the received stream */
-       PST_OVERRUN = 2,       /* != 0: a frame did not fit the reserved received buffer (its tail was dropped, never written) */
-       PST_RX_LCG = 3,        /* the receiver's own STC column generator (embed.h:134), started like the sender's */
-       PST_WORDS = 4 };
+/* (the per-context device words of the payload path, PST_*: pcamv_stc_extract.h) */
 
 /* The receiving side of one frame (k_extract_prepare -> k_extract_bits), and the comparison of the received stream with the payload. */
 struct ExtractDev {
@@ -75,27 +71,8 @@ __device__ int dev_glibc_rand(int *st)
     st[31] = f; st[32] = b;
     return (int)((v >> 1) & 0x7fffffff);
 }
-__device__ int dev_stc_matrix(int width, int height, unsigned *cols, long long *lcg)
-{
-    if (width >= 2 && width <= 20 && height >= 7 && height <= 12) {
-        for (int i = 0; i < width; i++) cols[i] = pcamv_stc_mats_dev[(height - 7) * 400 + (width - 1) * 20 + i];
-        return 1;
-    }
-    if ((1 << (height - 2)) < width) return 0;
-    unsigned mask = (1u << (height - 2)) - 1, bop = (1u << (height - 1)) + 1;
-    long hold = (long)*lcg;
-    for (int i = 0; i < width; i++) {
-        unsigned r; int j;
-        for (j = -1; j < i;) {
-            hold = hold * 214013L + 2531011L;
-            r = (((unsigned)(hold >> 16) & 0x7fff & mask) << 1) + bop;
-            for (j = 0; j < i; j++) if (cols[j] == r) break;
-        }
-        cols[i] = r;
-    }
-    *lcg = hold;
-    return 1;
-}
+/* (pcamv_stc_extract.h: the builder the host check of the receive-side chain compiles too) */
+__device__ __forceinline__ int dev_stc_matrix(int width, int height, unsigned *cols, long long *lcg) { return pcamv_stc_matrix(pcamv_stc_mats_dev, width, height, cols, lcg); }
 
 /* Carriers of a frame's records in embedding order (encoder.c:1566-1647), for a workgroup of 1024: every thread takes a run of
  * macroblocks [*lo, *hi), and gets the index of its first carrier in *base; returns the frame's carrier count.  Sender and
@@ -401,20 +378,13 @@ static __global__ void __launch_bounds__(256) k_mb_flips(const EmbedDev *__restr
 /* ------------------------------------------------------------------ receiving side
  * (the reference has no extractor; this is the library's own, pcamv_gpu_stc_extract_lcg, on the device)
  * k_extract_prepare, one workgroup per frame: the carriers of the frame as a decoder finds them, the LSB of each one's final MV,
- * the frame's n and m, the two sub-matrices from the receiver's own column generator (shorter then longer, as the host extractor
- * calls them), and the frame's place in the received stream: the write cursor moves by m whatever the frame turns out to be, so
- * that the offsets of sender and receiver stay aligned (m > n, or no matrix for the width: m zero bits -- the stream is zeroed
- * when reserved, so nothing is written for them). */
-static __global__ void __launch_bounds__(1024) k_extract_prepare(const ExtractDev *__restrict__ Xs)
+ * then on one thread what chains from frame to frame (pcamv_extract_chain_slot, pcamv_stc_extract.h): the frame's n and m, the two
+ * sub-matrices from the receiver's own column generator, and the frame's place in the received stream.
+ * A window of frames per context (k_extract_count, k_extract_chain) splits the two: the carriers of every frame of the window at once,
+ * then the chain over a context's frames in order. */
+/* the parallel part, a workgroup of 1024: X.stego filled, the frame's carrier count returned to every thread */
+__device__ __forceinline__ int dev_extract_carriers(const ExtractDev &X, int *s_cnt)
 {
-    const ExtractDev X = Xs[blockIdx.x];
-    __shared__ int s_cnt[1024];
-    __shared__ unsigned s_cols[2 * STC_MAXW];
-    const int t = threadIdx.x;
-    if (X.slice_status && *X.slice_status) {            /* (the whole workgroup: no barrier was reached) the slice did not parse: no bits */
-        if (t == 64) { X.hdr[0] = 0; X.hdr[1] = 0; X.hdr[2] = 0; *(long long *)(X.hdr + 6) = X.pstate[PST_RX]; }
-        return;
-    }
     int lo, hi, base, slots[16];
     const int n = dev_carrier_scan<true>(X.mbs, X.n_mb, s_cnt, &lo, &hi, &base);
     for (int xy = lo; xy < hi; xy++) {
@@ -426,24 +396,47 @@ static __global__ void __launch_bounds__(1024) k_extract_prepare(const ExtractDe
         }
         base += k;
     }
+    return n;
+}
+static __global__ void __launch_bounds__(1024) k_extract_prepare(const ExtractDev *__restrict__ Xs)
+{
+    const ExtractDev X = Xs[blockIdx.x];
+    __shared__ int s_cnt[1024];
+    __shared__ unsigned s_cols[2 * STC_MAXW];
+    const int t = threadIdx.x;
+    if (X.slice_status && *X.slice_status) {            /* (the whole workgroup: no barrier was reached) the slice did not parse: no bits */
+        if (t == 64) pcamv_extract_chain_slot(pcamv_stc_mats_dev, X.emrate, 1, X.rx != NULL, X.rx_cap_bits, X.hdr, s_cols, X.cols, X.pstate);
+        return;
+    }
+    const int n = dev_extract_carriers(X, s_cnt);
     if (t == 64) {
-        const int m = pcamv_stc_frame_bits(X.emrate, n);
-        const bool sched = m > 0 && m <= n;
-        const double invalpha = sched ? (double)n / m : 0.0;
-        const int shorter = (int)floor(invalpha), longer = (int)ceil(invalpha);
-        const int ok = sched && dev_stc_matrix(shorter, PCAMV_STC_HEIGHT, s_cols, X.pstate + PST_RX_LCG) &&
-                       dev_stc_matrix(longer, PCAMV_STC_HEIGHT, s_cols + STC_MAXW, X.pstate + PST_RX_LCG);
-        if (ok) {
-            for (int k = 0; k < shorter; k++) X.cols[k] = s_cols[k];
-            for (int k = 0; k < longer; k++) X.cols[STC_MAXW + k] = s_cols[STC_MAXW + k];
-        }
-        X.hdr[0] = n; X.hdr[1] = m; X.hdr[2] = ok;
-        const long long at = X.pstate[PST_RX];
-        *(long long *)(X.hdr + 6) = at;
-        if (X.rx) {
-            X.pstate[PST_RX] = at + m;
-            if (at + m > X.rx_cap_bits) X.pstate[PST_OVERRUN] = 1;
-        }
+        X.hdr[0] = n;
+        pcamv_extract_chain_slot(pcamv_stc_mats_dev, X.emrate, 0, X.rx != NULL, X.rx_cap_bits, X.hdr, s_cols, X.cols, X.pstate);
+    }
+}
+/* the window's first half, one workgroup per (context, slot): the slot's carriers and hdr[0] = n; a slot whose slice did not parse
+ * (or that took no unit) gets n = 0 and nothing else */
+static __global__ void __launch_bounds__(1024) k_extract_count(const ExtractDev *__restrict__ Xs)
+{
+    const ExtractDev X = Xs[blockIdx.x];
+    __shared__ int s_cnt[1024];
+    if (X.slice_status && *X.slice_status) {            /* (the whole workgroup: no barrier was reached) */
+        if (threadIdx.x == 64) X.hdr[0] = 0;
+        return;
+    }
+    const int n = dev_extract_carriers(X, s_cnt);
+    if (threadIdx.x == 64) X.hdr[0] = n;
+}
+/* the window's second half, one lane per context: the k slots of context i (Xs[i * k .. + k)) in slot order through
+ * pcamv_extract_chain_slot -- per slot a table copy or a short walk of the generator, so 64 contexts share a wave and nothing here
+ * is lane-parallel.  The columns are built where k_extract_bits reads them (a slot's own cols: LDS for 64 lanes' worth would be 128 KB) */
+static __global__ void __launch_bounds__(64) k_extract_chain(const ExtractDev *__restrict__ Xs, int n, int k)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    for (int w = 0; w < k; w++) {
+        const ExtractDev &X = Xs[(long long)i * k + w];
+        pcamv_extract_chain_slot(pcamv_stc_mats_dev, X.emrate, X.slice_status ? *X.slice_status : 0, X.rx != NULL, X.rx_cap_bits, X.hdr, X.cols, X.cols, X.pstate);
     }
 }
 

@@ -25,9 +25,10 @@
 #define NKEV 16                /* ... and a timer of the smaller kernels */
 enum { KT_ANALYSE, KT_EMBED_PREPARE, KT_EXTRACT_PREPARE, KT_EXTRACT_BITS, KT_PAYLOAD_CHECK, KT_PARSE_PSLICE, KT_PARSE_PSLICE_CAVLC, KT_WRITE_PSLICE, KT_WRITE_PSLICE_CAVLC, KT_NAL_TO_RBSP,
        KT_STREAM_PLAN, KT_STREAM_SCAN, KT_STREAM_PREFIX, KT_STREAM_PLACE, KT_STREAM_UNIT, KT_SLICE_HEADER, KT_STREAM_STATUS,
-       KT_STREAM_OPEN, KT_STREAM_SLOT, KT_STREAM_COMMIT, KT_N };
+       KT_STREAM_OPEN, KT_STREAM_SLOT, KT_STREAM_COMMIT, KT_STREAM_WINDOW_UNIT, KT_EXTRACT_COUNT, KT_EXTRACT_CHAIN, KT_N };
 #define PCAMV_FEATURES (PCAMV_FEATURE_PAYLOAD | PCAMV_FEATURE_SLICE_PARSER | PCAMV_FEATURE_SLICE_PARSER_CAVLC | PCAMV_FEATURE_SLICE_WRITER | \
-                        PCAMV_FEATURE_SLICE_WRITER_CAVLC | PCAMV_FEATURE_NAL_DEVICE | PCAMV_FEATURE_STREAM_DEVICE | PCAMV_FEATURE_STREAM_WRITER)
+                        PCAMV_FEATURE_SLICE_WRITER_CAVLC | PCAMV_FEATURE_NAL_DEVICE | PCAMV_FEATURE_STREAM_DEVICE | PCAMV_FEATURE_STREAM_WRITER | \
+                        PCAMV_FEATURE_STREAM_WINDOW)
 #define SLICE_GUARD_MBS 4       /* records behind a context's receive-side records that nothing may write (pcamv_gpu_debug_slice_records) */
 #define NSTAGE 2                /* staging buffers of extract_slices: a call waits for the one before the last */
 /* the stages of a step (batch_launch's `what`): plane production, analysis (search + RCA + encode), embedding, second pass */
@@ -86,6 +87,19 @@ struct StreamOut {
     uint8_t *d_head; size_t cap_head;
 };
 
+/* the slots of a window of slice units per context (pcamv_gpu_batch_stream_window): per context x slot what a step keeps per context --
+ * receive-side records with their guard, stego, hdr, cols, a status word, a row-scratch slot for wide pictures -- then the job arrays and
+ * RBSP slots of n * k jobs in one block, the copy of the cursors a launch reads, and NSTAGE sets of n * k descriptors taken in turn.
+ * Job i * k_call + w of a call is slot w of context i, and that job's memory is entry i * k_call + w of every array here */
+struct StreamWindow {
+    int k, k_last;              /* slots reserved per context; slots of the last window call */
+    pcamv_mb_t *d_mbs; uint8_t *d_stego; int *d_hdr; unsigned *d_cols; int *d_stat; uint8_t *d_scratch;
+    uint8_t *d_jobs; size_t cap_jobs;
+    long long *d_cursor_was;
+    ExtractDev *h_X, *d_X; hipEvent_t desc_done[NSTAGE]; int desc_used[NSTAGE], head;
+    hipEvent_t done; int used;  /* behind the last window call: the next one's stream waits for it, since they share the slots */
+};
+
 struct pcamv_ctx;
 /* A batch = the set of independent closed-GOP contexts whose frames advance together: every kernel
  * launch carries the same dependency step of all of them (descriptor arrays in device memory). */
@@ -116,6 +130,7 @@ struct pcamv_batch {
     /* ... handed byte streams: the index of every context's stream, and the job arrays and RBSP slots of a step, sized by index calls */
     StreamIndex sx;
     StageRing su_stage;
+    StreamWindow sw;
     /* sender to a stream (k_write_pslice, k_write_pslice_cavlc): the same of its own, and the staging of the callers' slice headers -- a
      * ring apart from the receiver's, since a write and a parse of one batch may be in flight on different streams */
     int *d_wstat; uint8_t *d_sw_tab, *d_sw_scratch;
@@ -151,6 +166,7 @@ struct pcamv_ctx {
      * by pcamv_gpu_rx_reserve / the first extraction); the cursors (PST_*) are E.pstate */
     uint8_t *d_payload_own; size_t payload_own_bytes;
     ExtractDev X; unsigned *d_rx; uint8_t *d_rx_bits; pcamv_mb_t *d_rx_mbs;
+    pcamv_batch *win; int win_i;    /* the batch whose window call parsed this context's last slices, and the context's place in it (else NULL) */
     int *d_trace;
     int8_t *d_flip_user;       /* pass 2 */
     uint8_t *d_mbflip;         /* [n_mb] per macroblock: a carrier of it is flipped in d_flip */
@@ -271,6 +287,15 @@ static void stream_index_free(StreamIndex &S)
     hipFree(S.d_at); hipFree(S.d_bad); hipFree(S.d_longest); hipFree(S.d_chunks); hipFree(S.d_table); hipFree(S.d_own);
     S = StreamIndex();
 }
+static void stream_window_free(StreamWindow &W)
+{
+    hipFree(W.d_mbs); hipFree(W.d_stego); hipFree(W.d_hdr); hipFree(W.d_cols); hipFree(W.d_stat); hipFree(W.d_scratch); hipFree(W.d_jobs);
+    hipFree(W.d_cursor_was); hipFree(W.d_X);
+    if (W.h_X) hipHostFree(W.h_X);
+    for (int r = 0; r < NSTAGE; r++) if (W.desc_done[r]) hipEventDestroy(W.desc_done[r]);
+    if (W.done) hipEventDestroy(W.done);
+    W = StreamWindow();
+}
 static void kt_destroy(KTimer &T) { for (int i = 0; i < NEV; i++) { if (T.e0[i]) hipEventDestroy(T.e0[i]); if (T.e1[i]) hipEventDestroy(T.e1[i]); } }
 
 extern "C" void pcamv_gpu_batch_destroy(pcamv_batch_t *b)
@@ -282,6 +307,7 @@ extern "C" void pcamv_gpu_batch_destroy(pcamv_batch_t *b)
         pcamv_ctx *c = b->ctx[i];
         if (!c) continue;
         if (c->last == b) c->last = NULL;
+        if (c->win == b) c->win = NULL;
         for (int k = 0; k < c->n_member; k++) if (c->member_of[k] == b) { c->member_of[k] = c->member_of[--c->n_member]; break; }
     }
     if (b->h_F) hipHostFree(b->h_F);
@@ -291,6 +317,7 @@ extern "C" void pcamv_gpu_batch_destroy(pcamv_batch_t *b)
     hipFree(b->d_sstat); hipFree(b->d_sp_tab); hipFree(b->d_sp_scratch);
     stage_destroy(b->rx_stage); stage_destroy(b->nal_stage); stage_destroy(b->su_stage);
     stream_index_free(b->sx);
+    stream_window_free(b->sw);
     hipFree(b->d_wstat); hipFree(b->d_sw_tab); hipFree(b->d_sw_scratch);
     stage_destroy(b->tx_stage);
     hipFree(b->so.d_own); hipFree(b->so.d_head);
@@ -437,7 +464,8 @@ static const char *kt_name(const pcamv_batch *b, int k)      /* what pcamv_gpu_b
 {
     static const char *const small[KT_N] = {NULL, "k_embed_prepare", "k_extract_prepare", "k_extract_bits", "k_payload_check", "k_parse_pslice", "k_parse_pslice_cavlc", "k_write_pslice",
                                             "k_write_pslice_cavlc", "k_nal_to_rbsp", "k_stream_plan", "k_stream_scan", "k_stream_prefix", "k_stream_place", "k_stream_unit",
-                                            "k_slice_header", "k_stream_status", "k_stream_open", "k_stream_slot", "k_stream_commit"};
+                                            "k_slice_header", "k_stream_status", "k_stream_open", "k_stream_slot", "k_stream_commit",
+                                            "k_stream_window_unit", "k_extract_count", "k_extract_chain"};
     return k == KT_ANALYSE ? dominant_kernel(b) : small[k];
 }
 extern "C" int pcamv_gpu_batch_copy_results_async(pcamv_batch_t *b, void *dst_mb, size_t mb_stride, void *dst_flip, size_t flip_stride, void *stream)
@@ -1163,20 +1191,26 @@ extern "C" int pcamv_gpu_rx_fetch(pcamv_ctx_t *c, uint8_t *bytes, int64_t n_bits
     return 0;
 }
 
-/* the two kernels of the receiving side for nx frames whose descriptors are at dX; emrate bounds the message bits of a frame */
-static void extract_launch(pcamv_batch *b, const ExtractDev *dX, int nx, int cap, float emrate, hipStream_t st)
+/* k_extract_bits for nx frames whose descriptors are at dX; emrate bounds the message bits of a frame */
+static void extract_bits_launch(pcamv_batch *b, const ExtractDev *dX, int nx, int cap, float emrate, hipStream_t st)
 {
-    int ev = kt_begin(b, KT_EXTRACT_PREPARE, st);
-    hipLaunchKernelGGL(k_extract_prepare, dim3(nx), dim3(1024), 0, st, dX);
-    kt_end(b, KT_EXTRACT_PREPARE, ev, st);
     /* workgroups per frame: enough for the most bits a frame of this rate can hold (+ the 63 positions in front of a frame's first
      * bit); the kernel strides if a frame has more (it cannot) */
     double most = emrate > 1.0f ? (double)(int)emrate : ceil((double)emrate * cap) + 1;
     if (most > cap) most = cap;
     const int groups = (int)((most + 63 + 255) / 256) > 0 ? (int)((most + 63 + 255) / 256) : 1;
-    ev = kt_begin(b, KT_EXTRACT_BITS, st);
-    hipLaunchKernelGGL(k_extract_bits, dim3(groups, nx), dim3(256), 0, st, dX);
+    const int ev = kt_begin(b, KT_EXTRACT_BITS, st);
+    for (int x0 = 0; x0 < nx; x0 += 65535)         /* (a grid's second dimension ends there: a window of many contexts has more frames) */
+        hipLaunchKernelGGL(k_extract_bits, dim3(groups, nx - x0 < 65535 ? nx - x0 : 65535), dim3(256), 0, st, dX + x0);
     kt_end(b, KT_EXTRACT_BITS, ev, st);
+}
+/* the two kernels of the receiving side for nx frames */
+static void extract_launch(pcamv_batch *b, const ExtractDev *dX, int nx, int cap, float emrate, hipStream_t st)
+{
+    const int ev = kt_begin(b, KT_EXTRACT_PREPARE, st);
+    hipLaunchKernelGGL(k_extract_prepare, dim3(nx), dim3(1024), 0, st, dX);
+    kt_end(b, KT_EXTRACT_PREPARE, ev, st);
+    extract_bits_launch(b, dX, nx, cap, emrate, st);
 }
 /* descriptors of the batch's contexts as they stand, into the next slot of the receiving side's ring */
 static int batch_push_xdescs(pcamv_batch *b, hipStream_t st, const ExtractDev **dX, int *slot_out)
@@ -1307,18 +1341,21 @@ static int slice_contexts(pcamv_batch *b, int want_rx, float emrate)
         pcamv_ctx *c = b->ctx[i];
         TRY(rx_scratch(c)); TRY(rx_mbs(c));
         c->X.mbs = c->d_rx_mbs; c->X.flip = NULL; c->X.bits = NULL; c->X.emrate = emrate; c->X.slice_status = b->d_sstat + i;
+        c->win = NULL;
     }
     return 0;
 }
-static void slice_launch(pcamv_batch *b, const ExtractDev *dX, SliceJobs J, int cavlc, hipStream_t st)
+/* (a window: `jobs` slices with the window's own scratch rows instead of one per context with the batch's) */
+static void slice_launch(pcamv_batch *b, const ExtractDev *dX, SliceJobs J, int cavlc, hipStream_t st, int jobs = 0, uint8_t *scratch = NULL)
 {
     const FrameDev &F = b->ctx[0]->F;
     const int kt = cavlc ? KT_PARSE_PSLICE_CAVLC : KT_PARSE_PSLICE;
-    J.tab = b->d_sp_tab; J.scratch = b->d_sp_scratch; J.scratch_stride = (long long)row_bytes(b, cavlc);
+    if (!jobs) { jobs = b->n; scratch = b->d_sp_scratch; }
+    J.tab = b->d_sp_tab; J.scratch = scratch; J.scratch_stride = (long long)row_bytes(b, cavlc);
     J.mb_w = F.mb_w; J.mb_h = F.mb_h; J.lds_cols = b->sp_lds_cols;
     const int ev = kt_begin(b, kt, st);
-    if (cavlc) hipLaunchKernelGGL(k_parse_pslice_cavlc, dim3(b->n), dim3(64), 0, st, dX, J);
-    else hipLaunchKernelGGL(k_parse_pslice, dim3(b->n), dim3(64), 0, st, dX, J);
+    if (cavlc) hipLaunchKernelGGL(k_parse_pslice_cavlc, dim3(jobs), dim3(64), 0, st, dX, J);
+    else hipLaunchKernelGGL(k_parse_pslice, dim3(jobs), dim3(64), 0, st, dX, J);
     kt_end(b, kt, ev, st);
 }
 /* parse (slices described by J, one per context) and, with extract != 0, the receiver's kernels behind it, all on `st` */
@@ -1576,6 +1613,14 @@ static int stream_index_checked(pcamv_batch *b, const void *bytes, size_t bytes_
     HIPCHK(b, hipSetDevice(b->device));
     return batch_live(b);
 }
+/* the job arrays and RBSP slots of a window of sw.k units per context, sized like a step's for n * k jobs; grown, never shrunk, and only
+ * where the device is idle (an index call behind its synchronisation, stream_window) */
+static int window_jobs_room(pcamv_batch *b)
+{
+    StreamWindow &W = b->sw;
+    const size_t jobs = (size_t)b->n * (size_t)W.k;
+    return grow(b, &W.d_jobs, &W.cap_jobs, stream_step_hdr((int)jobs) + jobs * (size_t)b->sx.slot);
+}
 /* behind the kernels: the one synchronisation of an index call, the counts to the host, the RBSP slots of the steps to come */
 static int stream_index_finish(pcamv_batch *b, const uint8_t *d_bytes, size_t bytes_size, int64_t *n_slices_out)
 {
@@ -1596,7 +1641,7 @@ static int stream_index_finish(pcamv_batch *b, const uint8_t *d_bytes, size_t by
             R.cap[k] = total;
         }
     S.bytes = d_bytes; S.bytes_size = (long long)bytes_size; S.ready = 1;
-    return 0;
+    return b->sw.k ? window_jobs_room(b) : 0;       /* (a window reserved earlier: its RBSP slots follow, as the steps' do) */
 }
 extern "C" int pcamv_gpu_batch_index_streams_device(pcamv_batch_t *b, const void *bytes, size_t bytes_size, const int64_t *off, const int64_t *len,
                                                     int64_t max_units, int64_t *n_slices_out, void *stream)
@@ -1668,10 +1713,130 @@ extern "C" int pcamv_gpu_batch_extract_stream_step(pcamv_batch_t *b, const pcamv
     const int rc = slices_run(b, SJ, cavlc, 1, emrate, st);
     /* the parser refused what an earlier stage had failed (len -1) with its own code: the first stage's code takes its place */
     ev = kt_begin(b, KT_STREAM_STATUS, st);
-    hipLaunchKernelGGL(k_stream_status, dim3((b->n + 63) / 64), dim3(64), 0, st, J.first, b->d_sstat, b->n);
+    hipLaunchKernelGGL(k_stream_status, dim3((b->n + 63) / 64), dim3(64), 0, st, J.first, b->d_sstat, b->n, (int *)NULL, 0);
     kt_end(b, KT_STREAM_STATUS, ev, st);
     const int rc1 = launched(b), rc2 = stage_release(b, b->su_stage, k, st);        /* released on every path */
     return rc ? rc : rc1 ? rc1 : rc2;
+}
+/* ---- a window of slice units per context in one launch (k_stream_window_unit, k_extract_count, k_extract_chain) */
+extern "C" int pcamv_gpu_batch_stream_window(pcamv_batch_t *b, int k)
+{
+    if (!b || k < 0 || k > PCAMV_STREAM_WINDOW_MAX) return fail(b, PCAMV_EINVAL, "a window holds 1 to %d units per context (0 releases it)", PCAMV_STREAM_WINDOW_MAX);
+    HIPCHK(b, hipSetDevice(b->device));
+    TRY(batch_live(b));
+    HIPCHK(b, hipDeviceSynchronize());
+    StreamWindow &W = b->sw;
+    stream_window_free(W);
+    for (int i = 0; i < b->n; i++) if (b->ctx[i]->win == b) b->ctx[i]->win = NULL;
+    if (!k) return 0;
+    if (!b->sx.ready) return fail(b, PCAMV_EINVAL, "no byte streams were handed to this batch yet (pcamv_gpu_batch_index_streams*): a window is reserved behind an index call");
+    const FrameDev &F = b->ctx[0]->F;
+    const int cavlc = !F.b_cabac, cap = b->ctx[0]->cap;
+    TRY(entropy_setup(b, &b->d_sstat, &b->d_sp_tab, &b->d_sp_scratch, cavlc, SP_NCTX));
+    for (int i = 0; i < b->n; i++) {            /* what the first slice call of a context makes: here, so that the window call finds it */
+        pcamv_ctx *c = b->ctx[i];
+        int rc_c = rx_scratch(c);
+        if (!rc_c) rc_c = rx_mbs(c);
+        if (rc_c) return fail(b, rc_c, "context %d: %s", i, c->err);
+    }
+    const size_t jobs = (size_t)b->n * (size_t)k, rec = (size_t)F.n_mb + SLICE_GUARD_MBS;
+    W.k = k;
+    int rc = 0;
+    hipError_t e = dalloc(&W.d_mbs, jobs * rec);
+    if (e == hipSuccess) e = dalloc(&W.d_stego, jobs * (size_t)cap);
+    if (e == hipSuccess) e = dalloc(&W.d_hdr, jobs * 8);
+    if (e == hipSuccess) e = dalloc(&W.d_cols, jobs * 2 * STC_MAXW);
+    if (e == hipSuccess) e = dalloc(&W.d_stat, jobs);
+    if (e == hipSuccess && F.mb_w > b->sp_lds_cols) e = dalloc(&W.d_scratch, jobs * row_bytes(b, cavlc));
+    if (e == hipSuccess) e = dalloc(&W.d_cursor_was, (size_t)b->n);
+    if (e == hipSuccess) e = dalloc(&W.d_X, jobs * NSTAGE);
+    if (e == hipSuccess) e = hipHostMalloc((void **)&W.h_X, sizeof(ExtractDev) * jobs * NSTAGE, hipHostMallocDefault);
+    for (int r = 0; r < NSTAGE && e == hipSuccess; r++) e = hipEventCreateWithFlags(&W.desc_done[r], hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&W.done, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipMemset(W.d_hdr, 0, jobs * 8 * sizeof(int));
+    if (e == hipSuccess) e = hipMemset(W.d_stat, 0, jobs * sizeof(int));
+    /* the guard behind every slot's records, as rx_mbs leaves it behind a context's */
+    if (e == hipSuccess) e = hipMemset2D(W.d_mbs + F.n_mb, rec * sizeof(pcamv_mb_t), 0xA5, SLICE_GUARD_MBS * sizeof(pcamv_mb_t), jobs);
+    if (e == hipSuccess) rc = window_jobs_room(b);
+    if (e != hipSuccess) rc = fail(b, e == hipErrorOutOfMemory ? PCAMV_ENOMEM : PCAMV_EHIP, "a window of %d units for %d contexts: %s", k, b->n, hipGetErrorString(e));
+    if (rc) stream_window_free(W);
+    return rc;
+}
+extern "C" int pcamv_gpu_batch_extract_stream_window(pcamv_batch_t *b, const pcamv_stream_params_t *params, float emrate, int k, int32_t *nal_header, void *stream)
+{
+    if (!b || !params) return PCAMV_EINVAL;
+    const int cavlc = !params->entropy_cabac;
+    TRY(slices_checked(b, emrate, 1, cavlc));
+    StreamIndex &S = b->sx;
+    StreamWindow &W = b->sw;
+    if (!S.ready) return fail(b, PCAMV_EINVAL, "no byte streams were handed to this batch yet (pcamv_gpu_batch_index_streams*)");
+    if (!W.k) return fail(b, PCAMV_EINVAL, "no window was reserved for this batch (pcamv_gpu_batch_stream_window)");
+    if (k < 1 || k > W.k) return fail(b, PCAMV_EINVAL, "a window of %d units: 1 to the %d reserved", k, W.k);
+    hipStream_t st = stream ? (hipStream_t)stream : b->ctx[0]->stream;
+    const FrameDev &F = b->ctx[0]->F;
+    const size_t n = (size_t)b->n, jobs = n * (size_t)k, hdr = stream_step_hdr((int)jobs), rec = (size_t)F.n_mb + SLICE_GUARD_MBS;
+    const int cap = b->ctx[0]->cap;
+    if (hdr + jobs * (size_t)S.slot > W.cap_jobs) return fail(b, PCAMV_EHIP, "the window's RBSP slots were not sized by the last index call");
+    if (W.used) HIPCHK(b, hipStreamWaitEvent(st, W.done, 0));           /* the call before this one read and wrote the same slots, perhaps on another stream */
+    const int r = W.head;
+    W.head = (r + 1) % NSTAGE;
+    if (W.desc_used[r]) HIPCHK(b, hipEventSynchronize(W.desc_done[r]));  /* (as a step's descriptor ring: the call before the last) */
+    ExtractDev *hX = W.h_X + (size_t)r * n * (size_t)W.k, *dX = W.d_X + (size_t)r * n * (size_t)W.k;
+    for (size_t i = 0; i < n; i++)
+        for (size_t w = 0; w < (size_t)k; w++) {
+            const size_t j = i * (size_t)k + w;
+            ExtractDev &X = hX[j];
+            X = b->ctx[i]->X;
+            X.mbs = W.d_mbs + j * rec; X.stego = W.d_stego + j * (size_t)cap; X.hdr = W.d_hdr + j * 8; X.cols = W.d_cols + j * 2 * STC_MAXW;
+            X.slice_status = W.d_stat + j;
+        }
+    HIPCHK(b, hipMemcpyAsync(dX, hX, sizeof(ExtractDev) * jobs, hipMemcpyHostToDevice, st));
+    HIPCHK(b, hipEventRecord(W.desc_done[r], st));
+    W.desc_used[r] = 1;
+    HIPCHK(b, hipMemcpyAsync(W.d_cursor_was, S.d_at + 5 * n, 8 * n, hipMemcpyDeviceToDevice, st));
+    uint8_t *d = W.d_jobs;
+    StreamStep J;
+    J.bytes = S.bytes; J.bytes_size = S.bytes_size; J.soff = S.d_at; J.slen = S.d_at + n; J.bad = S.d_bad;
+    J.table = S.d_table; J.max_units = S.max_units; J.stride = S.stride; J.n_slices = S.d_at + 4 * n; J.cursor = S.d_at + 5 * n;
+    J.rbsp = d + hdr; J.slot = S.slot; J.rbsp_size = (long long)jobs * S.slot;
+    J.off = (long long *)d; J.len = J.off + jobs; J.start_bit = J.len + jobs;
+    J.qp = (int *)(J.start_bit + jobs); J.first = J.qp + jobs; J.frame_num = J.first + jobs; J.nal_header = nal_header ? nal_header : J.frame_num + jobs;
+    J.P = *params; J.n = (int)jobs; J.cursor_was = W.d_cursor_was; J.k = k;
+    int ev = kt_begin(b, KT_STREAM_WINDOW_UNIT, st);
+    hipLaunchKernelGGL(k_stream_window_unit, dim3((unsigned)jobs), dim3(64), 0, st, J);
+    kt_end(b, KT_STREAM_WINDOW_UNIT, ev, st);
+    ev = kt_begin(b, KT_SLICE_HEADER, st);
+    hipLaunchKernelGGL(k_slice_header, dim3((unsigned)((jobs + 63) / 64)), dim3(64), 0, st, J);
+    kt_end(b, KT_SLICE_HEADER, ev, st);
+    SliceJobs SJ;
+    SJ.bytes = J.rbsp; SJ.bytes_size = J.rbsp_size; SJ.off = J.off; SJ.len = J.len; SJ.start_bit = J.start_bit; SJ.qp = cavlc ? NULL : J.qp;
+    slice_launch(b, dX, SJ, cavlc, st, (int)jobs, W.d_scratch);
+    ev = kt_begin(b, KT_EXTRACT_COUNT, st);
+    hipLaunchKernelGGL(k_extract_count, dim3((unsigned)jobs), dim3(1024), 0, st, dX);
+    kt_end(b, KT_EXTRACT_COUNT, ev, st);
+    ev = kt_begin(b, KT_EXTRACT_CHAIN, st);
+    hipLaunchKernelGGL(k_extract_chain, dim3((b->n + 63) / 64), dim3(64), 0, st, dX, b->n, k);
+    kt_end(b, KT_EXTRACT_CHAIN, ev, st);
+    extract_bits_launch(b, dX, (int)jobs, cap, emrate, st);
+    ev = kt_begin(b, KT_STREAM_STATUS, st);
+    hipLaunchKernelGGL(k_stream_status, dim3((unsigned)((jobs + 63) / 64)), dim3(64), 0, st, J.first, W.d_stat, (int)jobs, b->d_sstat, k);
+    kt_end(b, KT_STREAM_STATUS, ev, st);
+    W.k_last = k;
+    for (int i = 0; i < b->n; i++) { b->ctx[i]->win = b; b->ctx[i]->win_i = i; }
+    const int rc = launched(b);
+    HIPCHK(b, hipEventRecord(W.desc_done[r], st));          /* the descriptors are read until here */
+    HIPCHK(b, hipEventRecord(W.done, st));
+    W.used = 1;
+    return rc;
+}
+extern "C" int pcamv_gpu_batch_window_status(pcamv_batch_t *b, int32_t *status)
+{
+    if (!b || !status) return PCAMV_EINVAL;
+    HIPCHK(b, hipSetDevice(b->device));
+    if (!b->sw.k || !b->sw.k_last) return fail(b, PCAMV_EINVAL, "no window call was made on this batch yet");
+    HIPCHK(b, hipDeviceSynchronize());
+    HIPCHK(b, hipMemcpy(status, b->sw.d_stat, sizeof(int32_t) * (size_t)b->n * (size_t)b->sw.k_last, hipMemcpyDeviceToHost));
+    return 0;
 }
 extern "C" int pcamv_gpu_batch_stream_tell(pcamv_batch_t *b, int64_t *next, int64_t *total)
 {
@@ -1752,10 +1917,19 @@ extern "C" int pcamv_gpu_debug_slice_records(pcamv_ctx_t *c, pcamv_mb_t *out_mb,
     if (!c || !out_mb || !c->d_rx_mbs) return PCAMV_EINVAL;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipDeviceSynchronize());
-    HIPCHK(c, hipMemcpy(out_mb, c->d_rx_mbs, (size_t)c->F.n_mb * sizeof(pcamv_mb_t), hipMemcpyDeviceToHost));
+    const pcamv_mb_t *mbs = c->d_rx_mbs;
+    if (c->win && c->win->sw.k_last) {          /* behind a window call: the records of the last slot that took a unit, as its steps would have left them */
+        const pcamv_batch *b = c->win;
+        long long was = 0, now = 0;
+        HIPCHK(c, hipMemcpy(&was, b->sw.d_cursor_was + c->win_i, 8, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(&now, b->sx.d_at + 5 * (size_t)b->sx.n + c->win_i, 8, hipMemcpyDeviceToHost));
+        if (now > was && now - was <= b->sw.k_last)
+            mbs = b->sw.d_mbs + ((size_t)c->win_i * (size_t)b->sw.k_last + (size_t)(now - was - 1)) * ((size_t)c->F.n_mb + SLICE_GUARD_MBS);
+    }
+    HIPCHK(c, hipMemcpy(out_mb, mbs, (size_t)c->F.n_mb * sizeof(pcamv_mb_t), hipMemcpyDeviceToHost));
     if (guard_intact) {
         uint8_t g[SLICE_GUARD_MBS * sizeof(pcamv_mb_t)];
-        HIPCHK(c, hipMemcpy(g, c->d_rx_mbs + c->F.n_mb, sizeof(g), hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(g, mbs + c->F.n_mb, sizeof(g), hipMemcpyDeviceToHost));
         *guard_intact = 1;
         for (size_t i = 0; i < sizeof(g); i++) if (g[i] != 0xA5) *guard_intact = 0;
     }

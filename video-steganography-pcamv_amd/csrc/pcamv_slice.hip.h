@@ -22,7 +22,8 @@
  * k_stream_plan, k_stream_scan, k_stream_prefix, k_stream_place cut every context's Annex B byte stream into its NAL units, a wavefront
  * per chunk of a stream (pcamv_stream_index.h); k_stream_unit then takes one slice unit per context and call from the table and
  * unescapes it with k_nal_to_rbsp's control code, k_slice_header reads its slice header, one lane per context, into the job arrays the
- * parsers read, and k_stream_status puts the code of the first stage that failed where the parser put its own.
+ * parsers read, and k_stream_status puts the code of the first stage that failed where the parser put its own.  k_stream_window_unit
+ * takes a window of units per context instead, one wavefront per unit, for the same kernels over contexts x slots jobs.
  *
  * k_write_pslice (pcamv_slice_write.hip) is the other direction: a CABAC P slice of every context's last step written on the device, one
  * wavefront per slice (pcamv_slice_write.h, which also describes a launch: WriteJobs).
@@ -216,6 +217,9 @@ struct StreamStep {
     long long *off, *len, *start_bit; int *qp, *first, *nal_header, *frame_num;
     pcamv_stream_params_t P;
     int n;
+    /* a window of k units per context (k_stream_window_unit): the job arrays hold n * k entries, context-major (job i * k + w), `n` counts
+     * jobs, and cursor_was is a copy of the cursors made before the launch -- what the slot waves read, while one lane moves `cursor` */
+    const long long *cursor_was; int k;
 };
 static __global__ void __launch_bounds__(64) k_stream_unit(const StreamStep J)
 {
@@ -240,6 +244,32 @@ static __global__ void __launch_bounds__(64) k_stream_unit(const StreamStep J)
         J.off[i] = (long long)i * J.slot; J.first[i] = rc; J.start_bit[i] = 0; J.qp[i] = 0; J.frame_num[i] = -1;
     }
 }
+/* the same for slot w of context i, job j = i * k + w of a launch of n contexts x k slots: the unit at cursor + w into the job's own RBSP
+ * slot.  Slots beyond the table's end take nothing (PCAMV_EEOF); the wave of slot 0 moves the context's cursor over the slots that took
+ * a unit.  No wave waits on another: every wave reads the cursor's copy, which no kernel of the launch writes */
+static __global__ void __launch_bounds__(64) k_stream_window_unit(const StreamStep J)
+{
+    __shared__ uint32_t s_win[NU_WIN_DWORDS], s_out[NU_OUT_DWORDS];
+    const int j = blockIdx.x, i = j / J.k, w = j - i * J.k, lane = threadIdx.x;
+    const NuWork W = {s_win, s_out};
+    const long long was = J.cursor_was[i], cur = was + w, total = J.bad[i] ? 0 : J.n_slices[i], have = total < J.max_units ? total : J.max_units;
+    int rc = J.bad[i] ? PCAMV_EINVAL : PCAMV_EEOF, done = 0;
+    if (was >= 0 && cur < have) {
+        const pcamv_unit_t u = J.table[(long long)i * J.stride + cur];
+        const long long soff = J.soff[i], slen = J.slen[i];
+        rc = u.kind == PCAMV_UNIT_PSLICE ? PCAMV_EINVAL : PCAMV_EUNSUP;
+        if (u.kind == PCAMV_UNIT_PSLICE && u.off >= 0 && u.len >= 0 && u.len <= slen && u.off <= slen - u.len && u.len <= J.slot + 1 && soff >= 0 &&
+            slen <= J.bytes_size && soff <= J.bytes_size - slen) {
+            rc = pcamv_nal_unescape(W, J.bytes + soff + u.off, u.len, J.rbsp + (long long)j * J.slot, J.len + j, J.nal_header + j);
+            done = 1;
+        }
+    }
+    if (lane == 0) {
+        if (w == 0 && was >= 0 && was < have) J.cursor[i] = was + (have - was < J.k ? have - was : J.k);
+        if (!done) { J.len[j] = -1; J.nal_header[j] = -1; }
+        J.off[j] = (long long)j * J.slot; J.first[j] = rc; J.start_bit[j] = 0; J.qp[j] = 0; J.frame_num[j] = -1;
+    }
+}
 /* one lane per slice: the header of RBSP i (bytes[off[i] .. + len[i]) of the buffer the parser will read) */
 static __global__ void __launch_bounds__(64) k_slice_header(const StreamStep J)
 {
@@ -251,10 +281,13 @@ static __global__ void __launch_bounds__(64) k_slice_header(const StreamStep J)
     J.start_bit[i] = sb; J.qp[i] = qp; J.frame_num[i] = fn;
     if (rc) { J.first[i] = rc; J.len[i] = -1; }         /* as the unescaper marks a unit that failed: the parser refuses it */
 }
-static __global__ void __launch_bounds__(64) k_stream_status(const int *__restrict__ first, int *__restrict__ status, int n)
+/* (a window, k > 0: job i is slot i % k of context i / k, and the last slot's code is also the context's own word -- what k steps leave) */
+static __global__ void __launch_bounds__(64) k_stream_status(const int *__restrict__ first, int *__restrict__ status, int n, int *__restrict__ ctx_status, int k)
 {
     const int i = blockIdx.x * 64 + threadIdx.x;
-    if (i < n && first[i]) status[i] = first[i];
+    if (i >= n) return;
+    if (first[i]) status[i] = first[i];
+    if (k > 0 && i % k == k - 1) ctx_status[i / k] = status[i];
 }
 
 /* ---- the sender's byte streams (pcamv_stream_write.h), one lane per context.  ctx, table, slot, w_len are the library's; bytes and len

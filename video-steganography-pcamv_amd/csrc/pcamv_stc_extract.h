@@ -1,9 +1,9 @@
 /*
  * pcamv_stc_extract.h -- the receiving side of the syndrome-trellis code, one message bit at a time.
  *
- * Compiles for the device (k_extract_prepare / k_extract_bits, and the message length k_embed_prepare shares with them), for the host
- * side of the library (the column generator of pcamv_gpu_stc_extract_lcg) and for a plain C++ test driver
- * (tests/emu/stc_extract_driver.cpp): no HIP type, no table of its own.
+ * Compiles for the device (k_extract_prepare / k_extract_chain / k_extract_bits, and the message length and matrix builder
+ * k_embed_prepare shares with them), for the host side of the library (the column generator of pcamv_gpu_stc_extract_lcg) and for
+ * plain C++ test programs (tests/emu/stc_extract_driver.cpp, tests/fuzz/check_extract_window.cpp): no HIP type, no table of its own.
  *
  * The extractor of embed.h:340-393 is H * y over GF(2) with H made of two sub-matrices laid along the diagonal: message bit i owns
  * `width(i)` columns starting at column before(i) of the stego vector, and column k of that block reaches the message bits
@@ -76,8 +76,71 @@ PCAMV_HD void pcamv_stc_window(int j0, int j1, int n, int m, double invalpha, in
 /* packed payloads: 8 bits per byte, most significant bit first */
 PCAMV_HD unsigned pcamv_packed_bit(const uint8_t *bytes, long long i) { return (bytes[i >> 3] >> (7 - (int)(i & 7))) & 1u; }
 
-/* host side: sub-matrix columns as the embedder gets them (embed.h:141-199): the published tables for widths 2..20 (`table` = pcamv_stc_mats,
- * stc_mats.h), columns drawn from the code's own LCG (embed.h:134-139) outside that range */
+/* Sub-matrix columns as the embedding and the receiving kernels get them (embed.h:141-199): the published tables for widths 2..20
+ * (`table`: pcamv_stc_mats_dev on the device, pcamv_stc_mats on the host; stc_mats.h), columns drawn from the code's own LCG
+ * (embed.h:134-139) outside that range; 0, and the generator left where it was, for a width the height has no columns for */
+PCAMV_HD int pcamv_stc_matrix(const unsigned *table, int width, int height, unsigned *cols, long long *lcg)
+{
+    if (width >= 2 && width <= 20 && height >= 7 && height <= 12) {
+        for (int i = 0; i < width; i++) cols[i] = table[(height - 7) * 400 + (width - 1) * 20 + i];
+        return 1;
+    }
+    if ((1 << (height - 2)) < width) return 0;
+    unsigned mask = (1u << (height - 2)) - 1, bop = (1u << (height - 1)) + 1;
+    long hold = (long)*lcg;
+    for (int i = 0; i < width; i++) {
+        unsigned r = 0; int j;
+        for (j = -1; j < i;) {
+            hold = (long)((unsigned long)hold * 214013UL + 2531011UL);      /* (the reference's `long` product, wrapping as it does there) */
+            r = (((unsigned)(hold >> 16) & 0x7fff & mask) << 1) + bop;
+            for (j = 0; j < i; j++) if (cols[j] == r) break;
+        }
+        cols[i] = r;
+    }
+    *lcg = hold;
+    return 1;
+}
+
+/* per-context words of the payload path (device memory; the host check of the receive-side chain keeps the same four) */
+enum { PST_TX = 0,            /* payload bits the sender has consumed */
+       PST_RX = 1,            /* bits appended to the received stream */
+       PST_OVERRUN = 2,       /* != 0: a frame did not fit the reserved received buffer (its tail was dropped, never written) */
+       PST_RX_LCG = 3,        /* the receiver's own STC column generator (embed.h:134), started like the sender's */
+       PST_WORDS = 4 };
+
+/* What chains from frame to frame on the receiving side, for one frame whose carrier count is known (hdr[0] = n): the frame's m, the
+ * two sub-matrices from the receiver's column generator (shorter then longer, as the host extractor calls them), and the frame's
+ * place in the received stream.  The write cursor moves by m whatever the frame turns out to be, so that the offsets of sender and
+ * receiver stay aligned (m > n, or no matrix for the width: m zero bits -- the stream is zeroed when reserved, so nothing is
+ * written for them).  status != 0 (the frame's slice did not parse): no bits, cursor and generator stay, hdr[0] is not read.
+ * Thread 64 of k_extract_prepare runs this for its one frame, a lane of k_extract_chain for the slots of a window in slot order.
+ * `work` is where the columns are built (the generator compares every new column with all earlier ones: LDS where the caller has
+ * some), `cols` where they go once both sub-matrices stand; the two may be the same array.
+ * hdr: [0]=n [1]=m [2]=sub-matrices built [6..7]=bit offset of the frame in the received stream, low word first */
+PCAMV_HD void pcamv_extract_chain_slot(const unsigned *table, float emrate, int status, int have_rx, long long rx_cap_bits, int *hdr,
+                                       unsigned *work, unsigned *cols, long long *pstate)
+{
+    const long long at = pstate[PST_RX];
+    hdr[6] = (int)(unsigned)((unsigned long long)at & 0xffffffffu); hdr[7] = (int)(unsigned)((unsigned long long)at >> 32);
+    if (status) { hdr[0] = 0; hdr[1] = 0; hdr[2] = 0; return; }
+    const int n = hdr[0], m = pcamv_stc_frame_bits(emrate, n);
+    const bool sched = m > 0 && m <= n;
+    const double invalpha = sched ? (double)n / m : 0.0;
+    const int shorter = (int)floor(invalpha), longer = (int)ceil(invalpha);
+    const int ok = sched && pcamv_stc_matrix(table, shorter, PCAMV_STC_HEIGHT, work, pstate + PST_RX_LCG) &&
+                   pcamv_stc_matrix(table, longer, PCAMV_STC_HEIGHT, work + STC_MAXW, pstate + PST_RX_LCG);
+    if (ok && work != cols) {
+        for (int k = 0; k < shorter; k++) cols[k] = work[k];
+        for (int k = 0; k < longer; k++) cols[STC_MAXW + k] = work[STC_MAXW + k];
+    }
+    hdr[1] = m; hdr[2] = ok;
+    if (have_rx) {
+        pstate[PST_RX] = at + m;
+        if (at + m > rx_cap_bits) pstate[PST_OVERRUN] = 1;
+    }
+}
+
+/* host side: the same columns with the widths checked against STC_MAXW (a caller's array) */
 static inline int pcamv_stc_matrix_host(const unsigned *table, int width, int height, unsigned *cols, long long *lcg)
 {
     if (width >= 2 && width <= 20 && height >= 7 && height <= 12) {
@@ -90,7 +153,7 @@ static inline int pcamv_stc_matrix_host(const unsigned *table, int width, int he
     for (int i = 0; i < width; i++) {
         unsigned r = 0; int j;
         for (j = -1; j < i;) {
-            hold = hold * 214013L + 2531011L;
+            hold = (long)((unsigned long)hold * 214013UL + 2531011UL);      /* (the reference's `long` product, wrapping as it does there) */
             r = (((unsigned)(hold >> 16) & 0x7fff & mask) << 1) + bop;
             for (j = 0; j < i; j++) if (cols[j] == r) break;
         }

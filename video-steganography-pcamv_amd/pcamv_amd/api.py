@@ -344,6 +344,8 @@ def parse_slice_header(rbsp, nal_header, params):
 
 
 FEATURE_STREAM_WRITER = 0x80    # the sender writes Annex B byte streams: Batch.stream_open, Batch.write_stream_step, write_slice_header
+FEATURE_STREAM_WINDOW = 0x100   # a window of slice units per context in one call: Batch.stream_window, Batch.extract_stream_window
+STREAM_WINDOW_MAX = 64          # PCAMV_STREAM_WINDOW_MAX
 SLICE_HDR_MAX_BITS = 215        # PCAMV_SLICE_HDR_MAX_BITS
 SLICE_HDR_BYTES = 28            # PCAMV_SLICE_HDR_BYTES: a header's slot in the output of Encoder.slice_headers_write_device
 
@@ -953,6 +955,35 @@ class Batch:
         fn.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
         self._slice_chk(fn(self.b, C.byref(params), emrate, nal_header.data_ptr() if nal_header is not None else None, C.c_void_p(stream or None)),
                         "batch_extract_stream_step")
+
+    def stream_window(self, k):
+        """pcamv_gpu_batch_stream_window: reserve the per-slot memory of windows of up to k units per context (1 .. STREAM_WINDOW_MAX;
+        0 releases it), behind an index call.  k times the memory of the step path; synchronises and allocates"""
+        fn = self.lib.pcamv_gpu_batch_stream_window
+        fn.argtypes = [C.c_void_p, C.c_int]
+        self._slice_chk(fn(self.b, int(k)), "batch_stream_window")
+
+    def extract_stream_window(self, params, emrate, k, nal_header=None, stream=0):
+        """pcamv_gpu_batch_extract_stream_window: the next k slice units of every context's indexed stream in one call -- observationally
+        k extract_stream_step calls, with one launch of each kernel over contexts x slots.  window_status() afterwards gives every
+        slot's code (EEOF where the stream had no further unit; the cursor moves by the slots that took one), slice_status() the last
+        slot's.  nal_header (optional): int32 device tensor of n * k entries, context-major, receiving each unit's header byte"""
+        if nal_header is not None and (not _is_device_tensor(nal_header) or not nal_header.is_cuda or nal_header.element_size() != 4 or
+                                       not nal_header.is_contiguous() or nal_header.numel() != len(self.encs) * int(k)):
+            raise PcamvError(f"nal_header: int32, contiguous, on the device, one entry per context and slot ({len(self.encs)} x {int(k)})")
+        fn = self.lib.pcamv_gpu_batch_extract_stream_window
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_void_p]
+        self._slice_chk(fn(self.b, C.byref(params), emrate, int(k), nal_header.data_ptr() if nal_header is not None else None, C.c_void_p(stream or None)),
+                        "batch_extract_stream_window")
+        self._window_k = int(k)
+
+    def window_status(self):
+        """(n, k) int32: every slot's code of the last extract_stream_window call; synchronises"""
+        out = np.zeros((len(self.encs), getattr(self, "_window_k", 0) or 1), np.int32)
+        fn = self.lib.pcamv_gpu_batch_window_status
+        fn.argtypes = [C.c_void_p, C.c_void_p]
+        self._slice_chk(fn(self.b, _p(out)), "batch_window_status")
+        return out
 
     def stream_tell(self):
         """(next, total) per context: slice units taken so far (a take at the end does not count), slice units of the stream;
