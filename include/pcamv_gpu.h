@@ -345,6 +345,7 @@ int pcamv_gpu_abi_version(void);
 #define PCAMV_FEATURE_STREAM_DEVICE 0x40u       /* the receiver takes Annex B byte streams: units found and slice headers read on the device */
 #define PCAMV_FEATURE_STREAM_WRITER 0x80u       /* the sender writes Annex B byte streams: slice headers and unit placement on the device */
 #define PCAMV_FEATURE_STREAM_WINDOW 0x100u      /* the receiver on byte streams takes a window of slice units per context in one call */
+#define PCAMV_FEATURE_PARAM_SETS 0x200u        /* SPS / PPS read on the device, per stream: the *_param_sets and *_sets calls at the end of this file */
 unsigned pcamv_gpu_features(void);
 
 /* ---- Payload path: the caller's bits through the device-resident entry points, and back out on the device ----
@@ -571,8 +572,8 @@ int pcamv_gpu_slice_headers_device(pcamv_ctx_t *ctx, const uint8_t *bytes, size_
  * (or no header) the output is the bare slice data.  As a NAL unit: long start code, the header byte from nal_ref_idc and
  * nal_unit_type, the RBSP with emulation prevention as x264_nal_encode inserts it.  i_frame chooses the bit x264_cabac_encode_flush
  * takes from the frame counter (0x35a4e4f5 >> (i_frame & 31) & 1).
- * Contexts opened with b_cabac == 0 are refused with PCAMV_EUNSUP (they go through the *_cavlc calls below).  SPS, PPS, I frames and
- * several slices per picture stay the host's; so does the slice header in these calls -- the stream calls at the end of this file make
+ * Contexts opened with b_cabac == 0 are refused with PCAMV_EUNSUP (they go through the *_cavlc calls below).  I frames and several slices
+ * per picture stay the host's (SPS and PPS: pcamv_gpu_param_set_head, the last section of this file); so does the slice header in these calls -- the stream calls at the end of this file make
  * it on the device. */
 typedef struct pcamv_slice_hdr_t { const uint8_t *bits; int32_t n_bits; int32_t i_frame; int32_t nal_ref_idc; int32_t nal_unit_type; } pcamv_slice_hdr_t;
 /* The parity probe; synchronises.  mbs == NULL: the context's last frame -- final == 0 the first-pass records as they are, final != 0
@@ -614,8 +615,9 @@ int pcamv_gpu_rbsp_to_nal(const uint8_t *rbsp, size_t len, int nal_ref_idc, int 
  * step to its stream as [access unit delimiter +] P slice unit, the header made on the device from the step's QP, a picture counter
  * and the parameter sets.  Closed-loop contexts run step -> write_stream_step N times, then index_streams_device -> extract_stream_step
  * N times on the same (bytes, off, len): nothing per frame passes through the host on either side, and the bytes in between are a
- * well-formed Annex B stream.  Out of scope, the caller's as before: writing and parsing SPS / PPS, I frames (the stream's `head`, opaque
- * here), several slices per picture.
+ * well-formed Annex B stream.  SPS and PPS are written by pcamv_gpu_param_set_head and read by the *_param_sets calls (the last section of
+ * this file).  Out of scope, the caller's as before: I frames (they go into the stream's `head`, opaque here, behind the parameter
+ * sets), several slices per picture.
  *
  * write_slice_header: host code, no GPU; the semantics of the device's header writer on every input (csrc/pcamv_stream_write.h), and the
  * inverse of pcamv_gpu_parse_slice_header.  slice_header() (7.3.3) of a P slice for `params`, element by element as
@@ -681,6 +683,113 @@ int pcamv_gpu_batch_stream_written(pcamv_batch_t *batch, int64_t *bytes, int64_t
  * bits[i * PCAMV_SLICE_HDR_BYTES ..), bytes of a slot behind a header's last byte 0. */
 int pcamv_gpu_slice_headers_write_device(pcamv_ctx_t *ctx, const pcamv_stream_params_t *params, const pcamv_slice_fields_t *fields, int n,
                                          int32_t *rc, int32_t *n_bits, uint8_t *bits);
+
+/* ---- Parameter sets: SPS / PPS read on the device, per stream (PCAMV_FEATURE_PARAM_SETS) ----
+ *
+ * The stream calls above take one pcamv_stream_params_t for the whole batch from the caller.  With these calls a receiver hands over
+ * byte streams and nothing else: the units of nal_unit_type 7 and 8 of every context's stream are found, unescaped, parsed and resolved
+ * on the device into one table per context, and the *_sets calls read each slice header under the entry its pps_id names.  The
+ * contexts of a batch may come from different encoder configurations.  As everywhere here the host functions are the definition on
+ * every input, valid or not.  Still the caller's: I frames, several slices per picture, parameter sets that change within a stream.
+ *
+ * parse_sps reads seq_parameter_set_data() (7.3.2.1) of rbsp[0, len) -- the unit behind its header byte, unescaped -- in syntax order:
+ * profile_idc, the constraint byte, level_idc, sps_id; for profiles 100, 110, 122, 244, 44, 83, 86, 118, 128 chroma_format_idc, the two
+ * bit depths, the transform bypass flag and seq_scaling_matrix_present_flag (else 1 / 8 / 8 / 0 / 0); log2_max_frame_num; poc_type and
+ * its elements (type 1: the cycle is walked, its offsets are not kept); num_ref_frames, the gaps flag, width and height in macroblocks,
+ * frame_mbs_only_flag, direct_8x8_inference_flag, the cropping flag and its four ue, vui_parameters_present_flag.  The VUI is not read.
+ * parse_pps reads pic_parameter_set_rbsp() (7.3.2.2) through redundant_pic_cnt_present_flag and then, if more_rbsp_data(),
+ * transform_8x8_mode_flag, pic_scaling_matrix_present_flag and second_chroma_qp_index_offset (has_tail 1; without a tail the second
+ * offset is the first).  Data follows exactly if the read position lies before the last 1 bit of the RBSP; no 1 bit at or behind the
+ * position is PCAMV_EINVAL.
+ * The first failure in syntax order wins, and a read failure is found before the element is judged.  PCAMV_EINVAL: a read at or past
+ * the end, a ue with more than 31 leading zeros, sps_id > 31, pps_id > 255, log2_*_minus4 > 12, poc_type > 2, a POC cycle > 255,
+ * num_ref_idx_*_default_minus1 > 31, pic_init_qp_minus26 outside -26 .. 25, a chroma offset outside -12 .. 12, num_slice_groups_minus1
+ * > 7, more than 2^16 macroblocks in either direction.  PCAMV_EUNSUP, at the element that says so: chroma_format_idc != 1, a bit depth
+ * != 8, transform bypass, a sequence or picture scaling matrix, frame_mbs_only_flag 0, more than one slice group,
+ * transform_8x8_mode_flag 1.  weighted_pred and a default of several references are not refused here: the slice-header reader judges
+ * them per slice.  Elements without a range above are kept as the 32 bits read (num_ref_frames, the cropping offsets, pic_init_qs).
+ * On failure *out is all zeros.  Members are values, not the coded "minus" forms: log2_* 4 .. 16 (log2_max_poc_lsb 0 where poc_type
+ * is not 0), mb_w / mb_h counts, num_ref_idx_* counts, pic_init_qp / qs 26 + the coded value. */
+typedef struct pcamv_sps_t {
+    int32_t profile_idc, constraint_flags, level_idc, sps_id;
+    int32_t chroma_format_idc, bit_depth_luma, bit_depth_chroma, transform_bypass, seq_scaling_matrix_present;
+    int32_t log2_max_frame_num, poc_type, log2_max_poc_lsb, delta_pic_order_always_zero;
+    int32_t offset_for_non_ref_pic, offset_for_top_to_bottom_field, num_ref_frames_in_poc_cycle;
+    int32_t num_ref_frames, gaps_in_frame_num_allowed, mb_w, mb_h, frame_mbs_only, direct_8x8_inference;
+    int32_t frame_cropping, crop_left, crop_right, crop_top, crop_bottom, vui_parameters_present;
+} pcamv_sps_t;
+typedef struct pcamv_pps_t {
+    int32_t pps_id, sps_id, entropy_cabac, pic_order_present, num_slice_groups;
+    int32_t num_ref_idx_l0_default, num_ref_idx_l1_default, weighted_pred, weighted_bipred_idc;
+    int32_t pic_init_qp, pic_init_qs, chroma_qp_index_offset;
+    int32_t deblocking_filter_control_present, constrained_intra_pred, redundant_pic_cnt_present;
+    int32_t has_tail, transform_8x8_mode, pic_scaling_matrix_present, second_chroma_qp_index_offset;
+} pcamv_pps_t;
+int pcamv_gpu_parse_sps(const uint8_t *rbsp, size_t len, pcamv_sps_t *out);
+int pcamv_gpu_parse_pps(const uint8_t *rbsp, size_t len, pcamv_pps_t *out);
+/* The parameter sets of one stream, resolved: status, the picture size, and n_pps entries sorted by pps_id ascending, each a PPS merged
+ * with the SPS it names into what the slice-header reader takes (log2_max_poc_lsb 4 where poc_type is not 0: it is not read then).
+ *  1. The units considered are the stream's units of nal_unit_type 7 and 8, in stream order, as pcamv_gpu_annexb_index cuts them.  More
+ *     than PCAMV_PSET_UNITS_MAX of them: PCAMV_EUNSUP for the stream, before anything else.  A unit longer than PCAMV_PSET_UNIT_BYTES has
+ *     the code PCAMV_EUNSUP.
+ *  2. Each other unit is unescaped as by pcamv_gpu_nal_to_rbsp, whose failure is the unit's code, and then parsed.
+ *  3. The stream's status is the code of the first unit, in stream order, whose code is not 0 -- whether anything names that set or not.
+ *  4. Else the units are walked in stream order: at most PCAMV_PSET_SPS_MAX distinct sps_id and PCAMV_PSET_PPS_MAX distinct pps_id, and a
+ *     set sent again must equal the earlier one of its id member by member; the first unit that breaks either is PCAMV_EUNSUP.
+ *     Position does not matter: parameter sets are constant over a stream in this path, and a PPS may precede its SPS.
+ *  5. Else: no PPS at all is PCAMV_EINVAL; a PPS that names no SPS of the stream is PCAMV_EINVAL; SPS named by PPS that differ in mb_w x
+ *     mb_h are PCAMV_EUNSUP -- judged in this order.
+ * With a non-zero status mb_w, mb_h, n_pps and every entry are 0. */
+#define PCAMV_PSET_UNITS_MAX 64
+#define PCAMV_PSET_UNIT_BYTES 1024
+#define PCAMV_PSET_SPS_MAX 4
+#define PCAMV_PSET_PPS_MAX 8
+typedef struct pcamv_param_sets_t {
+    int32_t status, mb_w, mb_h, n_pps;
+    pcamv_stream_params_t pps[PCAMV_PSET_PPS_MAX];
+} pcamv_param_sets_t;
+int pcamv_gpu_stream_param_sets(const uint8_t *bytes, size_t len, pcamv_param_sets_t *out);
+/* pcamv_gpu_parse_slice_header under a stream's sets: with a non-zero status that status for every header; else exactly
+ * pcamv_gpu_parse_slice_header under the entry whose pps_id is the header's, PCAMV_EUNSUP if there is none (failures found before pps_id
+ * is read are the same under any parameters).  *entropy_cabac (optional): the entry's entropy mode, -1 where no entry was reached. */
+int pcamv_gpu_parse_slice_header_sets(const uint8_t *rbsp, size_t len, int nal_header, const pcamv_param_sets_t *sets, int64_t *start_bit,
+                                      int32_t *slice_qp, int32_t *frame_num, int32_t *entropy_cabac);
+/* The inverse, for the sender's `head`.  write_sps / write_pps write what the parsers read, with vui_parameters_present_flag 0 (the member
+ * is not looked at), for poc_type 1 a cycle of num_ref_frames_in_poc_cycle offsets 0, no optional PPS tail (has_tail must be 0 and the
+ * second chroma offset the first, else PCAMV_EINVAL), and rbsp_trailing_bits; they refuse, member by member in syntax order and with the
+ * parsers' codes, what the parsers refuse.  rbsp[cap] receives *len bytes (at most PCAMV_PSET_RBSP_MAX); cap too small: PCAMV_ENOMEM.
+ * param_set_head: an SPS unit (header byte 0x67) and a PPS unit (0x68) for `params` and a picture of mb_w x mb_h macroblocks, each with
+ * a long start code and emulation prevention (pcamv_gpu_rbsp_to_nal): constraint byte 0, frame macroblocks, 4:2:0, 8 bits, no cropping,
+ * direct_8x8_inference_flag 1, the POC type of `params` (type 1 with an empty cycle and offsets 0), one slice group, one default reference
+ * in list 1, pic_init_qs 26, chroma offset 0 -- what pcamv_gpu_batch_stream_open takes as head, or as its start. */
+#define PCAMV_PSET_RBSP_MAX 384
+int pcamv_gpu_write_sps(const pcamv_sps_t *sps, uint8_t *rbsp, size_t cap, size_t *len);
+int pcamv_gpu_write_pps(const pcamv_pps_t *pps, uint8_t *rbsp, size_t cap, size_t *len);
+int pcamv_gpu_param_set_head(const pcamv_stream_params_t *params, int mb_w, int mb_h, int sps_id, int num_ref_frames, int profile_idc, int level_idc,
+                             uint8_t *out, size_t cap, size_t *len);
+/* stream_param_sets: behind an index call (before one: PCAMV_EINVAL).  The parameter-set units of every indexed stream are found by a
+ * second run of the index kernels that selects types 7 and 8 (the index call itself costs what it did), unescaped one wavefront per
+ * unit into slots of PCAMV_PSET_UNIT_BYTES (k_pset_unit), parsed one lane per unit (k_pset_parse) and resolved one wavefront per stream
+ * (k_pset_resolve) by the rules above; a stream whose mb_w x mb_h is not the context's gets PCAMV_EUNSUP, one the index call refused
+ * PCAMV_EINVAL.  The sets stay on the device until the next index call.  The call waits for the device three times: for the whole device
+ * at its start (steps under the sets it replaces may be in flight on any stream), for `stream` in its middle -- the working memory is
+ * sized by the counts the scan found, not by n x 64 x 1 KB, and the places of the units go up with small blocking copies -- and for
+ * `stream` at its end, when it returns each context's status (host int32, optional) and the sets (host structs, optional).
+ * extract_stream_step_sets / extract_stream_window_sets: pcamv_gpu_batch_extract_stream_step / _window without `params` -- each header
+ * is read under its context's table (k_slice_header_sets).  PCAMV_EINVAL for the whole call if no stream_param_sets call followed the
+ * last index call.  The parser is the one of the contexts' own entropy mode: a batch holds contexts of one mode (pcamv_gpu_batch_create
+ * refuses others), so a batch of both modes cannot reach these calls.  Cursor,
+ * PCAMV_EEOF and kind-UNSUP handling are those calls'.  A context whose sets have a non-zero status still takes its unit and its cursor
+ * moves; it reports that status and appends nothing.  A slice whose PPS states the other entropy mode than its context's b_cabac is
+ * PCAMV_EUNSUP, judged where pps_id is.  No host synchronisation and no per-frame host arrays.  For a batch whose streams all carry
+ * the parameter sets P these calls are observationally the calls above with params = P.
+ * param_sets_device: the parity probe; n streams of one host buffer through the same kernels (no picture size is compared), the sets to
+ * sets_out[n].  Synchronises. */
+int pcamv_gpu_batch_stream_param_sets(pcamv_batch_t *batch, int32_t *status_out, pcamv_param_sets_t *sets_out, void *stream);
+int pcamv_gpu_batch_extract_stream_step_sets(pcamv_batch_t *batch, float emrate, int32_t *nal_header, void *stream);
+int pcamv_gpu_batch_extract_stream_window_sets(pcamv_batch_t *batch, float emrate, int k, int32_t *nal_header, void *stream);
+int pcamv_gpu_param_sets_device(pcamv_ctx_t *ctx, const uint8_t *bytes, size_t bytes_size, const int64_t *off, const int64_t *len, int n,
+                                pcamv_param_sets_t *sets_out);
 
 #ifdef __cplusplus
 }

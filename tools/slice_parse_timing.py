@@ -36,6 +36,19 @@ writer's kernel time of each form and the times of k_stream_slot and k_stream_co
 must be the same bytes.  Written to profiles/stream_write_timing.json, one line per entropy mode.
 
     python tools/slice_parse_timing.py --write-stream [--cavlc] [--counts 256,4096] [--reps 5] [--out profiles/stream_write_timing.json]
+
+With --param-sets the parameter sets read on the device: 256 and 4096 of the same streams of 8 frames behind a head of SPS +
+PPS (param_set_head), and in one run: the wall time of Batch.index_streams_device; of Batch.stream_param_sets, with the times of
+k_pset_unit, k_pset_parse and k_pset_resolve; and, in turn within every repetition, of Batch.extract_stream_window(k=8) with the
+caller's parameters against Batch.extract_stream_window_sets(k=8) under the streams' own sets, with k_slice_header next to
+k_slice_header_sets.  The two must receive the same bits.  Every wall time is given as median, minimum and maximum of the repetitions: the
+spread of the existing call is the margin the new one is held to.  With --parent-lib PATH -- a libpcamv_gpu.so built from the parent
+commit -- the same run first holds the index call against the parent's: this tool's --stream sweep three times with each library, in
+turn, every sweep a process of its own (PCAMV_GPU_LIB chooses the library); per count the three wall times and kernel totals of each,
+the medians, the parent's own spread and whether this library's median is slower than the parent's by more than that.  Written to
+profiles/param_sets_timing.json, one line per entropy mode.
+
+    python tools/slice_parse_timing.py --param-sets [--parent-lib PATH] [--cavlc] [--counts 256,4096] [--reps 5] [--out profiles/param_sets_timing.json]
 """
 import argparse
 import ctypes as C
@@ -319,6 +332,142 @@ def window_sweep(args, pcamv_amd, np, torch, out, slice_data, qp, m, want):
         e.close()
 
 
+def index_vs_parent(args, runs=3):
+    """--parent-lib: the --stream sweep `runs` times with the parent's library and with this one, in turn, a process each; per count
+    of streams the index call's wall time and the index kernels' total of every run, the medians, the parent's spread, the verdict"""
+    import subprocess
+    import tempfile
+    got = dict(parent=[], change=[])
+    for _ in range(runs):
+        for who in ("parent", "change"):
+            env = dict(os.environ)
+            env.pop("PCAMV_GPU_LIB", None)
+            if who == "parent":
+                env["PCAMV_GPU_LIB"] = os.path.abspath(args.parent_lib)
+            with tempfile.TemporaryDirectory() as d:
+                path = os.path.join(d, "stream.json")
+                cmd = [sys.executable, os.path.abspath(__file__), "--stream", "--counts", args.counts, "--reps", str(args.reps), "--out", path] + (["--cavlc"] if args.cavlc else [])
+                r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+                if r.returncode:
+                    sys.exit("slice_parse_timing.py: the --stream sweep with the %s library failed: %s" % (who, r.stderr[-500:]))
+                got[who].append(json.loads(open(path).read().splitlines()[0])["device"])
+    med = lambda v: sorted(v)[len(v) // 2]                  # noqa: E731
+    rows = []
+    for k, first in enumerate(got["parent"][0]):
+        row = dict(streams=first["streams"])
+        for key, short in (("index_streams_device_wall_ms", "wall"), ("index_kernels_total_ms", "kernels")):
+            a, b = [run[k][key] for run in got["parent"]], [run[k][key] for run in got["change"]]
+            row[short] = dict(parent_ms=a, change_ms=b, parent_median_ms=med(a), change_median_ms=med(b), parent_spread_ms=max(a) - min(a),
+                              change_minus_parent_ms=med(b) - med(a), within_parent_spread=bool(med(b) - med(a) <= max(a) - min(a)))
+        rows.append(row)
+    return dict(runs=runs, parent_lib=os.path.basename(args.parent_lib), device=rows)
+
+
+def param_sets_sweep(args, pcamv_amd, np, torch, out, slice_data, qp, m, want):
+    """--param-sets: per count n of streams of 8 frames behind an SPS and a PPS, in one run: the index call; stream_param_sets; and in
+    turn within every repetition, each between two synchronisations, extract_stream_window(k=8) and extract_stream_window_sets(k=8).  The
+    index call in front of each window call (it puts the cursors back) is the one that is timed"""
+    dev = torch.device("cuda", 0)
+    frames = 8
+    sp, units, body, _ = frames_stream(args, pcamv_amd, np, slice_data, qp, frames)
+    head = pcamv_amd.param_set_head(sp, out["width"] // 16, out["height"] // 16)
+    stream = head + body
+    sets = pcamv_amd.stream_param_sets(stream)
+    if sets.status or sets.entries() != [{k: getattr(sp, k) for k, _ in sp._fields_}]:
+        sys.exit("slice_parse_timing.py: the head does not resolve to the parameters it was made for")
+    parser = out["kernel"]
+    pset_kernels = ("k_pset_unit", "k_pset_parse", "k_pset_resolve")
+    out.update(kernel="k_pset_resolve", parser=parser, stream_bytes=len(stream), head_bytes=len(head), frames=frames)
+    p = pcamv_amd.param_default(out["width"], out["height"])
+    pcamv_amd.param_parse(p, "subme", 5)
+    p.b_cabac = 0 if args.cavlc else 1
+    med = lambda v: sorted(v)[len(v) // 2]                  # noqa: E731
+    stats = lambda v: dict(median_ms=med(v) * 1e3, min_ms=min(v) * 1e3, max_ms=max(v) * 1e3)     # noqa: E731
+    encs = []
+    for n in [int(v) for v in args.counts.split(",")]:
+        while len(encs) < n:
+            e = pcamv_amd.Encoder(p)
+            e.rx_reserve(frames * m + 64)
+            encs.append(e)
+        batch = pcamv_amd.Batch(encs[:n])
+        stride = (len(stream) + 3) | 1                      # every context its own copy, at odd offsets
+        data = torch.from_numpy(np.tile(np.frombuffer(stream + bytes(stride - len(stream)), np.uint8), n)).to(dev)
+        off = torch.arange(n, dtype=torch.int64, device=dev) * stride
+        length = torch.full((n,), len(stream), dtype=torch.int64, device=dev)
+        torch.cuda.synchronize()                            # the tensors are complete before the library's stream reads them
+        wall = dict(index=[], param_sets=[], window=[], window_sets=[])
+        ms, received = {}, {}
+
+        def fresh(timed):
+            for e in encs[:n]:
+                e.rx_reset()
+            torch.cuda.synchronize()
+            w0 = time.perf_counter()
+            counts = batch.index_streams_device(data, off, length, max_units=16)        # (synchronises itself)
+            if timed:
+                wall["index"].append(time.perf_counter() - w0)
+            if counts.tolist() != [frames] * n:
+                sys.exit("slice_parse_timing.py: the device's index differs from the host's")
+
+        fresh(False)
+        batch.stream_window(frames)
+        for rep in range(args.reps + 1):                    # the first round is not timed: allocations, code load
+            for name in (("window", "window_sets"), ("window_sets", "window"))[rep & 1]:        # the two forms take turns at going first
+                fresh(rep > 0)
+                header = "k_slice_header" if name == "window" else "k_slice_header_sets"
+                if name == "window_sets":
+                    for k in pset_kernels:
+                        batch.kernel_time(k, reset=True)
+                    w0 = time.perf_counter()
+                    status, _ = batch.stream_param_sets()    # (synchronises itself)
+                    if rep:
+                        wall["param_sets"].append(time.perf_counter() - w0)
+                    if status.any():
+                        sys.exit("slice_parse_timing.py: a stream's parameter sets were refused")
+                    for k in pset_kernels:
+                        v, launches = batch.kernel_time(k, reset=True)
+                        if launches != 1:
+                            sys.exit("slice_parse_timing.py: a launch was not timed")
+                        if rep:
+                            ms[k] = ms.get(k, 0.0) + v / args.reps
+                for k in (header, parser):
+                    batch.kernel_time(k, reset=True)
+                w0 = time.perf_counter()
+                if name == "window":
+                    batch.extract_stream_window(sp, 0.5, frames)
+                else:
+                    batch.extract_stream_window_sets(0.5, frames)
+                torch.cuda.synchronize()
+                if rep:
+                    wall[name].append(time.perf_counter() - w0)
+                if (batch.window_status() != 0).any():
+                    sys.exit("slice_parse_timing.py: a unit failed on the device")
+                for k in (header, parser):
+                    v, launches = batch.kernel_time(k, reset=True)
+                    if launches != 1:
+                        sys.exit("slice_parse_timing.py: a launch was not timed")
+                    if rep:
+                        ms[name, k] = ms.get((name, k), 0.0) + v / args.reps
+                received[name] = [encs[0].received(packed=True).tobytes(), encs[n - 1].received(packed=True).tobytes(), encs[n - 1].rx_tell()[0]]
+                rec = encs[n - 1].slice_records()[0]
+                if any(not np.array_equal(rec[f], want[f]) for f in rec.dtype.names) or received[name][2] != frames * m:
+                    sys.exit("slice_parse_timing.py: the device's records differ from the host parser's")
+            if received["window"] != received["window_sets"]:
+                sys.exit("slice_parse_timing.py: the window under the streams' sets received other bits than the one with the caller's parameters")
+        spread = max(wall["window"]) - min(wall["window"])
+        out["device"].append(dict(streams=n, frames=frames, slices=frames * n, index_streams_device_wall=stats(wall["index"]),
+                                  stream_param_sets_wall=stats(wall["param_sets"]), pset_kernels_ms={k: ms[k] for k in pset_kernels},
+                                  extract_stream_window_wall=stats(wall["window"]), extract_stream_window_sets_wall=stats(wall["window_sets"]),
+                                  window_spread_ms=spread * 1e3, sets_minus_params_ms=(med(wall["window_sets"]) - med(wall["window"])) * 1e3,
+                                  within_spread=bool(med(wall["window_sets"]) - med(wall["window"]) <= spread),
+                                  k_slice_header_ms=ms["window", "k_slice_header"], k_slice_header_sets_ms=ms["window_sets", "k_slice_header_sets"],
+                                  parser_kernel_ms=dict(window=ms["window", parser], window_sets=ms["window_sets", parser])))
+        print(json.dumps(out["device"][-1]), flush=True)
+        batch.close()
+    for e in encs:
+        e.close()
+
+
 def write_stream_sweep(args, pcamv_amd, np, torch, mode):
     """--write-stream: one entry per count of chains.  Every round steps the chains, then writes the same frame twice in turn, each call
     between two synchronisations: Batch.write_step*(as_nal=True) with one host-made header, and Batch.write_stream_step on streams opened
@@ -417,15 +566,18 @@ def main():
     ap.add_argument("--stream", action="store_true", help="the receiver on byte streams: the index kernels, and a stream step next to a NAL step (profiles/stream_index_timing.json)")
     ap.add_argument("--window", action="store_true", help="a window of 8 units per stream next to 8 stream steps and to one step of 8 times the streams (profiles/stream_window_timing.json)")
     ap.add_argument("--write-stream", action="store_true", help="the sender's byte streams: write_stream_step next to write_step (profiles/stream_write_timing.json)")
-    ap.add_argument("--counts", default=None, help="default 1,64,1024,4096; with --nal, --stream or --write-stream 256,4096")
+    ap.add_argument("--param-sets", action="store_true", help="SPS / PPS read on the device: stream_param_sets, and a window under the streams' own sets next to one with the caller's parameters (profiles/param_sets_timing.json)")
+    ap.add_argument("--parent-lib", default=None, help="with --param-sets: a libpcamv_gpu.so of the parent commit; the index call is held against it first (three --stream sweeps each)")
+    ap.add_argument("--counts", default=None, help="default 1,64,1024,4096; with --nal, --stream, --param-sets or --write-stream 256,4096")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--host-threads", type=int, default=16)
     ap.add_argument("--out", default=None, help="default profiles/slice_parse_timing.json; with --nal profiles/nal_unescape_timing.json")
     args = ap.parse_args()
-    args.counts = args.counts or ("256" if args.window else "256,4096" if args.nal or args.stream or args.write_stream else "1,64,1024,4096")
-    args.out = args.out if args.out is not None else os.path.join(ROOT, "profiles", "stream_write_timing.json" if args.write_stream else "stream_index_timing.json" if args.stream else
+    args.counts = args.counts or ("256" if args.window else "256,4096" if args.nal or args.stream or args.write_stream or args.param_sets else "1,64,1024,4096")
+    args.out = args.out if args.out is not None else os.path.join(ROOT, "profiles", "param_sets_timing.json" if args.param_sets else "stream_write_timing.json" if args.write_stream else "stream_index_timing.json" if args.stream else
                                                                   "stream_window_timing.json" if args.window else
                                                                   "nal_unescape_timing.json" if args.nal else "slice_parse_timing.json")
+    index_cmp = index_vs_parent(args) if args.param_sets and args.parent_lib else None      # (before this process opens the device)
     import numpy as np
     import torch
     import pcamv_amd
@@ -466,6 +618,11 @@ def main():
         return write_line(args, out, mode)
     if args.window:
         window_sweep(args, pcamv_amd, np, torch, out, g["slice_data"].tobytes(), qp, m, want)
+        return write_line(args, out, mode)
+    if args.param_sets:
+        if index_cmp:
+            out["index_vs_parent"] = index_cmp
+        param_sets_sweep(args, pcamv_amd, np, torch, out, g["slice_data"].tobytes(), qp, m, want)
         return write_line(args, out, mode)
     w0 = time.perf_counter(); host_parse(200); one = (time.perf_counter() - w0) / 200
     with ThreadPoolExecutor(args.host_threads) as ex:

@@ -17,6 +17,7 @@
 #include "pcamv_slice.hip.h"
 #include "pcamv_host_tables.h"
 #include "pcamv_mvsyntax.h"
+#include "pcamv_param_sets_host.h"
 #include "pcamv_rd_select.h"
 
 #define PCAMV_ABI_VERSION 3
@@ -25,10 +26,11 @@
 #define NKEV 16                /* ... and a timer of the smaller kernels */
 enum { KT_ANALYSE, KT_EMBED_PREPARE, KT_EXTRACT_PREPARE, KT_EXTRACT_BITS, KT_PAYLOAD_CHECK, KT_PARSE_PSLICE, KT_PARSE_PSLICE_CAVLC, KT_WRITE_PSLICE, KT_WRITE_PSLICE_CAVLC, KT_NAL_TO_RBSP,
        KT_STREAM_PLAN, KT_STREAM_SCAN, KT_STREAM_PREFIX, KT_STREAM_PLACE, KT_STREAM_UNIT, KT_SLICE_HEADER, KT_STREAM_STATUS,
-       KT_STREAM_OPEN, KT_STREAM_SLOT, KT_STREAM_COMMIT, KT_STREAM_WINDOW_UNIT, KT_EXTRACT_COUNT, KT_EXTRACT_CHAIN, KT_N };
+       KT_STREAM_OPEN, KT_STREAM_SLOT, KT_STREAM_COMMIT, KT_STREAM_WINDOW_UNIT, KT_EXTRACT_COUNT, KT_EXTRACT_CHAIN,
+       KT_PSET_UNIT, KT_PSET_PARSE, KT_PSET_RESOLVE, KT_SLICE_HEADER_SETS, KT_N };
 #define PCAMV_FEATURES (PCAMV_FEATURE_PAYLOAD | PCAMV_FEATURE_SLICE_PARSER | PCAMV_FEATURE_SLICE_PARSER_CAVLC | PCAMV_FEATURE_SLICE_WRITER | \
                         PCAMV_FEATURE_SLICE_WRITER_CAVLC | PCAMV_FEATURE_NAL_DEVICE | PCAMV_FEATURE_STREAM_DEVICE | PCAMV_FEATURE_STREAM_WRITER | \
-                        PCAMV_FEATURE_STREAM_WINDOW)
+                        PCAMV_FEATURE_STREAM_WINDOW | PCAMV_FEATURE_PARAM_SETS)
 #define SLICE_GUARD_MBS 4       /* records behind a context's receive-side records that nothing may write (pcamv_gpu_debug_slice_records) */
 #define NSTAGE 2                /* staging buffers of extract_slices: a call waits for the one before the last */
 /* the stages of a step (batch_launch's `what`): plane production, analysis (search + RCA + encode), embedding, second pass */
@@ -74,6 +76,17 @@ struct StreamIndex {
     int *d_bad; unsigned long long *d_longest; SiChunk *d_chunks; pcamv_unit_t *d_table; uint8_t *d_own;
     size_t cap_n, cap_chunks, cap_table, cap_own;
     const uint8_t *bytes; long long bytes_size, slot;
+};
+
+/* the parameter sets of n indexed streams (k_pset_unit, k_pset_parse, k_pset_resolve): the tables of their units of type 7 / 8, the
+ * per-stream counts, and per unit of the last run its place, slot and record; d_sets is what k_slice_header_sets reads.  `ready` holds
+ * from a stream_param_sets call to the next index call */
+struct StreamSets {
+    int ready;
+    pcamv_unit_t *d_table; long long *d_cnt; pcamv_param_sets_t *d_sets;       /* d_cnt: [n_units n][count n][u_base n + 1] */
+    size_t cap_table, cap_cnt, cap_sets;
+    long long *d_len; int *d_map; PsRec *d_rec; uint8_t *d_slots;               /* d_map: [u_stream U][u_index U][nal_header U][first U] */
+    size_t cap_len, cap_map, cap_rec, cap_slots;
 };
 
 /* the byte streams a batch writes (pcamv_gpu_batch_stream_open): the borrowed buffer and length array, the settings every picture shares,
@@ -129,6 +142,7 @@ struct pcamv_batch {
     StageRing nal_stage;
     /* ... handed byte streams: the index of every context's stream, and the job arrays and RBSP slots of a step, sized by index calls */
     StreamIndex sx;
+    StreamSets ps;              /* ... and their parameter sets, for the *_sets calls */
     StageRing su_stage;
     StreamWindow sw;
     /* sender to a stream (k_write_pslice, k_write_pslice_cavlc): the same of its own, and the staging of the callers' slice headers -- a
@@ -287,6 +301,11 @@ static void stream_index_free(StreamIndex &S)
     hipFree(S.d_at); hipFree(S.d_bad); hipFree(S.d_longest); hipFree(S.d_chunks); hipFree(S.d_table); hipFree(S.d_own);
     S = StreamIndex();
 }
+static void stream_sets_free(StreamSets &P)
+{
+    hipFree(P.d_table); hipFree(P.d_cnt); hipFree(P.d_sets); hipFree(P.d_len); hipFree(P.d_map); hipFree(P.d_rec); hipFree(P.d_slots);
+    P = StreamSets();
+}
 static void stream_window_free(StreamWindow &W)
 {
     hipFree(W.d_mbs); hipFree(W.d_stego); hipFree(W.d_hdr); hipFree(W.d_cols); hipFree(W.d_stat); hipFree(W.d_scratch); hipFree(W.d_jobs);
@@ -317,6 +336,7 @@ extern "C" void pcamv_gpu_batch_destroy(pcamv_batch_t *b)
     hipFree(b->d_sstat); hipFree(b->d_sp_tab); hipFree(b->d_sp_scratch);
     stage_destroy(b->rx_stage); stage_destroy(b->nal_stage); stage_destroy(b->su_stage);
     stream_index_free(b->sx);
+    stream_sets_free(b->ps);
     stream_window_free(b->sw);
     hipFree(b->d_wstat); hipFree(b->d_sw_tab); hipFree(b->d_sw_scratch);
     stage_destroy(b->tx_stage);
@@ -465,7 +485,8 @@ static const char *kt_name(const pcamv_batch *b, int k)      /* what pcamv_gpu_b
     static const char *const small[KT_N] = {NULL, "k_embed_prepare", "k_extract_prepare", "k_extract_bits", "k_payload_check", "k_parse_pslice", "k_parse_pslice_cavlc", "k_write_pslice",
                                             "k_write_pslice_cavlc", "k_nal_to_rbsp", "k_stream_plan", "k_stream_scan", "k_stream_prefix", "k_stream_place", "k_stream_unit",
                                             "k_slice_header", "k_stream_status", "k_stream_open", "k_stream_slot", "k_stream_commit",
-                                            "k_stream_window_unit", "k_extract_count", "k_extract_chain"};
+                                            "k_stream_window_unit", "k_extract_count", "k_extract_chain", "k_pset_unit", "k_pset_parse", "k_pset_resolve",
+                                            "k_slice_header_sets"};
     return k == KT_ANALYSE ? dominant_kernel(b) : small[k];
 }
 extern "C" int pcamv_gpu_batch_copy_results_async(pcamv_batch_t *b, void *dst_mb, size_t mb_stride, void *dst_flip, size_t flip_stride, void *stream)
@@ -689,8 +710,9 @@ static int stage_send(pcamv_batch *b, StageRing &R, int k, size_t total, hipStre
     HIPCHK(b, hipMemcpyAsync(R.d[k], R.h[k], total, hipMemcpyHostToDevice, st));
     return stage_release(b, R, k, st);
 }
-/* the job arrays in front of a stream step's RBSP slots: [off n][len n][start_bit n] int64, [qp n][first n][frame_num n][nal_header n] int32 */
-static size_t stream_step_hdr(int n) { return ((size_t)n * (3 * 8 + 4 * 4) + 15) & ~(size_t)15; }
+/* the job arrays in front of a stream step's RBSP slots: [off n][len n][start_bit n] int64, [qp n][first n][frame_num n][nal_header n][entropy n] int32
+ * (entropy: what k_slice_header_sets alone writes, the mode of the entry each header was read under) */
+static size_t stream_step_hdr(int n) { return ((size_t)n * (3 * 8 + 5 * 4) + 15) & ~(size_t)15; }
 /* take the next descriptor slot, fill it from the contexts' current FrameDev/EmbedDev and queue its upload */
 static int batch_push_descs(pcamv_batch *b, hipStream_t st, const FrameDev **dF, const EmbedDev **dE, int *slot_out)
 {
@@ -1597,13 +1619,13 @@ static int stream_index_run(pcamv_batch *b, StreamIndex &S, const uint8_t *d_byt
     hipLaunchKernelGGL(k_stream_plan, dim3(1), dim3(64), 0, st, J);
     kt_end(b, KT_STREAM_PLAN, ev, st);
     ev = kt_begin(b, KT_STREAM_SCAN, st);
-    hipLaunchKernelGGL(k_stream_scan, dim3(chunks), dim3(64), 0, st, J);
+    hipLaunchKernelGGL(k_stream_scan<0>, dim3(chunks), dim3(64), 0, st, J);
     kt_end(b, KT_STREAM_SCAN, ev, st);
     ev = kt_begin(b, KT_STREAM_PREFIX, st);
-    hipLaunchKernelGGL(k_stream_prefix, dim3(S.n), dim3(64), 0, st, J);
+    hipLaunchKernelGGL(k_stream_prefix<0>, dim3(S.n), dim3(64), 0, st, J);
     kt_end(b, KT_STREAM_PREFIX, ev, st);
     ev = kt_begin(b, KT_STREAM_PLACE, st);
-    hipLaunchKernelGGL(k_stream_place, dim3(chunks), dim3(64), 0, st, J);
+    hipLaunchKernelGGL(k_stream_place<0>, dim3(chunks), dim3(64), 0, st, J);
     kt_end(b, KT_STREAM_PLACE, ev, st);
     return launched(b);
 }
@@ -1641,6 +1663,7 @@ static int stream_index_finish(pcamv_batch *b, const uint8_t *d_bytes, size_t by
             R.cap[k] = total;
         }
     S.bytes = d_bytes; S.bytes_size = (long long)bytes_size; S.ready = 1;
+    b->ps.ready = 0;                                /* the sets belong to the streams of the index call before */
     return b->sw.k ? window_jobs_room(b) : 0;       /* (a window reserved earlier: its RBSP slots follow, as the steps' do) */
 }
 extern "C" int pcamv_gpu_batch_index_streams_device(pcamv_batch_t *b, const void *bytes, size_t bytes_size, const int64_t *off, const int64_t *len,
@@ -1683,13 +1706,39 @@ extern "C" int pcamv_gpu_batch_index_streams(pcamv_batch_t *b, const pcamv_strea
     TRY(stream_index_run(b, S, S.d_own + hdr, total - hdr, (const long long *)S.d_own, (const long long *)S.d_own + n, 0, st));
     return stream_index_finish(b, S.d_own + hdr, total - hdr, n_slices_out);
 }
-extern "C" int pcamv_gpu_batch_extract_stream_step(pcamv_batch_t *b, const pcamv_stream_params_t *params, float emrate, int32_t *nal_header, void *stream)
+/* the entropy mode of a *_sets call is the contexts' own: 1 CAVLC, 0 CABAC (a batch holds contexts of one mode: pcamv_gpu_batch_create) */
+static int sets_mode(pcamv_batch *b, int *cavlc)
 {
-    if (!b || !params) return PCAMV_EINVAL;
-    const int cavlc = !params->entropy_cabac;
+    if (!b) return PCAMV_EINVAL;
+    TRY(batch_live(b));
+    *cavlc = !b->ctx[0]->F.b_cabac;
+    return 0;
+}
+/* the header stage of a step or a window: under `params`, or (NULL) under every context's own sets */
+static void slice_header_launch(pcamv_batch *b, StreamStep &J, const pcamv_stream_params_t *params, int cavlc, int sets_k, size_t jobs, hipStream_t st)
+{
+    J.sets = NULL; J.sets_k = sets_k; J.want_cabac = !cavlc; J.entropy = J.frame_num + 2 * jobs;
+    if (params) {
+        J.P = *params;
+        const int ev = kt_begin(b, KT_SLICE_HEADER, st);
+        hipLaunchKernelGGL(k_slice_header, dim3((unsigned)((jobs + 63) / 64)), dim3(64), 0, st, J);
+        kt_end(b, KT_SLICE_HEADER, ev, st);
+    } else {
+        J.P = pcamv_stream_params_t();
+        J.sets = b->ps.d_sets;
+        const int ev = kt_begin(b, KT_SLICE_HEADER_SETS, st);
+        hipLaunchKernelGGL(k_slice_header_sets, dim3((unsigned)((jobs + 63) / 64)), dim3(64), 0, st, J);
+        kt_end(b, KT_SLICE_HEADER_SETS, ev, st);
+    }
+}
+static int extract_stream_step(pcamv_batch_t *b, const pcamv_stream_params_t *params, float emrate, int32_t *nal_header, void *stream)
+{
+    int cavlc = 0;
+    if (params) cavlc = !params->entropy_cabac; else TRY(sets_mode(b, &cavlc));
     TRY(slices_checked(b, emrate, 1, cavlc));
     StreamIndex &S = b->sx;
     if (!S.ready) return fail(b, PCAMV_EINVAL, "no byte streams were handed to this batch yet (pcamv_gpu_batch_index_streams*)");
+    if (!params && !b->ps.ready) return fail(b, PCAMV_EINVAL, "the parameter sets of the indexed streams were not read yet (pcamv_gpu_batch_stream_param_sets behind the index call)");
     hipStream_t st = stream ? (hipStream_t)stream : b->ctx[0]->stream;
     const size_t n = (size_t)b->n, hdr = stream_step_hdr(b->n);
     int k;
@@ -1701,13 +1750,11 @@ extern "C" int pcamv_gpu_batch_extract_stream_step(pcamv_batch_t *b, const pcamv
     J.rbsp = d + hdr; J.slot = S.slot; J.rbsp_size = (long long)n * S.slot;
     J.off = (long long *)d; J.len = J.off + n; J.start_bit = J.len + n;
     J.qp = (int *)(J.start_bit + n); J.first = J.qp + n; J.frame_num = J.first + n; J.nal_header = nal_header ? nal_header : J.frame_num + n;
-    J.P = *params; J.n = b->n;
+    J.n = b->n; J.cursor_was = NULL; J.k = 0;
     int ev = kt_begin(b, KT_STREAM_UNIT, st);
     hipLaunchKernelGGL(k_stream_unit, dim3(b->n), dim3(64), 0, st, J);
     kt_end(b, KT_STREAM_UNIT, ev, st);
-    ev = kt_begin(b, KT_SLICE_HEADER, st);
-    hipLaunchKernelGGL(k_slice_header, dim3((b->n + 63) / 64), dim3(64), 0, st, J);
-    kt_end(b, KT_SLICE_HEADER, ev, st);
+    slice_header_launch(b, J, params, cavlc, 1, n, st);
     SliceJobs SJ;
     SJ.bytes = J.rbsp; SJ.bytes_size = J.rbsp_size; SJ.off = J.off; SJ.len = J.len; SJ.start_bit = J.start_bit; SJ.qp = cavlc ? NULL : J.qp;
     const int rc = slices_run(b, SJ, cavlc, 1, emrate, st);
@@ -1717,6 +1764,16 @@ extern "C" int pcamv_gpu_batch_extract_stream_step(pcamv_batch_t *b, const pcamv
     kt_end(b, KT_STREAM_STATUS, ev, st);
     const int rc1 = launched(b), rc2 = stage_release(b, b->su_stage, k, st);        /* released on every path */
     return rc ? rc : rc1 ? rc1 : rc2;
+}
+extern "C" int pcamv_gpu_batch_extract_stream_step(pcamv_batch_t *b, const pcamv_stream_params_t *params, float emrate, int32_t *nal_header, void *stream)
+{
+    if (!b || !params) return PCAMV_EINVAL;
+    return extract_stream_step(b, params, emrate, nal_header, stream);
+}
+extern "C" int pcamv_gpu_batch_extract_stream_step_sets(pcamv_batch_t *b, float emrate, int32_t *nal_header, void *stream)
+{
+    if (!b) return PCAMV_EINVAL;
+    return extract_stream_step(b, NULL, emrate, nal_header, stream);
 }
 /* ---- a window of slice units per context in one launch (k_stream_window_unit, k_extract_count, k_extract_chain) */
 extern "C" int pcamv_gpu_batch_stream_window(pcamv_batch_t *b, int k)
@@ -1762,14 +1819,15 @@ extern "C" int pcamv_gpu_batch_stream_window(pcamv_batch_t *b, int k)
     if (rc) stream_window_free(W);
     return rc;
 }
-extern "C" int pcamv_gpu_batch_extract_stream_window(pcamv_batch_t *b, const pcamv_stream_params_t *params, float emrate, int k, int32_t *nal_header, void *stream)
+static int extract_stream_window(pcamv_batch_t *b, const pcamv_stream_params_t *params, float emrate, int k, int32_t *nal_header, void *stream)
 {
-    if (!b || !params) return PCAMV_EINVAL;
-    const int cavlc = !params->entropy_cabac;
+    int cavlc = 0;
+    if (params) cavlc = !params->entropy_cabac; else TRY(sets_mode(b, &cavlc));
     TRY(slices_checked(b, emrate, 1, cavlc));
     StreamIndex &S = b->sx;
     StreamWindow &W = b->sw;
     if (!S.ready) return fail(b, PCAMV_EINVAL, "no byte streams were handed to this batch yet (pcamv_gpu_batch_index_streams*)");
+    if (!params && !b->ps.ready) return fail(b, PCAMV_EINVAL, "the parameter sets of the indexed streams were not read yet (pcamv_gpu_batch_stream_param_sets behind the index call)");
     if (!W.k) return fail(b, PCAMV_EINVAL, "no window was reserved for this batch (pcamv_gpu_batch_stream_window)");
     if (k < 1 || k > W.k) return fail(b, PCAMV_EINVAL, "a window of %d units: 1 to the %d reserved", k, W.k);
     hipStream_t st = stream ? (hipStream_t)stream : b->ctx[0]->stream;
@@ -1801,13 +1859,11 @@ extern "C" int pcamv_gpu_batch_extract_stream_window(pcamv_batch_t *b, const pca
     J.rbsp = d + hdr; J.slot = S.slot; J.rbsp_size = (long long)jobs * S.slot;
     J.off = (long long *)d; J.len = J.off + jobs; J.start_bit = J.len + jobs;
     J.qp = (int *)(J.start_bit + jobs); J.first = J.qp + jobs; J.frame_num = J.first + jobs; J.nal_header = nal_header ? nal_header : J.frame_num + jobs;
-    J.P = *params; J.n = (int)jobs; J.cursor_was = W.d_cursor_was; J.k = k;
+    J.n = (int)jobs; J.cursor_was = W.d_cursor_was; J.k = k;
     int ev = kt_begin(b, KT_STREAM_WINDOW_UNIT, st);
     hipLaunchKernelGGL(k_stream_window_unit, dim3((unsigned)jobs), dim3(64), 0, st, J);
     kt_end(b, KT_STREAM_WINDOW_UNIT, ev, st);
-    ev = kt_begin(b, KT_SLICE_HEADER, st);
-    hipLaunchKernelGGL(k_slice_header, dim3((unsigned)((jobs + 63) / 64)), dim3(64), 0, st, J);
-    kt_end(b, KT_SLICE_HEADER, ev, st);
+    slice_header_launch(b, J, params, cavlc, k, jobs, st);
     SliceJobs SJ;
     SJ.bytes = J.rbsp; SJ.bytes_size = J.rbsp_size; SJ.off = J.off; SJ.len = J.len; SJ.start_bit = J.start_bit; SJ.qp = cavlc ? NULL : J.qp;
     slice_launch(b, dX, SJ, cavlc, st, (int)jobs, W.d_scratch);
@@ -1828,6 +1884,16 @@ extern "C" int pcamv_gpu_batch_extract_stream_window(pcamv_batch_t *b, const pca
     HIPCHK(b, hipEventRecord(W.done, st));
     W.used = 1;
     return rc;
+}
+extern "C" int pcamv_gpu_batch_extract_stream_window(pcamv_batch_t *b, const pcamv_stream_params_t *params, float emrate, int k, int32_t *nal_header, void *stream)
+{
+    if (!b || !params) return PCAMV_EINVAL;
+    return extract_stream_window(b, params, emrate, k, nal_header, stream);
+}
+extern "C" int pcamv_gpu_batch_extract_stream_window_sets(pcamv_batch_t *b, float emrate, int k, int32_t *nal_header, void *stream)
+{
+    if (!b) return PCAMV_EINVAL;
+    return extract_stream_window(b, NULL, emrate, k, nal_header, stream);
 }
 extern "C" int pcamv_gpu_batch_window_status(pcamv_batch_t *b, int32_t *status)
 {
@@ -1910,6 +1976,176 @@ extern "C" int pcamv_gpu_slice_headers_device(pcamv_ctx_t *c, const uint8_t *byt
     HIPCHK(c, hipMemcpy(slice_qp, J.qp, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(rc_out, J.first, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(frame_num, J.frame_num, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+    return 0;
+}
+/* ---- parameter sets per stream (k_pset_unit, k_pset_parse, k_pset_resolve; pcamv_param_sets.h) */
+/* The streams S indexed (placement, chunk bases and refusals are S's; its chunk summaries are working memory again) through the scan
+ * that selects units of type 7 / 8 and the three kernels, on `st`.  Waits for `st` twice: for the counts, by which the per-unit memory is
+ * sized (the map of the units goes up with blocking copies), and at the end.  want_w / want_h: the picture size every stream must have, 0: any */
+static int pset_run(pcamv_batch *b, const StreamIndex &S, const uint8_t *d_bytes, long long bytes_size, StreamSets &P, int want_w, int want_h, hipStream_t st)
+{
+    const size_t n = (size_t)S.n;
+    P.ready = 0;
+    TRY(grow(b, &P.d_table, &P.cap_table, n * PCAMV_PSET_UNITS_MAX));
+    TRY(grow(b, &P.d_cnt, &P.cap_cnt, 3 * n + 1));
+    TRY(grow(b, &P.d_sets, &P.cap_sets, n));
+    HIPCHK(b, hipMemsetAsync(P.d_cnt, 0, 8 * (3 * n + 1), st));
+    StreamJobs J;
+    J.bytes = d_bytes; J.bytes_size = bytes_size; J.off = S.d_at; J.len = S.d_at + n;
+    J.chunk_base = S.d_at + 2 * n; J.bad = S.d_bad; J.chunks = S.d_chunks; J.max_chunks = S.max_chunks;
+    J.table = P.d_table; J.max_units = PCAMV_PSET_UNITS_MAX; J.stride = PCAMV_PSET_UNITS_MAX; J.all = 0;
+    J.n_units = P.d_cnt; J.n_slices = P.d_cnt + n; J.cursor = NULL; J.longest = NULL; J.n = S.n;
+    const unsigned chunks = (unsigned)S.max_chunks;
+    int ev = kt_begin(b, KT_STREAM_SCAN, st);
+    hipLaunchKernelGGL(k_stream_scan<SI_SEL_PSET>, dim3(chunks), dim3(64), 0, st, J);
+    kt_end(b, KT_STREAM_SCAN, ev, st);
+    ev = kt_begin(b, KT_STREAM_PREFIX, st);
+    hipLaunchKernelGGL(k_stream_prefix<SI_SEL_PSET>, dim3(S.n), dim3(64), 0, st, J);
+    kt_end(b, KT_STREAM_PREFIX, ev, st);
+    ev = kt_begin(b, KT_STREAM_PLACE, st);
+    hipLaunchKernelGGL(k_stream_place<SI_SEL_PSET>, dim3(chunks), dim3(64), 0, st, J);
+    kt_end(b, KT_STREAM_PLACE, ev, st);
+    TRY(launched(b));
+    HIPCHK(b, hipStreamSynchronize(st));
+    /* the launch's units, stream by stream: the first PCAMV_PSET_UNITS_MAX of each stream the index took */
+    HostTmp<long long> h_cnt(2 * n + 1); HostTmp<int> h_bad(n ? n : 1);
+    if (!h_cnt || !h_bad) return fail(b, PCAMV_ENOMEM, "no memory for the counts of %zu streams", n);
+    HIPCHK(b, hipMemcpy(h_cnt, P.d_cnt + n, 8 * n, hipMemcpyDeviceToHost));
+    HIPCHK(b, hipMemcpy(h_bad, S.d_bad, 4 * n, hipMemcpyDeviceToHost));
+    long long *h_base = h_cnt + n;
+    size_t units = 0;
+    for (size_t i = 0; i < n; i++) {
+        const long long c = h_bad[i] || h_cnt[i] < 0 ? 0 : h_cnt[i] < PCAMV_PSET_UNITS_MAX ? h_cnt[i] : PCAMV_PSET_UNITS_MAX;
+        h_base[i] = (long long)units;
+        units += (size_t)c;
+    }
+    h_base[n] = (long long)units;
+    const size_t U = units ? units : 1;
+    HostTmp<int> h_map(2 * U);
+    if (!h_map) return fail(b, PCAMV_ENOMEM, "no memory for the places of %zu parameter-set units", units);
+    for (size_t i = 0; i < n; i++)
+        for (long long x = 0; x < h_base[i + 1] - h_base[i]; x++) { h_map[h_base[i] + x] = (int)i; h_map[U + h_base[i] + x] = (int)x; }
+    TRY(grow(b, &P.d_len, &P.cap_len, U)); TRY(grow(b, &P.d_map, &P.cap_map, 4 * U));
+    TRY(grow(b, &P.d_rec, &P.cap_rec, U)); TRY(grow(b, &P.d_slots, &P.cap_slots, U * PCAMV_PSET_UNIT_BYTES));
+    HIPCHK(b, hipMemcpy(P.d_map, h_map, 4 * 2 * U, hipMemcpyHostToDevice));
+    HIPCHK(b, hipMemcpy(P.d_cnt + 2 * n, h_base, 8 * (n + 1), hipMemcpyHostToDevice));
+    PsetJobs Q;
+    Q.bytes = d_bytes; Q.bytes_size = bytes_size; Q.soff = S.d_at; Q.slen = S.d_at + n; Q.bad = S.d_bad;
+    Q.table = P.d_table; Q.count = P.d_cnt + n;
+    Q.u_stream = P.d_map; Q.u_index = P.d_map + U; Q.u_base = P.d_cnt + 2 * n; Q.n_units = (int)units;
+    Q.slots = P.d_slots; Q.rbsp_len = P.d_len; Q.nal_header = P.d_map + 2 * U; Q.first = P.d_map + 3 * U; Q.rec = P.d_rec;
+    Q.sets = P.d_sets; Q.n = S.n; Q.want_w = want_w; Q.want_h = want_h;
+    if (units) {
+        ev = kt_begin(b, KT_PSET_UNIT, st);
+        hipLaunchKernelGGL(k_pset_unit, dim3((unsigned)units), dim3(64), 0, st, Q);
+        kt_end(b, KT_PSET_UNIT, ev, st);
+        ev = kt_begin(b, KT_PSET_PARSE, st);
+        hipLaunchKernelGGL(k_pset_parse, dim3((unsigned)((units + 63) / 64)), dim3(64), 0, st, Q);
+        kt_end(b, KT_PSET_PARSE, ev, st);
+    }
+    ev = kt_begin(b, KT_PSET_RESOLVE, st);
+    hipLaunchKernelGGL(k_pset_resolve, dim3(S.n), dim3(64), 0, st, Q);
+    kt_end(b, KT_PSET_RESOLVE, ev, st);
+    TRY(launched(b));
+    HIPCHK(b, hipStreamSynchronize(st));
+    return 0;
+}
+extern "C" int pcamv_gpu_batch_stream_param_sets(pcamv_batch_t *b, int32_t *status_out, pcamv_param_sets_t *sets_out, void *stream)
+{
+    if (!b) return PCAMV_EINVAL;
+    HIPCHK(b, hipSetDevice(b->device));
+    TRY(batch_live(b));
+    const StreamIndex &S = b->sx;
+    if (!S.ready) return fail(b, PCAMV_EINVAL, "no byte streams were handed to this batch yet (pcamv_gpu_batch_index_streams*)");
+    hipStream_t st = stream ? (hipStream_t)stream : b->ctx[0]->stream;
+    HIPCHK(b, hipDeviceSynchronize());              /* (steps under the sets that are replaced may be in flight) */
+    TRY(pset_run(b, S, S.bytes, S.bytes_size, b->ps, b->ctx[0]->F.mb_w, b->ctx[0]->F.mb_h, st));
+    const size_t n = (size_t)S.n;
+    if (status_out || sets_out) {
+        HostTmp<pcamv_param_sets_t> h(n);
+        if (!h) return fail(b, PCAMV_ENOMEM, "no memory for the sets of %zu streams", n);
+        HIPCHK(b, hipMemcpy(h, b->ps.d_sets, n * sizeof(pcamv_param_sets_t), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < n && status_out; i++) status_out[i] = h[i].status;
+        if (sets_out) memcpy(sets_out, h, n * sizeof(pcamv_param_sets_t));
+    }
+    b->ps.ready = 1;
+    return 0;
+}
+/* the parity probe: n streams of one host buffer through the index kernels (for their chunks) and the parameter-set kernels */
+extern "C" int pcamv_gpu_param_sets_device(pcamv_ctx_t *c, const uint8_t *bytes, size_t bytes_size, const int64_t *off, const int64_t *len, int n,
+                                           pcamv_param_sets_t *sets_out)
+{
+    if (!c || (!bytes && bytes_size) || !off || !len || !sets_out || n < 1 || bytes_size > ((size_t)1 << 40)) return PCAMV_EINVAL;
+    pcamv_batch *b = c->self;
+    HIPCHK(c, hipSetDevice(c->device));
+    DevTmp<uint8_t> d_bytes; DevTmp<long long> d_at;
+    HIPCHK(c, d_bytes.alloc(bytes_size ? bytes_size : 1)); HIPCHK(c, d_at.alloc(2 * (size_t)n));
+    if (bytes_size) HIPCHK(c, hipMemcpy(d_bytes, bytes, bytes_size, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_at, off, sizeof(int64_t) * n, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_at + n, len, sizeof(int64_t) * n, hipMemcpyHostToDevice));
+    StreamIndex S = StreamIndex();
+    StreamSets P = StreamSets();
+    int rc = stream_index_room(b, S, n, 1, 0, bytes_size);
+    if (!rc) rc = stream_index_run(b, S, d_bytes, bytes_size, d_at, d_at + n, 0, c->stream);
+    if (!rc) rc = pset_run(b, S, d_bytes, (long long)bytes_size, P, 0, 0, c->stream);
+    hipError_t e = hipSuccess;
+    if (!rc) e = hipMemcpy(sets_out, P.d_sets, (size_t)n * sizeof(pcamv_param_sets_t), hipMemcpyDeviceToHost);
+    stream_index_free(S);
+    stream_sets_free(P);
+    if (e != hipSuccess) return fail(c, PCAMV_EHIP, "param_sets_device: %s", hipGetErrorString(e));
+    return on_behalf(c, b, rc);
+}
+/* the inverse, host code: what the parsers read, written (pcamv_param_sets.h) */
+extern "C" int pcamv_gpu_write_sps(const pcamv_sps_t *sps, uint8_t *rbsp, size_t cap, size_t *len)
+{
+    if (len) *len = 0;
+    if (!sps || !len || (!rbsp && cap)) return PCAMV_EINVAL;
+    uint8_t tmp[PCAMV_PSET_RBSP_MAX];
+    const int n = ps_write_sps(*sps, tmp);
+    if (n < 0) return n;
+    if ((size_t)n > cap) return PCAMV_ENOMEM;
+    memcpy(rbsp, tmp, (size_t)n);
+    *len = (size_t)n;
+    return 0;
+}
+extern "C" int pcamv_gpu_write_pps(const pcamv_pps_t *pps, uint8_t *rbsp, size_t cap, size_t *len)
+{
+    if (len) *len = 0;
+    if (!pps || !len || (!rbsp && cap)) return PCAMV_EINVAL;
+    uint8_t tmp[PCAMV_PSET_RBSP_MAX];
+    const int n = ps_write_pps(*pps, tmp);
+    if (n < 0) return n;
+    if ((size_t)n > cap) return PCAMV_ENOMEM;
+    memcpy(rbsp, tmp, (size_t)n);
+    *len = (size_t)n;
+    return 0;
+}
+extern "C" int pcamv_gpu_rbsp_to_nal(const uint8_t *rbsp, size_t len, int nal_ref_idc, int nal_unit_type, uint8_t *nal, size_t cap, size_t *nal_len);
+extern "C" int pcamv_gpu_param_set_head(const pcamv_stream_params_t *params, int mb_w, int mb_h, int sps_id, int num_ref_frames, int profile_idc, int level_idc,
+                                        uint8_t *out, size_t cap, size_t *len)
+{
+    if (len) *len = 0;
+    if (!params || !len || (!out && cap) || !sws_params_ok(*params)) return PCAMV_EINVAL;
+    const pcamv_stream_params_t &P = *params;
+    pcamv_sps_t S = pcamv_sps_t();
+    S.profile_idc = profile_idc; S.level_idc = level_idc; S.sps_id = sps_id;
+    S.chroma_format_idc = 1; S.bit_depth_luma = 8; S.bit_depth_chroma = 8;
+    S.log2_max_frame_num = P.log2_max_frame_num; S.poc_type = P.poc_type; S.log2_max_poc_lsb = P.poc_type == 0 ? P.log2_max_poc_lsb : 0;
+    S.delta_pic_order_always_zero = P.poc_type == 1 ? !!P.delta_pic_order_always_zero : 0;
+    S.num_ref_frames = num_ref_frames; S.mb_w = mb_w; S.mb_h = mb_h; S.frame_mbs_only = 1; S.direct_8x8_inference = 1;
+    pcamv_pps_t Q = pcamv_pps_t();
+    Q.pps_id = P.pps_id; Q.sps_id = sps_id; Q.entropy_cabac = !!P.entropy_cabac; Q.pic_order_present = !!P.pic_order_present; Q.num_slice_groups = 1;
+    Q.num_ref_idx_l0_default = P.num_ref_idx_l0_default; Q.num_ref_idx_l1_default = 1; Q.weighted_pred = !!P.weighted_pred;
+    Q.pic_init_qp = P.pic_init_qp; Q.pic_init_qs = 26; Q.deblocking_filter_control_present = !!P.deblocking_filter_control_present;
+    Q.redundant_pic_cnt_present = !!P.redundant_pic_cnt_present;
+    uint8_t rs[PCAMV_PSET_RBSP_MAX], rp[PCAMV_PSET_RBSP_MAX];
+    const int ns = ps_write_sps(S, rs), np = ps_write_pps(Q, rp);
+    if (ns < 0) return ns;
+    if (np < 0) return np;
+    size_t a = 0, c2 = 0;
+    TRY(pcamv_gpu_rbsp_to_nal(rs, (size_t)ns, 3, 7, out, cap, &a));
+    TRY(pcamv_gpu_rbsp_to_nal(rp, (size_t)np, 3, 8, out + a, cap - a, &c2));
+    *len = a + c2;
     return 0;
 }
 extern "C" int pcamv_gpu_debug_slice_records(pcamv_ctx_t *c, pcamv_mb_t *out_mb, int *guard_intact)

@@ -25,6 +25,10 @@
  * parsers read, and k_stream_status puts the code of the first stage that failed where the parser put its own.  k_stream_window_unit
  * takes a window of units per context instead, one wavefront per unit, for the same kernels over contexts x slots jobs.
  *
+ * k_pset_unit, k_pset_parse, k_pset_resolve read every stream's SPS / PPS units into one table of parameter sets per context
+ * (pcamv_param_sets.h; the units are found by the instances of k_stream_scan / k_stream_prefix / k_stream_place made for SI_SEL_PSET), and
+ * k_slice_header_sets is k_slice_header under those tables in place of one parameter set for the batch.
+ *
  * k_write_pslice (pcamv_slice_write.hip) is the other direction: a CABAC P slice of every context's last step written on the device, one
  * wavefront per slice (pcamv_slice_write.h, which also describes a launch: WriteJobs).
  *
@@ -39,6 +43,7 @@
 #include "pcamv_slice_parse_cavlc.h"
 #include "pcamv_nal_unescape.h"
 #include "pcamv_stream_index.h"
+#include "pcamv_param_sets.h"
 #include "pcamv_slice_write.h"
 #include "pcamv_stream_write.h"
 
@@ -131,7 +136,9 @@ struct StreamJobs {
     long long *n_units, *n_slices, *cursor; unsigned long long *longest;
     int n;
 };
-SP_HD SiTable stream_table(const StreamJobs &J, int i) { const SiTable T = {J.table + (long long)i * J.stride, J.max_units, J.all, J.longest}; return T; }
+/* sel -- 0: the slice units; SI_SEL_PSET: the parameter-set units are what is counted and listed -- is a constant of each instance of the
+ * three kernels below, so the instances the index call launches hold no trace of the other selection */
+SP_HD SiTable stream_table(const StreamJobs &J, int i, int sel) { const SiTable T = {J.table + (long long)i * J.stride, J.max_units, J.all, J.longest, sel}; return T; }
 /* one wavefront: the chunks of every stream, their exclusive prefix.  Lane l owns streams [l * seg, (l + 1) * seg) and walks them one
  * after the other, so the kernel's time grows linearly with n (0.04 ms at 4096 streams): beyond some 10^5 streams of one call a scan over
  * several waves would be the next step */
@@ -178,32 +185,32 @@ static __device__ int stream_of_chunk(const StreamJobs &J, long long f, long lon
     }
     return -1;
 }
-static __global__ void __launch_bounds__(64) k_stream_scan(const StreamJobs J)
+template <int SEL> static __global__ void __launch_bounds__(64) k_stream_scan(const StreamJobs J)
 {
     __shared__ uint32_t s_win[SI_WIN_DWORDS];
     long long c = 0;
     const int i = stream_of_chunk(J, blockIdx.x, &c);
     if (i < 0) return;
     const SiWork W = {s_win, nullptr};
-    si_scan(W, J.bytes + J.off[i], J.len[i], c, 0, J.chunks + blockIdx.x, stream_table(J, i));
+    si_scan(W, J.bytes + J.off[i], J.len[i], c, 0, J.chunks + blockIdx.x, stream_table(J, i, SEL));
 }
-static __global__ void __launch_bounds__(64) k_stream_prefix(const StreamJobs J)
+template <int SEL> static __global__ void __launch_bounds__(64) k_stream_prefix(const StreamJobs J)
 {
     __shared__ SiChunk s_sc[64];
     const int i = blockIdx.x;
     if (J.bad[i]) return;
     const SiWork W = {nullptr, s_sc};
     const uint8_t *src = J.bytes + J.off[i];
-    si_prefix(W, src, J.len[i], J.chunks + J.chunk_base[i], si_chunks(src, J.len[i]), stream_table(J, i), J.n_units + i, J.n_slices + i);
+    si_prefix(W, src, J.len[i], J.chunks + J.chunk_base[i], si_chunks(src, J.len[i]), stream_table(J, i, SEL), J.n_units + i, J.n_slices + i);
 }
-static __global__ void __launch_bounds__(64) k_stream_place(const StreamJobs J)
+template <int SEL> static __global__ void __launch_bounds__(64) k_stream_place(const StreamJobs J)
 {
     __shared__ uint32_t s_win[SI_WIN_DWORDS];
     long long c = 0;
     const int i = stream_of_chunk(J, blockIdx.x, &c);
     if (i < 0) return;
     const SiWork W = {s_win, nullptr};
-    si_scan(W, J.bytes + J.off[i], J.len[i], c, 1, J.chunks + blockIdx.x, stream_table(J, i));
+    si_scan(W, J.bytes + J.off[i], J.len[i], c, 1, J.chunks + blockIdx.x, stream_table(J, i, SEL));
 }
 
 /* one step of the stream receiver: context i's next slice unit (table[i * max_units + cursor[i]], a unit of its stream bytes[soff[i] ..
@@ -220,6 +227,8 @@ struct StreamStep {
     /* a window of k units per context (k_stream_window_unit): the job arrays hold n * k entries, context-major (job i * k + w), `n` counts
      * jobs, and cursor_was is a copy of the cursors made before the launch -- what the slot waves read, while one lane moves `cursor` */
     const long long *cursor_was; int k;
+    /* k_slice_header_sets: the table of context i / sets_k, the entropy mode of the batch's contexts, and where the entry's mode goes */
+    const pcamv_param_sets_t *sets; int sets_k, want_cabac; int *entropy;
 };
 static __global__ void __launch_bounds__(64) k_stream_unit(const StreamStep J)
 {
@@ -281,6 +290,20 @@ static __global__ void __launch_bounds__(64) k_slice_header(const StreamStep J)
     J.start_bit[i] = sb; J.qp[i] = qp; J.frame_num[i] = fn;
     if (rc) { J.first[i] = rc; J.len[i] = -1; }         /* as the unescaper marks a unit that failed: the parser refuses it */
 }
+/* the same under the parameter sets of the slice's own stream: the table of context i / sets_k, the entry its pps_id names */
+static __global__ void __launch_bounds__(64) k_slice_header_sets(const StreamStep J)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= J.n) return;
+    J.entropy[i] = -1;
+    if (J.first[i]) return;
+    const long long off = J.off[i], len = J.len[i];
+    long long sb = -1; int qp = -1, fn = -1, mode = -1, rc = PCAMV_EINVAL;
+    if (off >= 0 && len >= 0 && len <= J.rbsp_size && off <= J.rbsp_size - len)
+        rc = pcamv_slice_header_read_sets(J.rbsp + off, len, J.nal_header[i], J.sets[i / J.sets_k], J.want_cabac, &sb, &qp, &fn, &mode);
+    J.start_bit[i] = sb; J.qp[i] = qp; J.frame_num[i] = fn; J.entropy[i] = mode;
+    if (rc) { J.first[i] = rc; J.len[i] = -1; }
+}
 /* (a window, k > 0: job i is slot i % k of context i / k, and the last slot's code is also the context's own word -- what k steps leave) */
 static __global__ void __launch_bounds__(64) k_stream_status(const int *__restrict__ first, int *__restrict__ status, int n, int *__restrict__ ctx_status, int k)
 {
@@ -288,6 +311,68 @@ static __global__ void __launch_bounds__(64) k_stream_status(const int *__restri
     if (i >= n) return;
     if (first[i]) status[i] = first[i];
     if (k > 0 && i % k == k - 1) ctx_status[i / k] = status[i];
+}
+
+/* ---- parameter sets.  Stream i is bytes[soff[i] .. + slen[i]); its units of type 7 / 8 are table[i * PCAMV_PSET_UNITS_MAX ..) (the first
+ * PCAMV_PSET_UNITS_MAX of count[i]).  The launch's units are numbered stream by stream: unit j is unit u_index[j] of stream u_stream[j],
+ * stream i's are [u_base[i], u_base[i + 1]).  Unit j's RBSP goes to its slot of PCAMV_PSET_UNIT_BYTES bytes, its record to rec[j] */
+struct PsetJobs {
+    const uint8_t *bytes; long long bytes_size;
+    const long long *soff, *slen; const int *bad;
+    const pcamv_unit_t *table; const long long *count;
+    const int *u_stream, *u_index; const long long *u_base; int n_units;
+    uint8_t *slots; long long *rbsp_len; int *nal_header, *first; PsRec *rec;
+    pcamv_param_sets_t *sets; int n, want_w, want_h;
+};
+/* one wavefront per unit: the unescaper of k_nal_to_rbsp into the unit's slot */
+static __global__ void __launch_bounds__(64) k_pset_unit(const PsetJobs J)
+{
+    __shared__ uint32_t s_win[NU_WIN_DWORDS], s_out[NU_OUT_DWORDS];
+    const int j = blockIdx.x, lane = threadIdx.x;
+    if (j >= J.n_units) return;
+    const NuWork W = {s_win, s_out};
+    const int i = J.u_stream[j], x = J.u_index[j];
+    int rc = PCAMV_EINVAL, done = 0;
+    if (i >= 0 && i < J.n && x >= 0 && x < PCAMV_PSET_UNITS_MAX && !J.bad[i]) {
+        const pcamv_unit_t u = J.table[(long long)i * PCAMV_PSET_UNITS_MAX + x];
+        const long long soff = J.soff[i], slen = J.slen[i];
+        if (u.off >= 0 && u.len >= 1 && u.len <= slen && u.off <= slen - u.len && soff >= 0 && slen <= J.bytes_size && soff <= J.bytes_size - slen) {
+            if (u.len > PCAMV_PSET_UNIT_BYTES) { rc = PCAMV_EUNSUP; if (lane == 0) J.nal_header[j] = u.nal_header; }
+            else rc = pcamv_nal_unescape(W, J.bytes + soff + u.off, u.len, J.slots + (long long)j * PCAMV_PSET_UNIT_BYTES, J.rbsp_len + j, J.nal_header + j);
+            done = 1;
+        }
+    }
+    if (lane == 0) {
+        if (!done) J.nal_header[j] = -1;
+        if (rc) J.rbsp_len[j] = -1;
+        J.first[j] = rc;
+    }
+}
+/* one lane per unit: the RBSP parsed into the unit's record; a unit that failed before keeps its code */
+static __global__ void __launch_bounds__(64) k_pset_parse(const PsetJobs J)
+{
+    const int j = blockIdx.x * 64 + threadIdx.x;
+    if (j >= J.n_units) return;
+    const long long len = J.rbsp_len[j];
+    const int hdr = J.nal_header[j];
+    if (J.first[j] || len < 0 || len > PCAMV_PSET_UNIT_BYTES) {
+        PsRec r;
+        memset(&r, 0, sizeof(r));
+        r.code = J.first[j] ? J.first[j] : PCAMV_EINVAL; r.type = hdr < 0 ? 0 : hdr & 31;
+        J.rec[j] = r;
+        return;
+    }
+    ps_parse_unit(J.slots + (long long)j * PCAMV_PSET_UNIT_BYTES, len, hdr, J.rec + j);
+}
+/* one wavefront per stream: its records resolved into its table */
+static __global__ void __launch_bounds__(64) k_pset_resolve(const PsetJobs J)
+{
+    const int i = blockIdx.x;
+    if (i >= J.n) return;
+    const long long base = J.u_base[i], have = J.u_base[i + 1] - base;
+    long long count = J.bad[i] ? 0 : J.count[i];
+    if (count < have) count = have;             /* (never: the host listed min(count, PCAMV_PSET_UNITS_MAX) of them) */
+    ps_resolve(J.rec + base, have < PCAMV_PSET_UNITS_MAX ? have : count, J.bad[i] ? PCAMV_EINVAL : 0, J.want_w, J.want_h, J.sets + i);
 }
 
 /* ---- the sender's byte streams (pcamv_stream_write.h), one lane per context.  ctx, table, slot, w_len are the library's; bytes and len

@@ -45,7 +45,10 @@ static_assert(SI_CHUNK % SI_PASS == 0 && SI_CHUNK >= SI_PASS, "a chunk is whole 
  * si_prefix: the same summed / latest over the chunks before it */
 struct SiChunk { long long units, slices, nz, q; };
 struct SiWork { uint32_t *win; SiChunk *sc; };          /* LDS of the wave: SI_WIN_DWORDS dwords, 64 summaries */
-struct SiTable { pcamv_unit_t *units; long long max_units; int all; unsigned long long *longest; };   /* all: every unit, else the slice units */
+/* all: every unit, else the selected ones -- the slice units, or with sel == SI_SEL_PSET the units of nal_unit_type 7 and 8, which then
+ * are what "slice unit" and `slices` read as throughout (pcamv_param_sets.h) */
+#define SI_SEL_PSET 1
+struct SiTable { pcamv_unit_t *units; long long max_units; int all; unsigned long long *longest; int sel; };
 
 SP_HD long long si_chunks(const uint8_t *src, long long len) { return len > 0 ? (len + (long long)((uintptr_t)src & 3u) + SI_CHUNK - 1) / SI_CHUNK : 0; }
 SP_HD int si_top(uint64_t m) { return 63 - __builtin_clzll(m); }         /* m != 0 */
@@ -63,13 +66,21 @@ SP_HD int si_kind(int h, int p0)
     if (st == 0 || st == 5) return PCAMV_UNIT_PSLICE;
     return st == 2 || st == 7 ? PCAMV_UNIT_OTHER : PCAMV_UNIT_UNSUP;
 }
+/* is a unit of this header byte and first payload byte one the table selects */
+SP_HD int si_selected(const SiTable &T, int h, int p0)
+{
+    if (T.sel == SI_SEL_PSET) return h >= 0 && ((h & 31) == 7 || (h & 31) == 8);
+    return si_kind(h, p0) != PCAMV_UNIT_OTHER;
+}
 /* the unit src[s, e) into its place of the table: number u among all units, the slices-th slice unit if it is one */
 SP_HD void si_emit(const SiTable &T, const uint8_t *src, long long s, long long e, long long u, long long slices_before)
 {
     if (e < s) e = s;
     const long long n = e - s;
     const int h = n > 0 ? (int)src[s] : -1, kind = si_kind(h, n > 1 ? (int)src[s + 1] : -1);
-    const long long at = T.all ? u : kind != PCAMV_UNIT_OTHER ? slices_before : -1;
+    /* (with sel a constant 0 this is the kind just made: the index call's instances read as they did without the other selection) */
+    const int picked = T.sel == SI_SEL_PSET ? si_selected(T, h, -1) : kind != PCAMV_UNIT_OTHER;
+    const long long at = T.all ? u : picked ? slices_before : -1;
     if (at < 0 || at >= T.max_units) return;
     pcamv_unit_t *o = T.units + at;
     o->off = s; o->len = n; o->nal_header = h; o->kind = kind;
@@ -123,7 +134,7 @@ SP_HD void si_scan(const SiWork &W, const uint8_t *src, long long len, long long
                 const int in = i >= 0 && i < hi;
                 const int pre = in && i >= 2 && b3 == 0x010000u;
                 int sl = 0;
-                if (pre) sl = si_kind(i + 1 < len ? (int)src[i + 1] : -1, i + 2 < len ? (int)src[i + 2] : -1) != PCAMV_UNIT_OTHER;
+                if (pre) sl = si_selected(T, i + 1 < len ? (int)src[i + 1] : -1, i + 2 < len ? (int)src[i + 2] : -1);
                 NU_VOTE(mp[k], l, pre); NU_VOTE(ms[k], l, sl); NU_VOTE(mz[k], l, in && (b3 >> 16) != 0);
             }
         }

@@ -390,6 +390,167 @@ def write_slice_header(params, fields):
     return np.unpackbits(out, bitorder="big")[:n.value].tolist()
 
 
+FEATURE_PARAM_SETS = 0x200      # SPS / PPS read on the device, per stream: Batch.stream_param_sets, Batch.extract_stream_*_sets
+PSET_UNITS_MAX, PSET_UNIT_BYTES, PSET_SPS_MAX, PSET_PPS_MAX, PSET_RBSP_MAX = 64, 1024, 4, 8, 384       # PCAMV_PSET_*
+ENOMEM = -3
+
+
+class _Members(C.Structure):
+    """a C struct of int32 members that compares and prints by them"""
+
+    def members(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+    def __eq__(self, other):
+        return type(other) is type(self) and bytes(self) == bytes(other)
+
+    def __ne__(self, other):
+        return not self == other
+
+    __hash__ = None
+
+    def __repr__(self):
+        return f"{type(self).__name__}({', '.join(f'{k}={v}' for k, v in self.members().items())})"
+
+
+class Sps(_Members):
+    """pcamv_sps_t: seq_parameter_set_data() up to vui_parameters_present_flag, values not "minus" forms (log2_* 4 .. 16, mb_w / mb_h
+    counts)"""
+    _fields_ = [(n, C.c_int32) for n in ("profile_idc", "constraint_flags", "level_idc", "sps_id", "chroma_format_idc", "bit_depth_luma",
+                                         "bit_depth_chroma", "transform_bypass", "seq_scaling_matrix_present", "log2_max_frame_num", "poc_type",
+                                         "log2_max_poc_lsb", "delta_pic_order_always_zero", "offset_for_non_ref_pic", "offset_for_top_to_bottom_field",
+                                         "num_ref_frames_in_poc_cycle", "num_ref_frames", "gaps_in_frame_num_allowed", "mb_w", "mb_h", "frame_mbs_only",
+                                         "direct_8x8_inference", "frame_cropping", "crop_left", "crop_right", "crop_top", "crop_bottom",
+                                         "vui_parameters_present")]
+
+    def __init__(self, **kw):
+        d = dict(profile_idc=66, level_idc=30, chroma_format_idc=1, bit_depth_luma=8, bit_depth_chroma=8, log2_max_frame_num=4, poc_type=2,
+                 num_ref_frames=1, mb_w=11, mb_h=9, frame_mbs_only=1, direct_8x8_inference=1)
+        d.update(kw)
+        super().__init__(**d)
+
+
+class Pps(_Members):
+    """pcamv_pps_t: pic_parameter_set_rbsp(); num_ref_idx_* are counts, pic_init_qp / qs 26 + the coded value; without the optional
+    tail (has_tail 0) the second chroma offset is the first"""
+    _fields_ = [(n, C.c_int32) for n in ("pps_id", "sps_id", "entropy_cabac", "pic_order_present", "num_slice_groups", "num_ref_idx_l0_default",
+                                         "num_ref_idx_l1_default", "weighted_pred", "weighted_bipred_idc", "pic_init_qp", "pic_init_qs",
+                                         "chroma_qp_index_offset", "deblocking_filter_control_present", "constrained_intra_pred",
+                                         "redundant_pic_cnt_present", "has_tail", "transform_8x8_mode", "pic_scaling_matrix_present",
+                                         "second_chroma_qp_index_offset")]
+
+    def __init__(self, **kw):
+        d = dict(entropy_cabac=1, num_slice_groups=1, num_ref_idx_l0_default=1, num_ref_idx_l1_default=1, pic_init_qp=26, pic_init_qs=26)
+        d.update(kw)
+        d.setdefault("second_chroma_qp_index_offset", d.get("chroma_qp_index_offset", 0))
+        super().__init__(**d)
+
+
+class ParamSets(C.Structure):
+    """pcamv_param_sets_t: the parameter sets of one stream, resolved -- status, the picture size in macroblocks, n_pps entries sorted by
+    pps_id, each a StreamParams (a PPS merged with the SPS it names)"""
+    _fields_ = [("status", C.c_int32), ("mb_w", C.c_int32), ("mb_h", C.c_int32), ("n_pps", C.c_int32), ("pps", StreamParams * PSET_PPS_MAX)]
+
+    def entries(self):
+        """the n_pps entries as dicts"""
+        return [{n: getattr(self.pps[k], n) for n, _ in StreamParams._fields_} for k in range(self.n_pps)]
+
+    def entry(self, pps_id):
+        """the StreamParams of pps_id, None if the stream has none"""
+        for k in range(self.n_pps):
+            if self.pps[k].pps_id == pps_id:
+                return self.pps[k]
+        return None
+
+    def __eq__(self, other):
+        return isinstance(other, ParamSets) and bytes(self) == bytes(other)
+
+    def __ne__(self, other):
+        return not self == other
+
+    __hash__ = None
+
+    def __repr__(self):
+        return f"ParamSets(status={self.status}, mb_w={self.mb_w}, mb_h={self.mb_h}, entries={self.entries()})"
+
+
+def _bytes_arg(data):
+    return np.frombuffer(bytes(data), np.uint8) if len(data) else np.zeros(1, np.uint8)
+
+
+def parse_sps(rbsp):
+    """pcamv_gpu_parse_sps: (return code, Sps) of an SPS unit's RBSP (behind the header byte, unescaped); the Sps is all zeros when the
+    code is not 0"""
+    out = Sps()
+    fn = load_library().pcamv_gpu_parse_sps
+    fn.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
+    rc = fn(_p(_bytes_arg(rbsp)), len(rbsp), C.byref(out))
+    return rc, out
+
+
+def parse_pps(rbsp):
+    """pcamv_gpu_parse_pps: (return code, Pps) of a PPS unit's RBSP"""
+    out = Pps()
+    fn = load_library().pcamv_gpu_parse_pps
+    fn.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
+    rc = fn(_p(_bytes_arg(rbsp)), len(rbsp), C.byref(out))
+    return rc, out
+
+
+def stream_param_sets(data):
+    """pcamv_gpu_stream_param_sets: the ParamSets of an Annex B byte stream (its status is the return code)"""
+    out = ParamSets()
+    fn = load_library().pcamv_gpu_stream_param_sets
+    fn.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
+    rc = fn(_p(_bytes_arg(data)), len(data), C.byref(out))
+    if rc != out.status:
+        raise PcamvError(f"pcamv_gpu_stream_param_sets failed: {rc}")
+    return out
+
+
+def parse_slice_header_sets(rbsp, nal_header, sets):
+    """pcamv_gpu_parse_slice_header_sets: parse_slice_header under the entry of `sets` (a ParamSets) that the header's pps_id names:
+    (return code, start_bit, slice QP, frame_num, the entry's entropy mode or -1)"""
+    sb, qp, fn_, mode = C.c_int64(), C.c_int32(), C.c_int32(), C.c_int32()
+    fn = load_library().pcamv_gpu_parse_slice_header_sets
+    fn.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    rc = fn(_p(_bytes_arg(rbsp)), len(rbsp), int(nal_header), C.byref(sets), C.byref(sb), C.byref(qp), C.byref(fn_), C.byref(mode))
+    return rc, sb.value, qp.value, fn_.value, mode.value
+
+
+def _write_set(call, what):
+    out = np.zeros(PSET_RBSP_MAX, np.uint8)
+    n = C.c_size_t()
+    fn = getattr(load_library(), call)
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    rc = fn(C.byref(what), _p(out), len(out), C.byref(n))
+    return rc, bytes(out[:n.value])
+
+
+def write_sps(sps):
+    """pcamv_gpu_write_sps: (return code, the RBSP of an SPS unit for an Sps) -- what parse_sps reads, vui_parameters_present_flag 0,
+    rbsp_trailing_bits added; the parser's code and b"" for what the parser refuses"""
+    return _write_set("pcamv_gpu_write_sps", sps)
+
+
+def write_pps(pps):
+    """pcamv_gpu_write_pps: (return code, the RBSP of a PPS unit for a Pps), without the optional tail"""
+    return _write_set("pcamv_gpu_write_pps", pps)
+
+
+def param_set_head(params, mb_w, mb_h, sps_id=0, num_ref_frames=1, profile_idc=100, level_idc=30):
+    """pcamv_gpu_param_set_head: an SPS unit and a PPS unit for a StreamParams and a picture size in macroblocks, each with a long
+    start code and emulation prevention -- what Batch.stream_open takes as head"""
+    out = np.zeros(2 * (6 + PSET_RBSP_MAX * 3 // 2), np.uint8)
+    n = C.c_size_t()
+    fn = load_library().pcamv_gpu_param_set_head
+    fn.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    rc = fn(C.byref(params), int(mb_w), int(mb_h), int(sps_id), int(num_ref_frames), int(profile_idc), int(level_idc), _p(out), len(out), C.byref(n))
+    if rc:
+        raise PcamvError(f"pcamv_gpu_param_set_head failed: {rc}")
+    return bytes(out[:n.value])
+
+
 def features():
     """pcamv_gpu_features: mask of FEATURE_* the loaded library has"""
     lib = load_library()
@@ -671,6 +832,22 @@ class Encoder:
         self._chk(fn(self.ctx, _p(data if len(data) else pad), len(data), _p(off), _p(length), _p(nal_header), n, C.byref(params), _p(rc), _p(sb), _p(qp), _p(fnum)),
                   "slice_headers_device")
         return rc, sb, qp, fnum
+
+    def param_sets_device(self, data, off, length):
+        """pcamv_gpu_param_sets_device: the parameter sets of the byte streams data[off[i] : off[i] + length[i]] read by the index
+        kernels' parameter-set selection, k_pset_unit, k_pset_parse and k_pset_resolve -- the parity probe of Batch.stream_param_sets,
+        to be compared with stream_param_sets.  Returns a list of ParamSets"""
+        data, off, length = np.ascontiguousarray(data, np.uint8), np.ascontiguousarray(off, np.int64), np.ascontiguousarray(length, np.int64)
+        n = len(off)
+        out = np.full((n + 1) * C.sizeof(ParamSets), 0xA5, np.uint8)         # a guard entry behind the n the library fills
+        pad = np.zeros(1, np.uint8)
+        fn = self.lib.pcamv_gpu_param_sets_device
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        self._chk(fn(self.ctx, _p(data if len(data) else pad), len(data), _p(off), _p(length), n, _p(out)), "param_sets_device")
+        if not (out[n * C.sizeof(ParamSets):] == 0xA5).all():
+            raise PcamvError("param_sets_device wrote behind the sets it was asked for")
+        raw = out.tobytes()
+        return [ParamSets.from_buffer_copy(raw[i * C.sizeof(ParamSets):(i + 1) * C.sizeof(ParamSets)]) for i in range(n)]
 
     def slice_headers_write_device(self, cases):
         """pcamv_gpu_slice_headers_write_device: the P slice headers of `cases`, a list of (StreamParams, SliceFields), written by
@@ -955,6 +1132,41 @@ class Batch:
         fn.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
         self._slice_chk(fn(self.b, C.byref(params), emrate, nal_header.data_ptr() if nal_header is not None else None, C.c_void_p(stream or None)),
                         "batch_extract_stream_step")
+
+    def stream_param_sets(self, stream=0):
+        """pcamv_gpu_batch_stream_param_sets: behind an index call, the SPS / PPS units of every context's indexed stream found,
+        unescaped, parsed and resolved on the device; the sets stay there for the *_sets calls until the next index call.  Synchronises;
+        returns (status per context as int32 -- EUNSUP also where the stream's picture size is not the context's --, a list of
+        ParamSets)"""
+        n = len(self.encs)
+        status, sets = np.zeros(n, np.int32), (ParamSets * n)()
+        fn = self.lib.pcamv_gpu_batch_stream_param_sets
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._slice_chk(fn(self.b, _p(status), sets, C.c_void_p(stream or None)), "batch_stream_param_sets")
+        return status, [ParamSets.from_buffer_copy(bytes(sets[i])) for i in range(n)]
+
+    def extract_stream_step_sets(self, emrate, stream=0, nal_header=None):
+        """pcamv_gpu_batch_extract_stream_step_sets: extract_stream_step with every slice header read under its own context's
+        parameter sets (stream_param_sets) in place of one StreamParams for the batch.  A context whose sets have a non-zero status
+        takes its unit, reports that status and appends nothing"""
+        if nal_header is not None and (not _is_device_tensor(nal_header) or not nal_header.is_cuda or nal_header.element_size() != 4 or
+                                       not nal_header.is_contiguous() or nal_header.numel() != len(self.encs)):
+            raise PcamvError(f"nal_header: int32, contiguous, on the device, one entry per context ({len(self.encs)})")
+        fn = self.lib.pcamv_gpu_batch_extract_stream_step_sets
+        fn.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
+        self._slice_chk(fn(self.b, emrate, nal_header.data_ptr() if nal_header is not None else None, C.c_void_p(stream or None)),
+                        "batch_extract_stream_step_sets")
+
+    def extract_stream_window_sets(self, emrate, k, nal_header=None, stream=0):
+        """pcamv_gpu_batch_extract_stream_window_sets: extract_stream_window under every context's own parameter sets"""
+        if nal_header is not None and (not _is_device_tensor(nal_header) or not nal_header.is_cuda or nal_header.element_size() != 4 or
+                                       not nal_header.is_contiguous() or nal_header.numel() != len(self.encs) * int(k)):
+            raise PcamvError(f"nal_header: int32, contiguous, on the device, one entry per context and slot ({len(self.encs)} x {int(k)})")
+        fn = self.lib.pcamv_gpu_batch_extract_stream_window_sets
+        fn.argtypes = [C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_void_p]
+        self._slice_chk(fn(self.b, emrate, int(k), nal_header.data_ptr() if nal_header is not None else None, C.c_void_p(stream or None)),
+                        "batch_extract_stream_window_sets")
+        self._window_k = int(k)
 
     def stream_window(self, k):
         """pcamv_gpu_batch_stream_window: reserve the per-slot memory of windows of up to k units per context (1 .. STREAM_WINDOW_MAX;
