@@ -346,6 +346,7 @@ int pcamv_gpu_abi_version(void);
 #define PCAMV_FEATURE_STREAM_WRITER 0x80u       /* the sender writes Annex B byte streams: slice headers and unit placement on the device */
 #define PCAMV_FEATURE_STREAM_WINDOW 0x100u      /* the receiver on byte streams takes a window of slice units per context in one call */
 #define PCAMV_FEATURE_PARAM_SETS 0x200u        /* SPS / PPS read on the device, per stream: the *_param_sets and *_sets calls at the end of this file */
+#define PCAMV_FEATURE_VIDEO 0x400u      /* one video of many chains: per-chain heads, streams joined, a video cut at its IDR units on the device */
 unsigned pcamv_gpu_features(void);
 
 /* ---- Payload path: the caller's bits through the device-resident entry points, and back out on the device ----
@@ -790,6 +791,72 @@ int pcamv_gpu_batch_extract_stream_step_sets(pcamv_batch_t *batch, float emrate,
 int pcamv_gpu_batch_extract_stream_window_sets(pcamv_batch_t *batch, float emrate, int k, int32_t *nal_header, void *stream);
 int pcamv_gpu_param_sets_device(pcamv_ctx_t *ctx, const uint8_t *bytes, size_t bytes_size, const int64_t *off, const int64_t *len, int n,
                                 pcamv_param_sets_t *sets_out);
+
+/* ---- One video of many chains: streams joined on the sender, the video cut at IDR units on the receiver (PCAMV_FEATURE_VIDEO) ----
+ *
+ * A chain is one closed GOP; a video is the chains' streams behind each other, each with an IDR picture of its own at its head.  The
+ * calls above write and read one stream per context.  With these the sender gives every context its own head, appends the contexts'
+ * streams to one video on the device, and the receiver is handed that video and nothing else: GOP g goes to context g - first_gop.  As
+ * everywhere here the host function is the definition on every input, valid or not.
+ *
+ * annexb_gops, host code.  U[0 .. m) are the units of bytes[0, len) as pcamv_gpu_annexb_index lists them; the type of a unit is
+ * nal_header & 31, an empty unit has none; VCL means types 1 .. 5.  Unit u opens a GOP iff its type is 5 and the nearest VCL unit
+ * before it, if there is one, is not of type 5: the IDR slices of one picture, and IDR pictures directly behind each other, stay in one
+ * GOP.  The GOP's first unit f is the unit behind that nearest VCL unit (0 if there is none), so delimiters, SEI and parameter sets in
+ * front of the IDR unit belong to the GOP; its first byte is U[f - 1].off + U[f - 1].len (0 for f = 0), so the zeros and the start code
+ * go with the unit they introduce.  GOP g is the bytes from its first byte to the next GOP's first byte, or to len; n_units likewise
+ * counts to the next GOP's first unit, or to m.  *preamble: the bytes in front of the first GOP (units before any IDR picture, which
+ * belong to no context), len if there is no GOP.  gops[cap] receives the first cap GOPs, *n_gops counts them all. */
+typedef struct pcamv_gop_t { int64_t off, len, first_unit, n_units; } pcamv_gop_t;
+int pcamv_gpu_annexb_gops(const uint8_t *bytes, size_t len, pcamv_gop_t *gops, size_t cap, int64_t *n_gops, int64_t *preamble);
+/* stream_open_heads: pcamv_gpu_batch_stream_open with a head per context.  `heads` is a borrowed device buffer of heads_size bytes (at
+ * most 2^40) that the queued work reads; head_off / head_len are device int64 arrays of one entry per context, read by this call alone
+ * like off / cap.  Observationally the call is stream_open with head = heads[head_off[i] .. + head_len[i]) for context i, its refusal
+ * rules and len[i] included; a context whose head does not lie inside `heads`, is longer than 2^24 or does not fit its region gets len 0
+ * and PCAMV_EINVAL in every step, and nothing is written for it.  The decision is made on the device, one lane per context
+ * (k_stream_open_heads); the bytes go through k_stream_copy: one wavefront per PCAMV_STREAM_CHUNK destination bytes of a head, whole
+ * aligned dwords (16 bytes per lane where all of them are the head's) and single bytes at the two ends only.  The call waits once for
+ * `stream`, as stream_open does, and for none of its kernels.
+ *
+ * join_streams: behind an open of either kind (before one: PCAMV_EINVAL).  video_off (device int64[1]) and video_len (device int64[1],
+ * in and out) say where in `video` (a borrowed device buffer of video_size bytes) the video begins and how long it is so far; the
+ * streams of contexts 0 .. n - 1, as long as they are on `stream` at that point, are appended in context order and video_len grows by
+ * their sum.  placed (device int64[n], optional) receives where each context's bytes went, counted from video_off, -1 for a context whose
+ * stream is empty or whose open was refused.  Such a context contributes nothing, so THE GOPS BEHIND IT MOVE UP BY ONE in the video:
+ * `placed` is how the caller learns of it.  If video_off or video_len is negative or the sum does not fit video_size, nothing is written,
+ * video_len stays, every placed[i] is -1 and the status is PCAMV_ENOMEM.  pcamv_gpu_batch_join_status synchronises and returns the last
+ * join's status as its value.  `video` overlapping the open buffer, or an open buffer of more than 2^40 bytes: PCAMV_EINVAL, judged on
+ * the host before anything is queued.  The call does not synchronise: it queues k_stream_join (one wavefront: a lane-parallel prefix over
+ * the lengths), k_stream_copy_plan and k_stream_copy.  Appending is what lets a video of more GOPs than contexts be written in rounds.
+ *
+ * index_video_device: off / len are device int64[1] -- what a join left can be handed over as it is -- and describe one video inside
+ * `bytes` (borrowed until the next index call).  Observationally: pcamv_gpu_annexb_gops on the video, then
+ * pcamv_gpu_batch_index_streams_device with context i's stream set to GOP first_gop + i; a context past the last GOP gets the length 0,
+ * so its count is 0 and every step is PCAMV_EEOF.  *n_gops / *preamble (host, optional) are the video's, whatever first_gop is.  A video
+ * that does not lie inside `bytes`: PCAMV_EINVAL.  On the device the index kernels list ALL units of the video into a table sized by the
+ * counts their first scan found (the prefix over the one long stream's chunks runs in two levels on many wavefronts, k_video_prefix_*;
+ * k_stream_prefix walks a stream's chunks with one); k_video_cut, one wavefront, walks it in passes of 64 units and writes every context's (off, len), which
+ * the index kernels then take as they take a caller's.  TWO host synchronisations: one for the unit count that sizes the table, one at
+ * the end as in every index call.  One video per call.  index_video is the same on host bytes, staged with one copy.
+ * Behind an index_video call stream_param_sets resolves the parameter sets of the VIDEO once, by the rules above (units of type 7 / 8
+ * anywhere in it, position not mattering), and every context reads its slice headers under that one table; status_out / sets_out return
+ * it per context.  GOPs behind the first often carry no parameter sets of their own.  Behind a plain index call nothing changes; an index
+ * call of either kind decides which holds.
+ * video_gops_device: the parity probe; n videos of one host buffer through the same kernels, gops_out n tables of cap_per_video +
+ * PCAMV_UNIT_GUARD entries each (every byte 0xA5 beforehand; the first min(n_gops, cap_per_video) are filled), n_gops[i] / preamble[i]
+ * as annexb_gops gives them (both PCAMV_EINVAL for a video outside the buffer).  Synchronises. */
+int pcamv_gpu_batch_stream_open_heads(pcamv_batch_t *batch, void *bytes, size_t bytes_size, const int64_t *off, const int64_t *cap, int64_t *len,
+                                      const pcamv_stream_params_t *params, const pcamv_stream_write_t *wr, const void *heads, size_t heads_size,
+                                      const int64_t *head_off, const int64_t *head_len, void *stream);
+int pcamv_gpu_batch_join_streams(pcamv_batch_t *batch, void *video, size_t video_size, const int64_t *video_off, int64_t *video_len, int64_t *placed,
+                                 void *stream);
+int pcamv_gpu_batch_join_status(pcamv_batch_t *batch);
+int pcamv_gpu_batch_index_video_device(pcamv_batch_t *batch, const void *bytes, size_t bytes_size, const int64_t *off, const int64_t *len,
+                                       int64_t first_gop, int64_t max_units, int64_t *n_gops, int64_t *preamble, int64_t *n_slices_out, void *stream);
+int pcamv_gpu_batch_index_video(pcamv_batch_t *batch, const uint8_t *bytes, size_t len, int64_t first_gop, int64_t max_units, int64_t *n_gops,
+                                int64_t *preamble, int64_t *n_slices_out, void *stream);
+int pcamv_gpu_video_gops_device(pcamv_ctx_t *ctx, const uint8_t *bytes, size_t bytes_size, const int64_t *off, const int64_t *len, int n,
+                                pcamv_gop_t *gops_out, int64_t cap_per_video, int64_t *n_gops, int64_t *preamble);
 
 #ifdef __cplusplus
 }

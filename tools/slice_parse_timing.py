@@ -49,6 +49,15 @@ the medians, the parent's own spread and whether this library's median is slower
 profiles/param_sets_timing.json, one line per entropy mode.
 
     python tools/slice_parse_timing.py --param-sets [--parent-lib PATH] [--cavlc] [--counts 256,4096] [--reps 5] [--out profiles/param_sets_timing.json]
+
+With --video one video of many chains: 256 and 4096 chains of a head -- SPS, PPS and a stand-in IDR unit of 24 KiB, a CIF IDR
+picture's size -- and the same 8 frames.  In one run, the two of each pair taking turns within every repetition, each call between two
+synchronisations on the host clock (median, minimum and maximum of the repetitions) and its kernels by hipEvents: Batch.stream_open_heads
+against Batch.stream_open with one head of the same length; Batch.join_streams against a plain device-to-device copy of the same bytes
+(k_stream_copy's GB/s is its bytes over its own time); Batch.index_video_device against Batch.index_streams_device given the GOPs' (off,
+len) by the host, and against pcamv_gpu_annexb_gops on one host thread.  Written to profiles/video_timing.json, one line per entropy mode.
+
+    python tools/slice_parse_timing.py --video [--cavlc] [--counts 256,4096] [--reps 5] [--out profiles/video_timing.json]
 """
 import argparse
 import ctypes as C
@@ -559,6 +568,124 @@ def write_stream_sweep(args, pcamv_amd, np, torch, mode):
     return out
 
 
+def video_sweep(args, pcamv_amd, np, torch, out, slice_data, qp):
+    """--video: one entry per count of chains.  A chain is a head -- SPS, PPS and a stand-in IDR unit of a CIF IDR picture's size --
+    and 8 frames.  In one run, the members of each pair taking turns within every repetition, each call between two synchronisations
+    on the host clock and its kernels by hipEvents: stream_open_heads / stream_open with one head of the same length; join_streams / a
+    plain device-to-device copy of the same bytes; index_video_device / index_streams_device given the GOPs' (off, len) by the host,
+    and pcamv_gpu_annexb_gops on one host thread"""
+    dev = torch.device("cuda", 0)
+    frames, idr_bytes = 8, 24 * 1024
+    sp, units, body, _ = frames_stream(args, pcamv_amd, np, slice_data, qp, frames)
+    rng = np.random.default_rng(1)
+    head = pcamv_amd.param_set_head(sp, out["width"] // 16, out["height"] // 16) + b"\x00\x00\x00\x01\x65" + bytes(rng.integers(0x80, 256, idr_bytes).astype(np.uint8))
+    chain = head + body
+    out.update(kernel="k_stream_copy", frames=frames, head_bytes=len(head), chain_bytes=len(chain), chunk=pcamv_amd.stream_chunk())
+    wr = pcamv_amd.StreamWrite(nal_ref_idc=2, slice_type=5, first_pic=1, first_i_frame=1)
+    p = pcamv_amd.param_default(out["width"], out["height"])
+    pcamv_amd.param_parse(p, "subme", 5)
+    p.b_cabac = 0 if args.cavlc else 1
+    lib = pcamv_amd.load_library()
+    lib.pcamv_gpu_annexb_gops.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    med = lambda v: sorted(v)[len(v) // 2]                  # noqa: E731
+    stat = lambda v: dict(median_ms=med(v), min_ms=min(v), max_ms=max(v))      # noqa: E731
+    encs = []
+    for n in [int(v) for v in args.counts.split(",")]:
+        while len(encs) < n:
+            encs.append(pcamv_amd.Encoder(p))
+        batch = pcamv_amd.Batch(encs[:n])
+        region = (len(chain) + 64 + 3) | 1                  # every region at an odd offset
+        data = torch.zeros(n * region + 16, dtype=torch.uint8, device=dev)
+        off = torch.arange(n, dtype=torch.int64, device=dev) * region + 1
+        cap = torch.full((n,), region - 2, dtype=torch.int64, device=dev)
+        length = torch.zeros(n, dtype=torch.int64, device=dev)
+        stride = (len(chain) + 5) | 1
+        blob = torch.from_numpy(np.tile(np.frombuffer(chain + bytes(stride - len(chain)), np.uint8), n)).to(dev)   # every chain's own bytes, at odd offsets
+        h_off = torch.arange(n, dtype=torch.int64, device=dev) * stride
+        h_head, h_chain = (torch.full((n,), v, dtype=torch.int64, device=dev) for v in (len(head), len(chain)))
+        video = torch.zeros(n * len(chain) + 64, dtype=torch.uint8, device=dev)
+        plain = torch.zeros(n * len(chain), dtype=torch.uint8, device=dev)
+        voff, vlen = torch.zeros(1, dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.int64, device=dev)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+
+        def timed(call, kernels=()):
+            """the call between two synchronisations: (wall ms, the summed hipEvent time of each named kernel's launches)"""
+            for k in kernels:
+                batch.kernel_time(k, reset=True)
+            torch.cuda.synchronize()
+            w0 = time.perf_counter()
+            call()
+            torch.cuda.synchronize()
+            w = (time.perf_counter() - w0) * 1e3
+            return w, {k: ms * launches for k, (ms, launches) in ((k, batch.kernel_time(k, reset=True)) for k in kernels)}
+
+        def plain_copy():
+            e0.record(); plain.copy_(video[:plain.numel()]); e1.record()
+
+        index_kernels = ("k_stream_plan", "k_stream_scan", "k_stream_prefix", "k_stream_place")
+        g_off = torch.arange(n, dtype=torch.int64, device=dev) * len(chain)     # what a host that had cut the video would hand over
+        found = {}
+
+        def index_video():
+            found["video"] = batch.index_video_device(video, voff, vlen, max_units=16)
+
+        def index_streams():
+            found["streams"] = batch.index_streams_device(video, g_off, h_chain, max_units=16)
+
+        calls = dict(open_heads=(lambda: batch.stream_open_heads(data, off, cap, length, sp, wr, blob, h_off, h_head), ("k_stream_open_heads", "k_stream_copy_plan", "k_stream_copy")),
+                     open=(lambda: batch.stream_open(data, off, cap, length, sp, wr, head=head), ("k_stream_open",)),
+                     join=(lambda: batch.join_streams(video, voff, vlen), ("k_stream_join", "k_stream_copy_plan", "k_stream_copy")),
+                     plain=(plain_copy, ()),
+                     index_video=(index_video, index_kernels + ("k_video_cut",)), index_streams=(index_streams, index_kernels))
+        wall, kernel = {k: [] for k in calls}, {k: [] for k in calls}
+        plain_event_ms = []
+        for t in range(args.reps + 1):                      # the first round is not timed: allocations, code load
+            for pair in (("open_heads", "open"), ("join", "plain"), ("index_video", "index_streams")):
+                if pair[0] == "join":
+                    batch.stream_open_heads(data, off, cap, length, sp, wr, blob, h_off, h_chain)  # every stream is its whole chain
+                for name in pair[::-1] if t & 1 else pair:  # the two of a pair take turns at going first
+                    if name == "join":
+                        vlen.zero_()
+                    w, ks = timed(*calls[name])
+                    if t:
+                        wall[name].append(w); kernel[name].append(ks)
+                        if name == "plain":
+                            plain_event_ms.append(e0.elapsed_time(e1))
+                if pair[0] == "join" and (batch.join_status() != 0 or int(vlen.cpu()[0]) != n * len(chain)):
+                    sys.exit("slice_parse_timing.py: the join failed")
+            if found["video"][0] != n or found["video"][1] != 0 or found["video"][2].tolist() != [frames] * n or found["streams"].tolist() != [frames] * n:
+                sys.exit("slice_parse_timing.py: an index call found other units than the host")
+        kmed = lambda name: {k: med([r[k] for r in kernel[name]]) for k in calls[name][1]}    # noqa: E731
+        if not torch.equal(video[:n * len(chain)], plain) or video[:n * len(chain)].cpu().numpy().tobytes() != chain * n:
+            sys.exit("slice_parse_timing.py: the video is not the chains behind each other")
+        hv = np.frombuffer(chain * n, np.uint8)
+        gops = np.zeros(n, pcamv_amd.GOP_DTYPE)
+        a, b = C.c_int64(), C.c_int64()
+        host = []
+        for _ in range(3):
+            w0 = time.perf_counter()
+            if lib.pcamv_gpu_annexb_gops(hv.ctypes.data, len(hv), gops.ctypes.data, n, C.byref(a), C.byref(b)) or a.value != n:
+                sys.exit("slice_parse_timing.py: the host cut failed")
+            host.append((time.perf_counter() - w0) * 1e3)
+        total = n * len(chain)
+        copy_ms, head_copy_ms = kmed("join")["k_stream_copy"], kmed("open_heads")["k_stream_copy"]
+        out["device"].append(dict(chains=n, video_bytes=total, stream_open_heads_wall=stat(wall["open_heads"]), stream_open_wall=stat(wall["open"]),
+                                  open_heads_kernels_ms=kmed("open_heads"), open_kernels_ms=kmed("open"),
+                                  open_heads_copy_gb_per_s=n * len(head) / (head_copy_ms * 1e-3) / 1e9,
+                                  join_streams_wall=stat(wall["join"]), plain_copy_wall=stat(wall["plain"]), plain_copy_event_ms=med(plain_event_ms),
+                                  plain_copy_gb_per_s=total / (med(plain_event_ms) * 1e-3) / 1e9, join_kernels_ms=kmed("join"),
+                                  k_stream_copy_gb_per_s=total / (copy_ms * 1e-3) / 1e9, k_stream_copy_over_plain_copy=copy_ms / med(plain_event_ms),
+                                  index_video_device_wall=stat(wall["index_video"]), index_streams_device_wall=stat(wall["index_streams"]),
+                                  index_wall_ratio=med(wall["index_video"]) / med(wall["index_streams"]),
+                                  index_video_kernels_ms=kmed("index_video"), index_streams_kernels_ms=kmed("index_streams"),
+                                  host_annexb_gops_one_thread_ms=med(host), host_gb_per_s=total / (med(host) * 1e-3) / 1e9))
+        print(json.dumps(out["device"][-1]), flush=True)
+        batch.close()
+    for e in encs:
+        e.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cavlc", action="store_true", help="CAVLC slices on --no-cabac contexts instead of CABAC ones")
@@ -567,14 +694,15 @@ def main():
     ap.add_argument("--window", action="store_true", help="a window of 8 units per stream next to 8 stream steps and to one step of 8 times the streams (profiles/stream_window_timing.json)")
     ap.add_argument("--write-stream", action="store_true", help="the sender's byte streams: write_stream_step next to write_step (profiles/stream_write_timing.json)")
     ap.add_argument("--param-sets", action="store_true", help="SPS / PPS read on the device: stream_param_sets, and a window under the streams' own sets next to one with the caller's parameters (profiles/param_sets_timing.json)")
+    ap.add_argument("--video", action="store_true", help="one video of many chains: stream_open_heads, join_streams and index_video_device next to their yardsticks (profiles/video_timing.json)")
     ap.add_argument("--parent-lib", default=None, help="with --param-sets: a libpcamv_gpu.so of the parent commit; the index call is held against it first (three --stream sweeps each)")
     ap.add_argument("--counts", default=None, help="default 1,64,1024,4096; with --nal, --stream, --param-sets or --write-stream 256,4096")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--host-threads", type=int, default=16)
     ap.add_argument("--out", default=None, help="default profiles/slice_parse_timing.json; with --nal profiles/nal_unescape_timing.json")
     args = ap.parse_args()
-    args.counts = args.counts or ("256" if args.window else "256,4096" if args.nal or args.stream or args.write_stream or args.param_sets else "1,64,1024,4096")
-    args.out = args.out if args.out is not None else os.path.join(ROOT, "profiles", "param_sets_timing.json" if args.param_sets else "stream_write_timing.json" if args.write_stream else "stream_index_timing.json" if args.stream else
+    args.counts = args.counts or ("256" if args.window else "256,4096" if args.nal or args.stream or args.write_stream or args.param_sets or args.video else "1,64,1024,4096")
+    args.out = args.out if args.out is not None else os.path.join(ROOT, "profiles", "video_timing.json" if args.video else "param_sets_timing.json" if args.param_sets else "stream_write_timing.json" if args.write_stream else "stream_index_timing.json" if args.stream else
                                                                   "stream_window_timing.json" if args.window else
                                                                   "nal_unescape_timing.json" if args.nal else "slice_parse_timing.json")
     index_cmp = index_vs_parent(args) if args.param_sets and args.parent_lib else None      # (before this process opens the device)
@@ -618,6 +746,9 @@ def main():
         return write_line(args, out, mode)
     if args.window:
         window_sweep(args, pcamv_amd, np, torch, out, g["slice_data"].tobytes(), qp, m, want)
+        return write_line(args, out, mode)
+    if args.video:
+        video_sweep(args, pcamv_amd, np, torch, out, g["slice_data"].tobytes(), qp)
         return write_line(args, out, mode)
     if args.param_sets:
         if index_cmp:

@@ -27,10 +27,11 @@
 enum { KT_ANALYSE, KT_EMBED_PREPARE, KT_EXTRACT_PREPARE, KT_EXTRACT_BITS, KT_PAYLOAD_CHECK, KT_PARSE_PSLICE, KT_PARSE_PSLICE_CAVLC, KT_WRITE_PSLICE, KT_WRITE_PSLICE_CAVLC, KT_NAL_TO_RBSP,
        KT_STREAM_PLAN, KT_STREAM_SCAN, KT_STREAM_PREFIX, KT_STREAM_PLACE, KT_STREAM_UNIT, KT_SLICE_HEADER, KT_STREAM_STATUS,
        KT_STREAM_OPEN, KT_STREAM_SLOT, KT_STREAM_COMMIT, KT_STREAM_WINDOW_UNIT, KT_EXTRACT_COUNT, KT_EXTRACT_CHAIN,
-       KT_PSET_UNIT, KT_PSET_PARSE, KT_PSET_RESOLVE, KT_SLICE_HEADER_SETS, KT_N };
+       KT_PSET_UNIT, KT_PSET_PARSE, KT_PSET_RESOLVE, KT_SLICE_HEADER_SETS,
+       KT_STREAM_OPEN_HEADS, KT_STREAM_JOIN, KT_STREAM_COPY_PLAN, KT_STREAM_COPY, KT_VIDEO_CUT, KT_N };
 #define PCAMV_FEATURES (PCAMV_FEATURE_PAYLOAD | PCAMV_FEATURE_SLICE_PARSER | PCAMV_FEATURE_SLICE_PARSER_CAVLC | PCAMV_FEATURE_SLICE_WRITER | \
                         PCAMV_FEATURE_SLICE_WRITER_CAVLC | PCAMV_FEATURE_NAL_DEVICE | PCAMV_FEATURE_STREAM_DEVICE | PCAMV_FEATURE_STREAM_WRITER | \
-                        PCAMV_FEATURE_STREAM_WINDOW | PCAMV_FEATURE_PARAM_SETS)
+                        PCAMV_FEATURE_STREAM_WINDOW | PCAMV_FEATURE_PARAM_SETS | PCAMV_FEATURE_VIDEO)
 #define SLICE_GUARD_MBS 4       /* records behind a context's receive-side records that nothing may write (pcamv_gpu_debug_slice_records) */
 #define NSTAGE 2                /* staging buffers of extract_slices: a call waits for the one before the last */
 /* the stages of a step (batch_launch's `what`): plane production, analysis (search + RCA + encode), embedding, second pass */
@@ -76,6 +77,7 @@ struct StreamIndex {
     int *d_bad; unsigned long long *d_longest; SiChunk *d_chunks; pcamv_unit_t *d_table; uint8_t *d_own;
     size_t cap_n, cap_chunks, cap_table, cap_own;
     const uint8_t *bytes; long long bytes_size, slot;
+    SiChunk *d_keep; size_t cap_keep;   /* a video's index (video_units_run): the chunks' summaries as the first scan left them */
 };
 
 /* the parameter sets of n indexed streams (k_pset_unit, k_pset_parse, k_pset_resolve): the tables of their units of type 7 / 8, the
@@ -98,6 +100,8 @@ struct StreamOut {
     SwsSetup S;
     uint8_t *d_own; size_t cap_own;     /* [SwsCtx n][w_off n][w_cap n][w_len n][off n][cap n][first n][table: n entries, n slots] */
     uint8_t *d_head; size_t cap_head;
+    uint8_t *d_copy; size_t cap_copy;   /* the copy launches of stream_open_heads and join_streams: [VcJob n][chunk_base n + 1][head_off n][head_len n][join status] */
+    int joined;                         /* a join was queued since the open: its status is there to be read */
 };
 
 /* the slots of a window of slice units per context (pcamv_gpu_batch_stream_window): per context x slot what a step keeps per context --
@@ -143,6 +147,10 @@ struct pcamv_batch {
     /* ... handed byte streams: the index of every context's stream, and the job arrays and RBSP slots of a step, sized by index calls */
     StreamIndex sx;
     StreamSets ps;              /* ... and their parameter sets, for the *_sets calls */
+    /* ... handed one video (pcamv_gpu_batch_index_video*): the index of the video as one stream with all its units listed, the contexts'
+     * (off, len) k_video_cut makes of it -- [off n][len n][n_gops][preamble] --, and the video's own sets; `video` holds from such a call to
+     * the next index call of either kind */
+    StreamIndex vx; StreamSets vps; long long *d_vcut; size_t cap_vcut; int video;
     StageRing su_stage;
     StreamWindow sw;
     /* sender to a stream (k_write_pslice, k_write_pslice_cavlc): the same of its own, and the staging of the callers' slice headers -- a
@@ -298,7 +306,7 @@ static void stage_destroy(StageRing &R)
 }
 static void stream_index_free(StreamIndex &S)
 {
-    hipFree(S.d_at); hipFree(S.d_bad); hipFree(S.d_longest); hipFree(S.d_chunks); hipFree(S.d_table); hipFree(S.d_own);
+    hipFree(S.d_at); hipFree(S.d_bad); hipFree(S.d_longest); hipFree(S.d_chunks); hipFree(S.d_table); hipFree(S.d_own); hipFree(S.d_keep);
     S = StreamIndex();
 }
 static void stream_sets_free(StreamSets &P)
@@ -337,10 +345,11 @@ extern "C" void pcamv_gpu_batch_destroy(pcamv_batch_t *b)
     stage_destroy(b->rx_stage); stage_destroy(b->nal_stage); stage_destroy(b->su_stage);
     stream_index_free(b->sx);
     stream_sets_free(b->ps);
+    stream_index_free(b->vx); stream_sets_free(b->vps); hipFree(b->d_vcut);
     stream_window_free(b->sw);
     hipFree(b->d_wstat); hipFree(b->d_sw_tab); hipFree(b->d_sw_scratch);
     stage_destroy(b->tx_stage);
-    hipFree(b->so.d_own); hipFree(b->so.d_head);
+    hipFree(b->so.d_own); hipFree(b->so.d_head); hipFree(b->so.d_copy);
     ring_destroy(b->ring); ring_destroy(b->xring);
     for (KTimer &T : b->kt) kt_destroy(T);
     free(b->ctx);
@@ -486,7 +495,7 @@ static const char *kt_name(const pcamv_batch *b, int k)      /* what pcamv_gpu_b
                                             "k_write_pslice_cavlc", "k_nal_to_rbsp", "k_stream_plan", "k_stream_scan", "k_stream_prefix", "k_stream_place", "k_stream_unit",
                                             "k_slice_header", "k_stream_status", "k_stream_open", "k_stream_slot", "k_stream_commit",
                                             "k_stream_window_unit", "k_extract_count", "k_extract_chain", "k_pset_unit", "k_pset_parse", "k_pset_resolve",
-                                            "k_slice_header_sets"};
+                                            "k_slice_header_sets", "k_stream_open_heads", "k_stream_join", "k_stream_copy_plan", "k_stream_copy", "k_video_cut"};
     return k == KT_ANALYSE ? dominant_kernel(b) : small[k];
 }
 extern "C" int pcamv_gpu_batch_copy_results_async(pcamv_batch_t *b, void *dst_mb, size_t mb_stride, void *dst_flip, size_t flip_stride, void *stream)
@@ -1664,6 +1673,7 @@ static int stream_index_finish(pcamv_batch *b, const uint8_t *d_bytes, size_t by
         }
     S.bytes = d_bytes; S.bytes_size = (long long)bytes_size; S.ready = 1;
     b->ps.ready = 0;                                /* the sets belong to the streams of the index call before */
+    b->video = 0;                                   /* (pcamv_gpu_batch_index_video* sets it behind this) */
     return b->sw.k ? window_jobs_room(b) : 0;       /* (a window reserved earlier: its RBSP slots follow, as the steps' do) */
 }
 extern "C" int pcamv_gpu_batch_index_streams_device(pcamv_batch_t *b, const void *bytes, size_t bytes_size, const int64_t *off, const int64_t *len,
@@ -1705,6 +1715,159 @@ extern "C" int pcamv_gpu_batch_index_streams(pcamv_batch_t *b, const pcamv_strea
     TRY(stream_index_room(b, S, b->n, max_units, 0, total - hdr));
     TRY(stream_index_run(b, S, S.d_own + hdr, total - hdr, (const long long *)S.d_own, (const long long *)S.d_own + n, 0, st));
     return stream_index_finish(b, S.d_own + hdr, total - hdr, n_slices_out);
+}
+/* ---- one video (k_video_cut; pcamv_video.h) */
+/* The S.n videos (d_off[v], d_len[v]) of d_bytes with ALL their units listed: plan, scan and prefix with a table of no entries give the
+ * counts, the one wait for `st` brings them to the host (h_units[S.n]: a video's count, PCAMV_EINVAL for one outside the buffer), the
+ * table is made for the largest, and prefix and place run again over the summaries the scan left (kept aside, since the prefix works
+ * in place): the bytes are read twice, as by a plain index call */
+/* the prefix between scan and place: k_stream_prefix, a wavefront per stream, or for one long stream the same in two levels on many */
+template <int SEL> static void video_prefix_launch(pcamv_batch *b, const StreamIndex &S, const StreamJobs &J, hipStream_t st)
+{
+    const int ev = kt_begin(b, KT_STREAM_PREFIX, st);
+    if (S.n == 1 && S.d_keep) {
+        SiChunk *B = S.d_keep + S.max_chunks;
+        const unsigned blocks = (unsigned)((S.max_chunks + VP_BLOCK - 1) / VP_BLOCK);
+        hipLaunchKernelGGL(k_video_prefix_local, dim3(blocks), dim3(64), 0, st, J, B);
+        hipLaunchKernelGGL(k_video_prefix_top<SEL>, dim3(1), dim3(64), 0, st, J, B);
+        hipLaunchKernelGGL(k_video_prefix_apply, dim3((unsigned)((S.max_chunks + 63) / 64)), dim3(64), 0, st, J, B);
+    } else hipLaunchKernelGGL(k_stream_prefix<SEL>, dim3(S.n), dim3(64), 0, st, J);
+    kt_end(b, KT_STREAM_PREFIX, ev, st);
+}
+static int video_units_run(pcamv_batch *b, StreamIndex &S, const uint8_t *d_bytes, size_t bytes_size, const long long *d_off, const long long *d_len, long long *h_units,
+                           hipStream_t st)
+{
+    const size_t n = (size_t)S.n;
+    TRY(stream_index_room(b, S, S.n, 1, 0, bytes_size));
+    TRY(grow(b, &S.d_keep, &S.cap_keep, (size_t)S.max_chunks + (size_t)(S.max_chunks + VP_BLOCK - 1) / VP_BLOCK));    /* (the kept summaries, then the blocks') */
+    HIPCHK(b, hipMemcpyAsync(S.d_at, d_off, 8 * n, hipMemcpyDeviceToDevice, st));
+    HIPCHK(b, hipMemcpyAsync(S.d_at + n, d_len, 8 * n, hipMemcpyDeviceToDevice, st));
+    HIPCHK(b, hipMemsetAsync(S.d_longest, 0, 8, st));
+    StreamJobs J;
+    J.bytes = d_bytes; J.bytes_size = (long long)bytes_size; J.off = S.d_at; J.len = S.d_at + n;
+    J.chunk_base = S.d_at + 2 * n; J.bad = S.d_bad; J.chunks = S.d_chunks; J.max_chunks = S.max_chunks;
+    J.table = S.d_table; J.max_units = 0; J.stride = 0; J.all = 1;
+    J.n_units = S.d_at + 3 * n; J.n_slices = S.d_at + 4 * n; J.cursor = S.d_at + 5 * n; J.longest = S.d_longest; J.n = S.n;
+    const unsigned chunks = (unsigned)S.max_chunks;
+    int ev = kt_begin(b, KT_STREAM_PLAN, st);
+    hipLaunchKernelGGL(k_stream_plan, dim3(1), dim3(64), 0, st, J);
+    kt_end(b, KT_STREAM_PLAN, ev, st);
+    ev = kt_begin(b, KT_STREAM_SCAN, st);
+    hipLaunchKernelGGL(k_stream_scan<0>, dim3(chunks), dim3(64), 0, st, J);
+    kt_end(b, KT_STREAM_SCAN, ev, st);
+    HIPCHK(b, hipMemcpyAsync(S.d_keep, S.d_chunks, (size_t)S.max_chunks * sizeof(SiChunk), hipMemcpyDeviceToDevice, st));
+    video_prefix_launch<0>(b, S, J, st);
+    TRY(launched(b));
+    HIPCHK(b, hipStreamSynchronize(st));
+    HIPCHK(b, hipMemcpy(h_units, S.d_at + 3 * n, 8 * n, hipMemcpyDeviceToHost));
+    long long most = 1;
+    for (size_t v = 0; v < n; v++) if (h_units[v] > most) most = h_units[v];
+    if (most > (1LL << 28)) return fail(b, PCAMV_ENOMEM, "a video of %lld units: the table of all of them is limited to 2^28 entries", most);
+    S.max_units = most; S.stride = most;
+    TRY(grow(b, &S.d_table, &S.cap_table, n * (size_t)most));
+    J.table = S.d_table; J.max_units = most; J.stride = most;
+    HIPCHK(b, hipMemcpyAsync(S.d_chunks, S.d_keep, (size_t)S.max_chunks * sizeof(SiChunk), hipMemcpyDeviceToDevice, st));
+    video_prefix_launch<0>(b, S, J, st);
+    ev = kt_begin(b, KT_STREAM_PLACE, st);
+    hipLaunchKernelGGL(k_stream_place<0>, dim3(chunks), dim3(64), 0, st, J);
+    kt_end(b, KT_STREAM_PLACE, ev, st);
+    return launched(b);
+}
+static VideoCut video_cut_jobs(const StreamIndex &S)
+{
+    const size_t n = (size_t)S.n;
+    VideoCut Q = VideoCut();
+    Q.table = S.d_table; Q.stride = S.stride; Q.n_units = S.d_at + 3 * n; Q.off = S.d_at; Q.len = S.d_at + n; Q.bad = S.d_bad;
+    return Q;
+}
+/* the video (d_off[0], d_len[0]) of d_bytes to the batch's contexts: GOP first_gop + i is context i's stream */
+static int index_video_run(pcamv_batch *b, const uint8_t *d_bytes, size_t bytes_size, const long long *d_off, const long long *d_len, long long first_gop,
+                           long long max_units, int64_t *n_gops, int64_t *preamble, int64_t *n_slices_out, hipStream_t st)
+{
+    const size_t n = (size_t)b->n;
+    StreamIndex &V = b->vx;
+    b->video = 0; b->sx.ready = 0; b->ps.ready = 0;
+    /* (the video's own tables and the contexts' (off, len) are read by this call's kernels and by stream_param_sets alone, which waits) */
+    TRY(grow(b, &b->d_vcut, &b->cap_vcut, 2 * n + 2));
+    V.n = 1;
+    long long units = 0;
+    TRY(video_units_run(b, V, d_bytes, bytes_size, d_off, d_len, &units, st));
+    if (units < 0) return fail(b, PCAMV_EINVAL, "the video does not lie inside the buffer");
+    VideoCut Q = video_cut_jobs(V);
+    Q.first = first_gop; Q.ctx_off = b->d_vcut; Q.ctx_len = b->d_vcut + n; Q.n_ctx = b->n; Q.n_gops = b->d_vcut + 2 * n; Q.preamble = b->d_vcut + 2 * n + 1;
+    const int ev = kt_begin(b, KT_VIDEO_CUT, st);
+    hipLaunchKernelGGL(k_video_cut, dim3(1), dim3(64), 0, st, Q);
+    kt_end(b, KT_VIDEO_CUT, ev, st);
+    TRY(stream_index_room(b, b->sx, b->n, max_units, 0, bytes_size));
+    TRY(stream_index_run(b, b->sx, d_bytes, bytes_size, Q.ctx_off, Q.ctx_len, 0, st));
+    TRY(stream_index_finish(b, d_bytes, bytes_size, n_slices_out));
+    static_assert(sizeof(long long) == sizeof(int64_t), "the counts are copied as they are");
+    if (n_gops) HIPCHK(b, hipMemcpy(n_gops, Q.n_gops, 8, hipMemcpyDeviceToHost));
+    if (preamble) HIPCHK(b, hipMemcpy(preamble, Q.preamble, 8, hipMemcpyDeviceToHost));
+    b->video = 1;
+    return 0;
+}
+extern "C" int pcamv_gpu_batch_index_video_device(pcamv_batch_t *b, const void *bytes, size_t bytes_size, const int64_t *off, const int64_t *len,
+                                                  int64_t first_gop, int64_t max_units, int64_t *n_gops, int64_t *preamble, int64_t *n_slices_out, void *stream)
+{
+    if (!off || !len || first_gop < 0 || first_gop > (1LL << 40)) return PCAMV_EINVAL;
+    TRY(stream_index_checked(b, bytes, bytes_size, max_units));
+    hipStream_t st = stream ? (hipStream_t)stream : b->ctx[0]->stream;
+    return index_video_run(b, (const uint8_t *)bytes, bytes_size, (const long long *)off, (const long long *)len, first_gop, max_units, n_gops, preamble, n_slices_out, st);
+}
+/* a host video into the index's own buffer -- [off = 0][len] int64, then the bytes -- with one copy */
+extern "C" int pcamv_gpu_batch_index_video(pcamv_batch_t *b, const uint8_t *bytes, size_t len, int64_t first_gop, int64_t max_units, int64_t *n_gops,
+                                           int64_t *preamble, int64_t *n_slices_out, void *stream)
+{
+    if ((!bytes && len) || len > ((size_t)1 << 36) || first_gop < 0 || first_gop > (1LL << 40)) return PCAMV_EINVAL;
+    TRY(stream_index_checked(b, b, 0, max_units));
+    StreamIndex &S = b->sx;
+    S.ready = 0;
+    HIPCHK(b, hipDeviceSynchronize());              /* (steps on the buffer that is replaced may be in flight) */
+    TRY(grow(b, &S.d_own, &S.cap_own, 16 + len));
+    const long long at[2] = {0, (long long)len};
+    HIPCHK(b, hipMemcpy(S.d_own, at, 16, hipMemcpyHostToDevice));
+    if (len) HIPCHK(b, hipMemcpy(S.d_own + 16, bytes, len, hipMemcpyHostToDevice));
+    hipStream_t st = stream ? (hipStream_t)stream : b->ctx[0]->stream;
+    return index_video_run(b, S.d_own + 16, len, (const long long *)S.d_own, (const long long *)S.d_own + 1, first_gop, max_units, n_gops, preamble, n_slices_out, st);
+}
+/* the parity probe of the cut: n videos of one host buffer, every video's units listed and walked by a wavefront of its own */
+extern "C" int pcamv_gpu_video_gops_device(pcamv_ctx_t *c, const uint8_t *bytes, size_t bytes_size, const int64_t *off, const int64_t *len, int n,
+                                           pcamv_gop_t *gops_out, int64_t cap_per_video, int64_t *n_gops, int64_t *preamble)
+{
+    if (!c || (!bytes && bytes_size) || !off || !len || !gops_out || !n_gops || !preamble || n < 1 || n > (1 << 20) || cap_per_video < 0 ||
+        cap_per_video > (1LL << 24) || bytes_size > ((size_t)1 << 40)) return PCAMV_EINVAL;
+    pcamv_batch *b = c->self;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t entries = (size_t)n * (size_t)(cap_per_video + PCAMV_UNIT_GUARD);
+    DevTmp<uint8_t> d_bytes; DevTmp<long long> d_at; DevTmp<pcamv_gop_t> d_gops;
+    HIPCHK(c, d_bytes.alloc(bytes_size ? bytes_size : 1)); HIPCHK(c, d_at.alloc(4 * (size_t)n)); HIPCHK(c, d_gops.alloc(entries));
+    if (bytes_size) HIPCHK(c, hipMemcpy(d_bytes, bytes, bytes_size, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_at, off, sizeof(int64_t) * n, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_at + n, len, sizeof(int64_t) * n, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemset(d_gops, 0xA5, entries * sizeof(pcamv_gop_t)));
+    HostTmp<long long> h_units((size_t)n);
+    if (!h_units) return fail(c, PCAMV_ENOMEM, "no memory for the counts of %d videos", n);
+    StreamIndex S = StreamIndex();
+    S.n = n;
+    int rc = video_units_run(b, S, d_bytes, bytes_size, d_at, d_at + n, h_units, c->stream);
+    hipError_t e = hipSuccess;
+    if (!rc) {
+        VideoCut Q = video_cut_jobs(S);
+        Q.gops = d_gops; Q.gstride = cap_per_video + PCAMV_UNIT_GUARD; Q.cap = cap_per_video;
+        Q.n_gops = d_at + 2 * (size_t)n; Q.preamble = d_at + 3 * (size_t)n;
+        const int ev = kt_begin(b, KT_VIDEO_CUT, c->stream);
+        hipLaunchKernelGGL(k_video_cut, dim3(n), dim3(64), 0, c->stream, Q);
+        kt_end(b, KT_VIDEO_CUT, ev, c->stream);
+        rc = launched(b);
+    }
+    if (!rc) e = hipStreamSynchronize(c->stream);
+    if (!rc && e == hipSuccess) e = hipMemcpy(gops_out, d_gops, entries * sizeof(pcamv_gop_t), hipMemcpyDeviceToHost);
+    if (!rc && e == hipSuccess) e = hipMemcpy(n_gops, d_at + 2 * (size_t)n, 8 * (size_t)n, hipMemcpyDeviceToHost);
+    if (!rc && e == hipSuccess) e = hipMemcpy(preamble, d_at + 3 * (size_t)n, 8 * (size_t)n, hipMemcpyDeviceToHost);
+    stream_index_free(S);
+    if (e != hipSuccess) return fail(c, PCAMV_EHIP, "video_gops_device: %s", hipGetErrorString(e));
+    return on_behalf(c, b, rc);
 }
 /* the entropy mode of a *_sets call is the contexts' own: 1 CAVLC, 0 CABAC (a batch holds contexts of one mode: pcamv_gpu_batch_create) */
 static int sets_mode(pcamv_batch *b, int *cavlc)
@@ -1999,9 +2162,7 @@ static int pset_run(pcamv_batch *b, const StreamIndex &S, const uint8_t *d_bytes
     int ev = kt_begin(b, KT_STREAM_SCAN, st);
     hipLaunchKernelGGL(k_stream_scan<SI_SEL_PSET>, dim3(chunks), dim3(64), 0, st, J);
     kt_end(b, KT_STREAM_SCAN, ev, st);
-    ev = kt_begin(b, KT_STREAM_PREFIX, st);
-    hipLaunchKernelGGL(k_stream_prefix<SI_SEL_PSET>, dim3(S.n), dim3(64), 0, st, J);
-    kt_end(b, KT_STREAM_PREFIX, ev, st);
+    video_prefix_launch<SI_SEL_PSET>(b, S, J, st);          /* (k_stream_prefix, but for a video's own index: one long stream) */
     ev = kt_begin(b, KT_STREAM_PLACE, st);
     hipLaunchKernelGGL(k_stream_place<SI_SEL_PSET>, dim3(chunks), dim3(64), 0, st, J);
     kt_end(b, KT_STREAM_PLACE, ev, st);
@@ -2059,8 +2220,14 @@ extern "C" int pcamv_gpu_batch_stream_param_sets(pcamv_batch_t *b, int32_t *stat
     if (!S.ready) return fail(b, PCAMV_EINVAL, "no byte streams were handed to this batch yet (pcamv_gpu_batch_index_streams*)");
     hipStream_t st = stream ? (hipStream_t)stream : b->ctx[0]->stream;
     HIPCHK(b, hipDeviceSynchronize());              /* (steps under the sets that are replaced may be in flight) */
-    TRY(pset_run(b, S, S.bytes, S.bytes_size, b->ps, b->ctx[0]->F.mb_w, b->ctx[0]->F.mb_h, st));
     const size_t n = (size_t)S.n;
+    if (b->video) {         /* the video's sets, resolved once, are every context's: GOPs behind the first often carry none of their own */
+        TRY(pset_run(b, b->vx, S.bytes, S.bytes_size, b->vps, b->ctx[0]->F.mb_w, b->ctx[0]->F.mb_h, st));
+        TRY(grow(b, &b->ps.d_sets, &b->ps.cap_sets, n));
+        hipLaunchKernelGGL(k_pset_spread, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, b->vps.d_sets, b->ps.d_sets, (int)n);
+        TRY(launched(b));
+        HIPCHK(b, hipStreamSynchronize(st));
+    } else TRY(pset_run(b, S, S.bytes, S.bytes_size, b->ps, b->ctx[0]->F.mb_w, b->ctx[0]->F.mb_h, st));
     if (status_out || sets_out) {
         HostTmp<pcamv_param_sets_t> h(n);
         if (!h) return fail(b, PCAMV_ENOMEM, "no memory for the sets of %zu streams", n);
@@ -2410,6 +2577,8 @@ extern "C" int pcamv_gpu_write_slice_header(const pcamv_stream_params_t *params,
 }
 /* the arrays of the library's block for n contexts (StreamOut::d_own), every one at a multiple of 8 */
 static size_t stream_out_bytes(int n) { return (size_t)n * (sizeof(SwsCtx) + 5 * 8 + 4 + SWS_HDR_WORDS * 4 + PCAMV_SLICE_HDR_BYTES) + 8; }
+/* ... and of the block of a copy launch (StreamOut::d_copy; stream_copy_jobs below) */
+static size_t stream_copy_bytes(int n) { return (size_t)n * (sizeof(VcJob) + 3 * 8) + 8 + 8; }
 static StreamWrite stream_out_jobs(const pcamv_batch *b)
 {
     const StreamOut &O = b->so;
@@ -2437,12 +2606,13 @@ extern "C" int pcamv_gpu_batch_stream_open(pcamv_batch_t *b, void *bytes, size_t
     if (ok) return fail(b, ok, wr->nal_ref_idc == 0 ? "nal_ref_idc 0: in this path a chain's P frame is the next one's reference" :
                                "stream_open: parameter sets or stream settings out of range");
     StreamOut &O = b->so;
-    O.ready = 0;
+    O.ready = 0; O.joined = 0;
     hipStream_t st = stream ? (hipStream_t)stream : b->ctx[0]->stream;
     const size_t total = stream_out_bytes(b->n);
-    if (total > O.cap_own || head_len > O.cap_head) HIPCHK(b, hipDeviceSynchronize());        /* (steps on the blocks that are replaced may be in flight) */
+    if (total > O.cap_own || head_len > O.cap_head || stream_copy_bytes(b->n) > O.cap_copy) HIPCHK(b, hipDeviceSynchronize());        /* (steps on the blocks that are replaced may be in flight) */
     TRY(grow(b, &O.d_own, &O.cap_own, total));
     TRY(grow(b, &O.d_head, &O.cap_head, head_len));
+    TRY(grow(b, &O.d_copy, &O.cap_copy, stream_copy_bytes(b->n)));        /* (what a join behind this open works in) */
     O.bytes = (uint8_t *)bytes; O.bytes_size = (long long)bytes_size; O.len = (long long *)len; O.S = S;
     StreamWrite J = stream_out_jobs(b);
     static_assert(sizeof(long long) == sizeof(int64_t), "the caller's int64 arrays are read as they are");
@@ -2457,6 +2627,106 @@ extern "C" int pcamv_gpu_batch_stream_open(pcamv_batch_t *b, void *bytes, size_t
     TRY(launched(b));
     O.ready = 1;
     return 0;
+}
+/* ---- a head per context, and the streams joined into one video (k_stream_open_heads, k_stream_join, k_stream_copy_plan, k_stream_copy;
+ * pcamv_video.h).  The arrays of a copy launch in the library's block StreamOut::d_copy, every one at a multiple of 8 */
+static CopyJobs stream_copy_jobs(const pcamv_batch *b, const uint8_t *src, uint8_t *dst)
+{
+    static_assert(sizeof(VcJob) % 8 == 0, "the int64 arrays follow the jobs");
+    const CopyJobs C = {src, dst, (VcJob *)b->so.d_copy, (long long *)((VcJob *)b->so.d_copy + b->n), b->n};
+    return C;
+}
+static long long *stream_copy_heads(const pcamv_batch *b) { return stream_copy_jobs(b, NULL, NULL).chunk_base + b->n + 1; }     /* [head_off n][head_len n] */
+static int *stream_join_word(const pcamv_batch *b) { return (int *)(stream_copy_heads(b) + 2 * (size_t)b->n); }
+/* the plan and the copy behind the kernel that made the jobs; no job holds more than `most` bytes in all, which is what the host knows */
+static void stream_copy_launch(pcamv_batch *b, const CopyJobs &C, unsigned long long most, hipStream_t st)
+{
+    unsigned long long waves = most / VC_CHUNK + 2ULL * (unsigned)C.n + 1;
+    if (waves > (1u << 16)) waves = 1u << 16;      /* (a wavefront then takes several chunks in turn) */
+    int ev = kt_begin(b, KT_STREAM_COPY_PLAN, st);
+    hipLaunchKernelGGL(k_stream_copy_plan, dim3(1), dim3(64), 0, st, C);
+    kt_end(b, KT_STREAM_COPY_PLAN, ev, st);
+    ev = kt_begin(b, KT_STREAM_COPY, st);
+    hipLaunchKernelGGL(k_stream_copy, dim3((unsigned)waves), dim3(64), 0, st, C);
+    kt_end(b, KT_STREAM_COPY, ev, st);
+}
+static int ranges_overlap(const void *a, size_t a_size, const void *b, size_t b_size)
+{
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a_size && b_size && a0 < b0 + b_size && b0 < a0 + a_size;
+}
+extern "C" int pcamv_gpu_batch_stream_open_heads(pcamv_batch_t *b, void *bytes, size_t bytes_size, const int64_t *off, const int64_t *cap, int64_t *len,
+                                                 const pcamv_stream_params_t *params, const pcamv_stream_write_t *wr, const void *heads, size_t heads_size,
+                                                 const int64_t *head_off, const int64_t *head_len, void *stream)
+{
+    if (!b || !bytes || !off || !cap || !len || !params || !wr || !heads || !head_off || !head_len || heads_size > ((size_t)1 << 40) ||
+        bytes_size > ((size_t)1 << 62) || ranges_overlap(bytes, bytes_size, heads, heads_size)) return PCAMV_EINVAL;
+    HIPCHK(b, hipSetDevice(b->device));
+    TRY(batch_live(b));
+    SwsSetup S; S.P = *params; S.W = *wr;
+    const int ok = sws_setup_ok(S);
+    if (ok == PCAMV_EUNSUP) return fail(b, ok, "weighted prediction: the header writer has no pred_weight_table");
+    if (ok) return fail(b, ok, wr->nal_ref_idc == 0 ? "nal_ref_idc 0: in this path a chain's P frame is the next one's reference" :
+                               "stream_open_heads: parameter sets or stream settings out of range");
+    StreamOut &O = b->so;
+    O.ready = 0; O.joined = 0;
+    hipStream_t st = stream ? (hipStream_t)stream : b->ctx[0]->stream;
+    const size_t total = stream_out_bytes(b->n), n = (size_t)b->n;
+    if (total > O.cap_own || stream_copy_bytes(b->n) > O.cap_copy) HIPCHK(b, hipDeviceSynchronize());   /* (steps on the blocks that are replaced may be in flight) */
+    TRY(grow(b, &O.d_own, &O.cap_own, total));
+    TRY(grow(b, &O.d_copy, &O.cap_copy, stream_copy_bytes(b->n)));
+    O.bytes = (uint8_t *)bytes; O.bytes_size = (long long)bytes_size; O.len = (long long *)len; O.S = S;
+    StreamWrite J = stream_out_jobs(b);
+    const CopyJobs C = stream_copy_jobs(b, (const uint8_t *)heads, O.bytes);
+    long long *h_at = stream_copy_heads(b);
+    HIPCHK(b, hipMemcpyAsync((void *)J.off, off, 8 * n, hipMemcpyDeviceToDevice, st));
+    HIPCHK(b, hipMemcpyAsync((void *)J.cap, cap, 8 * n, hipMemcpyDeviceToDevice, st));
+    HIPCHK(b, hipMemcpyAsync(h_at, head_off, 8 * n, hipMemcpyDeviceToDevice, st));
+    HIPCHK(b, hipMemcpyAsync(h_at + n, head_len, 8 * n, hipMemcpyDeviceToDevice, st));
+    HIPCHK(b, hipStreamSynchronize(st));                                /* the four arrays are read by this call alone: copied on return */
+    const HeadJobs H = {(long long)heads_size, h_at, h_at + n, C.jobs};
+    const int ev = kt_begin(b, KT_STREAM_OPEN_HEADS, st);
+    hipLaunchKernelGGL(k_stream_open_heads, dim3((b->n + 63) / 64), dim3(64), 0, st, J, H);
+    kt_end(b, KT_STREAM_OPEN_HEADS, ev, st);
+    /* the regions do not overlap, so the heads that are taken hold no more than the buffer; each no more than `heads` and VC_HEAD_MAX */
+    const unsigned long long each = heads_size < (size_t)VC_HEAD_MAX ? heads_size : (unsigned long long)VC_HEAD_MAX, all = each * n;
+    stream_copy_launch(b, C, all < bytes_size ? all : bytes_size, st);
+    TRY(launched(b));
+    O.ready = 1;
+    return 0;
+}
+extern "C" int pcamv_gpu_batch_join_streams(pcamv_batch_t *b, void *video, size_t video_size, const int64_t *video_off, int64_t *video_len, int64_t *placed,
+                                            void *stream)
+{
+    if (!b || !video || !video_off || !video_len || video_size > ((size_t)1 << 40)) return PCAMV_EINVAL;
+    HIPCHK(b, hipSetDevice(b->device));
+    TRY(batch_live(b));
+    StreamOut &O = b->so;
+    if (!O.ready) return fail(b, PCAMV_EINVAL, "no byte streams were opened on this batch yet (pcamv_gpu_batch_stream_open*)");
+    if (O.bytes_size > (1LL << 40)) return fail(b, PCAMV_EINVAL, "join_streams: the open buffer holds more than 2^40 bytes");
+    if (ranges_overlap(video, video_size, O.bytes, (size_t)O.bytes_size)) return fail(b, PCAMV_EINVAL, "join_streams: the video overlaps the buffer the streams are written to");
+    hipStream_t st = stream ? (hipStream_t)stream : b->ctx[0]->stream;
+    const CopyJobs C = stream_copy_jobs(b, O.bytes, (uint8_t *)video);
+    const JoinJobs Q = {(const SwsCtx *)O.d_own, b->n, (long long)video_size, (const long long *)video_off, (long long *)video_len, (long long *)placed,
+                        stream_join_word(b), C.jobs};
+    const int ev = kt_begin(b, KT_STREAM_JOIN, st);
+    hipLaunchKernelGGL(k_stream_join, dim3(1), dim3(64), 0, st, Q);
+    kt_end(b, KT_STREAM_JOIN, ev, st);
+    stream_copy_launch(b, C, (unsigned long long)O.bytes_size < video_size ? (unsigned long long)O.bytes_size : video_size, st);
+    TRY(launched(b));
+    O.joined = 1;
+    return 0;
+}
+/* synchronises */
+extern "C" int pcamv_gpu_batch_join_status(pcamv_batch_t *b)
+{
+    if (!b) return PCAMV_EINVAL;
+    HIPCHK(b, hipSetDevice(b->device));
+    if (!b->so.ready || !b->so.joined) return fail(b, PCAMV_EINVAL, "no streams were joined on this batch since its last open (pcamv_gpu_batch_join_streams)");
+    HIPCHK(b, hipDeviceSynchronize());
+    int rc = 0;
+    HIPCHK(b, hipMemcpy(&rc, stream_join_word(b), sizeof(rc), hipMemcpyDeviceToHost));
+    return rc ? fail(b, rc, "join_streams: the streams do not fit what is left of the video buffer") : 0;
 }
 extern "C" int pcamv_gpu_batch_write_stream_step(pcamv_batch_t *b, void *stream)
 {

@@ -624,6 +624,36 @@ extern "C" int pcamv_gpu_annexb_index(const uint8_t *bytes, size_t len, pcamv_un
     *n_units = nu; *n_slices = ns;
     return 0;
 }
+/* A video cut into its GOPs (the rule: include/pcamv_gpu.h); what k_video_cut does (pcamv_video.h) on every input, valid or not.  The
+ * units are walked once with what the rule needs of the past: the nearest VCL unit so far and whether it is an IDR unit */
+extern "C" int pcamv_gpu_annexb_gops(const uint8_t *bytes, size_t len, pcamv_gop_t *gops, size_t cap, int64_t *n_gops, int64_t *preamble)
+{
+    if ((!bytes && len) || (!gops && cap) || !n_gops || !preamble) return PCAMV_EINVAL;
+    int64_t nu = 0, ns = 0;
+    pcamv_gpu_annexb_index(bytes, len, NULL, 0, &nu, &ns);
+    pcamv_unit_t *units = (pcamv_unit_t *)malloc((size_t)(nu ? nu : 1) * sizeof(pcamv_unit_t));
+    if (!units) return PCAMV_ENOMEM;
+    pcamv_gpu_annexb_index(bytes, len, units, (size_t)nu, &nu, &ns);
+    int64_t n = 0, last_vcl = -1, open_off = 0, open_unit = 0;
+    for (int64_t u = 0; u < nu; u++) {
+        const int type = units[u].nal_header < 0 ? 0 : units[u].nal_header & 31;
+        if (type < 1 || type > 5) continue;
+        if (type == 5 && (last_vcl < 0 || (units[last_vcl].nal_header & 31) != 5)) {
+            const int64_t f = last_vcl + 1, at = f ? units[f - 1].off + units[f - 1].len : 0;
+            if (n > 0 && (size_t)(n - 1) < cap) { gops[n - 1].len = at - open_off; gops[n - 1].n_units = f - open_unit; }
+            if ((size_t)n < cap) { gops[n].off = at; gops[n].first_unit = f; }
+            if (n == 0) *preamble = at;
+            open_off = at; open_unit = f;
+            n++;
+        }
+        last_vcl = u;
+    }
+    if (n > 0 && (size_t)(n - 1) < cap) { gops[n - 1].len = (int64_t)len - open_off; gops[n - 1].n_units = nu - open_unit; }
+    if (n == 0) *preamble = (int64_t)len;
+    *n_gops = n;
+    free(units);
+    return 0;
+}
 namespace mvsyntax {
 struct HdrBits {                /* the RBSP bit by bit; past its end every read fails */
     const uint8_t *d; uint64_t nbits, pos; int bad;

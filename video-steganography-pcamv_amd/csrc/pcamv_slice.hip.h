@@ -35,6 +35,12 @@
  * k_stream_open, k_stream_slot, k_stream_commit put that writer's units into one Annex B byte stream per context (pcamv_stream_write.h), one
  * lane per context: k_stream_slot in front of the writer makes each picture's slice header in the header table the writer reads and gives
  * the writer its place at the stream's end, k_stream_commit behind it moves the stream's end over what was written.
+ *
+ * k_stream_open_heads, k_stream_join, k_stream_copy_plan, k_stream_copy and k_video_cut make one video of many chains (pcamv_video.h): a
+ * head of its own at the start of every context's stream, the contexts' streams behind each other in one video -- both through
+ * k_stream_copy, a wavefront per chunk of a job's destination -- and on the receiving side a video's table of units walked by one
+ * wavefront into the contexts' (off, len), which the index kernels take from there.  k_video_prefix_local / _top / _apply are
+ * k_stream_prefix for that one long stream, in two levels on many wavefronts.  k_pset_spread gives every context the video's sets.
  */
 #ifndef PCAMV_SLICE_HIP_H
 #define PCAMV_SLICE_HIP_H
@@ -46,6 +52,7 @@
 #include "pcamv_param_sets.h"
 #include "pcamv_slice_write.h"
 #include "pcamv_stream_write.h"
+#include "pcamv_video.h"
 
 /* the slices of one launch: slice i is bytes[off[i] .. off[i] + len[i]), its slice data starts behind bit start_bit[i], slice QP qp[i] */
 struct SliceJobs {
@@ -411,6 +418,96 @@ static __global__ void __launch_bounds__(64) k_stream_commit(const StreamWrite J
     long long len = 0; int rc = 0;
     sws_commit(J.S, c, J.first[i], J.w_len[i], J.status[i], &len, &rc);
     J.ctx[i] = c; J.len[i] = len; J.status[i] = rc;
+}
+/* ---- one video of many chains (pcamv_video.h).  A copy launch: n jobs of offsets into src and dst, made by the kernel in front of it;
+ * chunk_base[0 .. n] is k_stream_copy_plan's.  The grid is sized by what the host knows the jobs cannot exceed, and capped: a wavefront
+ * takes flat chunks blockIdx.x, blockIdx.x + gridDim.x, ... below the total the plan found, and none if there is none for it */
+struct CopyJobs { const uint8_t *src; uint8_t *dst; VcJob *jobs; long long *chunk_base; int n; };
+static __global__ void __launch_bounds__(64) k_stream_copy_plan(const CopyJobs J)
+{
+    __shared__ long long s_sum[64];
+    vc_plan(s_sum, J.dst, J.jobs, J.n, J.chunk_base);
+}
+static __global__ void __launch_bounds__(64) k_stream_copy(const CopyJobs J)
+{
+    const long long total = J.chunk_base[J.n];
+    for (long long f = blockIdx.x; f < total; f += gridDim.x) {
+        long long c = 0;
+        const VcJob j = J.jobs[vc_job_of(J.chunk_base, J.n, f, &c)];
+        vc_copy_chunk(J.src + j.src, J.dst + j.dst, j.len, c);
+    }
+}
+/* stream_open with a head per context: one lane per context decides and makes the context's copy job (J.head: the heads' buffer) */
+struct HeadJobs { long long heads_size; const long long *head_off, *head_len; VcJob *jobs; };
+static __global__ void __launch_bounds__(64) k_stream_open_heads(const StreamWrite J, const HeadJobs H)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= J.n) return;
+    SwsCtx c;
+    long long len = 0;
+    H.jobs[i] = vj_head(c, J.bytes_size, J.off[i], J.cap[i], H.heads_size, H.head_off[i], H.head_len[i], &len);
+    J.ctx[i] = c; J.len[i] = len;
+}
+struct JoinJobs { const SwsCtx *ctx; int n; long long video_size; const long long *video_off; long long *video_len, *placed; int *status; VcJob *jobs; };
+static __global__ void __launch_bounds__(64) k_stream_join(const JoinJobs J)
+{
+    __shared__ long long s_sum[64];
+    vj_join(s_sum, J.ctx, J.n, J.video_size, J.video_off, J.video_len, J.placed, J.status, J.jobs);
+}
+/* one wavefront per video: video v's units are table[v * stride .. + n_units[v]) (all of them: the index kernels were given room for the
+ * count), its GOPs go to gops[v * gstride ..) and, for the one video of a batch, to the contexts' (off, len).  A video the index refused
+ * has PCAMV_EINVAL for both counts */
+struct VideoCut {
+    const pcamv_unit_t *table; long long stride; const long long *n_units, *off, *len; const int *bad;
+    pcamv_gop_t *gops; long long gstride, first, cap;
+    long long *ctx_off, *ctx_len; int n_ctx;
+    long long *n_gops, *preamble;
+};
+static __global__ void __launch_bounds__(64) k_video_cut(const VideoCut J)
+{
+    __shared__ long long s_start[65], s_unit[65];
+    const int v = blockIdx.x;
+    if (J.bad[v]) {
+        if (threadIdx.x == 0) { J.n_gops[v] = PCAMV_EINVAL; J.preamble[v] = PCAMV_EINVAL; }
+        for (int r = threadIdx.x; r < J.n_ctx; r += 64) { J.ctx_off[r] = 0; J.ctx_len[r] = 0; }
+        return;
+    }
+    const VgWork W = {s_start, s_unit};
+    const VgOut O = {J.gops + (long long)v * J.gstride, J.first, J.cap, J.ctx_off, J.ctx_len, J.off[v], J.n_ctx, J.n_gops + v, J.preamble + v};
+    long long m = J.n_units[v];
+    if (m > J.stride) m = J.stride;             /* (never: the table was sized by this count) */
+    vg_cut(W, J.table + (long long)v * J.stride, m, J.len[v], O);
+}
+/* k_stream_prefix for an index of ONE stream, in two levels (vp_local / si_prefix over the blocks / vp_apply): B has room for a summary
+ * per VP_BLOCK chunks.  The grids are sized by max_chunks; what lies beyond the stream's chunks exits */
+static __global__ void __launch_bounds__(64) k_video_prefix_local(const StreamJobs J, SiChunk *__restrict__ B)
+{
+    __shared__ SiChunk s_sc[64];
+    if (J.bad[0]) return;
+    const uint8_t *src = J.bytes + J.off[0];
+    const long long n_chunks = si_chunks(src, J.len[0]);
+    if ((long long)blockIdx.x * VP_BLOCK >= n_chunks) return;
+    const SiWork W = {nullptr, s_sc};
+    vp_local(W, src, J.len[0], J.chunks + J.chunk_base[0], n_chunks, blockIdx.x, B);
+}
+template <int SEL> static __global__ void __launch_bounds__(64) k_video_prefix_top(const StreamJobs J, SiChunk *__restrict__ B)
+{
+    __shared__ SiChunk s_sc[64];
+    if (J.bad[0]) return;
+    const uint8_t *src = J.bytes + J.off[0];
+    const SiWork W = {nullptr, s_sc};
+    si_prefix(W, src, J.len[0], B, (si_chunks(src, J.len[0]) + VP_BLOCK - 1) / VP_BLOCK, stream_table(J, 0, SEL), J.n_units, J.n_slices);
+}
+static __global__ void __launch_bounds__(64) k_video_prefix_apply(const StreamJobs J, const SiChunk *__restrict__ B)
+{
+    if (J.bad[0]) return;
+    vp_apply(J.chunks + J.chunk_base[0], si_chunks(J.bytes + J.off[0], J.len[0]), B, (long long)blockIdx.x * 64 + threadIdx.x);
+}
+/* the video's one table of parameter sets to every context */
+static __global__ void __launch_bounds__(64) k_pset_spread(const pcamv_param_sets_t *__restrict__ one, pcamv_param_sets_t *__restrict__ sets, int n)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i < n) sets[i] = *one;
 }
 /* the parity probe of the header writer: case i's parameter set and members, its slot of PCAMV_SLICE_HDR_BYTES bytes (zeros beforehand) */
 static __global__ void __launch_bounds__(64) k_slice_headers_write(const pcamv_stream_params_t *__restrict__ P, const pcamv_slice_fields_t *__restrict__ f,

@@ -478,6 +478,26 @@ def _bytes_arg(data):
     return np.frombuffer(bytes(data), np.uint8) if len(data) else np.zeros(1, np.uint8)
 
 
+FEATURE_VIDEO = 0x400           # one video of many chains: Batch.stream_open_heads, Batch.join_streams, Batch.index_video*, annexb_gops
+GOP_DTYPE = np.dtype([("off", np.int64), ("len", np.int64), ("first_unit", np.int64), ("n_units", np.int64)])       # pcamv_gop_t
+
+
+def annexb_gops(data, cap=None):
+    """pcamv_gpu_annexb_gops: (the first `cap` GOPs of an Annex B video as a GOP_DTYPE array, the number of GOPs, the bytes in front of
+    the first GOP).  An IDR unit opens a GOP unless the nearest slice unit before it is an IDR unit too; the GOP begins with the first
+    unit behind that slice unit, zeros and start code included"""
+    buf = _bytes_arg(data)
+    cap = len(data) // 4 + 1 if cap is None else int(cap)
+    gops = np.zeros(max(cap, 1), GOP_DTYPE)
+    n, pre = C.c_int64(), C.c_int64()
+    fn = load_library().pcamv_gpu_annexb_gops
+    fn.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    rc = fn(_p(buf), len(data), _p(gops), cap, C.byref(n), C.byref(pre))
+    if rc:
+        raise PcamvError(f"pcamv_gpu_annexb_gops failed: {rc}")
+    return gops[:min(cap, n.value)], n.value, pre.value
+
+
 def parse_sps(rbsp):
     """pcamv_gpu_parse_sps: (return code, Sps) of an SPS unit's RBSP (behind the header byte, unescaped); the Sps is all zeros when the
     code is not 0"""
@@ -817,6 +837,29 @@ class Encoder:
         fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         self._chk(fn(self.ctx, _p(data if len(data) else pad), len(data), _p(off), _p(length), n, _p(tables), int(cap), _p(nu), _p(ns)), "index_streams_probe")
         return tables, nu, ns
+
+    def video_gops_device(self, videos, cap=None):
+        """pcamv_gpu_video_gops_device: every video of `videos` (a list of bytes) cut into its GOPs by the index kernels and k_video_cut,
+        a wavefront per video -- the parity probe of Batch.index_video*, to be compared with annexb_gops.  The videos go up in one
+        buffer, each at an odd offset with other bytes around it.  Returns (tables, n_gops, preamble): tables a GOP_DTYPE array of
+        shape (n, cap + UNIT_GUARD) as the device left it (filled with bytes 0xA5 beforehand: entries past min(n_gops, cap), the guard
+        among them, still hold that)"""
+        n = len(videos)
+        cap = max([len(v) // 4 + 1 for v in videos] + [1]) if cap is None else int(cap)
+        off, at = np.zeros(n, np.int64), 1
+        for k, v in enumerate(videos):
+            off[k] = at
+            at += (len(v) + 2) | 1      # odd offsets stay odd
+        data = np.full(at, 0xEE, np.uint8)
+        for o, v in zip(off, videos):
+            data[o:o + len(v)] = np.frombuffer(bytes(v), np.uint8)
+        length = np.array([len(v) for v in videos], np.int64)
+        tables = np.zeros((n, cap + UNIT_GUARD), GOP_DTYPE)
+        ng, pre = np.zeros(n, np.int64), np.zeros(n, np.int64)
+        fn = self.lib.pcamv_gpu_video_gops_device
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        self._chk(fn(self.ctx, _p(data), len(data), _p(off), _p(length), n, _p(tables), cap, _p(ng), _p(pre)), "video_gops_device")
+        return tables, ng, pre
 
     def slice_headers_device(self, data, off, length, nal_header, params):
         """pcamv_gpu_slice_headers_device: the P slice headers of the RBSPs data[off[i] : off[i] + length[i]] read by k_slice_header,
@@ -1280,6 +1323,76 @@ class Batch:
         fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         self._slice_chk(fn(self.b, data.data_ptr(), data.numel(), off.data_ptr(), cap.data_ptr(), length.data_ptr(), C.byref(params), C.byref(wr),
                            _p(keep), len(head), C.c_void_p(stream or None)), "batch_stream_open")
+
+    def _dev_check(self, tensors):
+        """(tensor, element size, "name: type", entries or None) each: on the device, contiguous, of that size"""
+        for t, size, what, count in tensors:
+            if not _is_device_tensor(t) or not t.is_cuda or t.element_size() != size or not t.is_contiguous():
+                raise PcamvError(f"{what}, contiguous, on the device")
+            if count is not None and t.numel() != count:
+                raise PcamvError(f"{what.split(':')[0]}: {count} entries")
+
+    def stream_open_heads(self, data, off, cap, length, params, wr, heads, head_off, head_len, stream=0):
+        """pcamv_gpu_batch_stream_open_heads: stream_open with a head of its own for every context -- heads[head_off[i] : head_off[i] +
+        head_len[i]] of a contiguous uint8 device tensor (borrowed until the queued work is done); head_off / head_len int64 device
+        tensors read by this call alone.  Each GOP of a video has its own IDR picture: this is what lets the contexts' streams be the
+        GOPs of one video.  A context whose head does not lie inside `heads`, is longer than 2^24 or does not fit its region gets
+        length 0 and write_status() -1 in every step.  The bytes go through k_stream_copy"""
+        n = len(self.encs)
+        self._dev_check([(data, 1, "data: uint8", None), (off, 8, "off: int64", n), (cap, 8, "cap: int64", n), (length, 8, "length: int64", n),
+                         (heads, 1, "heads: uint8", None), (head_off, 8, "head_off: int64", n), (head_len, 8, "head_len: int64", n)])
+        fn = self.lib.pcamv_gpu_batch_stream_open_heads
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 6 + [C.c_size_t] + [C.c_void_p] * 3
+        self._slice_chk(fn(self.b, data.data_ptr(), data.numel(), off.data_ptr(), cap.data_ptr(), length.data_ptr(), C.byref(params), C.byref(wr),
+                           heads.data_ptr(), heads.numel(), head_off.data_ptr(), head_len.data_ptr(), C.c_void_p(stream or None)), "batch_stream_open_heads")
+
+    def join_streams(self, video, video_off, video_len, placed=None, stream=0):
+        """pcamv_gpu_batch_join_streams: the contexts' streams, as long as they are at this point of `stream`, appended in context order
+        to the video that begins at video[video_off[0]] and is video_len[0] bytes long so far (uint8 device tensor; int64 device tensors
+        of one entry; video_len is moved on).  placed (optional, int64 device tensor of one entry per context) receives where each
+        context's bytes went, counted from video_off, -1 for a context with an empty or refused stream -- the GOPs behind such a
+        context move up by one.  Nothing is written if the streams do not fit (join_status() -3).  No host synchronisation"""
+        n = len(self.encs)
+        self._dev_check([(video, 1, "video: uint8", None), (video_off, 8, "video_off: int64", 1), (video_len, 8, "video_len: int64", 1)] +
+                        ([(placed, 8, "placed: int64", n)] if placed is not None else []))
+        fn = self.lib.pcamv_gpu_batch_join_streams
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._slice_chk(fn(self.b, video.data_ptr(), video.numel(), video_off.data_ptr(), video_len.data_ptr(),
+                           placed.data_ptr() if placed is not None else None, C.c_void_p(stream or None)), "batch_join_streams")
+
+    def join_status(self):
+        """the last join_streams' code: 0, or ENOMEM (-3) where the streams did not fit the video buffer; synchronises"""
+        fn = self.lib.pcamv_gpu_batch_join_status
+        fn.argtypes = [C.c_void_p]
+        rc = fn(self.b)
+        if rc not in (0, ENOMEM):
+            self._slice_chk(rc, "batch_join_status")
+        return rc
+
+    def index_video_device(self, data, off, length, first_gop=0, max_units=64, stream=0):
+        """pcamv_gpu_batch_index_video_device: one video, data[off[0] : off[0] + length[0]] of a contiguous uint8 device tensor (off /
+        length int64 device tensors of one entry: what join_streams left), cut at its IDR units on the device (annexb_gops' rule); GOP
+        first_gop + i becomes context i's stream as by index_streams_device, a context past the last GOP an empty one.  Two host
+        synchronisations.  Returns (n_gops, preamble, every context's slice-unit count).  stream_param_sets behind this call resolves
+        the video's parameter sets once, for every context"""
+        n = len(self.encs)
+        self._dev_check([(data, 1, "data: uint8", None), (off, 8, "off: int64", 1), (length, 8, "length: int64", 1)])
+        out, ng, pre = np.zeros(n, np.int64), C.c_int64(), C.c_int64()
+        fn = self.lib.pcamv_gpu_batch_index_video_device
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._slice_chk(fn(self.b, data.data_ptr(), data.numel(), off.data_ptr(), length.data_ptr(), int(first_gop), int(max_units), C.byref(ng), C.byref(pre),
+                           _p(out), C.c_void_p(stream or None)), "batch_index_video_device")
+        return ng.value, pre.value, out
+
+    def index_video(self, video, first_gop=0, max_units=64, stream=0):
+        """pcamv_gpu_batch_index_video: the same on host bytes, staged with one copy"""
+        buf = _bytes_arg(video)
+        out, ng, pre = np.zeros(len(self.encs), np.int64), C.c_int64(), C.c_int64()
+        fn = self.lib.pcamv_gpu_batch_index_video
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._slice_chk(fn(self.b, _p(buf), len(video), int(first_gop), int(max_units), C.byref(ng), C.byref(pre), _p(out), C.c_void_p(stream or None)),
+                        "batch_index_video")
+        return ng.value, pre.value, out
 
     def write_stream_step(self, stream=0):
         """pcamv_gpu_batch_write_stream_step: every context's last step appended to its stream as [access unit delimiter +] P slice
