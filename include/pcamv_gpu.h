@@ -275,7 +275,8 @@ int pcamv_gpu_fetch_results(pcamv_ctx_t *ctx, pcamv_mb_t *out_mb, pcamv_embed_t 
 int  pcamv_gpu_batch_create(pcamv_ctx_t *const *ctxs, int n, pcamv_batch_t **batch);
 void pcamv_gpu_batch_destroy(pcamv_batch_t *batch);
 int  pcamv_gpu_batch_step(pcamv_batch_t *batch, int qp, float emrate, void *stream);
-/* kernel: the dominant kernel's name (below), or one of "k_embed_prepare", "k_extract_prepare", "k_extract_bits", "k_payload_check" */
+/* kernel: the dominant kernel's name (below), or one of "k_embed_prepare", "k_extract_prepare", "k_extract_bits", "k_payload_check",
+ * "k_message_count", "k_message_plan", "k_message_jobs", "k_extract_chain_message", "k_message_check" (the two kernels of a check under one timer) */
 int  pcamv_gpu_batch_kernel_time(pcamv_batch_t *batch, const char *kernel, double *avg_ms, int *launches, int reset);    /* ... or "k_parse_pslice", "k_parse_pslice_cavlc" */
 const char *pcamv_gpu_batch_last_error(const pcamv_batch_t *batch);
 /* Closed loop on the device: with on != 0 every batch step ends with pass 2 + the loop filter (embedding must be
@@ -347,6 +348,7 @@ int pcamv_gpu_abi_version(void);
 #define PCAMV_FEATURE_STREAM_WINDOW 0x100u      /* the receiver on byte streams takes a window of slice units per context in one call */
 #define PCAMV_FEATURE_PARAM_SETS 0x200u        /* SPS / PPS read on the device, per stream: the *_param_sets and *_sets calls at the end of this file */
 #define PCAMV_FEATURE_VIDEO 0x400u      /* one video of many chains: per-chain heads, streams joined, a video cut at its IDR units on the device */
+#define PCAMV_FEATURE_MESSAGE 0x800u    /* one message for a batch, split over its contexts' frames on the device (behind the payload path below) */
 unsigned pcamv_gpu_features(void);
 
 /* ---- Payload path: the caller's bits through the device-resident entry points, and back out on the device ----
@@ -390,6 +392,66 @@ int pcamv_gpu_extract_pframe(pcamv_ctx_t *ctx, const pcamv_mb_t *mbs, float emra
 /* diff[i] = number of bits in which context i's received stream differs from its attached payload, payload bits past its end
  * counting as zeros: the BER numerator of every chain from one kernel and one small copy.  Synchronises. */
 int pcamv_gpu_batch_payload_check(pcamv_batch_t *batch, int64_t *diff);
+
+/* ---- One message for one video: a batch-wide payload split on the device (PCAMV_FEATURE_MESSAGE) ----
+ *
+ * A payload belongs to one context, but a frame's message length m = frame_bits(emrate, n) is known only on the device, after that
+ * frame's analysis: a caller with ONE message for the many chains of a video cannot split it beforehand.  A message attached to a
+ * batch is split there.  The rule (csrc/pcamv_message.h is its definition, pcamv_gpu_message_plan its export without a GPU):
+ *
+ *   A job is one frame of one context in one call; a step call has k = 1 slot per context, a window call k.  The jobs of a call are
+ *   ordered slot-major, context-minor: (w, i) before (w', i') iff w < w', or w == w' and i < i' -- a window of k is observationally
+ *   k steps.  With the batch cursor B at the start of the call, job (w, i) owns the message bits at(w, i) .. at(w, i) + m(w, i) - 1,
+ *   at(w, i) = B + the sum of m over the jobs before it, and afterwards B += the sum of m over all jobs.  A job of status 0
+ *   contributes its m whatever stc_ok or the sub-matrices turn out to be (the per-context rule); PCAMV_EEOF contributes 0 bits and is
+ *   no failure; any other status contributes 0 bits and is a failure: its m is unknown, so everything behind it is misaligned.
+ *   Two sticky words: valid_bits = the smallest `at` of a failed job (received_bits while there is none), first_bad = that job's
+ *   (calls since the reset before its own, w, i), -1 each while there is none.  Bits past the message's end are zeros on the sender;
+ *   bits at or beyond the receiver's reservation are dropped, never written, and the next synchronising call of this group returns
+ *   PCAMV_ENOMEM once (the rule of a context's stream).  The column generators stay per context on both sides, advanced in slot order.
+ *
+ * The contract between sender and receiver, next to the emrate contract: the receiving batch has the sender's context count,
+ * context i takes GOP first_gop + i (pcamv_gpu_batch_index_video*), and rounds follow the sender's order.  A picture the sender
+ * failed to write (pcamv_gpu_batch_write_status -3) still consumed its m bits, which no receiver can see: checking write_status stays
+ * the caller's, as do error correction and the distribution of a message across GPUs.
+ *
+ * Sender.  set_message attaches packed bytes (copied; set_message_device borrows a device buffer) to the batch and sets the cursor to
+ * start_bit, so that another batch -- a last, smaller round -- can continue a message; NULL / 0 detaches.  PCAMV_EINVAL if a member
+ * context has a payload of its own (or belongs to another batch with a message).  While attached, pcamv_gpu_set_payload*,
+ * pcamv_gpu_step_device and pcamv_gpu_embed_pframe(message == NULL) on a member return PCAMV_EINVAL; an explicit `message` still wins
+ * and moves nothing.  Every batch_step with emrate > 0 then runs k_message_count (every context's n, m), k_message_plan (every
+ * context's place, into its payload cursor) and the embedding stage as with a payload.  message_tell synchronises: the cursor, the
+ * message's bits. */
+int pcamv_gpu_batch_set_message(pcamv_batch_t *batch, const uint8_t *bytes, int64_t n_bits, int64_t start_bit);
+int pcamv_gpu_batch_set_message_device(pcamv_batch_t *batch, const void *device_bytes, int64_t n_bits, int64_t start_bit);
+int pcamv_gpu_batch_message_tell(pcamv_batch_t *batch, int64_t *next_bit, int64_t *n_bits);
+/* Receiver.  rx_message_reserve makes room for n_bits of one received stream for the batch (0 releases) and empties it;
+ * rx_message_reset empties it: cursor 0, the sticky words cleared, every member's column generator at its initial state.  While the
+ * reservation exists every extract call of the batch (extract_step, extract_slices*, extract_nals*, extract_stream_step*,
+ * extract_stream_window*, the *_sets forms) writes into it by the rule -- k_extract_count, k_message_jobs, k_message_plan,
+ * k_extract_chain_message, k_extract_bits -- and the contexts need no reservation of their own: their streams and cursors do not
+ * move.  slice_status, window_status and the stream cursors behave as without one.  The extract calls of a batch with a reservation
+ * belong on one stream.  rx_message_tell / rx_message_fetch / message_check synchronise.  message_check: the number of bits in
+ * which the received stream differs from the message attached to this batch over [0, min(received, reserved)), message bits past
+ * its end counting as zeros. */
+int pcamv_gpu_batch_rx_message_reserve(pcamv_batch_t *batch, int64_t n_bits);
+int pcamv_gpu_batch_rx_message_reset(pcamv_batch_t *batch);
+int pcamv_gpu_batch_rx_message_tell(pcamv_batch_t *batch, int64_t *received_bits, int64_t *reserved_bits, int64_t *valid_bits, int64_t first_bad[3]);
+int pcamv_gpu_batch_rx_message_fetch(pcamv_batch_t *batch, uint8_t *bytes, int64_t n_bits);
+int pcamv_gpu_batch_message_check(pcamv_batch_t *batch, int64_t *diff, int64_t *received_bits, int64_t *valid_bits);
+/* (tests) synchronises; *guard_intact = are the guard words the library keeps behind the batch's received stream untouched */
+int pcamv_gpu_batch_debug_rx_message_guard(pcamv_batch_t *batch, int *guard_intact);
+/* The rule without a GPU.  m / status: [contexts * k], job i * k + w is slot w of context i (status NULL: all 0); capacity < 0: none.
+ * state: PCAMV_MESSAGE_STATE_WORDS words -- [0] cursor, [1] smallest `at` of a failed job or -1, [2..4] first_bad, [5] overrun flag,
+ * [6] calls so far -- made by message_state_reset, carried from call to call; at: [contexts * k] out.  message_frame_bits: m of a
+ * frame with n carriers, as both sides compute it.  message_plan_device is the parity probe of k_message_plan: the same on the
+ * device for the caller's arrays, no context's state involved; `at` has room for one word more, which comes back as the device
+ * left it (bytes 0xA5 beforehand). */
+#define PCAMV_MESSAGE_STATE_WORDS 8
+void pcamv_gpu_message_state_reset(int64_t *state, int64_t cursor);
+int32_t pcamv_gpu_message_frame_bits(float emrate, int32_t n_carriers);
+int pcamv_gpu_message_plan(const int32_t *m, const int32_t *status, int contexts, int k, int64_t capacity, int64_t *state, int64_t *at);
+int pcamv_gpu_message_plan_device(pcamv_ctx_t *ctx, const int32_t *m, const int32_t *status, int contexts, int k, int64_t capacity, int64_t *state, int64_t *at);
 
 /* ---- Receiver from a stream: CABAC P slices parsed on the device (kernel k_parse_pslice, one wavefront per slice) ----
  *

@@ -3,7 +3,11 @@ chains in flight, first on the rand() stream, then with a payload per chain and 
 Prints one JSON line: ms per step, and the average ms of k_embed_prepare (both ways), k_extract_prepare, k_extract_bits and of the
 payload check (one kernel over the batch + one copy, host clock).  Needs a GPU.
 
-    python tools/payload_timing.py [--gops 256] [--steps 6] [--warmup 2]
+--message: in the same run, behind the payload per chain, ONE message for the batch (Batch.set_message, a batch reservation): ms per step
+next to the per-chain path's, k_message_count and k_message_plan next to k_embed_prepare, k_message_jobs / k_extract_chain_message on
+the receiving side, and one message_check against payload_check.  The line is also written to profiles/message_timing.json.
+
+    python tools/payload_timing.py [--gops 256] [--steps 6] [--warmup 2] [--message [--out FILE]]
 """
 import argparse
 import json
@@ -22,6 +26,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--qp", type=int, default=26)
     ap.add_argument("--emrate", type=float, default=0.5)
+    ap.add_argument("--message", action="store_true", help="then one message for the batch, in the same run")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "message_timing.json"), help="--message: the file the line is appended to")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -76,8 +82,37 @@ def main():
     out["k_payload_check_ms"] = run.batch.kernel_time("k_payload_check", reset=True)[0]
     out["bits_per_chain"] = int(np.mean([enc.rx_tell()[0] for enc in run.encs]))
     out["chains_with_bit_errors"] = int((counts != 0).sum())
+    if args.message:
+        for enc in run.encs:
+            enc.set_payload(None)
+            enc.rx_reserve(0)
+        run.batch.set_message(rng.integers(0, 256, total // 8 * args.gops, dtype=np.uint8))
+        run.batch.rx_message_reserve(total * args.gops)
+        loop(t, 1, True); t += 1                      # first launches of the new kernels
+        names = ("k_embed_prepare", "k_message_count", "k_message_plan", "k_extract_count", "k_message_jobs", "k_extract_chain_message", "k_extract_bits")
+        for name in names:
+            run.batch.kernel_time(name, reset=True)
+        out["message_ms_per_step"] = loop(t, args.steps, True); t += args.steps
+        for name in names:
+            out[name + "_message_ms"] = run.batch.kernel_time(name, reset=True)[0]
+        out["k_message_plan_launches_per_step"] = 2   # one for the sender's step, one for extract_step
+        run.batch.message_check()
+        w0 = time.perf_counter()
+        diff, got, valid = run.batch.message_check()
+        out["message_check_wall_ms"] = (time.perf_counter() - w0) * 1e3
+        out["k_message_check_ms"] = run.batch.kernel_time("k_message_check", reset=True)[0]
+        out["message_bits"], out["message_bit_errors"], out["message_valid_bits"] = got, diff, valid
+        out["message_over_payload_step"] = out["message_ms_per_step"] / out["payload_ms_per_step"]
     run.close()
     print(json.dumps(out))
+    if args.message:
+        kept = []                                     # (the file's other lines: slice_parse_timing.py --window --message, one per entropy mode)
+        if os.path.exists(args.out):
+            kept = [ln for ln in open(args.out).read().splitlines() if ln.strip() and json.loads(ln).get("mode") != "payload_message"]
+        with open(args.out, "w") as f:
+            f.write("\n".join(sorted(kept + [json.dumps(dict(mode="payload_message", tool="payload_timing.py --message", **out))])) + "\n")
+        if out["message_bit_errors"] or out["message_valid_bits"] != out["message_bits"]:
+            sys.exit("payload_timing.py: the batch's received stream differs from its message")
     if out["chains_with_bit_errors"]:
         sys.exit("payload_timing.py: a chain's received stream differs from its payload")
 

@@ -28,6 +28,7 @@ Written to profiles/stream_window_timing.json, one line per entropy mode.
     python tools/slice_parse_timing.py --nal [--cavlc] [--counts 256,4096] [--reps 5] [--out profiles/nal_unescape_timing.json]
     python tools/slice_parse_timing.py --stream [--cavlc] [--counts 256,4096] [--reps 5] [--out profiles/stream_index_timing.json]
     python tools/slice_parse_timing.py --window [--cavlc] [--counts 256] [--reps 5] [--out profiles/stream_window_timing.json]
+    python tools/slice_parse_timing.py --window --message [--cavlc] [--counts 256]    # the same window with and without a batch reservation (profiles/message_timing.json)
 
 With --write-stream the sender's byte streams: 256 and 4096 closed-loop CIF chains (--me hex --subme 6, QP 26) that step
 and then write the same frame twice in turn -- Batch.write_step*(as_nal=True) with one host-made header, and Batch.write_stream_step,
@@ -337,6 +338,74 @@ def window_sweep(args, pcamv_amd, np, torch, out, slice_data, qp, m, want):
                                   parser_kernel_ms=dict(steps_each=ms["steps", parser], window=ms["window", parser], floor=ms["floor", parser]),
                                   window_kernels_ms={k: ms["window", k] for k in window_kernels}))
         few.close(); many.close()
+    for e in encs:
+        e.close()
+
+
+def window_message_sweep(args, pcamv_amd, np, torch, out, slice_data, qp, m, want):
+    """--window --message: per count n of streams of 8 frames, in one run and in turn within every repetition, each between two
+    synchronisations: one extract_stream_window(k=8) into the contexts' own streams, and the same window with a batch reservation
+    (one message for the batch: k_message_jobs, k_message_plan and k_extract_chain_message in the place of k_extract_chain).  The
+    batch's stream must hold what the contexts' streams hold, in plan order"""
+    dev = torch.device("cuda", 0)
+    frames = 8
+    sp, units, stream, _ = frames_stream(args, pcamv_amd, np, slice_data, qp, frames)
+    out.update(kernel="k_message_plan", parser=out["kernel"], stream_bytes=len(stream), frames=frames)
+    p = pcamv_amd.param_default(out["width"], out["height"])
+    pcamv_amd.param_parse(p, "subme", 5)
+    p.b_cabac = 0 if args.cavlc else 1
+    kernels = dict(own=("k_extract_count", "k_extract_chain", "k_extract_bits"),
+                   message=("k_extract_count", "k_message_jobs", "k_message_plan", "k_extract_chain_message", "k_extract_bits"))
+    encs = []
+    for n in [int(v) for v in args.counts.split(",")]:
+        while len(encs) < n:
+            e = pcamv_amd.Encoder(p)
+            e.rx_reserve(frames * m + 64)
+            encs.append(e)
+        batch = pcamv_amd.Batch(encs[:n])
+        stride = (len(stream) + 3) | 1
+        data = torch.from_numpy(np.tile(np.frombuffer(stream + bytes(stride - len(stream)), np.uint8), n)).to(dev)
+        off = torch.arange(n, dtype=torch.int64, device=dev) * stride
+        length = torch.full((n,), len(stream), dtype=torch.int64, device=dev)
+        torch.cuda.synchronize()
+        batch.index_streams_device(data, off, length, max_units=16)
+        batch.stream_window(frames)
+        wall, ms = dict(own=0.0, message=0.0), {}
+        for rep in range(args.reps + 1):                    # the first round is not timed: allocations, code load
+            for name in ("own", "message"):
+                batch.rx_message_reserve(frames * n * m + 64 if name == "message" else 0)
+                for e in encs[:n]:
+                    e.rx_reset()
+                if batch.index_streams_device(data, off, length, max_units=16).tolist() != [frames] * n:
+                    sys.exit("slice_parse_timing.py: the device's index differs from the host's")
+                for k in kernels[name]:
+                    batch.kernel_time(k, reset=True)
+                w0 = time.perf_counter()
+                batch.extract_stream_window(sp, 0.5, frames)
+                torch.cuda.synchronize()
+                if rep:
+                    wall[name] += (time.perf_counter() - w0) / args.reps
+                if (batch.window_status() != 0).any():
+                    sys.exit("slice_parse_timing.py: a unit failed on the device")
+                for k in kernels[name]:
+                    v, launches = batch.kernel_time(k, reset=True)
+                    if launches != 1:
+                        sys.exit("slice_parse_timing.py: a launch was not timed")
+                    if rep:
+                        ms[name, k] = ms.get((name, k), 0.0) + v / args.reps
+                if name == "own":
+                    own = [encs[0].received(), encs[n - 1].received()]
+                else:
+                    got, _, valid, _ = batch.rx_message_tell()
+                    rx = batch.message_received()
+                    first = np.concatenate([rx[(w * n) * m:(w * n + 1) * m] for w in range(frames)])
+                    last = np.concatenate([rx[(w * n + n - 1) * m:(w * n + n) * m] for w in range(frames)])
+                    if got != frames * n * m or valid != got or not np.array_equal(first, own[0]) or not np.array_equal(last, own[1]):
+                        sys.exit("slice_parse_timing.py: the batch's stream differs from the contexts' streams in plan order")
+        out["device"].append(dict(streams=n, frames=frames, slices=frames * n, own_wall_ms=wall["own"] * 1e3, message_wall_ms=wall["message"] * 1e3,
+                                  message_over_own=wall["message"] / wall["own"], own_kernels_ms={k: ms["own", k] for k in kernels["own"]},
+                                  message_kernels_ms={k: ms["message", k] for k in kernels["message"]}))
+        batch.close()
     for e in encs:
         e.close()
 
@@ -692,6 +761,7 @@ def main():
     ap.add_argument("--nal", action="store_true", help="the receiver on NAL units: k_nal_to_rbsp next to the parser (profiles/nal_unescape_timing.json)")
     ap.add_argument("--stream", action="store_true", help="the receiver on byte streams: the index kernels, and a stream step next to a NAL step (profiles/stream_index_timing.json)")
     ap.add_argument("--window", action="store_true", help="a window of 8 units per stream next to 8 stream steps and to one step of 8 times the streams (profiles/stream_window_timing.json)")
+    ap.add_argument("--message", action="store_true", help="with --window: one window of 8 with a batch reservation (one message for the batch) next to the same window without one (profiles/message_timing.json)")
     ap.add_argument("--write-stream", action="store_true", help="the sender's byte streams: write_stream_step next to write_step (profiles/stream_write_timing.json)")
     ap.add_argument("--param-sets", action="store_true", help="SPS / PPS read on the device: stream_param_sets, and a window under the streams' own sets next to one with the caller's parameters (profiles/param_sets_timing.json)")
     ap.add_argument("--video", action="store_true", help="one video of many chains: stream_open_heads, join_streams and index_video_device next to their yardsticks (profiles/video_timing.json)")
@@ -703,7 +773,7 @@ def main():
     args = ap.parse_args()
     args.counts = args.counts or ("256" if args.window else "256,4096" if args.nal or args.stream or args.write_stream or args.param_sets or args.video else "1,64,1024,4096")
     args.out = args.out if args.out is not None else os.path.join(ROOT, "profiles", "video_timing.json" if args.video else "param_sets_timing.json" if args.param_sets else "stream_write_timing.json" if args.write_stream else "stream_index_timing.json" if args.stream else
-                                                                  "stream_window_timing.json" if args.window else
+                                                                  "message_timing.json" if args.window and args.message else "stream_window_timing.json" if args.window else
                                                                   "nal_unescape_timing.json" if args.nal else "slice_parse_timing.json")
     index_cmp = index_vs_parent(args) if args.param_sets and args.parent_lib else None      # (before this process opens the device)
     import numpy as np
@@ -743,6 +813,11 @@ def main():
         return write_line(args, out, mode)
     if args.stream:
         stream_sweep(args, pcamv_amd, np, torch, out, g["slice_data"].tobytes(), qp, m, want)
+        return write_line(args, out, mode)
+    if args.window and args.message:
+        window_message_sweep(args, pcamv_amd, np, torch, out, g["slice_data"].tobytes(), qp, m, want)
+        out["tool"] = "slice_parse_timing.py --window --message"
+        out["mode"] = mode = "window_message_" + mode
         return write_line(args, out, mode)
     if args.window:
         window_sweep(args, pcamv_amd, np, torch, out, g["slice_data"].tobytes(), qp, m, want)

@@ -14,6 +14,7 @@
 #include "pcamv_planes.hip.h"
 #include "pcamv_kernels.hip.h"
 #include "pcamv_embed.hip.h"
+#include "pcamv_message.hip.h"
 #include "pcamv_slice.hip.h"
 #include "pcamv_host_tables.h"
 #include "pcamv_mvsyntax.h"
@@ -28,10 +29,12 @@ enum { KT_ANALYSE, KT_EMBED_PREPARE, KT_EXTRACT_PREPARE, KT_EXTRACT_BITS, KT_PAY
        KT_STREAM_PLAN, KT_STREAM_SCAN, KT_STREAM_PREFIX, KT_STREAM_PLACE, KT_STREAM_UNIT, KT_SLICE_HEADER, KT_STREAM_STATUS,
        KT_STREAM_OPEN, KT_STREAM_SLOT, KT_STREAM_COMMIT, KT_STREAM_WINDOW_UNIT, KT_EXTRACT_COUNT, KT_EXTRACT_CHAIN,
        KT_PSET_UNIT, KT_PSET_PARSE, KT_PSET_RESOLVE, KT_SLICE_HEADER_SETS,
-       KT_STREAM_OPEN_HEADS, KT_STREAM_JOIN, KT_STREAM_COPY_PLAN, KT_STREAM_COPY, KT_VIDEO_CUT, KT_N };
+       KT_STREAM_OPEN_HEADS, KT_STREAM_JOIN, KT_STREAM_COPY_PLAN, KT_STREAM_COPY, KT_VIDEO_CUT,
+       KT_MESSAGE_COUNT, KT_MESSAGE_PLAN, KT_MESSAGE_JOBS, KT_EXTRACT_CHAIN_MESSAGE, KT_MESSAGE_CHECK, KT_N };
 #define PCAMV_FEATURES (PCAMV_FEATURE_PAYLOAD | PCAMV_FEATURE_SLICE_PARSER | PCAMV_FEATURE_SLICE_PARSER_CAVLC | PCAMV_FEATURE_SLICE_WRITER | \
                         PCAMV_FEATURE_SLICE_WRITER_CAVLC | PCAMV_FEATURE_NAL_DEVICE | PCAMV_FEATURE_STREAM_DEVICE | PCAMV_FEATURE_STREAM_WRITER | \
-                        PCAMV_FEATURE_STREAM_WINDOW | PCAMV_FEATURE_PARAM_SETS | PCAMV_FEATURE_VIDEO)
+                        PCAMV_FEATURE_STREAM_WINDOW | PCAMV_FEATURE_PARAM_SETS | PCAMV_FEATURE_VIDEO | PCAMV_FEATURE_MESSAGE)
+#define MSG_GUARD_WORDS 4       /* words behind a batch's received stream that nothing may write */
 #define SLICE_GUARD_MBS 4       /* records behind a context's receive-side records that nothing may write (pcamv_gpu_debug_slice_records) */
 #define NSTAGE 2                /* staging buffers of extract_slices: a call waits for the one before the last */
 /* the stages of a step (batch_launch's `what`): plane production, analysis (search + RCA + encode), embedding, second pass */
@@ -159,6 +162,13 @@ struct pcamv_batch {
     StageRing tx_stage;
     /* ... that writes byte streams (k_stream_open, k_stream_slot, k_stream_commit): what stream_open was given and the library's own of it */
     StreamOut so;
+    /* one message for the batch (pcamv_message.hip.h).  Sender: the attached message (own copy, or the caller's device buffer), the state
+     * words (MSG_*) with the batch cursor, and per context of a step its m and its planned place.  Receiver: the batch's received stream
+     * and its state, per job of a call (m, status) and the planned place -- room for a window of PCAMV_STREAM_WINDOW_MAX --, and the
+     * partial sums of message_check, the result behind them */
+    const uint8_t *d_msg; long long msg_bits; uint8_t *d_msg_own; size_t msg_own_bytes;
+    long long *d_mtx; int *d_mtx_m; long long *d_mtx_at;
+    unsigned *d_mrx; long long mrx_bits; long long *d_mrx_state; int *d_mrx_job; long long *d_mrx_at, *d_mchk;
     KTimer kt[KT_N];            /* the timed kernels; the events of a timer are made by its first launch */
     char err[256];
 };
@@ -350,6 +360,8 @@ extern "C" void pcamv_gpu_batch_destroy(pcamv_batch_t *b)
     hipFree(b->d_wstat); hipFree(b->d_sw_tab); hipFree(b->d_sw_scratch);
     stage_destroy(b->tx_stage);
     hipFree(b->so.d_own); hipFree(b->so.d_head); hipFree(b->so.d_copy);
+    hipFree(b->d_msg_own); hipFree(b->d_mtx); hipFree(b->d_mtx_m); hipFree(b->d_mtx_at);
+    hipFree(b->d_mrx); hipFree(b->d_mrx_state); hipFree(b->d_mrx_job); hipFree(b->d_mrx_at); hipFree(b->d_mchk);
     ring_destroy(b->ring); ring_destroy(b->xring);
     for (KTimer &T : b->kt) kt_destroy(T);
     free(b->ctx);
@@ -495,7 +507,8 @@ static const char *kt_name(const pcamv_batch *b, int k)      /* what pcamv_gpu_b
                                             "k_write_pslice_cavlc", "k_nal_to_rbsp", "k_stream_plan", "k_stream_scan", "k_stream_prefix", "k_stream_place", "k_stream_unit",
                                             "k_slice_header", "k_stream_status", "k_stream_open", "k_stream_slot", "k_stream_commit",
                                             "k_stream_window_unit", "k_extract_count", "k_extract_chain", "k_pset_unit", "k_pset_parse", "k_pset_resolve",
-                                            "k_slice_header_sets", "k_stream_open_heads", "k_stream_join", "k_stream_copy_plan", "k_stream_copy", "k_video_cut"};
+                                            "k_slice_header_sets", "k_stream_open_heads", "k_stream_join", "k_stream_copy_plan", "k_stream_copy", "k_video_cut",
+                                            "k_message_count", "k_message_plan", "k_message_jobs", "k_extract_chain_message", "k_message_check"};
     return k == KT_ANALYSE ? dominant_kernel(b) : small[k];
 }
 extern "C" int pcamv_gpu_batch_copy_results_async(pcamv_batch_t *b, void *dst_mb, size_t mb_stride, void *dst_flip, size_t flip_stride, void *stream)
@@ -729,6 +742,7 @@ static int batch_push_descs(pcamv_batch *b, hipStream_t st, const FrameDev **dF,
     TRY(ring_take(b, b->ring, &slot));
     FrameDev *hF = b->h_F + (size_t)slot * b->n; EmbedDev *hE = b->h_E + (size_t)slot * b->n;
     for (int i = 0; i < b->n; i++) { hF[i] = b->ctx[i]->F; hF[i].self = b->d_F + (size_t)slot * b->n + i; hE[i] = b->ctx[i]->E; }
+    if (b->d_msg) for (int i = 0; i < b->n; i++) { hE[i].payload = b->d_msg; hE[i].payload_bits = b->msg_bits; }       /* one message for the batch: k_message_plan sets every cursor */
     HIPCHK(b, hipMemcpyAsync(b->d_F + (size_t)slot * b->n, hF, sizeof(FrameDev) * b->n, hipMemcpyHostToDevice, st));
     HIPCHK(b, hipMemcpyAsync(b->d_E + (size_t)slot * b->n, hE, sizeof(EmbedDev) * b->n, hipMemcpyHostToDevice, st));
     *dF = b->d_F + (size_t)slot * b->n; *dE = b->d_E + (size_t)slot * b->n; *slot_out = slot;
@@ -818,6 +832,14 @@ static int batch_launch(pcamv_batch *b, int what, hipStream_t st)
             hipLaunchKernelGGL(k_rca, dim3(F.n_mb * b->slots_per_mb, G), dim3(64), 0, st, dF, b->slots_per_mb);
             hipLaunchKernelGGL(k_encode, dim3(F.n_mb, G), dim3(64), 0, st, dF);
         }
+    }
+    if ((what & ST_EMBED) && b->d_msg) {     /* every context's m, then the place of each in the message: pstate[PST_TX], which k_embed_prepare reads */
+        int ev = kt_begin(b, KT_MESSAGE_COUNT, st);
+        hipLaunchKernelGGL(k_message_count, dim3(G), dim3(256), 0, st, dE, b->d_mtx_m);
+        kt_end(b, KT_MESSAGE_COUNT, ev, st);
+        ev = kt_begin(b, KT_MESSAGE_PLAN, st);
+        hipLaunchKernelGGL(k_message_plan, dim3(1), dim3(MSG_PLAN_THREADS), 0, st, b->d_mtx_m, (const int *)NULL, b->n, 1, PCAMV_MSG_NO_CAP, b->d_mtx, b->d_mtx_at, dE);
+        kt_end(b, KT_MESSAGE_PLAN, ev, st);
     }
     if (what & ST_EMBED) {
         const int ev = kt_begin(b, KT_EMBED_PREPARE, st);
@@ -971,9 +993,17 @@ static int embed_stage(pcamv_ctx *c, float emrate, const uint8_t *message, int m
     TRY(ctx_launch(c, ST_EMBED));
     return fetch_embed(c, out);
 }
+/* is the context a member of a batch that has one message attached?  Its bits then come from that batch's steps alone */
+static int ctx_under_message(pcamv_ctx *c, const char *call)
+{
+    for (int k = 0; k < c->n_member; k++)
+        if (c->member_of[k]->d_msg) return fail(c, PCAMV_EINVAL, "%s: a batch of this context has a message attached (pcamv_gpu_batch_set_message)", call);
+    return 0;
+}
 extern "C" int pcamv_gpu_embed_pframe(pcamv_ctx_t *c, float emrate, const uint8_t *message, int message_len, pcamv_embed_t *out)
 {
     if (!c || !out || emrate <= 0) return PCAMV_EINVAL;
+    if (!message) TRY(ctx_under_message(c, "embed_pframe without a message"));
     HIPCHK(c, hipSetDevice(c->device));
     return embed_stage(c, emrate, message, message_len, out);
 }
@@ -1092,6 +1122,7 @@ extern "C" int pcamv_gpu_batch_step(pcamv_batch_t *b, int qp, float emrate, void
 extern "C" int pcamv_gpu_step_device(pcamv_ctx_t *c, int qp, float emrate, void *stream)
 {
     if (!c) return PCAMV_EINVAL;
+    TRY(ctx_under_message(c, "step_device"));
     return on_behalf(c, c->self, pcamv_gpu_batch_step(c->self, qp, emrate, stream ? stream : (void *)c->stream));
 }
 extern "C" int pcamv_gpu_fetch_results(pcamv_ctx_t *c, pcamv_mb_t *out_mb, pcamv_embed_t *out)
@@ -1119,6 +1150,7 @@ static int payload_attach(pcamv_ctx *c, const uint8_t *d_bytes, int64_t n_bits)
 extern "C" int pcamv_gpu_set_payload(pcamv_ctx_t *c, const uint8_t *bytes, int64_t n_bits)
 {
     if (!c || n_bits < 0 || (n_bits > 0 && !bytes)) return PCAMV_EINVAL;
+    TRY(ctx_under_message(c, "set_payload"));
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipDeviceSynchronize());          /* frames in flight still read the payload attached so far */
     const size_t nb = bytes ? (size_t)((n_bits + 7) >> 3) : 0;
@@ -1133,6 +1165,7 @@ extern "C" int pcamv_gpu_set_payload(pcamv_ctx_t *c, const uint8_t *bytes, int64
 extern "C" int pcamv_gpu_set_payload_device(pcamv_ctx_t *c, const void *d_bytes, int64_t n_bits)
 {
     if (!c || n_bits < 0 || (n_bits > 0 && !d_bytes)) return PCAMV_EINVAL;
+    TRY(ctx_under_message(c, "set_payload_device"));
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipDeviceSynchronize());
     return payload_attach(c, d_bytes ? (const uint8_t *)d_bytes : NULL, d_bytes ? n_bits : 0);
@@ -1235,9 +1268,34 @@ static void extract_bits_launch(pcamv_batch *b, const ExtractDev *dX, int nx, in
         hipLaunchKernelGGL(k_extract_bits, dim3(groups, nx - x0 < 65535 ? nx - x0 : 65535), dim3(256), 0, st, dX + x0);
     kt_end(b, KT_EXTRACT_BITS, ev, st);
 }
-/* the two kernels of the receiving side for nx frames */
-static void extract_launch(pcamv_batch *b, const ExtractDev *dX, int nx, int cap, float emrate, hipStream_t st)
+/* Under a batch reservation (one message for the batch): behind k_extract_count, the frames of a call of k slots per context get their
+ * places in the batch's stream from one plan over all of them, then the chain with those places.  first: the codes of a stream call's
+ * first stages (or NULL) */
+static void extract_message_chain_launch(pcamv_batch *b, const ExtractDev *dX, int k, const int *first, hipStream_t st)
 {
+    const int jobs = b->n * k;
+    int *m = b->d_mrx_job, *status = b->d_mrx_job + (size_t)b->n * PCAMV_STREAM_WINDOW_MAX;
+    int ev = kt_begin(b, KT_MESSAGE_JOBS, st);
+    hipLaunchKernelGGL(k_message_jobs, dim3((jobs + 255) / 256), dim3(256), 0, st, dX, first, jobs, m, status);
+    kt_end(b, KT_MESSAGE_JOBS, ev, st);
+    ev = kt_begin(b, KT_MESSAGE_PLAN, st);
+    hipLaunchKernelGGL(k_message_plan, dim3(1), dim3(MSG_PLAN_THREADS), 0, st, m, status, b->n, k, b->mrx_bits, b->d_mrx_state, b->d_mrx_at, (const EmbedDev *)NULL);
+    kt_end(b, KT_MESSAGE_PLAN, ev, st);
+    ev = kt_begin(b, KT_EXTRACT_CHAIN_MESSAGE, st);
+    hipLaunchKernelGGL(k_extract_chain_message, dim3((b->n + 63) / 64), dim3(64), 0, st, dX, b->n, k, status, b->d_mrx_at);
+    kt_end(b, KT_EXTRACT_CHAIN_MESSAGE, ev, st);
+}
+/* the two kernels of the receiving side for nx frames (with a batch reservation: the frames of the batch's contexts, a window of one) */
+static void extract_launch(pcamv_batch *b, const ExtractDev *dX, int nx, int cap, float emrate, hipStream_t st, const int *first = NULL)
+{
+    if (b->d_mrx) {
+        const int ev = kt_begin(b, KT_EXTRACT_COUNT, st);
+        hipLaunchKernelGGL(k_extract_count, dim3(nx), dim3(1024), 0, st, dX);
+        kt_end(b, KT_EXTRACT_COUNT, ev, st);
+        extract_message_chain_launch(b, dX, 1, first, st);
+        extract_bits_launch(b, dX, nx, cap, emrate, st);
+        return;
+    }
     const int ev = kt_begin(b, KT_EXTRACT_PREPARE, st);
     hipLaunchKernelGGL(k_extract_prepare, dim3(nx), dim3(1024), 0, st, dX);
     kt_end(b, KT_EXTRACT_PREPARE, ev, st);
@@ -1256,6 +1314,7 @@ static int batch_push_xdescs(pcamv_batch *b, hipStream_t st, const ExtractDev **
     TRY(ring_take(b, b->xring, &slot));
     ExtractDev *hX = b->h_X + (size_t)slot * b->n;
     for (int i = 0; i < b->n; i++) hX[i] = b->ctx[i]->X;
+    if (b->d_mrx) for (int i = 0; i < b->n; i++) { hX[i].rx = b->d_mrx; hX[i].rx_cap_bits = b->mrx_bits; }      /* a batch reservation: every frame writes into the batch's stream */
     HIPCHK(b, hipMemcpyAsync(b->d_X + (size_t)slot * b->n, hX, sizeof(ExtractDev) * b->n, hipMemcpyHostToDevice, st));
     *dX = b->d_X + (size_t)slot * b->n; *slot_out = slot;
     return 0;
@@ -1269,7 +1328,8 @@ extern "C" int pcamv_gpu_batch_extract_step(pcamv_batch_t *b, float emrate, void
     TRY(batch_live(b));
     for (int i = 0; i < b->n; i++) {
         pcamv_ctx *c = b->ctx[i];
-        if (!c->d_rx) return fail(b, PCAMV_EINVAL, "context %d has no received buffer (pcamv_gpu_rx_reserve)", i);
+        if (!c->d_rx && !b->d_mrx) return fail(b, PCAMV_EINVAL, "context %d has no received buffer (pcamv_gpu_rx_reserve)", i);
+        if (b->d_mrx) { const int rc_c = rx_scratch(c); if (rc_c) return fail(b, rc_c, "context %d: %s", i, c->err); }
         c->X.mbs = c->F.rec_mb; c->X.flip = c->d_flip; c->X.bits = NULL; c->X.emrate = emrate; c->X.slice_status = NULL;
     }
     hipStream_t st = stream ? (hipStream_t)stream : b->ctx[0]->stream;
@@ -1366,7 +1426,7 @@ static int slice_contexts(pcamv_batch *b, int want_rx, float emrate)
 {
     for (int i = 0; i < b->n; i++) {
         pcamv_ctx *c = b->ctx[i];
-        if (want_rx && !c->d_rx) return fail(b, PCAMV_EINVAL, "context %d has no received buffer (pcamv_gpu_rx_reserve)", i);
+        if (want_rx && !c->d_rx && !b->d_mrx) return fail(b, PCAMV_EINVAL, "context %d has no received buffer (pcamv_gpu_rx_reserve)", i);
     }
     for (int i = 0; i < b->n; i++) {
         pcamv_ctx *c = b->ctx[i];
@@ -1390,12 +1450,12 @@ static void slice_launch(pcamv_batch *b, const ExtractDev *dX, SliceJobs J, int 
     kt_end(b, kt, ev, st);
 }
 /* parse (slices described by J, one per context) and, with extract != 0, the receiver's kernels behind it, all on `st` */
-static int slices_run(pcamv_batch *b, SliceJobs J, int cavlc, int extract, float emrate, hipStream_t st)
+static int slices_run(pcamv_batch *b, SliceJobs J, int cavlc, int extract, float emrate, hipStream_t st, const int *first = NULL)
 {
     const ExtractDev *dX; int slot;
     TRY(batch_push_xdescs(b, st, &dX, &slot));
     slice_launch(b, dX, J, cavlc, st);
-    if (extract) extract_launch(b, dX, b->n, b->ctx[0]->cap, emrate, st);
+    if (extract) extract_launch(b, dX, b->n, b->ctx[0]->cap, emrate, st, first);
     TRY(launched(b));
     return ring_release(b, b->xring, slot, st);
 }
@@ -1920,7 +1980,7 @@ static int extract_stream_step(pcamv_batch_t *b, const pcamv_stream_params_t *pa
     slice_header_launch(b, J, params, cavlc, 1, n, st);
     SliceJobs SJ;
     SJ.bytes = J.rbsp; SJ.bytes_size = J.rbsp_size; SJ.off = J.off; SJ.len = J.len; SJ.start_bit = J.start_bit; SJ.qp = cavlc ? NULL : J.qp;
-    const int rc = slices_run(b, SJ, cavlc, 1, emrate, st);
+    const int rc = slices_run(b, SJ, cavlc, 1, emrate, st, J.first);
     /* the parser refused what an earlier stage had failed (len -1) with its own code: the first stage's code takes its place */
     ev = kt_begin(b, KT_STREAM_STATUS, st);
     hipLaunchKernelGGL(k_stream_status, dim3((b->n + 63) / 64), dim3(64), 0, st, J.first, b->d_sstat, b->n, (int *)NULL, 0);
@@ -2010,6 +2070,7 @@ static int extract_stream_window(pcamv_batch_t *b, const pcamv_stream_params_t *
             X = b->ctx[i]->X;
             X.mbs = W.d_mbs + j * rec; X.stego = W.d_stego + j * (size_t)cap; X.hdr = W.d_hdr + j * 8; X.cols = W.d_cols + j * 2 * STC_MAXW;
             X.slice_status = W.d_stat + j;
+            if (b->d_mrx) { X.rx = b->d_mrx; X.rx_cap_bits = b->mrx_bits; }
         }
     HIPCHK(b, hipMemcpyAsync(dX, hX, sizeof(ExtractDev) * jobs, hipMemcpyHostToDevice, st));
     HIPCHK(b, hipEventRecord(W.desc_done[r], st));
@@ -2033,9 +2094,12 @@ static int extract_stream_window(pcamv_batch_t *b, const pcamv_stream_params_t *
     ev = kt_begin(b, KT_EXTRACT_COUNT, st);
     hipLaunchKernelGGL(k_extract_count, dim3((unsigned)jobs), dim3(1024), 0, st, dX);
     kt_end(b, KT_EXTRACT_COUNT, ev, st);
-    ev = kt_begin(b, KT_EXTRACT_CHAIN, st);
-    hipLaunchKernelGGL(k_extract_chain, dim3((b->n + 63) / 64), dim3(64), 0, st, dX, b->n, k);
-    kt_end(b, KT_EXTRACT_CHAIN, ev, st);
+    if (b->d_mrx) extract_message_chain_launch(b, dX, k, J.first, st);
+    else {
+        ev = kt_begin(b, KT_EXTRACT_CHAIN, st);
+        hipLaunchKernelGGL(k_extract_chain, dim3((b->n + 63) / 64), dim3(64), 0, st, dX, b->n, k);
+        kt_end(b, KT_EXTRACT_CHAIN, ev, st);
+    }
     extract_bits_launch(b, dX, (int)jobs, cap, emrate, st);
     ev = kt_begin(b, KT_STREAM_STATUS, st);
     hipLaunchKernelGGL(k_stream_status, dim3((unsigned)((jobs + 63) / 64)), dim3(64), 0, st, J.first, W.d_stat, (int)jobs, b->d_sstat, k);
@@ -2358,6 +2422,209 @@ extern "C" int pcamv_gpu_batch_payload_check(pcamv_batch_t *b, int64_t *diff)
     static_assert(sizeof(long long) == sizeof(int64_t), "payload_check copies the counts as they are");
     HIPCHK(b, hipMemcpy(diff, b->d_chk, sizeof(int64_t) * b->n, hipMemcpyDeviceToHost));
     for (int i = 0; i < b->n; i++) { const int rc = rx_check(b->ctx[i], NULL); if (rc) return fail(b, rc, "context %d: %s", i, b->ctx[i]->err); }
+    return 0;
+}
+
+/* ------------------------------------------------------------------ one message for the batch (pcamv_message.h, pcamv_message.hip.h) */
+extern "C" int pcamv_gpu_message_plan(const int32_t *m, const int32_t *status, int contexts, int k, int64_t capacity, int64_t *state, int64_t *at)
+{
+    if (!m || !state || !at || contexts < 1 || k < 1) return PCAMV_EINVAL;
+    static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(int) == sizeof(int32_t), "the caller's arrays are read as they are");
+    pcamv_message_plan(m, status, contexts, k, capacity < 0 ? PCAMV_MSG_NO_CAP : capacity, PCAMV_EEOF, (long long *)state, (long long *)at);
+    return 0;
+}
+extern "C" void pcamv_gpu_message_state_reset(int64_t *state, int64_t cursor) { if (state) pcamv_message_state_reset((long long *)state, cursor); }
+extern "C" int32_t pcamv_gpu_message_frame_bits(float emrate, int32_t n_carriers) { return pcamv_stc_frame_bits(emrate, n_carriers); }
+/* the parity probe: k_message_plan on the caller's arrays, no context's state involved */
+extern "C" int pcamv_gpu_message_plan_device(pcamv_ctx_t *c, const int32_t *m, const int32_t *status, int contexts, int k, int64_t capacity, int64_t *state, int64_t *at)
+{
+    if (!c || !m || !state || !at || contexts < 1 || k < 1 || (long long)contexts * k > (1LL << 24)) return PCAMV_EINVAL;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t jobs = (size_t)contexts * (size_t)k;
+    DevTmp<int> d_m, d_st; DevTmp<long long> d_state, d_at;
+    HIPCHK(c, d_m.alloc(jobs)); HIPCHK(c, d_at.alloc(jobs + 1)); HIPCHK(c, d_state.alloc(MSG_WORDS));
+    if (status) HIPCHK(c, d_st.alloc(jobs));
+    HIPCHK(c, hipMemcpy(d_m, m, jobs * 4, hipMemcpyHostToDevice));
+    if (status) HIPCHK(c, hipMemcpy(d_st, status, jobs * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_state, state, MSG_WORDS * 8, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemset(d_at, 0xA5, (jobs + 1) * 8));           /* (the word behind the jobs comes back with them: at[jobs] is the caller's to look at) */
+    hipLaunchKernelGGL(k_message_plan, dim3(1), dim3(MSG_PLAN_THREADS), 0, c->stream, d_m, status ? (const int *)d_st : (const int *)NULL, contexts, k,
+                       capacity < 0 ? PCAMV_MSG_NO_CAP : (long long)capacity, d_state, d_at, (const EmbedDev *)NULL);
+    TRY(launched(c));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(state, d_state, MSG_WORDS * 8, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(at, d_at, (jobs + 1) * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+/* Sender */
+/* a message can be attached only where no member has another source of bits attached: refused before anything changes */
+static int message_members_free(pcamv_batch *b)
+{
+    for (int i = 0; i < b->n; i++) {
+        pcamv_ctx *c = b->ctx[i];
+        if (c->E.payload) return fail(b, PCAMV_EINVAL, "context %d has a payload of its own attached (pcamv_gpu_set_payload)", i);
+        for (int k = 0; k < c->n_member; k++)
+            if (c->member_of[k] != b && c->member_of[k]->d_msg) return fail(b, PCAMV_EINVAL, "context %d belongs to another batch that has a message attached", i);
+    }
+    return 0;
+}
+static int message_attach(pcamv_batch *b, const uint8_t *d_bytes, int64_t n_bits, int64_t start_bit)
+{
+    if (d_bytes) {
+        if (!b->d_mtx) {
+            HIPCHK(b, dalloc(&b->d_mtx, MSG_WORDS)); HIPCHK(b, dalloc(&b->d_mtx_m, (size_t)b->n)); HIPCHK(b, dalloc(&b->d_mtx_at, (size_t)b->n));
+        }
+        long long st[MSG_WORDS];
+        pcamv_message_state_reset(st, start_bit);
+        HIPCHK(b, hipMemcpy(b->d_mtx, st, sizeof(st), hipMemcpyHostToDevice));
+    }
+    b->d_msg = d_bytes; b->msg_bits = d_bytes ? n_bits : 0;
+    return 0;
+}
+extern "C" int pcamv_gpu_batch_set_message(pcamv_batch_t *b, const uint8_t *bytes, int64_t n_bits, int64_t start_bit)
+{
+    if (!b || n_bits < 0 || start_bit < 0) return PCAMV_EINVAL;
+    HIPCHK(b, hipSetDevice(b->device));
+    TRY(batch_live(b));
+    HIPCHK(b, hipDeviceSynchronize());          /* frames in flight still read the message attached so far */
+    if (!bytes || !n_bits) return message_attach(b, NULL, 0, 0);
+    TRY(message_members_free(b));
+    const size_t nb = (size_t)((n_bits + 7) >> 3);
+    if (nb > b->msg_own_bytes) {
+        hipFree(b->d_msg_own); b->d_msg_own = NULL; b->msg_own_bytes = 0; b->d_msg = NULL;
+        HIPCHK(b, dalloc(&b->d_msg_own, nb));
+        b->msg_own_bytes = nb;
+    }
+    b->d_msg = NULL;                            /* (detached until the new bytes stand) */
+    HIPCHK(b, hipMemcpy(b->d_msg_own, bytes, nb, hipMemcpyHostToDevice));
+    return message_attach(b, b->d_msg_own, n_bits, start_bit);
+}
+extern "C" int pcamv_gpu_batch_set_message_device(pcamv_batch_t *b, const void *d_bytes, int64_t n_bits, int64_t start_bit)
+{
+    if (!b || n_bits < 0 || start_bit < 0) return PCAMV_EINVAL;
+    HIPCHK(b, hipSetDevice(b->device));
+    TRY(batch_live(b));
+    HIPCHK(b, hipDeviceSynchronize());
+    if (d_bytes && n_bits) TRY(message_members_free(b));
+    return message_attach(b, d_bytes && n_bits ? (const uint8_t *)d_bytes : NULL, n_bits, start_bit);
+}
+extern "C" int pcamv_gpu_batch_message_tell(pcamv_batch_t *b, int64_t *next_bit, int64_t *n_bits)
+{
+    if (!b) return PCAMV_EINVAL;
+    HIPCHK(b, hipSetDevice(b->device));
+    if (!b->d_msg) return fail(b, PCAMV_EINVAL, "no message is attached to this batch (pcamv_gpu_batch_set_message)");
+    HIPCHK(b, hipDeviceSynchronize());
+    long long cur = 0;
+    HIPCHK(b, hipMemcpy(&cur, b->d_mtx + MSG_CURSOR, sizeof(cur), hipMemcpyDeviceToHost));
+    if (next_bit) *next_bit = cur;
+    if (n_bits) *n_bits = b->msg_bits;
+    return 0;
+}
+/* Receiver */
+extern "C" int pcamv_gpu_batch_rx_message_reset(pcamv_batch_t *b)
+{
+    if (!b) return PCAMV_EINVAL;
+    HIPCHK(b, hipSetDevice(b->device));
+    TRY(batch_live(b));
+    if (!b->d_mrx) return fail(b, PCAMV_EINVAL, "this batch has no reservation (pcamv_gpu_batch_rx_message_reserve)");
+    HIPCHK(b, hipDeviceSynchronize());
+    long long st[MSG_WORDS];
+    pcamv_message_state_reset(st, 0);
+    HIPCHK(b, hipMemcpy(b->d_mrx_state, st, sizeof(st), hipMemcpyHostToDevice));
+    HIPCHK(b, hipMemset(b->d_mrx, 0, (size_t)((b->mrx_bits + 31) >> 5) * 4));
+    const long long lcg = 1;                    /* every context's column generator at its initial state; its own stream stays as it is */
+    for (int i = 0; i < b->n; i++) HIPCHK(b, hipMemcpy(b->ctx[i]->E.pstate + PST_RX_LCG, &lcg, sizeof(lcg), hipMemcpyHostToDevice));
+    return 0;
+}
+extern "C" int pcamv_gpu_batch_rx_message_reserve(pcamv_batch_t *b, int64_t n_bits)
+{
+    if (!b || n_bits < 0) return PCAMV_EINVAL;
+    HIPCHK(b, hipSetDevice(b->device));
+    TRY(batch_live(b));
+    HIPCHK(b, hipDeviceSynchronize());
+    hipFree(b->d_mrx); b->d_mrx = NULL; b->mrx_bits = 0;
+    if (!n_bits) return 0;
+    const size_t jobs = (size_t)b->n * PCAMV_STREAM_WINDOW_MAX;
+    if (!b->d_mrx_state) {
+        HIPCHK(b, dalloc(&b->d_mrx_state, MSG_WORDS)); HIPCHK(b, dalloc(&b->d_mrx_job, 2 * jobs)); HIPCHK(b, dalloc(&b->d_mrx_at, jobs));
+        HIPCHK(b, dalloc(&b->d_mchk, MSG_CHECK_GROUPS + 1));
+    }
+    const size_t words = (size_t)((n_bits + 31) >> 5);
+    HIPCHK(b, dalloc(&b->d_mrx, words + MSG_GUARD_WORDS));          /* guard words behind the stream that nothing may write (pcamv_gpu_batch_debug_rx_message_guard) */
+    HIPCHK(b, hipMemset(b->d_mrx + words, 0xA5, MSG_GUARD_WORDS * 4));
+    b->mrx_bits = n_bits;
+    const int rc = pcamv_gpu_batch_rx_message_reset(b);
+    if (rc) { hipFree(b->d_mrx); b->d_mrx = NULL; b->mrx_bits = 0; }
+    return rc;
+}
+/* synchronises; are the guard words behind the batch's received stream as the reservation left them? */
+extern "C" int pcamv_gpu_batch_debug_rx_message_guard(pcamv_batch_t *b, int *guard_intact)
+{
+    if (!b || !guard_intact || !b->d_mrx) return PCAMV_EINVAL;
+    HIPCHK(b, hipSetDevice(b->device));
+    HIPCHK(b, hipDeviceSynchronize());
+    uint8_t g[MSG_GUARD_WORDS * 4];
+    HIPCHK(b, hipMemcpy(g, b->d_mrx + (size_t)((b->mrx_bits + 31) >> 5), sizeof(g), hipMemcpyDeviceToHost));
+    *guard_intact = 1;
+    for (size_t i = 0; i < sizeof(g); i++) if (g[i] != 0xA5) *guard_intact = 0;
+    return 0;
+}
+/* after a synchronisation: the state words; did a frame run past the batch's reservation?  (reported once, like rx_check) */
+static int rx_message_check(pcamv_batch *b, long long *st)
+{
+    if (!b->d_mrx) return fail(b, PCAMV_EINVAL, "this batch has no reservation (pcamv_gpu_batch_rx_message_reserve)");
+    HIPCHK(b, hipDeviceSynchronize());
+    HIPCHK(b, hipMemcpy(st, b->d_mrx_state, MSG_WORDS * sizeof(long long), hipMemcpyDeviceToHost));
+    if (st[MSG_OVERRUN]) {
+        hipMemset(b->d_mrx_state + MSG_OVERRUN, 0, sizeof(long long));
+        return fail(b, PCAMV_ENOMEM, "received message: %lld bits extracted, %lld reserved (the bits beyond were dropped)", st[MSG_CURSOR], b->mrx_bits);
+    }
+    return 0;
+}
+extern "C" int pcamv_gpu_batch_rx_message_tell(pcamv_batch_t *b, int64_t *received_bits, int64_t *reserved_bits, int64_t *valid_bits, int64_t first_bad[3])
+{
+    if (!b) return PCAMV_EINVAL;
+    HIPCHK(b, hipSetDevice(b->device));
+    long long st[MSG_WORDS] = {0};
+    const int rc = rx_message_check(b, st);
+    if (rc && rc != PCAMV_ENOMEM) return rc;
+    if (received_bits) *received_bits = st[MSG_CURSOR];
+    if (reserved_bits) *reserved_bits = b->mrx_bits;
+    if (valid_bits) *valid_bits = st[MSG_VALID] < 0 ? st[MSG_CURSOR] : st[MSG_VALID];
+    if (first_bad) { first_bad[0] = st[MSG_BAD_CALL]; first_bad[1] = st[MSG_BAD_SLOT]; first_bad[2] = st[MSG_BAD_CTX]; }
+    return rc;
+}
+extern "C" int pcamv_gpu_batch_rx_message_fetch(pcamv_batch_t *b, uint8_t *bytes, int64_t n_bits)
+{
+    if (!b || !bytes || n_bits < 0 || n_bits > b->mrx_bits) return PCAMV_EINVAL;
+    HIPCHK(b, hipSetDevice(b->device));
+    long long st[MSG_WORDS];
+    TRY(rx_message_check(b, st));
+    if (n_bits) HIPCHK(b, hipMemcpy(bytes, b->d_mrx, (size_t)((n_bits + 7) >> 3), hipMemcpyDeviceToHost));
+    return 0;
+}
+extern "C" int pcamv_gpu_batch_message_check(pcamv_batch_t *b, int64_t *diff, int64_t *received_bits, int64_t *valid_bits)
+{
+    if (!b || !diff) return PCAMV_EINVAL;
+    HIPCHK(b, hipSetDevice(b->device));
+    TRY(batch_live(b));
+    if (!b->d_msg) return fail(b, PCAMV_EINVAL, "no message is attached to this batch (pcamv_gpu_batch_set_message)");
+    long long state[MSG_WORDS];
+    TRY(rx_message_check(b, state));
+    hipStream_t st = b->ctx[0]->stream;
+    long long got = state[MSG_CURSOR] < b->mrx_bits ? state[MSG_CURSOR] : b->mrx_bits;
+    long long groups = (((got + 7) >> 3) + 255) / 256;
+    groups = groups < 1 ? 1 : groups > MSG_CHECK_GROUPS ? MSG_CHECK_GROUPS : groups;
+    const int ev = kt_begin(b, KT_MESSAGE_CHECK, st);
+    hipLaunchKernelGGL(k_message_check, dim3((unsigned)groups), dim3(256), 0, st, (const uint8_t *)b->d_mrx, b->mrx_bits, b->d_mrx_state, b->d_msg, b->msg_bits, b->d_mchk);
+    hipLaunchKernelGGL(k_message_check_sum, dim3(1), dim3(256), 0, st, b->d_mchk, (int)groups, b->d_mchk + MSG_CHECK_GROUPS);
+    kt_end(b, KT_MESSAGE_CHECK, ev, st);
+    TRY(launched(b));
+    HIPCHK(b, hipStreamSynchronize(st));
+    static_assert(sizeof(long long) == sizeof(int64_t), "message_check copies the count as it is");
+    HIPCHK(b, hipMemcpy(diff, b->d_mchk + MSG_CHECK_GROUPS, sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (received_bits) *received_bits = state[MSG_CURSOR];
+    if (valid_bits) *valid_bits = state[MSG_VALID] < 0 ? state[MSG_CURSOR] : state[MSG_VALID];
     return 0;
 }
 

@@ -1,7 +1,7 @@
 /*
  * pcamv_stc_extract.h -- the receiving side of the syndrome-trellis code, one message bit at a time.
  *
- * Compiles for the device (k_extract_prepare / k_extract_chain / k_extract_bits, and the message length and matrix builder
+ * Compiles for the device (k_extract_prepare / k_extract_chain / k_extract_chain_message / k_extract_bits, and the message length and matrix builder
  * k_embed_prepare shares with them), for the host side of the library (the column generator of pcamv_gpu_stc_extract_lcg) and for
  * plain C++ test programs (tests/emu/stc_extract_driver.cpp, tests/fuzz/check_extract_window.cpp): no HIP type, no table of its own.
  *
@@ -117,27 +117,40 @@ enum { PST_TX = 0,            /* payload bits the sender has consumed */
  * `work` is where the columns are built (the generator compares every new column with all earlier ones: LDS where the caller has
  * some), `cols` where they go once both sub-matrices stand; the two may be the same array.
  * hdr: [0]=n [1]=m [2]=sub-matrices built [6..7]=bit offset of the frame in the received stream, low word first */
-PCAMV_HD void pcamv_extract_chain_slot(const unsigned *table, float emrate, int status, int have_rx, long long rx_cap_bits, int *hdr,
-                                       unsigned *work, unsigned *cols, long long *pstate)
+/* (the frame itself, whoever decided its place `at`: hdr and the columns, the generator moved; returns m, -1 for status != 0) */
+PCAMV_HD int pcamv_extract_chain_frame(const unsigned *table, float emrate, int status, long long at, int *hdr, unsigned *work, unsigned *cols, long long *lcg)
 {
-    const long long at = pstate[PST_RX];
     hdr[6] = (int)(unsigned)((unsigned long long)at & 0xffffffffu); hdr[7] = (int)(unsigned)((unsigned long long)at >> 32);
-    if (status) { hdr[0] = 0; hdr[1] = 0; hdr[2] = 0; return; }
+    if (status) { hdr[0] = 0; hdr[1] = 0; hdr[2] = 0; return -1; }
     const int n = hdr[0], m = pcamv_stc_frame_bits(emrate, n);
     const bool sched = m > 0 && m <= n;
     const double invalpha = sched ? (double)n / m : 0.0;
     const int shorter = (int)floor(invalpha), longer = (int)ceil(invalpha);
-    const int ok = sched && pcamv_stc_matrix(table, shorter, PCAMV_STC_HEIGHT, work, pstate + PST_RX_LCG) &&
-                   pcamv_stc_matrix(table, longer, PCAMV_STC_HEIGHT, work + STC_MAXW, pstate + PST_RX_LCG);
+    const int ok = sched && pcamv_stc_matrix(table, shorter, PCAMV_STC_HEIGHT, work, lcg) && pcamv_stc_matrix(table, longer, PCAMV_STC_HEIGHT, work + STC_MAXW, lcg);
     if (ok && work != cols) {
         for (int k = 0; k < shorter; k++) cols[k] = work[k];
         for (int k = 0; k < longer; k++) cols[STC_MAXW + k] = work[STC_MAXW + k];
     }
     hdr[1] = m; hdr[2] = ok;
-    if (have_rx) {
+    return m;
+}
+PCAMV_HD void pcamv_extract_chain_slot(const unsigned *table, float emrate, int status, int have_rx, long long rx_cap_bits, int *hdr,
+                                       unsigned *work, unsigned *cols, long long *pstate)
+{
+    const long long at = pstate[PST_RX];
+    const int m = pcamv_extract_chain_frame(table, emrate, status, at, hdr, work, cols, pstate + PST_RX_LCG);
+    if (m >= 0 && have_rx) {
         pstate[PST_RX] = at + m;
         if (at + m > rx_cap_bits) pstate[PST_OVERRUN] = 1;
     }
+}
+/* The sibling for a frame whose place was planned for the whole batch (one message for the batch, pcamv_message.h): `at` is given,
+ * hdr[6..7] and hdr[1..2] are written and the context's column generator moves as above -- the generators stay per context, advanced in
+ * slot order --, while the context's own stream is not involved: PST_RX and PST_OVERRUN stay as they are. */
+PCAMV_HD void pcamv_extract_chain_slot_at(const unsigned *table, float emrate, int status, long long at, int *hdr, unsigned *work, unsigned *cols,
+                                          long long *pstate)
+{
+    pcamv_extract_chain_frame(table, emrate, status, at, hdr, work, cols, pstate + PST_RX_LCG);
 }
 
 /* host side: the same columns with the widths checked against STC_MAXW (a caller's array) */

@@ -498,6 +498,55 @@ def annexb_gops(data, cap=None):
     return gops[:min(cap, n.value)], n.value, pre.value
 
 
+FEATURE_MESSAGE = 0x800         # one message for a batch: Batch.set_message, Batch.rx_message_reserve, Batch.message_check, message_plan
+MESSAGE_STATE_WORDS = 8
+
+
+def _message_args(m, status, contexts, k, emrate):
+    m = np.ascontiguousarray(m, np.int32).reshape(-1)
+    if len(m) != contexts * k or contexts < 1 or k < 1:
+        raise PcamvError(f"message_plan: {len(m)} jobs for {contexts} contexts x {k} slots")
+    if emrate is not None:              # carrier counts were given: m as both sides compute it
+        fn = load_library().pcamv_gpu_message_frame_bits
+        fn.restype, fn.argtypes = C.c_int32, [C.c_float, C.c_int32]
+        m = np.array([fn(C.c_float(emrate), int(n)) for n in m], np.int32)
+    if status is not None:
+        status = np.ascontiguousarray(status, np.int32).reshape(-1)
+        if len(status) != len(m):
+            raise PcamvError("message_plan: one status per job")
+    return m, status
+
+
+def _message_result(state, at):
+    got = int(state[0])
+    return {"at": at, "cursor": got, "valid_bits": got if state[1] < 0 else int(state[1]), "first_bad": tuple(int(v) for v in state[2:5]),
+            "overrun": bool(state[5]), "state": state}
+
+
+def message_plan(m, status=None, contexts=None, k=1, start=0, capacity=-1, emrate=None, state=None):
+    """pcamv_gpu_message_plan: which bits of a batch's one message every job of a call takes, without a GPU.  m (or, with emrate, the
+    carrier counts) and status are arrays of contexts * k jobs, job i * k + w = slot w of context i; the order is slot-major.  `start`
+    is the batch cursor, or `state` what an earlier call returned (sticky valid_bits / first_bad, the call count).  capacity < 0: no
+    reservation.  Returns a dict: at (per job), cursor, valid_bits, first_bad (call, slot, context; -1 each: none), overrun, state"""
+    contexts = (len(np.reshape(m, -1)) // k) if contexts is None else contexts
+    m, status = _message_args(m, status, contexts, k, emrate)
+    lib = load_library()
+    st = np.zeros(MESSAGE_STATE_WORDS, np.int64)
+    if state is None:
+        lib.pcamv_gpu_message_state_reset.restype = None
+        lib.pcamv_gpu_message_state_reset.argtypes = [C.c_void_p, C.c_int64]
+        lib.pcamv_gpu_message_state_reset(_p(st), int(start))
+    else:
+        st[:] = state
+    at = np.zeros(len(m), np.int64)
+    fn = lib.pcamv_gpu_message_plan
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]
+    rc = fn(_p(m), _p(status) if status is not None else None, contexts, k, int(capacity), _p(st), _p(at))
+    if rc:
+        raise PcamvError(f"pcamv_gpu_message_plan failed: {rc}")
+    return _message_result(st, at)
+
+
 def parse_sps(rbsp):
     """pcamv_gpu_parse_sps: (return code, Sps) of an SPS unit's RBSP (behind the header byte, unescaped); the Sps is all zeros when the
     code is not 0"""
@@ -860,6 +909,27 @@ class Encoder:
         fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         self._chk(fn(self.ctx, _p(data), len(data), _p(off), _p(length), n, _p(tables), cap, _p(ng), _p(pre)), "video_gops_device")
         return tables, ng, pre
+
+    def message_plan_device(self, m, status=None, contexts=None, k=1, start=0, capacity=-1, emrate=None, state=None):
+        """pcamv_gpu_message_plan_device: message_plan by k_message_plan on the caller's arrays -- the parity probe of the kernel, no
+        context's state involved.  The same result dict; "guard" is the word behind the jobs' `at` as the device left it (bytes 0xA5
+        beforehand)"""
+        contexts = (len(np.reshape(m, -1)) // k) if contexts is None else contexts
+        m, status = _message_args(m, status, contexts, k, emrate)
+        st = np.zeros(MESSAGE_STATE_WORDS, np.int64)
+        if state is None:
+            self.lib.pcamv_gpu_message_state_reset.restype = None
+            self.lib.pcamv_gpu_message_state_reset.argtypes = [C.c_void_p, C.c_int64]
+            self.lib.pcamv_gpu_message_state_reset(_p(st), int(start))
+        else:
+            st[:] = state
+        at = np.zeros(len(m) + 1, np.int64)
+        fn = self.lib.pcamv_gpu_message_plan_device
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]
+        self._chk(fn(self.ctx, _p(m), _p(status) if status is not None else None, contexts, k, int(capacity), _p(st), _p(at)), "message_plan_device")
+        out = _message_result(st, at[:-1])
+        out["guard"] = int(at[-1])
+        return out
 
     def slice_headers_device(self, data, off, length, nal_header, params):
         """pcamv_gpu_slice_headers_device: the P slice headers of the RBSPs data[off[i] : off[i] + length[i]] read by k_slice_header,
@@ -1433,6 +1503,84 @@ class Batch:
         if rc:
             raise PcamvError(f"batch_payload_check failed ({rc}): {self.lib.pcamv_gpu_batch_last_error(self.b).decode()}")
         return out
+
+    # one message for the batch: split over the contexts' frames on the device (pcamv_gpu.h: the rule; message_plan: the same without a GPU)
+    def _msg_chk(self, rc, what):
+        if rc:
+            raise PcamvError(f"{what} failed ({rc}): {self.lib.pcamv_gpu_batch_last_error(self.b).decode()}")
+
+    def set_message(self, payload, n_bits=None, start_bit=0):
+        """attach one message to the batch: packed bytes (pack_bits) as a numpy array / bytes (copied), or a torch uint8 device tensor
+        (borrowed: kept referenced here while attached); n_bits defaults to all of it; the batch cursor starts at start_bit.  None detaches.
+        Refused if a member has a payload of its own"""
+        self.lib.pcamv_gpu_batch_set_message.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]
+        self.lib.pcamv_gpu_batch_set_message_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]
+        self._message_keep = None
+        if payload is None:
+            return self._msg_chk(self.lib.pcamv_gpu_batch_set_message(self.b, None, 0, 0), "batch_set_message")
+        if _is_device_tensor(payload):
+            if not payload.is_cuda or payload.element_size() != 1 or not payload.is_contiguous():
+                raise PcamvError("a borrowed message is a contiguous uint8 tensor on the device")
+            n_bits = 8 * payload.numel() if n_bits is None else n_bits
+            if n_bits > 8 * payload.numel():
+                raise PcamvError("n_bits beyond the tensor")
+            self._msg_chk(self.lib.pcamv_gpu_batch_set_message_device(self.b, C.c_void_p(payload.data_ptr()), n_bits, start_bit), "batch_set_message_device")
+            self._message_keep = payload
+            return None
+        data = np.frombuffer(payload, np.uint8) if isinstance(payload, (bytes, bytearray)) else np.ascontiguousarray(payload, np.uint8)
+        n_bits = 8 * len(data) if n_bits is None else n_bits
+        if n_bits > 8 * len(data):
+            raise PcamvError("n_bits beyond the buffer")
+        self._msg_chk(self.lib.pcamv_gpu_batch_set_message(self.b, _p(data), n_bits, start_bit), "batch_set_message")
+
+    def message_tell(self):
+        """(the batch cursor: message bits handed out so far, start_bit included; bits of the attached message); synchronises"""
+        nxt, total = C.c_int64(), C.c_int64()
+        self.lib.pcamv_gpu_batch_message_tell.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        self._msg_chk(self.lib.pcamv_gpu_batch_message_tell(self.b, C.byref(nxt), C.byref(total)), "batch_message_tell")
+        return nxt.value, total.value
+
+    def rx_message_reserve(self, n_bits):
+        """room for n_bits of one received stream for the batch (0 releases it); while it exists every extract call writes into it"""
+        self.lib.pcamv_gpu_batch_rx_message_reserve.argtypes = [C.c_void_p, C.c_int64]
+        self._msg_chk(self.lib.pcamv_gpu_batch_rx_message_reserve(self.b, n_bits), "batch_rx_message_reserve")
+
+    def rx_message_reset(self):
+        self.lib.pcamv_gpu_batch_rx_message_reset.argtypes = [C.c_void_p]
+        self._msg_chk(self.lib.pcamv_gpu_batch_rx_message_reset(self.b), "batch_rx_message_reset")
+
+    def rx_message_tell(self):
+        """(received bits, reserved bits, valid_bits, first_bad = (call, slot, context) or (-1, -1, -1)); synchronises; raises once after
+        a frame ran past the reservation"""
+        got, cap, valid = C.c_int64(), C.c_int64(), C.c_int64()
+        bad = np.zeros(3, np.int64)
+        self.lib.pcamv_gpu_batch_rx_message_tell.argtypes = [C.c_void_p] * 5
+        self._msg_chk(self.lib.pcamv_gpu_batch_rx_message_tell(self.b, C.byref(got), C.byref(cap), C.byref(valid), _p(bad)), "batch_rx_message_tell")
+        return got.value, cap.value, valid.value, tuple(int(v) for v in bad)
+
+    def message_received(self, n_bits=None, packed=False):
+        """the batch's received stream so far (or its first n_bits): one bit per element, or the packed bytes"""
+        self.lib.pcamv_gpu_batch_rx_message_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+        if n_bits is None:
+            got, cap = self.rx_message_tell()[:2]
+            n_bits = min(got, cap)
+        out = np.zeros((n_bits + 7) // 8, np.uint8)
+        self._msg_chk(self.lib.pcamv_gpu_batch_rx_message_fetch(self.b, _p(out), n_bits), "batch_rx_message_fetch")
+        return out if packed else unpack_bits(out, n_bits)
+
+    def rx_message_guard_intact(self):
+        """(tests) are the guard words behind the batch's received stream untouched; synchronises"""
+        ok = C.c_int()
+        self._msg_chk(self.lib.pcamv_gpu_batch_debug_rx_message_guard(self.b, C.byref(ok)), "batch_debug_rx_message_guard")
+        return bool(ok.value)
+
+    def message_check(self):
+        """(bits in which the received stream differs from the attached message over what was received and reserved, zeros past the
+        message's end; received bits; valid_bits); synchronises"""
+        diff, got, valid = C.c_int64(), C.c_int64(), C.c_int64()
+        self.lib.pcamv_gpu_batch_message_check.argtypes = [C.c_void_p] * 4
+        self._msg_chk(self.lib.pcamv_gpu_batch_message_check(self.b, C.byref(diff), C.byref(got), C.byref(valid)), "batch_message_check")
+        return diff.value, got.value, valid.value
 
     def dominant_kernel(self):
         self.lib.pcamv_gpu_batch_dominant_kernel.restype = C.c_char_p
