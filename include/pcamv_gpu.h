@@ -132,14 +132,25 @@ int  pcamv_gpu_open(const pcamv_params_t *param, int device, pcamv_ctx_t **ctx);
 void pcamv_gpu_close(pcamv_ctx_t *ctx);
 const char *pcamv_gpu_last_error(const pcamv_ctx_t *ctx);
 
-/* Source picture, I420, caller-owned host planes. */
+/* What a context remembers between calls (tests/test_gpu_call_order.py):
+ *   - its QP is that of the last analysis or step (analyse_pframe, step_device, batch_step).  Pass 2, the loop filter and the slice
+ *     writers work at it.  The probes (block_costs, rd_probe) take a QP of their own and leave the context as they found it: whatever
+ *     runs after a probe computes what it would have computed without it;
+ *   - pass2_pframe takes the context's state as it is now: the records in the record buffer, the source and the reference planes the
+ *     context holds, the QP above.  It may take over the first pass' pixels of a macroblock whose motion did not change only while all
+ *     of that is what the first pass saw.  A new source (upload_fenc, set_fenc_device), a host set_ref, new records (embed_records)
+ *     and a step reported incomplete drop that reuse: every macroblock is then encoded again.  set_ref_device does not: its planes
+ *     are produced by the next step, and a pass 2 before that step still runs against the reference before. */
+
+/* Source picture, I420, caller-owned host planes.  A pass 2 that follows encodes every macroblock on it. */
 int pcamv_gpu_upload_fenc(pcamv_ctx_t *ctx, const uint8_t *const plane[3], const int stride[3]);
 
 /* Reconstructed reference picture (already deblocked by the caller), I420 host planes, plus
  * the previous frame's final motion field for the temporal candidates
  * (x264_mb_predict_mv_ref16x16, common/macroblock.c:444-467): prev_mv is [mb_h*4][mb_w*4][2]
  * quarter-pel, prev_ref is [mb_h*2][mb_w*2]; both NULL when the reference is an I frame.
- * Produces the padded full/H/V/HV luma planes and padded chroma on the device. */
+ * Produces the padded full/H/V/HV luma planes and padded chroma on the device, at once: a pass 2
+ * that follows runs against the new reference and encodes every macroblock again. */
 int pcamv_gpu_set_ref(pcamv_ctx_t *ctx, const uint8_t *const plane[3], const int stride[3],
                       const int16_t *prev_mv, const int8_t *prev_ref);
 
@@ -177,7 +188,12 @@ int pcamv_gpu_final_mvs(pcamv_ctx_t *ctx, pcamv_mb_t *out_mb);
  * device), P_SKIP macroblocks take the skip prediction from their final neighbours; out_final (optional)
  * receives the record with the final MVs, recon[3] the reconstruction before the loop filter, deblocked[3]
  * after it.  The deblocked picture stays in the context's reconstruction planes (the next reference) and the
- * final motion field is what PCAMV_PREV_FIELD_INTERNAL hands to the next frame.  One QP per frame (CQP). */
+ * final motion field is what PCAMV_PREV_FIELD_INTERNAL hands to the next frame.  One QP per frame (CQP): that of
+ * the last analysis or step, whatever QP a probe was given since.  The call takes the context's state as given --
+ * the records in the record buffer (an analysis', or embed_records'), the source and the reference planes the
+ * context holds now.  A macroblock whose motion did not change keeps the first pass' pixels only while all of that
+ * is what the first pass saw and no second pass has run over them; otherwise it is encoded again.  A context that
+ * has run no analysis or step has no QP, and nothing for this call to work on. */
 int pcamv_gpu_pass2_pframe(pcamv_ctx_t *ctx, const uint8_t *flips, int n_flips, pcamv_mb_t *out_final,
                            uint8_t *const recon[3], uint8_t *const deblocked[3]);
 
@@ -248,7 +264,10 @@ int pcamv_gpu_parse_slice_header(const uint8_t *rbsp, size_t len, int nal_header
                                  int32_t *slice_qp, int32_t *frame_num);
 
 /* Device-resident variants used by bench.py and the multi-frame pipeline: planes are raw
- * device pointers (hipMalloc / torch storage), tightly packed like recon[] above. */
+ * device pointers (hipMalloc / torch storage), tightly packed like recon[] above.
+ * set_ref_device takes effect with the plane production of the next step: a pass2_pframe before that step still
+ * runs against the reference before (the second pass reads the produced planes only), first-pass pixels included.
+ * set_fenc_device takes effect at once, like upload_fenc: a pass 2 that follows encodes every macroblock on it. */
 int pcamv_gpu_set_ref_device(pcamv_ctx_t *ctx, const void *y, const void *u, const void *v,
                              const void *prev_mv, const void *prev_ref);
 /* pass as prev_mv and prev_ref to chain frames on the device: the temporal candidates then come
@@ -303,7 +322,9 @@ int pcamv_gpu_kernel_time(pcamv_ctx_t *ctx, const char *kernel, double *avg_ms, 
 /* Pixel-metric probe for parity tests of the cost functions themselves (common/pixel.c SAD/SATD,
  * common/mc.c get_ref / mc_chroma): n requests {mb_x, mb_y, i_pixel, xoff, yoff, mvx, mvy (qpel),
  * satd}, each answered with {luma cost, U cost, V cost} of the uploaded fenc block against the
- * current reference at that MV (no MV-bit cost added). */
+ * current reference at that MV (no MV-bit cost added).  qp is the probe's own: the context keeps the QP of its
+ * last analysis or step, and pass 2, the embedding stage, the writers and the next analysis behave as if the probe
+ * had not happened (the context's table for qp is made on first use and kept). */
 int pcamv_gpu_block_costs(pcamv_ctx_t *ctx, int qp, int n, const int32_t *req, int32_t *out);
 
 /* Probe of the RD stage's metrics and intra predictors on caller-supplied pixels, for parity tests against reference-minted vectors
@@ -314,14 +335,16 @@ int pcamv_gpu_block_costs(pcamv_ctx_t *ctx, int qp, int n, const int32_t *req, i
  * left[3][16], int32 avail at byte 900 (bit 0 left, bit 1 top).  out: 32 int32 per request -- 0 ssd 16x16 + 2 x 8x8 of source vs
  * second block, 1 the same + the psy term (ssd_mb), 2 / 3 hadamard_ac 16x16 of the second block's luma (4x4 / 8x8 energies),
  * 4 / 5 fenc_satd_sum / fenc_sa8d_sum of the source, 6..9 intra 16x16 V, H, DC (variant by avail), P, 10..13 intra chroma DC
- * (variant), H, V, P over both planes, 14..25 the twelve 4x4 modes on block 0 (x264's I_PRED_4x4 order); unavailable = 1 << 28. */
+ * (variant), H, V, P over both planes, 14..25 the twelve 4x4 modes on block 0 (x264's I_PRED_4x4 order); unavailable = 1 << 28.
+ * Like pcamv_gpu_block_costs it leaves the context as it found it: qp, and the slice-start context states that go with it, are the probe's own. */
 int pcamv_gpu_rd_probe(pcamv_ctx_t *ctx, int qp, int n, const uint8_t *req, int32_t *out);
 
 /* Probe of the embedding stage on a caller's records, for parity tests of the cover / cost assembly and the syndrome-trellis kernels
  * at inputs no analysis produces: mbs[mb_count] is copied into the context's record buffer, then the stage runs exactly as
  * pcamv_gpu_embed_pframe runs it (same kernels and outputs; the rand() stream, the payload cursor and the column generator move the
  * same way).  Afterwards the context stands as after an analysis that produced those records: pcamv_gpu_final_mvs,
- * pcamv_gpu_batch_extract_step and the slice writers' final motion see them and the new flip map.  Synchronises. */
+ * pcamv_gpu_batch_extract_step and the slice writers' final motion see them and the new flip map; pcamv_gpu_pass2_pframe encodes
+ * every macroblock of them (the reconstruction planes hold no first pass of these records).  Synchronises. */
 int pcamv_gpu_embed_records(pcamv_ctx_t *ctx, const pcamv_mb_t *mbs, float emrate,
                             const uint8_t *message, int message_len, pcamv_embed_t *out);
 

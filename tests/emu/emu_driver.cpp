@@ -72,6 +72,22 @@ extern "C" int emu_analyse_pframe(const pcamv_params_t *p, int qp, int embed,
     return 0;
 }
 
+/* The per-QP tables the library uploads (ensure_qp_tables, pcamv_gpu.hip), as pcamv_host_tables.h builds them, for
+ * tests/test_host_tables.py: the MV bit costs (PCAMV_COST_MV_LEN entries) and the slice-start context states (460 + 4 bytes). */
+extern "C" int emu_cost_mv_len(void) { return PCAMV_COST_MV_LEN; }
+extern "C" int emu_build_cost_mv(int qp, int16_t *out)
+{
+    if (qp < 0 || qp > 51 || !out) return -1;
+    pcamv_build_cost_mv(qp, out);
+    return 0;
+}
+extern "C" int emu_build_cabac_init(int qp, uint8_t *out /* [464] */)
+{
+    if (qp < 0 || qp > 51 || !out) return -1;
+    pcamv_build_cabac_init(qp, out);
+    return 0;
+}
+
 extern "C" void emu_get_stats(long long *out, int reset) { for (int i = 0; i < 32; i++) { out[i] = emu_stats[i]; if (reset) emu_stats[i] = 0; } }
 
 /* The strip layout of the device's luma planes (pcamv_common.h): the host-side statement of its address arithmetic, for

@@ -623,7 +623,8 @@ extern "C" void pcamv_gpu_close(pcamv_ctx_t *c)
     delete c;
 }
 
-static int ensure_qp(pcamv_ctx *c, int qp)
+/* the per-QP tables of a context (MV bit costs; --subme >= 6: the context states at the slice start), made on first use and kept */
+static int ensure_qp_tables(pcamv_ctx *c, int qp)
 {
     if (qp < 0 || qp > 51) return fail(c, PCAMV_EINVAL, "qp %d out of range", qp);
     if (!c->d_cost_mv[qp]) {
@@ -633,19 +634,44 @@ static int ensure_qp(pcamv_ctx *c, int qp)
         TRY(ctx_alloc(c, &c->d_cost_mv[qp], (size_t)PCAMV_COST_MV_LEN + 1));      /* + 1: prim_mv_cost fetches the dword that holds an entry */
         HIPCHK(c, hipMemcpy(c->d_cost_mv[qp], h, PCAMV_COST_MV_LEN * sizeof(int16_t), hipMemcpyHostToDevice));
     }
-    pcamv_frame_set_qp(&c->F, &c->p, qp);
-    c->F.cost_mv = c->d_cost_mv[qp] + PCAMV_COST_MV_CENTRE;
-    if (c->F.b_mbrd) {          /* context states at the slice start for this QP (x264_cabac_context_init, encoder.c:1227) */
-        if (!c->d_cabac_init[qp]) {
-            uint8_t init[PCAMV_CHAIN_BYTES] = {0};       /* states, then nothing left over from an earlier macroblock */
-            pcamv_build_cabac_init(qp, init);
-            TRY(ctx_alloc(c, &c->d_cabac_init[qp], (size_t)PCAMV_CHAIN_BYTES));
-            HIPCHK(c, hipMemcpy(c->d_cabac_init[qp], init, PCAMV_CHAIN_BYTES, hipMemcpyHostToDevice));
-        }
-        c->F.cabac_init = c->d_cabac_init[qp];
+    if (c->F.b_mbrd && !c->d_cabac_init[qp]) {       /* context states at the slice start for this QP (x264_cabac_context_init, encoder.c:1227) */
+        uint8_t init[PCAMV_CHAIN_BYTES] = {0};       /* states, then nothing left over from an earlier macroblock */
+        pcamv_build_cabac_init(qp, init);
+        TRY(ctx_alloc(c, &c->d_cabac_init[qp], (size_t)PCAMV_CHAIN_BYTES));
+        HIPCHK(c, hipMemcpy(c->d_cabac_init[qp], init, PCAMV_CHAIN_BYTES, hipMemcpyHostToDevice));
     }
     return 0;
 }
+/* the QP-dependent part of a frame descriptor of context c, from the context's tables for that QP: of the context's own descriptor for
+ * an analysis or a step (ensure_qp), of a probe's private copy for a probe (probe_frame) */
+static void frame_use_qp(const pcamv_ctx *c, FrameDev *F, int qp)
+{
+    pcamv_frame_set_qp(F, &c->p, qp);
+    F->cost_mv = c->d_cost_mv[qp] + PCAMV_COST_MV_CENTRE;
+    if (F->b_mbrd) F->cabac_init = c->d_cabac_init[qp];
+}
+/* an analysis or a step at this QP: it becomes the context's, the one pass 2, the loop filter and the writers work at until the next */
+static int ensure_qp(pcamv_ctx *c, int qp)
+{
+    TRY(ensure_qp_tables(c, qp));
+    frame_use_qp(c, &c->F, qp);
+    return 0;
+}
+/* The frame descriptor of a probe (block_costs, rd_probe): a copy of the context's with the probe's QP, on the device for the probe's
+ * one launch.  The context keeps its own QP, so whatever runs on it after the probe computes what it would have without it. */
+static int probe_frame(pcamv_ctx *c, int qp, DevTmp<FrameDev> &d_F)
+{
+    TRY(ensure_qp_tables(c, qp));
+    HIPCHK(c, d_F.alloc(1));
+    FrameDev hF = c->F; hF.self = d_F;
+    frame_use_qp(c, &hF, qp);
+    HIPCHK(c, hipMemcpy(d_F, &hF, sizeof(FrameDev), hipMemcpyHostToDevice));
+    return 0;
+}
+/* The second pass may take the first pass' pixels and non-zero flags for a macroblock whose motion did not change (mbk_pass2) only while
+ * records, source, reference planes and quantiser are what the first pass saw: whatever replaces one of them between an analysis and
+ * pcamv_gpu_pass2_pframe calls this, and so does a step found incomplete. */
+static void drop_rec_reuse(pcamv_ctx *c) { c->rec_pristine = 0; }
 /* diagnostics (parity tests): FNV-1a of the 460 CABAC context states after every macroblock of the following analyses */
 extern "C" int pcamv_gpu_debug_state_hash(pcamv_ctx_t *c, int enable)
 {
@@ -673,12 +699,14 @@ extern "C" int pcamv_gpu_upload_fenc(pcamv_ctx_t *c, const uint8_t *const plane[
         HIPCHK(c, hipMemcpy2D(c->d_fenc[i], w, plane[i], stride[i], w, h, hipMemcpyHostToDevice));   /* caller memory is pageable: blocking copy */
         c->F.fenc[i] = c->d_fenc[i];
     }
+    drop_rec_reuse(c);          /* a new source: a second pass re-encodes every macroblock on it */
     return 0;
 }
 extern "C" int pcamv_gpu_set_fenc_device(pcamv_ctx_t *c, const void *y, const void *u, const void *v)
 {
     if (!c || !y || !u || !v) return PCAMV_EINVAL;
     c->F.fenc[0] = (const uint8_t *)y; c->F.fenc[1] = (const uint8_t *)u; c->F.fenc[2] = (const uint8_t *)v;
+    drop_rec_reuse(c);
     return 0;
 }
 
@@ -872,6 +900,7 @@ static int flow_check(pcamv_batch *b)
     HIPCHK(b, hipMemcpy(&bad, b->fl.ctr + FLOW_ERR, sizeof(bad), hipMemcpyDeviceToHost));
     if (bad) {
         hipMemset(b->fl.ctr + FLOW_ERR, 0, sizeof(unsigned));
+        for (int i = 0; i < b->n; i++) if (b->ctx[i]) drop_rec_reuse(b->ctx[i]);      /* no first pass' reconstruction to speak of */
         return fail(b, PCAMV_EHIP, "dataflow kernel: queue wait timed out (results of the last step are incomplete)");
     }
     return 0;
@@ -896,10 +925,14 @@ extern "C" int pcamv_gpu_set_ref(pcamv_ctx_t *c, const uint8_t *const plane[3], 
         HIPCHK(c, hipMemcpy(c->d_prev_mv, prev_mv, (size_t)c->F.n_mb * 64, hipMemcpyHostToDevice));
         HIPCHK(c, hipMemcpy(c->d_prev_ref, prev_ref, (size_t)c->F.n_mb * 4, hipMemcpyHostToDevice));
     }
+    drop_rec_reuse(c);          /* the planes below are the new reference's at once: a second pass re-encodes every macroblock against them */
     TRY(ctx_launch(c, ST_PLANES));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
+/* (The planes the analysis and the second pass read -- luma_base, chroma_base -- are made from these by the next step's plane production;
+ * F.raw is read by k_hpel / k_chroma_pad alone.  Until that step a second pass runs against the planes of the reference before, and what
+ * the first pass left of it stays valid.) */
 extern "C" int pcamv_gpu_set_ref_device(pcamv_ctx_t *c, const void *y, const void *u, const void *v, const void *prev_mv, const void *prev_ref)
 {
     if (!c || !y || !u || !v) return PCAMV_EINVAL;
@@ -1016,6 +1049,7 @@ extern "C" int pcamv_gpu_embed_records(pcamv_ctx_t *c, const pcamv_mb_t *mbs, fl
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipDeviceSynchronize());          /* work in flight (a receiver's launch on another stream) may still read the records */
     HIPCHK(c, hipMemcpy(c->F.rec_mb, mbs, (size_t)c->F.n_mb * sizeof(pcamv_mb_t), hipMemcpyHostToDevice));
+    drop_rec_reuse(c);          /* the reconstruction planes hold no first pass of THESE records */
     return embed_stage(c, emrate, message, message_len, out);
 }
 
@@ -3115,12 +3149,10 @@ extern "C" int pcamv_gpu_block_costs(pcamv_ctx_t *c, int qp, int n, const int32_
         if (r[3] < 0 || r[4] < 0 || r[3] + bw[r[2]] > 16 || r[4] + bh[r[2]] > 16) return fail(c, PCAMV_EINVAL, "request %d: block outside its macroblock", i);
         if (px < -28 || py < -28 || px + bw[r[2]] > c->F.w + 24 || py + bh[r[2]] > c->F.h + 24) return fail(c, PCAMV_EINVAL, "request %d leaves the padded plane", i);
     }
-    TRY(ensure_qp(c, qp));
     DevTmp<int> d_req, d_out; DevTmp<FrameDev> d_F;
-    HIPCHK(c, d_req.alloc((size_t)n * 8)); HIPCHK(c, d_out.alloc((size_t)n * 3)); HIPCHK(c, d_F.alloc(1));
+    TRY(probe_frame(c, qp, d_F));
+    HIPCHK(c, d_req.alloc((size_t)n * 8)); HIPCHK(c, d_out.alloc((size_t)n * 3));
     HIPCHK(c, hipMemcpy(d_req, req, (size_t)n * 8 * sizeof(int), hipMemcpyHostToDevice));
-    FrameDev hF = c->F; hF.self = d_F;
-    HIPCHK(c, hipMemcpy(d_F, &hF, sizeof(FrameDev), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_block_costs, dim3(n), dim3(64), 0, c->stream, (const FrameDev *)d_F, (const int *)d_req, (int *)d_out);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(out, d_out, (size_t)n * 3 * sizeof(int), hipMemcpyDeviceToHost));
@@ -3131,12 +3163,10 @@ extern "C" int pcamv_gpu_rd_probe(pcamv_ctx_t *c, int qp, int n, const uint8_t *
 {
     if (!c || !req || !out || n <= 0) return PCAMV_EINVAL;
     HIPCHK(c, hipSetDevice(c->device));
-    TRY(ensure_qp(c, qp));
     DevTmp<uint8_t> d_req; DevTmp<int> d_out; DevTmp<FrameDev> d_F;
-    HIPCHK(c, d_req.alloc((size_t)n * 1024)); HIPCHK(c, d_out.alloc((size_t)n * 32)); HIPCHK(c, d_F.alloc(1));
+    TRY(probe_frame(c, qp, d_F));
+    HIPCHK(c, d_req.alloc((size_t)n * 1024)); HIPCHK(c, d_out.alloc((size_t)n * 32));
     HIPCHK(c, hipMemcpy(d_req, req, (size_t)n * 1024, hipMemcpyHostToDevice));
-    FrameDev hF = c->F; hF.self = d_F;
-    HIPCHK(c, hipMemcpy(d_F, &hF, sizeof(FrameDev), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_rd_probe, dim3(n), dim3(64), 0, c->stream, (const FrameDev *)d_F, (const uint8_t *)d_req, (int *)d_out);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(out, d_out, (size_t)n * 32 * sizeof(int), hipMemcpyDeviceToHost));
