@@ -140,7 +140,10 @@ const char *pcamv_gpu_last_error(const pcamv_ctx_t *ctx);
  *     context holds, the QP above.  It may take over the first pass' pixels of a macroblock whose motion did not change only while all
  *     of that is what the first pass saw.  A new source (upload_fenc, set_fenc_device), a host set_ref, new records (embed_records)
  *     and a step reported incomplete drop that reuse: every macroblock is then encoded again.  set_ref_device does not: its planes
- *     are produced by the next step, and a pass 2 before that step still runs against the reference before. */
+ *     are produced by the next step, and a pass 2 before that step still runs against the reference before;
+ *   - encode_idr and write_stream_idr leave a context as a host set_ref with no previous motion leaves it: the reconstruction of the IDR
+ *     picture is the reference at once, its planes produced, the reuse of first-pass pixels dropped.  They take a QP of their own and
+ *     leave the context's: pass2_pframe and the writers behind them behave as behind that set_ref. */
 
 /* Source picture, I420, caller-owned host planes.  A pass 2 that follows encodes every macroblock on it. */
 int pcamv_gpu_upload_fenc(pcamv_ctx_t *ctx, const uint8_t *const plane[3], const int stride[3]);
@@ -372,6 +375,7 @@ int pcamv_gpu_abi_version(void);
 #define PCAMV_FEATURE_PARAM_SETS 0x200u        /* SPS / PPS read on the device, per stream: the *_param_sets and *_sets calls at the end of this file */
 #define PCAMV_FEATURE_VIDEO 0x400u      /* one video of many chains: per-chain heads, streams joined, a video cut at its IDR units on the device */
 #define PCAMV_FEATURE_MESSAGE 0x800u    /* one message for a batch, split over its contexts' frames on the device (behind the payload path below) */
+#define PCAMV_FEATURE_IDR 0x1000u       /* the IDR picture a chain starts with coded on the device (the last section of this file) */
 unsigned pcamv_gpu_features(void);
 
 /* ---- Payload path: the caller's bits through the device-resident entry points, and back out on the device ----
@@ -658,8 +662,8 @@ int pcamv_gpu_slice_headers_device(pcamv_ctx_t *ctx, const uint8_t *bytes, size_
  * (or no header) the output is the bare slice data.  As a NAL unit: long start code, the header byte from nal_ref_idc and
  * nal_unit_type, the RBSP with emulation prevention as x264_nal_encode inserts it.  i_frame chooses the bit x264_cabac_encode_flush
  * takes from the frame counter (0x35a4e4f5 >> (i_frame & 31) & 1).
- * Contexts opened with b_cabac == 0 are refused with PCAMV_EUNSUP (they go through the *_cavlc calls below).  I frames and several slices
- * per picture stay the host's (SPS and PPS: pcamv_gpu_param_set_head, the last section of this file); so does the slice header in these calls -- the stream calls at the end of this file make
+ * Contexts opened with b_cabac == 0 are refused with PCAMV_EUNSUP (they go through the *_cavlc calls below).  Several slices
+ * per picture stay the host's (a chain's IDR picture: the last section of this file) (SPS and PPS: pcamv_gpu_param_set_head, the last section of this file); so does the slice header in these calls -- the stream calls at the end of this file make
  * it on the device. */
 typedef struct pcamv_slice_hdr_t { const uint8_t *bits; int32_t n_bits; int32_t i_frame; int32_t nal_ref_idc; int32_t nal_unit_type; } pcamv_slice_hdr_t;
 /* The parity probe; synchronises.  mbs == NULL: the context's last frame -- final == 0 the first-pass records as they are, final != 0
@@ -702,8 +706,8 @@ int pcamv_gpu_rbsp_to_nal(const uint8_t *rbsp, size_t len, int nal_ref_idc, int 
  * and the parameter sets.  Closed-loop contexts run step -> write_stream_step N times, then index_streams_device -> extract_stream_step
  * N times on the same (bytes, off, len): nothing per frame passes through the host on either side, and the bytes in between are a
  * well-formed Annex B stream.  SPS and PPS are written by pcamv_gpu_param_set_head and read by the *_param_sets calls (the last section of
- * this file).  Out of scope, the caller's as before: I frames (they go into the stream's `head`, opaque here, behind the parameter
- * sets), several slices per picture.
+ * this file).  A chain's IDR picture is written by pcamv_gpu_batch_write_stream_idr (the last section of this file), or stays the caller's
+ * and goes into the stream's `head`, opaque here, behind the parameter sets.  Out of scope: several slices per picture.
  *
  * write_slice_header: host code, no GPU; the semantics of the device's header writer on every input (csrc/pcamv_stream_write.h), and the
  * inverse of pcamv_gpu_parse_slice_header.  slice_header() (7.3.3) of a P slice for `params`, element by element as
@@ -776,7 +780,7 @@ int pcamv_gpu_slice_headers_write_device(pcamv_ctx_t *ctx, const pcamv_stream_pa
  * byte streams and nothing else: the units of nal_unit_type 7 and 8 of every context's stream are found, unescaped, parsed and resolved
  * on the device into one table per context, and the *_sets calls read each slice header under the entry its pps_id names.  The
  * contexts of a batch may come from different encoder configurations.  As everywhere here the host functions are the definition on
- * every input, valid or not.  Still the caller's: I frames, several slices per picture, parameter sets that change within a stream.
+ * every input, valid or not.  Still the caller's: several slices per picture, parameter sets that change within a stream.
  *
  * parse_sps reads seq_parameter_set_data() (7.3.2.1) of rbsp[0, len) -- the unit behind its header byte, unescaped -- in syntax order:
  * profile_idc, the constraint byte, level_idc, sps_id; for profiles 100, 110, 122, 244, 44, 83, 86, 118, 128 chroma_format_idc, the two
@@ -942,6 +946,64 @@ int pcamv_gpu_batch_index_video(pcamv_batch_t *batch, const uint8_t *bytes, size
                                 int64_t *preamble, int64_t *n_slices_out, void *stream);
 int pcamv_gpu_video_gops_device(pcamv_ctx_t *ctx, const uint8_t *bytes, size_t bytes_size, const int64_t *off, const int64_t *len, int n,
                                 pcamv_gop_t *gops_out, int64_t cap_per_video, int64_t *n_gops, int64_t *preamble);
+
+/* ---- IDR pictures coded on the device: the picture every chain starts with (PCAMV_FEATURE_IDR) ----
+ *
+ * The calls above predict a chain's first P picture from a reference the caller brought.  With these the library makes that picture
+ * itself: a context's source coded as one IDR I slice on the device, its reconstruction installed as the context's reference, its unit
+ * put into the context's stream.  Scope, fixed: one slice per picture, Intra16x16 macroblocks only -- luma vertical / horizontal / DC /
+ * plane and the four chroma modes, chosen per macroblock by SATD among the modes whose neighbours exist -- one QP (mb_qp_delta 0), the
+ * intra dead zone i_luma_deadzone[1] and the context's i_chroma_qp_offset, CAVLC slice data whatever the context's b_cabac (an IDR slice
+ * names a PPS of its own: a CABAC stream carries a second PPS with entropy_coding_mode_flag 0, which is legal), no loop filter
+ * (disable_deblocking_filter_idc 1, so that PPS needs deblocking control).  Every quantised level is clamped to +-2063, the largest
+ * magnitude level_prefix 15 expresses at every suffix length, before the reconstruction (csrc/pcamv_idr.h derives it).  NOT the
+ * reference's I-frame coder, and not bit-equal with it: an I picture carries no payload, and exact here means that a decoder
+ * reconstructs precisely the planes the chain predicts from.
+ *
+ * write_idr_slice_header / parse_idr_slice_header: host code, no GPU; the definition on every input.  slice_header() (7.3.3) of an IDR I
+ * slice: first_mb_in_slice 0, slice_type 7, pps_id, frame_num 0, idr_pic_id, the POC elements of the POC type (all zero),
+ * redundant_pic_cnt 0 if present, no_output_of_prior_pics_flag 0, long_term_reference_flag 0, slice_qp_delta,
+ * disable_deblocking_filter_idc 1.  The writer refuses before anything is written: PCAMV_EINVAL for params outside their ranges,
+ * nal_ref_idc outside 1 .. 3, idr_pic_id outside 0 .. 65535, slice_qp outside 0 .. 51; then PCAMV_EUNSUP for weighted_pred, entropy_cabac
+ * and a PPS without deblocking control; PCAMV_ENOMEM for cap too small.  bits / n_bits as pcamv_gpu_write_slice_header gives them.
+ * The parser reads rbsp[0, len) (the unit behind its header byte, unescaped) under the rules of pcamv_gpu_parse_slice_header -- a read
+ * failure is PCAMV_EINVAL and found before the element is judged: nal_unit_type != 5, first_mb_in_slice != 0, slice_type not 2 or 7, another
+ * pps_id: PCAMV_EUNSUP; frame_num != 0 or idr_pic_id above 65535: PCAMV_EINVAL; long_term_reference_flag 1, entropy_cabac, no deblocking
+ * control or an idc of 0 or 2: PCAMV_EUNSUP; a QP outside 0 .. 51 or an idc above 2: PCAMV_EINVAL.  All three outputs are -1 on failure.
+ *
+ * decode_islice_cavlc: host code, no GPU.  An independent decoder of exactly this subset -- Intra16x16, CAVLC, one QP, no filter -- from
+ * bit start_bit of the RBSP; y / u / v receive the planes tightly packed (16 mb_w x 16 mb_h, half that twice).  PCAMV_EUNSUP for any other
+ * macroblock type or a non-zero mb_qp_delta, PCAMV_EINVAL for bad data (a read past the end, a code no table holds, a level_prefix above
+ * 15, a mode whose neighbours are missing, coefficients past a block's end, anything but rbsp_trailing_bits behind the last macroblock).
+ * With the device coder it shares the code tables and nothing else: it is what the tests hold the device to, and what a user calls to see
+ * the picture.
+ *
+ * encode_idr: the probe; synchronises.  The context's current source at `qp` as one IDR slice: out[cap] receives *len bytes, the RBSP or
+ * (as_nal) the unit with long start code, header byte 0x65 and emulation prevention; the header is write_idr_slice_header's for
+ * pcamv_stream_params_t {4, 0, 4, 0, 0, 0, 1, 0, 0, 26, 1, pps_id} and nal_ref_idc 3.  The unfiltered reconstruction is installed as the
+ * context's reference, as a host set_ref with no previous motion installs one (the rule under "what a context remembers"), and is
+ * readable through fetch_recon / recon_device / get_ref_planes.  A unit that does not fit is PCAMV_ENOMEM; the reference is installed all
+ * the same.  idr_bound: a capacity that always fits.
+ *
+ * write_stream_idr: behind stream_open / stream_open_heads and before the first write_stream_step since that open, else PCAMV_EINVAL; the
+ * open must have first_pic 0, else PCAMV_EINVAL; the stream's PPS must have deblocking control, else PCAMV_EUNSUP; all before anything is
+ * queued.  Every context's source becomes picture 0 of its stream, [09 10 delimiter +] IDR unit of the stream's nal_ref_idc behind the
+ * head (which now holds parameter sets only), under the stream's parameter sets with pps_id as given and entropy_cabac 0; every context
+ * gets its reference; the picture counter moves to 1, so the first P picture has frame_num 1 and poc_lsb 2 by the rule of
+ * pcamv_stream_write_t.  No host synchronisation.  pcamv_gpu_batch_write_status reports 0 / PCAMV_ENOMEM (stream and len[i] unchanged) /
+ * PCAMV_EINVAL as for a step; a picture that did not fit still installs the reference and moves the counter, as a P picture does.
+ * Kernels (pcamv_gpu_batch_kernel_time knows them by name): k_idr_mb, one wavefront per macroblock, one launch per anti-diagonal x + y;
+ * k_idr_prefix; k_idr_pack, one lane per dword of the RBSP; k_idr_unit, one wavefront per context; k_stream_commit.  The working memory
+ * is the batch's, made at first use and released with it: 2842 bytes per macroblock and place, at most 8 GiB; larger batches run their
+ * contexts in groups inside the call. */
+int pcamv_gpu_write_idr_slice_header(const pcamv_stream_params_t *params, int nal_ref_idc, int idr_pic_id, int slice_qp, uint8_t *bits, size_t cap, int32_t *n_bits);
+int pcamv_gpu_parse_idr_slice_header(const uint8_t *rbsp, size_t len, int nal_header, const pcamv_stream_params_t *params, int64_t *start_bit,
+                                     int32_t *slice_qp, int32_t *idr_pic_id);
+int pcamv_gpu_decode_islice_cavlc(const uint8_t *rbsp, size_t len, size_t start_bit, int mb_w, int mb_h, int slice_qp, int chroma_qp_index_offset,
+                                  uint8_t *y, uint8_t *u, uint8_t *v);
+int pcamv_gpu_encode_idr(pcamv_ctx_t *ctx, int qp, int pps_id, int idr_pic_id, int as_nal, uint8_t *out, size_t cap, size_t *len);
+int64_t pcamv_gpu_idr_bound(const pcamv_ctx_t *ctx, int as_nal);
+int pcamv_gpu_batch_write_stream_idr(pcamv_batch_t *batch, int qp, int pps_id, int idr_pic_id, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,107 @@
+"""Timing of the IDR pictures coded on the device: the payload tool's workload (1080p, --me umh --subme 7, CABAC, closed
+loop, 256 chains).  In one run: Batch.write_stream_idr of every chain's first picture -- wall clock, and each of its kernels through
+kernel_time -- next to one closed-loop P step of the same batch, and the bytes of an IDR picture next to a P picture's.  Prints one JSON
+line and writes it to profiles/idr_timing.json.  Needs a GPU.
+
+    python tools/idr_timing.py [--gops 256] [--steps 3] [--warmup 1] [--reps 3] [--out FILE]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "video-steganography-pcamv_amd")]
+KERNELS = ("k_idr_mb", "k_idr_prefix", "k_idr_pack", "k_idr_unit", "k_stream_commit")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gops", type=int, default=256)
+    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--qp", type=int, default=26)
+    ap.add_argument("--emrate", type=float, default=0.5)
+    ap.add_argument("--region", type=int, default=6 << 20, help="bytes of a chain's stream")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "idr_timing.json"))
+    args = ap.parse_args()
+    import numpy as np
+    import torch
+    import pcamv_amd
+    from pcamv_amd.synth import make_clip
+    import bench
+    if not torch.cuda.is_available():
+        sys.exit("idr_timing.py needs a GPU: the HIP path has no CPU fallback")
+    dev = torch.device("cuda", 0)
+    W, H = 1920, 1088
+    p = pcamv_amd.param_default(W, H)
+    pcamv_amd.param_parse(p, "me", "umh")
+    pcamv_amd.param_parse(p, "subme", 7)
+    clip = make_clip(W, H, 9, seed=13)
+    dframes = [[torch.from_numpy(pl).to(dev) for pl in fr] for fr in clip]
+    n = args.gops
+    run = bench.Gops(pcamv_amd, p, dframes, list(range(n)), 0, True)
+    sp = pcamv_amd.StreamParams(log2_max_frame_num=5, poc_type=0, log2_max_poc_lsb=7, entropy_cabac=1, deblocking_filter_control_present=1, pic_init_qp=26, pps_id=0)
+    head, _ = pcamv_amd.param_set_head_idr(sp, W // 16, H // 16, idr_pps_id=1)
+    wr = pcamv_amd.StreamWrite(nal_ref_idc=2, slice_type=5, first_pic=0, first_i_frame=0, disable_deblocking_filter_idc=-1, aud=1)
+    data = torch.zeros(n * args.region, dtype=torch.uint8, device=dev)
+    off = torch.arange(n, dtype=torch.int64, device=dev) * args.region
+    cap = torch.full((n,), args.region, dtype=torch.int64, device=dev)
+    length = torch.zeros(n, dtype=torch.int64, device=dev)
+    stream = torch.cuda.Stream(device=dev)
+    for k, enc in enumerate(run.encs):
+        enc.set_fenc_device(*[pl.data_ptr() for pl in dframes[bench.tri(run.phases[k], len(dframes))]])
+    out = dict(gops=n, width=W, height=H, qp=args.qp, emrate=args.emrate, reps=args.reps, steps=args.steps)
+    wall = []
+    for rep in range(args.reps + 1):            # the first call makes the working memory and is not counted
+        torch.cuda.synchronize()
+        run.batch.stream_open(data, off, cap, length, sp, wr, head=head, stream=stream.cuda_stream)
+        torch.cuda.synchronize()
+        if rep == 1:
+            for name in KERNELS:
+                run.batch.kernel_time(name, reset=True)
+        w0 = time.perf_counter()
+        run.batch.write_stream_idr(args.qp, pps_id=1, idr_pic_id=rep, stream=stream.cuda_stream)
+        torch.cuda.synchronize()
+        if rep:
+            wall.append((time.perf_counter() - w0) * 1e3)
+    status = run.batch.write_status()
+    out["idr_status_nonzero"] = int((status != 0).sum())
+    out["write_stream_idr_wall_ms"] = wall
+    for name in KERNELS:
+        ms, launches = run.batch.kernel_time(name, reset=True)
+        out[name + "_ms_per_call"] = ms * launches / max(args.reps, 1)
+        out[name + "_timed_spans_per_call"] = launches / max(args.reps, 1)
+    idr_bytes = (length.cpu().numpy() - len(head) - 6).astype(np.int64)
+    out["idr_unit_bytes"] = dict(min=int(idr_bytes.min()), mean=float(idr_bytes.mean()), max=int(idr_bytes.max()))
+    out["diagonals"] = W // 16 + H // 16 - 1
+
+    def loop(t0, steps, write):
+        torch.cuda.synchronize()
+        w0 = time.perf_counter()
+        for t in range(t0, t0 + steps):
+            run.step(t, args.qp, args.emrate, stream.cuda_stream)
+            if write:
+                run.batch.write_stream_step(stream.cuda_stream)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - w0) * 1e3 / steps
+
+    loop(0, args.warmup, False)
+    out["p_step_ms"] = loop(args.warmup, args.steps, False)
+    before = length.cpu().numpy().copy()
+    out["p_step_with_write_ms"] = loop(args.warmup + args.steps, 1, True)
+    p_bytes = (length.cpu().numpy() - before - 6).astype(np.int64)
+    out["p_write_status_nonzero"] = int((run.batch.write_status() != 0).sum())
+    out["p_unit_bytes"] = dict(min=int(p_bytes.min()), mean=float(p_bytes.mean()), max=int(p_bytes.max()))
+    out["idr_over_p_step"] = float(np.median(wall)) / out["p_step_ms"]
+    line = json.dumps(dict(mode="idr", tool="idr_timing.py", **out))
+    print(line)
+    with open(args.out, "w") as f:
+        f.write(line + "\n")
+    run.leave_to_exit()
+
+
+if __name__ == "__main__":
+    main()

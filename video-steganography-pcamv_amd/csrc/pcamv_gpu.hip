@@ -20,6 +20,7 @@
 #include "pcamv_mvsyntax.h"
 #include "pcamv_param_sets_host.h"
 #include "pcamv_rd_select.h"
+#include "pcamv_idr_defs.h"
 
 #define PCAMV_ABI_VERSION 3
 #define NEV 32                 /* launches the analysis kernel's timer remembers between two kernel_time calls ... */
@@ -30,10 +31,11 @@ enum { KT_ANALYSE, KT_EMBED_PREPARE, KT_EXTRACT_PREPARE, KT_EXTRACT_BITS, KT_PAY
        KT_STREAM_OPEN, KT_STREAM_SLOT, KT_STREAM_COMMIT, KT_STREAM_WINDOW_UNIT, KT_EXTRACT_COUNT, KT_EXTRACT_CHAIN,
        KT_PSET_UNIT, KT_PSET_PARSE, KT_PSET_RESOLVE, KT_SLICE_HEADER_SETS,
        KT_STREAM_OPEN_HEADS, KT_STREAM_JOIN, KT_STREAM_COPY_PLAN, KT_STREAM_COPY, KT_VIDEO_CUT,
-       KT_MESSAGE_COUNT, KT_MESSAGE_PLAN, KT_MESSAGE_JOBS, KT_EXTRACT_CHAIN_MESSAGE, KT_MESSAGE_CHECK, KT_N };
+       KT_MESSAGE_COUNT, KT_MESSAGE_PLAN, KT_MESSAGE_JOBS, KT_EXTRACT_CHAIN_MESSAGE, KT_MESSAGE_CHECK,
+       KT_IDR_MB, KT_IDR_PREFIX, KT_IDR_PACK, KT_IDR_UNIT, KT_N };
 #define PCAMV_FEATURES (PCAMV_FEATURE_PAYLOAD | PCAMV_FEATURE_SLICE_PARSER | PCAMV_FEATURE_SLICE_PARSER_CAVLC | PCAMV_FEATURE_SLICE_WRITER | \
                         PCAMV_FEATURE_SLICE_WRITER_CAVLC | PCAMV_FEATURE_NAL_DEVICE | PCAMV_FEATURE_STREAM_DEVICE | PCAMV_FEATURE_STREAM_WRITER | \
-                        PCAMV_FEATURE_STREAM_WINDOW | PCAMV_FEATURE_PARAM_SETS | PCAMV_FEATURE_VIDEO | PCAMV_FEATURE_MESSAGE)
+                        PCAMV_FEATURE_STREAM_WINDOW | PCAMV_FEATURE_PARAM_SETS | PCAMV_FEATURE_VIDEO | PCAMV_FEATURE_MESSAGE | PCAMV_FEATURE_IDR)
 #define MSG_GUARD_WORDS 4       /* words behind a batch's received stream that nothing may write */
 #define SLICE_GUARD_MBS 4       /* records behind a context's receive-side records that nothing may write (pcamv_gpu_debug_slice_records) */
 #define NSTAGE 2                /* staging buffers of extract_slices: a call waits for the one before the last */
@@ -105,6 +107,7 @@ struct StreamOut {
     uint8_t *d_head; size_t cap_head;
     uint8_t *d_copy; size_t cap_copy;   /* the copy launches of stream_open_heads and join_streams: [VcJob n][chunk_base n + 1][head_off n][head_len n][join status] */
     int joined;                         /* a join was queued since the open: its status is there to be read */
+    int stepped;                        /* a write_stream_step or a write_stream_idr was queued since the open: an IDR picture no longer belongs here */
 };
 
 /* the slots of a window of slice units per context (pcamv_gpu_batch_stream_window): per context x slot what a step keeps per context --
@@ -169,6 +172,10 @@ struct pcamv_batch {
     const uint8_t *d_msg; long long msg_bits; uint8_t *d_msg_own; size_t msg_own_bytes;
     long long *d_mtx; int *d_mtx_m; long long *d_mtx_at;
     unsigned *d_mrx; long long mrx_bits; long long *d_mrx_state; int *d_mrx_job; long long *d_mrx_at, *d_mchk;
+    /* IDR pictures coded on the device (pcamv_idr.hip): the working memory of a group of `group` contexts in one block -- per place the
+     * counts, the bit-string slots, the bit counts, the prefix and the RBSP --, per context a failure word, the slot's code and the probe's
+     * {off, cap, len}, and the code tables */
+    uint8_t *d_idr; size_t cap_idr; int idr_group; uint8_t *d_idr_ctx; uint8_t *d_idr_tab;
     KTimer kt[KT_N];            /* the timed kernels; the events of a timer are made by its first launch */
     char err[256];
 };
@@ -360,6 +367,7 @@ extern "C" void pcamv_gpu_batch_destroy(pcamv_batch_t *b)
     hipFree(b->d_wstat); hipFree(b->d_sw_tab); hipFree(b->d_sw_scratch);
     stage_destroy(b->tx_stage);
     hipFree(b->so.d_own); hipFree(b->so.d_head); hipFree(b->so.d_copy);
+    hipFree(b->d_idr); hipFree(b->d_idr_ctx); hipFree(b->d_idr_tab);
     hipFree(b->d_msg_own); hipFree(b->d_mtx); hipFree(b->d_mtx_m); hipFree(b->d_mtx_at);
     hipFree(b->d_mrx); hipFree(b->d_mrx_state); hipFree(b->d_mrx_job); hipFree(b->d_mrx_at); hipFree(b->d_mchk);
     ring_destroy(b->ring); ring_destroy(b->xring);
@@ -508,7 +516,8 @@ static const char *kt_name(const pcamv_batch *b, int k)      /* what pcamv_gpu_b
                                             "k_slice_header", "k_stream_status", "k_stream_open", "k_stream_slot", "k_stream_commit",
                                             "k_stream_window_unit", "k_extract_count", "k_extract_chain", "k_pset_unit", "k_pset_parse", "k_pset_resolve",
                                             "k_slice_header_sets", "k_stream_open_heads", "k_stream_join", "k_stream_copy_plan", "k_stream_copy", "k_video_cut",
-                                            "k_message_count", "k_message_plan", "k_message_jobs", "k_extract_chain_message", "k_message_check"};
+                                            "k_message_count", "k_message_plan", "k_message_jobs", "k_extract_chain_message", "k_message_check",
+                                            "k_idr_mb", "k_idr_prefix", "k_idr_pack", "k_idr_unit"};
     return k == KT_ANALYSE ? dominant_kernel(b) : small[k];
 }
 extern "C" int pcamv_gpu_batch_copy_results_async(pcamv_batch_t *b, void *dst_mb, size_t mb_stride, void *dst_flip, size_t flip_stride, void *stream)
@@ -2907,7 +2916,7 @@ extern "C" int pcamv_gpu_batch_stream_open(pcamv_batch_t *b, void *bytes, size_t
     if (ok) return fail(b, ok, wr->nal_ref_idc == 0 ? "nal_ref_idc 0: in this path a chain's P frame is the next one's reference" :
                                "stream_open: parameter sets or stream settings out of range");
     StreamOut &O = b->so;
-    O.ready = 0; O.joined = 0;
+    O.ready = 0; O.joined = 0; O.stepped = 0;
     hipStream_t st = stream ? (hipStream_t)stream : b->ctx[0]->stream;
     const size_t total = stream_out_bytes(b->n);
     if (total > O.cap_own || head_len > O.cap_head || stream_copy_bytes(b->n) > O.cap_copy) HIPCHK(b, hipDeviceSynchronize());        /* (steps on the blocks that are replaced may be in flight) */
@@ -2970,7 +2979,7 @@ extern "C" int pcamv_gpu_batch_stream_open_heads(pcamv_batch_t *b, void *bytes, 
     if (ok) return fail(b, ok, wr->nal_ref_idc == 0 ? "nal_ref_idc 0: in this path a chain's P frame is the next one's reference" :
                                "stream_open_heads: parameter sets or stream settings out of range");
     StreamOut &O = b->so;
-    O.ready = 0; O.joined = 0;
+    O.ready = 0; O.joined = 0; O.stepped = 0;
     hipStream_t st = stream ? (hipStream_t)stream : b->ctx[0]->stream;
     const size_t total = stream_out_bytes(b->n), n = (size_t)b->n;
     if (total > O.cap_own || stream_copy_bytes(b->n) > O.cap_copy) HIPCHK(b, hipDeviceSynchronize());   /* (steps on the blocks that are replaced may be in flight) */
@@ -3042,7 +3051,184 @@ extern "C" int pcamv_gpu_batch_write_stream_step(pcamv_batch_t *b, void *stream)
     J.bytes = SJ.bytes; J.bytes_size = SJ.bytes_size;
     J.off = SJ.w_off; J.cap = SJ.w_cap; J.len = SJ.w_len;
     J.mbs = NULL; J.as_nal = 1; J.final = 1;
+    b->so.stepped = 1;
     return write_run(b, J, NULL, 0, cavlc, stream ? (hipStream_t)stream : b->ctx[0]->stream, &SJ);
+}
+/* ------------------------------------------------------------------ IDR pictures coded on the device (k_idr_mb, k_idr_prefix, k_idr_pack, k_idr_slot, k_idr_unit; pcamv_idr.hip) */
+void pcamv_launch_idr_mb(const IdrJobs &J, int g0, int g, int mb_w, int mb_h, hipStream_t st);
+void pcamv_launch_idr_prefix(const IdrJobs &J, int g0, int g, hipStream_t st);
+void pcamv_launch_idr_pack(const IdrJobs &J, int g0, int g, hipStream_t st);
+void pcamv_launch_idr_unit(const IdrJobs &J, int g0, int g, hipStream_t st);
+void pcamv_launch_idr_slot(const IdrJobs &J, const void *sws_ctx, int n, hipStream_t st);
+extern "C" int pcamv_gpu_write_idr_slice_header(const pcamv_stream_params_t *params, int nal_ref_idc, int idr_pic_id, int slice_qp, uint8_t *bits, size_t cap, int32_t *n_bits)
+{
+    if (n_bits) *n_bits = 0;
+    if (!params || !n_bits || (!bits && cap)) return PCAMV_EINVAL;
+    int n = 0;
+    TRY(pcamv_idr_header_write(*params, nal_ref_idc, idr_pic_id, slice_qp, NULL, &n));         /* judged and counted; nothing stored */
+    if ((size_t)(n + 7) / 8 > cap) return PCAMV_ENOMEM;
+    const int rc = pcamv_idr_header_write(*params, nal_ref_idc, idr_pic_id, slice_qp, bits, &n);
+    *n_bits = n;
+    return rc;
+}
+extern "C" int64_t pcamv_gpu_idr_bound(const pcamv_ctx_t *c, int as_nal) { return c ? (int64_t)idr_bound(c->F.n_mb, as_nal) : PCAMV_EINVAL; }
+/* the working memory of one place of a group: bytes per context */
+static size_t idr_place_bytes(int n_mb, size_t *rbsp_stride)
+{
+    const size_t rbsp = ((size_t)idr_bound(n_mb, 0) + 255) & ~(size_t)255;
+    if (rbsp_stride) *rbsp_stride = rbsp;
+    return (((size_t)n_mb * (IDR_NZ_BYTES + IDR_SLOT_DWORDS * 4 + 4) + ((size_t)n_mb + 1) * 8 + rbsp + 255) & ~(size_t)255) + 256;     /* (+ 256: the counts of a group end at a multiple of 256) */
+}
+#define IDR_GROUP_BYTES ((size_t)8 << 30)       /* the most working memory a batch keeps for its IDR pictures: larger batches run in groups */
+/* the working memory (made at first use, kept until the batch goes), the tables, and J but for its destination */
+static int idr_setup(pcamv_batch *b, int qp, const uint8_t *hdr, int hdr_bits, int nal_byte, IdrJobs *J)
+{
+    const pcamv_ctx *c0 = b->ctx[0];
+    const int n_mb = c0->F.n_mb;
+    for (int i = 0; i < b->n; i++) {
+        const pcamv_ctx *c = b->ctx[i];
+        if (!c->F.fenc[0] || !c->F.fenc[1] || !c->F.fenc[2]) return fail(b, PCAMV_EINVAL, "context %d has no source picture (pcamv_gpu_upload_fenc, pcamv_gpu_set_fenc_device)", i);
+        if (c->p.i_luma_deadzone[1] != c0->p.i_luma_deadzone[1]) return fail(b, PCAMV_EINVAL, "the contexts of a batch share one intra dead zone");
+    }
+    if (c0->p.i_luma_deadzone[1] < 0 || c0->p.i_luma_deadzone[1] > 32) return fail(b, PCAMV_EINVAL, "i_luma_deadzone[1] outside 0 .. 32");
+    size_t rbsp_stride = 0;
+    const size_t place = idr_place_bytes(n_mb, &rbsp_stride);
+    int group = (int)(IDR_GROUP_BYTES / place);
+    group = group < 1 ? 1 : group > b->n ? b->n : group;
+    if (!b->d_idr || b->idr_group != group) {
+        if (b->d_idr) HIPCHK(b, hipDeviceSynchronize());
+        TRY(grow(b, &b->d_idr, &b->cap_idr, place * (size_t)group));
+        b->idr_group = group;
+    }
+    if (!b->d_idr_ctx) HIPCHK(b, dalloc(&b->d_idr_ctx, (size_t)b->n * (2 * 4 + 3 * 8)));
+    if (!b->d_wstat) HIPCHK(b, dalloc(&b->d_wstat, (size_t)b->n));
+    if (!b->d_idr_tab) {
+        uint8_t tab[SV_TAB_BYTES];
+        if (sv_build_tables(tab)) return fail(b, PCAMV_EINVAL, "the CAVLC code tables do not fit their entries");
+        HIPCHK(b, dalloc(&b->d_idr_tab, (size_t)SV_TAB_BYTES));
+        HIPCHK(b, hipMemcpy(b->d_idr_tab, tab, SV_TAB_BYTES, hipMemcpyHostToDevice));
+    }
+    IdrJobs &j = *J;
+    memset((void *)&j, 0, sizeof(j));
+    const size_t g = (size_t)group, n = (size_t)n_mb;
+    uint8_t *at = b->d_idr;
+    j.pre = (long long *)at; at += g * (n + 1) * 8;
+    j.slots = (uint32_t *)at; at += g * n * IDR_SLOT_DWORDS * 4;
+    j.bits = (int *)at; at += g * n * 4;
+    j.nz = at; at += (g * n * IDR_NZ_BYTES + 255) & ~(size_t)255;
+    j.rbsp = at; j.rbsp_stride = (long long)rbsp_stride;
+    j.tab = b->d_idr_tab;
+    j.bad = (int *)(b->d_idr_ctx + (size_t)b->n * 24); j.first = j.bad + b->n;
+    memcpy(j.hdr, hdr, IDR_HDR_BYTES);
+    for (int o = -12; o <= 12; o++) { const int q = qp + o; j.qpc_of[12 + o] = pcamv_chroma_qp_tab[q < 0 ? 0 : q > 51 ? 51 : q]; }
+    j.hdr_bits = hdr_bits; j.nal_byte = nal_byte; j.n_mb = n_mb; j.qp = qp; j.dz = c0->p.i_luma_deadzone[1];
+    j.status = b->d_wstat;
+    return 0;
+}
+/* every context's source coded, group by group, on `st`; then every context's reconstruction becomes its reference: copied into the
+ * context's own reference planes, and the plane production of a step with no previous motion -- the state pcamv_gpu_set_ref leaves */
+static int idr_run(pcamv_batch *b, IdrJobs &J, const void *sws_ctx, hipStream_t st)
+{
+    const FrameDev *dF; const EmbedDev *dE; int slot;
+    TRY(batch_push_descs(b, st, &dF, &dE, &slot));
+    J.Fs = dF;
+    const FrameDev &F = b->ctx[0]->F;
+    if (sws_ctx) pcamv_launch_idr_slot(J, sws_ctx, b->n, st);
+    for (int g0 = 0; g0 < b->n; g0 += b->idr_group) {
+        const int g = b->n - g0 < b->idr_group ? b->n - g0 : b->idr_group;
+        int ev = kt_begin(b, KT_IDR_MB, st);
+        pcamv_launch_idr_mb(J, g0, g, F.mb_w, F.mb_h, st);
+        kt_end(b, KT_IDR_MB, ev, st);
+        ev = kt_begin(b, KT_IDR_PREFIX, st);
+        pcamv_launch_idr_prefix(J, g0, g, st);
+        kt_end(b, KT_IDR_PREFIX, ev, st);
+        ev = kt_begin(b, KT_IDR_PACK, st);
+        pcamv_launch_idr_pack(J, g0, g, st);
+        kt_end(b, KT_IDR_PACK, ev, st);
+        ev = kt_begin(b, KT_IDR_UNIT, st);
+        pcamv_launch_idr_unit(J, g0, g, st);
+        kt_end(b, KT_IDR_UNIT, ev, st);
+    }
+    TRY(launched(b));
+    TRY(ring_release(b, b->ring, slot, st));
+    const size_t ysz = (size_t)F.w * F.h;
+    for (int i = 0; i < b->n; i++) {
+        pcamv_ctx *c = b->ctx[i];
+        for (int k = 0; k < 3; k++) {
+            HIPCHK(b, hipMemcpyAsync(c->d_raw[k], c->F.rec[k], k ? ysz / 4 : ysz, hipMemcpyDeviceToDevice, st));
+            c->F.raw[k] = c->d_raw[k];
+        }
+        c->F.have_prev = 0; c->F.ref_is_inter = 0; c->prev_internal = 0;
+        c->F.mv = c->d_mv; c->F.ref8 = c->d_ref8; c->F.prev_mv = c->d_prev_mv; c->F.prev_ref = c->d_prev_ref;
+        drop_rec_reuse(c);
+    }
+    return batch_launch(b, ST_PLANES, st);
+}
+/* the parameter sets the probe's header is written under: pcamv_stream_params_t {4, 0, 4, 0, 0, 0, 1, 0, 0, 26, 1, pps_id} */
+static pcamv_stream_params_t idr_probe_params(int pps_id)
+{
+    pcamv_stream_params_t P = {4, 0, 4, 0, 0, 0, 1, 0, 0, 26, 1, pps_id};
+    return P;
+}
+extern "C" int pcamv_gpu_encode_idr(pcamv_ctx_t *c, int qp, int pps_id, int idr_pic_id, int as_nal, uint8_t *out, size_t cap, size_t *len)
+{
+    if (!c || !out || !len || cap > ((size_t)1 << 40)) return PCAMV_EINVAL;
+    *len = 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    pcamv_batch *b = c->self;
+    TRY(on_behalf(c, b, batch_live(b)));
+    uint8_t hdr[IDR_HDR_BYTES] = {0};
+    int hdr_bits = 0;
+    const pcamv_stream_params_t P = idr_probe_params(pps_id);
+    const int hrc = pcamv_idr_header_write(P, 3, idr_pic_id, qp, hdr, &hdr_bits);
+    if (hrc) return fail(c, hrc, "encode_idr: qp outside 0 .. 51, pps_id outside 0 .. 255 or idr_pic_id outside 0 .. 65535");
+    IdrJobs J;
+    TRY(on_behalf(c, b, idr_setup(b, qp, hdr, hdr_bits, 3 << 5 | 5, &J)));
+    DevTmp<uint8_t> d_out;
+    HIPCHK(c, d_out.alloc(cap ? cap : 1));
+    long long *arr = (long long *)b->d_idr_ctx;
+    const long long h_arr[3] = {0, (long long)cap, 0};
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(arr, h_arr, sizeof(h_arr), hipMemcpyHostToDevice));
+    J.bytes = d_out; J.bytes_size = (long long)cap; J.off = arr; J.cap = arr + 1; J.len = arr + 2; J.as_nal = as_nal != 0; J.first = NULL;
+    TRY(on_behalf(c, b, idr_run(b, J, NULL, c->stream)));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    int st = 0; long long n = 0;
+    HIPCHK(c, hipMemcpy(&st, b->d_wstat, sizeof(st), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&n, arr + 2, sizeof(n), hipMemcpyDeviceToHost));
+    if (st) return fail(c, st, st == PCAMV_ENOMEM ? "the IDR unit does not fit %zu bytes (pcamv_gpu_idr_bound gives a capacity that always does)" : "encode_idr: the coder failed", cap);
+    if (n < 0 || (size_t)n > cap) return fail(c, PCAMV_EHIP, "encode_idr: length corrupt");
+    if (n) HIPCHK(c, hipMemcpy(out, d_out, (size_t)n, hipMemcpyDeviceToHost));
+    *len = (size_t)n;
+    return 0;
+}
+extern "C" int pcamv_gpu_batch_write_stream_idr(pcamv_batch_t *b, int qp, int pps_id, int idr_pic_id, void *stream)
+{
+    if (!b) return PCAMV_EINVAL;
+    HIPCHK(b, hipSetDevice(b->device));
+    TRY(batch_live(b));
+    StreamOut &O = b->so;
+    if (!O.ready) return fail(b, PCAMV_EINVAL, "no byte streams were opened on this batch yet (pcamv_gpu_batch_stream_open)");
+    if (O.stepped) return fail(b, PCAMV_EINVAL, "write_stream_idr belongs behind the open and before the first picture of its streams");
+    if (O.S.W.first_pic != 0) return fail(b, PCAMV_EINVAL, "an IDR picture is picture 0 of its stream: the open must have first_pic 0");
+    pcamv_stream_params_t P = O.S.P;
+    P.pps_id = pps_id; P.entropy_cabac = 0;             /* the PPS the IDR slices name: the stream's but for its id and its entropy mode */
+    if (!P.deblocking_filter_control_present) return fail(b, PCAMV_EUNSUP, "the IDR picture is not filtered and its header must say so: the PPS needs deblocking_filter_control_present");
+    uint8_t hdr[IDR_HDR_BYTES] = {0};
+    int hdr_bits = 0;
+    const int hrc = pcamv_idr_header_write(P, O.S.W.nal_ref_idc, idr_pic_id, qp, hdr, &hdr_bits);
+    if (hrc) return fail(b, hrc, "write_stream_idr: qp outside 0 .. 51, pps_id outside 0 .. 255 or idr_pic_id outside 0 .. 65535");
+    hipStream_t st = stream ? (hipStream_t)stream : b->ctx[0]->stream;
+    IdrJobs J;
+    TRY(idr_setup(b, qp, hdr, hdr_bits, O.S.W.nal_ref_idc << 5 | 5, &J));
+    const StreamWrite SJ = stream_out_jobs(b);
+    J.bytes = SJ.bytes; J.bytes_size = SJ.bytes_size; J.off = SJ.w_off; J.cap = SJ.w_cap; J.len = SJ.w_len; J.first = SJ.first; J.as_nal = 1; J.aud = O.S.W.aud;
+    O.stepped = 1;
+    TRY(idr_run(b, J, SJ.ctx, st));
+    const int ev = kt_begin(b, KT_STREAM_COMMIT, st);
+    hipLaunchKernelGGL(k_stream_commit, dim3((b->n + 63) / 64), dim3(64), 0, st, SJ);
+    kt_end(b, KT_STREAM_COMMIT, ev, st);
+    return launched(b);
 }
 /* synchronises */
 extern "C" int pcamv_gpu_batch_stream_written(pcamv_batch_t *b, int64_t *bytes, int64_t *pictures, int64_t *units)

@@ -1,0 +1,134 @@
+/*
+ * pcamv_idr.hip -- the IDR picture of every chain coded on the device (gfx950): k_idr_mb, k_idr_prefix, k_idr_pack, k_idr_slot,
+ * k_idr_unit.  The coder itself is pcamv_idr.h (shared with the host check); this unit gives it its working memory and its place in a
+ * batch.
+ *
+ *   k_idr_mb      one wavefront per macroblock, launched once per anti-diagonal x + y = d over the contexts of a group (Intra16x16 reads
+ *                 left, top and top-left only): mode decision, transform, reconstruction, counts, the macroblock's bit string.  The
+ *                 working memory is LDS of the wave (IdrWork); the code tables are read where they lie.
+ *   k_idr_prefix  per context the exclusive prefix of the macroblocks' bit counts, the header's bits in front: every thread sums a run
+ *                 of macroblocks, the block scans the runs' sums in LDS, every thread writes its run.
+ *   k_idr_pack    one lane per destination dword of the RBSP (idr_pack_dword).
+ *   k_idr_slot    (streams) one lane per context: the access unit delimiter 09 10 at the stream's end, the place the unit gets.
+ *   k_idr_unit    one wavefront per context: start code, header byte and emulation prevention through the slice writers' output path,
+ *                 nothing stored at or beyond the capacity.
+ * No spin-wait and no dependency between the waves of a launch.  Every store is an ordinary vector store.  Nothing else is defined here.
+ */
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "pcamv_flow.hip.h"
+#include "pcamv_idr.h"
+
+/* context i's picture at its place in the group */
+static __device__ IdrPic idr_pic(const IdrJobs &J, int i, int place)
+{
+    const FrameDev &F = J.Fs[i];
+    const int off = F.chroma_qp_offset < -12 ? -12 : F.chroma_qp_offset > 12 ? 12 : F.chroma_qp_offset;
+    IdrPic P;
+    for (int k = 0; k < 3; k++) { P.src[k] = F.fenc[k]; P.rec[k] = F.rec[k]; }
+    P.mb_w = F.mb_w; P.mb_h = J.n_mb / F.mb_w; P.qp = J.qp; P.qpc = J.qpc_of[12 + off]; P.dz = J.dz;
+    P.nz = J.nz + (size_t)place * IDR_NZ_BYTES * J.n_mb; P.slots = J.slots + (size_t)place * IDR_SLOT_DWORDS * J.n_mb; P.bits = J.bits + (size_t)place * J.n_mb;
+    P.clamped = nullptr;
+    return P;
+}
+
+static __global__ void __launch_bounds__(64) k_idr_mb(const IdrJobs J, int d, int g0)
+{
+    __shared__ IdrWork W;
+    const IdrPic P = idr_pic(J, g0 + blockIdx.y, blockIdx.y);
+    const int y_lo = d - (P.mb_w - 1) > 0 ? d - (P.mb_w - 1) : 0, my = y_lo + (int)blockIdx.x, mx = d - my;
+    if (my >= P.mb_h || mx < 0 || mx >= P.mb_w) return;
+    idr_mb(W, P, (const uint16_t *)J.tab, mx, my);
+}
+
+#define IDR_PREFIX_THREADS 1024
+static __global__ void __launch_bounds__(IDR_PREFIX_THREADS) k_idr_prefix(const IdrJobs J, int g0)
+{
+    __shared__ long long s_sum[IDR_PREFIX_THREADS];
+    __shared__ int s_bad;
+    const int i = g0 + blockIdx.x, t = threadIdx.x;
+    const IdrPic P = idr_pic(J, i, blockIdx.x);
+    const int n_mb = P.mb_w * P.mb_h, run = (n_mb + IDR_PREFIX_THREADS - 1) / IDR_PREFIX_THREADS;
+    const int lo = t * run < n_mb ? t * run : n_mb, hi = lo + run < n_mb ? lo + run : n_mb;
+    long long *pre = J.pre + (long long)blockIdx.x * (J.n_mb + 1);
+    if (t == 0) s_bad = 0;
+    __syncthreads();
+    long long sum = 0;
+    int bad = 0;
+    for (int k = lo; k < hi; k++) { const int b = P.bits[k]; if (b < 0) bad = 1; else sum += b; }
+    if (bad) s_bad = 1;
+    s_sum[t] = sum;
+    __syncthreads();
+    for (int step = 1; step < IDR_PREFIX_THREADS; step <<= 1) {
+        const long long v = t >= step ? s_sum[t - step] : 0;
+        __syncthreads();
+        s_sum[t] += v;
+        __syncthreads();
+    }
+    long long at = J.hdr_bits + s_sum[t] - sum;
+    for (int k = lo; k < hi; k++) { pre[k] = at; const int b = P.bits[k]; at += b < 0 ? 0 : b; }
+    if (t == IDR_PREFIX_THREADS - 1) { pre[n_mb] = J.hdr_bits + s_sum[t]; J.bad[i] = s_bad; }
+}
+
+static __global__ void __launch_bounds__(256) k_idr_pack(const IdrJobs J, int g0)
+{
+    const IdrPic P = idr_pic(J, g0 + blockIdx.y, blockIdx.y);
+    const int n_mb = P.mb_w * P.mb_h;
+    const long long *pre = J.pre + (long long)blockIdx.y * (J.n_mb + 1);
+    const long long k = (long long)blockIdx.x * 256 + threadIdx.x, dwords = (idr_rbsp_bytes(pre[n_mb]) + 3) >> 2;
+    if (k >= dwords || k >= J.rbsp_stride / 4) return;
+    ((uint32_t *)(J.rbsp + (long long)blockIdx.y * J.rbsp_stride))[k] = idr_pack_dword(k, J.hdr, J.hdr_bits, pre, P.slots, n_mb);
+}
+
+/* the sibling of k_stream_slot for a picture whose unit is made here: the delimiter and the unit succeed or fail together */
+static __global__ void __launch_bounds__(64) k_idr_slot(const IdrJobs J, const SwsCtx *ctx, int n)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const SwsCtx c = ctx[i];
+    long long off = 0, cap = -1; int first = PCAMV_EINVAL;
+    if (!c.bad) {
+        const long long aud = J.aud ? IDR_AUD_BYTES : 0, room = c.cap - c.cur;
+        off = c.off + c.cur; cap = 0; first = PCAMV_ENOMEM;
+        if (room >= aud) {
+            if (aud) { uint8_t *p = J.bytes + off; p[0] = 0; p[1] = 0; p[2] = 0; p[3] = 1; p[4] = 0x09; p[5] = 0x10; }      /* primary_pic_type 0 (I), the stop bit */
+            off += aud; cap = room - aud; first = 0;
+        }
+    }
+    J.off[i] = off; J.cap[i] = cap; J.first[i] = first;
+}
+
+static __global__ void __launch_bounds__(64) k_idr_unit(const IdrJobs J, int g0)
+{
+    __shared__ uint32_t s_win[64], s_obuf[SW_OBUF / 4];
+    const int i = g0 + blockIdx.x;
+    const IdrPic P = idr_pic(J, i, blockIdx.x);
+    const long long *pre = J.pre + (long long)blockIdx.x * (J.n_mb + 1);
+    const long long off = J.off[i], cap = J.cap[i], rbsp_len = idr_rbsp_bytes(pre[P.mb_w * P.mb_h]);
+    long long len = 0;
+    int rc = PCAMV_EINVAL;
+    IdrOut O;
+    O.obuf = s_obuf;
+    if (off >= 0 && cap >= 0 && cap <= J.bytes_size && off <= J.bytes_size - cap && !J.bad[i] && rbsp_len <= J.rbsp_stride)
+        rc = idr_unit(O, s_win, J.rbsp + (long long)blockIdx.x * J.rbsp_stride, rbsp_len, J.nal_byte, J.as_nal, J.bytes + off, cap, &len);
+    if (threadIdx.x == 0) { J.status[i] = rc; J.len[i] = rc ? 0 : len; }
+}
+
+void pcamv_launch_idr_mb(const IdrJobs &J, int g0, int g, int mb_w, int mb_h, hipStream_t st)
+{
+    for (int d = 0; d < mb_w + mb_h - 1; d++) {
+        const int y_lo = d - (mb_w - 1) > 0 ? d - (mb_w - 1) : 0, y_hi = d < mb_h - 1 ? d : mb_h - 1;
+        hipLaunchKernelGGL(k_idr_mb, dim3((unsigned)(y_hi - y_lo + 1), (unsigned)g), dim3(64), 0, st, J, d, g0);
+    }
+}
+void pcamv_launch_idr_prefix(const IdrJobs &J, int g0, int g, hipStream_t st) { hipLaunchKernelGGL(k_idr_prefix, dim3((unsigned)g), dim3(IDR_PREFIX_THREADS), 0, st, J, g0); }
+void pcamv_launch_idr_pack(const IdrJobs &J, int g0, int g, hipStream_t st)
+{
+    const long long dwords = J.rbsp_stride / 4;
+    hipLaunchKernelGGL(k_idr_pack, dim3((unsigned)((dwords + 255) / 256), (unsigned)g), dim3(256), 0, st, J, g0);
+}
+void pcamv_launch_idr_unit(const IdrJobs &J, int g0, int g, hipStream_t st) { hipLaunchKernelGGL(k_idr_unit, dim3((unsigned)g), dim3(64), 0, st, J, g0); }
+void pcamv_launch_idr_slot(const IdrJobs &J, const void *sws_ctx, int n, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_idr_slot, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, J, (const SwsCtx *)sws_ctx, n);
+}

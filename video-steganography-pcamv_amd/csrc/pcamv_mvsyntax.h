@@ -743,4 +743,290 @@ extern "C" int pcamv_gpu_parse_slice_header(const uint8_t *rbsp, size_t len, int
     *start_bit = (int64_t)b.pos; *slice_qp = (int32_t)qp; *frame_num = (int32_t)fn;
     return 0;
 }
+
+/* ---------------------------------------------------------------- the IDR picture of a chain: its slice header read, its I slice decoded
+ * The header of an IDR I slice as pcamv_gpu_write_idr_slice_header writes it (csrc/pcamv_idr.h), read in syntax order under the rules of
+ * pcamv_gpu_parse_slice_header: nal_unit_type != 5, first_mb_in_slice != 0, slice_type not 2 or 7, pps_id != params->pps_id:
+ * PCAMV_EUNSUP; frame_num != 0: PCAMV_EINVAL (7.4.3: an IDR picture's is 0); idr_pic_id above 65535: PCAMV_EINVAL; the POC elements and
+ * redundant_pic_cnt are read and not judged; with nal_ref_idc != 0 the two marking flags, long_term_reference_flag 1: PCAMV_EUNSUP;
+ * entropy_cabac: PCAMV_EUNSUP (the decoder below reads CAVLC); slice_qp_delta, a QP outside 0 .. 51: PCAMV_EINVAL; without deblocking
+ * control, or with an idc that is not 1: PCAMV_EUNSUP (the picture would be filtered), an idc above 2 PCAMV_EINVAL.  A read at or past the
+ * end and a ue with more than 31 leading zeros are PCAMV_EINVAL, found before the element is judged.  All three outputs -1 on failure. */
+extern "C" int pcamv_gpu_parse_idr_slice_header(const uint8_t *rbsp, size_t len, int nal_header, const pcamv_stream_params_t *params, int64_t *start_bit,
+                                                int32_t *slice_qp, int32_t *idr_pic_id)
+{
+    if (start_bit) *start_bit = -1;
+    if (slice_qp) *slice_qp = -1;
+    if (idr_pic_id) *idr_pic_id = -1;
+    if ((!rbsp && len) || !start_bit || !slice_qp || !idr_pic_id || !pcamv_stream_params_ok(params) || len > ((size_t)1 << 40)) return PCAMV_EINVAL;
+    if (nal_header < 0 || (nal_header & 31) != 5) return PCAMV_EUNSUP;
+    const pcamv_stream_params_t &P = *params;
+    mvsyntax::HdrBits b = {rbsp, (uint64_t)len * 8, 0, 0};
+#define HDR_EOF() do { if (b.bad) return PCAMV_EINVAL; } while (0)
+    if (b.ue() != 0) { HDR_EOF(); return PCAMV_EUNSUP; }
+    HDR_EOF();
+    const uint64_t slice_type = b.ue(); HDR_EOF();
+    if (slice_type != 2 && slice_type != 7) return PCAMV_EUNSUP;
+    const uint64_t pps_id = b.ue(); HDR_EOF();
+    if (pps_id != (uint64_t)P.pps_id) return PCAMV_EUNSUP;
+    const uint32_t fn = b.u(P.log2_max_frame_num); HDR_EOF();
+    if (fn != 0) return PCAMV_EINVAL;
+    const uint64_t id = b.ue(); HDR_EOF();
+    if (id > 65535) return PCAMV_EINVAL;
+    if (P.poc_type == 0) {
+        b.u(P.log2_max_poc_lsb); HDR_EOF();
+        if (P.pic_order_present) { b.se(); HDR_EOF(); }
+    } else if (P.poc_type == 1 && !P.delta_pic_order_always_zero) {
+        b.se(); HDR_EOF();
+        if (P.pic_order_present) { b.se(); HDR_EOF(); }
+    }
+    if (P.redundant_pic_cnt_present) { b.ue(); HDR_EOF(); }
+    if ((nal_header >> 5) & 3) {
+        b.get1(); HDR_EOF();                                                    /* no_output_of_prior_pics_flag */
+        const unsigned lt = b.get1(); HDR_EOF();
+        if (lt) return PCAMV_EUNSUP;
+    }
+    if (P.entropy_cabac) return PCAMV_EUNSUP;
+    const int64_t qp = P.pic_init_qp + b.se(); HDR_EOF();
+    if (qp < 0 || qp > 51) return PCAMV_EINVAL;
+    if (!P.deblocking_filter_control_present) return PCAMV_EUNSUP;
+    const uint64_t idc = b.ue(); HDR_EOF();
+    if (idc > 2) return PCAMV_EINVAL;
+    if (idc != 1) return PCAMV_EUNSUP;
+#undef HDR_EOF
+    if (b.pos >= b.nbits) return PCAMV_EINVAL;
+    *start_bit = (int64_t)b.pos; *slice_qp = (int32_t)qp; *idr_pic_id = (int32_t)id;
+    return 0;
+}
+
+namespace mvsyntax {
+/* A decoder of exactly the I slices the device writes: Intra16x16 macroblocks, CAVLC, one QP, no loop filter (H.264 7.3.5, 8.3.3, 8.3.4,
+ * 8.5, 9.2).  Written from the standard alone; with the device's coder (csrc/pcamv_idr.h) it shares the code tables and nothing else.
+ * Every read is bounded: BitRd gives zeros past the end and counts the overrun, which fails the macroblock. */
+struct IDec {
+    BitRd b;
+    int mb_w, mb_h, qp, qpc;
+    uint8_t *pl[3]; uint8_t *nz;                        /* the planes; total_coeff of the AC blocks [n_mb][24] */
+
+    static int clip8(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
+    static int vscale(int q6, int i, int j)
+    {
+        static const int v[6][3] = {{10, 16, 13}, {11, 18, 14}, {13, 20, 16}, {14, 23, 18}, {16, 25, 20}, {18, 29, 23}};
+        return v[q6][(i & 1) && (j & 1) ? 1 : !(i & 1) && !(j & 1) ? 0 : 2];
+    }
+    /* residual_block_cavlc (9.2) into lv[0 .. maxc) in scan order; false on bad data */
+    bool residual(int tab, int maxc, int *lv, int *total_out)
+    {
+        for (int i = 0; i < maxc; i++) lv[i] = 0;
+        *total_out = 0;
+        int total = -1, t1 = 0;
+        if (b.peek(pcamv_vlc_coeff0_len[tab]) == pcamv_vlc_coeff0_code[tab]) { b.get(pcamv_vlc_coeff0_len[tab]); return !b.overrun; }
+        for (int tc = 1; tc <= (tab == 4 ? 4 : 16) && total < 0; tc++)
+            for (int tr = 0; tr <= (tc < 3 ? tc : 3); tr++) {
+                const int k = tab * 64 + (tc - 1) * 4 + tr, len = pcamv_vlc_coeff_len[k];
+                if (len && b.peek(len) == pcamv_vlc_coeff_code[k]) { b.get(len); total = tc; t1 = tr; break; }
+            }
+        if (total < 0 || total > maxc || b.overrun) return false;
+        int level[16];
+        int suffix_len = total > 10 && t1 < 3;
+        for (int i = 0; i < total; i++) {
+            if (i < t1) { level[i] = b.get(1) ? -1 : 1; continue; }
+            int prefix = 0;
+            while (!b.get(1)) if (++prefix > 15 || b.overrun) return false;         /* no prefix above 15 below the High profiles */
+            if (b.overrun) return false;
+            const int ssize = (prefix == 14 && suffix_len == 0) ? 4 : (prefix == 15 ? 12 : suffix_len);
+            int code = ((prefix < 15 ? prefix : 15) << suffix_len) + (ssize ? (int)b.get(ssize) : 0);
+            if (prefix == 15 && suffix_len == 0) code += 15;
+            if (i == t1 && t1 < 3) code += 2;
+            level[i] = code & 1 ? (-code - 1) >> 1 : (code + 2) >> 1;
+            const int a = level[i] < 0 ? -level[i] : level[i];
+            if (suffix_len == 0) suffix_len = 1;
+            if (a > (3 << (suffix_len - 1)) && suffix_len < 6) suffix_len++;
+        }
+        int zeros = 0;
+        if (total < maxc) {
+            const unsigned char *len = tab == 4 ? &pcamv_vlc_total_zeros_dc_len[(total - 1) * 4] : &pcamv_vlc_total_zeros_len[(total - 1) * 16];
+            const unsigned short *code = tab == 4 ? &pcamv_vlc_total_zeros_dc_code[(total - 1) * 4] : &pcamv_vlc_total_zeros_code[(total - 1) * 16];
+            int z, nzc = tab == 4 ? 4 : 16;
+            for (z = 0; z < nzc; z++) if (len[z] && b.peek(len[z]) == code[z]) { b.get(len[z]); break; }
+            if (z == nzc || z + total > maxc) return false;
+            zeros = z;
+        }
+        int pos = total + zeros - 1;                    /* the place of the last coefficient, which is level[0] */
+        for (int i = 0; i < total; i++) {
+            if (pos < 0 || pos >= maxc) return false;
+            lv[pos] = level[i];
+            int run = 0;
+            if (i < total - 1 && zeros > 0) {
+                const int zl = zeros - 1 < 6 ? zeros - 1 : 6;
+                int r;
+                for (r = 0; r < 16; r++) { const int len = pcamv_vlc_run_before_len[zl * 16 + r]; if (len && b.peek(len) == pcamv_vlc_run_before_code[zl * 16 + r]) { b.get(len); break; } }
+                if (r == 16 || r > zeros) return false;
+                run = r; zeros -= r;
+            } else if (i == total - 1) run = zeros;
+            pos -= 1 + run;
+        }
+        *total_out = total;
+        return !b.overrun;
+    }
+    static int nc_class(int na, int nb)
+    {
+        const int nc = na >= 0 && nb >= 0 ? (na + nb + 1) >> 1 : na >= 0 ? na : nb >= 0 ? nb : 0;
+        return nc < 2 ? 0 : nc < 4 ? 1 : nc < 8 ? 2 : 3;
+    }
+    /* 8.5.12 on a block of dequantised coefficients c[i][j], added to the prediction at p (pitch w) */
+    static void add_idct(const int c[4][4], uint8_t *p, int w)
+    {
+        int f[4][4], r[4][4];
+        for (int i = 0; i < 4; i++) {
+            const int e0 = c[i][0] + c[i][2], e1 = c[i][0] - c[i][2], e2 = (c[i][1] >> 1) - c[i][3], e3 = c[i][1] + (c[i][3] >> 1);
+            f[i][0] = e0 + e3; f[i][1] = e1 + e2; f[i][2] = e1 - e2; f[i][3] = e0 - e3;
+        }
+        for (int j = 0; j < 4; j++) {
+            const int g0 = f[0][j] + f[2][j], g1 = f[0][j] - f[2][j], g2 = (f[1][j] >> 1) - f[3][j], g3 = f[1][j] + (f[3][j] >> 1);
+            r[0][j] = g0 + g3; r[1][j] = g1 + g2; r[2][j] = g1 - g2; r[3][j] = g0 - g3;
+        }
+        for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) p[i * w + j] = (uint8_t)clip8(p[i * w + j] + ((r[i][j] + 32) >> 6));
+    }
+    /* the prediction of a whole plane block of n x n at (px, py) of plane c: kind 0 DC, 1 horizontal, 2 vertical, 3 plane */
+    void predict(int c, int n, int px, int py, int kind, bool left, bool top)
+    {
+        const int w = (c ? 8 : 16) * mb_w;
+        uint8_t *p = pl[c] + (size_t)py * w + px;
+        int T[17], L[16];                               /* T[0]: above-left, T[1 + x], L[y] */
+        for (int x = -1; x < n; x++) T[1 + x] = top && (x >= 0 || left) ? p[-w + x] : 128;
+        for (int y = 0; y < n; y++) L[y] = left ? p[y * w - 1] : 128;
+        if (kind == 1) { for (int y = 0; y < n; y++) for (int x = 0; x < n; x++) p[y * w + x] = (uint8_t)L[y]; return; }
+        if (kind == 2) { for (int y = 0; y < n; y++) for (int x = 0; x < n; x++) p[y * w + x] = (uint8_t)T[1 + x]; return; }
+        if (kind == 3) {
+            const int h = n / 2;
+            int H = 0, V = 0;
+            for (int k = 0; k < h; k++) { H += (k + 1) * (T[1 + h + k] - T[1 + h - 2 - k]); V += (k + 1) * (L[h + k] - (h - 2 - k < 0 ? T[0] : L[h - 2 - k])); }
+            const int a = 16 * (L[n - 1] + T[n]), bb = n == 16 ? (5 * H + 32) >> 6 : (34 * H + 32) >> 6, cc = n == 16 ? (5 * V + 32) >> 6 : (34 * V + 32) >> 6;
+            for (int y = 0; y < n; y++) for (int x = 0; x < n; x++) p[y * w + x] = (uint8_t)clip8((a + bb * (x - (h - 1)) + cc * (y - (h - 1)) + 16) >> 5);
+            return;
+        }
+        if (n == 16) {
+            int st = 0, sl = 0;
+            for (int k = 0; k < 16; k++) { st += T[1 + k]; sl += L[k]; }
+            const int dc = top && left ? (st + sl + 16) >> 5 : top ? (st + 8) >> 4 : left ? (sl + 8) >> 4 : 128;
+            for (int y = 0; y < 16; y++) for (int x = 0; x < 16; x++) p[y * w + x] = (uint8_t)dc;
+            return;
+        }
+        for (int by = 0; by < 2; by++)                  /* 8.3.4.1 .. 8.3.4.3: each 4x4 block of the chroma block has its own DC */
+            for (int bx = 0; bx < 2; bx++) {
+                int st = 0, sl = 0, dc;
+                for (int k = 0; k < 4; k++) { st += T[1 + 4 * bx + k]; sl += L[4 * by + k]; }
+                if (bx == by) dc = top && left ? (st + sl + 4) >> 3 : top ? (st + 2) >> 2 : left ? (sl + 2) >> 2 : 128;
+                else if (bx) dc = top ? (st + 2) >> 2 : left ? (sl + 2) >> 2 : 128;
+                else dc = left ? (sl + 2) >> 2 : top ? (st + 2) >> 2 : 128;
+                for (int y = 0; y < 4; y++) for (int x = 0; x < 4; x++) p[(4 * by + y) * w + 4 * bx + x] = (uint8_t)dc;
+            }
+    }
+    int run()
+    {
+        static const int zz[16][2] = {{0, 0}, {0, 1}, {1, 0}, {2, 0}, {1, 1}, {0, 2}, {0, 3}, {1, 2}, {2, 1}, {3, 0}, {3, 1}, {2, 2}, {1, 3}, {2, 3}, {3, 2}, {3, 3}};
+        static const int A[4][4] = {{1, 1, 1, 1}, {1, 1, -1, -1}, {1, -1, -1, 1}, {1, -1, 1, -1}};
+        for (int my = 0; my < mb_h; my++)
+            for (int mx = 0; mx < mb_w; mx++) {
+                const int xy = my * mb_w + mx;
+                const bool left = mx > 0, top = my > 0;
+                const unsigned mb_type = b.ue();
+                if (b.overrun) return PCAMV_EINVAL;
+                if (mb_type == 0 || mb_type > 24) return mb_type <= 25 ? PCAMV_EUNSUP : PCAMV_EINVAL;      /* I_NxN, I_PCM: not this subset */
+                const int mode = (int)(mb_type - 1) & 3, cbp_c = (int)((mb_type - 1) >> 2) % 3, cbp_l = mb_type > 12 ? 15 : 0;
+                const unsigned cmode = b.ue();
+                if (b.overrun || cmode > 3) return PCAMV_EINVAL;
+                if (b.se() != 0 || b.overrun) return b.overrun ? PCAMV_EINVAL : PCAMV_EUNSUP;              /* mb_qp_delta: one QP */
+                /* a mode whose neighbours are missing is bad data (8.3.3, 8.3.4) */
+                const int lkind = mode == 0 ? 2 : mode == 1 ? 1 : mode == 2 ? 0 : 3;
+                const int kinds[2] = {lkind, (int)cmode};
+                for (int k = 0; k < 2; k++) if ((kinds[k] == 1 && !left) || (kinds[k] == 2 && !top) || (kinds[k] == 3 && !(left && top))) return PCAMV_EINVAL;
+                uint8_t *cnt = nz + (size_t)xy * 24;
+                const uint8_t *cl = left ? cnt - 24 : NULL, *ct = top ? cnt - 24 * mb_w : NULL;
+                memset(cnt, 0, 24);
+                auto blk_at = [](int x, int y) { return (x & 1) | (y & 1) << 1 | (x & 2) << 1 | (y & 2) << 2; };
+                auto luma_nc = [&](int bi) {
+                    const int x = blk_x(bi), y = blk_y(bi);
+                    const int na = x > 0 ? cnt[blk_at(x - 1, y)] : cl ? cl[blk_at(3, y)] : -1, nb = y > 0 ? cnt[blk_at(x, y - 1)] : ct ? ct[blk_at(x, 3)] : -1;
+                    return nc_class(na, nb);
+                };
+                int dc[16], ac[16][16], total;
+                if (!residual(luma_nc(0), 16, dc, &total)) return PCAMV_EINVAL;
+                for (int bi = 0; bi < 16; bi++) {
+                    ac[bi][0] = 0;
+                    for (int i = 1; i < 16; i++) ac[bi][i] = 0;
+                    if (cbp_l) {
+                        if (!residual(luma_nc(bi), 15, ac[bi] + 1, &total)) return PCAMV_EINVAL;
+                        cnt[bi] = (uint8_t)total;
+                    }
+                }
+                int cdc[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}, cac[2][4][16];
+                memset(cac, 0, sizeof(cac));
+                if (cbp_c) for (int c = 0; c < 2; c++) if (!residual(4, 4, cdc[c], &total)) return PCAMV_EINVAL;
+                if (cbp_c == 2)
+                    for (int c = 0; c < 2; c++)
+                        for (int k = 0; k < 4; k++) {
+                            const int base = 16 + 4 * c, x = k & 1, y = k >> 1;
+                            const int na = x ? cnt[base + 2 * y] : cl ? cl[base + 2 * y + 1] : -1, nb = y ? cnt[base + x] : ct ? ct[base + 2 + x] : -1;
+                            if (!residual(nc_class(na, nb), 15, cac[c][k] + 1, &total)) return PCAMV_EINVAL;
+                            cnt[base + k] = (uint8_t)total;
+                        }
+                /* luma: prediction, the DCs through 8.5.10, every block through 8.5.12 */
+                predict(0, 16, 16 * mx, 16 * my, lkind, left, top);
+                int cm[4][4], fm[4][4], t[4][4];
+                for (int i = 0; i < 16; i++) cm[zz[i][0]][zz[i][1]] = dc[i];
+                for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) { t[i][j] = 0; for (int k = 0; k < 4; k++) t[i][j] += A[i][k] * cm[k][j]; }
+                for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) { fm[i][j] = 0; for (int k = 0; k < 4; k++) fm[i][j] += t[i][k] * A[k][j]; }
+                const int q6 = qp % 6, qd = qp / 6;
+                for (int bi = 0; bi < 16; bi++) {
+                    const int x = blk_x(bi), y = blk_y(bi);
+                    int c4[4][4];
+                    for (int i = 1; i < 16; i++) c4[zz[i][0]][zz[i][1]] = ac[bi][i] * vscale(q6, zz[i][0], zz[i][1]) * (1 << qd);
+                    const int f = fm[y][x] * 16 * vscale(q6, 0, 0);
+                    c4[0][0] = qd >= 6 ? f * (1 << (qd - 6)) : (f + (1 << (5 - qd))) >> (6 - qd);
+                    add_idct(c4, pl[0] + (size_t)(16 * my + 4 * y) * 16 * mb_w + 16 * mx + 4 * x, 16 * mb_w);
+                }
+                const int c6 = qpc % 6, cd = qpc / 6;
+                for (int c = 0; c < 2; c++) {
+                    predict(1 + c, 8, 8 * mx, 8 * my, (int)cmode, left, top);
+                    const int *d = cdc[c];
+                    const int f4[4] = {d[0] + d[1] + d[2] + d[3], d[0] - d[1] + d[2] - d[3], d[0] + d[1] - d[2] - d[3], d[0] - d[1] - d[2] + d[3]};
+                    for (int k = 0; k < 4; k++) {
+                        int c4[4][4];
+                        for (int i = 1; i < 16; i++) c4[zz[i][0]][zz[i][1]] = cac[c][k][i] * vscale(c6, zz[i][0], zz[i][1]) * (1 << cd);
+                        c4[0][0] = (f4[k] * 16 * vscale(c6, 0, 0) * (1 << cd)) >> 5;
+                        add_idct(c4, pl[1 + c] + (size_t)(8 * my + 4 * (k >> 1)) * 8 * mb_w + 8 * mx + 4 * (k & 1), 8 * mb_w);
+                    }
+                }
+                if (b.overrun) return PCAMV_EINVAL;
+            }
+        /* rbsp_slice_trailing_bits: the stop bit, zeros to the end of its byte, nothing but cabac_zero_words-free zeros behind */
+        if (b.pos >= b.nbits || !b.get(1)) return PCAMV_EINVAL;
+        while (b.pos & 7) if (b.get(1)) return PCAMV_EINVAL;
+        while (b.pos < b.nbits) if (b.get(8)) return PCAMV_EINVAL;
+        return 0;
+    }
+};
+}
+/* y / u / v receive the planes tightly packed (16 mb_w x 16 mb_h, half that twice); on failure their contents are unspecified */
+extern "C" int pcamv_gpu_decode_islice_cavlc(const uint8_t *rbsp, size_t len, size_t start_bit, int mb_w, int mb_h, int slice_qp, int chroma_qp_index_offset,
+                                             uint8_t *y, uint8_t *u, uint8_t *v)
+{
+    static const uint8_t qpc_tab[52] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29,
+                                        29, 30, 31, 32, 32, 33, 34, 34, 35, 35, 36, 36, 37, 37, 37, 38, 38, 38, 39, 39, 39, 39};      /* Table 8-15 */
+    if (!rbsp || !y || !u || !v || len < 1 || len > ((size_t)1 << 31) || start_bit >= len * 8 || mb_w < 1 || mb_h < 1 || mb_w > (1 << 16) || mb_h > (1 << 16) ||
+        (long long)mb_w * mb_h > (1 << 20) || slice_qp < 0 || slice_qp > 51 || chroma_qp_index_offset < -12 || chroma_qp_index_offset > 12) return PCAMV_EINVAL;
+    mvsyntax::IDec D;
+    D.b.d = rbsp; D.b.nbits = len * 8; D.b.pos = start_bit; D.b.overrun = 0;
+    D.mb_w = mb_w; D.mb_h = mb_h; D.qp = slice_qp;
+    const int qi = slice_qp + chroma_qp_index_offset;
+    D.qpc = qpc_tab[qi < 0 ? 0 : qi > 51 ? 51 : qi];
+    D.pl[0] = y; D.pl[1] = u; D.pl[2] = v;
+    D.nz = (uint8_t *)calloc((size_t)mb_w * mb_h, 24);
+    if (!D.nz) return PCAMV_ENOMEM;
+    const int rc = D.run();
+    free(D.nz);
+    return rc;
+}
 #endif

@@ -132,8 +132,8 @@ def lib_path():
 
 
 # the library's translation units (csrc/<unit>.hip): the host side with the common kernels, the --me tesa instance of the analysis kernel,
-# the per-diagonal second pass, the two slice writers, and the six builds of the analysis kernel's --subme 6 / 7 instance
-UNITS = ("pcamv_gpu", "pcamv_pass2_diag", "pcamv_slice_write", "pcamv_slice_write_cavlc", "pcamv_tesa", "pcamv_rd", "pcamv_rd_lo", "pcamv_rd_spec", "pcamv_rd_spec2", "pcamv_rd_spec4", "pcamv_rd_tesa")
+# the per-diagonal second pass, the two slice writers, the IDR coder, and the six builds of the analysis kernel's --subme 6 / 7 instance
+UNITS = ("pcamv_gpu", "pcamv_pass2_diag", "pcamv_slice_write", "pcamv_slice_write_cavlc", "pcamv_idr", "pcamv_tesa", "pcamv_rd", "pcamv_rd_lo", "pcamv_rd_spec", "pcamv_rd_spec2", "pcamv_rd_spec4", "pcamv_rd_tesa")
 
 
 def build_library(force=False):
@@ -620,6 +620,91 @@ def param_set_head(params, mb_w, mb_h, sps_id=0, num_ref_frames=1, profile_idc=1
     return bytes(out[:n.value])
 
 
+FEATURE_IDR = 0x1000            # the IDR picture a chain starts with coded on the device: Encoder.encode_idr, Batch.write_stream_idr, decode_idr
+IDR_HDR_BYTES = 24              # room for the longest IDR slice header
+IDR_PROBE_PARAMS = dict(log2_max_frame_num=4, poc_type=0, log2_max_poc_lsb=4, num_ref_idx_l0_default=1, entropy_cabac=0, pic_init_qp=26,
+                        deblocking_filter_control_present=1)     # the parameter sets Encoder.encode_idr writes its header under (+ pps_id)
+
+
+def write_idr_slice_header(params, nal_ref_idc, idr_pic_id, slice_qp):
+    """pcamv_gpu_write_idr_slice_header: (packed bytes, number of bits) of the header of an IDR I slice for a StreamParams -- which must
+    say entropy_cabac 0 and deblocking_filter_control_present 1.  Raises PcamvError with the library's code (-1: a value out of range,
+    -5: weighted prediction, CABAC, or no deblocking control)"""
+    out = np.zeros(IDR_HDR_BYTES, np.uint8)
+    n = C.c_int32()
+    fn = load_library().pcamv_gpu_write_idr_slice_header
+    fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32)]
+    rc = fn(C.byref(params), int(nal_ref_idc), int(idr_pic_id), int(slice_qp), _p(out), len(out), C.byref(n))
+    if rc:
+        raise PcamvError(f"pcamv_gpu_write_idr_slice_header failed: {rc}")
+    return bytes(out[:(n.value + 7) // 8]), n.value
+
+
+def parse_idr_slice_header(rbsp, nal_header, params):
+    """pcamv_gpu_parse_idr_slice_header: (return code, start_bit, slice QP, idr_pic_id) of the IDR I slice header at the start of an RBSP;
+    the last three are -1 when the code is not 0"""
+    buf = np.frombuffer(bytes(rbsp), np.uint8) if len(rbsp) else np.zeros(1, np.uint8)
+    sb, qp, pid = C.c_int64(), C.c_int32(), C.c_int32()
+    fn = load_library().pcamv_gpu_parse_idr_slice_header
+    fn.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    rc = fn(_p(buf), len(rbsp), int(nal_header), C.byref(params), C.byref(sb), C.byref(qp), C.byref(pid))
+    return rc, sb.value, qp.value, pid.value
+
+
+def decode_islice_cavlc(rbsp, start_bit, mb_w, mb_h, slice_qp, chroma_qp_index_offset=0):
+    """pcamv_gpu_decode_islice_cavlc: (return code, (Y, U, V)) of the I slice data at bit start_bit of an RBSP -- Intra16x16 macroblocks,
+    CAVLC, one QP, no loop filter; the planes are None when the code is not 0"""
+    buf = np.frombuffer(bytes(rbsp), np.uint8) if len(rbsp) else np.zeros(1, np.uint8)
+    w, h = 16 * int(mb_w), 16 * int(mb_h)
+    planes = [np.zeros(s, np.uint8) for s in ((h, w), (h // 2, w // 2), (h // 2, w // 2))] if 0 < mb_w <= 65536 and 0 < mb_h <= 65536 and mb_w * mb_h <= 1 << 20 else \
+             [np.zeros((1, 1), np.uint8)] * 3
+    fn = load_library().pcamv_gpu_decode_islice_cavlc
+    fn.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    rc = fn(_p(buf), len(rbsp), int(start_bit), int(mb_w), int(mb_h), int(slice_qp), int(chroma_qp_index_offset), *[_p(p) for p in planes])
+    return rc, (tuple(planes) if rc == 0 else None)
+
+
+def decode_idr(unit, mb_w, mb_h, params=None, chroma_qp_index_offset=0):
+    """the picture of an IDR unit (start code optional) as the library's host decoder reconstructs it: (Y, U, V), and the slice QP and
+    idr_pic_id its header states.  params: the StreamParams of the PPS the slice names (default: those Encoder.encode_idr writes under,
+    with the unit's own pps_id).  Raises PcamvError with the code of the step that failed"""
+    rbsp, ref_idc, typ = nal_to_rbsp(unit)
+    if params is None:
+        # the unit's pps_id: the third ue of the header (first_mb_in_slice, slice_type, pps_id)
+        bits = np.unpackbits(np.frombuffer(rbsp[:16], np.uint8))
+        pos, vals = 0, []
+        for _ in range(3):
+            z = 0
+            while pos < len(bits) and not bits[pos]:
+                z, pos = z + 1, pos + 1
+            v = 0
+            for b in bits[pos:pos + z + 1]:
+                v = 2 * v + int(b)
+            pos += z + 1
+            vals.append(v - 1)
+        params = StreamParams(**dict(IDR_PROBE_PARAMS, pps_id=min(max(vals[2], 0), 255)))
+    rc, sb, qp, pid = parse_idr_slice_header(rbsp, ref_idc << 5 | typ, params)
+    if rc:
+        raise PcamvError(f"pcamv_gpu_parse_idr_slice_header failed: {rc}")
+    rc, planes = decode_islice_cavlc(rbsp, sb, mb_w, mb_h, qp, chroma_qp_index_offset)
+    if rc:
+        raise PcamvError(f"pcamv_gpu_decode_islice_cavlc failed: {rc}")
+    return planes, qp, pid
+
+
+def param_set_head_idr(params, mb_w, mb_h, idr_pps_id=1, sps_id=0, num_ref_frames=1, profile_idc=100, level_idc=30):
+    """the head of a stream whose IDR picture the library writes (Batch.write_stream_idr): param_set_head for the stream's StreamParams,
+    then the PPS unit of the same again with pps_id = idr_pps_id, entropy_cabac 0 and deblocking_filter_control_present 1 -- the PPS
+    the IDR slices name: SPS, PPS, PPS.  Returns the bytes and the StreamParams of the second set."""
+    if int(idr_pps_id) == params.pps_id:
+        raise PcamvError("param_set_head_idr: the IDR pictures' PPS needs an id of its own")
+    second = StreamParams(**{n: getattr(params, n) for n, _ in StreamParams._fields_})
+    second.pps_id, second.entropy_cabac, second.deblocking_filter_control_present = int(idr_pps_id), 0, 1
+    again = param_set_head(second, mb_w, mb_h, sps_id, num_ref_frames, profile_idc, level_idc)
+    pps = again.find(b"\x00\x00\x00\x01", 4)         # behind the SPS unit, which the first head holds already
+    return param_set_head(params, mb_w, mb_h, sps_id, num_ref_frames, profile_idc, level_idc) + again[pps:], second
+
+
 def features():
     """pcamv_gpu_features: mask of FEATURE_* the loaded library has"""
     lib = load_library()
@@ -975,6 +1060,30 @@ class Encoder:
         fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         self._chk(fn(self.ctx, ps, fs, n, _p(rc), _p(nb), _p(bits)), "slice_headers_write_device")
         return rc, nb, bits
+
+    def idr_bound(self, as_nal=True):
+        """pcamv_gpu_idr_bound: a capacity under which no IDR picture of this size fails to be written"""
+        self.lib.pcamv_gpu_idr_bound.restype = C.c_int64
+        self.lib.pcamv_gpu_idr_bound.argtypes = [C.c_void_p, C.c_int]
+        n = self.lib.pcamv_gpu_idr_bound(self.ctx, int(bool(as_nal)))
+        if n < 0:
+            raise PcamvError(f"idr_bound failed ({n})")
+        return int(n)
+
+    def encode_idr(self, qp, pps_id=1, idr_pic_id=0, as_nal=True, cap=None):
+        """pcamv_gpu_encode_idr: this context's current source coded on the device as one IDR I slice (Intra16x16, CAVLC, no loop filter),
+        as bytes -- the unit with start code and emulation prevention, or with as_nal=False the RBSP.  The unfiltered reconstruction
+        becomes the context's reference as after a host set_ref with no previous motion (fetch_recon, ref_planes show it).  The header
+        is written under StreamParams(**IDR_PROBE_PARAMS, pps_id=pps_id) with nal_ref_idc 3.  cap: the capacity offered (default:
+        idr_bound); a unit that does not fit raises (-3)"""
+        if cap is None:
+            cap = self.idr_bound(as_nal)
+        out = np.zeros(max(int(cap), 1), np.uint8)
+        n = C.c_size_t()
+        fn = self.lib.pcamv_gpu_encode_idr
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        self._chk(fn(self.ctx, int(qp), int(pps_id), int(idr_pic_id), int(bool(as_nal)), _p(out), int(cap), C.byref(n)), "encode_idr")
+        return out[:n.value].tobytes()
 
     def slice_bound(self, hdr_bits=0, as_nal=False):
         """pcamv_gpu_slice_bound: a capacity under which no slice of this picture size fails to be written"""
@@ -1474,6 +1583,15 @@ class Batch:
         fn = self.lib.pcamv_gpu_batch_write_stream_step
         fn.argtypes = [C.c_void_p, C.c_void_p]
         self._slice_chk(fn(self.b, C.c_void_p(stream or None)), "batch_write_stream_step")
+
+    def write_stream_idr(self, qp, pps_id=1, idr_pic_id=0, stream=0):
+        """pcamv_gpu_batch_write_stream_idr: every context's current source coded on the device as the IDR picture of its stream --
+        picture 0, behind the head and before the first write_stream_step since the open, which must have first_pic 0 -- and its
+        unfiltered reconstruction installed as the context's reference.  The IDR slices name the PPS pps_id, which the head must hold
+        with entropy_cabac 0 and deblocking control (param_set_head_idr).  No host sync; write_status() afterwards as for a step"""
+        fn = self.lib.pcamv_gpu_batch_write_stream_idr
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        self._slice_chk(fn(self.b, int(qp), int(pps_id), int(idr_pic_id), C.c_void_p(stream or None)), "batch_write_stream_idr")
 
     def stream_written(self):
         """(bytes, pictures, units) per context: the stream's length, the steps since stream_open, the slice units in the stream;
