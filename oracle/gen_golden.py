@@ -243,10 +243,41 @@ def pslice_fixture(name, W, H, me, subme, qp, inter, seed, static, noise=6, fina
     print(name, len(data), "bytes of slice data,", d["nal_escapes"], "emulation prevention bytes,", dict(zip(*np.unique(mbs["type"], return_counts=True))))
 
 
+class Refused(Exception):
+    """a picture the I-slice recipe does not take: change the picture"""
+
+
+def islice_fixture_data(case):
+    """one picture of tests/islice_cases.py as the reference codes it in one I slice of Intra16x16 macroblocks (refh_code_iframe: its
+    analysis with --subme 5 and no I4x4, x264_macroblock_encode, x264_macroblock_write_cavlc; constant QP, no AQ, no loop filter):
+    the second opinion of the product's IDR coder and decoder.  Refused: a macroblock that is not I_16x16, an mb_qp_delta, a level
+    beyond level_prefix 15 (the reference then warns and clips).  The harness never sets h->mb.b_lossless (encoder.c:411 does, and is
+    not linked), so QP 0 is coded with the transform like every other QP."""
+    import islice_cases as isc
+    mb_w, mb_h, qp, off, kind, seed = case
+    planes = isc.picture(kind, mb_w, mb_h, seed)
+    r = refh.Ref(16 * mb_w, 16 * mb_h, qp=qp, me="hex", subme=5, mv_range=64, cabac=0, embed=0, chroma_qp_offset=off)
+    r.set_fenc(*planes)
+    c = r.code_iframe(qp)
+    if c["not_i16x16"] or c["dqp"] or c["warnings"]:
+        raise Refused(f"{isc.name(case)}: {c['not_i16x16']} macroblocks not I_16x16, {c['dqp']} with a QP delta, {c['warnings']} warnings")
+    data = np.frombuffer(r.slice_data(), np.uint8)
+    assert len(data) == (c["bits"] + 8) // 8
+    return dict(mb_w=np.int32(mb_w), mb_h=np.int32(mb_h), qp=np.int32(qp), chroma_offset=np.int32(off), src_y=planes[0], src_u=planes[1], src_v=planes[2],
+                slice_data=data, bits=np.int32(c["bits"]), rec_y=c["rec"][0], rec_u=c["rec"][1], rec_v=c["rec"][2],
+                modes=c["mb"][:, 1:4].astype(np.int32), levels=c["levels"])
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     if not refh.available():
         sys.exit("oracle/_ref/libpcamv_ref.so missing: run `make -C oracle ref` where /root/reference exists")
+    if "--islice-only" in sys.argv:            # tests/islice_cases.py: the reference's Intra16x16 CAVLC I slices
+        import islice_cases as isc
+        for case in isc.CASES:
+            np.savez_compressed(isc.path(case), **islice_fixture_data(case))
+            print(isc.name(case), os.path.getsize(isc.path(case)), "bytes")
+        sys.exit(0)
     if "--pslice-only" in sys.argv:
         pslice_fixture("pslice_qcif_hex_subme5_final", 176, 144, "hex", 5, 26, 0x1 | 0x100, 5, 48, final=True)
         pslice_fixture("pslice_cif_umh_subme7_final", 352, 288, "umh", 7, 26, 0x1 | 0x100, 6, 96, final=True)

@@ -380,6 +380,78 @@ int refh_slice_data(void *ctx, uint8_t *buf, int cap)
     return n;
 }
 
+/* One picture as one I slice of Intra16x16 macroblocks through the reference's own analysis, macroblock coder and CAVLC writer: the
+ * second opinion of the product's IDR coder and decoder (tests/golden/islice_ref_*.npz).  The caller's context is a CAVLC one without
+ * embedding, at --subme below 6 (no RD decision); h->param.analyse.intra = 0 leaves x264_mb_analyse_intra nothing but the four 16x16
+ * modes.  No loop filter runs: rec_* is the unfiltered reconstruction.  Per macroblock: mb[4] = the reference's type, Intra16x16PredMode
+ * and intra_chroma_pred_mode in the standard's numbering, coded block pattern (luma | chroma << 4); lev[384] = the levels the slice
+ * codes in scan order, from h->dct: Intra16x16DCLevel 16, the sixteen luma AC blocks 15 each by luma4x4BlkIdx, Cb DC 4, Cr DC 4, the
+ * four Cb then the four Cr AC blocks 15 each (blocks the slice codes as empty are zero).  info[4] = slice-data bits before the
+ * trailing bits, macroblocks that are not I_16x16, macroblocks whose QP is not the slice's, warnings the reference logged (its CAVLC
+ * writer warns of a level beyond level_prefix 15).  refh_slice_data afterwards returns the bytes. */
+static int refh_warnings;
+static void refh_log_count(void *p, int level, const char *fmt, va_list ap) { if (level <= X264_LOG_WARNING) refh_warnings++; refh_log(p, level, fmt, ap); }
+int refh_code_iframe(void *ctx, int qp, int32_t *mb, int16_t *lev, int32_t *info, uint8_t *rec_y, uint8_t *rec_u, uint8_t *rec_v)
+{
+    refh_t *c = ctx; x264_t *h = c->h;
+    if (h->param.b_cabac || h->param.eparam.iEmRate != 0) return -1;
+    const unsigned keep_intra = h->param.analyse.intra;
+    h->param.analyse.intra = 0;
+    h->param.pf_log = refh_log_count; refh_warnings = 0;
+    h->sh.i_type = SLICE_TYPE_I;
+    h->sh.i_first_mb = 0; h->sh.i_last_mb = h->mb.i_mb_count;
+    h->sh.b_mbaff = 0; h->sh.i_num_ref_idx_l0_active = 1; h->sh.i_qp = qp;
+    h->sh.i_disable_deblocking_filter_idc = 1;
+    h->i_ref0 = 0; h->i_ref1 = 0;
+    h->mb.pic.i_fref[0] = 0; h->mb.pic.i_fref[1] = 0;
+    h->fdec->i_poc = 0; h->fdec->b_kept_as_ref = 1; h->fdec->i_frame = 0;
+    h->fenc->i_poc = 0;
+    h->info.embed_flag = 0; h->info.firstTime = 1;
+    x264_macroblock_slice_init(h);
+    x264_ratecontrol_start(h, qp + 1);
+    memset(&h->stat.frame, 0, sizeof(h->stat.frame));
+    h->mb.i_last_qp = qp; h->mb.i_last_dqp = 0;
+    bs_init(&h->out.bs, h->out.p_bitstream, h->out.i_bitstream);
+    info[1] = info[2] = 0;
+    for (int my = 0; my < c->mb_h; my++)
+        for (int mx = 0; mx < c->mb_w; mx++) {
+            int mb_xy = my * c->mb_w + mx;
+            if (mx == 0) refh_row_start(h, my);
+            x264_macroblock_cache_load(h, mx, my);
+            x264_macroblock_analyse(h);
+            x264_macroblock_encode(h);
+            if (h->out.bs.p > h->out.bs.p_end - 4096) return -2;
+            x264_macroblock_write_cavlc(h, &h->out.bs);
+            int32_t *o = mb + 4 * mb_xy; int16_t *l = lev + 384 * mb_xy;
+            memset(l, 0, 384 * sizeof(int16_t));
+            o[0] = h->mb.i_type;
+            if (h->mb.i_type != I_16x16) { info[1]++; o[1] = o[2] = o[3] = -1; x264_macroblock_cache_save(h); continue; }
+            if (h->mb.i_qp != qp) info[2]++;
+            o[1] = x264_mb_pred_mode16x16_fix[h->mb.i_intra16x16_pred_mode];
+            o[2] = x264_mb_pred_mode8x8c_fix[h->mb.i_chroma_pred_mode];
+            o[3] = h->mb.i_cbp_luma | h->mb.i_cbp_chroma << 4;
+            /* a block whose count in the non-zero cache is 0 is coded as "no coefficient" whatever h->dct still holds from an earlier macroblock */
+#define REFH_NZ(i) h->mb.cache.non_zero_count[x264_scan8[i]]
+            if (REFH_NZ(24)) memcpy(l, h->dct.luma16x16_dc, 16 * sizeof(int16_t));
+            if (h->mb.i_cbp_luma) for (int i = 0; i < 16; i++) if (REFH_NZ(i)) memcpy(l + 16 + 15 * i, h->dct.luma4x4[i] + 1, 15 * sizeof(int16_t));
+            if (h->mb.i_cbp_chroma) for (int i = 0; i < 2; i++) if (REFH_NZ(25 + i)) memcpy(l + 256 + 4 * i, h->dct.chroma_dc[i], 4 * sizeof(int16_t));
+            if (h->mb.i_cbp_chroma & 2) for (int i = 0; i < 8; i++) if (REFH_NZ(16 + i)) memcpy(l + 264 + 15 * i, h->dct.luma4x4[16 + i] + 1, 15 * sizeof(int16_t));
+#undef REFH_NZ
+            x264_macroblock_cache_save(h);
+        }
+    c->tail_skip = 0;
+    info[0] = bs_pos(&h->out.bs);
+    info[3] = refh_warnings;
+    h->param.analyse.intra = keep_intra; h->param.pf_log = refh_log;
+    x264_frame_t *f = h->fdec;
+    for (int y = 0; y < c->height; y++) memcpy(rec_y + (size_t)y * c->width, f->plane[0] + (size_t)y * f->i_stride[0], c->width);
+    for (int y = 0; y < c->height / 2; y++) {
+        memcpy(rec_u + (size_t)y * c->width / 2, f->plane[1] + (size_t)y * f->i_stride[1], c->width / 2);
+        memcpy(rec_v + (size_t)y * c->width / 2, f->plane[2] + (size_t)y * f->i_stride[2], c->width / 2);
+    }
+    return 0;
+}
+
 /* Pass 2 of the fork's two-pass P frame (encoder.c:2380-2390 re-enters x264_slice_write with firstTime = 0):
  * x264_macroblock_analyse forces type / partition / MVs from h->info.cache and swaps in mv_stego where
  * h->info.filp says so (analyse.c:2574-2577, 2658-2679, 2870-3107), x264_macroblock_encode reconstructs,

@@ -38,6 +38,12 @@ def available():
     return os.path.exists(LIB_PATH)
 
 
+def has(entry):
+    """whether the library present was built from a harness that has the entry point: a prebuilt library carried to a place without
+    the reference tree stays as old as the harness it was built from"""
+    return available() and hasattr(lib(), entry)
+
+
 _lib = None
 
 
@@ -122,6 +128,20 @@ class Ref:
         if nmv < 0:
             raise RuntimeError("refh_pass2_pframe failed")
         return mbs, nnz, tuple(planes[:3]), tuple(planes[3:]), nmv
+
+    def code_iframe(self, qp=None):
+        """the picture set by set_fenc as one I slice of Intra16x16 macroblocks (refh_code_iframe; a CAVLC context without embedding):
+        dict of mb [n][4] (the reference's type, luma mode, chroma mode, cbp), levels [n][384], bits, not_i16x16, dqp, warnings, rec"""
+        n = self.mb_w * self.mb_h
+        mb = np.zeros((n, 4), np.int32)
+        lev = np.zeros((n, 384), np.int16)
+        info = np.zeros(4, np.int32)
+        rec = [np.zeros((self.h >> s, self.w >> s), np.uint8) for s in (0, 1, 1)]
+        lib().refh_code_iframe.restype = C.c_int
+        rc = lib().refh_code_iframe(self.ctx, self.qp if qp is None else qp, _p(mb), _p(lev), _p(info), *[_p(a) for a in rec])
+        if rc:
+            raise RuntimeError(f"refh_code_iframe: {rc}")
+        return dict(mb=mb, levels=lev, bits=int(info[0]), not_i16x16=int(info[1]), dqp=int(info[2]), warnings=int(info[3]), rec=tuple(rec))
 
     def slice_data(self):
         """bytes the reference's entropy coder wrote for the frame analysed / re-encoded last: CABAC from the first mb_skip_flag on,

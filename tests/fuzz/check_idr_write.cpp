@@ -6,10 +6,15 @@
  * macroblocks' bit counts and the header's add up to the prefix's total and to the RBSP's length; no level went past the clamp (the
  * writer's own clip never fired); a block one byte short gives PCAMV_ENOMEM.  Then the decoder is fed damaged and truncated slices.
  *
- * usage: check_idr_write <cases.bin> <out.bin> <fuzz iterations per case>      (the case file: tests/idr_cases.py write_case_file)
+ * usage: check_idr_write <cases.bin> <out.bin> <fuzz iterations per case> [<streams.bin>]      (the case file: tests/idr_cases.py write_case_file)
  * prints one line per case "<index> <rc> <unit bytes> <rbsp bytes> <levels clamped> <00 00 0x in the RBSP> <mode of macroblock (1,1) or -1>"
  * and a summary "cases <n> bad <n> clamped <n> emulation <n>"; out.bin receives per case int64 length + the unit, then the coder's
- * reconstruction.  Exit status 1 on any failure, 2 for a file that is no case file. */
+ * reconstruction.  Exit status 1 on any failure, 2 for a file that is no case file.
+ *
+ * streams.bin (tests/test_idr_cpu.py writes it from tests/golden/islice_ref_*.npz): I slices another coder made, with the planes that coder
+ * reconstructed -- int32 count, then per stream int32 mb_w, mb_h, qp, chroma offset, start bit, bytes; the bytes; Y, U, V.  Each is decoded
+ * from a heap block of exactly its size and must give those planes: "ref <index> <rc> <planes equal>" per stream and "refs <n> bad <n>",
+ * printed before the cases' lines. */
 #include "slice_write_cavlc_host.h"
 #include "pcamv_idr.h"
 #include "pcamv_mvsyntax.h"
@@ -30,7 +35,27 @@ int main(int argc, char **argv)
     uint8_t *tab = (uint8_t *)malloc(SV_TAB_BYTES);
     if (sv_build_tables(tab)) return 2;
     std::mt19937 rng(11);
-    long bad = 0, clamped_cases = 0, emul_cases = 0;
+    long bad = 0, ref_bad = 0, clamped_cases = 0, emul_cases = 0;
+    if (argc > 4) {
+        FILE *fr = fopen(argv[4], "rb");
+        int32_t n = 0;
+        if (!fr || fread(&n, 4, 1, fr) != 1 || n < 0) return 2;
+        for (int k = 0; k < n; k++) {
+            int32_t h[6];
+            if (fread(h, 4, 6, fr) != 6 || h[0] < 1 || h[1] < 1 || h[0] * h[1] > 4096 || h[4] < 0 || h[5] < 1 || h[5] > (1 << 24)) return 2;
+            const size_t ysz = (size_t)256 * h[0] * h[1];
+            std::vector<uint8_t> data((size_t)h[5]), want[3] = {std::vector<uint8_t>(ysz), std::vector<uint8_t>(ysz / 4), std::vector<uint8_t>(ysz / 4)};
+            if (fread(data.data(), 1, data.size(), fr) != data.size()) return 2;
+            for (auto &w : want) if (fread(w.data(), 1, w.size(), fr) != w.size()) return 2;
+            std::vector<uint8_t> dy(ysz), du(ysz / 4), dv(ysz / 4);
+            const int rc = pcamv_gpu_decode_islice_cavlc(data.data(), data.size(), (size_t)h[4], h[0], h[1], h[2], h[3], dy.data(), du.data(), dv.data());
+            const int same = !rc && dy == want[0] && du == want[1] && dv == want[2];
+            printf("ref %d %d %d\n", k, rc, same);
+            ref_bad += !same;
+        }
+        fclose(fr);
+        printf("refs %d bad %ld\n", (int)n, ref_bad);
+    }
     for (int k = 0; k < count; k++) {
         Case c;
         if (fread(&c.mb_w, 4, 8, f) != 8 || fread(c.hdr, 1, IDR_HDR_BYTES, f) != IDR_HDR_BYTES) return 2;
@@ -107,5 +132,5 @@ int main(int argc, char **argv)
     fclose(f); fclose(fo);
     free(tab);
     printf("cases %d bad %ld clamped %ld emulation %ld\n", count, bad, clamped_cases, emul_cases);
-    return bad ? 1 : 0;
+    return bad || ref_bad ? 1 : 0;
 }

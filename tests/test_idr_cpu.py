@@ -3,13 +3,29 @@
 independent host decoder.  The decoded planes must equal the coder's own reconstruction byte for byte and the bit total the prefix's; the
 level clamp must be reached (the 0 / 255 checkerboard at QP 0 is such an input) and never exceeded; at least one RBSP must hold 00 00 0x,
 so that emulation prevention is exercised; the ramps must pick the horizontal, the vertical and the plane mode; and the decoder must
-survive damaged, truncated and random bytes without a sanitizer report."""
+survive damaged, truncated and random bytes without a sanitizer report.  The same program, in the same run, decodes the reference's I
+slices (tests/golden/islice_ref_*.npz, at bit 0 and behind a header of 5 bits) and must arrive at the reference's planes."""
+import struct
 import subprocess
 
+import numpy as np
 import pytest
 
 import idr_cases as ic
+import islice_cases as isc
 import pcamv_amd
+
+
+def _write_ref_streams(path):
+    """the reference's I slices for check_idr_write's fourth argument; returns how many"""
+    entries = []
+    for case, fx in isc.fixtures():
+        data = fx["slice_data"].tobytes()
+        for buf, sb in ((data, 0), (isc.shifted(data, 5), 5)):
+            entries.append(struct.pack("<6i", case[0], case[1], case[2], case[3], sb, len(buf)) + buf + b"".join(np.ascontiguousarray(fx[k]).tobytes() for k in ("rec_y", "rec_u", "rec_v")))
+    with open(path, "wb") as f:
+        f.write(struct.pack("<i", len(entries)) + b"".join(entries))
+    return len(entries)
 
 
 @pytest.fixture(scope="module")
@@ -22,7 +38,12 @@ def run(tmp_path_factory):
         cases.append(dict(mb_w=mb_w, mb_h=mb_h, qp=qp, dz=11, chroma_offset=(0, -2, 3)[len(cases) % 3], planes=ic.picture(kind, mb_w, mb_h), hdr=hdr, hdr_bits=n,
                           nal_byte=0x65, kind=kind))
     ic.write_case_file(d / "cases.bin", cases)
-    r = subprocess.run([exe, str(d / "cases.bin"), str(d / "out.bin"), "40"], capture_output=True, text=True, timeout=900)
+    n_ref = _write_ref_streams(d / "streams.bin")
+    r = subprocess.run([exe, str(d / "cases.bin"), str(d / "out.bin"), "40", str(d / "streams.bin")], capture_output=True, text=True, timeout=900)
+    # the reference streams' lines come first and go their own way; what is left is the cases' report
+    lines = r.stdout.splitlines()
+    r.ref_lines, r.n_ref = [ln for ln in lines if ln.startswith("ref")], n_ref
+    r.stdout = "\n".join(ln for ln in lines if not ln.startswith("ref")) + "\n"
     return cases, r
 
 
@@ -38,6 +59,15 @@ def test_coder_and_decoder_agree_under_sanitizers(run):
         assert rc == 0, (k, rc, c["kind"], c["mb_w"], c["mb_h"], c["qp"])
         assert unit >= rbsp + 5
     assert lines[-1].startswith(f"cases {len(cases)} bad 0 ")
+
+
+def test_decoder_reads_the_reference_streams_under_sanitizers(run):
+    cases, r = run
+    assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-3000:]
+    assert r.n_ref == 2 * len(isc.CASES) and len(r.ref_lines) == r.n_ref + 1, r.ref_lines[-3:]
+    for k, ln in enumerate(r.ref_lines[:-1]):
+        assert ln.split() == ["ref", str(k), "0", "1"], (ln, isc.name(isc.CASES[k // 2]), "start bit", 5 * (k % 2))
+    assert r.ref_lines[-1] == f"refs {r.n_ref} bad 0"
 
 
 def test_clamp_is_reached_by_the_checkerboard_at_qp0(run):
