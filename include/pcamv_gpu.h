@@ -297,9 +297,20 @@ int pcamv_gpu_fetch_results(pcamv_ctx_t *ctx, pcamv_mb_t *out_mb, pcamv_embed_t 
 int  pcamv_gpu_batch_create(pcamv_ctx_t *const *ctxs, int n, pcamv_batch_t **batch);
 void pcamv_gpu_batch_destroy(pcamv_batch_t *batch);
 int  pcamv_gpu_batch_step(pcamv_batch_t *batch, int qp, float emrate, void *stream);
-/* kernel: the dominant kernel's name (below), or one of "k_embed_prepare", "k_extract_prepare", "k_extract_bits", "k_payload_check",
- * "k_message_count", "k_message_plan", "k_message_jobs", "k_extract_chain_message", "k_message_check" (the two kernels of a check under one timer) */
-int  pcamv_gpu_batch_kernel_time(pcamv_batch_t *batch, const char *kernel, double *avg_ms, int *launches, int reset);    /* ... or "k_parse_pslice", "k_parse_pslice_cavlc" */
+/* The time of one of the batch's timed kernels: the average over its launches since the last reset, and their number.  Synchronises.
+ * kernel: the dominant kernel's name (pcamv_gpu_batch_dominant_kernel, below), or one of the 40 that follow -- the list the library
+ * keeps as PCAMV_TIMERS in csrc/pcamv_gpu.hip; any other name is PCAMV_EINVAL:
+ *   the embedding and the receiving side: "k_embed_prepare", "k_extract_prepare", "k_extract_bits", "k_payload_check",
+ *     "k_extract_count", "k_extract_chain";
+ *   slices and NAL units: "k_parse_pslice", "k_parse_pslice_cavlc", "k_write_pslice", "k_write_pslice_cavlc", "k_nal_to_rbsp";
+ *   byte streams received: "k_stream_plan", "k_stream_scan", "k_stream_prefix" (with the three kernels of a video's prefix),
+ *     "k_stream_place", "k_stream_unit", "k_slice_header", "k_slice_header_sets", "k_stream_status", "k_stream_window_unit",
+ *     "k_pset_unit", "k_pset_parse", "k_pset_resolve", "k_video_cut";
+ *   byte streams written: "k_stream_open", "k_stream_open_heads", "k_stream_slot", "k_stream_commit", "k_stream_join",
+ *     "k_stream_copy_plan", "k_stream_copy", "k_idr_mb", "k_idr_prefix", "k_idr_pack", "k_idr_unit";
+ *   one message for the batch: "k_message_count", "k_message_plan", "k_message_jobs", "k_extract_chain_message",
+ *     "k_message_check" (the two kernels of a check under one timer) */
+int  pcamv_gpu_batch_kernel_time(pcamv_batch_t *batch, const char *kernel, double *avg_ms, int *launches, int reset);
 const char *pcamv_gpu_batch_last_error(const pcamv_batch_t *batch);
 /* Closed loop on the device: with on != 0 every batch step ends with pass 2 + the loop filter (embedding must be
  * on: the flip map comes from it), leaving each context's deblocked reconstruction in its device planes

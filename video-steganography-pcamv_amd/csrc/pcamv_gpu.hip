@@ -26,13 +26,27 @@
 #define NEV 32                 /* launches the analysis kernel's timer remembers between two kernel_time calls ... */
 #define NRING 8
 #define NKEV 16                /* ... and a timer of the smaller kernels */
-enum { KT_ANALYSE, KT_EMBED_PREPARE, KT_EXTRACT_PREPARE, KT_EXTRACT_BITS, KT_PAYLOAD_CHECK, KT_PARSE_PSLICE, KT_PARSE_PSLICE_CAVLC, KT_WRITE_PSLICE, KT_WRITE_PSLICE_CAVLC, KT_NAL_TO_RBSP,
-       KT_STREAM_PLAN, KT_STREAM_SCAN, KT_STREAM_PREFIX, KT_STREAM_PLACE, KT_STREAM_UNIT, KT_SLICE_HEADER, KT_STREAM_STATUS,
-       KT_STREAM_OPEN, KT_STREAM_SLOT, KT_STREAM_COMMIT, KT_STREAM_WINDOW_UNIT, KT_EXTRACT_COUNT, KT_EXTRACT_CHAIN,
-       KT_PSET_UNIT, KT_PSET_PARSE, KT_PSET_RESOLVE, KT_SLICE_HEADER_SETS,
-       KT_STREAM_OPEN_HEADS, KT_STREAM_JOIN, KT_STREAM_COPY_PLAN, KT_STREAM_COPY, KT_VIDEO_CUT,
-       KT_MESSAGE_COUNT, KT_MESSAGE_PLAN, KT_MESSAGE_JOBS, KT_EXTRACT_CHAIN_MESSAGE, KT_MESSAGE_CHECK,
-       KT_IDR_MB, KT_IDR_PREFIX, KT_IDR_PACK, KT_IDR_UNIT, KT_N };
+/* The timed kernels, stated here only: X(timer, the name pcamv_gpu_batch_kernel_time knows it by); the enum and the table of names
+ * (kt_name) are made from the list, so a timer has its place in both or in neither.  KT_ANALYSE goes by the name of the batch's
+ * instance of the analysis kernel (dominant_kernel) */
+#define PCAMV_TIMERS(X) \
+    X(KT_ANALYSE, NULL) \
+    X(KT_EMBED_PREPARE, "k_embed_prepare") X(KT_EXTRACT_PREPARE, "k_extract_prepare") X(KT_EXTRACT_BITS, "k_extract_bits") \
+    X(KT_PAYLOAD_CHECK, "k_payload_check") X(KT_PARSE_PSLICE, "k_parse_pslice") X(KT_PARSE_PSLICE_CAVLC, "k_parse_pslice_cavlc") \
+    X(KT_WRITE_PSLICE, "k_write_pslice") X(KT_WRITE_PSLICE_CAVLC, "k_write_pslice_cavlc") X(KT_NAL_TO_RBSP, "k_nal_to_rbsp") \
+    X(KT_STREAM_PLAN, "k_stream_plan") X(KT_STREAM_SCAN, "k_stream_scan") X(KT_STREAM_PREFIX, "k_stream_prefix") \
+    X(KT_STREAM_PLACE, "k_stream_place") X(KT_STREAM_UNIT, "k_stream_unit") X(KT_SLICE_HEADER, "k_slice_header") \
+    X(KT_STREAM_STATUS, "k_stream_status") X(KT_STREAM_OPEN, "k_stream_open") X(KT_STREAM_SLOT, "k_stream_slot") \
+    X(KT_STREAM_COMMIT, "k_stream_commit") X(KT_STREAM_WINDOW_UNIT, "k_stream_window_unit") X(KT_EXTRACT_COUNT, "k_extract_count") \
+    X(KT_EXTRACT_CHAIN, "k_extract_chain") X(KT_PSET_UNIT, "k_pset_unit") X(KT_PSET_PARSE, "k_pset_parse") \
+    X(KT_PSET_RESOLVE, "k_pset_resolve") X(KT_SLICE_HEADER_SETS, "k_slice_header_sets") X(KT_STREAM_OPEN_HEADS, "k_stream_open_heads") \
+    X(KT_STREAM_JOIN, "k_stream_join") X(KT_STREAM_COPY_PLAN, "k_stream_copy_plan") X(KT_STREAM_COPY, "k_stream_copy") \
+    X(KT_VIDEO_CUT, "k_video_cut") X(KT_MESSAGE_COUNT, "k_message_count") X(KT_MESSAGE_PLAN, "k_message_plan") \
+    X(KT_MESSAGE_JOBS, "k_message_jobs") X(KT_EXTRACT_CHAIN_MESSAGE, "k_extract_chain_message") X(KT_MESSAGE_CHECK, "k_message_check") \
+    X(KT_IDR_MB, "k_idr_mb") X(KT_IDR_PREFIX, "k_idr_prefix") X(KT_IDR_PACK, "k_idr_pack") X(KT_IDR_UNIT, "k_idr_unit")
+#define KT_ENUM(id, name) id,
+enum { PCAMV_TIMERS(KT_ENUM) KT_N };
+#undef KT_ENUM
 #define PCAMV_FEATURES (PCAMV_FEATURE_PAYLOAD | PCAMV_FEATURE_SLICE_PARSER | PCAMV_FEATURE_SLICE_PARSER_CAVLC | PCAMV_FEATURE_SLICE_WRITER | \
                         PCAMV_FEATURE_SLICE_WRITER_CAVLC | PCAMV_FEATURE_NAL_DEVICE | PCAMV_FEATURE_STREAM_DEVICE | PCAMV_FEATURE_STREAM_WRITER | \
                         PCAMV_FEATURE_STREAM_WINDOW | PCAMV_FEATURE_PARAM_SETS | PCAMV_FEATURE_VIDEO | PCAMV_FEATURE_MESSAGE | PCAMV_FEATURE_IDR)
@@ -63,26 +77,67 @@ struct RdBuild {
 #define RD_ROW(id, occ, variant) {rd_build_spec(RD_##id), pcamv_launch_flow_rd<RD_##id>, pcamv_flow_rd_waves_per_cu<RD_##id>, RD_PROF_FN(id)},
 static const RdBuild rd_builds[RD_N_BUILDS] = {PCAMV_RD_BUILDS(RD_ROW)};
 
-/* one ring of NRING descriptor slots: a slot is written again only after the work that read it last (its event) is done */
-struct DescRing { int head, used[NRING]; hipEvent_t done[NRING]; };
+/* the error text of a context or of a batch */
+template <class Owner> static int fail(Owner *o, int code, const char *fmt, ...)
+{
+    if (o) { va_list ap; va_start(ap, fmt); vsnprintf(o->err, sizeof(o->err), fmt, ap); va_end(ap); }
+    return code;
+}
+#define HIPCHK(o, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(o, PCAMV_EHIP, "%s: %s", #call, hipGetErrorString(e_)); } while (0)
+#define TRY(call) do { const int rc_ = (call); if (rc_) return rc_; } while (0)
+
+template <class T> static hipError_t dalloc(T **p, size_t n) { return hipMalloc((void **)p, n * sizeof(T)); }
+/* Memory with one owner -- a batch or one of its parts, or the scope of a call -- which frees it when it goes: `cap` elements on the
+ * device (DevBuf), or in pinned host memory (PinBuf).  Pointers into somebody else's memory stay plain pointers.
+ * room() grows it and never shrinks it.  Freeing waits for the device, so a room() that may grow belongs in calls that may wait: creation,
+ * index calls, stream_window, stream_param_sets, set_message, the reserve calls, the opens and idr_setup behind their synchronisation,
+ * probes.  On the paths that queue work and return (steps, extract calls, write calls) it stands only where it finds its room, or
+ * makes it once for good (a batch's first extraction, a staging buffer outgrown: stage_take) */
+template <class T, bool PINNED = false> struct DevBuf {
+    T *p = NULL; size_t cap = 0;
+    DevBuf() = default; DevBuf(const DevBuf &) = delete; DevBuf &operator=(const DevBuf &) = delete; ~DevBuf() { release(); }
+    void release() { if (p) PINNED ? hipHostFree(p) : hipFree(p); p = NULL; cap = 0; }
+    /* oom: the owner's code for a device without memory left */
+    template <class Owner> int room(Owner *o, size_t n, int oom = PCAMV_EHIP)
+    {
+        if (p && n <= cap) return 0;
+        release();
+        const hipError_t e = PINNED ? hipHostMalloc((void **)&p, (n ? n : 1) * sizeof(T), hipHostMallocDefault) : dalloc(&p, n ? n : 1);
+        if (e != hipSuccess) return fail(o, e == hipErrorOutOfMemory ? oom : PCAMV_EHIP, "%zu bytes of %s memory: %s", n * sizeof(T), PINNED ? "pinned host" : "device", hipGetErrorString(e));
+        cap = n;
+        return 0;
+    }
+    operator T *() const { return p; }
+};
+template <class T> using PinBuf = DevBuf<T, true>;
+
+/* a ring of N slots taken in turn (ring_take, ring_release): a slot is written again only after the work that read it last (its event,
+ * made when the slot is first taken) is done */
+template <int N> struct EvRing {
+    int head = 0, used[N] = {}; hipEvent_t done[N] = {};
+    EvRing() = default; EvRing(const EvRing &) = delete;
+    ~EvRing() { for (hipEvent_t e : done) if (e) hipEventDestroy(e); }
+};
 /* hipEvents around the launches of one kernel, summed when pcamv_gpu_batch_kernel_time asks for it by name: a ring of the last `cap`
  * launches; one pair of events stands for `weight` launches (the anti-diagonals of PCAMV_SCHED=diag share a pair) */
-struct KTimer { hipEvent_t e0[NEV], e1[NEV]; int cap, weight, made, n, head, launches; double ms; };
+struct KTimer {
+    hipEvent_t e0[NEV], e1[NEV]; int cap, weight, made, n, head, launches; double ms;
+    ~KTimer() { for (int i = 0; i < NEV; i++) { if (e0[i]) hipEventDestroy(e0[i]); if (e1[i]) hipEventDestroy(e1[i]); } }
+};
 /* NSTAGE staging buffers taken in turn, each a pinned host block and its device copy made by the calls themselves (stage_take): a buffer
  * is filled again only after the work that read it last (its event) is done, so a call waits for the one before the last.  A ring
- * that only kernels fill (nal_stage) has no host blocks */
-struct StageRing { uint8_t *h[NSTAGE], *d[NSTAGE]; size_t cap[NSTAGE]; hipEvent_t done[NSTAGE]; int used[NSTAGE], head; };
+ * that only kernels fill (nal_stage, su_stage) has no host blocks */
+struct StageRing { EvRing<NSTAGE> ring; PinBuf<uint8_t> h[NSTAGE]; DevBuf<uint8_t> d[NSTAGE]; };
 
 /* the index of n byte streams (k_stream_plan .. k_stream_place): the library's copy of their placement, the working memory of the
  * scan, the tables; for a batch also what its steps need -- the borrowed buffer and the size of an RBSP slot */
 struct StreamIndex {
     int n, ready;
     long long max_units, stride, max_chunks;
-    long long *d_at;            /* [off n][len n][chunk_base n][n_units n][n_slices n][cursor n] */
-    int *d_bad; unsigned long long *d_longest; SiChunk *d_chunks; pcamv_unit_t *d_table; uint8_t *d_own;
-    size_t cap_n, cap_chunks, cap_table, cap_own;
-    const uint8_t *bytes; long long bytes_size, slot;
-    SiChunk *d_keep; size_t cap_keep;   /* a video's index (video_units_run): the chunks' summaries as the first scan left them */
+    DevBuf<long long> d_at;     /* [off n][len n][chunk_base n][n_units n][n_slices n][cursor n] */
+    DevBuf<int> d_bad; DevBuf<unsigned long long> d_longest; DevBuf<SiChunk> d_chunks; DevBuf<pcamv_unit_t> d_table; DevBuf<uint8_t> d_own;
+    const uint8_t *bytes; long long bytes_size, slot;       /* (borrowed: the caller's buffer, or d_own) */
+    DevBuf<SiChunk> d_keep;     /* a video's index (video_units_run): the chunks' summaries as the first scan left them */
 };
 
 /* the parameter sets of n indexed streams (k_pset_unit, k_pset_parse, k_pset_resolve): the tables of their units of type 7 / 8, the
@@ -90,10 +145,8 @@ struct StreamIndex {
  * from a stream_param_sets call to the next index call */
 struct StreamSets {
     int ready;
-    pcamv_unit_t *d_table; long long *d_cnt; pcamv_param_sets_t *d_sets;       /* d_cnt: [n_units n][count n][u_base n + 1] */
-    size_t cap_table, cap_cnt, cap_sets;
-    long long *d_len; int *d_map; PsRec *d_rec; uint8_t *d_slots;               /* d_map: [u_stream U][u_index U][nal_header U][first U] */
-    size_t cap_len, cap_map, cap_rec, cap_slots;
+    DevBuf<pcamv_unit_t> d_table; DevBuf<long long> d_cnt; DevBuf<pcamv_param_sets_t> d_sets;   /* d_cnt: [n_units n][count n][u_base n + 1] */
+    DevBuf<long long> d_len; DevBuf<int> d_map; DevBuf<PsRec> d_rec; DevBuf<uint8_t> d_slots;  /* d_map: [u_stream U][u_index U][nal_header U][first U] */
 };
 
 /* the byte streams a batch writes (pcamv_gpu_batch_stream_open): the borrowed buffer and length array, the settings every picture shares,
@@ -101,11 +154,11 @@ struct StreamSets {
  * k_stream_slot, the writer and k_stream_commit */
 struct StreamOut {
     int ready;
-    uint8_t *bytes; long long bytes_size; long long *len;
+    uint8_t *bytes; long long bytes_size; long long *len;       /* (borrowed: the caller's) */
     SwsSetup S;
-    uint8_t *d_own; size_t cap_own;     /* [SwsCtx n][w_off n][w_cap n][w_len n][off n][cap n][first n][table: n entries, n slots] */
-    uint8_t *d_head; size_t cap_head;
-    uint8_t *d_copy; size_t cap_copy;   /* the copy launches of stream_open_heads and join_streams: [VcJob n][chunk_base n + 1][head_off n][head_len n][join status] */
+    DevBuf<uint8_t> d_own;              /* [SwsCtx n][w_off n][w_cap n][w_len n][off n][cap n][first n][table: n entries, n slots] */
+    DevBuf<uint8_t> d_head;
+    DevBuf<uint8_t> d_copy;             /* the copy launches of stream_open_heads and join_streams: [VcJob n][chunk_base n + 1][head_off n][head_len n][join status] */
     int joined;                         /* a join was queued since the open: its status is there to be read */
     int stepped;                        /* a write_stream_step or a write_stream_idr was queued since the open: an IDR picture no longer belongs here */
 };
@@ -116,11 +169,12 @@ struct StreamOut {
  * Job i * k_call + w of a call is slot w of context i, and that job's memory is entry i * k_call + w of every array here */
 struct StreamWindow {
     int k, k_last;              /* slots reserved per context; slots of the last window call */
-    pcamv_mb_t *d_mbs; uint8_t *d_stego; int *d_hdr; unsigned *d_cols; int *d_stat; uint8_t *d_scratch;
-    uint8_t *d_jobs; size_t cap_jobs;
-    long long *d_cursor_was;
-    ExtractDev *h_X, *d_X; hipEvent_t desc_done[NSTAGE]; int desc_used[NSTAGE], head;
+    DevBuf<pcamv_mb_t> d_mbs; DevBuf<uint8_t> d_stego; DevBuf<int> d_hdr; DevBuf<unsigned> d_cols; DevBuf<int> d_stat; DevBuf<uint8_t> d_scratch;
+    DevBuf<uint8_t> d_jobs;
+    DevBuf<long long> d_cursor_was;
+    PinBuf<ExtractDev> h_X; DevBuf<ExtractDev> d_X; EvRing<NSTAGE> desc;
     hipEvent_t done; int used;  /* behind the last window call: the next one's stream waits for it, since they share the slots */
+    ~StreamWindow() { if (done) hipEventDestroy(done); }
 };
 
 struct pcamv_ctx;
@@ -130,22 +184,22 @@ struct pcamv_batch {
     int n, device, n_diag, slots_per_mb, max_diag;
     int W, H;
     pcamv_ctx **ctx;
-    FrameDev *h_F, *d_F;        /* NRING slots of n descriptors (pinned host / device) */
-    EmbedDev *h_E, *d_E;
-    DescRing ring;
+    PinBuf<FrameDev> h_F; DevBuf<FrameDev> d_F;         /* NRING slots of n descriptors (pinned host / device) */
+    PinBuf<EmbedDev> h_E; DevBuf<EmbedDev> d_E;
+    EvRing<NRING> ring;
     /* dataflow schedule (k_analyse_flow): queue + dependency counters, one persistent launch per step */
     int sched_flow, flow_waves, flow2_waves, closed_loop, stc_ns;
     int b_mbrd, b_tesa;         /* instance of the analysis kernel the batch's contexts need (fixed at creation) */
     const RdBuild *rd;          /* ... and which build of the RD instance (b_mbrd) */
-    unsigned *d_flow;
-    FlowDev fl, fl2;          /* queue descriptors of the analysis and of the second pass */
+    DevBuf<unsigned> d_flow;
+    FlowDev fl, fl2;          /* queue descriptors of the analysis and of the second pass (pointers into d_flow) */
     /* payload path: descriptors of the receiving side (their own ring, made by the first extraction) and the per-context counts of
      * payload_check */
-    ExtractDev *h_X, *d_X; long long *d_chk;
-    DescRing xring;
+    PinBuf<ExtractDev> h_X; DevBuf<ExtractDev> d_X; DevBuf<long long> d_chk;
+    EvRing<NRING> xring;
     /* receiver from a stream (k_parse_pslice, k_parse_pslice_cavlc; a batch is of one entropy mode): per-context status words, the tables, the row buffers of pictures too wide for LDS, and
      * the staging of host slices -- descriptor arrays then bytes in one block */
-    int *d_sstat; uint8_t *d_sp_tab, *d_sp_scratch;
+    DevBuf<int> d_sstat; DevBuf<uint8_t> d_sp_tab, d_sp_scratch;
     int sp_lds_cols;            /* pictures up to this many macroblocks wide keep the parser's row buffer in LDS (SP_LDS_COLS; PCAMV_SLICE_LDS_COLS lowers it) */
     StageRing rx_stage;
     /* ... handed NAL units (k_nal_to_rbsp): the RBSPs, their lengths and header bytes, which the parser of the same call reads */
@@ -156,12 +210,12 @@ struct pcamv_batch {
     /* ... handed one video (pcamv_gpu_batch_index_video*): the index of the video as one stream with all its units listed, the contexts'
      * (off, len) k_video_cut makes of it -- [off n][len n][n_gops][preamble] --, and the video's own sets; `video` holds from such a call to
      * the next index call of either kind */
-    StreamIndex vx; StreamSets vps; long long *d_vcut; size_t cap_vcut; int video;
+    StreamIndex vx; StreamSets vps; DevBuf<long long> d_vcut; int video;
     StageRing su_stage;
     StreamWindow sw;
     /* sender to a stream (k_write_pslice, k_write_pslice_cavlc): the same of its own, and the staging of the callers' slice headers -- a
      * ring apart from the receiver's, since a write and a parse of one batch may be in flight on different streams */
-    int *d_wstat; uint8_t *d_sw_tab, *d_sw_scratch;
+    DevBuf<int> d_wstat; DevBuf<uint8_t> d_sw_tab, d_sw_scratch;
     StageRing tx_stage;
     /* ... that writes byte streams (k_stream_open, k_stream_slot, k_stream_commit): what stream_open was given and the library's own of it */
     StreamOut so;
@@ -169,13 +223,13 @@ struct pcamv_batch {
      * words (MSG_*) with the batch cursor, and per context of a step its m and its planned place.  Receiver: the batch's received stream
      * and its state, per job of a call (m, status) and the planned place -- room for a window of PCAMV_STREAM_WINDOW_MAX --, and the
      * partial sums of message_check, the result behind them */
-    const uint8_t *d_msg; long long msg_bits; uint8_t *d_msg_own; size_t msg_own_bytes;
-    long long *d_mtx; int *d_mtx_m; long long *d_mtx_at;
-    unsigned *d_mrx; long long mrx_bits; long long *d_mrx_state; int *d_mrx_job; long long *d_mrx_at, *d_mchk;
+    const uint8_t *d_msg; long long msg_bits; DevBuf<uint8_t> d_msg_own;       /* (d_msg is borrowed: d_msg_own, or the caller's) */
+    DevBuf<long long> d_mtx; DevBuf<int> d_mtx_m; DevBuf<long long> d_mtx_at;
+    DevBuf<unsigned> d_mrx; long long mrx_bits; DevBuf<long long> d_mrx_state; DevBuf<int> d_mrx_job; DevBuf<long long> d_mrx_at, d_mchk;
     /* IDR pictures coded on the device (pcamv_idr.hip): the working memory of a group of `group` contexts in one block -- per place the
      * counts, the bit-string slots, the bit counts, the prefix and the RBSP --, per context a failure word, the slot's code and the probe's
      * {off, cap, len}, and the code tables */
-    uint8_t *d_idr; size_t cap_idr; int idr_group; uint8_t *d_idr_ctx; uint8_t *d_idr_tab;
+    DevBuf<uint8_t> d_idr; int idr_group; DevBuf<uint8_t> d_idr_ctx, d_idr_tab;
     KTimer kt[KT_N];            /* the timed kernels; the events of a timer are made by its first launch */
     char err[256];
 };
@@ -215,14 +269,6 @@ struct pcamv_ctx {
     char err[256];
 };
 
-/* the error text of a context or of a batch */
-template <class Owner> static int fail(Owner *o, int code, const char *fmt, ...)
-{
-    if (o) { va_list ap; va_start(ap, fmt); vsnprintf(o->err, sizeof(o->err), fmt, ap); va_end(ap); }
-    return code;
-}
-#define HIPCHK(o, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(o, PCAMV_EHIP, "%s: %s", #call, hipGetErrorString(e_)); } while (0)
-#define TRY(call) do { const int rc_ = (call); if (rc_) return rc_; } while (0)
 /* behind the launches of an entry point: did the runtime take them all? */
 template <class Owner> static int launched(Owner *o)
 {
@@ -259,7 +305,6 @@ extern "C" int pcamv_gpu_prof_fetch(unsigned long long *out, int reset)
 #endif
 extern "C" const char *pcamv_gpu_last_error(const pcamv_ctx_t *c) { return c ? c->err : "no context"; }
 
-template <class T> static hipError_t dalloc(T **p, size_t n) { return hipMalloc((void **)p, n * sizeof(T)); }
 /* device memory of a context: `count` elements in one allocation of its own, every byte set to `fill` if that is >= 0; released by
  * pcamv_gpu_close, whichever way the context got there, or before that by ctx_free */
 template <class T> static int ctx_alloc(pcamv_ctx *c, T **p, size_t count, int fill = -1)
@@ -275,13 +320,7 @@ template <class T> static void ctx_free(pcamv_ctx *c, T **p)
     for (int i = 0; i < c->n_owned; i++) if (c->owned[i] == (void *)*p) { c->owned[i] = c->owned[--c->n_owned]; break; }
     hipFree((void *)*p); *p = NULL;
 }
-/* temporaries released when their scope ends, on every return path: a device allocation and a host block */
-template <class T> struct DevTmp {
-    T *p = NULL;
-    DevTmp() {} DevTmp(const DevTmp &) = delete; ~DevTmp() { hipFree(p); }
-    hipError_t alloc(size_t n) { return dalloc(&p, n); }
-    operator T *() const { return p; }
-};
+/* a host block released when its scope ends, on every return path (a device temporary is a DevBuf) */
 template <class T> struct HostTmp {      /* NULL when there is no memory */
     T *p;
     explicit HostTmp(size_t n) : p((T *)malloc(n * sizeof(T))) {} HostTmp(const HostTmp &) = delete; ~HostTmp() { free(p); }
@@ -310,38 +349,8 @@ static void glibc_srand_state(int *st, unsigned seed)
 }
 
 /* ------------------------------------------------------------------ batches */
-static hipError_t ring_create(DescRing &r)
-{
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < NRING && e == hipSuccess; i++) e = hipEventCreateWithFlags(&r.done[i], hipEventDisableTiming);
-    return e;
-}
-static void ring_destroy(DescRing &r) { for (int i = 0; i < NRING; i++) if (r.done[i]) hipEventDestroy(r.done[i]); }
-static void stage_destroy(StageRing &R)
-{
-    for (int k = 0; k < NSTAGE; k++) { if (R.h[k]) hipHostFree(R.h[k]); hipFree(R.d[k]); if (R.done[k]) hipEventDestroy(R.done[k]); }
-}
-static void stream_index_free(StreamIndex &S)
-{
-    hipFree(S.d_at); hipFree(S.d_bad); hipFree(S.d_longest); hipFree(S.d_chunks); hipFree(S.d_table); hipFree(S.d_own); hipFree(S.d_keep);
-    S = StreamIndex();
-}
-static void stream_sets_free(StreamSets &P)
-{
-    hipFree(P.d_table); hipFree(P.d_cnt); hipFree(P.d_sets); hipFree(P.d_len); hipFree(P.d_map); hipFree(P.d_rec); hipFree(P.d_slots);
-    P = StreamSets();
-}
-static void stream_window_free(StreamWindow &W)
-{
-    hipFree(W.d_mbs); hipFree(W.d_stego); hipFree(W.d_hdr); hipFree(W.d_cols); hipFree(W.d_stat); hipFree(W.d_scratch); hipFree(W.d_jobs);
-    hipFree(W.d_cursor_was); hipFree(W.d_X);
-    if (W.h_X) hipHostFree(W.h_X);
-    for (int r = 0; r < NSTAGE; r++) if (W.desc_done[r]) hipEventDestroy(W.desc_done[r]);
-    if (W.done) hipEventDestroy(W.done);
-    W = StreamWindow();
-}
-static void kt_destroy(KTimer &T) { for (int i = 0; i < NEV; i++) { if (T.e0[i]) hipEventDestroy(T.e0[i]); if (T.e1[i]) hipEventDestroy(T.e1[i]); } }
-
+/* Whatever a batch owns -- device memory, pinned blocks, the events of its rings, timers and window -- is a member that frees itself:
+ * destroying the batch releases it all, however far its creation or a later reservation got */
 extern "C" void pcamv_gpu_batch_destroy(pcamv_batch_t *b)
 {
     if (!b) return;
@@ -354,24 +363,6 @@ extern "C" void pcamv_gpu_batch_destroy(pcamv_batch_t *b)
         if (c->win == b) c->win = NULL;
         for (int k = 0; k < c->n_member; k++) if (c->member_of[k] == b) { c->member_of[k] = c->member_of[--c->n_member]; break; }
     }
-    if (b->h_F) hipHostFree(b->h_F);
-    if (b->h_E) hipHostFree(b->h_E);
-    if (b->h_X) hipHostFree(b->h_X);
-    hipFree(b->d_F); hipFree(b->d_E); hipFree(b->d_flow); hipFree(b->d_X); hipFree(b->d_chk);
-    hipFree(b->d_sstat); hipFree(b->d_sp_tab); hipFree(b->d_sp_scratch);
-    stage_destroy(b->rx_stage); stage_destroy(b->nal_stage); stage_destroy(b->su_stage);
-    stream_index_free(b->sx);
-    stream_sets_free(b->ps);
-    stream_index_free(b->vx); stream_sets_free(b->vps); hipFree(b->d_vcut);
-    stream_window_free(b->sw);
-    hipFree(b->d_wstat); hipFree(b->d_sw_tab); hipFree(b->d_sw_scratch);
-    stage_destroy(b->tx_stage);
-    hipFree(b->so.d_own); hipFree(b->so.d_head); hipFree(b->so.d_copy);
-    hipFree(b->d_idr); hipFree(b->d_idr_ctx); hipFree(b->d_idr_tab);
-    hipFree(b->d_msg_own); hipFree(b->d_mtx); hipFree(b->d_mtx_m); hipFree(b->d_mtx_at);
-    hipFree(b->d_mrx); hipFree(b->d_mrx_state); hipFree(b->d_mrx_job); hipFree(b->d_mrx_at); hipFree(b->d_mchk);
-    ring_destroy(b->ring); ring_destroy(b->xring);
-    for (KTimer &T : b->kt) kt_destroy(T);
     free(b->ctx);
     delete b;
 }
@@ -398,16 +389,9 @@ static void flow_split_queues(FlowDev &fl, int n)
     }
 }
 
-extern "C" int pcamv_gpu_batch_create(pcamv_ctx_t *const *ctxs, int n, pcamv_batch_t **out)
+/* what pcamv_gpu_batch_create (below) makes of a new, empty batch; a failure leaves the clean-up to it */
+static int batch_create_impl(pcamv_batch *b, pcamv_ctx_t *const *ctxs, int n)
 {
-    if (!ctxs || n <= 0 || !out) return PCAMV_EINVAL;
-    *out = NULL;
-    for (int i = 0; i < n; i++)
-        if (!ctxs[i] || ctxs[i]->device != ctxs[0]->device || ctxs[i]->F.w != ctxs[0]->F.w || ctxs[i]->F.h != ctxs[0]->F.h ||
-            ctxs[i]->p.inter != ctxs[0]->p.inter || ctxs[i]->F.b_mbrd != ctxs[0]->F.b_mbrd || ctxs[i]->F.b_cabac != ctxs[0]->F.b_cabac) return PCAMV_EINVAL;
-    pcamv_batch *b = new (std::nothrow) pcamv_batch();
-    if (!b) return PCAMV_ENOMEM;
-    memset((void *)b, 0, sizeof(*b));
     b->n = n; b->device = ctxs[0]->device; b->W = ctxs[0]->F.w; b->H = ctxs[0]->F.h;
     b->b_mbrd = ctxs[0]->F.b_mbrd;
     for (int i = 0; i < n; i++) b->b_tesa |= ctxs[i]->F.me_method == PCAMV_ME_TESA;
@@ -425,15 +409,12 @@ extern "C" int pcamv_gpu_batch_create(pcamv_ctx_t *const *ctxs, int n, pcamv_bat
     b->sp_lds_cols = env_int("PCAMV_SLICE_LDS_COLS", 0, SP_LDS_COLS, SP_LDS_COLS);      /* (tests: 0 sends every picture through the global scratch rows) */
     for (int k = 0; k < KT_N; k++) { b->kt[k].cap = k == KT_ANALYSE ? NEV : NKEV; b->kt[k].weight = 1; }
     if (!b->sched_flow) b->kt[KT_ANALYSE].weight = b->n_diag;
-    hipError_t e = hipSetDevice(b->device);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&b->h_F, sizeof(FrameDev) * n * NRING, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&b->h_E, sizeof(EmbedDev) * n * NRING, hipHostMallocDefault);
-    if (e == hipSuccess) e = dalloc(&b->d_F, (size_t)n * NRING);
-    if (e == hipSuccess) e = dalloc(&b->d_E, (size_t)n * NRING);
-    if (e == hipSuccess) e = ring_create(b->ring);
-    if (e == hipSuccess && b->sched_flow) {
+    HIPCHK(b, hipSetDevice(b->device));
+    TRY(b->h_F.room(b, (size_t)n * NRING)); TRY(b->h_E.room(b, (size_t)n * NRING));
+    TRY(b->d_F.room(b, (size_t)n * NRING)); TRY(b->d_E.room(b, (size_t)n * NRING));
+    if (b->sched_flow) {
         const size_t total = (size_t)n * F.n_mb;
-        e = dalloc(&b->d_flow, FLOW_CTR_WORDS + 2 * total + (size_t)FLOW_RDONE_STRIDE * n);
+        TRY(b->d_flow.room(b, FLOW_CTR_WORDS + 2 * total + (size_t)FLOW_RDONE_STRIDE * n));
         /* the analysis: its queues, which build of it, how many waves */
         FlowDev &fl = b->fl;
         fl.ctr = b->d_flow; fl.queue = b->d_flow + FLOW_CTR_WORDS; fl.dep = (int *)(b->d_flow + FLOW_CTR_WORDS + total);
@@ -446,14 +427,14 @@ extern "C" int pcamv_gpu_batch_create(pcamv_ctx_t *const *ctxs, int n, pcamv_bat
          * / MV differences the macroblock coded before this one leaves in the cache (PCAMV_CHAIN_NZ) */
         fl.raster = F.b_mbrd && (F.b_cabac || sub8x8);
         int per_cu = 0, n_cu = 0;
-        if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_analyse_flow, 64, 0);
-        if (e == hipSuccess) e = hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, b->device);
-        if (e == hipSuccess && F.b_mbrd) {
+        HIPCHK(b, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_analyse_flow, 64, 0));
+        HIPCHK(b, hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, b->device));
+        if (F.b_mbrd) {
             /* which build of the RD instance (pcamv_rd_select.h: the rules and what was measured) */
             b->rd = &rd_builds[rd_select(n, n_cu, fl.raster, F.mb_w, sub8x8, b->b_tesa, getenv("PCAMV_RD_INSTANCE"), getenv("PCAMV_FLOW_SPEC"))];
             fl.spec = b->rd->spec != 0;
             per_cu = b->rd->waves_per_cu();
-            if (per_cu < 0) e = hipErrorUnknown;
+            if (per_cu < 0) return fail(b, PCAMV_EHIP, "the occupancy of the RD instance's build could not be read");
         }
         b->flow_waves = flow_wave_count(per_cu, n_cu, total);
         /* the second pass can take `unit` macroblocks of a row per task (PCAMV_PASS2_UNIT; the dependency graph is the
@@ -468,16 +449,28 @@ extern "C" int pcamv_gpu_batch_create(pcamv_ctx_t *const *ctxs, int n, pcamv_bat
         fl2.total = (unsigned)n * (unsigned)fl2.n_mb;
         flow_split_queues(fl2, n);
         fl2.dep = (int *)(b->d_flow + FLOW_CTR_WORDS + fl2.total);
-        if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_pass2_deblock_flow, 64, 0);
+        HIPCHK(b, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_pass2_deblock_flow, 64, 0));
         b->flow2_waves = flow_wave_count(per_cu, n_cu, fl2.total);
-        if (e == hipSuccess) e = hipMemset(b->d_flow, 0, FLOW_CTR_WORDS * sizeof(unsigned));
+        HIPCHK(b, hipMemset(b->d_flow, 0, FLOW_CTR_WORDS * sizeof(unsigned)));
     }
-    if (e != hipSuccess) { pcamv_gpu_batch_destroy(b); return PCAMV_EHIP; }
-    /* the contexts learn of the batch */
-    for (int i = 0; i < n; i++) if (ctxs[i]->n_member >= 16) { pcamv_gpu_batch_destroy(b); return PCAMV_EINVAL; }
+    /* the contexts learn of the batch (one that is refused below takes itself out of their lists again: pcamv_gpu_batch_destroy) */
+    for (int i = 0; i < n; i++) if (ctxs[i]->n_member >= 16) return PCAMV_EINVAL;
     for (int i = 0; i < n; i++) ctxs[i]->member_of[ctxs[i]->n_member++] = b;
     for (int i = 0; i < n; i++)         /* the kernel instance with --me tesa compiled in exists for the dataflow schedule only */
-        if ((ctxs[i]->F.me_method == PCAMV_ME_TESA || ctxs[i]->F.b_mbrd) && !b->sched_flow) { pcamv_gpu_batch_destroy(b); return PCAMV_EUNSUP; }     /* ... and so does the RD mode decision */
+        if ((ctxs[i]->F.me_method == PCAMV_ME_TESA || ctxs[i]->F.b_mbrd) && !b->sched_flow) return PCAMV_EUNSUP;     /* ... and so does the RD mode decision */
+    return 0;
+}
+extern "C" int pcamv_gpu_batch_create(pcamv_ctx_t *const *ctxs, int n, pcamv_batch_t **out)
+{
+    if (!ctxs || n <= 0 || !out) return PCAMV_EINVAL;
+    *out = NULL;
+    for (int i = 0; i < n; i++)
+        if (!ctxs[i] || ctxs[i]->device != ctxs[0]->device || ctxs[i]->F.w != ctxs[0]->F.w || ctxs[i]->F.h != ctxs[0]->F.h ||
+            ctxs[i]->p.inter != ctxs[0]->p.inter || ctxs[i]->F.b_mbrd != ctxs[0]->F.b_mbrd || ctxs[i]->F.b_cabac != ctxs[0]->F.b_cabac) return PCAMV_EINVAL;
+    pcamv_batch *b = new (std::nothrow) pcamv_batch();      /* (value-initialised: every field zero, every buffer empty) */
+    if (!b) return PCAMV_ENOMEM;
+    const int rc = batch_create_impl(b, ctxs, n);
+    if (rc) { pcamv_gpu_batch_destroy(b); return rc; }      /* one cleanup path: whatever was allocated so far is released */
     *out = b;
     return 0;
 }
@@ -511,13 +504,9 @@ static const char *dominant_kernel(const pcamv_batch *b)
 extern "C" const char *pcamv_gpu_batch_dominant_kernel(const pcamv_batch_t *b) { return dominant_kernel(b); }
 static const char *kt_name(const pcamv_batch *b, int k)      /* what pcamv_gpu_batch_kernel_time knows timer k by */
 {
-    static const char *const small[KT_N] = {NULL, "k_embed_prepare", "k_extract_prepare", "k_extract_bits", "k_payload_check", "k_parse_pslice", "k_parse_pslice_cavlc", "k_write_pslice",
-                                            "k_write_pslice_cavlc", "k_nal_to_rbsp", "k_stream_plan", "k_stream_scan", "k_stream_prefix", "k_stream_place", "k_stream_unit",
-                                            "k_slice_header", "k_stream_status", "k_stream_open", "k_stream_slot", "k_stream_commit",
-                                            "k_stream_window_unit", "k_extract_count", "k_extract_chain", "k_pset_unit", "k_pset_parse", "k_pset_resolve",
-                                            "k_slice_header_sets", "k_stream_open_heads", "k_stream_join", "k_stream_copy_plan", "k_stream_copy", "k_video_cut",
-                                            "k_message_count", "k_message_plan", "k_message_jobs", "k_extract_chain_message", "k_message_check",
-                                            "k_idr_mb", "k_idr_prefix", "k_idr_pack", "k_idr_unit"};
+#define KT_NAME(id, name) name,
+    static const char *const small[KT_N] = {PCAMV_TIMERS(KT_NAME)};
+#undef KT_NAME
     return k == KT_ANALYSE ? dominant_kernel(b) : small[k];
 }
 extern "C" int pcamv_gpu_batch_copy_results_async(pcamv_batch_t *b, void *dst_mb, size_t mb_stride, void *dst_flip, size_t flip_stride, void *stream)
@@ -668,10 +657,10 @@ static int ensure_qp(pcamv_ctx *c, int qp)
 }
 /* The frame descriptor of a probe (block_costs, rd_probe): a copy of the context's with the probe's QP, on the device for the probe's
  * one launch.  The context keeps its own QP, so whatever runs on it after the probe computes what it would have without it. */
-static int probe_frame(pcamv_ctx *c, int qp, DevTmp<FrameDev> &d_F)
+static int probe_frame(pcamv_ctx *c, int qp, DevBuf<FrameDev> &d_F)
 {
     TRY(ensure_qp_tables(c, qp));
-    HIPCHK(c, d_F.alloc(1));
+    TRY(d_F.room(c, 1));
     FrameDev hF = c->F; hF.self = d_F;
     frame_use_qp(c, &hF, qp);
     HIPCHK(c, hipMemcpy(d_F, &hF, sizeof(FrameDev), hipMemcpyHostToDevice));
@@ -721,47 +710,39 @@ extern "C" int pcamv_gpu_set_fenc_device(pcamv_ctx_t *c, const void *y, const vo
 
 /* ------------------------------------------------------------------ batched launches */
 /* the ring's next slot, once its descriptors are no longer in flight */
-static int ring_take(pcamv_batch *b, DescRing &r, int *slot_out)
+template <int N> static int ring_take(pcamv_batch *b, EvRing<N> &r, int *slot_out)
 {
     const int slot = r.head;
-    r.head = (r.head + 1) % NRING;
+    r.head = (slot + 1) % N;
+    if (!r.done[slot]) HIPCHK(b, hipEventCreateWithFlags(&r.done[slot], hipEventDisableTiming));
     if (r.used[slot]) HIPCHK(b, hipEventSynchronize(r.done[slot]));
     *slot_out = slot;
     return 0;
 }
 /* ... and what was queued on `st` so far is what reads them */
-static int ring_release(pcamv_batch *b, DescRing &r, int slot, hipStream_t st)
+template <int N> static int ring_release(pcamv_batch *b, EvRing<N> &r, int slot, hipStream_t st)
 {
     HIPCHK(b, hipEventRecord(r.done[slot], st));
     r.used[slot] = 1;
     return 0;
 }
-/* the staging ring's next buffer with room for `total` bytes (regrown with a quarter to spare), once it is no longer in flight;
- * host == 0: the device side alone */
+/* the staging ring's buffer k with room for `total` bytes and `spare` more where it has to grow; host == 0: the device side alone.
+ * The only place that sizes a ring's buffers.  Growing frees, which waits for the device: an index call sizes su_stage behind its
+ * synchronisation; the rings of host slices and headers grow inside the call that outgrows them (stage_take) */
+static int stage_room(pcamv_batch *b, StageRing &R, int k, size_t total, size_t spare, int host)
+{
+    if (total <= R.d[k].cap && (!host || total <= R.h[k].cap)) return 0;       /* (both sides: a side that could not be made is empty, and is made again here) */
+    if (host) TRY(R.h[k].room(b, total + spare));
+    return R.d[k].room(b, total + spare);
+}
+/* the staging ring's next buffer with room for `total` bytes (regrown with a quarter to spare), once it is no longer in flight */
 static int stage_take(pcamv_batch *b, StageRing &R, size_t total, int *k_out, int host = 1)
 {
-    const int k = R.head;
-    R.head = (k + 1) % NSTAGE;
-    if (!R.done[k]) HIPCHK(b, hipEventCreateWithFlags(&R.done[k], hipEventDisableTiming));
-    if (R.used[k]) HIPCHK(b, hipEventSynchronize(R.done[k]));
-    if (total > R.cap[k]) {
-        if (R.h[k]) hipHostFree(R.h[k]);
-        hipFree(R.d[k]); R.h[k] = NULL; R.d[k] = NULL; R.cap[k] = 0;
-        const size_t cap = total + total / 4;
-        if (host) HIPCHK(b, hipHostMalloc((void **)&R.h[k], cap, hipHostMallocDefault));
-        HIPCHK(b, dalloc(&R.d[k], cap));
-        R.cap[k] = cap;
-    }
-    *k_out = k;
-    return 0;
+    TRY(ring_take(b, R.ring, k_out));
+    return stage_room(b, R, *k_out, total, total / 4, host);
 }
 /* what was queued on `st` so far is what reads buffer k: called once the kernels that read its device side are queued */
-static int stage_release(pcamv_batch *b, StageRing &R, int k, hipStream_t st)
-{
-    HIPCHK(b, hipEventRecord(R.done[k], st));
-    R.used[k] = 1;
-    return 0;
-}
+static int stage_release(pcamv_batch *b, StageRing &R, int k, hipStream_t st) { return ring_release(b, R.ring, k, st); }
 /* the first `total` bytes of buffer k to the device, one copy on `st`.  From here on the buffer is in flight whatever happens to the
  * kernels: the event stands for the copy until stage_release moves it behind the kernels that read the device side */
 static int stage_send(pcamv_batch *b, StageRing &R, int k, size_t total, hipStream_t st)
@@ -798,24 +779,25 @@ template <class Launch> static void diag_launch(int n_diag, const FrameDev &F, L
     }
 }
 
-/* the events of timer k around what is queued on `st` between kt_begin and kt_end; a timer whose events cannot be made stays off */
-static int kt_begin(pcamv_batch *b, int k, hipStream_t st)
+/* A timed launch: the events of timer k around what `launch` queues on `st`, the only place that records them.  A timer whose events
+ * cannot be made stays off, and its launches go untimed */
+template <class Launch> static void timed(pcamv_batch *b, int k, hipStream_t st, Launch launch)
 {
     KTimer &T = b->kt[k];
-    if (T.made < 0) return -1;
     if (!T.made) {
-        for (int i = 0; i < T.cap; i++) if (hipEventCreate(&T.e0[i]) != hipSuccess || hipEventCreate(&T.e1[i]) != hipSuccess) { T.made = -1; return -1; }
         T.made = 1;
+        for (int i = 0; i < T.cap && T.made > 0; i++) if (hipEventCreate(&T.e0[i]) != hipSuccess || hipEventCreate(&T.e1[i]) != hipSuccess) T.made = -1;
     }
+    if (T.made < 0) { launch(); return; }
     hipEventRecord(T.e0[T.head], st);
-    return T.head;
-}
-static void kt_end(pcamv_batch *b, int k, int ev, hipStream_t st)
-{
-    KTimer &T = b->kt[k];
-    if (ev < 0) return;
-    hipEventRecord(T.e1[ev], st);
+    launch();
+    hipEventRecord(T.e1[T.head], st);
     T.head = (T.head + 1) % T.cap; if (T.n < T.cap) T.n++;
+}
+/* ... of one kernel of this unit */
+template <class Kernel, class... Args> static void timed_kernel(pcamv_batch *b, int k, hipStream_t st, Kernel kernel, dim3 grid, dim3 block, const Args &... args)
+{
+    timed(b, k, st, [&] { hipLaunchKernelGGL(kernel, grid, block, 0, st, args...); });
 }
 
 /* the second pass takes the frame's reconstruction as it stands: the first pass' own, once (then it has been filtered in place) */
@@ -857,31 +839,25 @@ static int batch_launch(pcamv_batch *b, int what, hipStream_t st)
         for (int i = 0; i < b->n; i++) b->ctx[i]->last = b;
         if (b->sched_flow) {        /* timed: the analysis kernel without k_flow_init */
             hipLaunchKernelGGL(k_flow_init, dim3((b->fl.total + 255) / 256), dim3(256), 0, st, b->fl);
-            const int ev = kt_begin(b, KT_ANALYSE, st);
-            if (b->b_mbrd) b->rd->launch((unsigned)b->flow_waves, st, dF, b->fl);
-            else if (b->b_tesa) pcamv_launch_flow_tesa((unsigned)b->flow_waves, st, dF, b->fl);
-            else hipLaunchKernelGGL(k_analyse_flow, dim3(b->flow_waves), dim3(64), 0, st, dF, b->fl);
-            kt_end(b, KT_ANALYSE, ev, st);
+            timed(b, KT_ANALYSE, st, [&] {
+                if (b->b_mbrd) b->rd->launch((unsigned)b->flow_waves, st, dF, b->fl);
+                else if (b->b_tesa) pcamv_launch_flow_tesa((unsigned)b->flow_waves, st, dF, b->fl);
+                else hipLaunchKernelGGL(k_analyse_flow, dim3(b->flow_waves), dim3(64), 0, st, dF, b->fl);
+            });
         } else {                    /* timed: the n_diag launches of the search (one pair of events, KTimer::weight), without k_rca / k_encode */
-            const int ev = kt_begin(b, KT_ANALYSE, st);
-            diag_launch(b->n_diag, F, [&](int cnt, int d) { hipLaunchKernelGGL(k_search_diag<0>, dim3(cnt, G), dim3(64), 0, st, dF, d); });
-            kt_end(b, KT_ANALYSE, ev, st);
+            timed(b, KT_ANALYSE, st, [&] {
+                diag_launch(b->n_diag, F, [&](int cnt, int d) { hipLaunchKernelGGL(k_search_diag<0>, dim3(cnt, G), dim3(64), 0, st, dF, d); });
+            });
             hipLaunchKernelGGL(k_rca, dim3(F.n_mb * b->slots_per_mb, G), dim3(64), 0, st, dF, b->slots_per_mb);
             hipLaunchKernelGGL(k_encode, dim3(F.n_mb, G), dim3(64), 0, st, dF);
         }
     }
     if ((what & ST_EMBED) && b->d_msg) {     /* every context's m, then the place of each in the message: pstate[PST_TX], which k_embed_prepare reads */
-        int ev = kt_begin(b, KT_MESSAGE_COUNT, st);
-        hipLaunchKernelGGL(k_message_count, dim3(G), dim3(256), 0, st, dE, b->d_mtx_m);
-        kt_end(b, KT_MESSAGE_COUNT, ev, st);
-        ev = kt_begin(b, KT_MESSAGE_PLAN, st);
-        hipLaunchKernelGGL(k_message_plan, dim3(1), dim3(MSG_PLAN_THREADS), 0, st, b->d_mtx_m, (const int *)NULL, b->n, 1, PCAMV_MSG_NO_CAP, b->d_mtx, b->d_mtx_at, dE);
-        kt_end(b, KT_MESSAGE_PLAN, ev, st);
+        timed_kernel(b, KT_MESSAGE_COUNT, st, k_message_count, dim3(G), dim3(256), dE, b->d_mtx_m);
+        timed_kernel(b, KT_MESSAGE_PLAN, st, k_message_plan, dim3(1), dim3(MSG_PLAN_THREADS), b->d_mtx_m, (const int *)NULL, b->n, 1, PCAMV_MSG_NO_CAP, b->d_mtx, b->d_mtx_at, dE);
     }
     if (what & ST_EMBED) {
-        const int ev = kt_begin(b, KT_EMBED_PREPARE, st);
-        hipLaunchKernelGGL(k_embed_prepare, dim3(G), dim3(1024), 0, st, dE);
-        kt_end(b, KT_EMBED_PREPARE, ev, st);
+        timed_kernel(b, KT_EMBED_PREPARE, st, k_embed_prepare, dim3(G), dim3(1024), dE);
         /* 2 trellis states per thread: measured 3.25 / 2.89 / 2.90 ms per 1080p frame for 1 / 2 / 4 */
         /* (one frame alone: 2 trellis states per thread is the fastest chain; thousands of frames: 4 states per thread = 4 waves per frame, so
          * that a CU holds eight frames' trellises instead of four and the batch needs half the rounds: 18.6 -> 13.3 ms per 4096-frame step) */
@@ -1306,10 +1282,10 @@ static void extract_bits_launch(pcamv_batch *b, const ExtractDev *dX, int nx, in
     double most = emrate > 1.0f ? (double)(int)emrate : ceil((double)emrate * cap) + 1;
     if (most > cap) most = cap;
     const int groups = (int)((most + 63 + 255) / 256) > 0 ? (int)((most + 63 + 255) / 256) : 1;
-    const int ev = kt_begin(b, KT_EXTRACT_BITS, st);
-    for (int x0 = 0; x0 < nx; x0 += 65535)         /* (a grid's second dimension ends there: a window of many contexts has more frames) */
-        hipLaunchKernelGGL(k_extract_bits, dim3(groups, nx - x0 < 65535 ? nx - x0 : 65535), dim3(256), 0, st, dX + x0);
-    kt_end(b, KT_EXTRACT_BITS, ev, st);
+    timed(b, KT_EXTRACT_BITS, st, [&] {
+        for (int x0 = 0; x0 < nx; x0 += 65535)     /* (a grid's second dimension ends there: a window of many contexts has more frames) */
+            hipLaunchKernelGGL(k_extract_bits, dim3(groups, nx - x0 < 65535 ? nx - x0 : 65535), dim3(256), 0, st, dX + x0);
+    });
 }
 /* Under a batch reservation (one message for the batch): behind k_extract_count, the frames of a call of k slots per context get their
  * places in the batch's stream from one plan over all of them, then the chain with those places.  first: the codes of a stream call's
@@ -1318,40 +1294,24 @@ static void extract_message_chain_launch(pcamv_batch *b, const ExtractDev *dX, i
 {
     const int jobs = b->n * k;
     int *m = b->d_mrx_job, *status = b->d_mrx_job + (size_t)b->n * PCAMV_STREAM_WINDOW_MAX;
-    int ev = kt_begin(b, KT_MESSAGE_JOBS, st);
-    hipLaunchKernelGGL(k_message_jobs, dim3((jobs + 255) / 256), dim3(256), 0, st, dX, first, jobs, m, status);
-    kt_end(b, KT_MESSAGE_JOBS, ev, st);
-    ev = kt_begin(b, KT_MESSAGE_PLAN, st);
-    hipLaunchKernelGGL(k_message_plan, dim3(1), dim3(MSG_PLAN_THREADS), 0, st, m, status, b->n, k, b->mrx_bits, b->d_mrx_state, b->d_mrx_at, (const EmbedDev *)NULL);
-    kt_end(b, KT_MESSAGE_PLAN, ev, st);
-    ev = kt_begin(b, KT_EXTRACT_CHAIN_MESSAGE, st);
-    hipLaunchKernelGGL(k_extract_chain_message, dim3((b->n + 63) / 64), dim3(64), 0, st, dX, b->n, k, status, b->d_mrx_at);
-    kt_end(b, KT_EXTRACT_CHAIN_MESSAGE, ev, st);
+    timed_kernel(b, KT_MESSAGE_JOBS, st, k_message_jobs, dim3((jobs + 255) / 256), dim3(256), dX, first, jobs, m, status);
+    timed_kernel(b, KT_MESSAGE_PLAN, st, k_message_plan, dim3(1), dim3(MSG_PLAN_THREADS), m, status, b->n, k, b->mrx_bits, b->d_mrx_state, b->d_mrx_at, (const EmbedDev *)NULL);
+    timed_kernel(b, KT_EXTRACT_CHAIN_MESSAGE, st, k_extract_chain_message, dim3((b->n + 63) / 64), dim3(64), dX, b->n, k, status, b->d_mrx_at);
 }
 /* the two kernels of the receiving side for nx frames (with a batch reservation: the frames of the batch's contexts, a window of one) */
 static void extract_launch(pcamv_batch *b, const ExtractDev *dX, int nx, int cap, float emrate, hipStream_t st, const int *first = NULL)
 {
     if (b->d_mrx) {
-        const int ev = kt_begin(b, KT_EXTRACT_COUNT, st);
-        hipLaunchKernelGGL(k_extract_count, dim3(nx), dim3(1024), 0, st, dX);
-        kt_end(b, KT_EXTRACT_COUNT, ev, st);
+        timed_kernel(b, KT_EXTRACT_COUNT, st, k_extract_count, dim3(nx), dim3(1024), dX);
         extract_message_chain_launch(b, dX, 1, first, st);
-        extract_bits_launch(b, dX, nx, cap, emrate, st);
-        return;
-    }
-    const int ev = kt_begin(b, KT_EXTRACT_PREPARE, st);
-    hipLaunchKernelGGL(k_extract_prepare, dim3(nx), dim3(1024), 0, st, dX);
-    kt_end(b, KT_EXTRACT_PREPARE, ev, st);
+    } else timed_kernel(b, KT_EXTRACT_PREPARE, st, k_extract_prepare, dim3(nx), dim3(1024), dX);
     extract_bits_launch(b, dX, nx, cap, emrate, st);
 }
 /* descriptors of the batch's contexts as they stand, into the next slot of the receiving side's ring */
 static int batch_push_xdescs(pcamv_batch *b, hipStream_t st, const ExtractDev **dX, int *slot_out)
 {
-    if (!b->d_X) {
-        HIPCHK(b, hipHostMalloc((void **)&b->h_X, sizeof(ExtractDev) * b->n * NRING, hipHostMallocDefault));
-        HIPCHK(b, dalloc(&b->d_X, (size_t)b->n * NRING));
-        HIPCHK(b, dalloc(&b->d_chk, (size_t)b->n));
-        HIPCHK(b, ring_create(b->xring));
+    if (!b->d_chk) {            /* (a batch's first extraction: made once, never regrown) */
+        TRY(b->h_X.room(b, (size_t)b->n * NRING)); TRY(b->d_X.room(b, (size_t)b->n * NRING)); TRY(b->d_chk.room(b, (size_t)b->n));
     }
     int slot;
     TRY(ring_take(b, b->xring, &slot));
@@ -1427,34 +1387,31 @@ static int entropy_mode(pcamv_batch *b, int cavlc, const char *for_cavlc, const 
  * init_p[2 * nctx] | transition[256] | range_lps[512] for the nctx contexts the kernel keeps */
 static_assert(SP_TAB_INIT == 0 && SP_TAB_TRANS == 2 * SP_NCTX && SP_TAB_RLPS == 2 * SP_NCTX + 256 && SP_TAB_BYTES == 2 * SP_NCTX + 768, "k_parse_pslice reads another table block than entropy_tab makes");
 static_assert(SW_TAB_INIT == 0 && SW_TAB_TRANS == 2 * SW_NCTX && SW_TAB_RLPS == 2 * SW_NCTX + 256 && SW_TAB_BYTES == 2 * SW_NCTX + 768, "k_write_pslice reads another table block than entropy_tab makes");
-static int entropy_tab(pcamv_batch *b, uint8_t **d_tab, int cavlc, int nctx)
+static int entropy_tab(pcamv_batch *b, DevBuf<uint8_t> &d_tab, int cavlc, int nctx)
 {
     uint8_t tab[SV_TAB_BYTES > SW_TAB_BYTES ? SV_TAB_BYTES : SW_TAB_BYTES];
     static_assert(SP_NCTX <= SW_NCTX, "entropy_tab's block is sized for the writer's contexts");
-    if (*d_tab) return 0;
-    if (cavlc && sv_build_tables(tab)) return fail(b, PCAMV_EINVAL, "a CAVLC code of pcamv_entropy_tables.h does not fit the %stable entry", d_tab == &b->d_sp_tab ? "parser's " : "");
+    if (d_tab) return 0;
+    if (cavlc && sv_build_tables(tab)) return fail(b, PCAMV_EINVAL, "a CAVLC code of pcamv_entropy_tables.h does not fit the %stable entry", &d_tab == &b->d_sp_tab ? "parser's " : "");
     if (!cavlc) { memcpy(tab, pcamv_cabac_init_p, 2 * nctx); memcpy(tab + 2 * nctx, pcamv_cabac_transition, 256); memcpy(tab + 2 * nctx + 256, pcamv_cabac_range_lps, 512); }
     const size_t bytes = cavlc ? (size_t)SV_TAB_BYTES : (size_t)2 * nctx + 768;
-    HIPCHK(b, dalloc(d_tab, bytes));
-    HIPCHK(b, hipMemcpy(*d_tab, tab, bytes, hipMemcpyHostToDevice));
+    TRY(d_tab.room(b, bytes));
+    HIPCHK(b, hipMemcpy(d_tab, tab, bytes, hipMemcpyHostToDevice));
     return 0;
 }
 /* the row buffers of a launch, one per slice: the bytes of each, and the allocation for pictures too wide for LDS */
 static size_t row_bytes(const pcamv_batch *b, int cavlc) { return (size_t)(cavlc ? SV_ROW_BYTES : SP_ROW_BYTES) * b->ctx[0]->F.mb_w; }
-static int scratch_rows(pcamv_batch *b, uint8_t **d_scratch, int cavlc)
+/* what every launch of a parser or a writer needs of the batch: status words, the tables of its mode, scratch rows (each made by the
+ * first call that needs it, never regrown) */
+static int entropy_setup(pcamv_batch *b, DevBuf<int> &d_stat, DevBuf<uint8_t> &d_tab, DevBuf<uint8_t> &d_scratch, int cavlc, int nctx)
 {
-    if (b->ctx[0]->F.mb_w > b->sp_lds_cols && !*d_scratch) HIPCHK(b, dalloc(d_scratch, (size_t)b->n * row_bytes(b, cavlc)));
+    if (!d_stat) TRY(d_stat.room(b, (size_t)b->n));
+    TRY(entropy_tab(b, d_tab, cavlc, nctx));
+    if (b->ctx[0]->F.mb_w > b->sp_lds_cols && !d_scratch) TRY(d_scratch.room(b, (size_t)b->n * row_bytes(b, cavlc)));
     return 0;
 }
-/* what every launch of a parser or a writer needs of the batch: status words, the tables of its mode, scratch rows */
-static int entropy_setup(pcamv_batch *b, int **d_stat, uint8_t **d_tab, uint8_t **d_scratch, int cavlc, int nctx)
-{
-    if (!*d_stat) HIPCHK(b, dalloc(d_stat, (size_t)b->n));
-    TRY(entropy_tab(b, d_tab, cavlc, nctx));
-    return scratch_rows(b, d_scratch, cavlc);
-}
 /* synchronises; the status words of the batch's last parse or write call */
-static int status_fetch(pcamv_batch *b, int *pcamv_batch::*d_stat, int32_t *status, const char *none_yet)
+static int status_fetch(pcamv_batch *b, DevBuf<int> pcamv_batch::*d_stat, int32_t *status, const char *none_yet)
 {
     if (!b || !status) return PCAMV_EINVAL;
     HIPCHK(b, hipSetDevice(b->device));
@@ -1483,14 +1440,11 @@ static int slice_contexts(pcamv_batch *b, int want_rx, float emrate)
 static void slice_launch(pcamv_batch *b, const ExtractDev *dX, SliceJobs J, int cavlc, hipStream_t st, int jobs = 0, uint8_t *scratch = NULL)
 {
     const FrameDev &F = b->ctx[0]->F;
-    const int kt = cavlc ? KT_PARSE_PSLICE_CAVLC : KT_PARSE_PSLICE;
     if (!jobs) { jobs = b->n; scratch = b->d_sp_scratch; }
     J.tab = b->d_sp_tab; J.scratch = scratch; J.scratch_stride = (long long)row_bytes(b, cavlc);
     J.mb_w = F.mb_w; J.mb_h = F.mb_h; J.lds_cols = b->sp_lds_cols;
-    const int ev = kt_begin(b, kt, st);
-    if (cavlc) hipLaunchKernelGGL(k_parse_pslice_cavlc, dim3(jobs), dim3(64), 0, st, dX, J);
-    else hipLaunchKernelGGL(k_parse_pslice, dim3(jobs), dim3(64), 0, st, dX, J);
-    kt_end(b, kt, ev, st);
+    if (cavlc) timed_kernel(b, KT_PARSE_PSLICE_CAVLC, st, k_parse_pslice_cavlc, dim3(jobs), dim3(64), dX, J);
+    else timed_kernel(b, KT_PARSE_PSLICE, st, k_parse_pslice, dim3(jobs), dim3(64), dX, J);
 }
 /* parse (slices described by J, one per context) and, with extract != 0, the receiver's kernels behind it, all on `st` */
 static int slices_run(pcamv_batch *b, SliceJobs J, int cavlc, int extract, float emrate, hipStream_t st, const int *first = NULL)
@@ -1536,7 +1490,7 @@ static int slices_checked(pcamv_batch *b, float emrate, int want_rx, int cavlc)
     HIPCHK(b, hipSetDevice(b->device));
     TRY(batch_live(b));
     TRY(entropy_mode(b, cavlc, "pcamv_gpu_batch_extract_slices_cavlc* and pcamv_gpu_parse_pslice_cavlc_device parse", "pcamv_gpu_batch_extract_slices* and pcamv_gpu_parse_pslice_cabac_device parse"));
-    TRY(entropy_setup(b, &b->d_sstat, &b->d_sp_tab, &b->d_sp_scratch, cavlc, SP_NCTX));
+    TRY(entropy_setup(b, b->d_sstat, b->d_sp_tab, b->d_sp_scratch, cavlc, SP_NCTX));
     return slice_contexts(b, want_rx, emrate);
 }
 /* Unescape first (k_nal_to_rbsp, one wavefront per unit, queued on `st`): the n NAL units J describes into the next buffer of nal_stage
@@ -1555,9 +1509,7 @@ static int nals_unescape(pcamv_batch *b, int n, SliceJobs *J, int *d_status, int
     N.bytes = J->bytes; N.bytes_size = J->bytes_size; N.off = J->off; N.len = J->len;
     N.rbsp_len = (long long *)d; N.nal_header = nal_header ? nal_header : (int *)(N.rbsp_len + n); N.rbsp = d + hdr; N.status = d_status;
     if (preload) HIPCHK(b, hipMemcpyAsync(N.rbsp, preload, (size_t)J->bytes_size, hipMemcpyHostToDevice, st));
-    const int ev = kt_begin(b, KT_NAL_TO_RBSP, st);
-    hipLaunchKernelGGL(k_nal_to_rbsp, dim3(n), dim3(64), 0, st, N);
-    kt_end(b, KT_NAL_TO_RBSP, ev, st);
+    timed_kernel(b, KT_NAL_TO_RBSP, st, k_nal_to_rbsp, dim3(n), dim3(64), N);
     J->bytes = N.rbsp; J->len = N.rbsp_len;
     *stage_out = k;
     return 0;
@@ -1630,6 +1582,18 @@ extern "C" int pcamv_gpu_batch_extract_nals_cavlc_device(pcamv_batch_t *b, const
 {
     return extract_slices_device(b, bytes, bytes_size, off, len, start_bit, NULL, 1, 1, nal_header, emrate, stream);
 }
+/* What the parity probes of the stream kernels open with: the host's (bytes, off[n], len[n]) on the context's device, in temporaries
+ * of the probe -- d_at holds `arrays` arrays of n, [off][len] and what the probe keeps behind them */
+static int probe_upload(pcamv_ctx *c, DevBuf<uint8_t> &d_bytes, DevBuf<long long> &d_at, const uint8_t *bytes, size_t bytes_size, const int64_t *off,
+                        const int64_t *len, int n, int arrays)
+{
+    HIPCHK(c, hipSetDevice(c->device));
+    TRY(d_bytes.room(c, bytes_size ? bytes_size : 1)); TRY(d_at.room(c, (size_t)arrays * (size_t)n));
+    if (bytes_size) HIPCHK(c, hipMemcpy(d_bytes, bytes, bytes_size, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_at, off, sizeof(int64_t) * n, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_at + n, len, sizeof(int64_t) * n, hipMemcpyHostToDevice));
+    return 0;
+}
 /* the parity probe of k_nal_to_rbsp: n units of one host buffer through one launch, everything copied back */
 extern "C" int pcamv_gpu_nal_to_rbsp_device(pcamv_ctx_t *c, const uint8_t *bytes, size_t bytes_size, const int64_t *off, const int64_t *len, int n,
                                             uint8_t *out, int64_t *out_len, int32_t *status, int32_t *nal_header)
@@ -1637,12 +1601,8 @@ extern "C" int pcamv_gpu_nal_to_rbsp_device(pcamv_ctx_t *c, const uint8_t *bytes
     if (!c || !bytes || !off || !len || !out || !out_len || !status || n < 0 || bytes_size > ((size_t)1 << 40)) return PCAMV_EINVAL;
     if (!n) return 0;
     pcamv_batch *b = c->self;
-    HIPCHK(c, hipSetDevice(c->device));
-    DevTmp<uint8_t> d_bytes; DevTmp<long long> d_at; DevTmp<int> d_status;
-    HIPCHK(c, d_bytes.alloc(bytes_size ? bytes_size : 1)); HIPCHK(c, d_at.alloc(2 * (size_t)n)); HIPCHK(c, d_status.alloc((size_t)n));
-    HIPCHK(c, hipMemcpy(d_bytes, bytes, bytes_size, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(d_at, off, sizeof(int64_t) * n, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(d_at + n, len, sizeof(int64_t) * n, hipMemcpyHostToDevice));
+    DevBuf<uint8_t> d_bytes; DevBuf<long long> d_at; DevBuf<int> d_status;
+    TRY(probe_upload(c, d_bytes, d_at, bytes, bytes_size, off, len, n, 2)); TRY(d_status.room(c, (size_t)n));
     SliceJobs J;
     J.bytes = d_bytes; J.bytes_size = (long long)bytes_size; J.off = d_at; J.len = d_at + n;
     int k;
@@ -1691,28 +1651,15 @@ extern "C" int pcamv_gpu_parse_pslice_cavlc_device(pcamv_ctx_t *c, const uint8_t
 /* ------------------------------------------------------------------ receiver on byte streams (k_stream_*, k_slice_header, pcamv_slice.hip.h) */
 extern "C" int pcamv_gpu_stream_chunk(void) { return SI_CHUNK; }
 /* the device memory of an index of n streams in bytes_size bytes, tables of max_units entries and `guard` more behind each: grown, never
- * shrunk (a hipFree waits for the device: only a call that may synchronise gets here) */
-template <class T> static int grow(pcamv_batch *b, T **p, size_t *cap, size_t want)
-{
-    if (want <= *cap && *p) return 0;
-    hipFree(*p); *p = NULL; *cap = 0;
-    HIPCHK(b, dalloc(p, want ? want : 1));
-    *cap = want;
-    return 0;
-}
+ * shrunk (freeing waits for the device: only a call that may synchronise gets here) */
 static int stream_index_room(pcamv_batch *b, StreamIndex &S, int n, long long max_units, int guard, size_t bytes_size)
 {
     S.ready = 0;
     S.n = n; S.max_units = max_units; S.stride = max_units + guard;
     S.max_chunks = (long long)(bytes_size / SI_CHUNK) + 2LL * n + 2;
-    if ((size_t)n > S.cap_n || !S.d_at) {
-        size_t c1 = 0, c2 = 0;
-        TRY(grow(b, &S.d_at, &c1, 6 * (size_t)n)); TRY(grow(b, &S.d_bad, &c2, (size_t)n));
-        S.cap_n = (size_t)n;
-    }
-    if (!S.d_longest) HIPCHK(b, dalloc(&S.d_longest, 1));
-    TRY(grow(b, &S.d_chunks, &S.cap_chunks, (size_t)S.max_chunks));
-    return grow(b, &S.d_table, &S.cap_table, (size_t)n * (size_t)S.stride);
+    TRY(S.d_at.room(b, 6 * (size_t)n)); TRY(S.d_bad.room(b, (size_t)n)); TRY(S.d_longest.room(b, 1));
+    TRY(S.d_chunks.room(b, (size_t)S.max_chunks));
+    return S.d_table.room(b, (size_t)n * (size_t)S.stride);
 }
 /* the four kernels on `st`: streams (d_off[i], d_len[i]) of d_bytes; all != 0: every unit into the tables, else the slice units */
 static int stream_index_run(pcamv_batch *b, StreamIndex &S, const uint8_t *d_bytes, size_t bytes_size, const long long *d_off, const long long *d_len, int all, hipStream_t st)
@@ -1727,18 +1674,10 @@ static int stream_index_run(pcamv_batch *b, StreamIndex &S, const uint8_t *d_byt
     J.table = S.d_table; J.max_units = S.max_units; J.stride = S.stride; J.all = all;
     J.n_units = S.d_at + 3 * n; J.n_slices = S.d_at + 4 * n; J.cursor = S.d_at + 5 * n; J.longest = S.d_longest; J.n = S.n;
     const unsigned chunks = (unsigned)S.max_chunks;
-    int ev = kt_begin(b, KT_STREAM_PLAN, st);
-    hipLaunchKernelGGL(k_stream_plan, dim3(1), dim3(64), 0, st, J);
-    kt_end(b, KT_STREAM_PLAN, ev, st);
-    ev = kt_begin(b, KT_STREAM_SCAN, st);
-    hipLaunchKernelGGL(k_stream_scan<0>, dim3(chunks), dim3(64), 0, st, J);
-    kt_end(b, KT_STREAM_SCAN, ev, st);
-    ev = kt_begin(b, KT_STREAM_PREFIX, st);
-    hipLaunchKernelGGL(k_stream_prefix<0>, dim3(S.n), dim3(64), 0, st, J);
-    kt_end(b, KT_STREAM_PREFIX, ev, st);
-    ev = kt_begin(b, KT_STREAM_PLACE, st);
-    hipLaunchKernelGGL(k_stream_place<0>, dim3(chunks), dim3(64), 0, st, J);
-    kt_end(b, KT_STREAM_PLACE, ev, st);
+    timed_kernel(b, KT_STREAM_PLAN, st, k_stream_plan, dim3(1), dim3(64), J);
+    timed_kernel(b, KT_STREAM_SCAN, st, k_stream_scan<0>, dim3(chunks), dim3(64), J);
+    timed_kernel(b, KT_STREAM_PREFIX, st, k_stream_prefix<0>, dim3(S.n), dim3(64), J);
+    timed_kernel(b, KT_STREAM_PLACE, st, k_stream_place<0>, dim3(chunks), dim3(64), J);
     return launched(b);
 }
 static int stream_index_checked(pcamv_batch *b, const void *bytes, size_t bytes_size, long long max_units)
@@ -1753,7 +1692,7 @@ static int window_jobs_room(pcamv_batch *b)
 {
     StreamWindow &W = b->sw;
     const size_t jobs = (size_t)b->n * (size_t)W.k;
-    return grow(b, &W.d_jobs, &W.cap_jobs, stream_step_hdr((int)jobs) + jobs * (size_t)b->sx.slot);
+    return W.d_jobs.room(b, stream_step_hdr((int)jobs) + jobs * (size_t)b->sx.slot);
 }
 /* behind the kernels: the one synchronisation of an index call, the counts to the host, the RBSP slots of the steps to come */
 static int stream_index_finish(pcamv_batch *b, const uint8_t *d_bytes, size_t bytes_size, int64_t *n_slices_out)
@@ -1767,13 +1706,7 @@ static int stream_index_finish(pcamv_batch *b, const uint8_t *d_bytes, size_t by
     /* an RBSP is shorter than its unit by the header byte at least; slots at multiples of 4 */
     S.slot = (long long)((longest + 3) & ~3ULL); if (S.slot < 4) S.slot = 4;
     const size_t total = stream_step_hdr(S.n) + (size_t)S.n * (size_t)S.slot;
-    StageRing &R = b->su_stage;
-    for (int k = 0; k < NSTAGE; k++)
-        if (total > R.cap[k]) {
-            hipFree(R.d[k]); R.d[k] = NULL; R.cap[k] = 0;
-            HIPCHK(b, dalloc(&R.d[k], total));
-            R.cap[k] = total;
-        }
+    for (int k = 0; k < NSTAGE; k++) TRY(stage_room(b, b->su_stage, k, total, 0, 0));       /* (every buffer: the steps find their room) */
     S.bytes = d_bytes; S.bytes_size = (long long)bytes_size; S.ready = 1;
     b->ps.ready = 0;                                /* the sets belong to the streams of the index call before */
     b->video = 0;                                   /* (pcamv_gpu_batch_index_video* sets it behind this) */
@@ -1812,11 +1745,11 @@ extern "C" int pcamv_gpu_batch_index_streams(pcamv_batch_t *b, const pcamv_strea
     StreamIndex &S = b->sx;
     S.ready = 0;
     HIPCHK(b, hipDeviceSynchronize());              /* (steps on the buffer that is replaced may be in flight) */
-    TRY(grow(b, &S.d_own, &S.cap_own, total));
+    TRY(S.d_own.room(b, total));
     hipStream_t st = stream ? (hipStream_t)stream : b->ctx[0]->stream;
     HIPCHK(b, hipMemcpy(S.d_own, h.p, total, hipMemcpyHostToDevice));       /* (complete on return: the host block does not outlive this call) */
     TRY(stream_index_room(b, S, b->n, max_units, 0, total - hdr));
-    TRY(stream_index_run(b, S, S.d_own + hdr, total - hdr, (const long long *)S.d_own, (const long long *)S.d_own + n, 0, st));
+    TRY(stream_index_run(b, S, S.d_own + hdr, total - hdr, (const long long *)S.d_own.p, (const long long *)S.d_own.p + n, 0, st));
     return stream_index_finish(b, S.d_own + hdr, total - hdr, n_slices_out);
 }
 /* ---- one video (k_video_cut; pcamv_video.h) */
@@ -1827,22 +1760,22 @@ extern "C" int pcamv_gpu_batch_index_streams(pcamv_batch_t *b, const pcamv_strea
 /* the prefix between scan and place: k_stream_prefix, a wavefront per stream, or for one long stream the same in two levels on many */
 template <int SEL> static void video_prefix_launch(pcamv_batch *b, const StreamIndex &S, const StreamJobs &J, hipStream_t st)
 {
-    const int ev = kt_begin(b, KT_STREAM_PREFIX, st);
-    if (S.n == 1 && S.d_keep) {
-        SiChunk *B = S.d_keep + S.max_chunks;
-        const unsigned blocks = (unsigned)((S.max_chunks + VP_BLOCK - 1) / VP_BLOCK);
-        hipLaunchKernelGGL(k_video_prefix_local, dim3(blocks), dim3(64), 0, st, J, B);
-        hipLaunchKernelGGL(k_video_prefix_top<SEL>, dim3(1), dim3(64), 0, st, J, B);
-        hipLaunchKernelGGL(k_video_prefix_apply, dim3((unsigned)((S.max_chunks + 63) / 64)), dim3(64), 0, st, J, B);
-    } else hipLaunchKernelGGL(k_stream_prefix<SEL>, dim3(S.n), dim3(64), 0, st, J);
-    kt_end(b, KT_STREAM_PREFIX, ev, st);
+    timed(b, KT_STREAM_PREFIX, st, [&] {
+        if (S.n == 1 && S.d_keep) {
+            SiChunk *B = S.d_keep + S.max_chunks;
+            const unsigned blocks = (unsigned)((S.max_chunks + VP_BLOCK - 1) / VP_BLOCK);
+            hipLaunchKernelGGL(k_video_prefix_local, dim3(blocks), dim3(64), 0, st, J, B);
+            hipLaunchKernelGGL(k_video_prefix_top<SEL>, dim3(1), dim3(64), 0, st, J, B);
+            hipLaunchKernelGGL(k_video_prefix_apply, dim3((unsigned)((S.max_chunks + 63) / 64)), dim3(64), 0, st, J, B);
+        } else hipLaunchKernelGGL(k_stream_prefix<SEL>, dim3(S.n), dim3(64), 0, st, J);
+    });
 }
 static int video_units_run(pcamv_batch *b, StreamIndex &S, const uint8_t *d_bytes, size_t bytes_size, const long long *d_off, const long long *d_len, long long *h_units,
                            hipStream_t st)
 {
     const size_t n = (size_t)S.n;
     TRY(stream_index_room(b, S, S.n, 1, 0, bytes_size));
-    TRY(grow(b, &S.d_keep, &S.cap_keep, (size_t)S.max_chunks + (size_t)(S.max_chunks + VP_BLOCK - 1) / VP_BLOCK));    /* (the kept summaries, then the blocks') */
+    TRY(S.d_keep.room(b, (size_t)S.max_chunks + (size_t)(S.max_chunks + VP_BLOCK - 1) / VP_BLOCK));    /* (the kept summaries, then the blocks') */
     HIPCHK(b, hipMemcpyAsync(S.d_at, d_off, 8 * n, hipMemcpyDeviceToDevice, st));
     HIPCHK(b, hipMemcpyAsync(S.d_at + n, d_len, 8 * n, hipMemcpyDeviceToDevice, st));
     HIPCHK(b, hipMemsetAsync(S.d_longest, 0, 8, st));
@@ -1852,12 +1785,8 @@ static int video_units_run(pcamv_batch *b, StreamIndex &S, const uint8_t *d_byte
     J.table = S.d_table; J.max_units = 0; J.stride = 0; J.all = 1;
     J.n_units = S.d_at + 3 * n; J.n_slices = S.d_at + 4 * n; J.cursor = S.d_at + 5 * n; J.longest = S.d_longest; J.n = S.n;
     const unsigned chunks = (unsigned)S.max_chunks;
-    int ev = kt_begin(b, KT_STREAM_PLAN, st);
-    hipLaunchKernelGGL(k_stream_plan, dim3(1), dim3(64), 0, st, J);
-    kt_end(b, KT_STREAM_PLAN, ev, st);
-    ev = kt_begin(b, KT_STREAM_SCAN, st);
-    hipLaunchKernelGGL(k_stream_scan<0>, dim3(chunks), dim3(64), 0, st, J);
-    kt_end(b, KT_STREAM_SCAN, ev, st);
+    timed_kernel(b, KT_STREAM_PLAN, st, k_stream_plan, dim3(1), dim3(64), J);
+    timed_kernel(b, KT_STREAM_SCAN, st, k_stream_scan<0>, dim3(chunks), dim3(64), J);
     HIPCHK(b, hipMemcpyAsync(S.d_keep, S.d_chunks, (size_t)S.max_chunks * sizeof(SiChunk), hipMemcpyDeviceToDevice, st));
     video_prefix_launch<0>(b, S, J, st);
     TRY(launched(b));
@@ -1867,13 +1796,11 @@ static int video_units_run(pcamv_batch *b, StreamIndex &S, const uint8_t *d_byte
     for (size_t v = 0; v < n; v++) if (h_units[v] > most) most = h_units[v];
     if (most > (1LL << 28)) return fail(b, PCAMV_ENOMEM, "a video of %lld units: the table of all of them is limited to 2^28 entries", most);
     S.max_units = most; S.stride = most;
-    TRY(grow(b, &S.d_table, &S.cap_table, n * (size_t)most));
+    TRY(S.d_table.room(b, n * (size_t)most));
     J.table = S.d_table; J.max_units = most; J.stride = most;
     HIPCHK(b, hipMemcpyAsync(S.d_chunks, S.d_keep, (size_t)S.max_chunks * sizeof(SiChunk), hipMemcpyDeviceToDevice, st));
     video_prefix_launch<0>(b, S, J, st);
-    ev = kt_begin(b, KT_STREAM_PLACE, st);
-    hipLaunchKernelGGL(k_stream_place<0>, dim3(chunks), dim3(64), 0, st, J);
-    kt_end(b, KT_STREAM_PLACE, ev, st);
+    timed_kernel(b, KT_STREAM_PLACE, st, k_stream_place<0>, dim3(chunks), dim3(64), J);
     return launched(b);
 }
 static VideoCut video_cut_jobs(const StreamIndex &S)
@@ -1891,16 +1818,14 @@ static int index_video_run(pcamv_batch *b, const uint8_t *d_bytes, size_t bytes_
     StreamIndex &V = b->vx;
     b->video = 0; b->sx.ready = 0; b->ps.ready = 0;
     /* (the video's own tables and the contexts' (off, len) are read by this call's kernels and by stream_param_sets alone, which waits) */
-    TRY(grow(b, &b->d_vcut, &b->cap_vcut, 2 * n + 2));
+    TRY(b->d_vcut.room(b, 2 * n + 2));
     V.n = 1;
     long long units = 0;
     TRY(video_units_run(b, V, d_bytes, bytes_size, d_off, d_len, &units, st));
     if (units < 0) return fail(b, PCAMV_EINVAL, "the video does not lie inside the buffer");
     VideoCut Q = video_cut_jobs(V);
     Q.first = first_gop; Q.ctx_off = b->d_vcut; Q.ctx_len = b->d_vcut + n; Q.n_ctx = b->n; Q.n_gops = b->d_vcut + 2 * n; Q.preamble = b->d_vcut + 2 * n + 1;
-    const int ev = kt_begin(b, KT_VIDEO_CUT, st);
-    hipLaunchKernelGGL(k_video_cut, dim3(1), dim3(64), 0, st, Q);
-    kt_end(b, KT_VIDEO_CUT, ev, st);
+    timed_kernel(b, KT_VIDEO_CUT, st, k_video_cut, dim3(1), dim3(64), Q);
     TRY(stream_index_room(b, b->sx, b->n, max_units, 0, bytes_size));
     TRY(stream_index_run(b, b->sx, d_bytes, bytes_size, Q.ctx_off, Q.ctx_len, 0, st));
     TRY(stream_index_finish(b, d_bytes, bytes_size, n_slices_out));
@@ -1927,12 +1852,12 @@ extern "C" int pcamv_gpu_batch_index_video(pcamv_batch_t *b, const uint8_t *byte
     StreamIndex &S = b->sx;
     S.ready = 0;
     HIPCHK(b, hipDeviceSynchronize());              /* (steps on the buffer that is replaced may be in flight) */
-    TRY(grow(b, &S.d_own, &S.cap_own, 16 + len));
+    TRY(S.d_own.room(b, 16 + len));
     const long long at[2] = {0, (long long)len};
     HIPCHK(b, hipMemcpy(S.d_own, at, 16, hipMemcpyHostToDevice));
     if (len) HIPCHK(b, hipMemcpy(S.d_own + 16, bytes, len, hipMemcpyHostToDevice));
     hipStream_t st = stream ? (hipStream_t)stream : b->ctx[0]->stream;
-    return index_video_run(b, S.d_own + 16, len, (const long long *)S.d_own, (const long long *)S.d_own + 1, first_gop, max_units, n_gops, preamble, n_slices_out, st);
+    return index_video_run(b, S.d_own + 16, len, (const long long *)S.d_own.p, (const long long *)S.d_own.p + 1, first_gop, max_units, n_gops, preamble, n_slices_out, st);
 }
 /* the parity probe of the cut: n videos of one host buffer, every video's units listed and walked by a wavefront of its own */
 extern "C" int pcamv_gpu_video_gops_device(pcamv_ctx_t *c, const uint8_t *bytes, size_t bytes_size, const int64_t *off, const int64_t *len, int n,
@@ -1941,36 +1866,25 @@ extern "C" int pcamv_gpu_video_gops_device(pcamv_ctx_t *c, const uint8_t *bytes,
     if (!c || (!bytes && bytes_size) || !off || !len || !gops_out || !n_gops || !preamble || n < 1 || n > (1 << 20) || cap_per_video < 0 ||
         cap_per_video > (1LL << 24) || bytes_size > ((size_t)1 << 40)) return PCAMV_EINVAL;
     pcamv_batch *b = c->self;
-    HIPCHK(c, hipSetDevice(c->device));
     const size_t entries = (size_t)n * (size_t)(cap_per_video + PCAMV_UNIT_GUARD);
-    DevTmp<uint8_t> d_bytes; DevTmp<long long> d_at; DevTmp<pcamv_gop_t> d_gops;
-    HIPCHK(c, d_bytes.alloc(bytes_size ? bytes_size : 1)); HIPCHK(c, d_at.alloc(4 * (size_t)n)); HIPCHK(c, d_gops.alloc(entries));
-    if (bytes_size) HIPCHK(c, hipMemcpy(d_bytes, bytes, bytes_size, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(d_at, off, sizeof(int64_t) * n, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(d_at + n, len, sizeof(int64_t) * n, hipMemcpyHostToDevice));
+    DevBuf<uint8_t> d_bytes; DevBuf<long long> d_at; DevBuf<pcamv_gop_t> d_gops;
+    TRY(probe_upload(c, d_bytes, d_at, bytes, bytes_size, off, len, n, 4)); TRY(d_gops.room(c, entries));
     HIPCHK(c, hipMemset(d_gops, 0xA5, entries * sizeof(pcamv_gop_t)));
     HostTmp<long long> h_units((size_t)n);
     if (!h_units) return fail(c, PCAMV_ENOMEM, "no memory for the counts of %d videos", n);
-    StreamIndex S = StreamIndex();
+    StreamIndex S{};            /* (the probe's own index: freed with the scope) */
     S.n = n;
-    int rc = video_units_run(b, S, d_bytes, bytes_size, d_at, d_at + n, h_units, c->stream);
-    hipError_t e = hipSuccess;
-    if (!rc) {
-        VideoCut Q = video_cut_jobs(S);
-        Q.gops = d_gops; Q.gstride = cap_per_video + PCAMV_UNIT_GUARD; Q.cap = cap_per_video;
-        Q.n_gops = d_at + 2 * (size_t)n; Q.preamble = d_at + 3 * (size_t)n;
-        const int ev = kt_begin(b, KT_VIDEO_CUT, c->stream);
-        hipLaunchKernelGGL(k_video_cut, dim3(n), dim3(64), 0, c->stream, Q);
-        kt_end(b, KT_VIDEO_CUT, ev, c->stream);
-        rc = launched(b);
-    }
-    if (!rc) e = hipStreamSynchronize(c->stream);
-    if (!rc && e == hipSuccess) e = hipMemcpy(gops_out, d_gops, entries * sizeof(pcamv_gop_t), hipMemcpyDeviceToHost);
-    if (!rc && e == hipSuccess) e = hipMemcpy(n_gops, d_at + 2 * (size_t)n, 8 * (size_t)n, hipMemcpyDeviceToHost);
-    if (!rc && e == hipSuccess) e = hipMemcpy(preamble, d_at + 3 * (size_t)n, 8 * (size_t)n, hipMemcpyDeviceToHost);
-    stream_index_free(S);
-    if (e != hipSuccess) return fail(c, PCAMV_EHIP, "video_gops_device: %s", hipGetErrorString(e));
-    return on_behalf(c, b, rc);
+    TRY(on_behalf(c, b, video_units_run(b, S, d_bytes, bytes_size, d_at, d_at + n, h_units, c->stream)));
+    VideoCut Q = video_cut_jobs(S);
+    Q.gops = d_gops; Q.gstride = cap_per_video + PCAMV_UNIT_GUARD; Q.cap = cap_per_video;
+    Q.n_gops = d_at + 2 * (size_t)n; Q.preamble = d_at + 3 * (size_t)n;
+    timed_kernel(b, KT_VIDEO_CUT, c->stream, k_video_cut, dim3(n), dim3(64), Q);
+    TRY(on_behalf(c, b, launched(b)));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(gops_out, d_gops, entries * sizeof(pcamv_gop_t), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(n_gops, d_at + 2 * (size_t)n, 8 * (size_t)n, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(preamble, d_at + 3 * (size_t)n, 8 * (size_t)n, hipMemcpyDeviceToHost));
+    return 0;
 }
 /* the entropy mode of a *_sets call is the contexts' own: 1 CAVLC, 0 CABAC (a batch holds contexts of one mode: pcamv_gpu_batch_create) */
 static int sets_mode(pcamv_batch *b, int *cavlc)
@@ -1986,15 +1900,11 @@ static void slice_header_launch(pcamv_batch *b, StreamStep &J, const pcamv_strea
     J.sets = NULL; J.sets_k = sets_k; J.want_cabac = !cavlc; J.entropy = J.frame_num + 2 * jobs;
     if (params) {
         J.P = *params;
-        const int ev = kt_begin(b, KT_SLICE_HEADER, st);
-        hipLaunchKernelGGL(k_slice_header, dim3((unsigned)((jobs + 63) / 64)), dim3(64), 0, st, J);
-        kt_end(b, KT_SLICE_HEADER, ev, st);
+        timed_kernel(b, KT_SLICE_HEADER, st, k_slice_header, dim3((unsigned)((jobs + 63) / 64)), dim3(64), J);
     } else {
         J.P = pcamv_stream_params_t();
         J.sets = b->ps.d_sets;
-        const int ev = kt_begin(b, KT_SLICE_HEADER_SETS, st);
-        hipLaunchKernelGGL(k_slice_header_sets, dim3((unsigned)((jobs + 63) / 64)), dim3(64), 0, st, J);
-        kt_end(b, KT_SLICE_HEADER_SETS, ev, st);
+        timed_kernel(b, KT_SLICE_HEADER_SETS, st, k_slice_header_sets, dim3((unsigned)((jobs + 63) / 64)), dim3(64), J);
     }
 }
 static int extract_stream_step(pcamv_batch_t *b, const pcamv_stream_params_t *params, float emrate, int32_t *nal_header, void *stream)
@@ -2017,17 +1927,13 @@ static int extract_stream_step(pcamv_batch_t *b, const pcamv_stream_params_t *pa
     J.off = (long long *)d; J.len = J.off + n; J.start_bit = J.len + n;
     J.qp = (int *)(J.start_bit + n); J.first = J.qp + n; J.frame_num = J.first + n; J.nal_header = nal_header ? nal_header : J.frame_num + n;
     J.n = b->n; J.cursor_was = NULL; J.k = 0;
-    int ev = kt_begin(b, KT_STREAM_UNIT, st);
-    hipLaunchKernelGGL(k_stream_unit, dim3(b->n), dim3(64), 0, st, J);
-    kt_end(b, KT_STREAM_UNIT, ev, st);
+    timed_kernel(b, KT_STREAM_UNIT, st, k_stream_unit, dim3(b->n), dim3(64), J);
     slice_header_launch(b, J, params, cavlc, 1, n, st);
     SliceJobs SJ;
     SJ.bytes = J.rbsp; SJ.bytes_size = J.rbsp_size; SJ.off = J.off; SJ.len = J.len; SJ.start_bit = J.start_bit; SJ.qp = cavlc ? NULL : J.qp;
     const int rc = slices_run(b, SJ, cavlc, 1, emrate, st, J.first);
     /* the parser refused what an earlier stage had failed (len -1) with its own code: the first stage's code takes its place */
-    ev = kt_begin(b, KT_STREAM_STATUS, st);
-    hipLaunchKernelGGL(k_stream_status, dim3((b->n + 63) / 64), dim3(64), 0, st, J.first, b->d_sstat, b->n, (int *)NULL, 0);
-    kt_end(b, KT_STREAM_STATUS, ev, st);
+    timed_kernel(b, KT_STREAM_STATUS, st, k_stream_status, dim3((b->n + 63) / 64), dim3(64), J.first, b->d_sstat, b->n, (int *)NULL, 0);
     const int rc1 = launched(b), rc2 = stage_release(b, b->su_stage, k, st);        /* released on every path */
     return rc ? rc : rc1 ? rc1 : rc2;
 }
@@ -2042,20 +1948,17 @@ extern "C" int pcamv_gpu_batch_extract_stream_step_sets(pcamv_batch_t *b, float 
     return extract_stream_step(b, NULL, emrate, nal_header, stream);
 }
 /* ---- a window of slice units per context in one launch (k_stream_window_unit, k_extract_count, k_extract_chain) */
-extern "C" int pcamv_gpu_batch_stream_window(pcamv_batch_t *b, int k)
+/* the window as a new batch has it: what it owned is freed (which waits for the device), every field is zero again.  Destroyed and
+ * value-initialised in place, so that no list of its members stands here: they are buffers, a ring and plain data, whose making cannot fail */
+static void window_release(StreamWindow &W) { W.~StreamWindow(); new (&W) StreamWindow(); }
+/* the memory of a window of k on a released one, for pcamv_gpu_batch_stream_window (below); a failure leaves the clean-up to it */
+static int window_reserve(pcamv_batch *b, int k)
 {
-    if (!b || k < 0 || k > PCAMV_STREAM_WINDOW_MAX) return fail(b, PCAMV_EINVAL, "a window holds 1 to %d units per context (0 releases it)", PCAMV_STREAM_WINDOW_MAX);
-    HIPCHK(b, hipSetDevice(b->device));
-    TRY(batch_live(b));
-    HIPCHK(b, hipDeviceSynchronize());
     StreamWindow &W = b->sw;
-    stream_window_free(W);
-    for (int i = 0; i < b->n; i++) if (b->ctx[i]->win == b) b->ctx[i]->win = NULL;
-    if (!k) return 0;
     if (!b->sx.ready) return fail(b, PCAMV_EINVAL, "no byte streams were handed to this batch yet (pcamv_gpu_batch_index_streams*): a window is reserved behind an index call");
     const FrameDev &F = b->ctx[0]->F;
     const int cavlc = !F.b_cabac, cap = b->ctx[0]->cap;
-    TRY(entropy_setup(b, &b->d_sstat, &b->d_sp_tab, &b->d_sp_scratch, cavlc, SP_NCTX));
+    TRY(entropy_setup(b, b->d_sstat, b->d_sp_tab, b->d_sp_scratch, cavlc, SP_NCTX));
     for (int i = 0; i < b->n; i++) {            /* what the first slice call of a context makes: here, so that the window call finds it */
         pcamv_ctx *c = b->ctx[i];
         int rc_c = rx_scratch(c);
@@ -2064,25 +1967,30 @@ extern "C" int pcamv_gpu_batch_stream_window(pcamv_batch_t *b, int k)
     }
     const size_t jobs = (size_t)b->n * (size_t)k, rec = (size_t)F.n_mb + SLICE_GUARD_MBS;
     W.k = k;
-    int rc = 0;
-    hipError_t e = dalloc(&W.d_mbs, jobs * rec);
-    if (e == hipSuccess) e = dalloc(&W.d_stego, jobs * (size_t)cap);
-    if (e == hipSuccess) e = dalloc(&W.d_hdr, jobs * 8);
-    if (e == hipSuccess) e = dalloc(&W.d_cols, jobs * 2 * STC_MAXW);
-    if (e == hipSuccess) e = dalloc(&W.d_stat, jobs);
-    if (e == hipSuccess && F.mb_w > b->sp_lds_cols) e = dalloc(&W.d_scratch, jobs * row_bytes(b, cavlc));
-    if (e == hipSuccess) e = dalloc(&W.d_cursor_was, (size_t)b->n);
-    if (e == hipSuccess) e = dalloc(&W.d_X, jobs * NSTAGE);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&W.h_X, sizeof(ExtractDev) * jobs * NSTAGE, hipHostMallocDefault);
-    for (int r = 0; r < NSTAGE && e == hipSuccess; r++) e = hipEventCreateWithFlags(&W.desc_done[r], hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&W.done, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipMemset(W.d_hdr, 0, jobs * 8 * sizeof(int));
-    if (e == hipSuccess) e = hipMemset(W.d_stat, 0, jobs * sizeof(int));
+    /* (a device without the memory for the window is PCAMV_ENOMEM here: the caller can reserve a smaller one) */
+    TRY(W.d_mbs.room(b, jobs * rec, PCAMV_ENOMEM)); TRY(W.d_stego.room(b, jobs * (size_t)cap, PCAMV_ENOMEM));
+    TRY(W.d_hdr.room(b, jobs * 8, PCAMV_ENOMEM)); TRY(W.d_cols.room(b, jobs * 2 * STC_MAXW, PCAMV_ENOMEM)); TRY(W.d_stat.room(b, jobs, PCAMV_ENOMEM));
+    if (F.mb_w > b->sp_lds_cols) TRY(W.d_scratch.room(b, jobs * row_bytes(b, cavlc), PCAMV_ENOMEM));
+    TRY(W.d_cursor_was.room(b, (size_t)b->n, PCAMV_ENOMEM));
+    TRY(W.d_X.room(b, jobs * NSTAGE, PCAMV_ENOMEM)); TRY(W.h_X.room(b, jobs * NSTAGE, PCAMV_ENOMEM));
+    HIPCHK(b, hipEventCreateWithFlags(&W.done, hipEventDisableTiming));
+    HIPCHK(b, hipMemset(W.d_hdr, 0, jobs * 8 * sizeof(int)));
+    HIPCHK(b, hipMemset(W.d_stat, 0, jobs * sizeof(int)));
     /* the guard behind every slot's records, as rx_mbs leaves it behind a context's */
-    if (e == hipSuccess) e = hipMemset2D(W.d_mbs + F.n_mb, rec * sizeof(pcamv_mb_t), 0xA5, SLICE_GUARD_MBS * sizeof(pcamv_mb_t), jobs);
-    if (e == hipSuccess) rc = window_jobs_room(b);
-    if (e != hipSuccess) rc = fail(b, e == hipErrorOutOfMemory ? PCAMV_ENOMEM : PCAMV_EHIP, "a window of %d units for %d contexts: %s", k, b->n, hipGetErrorString(e));
-    if (rc) stream_window_free(W);
+    HIPCHK(b, hipMemset2D(W.d_mbs + F.n_mb, rec * sizeof(pcamv_mb_t), 0xA5, SLICE_GUARD_MBS * sizeof(pcamv_mb_t), jobs));
+    return window_jobs_room(b);
+}
+extern "C" int pcamv_gpu_batch_stream_window(pcamv_batch_t *b, int k)
+{
+    if (!b || k < 0 || k > PCAMV_STREAM_WINDOW_MAX) return fail(b, PCAMV_EINVAL, "a window holds 1 to %d units per context (0 releases it)", PCAMV_STREAM_WINDOW_MAX);
+    HIPCHK(b, hipSetDevice(b->device));
+    TRY(batch_live(b));
+    HIPCHK(b, hipDeviceSynchronize());
+    window_release(b->sw);
+    for (int i = 0; i < b->n; i++) if (b->ctx[i]->win == b) b->ctx[i]->win = NULL;
+    if (!k) return 0;
+    const int rc = window_reserve(b, k);
+    if (rc) window_release(b->sw);
     return rc;
 }
 static int extract_stream_window(pcamv_batch_t *b, const pcamv_stream_params_t *params, float emrate, int k, int32_t *nal_header, void *stream)
@@ -2100,11 +2008,10 @@ static int extract_stream_window(pcamv_batch_t *b, const pcamv_stream_params_t *
     const FrameDev &F = b->ctx[0]->F;
     const size_t n = (size_t)b->n, jobs = n * (size_t)k, hdr = stream_step_hdr((int)jobs), rec = (size_t)F.n_mb + SLICE_GUARD_MBS;
     const int cap = b->ctx[0]->cap;
-    if (hdr + jobs * (size_t)S.slot > W.cap_jobs) return fail(b, PCAMV_EHIP, "the window's RBSP slots were not sized by the last index call");
-    if (W.used) HIPCHK(b, hipStreamWaitEvent(st, W.done, 0));           /* the call before this one read and wrote the same slots, perhaps on another stream */
-    const int r = W.head;
-    W.head = (r + 1) % NSTAGE;
-    if (W.desc_used[r]) HIPCHK(b, hipEventSynchronize(W.desc_done[r]));  /* (as a step's descriptor ring: the call before the last) */
+    if (hdr + jobs * (size_t)S.slot > W.d_jobs.cap) return fail(b, PCAMV_EHIP, "the window's RBSP slots were not sized by the last index call");
+    if (W.used) HIPCHK(b, hipStreamWaitEvent(st, W.done, 0));           /* the call before this one read and wrote the same slots, perhaps on another stream: before anything is written */
+    int r;
+    TRY(ring_take(b, W.desc, &r));                                      /* (as a step's descriptor ring: the call before the last) */
     ExtractDev *hX = W.h_X + (size_t)r * n * (size_t)W.k, *dX = W.d_X + (size_t)r * n * (size_t)W.k;
     for (size_t i = 0; i < n; i++)
         for (size_t w = 0; w < (size_t)k; w++) {
@@ -2116,8 +2023,8 @@ static int extract_stream_window(pcamv_batch_t *b, const pcamv_stream_params_t *
             if (b->d_mrx) { X.rx = b->d_mrx; X.rx_cap_bits = b->mrx_bits; }
         }
     HIPCHK(b, hipMemcpyAsync(dX, hX, sizeof(ExtractDev) * jobs, hipMemcpyHostToDevice, st));
-    HIPCHK(b, hipEventRecord(W.desc_done[r], st));
-    W.desc_used[r] = 1;
+    /* (the slot's event is recorded once, by ring_release behind the last kernel, and not here behind the copy as well, as stage_send does
+     * for a staging buffer: only the copy below can return in between, and only with an error of the runtime, which the call reports) */
     HIPCHK(b, hipMemcpyAsync(W.d_cursor_was, S.d_at + 5 * n, 8 * n, hipMemcpyDeviceToDevice, st));
     uint8_t *d = W.d_jobs;
     StreamStep J;
@@ -2127,30 +2034,20 @@ static int extract_stream_window(pcamv_batch_t *b, const pcamv_stream_params_t *
     J.off = (long long *)d; J.len = J.off + jobs; J.start_bit = J.len + jobs;
     J.qp = (int *)(J.start_bit + jobs); J.first = J.qp + jobs; J.frame_num = J.first + jobs; J.nal_header = nal_header ? nal_header : J.frame_num + jobs;
     J.n = (int)jobs; J.cursor_was = W.d_cursor_was; J.k = k;
-    int ev = kt_begin(b, KT_STREAM_WINDOW_UNIT, st);
-    hipLaunchKernelGGL(k_stream_window_unit, dim3((unsigned)jobs), dim3(64), 0, st, J);
-    kt_end(b, KT_STREAM_WINDOW_UNIT, ev, st);
+    timed_kernel(b, KT_STREAM_WINDOW_UNIT, st, k_stream_window_unit, dim3((unsigned)jobs), dim3(64), J);
     slice_header_launch(b, J, params, cavlc, k, jobs, st);
     SliceJobs SJ;
     SJ.bytes = J.rbsp; SJ.bytes_size = J.rbsp_size; SJ.off = J.off; SJ.len = J.len; SJ.start_bit = J.start_bit; SJ.qp = cavlc ? NULL : J.qp;
     slice_launch(b, dX, SJ, cavlc, st, (int)jobs, W.d_scratch);
-    ev = kt_begin(b, KT_EXTRACT_COUNT, st);
-    hipLaunchKernelGGL(k_extract_count, dim3((unsigned)jobs), dim3(1024), 0, st, dX);
-    kt_end(b, KT_EXTRACT_COUNT, ev, st);
+    timed_kernel(b, KT_EXTRACT_COUNT, st, k_extract_count, dim3((unsigned)jobs), dim3(1024), dX);
     if (b->d_mrx) extract_message_chain_launch(b, dX, k, J.first, st);
-    else {
-        ev = kt_begin(b, KT_EXTRACT_CHAIN, st);
-        hipLaunchKernelGGL(k_extract_chain, dim3((b->n + 63) / 64), dim3(64), 0, st, dX, b->n, k);
-        kt_end(b, KT_EXTRACT_CHAIN, ev, st);
-    }
+    else timed_kernel(b, KT_EXTRACT_CHAIN, st, k_extract_chain, dim3((b->n + 63) / 64), dim3(64), dX, b->n, k);
     extract_bits_launch(b, dX, (int)jobs, cap, emrate, st);
-    ev = kt_begin(b, KT_STREAM_STATUS, st);
-    hipLaunchKernelGGL(k_stream_status, dim3((unsigned)((jobs + 63) / 64)), dim3(64), 0, st, J.first, W.d_stat, (int)jobs, b->d_sstat, k);
-    kt_end(b, KT_STREAM_STATUS, ev, st);
+    timed_kernel(b, KT_STREAM_STATUS, st, k_stream_status, dim3((unsigned)((jobs + 63) / 64)), dim3(64), J.first, W.d_stat, (int)jobs, b->d_sstat, k);
     W.k_last = k;
     for (int i = 0; i < b->n; i++) { b->ctx[i]->win = b; b->ctx[i]->win_i = i; }
     const int rc = launched(b);
-    HIPCHK(b, hipEventRecord(W.desc_done[r], st));          /* the descriptors are read until here */
+    TRY(ring_release(b, W.desc, r, st));                    /* the descriptors are read until here: behind the last kernel that reads them */
     HIPCHK(b, hipEventRecord(W.done, st));
     W.used = 1;
     return rc;
@@ -2192,30 +2089,23 @@ extern "C" int pcamv_gpu_index_streams_probe(pcamv_ctx_t *c, const uint8_t *byte
     if (!c || (!bytes && bytes_size) || !off || !len || !units_out || !n_units || !n_slices || n < 1 || cap_per_stream < 0 || cap_per_stream > (1LL << 24) ||
         bytes_size > ((size_t)1 << 40)) return PCAMV_EINVAL;
     pcamv_batch *b = c->self;
-    HIPCHK(c, hipSetDevice(c->device));
-    DevTmp<uint8_t> d_bytes; DevTmp<long long> d_at;
-    HIPCHK(c, d_bytes.alloc(bytes_size ? bytes_size : 1)); HIPCHK(c, d_at.alloc(2 * (size_t)n));
-    if (bytes_size) HIPCHK(c, hipMemcpy(d_bytes, bytes, bytes_size, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(d_at, off, sizeof(int64_t) * n, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(d_at + n, len, sizeof(int64_t) * n, hipMemcpyHostToDevice));
-    StreamIndex S = StreamIndex();
-    int rc = stream_index_room(b, S, n, cap_per_stream, PCAMV_UNIT_GUARD, bytes_size);
+    DevBuf<uint8_t> d_bytes; DevBuf<long long> d_at;
+    TRY(probe_upload(c, d_bytes, d_at, bytes, bytes_size, off, len, n, 2));
+    StreamIndex S{};            /* (the probe's own index: freed with the scope) */
+    TRY(on_behalf(c, b, stream_index_room(b, S, n, cap_per_stream, PCAMV_UNIT_GUARD, bytes_size)));
     const size_t entries = (size_t)n * (size_t)(cap_per_stream + PCAMV_UNIT_GUARD);
-    hipError_t e = hipSuccess;
-    if (!rc) e = hipMemsetAsync(S.d_table, 0xA5, entries * sizeof(pcamv_unit_t), c->stream);
-    if (!rc && e == hipSuccess) rc = stream_index_run(b, S, d_bytes, bytes_size, d_at, d_at + n, 1, c->stream);
-    if (!rc && e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (!rc && e == hipSuccess) e = hipMemcpy(units_out, S.d_table, entries * sizeof(pcamv_unit_t), hipMemcpyDeviceToHost);
-    if (!rc && e == hipSuccess) e = hipMemcpy(n_units, S.d_at + 3 * (size_t)n, 8 * (size_t)n, hipMemcpyDeviceToHost);
-    if (!rc && e == hipSuccess) e = hipMemcpy(n_slices, S.d_at + 4 * (size_t)n, 8 * (size_t)n, hipMemcpyDeviceToHost);
+    HIPCHK(c, hipMemsetAsync(S.d_table, 0xA5, entries * sizeof(pcamv_unit_t), c->stream));      /* (guards included: they come back as they were left) */
+    TRY(on_behalf(c, b, stream_index_run(b, S, d_bytes, bytes_size, d_at, d_at + n, 1, c->stream)));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(units_out, S.d_table, entries * sizeof(pcamv_unit_t), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(n_units, S.d_at + 3 * (size_t)n, 8 * (size_t)n, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(n_slices, S.d_at + 4 * (size_t)n, 8 * (size_t)n, hipMemcpyDeviceToHost));
     HostTmp<uint8_t> back(bytes_size ? bytes_size : 1);
-    if (!rc && e == hipSuccess && back && bytes_size) {
-        e = hipMemcpy(back.p, d_bytes, bytes_size, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && memcmp(back.p, bytes, bytes_size)) rc = fail(b, PCAMV_EHIP, "the index kernels changed the streams' bytes");
+    if (back && bytes_size) {
+        HIPCHK(c, hipMemcpy(back.p, d_bytes, bytes_size, hipMemcpyDeviceToHost));
+        if (memcmp(back.p, bytes, bytes_size)) return fail(c, PCAMV_EHIP, "the index kernels changed the streams' bytes");
     }
-    stream_index_free(S);
-    if (e != hipSuccess) return fail(c, PCAMV_EHIP, "index_streams_probe: %s", hipGetErrorString(e));
-    return on_behalf(c, b, rc);
+    return 0;
 }
 /* the parity probe of k_slice_header: n RBSPs of one host buffer, one lane each */
 extern "C" int pcamv_gpu_slice_headers_device(pcamv_ctx_t *c, const uint8_t *bytes, size_t bytes_size, const int64_t *off, const int64_t *len,
@@ -2225,21 +2115,15 @@ extern "C" int pcamv_gpu_slice_headers_device(pcamv_ctx_t *c, const uint8_t *byt
     if (!c || (!bytes && bytes_size) || !off || !len || !nal_header || !params || !rc_out || !start_bit || !slice_qp || !frame_num || n < 1 ||
         bytes_size > ((size_t)1 << 40)) return PCAMV_EINVAL;
     pcamv_batch *b = c->self;
-    HIPCHK(c, hipSetDevice(c->device));
-    DevTmp<uint8_t> d_bytes; DevTmp<long long> d_at; DevTmp<int> d_int;
-    HIPCHK(c, d_bytes.alloc(bytes_size ? bytes_size : 1)); HIPCHK(c, d_at.alloc(3 * (size_t)n)); HIPCHK(c, d_int.alloc(4 * (size_t)n));
-    if (bytes_size) HIPCHK(c, hipMemcpy(d_bytes, bytes, bytes_size, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(d_at, off, sizeof(int64_t) * n, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(d_at + n, len, sizeof(int64_t) * n, hipMemcpyHostToDevice));
+    DevBuf<uint8_t> d_bytes; DevBuf<long long> d_at; DevBuf<int> d_int;
+    TRY(probe_upload(c, d_bytes, d_at, bytes, bytes_size, off, len, n, 3)); TRY(d_int.room(c, 4 * (size_t)n));
     HIPCHK(c, hipMemset(d_int, 0, sizeof(int) * 4 * (size_t)n));
     HIPCHK(c, hipMemcpy(d_int + 2 * (size_t)n, nal_header, sizeof(int32_t) * n, hipMemcpyHostToDevice));
     StreamStep J = StreamStep();
     J.rbsp = d_bytes; J.rbsp_size = (long long)bytes_size; J.off = d_at; J.len = d_at + n; J.start_bit = d_at + 2 * (size_t)n;
     J.qp = d_int; J.first = d_int + n; J.nal_header = d_int + 2 * (size_t)n; J.frame_num = d_int + 3 * (size_t)n;
     J.P = *params; J.n = n;
-    const int ev = kt_begin(b, KT_SLICE_HEADER, c->stream);
-    hipLaunchKernelGGL(k_slice_header, dim3((n + 63) / 64), dim3(64), 0, c->stream, J);
-    kt_end(b, KT_SLICE_HEADER, ev, c->stream);
+    timed_kernel(b, KT_SLICE_HEADER, c->stream, k_slice_header, dim3((n + 63) / 64), dim3(64), J);
     TRY(on_behalf(c, b, launched(b)));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(start_bit, J.start_bit, sizeof(int64_t) * n, hipMemcpyDeviceToHost));
@@ -2256,9 +2140,7 @@ static int pset_run(pcamv_batch *b, const StreamIndex &S, const uint8_t *d_bytes
 {
     const size_t n = (size_t)S.n;
     P.ready = 0;
-    TRY(grow(b, &P.d_table, &P.cap_table, n * PCAMV_PSET_UNITS_MAX));
-    TRY(grow(b, &P.d_cnt, &P.cap_cnt, 3 * n + 1));
-    TRY(grow(b, &P.d_sets, &P.cap_sets, n));
+    TRY(P.d_table.room(b, n * PCAMV_PSET_UNITS_MAX)); TRY(P.d_cnt.room(b, 3 * n + 1)); TRY(P.d_sets.room(b, n));
     HIPCHK(b, hipMemsetAsync(P.d_cnt, 0, 8 * (3 * n + 1), st));
     StreamJobs J;
     J.bytes = d_bytes; J.bytes_size = bytes_size; J.off = S.d_at; J.len = S.d_at + n;
@@ -2266,13 +2148,9 @@ static int pset_run(pcamv_batch *b, const StreamIndex &S, const uint8_t *d_bytes
     J.table = P.d_table; J.max_units = PCAMV_PSET_UNITS_MAX; J.stride = PCAMV_PSET_UNITS_MAX; J.all = 0;
     J.n_units = P.d_cnt; J.n_slices = P.d_cnt + n; J.cursor = NULL; J.longest = NULL; J.n = S.n;
     const unsigned chunks = (unsigned)S.max_chunks;
-    int ev = kt_begin(b, KT_STREAM_SCAN, st);
-    hipLaunchKernelGGL(k_stream_scan<SI_SEL_PSET>, dim3(chunks), dim3(64), 0, st, J);
-    kt_end(b, KT_STREAM_SCAN, ev, st);
+    timed_kernel(b, KT_STREAM_SCAN, st, k_stream_scan<SI_SEL_PSET>, dim3(chunks), dim3(64), J);
     video_prefix_launch<SI_SEL_PSET>(b, S, J, st);          /* (k_stream_prefix, but for a video's own index: one long stream) */
-    ev = kt_begin(b, KT_STREAM_PLACE, st);
-    hipLaunchKernelGGL(k_stream_place<SI_SEL_PSET>, dim3(chunks), dim3(64), 0, st, J);
-    kt_end(b, KT_STREAM_PLACE, ev, st);
+    timed_kernel(b, KT_STREAM_PLACE, st, k_stream_place<SI_SEL_PSET>, dim3(chunks), dim3(64), J);
     TRY(launched(b));
     HIPCHK(b, hipStreamSynchronize(st));
     /* the launch's units, stream by stream: the first PCAMV_PSET_UNITS_MAX of each stream the index took */
@@ -2293,8 +2171,7 @@ static int pset_run(pcamv_batch *b, const StreamIndex &S, const uint8_t *d_bytes
     if (!h_map) return fail(b, PCAMV_ENOMEM, "no memory for the places of %zu parameter-set units", units);
     for (size_t i = 0; i < n; i++)
         for (long long x = 0; x < h_base[i + 1] - h_base[i]; x++) { h_map[h_base[i] + x] = (int)i; h_map[U + h_base[i] + x] = (int)x; }
-    TRY(grow(b, &P.d_len, &P.cap_len, U)); TRY(grow(b, &P.d_map, &P.cap_map, 4 * U));
-    TRY(grow(b, &P.d_rec, &P.cap_rec, U)); TRY(grow(b, &P.d_slots, &P.cap_slots, U * PCAMV_PSET_UNIT_BYTES));
+    TRY(P.d_len.room(b, U)); TRY(P.d_map.room(b, 4 * U)); TRY(P.d_rec.room(b, U)); TRY(P.d_slots.room(b, U * PCAMV_PSET_UNIT_BYTES));
     HIPCHK(b, hipMemcpy(P.d_map, h_map, 4 * 2 * U, hipMemcpyHostToDevice));
     HIPCHK(b, hipMemcpy(P.d_cnt + 2 * n, h_base, 8 * (n + 1), hipMemcpyHostToDevice));
     PsetJobs Q;
@@ -2304,16 +2181,10 @@ static int pset_run(pcamv_batch *b, const StreamIndex &S, const uint8_t *d_bytes
     Q.slots = P.d_slots; Q.rbsp_len = P.d_len; Q.nal_header = P.d_map + 2 * U; Q.first = P.d_map + 3 * U; Q.rec = P.d_rec;
     Q.sets = P.d_sets; Q.n = S.n; Q.want_w = want_w; Q.want_h = want_h;
     if (units) {
-        ev = kt_begin(b, KT_PSET_UNIT, st);
-        hipLaunchKernelGGL(k_pset_unit, dim3((unsigned)units), dim3(64), 0, st, Q);
-        kt_end(b, KT_PSET_UNIT, ev, st);
-        ev = kt_begin(b, KT_PSET_PARSE, st);
-        hipLaunchKernelGGL(k_pset_parse, dim3((unsigned)((units + 63) / 64)), dim3(64), 0, st, Q);
-        kt_end(b, KT_PSET_PARSE, ev, st);
+        timed_kernel(b, KT_PSET_UNIT, st, k_pset_unit, dim3((unsigned)units), dim3(64), Q);
+        timed_kernel(b, KT_PSET_PARSE, st, k_pset_parse, dim3((unsigned)((units + 63) / 64)), dim3(64), Q);
     }
-    ev = kt_begin(b, KT_PSET_RESOLVE, st);
-    hipLaunchKernelGGL(k_pset_resolve, dim3(S.n), dim3(64), 0, st, Q);
-    kt_end(b, KT_PSET_RESOLVE, ev, st);
+    timed_kernel(b, KT_PSET_RESOLVE, st, k_pset_resolve, dim3(S.n), dim3(64), Q);
     TRY(launched(b));
     HIPCHK(b, hipStreamSynchronize(st));
     return 0;
@@ -2330,8 +2201,8 @@ extern "C" int pcamv_gpu_batch_stream_param_sets(pcamv_batch_t *b, int32_t *stat
     const size_t n = (size_t)S.n;
     if (b->video) {         /* the video's sets, resolved once, are every context's: GOPs behind the first often carry none of their own */
         TRY(pset_run(b, b->vx, S.bytes, S.bytes_size, b->vps, b->ctx[0]->F.mb_w, b->ctx[0]->F.mb_h, st));
-        TRY(grow(b, &b->ps.d_sets, &b->ps.cap_sets, n));
-        hipLaunchKernelGGL(k_pset_spread, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, b->vps.d_sets, b->ps.d_sets, (int)n);
+        TRY(b->ps.d_sets.room(b, n));
+        hipLaunchKernelGGL(k_pset_spread, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, b->vps.d_sets.p, b->ps.d_sets.p, (int)n);
         TRY(launched(b));
         HIPCHK(b, hipStreamSynchronize(st));
     } else TRY(pset_run(b, S, S.bytes, S.bytes_size, b->ps, b->ctx[0]->F.mb_w, b->ctx[0]->F.mb_h, st));
@@ -2351,23 +2222,14 @@ extern "C" int pcamv_gpu_param_sets_device(pcamv_ctx_t *c, const uint8_t *bytes,
 {
     if (!c || (!bytes && bytes_size) || !off || !len || !sets_out || n < 1 || bytes_size > ((size_t)1 << 40)) return PCAMV_EINVAL;
     pcamv_batch *b = c->self;
-    HIPCHK(c, hipSetDevice(c->device));
-    DevTmp<uint8_t> d_bytes; DevTmp<long long> d_at;
-    HIPCHK(c, d_bytes.alloc(bytes_size ? bytes_size : 1)); HIPCHK(c, d_at.alloc(2 * (size_t)n));
-    if (bytes_size) HIPCHK(c, hipMemcpy(d_bytes, bytes, bytes_size, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(d_at, off, sizeof(int64_t) * n, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(d_at + n, len, sizeof(int64_t) * n, hipMemcpyHostToDevice));
-    StreamIndex S = StreamIndex();
-    StreamSets P = StreamSets();
-    int rc = stream_index_room(b, S, n, 1, 0, bytes_size);
-    if (!rc) rc = stream_index_run(b, S, d_bytes, bytes_size, d_at, d_at + n, 0, c->stream);
-    if (!rc) rc = pset_run(b, S, d_bytes, (long long)bytes_size, P, 0, 0, c->stream);
-    hipError_t e = hipSuccess;
-    if (!rc) e = hipMemcpy(sets_out, P.d_sets, (size_t)n * sizeof(pcamv_param_sets_t), hipMemcpyDeviceToHost);
-    stream_index_free(S);
-    stream_sets_free(P);
-    if (e != hipSuccess) return fail(c, PCAMV_EHIP, "param_sets_device: %s", hipGetErrorString(e));
-    return on_behalf(c, b, rc);
+    DevBuf<uint8_t> d_bytes; DevBuf<long long> d_at;
+    TRY(probe_upload(c, d_bytes, d_at, bytes, bytes_size, off, len, n, 2));
+    StreamIndex S{}; StreamSets P{};    /* (the probe's own: freed with the scope) */
+    TRY(on_behalf(c, b, stream_index_room(b, S, n, 1, 0, bytes_size)));
+    TRY(on_behalf(c, b, stream_index_run(b, S, d_bytes, bytes_size, d_at, d_at + n, 0, c->stream)));
+    TRY(on_behalf(c, b, pset_run(b, S, d_bytes, (long long)bytes_size, P, 0, 0, c->stream)));
+    HIPCHK(c, hipMemcpy(sets_out, P.d_sets, (size_t)n * sizeof(pcamv_param_sets_t), hipMemcpyDeviceToHost));
+    return 0;
 }
 /* the inverse, host code: what the parsers read, written (pcamv_param_sets.h) */
 extern "C" int pcamv_gpu_write_sps(const pcamv_sps_t *sps, uint8_t *rbsp, size_t cap, size_t *len)
@@ -2456,9 +2318,7 @@ extern "C" int pcamv_gpu_batch_payload_check(pcamv_batch_t *b, int64_t *diff)
     HIPCHK(b, hipDeviceSynchronize());
     const ExtractDev *dX; int slot;
     TRY(batch_push_xdescs(b, st, &dX, &slot));
-    int ev = kt_begin(b, KT_PAYLOAD_CHECK, st);
-    hipLaunchKernelGGL(k_payload_check, dim3(b->n), dim3(256), 0, st, dX, b->d_chk);
-    kt_end(b, KT_PAYLOAD_CHECK, ev, st);
+    timed_kernel(b, KT_PAYLOAD_CHECK, st, k_payload_check, dim3(b->n), dim3(256), dX, b->d_chk);
     TRY(launched(b));
     TRY(ring_release(b, b->xring, slot, st));
     HIPCHK(b, hipStreamSynchronize(st));
@@ -2484,9 +2344,9 @@ extern "C" int pcamv_gpu_message_plan_device(pcamv_ctx_t *c, const int32_t *m, c
     if (!c || !m || !state || !at || contexts < 1 || k < 1 || (long long)contexts * k > (1LL << 24)) return PCAMV_EINVAL;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t jobs = (size_t)contexts * (size_t)k;
-    DevTmp<int> d_m, d_st; DevTmp<long long> d_state, d_at;
-    HIPCHK(c, d_m.alloc(jobs)); HIPCHK(c, d_at.alloc(jobs + 1)); HIPCHK(c, d_state.alloc(MSG_WORDS));
-    if (status) HIPCHK(c, d_st.alloc(jobs));
+    DevBuf<int> d_m, d_st; DevBuf<long long> d_state, d_at;
+    TRY(d_m.room(c, jobs)); TRY(d_at.room(c, jobs + 1)); TRY(d_state.room(c, MSG_WORDS));
+    if (status) TRY(d_st.room(c, jobs));
     HIPCHK(c, hipMemcpy(d_m, m, jobs * 4, hipMemcpyHostToDevice));
     if (status) HIPCHK(c, hipMemcpy(d_st, status, jobs * 4, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(d_state, state, MSG_WORDS * 8, hipMemcpyHostToDevice));
@@ -2514,9 +2374,7 @@ static int message_members_free(pcamv_batch *b)
 static int message_attach(pcamv_batch *b, const uint8_t *d_bytes, int64_t n_bits, int64_t start_bit)
 {
     if (d_bytes) {
-        if (!b->d_mtx) {
-            HIPCHK(b, dalloc(&b->d_mtx, MSG_WORDS)); HIPCHK(b, dalloc(&b->d_mtx_m, (size_t)b->n)); HIPCHK(b, dalloc(&b->d_mtx_at, (size_t)b->n));
-        }
+        TRY(b->d_mtx.room(b, MSG_WORDS)); TRY(b->d_mtx_m.room(b, (size_t)b->n)); TRY(b->d_mtx_at.room(b, (size_t)b->n));      /* (made by the first message) */
         long long st[MSG_WORDS];
         pcamv_message_state_reset(st, start_bit);
         HIPCHK(b, hipMemcpy(b->d_mtx, st, sizeof(st), hipMemcpyHostToDevice));
@@ -2533,12 +2391,8 @@ extern "C" int pcamv_gpu_batch_set_message(pcamv_batch_t *b, const uint8_t *byte
     if (!bytes || !n_bits) return message_attach(b, NULL, 0, 0);
     TRY(message_members_free(b));
     const size_t nb = (size_t)((n_bits + 7) >> 3);
-    if (nb > b->msg_own_bytes) {
-        hipFree(b->d_msg_own); b->d_msg_own = NULL; b->msg_own_bytes = 0; b->d_msg = NULL;
-        HIPCHK(b, dalloc(&b->d_msg_own, nb));
-        b->msg_own_bytes = nb;
-    }
     b->d_msg = NULL;                            /* (detached until the new bytes stand) */
+    TRY(b->d_msg_own.room(b, nb));
     HIPCHK(b, hipMemcpy(b->d_msg_own, bytes, nb, hipMemcpyHostToDevice));
     return message_attach(b, b->d_msg_own, n_bits, start_bit);
 }
@@ -2585,19 +2439,17 @@ extern "C" int pcamv_gpu_batch_rx_message_reserve(pcamv_batch_t *b, int64_t n_bi
     HIPCHK(b, hipSetDevice(b->device));
     TRY(batch_live(b));
     HIPCHK(b, hipDeviceSynchronize());
-    hipFree(b->d_mrx); b->d_mrx = NULL; b->mrx_bits = 0;
+    b->d_mrx.release(); b->mrx_bits = 0;        /* (a reservation is a buffer of its own size: while there is none, d_mrx is NULL) */
     if (!n_bits) return 0;
     const size_t jobs = (size_t)b->n * PCAMV_STREAM_WINDOW_MAX;
-    if (!b->d_mrx_state) {
-        HIPCHK(b, dalloc(&b->d_mrx_state, MSG_WORDS)); HIPCHK(b, dalloc(&b->d_mrx_job, 2 * jobs)); HIPCHK(b, dalloc(&b->d_mrx_at, jobs));
-        HIPCHK(b, dalloc(&b->d_mchk, MSG_CHECK_GROUPS + 1));
-    }
+    TRY(b->d_mrx_state.room(b, MSG_WORDS)); TRY(b->d_mrx_job.room(b, 2 * jobs)); TRY(b->d_mrx_at.room(b, jobs));     /* (made by the first reservation) */
+    TRY(b->d_mchk.room(b, MSG_CHECK_GROUPS + 1));
     const size_t words = (size_t)((n_bits + 31) >> 5);
-    HIPCHK(b, dalloc(&b->d_mrx, words + MSG_GUARD_WORDS));          /* guard words behind the stream that nothing may write (pcamv_gpu_batch_debug_rx_message_guard) */
+    TRY(b->d_mrx.room(b, words + MSG_GUARD_WORDS));                 /* guard words behind the stream that nothing may write (pcamv_gpu_batch_debug_rx_message_guard) */
     HIPCHK(b, hipMemset(b->d_mrx + words, 0xA5, MSG_GUARD_WORDS * 4));
     b->mrx_bits = n_bits;
     const int rc = pcamv_gpu_batch_rx_message_reset(b);
-    if (rc) { hipFree(b->d_mrx); b->d_mrx = NULL; b->mrx_bits = 0; }
+    if (rc) { b->d_mrx.release(); b->mrx_bits = 0; }
     return rc;
 }
 /* synchronises; are the guard words behind the batch's received stream as the reservation left them? */
@@ -2658,10 +2510,10 @@ extern "C" int pcamv_gpu_batch_message_check(pcamv_batch_t *b, int64_t *diff, in
     long long got = state[MSG_CURSOR] < b->mrx_bits ? state[MSG_CURSOR] : b->mrx_bits;
     long long groups = (((got + 7) >> 3) + 255) / 256;
     groups = groups < 1 ? 1 : groups > MSG_CHECK_GROUPS ? MSG_CHECK_GROUPS : groups;
-    const int ev = kt_begin(b, KT_MESSAGE_CHECK, st);
-    hipLaunchKernelGGL(k_message_check, dim3((unsigned)groups), dim3(256), 0, st, (const uint8_t *)b->d_mrx, b->mrx_bits, b->d_mrx_state, b->d_msg, b->msg_bits, b->d_mchk);
-    hipLaunchKernelGGL(k_message_check_sum, dim3(1), dim3(256), 0, st, b->d_mchk, (int)groups, b->d_mchk + MSG_CHECK_GROUPS);
-    kt_end(b, KT_MESSAGE_CHECK, ev, st);
+    timed(b, KT_MESSAGE_CHECK, st, [&] {        /* (the two kernels of a check under one timer) */
+        hipLaunchKernelGGL(k_message_check, dim3((unsigned)groups), dim3(256), 0, st, (const uint8_t *)b->d_mrx.p, b->mrx_bits, b->d_mrx_state, b->d_msg, b->msg_bits, b->d_mchk);
+        hipLaunchKernelGGL(k_message_check_sum, dim3(1), dim3(256), 0, st, b->d_mchk, (int)groups, b->d_mchk + MSG_CHECK_GROUPS);
+    });
     TRY(launched(b));
     HIPCHK(b, hipStreamSynchronize(st));
     static_assert(sizeof(long long) == sizeof(int64_t), "message_check copies the count as it is");
@@ -2682,7 +2534,7 @@ static int write_setup(pcamv_batch *b, int cavlc)
 {
     TRY(entropy_mode(b, cavlc, "pcamv_gpu_write_pslice_cavlc and pcamv_gpu_batch_write_step_cavlc write", "pcamv_gpu_write_pslice and pcamv_gpu_batch_write_step write"));
     for (int i = 0; i < b->n; i++) if (!b->ctx[i]->last) return fail(b, PCAMV_EINVAL, "context %d has analysed no frame yet: there is nothing to write", i);
-    return entropy_setup(b, &b->d_wstat, &b->d_sw_tab, &b->d_sw_scratch, cavlc, SW_NCTX);
+    return entropy_setup(b, b->d_wstat, b->d_sw_tab, b->d_sw_scratch, cavlc, SW_NCTX);
 }
 /* the callers' headers into the next staging buffer -- n_hdr entries of SW_HDR_WORDS words, then the bits of each at a multiple of
  * 4 -- with one copy on `st`; *stage_out is released (stage_release) once the kernel that reads it is queued */
@@ -2708,7 +2560,7 @@ static int write_stage(pcamv_batch *b, const pcamv_slice_hdr_t *hdrs, int n_hdr,
         at += (nb + 3) & ~(size_t)3;
     }
     TRY(stage_send(b, b->tx_stage, k, total, st));
-    *d_hdr = (const int *)b->tx_stage.d[k]; *stage_out = k;
+    *d_hdr = (const int *)b->tx_stage.d[k].p; *stage_out = k;
     return 0;
 }
 /* one launch over the batch's contexts as they stand: J brings the destination and the mode.  The headers are the host's (hdrs, staged
@@ -2727,21 +2579,10 @@ static int write_run(pcamv_batch *b, WriteJobs J, const pcamv_slice_hdr_t *hdrs,
     const FrameDev *dF; const EmbedDev *dE; int slot;
     int rc = batch_push_descs(b, st, &dF, &dE, &slot);
     if (!rc) {
-        if (sw) {
-            const int ev = kt_begin(b, KT_STREAM_SLOT, st);
-            hipLaunchKernelGGL(k_stream_slot, dim3((b->n + 63) / 64), dim3(64), 0, st, dF, *sw);
-            kt_end(b, KT_STREAM_SLOT, ev, st);
-        }
-        const int kt = cavlc ? KT_WRITE_PSLICE_CAVLC : KT_WRITE_PSLICE;
-        const int ev = kt_begin(b, kt, st);
-        if (cavlc) pcamv_launch_write_pslice_cavlc((unsigned)b->n, st, dF, J);
-        else pcamv_launch_write_pslice((unsigned)b->n, st, dF, J);
-        kt_end(b, kt, ev, st);
-        if (sw) {
-            const int ev2 = kt_begin(b, KT_STREAM_COMMIT, st);
-            hipLaunchKernelGGL(k_stream_commit, dim3((b->n + 63) / 64), dim3(64), 0, st, *sw);
-            kt_end(b, KT_STREAM_COMMIT, ev2, st);
-        }
+        if (sw) timed_kernel(b, KT_STREAM_SLOT, st, k_stream_slot, dim3((b->n + 63) / 64), dim3(64), dF, *sw);
+        if (cavlc) timed(b, KT_WRITE_PSLICE_CAVLC, st, [&] { pcamv_launch_write_pslice_cavlc((unsigned)b->n, st, dF, J); });
+        else timed(b, KT_WRITE_PSLICE, st, [&] { pcamv_launch_write_pslice((unsigned)b->n, st, dF, J); });
+        if (sw) timed_kernel(b, KT_STREAM_COMMIT, st, k_stream_commit, dim3((b->n + 63) / 64), dim3(64), *sw);
         rc = launched(b);
         if (!rc) rc = ring_release(b, b->ring, slot, st);
     }
@@ -2816,27 +2657,22 @@ static int write_pslice(pcamv_ctx_t *c, const pcamv_slice_hdr_t *hdr, int final,
         HIPCHK(c, hipStreamSynchronize(c->stream));
         HIPCHK(c, hipMemcpy(c->d_rx_mbs, mbs, (size_t)c->F.n_mb * sizeof(pcamv_mb_t), hipMemcpyHostToDevice));
     }
-    uint8_t *d_out = NULL;
+    DevBuf<uint8_t> d_out;      /* [off][cap][len] int64, then the slice */
     const size_t arr = 3 * sizeof(long long);
-    HIPCHK(c, hipMalloc((void **)&d_out, arr + (cap ? cap : 1)));
+    TRY(d_out.room(c, arr + (cap ? cap : 1)));
     const long long h_arr[3] = {0, (long long)cap, 0};
-    int rc = 0, st = 0;
+    int st = 0;
     long long n = 0;
-    hipError_t e = hipMemcpy(d_out, h_arr, arr, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        WriteJobs J = {};
-        J.bytes = d_out + arr; J.bytes_size = (long long)cap;
-        J.off = (const long long *)d_out; J.cap = J.off + 1; J.len = (long long *)d_out + 2;
-        J.mbs = mbs ? c->d_rx_mbs : NULL; J.as_nal = as_nal != 0; J.final = final != 0;
-        rc = on_behalf(c, b, write_run(b, J, hdr, hdr ? 1 : 0, cavlc, c->stream));
-        if (!rc) e = hipStreamSynchronize(c->stream);
-        if (!rc && e == hipSuccess) e = hipMemcpy(&st, b->d_wstat, sizeof(st), hipMemcpyDeviceToHost);
-        if (!rc && e == hipSuccess) e = hipMemcpy(&n, d_out + 2 * sizeof(long long), sizeof(n), hipMemcpyDeviceToHost);
-        if (!rc && e == hipSuccess && !st && n >= 0 && (size_t)n <= cap && n) e = hipMemcpy(out, d_out + arr, (size_t)n, hipMemcpyDeviceToHost);
-    }
-    hipFree(d_out);
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(c, PCAMV_EHIP, "write_pslice: %s", hipGetErrorString(e));
+    HIPCHK(c, hipMemcpy(d_out, h_arr, arr, hipMemcpyHostToDevice));
+    WriteJobs J = {};
+    J.bytes = d_out + arr; J.bytes_size = (long long)cap;
+    J.off = (const long long *)d_out.p; J.cap = J.off + 1; J.len = (long long *)d_out.p + 2;
+    J.mbs = mbs ? c->d_rx_mbs : NULL; J.as_nal = as_nal != 0; J.final = final != 0;
+    TRY(on_behalf(c, b, write_run(b, J, hdr, hdr ? 1 : 0, cavlc, c->stream)));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(&st, b->d_wstat, sizeof(st), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&n, J.len, sizeof(n), hipMemcpyDeviceToHost));
+    if (!st && n > 0 && (size_t)n <= cap) HIPCHK(c, hipMemcpy(out, J.bytes, (size_t)n, hipMemcpyDeviceToHost));
     if (st) return fail(c, st, st == PCAMV_ENOMEM ? "the slice does not fit %zu bytes (pcamv_gpu_slice_bound gives a capacity that always does)" :
                         "the records are no P macroblocks of this path (type, partition or sub-partition out of range)", cap);
     if (n < 0 || (size_t)n > cap) return fail(c, PCAMV_EHIP, "write_pslice: length corrupt");
@@ -2896,7 +2732,7 @@ static StreamWrite stream_out_jobs(const pcamv_batch *b)
     static_assert(sizeof(SwsCtx) % 8 == 0, "the int64 arrays follow the contexts' states");
     StreamWrite J = StreamWrite();
     J.bytes = O.bytes; J.bytes_size = O.bytes_size; J.len = O.len;
-    J.ctx = (SwsCtx *)O.d_own;
+    J.ctx = (SwsCtx *)O.d_own.p;
     J.w_off = (long long *)(J.ctx + n); J.w_cap = J.w_off + n; J.w_len = J.w_cap + n;
     long long *at = J.w_len + n;
     J.off = at; J.cap = at + n;
@@ -2919,10 +2755,10 @@ extern "C" int pcamv_gpu_batch_stream_open(pcamv_batch_t *b, void *bytes, size_t
     O.ready = 0; O.joined = 0; O.stepped = 0;
     hipStream_t st = stream ? (hipStream_t)stream : b->ctx[0]->stream;
     const size_t total = stream_out_bytes(b->n);
-    if (total > O.cap_own || head_len > O.cap_head || stream_copy_bytes(b->n) > O.cap_copy) HIPCHK(b, hipDeviceSynchronize());        /* (steps on the blocks that are replaced may be in flight) */
-    TRY(grow(b, &O.d_own, &O.cap_own, total));
-    TRY(grow(b, &O.d_head, &O.cap_head, head_len));
-    TRY(grow(b, &O.d_copy, &O.cap_copy, stream_copy_bytes(b->n)));        /* (what a join behind this open works in) */
+    if (total > O.d_own.cap || head_len > O.d_head.cap || stream_copy_bytes(b->n) > O.d_copy.cap) HIPCHK(b, hipDeviceSynchronize());        /* (steps on the blocks that are replaced may be in flight) */
+    TRY(O.d_own.room(b, total));
+    TRY(O.d_head.room(b, head_len));
+    TRY(O.d_copy.room(b, stream_copy_bytes(b->n)));        /* (what a join behind this open works in) */
     O.bytes = (uint8_t *)bytes; O.bytes_size = (long long)bytes_size; O.len = (long long *)len; O.S = S;
     StreamWrite J = stream_out_jobs(b);
     static_assert(sizeof(long long) == sizeof(int64_t), "the caller's int64 arrays are read as they are");
@@ -2931,9 +2767,7 @@ extern "C" int pcamv_gpu_batch_stream_open(pcamv_batch_t *b, void *bytes, size_t
     if (head_len) HIPCHK(b, hipMemcpyAsync(O.d_head, head, head_len, hipMemcpyHostToDevice, st));
     HIPCHK(b, hipStreamSynchronize(st));                                /* off, cap and head are read by this call alone: copied on return */
     J.head_len = (long long)head_len;
-    const int ev = kt_begin(b, KT_STREAM_OPEN, st);
-    hipLaunchKernelGGL(k_stream_open, dim3((b->n + 63) / 64), dim3(64), 0, st, J);
-    kt_end(b, KT_STREAM_OPEN, ev, st);
+    timed_kernel(b, KT_STREAM_OPEN, st, k_stream_open, dim3((b->n + 63) / 64), dim3(64), J);
     TRY(launched(b));
     O.ready = 1;
     return 0;
@@ -2943,7 +2777,7 @@ extern "C" int pcamv_gpu_batch_stream_open(pcamv_batch_t *b, void *bytes, size_t
 static CopyJobs stream_copy_jobs(const pcamv_batch *b, const uint8_t *src, uint8_t *dst)
 {
     static_assert(sizeof(VcJob) % 8 == 0, "the int64 arrays follow the jobs");
-    const CopyJobs C = {src, dst, (VcJob *)b->so.d_copy, (long long *)((VcJob *)b->so.d_copy + b->n), b->n};
+    const CopyJobs C = {src, dst, (VcJob *)b->so.d_copy.p, (long long *)((VcJob *)b->so.d_copy.p + b->n), b->n};
     return C;
 }
 static long long *stream_copy_heads(const pcamv_batch *b) { return stream_copy_jobs(b, NULL, NULL).chunk_base + b->n + 1; }     /* [head_off n][head_len n] */
@@ -2953,12 +2787,8 @@ static void stream_copy_launch(pcamv_batch *b, const CopyJobs &C, unsigned long 
 {
     unsigned long long waves = most / VC_CHUNK + 2ULL * (unsigned)C.n + 1;
     if (waves > (1u << 16)) waves = 1u << 16;      /* (a wavefront then takes several chunks in turn) */
-    int ev = kt_begin(b, KT_STREAM_COPY_PLAN, st);
-    hipLaunchKernelGGL(k_stream_copy_plan, dim3(1), dim3(64), 0, st, C);
-    kt_end(b, KT_STREAM_COPY_PLAN, ev, st);
-    ev = kt_begin(b, KT_STREAM_COPY, st);
-    hipLaunchKernelGGL(k_stream_copy, dim3((unsigned)waves), dim3(64), 0, st, C);
-    kt_end(b, KT_STREAM_COPY, ev, st);
+    timed_kernel(b, KT_STREAM_COPY_PLAN, st, k_stream_copy_plan, dim3(1), dim3(64), C);
+    timed_kernel(b, KT_STREAM_COPY, st, k_stream_copy, dim3((unsigned)waves), dim3(64), C);
 }
 static int ranges_overlap(const void *a, size_t a_size, const void *b, size_t b_size)
 {
@@ -2982,9 +2812,9 @@ extern "C" int pcamv_gpu_batch_stream_open_heads(pcamv_batch_t *b, void *bytes, 
     O.ready = 0; O.joined = 0; O.stepped = 0;
     hipStream_t st = stream ? (hipStream_t)stream : b->ctx[0]->stream;
     const size_t total = stream_out_bytes(b->n), n = (size_t)b->n;
-    if (total > O.cap_own || stream_copy_bytes(b->n) > O.cap_copy) HIPCHK(b, hipDeviceSynchronize());   /* (steps on the blocks that are replaced may be in flight) */
-    TRY(grow(b, &O.d_own, &O.cap_own, total));
-    TRY(grow(b, &O.d_copy, &O.cap_copy, stream_copy_bytes(b->n)));
+    if (total > O.d_own.cap || stream_copy_bytes(b->n) > O.d_copy.cap) HIPCHK(b, hipDeviceSynchronize());   /* (steps on the blocks that are replaced may be in flight) */
+    TRY(O.d_own.room(b, total));
+    TRY(O.d_copy.room(b, stream_copy_bytes(b->n)));
     O.bytes = (uint8_t *)bytes; O.bytes_size = (long long)bytes_size; O.len = (long long *)len; O.S = S;
     StreamWrite J = stream_out_jobs(b);
     const CopyJobs C = stream_copy_jobs(b, (const uint8_t *)heads, O.bytes);
@@ -2995,9 +2825,7 @@ extern "C" int pcamv_gpu_batch_stream_open_heads(pcamv_batch_t *b, void *bytes, 
     HIPCHK(b, hipMemcpyAsync(h_at + n, head_len, 8 * n, hipMemcpyDeviceToDevice, st));
     HIPCHK(b, hipStreamSynchronize(st));                                /* the four arrays are read by this call alone: copied on return */
     const HeadJobs H = {(long long)heads_size, h_at, h_at + n, C.jobs};
-    const int ev = kt_begin(b, KT_STREAM_OPEN_HEADS, st);
-    hipLaunchKernelGGL(k_stream_open_heads, dim3((b->n + 63) / 64), dim3(64), 0, st, J, H);
-    kt_end(b, KT_STREAM_OPEN_HEADS, ev, st);
+    timed_kernel(b, KT_STREAM_OPEN_HEADS, st, k_stream_open_heads, dim3((b->n + 63) / 64), dim3(64), J, H);
     /* the regions do not overlap, so the heads that are taken hold no more than the buffer; each no more than `heads` and VC_HEAD_MAX */
     const unsigned long long each = heads_size < (size_t)VC_HEAD_MAX ? heads_size : (unsigned long long)VC_HEAD_MAX, all = each * n;
     stream_copy_launch(b, C, all < bytes_size ? all : bytes_size, st);
@@ -3017,11 +2845,9 @@ extern "C" int pcamv_gpu_batch_join_streams(pcamv_batch_t *b, void *video, size_
     if (ranges_overlap(video, video_size, O.bytes, (size_t)O.bytes_size)) return fail(b, PCAMV_EINVAL, "join_streams: the video overlaps the buffer the streams are written to");
     hipStream_t st = stream ? (hipStream_t)stream : b->ctx[0]->stream;
     const CopyJobs C = stream_copy_jobs(b, O.bytes, (uint8_t *)video);
-    const JoinJobs Q = {(const SwsCtx *)O.d_own, b->n, (long long)video_size, (const long long *)video_off, (long long *)video_len, (long long *)placed,
+    const JoinJobs Q = {(const SwsCtx *)O.d_own.p, b->n, (long long)video_size, (const long long *)video_off, (long long *)video_len, (long long *)placed,
                         stream_join_word(b), C.jobs};
-    const int ev = kt_begin(b, KT_STREAM_JOIN, st);
-    hipLaunchKernelGGL(k_stream_join, dim3(1), dim3(64), 0, st, Q);
-    kt_end(b, KT_STREAM_JOIN, ev, st);
+    timed_kernel(b, KT_STREAM_JOIN, st, k_stream_join, dim3(1), dim3(64), Q);
     stream_copy_launch(b, C, (unsigned long long)O.bytes_size < video_size ? (unsigned long long)O.bytes_size : video_size, st);
     TRY(launched(b));
     O.joined = 1;
@@ -3096,16 +2922,16 @@ static int idr_setup(pcamv_batch *b, int qp, const uint8_t *hdr, int hdr_bits, i
     int group = (int)(IDR_GROUP_BYTES / place);
     group = group < 1 ? 1 : group > b->n ? b->n : group;
     if (!b->d_idr || b->idr_group != group) {
-        if (b->d_idr) HIPCHK(b, hipDeviceSynchronize());
-        TRY(grow(b, &b->d_idr, &b->cap_idr, place * (size_t)group));
+        if (b->d_idr) HIPCHK(b, hipDeviceSynchronize());    /* (regrown only behind this: pictures in flight work in the block) */
+        TRY(b->d_idr.room(b, place * (size_t)group));
         b->idr_group = group;
     }
-    if (!b->d_idr_ctx) HIPCHK(b, dalloc(&b->d_idr_ctx, (size_t)b->n * (2 * 4 + 3 * 8)));
-    if (!b->d_wstat) HIPCHK(b, dalloc(&b->d_wstat, (size_t)b->n));
+    if (!b->d_idr_ctx) TRY(b->d_idr_ctx.room(b, (size_t)b->n * (2 * 4 + 3 * 8)));
+    if (!b->d_wstat) TRY(b->d_wstat.room(b, (size_t)b->n));
     if (!b->d_idr_tab) {
         uint8_t tab[SV_TAB_BYTES];
         if (sv_build_tables(tab)) return fail(b, PCAMV_EINVAL, "the CAVLC code tables do not fit their entries");
-        HIPCHK(b, dalloc(&b->d_idr_tab, (size_t)SV_TAB_BYTES));
+        TRY(b->d_idr_tab.room(b, (size_t)SV_TAB_BYTES));
         HIPCHK(b, hipMemcpy(b->d_idr_tab, tab, SV_TAB_BYTES, hipMemcpyHostToDevice));
     }
     IdrJobs &j = *J;
@@ -3136,18 +2962,10 @@ static int idr_run(pcamv_batch *b, IdrJobs &J, const void *sws_ctx, hipStream_t 
     if (sws_ctx) pcamv_launch_idr_slot(J, sws_ctx, b->n, st);
     for (int g0 = 0; g0 < b->n; g0 += b->idr_group) {
         const int g = b->n - g0 < b->idr_group ? b->n - g0 : b->idr_group;
-        int ev = kt_begin(b, KT_IDR_MB, st);
-        pcamv_launch_idr_mb(J, g0, g, F.mb_w, F.mb_h, st);
-        kt_end(b, KT_IDR_MB, ev, st);
-        ev = kt_begin(b, KT_IDR_PREFIX, st);
-        pcamv_launch_idr_prefix(J, g0, g, st);
-        kt_end(b, KT_IDR_PREFIX, ev, st);
-        ev = kt_begin(b, KT_IDR_PACK, st);
-        pcamv_launch_idr_pack(J, g0, g, st);
-        kt_end(b, KT_IDR_PACK, ev, st);
-        ev = kt_begin(b, KT_IDR_UNIT, st);
-        pcamv_launch_idr_unit(J, g0, g, st);
-        kt_end(b, KT_IDR_UNIT, ev, st);
+        timed(b, KT_IDR_MB, st, [&] { pcamv_launch_idr_mb(J, g0, g, F.mb_w, F.mb_h, st); });
+        timed(b, KT_IDR_PREFIX, st, [&] { pcamv_launch_idr_prefix(J, g0, g, st); });
+        timed(b, KT_IDR_PACK, st, [&] { pcamv_launch_idr_pack(J, g0, g, st); });
+        timed(b, KT_IDR_UNIT, st, [&] { pcamv_launch_idr_unit(J, g0, g, st); });
     }
     TRY(launched(b));
     TRY(ring_release(b, b->ring, slot, st));
@@ -3184,9 +3002,9 @@ extern "C" int pcamv_gpu_encode_idr(pcamv_ctx_t *c, int qp, int pps_id, int idr_
     if (hrc) return fail(c, hrc, "encode_idr: qp outside 0 .. 51, pps_id outside 0 .. 255 or idr_pic_id outside 0 .. 65535");
     IdrJobs J;
     TRY(on_behalf(c, b, idr_setup(b, qp, hdr, hdr_bits, 3 << 5 | 5, &J)));
-    DevTmp<uint8_t> d_out;
-    HIPCHK(c, d_out.alloc(cap ? cap : 1));
-    long long *arr = (long long *)b->d_idr_ctx;
+    DevBuf<uint8_t> d_out;
+    TRY(d_out.room(c, cap ? cap : 1));
+    long long *arr = (long long *)b->d_idr_ctx.p;
     const long long h_arr[3] = {0, (long long)cap, 0};
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(arr, h_arr, sizeof(h_arr), hipMemcpyHostToDevice));
@@ -3225,9 +3043,7 @@ extern "C" int pcamv_gpu_batch_write_stream_idr(pcamv_batch_t *b, int qp, int pp
     J.bytes = SJ.bytes; J.bytes_size = SJ.bytes_size; J.off = SJ.w_off; J.cap = SJ.w_cap; J.len = SJ.w_len; J.first = SJ.first; J.as_nal = 1; J.aud = O.S.W.aud;
     O.stepped = 1;
     TRY(idr_run(b, J, SJ.ctx, st));
-    const int ev = kt_begin(b, KT_STREAM_COMMIT, st);
-    hipLaunchKernelGGL(k_stream_commit, dim3((b->n + 63) / 64), dim3(64), 0, st, SJ);
-    kt_end(b, KT_STREAM_COMMIT, ev, st);
+    timed_kernel(b, KT_STREAM_COMMIT, st, k_stream_commit, dim3((b->n + 63) / 64), dim3(64), SJ);
     return launched(b);
 }
 /* synchronises */
@@ -3253,9 +3069,9 @@ extern "C" int pcamv_gpu_slice_headers_write_device(pcamv_ctx_t *c, const pcamv_
 {
     if (!c || !params || !fields || !rc_out || !n_bits || !bits || n < 1 || n > (1 << 24)) return PCAMV_EINVAL;
     HIPCHK(c, hipSetDevice(c->device));
-    DevTmp<pcamv_stream_params_t> d_p; DevTmp<pcamv_slice_fields_t> d_f; DevTmp<int> d_int; DevTmp<uint8_t> d_bits;
+    DevBuf<pcamv_stream_params_t> d_p; DevBuf<pcamv_slice_fields_t> d_f; DevBuf<int> d_int; DevBuf<uint8_t> d_bits;
     const size_t slots = (size_t)n * PCAMV_SLICE_HDR_BYTES;
-    HIPCHK(c, d_p.alloc((size_t)n)); HIPCHK(c, d_f.alloc((size_t)n)); HIPCHK(c, d_int.alloc(2 * (size_t)n)); HIPCHK(c, d_bits.alloc(slots));
+    TRY(d_p.room(c, (size_t)n)); TRY(d_f.room(c, (size_t)n)); TRY(d_int.room(c, 2 * (size_t)n)); TRY(d_bits.room(c, slots));
     HIPCHK(c, hipMemcpy(d_p, params, sizeof(*params) * (size_t)n, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(d_f, fields, sizeof(*fields) * (size_t)n, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemset(d_int, 0xA5, sizeof(int) * 2 * (size_t)n));
@@ -3335,9 +3151,9 @@ extern "C" int pcamv_gpu_block_costs(pcamv_ctx_t *c, int qp, int n, const int32_
         if (r[3] < 0 || r[4] < 0 || r[3] + bw[r[2]] > 16 || r[4] + bh[r[2]] > 16) return fail(c, PCAMV_EINVAL, "request %d: block outside its macroblock", i);
         if (px < -28 || py < -28 || px + bw[r[2]] > c->F.w + 24 || py + bh[r[2]] > c->F.h + 24) return fail(c, PCAMV_EINVAL, "request %d leaves the padded plane", i);
     }
-    DevTmp<int> d_req, d_out; DevTmp<FrameDev> d_F;
+    DevBuf<int> d_req, d_out; DevBuf<FrameDev> d_F;
     TRY(probe_frame(c, qp, d_F));
-    HIPCHK(c, d_req.alloc((size_t)n * 8)); HIPCHK(c, d_out.alloc((size_t)n * 3));
+    TRY(d_req.room(c, (size_t)n * 8)); TRY(d_out.room(c, (size_t)n * 3));
     HIPCHK(c, hipMemcpy(d_req, req, (size_t)n * 8 * sizeof(int), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_block_costs, dim3(n), dim3(64), 0, c->stream, (const FrameDev *)d_F, (const int *)d_req, (int *)d_out);
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -3349,9 +3165,9 @@ extern "C" int pcamv_gpu_rd_probe(pcamv_ctx_t *c, int qp, int n, const uint8_t *
 {
     if (!c || !req || !out || n <= 0) return PCAMV_EINVAL;
     HIPCHK(c, hipSetDevice(c->device));
-    DevTmp<uint8_t> d_req; DevTmp<int> d_out; DevTmp<FrameDev> d_F;
+    DevBuf<uint8_t> d_req; DevBuf<int> d_out; DevBuf<FrameDev> d_F;
     TRY(probe_frame(c, qp, d_F));
-    HIPCHK(c, d_req.alloc((size_t)n * 1024)); HIPCHK(c, d_out.alloc((size_t)n * 32));
+    TRY(d_req.room(c, (size_t)n * 1024)); TRY(d_out.room(c, (size_t)n * 32));
     HIPCHK(c, hipMemcpy(d_req, req, (size_t)n * 1024, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_rd_probe, dim3(n), dim3(64), 0, c->stream, (const FrameDev *)d_F, (const uint8_t *)d_req, (int *)d_out);
     HIPCHK(c, hipStreamSynchronize(c->stream));
