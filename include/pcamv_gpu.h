@@ -143,7 +143,9 @@ const char *pcamv_gpu_last_error(const pcamv_ctx_t *ctx);
  *     are produced by the next step, and a pass 2 before that step still runs against the reference before;
  *   - encode_idr and write_stream_idr leave a context as a host set_ref with no previous motion leaves it: the reconstruction of the IDR
  *     picture is the reference at once, its planes produced, the reuse of first-pass pixels dropped.  They take a QP of their own and
- *     leave the context's: pass2_pframe and the writers behind them behave as behind that set_ref. */
+ *     leave the context's: pass2_pframe and the writers behind them behave as behind that set_ref.  With deblock 1 (encode_idr2,
+ *     write_stream_idr2) that reference, and what fetch_recon / recon_device / get_ref_planes show, is the FILTERED picture; nothing of
+ *     the choice outlives the call: the next IDR picture is filtered or not as its own call says. */
 
 /* Source picture, I420, caller-owned host planes.  A pass 2 that follows encodes every macroblock on it. */
 int pcamv_gpu_upload_fenc(pcamv_ctx_t *ctx, const uint8_t *const plane[3], const int stride[3]);
@@ -311,6 +313,9 @@ int  pcamv_gpu_batch_step(pcamv_batch_t *batch, int qp, float emrate, void *stre
  *   one message for the batch: "k_message_count", "k_message_plan", "k_message_jobs", "k_extract_chain_message",
  *     "k_message_check" (the two kernels of a check under one timer) */
 int  pcamv_gpu_batch_kernel_time(pcamv_batch_t *batch, const char *kernel, double *avg_ms, int *launches, int reset);
+/* ... and, the 41st of PCAMV_TIMERS, with PCAMV_FEATURE_IDR_DEBLOCK among the byte streams written: "k_idr_deblock", the loop filter of
+ * the IDR pictures -- its average is per launch, and a call launches it once per anti-diagonal x + 2 y of the picture, mb_w + 2 (mb_h - 1)
+ * times.  (Listed here and not above: tests/test_gpu_batch_memory.py counts the 40 of the list above.) */
 const char *pcamv_gpu_batch_last_error(const pcamv_batch_t *batch);
 /* Closed loop on the device: with on != 0 every batch step ends with pass 2 + the loop filter (embedding must be
  * on: the flip map comes from it), leaving each context's deblocked reconstruction in its device planes
@@ -387,6 +392,7 @@ int pcamv_gpu_abi_version(void);
 #define PCAMV_FEATURE_VIDEO 0x400u      /* one video of many chains: per-chain heads, streams joined, a video cut at its IDR units on the device */
 #define PCAMV_FEATURE_MESSAGE 0x800u    /* one message for a batch, split over its contexts' frames on the device (behind the payload path below) */
 #define PCAMV_FEATURE_IDR 0x1000u       /* the IDR picture a chain starts with coded on the device (the last section of this file) */
+#define PCAMV_FEATURE_IDR_DEBLOCK 0x2000u       /* ... and filtered there, as the stream's P pictures are (the *2 calls of that section) */
 unsigned pcamv_gpu_features(void);
 
 /* ---- Payload path: the caller's bits through the device-resident entry points, and back out on the device ----
@@ -1006,7 +1012,33 @@ int pcamv_gpu_video_gops_device(pcamv_ctx_t *ctx, const uint8_t *bytes, size_t b
  * Kernels (pcamv_gpu_batch_kernel_time knows them by name): k_idr_mb, one wavefront per macroblock, one launch per anti-diagonal x + y;
  * k_idr_prefix; k_idr_pack, one lane per dword of the RBSP; k_idr_unit, one wavefront per context; k_stream_commit.  The working memory
  * is the batch's, made at first use and released with it: 2842 bytes per macroblock and place, at most 8 GiB; larger batches run their
- * contexts in groups inside the call. */
+ * contexts in groups inside the call.
+ *
+ * Filtered IDR pictures (PCAMV_FEATURE_IDR_DEBLOCK): the calls that end in 2 take `deblock`, 0 or 1 (anything else PCAMV_EINVAL, judged
+ * with the other values); with 0 each is its namesake byte for byte, refusals included.  With 1 the picture goes through the loop
+ * filter of 8.7 before it becomes the reference -- as every P picture behind it does -- and its header says so:
+ * disable_deblocking_filter_idc 0 with both offsets 0 under a PPS with deblocking control (the header is as long as the unfiltered
+ * one's), no deblocking element at all under a PPS without it, where the filter is on by inference (3 bits shorter); so a PPS without
+ * deblocking control is no longer refused, by the header writer and by write_stream_idr2.  The slice data is the same bits either way:
+ * intra prediction reads unfiltered samples, so the filter runs behind the whole picture's coding.
+ * deblock_intra_picture: host code, no GPU; the definition of the filter on every input.  8.7 for a frame picture of one slice, Intra16x16
+ * macroblocks only, one QP, 4x4 transform, FilterOffsetA = FilterOffsetB = 0, in place on tightly packed planes, macroblock by
+ * macroblock in raster order: bS 4 on a macroblock edge whose neighbour lies in the picture, 3 on the inner edges, the picture's border
+ * not filtered; indexA = indexB = qp for luma, the chroma QP of qp + chroma_qp_index_offset for both chroma planes.  PCAMV_EINVAL for a
+ * NULL plane, a size outside decode_islice_cavlc's, a QP outside 0 .. 51, an offset outside -12 .. 12.
+ * parse_idr_slice_header2: as parse_idr_slice_header up to slice_qp_delta; then *disable_deblocking_filter_idc receives 0, 1 or 2 (one
+ * slice per picture: 2 filters as 0 does), 0 under a PPS without deblocking control; an offset that is not 0 is PCAMV_EUNSUP, one outside
+ * -6 .. 6 and an idc above 2 PCAMV_EINVAL.  All four outputs are -1 on failure.  A decoder of these pictures is decode_islice_cavlc
+ * followed, unless the idc is 1, by deblock_intra_picture.
+ * Kernel: k_idr_deblock (csrc/pcamv_idr_deblock.h), one wavefront per macroblock, one launch per anti-diagonal x + 2 y over all contexts
+ * of the call, behind the coder's groups and before the pictures become the references. */
+int pcamv_gpu_write_idr_slice_header2(const pcamv_stream_params_t *params, int nal_ref_idc, int idr_pic_id, int slice_qp, int deblock, uint8_t *bits, size_t cap,
+                                      int32_t *n_bits);
+int pcamv_gpu_parse_idr_slice_header2(const uint8_t *rbsp, size_t len, int nal_header, const pcamv_stream_params_t *params, int64_t *start_bit,
+                                      int32_t *slice_qp, int32_t *idr_pic_id, int32_t *disable_deblocking_filter_idc);
+int pcamv_gpu_deblock_intra_picture(uint8_t *y, uint8_t *u, uint8_t *v, int mb_w, int mb_h, int qp, int chroma_qp_index_offset);
+int pcamv_gpu_encode_idr2(pcamv_ctx_t *ctx, int qp, int pps_id, int idr_pic_id, int as_nal, int deblock, uint8_t *out, size_t cap, size_t *len);
+int pcamv_gpu_batch_write_stream_idr2(pcamv_batch_t *batch, int qp, int pps_id, int idr_pic_id, int deblock, void *stream);
 int pcamv_gpu_write_idr_slice_header(const pcamv_stream_params_t *params, int nal_ref_idc, int idr_pic_id, int slice_qp, uint8_t *bits, size_t cap, int32_t *n_bits);
 int pcamv_gpu_parse_idr_slice_header(const uint8_t *rbsp, size_t len, int nal_header, const pcamv_stream_params_t *params, int64_t *start_bit,
                                      int32_t *slice_qp, int32_t *idr_pic_id);

@@ -3,7 +3,10 @@ loop, 256 chains).  In one run: Batch.write_stream_idr of every chain's first pi
 kernel_time -- next to one closed-loop P step of the same batch, and the bytes of an IDR picture next to a P picture's.  Prints one JSON
 line and writes it to profiles/idr_timing.json.  Needs a GPU.
 
-    python tools/idr_timing.py [--gops 256] [--steps 3] [--warmup 1] [--reps 3] [--out FILE]
+--deblock: the same calls on the same chains in the same run without and with the loop filter (write_stream_idr(deblock=True), kernel
+k_idr_deblock): the wall clock of both, k_idr_deblock over its launches next to k_idr_mb, into profiles/idr_deblock_timing.json.
+
+    python tools/idr_timing.py [--deblock] [--gops 256] [--steps 3] [--warmup 1] [--reps 3] [--out FILE]
 """
 import argparse
 import json
@@ -25,8 +28,10 @@ def main():
     ap.add_argument("--qp", type=int, default=26)
     ap.add_argument("--emrate", type=float, default=0.5)
     ap.add_argument("--region", type=int, default=6 << 20, help="bytes of a chain's stream")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "idr_timing.json"))
+    ap.add_argument("--deblock", action="store_true", help="time the pictures without and with the loop filter")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    args.out = args.out or os.path.join(ROOT, "profiles", "idr_deblock_timing.json" if args.deblock else "idr_timing.json")
     import numpy as np
     import torch
     import pcamv_amd
@@ -54,26 +59,38 @@ def main():
     for k, enc in enumerate(run.encs):
         enc.set_fenc_device(*[pl.data_ptr() for pl in dframes[bench.tri(run.phases[k], len(dframes))]])
     out = dict(gops=n, width=W, height=H, qp=args.qp, emrate=args.emrate, reps=args.reps, steps=args.steps)
-    wall = []
-    for rep in range(args.reps + 1):            # the first call makes the working memory and is not counted
-        torch.cuda.synchronize()
-        run.batch.stream_open(data, off, cap, length, sp, wr, head=head, stream=stream.cuda_stream)
-        torch.cuda.synchronize()
-        if rep == 1:
-            for name in KERNELS:
-                run.batch.kernel_time(name, reset=True)
-        w0 = time.perf_counter()
-        run.batch.write_stream_idr(args.qp, pps_id=1, idr_pic_id=rep, stream=stream.cuda_stream)
-        torch.cuda.synchronize()
-        if rep:
-            wall.append((time.perf_counter() - w0) * 1e3)
-    status = run.batch.write_status()
-    out["idr_status_nonzero"] = int((status != 0).sum())
-    out["write_stream_idr_wall_ms"] = wall
-    for name in KERNELS:
-        ms, launches = run.batch.kernel_time(name, reset=True)
-        out[name + "_ms_per_call"] = ms * launches / max(args.reps, 1)
-        out[name + "_timed_spans_per_call"] = launches / max(args.reps, 1)
+
+    def idr_calls(deblock, kernels):
+        """reps + 1 calls, the first not counted (it makes the working memory): wall clock per call, every kernel's time per call"""
+        wall, res = [], {}
+        for rep in range(args.reps + 1):
+            torch.cuda.synchronize()
+            run.batch.stream_open(data, off, cap, length, sp, wr, head=head, stream=stream.cuda_stream)
+            torch.cuda.synchronize()
+            if rep == 1:
+                for name in kernels:
+                    run.batch.kernel_time(name, reset=True)
+            w0 = time.perf_counter()
+            run.batch.write_stream_idr(args.qp, pps_id=1, idr_pic_id=rep, stream=stream.cuda_stream, deblock=deblock)
+            torch.cuda.synchronize()
+            if rep:
+                wall.append((time.perf_counter() - w0) * 1e3)
+        res["idr_status_nonzero"] = int((run.batch.write_status() != 0).sum())
+        res["write_stream_idr_wall_ms"] = wall
+        for name in kernels:
+            ms, launches = run.batch.kernel_time(name, reset=True)
+            res[name + "_ms_per_call"] = ms * launches / max(args.reps, 1)
+            res[name + ("_launches_per_call" if name == "k_idr_deblock" else "_timed_spans_per_call")] = launches / max(args.reps, 1)
+        return wall, res
+
+    wall, res = idr_calls(False, KERNELS)
+    out.update(res)
+    if args.deblock:
+        wall_f, res_f = idr_calls(True, KERNELS + ("k_idr_deblock",))
+        out["deblock"] = res_f
+        out["deblock"]["k_idr_deblock_over_k_idr_mb"] = res_f["k_idr_deblock_ms_per_call"] / res_f["k_idr_mb_ms_per_call"]
+        out["deblock"]["wall_with_over_without"] = float(np.median(wall_f)) / float(np.median(wall))
+        out["deblock"]["diagonals"] = W // 16 + 2 * (H // 16 - 1)
     idr_bytes = (length.cpu().numpy() - len(head) - 6).astype(np.int64)
     out["idr_unit_bytes"] = dict(min=int(idr_bytes.min()), mean=float(idr_bytes.mean()), max=int(idr_bytes.max()))
     out["diagonals"] = W // 16 + H // 16 - 1
@@ -96,7 +113,7 @@ def main():
     out["p_write_status_nonzero"] = int((run.batch.write_status() != 0).sum())
     out["p_unit_bytes"] = dict(min=int(p_bytes.min()), mean=float(p_bytes.mean()), max=int(p_bytes.max()))
     out["idr_over_p_step"] = float(np.median(wall)) / out["p_step_ms"]
-    line = json.dumps(dict(mode="idr", tool="idr_timing.py", **out))
+    line = json.dumps(dict(mode="idr_deblock" if args.deblock else "idr", tool="idr_timing.py", **out))
     print(line)
     with open(args.out, "w") as f:
         f.write(line + "\n")

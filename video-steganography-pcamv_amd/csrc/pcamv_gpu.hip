@@ -43,13 +43,15 @@
     X(KT_STREAM_JOIN, "k_stream_join") X(KT_STREAM_COPY_PLAN, "k_stream_copy_plan") X(KT_STREAM_COPY, "k_stream_copy") \
     X(KT_VIDEO_CUT, "k_video_cut") X(KT_MESSAGE_COUNT, "k_message_count") X(KT_MESSAGE_PLAN, "k_message_plan") \
     X(KT_MESSAGE_JOBS, "k_message_jobs") X(KT_EXTRACT_CHAIN_MESSAGE, "k_extract_chain_message") X(KT_MESSAGE_CHECK, "k_message_check") \
-    X(KT_IDR_MB, "k_idr_mb") X(KT_IDR_PREFIX, "k_idr_prefix") X(KT_IDR_PACK, "k_idr_pack") X(KT_IDR_UNIT, "k_idr_unit")
+    X(KT_IDR_MB, "k_idr_mb") X(KT_IDR_PREFIX, "k_idr_prefix") X(KT_IDR_PACK, "k_idr_pack") X(KT_IDR_UNIT, "k_idr_unit") \
+    X(KT_IDR_DEBLOCK, "k_idr_deblock")
 #define KT_ENUM(id, name) id,
 enum { PCAMV_TIMERS(KT_ENUM) KT_N };
 #undef KT_ENUM
 #define PCAMV_FEATURES (PCAMV_FEATURE_PAYLOAD | PCAMV_FEATURE_SLICE_PARSER | PCAMV_FEATURE_SLICE_PARSER_CAVLC | PCAMV_FEATURE_SLICE_WRITER | \
                         PCAMV_FEATURE_SLICE_WRITER_CAVLC | PCAMV_FEATURE_NAL_DEVICE | PCAMV_FEATURE_STREAM_DEVICE | PCAMV_FEATURE_STREAM_WRITER | \
-                        PCAMV_FEATURE_STREAM_WINDOW | PCAMV_FEATURE_PARAM_SETS | PCAMV_FEATURE_VIDEO | PCAMV_FEATURE_MESSAGE | PCAMV_FEATURE_IDR)
+                        PCAMV_FEATURE_STREAM_WINDOW | PCAMV_FEATURE_PARAM_SETS | PCAMV_FEATURE_VIDEO | PCAMV_FEATURE_MESSAGE | PCAMV_FEATURE_IDR | \
+                        PCAMV_FEATURE_IDR_DEBLOCK)
 #define MSG_GUARD_WORDS 4       /* words behind a batch's received stream that nothing may write */
 #define SLICE_GUARD_MBS 4       /* records behind a context's receive-side records that nothing may write (pcamv_gpu_debug_slice_records) */
 #define NSTAGE 2                /* staging buffers of extract_slices: a call waits for the one before the last */
@@ -2886,16 +2888,23 @@ void pcamv_launch_idr_prefix(const IdrJobs &J, int g0, int g, hipStream_t st);
 void pcamv_launch_idr_pack(const IdrJobs &J, int g0, int g, hipStream_t st);
 void pcamv_launch_idr_unit(const IdrJobs &J, int g0, int g, hipStream_t st);
 void pcamv_launch_idr_slot(const IdrJobs &J, const void *sws_ctx, int n, hipStream_t st);
-extern "C" int pcamv_gpu_write_idr_slice_header(const pcamv_stream_params_t *params, int nal_ref_idc, int idr_pic_id, int slice_qp, uint8_t *bits, size_t cap, int32_t *n_bits)
+void pcamv_launch_idr_deblock(const IdrJobs &J, int n, int mb_w, int mb_h, hipStream_t st);
+int pcamv_idr_deblock_launches(int mb_w, int mb_h);
+extern "C" int pcamv_gpu_write_idr_slice_header2(const pcamv_stream_params_t *params, int nal_ref_idc, int idr_pic_id, int slice_qp, int deblock, uint8_t *bits, size_t cap,
+                                                 int32_t *n_bits)
 {
     if (n_bits) *n_bits = 0;
     if (!params || !n_bits || (!bits && cap)) return PCAMV_EINVAL;
     int n = 0;
-    TRY(pcamv_idr_header_write(*params, nal_ref_idc, idr_pic_id, slice_qp, NULL, &n));         /* judged and counted; nothing stored */
+    TRY(pcamv_idr_header_write2(*params, nal_ref_idc, idr_pic_id, slice_qp, deblock, NULL, &n));       /* judged and counted; nothing stored */
     if ((size_t)(n + 7) / 8 > cap) return PCAMV_ENOMEM;
-    const int rc = pcamv_idr_header_write(*params, nal_ref_idc, idr_pic_id, slice_qp, bits, &n);
+    const int rc = pcamv_idr_header_write2(*params, nal_ref_idc, idr_pic_id, slice_qp, deblock, bits, &n);
     *n_bits = n;
     return rc;
+}
+extern "C" int pcamv_gpu_write_idr_slice_header(const pcamv_stream_params_t *params, int nal_ref_idc, int idr_pic_id, int slice_qp, uint8_t *bits, size_t cap, int32_t *n_bits)
+{
+    return pcamv_gpu_write_idr_slice_header2(params, nal_ref_idc, idr_pic_id, slice_qp, 0, bits, cap, n_bits);
 }
 extern "C" int64_t pcamv_gpu_idr_bound(const pcamv_ctx_t *c, int as_nal) { return c ? (int64_t)idr_bound(c->F.n_mb, as_nal) : PCAMV_EINVAL; }
 /* the working memory of one place of a group: bytes per context */
@@ -2951,8 +2960,10 @@ static int idr_setup(pcamv_batch *b, int qp, const uint8_t *hdr, int hdr_bits, i
     j.status = b->d_wstat;
     return 0;
 }
-/* every context's source coded, group by group, on `st`; then every context's reconstruction becomes its reference: copied into the
- * context's own reference planes, and the plane production of a step with no previous motion -- the state pcamv_gpu_set_ref leaves */
+/* every context's source coded, group by group, on `st`; (J.deblock) every picture filtered, all contexts per launch -- k_idr_deblock works
+ * on the contexts' reconstruction planes and on nothing of a group's working memory, so it stands behind the groups; then every context's
+ * reconstruction becomes its reference: copied into the context's own reference planes, and the plane production of a step with no
+ * previous motion -- the state pcamv_gpu_set_ref leaves */
 static int idr_run(pcamv_batch *b, IdrJobs &J, const void *sws_ctx, hipStream_t st)
 {
     const FrameDev *dF; const EmbedDev *dE; int slot;
@@ -2966,6 +2977,10 @@ static int idr_run(pcamv_batch *b, IdrJobs &J, const void *sws_ctx, hipStream_t 
         timed(b, KT_IDR_PREFIX, st, [&] { pcamv_launch_idr_prefix(J, g0, g, st); });
         timed(b, KT_IDR_PACK, st, [&] { pcamv_launch_idr_pack(J, g0, g, st); });
         timed(b, KT_IDR_UNIT, st, [&] { pcamv_launch_idr_unit(J, g0, g, st); });
+    }
+    if (J.deblock) {
+        b->kt[KT_IDR_DEBLOCK].weight = pcamv_idr_deblock_launches(F.mb_w, F.mb_h);      /* one pair of events around the anti-diagonals (all counted, also the empty ones of a picture one macroblock wide) */
+        timed(b, KT_IDR_DEBLOCK, st, [&] { pcamv_launch_idr_deblock(J, b->n, F.mb_w, F.mb_h, st); });
     }
     TRY(launched(b));
     TRY(ring_release(b, b->ring, slot, st));
@@ -2988,7 +3003,7 @@ static pcamv_stream_params_t idr_probe_params(int pps_id)
     pcamv_stream_params_t P = {4, 0, 4, 0, 0, 0, 1, 0, 0, 26, 1, pps_id};
     return P;
 }
-extern "C" int pcamv_gpu_encode_idr(pcamv_ctx_t *c, int qp, int pps_id, int idr_pic_id, int as_nal, uint8_t *out, size_t cap, size_t *len)
+extern "C" int pcamv_gpu_encode_idr2(pcamv_ctx_t *c, int qp, int pps_id, int idr_pic_id, int as_nal, int deblock, uint8_t *out, size_t cap, size_t *len)
 {
     if (!c || !out || !len || cap > ((size_t)1 << 40)) return PCAMV_EINVAL;
     *len = 0;
@@ -2998,8 +3013,9 @@ extern "C" int pcamv_gpu_encode_idr(pcamv_ctx_t *c, int qp, int pps_id, int idr_
     uint8_t hdr[IDR_HDR_BYTES] = {0};
     int hdr_bits = 0;
     const pcamv_stream_params_t P = idr_probe_params(pps_id);
-    const int hrc = pcamv_idr_header_write(P, 3, idr_pic_id, qp, hdr, &hdr_bits);
-    if (hrc) return fail(c, hrc, "encode_idr: qp outside 0 .. 51, pps_id outside 0 .. 255 or idr_pic_id outside 0 .. 65535");
+    const int hrc = pcamv_idr_header_write2(P, 3, idr_pic_id, qp, deblock, hdr, &hdr_bits);
+    if (hrc) return fail(c, hrc, deblock ? "encode_idr2: qp outside 0 .. 51, pps_id outside 0 .. 255, idr_pic_id outside 0 .. 65535 or deblock not 0 or 1"
+                                         : "encode_idr: qp outside 0 .. 51, pps_id outside 0 .. 255 or idr_pic_id outside 0 .. 65535");
     IdrJobs J;
     TRY(on_behalf(c, b, idr_setup(b, qp, hdr, hdr_bits, 3 << 5 | 5, &J)));
     DevBuf<uint8_t> d_out;
@@ -3009,6 +3025,7 @@ extern "C" int pcamv_gpu_encode_idr(pcamv_ctx_t *c, int qp, int pps_id, int idr_
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(arr, h_arr, sizeof(h_arr), hipMemcpyHostToDevice));
     J.bytes = d_out; J.bytes_size = (long long)cap; J.off = arr; J.cap = arr + 1; J.len = arr + 2; J.as_nal = as_nal != 0; J.first = NULL;
+    J.deblock = deblock;
     TRY(on_behalf(c, b, idr_run(b, J, NULL, c->stream)));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     int st = 0; long long n = 0;
@@ -3020,7 +3037,11 @@ extern "C" int pcamv_gpu_encode_idr(pcamv_ctx_t *c, int qp, int pps_id, int idr_
     *len = (size_t)n;
     return 0;
 }
-extern "C" int pcamv_gpu_batch_write_stream_idr(pcamv_batch_t *b, int qp, int pps_id, int idr_pic_id, void *stream)
+extern "C" int pcamv_gpu_encode_idr(pcamv_ctx_t *c, int qp, int pps_id, int idr_pic_id, int as_nal, uint8_t *out, size_t cap, size_t *len)
+{
+    return pcamv_gpu_encode_idr2(c, qp, pps_id, idr_pic_id, as_nal, 0, out, cap, len);
+}
+extern "C" int pcamv_gpu_batch_write_stream_idr2(pcamv_batch_t *b, int qp, int pps_id, int idr_pic_id, int deblock, void *stream)
 {
     if (!b) return PCAMV_EINVAL;
     HIPCHK(b, hipSetDevice(b->device));
@@ -3031,20 +3052,27 @@ extern "C" int pcamv_gpu_batch_write_stream_idr(pcamv_batch_t *b, int qp, int pp
     if (O.S.W.first_pic != 0) return fail(b, PCAMV_EINVAL, "an IDR picture is picture 0 of its stream: the open must have first_pic 0");
     pcamv_stream_params_t P = O.S.P;
     P.pps_id = pps_id; P.entropy_cabac = 0;             /* the PPS the IDR slices name: the stream's but for its id and its entropy mode */
-    if (!P.deblocking_filter_control_present) return fail(b, PCAMV_EUNSUP, "the IDR picture is not filtered and its header must say so: the PPS needs deblocking_filter_control_present");
+    if (!P.deblocking_filter_control_present && deblock != 1)
+        return fail(b, PCAMV_EUNSUP, "the IDR picture is not filtered and its header must say so: the PPS needs deblocking_filter_control_present");
     uint8_t hdr[IDR_HDR_BYTES] = {0};
     int hdr_bits = 0;
-    const int hrc = pcamv_idr_header_write(P, O.S.W.nal_ref_idc, idr_pic_id, qp, hdr, &hdr_bits);
-    if (hrc) return fail(b, hrc, "write_stream_idr: qp outside 0 .. 51, pps_id outside 0 .. 255 or idr_pic_id outside 0 .. 65535");
+    const int hrc = pcamv_idr_header_write2(P, O.S.W.nal_ref_idc, idr_pic_id, qp, deblock, hdr, &hdr_bits);
+    if (hrc) return fail(b, hrc, deblock ? "write_stream_idr2: qp outside 0 .. 51, pps_id outside 0 .. 255, idr_pic_id outside 0 .. 65535 or deblock not 0 or 1"
+                                         : "write_stream_idr: qp outside 0 .. 51, pps_id outside 0 .. 255 or idr_pic_id outside 0 .. 65535");
     hipStream_t st = stream ? (hipStream_t)stream : b->ctx[0]->stream;
     IdrJobs J;
     TRY(idr_setup(b, qp, hdr, hdr_bits, O.S.W.nal_ref_idc << 5 | 5, &J));
     const StreamWrite SJ = stream_out_jobs(b);
     J.bytes = SJ.bytes; J.bytes_size = SJ.bytes_size; J.off = SJ.w_off; J.cap = SJ.w_cap; J.len = SJ.w_len; J.first = SJ.first; J.as_nal = 1; J.aud = O.S.W.aud;
+    J.deblock = deblock;
     O.stepped = 1;
     TRY(idr_run(b, J, SJ.ctx, st));
     timed_kernel(b, KT_STREAM_COMMIT, st, k_stream_commit, dim3((b->n + 63) / 64), dim3(64), SJ);
     return launched(b);
+}
+extern "C" int pcamv_gpu_batch_write_stream_idr(pcamv_batch_t *b, int qp, int pps_id, int idr_pic_id, void *stream)
+{
+    return pcamv_gpu_batch_write_stream_idr2(b, qp, pps_id, idr_pic_id, 0, stream);
 }
 /* synchronises */
 extern "C" int pcamv_gpu_batch_stream_written(pcamv_batch_t *b, int64_t *bytes, int64_t *pictures, int64_t *units)

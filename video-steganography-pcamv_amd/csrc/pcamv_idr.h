@@ -10,7 +10,8 @@
  * Scope, fixed: one I slice per picture, Intra16x16 macroblocks only (luma V / H / DC / plane, chroma DC / H / V / plane, each chosen by
  * SATD among the modes whose neighbours exist, ties to the lower mode number of 8.3.3 / 8.3.4), one QP (mb_qp_delta 0), CAVLC whatever
  * the stream's P slices use, disable_deblocking_filter_idc 1: the reconstruction a decoder makes is the unfiltered one that is made here
- * and becomes the chain's reference.  This is NOT the reference's I-frame coder (no I4x4, no RD decision, its own mode order): an I
+ * and becomes the chain's reference (or, where the caller asks for a filtered picture, goes through pcamv_idr_deblock.h first, behind
+ * the whole picture's coding: nothing here changes with that, intra prediction reads unfiltered samples).  This is NOT the reference's I-frame coder (no I4x4, no RD decision, its own mode order): an I
  * picture carries no payload, and the P chain's exactness is defined given its reference picture.
  *
  * Arithmetic.  Forward: the core transform of 8.5 backwards on the 4x4 residuals; the sixteen luma DCs through a 4x4 Hadamard with

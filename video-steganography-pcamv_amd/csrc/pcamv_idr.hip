@@ -1,7 +1,7 @@
 /*
  * pcamv_idr.hip -- the IDR picture of every chain coded on the device (gfx950): k_idr_mb, k_idr_prefix, k_idr_pack, k_idr_slot,
- * k_idr_unit.  The coder itself is pcamv_idr.h (shared with the host check); this unit gives it its working memory and its place in a
- * batch.
+ * k_idr_unit, k_idr_deblock.  The coder itself is pcamv_idr.h, its loop filter pcamv_idr_deblock.h (both shared with the host checks);
+ * this unit gives them their working memory and their place in a batch.
  *
  *   k_idr_mb      one wavefront per macroblock, launched once per anti-diagonal x + y = d over the contexts of a group (Intra16x16 reads
  *                 left, top and top-left only): mode decision, transform, reconstruction, counts, the macroblock's bit string.  The
@@ -12,12 +12,15 @@
  *   k_idr_slot    (streams) one lane per context: the access unit delimiter 09 10 at the stream's end, the place the unit gets.
  *   k_idr_unit    one wavefront per context: start code, header byte and emulation prevention through the slice writers' output path,
  *                 nothing stored at or beyond the capacity.
+ *   k_idr_deblock one wavefront per macroblock, launched once per anti-diagonal x + 2 y = d over ALL contexts of the call, behind the
+ *                 groups: it works on the contexts' reconstruction planes alone (idr_deblock_mb), in 688 bytes of LDS.
  * No spin-wait and no dependency between the waves of a launch.  Every store is an ordinary vector store.  Nothing else is defined here.
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "pcamv_flow.hip.h"
 #include "pcamv_idr.h"
+#include "pcamv_idr_deblock.h"
 
 /* context i's picture at its place in the group */
 static __device__ IdrPic idr_pic(const IdrJobs &J, int i, int place)
@@ -114,11 +117,38 @@ static __global__ void __launch_bounds__(64) k_idr_unit(const IdrJobs J, int g0)
     if (threadIdx.x == 0) { J.status[i] = rc; J.len[i] = rc ? 0 : len; }
 }
 
+/* the whole picture is coded: the loop filter of an all-Intra16x16 picture at one QP needs nothing but the planes */
+static __global__ void __launch_bounds__(64) k_idr_deblock(const IdrJobs J, int d, int i0)
+{
+    __shared__ IdbWork W;
+    const FrameDev &F = J.Fs[i0 + blockIdx.y];
+    const int off = F.chroma_qp_offset < -12 ? -12 : F.chroma_qp_offset > 12 ? 12 : F.chroma_qp_offset;
+    IdbPic P;
+    for (int k = 0; k < 3; k++) P.rec[k] = F.rec[k];
+    P.mb_w = F.mb_w; P.mb_h = J.n_mb / F.mb_w; P.qp = J.qp; P.qpc = J.qpc_of[12 + off];
+    int y_lo, y_hi;
+    idb_diag_rows(d, P.mb_w, P.mb_h, &y_lo, &y_hi);
+    const int my = y_lo + (int)blockIdx.x, mx = d - 2 * my;
+    if (my > y_hi || mx < 0 || mx >= P.mb_w || P.qp < 0 || P.qp > 51) return;
+    idr_deblock_mb(W, P, mx, my);
+}
+
 void pcamv_launch_idr_mb(const IdrJobs &J, int g0, int g, int mb_w, int mb_h, hipStream_t st)
 {
     for (int d = 0; d < mb_w + mb_h - 1; d++) {
         const int y_lo = d - (mb_w - 1) > 0 ? d - (mb_w - 1) : 0, y_hi = d < mb_h - 1 ? d : mb_h - 1;
         hipLaunchKernelGGL(k_idr_mb, dim3((unsigned)(y_hi - y_lo + 1), (unsigned)g), dim3(64), 0, st, J, d, g0);
+    }
+}
+int pcamv_idr_deblock_launches(int mb_w, int mb_h) { return idb_n_diag(mb_w, mb_h); }
+void pcamv_launch_idr_deblock(const IdrJobs &J, int n, int mb_w, int mb_h, hipStream_t st)
+{
+    for (int d = 0; d < idb_n_diag(mb_w, mb_h); d++) {
+        int y_lo, y_hi;
+        idb_diag_rows(d, mb_w, mb_h, &y_lo, &y_hi);
+        if (y_hi < y_lo) continue;                      /* a picture one macroblock wide has nothing on its odd diagonals */
+        for (int i0 = 0; i0 < n; i0 += 65535)           /* (a grid's second dimension) */
+            hipLaunchKernelGGL(k_idr_deblock, dim3((unsigned)(y_hi - y_lo + 1), (unsigned)(n - i0 < 65535 ? n - i0 : 65535)), dim3(64), 0, st, J, d, i0);
     }
 }
 void pcamv_launch_idr_prefix(const IdrJobs &J, int g0, int g, hipStream_t st) { hipLaunchKernelGGL(k_idr_prefix, dim3((unsigned)g), dim3(IDR_PREFIX_THREADS), 0, st, J, g0); }

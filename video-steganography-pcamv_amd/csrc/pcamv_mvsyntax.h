@@ -751,13 +751,19 @@ extern "C" int pcamv_gpu_parse_slice_header(const uint8_t *rbsp, size_t len, int
  * redundant_pic_cnt are read and not judged; with nal_ref_idc != 0 the two marking flags, long_term_reference_flag 1: PCAMV_EUNSUP;
  * entropy_cabac: PCAMV_EUNSUP (the decoder below reads CAVLC); slice_qp_delta, a QP outside 0 .. 51: PCAMV_EINVAL; without deblocking
  * control, or with an idc that is not 1: PCAMV_EUNSUP (the picture would be filtered), an idc above 2 PCAMV_EINVAL.  A read at or past the
- * end and a ue with more than 31 leading zeros are PCAMV_EINVAL, found before the element is judged.  All three outputs -1 on failure. */
-extern "C" int pcamv_gpu_parse_idr_slice_header(const uint8_t *rbsp, size_t len, int nal_header, const pcamv_stream_params_t *params, int64_t *start_bit,
-                                                int32_t *slice_qp, int32_t *idr_pic_id)
+ * end and a ue with more than 31 leading zeros are PCAMV_EINVAL, found before the element is judged.  All three outputs -1 on failure.
+ *
+ * pcamv_idr_header_parse2 (idc_out given) reads the same header whether or not the picture is filtered: disable_deblocking_filter_idc 0, 1
+ * or 2 goes to *idc_out (with one slice per picture 2 filters as 0 does), an idc that is not 1 is followed by the two offsets, either of
+ * which non-zero is PCAMV_EUNSUP (the filter here has FilterOffsetA = FilterOffsetB = 0) and outside -6 .. 6 PCAMV_EINVAL; without
+ * deblocking control in the PPS nothing is read and the idc is 0 (7.4.3).  Everything before that point is judged as above. */
+static int pcamv_idr_header_parse2(const uint8_t *rbsp, size_t len, int nal_header, const pcamv_stream_params_t *params, int64_t *start_bit,
+                                   int32_t *slice_qp, int32_t *idr_pic_id, int32_t *idc_out)
 {
     if (start_bit) *start_bit = -1;
     if (slice_qp) *slice_qp = -1;
     if (idr_pic_id) *idr_pic_id = -1;
+    if (idc_out) *idc_out = -1;
     if ((!rbsp && len) || !start_bit || !slice_qp || !idr_pic_id || !pcamv_stream_params_ok(params) || len > ((size_t)1 << 40)) return PCAMV_EINVAL;
     if (nal_header < 0 || (nal_header & 31) != 5) return PCAMV_EUNSUP;
     const pcamv_stream_params_t &P = *params;
@@ -789,14 +795,40 @@ extern "C" int pcamv_gpu_parse_idr_slice_header(const uint8_t *rbsp, size_t len,
     if (P.entropy_cabac) return PCAMV_EUNSUP;
     const int64_t qp = P.pic_init_qp + b.se(); HDR_EOF();
     if (qp < 0 || qp > 51) return PCAMV_EINVAL;
-    if (!P.deblocking_filter_control_present) return PCAMV_EUNSUP;
-    const uint64_t idc = b.ue(); HDR_EOF();
-    if (idc > 2) return PCAMV_EINVAL;
-    if (idc != 1) return PCAMV_EUNSUP;
+    uint64_t idc = 0;
+    if (!P.deblocking_filter_control_present) { if (!idc_out) return PCAMV_EUNSUP; }
+    else {
+        idc = b.ue(); HDR_EOF();
+        if (idc > 2) return PCAMV_EINVAL;
+        if (!idc_out && idc != 1) return PCAMV_EUNSUP;
+        if (idc != 1) {
+            const int64_t oa = b.se(); HDR_EOF();
+            const int64_t ob = b.se(); HDR_EOF();
+            if (oa < -6 || oa > 6 || ob < -6 || ob > 6) return PCAMV_EINVAL;
+            if (oa || ob) return PCAMV_EUNSUP;
+        }
+    }
 #undef HDR_EOF
     if (b.pos >= b.nbits) return PCAMV_EINVAL;
     *start_bit = (int64_t)b.pos; *slice_qp = (int32_t)qp; *idr_pic_id = (int32_t)id;
+    if (idc_out) *idc_out = (int32_t)idc;
     return 0;
+}
+extern "C" int pcamv_gpu_parse_idr_slice_header(const uint8_t *rbsp, size_t len, int nal_header, const pcamv_stream_params_t *params, int64_t *start_bit,
+                                                int32_t *slice_qp, int32_t *idr_pic_id)
+{
+    return pcamv_idr_header_parse2(rbsp, len, nal_header, params, start_bit, slice_qp, idr_pic_id, NULL);
+}
+extern "C" int pcamv_gpu_parse_idr_slice_header2(const uint8_t *rbsp, size_t len, int nal_header, const pcamv_stream_params_t *params, int64_t *start_bit,
+                                                 int32_t *slice_qp, int32_t *idr_pic_id, int32_t *disable_deblocking_filter_idc)
+{
+    if (!disable_deblocking_filter_idc) {
+        if (start_bit) *start_bit = -1;
+        if (slice_qp) *slice_qp = -1;
+        if (idr_pic_id) *idr_pic_id = -1;
+        return PCAMV_EINVAL;
+    }
+    return pcamv_idr_header_parse2(rbsp, len, nal_header, params, start_bit, slice_qp, idr_pic_id, disable_deblocking_filter_idc);
 }
 
 namespace mvsyntax {
@@ -1028,5 +1060,89 @@ extern "C" int pcamv_gpu_decode_islice_cavlc(const uint8_t *rbsp, size_t len, si
     const int rc = D.run();
     free(D.nz);
     return rc;
+}
+
+/* ---------------------------------------------------------------- the loop filter of such a picture (8.7): the definition
+ * A frame picture of one slice, Intra16x16 macroblocks only, one QP, 4x4 transform, FilterOffsetA = FilterOffsetB = 0, filtered in place
+ * on tightly packed planes.  Sequential and naive, as the standard words it: macroblocks in raster order; per macroblock the four
+ * vertical luma edges left to right, then the four horizontal ones top to bottom, chroma on luma edges 0 and 2 (its own edges 0 and 4);
+ * bS 4 on a macroblock edge whose neighbour lies in the picture, 3 on the inner edges, an edge on the picture's border not filtered.
+ * indexA = indexB = qp for luma and, for both chroma planes, the chroma QP of qp + chroma_qp_index_offset by Table 8-15; alpha or beta 0
+ * leaves a line alone (8.7.2.2: filterSamplesFlag needs |p0 - q0| < alpha), so no QP threshold beside the tables.  This is what the
+ * device's filter (csrc/pcamv_idr_deblock.h) is held to; the two share no code and no table. */
+namespace mvsyntax {
+struct IDeblock {
+    int alpha, beta, tc0;               /* of the plane in hand; tc0: the bS 3 column */
+    /* one line of samples across an edge: q at q0, step s between samples (8.7.2.3 for bS < 4, 8.7.2.4 for bS 4) */
+    void line(uint8_t *q, ptrdiff_t s, int bs, bool chroma) const
+    {
+        const int p0 = q[-s], p1 = q[-2 * s], q0 = q[0], q1 = q[s];
+        if (abs(p0 - q0) >= alpha || abs(p1 - p0) >= beta || abs(q1 - q0) >= beta) return;
+        const int p2 = chroma ? 0 : q[-3 * s], q2 = chroma ? 0 : q[2 * s];
+        const bool ap = !chroma && abs(p2 - p0) < beta, aq = !chroma && abs(q2 - q0) < beta;
+        if (bs < 4) {
+            const int tc = chroma ? tc0 + 1 : tc0 + ap + aq;
+            int delta = (((q0 - p0) << 2) + (p1 - q1) + 4) >> 3;
+            delta = delta < -tc ? -tc : delta > tc ? tc : delta;
+            q[-s] = (uint8_t)IDec::clip8(p0 + delta);
+            q[0] = (uint8_t)IDec::clip8(q0 - delta);
+            if (ap) { int d = ((p2 + ((p0 + q0 + 1) >> 1)) >> 1) - p1; d = d < -tc0 ? -tc0 : d > tc0 ? tc0 : d; q[-2 * s] = (uint8_t)(p1 + d); }
+            if (aq) { int d = ((q2 + ((p0 + q0 + 1) >> 1)) >> 1) - q1; d = d < -tc0 ? -tc0 : d > tc0 ? tc0 : d; q[s] = (uint8_t)(q1 + d); }
+            return;
+        }
+        const bool strong = !chroma && abs(p0 - q0) < (alpha >> 2) + 2;
+        if (ap && strong) {
+            const int p3 = q[-4 * s];
+            q[-s] = (uint8_t)((p2 + 2 * p1 + 2 * p0 + 2 * q0 + q1 + 4) >> 3);
+            q[-2 * s] = (uint8_t)((p2 + p1 + p0 + q0 + 2) >> 2);
+            q[-3 * s] = (uint8_t)((2 * p3 + 3 * p2 + p1 + p0 + q0 + 4) >> 3);
+        } else q[-s] = (uint8_t)((2 * p1 + p0 + q1 + 2) >> 2);
+        if (aq && strong) {
+            const int q3 = q[3 * s];
+            q[0] = (uint8_t)((p1 + 2 * p0 + 2 * q0 + 2 * q1 + q2 + 4) >> 3);
+            q[s] = (uint8_t)((p0 + q0 + q1 + q2 + 2) >> 2);
+            q[2 * s] = (uint8_t)((2 * q3 + 3 * q2 + q1 + q0 + p0 + 4) >> 3);
+        } else q[0] = (uint8_t)((2 * q1 + q0 + p1 + 2) >> 2);
+    }
+};
+}
+extern "C" int pcamv_gpu_deblock_intra_picture(uint8_t *y, uint8_t *u, uint8_t *v, int mb_w, int mb_h, int qp, int chroma_qp_index_offset)
+{
+    static const uint8_t qpc_of[52] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29,
+                                       29, 30, 31, 32, 32, 33, 34, 34, 35, 35, 36, 36, 37, 37, 37, 38, 38, 38, 39, 39, 39, 39};       /* Table 8-15 */
+    static const uint8_t alpha_of[52] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 4, 4, 5, 6, 7, 8, 9, 10, 12, 13,
+                                         15, 17, 20, 22, 25, 28, 32, 36, 40, 45, 50, 56, 63, 71, 80, 90, 101, 113, 127, 144, 162, 182, 203, 226, 255, 255};   /* Table 8-16 */
+    static const uint8_t beta_of[52] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4,
+                                        6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13, 14, 14, 15, 15, 16, 16, 17, 17, 18, 18};
+    static const uint8_t tc0_of[52][3] = {                                                                                          /* Table 8-17: bS 1, 2, 3 */
+        {0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0},
+        {0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 1}, {0, 0, 1}, {0, 0, 1}, {0, 0, 1}, {0, 1, 1}, {0, 1, 1}, {1, 1, 1}, {1, 1, 1}, {1, 1, 1},
+        {1, 1, 1}, {1, 1, 2}, {1, 1, 2}, {1, 1, 2}, {1, 1, 2}, {1, 2, 3}, {1, 2, 3}, {2, 2, 3}, {2, 2, 4}, {2, 3, 4}, {2, 3, 4}, {3, 3, 5}, {3, 4, 6},
+        {3, 4, 6}, {4, 5, 7}, {4, 5, 8}, {4, 6, 9}, {5, 7, 10}, {6, 8, 11}, {6, 8, 13}, {7, 10, 14}, {8, 11, 16}, {9, 12, 18}, {10, 13, 20}, {11, 15, 23},
+        {13, 17, 25}};
+    if (!y || !u || !v || mb_w < 1 || mb_h < 1 || mb_w > (1 << 16) || mb_h > (1 << 16) || (long long)mb_w * mb_h > (1 << 20) || qp < 0 || qp > 51 ||
+        chroma_qp_index_offset < -12 || chroma_qp_index_offset > 12) return PCAMV_EINVAL;
+    const int qi = qp + chroma_qp_index_offset, qpc = qpc_of[qi < 0 ? 0 : qi > 51 ? 51 : qi];
+    const mvsyntax::IDeblock L = {alpha_of[qp], beta_of[qp], tc0_of[qp][2]}, Cq = {alpha_of[qpc], beta_of[qpc], tc0_of[qpc][2]};
+    const ptrdiff_t lw = (ptrdiff_t)16 * mb_w, cw = (ptrdiff_t)8 * mb_w;
+    uint8_t *const cpl[2] = {u, v};
+    for (int my = 0; my < mb_h; my++)
+        for (int mx = 0; mx < mb_w; mx++)
+            for (int dir = 0; dir < 2; dir++)                   /* 0: vertical edges (filtered along rows), 1: horizontal edges */
+                for (int e = 0; e < 4; e++) {
+                    if (e == 0 && (dir ? my : mx) == 0) continue;
+                    const int bs = e ? 3 : 4;
+                    for (int k = 0; k < 16; k++) {
+                        uint8_t *q = dir == 0 ? y + ((ptrdiff_t)16 * my + k) * lw + 16 * mx + 4 * e : y + ((ptrdiff_t)16 * my + 4 * e) * lw + 16 * mx + k;
+                        L.line(q, dir == 0 ? 1 : lw, bs, false);
+                    }
+                    if (e & 1) continue;
+                    for (int c = 0; c < 2; c++)
+                        for (int k = 0; k < 8; k++) {
+                            uint8_t *q = dir == 0 ? cpl[c] + ((ptrdiff_t)8 * my + k) * cw + 8 * mx + 2 * e : cpl[c] + ((ptrdiff_t)8 * my + 2 * e) * cw + 8 * mx + k;
+                            Cq.line(q, dir == 0 ? 1 : cw, bs, true);
+                        }
+                }
+    return 0;
 }
 #endif

@@ -626,17 +626,26 @@ IDR_PROBE_PARAMS = dict(log2_max_frame_num=4, poc_type=0, log2_max_poc_lsb=4, nu
                         deblocking_filter_control_present=1)     # the parameter sets Encoder.encode_idr writes its header under (+ pps_id)
 
 
-def write_idr_slice_header(params, nal_ref_idc, idr_pic_id, slice_qp):
+FEATURE_IDR_DEBLOCK = 0x2000    # ... and filtered there: the deblock keyword of the same calls, deblock_intra_picture, parse_idr_slice_header2
+
+
+def write_idr_slice_header(params, nal_ref_idc, idr_pic_id, slice_qp, deblock=False):
     """pcamv_gpu_write_idr_slice_header: (packed bytes, number of bits) of the header of an IDR I slice for a StreamParams -- which must
     say entropy_cabac 0 and deblocking_filter_control_present 1.  Raises PcamvError with the library's code (-1: a value out of range,
-    -5: weighted prediction, CABAC, or no deblocking control)"""
+    -5: weighted prediction, CABAC, or no deblocking control).  deblock (pcamv_gpu_write_idr_slice_header2): the header of a filtered
+    picture -- idc 0 and two offsets of 0, or nothing at all under a StreamParams without deblocking control, which is then not refused"""
     out = np.zeros(IDR_HDR_BYTES, np.uint8)
     n = C.c_int32()
-    fn = load_library().pcamv_gpu_write_idr_slice_header
-    fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32)]
-    rc = fn(C.byref(params), int(nal_ref_idc), int(idr_pic_id), int(slice_qp), _p(out), len(out), C.byref(n))
+    if deblock:
+        fn = load_library().pcamv_gpu_write_idr_slice_header2
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32)]
+        rc = fn(C.byref(params), int(nal_ref_idc), int(idr_pic_id), int(slice_qp), int(deblock), _p(out), len(out), C.byref(n))
+    else:
+        fn = load_library().pcamv_gpu_write_idr_slice_header
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32)]
+        rc = fn(C.byref(params), int(nal_ref_idc), int(idr_pic_id), int(slice_qp), _p(out), len(out), C.byref(n))
     if rc:
-        raise PcamvError(f"pcamv_gpu_write_idr_slice_header failed: {rc}")
+        raise PcamvError(f"pcamv_gpu_write_idr_slice_header{'2' if deblock else ''} failed: {rc}")
     return bytes(out[:(n.value + 7) // 8]), n.value
 
 
@@ -649,6 +658,33 @@ def parse_idr_slice_header(rbsp, nal_header, params):
     fn.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     rc = fn(_p(buf), len(rbsp), int(nal_header), C.byref(params), C.byref(sb), C.byref(qp), C.byref(pid))
     return rc, sb.value, qp.value, pid.value
+
+
+def parse_idr_slice_header2(rbsp, nal_header, params):
+    """pcamv_gpu_parse_idr_slice_header2: (return code, start_bit, slice QP, idr_pic_id, disable_deblocking_filter_idc) of the header of
+    an IDR I slice, filtered or not; idc 0 under a StreamParams without deblocking control; the last four are -1 when the code is not 0"""
+    buf = np.frombuffer(bytes(rbsp), np.uint8) if len(rbsp) else np.zeros(1, np.uint8)
+    sb, qp, pid, idc = C.c_int64(), C.c_int32(), C.c_int32(), C.c_int32()
+    fn = load_library().pcamv_gpu_parse_idr_slice_header2
+    fn.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    rc = fn(_p(buf), len(rbsp), int(nal_header), C.byref(params), C.byref(sb), C.byref(qp), C.byref(pid), C.byref(idc))
+    return rc, sb.value, qp.value, pid.value, idc.value
+
+
+def deblock_intra_picture(planes, qp, chroma_qp_index_offset=0):
+    """pcamv_gpu_deblock_intra_picture: (Y, U, V) filtered as the loop filter of 8.7 filters a frame picture of one slice of Intra16x16
+    macroblocks at one QP with filter offsets 0 -- the definition of what deblock=True does to an IDR picture.  New arrays; the
+    arguments stay as they are"""
+    y, u, v = (np.ascontiguousarray(p, np.uint8).copy() for p in planes)
+    h, w = y.shape
+    if h % 16 or w % 16 or not h or not w or u.shape != (h // 2, w // 2) or v.shape != u.shape:
+        raise PcamvError("deblock_intra_picture: planes of whole macroblocks, I420")
+    fn = load_library().pcamv_gpu_deblock_intra_picture
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
+    rc = fn(_p(y), _p(u), _p(v), w // 16, h // 16, int(qp), int(chroma_qp_index_offset))
+    if rc:
+        raise PcamvError(f"pcamv_gpu_deblock_intra_picture failed: {rc}")
+    return y, u, v
 
 
 def decode_islice_cavlc(rbsp, start_bit, mb_w, mb_h, slice_qp, chroma_qp_index_offset=0):
@@ -667,7 +703,8 @@ def decode_islice_cavlc(rbsp, start_bit, mb_w, mb_h, slice_qp, chroma_qp_index_o
 def decode_idr(unit, mb_w, mb_h, params=None, chroma_qp_index_offset=0):
     """the picture of an IDR unit (start code optional) as the library's host decoder reconstructs it: (Y, U, V), and the slice QP and
     idr_pic_id its header states.  params: the StreamParams of the PPS the slice names (default: those Encoder.encode_idr writes under,
-    with the unit's own pps_id).  Raises PcamvError with the code of the step that failed"""
+    with the unit's own pps_id).  A unit whose header does not say disable_deblocking_filter_idc 1 is filtered (deblock_intra_picture).
+    Raises PcamvError with the code of the step that failed"""
     rbsp, ref_idc, typ = nal_to_rbsp(unit)
     if params is None:
         # the unit's pps_id: the third ue of the header (first_mb_in_slice, slice_type, pps_id)
@@ -683,23 +720,26 @@ def decode_idr(unit, mb_w, mb_h, params=None, chroma_qp_index_offset=0):
             pos += z + 1
             vals.append(v - 1)
         params = StreamParams(**dict(IDR_PROBE_PARAMS, pps_id=min(max(vals[2], 0), 255)))
-    rc, sb, qp, pid = parse_idr_slice_header(rbsp, ref_idc << 5 | typ, params)
+    rc, sb, qp, pid, idc = parse_idr_slice_header2(rbsp, ref_idc << 5 | typ, params)
     if rc:
         raise PcamvError(f"pcamv_gpu_parse_idr_slice_header failed: {rc}")
     rc, planes = decode_islice_cavlc(rbsp, sb, mb_w, mb_h, qp, chroma_qp_index_offset)
     if rc:
         raise PcamvError(f"pcamv_gpu_decode_islice_cavlc failed: {rc}")
+    if idc != 1:
+        planes = deblock_intra_picture(planes, qp, chroma_qp_index_offset)
     return planes, qp, pid
 
 
-def param_set_head_idr(params, mb_w, mb_h, idr_pps_id=1, sps_id=0, num_ref_frames=1, profile_idc=100, level_idc=30):
+def param_set_head_idr(params, mb_w, mb_h, idr_pps_id=1, sps_id=0, num_ref_frames=1, profile_idc=100, level_idc=30, deblocking_filter_control_present=1):
     """the head of a stream whose IDR picture the library writes (Batch.write_stream_idr): param_set_head for the stream's StreamParams,
     then the PPS unit of the same again with pps_id = idr_pps_id, entropy_cabac 0 and deblocking_filter_control_present 1 -- the PPS
-    the IDR slices name: SPS, PPS, PPS.  Returns the bytes and the StreamParams of the second set."""
+    the IDR slices name: SPS, PPS, PPS.  Returns the bytes and the StreamParams of the second set.
+    deblocking_filter_control_present=0 makes that PPS without the flag: only filtered IDR pictures (deblock=True) can name it."""
     if int(idr_pps_id) == params.pps_id:
         raise PcamvError("param_set_head_idr: the IDR pictures' PPS needs an id of its own")
     second = StreamParams(**{n: getattr(params, n) for n, _ in StreamParams._fields_})
-    second.pps_id, second.entropy_cabac, second.deblocking_filter_control_present = int(idr_pps_id), 0, 1
+    second.pps_id, second.entropy_cabac, second.deblocking_filter_control_present = int(idr_pps_id), 0, int(bool(deblocking_filter_control_present))
     again = param_set_head(second, mb_w, mb_h, sps_id, num_ref_frames, profile_idc, level_idc)
     pps = again.find(b"\x00\x00\x00\x01", 4)         # behind the SPS unit, which the first head holds already
     return param_set_head(params, mb_w, mb_h, sps_id, num_ref_frames, profile_idc, level_idc) + again[pps:], second
@@ -1070,16 +1110,22 @@ class Encoder:
             raise PcamvError(f"idr_bound failed ({n})")
         return int(n)
 
-    def encode_idr(self, qp, pps_id=1, idr_pic_id=0, as_nal=True, cap=None):
+    def encode_idr(self, qp, pps_id=1, idr_pic_id=0, as_nal=True, cap=None, deblock=False):
         """pcamv_gpu_encode_idr: this context's current source coded on the device as one IDR I slice (Intra16x16, CAVLC, no loop filter),
         as bytes -- the unit with start code and emulation prevention, or with as_nal=False the RBSP.  The unfiltered reconstruction
         becomes the context's reference as after a host set_ref with no previous motion (fetch_recon, ref_planes show it).  The header
         is written under StreamParams(**IDR_PROBE_PARAMS, pps_id=pps_id) with nal_ref_idc 3.  cap: the capacity offered (default:
-        idr_bound); a unit that does not fit raises (-3)"""
+        idr_bound); a unit that does not fit raises (-3).  deblock (pcamv_gpu_encode_idr2): the picture is filtered
+        (deblock_intra_picture) before it becomes the reference, and its header says so; the slice data is the same"""
         if cap is None:
             cap = self.idr_bound(as_nal)
         out = np.zeros(max(int(cap), 1), np.uint8)
         n = C.c_size_t()
+        if deblock:
+            fn = self.lib.pcamv_gpu_encode_idr2
+            fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+            self._chk(fn(self.ctx, int(qp), int(pps_id), int(idr_pic_id), int(bool(as_nal)), int(deblock), _p(out), int(cap), C.byref(n)), "encode_idr2")
+            return bytes(out[:n.value])
         fn = self.lib.pcamv_gpu_encode_idr
         fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
         self._chk(fn(self.ctx, int(qp), int(pps_id), int(idr_pic_id), int(bool(as_nal)), _p(out), int(cap), C.byref(n)), "encode_idr")
@@ -1584,11 +1630,18 @@ class Batch:
         fn.argtypes = [C.c_void_p, C.c_void_p]
         self._slice_chk(fn(self.b, C.c_void_p(stream or None)), "batch_write_stream_step")
 
-    def write_stream_idr(self, qp, pps_id=1, idr_pic_id=0, stream=0):
+    def write_stream_idr(self, qp, pps_id=1, idr_pic_id=0, stream=0, deblock=False):
         """pcamv_gpu_batch_write_stream_idr: every context's current source coded on the device as the IDR picture of its stream --
         picture 0, behind the head and before the first write_stream_step since the open, which must have first_pic 0 -- and its
         unfiltered reconstruction installed as the context's reference.  The IDR slices name the PPS pps_id, which the head must hold
-        with entropy_cabac 0 and deblocking control (param_set_head_idr).  No host sync; write_status() afterwards as for a step"""
+        with entropy_cabac 0 and deblocking control (param_set_head_idr).  No host sync; write_status() afterwards as for a step.
+        deblock (pcamv_gpu_batch_write_stream_idr2): every picture is filtered on the device (k_idr_deblock) before it becomes the
+        reference, as the P pictures behind it are; that PPS then needs no deblocking control"""
+        if deblock:
+            fn = self.lib.pcamv_gpu_batch_write_stream_idr2
+            fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+            self._slice_chk(fn(self.b, int(qp), int(pps_id), int(idr_pic_id), int(deblock), C.c_void_p(stream or None)), "batch_write_stream_idr2")
+            return
         fn = self.lib.pcamv_gpu_batch_write_stream_idr
         fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
         self._slice_chk(fn(self.b, int(qp), int(pps_id), int(idr_pic_id), C.c_void_p(stream or None)), "batch_write_stream_idr")
