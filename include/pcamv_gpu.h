@@ -315,7 +315,10 @@ int  pcamv_gpu_batch_step(pcamv_batch_t *batch, int qp, float emrate, void *stre
 int  pcamv_gpu_batch_kernel_time(pcamv_batch_t *batch, const char *kernel, double *avg_ms, int *launches, int reset);
 /* ... and, the 41st of PCAMV_TIMERS, with PCAMV_FEATURE_IDR_DEBLOCK among the byte streams written: "k_idr_deblock", the loop filter of
  * the IDR pictures -- its average is per launch, and a call launches it once per anti-diagonal x + 2 y of the picture, mb_w + 2 (mb_h - 1)
- * times.  (Listed here and not above: tests/test_gpu_batch_memory.py counts the 40 of the list above.) */
+ * times.  (Listed here and not above: tests/test_gpu_batch_memory.py counts the 40 of the list above.)
+ * With PCAMV_FEATURE_IDR_SLICES, the 42nd and 43rd: "k_idr_unit_len", one wavefront per (context, slice) counting its unit's bytes, and
+ * "k_idr_place", one lane per context placing its units; both are launched only for pictures of more than one slice, for which
+ * "k_idr_prefix", "k_idr_pack" and "k_idr_unit" time the kernels that work per slice. */
 const char *pcamv_gpu_batch_last_error(const pcamv_batch_t *batch);
 /* Closed loop on the device: with on != 0 every batch step ends with pass 2 + the loop filter (embedding must be
  * on: the flip map comes from it), leaving each context's deblocked reconstruction in its device planes
@@ -393,6 +396,7 @@ int pcamv_gpu_abi_version(void);
 #define PCAMV_FEATURE_MESSAGE 0x800u    /* one message for a batch, split over its contexts' frames on the device (behind the payload path below) */
 #define PCAMV_FEATURE_IDR 0x1000u       /* the IDR picture a chain starts with coded on the device (the last section of this file) */
 #define PCAMV_FEATURE_IDR_DEBLOCK 0x2000u       /* ... and filtered there, as the stream's P pictures are (the *2 calls of that section) */
+#define PCAMV_FEATURE_IDR_SLICES 0x4000u        /* ... in several slices of whole macroblock rows, a wavefront per slice (the *3 calls of that section) */
 unsigned pcamv_gpu_features(void);
 
 /* ---- Payload path: the caller's bits through the device-resident entry points, and back out on the device ----
@@ -968,7 +972,7 @@ int pcamv_gpu_video_gops_device(pcamv_ctx_t *ctx, const uint8_t *bytes, size_t b
  *
  * The calls above predict a chain's first P picture from a reference the caller brought.  With these the library makes that picture
  * itself: a context's source coded as one IDR I slice on the device, its reconstruction installed as the context's reference, its unit
- * put into the context's stream.  Scope, fixed: one slice per picture, Intra16x16 macroblocks only -- luma vertical / horizontal / DC /
+ * put into the context's stream.  Scope, fixed: one slice per picture (or, with the *3 calls below, several of whole rows), Intra16x16 macroblocks only -- luma vertical / horizontal / DC /
  * plane and the four chroma modes, chosen per macroblock by SATD among the modes whose neighbours exist -- one QP (mb_qp_delta 0), the
  * intra dead zone i_luma_deadzone[1] and the context's i_chroma_qp_offset, CAVLC slice data whatever the context's b_cabac (an IDR slice
  * names a PPS of its own: a CABAC stream carries a second PPS with entropy_coding_mode_flag 0, which is legal), no loop filter
@@ -1031,7 +1035,49 @@ int pcamv_gpu_video_gops_device(pcamv_ctx_t *ctx, const uint8_t *bytes, size_t b
  * -6 .. 6 and an idc above 2 PCAMV_EINVAL.  All four outputs are -1 on failure.  A decoder of these pictures is decode_islice_cavlc
  * followed, unless the idc is 1, by deblock_intra_picture.
  * Kernel: k_idr_deblock (csrc/pcamv_idr_deblock.h), one wavefront per macroblock, one launch per anti-diagonal x + 2 y over all contexts
- * of the call, behind the coder's groups and before the pictures become the references. */
+ * of the call, behind the coder's groups and before the pictures become the references.
+ *
+ * Several slices per picture (PCAMV_FEATURE_IDR_SLICES): the calls that end in 3 take `slice_rows` R, the macroblock rows of a slice.  R = 0
+ * or R >= mb_h: one slice, the *2 call byte for byte through the same launches.  1 <= R < mb_h: S = ceil(mb_h / R) slices, slice s the rows
+ * [s R, min((s + 1) R, mb_h)), the last one possibly shorter.  R < 0 is PCAMV_EINVAL, judged with the other values before anything is
+ * queued.  Slices are whole rows: a macroblock's left neighbour is always in its slice, its top and top-left neighbours are there
+ * together or not at all.  A macroblock is coded as before with "available" meaning "in the slice": the modes to choose among, the
+ * prediction, nC of 9.2.1.  Every slice's header says the same -- slice_type 7, pps_id, frame_num 0, idr_pic_id, the POC elements,
+ * slice_qp_delta, the deblocking elements -- but for first_mb_in_slice = s R mb_w; one access unit delimiter per picture, in front of
+ * slice 0.  deblock 1: idc 0, the filter crosses slice edges and is the one-slice picture's (bS 4 / 3 by position); deblock 0: idc 1 in
+ * every slice.  P pictures stay one slice per picture.
+ * write_idr_slice_header3: header2 with first_mb_in_slice = first_mb, 0 .. 2^20 - 1 (else PCAMV_EINVAL, with the other values).
+ * parse_idr_slice_header3: header2's parser that reads first_mb_in_slice into *first_mb (above 2^20 - 1: PCAMV_EINVAL) where the others
+ * refuse a value that is not 0; all five outputs -1 on failure.
+ * encode_idr3: with S > 1, out receives the S units behind each other and as_nal must be 1 (RBSPs behind each other mean nothing):
+ * PCAMV_EINVAL otherwise, before anything is queued.  A capacity below the sum of the units is PCAMV_ENOMEM.  idr_bound3: the sum of
+ * idr_bound over the slices.
+ * write_stream_idr3: the stream receives [delimiter +] the S units back to back; they fit together or the stream and len[i] stay as they
+ * are (PCAMV_ENOMEM), as a delimiter and its unit do.  The picture counter moves by 1, the unit counter (stream_written's third value) by S.
+ * The receiving side needs nothing: the IDR slices of one picture stay in one GOP (the rule at "One video of many chains") and are
+ * PCAMV_UNIT_OTHER in an index.
+ * decode_idr_picture: host code, no GPU; the definition the device is held to.  bytes[0, len) is Annex B; its units of type 5 are the
+ * picture's slices in order, units that are no VCL units are passed over.  Every header is read by parse_idr_slice_header3 under params;
+ * each slice is decoded by decode_islice_cavlc as a picture of its own rows into the planes y / u / v (16 mb_w x 16 mb_h, half that
+ * twice), and unless the idc is 1 the whole picture then goes through deblock_intra_picture.  PCAMV_EUNSUP: a first_mb that is no
+ * multiple of mb_w; slices out of order, overlapping or not covering the picture (a slice that does not end where the next begins, or
+ * the last one at the picture's end, fails its decoder's end-of-slice rule and is reported so); slices that disagree in QP, idr_pic_id
+ * or idc; idc 2 with more than one slice; a VCL unit of another type among them.  No slice at all: PCAMV_EINVAL.  *n_slices: how many.
+ * Kernels with S > 1: k_idr_mb as before; k_idr_prefix restarts at every slice behind that slice's header; k_idr_pack works per (slice,
+ * context); k_idr_unit_len, one wavefront per (context, slice), counts the unit's bytes by the writer's own walk with the stores
+ * suppressed; k_idr_place, one lane per context, places the units or refuses them all; k_idr_unit, one wavefront per (context, slice),
+ * writes at its place -- units that are neighbours share a dword, and no dword store covers a byte outside the unit's own.  With S = 1
+ * there is no length pass.  Working memory: 2842 bytes per macroblock and place as before, and 64 S per place (a prefix entry, a header's
+ * room in the RBSP, a unit's length and offset); the 8 GiB cap and the groups stand. */
+int pcamv_gpu_write_idr_slice_header3(const pcamv_stream_params_t *params, int nal_ref_idc, int idr_pic_id, int slice_qp, int deblock, int64_t first_mb, uint8_t *bits,
+                                      size_t cap, int32_t *n_bits);
+int pcamv_gpu_parse_idr_slice_header3(const uint8_t *rbsp, size_t len, int nal_header, const pcamv_stream_params_t *params, int64_t *start_bit,
+                                      int32_t *slice_qp, int32_t *idr_pic_id, int32_t *disable_deblocking_filter_idc, int64_t *first_mb);
+int pcamv_gpu_encode_idr3(pcamv_ctx_t *ctx, int qp, int pps_id, int idr_pic_id, int as_nal, int deblock, int slice_rows, uint8_t *out, size_t cap, size_t *len);
+int pcamv_gpu_batch_write_stream_idr3(pcamv_batch_t *batch, int qp, int pps_id, int idr_pic_id, int deblock, int slice_rows, void *stream);
+int64_t pcamv_gpu_idr_bound3(const pcamv_ctx_t *ctx, int as_nal, int slice_rows);
+int pcamv_gpu_decode_idr_picture(const uint8_t *bytes, size_t len, int mb_w, int mb_h, const pcamv_stream_params_t *params, int chroma_qp_index_offset,
+                                 uint8_t *y, uint8_t *u, uint8_t *v, int32_t *slice_qp, int32_t *idr_pic_id, int32_t *n_slices);
 int pcamv_gpu_write_idr_slice_header2(const pcamv_stream_params_t *params, int nal_ref_idc, int idr_pic_id, int slice_qp, int deblock, uint8_t *bits, size_t cap,
                                       int32_t *n_bits);
 int pcamv_gpu_parse_idr_slice_header2(const uint8_t *rbsp, size_t len, int nal_header, const pcamv_stream_params_t *params, int64_t *start_bit,

@@ -6,7 +6,12 @@ line and writes it to profiles/idr_timing.json.  Needs a GPU.
 --deblock: the same calls on the same chains in the same run without and with the loop filter (write_stream_idr(deblock=True), kernel
 k_idr_deblock): the wall clock of both, k_idr_deblock over its launches next to k_idr_mb, into profiles/idr_deblock_timing.json.
 
-    python tools/idr_timing.py [--deblock] [--gops 256] [--steps 3] [--warmup 1] [--reps 3] [--out FILE]
+--slice-rows R[,R...]: the same chains in the same run with the pictures in slices of R macroblock rows (write_stream_idr(slice_rows=R);
+0: one slice), reps calls each after a first: per R the wall clock, every k_idr_* timer (k_idr_unit_len and k_idr_place run only with
+more than one slice) and the bytes of a picture -- the S - 1 further headers and what prediction loses at the slice edges show there --
+into profiles/idr_slices_timing.json.
+
+    python tools/idr_timing.py [--deblock | --slice-rows 0,1,4,17] [--gops 256] [--steps 3] [--warmup 1] [--reps 3] [--out FILE]
 """
 import argparse
 import json
@@ -17,6 +22,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "video-steganography-pcamv_amd")]
 KERNELS = ("k_idr_mb", "k_idr_prefix", "k_idr_pack", "k_idr_unit", "k_stream_commit")
+SLICE_KERNELS = ("k_idr_mb", "k_idr_prefix", "k_idr_pack", "k_idr_unit_len", "k_idr_place", "k_idr_unit", "k_stream_commit")
 
 
 def main():
@@ -29,9 +35,11 @@ def main():
     ap.add_argument("--emrate", type=float, default=0.5)
     ap.add_argument("--region", type=int, default=6 << 20, help="bytes of a chain's stream")
     ap.add_argument("--deblock", action="store_true", help="time the pictures without and with the loop filter")
+    ap.add_argument("--slice-rows", default=None, help="comma-separated macroblock rows per slice to time, 0: one slice")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    args.out = args.out or os.path.join(ROOT, "profiles", "idr_deblock_timing.json" if args.deblock else "idr_timing.json")
+    slice_rows = [int(v) for v in args.slice_rows.split(",")] if args.slice_rows else None
+    args.out = args.out or os.path.join(ROOT, "profiles", "idr_slices_timing.json" if slice_rows is not None else "idr_deblock_timing.json" if args.deblock else "idr_timing.json")
     import numpy as np
     import torch
     import pcamv_amd
@@ -60,7 +68,7 @@ def main():
         enc.set_fenc_device(*[pl.data_ptr() for pl in dframes[bench.tri(run.phases[k], len(dframes))]])
     out = dict(gops=n, width=W, height=H, qp=args.qp, emrate=args.emrate, reps=args.reps, steps=args.steps)
 
-    def idr_calls(deblock, kernels):
+    def idr_calls(deblock, kernels, rows=0):
         """reps + 1 calls, the first not counted (it makes the working memory): wall clock per call, every kernel's time per call"""
         wall, res = [], {}
         for rep in range(args.reps + 1):
@@ -71,7 +79,7 @@ def main():
                 for name in kernels:
                     run.batch.kernel_time(name, reset=True)
             w0 = time.perf_counter()
-            run.batch.write_stream_idr(args.qp, pps_id=1, idr_pic_id=rep, stream=stream.cuda_stream, deblock=deblock)
+            run.batch.write_stream_idr(args.qp, pps_id=1, idr_pic_id=rep, stream=stream.cuda_stream, deblock=deblock, slice_rows=rows)
             torch.cuda.synchronize()
             if rep:
                 wall.append((time.perf_counter() - w0) * 1e3)
@@ -83,6 +91,21 @@ def main():
             res[name + ("_launches_per_call" if name == "k_idr_deblock" else "_timed_spans_per_call")] = launches / max(args.reps, 1)
         return wall, res
 
+    if slice_rows is not None:
+        mb_h = H // 16
+        out["slice_rows"] = {}
+        for rows in slice_rows:
+            wall, res = idr_calls(False, SLICE_KERNELS, rows)
+            S = 1 if rows <= 0 or rows >= mb_h else -(-mb_h // rows)
+            nbytes = (length.cpu().numpy() - len(head) - 6).astype(np.int64)
+            res.update(slices=S, wall_ms_median=float(np.median(wall)), picture_bytes=dict(min=int(nbytes.min()), mean=float(nbytes.mean()), max=int(nbytes.max())))
+            out["slice_rows"][str(rows)] = res
+        line = json.dumps(dict(mode="idr_slices", tool="idr_timing.py", **out))
+        print(line)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+        run.leave_to_exit()
+        return
     wall, res = idr_calls(False, KERNELS)
     out.update(res)
     if args.deblock:

@@ -11,6 +11,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <new>
+#include <vector>
 #include "pcamv_planes.hip.h"
 #include "pcamv_kernels.hip.h"
 #include "pcamv_embed.hip.h"
@@ -44,14 +45,14 @@
     X(KT_VIDEO_CUT, "k_video_cut") X(KT_MESSAGE_COUNT, "k_message_count") X(KT_MESSAGE_PLAN, "k_message_plan") \
     X(KT_MESSAGE_JOBS, "k_message_jobs") X(KT_EXTRACT_CHAIN_MESSAGE, "k_extract_chain_message") X(KT_MESSAGE_CHECK, "k_message_check") \
     X(KT_IDR_MB, "k_idr_mb") X(KT_IDR_PREFIX, "k_idr_prefix") X(KT_IDR_PACK, "k_idr_pack") X(KT_IDR_UNIT, "k_idr_unit") \
-    X(KT_IDR_DEBLOCK, "k_idr_deblock")
+    X(KT_IDR_DEBLOCK, "k_idr_deblock") X(KT_IDR_UNIT_LEN, "k_idr_unit_len") X(KT_IDR_PLACE, "k_idr_place")
 #define KT_ENUM(id, name) id,
 enum { PCAMV_TIMERS(KT_ENUM) KT_N };
 #undef KT_ENUM
 #define PCAMV_FEATURES (PCAMV_FEATURE_PAYLOAD | PCAMV_FEATURE_SLICE_PARSER | PCAMV_FEATURE_SLICE_PARSER_CAVLC | PCAMV_FEATURE_SLICE_WRITER | \
                         PCAMV_FEATURE_SLICE_WRITER_CAVLC | PCAMV_FEATURE_NAL_DEVICE | PCAMV_FEATURE_STREAM_DEVICE | PCAMV_FEATURE_STREAM_WRITER | \
                         PCAMV_FEATURE_STREAM_WINDOW | PCAMV_FEATURE_PARAM_SETS | PCAMV_FEATURE_VIDEO | PCAMV_FEATURE_MESSAGE | PCAMV_FEATURE_IDR | \
-                        PCAMV_FEATURE_IDR_DEBLOCK)
+                        PCAMV_FEATURE_IDR_DEBLOCK | PCAMV_FEATURE_IDR_SLICES)
 #define MSG_GUARD_WORDS 4       /* words behind a batch's received stream that nothing may write */
 #define SLICE_GUARD_MBS 4       /* records behind a context's receive-side records that nothing may write (pcamv_gpu_debug_slice_records) */
 #define NSTAGE 2                /* staging buffers of extract_slices: a call waits for the one before the last */
@@ -2890,36 +2891,53 @@ void pcamv_launch_idr_unit(const IdrJobs &J, int g0, int g, hipStream_t st);
 void pcamv_launch_idr_slot(const IdrJobs &J, const void *sws_ctx, int n, hipStream_t st);
 void pcamv_launch_idr_deblock(const IdrJobs &J, int n, int mb_w, int mb_h, hipStream_t st);
 int pcamv_idr_deblock_launches(int mb_w, int mb_h);
-extern "C" int pcamv_gpu_write_idr_slice_header2(const pcamv_stream_params_t *params, int nal_ref_idc, int idr_pic_id, int slice_qp, int deblock, uint8_t *bits, size_t cap,
-                                                 int32_t *n_bits)
+void pcamv_launch_idr_prefix_slices(const IdrJobs &J, int g0, int g, hipStream_t st);
+void pcamv_launch_idr_pack_slices(const IdrJobs &J, int g0, int g, int mb_w, int mb_h, hipStream_t st);
+void pcamv_launch_idr_unit_len(const IdrJobs &J, int g0, int g, hipStream_t st);
+void pcamv_launch_idr_place(const IdrJobs &J, int g0, int g, hipStream_t st);
+void pcamv_launch_idr_unit_slices(const IdrJobs &J, int g0, int g, hipStream_t st);
+extern "C" int pcamv_gpu_write_idr_slice_header3(const pcamv_stream_params_t *params, int nal_ref_idc, int idr_pic_id, int slice_qp, int deblock, int64_t first_mb,
+                                                 uint8_t *bits, size_t cap, int32_t *n_bits)
 {
     if (n_bits) *n_bits = 0;
     if (!params || !n_bits || (!bits && cap)) return PCAMV_EINVAL;
     int n = 0;
-    TRY(pcamv_idr_header_write2(*params, nal_ref_idc, idr_pic_id, slice_qp, deblock, NULL, &n));       /* judged and counted; nothing stored */
+    TRY(pcamv_idr_header_write3(*params, nal_ref_idc, idr_pic_id, slice_qp, deblock, first_mb, NULL, &n));       /* judged and counted; nothing stored */
     if ((size_t)(n + 7) / 8 > cap) return PCAMV_ENOMEM;
-    const int rc = pcamv_idr_header_write2(*params, nal_ref_idc, idr_pic_id, slice_qp, deblock, bits, &n);
+    const int rc = pcamv_idr_header_write3(*params, nal_ref_idc, idr_pic_id, slice_qp, deblock, first_mb, bits, &n);
     *n_bits = n;
     return rc;
+}
+extern "C" int pcamv_gpu_write_idr_slice_header2(const pcamv_stream_params_t *params, int nal_ref_idc, int idr_pic_id, int slice_qp, int deblock, uint8_t *bits, size_t cap,
+                                                 int32_t *n_bits)
+{
+    return pcamv_gpu_write_idr_slice_header3(params, nal_ref_idc, idr_pic_id, slice_qp, deblock, 0, bits, cap, n_bits);
 }
 extern "C" int pcamv_gpu_write_idr_slice_header(const pcamv_stream_params_t *params, int nal_ref_idc, int idr_pic_id, int slice_qp, uint8_t *bits, size_t cap, int32_t *n_bits)
 {
     return pcamv_gpu_write_idr_slice_header2(params, nal_ref_idc, idr_pic_id, slice_qp, 0, bits, cap, n_bits);
 }
 extern "C" int64_t pcamv_gpu_idr_bound(const pcamv_ctx_t *c, int as_nal) { return c ? (int64_t)idr_bound(c->F.n_mb, as_nal) : PCAMV_EINVAL; }
-/* the working memory of one place of a group: bytes per context */
-static size_t idr_place_bytes(int n_mb, size_t *rbsp_stride)
+extern "C" int64_t pcamv_gpu_idr_bound3(const pcamv_ctx_t *c, int as_nal, int slice_rows)
 {
-    const size_t rbsp = ((size_t)idr_bound(n_mb, 0) + 255) & ~(size_t)255;
+    return c && slice_rows >= 0 ? (int64_t)idr_bound_slices(c->F.mb_w, c->F.mb_h, slice_rows, as_nal) : PCAMV_EINVAL;
+}
+/* the working memory of one place of a group: bytes per context.  Per macroblock 24 counts, a slot of 1408, a length of 4, a prefix
+ * entry of 8 and 1397.4 of RBSP: 2842; a picture of S > 1 slices adds 64 S per place -- a prefix entry, the room of a header and its
+ * paddings in the RBSP (IDR_SLICE_PAD_BYTES), a unit's length and its offset */
+static size_t idr_place_bytes(int n_mb, int n_slices, size_t *rbsp_stride)
+{
+    const size_t S = (size_t)n_slices;
+    const size_t rbsp = ((size_t)(S > 1 ? idr_slice_rbsp_at(n_mb, n_slices) : idr_bound(n_mb, 0)) + 255) & ~(size_t)255;
     if (rbsp_stride) *rbsp_stride = rbsp;
-    return (((size_t)n_mb * (IDR_NZ_BYTES + IDR_SLOT_DWORDS * 4 + 4) + ((size_t)n_mb + 1) * 8 + rbsp + 255) & ~(size_t)255) + 256;     /* (+ 256: the counts of a group end at a multiple of 256) */
+    return (((size_t)n_mb * (IDR_NZ_BYTES + IDR_SLOT_DWORDS * 4 + 4) + ((size_t)n_mb + S) * 8 + (S > 1 ? 16 * S : 0) + rbsp + 255) & ~(size_t)255) + 256;     /* (+ 256: the counts of a group end at a multiple of 256) */
 }
 #define IDR_GROUP_BYTES ((size_t)8 << 30)       /* the most working memory a batch keeps for its IDR pictures: larger batches run in groups */
 /* the working memory (made at first use, kept until the batch goes), the tables, and J but for its destination */
-static int idr_setup(pcamv_batch *b, int qp, const uint8_t *hdr, int hdr_bits, int nal_byte, IdrJobs *J)
+static int idr_setup(pcamv_batch *b, int qp, const uint8_t *hdr, int hdr_bits, int nal_byte, int slice_rows, IdrJobs *J)
 {
     const pcamv_ctx *c0 = b->ctx[0];
-    const int n_mb = c0->F.n_mb;
+    const int n_mb = c0->F.n_mb, n_slices = idr_n_slices(c0->F.mb_h, slice_rows);
     for (int i = 0; i < b->n; i++) {
         const pcamv_ctx *c = b->ctx[i];
         if (!c->F.fenc[0] || !c->F.fenc[1] || !c->F.fenc[2]) return fail(b, PCAMV_EINVAL, "context %d has no source picture (pcamv_gpu_upload_fenc, pcamv_gpu_set_fenc_device)", i);
@@ -2927,10 +2945,10 @@ static int idr_setup(pcamv_batch *b, int qp, const uint8_t *hdr, int hdr_bits, i
     }
     if (c0->p.i_luma_deadzone[1] < 0 || c0->p.i_luma_deadzone[1] > 32) return fail(b, PCAMV_EINVAL, "i_luma_deadzone[1] outside 0 .. 32");
     size_t rbsp_stride = 0;
-    const size_t place = idr_place_bytes(n_mb, &rbsp_stride);
+    const size_t place = idr_place_bytes(n_mb, n_slices, &rbsp_stride);
     int group = (int)(IDR_GROUP_BYTES / place);
     group = group < 1 ? 1 : group > b->n ? b->n : group;
-    if (!b->d_idr || b->idr_group != group) {
+    if (!b->d_idr || b->idr_group != group || place * (size_t)group > b->d_idr.cap) {       /* (the last: a call with more slices than any before) */
         if (b->d_idr) HIPCHK(b, hipDeviceSynchronize());    /* (regrown only behind this: pictures in flight work in the block) */
         TRY(b->d_idr.room(b, place * (size_t)group));
         b->idr_group = group;
@@ -2947,7 +2965,8 @@ static int idr_setup(pcamv_batch *b, int qp, const uint8_t *hdr, int hdr_bits, i
     memset((void *)&j, 0, sizeof(j));
     const size_t g = (size_t)group, n = (size_t)n_mb;
     uint8_t *at = b->d_idr;
-    j.pre = (long long *)at; at += g * (n + 1) * 8;
+    j.pre = (long long *)at; at += g * (n + (size_t)n_slices) * 8;
+    if (n_slices > 1) { j.ulen = (long long *)at; at += g * (size_t)n_slices * 8; j.uoff = (long long *)at; at += g * (size_t)n_slices * 8; }
     j.slots = (uint32_t *)at; at += g * n * IDR_SLOT_DWORDS * 4;
     j.bits = (int *)at; at += g * n * 4;
     j.nz = at; at += (g * n * IDR_NZ_BYTES + 255) & ~(size_t)255;
@@ -2958,26 +2977,56 @@ static int idr_setup(pcamv_batch *b, int qp, const uint8_t *hdr, int hdr_bits, i
     for (int o = -12; o <= 12; o++) { const int q = qp + o; j.qpc_of[12 + o] = pcamv_chroma_qp_tab[q < 0 ? 0 : q > 51 ? 51 : q]; }
     j.hdr_bits = hdr_bits; j.nal_byte = nal_byte; j.n_mb = n_mb; j.qp = qp; j.dz = c0->p.i_luma_deadzone[1];
     j.status = b->d_wstat;
+    j.n_slices = n_slices; j.slice_rows = n_slices > 1 ? slice_rows : 0;
+    return 0;
+}
+/* the headers of the S > 1 slices of a picture, which differ in first_mb_in_slice alone; the first is the one idr_setup was given */
+static int idr_slice_headers(const pcamv_stream_params_t &P, int nal_ref_idc, int idr_pic_id, int qp, int deblock, int mb_w, int mb_h, int slice_rows, std::vector<IdrSliceHdr> *tab)
+{
+    const int S = idr_n_slices(mb_h, slice_rows);
+    tab->assign(S > 1 ? (size_t)S : 0, IdrSliceHdr());
+    for (size_t s = 0; s < tab->size(); s++)
+        TRY(pcamv_idr_header_write3(P, nal_ref_idc, idr_pic_id, qp, deblock, idr_slice_first_mb(mb_w, mb_h, slice_rows, (int)s), (*tab)[s].hdr, &(*tab)[s].bits));
     return 0;
 }
 /* every context's source coded, group by group, on `st`; (J.deblock) every picture filtered, all contexts per launch -- k_idr_deblock works
  * on the contexts' reconstruction planes and on nothing of a group's working memory, so it stands behind the groups; then every context's
  * reconstruction becomes its reference: copied into the context's own reference planes, and the plane production of a step with no
  * previous motion -- the state pcamv_gpu_set_ref leaves */
-static int idr_run(pcamv_batch *b, IdrJobs &J, const void *sws_ctx, hipStream_t st)
+static int idr_run(pcamv_batch *b, IdrJobs &J, const void *sws_ctx, hipStream_t st, const std::vector<IdrSliceHdr> &shdr)
 {
+    int stage = -1;
+    if (J.n_slices > 1) {               /* the S headers: a small table through the staging ring of the writers' headers */
+        const size_t total = shdr.size() * sizeof(IdrSliceHdr);
+        if ((int)shdr.size() != J.n_slices) return fail(b, PCAMV_EINVAL, "the slices' headers are missing");
+        TRY(stage_take(b, b->tx_stage, total, &stage));
+        memcpy(b->tx_stage.h[stage], shdr.data(), total);
+        TRY(stage_send(b, b->tx_stage, stage, total, st));
+        J.shdr = (const IdrSliceHdr *)b->tx_stage.d[stage].p;
+        J.units = (SwsCtx *)sws_ctx;
+    }
     const FrameDev *dF; const EmbedDev *dE; int slot;
-    TRY(batch_push_descs(b, st, &dF, &dE, &slot));
+    const int prc = batch_push_descs(b, st, &dF, &dE, &slot);
+    if (prc) { if (stage >= 0) stage_release(b, b->tx_stage, stage, st); return prc; }
     J.Fs = dF;
     const FrameDev &F = b->ctx[0]->F;
     if (sws_ctx) pcamv_launch_idr_slot(J, sws_ctx, b->n, st);
     for (int g0 = 0; g0 < b->n; g0 += b->idr_group) {
         const int g = b->n - g0 < b->idr_group ? b->n - g0 : b->idr_group;
         timed(b, KT_IDR_MB, st, [&] { pcamv_launch_idr_mb(J, g0, g, F.mb_w, F.mb_h, st); });
+        if (J.n_slices > 1) {           /* several slices: a length pass and a placement in front of the units, which a wavefront each then writes */
+            timed(b, KT_IDR_PREFIX, st, [&] { pcamv_launch_idr_prefix_slices(J, g0, g, st); });
+            timed(b, KT_IDR_PACK, st, [&] { pcamv_launch_idr_pack_slices(J, g0, g, F.mb_w, F.mb_h, st); });
+            timed(b, KT_IDR_UNIT_LEN, st, [&] { pcamv_launch_idr_unit_len(J, g0, g, st); });
+            timed(b, KT_IDR_PLACE, st, [&] { pcamv_launch_idr_place(J, g0, g, st); });
+            timed(b, KT_IDR_UNIT, st, [&] { pcamv_launch_idr_unit_slices(J, g0, g, st); });
+            continue;
+        }
         timed(b, KT_IDR_PREFIX, st, [&] { pcamv_launch_idr_prefix(J, g0, g, st); });
         timed(b, KT_IDR_PACK, st, [&] { pcamv_launch_idr_pack(J, g0, g, st); });
         timed(b, KT_IDR_UNIT, st, [&] { pcamv_launch_idr_unit(J, g0, g, st); });
     }
+    if (stage >= 0) TRY(stage_release(b, b->tx_stage, stage, st));
     if (J.deblock) {
         b->kt[KT_IDR_DEBLOCK].weight = pcamv_idr_deblock_launches(F.mb_w, F.mb_h);      /* one pair of events around the anti-diagonals (all counted, also the empty ones of a picture one macroblock wide) */
         timed(b, KT_IDR_DEBLOCK, st, [&] { pcamv_launch_idr_deblock(J, b->n, F.mb_w, F.mb_h, st); });
@@ -3003,10 +3052,12 @@ static pcamv_stream_params_t idr_probe_params(int pps_id)
     pcamv_stream_params_t P = {4, 0, 4, 0, 0, 0, 1, 0, 0, 26, 1, pps_id};
     return P;
 }
-extern "C" int pcamv_gpu_encode_idr2(pcamv_ctx_t *c, int qp, int pps_id, int idr_pic_id, int as_nal, int deblock, uint8_t *out, size_t cap, size_t *len)
+extern "C" int pcamv_gpu_encode_idr3(pcamv_ctx_t *c, int qp, int pps_id, int idr_pic_id, int as_nal, int deblock, int slice_rows, uint8_t *out, size_t cap, size_t *len)
 {
     if (!c || !out || !len || cap > ((size_t)1 << 40)) return PCAMV_EINVAL;
     *len = 0;
+    if (slice_rows < 0) return fail(c, PCAMV_EINVAL, "encode_idr3: slice_rows below 0");
+    if (idr_n_slices(c->F.mb_h, slice_rows) > 1 && !as_nal) return fail(c, PCAMV_EINVAL, "encode_idr3: the RBSPs of several slices behind each other mean nothing: as_nal must be 1");
     HIPCHK(c, hipSetDevice(c->device));
     pcamv_batch *b = c->self;
     TRY(on_behalf(c, b, batch_live(b)));
@@ -3016,8 +3067,10 @@ extern "C" int pcamv_gpu_encode_idr2(pcamv_ctx_t *c, int qp, int pps_id, int idr
     const int hrc = pcamv_idr_header_write2(P, 3, idr_pic_id, qp, deblock, hdr, &hdr_bits);
     if (hrc) return fail(c, hrc, deblock ? "encode_idr2: qp outside 0 .. 51, pps_id outside 0 .. 255, idr_pic_id outside 0 .. 65535 or deblock not 0 or 1"
                                          : "encode_idr: qp outside 0 .. 51, pps_id outside 0 .. 255 or idr_pic_id outside 0 .. 65535");
+    std::vector<IdrSliceHdr> shdr;
+    TRY(idr_slice_headers(P, 3, idr_pic_id, qp, deblock, c->F.mb_w, c->F.mb_h, slice_rows, &shdr));
     IdrJobs J;
-    TRY(on_behalf(c, b, idr_setup(b, qp, hdr, hdr_bits, 3 << 5 | 5, &J)));
+    TRY(on_behalf(c, b, idr_setup(b, qp, hdr, hdr_bits, 3 << 5 | 5, slice_rows, &J)));
     DevBuf<uint8_t> d_out;
     TRY(d_out.room(c, cap ? cap : 1));
     long long *arr = (long long *)b->d_idr_ctx.p;
@@ -3026,7 +3079,7 @@ extern "C" int pcamv_gpu_encode_idr2(pcamv_ctx_t *c, int qp, int pps_id, int idr
     HIPCHK(c, hipMemcpy(arr, h_arr, sizeof(h_arr), hipMemcpyHostToDevice));
     J.bytes = d_out; J.bytes_size = (long long)cap; J.off = arr; J.cap = arr + 1; J.len = arr + 2; J.as_nal = as_nal != 0; J.first = NULL;
     J.deblock = deblock;
-    TRY(on_behalf(c, b, idr_run(b, J, NULL, c->stream)));
+    TRY(on_behalf(c, b, idr_run(b, J, NULL, c->stream, shdr)));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     int st = 0; long long n = 0;
     HIPCHK(c, hipMemcpy(&st, b->d_wstat, sizeof(st), hipMemcpyDeviceToHost));
@@ -3037,15 +3090,20 @@ extern "C" int pcamv_gpu_encode_idr2(pcamv_ctx_t *c, int qp, int pps_id, int idr
     *len = (size_t)n;
     return 0;
 }
+extern "C" int pcamv_gpu_encode_idr2(pcamv_ctx_t *c, int qp, int pps_id, int idr_pic_id, int as_nal, int deblock, uint8_t *out, size_t cap, size_t *len)
+{
+    return pcamv_gpu_encode_idr3(c, qp, pps_id, idr_pic_id, as_nal, deblock, 0, out, cap, len);
+}
 extern "C" int pcamv_gpu_encode_idr(pcamv_ctx_t *c, int qp, int pps_id, int idr_pic_id, int as_nal, uint8_t *out, size_t cap, size_t *len)
 {
     return pcamv_gpu_encode_idr2(c, qp, pps_id, idr_pic_id, as_nal, 0, out, cap, len);
 }
-extern "C" int pcamv_gpu_batch_write_stream_idr2(pcamv_batch_t *b, int qp, int pps_id, int idr_pic_id, int deblock, void *stream)
+extern "C" int pcamv_gpu_batch_write_stream_idr3(pcamv_batch_t *b, int qp, int pps_id, int idr_pic_id, int deblock, int slice_rows, void *stream)
 {
     if (!b) return PCAMV_EINVAL;
     HIPCHK(b, hipSetDevice(b->device));
     TRY(batch_live(b));
+    if (slice_rows < 0) return fail(b, PCAMV_EINVAL, "write_stream_idr3: slice_rows below 0");
     StreamOut &O = b->so;
     if (!O.ready) return fail(b, PCAMV_EINVAL, "no byte streams were opened on this batch yet (pcamv_gpu_batch_stream_open)");
     if (O.stepped) return fail(b, PCAMV_EINVAL, "write_stream_idr belongs behind the open and before the first picture of its streams");
@@ -3060,15 +3118,21 @@ extern "C" int pcamv_gpu_batch_write_stream_idr2(pcamv_batch_t *b, int qp, int p
     if (hrc) return fail(b, hrc, deblock ? "write_stream_idr2: qp outside 0 .. 51, pps_id outside 0 .. 255, idr_pic_id outside 0 .. 65535 or deblock not 0 or 1"
                                          : "write_stream_idr: qp outside 0 .. 51, pps_id outside 0 .. 255 or idr_pic_id outside 0 .. 65535");
     hipStream_t st = stream ? (hipStream_t)stream : b->ctx[0]->stream;
+    std::vector<IdrSliceHdr> shdr;
+    TRY(idr_slice_headers(P, O.S.W.nal_ref_idc, idr_pic_id, qp, deblock, b->ctx[0]->F.mb_w, b->ctx[0]->F.mb_h, slice_rows, &shdr));
     IdrJobs J;
-    TRY(idr_setup(b, qp, hdr, hdr_bits, O.S.W.nal_ref_idc << 5 | 5, &J));
+    TRY(idr_setup(b, qp, hdr, hdr_bits, O.S.W.nal_ref_idc << 5 | 5, slice_rows, &J));
     const StreamWrite SJ = stream_out_jobs(b);
     J.bytes = SJ.bytes; J.bytes_size = SJ.bytes_size; J.off = SJ.w_off; J.cap = SJ.w_cap; J.len = SJ.w_len; J.first = SJ.first; J.as_nal = 1; J.aud = O.S.W.aud;
     J.deblock = deblock;
     O.stepped = 1;
-    TRY(idr_run(b, J, SJ.ctx, st));
+    TRY(idr_run(b, J, SJ.ctx, st, shdr));
     timed_kernel(b, KT_STREAM_COMMIT, st, k_stream_commit, dim3((b->n + 63) / 64), dim3(64), SJ);
     return launched(b);
+}
+extern "C" int pcamv_gpu_batch_write_stream_idr2(pcamv_batch_t *b, int qp, int pps_id, int idr_pic_id, int deblock, void *stream)
+{
+    return pcamv_gpu_batch_write_stream_idr3(b, qp, pps_id, idr_pic_id, deblock, 0, stream);
 }
 extern "C" int pcamv_gpu_batch_write_stream_idr(pcamv_batch_t *b, int qp, int pps_id, int idr_pic_id, void *stream)
 {

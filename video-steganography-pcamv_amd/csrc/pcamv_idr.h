@@ -1,13 +1,14 @@
 /*
  * pcamv_idr.h -- the IDR picture a chain starts with, coded on the device: control code that compiles for the device and for the host.
  *
- * On the device it is the body of k_idr_mb, k_idr_prefix, k_idr_pack and k_idr_unit (pcamv_idr.hip); on the host it is what
- * tests/fuzz/check_idr_write.cpp compiles with the scalar form of SP_LANES (pcamv_slice_parse.h), to be decoded by the library's host
- * decoder pcamv_gpu_decode_islice_cavlc (pcamv_mvsyntax.h), which stays the independent check: the two share nothing but the code
+ * On the device it is the body of k_idr_mb, k_idr_prefix, k_idr_pack and k_idr_unit and of their siblings for pictures of several slices
+ * (pcamv_idr.hip); on the host it is what tests/fuzz/check_idr_write.cpp and check_idr_slices.cpp compile with the scalar form of
+ * SP_LANES (pcamv_slice_parse.h), to be decoded by the library's host decoder pcamv_gpu_decode_islice_cavlc (pcamv_mvsyntax.h), which stays the independent check: the two share nothing but the code
  * tables of sv_build_tables.  No HIP type.  Included behind pcamv_slice_write_cavlc.h (swv_block: a residual block's bit string by one
  * lane; the output path behind a final byte) and pcamv_stream_write.h (the bit writer of the slice headers).
  *
- * Scope, fixed: one I slice per picture, Intra16x16 macroblocks only (luma V / H / DC / plane, chroma DC / H / V / plane, each chosen by
+ * Scope, fixed: one I slice per picture, or several of whole macroblock rows (IdrPic::slice_rows; the layout: pcamv_idr_defs.h),
+ * Intra16x16 macroblocks only (luma V / H / DC / plane, chroma DC / H / V / plane, each chosen by
  * SATD among the modes whose neighbours exist, ties to the lower mode number of 8.3.3 / 8.3.4), one QP (mb_qp_delta 0), CAVLC whatever
  * the stream's P slices use, disable_deblocking_filter_idc 1: the reconstruction a decoder makes is the unfiltered one that is made here
  * and becomes the chain's reference (or, where the caller asks for a filtered picture, goes through pcamv_idr_deblock.h first, behind
@@ -29,7 +30,8 @@
  * One macroblock's bits (7.3.5 for an I slice): mb_type ue(1 + mode + 4 cbp_chroma + 12 (cbp_luma == 15)), intra_chroma_pred_mode ue,
  * mb_qp_delta se(0), Intra16x16DCLevel (always; nC as for luma block 0), the sixteen Intra16x16ACLevel blocks of 15 if any of them
  * has a level (cbp_luma 15, else 0), chroma DC if any chroma level, chroma AC if any chroma AC level.  total_coeff of the AC blocks is
- * what neighbours read for nC (9.2.1); the slice is the picture, so availability is the picture's edge.  CAVLC in an I slice has no
+ * what neighbours read for nC (9.2.1); availability is the slice's edge: the picture's, or with slice_rows the first row of the slice.
+ * CAVLC in an I slice has no
  * serial state -- no skip run, a constant QP -- so every macroblock's bit string is made where the macroblock is coded, into its own
  * slot of IDR_SLOT_DWORDS, and a prefix over the lengths places them.
  *
@@ -188,7 +190,8 @@ SP_HD int idr_nc_class(int na, int nb)
  * anti-diagonals before this one's are done.  Writes the block's reconstruction, counts, bit string and bit count. */
 PCAMV_DEV void idr_mb(IdrWork &W, const IdrPic &P, const uint16_t *vlc, int mx, int my)
 {
-    const int xy = my * P.mb_w + mx, avail = (mx > 0 ? 1 : 0) | (my > 0 ? 2 : 0);
+    /* available means in the slice (P.slice_rows whole rows): left always is, top and top-left are below the slice's first row */
+    const int xy = my * P.mb_w + mx, avail = (mx > 0 ? 1 : 0) | (my % idr_rows_per_slice(P.mb_h, P.slice_rows) > 0 ? 2 : 0);
     const int lw = 16 * P.mb_w, cw = 8 * P.mb_w;
     SP_SYNC();
     SP_LANES(l) {
@@ -207,7 +210,7 @@ PCAMV_DEV void idr_mb(IdrWork &W, const IdrPic &P, const uint16_t *vlc, int mx, 
         }
         if (l < IDR_NZ_BYTES) {
             W.nzl[l] = mx > 0 ? P.nz[(size_t)(xy - 1) * IDR_NZ_BYTES + l] : 0;
-            W.nzt[l] = my > 0 ? P.nz[(size_t)(xy - P.mb_w) * IDR_NZ_BYTES + l] : 0;
+            W.nzt[l] = (avail & 2) ? P.nz[(size_t)(xy - P.mb_w) * IDR_NZ_BYTES + l] : 0;
         }
         if (l < 27) W.nclamp[l] = 0;
     }
@@ -394,9 +397,12 @@ struct IdrOut {                         /* the members sw_emit works on (pcamv_s
 };
 /* rbsp[0, len) into dst[0, cap): (as_nal) long start code, header byte, emulation prevention.  win: 64 dwords.  Returns 0 and *len_out, or
  * PCAMV_ENOMEM with *len_out = 0; nothing is stored at or beyond cap */
-PCAMV_DEV int idr_unit(IdrOut &O, uint32_t *win, const uint8_t *rbsp, long long len, int nal_byte, int as_nal, uint8_t *dst, long long cap, long long *len_out)
+/* The walk itself.  count != 0: the length pass of a picture of several slices -- the same walk with no room at all (sw_raw counts what it
+ * does not store), carried to the end whatever the count: returns 0 and the unit's length, nothing stored */
+PCAMV_DEV int idr_unit_walk(IdrOut &O, uint32_t *win, const uint8_t *rbsp, long long len, int nal_byte, int as_nal, uint8_t *dst, long long cap, int count, long long *len_out)
 {
     *len_out = 0;
+    if (count) cap = 0;
     sw_out_begin(O, dst, cap);
     if (as_nal) { sw_raw(O, 0); sw_raw(O, 0); sw_raw(O, 0); sw_raw(O, 1); sw_raw(O, (uint32_t)nal_byte & 255u); O.as_nal = 1; }
     for (long long base = 0; base < len; base += 256) {             /* rbsp is dword-aligned and padded to whole dwords */
@@ -405,11 +411,42 @@ PCAMV_DEV int idr_unit(IdrOut &O, uint32_t *win, const uint8_t *rbsp, long long 
         SP_SYNC();
         const int m = len - base < 256 ? (int)(len - base) : 256;
         for (int k = 0; k < m; k++) sw_emit(O, SP_UNI(win[k >> 2]) >> (8 * (k & 3)));
-        if (O.n > O.cap) return PCAMV_ENOMEM;
+        if (!count && O.n > O.cap) return PCAMV_ENOMEM;
     }
+    if (count) { *len_out = O.n; return 0; }
     if (O.n > O.cap) return PCAMV_ENOMEM;
     if (O.fill) sw_flush(O);
     *len_out = O.n;
     return 0;
+}
+PCAMV_DEV int idr_unit(IdrOut &O, uint32_t *win, const uint8_t *rbsp, long long len, int nal_byte, int as_nal, uint8_t *dst, long long cap, long long *len_out)
+{
+    return idr_unit_walk(O, win, rbsp, len, nal_byte, as_nal, dst, cap, 0, len_out);
+}
+/* the units of a picture's S slices behind each other in cap bytes: uoff[0 .. S) from ulen[0 .. S) (idr_unit_walk's counts; a negative
+ * one: the slice could not be counted).  Returns 0 and the total, or PCAMV_ENOMEM / PCAMV_EINVAL with *total = 0: the slices of a picture
+ * succeed or fail together */
+SP_HD int idr_place(const long long *ulen, long long *uoff, int S, long long cap, long long *total)
+{
+    long long at = 0;
+    *total = 0;
+    for (int s = 0; s < S; s++) { if (ulen[s] < 0) return PCAMV_EINVAL; uoff[s] = at; at += ulen[s]; }
+    if (at > cap) return PCAMV_ENOMEM;
+    *total = at;
+    return 0;
+}
+/* the prefix rule of a picture of several slices, serially (the definition k_idr_prefix_slices is held to by the host check): pre gets
+ * n_mb + S entries, slice s's run at idr_slice_pre_at, its header's bits in front */
+SP_HD int idr_prefix_slices(const IdrPic &P, const IdrSliceHdr *shdr, long long *pre)
+{
+    const int S = idr_n_slices(P.mb_h, P.slice_rows);
+    int bad = 0;
+    for (int s = 0; s < S; s++) {
+        const int f = idr_slice_first_mb(P.mb_w, P.mb_h, P.slice_rows, s), n = idr_slice_n_mb(P.mb_w, P.mb_h, P.slice_rows, s);
+        long long *q = pre + idr_slice_pre_at(f, s), at = shdr[s].bits;
+        for (int k = 0; k < n; k++) { q[k] = at; if (P.bits[f + k] < 0) bad = 1; else at += P.bits[f + k]; }
+        q[n] = at;
+    }
+    return bad;
 }
 #endif

@@ -14,6 +14,10 @@
  *                 nothing stored at or beyond the capacity.
  *   k_idr_deblock one wavefront per macroblock, launched once per anti-diagonal x + 2 y = d over ALL contexts of the call, behind the
  *                 groups: it works on the contexts' reconstruction planes alone (idr_deblock_mb), in 688 bytes of LDS.
+ * A picture of S > 1 slices (IdrJobs::n_slices; whole macroblock rows, the layout in pcamv_idr_defs.h) goes through k_idr_mb with availability
+ * by slice, then k_idr_prefix_slices, k_idr_pack_slices, k_idr_unit_len (one wavefront per (context, slice): the unit's length by the
+ * writer's own walk, stores suppressed), k_idr_place (one lane per context: the units' places, all or none) and k_idr_unit_slices (one
+ * wavefront per (context, slice) into exactly its own bytes).  A picture of one slice is launched as it always was.
  * No spin-wait and no dependency between the waves of a launch.  Every store is an ordinary vector store.  Nothing else is defined here.
  */
 #include <hip/hip_runtime.h>
@@ -32,6 +36,7 @@ static __device__ IdrPic idr_pic(const IdrJobs &J, int i, int place)
     P.mb_w = F.mb_w; P.mb_h = J.n_mb / F.mb_w; P.qp = J.qp; P.qpc = J.qpc_of[12 + off]; P.dz = J.dz;
     P.nz = J.nz + (size_t)place * IDR_NZ_BYTES * J.n_mb; P.slots = J.slots + (size_t)place * IDR_SLOT_DWORDS * J.n_mb; P.bits = J.bits + (size_t)place * J.n_mb;
     P.clamped = nullptr;
+    P.slice_rows = J.slice_rows;
     return P;
 }
 
@@ -81,6 +86,118 @@ static __global__ void __launch_bounds__(256) k_idr_pack(const IdrJobs J, int g0
     const long long k = (long long)blockIdx.x * 256 + threadIdx.x, dwords = (idr_rbsp_bytes(pre[n_mb]) + 3) >> 2;
     if (k >= dwords || k >= J.rbsp_stride / 4) return;
     ((uint32_t *)(J.rbsp + (long long)blockIdx.y * J.rbsp_stride))[k] = idr_pack_dword(k, J.hdr, J.hdr_bits, pre, P.slots, n_mb);
+}
+
+/* ---- several slices per picture (J.n_slices = S > 1; the layout: pcamv_idr_defs.h).  A place's prefix array has J.n_mb + S entries.
+ * The prefix restarts at every slice behind that slice's header: the block's scan gives every macroblock the bits of all before it in
+ * the picture, written first where the macroblock's entry lies; every slice then takes the value at its first macroblock (kept in the
+ * place's uoff, which k_idr_place fills only later) and writes its stop bit's entry, which is no macroblock's; then every thread turns
+ * its own entries into the slice's.  A thread's run may hold a slice boundary: the slice is found per macroblock. */
+static __global__ void __launch_bounds__(IDR_PREFIX_THREADS) k_idr_prefix_slices(const IdrJobs J, int g0)
+{
+    __shared__ long long s_sum[IDR_PREFIX_THREADS];
+    __shared__ int s_bad;
+    const int i = g0 + blockIdx.x, t = threadIdx.x, S = J.n_slices;
+    const IdrPic P = idr_pic(J, i, blockIdx.x);
+    const int n_mb = P.mb_w * P.mb_h, run = (n_mb + IDR_PREFIX_THREADS - 1) / IDR_PREFIX_THREADS;
+    const int lo = t * run < n_mb ? t * run : n_mb, hi = lo + run < n_mb ? lo + run : n_mb;
+    long long *pre = J.pre + (long long)blockIdx.x * (J.n_mb + S), *base = J.uoff + (long long)blockIdx.x * S;
+    if (t == 0) s_bad = 0;
+    __syncthreads();
+    long long sum = 0;
+    int bad = 0;
+    for (int k = lo; k < hi; k++) { const int b = P.bits[k]; if (b < 0) bad = 1; else sum += b; }
+    if (bad) s_bad = 1;
+    s_sum[t] = sum;
+    __syncthreads();
+    for (int step = 1; step < IDR_PREFIX_THREADS; step <<= 1) {
+        const long long v = t >= step ? s_sum[t - step] : 0;
+        __syncthreads();
+        s_sum[t] += v;
+        __syncthreads();
+    }
+    const long long total = s_sum[IDR_PREFIX_THREADS - 1];
+    long long at = s_sum[t] - sum;
+    for (int k = lo; k < hi; k++) {
+        pre[k + idr_slice_of_row(P.mb_h, P.slice_rows, k / P.mb_w)] = at;
+        const int b = P.bits[k]; at += b < 0 ? 0 : b;
+    }
+    __syncthreads();
+    for (int s = t; s < S; s += IDR_PREFIX_THREADS) {
+        const long long f = idr_slice_first_mb(P.mb_w, P.mb_h, P.slice_rows, s), n = idr_slice_n_mb(P.mb_w, P.mb_h, P.slice_rows, s);
+        const long long first = pre[idr_slice_pre_at(f, s)], next = s + 1 < S ? pre[idr_slice_pre_at(f + n, s + 1)] : total;
+        base[s] = first;
+        pre[idr_slice_pre_at(f, s) + n] = J.shdr[s].bits + next - first;
+    }
+    __syncthreads();
+    for (int k = lo; k < hi; k++) {
+        const int s = idr_slice_of_row(P.mb_h, P.slice_rows, k / P.mb_w);
+        pre[k + s] += J.shdr[s].bits - base[s];
+    }
+    if (t == 0) J.bad[i] = s_bad;
+}
+
+/* blockIdx.y + q0 = place * S + slice; one lane per destination dword of that slice's RBSP */
+static __global__ void __launch_bounds__(256) k_idr_pack_slices(const IdrJobs J, int g0, int q0)
+{
+    const int S = J.n_slices, q = q0 + (int)blockIdx.y, place = q / S, s = q - place * S;
+    const IdrPic P = idr_pic(J, g0 + place, place);
+    const long long f = idr_slice_first_mb(P.mb_w, P.mb_h, P.slice_rows, s), n = idr_slice_n_mb(P.mb_w, P.mb_h, P.slice_rows, s);
+    const long long *pre = J.pre + (long long)place * (J.n_mb + S) + idr_slice_pre_at(f, s);
+    const long long k = (long long)blockIdx.x * 256 + threadIdx.x, dwords = (idr_rbsp_bytes(pre[n]) + 3) >> 2;
+    const long long at = idr_slice_rbsp_at(f, s), room = (idr_slice_rbsp_at(f + n, s + 1) - at) / 4;
+    if (k >= dwords || k >= room) return;
+    ((uint32_t *)(J.rbsp + (long long)place * J.rbsp_stride + at))[k] = idr_pack_dword(k, J.shdr[s].hdr, J.shdr[s].bits, pre, P.slots + (size_t)f * IDR_SLOT_DWORDS, (int)n);
+}
+
+/* one wavefront per (place, slice): the length its unit will have, by the writer's own walk with every store suppressed */
+static __global__ void __launch_bounds__(64) k_idr_unit_len(const IdrJobs J, int g0)
+{
+    __shared__ uint32_t s_win[64], s_obuf[SW_OBUF / 4];
+    const int S = J.n_slices, place = (int)(blockIdx.x / (unsigned)S), s = (int)blockIdx.x - place * S, i = g0 + place;
+    const IdrPic P = idr_pic(J, i, place);
+    const long long f = idr_slice_first_mb(P.mb_w, P.mb_h, P.slice_rows, s), n = idr_slice_n_mb(P.mb_w, P.mb_h, P.slice_rows, s);
+    const long long *pre = J.pre + (long long)place * (J.n_mb + S) + idr_slice_pre_at(f, s);
+    const long long at = idr_slice_rbsp_at(f, s), rbsp_len = idr_rbsp_bytes(pre[n]);
+    long long len = -1;
+    IdrOut O;
+    O.obuf = s_obuf;
+    if (!J.bad[i] && rbsp_len >= 0 && at + ((rbsp_len + 3) & ~3LL) <= idr_slice_rbsp_at(f + n, s + 1))
+        idr_unit_walk(O, s_win, J.rbsp + (long long)place * J.rbsp_stride + at, rbsp_len, J.nal_byte, J.as_nal, J.bytes, 0, 1, &len);
+    if (threadIdx.x == 0) J.ulen[(long long)place * S + s] = len;
+}
+
+/* one lane per context: where its S units go, or that they do not fit -- all of them or none */
+static __global__ void __launch_bounds__(64) k_idr_place(const IdrJobs J, int g0, int g)
+{
+    const int place = blockIdx.x * 64 + threadIdx.x, i = g0 + place, S = J.n_slices;
+    if (place >= g) return;
+    const long long off = J.off[i], cap = J.cap[i];
+    long long total = 0;
+    int rc = PCAMV_EINVAL;
+    if (off >= 0 && cap >= 0 && cap <= J.bytes_size && off <= J.bytes_size - cap && !J.bad[i])
+        rc = idr_place(J.ulen + (long long)place * S, J.uoff + (long long)place * S, S, cap, &total);
+    J.status[i] = rc; J.len[i] = rc ? 0 : total;
+    if (!rc && J.units) J.units[i].units += S - 1;      /* (k_stream_commit behind this call counts one unit for a picture that is there) */
+}
+
+/* one wavefront per (place, slice), writing at the place k_idr_place gave it, into exactly the bytes k_idr_unit_len counted: units that
+ * are neighbours share a dword, and sw_flush stores the bytes of a dword that is not wholly inside [dst, dst + cap) one by one */
+static __global__ void __launch_bounds__(64) k_idr_unit_slices(const IdrJobs J, int g0)
+{
+    __shared__ uint32_t s_win[64], s_obuf[SW_OBUF / 4];
+    const int S = J.n_slices, place = (int)(blockIdx.x / (unsigned)S), s = (int)blockIdx.x - place * S, i = g0 + place;
+    if (J.status[i]) return;
+    const IdrPic P = idr_pic(J, i, place);
+    const long long f = idr_slice_first_mb(P.mb_w, P.mb_h, P.slice_rows, s), n = idr_slice_n_mb(P.mb_w, P.mb_h, P.slice_rows, s);
+    const long long *pre = J.pre + (long long)place * (J.n_mb + S) + idr_slice_pre_at(f, s);
+    const long long at = idr_slice_rbsp_at(f, s), rbsp_len = idr_rbsp_bytes(pre[n]);
+    const long long uoff = J.uoff[(long long)place * S + s], ulen = J.ulen[(long long)place * S + s];
+    long long len = 0;
+    IdrOut O;
+    O.obuf = s_obuf;
+    if (uoff < 0 || ulen < 0 || uoff > J.cap[i] - ulen) return;         /* (k_idr_place's sum is within the capacity, which it judged) */
+    idr_unit(O, s_win, J.rbsp + (long long)place * J.rbsp_stride + at, rbsp_len, J.nal_byte, J.as_nal, J.bytes + J.off[i] + uoff, ulen, &len);
 }
 
 /* the sibling of k_stream_slot for a picture whose unit is made here: the delimiter and the unit succeed or fail together */
@@ -158,6 +275,18 @@ void pcamv_launch_idr_pack(const IdrJobs &J, int g0, int g, hipStream_t st)
     hipLaunchKernelGGL(k_idr_pack, dim3((unsigned)((dwords + 255) / 256), (unsigned)g), dim3(256), 0, st, J, g0);
 }
 void pcamv_launch_idr_unit(const IdrJobs &J, int g0, int g, hipStream_t st) { hipLaunchKernelGGL(k_idr_unit, dim3((unsigned)g), dim3(64), 0, st, J, g0); }
+/* the same four stages of a picture of several slices (J.n_slices > 1) */
+void pcamv_launch_idr_prefix_slices(const IdrJobs &J, int g0, int g, hipStream_t st) { hipLaunchKernelGGL(k_idr_prefix_slices, dim3((unsigned)g), dim3(IDR_PREFIX_THREADS), 0, st, J, g0); }
+void pcamv_launch_idr_pack_slices(const IdrJobs &J, int g0, int g, int mb_w, int mb_h, hipStream_t st)
+{
+    /* the longest slice is the first; its room in dwords bounds every slice's */
+    const long long dwords = idr_slice_rbsp_at(idr_slice_n_mb(mb_w, mb_h, J.slice_rows, 0), 1) / 4, total = (long long)g * J.n_slices;
+    for (long long q0 = 0; q0 < total; q0 += 65535)     /* (a grid's second dimension) */
+        hipLaunchKernelGGL(k_idr_pack_slices, dim3((unsigned)((dwords + 255) / 256), (unsigned)(total - q0 < 65535 ? total - q0 : 65535)), dim3(256), 0, st, J, g0, (int)q0);
+}
+void pcamv_launch_idr_unit_len(const IdrJobs &J, int g0, int g, hipStream_t st) { hipLaunchKernelGGL(k_idr_unit_len, dim3((unsigned)g * (unsigned)J.n_slices), dim3(64), 0, st, J, g0); }
+void pcamv_launch_idr_place(const IdrJobs &J, int g0, int g, hipStream_t st) { hipLaunchKernelGGL(k_idr_place, dim3((unsigned)((g + 63) / 64)), dim3(64), 0, st, J, g0, g); }
+void pcamv_launch_idr_unit_slices(const IdrJobs &J, int g0, int g, hipStream_t st) { hipLaunchKernelGGL(k_idr_unit_slices, dim3((unsigned)g * (unsigned)J.n_slices), dim3(64), 0, st, J, g0); }
 void pcamv_launch_idr_slot(const IdrJobs &J, const void *sws_ctx, int n, hipStream_t st)
 {
     hipLaunchKernelGGL(k_idr_slot, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, J, (const SwsCtx *)sws_ctx, n);

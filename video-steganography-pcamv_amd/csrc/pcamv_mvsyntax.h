@@ -756,10 +756,14 @@ extern "C" int pcamv_gpu_parse_slice_header(const uint8_t *rbsp, size_t len, int
  * pcamv_idr_header_parse2 (idc_out given) reads the same header whether or not the picture is filtered: disable_deblocking_filter_idc 0, 1
  * or 2 goes to *idc_out (with one slice per picture 2 filters as 0 does), an idc that is not 1 is followed by the two offsets, either of
  * which non-zero is PCAMV_EUNSUP (the filter here has FilterOffsetA = FilterOffsetB = 0) and outside -6 .. 6 PCAMV_EINVAL; without
- * deblocking control in the PPS nothing is read and the idc is 0 (7.4.3).  Everything before that point is judged as above. */
+ * deblocking control in the PPS nothing is read and the idc is 0 (7.4.3).  Everything before that point is judged as above.
+ *
+ * first_mb_out given (pcamv_gpu_parse_idr_slice_header3): first_mb_in_slice is read and handed out, up to 2^20 - 1 (above: PCAMV_EINVAL),
+ * and not refused; everything else as with idc_out. */
 static int pcamv_idr_header_parse2(const uint8_t *rbsp, size_t len, int nal_header, const pcamv_stream_params_t *params, int64_t *start_bit,
-                                   int32_t *slice_qp, int32_t *idr_pic_id, int32_t *idc_out)
+                                   int32_t *slice_qp, int32_t *idr_pic_id, int32_t *idc_out, int64_t *first_mb_out = NULL)
 {
+    if (first_mb_out) *first_mb_out = -1;
     if (start_bit) *start_bit = -1;
     if (slice_qp) *slice_qp = -1;
     if (idr_pic_id) *idr_pic_id = -1;
@@ -769,8 +773,9 @@ static int pcamv_idr_header_parse2(const uint8_t *rbsp, size_t len, int nal_head
     const pcamv_stream_params_t &P = *params;
     mvsyntax::HdrBits b = {rbsp, (uint64_t)len * 8, 0, 0};
 #define HDR_EOF() do { if (b.bad) return PCAMV_EINVAL; } while (0)
-    if (b.ue() != 0) { HDR_EOF(); return PCAMV_EUNSUP; }
-    HDR_EOF();
+    const uint64_t first_mb = b.ue(); HDR_EOF();
+    if (first_mb != 0 && !first_mb_out) return PCAMV_EUNSUP;
+    if (first_mb > (1u << 20) - 1) return PCAMV_EINVAL;
     const uint64_t slice_type = b.ue(); HDR_EOF();
     if (slice_type != 2 && slice_type != 7) return PCAMV_EUNSUP;
     const uint64_t pps_id = b.ue(); HDR_EOF();
@@ -812,6 +817,7 @@ static int pcamv_idr_header_parse2(const uint8_t *rbsp, size_t len, int nal_head
     if (b.pos >= b.nbits) return PCAMV_EINVAL;
     *start_bit = (int64_t)b.pos; *slice_qp = (int32_t)qp; *idr_pic_id = (int32_t)id;
     if (idc_out) *idc_out = (int32_t)idc;
+    if (first_mb_out) *first_mb_out = (int64_t)first_mb;
     return 0;
 }
 extern "C" int pcamv_gpu_parse_idr_slice_header(const uint8_t *rbsp, size_t len, int nal_header, const pcamv_stream_params_t *params, int64_t *start_bit,
@@ -829,6 +835,19 @@ extern "C" int pcamv_gpu_parse_idr_slice_header2(const uint8_t *rbsp, size_t len
         return PCAMV_EINVAL;
     }
     return pcamv_idr_header_parse2(rbsp, len, nal_header, params, start_bit, slice_qp, idr_pic_id, disable_deblocking_filter_idc);
+}
+extern "C" int pcamv_gpu_parse_idr_slice_header3(const uint8_t *rbsp, size_t len, int nal_header, const pcamv_stream_params_t *params, int64_t *start_bit,
+                                                 int32_t *slice_qp, int32_t *idr_pic_id, int32_t *disable_deblocking_filter_idc, int64_t *first_mb)
+{
+    if (!disable_deblocking_filter_idc || !first_mb) {
+        if (start_bit) *start_bit = -1;
+        if (slice_qp) *slice_qp = -1;
+        if (idr_pic_id) *idr_pic_id = -1;
+        if (disable_deblocking_filter_idc) *disable_deblocking_filter_idc = -1;
+        if (first_mb) *first_mb = -1;
+        return PCAMV_EINVAL;
+    }
+    return pcamv_idr_header_parse2(rbsp, len, nal_header, params, start_bit, slice_qp, idr_pic_id, disable_deblocking_filter_idc, first_mb);
 }
 
 namespace mvsyntax {
@@ -1143,6 +1162,67 @@ extern "C" int pcamv_gpu_deblock_intra_picture(uint8_t *y, uint8_t *u, uint8_t *
                             Cq.line(q, dir == 0 ? 1 : cw, bs, true);
                         }
                 }
+    return 0;
+}
+/* ---------------------------------------------------------------- an IDR picture of one or several slices: the definition
+ * bytes[0, len): Annex B.  Every unit of type 5 is a slice of the picture, in the order of the bytes; units that are no VCL units
+ * (delimiters, parameter sets, SEI) are passed over; a VCL unit of another type is PCAMV_EUNSUP.  Each slice's header is read by
+ * pcamv_gpu_parse_idr_slice_header3 under params; the slices must be whole macroblock rows (first_mb a multiple of mb_w), in order, behind
+ * each other without gap or overlap, the first at 0 and the last up to the picture's end, and agree in QP, idr_pic_id and idc: else
+ * PCAMV_EUNSUP (no slice at all: PCAMV_EINVAL).  A slice that begins at row r ends where the next begins; it is decoded by
+ * pcamv_gpu_decode_islice_cavlc as a picture of its own rows -- for whole-row slices exactly the availability of 7.4.1.2.1 and 9.2.1:
+ * nothing above the slice's first row -- into the picture's planes; unless the idc is 1, the whole picture then goes through
+ * pcamv_gpu_deblock_intra_picture (idc 0: slice edges are filtered as any macroblock edge; idc 2 is PCAMV_EUNSUP for more than one slice). */
+extern "C" int pcamv_gpu_decode_idr_picture(const uint8_t *bytes, size_t len, int mb_w, int mb_h, const pcamv_stream_params_t *params, int chroma_qp_index_offset,
+                                            uint8_t *y, uint8_t *u, uint8_t *v, int32_t *slice_qp, int32_t *idr_pic_id, int32_t *n_slices)
+{
+    if (slice_qp) *slice_qp = -1;
+    if (idr_pic_id) *idr_pic_id = -1;
+    if (n_slices) *n_slices = 0;
+    if (!bytes || !y || !u || !v || !slice_qp || !idr_pic_id || !n_slices || !pcamv_stream_params_ok(params) || len < 1 || len > ((size_t)1 << 31) || mb_w < 1 ||
+        mb_h < 1 || mb_w > (1 << 16) || mb_h > (1 << 16) || (long long)mb_w * mb_h > (1 << 20)) return PCAMV_EINVAL;
+    int64_t nu = 0, ns = 0;
+    pcamv_gpu_annexb_index(bytes, len, NULL, 0, &nu, &ns);
+    pcamv_unit_t *units = (pcamv_unit_t *)malloc((size_t)(nu ? nu : 1) * sizeof(pcamv_unit_t));
+    uint8_t *rbsp = (uint8_t *)malloc(len);
+    struct Sl { size_t unit; int64_t start_bit, first_mb; } *sl = (Sl *)malloc((size_t)(nu ? nu : 1) * sizeof(Sl));
+    int rc = units && rbsp && sl ? 0 : PCAMV_ENOMEM;
+    int n = 0, qp = -1, id = -1, idc = -1;
+    if (!rc) pcamv_gpu_annexb_index(bytes, len, units, (size_t)nu, &nu, &ns);
+    /* the headers: every slice judged before any is decoded */
+    for (int64_t k = 0; !rc && k < nu; k++) {
+        const int type = units[k].nal_header < 0 ? 0 : units[k].nal_header & 31;
+        if (type < 1 || type > 5) continue;
+        if (type != 5) { rc = PCAMV_EUNSUP; break; }
+        size_t rl = 0;
+        rc = pcamv_gpu_nal_to_rbsp(bytes + units[k].off, (size_t)units[k].len, rbsp, &rl, NULL, NULL);
+        if (rc) break;
+        int32_t q = -1, pid = -1, dc = -1;
+        Sl e = {(size_t)k, -1, -1};
+        rc = pcamv_gpu_parse_idr_slice_header3(rbsp, rl, units[k].nal_header, params, &e.start_bit, &q, &pid, &dc, &e.first_mb);
+        if (rc) break;
+        if (n && (q != qp || pid != id || dc != idc)) { rc = PCAMV_EUNSUP; break; }
+        if (e.first_mb % mb_w || e.first_mb >= (int64_t)mb_w * mb_h || (n ? e.first_mb <= sl[n - 1].first_mb : e.first_mb != 0)) { rc = PCAMV_EUNSUP; break; }
+        qp = q; id = pid; idc = dc;
+        sl[n++] = e;
+    }
+    if (!rc && !n) rc = PCAMV_EINVAL;
+    if (!rc && n > 1 && idc == 2) rc = PCAMV_EUNSUP;
+    const size_t lw = (size_t)16 * mb_w, cw = (size_t)8 * mb_w;
+    for (int k = 0; !rc && k < n; k++) {
+        const int r0 = (int)(sl[k].first_mb / mb_w), r1 = k + 1 < n ? (int)(sl[k + 1].first_mb / mb_w) : mb_h;
+        size_t rl = 0;
+        rc = pcamv_gpu_nal_to_rbsp(bytes + units[sl[k].unit].off, (size_t)units[sl[k].unit].len, rbsp, &rl, NULL, NULL);
+        /* rows r0 .. r1 - 1 as a picture of their own: tightly packed planes of the same width are those rows of the picture's planes; a
+         * slice that holds more or fewer macroblocks than its rows fails the decoder's end-of-slice rule, which is how overlap and gap show */
+        if (!rc) rc = pcamv_gpu_decode_islice_cavlc(rbsp, rl, (size_t)sl[k].start_bit, mb_w, r1 - r0, qp, chroma_qp_index_offset,
+                                                    y + (size_t)16 * r0 * lw, u + (size_t)8 * r0 * cw, v + (size_t)8 * r0 * cw);
+        if (rc == PCAMV_EINVAL) rc = PCAMV_EUNSUP;             /* (the slices do not cover the picture as their first_mb says) */
+    }
+    if (!rc && idc != 1) rc = pcamv_gpu_deblock_intra_picture(y, u, v, mb_w, mb_h, qp, chroma_qp_index_offset);
+    free(units); free(rbsp); free(sl);
+    if (rc) return rc;
+    *slice_qp = qp; *idr_pic_id = id; *n_slices = n;
     return 0;
 }
 #endif

@@ -629,13 +629,24 @@ IDR_PROBE_PARAMS = dict(log2_max_frame_num=4, poc_type=0, log2_max_poc_lsb=4, nu
 FEATURE_IDR_DEBLOCK = 0x2000    # ... and filtered there: the deblock keyword of the same calls, deblock_intra_picture, parse_idr_slice_header2
 
 
-def write_idr_slice_header(params, nal_ref_idc, idr_pic_id, slice_qp, deblock=False):
+FEATURE_IDR_SLICES = 0x4000     # ... in several slices of whole macroblock rows: the slice_rows keyword of the same calls, decode_idr_picture, parse_idr_slice_header3
+
+
+def write_idr_slice_header(params, nal_ref_idc, idr_pic_id, slice_qp, deblock=False, first_mb=0):
     """pcamv_gpu_write_idr_slice_header: (packed bytes, number of bits) of the header of an IDR I slice for a StreamParams -- which must
     say entropy_cabac 0 and deblocking_filter_control_present 1.  Raises PcamvError with the library's code (-1: a value out of range,
     -5: weighted prediction, CABAC, or no deblocking control).  deblock (pcamv_gpu_write_idr_slice_header2): the header of a filtered
-    picture -- idc 0 and two offsets of 0, or nothing at all under a StreamParams without deblocking control, which is then not refused"""
+    picture -- idc 0 and two offsets of 0, or nothing at all under a StreamParams without deblocking control, which is then not refused.
+    first_mb (pcamv_gpu_write_idr_slice_header3): first_mb_in_slice, 0 .. 2**20 - 1 -- the header of a later slice of the picture"""
     out = np.zeros(IDR_HDR_BYTES, np.uint8)
     n = C.c_int32()
+    if first_mb:
+        fn = load_library().pcamv_gpu_write_idr_slice_header3
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32)]
+        rc = fn(C.byref(params), int(nal_ref_idc), int(idr_pic_id), int(slice_qp), int(deblock), int(first_mb), _p(out), len(out), C.byref(n))
+        if rc:
+            raise PcamvError(f"pcamv_gpu_write_idr_slice_header3 failed: {rc}")
+        return bytes(out[:(n.value + 7) // 8]), n.value
     if deblock:
         fn = load_library().pcamv_gpu_write_idr_slice_header2
         fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32)]
@@ -669,6 +680,36 @@ def parse_idr_slice_header2(rbsp, nal_header, params):
     fn.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     rc = fn(_p(buf), len(rbsp), int(nal_header), C.byref(params), C.byref(sb), C.byref(qp), C.byref(pid), C.byref(idc))
     return rc, sb.value, qp.value, pid.value, idc.value
+
+
+def parse_idr_slice_header3(rbsp, nal_header, params):
+    """pcamv_gpu_parse_idr_slice_header3: (return code, start_bit, slice QP, idr_pic_id, disable_deblocking_filter_idc, first_mb_in_slice)
+    of the header of an IDR I slice, the first of its picture or a later one; the last five are -1 when the code is not 0"""
+    buf = np.frombuffer(bytes(rbsp), np.uint8) if len(rbsp) else np.zeros(1, np.uint8)
+    sb, qp, pid, idc, first = C.c_int64(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+    fn = load_library().pcamv_gpu_parse_idr_slice_header3
+    fn.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+    rc = fn(_p(buf), len(rbsp), int(nal_header), C.byref(params), C.byref(sb), C.byref(qp), C.byref(pid), C.byref(idc), C.byref(first))
+    return rc, sb.value, qp.value, pid.value, idc.value, first.value
+
+
+def decode_idr_picture(data, mb_w, mb_h, params=None, chroma_qp_index_offset=0):
+    """pcamv_gpu_decode_idr_picture: (return code, (Y, U, V), slice QP, idr_pic_id, number of slices) of the IDR picture whose slices are
+    the type-5 units of the Annex B bytes `data`, one or several of whole macroblock rows, as the library's host decoder reconstructs it
+    (filtered unless the slices say idc 1).  params: the StreamParams of the PPS the slices name (default: those Encoder.encode_idr
+    writes under, pps_id 1).  The planes are None and the numbers -1 / 0 when the code is not 0 (-5: slices that are no whole rows, out
+    of order, overlapping, not covering the picture or disagreeing, or another VCL unit among them)"""
+    if params is None:
+        params = StreamParams(**dict(IDR_PROBE_PARAMS, pps_id=1))
+    buf = np.frombuffer(bytes(data), np.uint8) if len(data) else np.zeros(1, np.uint8)
+    w, h = 16 * int(mb_w), 16 * int(mb_h)
+    planes = [np.zeros(s, np.uint8) for s in ((h, w), (h // 2, w // 2), (h // 2, w // 2))] if 0 < mb_w <= 65536 and 0 < mb_h <= 65536 and mb_w * mb_h <= 1 << 20 else \
+             [np.zeros((1, 1), np.uint8)] * 3
+    qp, pid, ns = C.c_int32(), C.c_int32(), C.c_int32()
+    fn = load_library().pcamv_gpu_decode_idr_picture
+    fn.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    rc = fn(_p(buf), len(data), int(mb_w), int(mb_h), C.byref(params), int(chroma_qp_index_offset), *[_p(p) for p in planes], C.byref(qp), C.byref(pid), C.byref(ns))
+    return rc, (tuple(planes) if rc == 0 else None), qp.value, pid.value, ns.value
 
 
 def deblock_intra_picture(planes, qp, chroma_qp_index_offset=0):
@@ -1101,8 +1142,16 @@ class Encoder:
         self._chk(fn(self.ctx, ps, fs, n, _p(rc), _p(nb), _p(bits)), "slice_headers_write_device")
         return rc, nb, bits
 
-    def idr_bound(self, as_nal=True):
-        """pcamv_gpu_idr_bound: a capacity under which no IDR picture of this size fails to be written"""
+    def idr_bound(self, as_nal=True, slice_rows=0):
+        """pcamv_gpu_idr_bound: a capacity under which no IDR picture of this size fails to be written; slice_rows
+        (pcamv_gpu_idr_bound3): ... in slices of that many macroblock rows"""
+        if slice_rows:
+            self.lib.pcamv_gpu_idr_bound3.restype = C.c_int64
+            self.lib.pcamv_gpu_idr_bound3.argtypes = [C.c_void_p, C.c_int, C.c_int]
+            n = self.lib.pcamv_gpu_idr_bound3(self.ctx, int(bool(as_nal)), int(slice_rows))
+            if n < 0:
+                raise PcamvError(f"idr_bound3 failed ({n})")
+            return int(n)
         self.lib.pcamv_gpu_idr_bound.restype = C.c_int64
         self.lib.pcamv_gpu_idr_bound.argtypes = [C.c_void_p, C.c_int]
         n = self.lib.pcamv_gpu_idr_bound(self.ctx, int(bool(as_nal)))
@@ -1110,17 +1159,24 @@ class Encoder:
             raise PcamvError(f"idr_bound failed ({n})")
         return int(n)
 
-    def encode_idr(self, qp, pps_id=1, idr_pic_id=0, as_nal=True, cap=None, deblock=False):
+    def encode_idr(self, qp, pps_id=1, idr_pic_id=0, as_nal=True, cap=None, deblock=False, slice_rows=0):
         """pcamv_gpu_encode_idr: this context's current source coded on the device as one IDR I slice (Intra16x16, CAVLC, no loop filter),
         as bytes -- the unit with start code and emulation prevention, or with as_nal=False the RBSP.  The unfiltered reconstruction
         becomes the context's reference as after a host set_ref with no previous motion (fetch_recon, ref_planes show it).  The header
         is written under StreamParams(**IDR_PROBE_PARAMS, pps_id=pps_id) with nal_ref_idc 3.  cap: the capacity offered (default:
         idr_bound); a unit that does not fit raises (-3).  deblock (pcamv_gpu_encode_idr2): the picture is filtered
-        (deblock_intra_picture) before it becomes the reference, and its header says so; the slice data is the same"""
+        (deblock_intra_picture) before it becomes the reference, and its header says so; the slice data is the same.  slice_rows
+        (pcamv_gpu_encode_idr3): the picture in slices of that many macroblock rows, their units behind each other (as_nal only);
+        0, or the picture's rows and more: one slice"""
         if cap is None:
-            cap = self.idr_bound(as_nal)
+            cap = self.idr_bound(as_nal, max(int(slice_rows), 0))
         out = np.zeros(max(int(cap), 1), np.uint8)
         n = C.c_size_t()
+        if slice_rows:
+            fn = self.lib.pcamv_gpu_encode_idr3
+            fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+            self._chk(fn(self.ctx, int(qp), int(pps_id), int(idr_pic_id), int(bool(as_nal)), int(deblock), int(slice_rows), _p(out), int(cap), C.byref(n)), "encode_idr3")
+            return bytes(out[:n.value])
         if deblock:
             fn = self.lib.pcamv_gpu_encode_idr2
             fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
@@ -1630,13 +1686,20 @@ class Batch:
         fn.argtypes = [C.c_void_p, C.c_void_p]
         self._slice_chk(fn(self.b, C.c_void_p(stream or None)), "batch_write_stream_step")
 
-    def write_stream_idr(self, qp, pps_id=1, idr_pic_id=0, stream=0, deblock=False):
+    def write_stream_idr(self, qp, pps_id=1, idr_pic_id=0, stream=0, deblock=False, slice_rows=0):
         """pcamv_gpu_batch_write_stream_idr: every context's current source coded on the device as the IDR picture of its stream --
         picture 0, behind the head and before the first write_stream_step since the open, which must have first_pic 0 -- and its
         unfiltered reconstruction installed as the context's reference.  The IDR slices name the PPS pps_id, which the head must hold
         with entropy_cabac 0 and deblocking control (param_set_head_idr).  No host sync; write_status() afterwards as for a step.
         deblock (pcamv_gpu_batch_write_stream_idr2): every picture is filtered on the device (k_idr_deblock) before it becomes the
-        reference, as the P pictures behind it are; that PPS then needs no deblocking control"""
+        reference, as the P pictures behind it are; that PPS then needs no deblocking control.  slice_rows
+        (pcamv_gpu_batch_write_stream_idr3): every picture in slices of that many macroblock rows, their units back to back behind one
+        delimiter; stream_written()'s unit counter moves by their number"""
+        if slice_rows:
+            fn = self.lib.pcamv_gpu_batch_write_stream_idr3
+            fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+            self._slice_chk(fn(self.b, int(qp), int(pps_id), int(idr_pic_id), int(deblock), int(slice_rows), C.c_void_p(stream or None)), "batch_write_stream_idr3")
+            return
         if deblock:
             fn = self.lib.pcamv_gpu_batch_write_stream_idr2
             fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
