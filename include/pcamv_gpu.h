@@ -318,7 +318,9 @@ int  pcamv_gpu_batch_kernel_time(pcamv_batch_t *batch, const char *kernel, doubl
  * times.  (Listed here and not above: tests/test_gpu_batch_memory.py counts the 40 of the list above.)
  * With PCAMV_FEATURE_IDR_SLICES, the 42nd and 43rd: "k_idr_unit_len", one wavefront per (context, slice) counting its unit's bytes, and
  * "k_idr_place", one lane per context placing its units; both are launched only for pictures of more than one slice, for which
- * "k_idr_prefix", "k_idr_pack" and "k_idr_unit" time the kernels that work per slice. */
+ * "k_idr_prefix", "k_idr_pack" and "k_idr_unit" time the kernels that work per slice.
+ * With PCAMV_FEATURE_IDR_I4X4, the 44th: "k_idr_mb4", which stands in k_idr_mb's place in a call with i4x4 != 0 -- its average is per
+ * launch, and such a call launches it once per anti-diagonal x + 2 y of the picture. */
 const char *pcamv_gpu_batch_last_error(const pcamv_batch_t *batch);
 /* Closed loop on the device: with on != 0 every batch step ends with pass 2 + the loop filter (embedding must be
  * on: the flip map comes from it), leaving each context's deblocked reconstruction in its device planes
@@ -397,6 +399,7 @@ int pcamv_gpu_abi_version(void);
 #define PCAMV_FEATURE_IDR 0x1000u       /* the IDR picture a chain starts with coded on the device (the last section of this file) */
 #define PCAMV_FEATURE_IDR_DEBLOCK 0x2000u       /* ... and filtered there, as the stream's P pictures are (the *2 calls of that section) */
 #define PCAMV_FEATURE_IDR_SLICES 0x4000u        /* ... in several slices of whole macroblock rows, a wavefront per slice (the *3 calls of that section) */
+#define PCAMV_FEATURE_IDR_I4X4 0x8000u          /* ... with Intra4x4 macroblocks beside the Intra16x16 ones (the *4 calls of that section, the decoders that end in 2) */
 unsigned pcamv_gpu_features(void);
 
 /* ---- Payload path: the caller's bits through the device-resident entry points, and back out on the device ----
@@ -1068,7 +1071,32 @@ int pcamv_gpu_video_gops_device(pcamv_ctx_t *ctx, const uint8_t *bytes, size_t b
  * suppressed; k_idr_place, one lane per context, places the units or refuses them all; k_idr_unit, one wavefront per (context, slice),
  * writes at its place -- units that are neighbours share a dword, and no dword store covers a byte outside the unit's own.  With S = 1
  * there is no length pass.  Working memory: 2842 bytes per macroblock and place as before, and 64 S per place (a prefix entry, a header's
- * room in the RBSP, a unit's length and offset); the 8 GiB cap and the groups stand. */
+ * room in the RBSP, a unit's length and offset); the 8 GiB cap and the groups stand.
+ *
+ * Intra4x4 macroblocks (PCAMV_FEATURE_IDR_I4X4): the calls that end in 4 take `i4x4` -- 0: every macroblock Intra16x16, and the call IS its
+ * *3 sibling, byte for byte and launch for launch; 1: per macroblock Intra4x4 where it costs less; 2: every macroblock Intra4x4 (a probe
+ * setting, and the smallest pictures on noisy content); anything else PCAMV_EINVAL before anything is queued.  The rule (the coder's own,
+ * not the reference's; csrc/pcamv_idr_i4x4.h): the macroblock is coded as before, which gives cost16, the SATD of the winning Intra16x16
+ * mode; then the sixteen 4x4 blocks in luma4x4BlkIdx order, each with the modes of 8.3.1.2 whose neighbours exist in the slice, cost
+ * SATD + lambda (1 for the predicted mode of 8.3.1.1, 4 for another), lambda the analysis' own at this QP, the lowest cost winning and
+ * ties going to the lower mode; every block transformed, quantised with the intra dead zone and the clamp of the other levels, and
+ * reconstructed before the next is predicted.  Intra4x4 iff 24 lambda + the sixteen costs < cost16.  Chroma is coded as before in
+ * both types.  An Intra4x4 macroblock is at most 11230 bits, 51 more than an Intra16x16 one, so idr_bound4 with i4x4 != 0 is larger
+ * than idr_bound3; the slot of a macroblock stays, the RBSP of a place grows by 6.4 bytes a macroblock and a place holds 16 more (the
+ * modes the neighbours read) in such calls only.  Kernel: k_idr_mb4 in k_idr_mb's place, one wavefront per macroblock, one launch per
+ * anti-diagonal x + 2 y (Intra4x4 reads the macroblock above-right); every other kernel is the same.  The loop filter is the same:
+ * with the 4x4 transform bS is 4 on macroblock edges and 3 inside for every intra macroblock.
+ * decode_islice_cavlc2 / decode_idr_picture2: `flags` bit 0 makes the host decoder accept I_NxN macroblocks (its own nine predictors,
+ * the intra column of Table 9-4, mb_qp_delta only with a pattern, nC across the macroblock types); other bits PCAMV_EINVAL; with flags 0
+ * they are the functions without the 2, which go on refusing mb_type 0 with PCAMV_EUNSUP.  With the flag: a mode whose neighbours do
+ * not exist and a pattern codeNum above 47 are PCAMV_EINVAL, mb_qp_delta != 0 PCAMV_EUNSUP. */
+int pcamv_gpu_encode_idr4(pcamv_ctx_t *ctx, int qp, int pps_id, int idr_pic_id, int as_nal, int deblock, int slice_rows, int i4x4, uint8_t *out, size_t cap, size_t *len);
+int pcamv_gpu_batch_write_stream_idr4(pcamv_batch_t *batch, int qp, int pps_id, int idr_pic_id, int deblock, int slice_rows, int i4x4, void *stream);
+int64_t pcamv_gpu_idr_bound4(const pcamv_ctx_t *ctx, int as_nal, int slice_rows, int i4x4);
+int pcamv_gpu_decode_islice_cavlc2(const uint8_t *rbsp, size_t len, size_t start_bit, int mb_w, int mb_h, int slice_qp, int chroma_qp_index_offset, int flags,
+                                   uint8_t *y, uint8_t *u, uint8_t *v);
+int pcamv_gpu_decode_idr_picture2(const uint8_t *bytes, size_t len, int mb_w, int mb_h, const pcamv_stream_params_t *params, int chroma_qp_index_offset, int flags,
+                                  uint8_t *y, uint8_t *u, uint8_t *v, int32_t *slice_qp, int32_t *idr_pic_id, int32_t *n_slices);
 int pcamv_gpu_write_idr_slice_header3(const pcamv_stream_params_t *params, int nal_ref_idc, int idr_pic_id, int slice_qp, int deblock, int64_t first_mb, uint8_t *bits,
                                       size_t cap, int32_t *n_bits);
 int pcamv_gpu_parse_idr_slice_header3(const uint8_t *rbsp, size_t len, int nal_header, const pcamv_stream_params_t *params, int64_t *start_bit,

@@ -11,7 +11,12 @@ k_idr_deblock): the wall clock of both, k_idr_deblock over its launches next to 
 more than one slice) and the bytes of a picture -- the S - 1 further headers and what prediction loses at the slice edges show there --
 into profiles/idr_slices_timing.json.
 
-    python tools/idr_timing.py [--deblock | --slice-rows 0,1,4,17] [--gops 256] [--steps 3] [--warmup 1] [--reps 3] [--out FILE]
+--i4x4: the same chains in the same run with i4x4 0 / 1 / 2 (write_stream_idr(i4x4=...); kernel k_idr_mb4 in k_idr_mb's place), reps
+calls each after a first: per setting the wall clock, every k_idr_* timer, the bytes of a picture, and of the first --count-chains chains
+the share of Intra4x4 macroblocks (read from the stream by tests/islice4_walk.py, syntax only) and the luma SSD of the reconstruction
+against the source, into profiles/idr_i4x4_timing.json.
+
+    python tools/idr_timing.py [--deblock | --slice-rows 0,1,4,17 | --i4x4] [--gops 256] [--steps 3] [--warmup 1] [--reps 3] [--out FILE]
 """
 import argparse
 import json
@@ -22,6 +27,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "video-steganography-pcamv_amd")]
 KERNELS = ("k_idr_mb", "k_idr_prefix", "k_idr_pack", "k_idr_unit", "k_stream_commit")
+I4_KERNELS = ("k_idr_mb", "k_idr_mb4", "k_idr_prefix", "k_idr_pack", "k_idr_unit", "k_stream_commit")
 SLICE_KERNELS = ("k_idr_mb", "k_idr_prefix", "k_idr_pack", "k_idr_unit_len", "k_idr_place", "k_idr_unit", "k_stream_commit")
 
 
@@ -36,10 +42,12 @@ def main():
     ap.add_argument("--region", type=int, default=6 << 20, help="bytes of a chain's stream")
     ap.add_argument("--deblock", action="store_true", help="time the pictures without and with the loop filter")
     ap.add_argument("--slice-rows", default=None, help="comma-separated macroblock rows per slice to time, 0: one slice")
+    ap.add_argument("--i4x4", action="store_true", help="time the pictures with i4x4 0, 1 and 2")
+    ap.add_argument("--count-chains", type=int, default=1, help="--i4x4: chains whose macroblock types and luma SSD are taken")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     slice_rows = [int(v) for v in args.slice_rows.split(",")] if args.slice_rows else None
-    args.out = args.out or os.path.join(ROOT, "profiles", "idr_slices_timing.json" if slice_rows is not None else "idr_deblock_timing.json" if args.deblock else "idr_timing.json")
+    args.out = args.out or os.path.join(ROOT, "profiles", "idr_i4x4_timing.json" if args.i4x4 else "idr_slices_timing.json" if slice_rows is not None else "idr_deblock_timing.json" if args.deblock else "idr_timing.json")
     import numpy as np
     import torch
     import pcamv_amd
@@ -68,7 +76,7 @@ def main():
         enc.set_fenc_device(*[pl.data_ptr() for pl in dframes[bench.tri(run.phases[k], len(dframes))]])
     out = dict(gops=n, width=W, height=H, qp=args.qp, emrate=args.emrate, reps=args.reps, steps=args.steps)
 
-    def idr_calls(deblock, kernels, rows=0):
+    def idr_calls(deblock, kernels, rows=0, i4x4=0):
         """reps + 1 calls, the first not counted (it makes the working memory): wall clock per call, every kernel's time per call"""
         wall, res = [], {}
         for rep in range(args.reps + 1):
@@ -79,7 +87,7 @@ def main():
                 for name in kernels:
                     run.batch.kernel_time(name, reset=True)
             w0 = time.perf_counter()
-            run.batch.write_stream_idr(args.qp, pps_id=1, idr_pic_id=rep, stream=stream.cuda_stream, deblock=deblock, slice_rows=rows)
+            run.batch.write_stream_idr(args.qp, pps_id=1, idr_pic_id=rep, stream=stream.cuda_stream, deblock=deblock, slice_rows=rows, i4x4=i4x4)
             torch.cuda.synchronize()
             if rep:
                 wall.append((time.perf_counter() - w0) * 1e3)
@@ -91,6 +99,36 @@ def main():
             res[name + ("_launches_per_call" if name == "k_idr_deblock" else "_timed_spans_per_call")] = launches / max(args.reps, 1)
         return wall, res
 
+    if args.i4x4:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import islice4_walk
+        mb_w, mb_h = W // 16, H // 16
+        _, idr_sp = pcamv_amd.param_set_head_idr(sp, mb_w, mb_h, idr_pps_id=1)
+        out["i4x4"] = {}
+        for i4 in (0, 1, 2):
+            wall, res = idr_calls(False, I4_KERNELS, 0, i4)
+            lens = length.cpu().numpy()
+            nbytes = (lens - len(head) - 6).astype(np.int64)
+            n4 = n_all = ssd = 0
+            for k in range(min(args.count_chains, n)):
+                unit = data[k * args.region + len(head) + 6 + 4:k * args.region + int(lens[k])].cpu().numpy().tobytes()
+                rbsp, ref_idc, typ = pcamv_amd.nal_to_rbsp(unit)
+                rc, sb, qp, pid, idc = pcamv_amd.parse_idr_slice_header2(rbsp, unit[0], idr_sp)
+                assert rc == 0 and qp == args.qp, (rc, qp)
+                mbs = islice4_walk.decode(rbsp, sb, mb_w, mb_h, qp, reconstruct=False).mbs
+                n4 += sum(1 for mb in mbs if mb[0])
+                n_all += len(mbs)
+                src = dframes[bench.tri(run.phases[k], len(dframes))][0].cpu().numpy().astype(np.int64)
+                ssd += int(((run.encs[k].fetch_recon()[0].astype(np.int64) - src) ** 2).sum())
+            res.update(wall_ms_median=float(np.median(wall)), picture_bytes=dict(min=int(nbytes.min()), mean=float(nbytes.mean()), max=int(nbytes.max())),
+                       counted_chains=min(args.count_chains, n), intra4x4_share=n4 / max(n_all, 1), luma_ssd_per_picture=ssd / max(min(args.count_chains, n), 1))
+            out["i4x4"][str(i4)] = res
+        line = json.dumps(dict(mode="idr_i4x4", tool="idr_timing.py", **out))
+        print(line)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+        run.leave_to_exit()
+        return
     if slice_rows is not None:
         mb_h = H // 16
         out["slice_rows"] = {}

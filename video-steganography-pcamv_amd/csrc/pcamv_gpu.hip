@@ -45,14 +45,14 @@
     X(KT_VIDEO_CUT, "k_video_cut") X(KT_MESSAGE_COUNT, "k_message_count") X(KT_MESSAGE_PLAN, "k_message_plan") \
     X(KT_MESSAGE_JOBS, "k_message_jobs") X(KT_EXTRACT_CHAIN_MESSAGE, "k_extract_chain_message") X(KT_MESSAGE_CHECK, "k_message_check") \
     X(KT_IDR_MB, "k_idr_mb") X(KT_IDR_PREFIX, "k_idr_prefix") X(KT_IDR_PACK, "k_idr_pack") X(KT_IDR_UNIT, "k_idr_unit") \
-    X(KT_IDR_DEBLOCK, "k_idr_deblock") X(KT_IDR_UNIT_LEN, "k_idr_unit_len") X(KT_IDR_PLACE, "k_idr_place")
+    X(KT_IDR_DEBLOCK, "k_idr_deblock") X(KT_IDR_UNIT_LEN, "k_idr_unit_len") X(KT_IDR_PLACE, "k_idr_place") X(KT_IDR_MB4, "k_idr_mb4")
 #define KT_ENUM(id, name) id,
 enum { PCAMV_TIMERS(KT_ENUM) KT_N };
 #undef KT_ENUM
 #define PCAMV_FEATURES (PCAMV_FEATURE_PAYLOAD | PCAMV_FEATURE_SLICE_PARSER | PCAMV_FEATURE_SLICE_PARSER_CAVLC | PCAMV_FEATURE_SLICE_WRITER | \
                         PCAMV_FEATURE_SLICE_WRITER_CAVLC | PCAMV_FEATURE_NAL_DEVICE | PCAMV_FEATURE_STREAM_DEVICE | PCAMV_FEATURE_STREAM_WRITER | \
                         PCAMV_FEATURE_STREAM_WINDOW | PCAMV_FEATURE_PARAM_SETS | PCAMV_FEATURE_VIDEO | PCAMV_FEATURE_MESSAGE | PCAMV_FEATURE_IDR | \
-                        PCAMV_FEATURE_IDR_DEBLOCK | PCAMV_FEATURE_IDR_SLICES)
+                        PCAMV_FEATURE_IDR_DEBLOCK | PCAMV_FEATURE_IDR_SLICES | PCAMV_FEATURE_IDR_I4X4)
 #define MSG_GUARD_WORDS 4       /* words behind a batch's received stream that nothing may write */
 #define SLICE_GUARD_MBS 4       /* records behind a context's receive-side records that nothing may write (pcamv_gpu_debug_slice_records) */
 #define NSTAGE 2                /* staging buffers of extract_slices: a call waits for the one before the last */
@@ -2885,6 +2885,7 @@ extern "C" int pcamv_gpu_batch_write_stream_step(pcamv_batch_t *b, void *stream)
 }
 /* ------------------------------------------------------------------ IDR pictures coded on the device (k_idr_mb, k_idr_prefix, k_idr_pack, k_idr_slot, k_idr_unit; pcamv_idr.hip) */
 void pcamv_launch_idr_mb(const IdrJobs &J, int g0, int g, int mb_w, int mb_h, hipStream_t st);
+void pcamv_launch_idr_mb4(const IdrJobs &J, int g0, int g, int mb_w, int mb_h, hipStream_t st);
 void pcamv_launch_idr_prefix(const IdrJobs &J, int g0, int g, hipStream_t st);
 void pcamv_launch_idr_pack(const IdrJobs &J, int g0, int g, hipStream_t st);
 void pcamv_launch_idr_unit(const IdrJobs &J, int g0, int g, hipStream_t st);
@@ -2918,23 +2919,27 @@ extern "C" int pcamv_gpu_write_idr_slice_header(const pcamv_stream_params_t *par
     return pcamv_gpu_write_idr_slice_header2(params, nal_ref_idc, idr_pic_id, slice_qp, 0, bits, cap, n_bits);
 }
 extern "C" int64_t pcamv_gpu_idr_bound(const pcamv_ctx_t *c, int as_nal) { return c ? (int64_t)idr_bound(c->F.n_mb, as_nal) : PCAMV_EINVAL; }
-extern "C" int64_t pcamv_gpu_idr_bound3(const pcamv_ctx_t *c, int as_nal, int slice_rows)
+extern "C" int64_t pcamv_gpu_idr_bound4(const pcamv_ctx_t *c, int as_nal, int slice_rows, int i4x4)
 {
-    return c && slice_rows >= 0 ? (int64_t)idr_bound_slices(c->F.mb_w, c->F.mb_h, slice_rows, as_nal) : PCAMV_EINVAL;
+    return c && slice_rows >= 0 && i4x4 >= 0 && i4x4 <= 2 ? (int64_t)idr_bound_slices_bits(c->F.mb_w, c->F.mb_h, slice_rows, as_nal, idr_mb_bits_of(i4x4)) : PCAMV_EINVAL;
 }
+extern "C" int64_t pcamv_gpu_idr_bound3(const pcamv_ctx_t *c, int as_nal, int slice_rows) { return pcamv_gpu_idr_bound4(c, as_nal, slice_rows, 0); }
 /* the working memory of one place of a group: bytes per context.  Per macroblock 24 counts, a slot of 1408, a length of 4, a prefix
  * entry of 8 and 1397.4 of RBSP: 2842; a picture of S > 1 slices adds 64 S per place -- a prefix entry, the room of a header and its
- * paddings in the RBSP (IDR_SLICE_PAD_BYTES), a unit's length and its offset */
-static size_t idr_place_bytes(int n_mb, int n_slices, size_t *rbsp_stride)
+ * paddings in the RBSP (IDR_SLICE_PAD_BYTES), a unit's length and its offset.  A call with i4x4 != 0 adds per macroblock the 16 modes
+ * and the 6.4 bytes of RBSP an Intra4x4 macroblock may be longer by (mb_bits: IDR_MB_BITS_I4), and 256 for the modes' own rounding */
+static size_t idr_place_bytes(int n_mb, int n_slices, int i4x4, size_t *rbsp_stride)
 {
     const size_t S = (size_t)n_slices;
-    const size_t rbsp = ((size_t)(S > 1 ? idr_slice_rbsp_at(n_mb, n_slices) : idr_bound(n_mb, 0)) + 255) & ~(size_t)255;
+    const int mb_bits = idr_mb_bits_of(i4x4);
+    const size_t rbsp = ((size_t)(S > 1 ? idr_slice_rbsp_at_bits(n_mb, n_slices, mb_bits) : idr_bound_bits(n_mb, 0, mb_bits)) + 255) & ~(size_t)255;
     if (rbsp_stride) *rbsp_stride = rbsp;
-    return (((size_t)n_mb * (IDR_NZ_BYTES + IDR_SLOT_DWORDS * 4 + 4) + ((size_t)n_mb + S) * 8 + (S > 1 ? 16 * S : 0) + rbsp + 255) & ~(size_t)255) + 256;     /* (+ 256: the counts of a group end at a multiple of 256) */
+    return (((size_t)n_mb * (IDR_NZ_BYTES + IDR_SLOT_DWORDS * 4 + 4 + (i4x4 ? IDR_MODE_BYTES : 0)) + ((size_t)n_mb + S) * 8 + (S > 1 ? 16 * S : 0) + rbsp + 255) & ~(size_t)255) +
+           (i4x4 ? 512 : 256);          /* (+ 256: the counts of a group end at a multiple of 256; so do the modes) */
 }
 #define IDR_GROUP_BYTES ((size_t)8 << 30)       /* the most working memory a batch keeps for its IDR pictures: larger batches run in groups */
 /* the working memory (made at first use, kept until the batch goes), the tables, and J but for its destination */
-static int idr_setup(pcamv_batch *b, int qp, const uint8_t *hdr, int hdr_bits, int nal_byte, int slice_rows, IdrJobs *J)
+static int idr_setup(pcamv_batch *b, int qp, const uint8_t *hdr, int hdr_bits, int nal_byte, int slice_rows, int i4x4, IdrJobs *J)
 {
     const pcamv_ctx *c0 = b->ctx[0];
     const int n_mb = c0->F.n_mb, n_slices = idr_n_slices(c0->F.mb_h, slice_rows);
@@ -2945,10 +2950,10 @@ static int idr_setup(pcamv_batch *b, int qp, const uint8_t *hdr, int hdr_bits, i
     }
     if (c0->p.i_luma_deadzone[1] < 0 || c0->p.i_luma_deadzone[1] > 32) return fail(b, PCAMV_EINVAL, "i_luma_deadzone[1] outside 0 .. 32");
     size_t rbsp_stride = 0;
-    const size_t place = idr_place_bytes(n_mb, n_slices, &rbsp_stride);
+    const size_t place = idr_place_bytes(n_mb, n_slices, i4x4, &rbsp_stride);
     int group = (int)(IDR_GROUP_BYTES / place);
     group = group < 1 ? 1 : group > b->n ? b->n : group;
-    if (!b->d_idr || b->idr_group != group || place * (size_t)group > b->d_idr.cap) {       /* (the last: a call with more slices than any before) */
+    if (!b->d_idr || b->idr_group != group || place * (size_t)group > b->d_idr.cap) {       /* (the last: a call with more slices than any before, or the first with i4x4) */
         if (b->d_idr) HIPCHK(b, hipDeviceSynchronize());    /* (regrown only behind this: pictures in flight work in the block) */
         TRY(b->d_idr.room(b, place * (size_t)group));
         b->idr_group = group;
@@ -2970,6 +2975,7 @@ static int idr_setup(pcamv_batch *b, int qp, const uint8_t *hdr, int hdr_bits, i
     j.slots = (uint32_t *)at; at += g * n * IDR_SLOT_DWORDS * 4;
     j.bits = (int *)at; at += g * n * 4;
     j.nz = at; at += (g * n * IDR_NZ_BYTES + 255) & ~(size_t)255;
+    if (i4x4) { j.modes = at; at += (g * n * IDR_MODE_BYTES + 255) & ~(size_t)255; }
     j.rbsp = at; j.rbsp_stride = (long long)rbsp_stride;
     j.tab = b->d_idr_tab;
     j.bad = (int *)(b->d_idr_ctx + (size_t)b->n * 24); j.first = j.bad + b->n;
@@ -2978,6 +2984,7 @@ static int idr_setup(pcamv_batch *b, int qp, const uint8_t *hdr, int hdr_bits, i
     j.hdr_bits = hdr_bits; j.nal_byte = nal_byte; j.n_mb = n_mb; j.qp = qp; j.dz = c0->p.i_luma_deadzone[1];
     j.status = b->d_wstat;
     j.n_slices = n_slices; j.slice_rows = n_slices > 1 ? slice_rows : 0;
+    j.i4x4 = i4x4; j.lambda = pcamv_lambda_tab[qp]; j.mb_bits = idr_mb_bits_of(i4x4);
     return 0;
 }
 /* the headers of the S > 1 slices of a picture, which differ in first_mb_in_slice alone; the first is the one idr_setup was given */
@@ -3013,7 +3020,11 @@ static int idr_run(pcamv_batch *b, IdrJobs &J, const void *sws_ctx, hipStream_t 
     if (sws_ctx) pcamv_launch_idr_slot(J, sws_ctx, b->n, st);
     for (int g0 = 0; g0 < b->n; g0 += b->idr_group) {
         const int g = b->n - g0 < b->idr_group ? b->n - g0 : b->idr_group;
-        timed(b, KT_IDR_MB, st, [&] { pcamv_launch_idr_mb(J, g0, g, F.mb_w, F.mb_h, st); });
+        if (J.i4x4) {
+            b->kt[KT_IDR_MB4].weight = pcamv_idr_deblock_launches(F.mb_w, F.mb_h);      /* (the anti-diagonals x + 2 y, as the filter's) */
+            timed(b, KT_IDR_MB4, st, [&] { pcamv_launch_idr_mb4(J, g0, g, F.mb_w, F.mb_h, st); });
+        } else
+            timed(b, KT_IDR_MB, st, [&] { pcamv_launch_idr_mb(J, g0, g, F.mb_w, F.mb_h, st); });
         if (J.n_slices > 1) {           /* several slices: a length pass and a placement in front of the units, which a wavefront each then writes */
             timed(b, KT_IDR_PREFIX, st, [&] { pcamv_launch_idr_prefix_slices(J, g0, g, st); });
             timed(b, KT_IDR_PACK, st, [&] { pcamv_launch_idr_pack_slices(J, g0, g, F.mb_w, F.mb_h, st); });
@@ -3052,11 +3063,12 @@ static pcamv_stream_params_t idr_probe_params(int pps_id)
     pcamv_stream_params_t P = {4, 0, 4, 0, 0, 0, 1, 0, 0, 26, 1, pps_id};
     return P;
 }
-extern "C" int pcamv_gpu_encode_idr3(pcamv_ctx_t *c, int qp, int pps_id, int idr_pic_id, int as_nal, int deblock, int slice_rows, uint8_t *out, size_t cap, size_t *len)
+extern "C" int pcamv_gpu_encode_idr4(pcamv_ctx_t *c, int qp, int pps_id, int idr_pic_id, int as_nal, int deblock, int slice_rows, int i4x4, uint8_t *out, size_t cap, size_t *len)
 {
     if (!c || !out || !len || cap > ((size_t)1 << 40)) return PCAMV_EINVAL;
     *len = 0;
     if (slice_rows < 0) return fail(c, PCAMV_EINVAL, "encode_idr3: slice_rows below 0");
+    if (i4x4 < 0 || i4x4 > 2) return fail(c, PCAMV_EINVAL, "encode_idr4: i4x4 is 0 (Intra16x16 only), 1 (decided per macroblock) or 2 (Intra4x4 everywhere)");
     if (idr_n_slices(c->F.mb_h, slice_rows) > 1 && !as_nal) return fail(c, PCAMV_EINVAL, "encode_idr3: the RBSPs of several slices behind each other mean nothing: as_nal must be 1");
     HIPCHK(c, hipSetDevice(c->device));
     pcamv_batch *b = c->self;
@@ -3070,7 +3082,7 @@ extern "C" int pcamv_gpu_encode_idr3(pcamv_ctx_t *c, int qp, int pps_id, int idr
     std::vector<IdrSliceHdr> shdr;
     TRY(idr_slice_headers(P, 3, idr_pic_id, qp, deblock, c->F.mb_w, c->F.mb_h, slice_rows, &shdr));
     IdrJobs J;
-    TRY(on_behalf(c, b, idr_setup(b, qp, hdr, hdr_bits, 3 << 5 | 5, slice_rows, &J)));
+    TRY(on_behalf(c, b, idr_setup(b, qp, hdr, hdr_bits, 3 << 5 | 5, slice_rows, i4x4, &J)));
     DevBuf<uint8_t> d_out;
     TRY(d_out.room(c, cap ? cap : 1));
     long long *arr = (long long *)b->d_idr_ctx.p;
@@ -3090,6 +3102,10 @@ extern "C" int pcamv_gpu_encode_idr3(pcamv_ctx_t *c, int qp, int pps_id, int idr
     *len = (size_t)n;
     return 0;
 }
+extern "C" int pcamv_gpu_encode_idr3(pcamv_ctx_t *c, int qp, int pps_id, int idr_pic_id, int as_nal, int deblock, int slice_rows, uint8_t *out, size_t cap, size_t *len)
+{
+    return pcamv_gpu_encode_idr4(c, qp, pps_id, idr_pic_id, as_nal, deblock, slice_rows, 0, out, cap, len);
+}
 extern "C" int pcamv_gpu_encode_idr2(pcamv_ctx_t *c, int qp, int pps_id, int idr_pic_id, int as_nal, int deblock, uint8_t *out, size_t cap, size_t *len)
 {
     return pcamv_gpu_encode_idr3(c, qp, pps_id, idr_pic_id, as_nal, deblock, 0, out, cap, len);
@@ -3098,12 +3114,13 @@ extern "C" int pcamv_gpu_encode_idr(pcamv_ctx_t *c, int qp, int pps_id, int idr_
 {
     return pcamv_gpu_encode_idr2(c, qp, pps_id, idr_pic_id, as_nal, 0, out, cap, len);
 }
-extern "C" int pcamv_gpu_batch_write_stream_idr3(pcamv_batch_t *b, int qp, int pps_id, int idr_pic_id, int deblock, int slice_rows, void *stream)
+extern "C" int pcamv_gpu_batch_write_stream_idr4(pcamv_batch_t *b, int qp, int pps_id, int idr_pic_id, int deblock, int slice_rows, int i4x4, void *stream)
 {
     if (!b) return PCAMV_EINVAL;
     HIPCHK(b, hipSetDevice(b->device));
     TRY(batch_live(b));
     if (slice_rows < 0) return fail(b, PCAMV_EINVAL, "write_stream_idr3: slice_rows below 0");
+    if (i4x4 < 0 || i4x4 > 2) return fail(b, PCAMV_EINVAL, "write_stream_idr4: i4x4 is 0 (Intra16x16 only), 1 (decided per macroblock) or 2 (Intra4x4 everywhere)");
     StreamOut &O = b->so;
     if (!O.ready) return fail(b, PCAMV_EINVAL, "no byte streams were opened on this batch yet (pcamv_gpu_batch_stream_open)");
     if (O.stepped) return fail(b, PCAMV_EINVAL, "write_stream_idr belongs behind the open and before the first picture of its streams");
@@ -3121,7 +3138,7 @@ extern "C" int pcamv_gpu_batch_write_stream_idr3(pcamv_batch_t *b, int qp, int p
     std::vector<IdrSliceHdr> shdr;
     TRY(idr_slice_headers(P, O.S.W.nal_ref_idc, idr_pic_id, qp, deblock, b->ctx[0]->F.mb_w, b->ctx[0]->F.mb_h, slice_rows, &shdr));
     IdrJobs J;
-    TRY(idr_setup(b, qp, hdr, hdr_bits, O.S.W.nal_ref_idc << 5 | 5, slice_rows, &J));
+    TRY(idr_setup(b, qp, hdr, hdr_bits, O.S.W.nal_ref_idc << 5 | 5, slice_rows, i4x4, &J));
     const StreamWrite SJ = stream_out_jobs(b);
     J.bytes = SJ.bytes; J.bytes_size = SJ.bytes_size; J.off = SJ.w_off; J.cap = SJ.w_cap; J.len = SJ.w_len; J.first = SJ.first; J.as_nal = 1; J.aud = O.S.W.aud;
     J.deblock = deblock;
@@ -3129,6 +3146,10 @@ extern "C" int pcamv_gpu_batch_write_stream_idr3(pcamv_batch_t *b, int qp, int p
     TRY(idr_run(b, J, SJ.ctx, st, shdr));
     timed_kernel(b, KT_STREAM_COMMIT, st, k_stream_commit, dim3((b->n + 63) / 64), dim3(64), SJ);
     return launched(b);
+}
+extern "C" int pcamv_gpu_batch_write_stream_idr3(pcamv_batch_t *b, int qp, int pps_id, int idr_pic_id, int deblock, int slice_rows, void *stream)
+{
+    return pcamv_gpu_batch_write_stream_idr4(b, qp, pps_id, idr_pic_id, deblock, slice_rows, 0, stream);
 }
 extern "C" int pcamv_gpu_batch_write_stream_idr2(pcamv_batch_t *b, int qp, int pps_id, int idr_pic_id, int deblock, void *stream)
 {

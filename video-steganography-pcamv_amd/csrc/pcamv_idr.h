@@ -8,11 +8,12 @@
  * lane; the output path behind a final byte) and pcamv_stream_write.h (the bit writer of the slice headers).
  *
  * Scope, fixed: one I slice per picture, or several of whole macroblock rows (IdrPic::slice_rows; the layout: pcamv_idr_defs.h),
- * Intra16x16 macroblocks only (luma V / H / DC / plane, chroma DC / H / V / plane, each chosen by
+ * Intra16x16 macroblocks -- behind a flag Intra4x4 ones beside them (IdrPic::i4x4: idr_mb4 of pcamv_idr_i4x4.h, which begins with
+ * idr_mb and replaces its luma where the Intra4x4 trial costs less; with the flag at 0 nothing here is touched) -- (luma V / H / DC / plane, chroma DC / H / V / plane, each chosen by
  * SATD among the modes whose neighbours exist, ties to the lower mode number of 8.3.3 / 8.3.4), one QP (mb_qp_delta 0), CAVLC whatever
  * the stream's P slices use, disable_deblocking_filter_idc 1: the reconstruction a decoder makes is the unfiltered one that is made here
  * and becomes the chain's reference (or, where the caller asks for a filtered picture, goes through pcamv_idr_deblock.h first, behind
- * the whole picture's coding: nothing here changes with that, intra prediction reads unfiltered samples).  This is NOT the reference's I-frame coder (no I4x4, no RD decision, its own mode order): an I
+ * the whole picture's coding: nothing here changes with that, intra prediction reads unfiltered samples).  This is NOT the reference's I-frame coder (its own I4x4 rule, no RD decision, its own mode order): an I
  * picture carries no payload, and the P chain's exactness is defined given its reference picture.
  *
  * Arithmetic.  Forward: the core transform of 8.5 backwards on the 4x4 residuals; the sixteen luma DCs through a 4x4 Hadamard with
@@ -35,7 +36,8 @@
  * serial state -- no skip run, a constant QP -- so every macroblock's bit string is made where the macroblock is coded, into its own
  * slot of IDR_SLOT_DWORDS, and a prefix over the lengths places them.
  *
- * Memory per context (IdrPic): 24 counts, a slot and a length per macroblock, a prefix entry per macroblock, the RBSP.
+ * Memory per context (IdrPic): 24 counts, a slot and a length per macroblock, a prefix entry per macroblock, the RBSP; with i4x4 the
+ * sixteen Intra4x4PredModes of every macroblock.
  */
 #ifndef PCAMV_IDR_H
 #define PCAMV_IDR_H

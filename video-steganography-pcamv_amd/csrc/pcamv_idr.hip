@@ -1,11 +1,15 @@
 /*
- * pcamv_idr.hip -- the IDR picture of every chain coded on the device (gfx950): k_idr_mb, k_idr_prefix, k_idr_pack, k_idr_slot,
- * k_idr_unit, k_idr_deblock.  The coder itself is pcamv_idr.h, its loop filter pcamv_idr_deblock.h (both shared with the host checks);
+ * pcamv_idr.hip -- the IDR picture of every chain coded on the device (gfx950): k_idr_mb, k_idr_mb4, k_idr_prefix, k_idr_pack, k_idr_slot,
+ * k_idr_unit, k_idr_deblock.  The coder itself is pcamv_idr.h with pcamv_idr_i4x4.h, its loop filter pcamv_idr_deblock.h (all shared with the host checks);
  * this unit gives them their working memory and their place in a batch.
  *
  *   k_idr_mb      one wavefront per macroblock, launched once per anti-diagonal x + y = d over the contexts of a group (Intra16x16 reads
  *                 left, top and top-left only): mode decision, transform, reconstruction, counts, the macroblock's bit string.  The
  *                 working memory is LDS of the wave (IdrWork); the code tables are read where they lie.
+ *   k_idr_mb4     in k_idr_mb's place in a call with i4x4 != 0 (IdrJobs::i4x4): the same macroblock, then the Intra4x4 trial -- sixteen
+ *                 blocks one after the other, a wave barrier between them, a lane per candidate mode, the winner's lane coding the block --
+ *                 the decision and, where Intra4x4 wins, its luma, counts, modes and bit string (idr_mb4; IdrWork and IdrWork4, 6080 bytes of
+ *                 LDS).  Launched once per anti-diagonal x + 2 y = d: Intra4x4 reads the macroblock above-right.
  *   k_idr_prefix  per context the exclusive prefix of the macroblocks' bit counts, the header's bits in front: every thread sums a run
  *                 of macroblocks, the block scans the runs' sums in LDS, every thread writes its run.
  *   k_idr_pack    one lane per destination dword of the RBSP (idr_pack_dword).
@@ -23,7 +27,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "pcamv_flow.hip.h"
-#include "pcamv_idr.h"
+#include "pcamv_idr_i4x4.h"
 #include "pcamv_idr_deblock.h"
 
 /* context i's picture at its place in the group */
@@ -47,6 +51,22 @@ static __global__ void __launch_bounds__(64) k_idr_mb(const IdrJobs J, int d, in
     const int y_lo = d - (P.mb_w - 1) > 0 ? d - (P.mb_w - 1) : 0, my = y_lo + (int)blockIdx.x, mx = d - my;
     if (my >= P.mb_h || mx < 0 || mx >= P.mb_w) return;
     idr_mb(W, P, (const uint16_t *)J.tab, mx, my);
+}
+
+/* a call with i4x4 != 0: the same macroblock and then the Intra4x4 trial, the decision and, where it wins, the Intra4x4 macroblock
+ * (idr_mb4).  Intra4x4 reads the macroblock above-right, which x + y does not order: one launch per anti-diagonal x + 2 y = d */
+static __global__ void __launch_bounds__(64) k_idr_mb4(const IdrJobs J, int d, int g0)
+{
+    __shared__ IdrWork W;
+    __shared__ IdrWork4 W4;
+    IdrPic P = idr_pic(J, g0 + blockIdx.y, blockIdx.y);
+    if (!J.modes) return;
+    P.i4x4 = J.i4x4; P.lambda = J.lambda; P.modes = J.modes + (size_t)blockIdx.y * IDR_MODE_BYTES * J.n_mb;      /* (this kernel's alone: the others leave them at their defaults) */
+    int y_lo, y_hi;
+    idb_diag_rows(d, P.mb_w, P.mb_h, &y_lo, &y_hi);
+    const int my = y_lo + (int)blockIdx.x, mx = d - 2 * my;
+    if (my > y_hi || mx < 0 || mx >= P.mb_w) return;
+    idr_mb4(W, W4, P, (const uint16_t *)J.tab, mx, my);
 }
 
 #define IDR_PREFIX_THREADS 1024
@@ -145,7 +165,7 @@ static __global__ void __launch_bounds__(256) k_idr_pack_slices(const IdrJobs J,
     const long long f = idr_slice_first_mb(P.mb_w, P.mb_h, P.slice_rows, s), n = idr_slice_n_mb(P.mb_w, P.mb_h, P.slice_rows, s);
     const long long *pre = J.pre + (long long)place * (J.n_mb + S) + idr_slice_pre_at(f, s);
     const long long k = (long long)blockIdx.x * 256 + threadIdx.x, dwords = (idr_rbsp_bytes(pre[n]) + 3) >> 2;
-    const long long at = idr_slice_rbsp_at(f, s), room = (idr_slice_rbsp_at(f + n, s + 1) - at) / 4;
+    const long long at = idr_slice_rbsp_at_bits(f, s, J.mb_bits), room = (idr_slice_rbsp_at_bits(f + n, s + 1, J.mb_bits) - at) / 4;
     if (k >= dwords || k >= room) return;
     ((uint32_t *)(J.rbsp + (long long)place * J.rbsp_stride + at))[k] = idr_pack_dword(k, J.shdr[s].hdr, J.shdr[s].bits, pre, P.slots + (size_t)f * IDR_SLOT_DWORDS, (int)n);
 }
@@ -158,11 +178,11 @@ static __global__ void __launch_bounds__(64) k_idr_unit_len(const IdrJobs J, int
     const IdrPic P = idr_pic(J, i, place);
     const long long f = idr_slice_first_mb(P.mb_w, P.mb_h, P.slice_rows, s), n = idr_slice_n_mb(P.mb_w, P.mb_h, P.slice_rows, s);
     const long long *pre = J.pre + (long long)place * (J.n_mb + S) + idr_slice_pre_at(f, s);
-    const long long at = idr_slice_rbsp_at(f, s), rbsp_len = idr_rbsp_bytes(pre[n]);
+    const long long at = idr_slice_rbsp_at_bits(f, s, J.mb_bits), rbsp_len = idr_rbsp_bytes(pre[n]);
     long long len = -1;
     IdrOut O;
     O.obuf = s_obuf;
-    if (!J.bad[i] && rbsp_len >= 0 && at + ((rbsp_len + 3) & ~3LL) <= idr_slice_rbsp_at(f + n, s + 1))
+    if (!J.bad[i] && rbsp_len >= 0 && at + ((rbsp_len + 3) & ~3LL) <= idr_slice_rbsp_at_bits(f + n, s + 1, J.mb_bits))
         idr_unit_walk(O, s_win, J.rbsp + (long long)place * J.rbsp_stride + at, rbsp_len, J.nal_byte, J.as_nal, J.bytes, 0, 1, &len);
     if (threadIdx.x == 0) J.ulen[(long long)place * S + s] = len;
 }
@@ -191,7 +211,7 @@ static __global__ void __launch_bounds__(64) k_idr_unit_slices(const IdrJobs J, 
     const IdrPic P = idr_pic(J, i, place);
     const long long f = idr_slice_first_mb(P.mb_w, P.mb_h, P.slice_rows, s), n = idr_slice_n_mb(P.mb_w, P.mb_h, P.slice_rows, s);
     const long long *pre = J.pre + (long long)place * (J.n_mb + S) + idr_slice_pre_at(f, s);
-    const long long at = idr_slice_rbsp_at(f, s), rbsp_len = idr_rbsp_bytes(pre[n]);
+    const long long at = idr_slice_rbsp_at_bits(f, s, J.mb_bits), rbsp_len = idr_rbsp_bytes(pre[n]);
     const long long uoff = J.uoff[(long long)place * S + s], ulen = J.ulen[(long long)place * S + s];
     long long len = 0;
     IdrOut O;
@@ -257,6 +277,15 @@ void pcamv_launch_idr_mb(const IdrJobs &J, int g0, int g, int mb_w, int mb_h, hi
         hipLaunchKernelGGL(k_idr_mb, dim3((unsigned)(y_hi - y_lo + 1), (unsigned)g), dim3(64), 0, st, J, d, g0);
     }
 }
+void pcamv_launch_idr_mb4(const IdrJobs &J, int g0, int g, int mb_w, int mb_h, hipStream_t st)
+{
+    for (int d = 0; d < idb_n_diag(mb_w, mb_h); d++) {
+        int y_lo, y_hi;
+        idb_diag_rows(d, mb_w, mb_h, &y_lo, &y_hi);
+        if (y_hi < y_lo) continue;                      /* a picture one macroblock wide has nothing on its odd diagonals */
+        hipLaunchKernelGGL(k_idr_mb4, dim3((unsigned)(y_hi - y_lo + 1), (unsigned)g), dim3(64), 0, st, J, d, g0);
+    }
+}
 int pcamv_idr_deblock_launches(int mb_w, int mb_h) { return idb_n_diag(mb_w, mb_h); }
 void pcamv_launch_idr_deblock(const IdrJobs &J, int n, int mb_w, int mb_h, hipStream_t st)
 {
@@ -280,7 +309,7 @@ void pcamv_launch_idr_prefix_slices(const IdrJobs &J, int g0, int g, hipStream_t
 void pcamv_launch_idr_pack_slices(const IdrJobs &J, int g0, int g, int mb_w, int mb_h, hipStream_t st)
 {
     /* the longest slice is the first; its room in dwords bounds every slice's */
-    const long long dwords = idr_slice_rbsp_at(idr_slice_n_mb(mb_w, mb_h, J.slice_rows, 0), 1) / 4, total = (long long)g * J.n_slices;
+    const long long dwords = idr_slice_rbsp_at_bits(idr_slice_n_mb(mb_w, mb_h, J.slice_rows, 0), 1, J.mb_bits) / 4, total = (long long)g * J.n_slices;
     for (long long q0 = 0; q0 < total; q0 += 65535)     /* (a grid's second dimension) */
         hipLaunchKernelGGL(k_idr_pack_slices, dim3((unsigned)((dwords + 255) / 256), (unsigned)(total - q0 < 65535 ? total - q0 : 65535)), dim3(256), 0, st, J, g0, (int)q0);
 }

@@ -5,9 +5,10 @@
  * (pcamv_mvsyntax.h), which stays the independent check: the two share no code and no table.  No HIP type.  Behind pcamv_slice_parse.h
  * (SP_HD, SP_LANES, SP_SYNC).
  *
- * Scope, fixed (8.7 for such a picture): a frame picture of one slice, Intra16x16 macroblocks only, one QP, 4x4 transform,
- * FilterOffsetA = FilterOffsetB = 0.  So nothing per macroblock is needed: bS is 4 on a macroblock edge whose neighbour lies in the
- * picture, 3 on the three inner edges, and an edge on the picture's border is not filtered; indexA = indexB = QP for luma and the
+ * Scope, fixed (8.7 for such a picture): a frame picture of one slice, intra macroblocks only -- Intra16x16, and with i4x4 Intra4x4
+ * (pcamv_idr_i4x4.h) --, one QP, 4x4 transform, FilterOffsetA = FilterOffsetB = 0.  So nothing per macroblock is needed: with the 4x4
+ * transform bS is 4 on the macroblock edges and 3 inside for every intra macroblock, whatever its type: 4 on a macroblock edge whose
+ * neighbour lies in the picture, 3 on the three inner edges, and an edge on the picture's border is not filtered; indexA = indexB = QP for luma and the
  * chroma QP for both chroma planes.  alpha or beta 0 (index below 16) leaves every line alone: |a - b| < 0 never holds.
  *
  * One macroblock by one wavefront.  Staged in the wave's working memory: the macroblock with the four columns to its left and the four

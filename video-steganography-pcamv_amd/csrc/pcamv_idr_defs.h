@@ -14,6 +14,14 @@
 #define IDR_MB_BITS 11179
 #define IDR_SLOT_DWORDS 352
 static_assert(IDR_MB_BITS <= 32 * IDR_SLOT_DWORDS, "a macroblock's bit string fits its slot");
+/* the longest Intra4x4 macroblock (pcamv_idr_i4x4.h): mb_type ue(0) 1, sixteen times prev_intra4x4_pred_mode_flag 0 and rem_intra4x4_pred_mode
+ * u(3) 64, chroma mode ue(<= 3) 5, coded_block_pattern me(v) of codeNum <= 47 11, mb_qp_delta 1, sixteen blocks of 16 (464 each), eight
+ * of 15 (436), two of 4 (118): 82 + 7424 + 3488 + 236 = 11230 bits, 51 more than an Intra16x16 one and still within the slot */
+#define IDR_MB_BITS_I4 11230
+static_assert(IDR_MB_BITS_I4 == 1 + 64 + 5 + 11 + 1 + 16 * 464 + 8 * 436 + 2 * 118, "the terms of the longest Intra4x4 macroblock");
+static_assert(IDR_MB_BITS_I4 >= IDR_MB_BITS && IDR_MB_BITS_I4 <= 32 * IDR_SLOT_DWORDS, "an Intra4x4 macroblock's bit string fits the same slot");
+#define IDR_I4_BIAS 24          /* cost4 = IDR_I4_BIAS * lambda + the sixteen winning costs: the coder's own rule, not measured */
+#define IDR_MODE_BYTES 16       /* Intra4x4PredMode of a macroblock's sixteen blocks by luma4x4BlkIdx; sixteen 2s (DC) for Intra16x16 (8.3.1.1) */
 #define IDR_NZ_BYTES 24         /* total_coeff of a macroblock's AC blocks: luma by luma4x4BlkIdx, Cb 0..3, Cr 0..3 */
 #define IDR_HDR_MAX_BITS 192    /* first_mb 1, slice_type ue(7) 7, pps_id 17, frame_num 16, idr_pic_id ue(65535) 33, POC <= 16 + 1 or 2, redundant 1,
                                  * the two marking flags, slice_qp_delta 13, the idc 3 -- or, of a filtered picture, idc 0 and two offsets of 0: 3 again, and
@@ -85,15 +93,22 @@ struct IdrPic {
     int *bits;                          /* [n_mb] their number; negative: the coder failed on this macroblock (never) */
     int *clamped;                       /* [n_mb] levels the clamp changed (optional: the host check) */
     int slice_rows = 0;                 /* macroblock rows per slice; 0 (and anything from mb_h up): the picture is one slice */
+    int i4x4 = 0;                       /* idr_mb4 (pcamv_idr_i4x4.h): 0 Intra16x16 only, 1 Intra4x4 where it costs less, 2 Intra4x4 everywhere */
+    int lambda = 0;                     /* pcamv_lambda_tab[qp]: the weight of a mode's bits in the Intra4x4 trial */
+    uint8_t *modes = nullptr;           /* [n_mb][IDR_MODE_BYTES]; only with i4x4 != 0 */
 };
 /* the bytes of an RBSP whose stop bit is bit end_bit */
 SP_HD long long idr_rbsp_bytes(long long end_bit) { return (end_bit + 8) >> 3; }
 /* a capacity that always fits: the RBSP of the longest macroblocks, as a unit with every third byte an emulation prevention byte */
-SP_HD long long idr_bound(long long n_mb, int as_nal)
+/* (idr_bound_bits, idr_slice_rbsp_at_bits, idr_bound_slices_bits: the same of macroblocks of at most mb_bits bits -- IDR_MB_BITS, or
+ * IDR_MB_BITS_I4 in a call that may code Intra4x4 macroblocks) */
+SP_HD long long idr_bound_bits(long long n_mb, int as_nal, int mb_bits)
 {
-    const long long rbsp = (IDR_HDR_MAX_BITS + n_mb * IDR_MB_BITS + 8) / 8 + 1;
+    const long long rbsp = (IDR_HDR_MAX_BITS + n_mb * mb_bits + 8) / 8 + 1;
     return as_nal ? 5 + rbsp + rbsp / 2 + 1 : rbsp;
 }
+SP_HD long long idr_bound(long long n_mb, int as_nal) { return idr_bound_bits(n_mb, as_nal, IDR_MB_BITS); }
+SP_HD int idr_mb_bits_of(int i4x4) { return i4x4 ? IDR_MB_BITS_I4 : IDR_MB_BITS; }
 
 /* ---------------------------------------------------------------- several slices per picture: the layout, stated once
  * A slice is slice_rows whole macroblock rows (the last one what is left), so a macroblock's left neighbour is always in its slice and
@@ -116,15 +131,17 @@ SP_HD int idr_slice_n_mb(int mb_w, int mb_h, int slice_rows, int s)
     return (y1 - y0) * mb_w;
 }
 SP_HD long long idr_slice_pre_at(long long first_mb, int s) { return first_mb + s; }
-SP_HD long long idr_slice_rbsp_at(long long first_mb, int s) { return (long long)IDR_SLICE_PAD_BYTES * s + 4 * ((first_mb * IDR_MB_BITS + 31) / 32); }
+SP_HD long long idr_slice_rbsp_at_bits(long long first_mb, int s, int mb_bits) { return (long long)IDR_SLICE_PAD_BYTES * s + 4 * ((first_mb * mb_bits + 31) / 32); }
+SP_HD long long idr_slice_rbsp_at(long long first_mb, int s) { return idr_slice_rbsp_at_bits(first_mb, s, IDR_MB_BITS); }
 /* a capacity that always fits the S units of a picture behind each other: the sum of idr_bound over its slices */
-SP_HD long long idr_bound_slices(int mb_w, int mb_h, int slice_rows, int as_nal)
+SP_HD long long idr_bound_slices_bits(int mb_w, int mb_h, int slice_rows, int as_nal, int mb_bits)
 {
     const int S = idr_n_slices(mb_h, slice_rows);
     long long sum = 0;
-    for (int s = 0; s < S; s++) sum += idr_bound(idr_slice_n_mb(mb_w, mb_h, slice_rows, s), as_nal);
+    for (int s = 0; s < S; s++) sum += idr_bound_bits(idr_slice_n_mb(mb_w, mb_h, slice_rows, s), as_nal, mb_bits);
     return sum;
 }
+SP_HD long long idr_bound_slices(int mb_w, int mb_h, int slice_rows, int as_nal) { return idr_bound_slices_bits(mb_w, mb_h, slice_rows, as_nal, IDR_MB_BITS); }
 /* a slice's header as the device reads it: the table of a call has S of them */
 struct IdrSliceHdr { uint8_t hdr[IDR_HDR_BYTES]; int bits, pad; };
 
@@ -145,5 +162,6 @@ struct IdrJobs {
     uint8_t *bytes; long long bytes_size;
     long long *off, *cap, *len; int *first, *status;
     int slice_rows, n_slices; const IdrSliceHdr *shdr; long long *ulen, *uoff; SwsCtx *units;
+    int i4x4, lambda, mb_bits; uint8_t *modes;          /* IdrPic's i4x4 and lambda; the bound of a macroblock's bits the RBSP offsets are laid out by; [n_mb][IDR_MODE_BYTES] per place */
 };
 #endif

@@ -974,6 +974,127 @@ struct IDec {
                 for (int y = 0; y < 4; y++) for (int x = 0; x < 4; x++) p[(4 * by + y) * w + 4 * bx + x] = (uint8_t)dc;
             }
     }
+    /* ---- I_NxN macroblocks (flags bit 0): Intra4x4 prediction (8.3.1), the 4x4 residual blocks of 16 (7.3.5.3), the intra column of
+     * Table 9-4.  modes: Intra4x4PredMode [n_mb][16] by luma4x4BlkIdx, sixteen 2s for an Intra16x16 macroblock (8.3.1.1) */
+    int flags = 0;
+    uint8_t *modes = NULL;
+    /* Intra4x4PredMode m of the block at (px, py) of the luma plane, in place: 8.3.1.2.1 .. 8.3.1.2.9.  hl / ht / hc / hr: the column to the
+     * left, the row above, the corner and the four samples above-right are there; false: the mode needs what is missing */
+    bool predict4(int px, int py, int m, bool hl, bool ht, bool hc, bool hr)
+    {
+        const int w = 16 * mb_w;
+        uint8_t *p = pl[0] + (size_t)py * w + px;
+        if (((m == 0 || m == 3 || m == 7) && !ht) || ((m == 1 || m == 8) && !hl) || ((m == 4 || m == 5 || m == 6) && !(hl && ht && hc)) || m < 0 || m > 8) return false;
+        /* the thirteen neighbours on one line: z[0 .. 3] the left column from the bottom up, z[4] the corner, z[5 .. 12] the row above and
+         * above-right, left to right; the diagonal modes filter along it */
+        int z[13];
+        for (int k = 0; k < 13; k++) z[k] = 128;
+        if (hl) for (int y = 0; y < 4; y++) z[3 - y] = p[y * w - 1];
+        if (hc) z[4] = p[-w - 1];
+        if (ht) { for (int x = 0; x < 4; x++) z[5 + x] = p[-w + x]; for (int x = 4; x < 8; x++) z[5 + x] = hr ? p[-w + x] : p[-w + 3]; }
+        auto f3 = [&](int a, int c, int e) { return (z[a] + 2 * z[c] + z[e] + 2) >> 2; };
+        auto f2 = [&](int a, int c) { return (z[a] + z[c] + 1) >> 1; };
+        int o[4][4];
+        if (m == 2) {
+            const int st = z[5] + z[6] + z[7] + z[8], sl = z[0] + z[1] + z[2] + z[3];
+            const int dc = hl && ht ? (st + sl + 4) >> 3 : hl ? (sl + 2) >> 2 : ht ? (st + 2) >> 2 : 128;
+            for (int y = 0; y < 4; y++) for (int x = 0; x < 4; x++) o[y][x] = dc;
+        }
+        for (int y = 0; y < 4; y++)
+            for (int x = 0; x < 4; x++) {
+                if (m == 0) o[y][x] = z[5 + x];
+                else if (m == 1) o[y][x] = z[3 - y];
+                else if (m == 3) o[y][x] = x + y == 6 ? (z[11] + 3 * z[12] + 2) >> 2 : f3(5 + x + y, 6 + x + y, 7 + x + y);
+                else if (m == 4) o[y][x] = f3(3 + x - y, 4 + x - y, 5 + x - y);                  /* along the line, around the place x - y of the corner */
+                else if (m == 5) {                                                              /* vertical-right: the row above, half a sample per row */
+                    const int q = 2 * x - y;
+                    o[y][x] = q < -1 ? f3(6 - y, 5 - y, 4 - y) : q == -1 ? f3(3, 4, 5) : q & 1 ? f3(3 + x - (y >> 1), 4 + x - (y >> 1), 5 + x - (y >> 1)) : f2(4 + x - (y >> 1), 5 + x - (y >> 1));
+                } else if (m == 6) {                                                            /* horizontal-down: the same along the left column */
+                    const int q = 2 * y - x;
+                    o[y][x] = q < -1 ? f3(2 + x, 3 + x, 4 + x) : q == -1 ? f3(3, 4, 5) : q & 1 ? f3(5 - y + (x >> 1), 4 - y + (x >> 1), 3 - y + (x >> 1)) : f2(4 - y + (x >> 1), 3 - y + (x >> 1));
+                } else if (m == 7) o[y][x] = y & 1 ? f3(5 + x + (y >> 1), 6 + x + (y >> 1), 7 + x + (y >> 1)) : f2(5 + x + (y >> 1), 6 + x + (y >> 1));
+                else if (m == 8) {
+                    const int q = x + 2 * y, k = 3 - y - (x >> 1);                               /* z[k]: the left sample of row y + (x >> 1) */
+                    o[y][x] = q > 5 ? z[0] : q == 5 ? (z[1] + 3 * z[0] + 2) >> 2 : q & 1 ? f3(k, k - 1, k - 2) : f2(k, k - 1);
+                }
+            }
+        for (int y = 0; y < 4; y++) for (int x = 0; x < 4; x++) p[y * w + x] = (uint8_t)o[y][x];
+        return true;
+    }
+    int mb_nxn(int mx, int my)
+    {
+        static const int zz[16][2] = {{0, 0}, {0, 1}, {1, 0}, {2, 0}, {1, 1}, {0, 2}, {0, 3}, {1, 2}, {2, 1}, {3, 0}, {3, 1}, {2, 2}, {1, 3}, {2, 3}, {3, 2}, {3, 3}};
+        /* Table 9-4, chroma_format_idc 1, the column of Intra_4x4: codeNum -> coded_block_pattern */
+        static const uint8_t cbp_of[48] = {47, 31, 15, 0, 23, 27, 29, 30, 7, 11, 13, 14, 39, 43, 45, 46, 16, 3, 5, 10, 12, 19, 21, 26,
+                                           28, 35, 37, 42, 44, 1, 2, 4, 8, 17, 18, 20, 24, 6, 9, 22, 25, 32, 33, 34, 36, 40, 38, 41};
+        const int xy = my * mb_w + mx;
+        const bool left = mx > 0, top = my > 0, topright = top && mx + 1 < mb_w;
+        auto blk_at = [](int x, int y) { return (x & 1) | (y & 1) << 1 | (x & 2) << 1 | (y & 2) << 2; };
+        uint8_t *md = modes + (size_t)xy * 16;
+        const uint8_t *ml = left ? md - 16 : NULL, *mt = top ? md - 16 * mb_w : NULL;
+        for (int bi = 0; bi < 16; bi++) {               /* 8.3.1.1 */
+            const int x = blk_x(bi), y = blk_y(bi);
+            const int ma = x > 0 ? md[blk_at(x - 1, y)] : ml ? ml[blk_at(3, y)] : -1, mb = y > 0 ? md[blk_at(x, y - 1)] : mt ? mt[blk_at(x, 3)] : -1;
+            const int pred = ma < 0 || mb < 0 ? 2 : ma < mb ? ma : mb;
+            if (b.get(1)) md[bi] = (uint8_t)pred;
+            else { const int rem = (int)b.get(3); md[bi] = (uint8_t)(rem < pred ? rem : rem + 1); }
+        }
+        const unsigned cmode = b.ue();
+        if (b.overrun || cmode > 3) return PCAMV_EINVAL;
+        const unsigned code = b.ue();
+        if (b.overrun || code > 47) return PCAMV_EINVAL;
+        const int cbp_l = cbp_of[code] & 15, cbp_c = cbp_of[code] >> 4;
+        if (cbp_l | cbp_c) if (b.se() != 0 || b.overrun) return b.overrun ? PCAMV_EINVAL : PCAMV_EUNSUP;    /* mb_qp_delta: one QP */
+        if ((cmode == 1 && !left) || (cmode == 2 && !top) || (cmode == 3 && !(left && top))) return PCAMV_EINVAL;
+        uint8_t *cnt = nz + (size_t)xy * 24;
+        const uint8_t *cl = left ? cnt - 24 : NULL, *ct = top ? cnt - 24 * mb_w : NULL;
+        memset(cnt, 0, 24);
+        int lv[16][16], total;
+        memset(lv, 0, sizeof(lv));
+        for (int bi = 0; bi < 16; bi++) {
+            if (!(cbp_l >> (bi >> 2) & 1)) continue;
+            const int x = blk_x(bi), y = blk_y(bi);
+            const int na = x > 0 ? cnt[blk_at(x - 1, y)] : cl ? cl[blk_at(3, y)] : -1, nb = y > 0 ? cnt[blk_at(x, y - 1)] : ct ? ct[blk_at(x, 3)] : -1;
+            if (!residual(nc_class(na, nb), 16, lv[bi], &total)) return PCAMV_EINVAL;
+            cnt[bi] = (uint8_t)total;
+        }
+        int cdc[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}, cac[2][4][16];
+        memset(cac, 0, sizeof(cac));
+        if (cbp_c) for (int c = 0; c < 2; c++) if (!residual(4, 4, cdc[c], &total)) return PCAMV_EINVAL;
+        if (cbp_c == 2)
+            for (int c = 0; c < 2; c++)
+                for (int k = 0; k < 4; k++) {
+                    const int base = 16 + 4 * c, x = k & 1, y = k >> 1;
+                    const int na = x ? cnt[base + 2 * y] : cl ? cl[base + 2 * y + 1] : -1, nb = y ? cnt[base + x] : ct ? ct[base + 2 + x] : -1;
+                    if (!residual(nc_class(na, nb), 15, cac[c][k] + 1, &total)) return PCAMV_EINVAL;
+                    cnt[base + k] = (uint8_t)total;
+                }
+        /* luma: block by block, each predicted from what is reconstructed so far (8.3.1.2), its sixteen coefficients through 8.5.12 */
+        const int q6 = qp % 6, qd = qp / 6;
+        for (int bi = 0; bi < 16; bi++) {
+            const int x = blk_x(bi), y = blk_y(bi);
+            const bool hl = x > 0 || left, ht = y > 0 || top, hc = x > 0 && y > 0 ? true : x > 0 ? top : y > 0 ? left : left && top;
+            /* above-right (6.4.11.4): a block decoded later, or one of the macroblock to the right, is not available */
+            const bool hr = y > 0 ? x < 3 && blk_at(x + 1, y - 1) < bi : x < 3 ? top : topright;
+            if (!predict4(16 * mx + 4 * x, 16 * my + 4 * y, md[bi], hl, ht, hc, hr)) return PCAMV_EINVAL;
+            int c4[4][4];
+            for (int i = 0; i < 16; i++) c4[zz[i][0]][zz[i][1]] = lv[bi][i] * vscale(q6, zz[i][0], zz[i][1]) * (1 << qd);
+            add_idct(c4, pl[0] + (size_t)(16 * my + 4 * y) * 16 * mb_w + 16 * mx + 4 * x, 16 * mb_w);
+        }
+        const int c6 = qpc % 6, cd = qpc / 6;
+        for (int c = 0; c < 2; c++) {
+            predict(1 + c, 8, 8 * mx, 8 * my, (int)cmode, left, top);
+            const int *d = cdc[c];
+            const int f4[4] = {d[0] + d[1] + d[2] + d[3], d[0] - d[1] + d[2] - d[3], d[0] + d[1] - d[2] - d[3], d[0] - d[1] - d[2] + d[3]};
+            for (int k = 0; k < 4; k++) {
+                int c4[4][4];
+                for (int i = 1; i < 16; i++) c4[zz[i][0]][zz[i][1]] = cac[c][k][i] * vscale(c6, zz[i][0], zz[i][1]) * (1 << cd);
+                c4[0][0] = (f4[k] * 16 * vscale(c6, 0, 0) * (1 << cd)) >> 5;
+                add_idct(c4, pl[1 + c] + (size_t)(8 * my + 4 * (k >> 1)) * 8 * mb_w + 8 * mx + 4 * (k & 1), 8 * mb_w);
+            }
+        }
+        return b.overrun ? PCAMV_EINVAL : 0;
+    }
     int run()
     {
         static const int zz[16][2] = {{0, 0}, {0, 1}, {1, 0}, {2, 0}, {1, 1}, {0, 2}, {0, 3}, {1, 2}, {2, 1}, {3, 0}, {3, 1}, {2, 2}, {1, 3}, {2, 3}, {3, 2}, {3, 3}};
@@ -984,6 +1105,12 @@ struct IDec {
                 const bool left = mx > 0, top = my > 0;
                 const unsigned mb_type = b.ue();
                 if (b.overrun) return PCAMV_EINVAL;
+                if (mb_type == 0 && (flags & 1)) {      /* I_NxN, where the caller asked for it */
+                    const int rc = mb_nxn(mx, my);
+                    if (rc) return rc;
+                    continue;
+                }
+                if (modes) memset(modes + (size_t)xy * 16, 2, 16);
                 if (mb_type == 0 || mb_type > 24) return mb_type <= 25 ? PCAMV_EUNSUP : PCAMV_EINVAL;      /* I_NxN, I_PCM: not this subset */
                 const int mode = (int)(mb_type - 1) & 3, cbp_c = (int)((mb_type - 1) >> 2) % 3, cbp_l = mb_type > 12 ? 15 : 0;
                 const unsigned cmode = b.ue();
@@ -1061,13 +1188,15 @@ struct IDec {
 };
 }
 /* y / u / v receive the planes tightly packed (16 mb_w x 16 mb_h, half that twice); on failure their contents are unspecified */
-extern "C" int pcamv_gpu_decode_islice_cavlc(const uint8_t *rbsp, size_t len, size_t start_bit, int mb_w, int mb_h, int slice_qp, int chroma_qp_index_offset,
-                                             uint8_t *y, uint8_t *u, uint8_t *v)
+/* ... cavlc2: flags bit 0 set makes it accept I_NxN macroblocks (Intra4x4: 8.3.1, the intra column of Table 9-4, mb_qp_delta only with a
+ * pattern, nC across the macroblock types) beside the Intra16x16 ones; other bits PCAMV_EINVAL.  With flags 0 it IS the function above */
+extern "C" int pcamv_gpu_decode_islice_cavlc2(const uint8_t *rbsp, size_t len, size_t start_bit, int mb_w, int mb_h, int slice_qp, int chroma_qp_index_offset, int flags,
+                                              uint8_t *y, uint8_t *u, uint8_t *v)
 {
     static const uint8_t qpc_tab[52] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29,
                                         29, 30, 31, 32, 32, 33, 34, 34, 35, 35, 36, 36, 37, 37, 37, 38, 38, 38, 39, 39, 39, 39};      /* Table 8-15 */
     if (!rbsp || !y || !u || !v || len < 1 || len > ((size_t)1 << 31) || start_bit >= len * 8 || mb_w < 1 || mb_h < 1 || mb_w > (1 << 16) || mb_h > (1 << 16) ||
-        (long long)mb_w * mb_h > (1 << 20) || slice_qp < 0 || slice_qp > 51 || chroma_qp_index_offset < -12 || chroma_qp_index_offset > 12) return PCAMV_EINVAL;
+        (long long)mb_w * mb_h > (1 << 20) || slice_qp < 0 || slice_qp > 51 || chroma_qp_index_offset < -12 || chroma_qp_index_offset > 12 || (flags & ~1)) return PCAMV_EINVAL;
     mvsyntax::IDec D;
     D.b.d = rbsp; D.b.nbits = len * 8; D.b.pos = start_bit; D.b.overrun = 0;
     D.mb_w = mb_w; D.mb_h = mb_h; D.qp = slice_qp;
@@ -1076,13 +1205,21 @@ extern "C" int pcamv_gpu_decode_islice_cavlc(const uint8_t *rbsp, size_t len, si
     D.pl[0] = y; D.pl[1] = u; D.pl[2] = v;
     D.nz = (uint8_t *)calloc((size_t)mb_w * mb_h, 24);
     if (!D.nz) return PCAMV_ENOMEM;
+    D.flags = flags;
+    if (flags & 1) { D.modes = (uint8_t *)malloc((size_t)mb_w * mb_h * 16); if (!D.modes) { free(D.nz); return PCAMV_ENOMEM; } }
     const int rc = D.run();
-    free(D.nz);
+    free(D.nz); free(D.modes);
     return rc;
+}
+extern "C" int pcamv_gpu_decode_islice_cavlc(const uint8_t *rbsp, size_t len, size_t start_bit, int mb_w, int mb_h, int slice_qp, int chroma_qp_index_offset,
+                                             uint8_t *y, uint8_t *u, uint8_t *v)
+{
+    return pcamv_gpu_decode_islice_cavlc2(rbsp, len, start_bit, mb_w, mb_h, slice_qp, chroma_qp_index_offset, 0, y, u, v);
 }
 
 /* ---------------------------------------------------------------- the loop filter of such a picture (8.7): the definition
- * A frame picture of one slice, Intra16x16 macroblocks only, one QP, 4x4 transform, FilterOffsetA = FilterOffsetB = 0, filtered in place
+ * A frame picture of one slice, intra macroblocks only (Intra16x16 or, with the 4x4 transform, Intra4x4: bS is 4 on macroblock edges and
+ * 3 inside for both), one QP, 4x4 transform, FilterOffsetA = FilterOffsetB = 0, filtered in place
  * on tightly packed planes.  Sequential and naive, as the standard words it: macroblocks in raster order; per macroblock the four
  * vertical luma edges left to right, then the four horizontal ones top to bottom, chroma on luma edges 0 and 2 (its own edges 0 and 4);
  * bS 4 on a macroblock edge whose neighbour lies in the picture, 3 on the inner edges, an edge on the picture's border not filtered.
@@ -1173,14 +1310,16 @@ extern "C" int pcamv_gpu_deblock_intra_picture(uint8_t *y, uint8_t *u, uint8_t *
  * pcamv_gpu_decode_islice_cavlc as a picture of its own rows -- for whole-row slices exactly the availability of 7.4.1.2.1 and 9.2.1:
  * nothing above the slice's first row -- into the picture's planes; unless the idc is 1, the whole picture then goes through
  * pcamv_gpu_deblock_intra_picture (idc 0: slice edges are filtered as any macroblock edge; idc 2 is PCAMV_EUNSUP for more than one slice). */
-extern "C" int pcamv_gpu_decode_idr_picture(const uint8_t *bytes, size_t len, int mb_w, int mb_h, const pcamv_stream_params_t *params, int chroma_qp_index_offset,
-                                            uint8_t *y, uint8_t *u, uint8_t *v, int32_t *slice_qp, int32_t *idr_pic_id, int32_t *n_slices)
+/* ... picture2: flags as pcamv_gpu_decode_islice_cavlc2's, handed to every slice.  The loop filter needs nothing more: with the 4x4
+ * transform bS is 4 on macroblock edges and 3 inside for every intra macroblock, Intra4x4 as Intra16x16 */
+extern "C" int pcamv_gpu_decode_idr_picture2(const uint8_t *bytes, size_t len, int mb_w, int mb_h, const pcamv_stream_params_t *params, int chroma_qp_index_offset, int flags,
+                                             uint8_t *y, uint8_t *u, uint8_t *v, int32_t *slice_qp, int32_t *idr_pic_id, int32_t *n_slices)
 {
     if (slice_qp) *slice_qp = -1;
     if (idr_pic_id) *idr_pic_id = -1;
     if (n_slices) *n_slices = 0;
     if (!bytes || !y || !u || !v || !slice_qp || !idr_pic_id || !n_slices || !pcamv_stream_params_ok(params) || len < 1 || len > ((size_t)1 << 31) || mb_w < 1 ||
-        mb_h < 1 || mb_w > (1 << 16) || mb_h > (1 << 16) || (long long)mb_w * mb_h > (1 << 20)) return PCAMV_EINVAL;
+        mb_h < 1 || mb_w > (1 << 16) || mb_h > (1 << 16) || (long long)mb_w * mb_h > (1 << 20) || (flags & ~1)) return PCAMV_EINVAL;
     int64_t nu = 0, ns = 0;
     pcamv_gpu_annexb_index(bytes, len, NULL, 0, &nu, &ns);
     pcamv_unit_t *units = (pcamv_unit_t *)malloc((size_t)(nu ? nu : 1) * sizeof(pcamv_unit_t));
@@ -1215,8 +1354,8 @@ extern "C" int pcamv_gpu_decode_idr_picture(const uint8_t *bytes, size_t len, in
         rc = pcamv_gpu_nal_to_rbsp(bytes + units[sl[k].unit].off, (size_t)units[sl[k].unit].len, rbsp, &rl, NULL, NULL);
         /* rows r0 .. r1 - 1 as a picture of their own: tightly packed planes of the same width are those rows of the picture's planes; a
          * slice that holds more or fewer macroblocks than its rows fails the decoder's end-of-slice rule, which is how overlap and gap show */
-        if (!rc) rc = pcamv_gpu_decode_islice_cavlc(rbsp, rl, (size_t)sl[k].start_bit, mb_w, r1 - r0, qp, chroma_qp_index_offset,
-                                                    y + (size_t)16 * r0 * lw, u + (size_t)8 * r0 * cw, v + (size_t)8 * r0 * cw);
+        if (!rc) rc = pcamv_gpu_decode_islice_cavlc2(rbsp, rl, (size_t)sl[k].start_bit, mb_w, r1 - r0, qp, chroma_qp_index_offset, flags,
+                                                     y + (size_t)16 * r0 * lw, u + (size_t)8 * r0 * cw, v + (size_t)8 * r0 * cw);
         if (rc == PCAMV_EINVAL) rc = PCAMV_EUNSUP;             /* (the slices do not cover the picture as their first_mb says) */
     }
     if (!rc && idc != 1) rc = pcamv_gpu_deblock_intra_picture(y, u, v, mb_w, mb_h, qp, chroma_qp_index_offset);
@@ -1224,5 +1363,10 @@ extern "C" int pcamv_gpu_decode_idr_picture(const uint8_t *bytes, size_t len, in
     if (rc) return rc;
     *slice_qp = qp; *idr_pic_id = id; *n_slices = n;
     return 0;
+}
+extern "C" int pcamv_gpu_decode_idr_picture(const uint8_t *bytes, size_t len, int mb_w, int mb_h, const pcamv_stream_params_t *params, int chroma_qp_index_offset,
+                                            uint8_t *y, uint8_t *u, uint8_t *v, int32_t *slice_qp, int32_t *idr_pic_id, int32_t *n_slices)
+{
+    return pcamv_gpu_decode_idr_picture2(bytes, len, mb_w, mb_h, params, chroma_qp_index_offset, 0, y, u, v, slice_qp, idr_pic_id, n_slices);
 }
 #endif

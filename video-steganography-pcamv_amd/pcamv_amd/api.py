@@ -632,6 +632,9 @@ FEATURE_IDR_DEBLOCK = 0x2000    # ... and filtered there: the deblock keyword of
 FEATURE_IDR_SLICES = 0x4000     # ... in several slices of whole macroblock rows: the slice_rows keyword of the same calls, decode_idr_picture, parse_idr_slice_header3
 
 
+FEATURE_IDR_I4X4 = 0x8000       # ... with Intra4x4 macroblocks beside the Intra16x16 ones: the i4x4 keyword of the same calls and of the host decoders
+
+
 def write_idr_slice_header(params, nal_ref_idc, idr_pic_id, slice_qp, deblock=False, first_mb=0):
     """pcamv_gpu_write_idr_slice_header: (packed bytes, number of bits) of the header of an IDR I slice for a StreamParams -- which must
     say entropy_cabac 0 and deblocking_filter_control_present 1.  Raises PcamvError with the library's code (-1: a value out of range,
@@ -693,12 +696,13 @@ def parse_idr_slice_header3(rbsp, nal_header, params):
     return rc, sb.value, qp.value, pid.value, idc.value, first.value
 
 
-def decode_idr_picture(data, mb_w, mb_h, params=None, chroma_qp_index_offset=0):
+def decode_idr_picture(data, mb_w, mb_h, params=None, chroma_qp_index_offset=0, i4x4=False):
     """pcamv_gpu_decode_idr_picture: (return code, (Y, U, V), slice QP, idr_pic_id, number of slices) of the IDR picture whose slices are
     the type-5 units of the Annex B bytes `data`, one or several of whole macroblock rows, as the library's host decoder reconstructs it
     (filtered unless the slices say idc 1).  params: the StreamParams of the PPS the slices name (default: those Encoder.encode_idr
     writes under, pps_id 1).  The planes are None and the numbers -1 / 0 when the code is not 0 (-5: slices that are no whole rows, out
-    of order, overlapping, not covering the picture or disagreeing, or another VCL unit among them)"""
+    of order, overlapping, not covering the picture or disagreeing, or another VCL unit among them).  i4x4
+    (pcamv_gpu_decode_idr_picture2): Intra4x4 macroblocks are decoded too, where the default refuses them (-5)"""
     if params is None:
         params = StreamParams(**dict(IDR_PROBE_PARAMS, pps_id=1))
     buf = np.frombuffer(bytes(data), np.uint8) if len(data) else np.zeros(1, np.uint8)
@@ -708,6 +712,12 @@ def decode_idr_picture(data, mb_w, mb_h, params=None, chroma_qp_index_offset=0):
     qp, pid, ns = C.c_int32(), C.c_int32(), C.c_int32()
     fn = load_library().pcamv_gpu_decode_idr_picture
     fn.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    if i4x4:
+        fn = load_library().pcamv_gpu_decode_idr_picture2
+        fn.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                       C.POINTER(C.c_int32)]
+        rc = fn(_p(buf), len(data), int(mb_w), int(mb_h), C.byref(params), int(chroma_qp_index_offset), 1, *[_p(p) for p in planes], C.byref(qp), C.byref(pid), C.byref(ns))
+        return rc, (tuple(planes) if rc == 0 else None), qp.value, pid.value, ns.value
     rc = fn(_p(buf), len(data), int(mb_w), int(mb_h), C.byref(params), int(chroma_qp_index_offset), *[_p(p) for p in planes], C.byref(qp), C.byref(pid), C.byref(ns))
     return rc, (tuple(planes) if rc == 0 else None), qp.value, pid.value, ns.value
 
@@ -728,24 +738,30 @@ def deblock_intra_picture(planes, qp, chroma_qp_index_offset=0):
     return y, u, v
 
 
-def decode_islice_cavlc(rbsp, start_bit, mb_w, mb_h, slice_qp, chroma_qp_index_offset=0):
+def decode_islice_cavlc(rbsp, start_bit, mb_w, mb_h, slice_qp, chroma_qp_index_offset=0, i4x4=False):
     """pcamv_gpu_decode_islice_cavlc: (return code, (Y, U, V)) of the I slice data at bit start_bit of an RBSP -- Intra16x16 macroblocks,
-    CAVLC, one QP, no loop filter; the planes are None when the code is not 0"""
+    CAVLC, one QP, no loop filter; the planes are None when the code is not 0.  i4x4 (pcamv_gpu_decode_islice_cavlc2 with flags 1):
+    Intra4x4 macroblocks are decoded too, where the default refuses them (-5)"""
     buf = np.frombuffer(bytes(rbsp), np.uint8) if len(rbsp) else np.zeros(1, np.uint8)
     w, h = 16 * int(mb_w), 16 * int(mb_h)
     planes = [np.zeros(s, np.uint8) for s in ((h, w), (h // 2, w // 2), (h // 2, w // 2))] if 0 < mb_w <= 65536 and 0 < mb_h <= 65536 and mb_w * mb_h <= 1 << 20 else \
              [np.zeros((1, 1), np.uint8)] * 3
     fn = load_library().pcamv_gpu_decode_islice_cavlc
     fn.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    if i4x4:
+        fn = load_library().pcamv_gpu_decode_islice_cavlc2
+        fn.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        rc = fn(_p(buf), len(rbsp), int(start_bit), int(mb_w), int(mb_h), int(slice_qp), int(chroma_qp_index_offset), 1, *[_p(p) for p in planes])
+        return rc, (tuple(planes) if rc == 0 else None)
     rc = fn(_p(buf), len(rbsp), int(start_bit), int(mb_w), int(mb_h), int(slice_qp), int(chroma_qp_index_offset), *[_p(p) for p in planes])
     return rc, (tuple(planes) if rc == 0 else None)
 
 
-def decode_idr(unit, mb_w, mb_h, params=None, chroma_qp_index_offset=0):
+def decode_idr(unit, mb_w, mb_h, params=None, chroma_qp_index_offset=0, i4x4=False):
     """the picture of an IDR unit (start code optional) as the library's host decoder reconstructs it: (Y, U, V), and the slice QP and
     idr_pic_id its header states.  params: the StreamParams of the PPS the slice names (default: those Encoder.encode_idr writes under,
     with the unit's own pps_id).  A unit whose header does not say disable_deblocking_filter_idc 1 is filtered (deblock_intra_picture).
-    Raises PcamvError with the code of the step that failed"""
+    i4x4: Intra4x4 macroblocks are decoded too, as decode_islice_cavlc's.  Raises PcamvError with the code of the step that failed"""
     rbsp, ref_idc, typ = nal_to_rbsp(unit)
     if params is None:
         # the unit's pps_id: the third ue of the header (first_mb_in_slice, slice_type, pps_id)
@@ -764,7 +780,7 @@ def decode_idr(unit, mb_w, mb_h, params=None, chroma_qp_index_offset=0):
     rc, sb, qp, pid, idc = parse_idr_slice_header2(rbsp, ref_idc << 5 | typ, params)
     if rc:
         raise PcamvError(f"pcamv_gpu_parse_idr_slice_header failed: {rc}")
-    rc, planes = decode_islice_cavlc(rbsp, sb, mb_w, mb_h, qp, chroma_qp_index_offset)
+    rc, planes = decode_islice_cavlc(rbsp, sb, mb_w, mb_h, qp, chroma_qp_index_offset, i4x4)
     if rc:
         raise PcamvError(f"pcamv_gpu_decode_islice_cavlc failed: {rc}")
     if idc != 1:
@@ -1142,9 +1158,17 @@ class Encoder:
         self._chk(fn(self.ctx, ps, fs, n, _p(rc), _p(nb), _p(bits)), "slice_headers_write_device")
         return rc, nb, bits
 
-    def idr_bound(self, as_nal=True, slice_rows=0):
+    def idr_bound(self, as_nal=True, slice_rows=0, i4x4=0):
         """pcamv_gpu_idr_bound: a capacity under which no IDR picture of this size fails to be written; slice_rows
-        (pcamv_gpu_idr_bound3): ... in slices of that many macroblock rows"""
+        (pcamv_gpu_idr_bound3): ... in slices of that many macroblock rows; i4x4 (pcamv_gpu_idr_bound4): ... that may hold Intra4x4
+        macroblocks"""
+        if i4x4:
+            self.lib.pcamv_gpu_idr_bound4.restype = C.c_int64
+            self.lib.pcamv_gpu_idr_bound4.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+            n = self.lib.pcamv_gpu_idr_bound4(self.ctx, int(bool(as_nal)), int(slice_rows), int(i4x4))
+            if n < 0:
+                raise PcamvError(f"idr_bound4 failed ({n})")
+            return int(n)
         if slice_rows:
             self.lib.pcamv_gpu_idr_bound3.restype = C.c_int64
             self.lib.pcamv_gpu_idr_bound3.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -1159,7 +1183,7 @@ class Encoder:
             raise PcamvError(f"idr_bound failed ({n})")
         return int(n)
 
-    def encode_idr(self, qp, pps_id=1, idr_pic_id=0, as_nal=True, cap=None, deblock=False, slice_rows=0):
+    def encode_idr(self, qp, pps_id=1, idr_pic_id=0, as_nal=True, cap=None, deblock=False, slice_rows=0, i4x4=0):
         """pcamv_gpu_encode_idr: this context's current source coded on the device as one IDR I slice (Intra16x16, CAVLC, no loop filter),
         as bytes -- the unit with start code and emulation prevention, or with as_nal=False the RBSP.  The unfiltered reconstruction
         becomes the context's reference as after a host set_ref with no previous motion (fetch_recon, ref_planes show it).  The header
@@ -1167,11 +1191,17 @@ class Encoder:
         idr_bound); a unit that does not fit raises (-3).  deblock (pcamv_gpu_encode_idr2): the picture is filtered
         (deblock_intra_picture) before it becomes the reference, and its header says so; the slice data is the same.  slice_rows
         (pcamv_gpu_encode_idr3): the picture in slices of that many macroblock rows, their units behind each other (as_nal only);
-        0, or the picture's rows and more: one slice"""
+        0, or the picture's rows and more: one slice.  i4x4 (pcamv_gpu_encode_idr4): 1 codes a macroblock as Intra4x4 where that costs
+        less than Intra16x16, 2 every macroblock; decode_idr and decode_idr_picture read such pictures with i4x4=True"""
         if cap is None:
-            cap = self.idr_bound(as_nal, max(int(slice_rows), 0))
+            cap = self.idr_bound(as_nal, max(int(slice_rows), 0), i4x4 if i4x4 in (1, 2) else 0)
         out = np.zeros(max(int(cap), 1), np.uint8)
         n = C.c_size_t()
+        if i4x4:
+            fn = self.lib.pcamv_gpu_encode_idr4
+            fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+            self._chk(fn(self.ctx, int(qp), int(pps_id), int(idr_pic_id), int(bool(as_nal)), int(deblock), int(slice_rows), int(i4x4), _p(out), int(cap), C.byref(n)), "encode_idr4")
+            return bytes(out[:n.value])
         if slice_rows:
             fn = self.lib.pcamv_gpu_encode_idr3
             fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
@@ -1686,7 +1716,7 @@ class Batch:
         fn.argtypes = [C.c_void_p, C.c_void_p]
         self._slice_chk(fn(self.b, C.c_void_p(stream or None)), "batch_write_stream_step")
 
-    def write_stream_idr(self, qp, pps_id=1, idr_pic_id=0, stream=0, deblock=False, slice_rows=0):
+    def write_stream_idr(self, qp, pps_id=1, idr_pic_id=0, stream=0, deblock=False, slice_rows=0, i4x4=0):
         """pcamv_gpu_batch_write_stream_idr: every context's current source coded on the device as the IDR picture of its stream --
         picture 0, behind the head and before the first write_stream_step since the open, which must have first_pic 0 -- and its
         unfiltered reconstruction installed as the context's reference.  The IDR slices name the PPS pps_id, which the head must hold
@@ -1694,7 +1724,13 @@ class Batch:
         deblock (pcamv_gpu_batch_write_stream_idr2): every picture is filtered on the device (k_idr_deblock) before it becomes the
         reference, as the P pictures behind it are; that PPS then needs no deblocking control.  slice_rows
         (pcamv_gpu_batch_write_stream_idr3): every picture in slices of that many macroblock rows, their units back to back behind one
-        delimiter; stream_written()'s unit counter moves by their number"""
+        delimiter; stream_written()'s unit counter moves by their number.  i4x4 (pcamv_gpu_batch_write_stream_idr4): 1 codes a
+        macroblock as Intra4x4 where that costs less, 2 every macroblock (k_idr_mb4); the streams need room by idr_bound(.., i4x4)"""
+        if i4x4:
+            fn = self.lib.pcamv_gpu_batch_write_stream_idr4
+            fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+            self._slice_chk(fn(self.b, int(qp), int(pps_id), int(idr_pic_id), int(deblock), int(slice_rows), int(i4x4), C.c_void_p(stream or None)), "batch_write_stream_idr4")
+            return
         if slice_rows:
             fn = self.lib.pcamv_gpu_batch_write_stream_idr3
             fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
