@@ -761,7 +761,12 @@ int pcamv_gpu_write_slice_header(const pcamv_stream_params_t *params, const pcam
  * (encoder.c:159-169: 0 if 15 < qp + 2 * min(alpha, beta) of the two offsets below, else 1); aud 0 or 1.
  * Picture k of a stream (k = 0: the first write_stream_step after stream_open) has frame_num = (first_pic + k) mod 2^log2_max_frame_num,
  * poc_lsb = 2 (first_pic + k) mod 2^log2_max_poc_lsb, all POC deltas and redundant_pic_cnt 0 (encoder.c:1153-1158, 2282, 2306 for a
- * stream without B frames) and, for the CABAC writer's flush, i_frame = first_i_frame + k. */
+ * stream without B frames) and, for the CABAC writer's flush, i_frame = first_i_frame + k.
+ * The three deblocking members are written as given and change nothing in the chain: a closed-loop step always runs the loop filter at
+ * FilterOffsetA = FilterOffsetB = 0 and predicts the next picture from the filtered planes.  So only disable_deblocking_filter_idc -1, 0
+ * or 2 with both offsets 0 describe what the chain predicts from, and only such a stream decodes to it (one slice per picture: 2 filters
+ * as 0 does; -1 says 1 up to QP 15, where alpha and beta are 0 and the filter moves no sample).  With idc 1, or with an offset that is
+ * not 0, a decoder reconstructs other pictures than the sender's and drifts (tests/test_gpu_pslice_decode.py). */
 typedef struct pcamv_stream_write_t {
     int32_t nal_ref_idc, slice_type, first_pic, first_i_frame;
     int32_t disable_deblocking_filter_idc;

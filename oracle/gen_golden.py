@@ -243,6 +243,49 @@ def pslice_fixture(name, W, H, me, subme, qp, inter, seed, static, noise=6, fina
     print(name, len(data), "bytes of slice data,", d["nal_escapes"], "emulation prevention bytes,", dict(zip(*np.unique(mbs["type"], return_counts=True))))
 
 
+def pdec_fixture(name, case):
+    """what tests/pslice_decode.py is held to before it reads anything of the product's (tests/test_pslice_decode_ref.py): a --no-cabac
+    P picture as the reference codes it, its slice data, its record, and its reconstruction, which for an encoder is normatively
+    what a decoder of that slice arrives at.  First pass (final=False): --partitions all, the reconstruction of the analysis, which
+    runs no loop filter.  Final pass: the second pass with the embedding's flips and its planes before and after the loop filter,
+    with 16x16 partitions only: on the second partitions of 16x8 / 8x16 / P_8x8 macroblocks the reference's second pass is not
+    defined (tests/test_reference_pass2_quirks.py), and there its slice does not decode to its own reconstruction.  Refused, by the
+    reference's own output alone: a final pass without a flip; one whose forced P_Skip macroblocks keep a stale vector (DESIGN.md 5b:
+    the neighbours' mvd are then written against a vector that 8.4.1.1 does not infer); one the loop filter leaves unchanged, but at
+    QP 10.  Arrays only."""
+    import pdec_cases as pc
+    mbw, mbh, me, subme, qp, seed, static, noise, final = case
+    W, H = 16 * mbw, 16 * mbh
+    inter = (0x1 | 0x100) if final else 0x31
+    clip = pc.clip(case)
+    mvr = orc.level_mv_range(W, H)
+    r = refh.Ref(W, H, qp=qp, me=me, subme=subme, mv_range=mvr, cabac=0, embed=1, inter_flags=inter)
+    r.set_ref(*clip[0]); r.set_fenc(*clip[1])
+    mbs, rec = r.analyse_pframe(qp)
+    d = dict(mb_w=np.int32(mbw), mb_h=np.int32(mbh), qp=np.int32(qp), chroma_offset=np.int32(r.chroma_qp_offset), final=np.int32(final))
+    pre, post = rec, None
+    if final:
+        o = orc.Oracle(orc.make_params(W, H, me=me, subme=subme, mv_range=mvr, inter=inter & 0x31, cabac=0))
+        e = o.embed_pframe(mbs.view(orc.MB_DTYPE), 0.5)
+        o.close()
+        mbs, _, pre, post, _ = r.pass2_pframe((np.asarray(e["flip"]) == 1).astype(np.int8), qp)
+        d["flips"] = np.int32(e["num_flip"])
+        stale = int(((mbs["type"] == refh.P_SKIP) & (mbs["mv"][:, 0] != mbs["pskip_mv"]).any(1)).sum())
+        same = all(np.array_equal(a, b) for a, b in zip(pre, post))
+        if not e["num_flip"] or stale or (same and qp >= 16):
+            raise Refused(f"{name}: {e['num_flip']} flips, {stale} stale P_Skip vectors, the loop filter changed {'nothing' if same else 'something'}")
+    d.update(slice_data=np.frombuffer(r.slice_data(), np.uint8), type=mbs["type"], partition=mbs["partition"], sub_partition=mbs["sub_partition"],
+             mv=mbs["mv"])
+    for k, nm in enumerate("yuv"):
+        d[f"ref_{nm}"] = clip[0][k]
+        d[f"pre_{nm}"] = pre[k]
+        if post is not None:
+            d[f"post_{nm}"] = post[k]
+    path = os.path.join(OUT, name + ".npz")
+    np.savez_compressed(path, **d)
+    print(name, os.path.getsize(path), "bytes; types L0/8x8/skip", np.bincount(mbs["type"], minlength=7)[4:].tolist(), "flips", int(d.get("flips", 0)))
+
+
 class Refused(Exception):
     """a picture the I-slice recipe does not take: change the picture"""
 
@@ -277,6 +320,11 @@ if __name__ == "__main__":
         for case in isc.CASES:
             np.savez_compressed(isc.path(case), **islice_fixture_data(case))
             print(isc.name(case), os.path.getsize(isc.path(case)), "bytes")
+        sys.exit(0)
+    if "--pdec-only" in sys.argv:              # tests/pdec_cases.py: what the tests' P-slice decoder is held to
+        import pdec_cases as pc
+        for c in pc.REF_FIXTURES:
+            pdec_fixture(pc.name(c), c)
         sys.exit(0)
     if "--pslice-only" in sys.argv:
         pslice_fixture("pslice_qcif_hex_subme5_final", 176, 144, "hex", 5, 26, 0x1 | 0x100, 5, 48, final=True)

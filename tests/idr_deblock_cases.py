@@ -121,6 +121,49 @@ def restate(planes, qp, chroma_offset=0, order=None, edge_fn=None, census=None):
     return tuple(out)
 
 
+def restate_bs(planes, qp_mb, bs, chroma_offset=0, offset_a=0, offset_b=0, census=None):
+    """(Y, U, V) filtered, new arrays, with the boundary strengths given and not derived: the same lines, thresholds and order as
+    restate().  qp_mb [mb_h][mb_w]: QP_Y of every macroblock (an edge takes the average of its two sides, 8.7.2.2); bs[direction]
+    [4 * mb_h][4 * mb_w]: bS 0 .. 4 of the edge on the left (direction 0) or on top (direction 1) of every 4x4 luma block, the
+    picture's border never read; a chroma line takes the bS of the luma line it lies on (8.7.2).  offset_a / offset_b: FilterOffsetA
+    and FilterOffsetB.  census: a Counter that receives per piece of an edge ("bS", value, "macroblock" or "inner", "luma" or
+    "chroma"), per line ("line", "filtered" or "not filtered by threshold") and what _line counts"""
+    out = [np.ascontiguousarray(p, np.uint8).copy() for p in planes]
+    h, w = out[0].shape
+    mb_w, mb_h = w // 16, h // 16
+    census = collections.Counter() if census is None else census
+    flat = [p.reshape(-1) for p in out]
+    for my in range(mb_h):
+        for mx in range(mb_w):
+            for direction in (0, 1):
+                for e in range(4):
+                    if e == 0 and (my if direction else mx) == 0:
+                        continue
+                    qq = int(qp_mb[my][mx])
+                    qp_ = int(qp_mb[my - 1][mx] if direction else qp_mb[my][mx - 1]) if e == 0 else qq
+                    for c in range(3):
+                        if c and e & 1:
+                            continue
+                        n, pitch = (8, w // 2) if c else (16, w)
+                        step = 2 * e if c else 4 * e
+                        first = (n * my) * pitch + n * mx + step if direction == 0 else (n * my + step) * pitch + n * mx
+                        av = (chroma_qp(qp_, chroma_offset) + chroma_qp(qq, chroma_offset) + 1) >> 1 if c else (qp_ + qq + 1) >> 1
+                        ia, ib = _clip(av + offset_a, 0, 51), _clip(av + offset_b, 0, 51)
+                        for k in range(n):
+                            j = (2 * k if c else k) >> 2               # the 4x4 luma block along the edge
+                            s = int(bs[direction][4 * my + j][4 * mx + e] if direction == 0 else bs[direction][4 * my + e][4 * mx + j])
+                            if k % (2 if c else 4) == 0:
+                                census["bS", s, "inner" if e else "macroblock", "chroma" if c else "luma"] += 1
+                            if s == 0:
+                                continue
+                            key = ("chroma" if c else "luma") + f" bs{s} not filtered"
+                            before = census[key]
+                            _line(flat[c], first + k * (pitch if direction == 0 else 1), 1 if direction == 0 else pitch, s, bool(c), ALPHA[ia], BETA[ib],
+                                  TC0[ia][min(s, 3) - 1], census)
+                            census["line", "not filtered by threshold" if census[key] != before else "filtered"] += 1
+    return tuple(out)
+
+
 def census_missing(census):
     return [k for k in CLASSES if not census[k]]
 
