@@ -320,7 +320,10 @@ int  pcamv_gpu_batch_kernel_time(pcamv_batch_t *batch, const char *kernel, doubl
  * "k_idr_place", one lane per context placing its units; both are launched only for pictures of more than one slice, for which
  * "k_idr_prefix", "k_idr_pack" and "k_idr_unit" time the kernels that work per slice.
  * With PCAMV_FEATURE_IDR_I4X4, the 44th: "k_idr_mb4", which stands in k_idr_mb's place in a call with i4x4 != 0 -- its average is per
- * launch, and such a call launches it once per anti-diagonal x + 2 y of the picture. */
+ * launch, and such a call launches it once per anti-diagonal x + 2 y of the picture.
+ * With PCAMV_FEATURE_RATE, the 45th and 46th: "k_frame_qp", one wavefront per context putting the row of the context's QP in force into
+ * the descriptor just pushed -- launched behind a descriptor upload only while some context of the batch has a QP in force on the
+ * device --, and "k_rate_update", one lane per context, behind k_stream_commit while a rate is open. */
 const char *pcamv_gpu_batch_last_error(const pcamv_batch_t *batch);
 /* Closed loop on the device: with on != 0 every batch step ends with pass 2 + the loop filter (embedding must be
  * on: the flip map comes from it), leaving each context's deblocked reconstruction in its device planes
@@ -400,6 +403,7 @@ int pcamv_gpu_abi_version(void);
 #define PCAMV_FEATURE_IDR_DEBLOCK 0x2000u       /* ... and filtered there, as the stream's P pictures are (the *2 calls of that section) */
 #define PCAMV_FEATURE_IDR_SLICES 0x4000u        /* ... in several slices of whole macroblock rows, a wavefront per slice (the *3 calls of that section) */
 #define PCAMV_FEATURE_IDR_I4X4 0x8000u          /* ... with Intra4x4 macroblocks beside the Intra16x16 ones (the *4 calls of that section, the decoders that end in 2) */
+#define PCAMV_FEATURE_RATE 0x10000u     /* a QP per context, from the host or from device memory, and the rate controller on the device (the section on rate control at the end of this file) */
 unsigned pcamv_gpu_features(void);
 
 /* ---- Payload path: the caller's bits through the device-resident entry points, and back out on the device ----
@@ -1126,6 +1130,69 @@ int pcamv_gpu_decode_islice_cavlc(const uint8_t *rbsp, size_t len, size_t start_
 int pcamv_gpu_encode_idr(pcamv_ctx_t *ctx, int qp, int pps_id, int idr_pic_id, int as_nal, uint8_t *out, size_t cap, size_t *len);
 int64_t pcamv_gpu_idr_bound(const pcamv_ctx_t *ctx, int as_nal);
 int pcamv_gpu_batch_write_stream_idr(pcamv_batch_t *batch, int qp, int pps_id, int idr_pic_id, void *stream);
+
+/* ---- A QP per context, and rate control on the device (PCAMV_FEATURE_RATE) ----
+ * pcamv_gpu_batch_step_qps: pcamv_gpu_batch_step with context i at qp[i] (a host array of the batch's size).  Any QP outside 0 .. 51
+ * refuses the call (PCAMV_EINVAL) before anything is queued or any context has changed.  Nothing a batch chooses at its creation
+ * depends on a QP: the build of the RD instance, the speculative chain, the flow queues and the trellis states per thread follow the
+ * batch's size, the picture's width, the partitions and the search method alone, so contexts at different QPs share them.
+ *
+ * pcamv_gpu_batch_step_qp_device: the same with the QPs in device memory -- d_qp, int32 per context, borrowed for this call, read on
+ * `stream` by the first kernel the call queues and by nothing later; no host synchronisation.  A value outside 0 .. 51 is clamped
+ * before it indexes anything, and the context's status word says so (pcamv_gpu_batch_qp_status: 0 / PCAMV_EINVAL, of the last such
+ * step).  How it works: the batch keeps, made by its first such call and equal to the host path by construction, one table of 52 rows
+ * per distinct (i_chroma_qp_offset, i_luma_deadzone[0], i_luma_deadzone[1]) among its contexts (at most PCAMV_QP_TABLES_MAX, else
+ * PCAMV_EUNSUP) -- a row is exactly what a host step at that QP writes into the frame descriptor: qp, chroma_qp, lambda, lambda2,
+ * lambda2_chroma, the quantiser sets, and the pointers to the MV cost table and the slice-start context states -- and one copy of
+ * those two tables that its contexts share, held only for the QPs allowed: all 52 (3.4 MB) for a caller's array, qp_min .. qp_max for a
+ * rate (a later call that allows more makes them again for the union, behind a synchronisation).  k_frame_qp, queued behind the descriptor upload, copies each
+ * context's row into its pushed descriptor, a dword per lane; every later kernel sees the descriptor a host step would have pushed.
+ * The QP in force belongs to the CONTEXT: one device cell, written by the step.  While it is in force every descriptor push for the
+ * context -- by any batch it is a member of, its own one-context batch included: write_stream_step, write_step*, write_pslice*,
+ * pass2_pframe, extract_step -- is followed by the patch, so the calls behind such a step work at the step's QP.  It ends with the
+ * context's next step or analysis at a host QP, or when the batch whose tables it uses is destroyed (the context then stands at the
+ * QP of its last host step).  Probes that take a QP of their own (block_costs, rd_probe, encode_idr) keep theirs.
+ * pcamv_gpu_qp_device / pcamv_gpu_batch_qps read the cells back (synchronising): the QP in force, or -1 where none is.
+ *
+ * The controller.  pcamv_gpu_batch_rate_open on a batch with open byte streams (else PCAMV_EINVAL; bad parameters PCAMV_EINVAL with
+ * nothing opened; PCAMV_EUNSUP as above) gives every context a state on the device: qp = qp_init, debt = 0, last_len = the stream's
+ * length as it stands on `stream`, pictures = 0.  While the rate is open, pcamv_gpu_batch_write_stream_step and
+ * pcamv_gpu_batch_write_stream_idr* queue k_rate_update behind their k_stream_commit, and pcamv_gpu_batch_step_rate is
+ * pcamv_gpu_batch_step_qp_device on the controller's own cells (PCAMV_EINVAL without a rate): a sender's loop is step_rate;
+ * write_stream_step and nothing else.  An IDR picture's bytes count like any other's; its own QP stays the caller's argument.
+ * pcamv_gpu_batch_stream_open* under an open rate is refused (PCAMV_EINVAL): close the rate first.  A message and a rate do not know of
+ * each other.  pcamv_gpu_batch_rate_tell synchronises and copies the states out.
+ * The rule, in integers only so that host and device agree bit for bit (pcamv_gpu_rate_update is its definition, without a GPU;
+ * pcamv_gpu_rate_update_device runs n cases -- parameters, state, len and status of each -- through the kernel's code, one lane each).  With T = target_bits, W = window, len the
+ * stream's length in bytes behind the picture:
+ *   1. bits = 8 * clamp(len - last_len, 0, 2^41), then last_len = len;
+ *   2. a write status that is not 0 (the picture did not fit): d = +max_step, debt unchanged;
+ *   3. else debt = clamp(debt + bits - T, -2^40, 2^40);
+ *   4. want = max(T - debt / W, T / 4, 1), divisions as C makes them;
+ *   5. with P[0 .. 6] = {65536, 73562, 82570, 92682, 104032, 116772, 131072} (2^(k/6) in Q16): if bits >= want, d is the largest
+ *      k <= max_step with bits * 65536 >= want * P[k]; else d is minus the largest k <= max_step with want * 65536 >= bits * P[k]
+ *      (bits = 0: -max_step);
+ *   6. qp = clamp(qp + d, qp_min, qp_max), pictures += 1.
+ * Parameters: 1 <= target_bits <= 2^40, 0 <= qp_min <= qp_init <= qp_max <= 51, max_step 1 .. 6, window 1 .. 1024.
+ * This is the library's own controller, not x264's ratecontrol.c (float arithmetic over complexity estimates the chain does not have);
+ * nothing is claimed on how well it holds a bitrate on real content -- only the rule, and that device and host agree on it.
+ * Out of scope: a QP per macroblock (mb_qp_delta), VBV, and the IDR picture's QP. */
+#define PCAMV_QP_TABLES_MAX 8
+typedef struct pcamv_rate_params_t { int64_t target_bits; int32_t qp_init, qp_min, qp_max, max_step, window, reserved; } pcamv_rate_params_t;
+typedef struct pcamv_rate_state_t { int64_t debt, last_len, pictures; int32_t qp, last_d; } pcamv_rate_state_t;
+int pcamv_gpu_batch_step_qps(pcamv_batch_t *batch, const int32_t *qp, float emrate, void *stream);
+int pcamv_gpu_batch_step_qp_device(pcamv_batch_t *batch, const int32_t *d_qp, float emrate, void *stream);
+int pcamv_gpu_batch_qp_status(pcamv_batch_t *batch, int32_t *status);
+int pcamv_gpu_batch_qps(pcamv_batch_t *batch, int32_t *qp);
+int pcamv_gpu_qp_device(pcamv_ctx_t *ctx, int32_t *qp);
+int pcamv_gpu_batch_rate_open(pcamv_batch_t *batch, const pcamv_rate_params_t *params, void *stream);
+int pcamv_gpu_batch_rate_close(pcamv_batch_t *batch);
+int pcamv_gpu_batch_step_rate(pcamv_batch_t *batch, float emrate, void *stream);
+int pcamv_gpu_batch_rate_tell(pcamv_batch_t *batch, pcamv_rate_state_t *states);
+/* one picture through the rule: *state moves on, *d (optional) is the step.  PCAMV_EINVAL for parameters out of range (nothing changes) */
+int pcamv_gpu_rate_update(const pcamv_rate_params_t *params, pcamv_rate_state_t *state, int64_t len, int32_t write_status, int32_t *d);
+int pcamv_gpu_rate_update_device(pcamv_ctx_t *ctx, const pcamv_rate_params_t *params, pcamv_rate_state_t *states, const int64_t *len, const int32_t *write_status,
+                                 int n, int32_t *d);
 
 #ifdef __cplusplus
 }

@@ -17,6 +17,7 @@
 #include "pcamv_embed.hip.h"
 #include "pcamv_message.hip.h"
 #include "pcamv_slice.hip.h"
+#include "pcamv_rate.hip.h"
 #include "pcamv_host_tables.h"
 #include "pcamv_mvsyntax.h"
 #include "pcamv_param_sets_host.h"
@@ -45,14 +46,15 @@
     X(KT_VIDEO_CUT, "k_video_cut") X(KT_MESSAGE_COUNT, "k_message_count") X(KT_MESSAGE_PLAN, "k_message_plan") \
     X(KT_MESSAGE_JOBS, "k_message_jobs") X(KT_EXTRACT_CHAIN_MESSAGE, "k_extract_chain_message") X(KT_MESSAGE_CHECK, "k_message_check") \
     X(KT_IDR_MB, "k_idr_mb") X(KT_IDR_PREFIX, "k_idr_prefix") X(KT_IDR_PACK, "k_idr_pack") X(KT_IDR_UNIT, "k_idr_unit") \
-    X(KT_IDR_DEBLOCK, "k_idr_deblock") X(KT_IDR_UNIT_LEN, "k_idr_unit_len") X(KT_IDR_PLACE, "k_idr_place") X(KT_IDR_MB4, "k_idr_mb4")
+    X(KT_IDR_DEBLOCK, "k_idr_deblock") X(KT_IDR_UNIT_LEN, "k_idr_unit_len") X(KT_IDR_PLACE, "k_idr_place") X(KT_IDR_MB4, "k_idr_mb4") \
+    X(KT_FRAME_QP, "k_frame_qp") X(KT_RATE_UPDATE, "k_rate_update")
 #define KT_ENUM(id, name) id,
 enum { PCAMV_TIMERS(KT_ENUM) KT_N };
 #undef KT_ENUM
 #define PCAMV_FEATURES (PCAMV_FEATURE_PAYLOAD | PCAMV_FEATURE_SLICE_PARSER | PCAMV_FEATURE_SLICE_PARSER_CAVLC | PCAMV_FEATURE_SLICE_WRITER | \
                         PCAMV_FEATURE_SLICE_WRITER_CAVLC | PCAMV_FEATURE_NAL_DEVICE | PCAMV_FEATURE_STREAM_DEVICE | PCAMV_FEATURE_STREAM_WRITER | \
                         PCAMV_FEATURE_STREAM_WINDOW | PCAMV_FEATURE_PARAM_SETS | PCAMV_FEATURE_VIDEO | PCAMV_FEATURE_MESSAGE | PCAMV_FEATURE_IDR | \
-                        PCAMV_FEATURE_IDR_DEBLOCK | PCAMV_FEATURE_IDR_SLICES | PCAMV_FEATURE_IDR_I4X4)
+                        PCAMV_FEATURE_IDR_DEBLOCK | PCAMV_FEATURE_IDR_SLICES | PCAMV_FEATURE_IDR_I4X4 | PCAMV_FEATURE_RATE)
 #define MSG_GUARD_WORDS 4       /* words behind a batch's received stream that nothing may write */
 #define SLICE_GUARD_MBS 4       /* records behind a context's receive-side records that nothing may write (pcamv_gpu_debug_slice_records) */
 #define NSTAGE 2                /* staging buffers of extract_slices: a call waits for the one before the last */
@@ -233,6 +235,14 @@ struct pcamv_batch {
      * counts, the bit-string slots, the bit counts, the prefix and the RBSP --, per context a failure word, the slot's code and the probe's
      * {off, cap, len}, and the code tables */
     DevBuf<uint8_t> d_idr; int idr_group; DevBuf<uint8_t> d_idr_ctx, d_idr_tab;
+    /* a QP per context on the device (pcamv_rate.h), made by the batch's first device-QP step: the MV cost tables and the slice-start
+     * context states of the QPs allowed so far (qp_lo .. qp_hi), which its contexts share; a table of 52 rows per distinct (chroma offset, deadzones) among them, and
+     * which of these each context reads; NRING slots of n patch jobs beside the descriptors'; the caller's array during such a step */
+    DevBuf<int16_t> d_qp_cost; DevBuf<uint8_t> d_qp_cabac; DevBuf<uint32_t> d_qp_rows; std::vector<int> qp_table_of; int qp_lo, qp_hi;
+    PinBuf<QpJob> h_Q; DevBuf<QpJob> d_Q;
+    const int *qp_src;
+    /* the rate controller: its parameters, per context its state and the cell step_rate hands to the step */
+    int rate_open; pcamv_rate_params_t rate; DevBuf<pcamv_rate_state_t> d_rate; DevBuf<int> d_rate_qp;
     KTimer kt[KT_N];            /* the timed kernels; the events of a timer are made by its first launch */
     char err[256];
 };
@@ -269,6 +279,9 @@ struct pcamv_ctx {
     int rec_pristine;          /* F.rec / F.nnz hold the first pass' reconstruction of the frame last analysed (no second pass has run over it) */
     /* --subme >= 6 */
     uint8_t *d_cabac_init[52]; uint32_t *d_dbg_hash;
+    /* the QP in force on the device: the cell {qp, status of the step that set it}; while qp_rows is set, every push of this context's
+     * descriptor is patched from that table, which is qp_owner's */
+    int *d_qp_cell; const uint32_t *qp_rows; pcamv_batch *qp_owner;
     char err[256];
 };
 
@@ -364,6 +377,7 @@ extern "C" void pcamv_gpu_batch_destroy(pcamv_batch_t *b)
         if (!c) continue;
         if (c->last == b) c->last = NULL;
         if (c->win == b) c->win = NULL;
+        if (c->qp_owner == b) { c->qp_owner = NULL; c->qp_rows = NULL; }      /* its tables go: the context stands at the QP of its last host step */
         for (int k = 0; k < c->n_member; k++) if (c->member_of[k] == b) { c->member_of[k] = c->member_of[--c->n_member]; break; }
     }
     free(b->ctx);
@@ -656,6 +670,7 @@ static int ensure_qp(pcamv_ctx *c, int qp)
 {
     TRY(ensure_qp_tables(c, qp));
     frame_use_qp(c, &c->F, qp);
+    c->qp_rows = NULL; c->qp_owner = NULL;      /* a QP in force on the device ends here */
     return 0;
 }
 /* The frame descriptor of a probe (block_costs, rd_probe): a copy of the context's with the probe's QP, on the device for the probe's
@@ -756,10 +771,15 @@ static int stage_send(pcamv_batch *b, StageRing &R, int k, size_t total, hipStre
 /* the job arrays in front of a stream step's RBSP slots: [off n][len n][start_bit n] int64, [qp n][first n][frame_num n][nal_header n][entropy n] int32
  * (entropy: what k_slice_header_sets alone writes, the mode of the entry each header was read under) */
 static size_t stream_step_hdr(int n) { return ((size_t)n * (3 * 8 + 5 * 4) + 15) & ~(size_t)15; }
-/* take the next descriptor slot, fill it from the contexts' current FrameDev/EmbedDev and queue its upload */
+static void batch_push_qp(pcamv_batch *b, hipStream_t st, int slot);
+/* take the next descriptor slot, fill it from the contexts' current FrameDev/EmbedDev and queue its upload; where a context has a QP
+ * in force on the device, the patch behind it (batch_push_qp) */
 static int batch_push_descs(pcamv_batch *b, hipStream_t st, const FrameDev **dF, const EmbedDev **dE, int *slot_out)
 {
-    int slot;
+    int slot, patch = 0;
+    for (int i = 0; i < b->n && !patch; i++) patch = b->ctx[i]->qp_rows != NULL;
+    if (patch && !b->h_Q) TRY(b->h_Q.room(b, (size_t)b->n * NRING));          /* (before a slot is taken: a slot taken is a slot released by the caller) */
+    if (patch && !b->d_Q) TRY(b->d_Q.room(b, (size_t)b->n * NRING));
     TRY(ring_take(b, b->ring, &slot));
     FrameDev *hF = b->h_F + (size_t)slot * b->n; EmbedDev *hE = b->h_E + (size_t)slot * b->n;
     for (int i = 0; i < b->n; i++) { hF[i] = b->ctx[i]->F; hF[i].self = b->d_F + (size_t)slot * b->n + i; hE[i] = b->ctx[i]->E; }
@@ -767,6 +787,7 @@ static int batch_push_descs(pcamv_batch *b, hipStream_t st, const FrameDev **dF,
     HIPCHK(b, hipMemcpyAsync(b->d_F + (size_t)slot * b->n, hF, sizeof(FrameDev) * b->n, hipMemcpyHostToDevice, st));
     HIPCHK(b, hipMemcpyAsync(b->d_E + (size_t)slot * b->n, hE, sizeof(EmbedDev) * b->n, hipMemcpyHostToDevice, st));
     *dF = b->d_F + (size_t)slot * b->n; *dE = b->d_E + (size_t)slot * b->n; *slot_out = slot;
+    if (patch) batch_push_qp(b, st, slot);       /* (an upload that fails shows in the caller's launched(): the slot is handed out either way) */
     return 0;
 }
 
@@ -801,6 +822,19 @@ template <class Launch> static void timed(pcamv_batch *b, int k, hipStream_t st,
 template <class Kernel, class... Args> static void timed_kernel(pcamv_batch *b, int k, hipStream_t st, Kernel kernel, dim3 grid, dim3 block, const Args &... args)
 {
     timed(b, k, st, [&] { hipLaunchKernelGGL(kernel, grid, block, 0, st, args...); });
+}
+
+/* The patch behind the upload of descriptor slot `slot`: the jobs of the batch's contexts in the slot of their own ring (made once for
+ * good by the first push that needs it, batch_push_descs), then k_frame_qp.  A context without a QP in force has an empty job */
+static void batch_push_qp(pcamv_batch *b, hipStream_t st, int slot)
+{
+    QpJob *hQ = b->h_Q + (size_t)slot * b->n, *dQ = b->d_Q + (size_t)slot * b->n;
+    for (int i = 0; i < b->n; i++) {
+        const pcamv_ctx *c = b->ctx[i];
+        hQ[i].cell = c->qp_rows ? c->d_qp_cell : NULL; hQ[i].rows = c->qp_rows; hQ[i].src = c->qp_rows && b->qp_src ? b->qp_src + i : NULL;
+    }
+    hipMemcpyAsync(dQ, hQ, sizeof(QpJob) * b->n, hipMemcpyHostToDevice, st);
+    timed_kernel(b, KT_FRAME_QP, st, k_frame_qp, dim3((unsigned)b->n), dim3(64), b->d_F + (size_t)slot * b->n, (const QpJob *)dQ);
 }
 
 /* the second pass takes the frame's reconstruction as it stands: the first pass' own, once (then it has been filtered in place) */
@@ -1124,22 +1158,234 @@ extern "C" int pcamv_gpu_pass2_pframe(pcamv_ctx_t *c, const uint8_t *flips, int 
     return 0;
 }
 
-/* one step of every context of the batch on resident inputs: plane production + analysis + embedding */
-extern "C" int pcamv_gpu_batch_step(pcamv_batch_t *b, int qp, float emrate, void *stream)
+/* ---- a QP per context on the device (pcamv_rate.h, k_frame_qp) */
+/* The batch's tables for device QPs lo .. hi: the MV cost tables and (--subme >= 6) the slice-start context states of the QPs allowed
+ * only (a rate's qp_min .. qp_max; 0 .. 51 for a caller's array), built by the functions the per-context tables come from, and per
+ * distinct (chroma offset, deadzones) among the contexts 52 rows taken out of a descriptor that pcamv_frame_set_qp and the two pointers
+ * were written into -- what frame_use_qp does.  The row of a QP outside lo .. hi, which nothing allowed selects, points at the tables of
+ * the nearest QP inside, so that no row holds a pointer to nothing.  Allocates and copies: the first device-QP step or rate_open of a
+ * batch pays for it, and so does one that allows QPs the tables do not hold yet -- they are made again for the union, behind a
+ * synchronisation, and the contexts that read the old rows are pointed at the new ones */
+static int qp_tables_setup(pcamv_batch *b, int lo, int hi)
+{
+    if (b->d_qp_rows && b->qp_lo <= lo && hi <= b->qp_hi) return 0;
+    if (b->d_qp_rows) { lo = lo < b->qp_lo ? lo : b->qp_lo; hi = hi > b->qp_hi ? hi : b->qp_hi; }
+    const size_t held = (size_t)(hi - lo + 1);
+    const size_t cost_stride = (size_t)PCAMV_COST_MV_LEN + 1, cabac_stride = ((size_t)PCAMV_CHAIN_BYTES + 255) & ~(size_t)255;
+    static_assert((PCAMV_COST_MV_LEN + 1) % 2 == 0, "prim_mv_cost fetches the dword that holds an entry: every QP's table starts on one");
+    std::vector<int> of((size_t)b->n), first;
+    for (int i = 0; i < b->n; i++) {
+        const pcamv_params_t &p = b->ctx[i]->p;
+        size_t t = 0;
+        for (; t < first.size(); t++) {
+            const pcamv_params_t &q = b->ctx[first[t]]->p;
+            if (q.i_chroma_qp_offset == p.i_chroma_qp_offset && q.i_luma_deadzone[0] == p.i_luma_deadzone[0] && q.i_luma_deadzone[1] == p.i_luma_deadzone[1]) break;
+        }
+        if (t == first.size()) first.push_back(i);
+        of[(size_t)i] = (int)t;
+    }
+    if (first.size() > PCAMV_QP_TABLES_MAX)
+        return fail(b, PCAMV_EUNSUP, "the batch's contexts have %zu distinct (chroma offset, deadzones): at most %d row tables are kept", first.size(), PCAMV_QP_TABLES_MAX);
+    HostTmp<int16_t> h_cost(held * cost_stride);
+    HostTmp<uint8_t> h_cabac(held * cabac_stride);
+    HostTmp<uint32_t> h_rows(first.size() * QPROW_QPS * QPROW_DWORDS);
+    if (!h_cost || !h_cabac || !h_rows) return fail(b, PCAMV_ENOMEM, "the tables of QPs %d .. %d", lo, hi);
+    memset(h_cost, 0, held * cost_stride * sizeof(int16_t)); memset(h_cabac, 0, held * cabac_stride);
+    DevBuf<int16_t> d_cost; DevBuf<uint8_t> d_cabac; DevBuf<uint32_t> d_rows;
+    TRY(d_cost.room(b, held * cost_stride)); TRY(d_rows.room(b, first.size() * QPROW_QPS * QPROW_DWORDS));
+    if (b->b_mbrd) TRY(d_cabac.room(b, held * cabac_stride));
+    for (int qp = lo; qp <= hi; qp++) {
+        pcamv_build_cost_mv(qp, h_cost + (size_t)(qp - lo) * cost_stride);
+        if (b->b_mbrd) pcamv_build_cabac_init(qp, h_cabac + (size_t)(qp - lo) * cabac_stride);
+    }
+    for (int qp = 0; qp < QPROW_QPS; qp++) {
+        const size_t at = (size_t)((qp < lo ? lo : qp > hi ? hi : qp) - lo);       /* (the tables of this QP, or of the nearest one held) */
+        for (size_t t = 0; t < first.size(); t++) {
+            const pcamv_ctx *c = b->ctx[first[t]];
+            FrameDev F = c->F;
+            pcamv_frame_set_qp(&F, &c->p, qp);
+            F.cost_mv = d_cost + at * cost_stride + PCAMV_COST_MV_CENTRE;
+            if (F.b_mbrd) F.cabac_init = d_cabac + at * cabac_stride;
+            qprow_take(&F, h_rows + (t * QPROW_QPS + (size_t)qp) * QPROW_DWORDS);
+        }
+    }
+    HIPCHK(b, hipMemcpy(d_cost, h_cost, held * cost_stride * sizeof(int16_t), hipMemcpyHostToDevice));
+    if (b->b_mbrd) HIPCHK(b, hipMemcpy(d_cabac, h_cabac, held * cabac_stride, hipMemcpyHostToDevice));
+    HIPCHK(b, hipMemcpy(d_rows, h_rows, first.size() * QPROW_QPS * QPROW_DWORDS * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (b->d_qp_rows) HIPCHK(b, hipDeviceSynchronize());      /* (the tables before these are freed on return: work in flight may still read them) */
+    std::swap(b->d_qp_cost.p, d_cost.p); std::swap(b->d_qp_cost.cap, d_cost.cap);
+    std::swap(b->d_qp_cabac.p, d_cabac.p); std::swap(b->d_qp_cabac.cap, d_cabac.cap);
+    std::swap(b->d_qp_rows.p, d_rows.p); std::swap(b->d_qp_rows.cap, d_rows.cap);
+    b->qp_table_of.swap(of);
+    b->qp_lo = lo; b->qp_hi = hi;
+    for (int i = 0; i < b->n; i++)
+        if (b->ctx[i]->qp_owner == b && b->ctx[i]->qp_rows) b->ctx[i]->qp_rows = b->d_qp_rows + (size_t)b->qp_table_of[(size_t)i] * QPROW_QPS * QPROW_DWORDS;
+    return 0;
+}
+/* What context i of the batch needs before it can take its QP from its device cell: the cell (zeros), and a host descriptor that holds
+ * what its last host QP left -- QP 26 where there was none, so that it never holds a table pointer that is NULL.  Changes no mode */
+static int qp_device_prepare(pcamv_batch *b, int i)
+{
+    pcamv_ctx *c = b->ctx[i];
+    if (!c->d_qp_cell) { const int rc = ctx_alloc(c, &c->d_qp_cell, 2, 0); if (rc) return fail(b, rc, "%s", c->err); }
+    if (!c->F.cost_mv) {
+        const uint32_t *rows = c->qp_rows; pcamv_batch *owner = c->qp_owner;
+        const int rc = ensure_qp(c, 26);
+        c->qp_rows = rows; c->qp_owner = owner;
+        if (rc) return fail(b, rc, "%s", c->err);
+    }
+    return 0;
+}
+/* ... and from here on (until ensure_qp) it does */
+static void qp_device_enter(pcamv_batch *b, int i)
+{
+    pcamv_ctx *c = b->ctx[i];
+    c->qp_rows = b->d_qp_rows + (size_t)b->qp_table_of[(size_t)i] * QPROW_QPS * QPROW_DWORDS; c->qp_owner = b;
+}
+
+/* one step of every context of the batch on resident inputs: plane production + analysis + embedding.  The QPs: qps[i] (host), else
+ * d_qp[i] (device, borrowed for the call; its values lie within lo .. hi or are clamped to 0 .. 51), else qp_all.  A device-QP step
+ * changes the contexts' mode only once nothing of its preparation can fail any more, and puts it back if its launches fail: no context
+ * is left reading a cell that no step has written */
+static int batch_step_at(pcamv_batch_t *b, int qp_all, const int32_t *qps, const int32_t *d_qp, float emrate, void *stream, int lo = 0, int hi = QPROW_QPS - 1)
 {
     if (!b) return PCAMV_EINVAL;
     HIPCHK(b, hipSetDevice(b->device));
     TRY(batch_live(b));
+    if (qps) for (int i = 0; i < b->n; i++) if (qps[i] < 0 || qps[i] > 51) return fail(b, PCAMV_EINVAL, "qp %d of context %d out of range", qps[i], i);
+    if (d_qp) TRY(qp_tables_setup(b, lo, hi));
+    for (int i = 0; d_qp && i < b->n; i++) {
+        TRY(qp_device_prepare(b, i));
+        if (!b->ctx[i]->F.raw[0]) return fail(b, PCAMV_EINVAL, "context %d has no reference", i);
+    }
+    std::vector<std::pair<const uint32_t *, pcamv_batch *>> was;
+    for (int i = 0; d_qp && i < b->n; i++) was.push_back({b->ctx[i]->qp_rows, b->ctx[i]->qp_owner});
     for (int i = 0; i < b->n; i++) {
         pcamv_ctx *c = b->ctx[i];
-        int rc = ensure_qp(c, qp);
-        if (rc) return fail(b, rc, "%s", c->err);
+        if (d_qp) qp_device_enter(b, i);
+        else {
+            int rc = ensure_qp(c, qps ? qps[i] : qp_all);
+            if (rc) return fail(b, rc, "%s", c->err);
+        }
         if (!c->F.raw[0]) return fail(b, PCAMV_EINVAL, "context %d has no reference", i);
         c->F.embed = emrate > 0; c->E.emrate = emrate; c->E.user_message = NULL; c->E.user_message_len = 0;
         c->F.flip = c->d_flip; c->F.mbflip = c->d_mbflip;        /* a closed-loop step applies the flip map of its own embedding stage, never a caller's map left by pass2_pframe */
     }
     hipStream_t st = stream ? (hipStream_t)stream : b->ctx[0]->stream;
-    return batch_launch(b, ST_PLANES | ST_ANALYSE | (emrate > 0 ? ST_EMBED : 0) | (b->closed_loop ? ST_PASS2 : 0), st);
+    b->qp_src = d_qp;           /* (the step's own push takes the caller's values into the cells; later pushes read the cells) */
+    const int rc = batch_launch(b, ST_PLANES | ST_ANALYSE | (emrate > 0 ? ST_EMBED : 0) | (b->closed_loop ? ST_PASS2 : 0), st);
+    b->qp_src = NULL;
+    if (rc) for (size_t i = 0; i < was.size(); i++) { b->ctx[i]->qp_rows = was[i].first; b->ctx[i]->qp_owner = was[i].second; }
+    return rc;
+}
+extern "C" int pcamv_gpu_batch_step(pcamv_batch_t *b, int qp, float emrate, void *stream) { return batch_step_at(b, qp, NULL, NULL, emrate, stream); }
+extern "C" int pcamv_gpu_batch_step_qps(pcamv_batch_t *b, const int32_t *qp, float emrate, void *stream)
+{
+    if (!b || !qp) return PCAMV_EINVAL;
+    return batch_step_at(b, 0, qp, NULL, emrate, stream);
+}
+extern "C" int pcamv_gpu_batch_step_qp_device(pcamv_batch_t *b, const int32_t *d_qp, float emrate, void *stream)
+{
+    if (!b || !d_qp) return PCAMV_EINVAL;
+    return batch_step_at(b, 0, NULL, d_qp, emrate, stream);
+}
+/* synchronises: word `w` of every context's cell (0: the QP in force, 1: the status of the step that set it), `none` where no QP is in force */
+static int qp_cells_fetch(pcamv_batch *b, int w, int none, int32_t *out)
+{
+    if (!b || !out) return PCAMV_EINVAL;
+    HIPCHK(b, hipSetDevice(b->device));
+    TRY(batch_live(b));
+    HIPCHK(b, hipDeviceSynchronize());
+    for (int i = 0; i < b->n; i++) {
+        out[i] = none;
+        if (b->ctx[i]->qp_rows) HIPCHK(b, hipMemcpy(&out[i], b->ctx[i]->d_qp_cell + w, sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+extern "C" int pcamv_gpu_batch_qp_status(pcamv_batch_t *b, int32_t *status) { return qp_cells_fetch(b, 1, 0, status); }
+extern "C" int pcamv_gpu_batch_qps(pcamv_batch_t *b, int32_t *qp) { return qp_cells_fetch(b, 0, -1, qp); }
+extern "C" int pcamv_gpu_qp_device(pcamv_ctx_t *c, int32_t *qp)
+{
+    if (!c || !qp) return PCAMV_EINVAL;
+    return on_behalf(c, c->self, qp_cells_fetch(c->self, 0, -1, qp));
+}
+
+/* ---- the rate controller (pcamv_rate.h: pcamv_rate_step is the rule; k_rate_update) */
+extern "C" int pcamv_gpu_rate_update(const pcamv_rate_params_t *params, pcamv_rate_state_t *state, int64_t len, int32_t write_status, int32_t *d)
+{
+    if (!params || !state || !pcamv_rate_params_ok(params)) return PCAMV_EINVAL;
+    const int step = pcamv_rate_step(params, state, (long long)len, write_status);
+    if (d) *d = step;
+    return 0;
+}
+extern "C" int pcamv_gpu_rate_update_device(pcamv_ctx_t *c, const pcamv_rate_params_t *params, pcamv_rate_state_t *states, const int64_t *len,
+                                            const int32_t *write_status, int n, int32_t *d)
+{
+    if (!c || !params || !states || !len || !write_status || !d || n < 1 || n > (1 << 24)) return PCAMV_EINVAL;
+    for (int i = 0; i < n; i++) if (!pcamv_rate_params_ok(&params[i])) return fail(c, PCAMV_EINVAL, "rate_update_device: the parameters of case %d are out of range", i);
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBuf<pcamv_rate_params_t> d_p; DevBuf<pcamv_rate_state_t> d_s; DevBuf<long long> d_len; DevBuf<int> d_int;
+    TRY(d_p.room(c, (size_t)n)); TRY(d_s.room(c, (size_t)n)); TRY(d_len.room(c, (size_t)n)); TRY(d_int.room(c, 2 * (size_t)n));
+    HIPCHK(c, hipMemcpy(d_p, params, sizeof(*params) * (size_t)n, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_s, states, sizeof(*states) * (size_t)n, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_len, len, 8 * (size_t)n, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_int, write_status, 4 * (size_t)n, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemset(d_int + n, 0xA5, 4 * (size_t)n));
+    hipLaunchKernelGGL(k_rate_cases, dim3((n + 63) / 64), dim3(64), 0, c->stream, (const pcamv_rate_params_t *)d_p, d_s.p, (const long long *)d_len, (const int *)d_int, n, d_int + n);
+    TRY(launched(c));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(states, d_s, sizeof(*states) * (size_t)n, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(d, d_int + n, 4 * (size_t)n, hipMemcpyDeviceToHost));
+    return 0;
+}
+/* the launch of k_rate_update over the batch's streams as they stand on `st`: behind an open, or behind a k_stream_commit */
+static void rate_launch(pcamv_batch *b, int open, hipStream_t st)
+{
+    RateJobs J;
+    J.P = b->rate; J.state = b->d_rate; J.qp = b->d_rate_qp; J.ctx = (const SwsCtx *)b->so.d_own.p; J.status = b->d_wstat; J.n = b->n; J.open = open;
+    timed_kernel(b, KT_RATE_UPDATE, st, k_rate_update, dim3((b->n + 63) / 64), dim3(64), J);
+}
+extern "C" int pcamv_gpu_batch_rate_open(pcamv_batch_t *b, const pcamv_rate_params_t *params, void *stream)
+{
+    if (!b || !params) return PCAMV_EINVAL;
+    HIPCHK(b, hipSetDevice(b->device));
+    TRY(batch_live(b));
+    if (!pcamv_rate_params_ok(params))
+        return fail(b, PCAMV_EINVAL, "rate_open: target_bits 1 .. 2^40, 0 <= qp_min <= qp_init <= qp_max <= 51, max_step 1 .. 6, window 1 .. 1024");
+    if (!b->so.ready) return fail(b, PCAMV_EINVAL, "rate_open: no byte streams were opened on this batch yet (pcamv_gpu_batch_stream_open)");
+    if (b->rate_open) HIPCHK(b, hipDeviceSynchronize());       /* (a re-open: the states are written again, and work in flight may still read them) */
+    b->rate_open = 0;
+    TRY(qp_tables_setup(b, params->qp_min, params->qp_max));
+    TRY(b->d_rate.room(b, (size_t)b->n)); TRY(b->d_rate_qp.room(b, (size_t)b->n));
+    if (!b->d_wstat) TRY(b->d_wstat.room(b, (size_t)b->n));
+    b->rate = *params;
+    rate_launch(b, 1, stream ? (hipStream_t)stream : b->ctx[0]->stream);
+    TRY(launched(b));
+    b->rate_open = 1;
+    return 0;
+}
+extern "C" int pcamv_gpu_batch_rate_close(pcamv_batch_t *b)
+{
+    if (!b) return PCAMV_EINVAL;
+    if (!b->rate_open) return fail(b, PCAMV_EINVAL, "rate_close: no rate is open on this batch");
+    b->rate_open = 0;           /* (the states stay where they are: steps in flight read the cells) */
+    return 0;
+}
+extern "C" int pcamv_gpu_batch_step_rate(pcamv_batch_t *b, float emrate, void *stream)
+{
+    if (!b) return PCAMV_EINVAL;
+    if (!b->rate_open) return fail(b, PCAMV_EINVAL, "step_rate: no rate is open on this batch (pcamv_gpu_batch_rate_open)");
+    return batch_step_at(b, 0, NULL, b->d_rate_qp, emrate, stream, b->rate.qp_min, b->rate.qp_max);
+}
+/* synchronises */
+extern "C" int pcamv_gpu_batch_rate_tell(pcamv_batch_t *b, pcamv_rate_state_t *states)
+{
+    if (!b || !states) return PCAMV_EINVAL;
+    if (!b->rate_open) return fail(b, PCAMV_EINVAL, "rate_tell: no rate is open on this batch");
+    HIPCHK(b, hipSetDevice(b->device));
+    HIPCHK(b, hipDeviceSynchronize());
+    HIPCHK(b, hipMemcpy(states, b->d_rate, sizeof(*states) * (size_t)b->n, hipMemcpyDeviceToHost));
+    return 0;
 }
 extern "C" int pcamv_gpu_step_device(pcamv_ctx_t *c, int qp, float emrate, void *stream)
 {
@@ -2586,6 +2832,7 @@ static int write_run(pcamv_batch *b, WriteJobs J, const pcamv_slice_hdr_t *hdrs,
         if (cavlc) timed(b, KT_WRITE_PSLICE_CAVLC, st, [&] { pcamv_launch_write_pslice_cavlc((unsigned)b->n, st, dF, J); });
         else timed(b, KT_WRITE_PSLICE, st, [&] { pcamv_launch_write_pslice((unsigned)b->n, st, dF, J); });
         if (sw) timed_kernel(b, KT_STREAM_COMMIT, st, k_stream_commit, dim3((b->n + 63) / 64), dim3(64), *sw);
+        if (sw && b->rate_open) rate_launch(b, 0, st);
         rc = launched(b);
         if (!rc) rc = ring_release(b, b->ring, slot, st);
     }
@@ -2754,6 +3001,7 @@ extern "C" int pcamv_gpu_batch_stream_open(pcamv_batch_t *b, void *bytes, size_t
     if (ok == PCAMV_EUNSUP) return fail(b, ok, "weighted prediction: the header writer has no pred_weight_table");
     if (ok) return fail(b, ok, wr->nal_ref_idc == 0 ? "nal_ref_idc 0: in this path a chain's P frame is the next one's reference" :
                                "stream_open: parameter sets or stream settings out of range");
+    if (b->rate_open) return fail(b, PCAMV_EINVAL, "a rate is open on this batch's streams: pcamv_gpu_batch_rate_close first");
     StreamOut &O = b->so;
     O.ready = 0; O.joined = 0; O.stepped = 0;
     hipStream_t st = stream ? (hipStream_t)stream : b->ctx[0]->stream;
@@ -2811,6 +3059,7 @@ extern "C" int pcamv_gpu_batch_stream_open_heads(pcamv_batch_t *b, void *bytes, 
     if (ok == PCAMV_EUNSUP) return fail(b, ok, "weighted prediction: the header writer has no pred_weight_table");
     if (ok) return fail(b, ok, wr->nal_ref_idc == 0 ? "nal_ref_idc 0: in this path a chain's P frame is the next one's reference" :
                                "stream_open_heads: parameter sets or stream settings out of range");
+    if (b->rate_open) return fail(b, PCAMV_EINVAL, "a rate is open on this batch's streams: pcamv_gpu_batch_rate_close first");
     StreamOut &O = b->so;
     O.ready = 0; O.joined = 0; O.stepped = 0;
     hipStream_t st = stream ? (hipStream_t)stream : b->ctx[0]->stream;
@@ -3145,6 +3394,7 @@ extern "C" int pcamv_gpu_batch_write_stream_idr4(pcamv_batch_t *b, int qp, int p
     O.stepped = 1;
     TRY(idr_run(b, J, SJ.ctx, st, shdr));
     timed_kernel(b, KT_STREAM_COMMIT, st, k_stream_commit, dim3((b->n + 63) / 64), dim3(64), SJ);
+    if (b->rate_open) rate_launch(b, 0, st);
     return launched(b);
 }
 extern "C" int pcamv_gpu_batch_write_stream_idr3(pcamv_batch_t *b, int qp, int pps_id, int idr_pic_id, int deblock, int slice_rows, void *stream)

@@ -802,6 +802,41 @@ def param_set_head_idr(params, mb_w, mb_h, idr_pps_id=1, sps_id=0, num_ref_frame
     return param_set_head(params, mb_w, mb_h, sps_id, num_ref_frames, profile_idc, level_idc) + again[pps:], second
 
 
+FEATURE_RATE = 0x10000          # a QP per context (Batch.step(qps=...), Batch.step_qp_device) and the rate controller on the device (Batch.rate_open, Batch.step_rate, rate_update)
+
+
+class RateParams(C.Structure):
+    """pcamv_rate_params_t: target_bits per picture, qp_init within [qp_min, qp_max], max_step 1 .. 6, window 1 .. 1024"""
+    _fields_ = [("target_bits", C.c_int64), ("qp_init", C.c_int32), ("qp_min", C.c_int32), ("qp_max", C.c_int32), ("max_step", C.c_int32),
+                ("window", C.c_int32), ("reserved", C.c_int32)]
+
+    def __init__(self, target_bits, qp_init=26, qp_min=0, qp_max=51, max_step=2, window=8):
+        super().__init__(int(target_bits), int(qp_init), int(qp_min), int(qp_max), int(max_step), int(window), 0)
+
+
+RATE_STATE_DTYPE = np.dtype([("debt", np.int64), ("last_len", np.int64), ("pictures", np.int64), ("qp", np.int32), ("last_d", np.int32)])      # pcamv_rate_state_t
+
+
+def rate_state(params, last_len=0):
+    """a controller's state as rate_open leaves it: one record of RATE_STATE_DTYPE"""
+    s = np.zeros(1, RATE_STATE_DTYPE)
+    s["qp"], s["last_len"] = params.qp_init, last_len
+    return s
+
+
+def rate_update(params, state, length, write_status=0):
+    """pcamv_gpu_rate_update, the controller's rule without a GPU: one picture -- the stream's length in bytes behind it and its write
+    status -- moves `state` (one record of RATE_STATE_DTYPE, in place) on; returns d.  Raises for parameters out of range"""
+    lib = load_library()
+    fn = lib.pcamv_gpu_rate_update
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
+    d = C.c_int32()
+    rc = fn(C.byref(params), _p(state), int(length), int(write_status), C.byref(d))
+    if rc:
+        raise PcamvError(f"rate_update failed ({rc}): parameters out of range")
+    return d.value
+
+
 def features():
     """pcamv_gpu_features: mask of FEATURE_* the loaded library has"""
     lib = load_library()
@@ -1113,6 +1148,24 @@ class Encoder:
         out["guard"] = int(at[-1])
         return out
 
+    def qp_device(self):
+        """the QP in force on the device for this context (a device-QP step set it), or -1; synchronises"""
+        q = C.c_int32()
+        self._chk(self.lib.pcamv_gpu_qp_device(self.ctx, C.byref(q)), "qp_device")
+        return q.value
+
+    def rate_update_device(self, params, states, lengths, write_status):
+        """pcamv_gpu_rate_update_device: n cases of (RateParams, state record, length, status) through k_rate_update's code, one lane
+        each; returns (states after, d)"""
+        n = len(params)
+        P = (RateParams * n)(*params)
+        st = np.ascontiguousarray(states, RATE_STATE_DTYPE).copy()
+        ln, ws, d = np.ascontiguousarray(lengths, np.int64), np.ascontiguousarray(write_status, np.int32), np.zeros(n, np.int32)
+        fn = self.lib.pcamv_gpu_rate_update_device
+        fn.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_void_p]
+        self._chk(fn(self.ctx, P, _p(st), _p(ln), _p(ws), n, _p(d)), "rate_update_device")
+        return st, d
+
     def slice_headers_device(self, data, off, length, nal_header, params):
         """pcamv_gpu_slice_headers_device: the P slice headers of the RBSPs data[off[i] : off[i] + length[i]] read by k_slice_header,
         one lane each -- the parity probe of Batch.extract_stream_step's header stage; (return codes, start bits, QPs, frame_nums) as
@@ -1374,10 +1427,69 @@ class Batch:
         self.lib.pcamv_gpu_batch_destroy.restype = None
         self.lib.pcamv_gpu_batch_destroy.argtypes = [C.c_void_p]
 
-    def step(self, qp, emrate, stream=0):
+    def step(self, qp=None, emrate=None, stream=0, qps=None):
+        """one step of every context at `qp`, or with qps=[...] context i at qps[i] (step_qps); emrate is required"""
+        if (qp is None) == (qps is None) or emrate is None:
+            raise PcamvError("batch.step takes a QP or qps=[...], one of the two, and an emrate")
+        if qps is not None:
+            return self.step_qps(qps, emrate, stream)
         rc = self.lib.pcamv_gpu_batch_step(self.b, qp, C.c_float(emrate), C.c_void_p(stream or None))
         if rc:
             raise PcamvError(f"batch_step failed ({rc}): {self.lib.pcamv_gpu_batch_last_error(self.b).decode()}")
+
+    def _rate_chk(self, rc, what):
+        if rc:
+            raise PcamvError(f"{what} failed ({rc}): {self.lib.pcamv_gpu_batch_last_error(self.b).decode()}")
+
+    def step_qps(self, qps, emrate, stream=0):
+        """pcamv_gpu_batch_step_qps: step() with context i at qps[i]; any QP outside 0 .. 51 refuses the call with nothing queued"""
+        q = np.ascontiguousarray(qps, np.int32)
+        if q.shape != (len(self.encs),):
+            raise PcamvError("one QP per context of the batch")
+        fn = self.lib.pcamv_gpu_batch_step_qps
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
+        self._rate_chk(fn(self.b, _p(q), C.c_float(emrate), C.c_void_p(stream or None)), "batch_step_qps")
+
+    def step_qp_device(self, d_qp, emrate, stream=0):
+        """pcamv_gpu_batch_step_qp_device: step() with the QPs in an int32 device tensor, borrowed for the call and read on `stream`; no
+        host sync.  Values outside 0 .. 51 are clamped (qp_status()).  The QPs stay in force for the calls behind the step"""
+        if not _is_device_tensor(d_qp) or not d_qp.is_cuda or d_qp.element_size() != 4 or d_qp.is_floating_point() or not d_qp.is_contiguous() or d_qp.numel() != len(self.encs):
+            raise PcamvError("the QPs are a contiguous int32 device tensor, one per context")
+        fn = self.lib.pcamv_gpu_batch_step_qp_device
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
+        self._rate_chk(fn(self.b, C.c_void_p(d_qp.data_ptr()), C.c_float(emrate), C.c_void_p(stream or None)), "batch_step_qp_device")
+
+    def qp_status(self):
+        """per context: 0, or -1 (EINVAL) where the last device-QP step clamped its value; synchronises"""
+        out = np.zeros(len(self.encs), np.int32)
+        self._rate_chk(self.lib.pcamv_gpu_batch_qp_status(self.b, _p(out)), "batch_qp_status")
+        return out
+
+    def qps(self):
+        """per context: the QP in force on the device, -1 where none is; synchronises"""
+        out = np.zeros(len(self.encs), np.int32)
+        self._rate_chk(self.lib.pcamv_gpu_batch_qps(self.b, _p(out)), "batch_qps")
+        return out
+
+    def rate_open(self, params, stream=0):
+        """pcamv_gpu_batch_rate_open: a controller per context of a batch with open streams (RateParams); afterwards a sender's loop is
+        step_rate(); write_stream_step()"""
+        self._rate_chk(self.lib.pcamv_gpu_batch_rate_open(self.b, C.byref(params), C.c_void_p(stream or None)), "batch_rate_open")
+
+    def rate_close(self):
+        self._rate_chk(self.lib.pcamv_gpu_batch_rate_close(self.b), "batch_rate_close")
+
+    def step_rate(self, emrate, stream=0):
+        """step_qp_device on the controller's own cells"""
+        fn = self.lib.pcamv_gpu_batch_step_rate
+        fn.argtypes = [C.c_void_p, C.c_float, C.c_void_p]
+        self._rate_chk(fn(self.b, C.c_float(emrate), C.c_void_p(stream or None)), "batch_step_rate")
+
+    def rate_tell(self):
+        """the controllers' states, one record of RATE_STATE_DTYPE per context; synchronises"""
+        out = np.zeros(len(self.encs), RATE_STATE_DTYPE)
+        self._rate_chk(self.lib.pcamv_gpu_batch_rate_tell(self.b, _p(out)), "batch_rate_tell")
+        return out
 
     def set_closed_loop(self, on=True):
         if self.lib.pcamv_gpu_batch_set_closed_loop(self.b, int(on)):
