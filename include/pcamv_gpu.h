@@ -323,7 +323,8 @@ int  pcamv_gpu_batch_kernel_time(pcamv_batch_t *batch, const char *kernel, doubl
  * launch, and such a call launches it once per anti-diagonal x + 2 y of the picture.
  * With PCAMV_FEATURE_RATE, the 45th and 46th: "k_frame_qp", one wavefront per context putting the row of the context's QP in force into
  * the descriptor just pushed -- launched behind a descriptor upload only while some context of the batch has a QP in force on the
- * device --, and "k_rate_update", one lane per context, behind k_stream_commit while a rate is open. */
+ * device --, and "k_rate_update", one lane per context, behind k_stream_commit while a rate is open.
+ * With PCAMV_FEATURE_SOURCE, the 47th: "k_source_feed", one launch per pcamv_gpu_batch_feed_device call and none otherwise. */
 const char *pcamv_gpu_batch_last_error(const pcamv_batch_t *batch);
 /* Closed loop on the device: with on != 0 every batch step ends with pass 2 + the loop filter (embedding must be
  * on: the flip map comes from it), leaving each context's deblocked reconstruction in its device planes
@@ -404,6 +405,7 @@ int pcamv_gpu_abi_version(void);
 #define PCAMV_FEATURE_IDR_SLICES 0x4000u        /* ... in several slices of whole macroblock rows, a wavefront per slice (the *3 calls of that section) */
 #define PCAMV_FEATURE_IDR_I4X4 0x8000u          /* ... with Intra4x4 macroblocks beside the Intra16x16 ones (the *4 calls of that section, the decoders that end in 2) */
 #define PCAMV_FEATURE_RATE 0x10000u     /* a QP per context, from the host or from device memory, and the rate controller on the device (the section on rate control at the end of this file) */
+#define PCAMV_FEATURE_SOURCE 0x20000u   /* the sender takes a video: pictures of any even size fed to all contexts of a batch out of a clip in device memory, and parameter sets that say how to crop them (the last section of this file) */
 unsigned pcamv_gpu_features(void);
 
 /* ---- Payload path: the caller's bits through the device-resident entry points, and back out on the device ----
@@ -1193,6 +1195,79 @@ int pcamv_gpu_batch_rate_tell(pcamv_batch_t *batch, pcamv_rate_state_t *states);
 int pcamv_gpu_rate_update(const pcamv_rate_params_t *params, pcamv_rate_state_t *state, int64_t len, int32_t write_status, int32_t *d);
 int pcamv_gpu_rate_update_device(pcamv_ctx_t *ctx, const pcamv_rate_params_t *params, pcamv_rate_state_t *states, const int64_t *len, const int32_t *write_status,
                                  int n, int32_t *d);
+
+/* ---- The sender takes a video: pictures of any size, fed to all contexts on the device (PCAMV_FEATURE_SOURCE) ----
+ * A context codes pictures of whole macroblocks (pcamv_gpu_open: width and height multiples of 16).  A source picture is width x height
+ * luma samples, both even, with 16 (mb_w - 1) < width <= 16 mb_w and the same for the height, in 4:2:0: three planes (I420; YV12 with
+ * planes 1 and 2 swapped, frame.c:206) or a luma plane and one plane of chroma pairs (NV12: U in the even bytes, V in the odd ones;
+ * NV21 the other way round), lines top-down or bottom-up (PCAMV_SRC_VFLIP, as X264_CSP_VFLIP, frame.c:211-215).  A clip is a byte
+ * range that holds pictures picture_stride bytes apart; plane k of a picture starts plane_off[k] bytes behind the picture's start and
+ * its lines lie pitch[k] bytes apart (NV12 / NV21: two planes, the third entry is not looked at).  Nothing is asked of the alignment of
+ * pitches, offsets or the clip's base.
+ * The rule (x264_frame_copy_picture, then x264_frame_expand_border_mod16, common/frame.c:190-220 and 310-337): coded plane i, of
+ * (16 mb_w >> !!i) x (16 mb_h >> !!i) samples, tightly packed, is
+ *     out_i[y][x] = src_i[min(y, h_i - 1)][min(x, w_i - 1)],   w_i = width >> !!i, h_i = height >> !!i
+ * -- the last real sample of a line repeated to the right, the last real line repeated downwards; with VFLIP src_i's line y is the
+ * caller's line h_i - 1 - y.
+ * pcamv_gpu_source_check validates a descriptor against a size in macroblocks and gives the number of whole pictures a clip of
+ * clip_bytes holds: every byte a picture index below that number reads lies inside the clip, and no byte is read that the rule does
+ * not name (bytes between a line's end and the next line, or between planes, may be unmapped).  PCAMV_EINVAL: an odd size, a size
+ * outside the macroblock grid, a pitch below a line's bytes (width for luma and for a plane of pairs, width / 2 for a planar chroma
+ * plane), an unknown format or flag, a negative offset, picture_stride < 1, or an offset, pitch or picture_stride above 2^40.
+ * pcamv_gpu_source_picture is the definition, sequential and naive: picture `picture` of a host clip into out[3] (PCAMV_EINVAL also
+ * for an index outside 0 .. n_pictures - 1).  pcamv_gpu_upload_picture runs it into a staging buffer and then does what
+ * pcamv_gpu_upload_fenc does: a host caller gets the same rule, and it is the parity probe beside the kernel.
+ *
+ * pcamv_gpu_batch_feed_device: one launch of k_source_feed over all contexts of the batch, queued on `stream` (NULL: the first
+ * context's), no host synchronisation: context i gets picture d_picture[i] (device int64, one per context) of the clip at d_clip
+ * (device memory, clip_bytes long), padded, into its own source planes -- the ones pcamv_gpu_upload_fenc fills -- and stands as
+ * pcamv_gpu_upload_fenc leaves a context: the planes are its source (a pcamv_gpu_set_fenc_device before is undone, one after takes over
+ * again), and a second pass re-encodes every macroblock.  Clip and indices are borrowed until the queued work has run; the caller moves
+ * the indices on with a device add, and a sender's loop is feed; step_rate; write_stream_step.  Ordering is the caller's: whatever
+ * writes d_picture or the clip must be ordered against `stream` -- queue the add on the stream handed to this call, and the calls that
+ * read the source (the step, write_stream_idr) on it too; with stream == NULL the feed runs on the first context's own stream, which is
+ * non-blocking (the null stream orders nothing against it) and which the caller cannot name: synchronise before the call then.  An index outside 0 .. n_pictures - 1
+ * gives that context the status PCAMV_EINVAL (pcamv_gpu_batch_feed_status, which synchronises; 0 otherwise, and 0 before any feed) and
+ * nothing of its planes is written; the others are unaffected.  A descriptor pcamv_gpu_source_check refuses for the contexts' size
+ * refuses the call with nothing queued.  The batch's first feed makes, once for good, the table of its contexts' plane addresses and
+ * the status words.
+ * The kernel: a wavefront per (context, macroblock row of luma | macroblock row of both chroma planes); the destination bytes of such
+ * a work item are one contiguous span of a tight plane, stored 16 bytes a lane (8 in chroma rows of an odd mb_w, which are only 8-byte
+ * aligned), 64 lanes side by side; loads are as wide as the source address allows at run time (the source tells 16, 8, 4, 2 and 1
+ * bytes apart; in the gfx950 code object the 4- and 2-byte cases are unaligned 8- and 16-byte loads, which the hardware serves); a
+ * chunk that crosses the picture's right edge is read byte by byte.
+ *
+ * pcamv_gpu_param_set_head2: pcamv_gpu_param_set_head for a picture of width x height samples, both even (else PCAMV_EINVAL):
+ * mb_w = (width + 15) / 16, mb_h likewise; frame_cropping_flag 1 iff a size is no multiple of 16, with frame_crop_right_offset
+ * (16 mb_w - width) / 2, frame_crop_bottom_offset (16 mb_h - height) / 2, left and top 0 (encoder/set.c:139-143, 275-281).  For sizes
+ * that are multiples of 16 the bytes are pcamv_gpu_param_set_head's.  A receiver reads the size back from the SPS (pcamv_gpu_parse_sps:
+ * 16 mb_w - 2 (crop_left + crop_right) by 16 mb_h - 2 (crop_top + crop_bottom)); pcamv_param_sets_t and the device-side receiver need
+ * the size in macroblocks only and stay as they are.
+ * Out of scope: RGB, 4:2:2 and 4:4:4 input (the reference refuses them too, frame.c:194), interlaced pictures. */
+#define PCAMV_SRC_I420 0
+#define PCAMV_SRC_YV12 1
+#define PCAMV_SRC_NV12 2
+#define PCAMV_SRC_NV21 3
+#define PCAMV_SRC_VFLIP 1
+typedef struct pcamv_source_t {
+    int32_t width, height;     /* the picture's own luma size: even, 16 (mb_w - 1) < width <= 16 mb_w, the same for height */
+    int32_t format;            /* PCAMV_SRC_I420 | PCAMV_SRC_YV12 | PCAMV_SRC_NV12 | PCAMV_SRC_NV21 */
+    int32_t flags;             /* PCAMV_SRC_VFLIP: lines bottom-up */
+    int64_t plane_off[3];      /* byte offset of each plane inside one picture (NV12 / NV21: two planes) */
+    int64_t pitch[3];          /* bytes between lines, > 0, at least a line's bytes */
+    int64_t picture_stride;    /* bytes between pictures of the clip */
+} pcamv_source_t;
+int pcamv_gpu_source_check(const pcamv_source_t *src, size_t clip_bytes, int mb_w, int mb_h, int64_t *n_pictures);
+int pcamv_gpu_source_picture(const pcamv_source_t *src, const uint8_t *clip, size_t clip_bytes, int64_t picture, int mb_w, int mb_h, uint8_t *const out[3]);
+int pcamv_gpu_upload_picture(pcamv_ctx_t *ctx, const pcamv_source_t *src, const uint8_t *clip, size_t clip_bytes, int64_t picture);
+int pcamv_gpu_batch_feed_device(pcamv_batch_t *batch, const void *d_clip, int64_t clip_bytes, const pcamv_source_t *src, const int64_t *d_picture, void *stream);
+int pcamv_gpu_batch_feed_status(pcamv_batch_t *batch, int32_t *status);
+int pcamv_gpu_param_set_head2(const pcamv_stream_params_t *params, int width, int height, int sps_id, int num_ref_frames, int profile_idc, int level_idc,
+                              uint8_t *out, size_t cap, size_t *len);
+/* diagnostics (tests): the context's own source planes, whole, into out[3] (tight, the coded size), and in *guard_intact (optional)
+ * whether the PCAMV_SRC_GUARD bytes behind each of them still hold what pcamv_gpu_open wrote there.  Synchronises */
+#define PCAMV_SRC_GUARD 64
+int pcamv_gpu_debug_fetch_fenc(pcamv_ctx_t *ctx, uint8_t *const out[3], int *guard_intact);
 
 #ifdef __cplusplus
 }

@@ -18,6 +18,7 @@
 #include "pcamv_message.hip.h"
 #include "pcamv_slice.hip.h"
 #include "pcamv_rate.hip.h"
+#include "pcamv_source.hip.h"
 #include "pcamv_host_tables.h"
 #include "pcamv_mvsyntax.h"
 #include "pcamv_param_sets_host.h"
@@ -47,14 +48,15 @@
     X(KT_MESSAGE_JOBS, "k_message_jobs") X(KT_EXTRACT_CHAIN_MESSAGE, "k_extract_chain_message") X(KT_MESSAGE_CHECK, "k_message_check") \
     X(KT_IDR_MB, "k_idr_mb") X(KT_IDR_PREFIX, "k_idr_prefix") X(KT_IDR_PACK, "k_idr_pack") X(KT_IDR_UNIT, "k_idr_unit") \
     X(KT_IDR_DEBLOCK, "k_idr_deblock") X(KT_IDR_UNIT_LEN, "k_idr_unit_len") X(KT_IDR_PLACE, "k_idr_place") X(KT_IDR_MB4, "k_idr_mb4") \
-    X(KT_FRAME_QP, "k_frame_qp") X(KT_RATE_UPDATE, "k_rate_update")
+    X(KT_FRAME_QP, "k_frame_qp") X(KT_RATE_UPDATE, "k_rate_update") X(KT_SOURCE_FEED, "k_source_feed")
 #define KT_ENUM(id, name) id,
 enum { PCAMV_TIMERS(KT_ENUM) KT_N };
 #undef KT_ENUM
 #define PCAMV_FEATURES (PCAMV_FEATURE_PAYLOAD | PCAMV_FEATURE_SLICE_PARSER | PCAMV_FEATURE_SLICE_PARSER_CAVLC | PCAMV_FEATURE_SLICE_WRITER | \
                         PCAMV_FEATURE_SLICE_WRITER_CAVLC | PCAMV_FEATURE_NAL_DEVICE | PCAMV_FEATURE_STREAM_DEVICE | PCAMV_FEATURE_STREAM_WRITER | \
                         PCAMV_FEATURE_STREAM_WINDOW | PCAMV_FEATURE_PARAM_SETS | PCAMV_FEATURE_VIDEO | PCAMV_FEATURE_MESSAGE | PCAMV_FEATURE_IDR | \
-                        PCAMV_FEATURE_IDR_DEBLOCK | PCAMV_FEATURE_IDR_SLICES | PCAMV_FEATURE_IDR_I4X4 | PCAMV_FEATURE_RATE)
+                        PCAMV_FEATURE_IDR_DEBLOCK | PCAMV_FEATURE_IDR_SLICES | PCAMV_FEATURE_IDR_I4X4 | PCAMV_FEATURE_RATE | PCAMV_FEATURE_SOURCE)
+#define SRC_GUARD_BYTE 0xC3     /* what the PCAMV_SRC_GUARD bytes behind a context's source planes hold */
 #define MSG_GUARD_WORDS 4       /* words behind a batch's received stream that nothing may write */
 #define SLICE_GUARD_MBS 4       /* records behind a context's receive-side records that nothing may write (pcamv_gpu_debug_slice_records) */
 #define NSTAGE 2                /* staging buffers of extract_slices: a call waits for the one before the last */
@@ -243,6 +245,9 @@ struct pcamv_batch {
     const int *qp_src;
     /* the rate controller: its parameters, per context its state and the cell step_rate hands to the step */
     int rate_open; pcamv_rate_params_t rate; DevBuf<pcamv_rate_state_t> d_rate; DevBuf<int> d_rate_qp;
+    /* the source feed (pcamv_source.h), made by the batch's first feed: the addresses of its contexts' source planes, [n][3], and a
+     * status word per context */
+    DevBuf<uint8_t *> d_src_planes; DevBuf<int> d_src_status;
     KTimer kt[KT_N];            /* the timed kernels; the events of a timer are made by its first launch */
     char err[256];
 };
@@ -577,7 +582,8 @@ static int open_impl(pcamv_ctx *c, const pcamv_params_t *p, int device)
     const size_t ysz = (size_t)F.w * F.h, lsz = (size_t)F.plane_size, csz = (size_t)F.cstride * F.clines, n_mb = (size_t)F.n_mb;
     EmbedDev &E = c->E;
     for (int i = 0; i < 3; i++) {
-        TRY(ctx_alloc(c, &c->d_fenc[i], i ? ysz / 4 : ysz));
+        TRY(ctx_alloc(c, &c->d_fenc[i], (i ? ysz / 4 : ysz) + PCAMV_SRC_GUARD));     /* (guard bytes behind the plane: pcamv_gpu_debug_fetch_fenc) */
+        HIPCHK(c, hipMemset(c->d_fenc[i] + (i ? ysz / 4 : ysz), SRC_GUARD_BYTE, PCAMV_SRC_GUARD));
         TRY(ctx_alloc(c, &c->d_raw[i], i ? ysz / 4 : ysz));
         TRY(ctx_alloc(c, &F.rec[i], i ? ysz / 4 : ysz));
         F.fenc[i] = c->d_fenc[i]; F.raw[i] = c->d_raw[i];
@@ -1387,6 +1393,98 @@ extern "C" int pcamv_gpu_batch_rate_tell(pcamv_batch_t *b, pcamv_rate_state_t *s
     HIPCHK(b, hipMemcpy(states, b->d_rate, sizeof(*states) * (size_t)b->n, hipMemcpyDeviceToHost));
     return 0;
 }
+/* ---- the source feed (pcamv_source.h, k_source_feed) */
+extern "C" int pcamv_gpu_source_check(const pcamv_source_t *src, size_t clip_bytes, int mb_w, int mb_h, int64_t *n_pictures)
+{
+    long long n = 0;
+    if (n_pictures) *n_pictures = 0;
+    if (clip_bytes > ((size_t)1 << 62)) return PCAMV_EINVAL;
+    const int rc = src_check(src, (long long)clip_bytes, mb_w, mb_h, &n);
+    if (!rc && n_pictures) *n_pictures = n;
+    return rc;
+}
+extern "C" int pcamv_gpu_source_picture(const pcamv_source_t *src, const uint8_t *clip, size_t clip_bytes, int64_t picture, int mb_w, int mb_h, uint8_t *const out[3])
+{
+    int64_t n = 0;
+    if (!clip || !out || !out[0] || !out[1] || !out[2]) return PCAMV_EINVAL;
+    TRY(pcamv_gpu_source_check(src, clip_bytes, mb_w, mb_h, &n));
+    if (picture < 0 || picture >= n) return PCAMV_EINVAL;
+    src_picture_naive(src, clip + picture * src->picture_stride, mb_w, mb_h, out);
+    return 0;
+}
+extern "C" int pcamv_gpu_upload_picture(pcamv_ctx_t *c, const pcamv_source_t *src, const uint8_t *clip, size_t clip_bytes, int64_t picture)
+{
+    if (!c || !src || !clip) return PCAMV_EINVAL;
+    const size_t ysz = (size_t)c->F.w * c->F.h;
+    HostTmp<uint8_t> tmp(ysz + ysz / 2);
+    if (!tmp) return fail(c, PCAMV_ENOMEM, "upload_picture: the staging planes");
+    uint8_t *const out[3] = {tmp, tmp + ysz, tmp + ysz + ysz / 4};
+    if (pcamv_gpu_source_picture(src, clip, clip_bytes, picture, c->F.mb_w, c->F.mb_h, out))
+        return fail(c, PCAMV_EINVAL, "upload_picture: the source does not describe pictures of this context's %d x %d macroblocks, or picture %lld is not inside the clip",
+                    c->F.mb_w, c->F.mb_h, (long long)picture);
+    const int stride[3] = {c->F.w, c->F.w / 2, c->F.w / 2};
+    return pcamv_gpu_upload_fenc(c, out, stride);
+}
+extern "C" int pcamv_gpu_batch_feed_device(pcamv_batch_t *b, const void *d_clip, int64_t clip_bytes, const pcamv_source_t *src, const int64_t *d_picture, void *stream)
+{
+    if (!b || !d_clip || !src || !d_picture) return PCAMV_EINVAL;
+    HIPCHK(b, hipSetDevice(b->device));
+    TRY(batch_live(b));
+    const FrameDev &F = b->ctx[0]->F;
+    SrcFeed J;
+    J.S = *src; J.clip = (const uint8_t *)d_clip; J.picture = (const long long *)d_picture; J.mb_w = F.mb_w; J.mb_h = F.mb_h; J.n = b->n;
+    if (clip_bytes < 0 || src_check(src, clip_bytes, F.mb_w, F.mb_h, &J.n_pictures))
+        return fail(b, PCAMV_EINVAL, "feed: the source does not describe pictures of %d x %d macroblocks (even sizes inside the last macroblock, pitches of a line at least, offsets >= 0)", F.mb_w, F.mb_h);
+    const long long blocks = (long long)b->n * src_items(F.mb_h);
+    if (blocks >= (1LL << 26)) return fail(b, PCAMV_EUNSUP, "feed: %lld work items in one launch (a launch of 64-lane blocks holds fewer than 2^26)", blocks);
+    if (!b->d_src_planes) {         /* once for good: the planes are the contexts' own from open to close */
+        std::vector<uint8_t *> h((size_t)b->n * 3);
+        for (int i = 0; i < b->n; i++) for (int k = 0; k < 3; k++) h[(size_t)i * 3 + k] = b->ctx[i]->d_fenc[k];
+        TRY(b->d_src_status.room(b, (size_t)b->n));
+        HIPCHK(b, hipMemset(b->d_src_status, 0, sizeof(int) * (size_t)b->n));
+        DevBuf<uint8_t *> d; TRY(d.room(b, h.size()));
+        HIPCHK(b, hipMemcpy(d, h.data(), sizeof(uint8_t *) * h.size(), hipMemcpyHostToDevice));
+        std::swap(b->d_src_planes.p, d.p); std::swap(b->d_src_planes.cap, d.cap);
+    }
+    J.planes = b->d_src_planes; J.status = b->d_src_status;
+    hipStream_t st = stream ? (hipStream_t)stream : b->ctx[0]->stream;
+    timed_kernel(b, KT_SOURCE_FEED, st, k_source_feed, dim3((unsigned)blocks), dim3(64), J);
+    TRY(launched(b));
+    for (int i = 0; i < b->n; i++) {
+        pcamv_ctx *c = b->ctx[i];
+        for (int k = 0; k < 3; k++) c->F.fenc[k] = c->d_fenc[k];
+        drop_rec_reuse(c);          /* a new source: a second pass re-encodes every macroblock on it */
+    }
+    return 0;
+}
+/* synchronises */
+extern "C" int pcamv_gpu_batch_feed_status(pcamv_batch_t *b, int32_t *status)
+{
+    if (!b || !status) return PCAMV_EINVAL;
+    HIPCHK(b, hipSetDevice(b->device));
+    HIPCHK(b, hipDeviceSynchronize());
+    if (!b->d_src_status) { memset(status, 0, sizeof(int32_t) * (size_t)b->n); return 0; }
+    HIPCHK(b, hipMemcpy(status, b->d_src_status, sizeof(int32_t) * (size_t)b->n, hipMemcpyDeviceToHost));
+    return 0;
+}
+extern "C" int pcamv_gpu_debug_fetch_fenc(pcamv_ctx_t *c, uint8_t *const out[3], int *guard_intact)
+{
+    if (!c || !out || !out[0] || !out[1] || !out[2]) return PCAMV_EINVAL;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipDeviceSynchronize());
+    const size_t ysz = (size_t)c->F.w * c->F.h;
+    int intact = 1;
+    for (int i = 0; i < 3; i++) {
+        const size_t sz = i ? ysz / 4 : ysz;
+        uint8_t g[PCAMV_SRC_GUARD];
+        HIPCHK(c, hipMemcpy(out[i], c->d_fenc[i], sz, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(g, c->d_fenc[i] + sz, PCAMV_SRC_GUARD, hipMemcpyDeviceToHost));
+        for (int k = 0; k < PCAMV_SRC_GUARD; k++) if (g[k] != SRC_GUARD_BYTE) intact = 0;
+    }
+    if (guard_intact) *guard_intact = intact;
+    return 0;
+}
+
 extern "C" int pcamv_gpu_step_device(pcamv_ctx_t *c, int qp, float emrate, void *stream)
 {
     if (!c) return PCAMV_EINVAL;
@@ -2506,8 +2604,9 @@ extern "C" int pcamv_gpu_write_pps(const pcamv_pps_t *pps, uint8_t *rbsp, size_t
     return 0;
 }
 extern "C" int pcamv_gpu_rbsp_to_nal(const uint8_t *rbsp, size_t len, int nal_ref_idc, int nal_unit_type, uint8_t *nal, size_t cap, size_t *nal_len);
-extern "C" int pcamv_gpu_param_set_head(const pcamv_stream_params_t *params, int mb_w, int mb_h, int sps_id, int num_ref_frames, int profile_idc, int level_idc,
-                                        uint8_t *out, size_t cap, size_t *len)
+/* crop_right / crop_bottom: luma samples of the coded picture that are not the picture's, both even */
+static int param_set_head_at(const pcamv_stream_params_t *params, int mb_w, int mb_h, int crop_right, int crop_bottom, int sps_id, int num_ref_frames, int profile_idc,
+                             int level_idc, uint8_t *out, size_t cap, size_t *len)
 {
     if (len) *len = 0;
     if (!params || !len || (!out && cap) || !sws_params_ok(*params)) return PCAMV_EINVAL;
@@ -2518,6 +2617,7 @@ extern "C" int pcamv_gpu_param_set_head(const pcamv_stream_params_t *params, int
     S.log2_max_frame_num = P.log2_max_frame_num; S.poc_type = P.poc_type; S.log2_max_poc_lsb = P.poc_type == 0 ? P.log2_max_poc_lsb : 0;
     S.delta_pic_order_always_zero = P.poc_type == 1 ? !!P.delta_pic_order_always_zero : 0;
     S.num_ref_frames = num_ref_frames; S.mb_w = mb_w; S.mb_h = mb_h; S.frame_mbs_only = 1; S.direct_8x8_inference = 1;
+    S.frame_cropping = crop_right || crop_bottom; S.crop_right = crop_right / 2; S.crop_bottom = crop_bottom / 2;       /* (set.c:139-143, 275-281) */
     pcamv_pps_t Q = pcamv_pps_t();
     Q.pps_id = P.pps_id; Q.sps_id = sps_id; Q.entropy_cabac = !!P.entropy_cabac; Q.pic_order_present = !!P.pic_order_present; Q.num_slice_groups = 1;
     Q.num_ref_idx_l0_default = P.num_ref_idx_l0_default; Q.num_ref_idx_l1_default = 1; Q.weighted_pred = !!P.weighted_pred;
@@ -2532,6 +2632,19 @@ extern "C" int pcamv_gpu_param_set_head(const pcamv_stream_params_t *params, int
     TRY(pcamv_gpu_rbsp_to_nal(rp, (size_t)np, 3, 8, out + a, cap - a, &c2));
     *len = a + c2;
     return 0;
+}
+extern "C" int pcamv_gpu_param_set_head(const pcamv_stream_params_t *params, int mb_w, int mb_h, int sps_id, int num_ref_frames, int profile_idc, int level_idc,
+                                        uint8_t *out, size_t cap, size_t *len)
+{
+    return param_set_head_at(params, mb_w, mb_h, 0, 0, sps_id, num_ref_frames, profile_idc, level_idc, out, cap, len);
+}
+extern "C" int pcamv_gpu_param_set_head2(const pcamv_stream_params_t *params, int width, int height, int sps_id, int num_ref_frames, int profile_idc, int level_idc,
+                                         uint8_t *out, size_t cap, size_t *len)
+{
+    if (len) *len = 0;
+    if (width < 2 || height < 2 || (width & 1) || (height & 1) || width > 16 * SRC_DIM_MAX || height > 16 * SRC_DIM_MAX) return PCAMV_EINVAL;
+    const int mb_w = (width + 15) / 16, mb_h = (height + 15) / 16;
+    return param_set_head_at(params, mb_w, mb_h, 16 * mb_w - width, 16 * mb_h - height, sps_id, num_ref_frames, profile_idc, level_idc, out, cap, len);
 }
 extern "C" int pcamv_gpu_debug_slice_records(pcamv_ctx_t *c, pcamv_mb_t *out_mb, int *guard_intact)
 {

@@ -607,16 +607,22 @@ def write_pps(pps):
     return _write_set("pcamv_gpu_write_pps", pps)
 
 
-def param_set_head(params, mb_w, mb_h, sps_id=0, num_ref_frames=1, profile_idc=100, level_idc=30):
+def param_set_head(params, mb_w=None, mb_h=None, sps_id=0, num_ref_frames=1, profile_idc=100, level_idc=30, width=None, height=None):
     """pcamv_gpu_param_set_head: an SPS unit and a PPS unit for a StreamParams and a picture size in macroblocks, each with a long
-    start code and emulation prevention -- what Batch.stream_open takes as head"""
+    start code and emulation prevention -- what Batch.stream_open takes as head.  With width= and height= in place of mb_w and mb_h
+    (pcamv_gpu_param_set_head2): a picture of that many samples, both even, in (width + 15) // 16 by (height + 15) // 16 macroblocks,
+    with the cropping that cuts the coded picture back to it"""
     out = np.zeros(2 * (6 + PSET_RBSP_MAX * 3 // 2), np.uint8)
     n = C.c_size_t()
-    fn = load_library().pcamv_gpu_param_set_head
+    if (width is None) != (height is None) or (width is None) == (mb_w is None) or (mb_w is None) != (mb_h is None):
+        raise PcamvError("param_set_head takes mb_w and mb_h, or width= and height=")
+    call = "pcamv_gpu_param_set_head" if width is None else "pcamv_gpu_param_set_head2"
+    fn = getattr(load_library(), call)
     fn.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
-    rc = fn(C.byref(params), int(mb_w), int(mb_h), int(sps_id), int(num_ref_frames), int(profile_idc), int(level_idc), _p(out), len(out), C.byref(n))
+    a, b = (mb_w, mb_h) if width is None else (width, height)
+    rc = fn(C.byref(params), int(a), int(b), int(sps_id), int(num_ref_frames), int(profile_idc), int(level_idc), _p(out), len(out), C.byref(n))
     if rc:
-        raise PcamvError(f"pcamv_gpu_param_set_head failed: {rc}")
+        raise PcamvError(f"{call} failed: {rc}")
     return bytes(out[:n.value])
 
 
@@ -788,18 +794,20 @@ def decode_idr(unit, mb_w, mb_h, params=None, chroma_qp_index_offset=0, i4x4=Fal
     return planes, qp, pid
 
 
-def param_set_head_idr(params, mb_w, mb_h, idr_pps_id=1, sps_id=0, num_ref_frames=1, profile_idc=100, level_idc=30, deblocking_filter_control_present=1):
+def param_set_head_idr(params, mb_w=None, mb_h=None, idr_pps_id=1, sps_id=0, num_ref_frames=1, profile_idc=100, level_idc=30, deblocking_filter_control_present=1,
+                       width=None, height=None):
     """the head of a stream whose IDR picture the library writes (Batch.write_stream_idr): param_set_head for the stream's StreamParams,
     then the PPS unit of the same again with pps_id = idr_pps_id, entropy_cabac 0 and deblocking_filter_control_present 1 -- the PPS
     the IDR slices name: SPS, PPS, PPS.  Returns the bytes and the StreamParams of the second set.
-    deblocking_filter_control_present=0 makes that PPS without the flag: only filtered IDR pictures (deblock=True) can name it."""
+    deblocking_filter_control_present=0 makes that PPS without the flag: only filtered IDR pictures (deblock=True) can name it.
+    width= and height= in place of mb_w and mb_h: as in param_set_head."""
     if int(idr_pps_id) == params.pps_id:
         raise PcamvError("param_set_head_idr: the IDR pictures' PPS needs an id of its own")
     second = StreamParams(**{n: getattr(params, n) for n, _ in StreamParams._fields_})
     second.pps_id, second.entropy_cabac, second.deblocking_filter_control_present = int(idr_pps_id), 0, int(bool(deblocking_filter_control_present))
-    again = param_set_head(second, mb_w, mb_h, sps_id, num_ref_frames, profile_idc, level_idc)
+    again = param_set_head(second, mb_w, mb_h, sps_id, num_ref_frames, profile_idc, level_idc, width, height)
     pps = again.find(b"\x00\x00\x00\x01", 4)         # behind the SPS unit, which the first head holds already
-    return param_set_head(params, mb_w, mb_h, sps_id, num_ref_frames, profile_idc, level_idc) + again[pps:], second
+    return param_set_head(params, mb_w, mb_h, sps_id, num_ref_frames, profile_idc, level_idc, width, height) + again[pps:], second
 
 
 FEATURE_RATE = 0x10000          # a QP per context (Batch.step(qps=...), Batch.step_qp_device) and the rate controller on the device (Batch.rate_open, Batch.step_rate, rate_update)
@@ -835,6 +843,93 @@ def rate_update(params, state, length, write_status=0):
     if rc:
         raise PcamvError(f"rate_update failed ({rc}): parameters out of range")
     return d.value
+
+
+FEATURE_SOURCE = 0x20000        # the sender takes a video: Source, Batch.feed, Encoder.upload_picture, source_picture, param_set_head(width=, height=), stream_picture_size
+SRC_I420, SRC_YV12, SRC_NV12, SRC_NV21 = 0, 1, 2, 3
+SRC_VFLIP = 1
+SRC_GUARD = 64                  # PCAMV_SRC_GUARD
+
+
+class Source(C.Structure):
+    """pcamv_source_t: pictures of width x height luma samples (both even) in a clip of bytes -- the format (SRC_I420, SRC_YV12, SRC_NV12,
+    SRC_NV21), flags (SRC_VFLIP: lines bottom-up), per plane its byte offset inside a picture and the bytes between its lines, and the
+    bytes between pictures.  The defaults describe tightly packed planes, one behind the other, and pictures back to back"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("format", C.c_int32), ("flags", C.c_int32), ("plane_off", C.c_int64 * 3),
+                ("pitch", C.c_int64 * 3), ("picture_stride", C.c_int64)]
+
+    def __init__(self, width, height, format=SRC_I420, flags=0, plane_off=None, pitch=None, picture_stride=None):
+        w, h = int(width), int(height)
+        pairs = format in (SRC_NV12, SRC_NV21)
+        tight = [w, w, 0] if pairs else [w, w // 2, w // 2]
+        pitch = list(tight if pitch is None else pitch) + [0] * 3
+        lines = [h, h // 2, h // 2]
+        if plane_off is None:
+            plane_off = [0, pitch[0] * lines[0], 0 if pairs else pitch[0] * lines[0] + pitch[1] * lines[1]]
+        plane_off = list(plane_off) + [0] * 3
+        if picture_stride is None:
+            picture_stride = max(plane_off[k] + pitch[k] * lines[k] for k in range(2 if pairs else 3))
+        super().__init__(w, h, int(format), int(flags), (C.c_int64 * 3)(*[int(v) for v in plane_off[:3]]), (C.c_int64 * 3)(*[int(v) for v in pitch[:3]]),
+                         int(picture_stride))
+
+    @property
+    def mb_size(self):
+        return (self.width + 15) // 16, (self.height + 15) // 16
+
+
+def source_check(source, clip_bytes, mb_w=None, mb_h=None):
+    """pcamv_gpu_source_check: the number of whole pictures a clip of clip_bytes holds under `source`, coded as mb_w x mb_h macroblocks
+    (default: the smallest that hold the picture); raises for a descriptor the library refuses"""
+    mb_w, mb_h = (source.mb_size[0] if mb_w is None else mb_w), (source.mb_size[1] if mb_h is None else mb_h)
+    n = C.c_int64()
+    fn = load_library().pcamv_gpu_source_check
+    fn.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_int64)]
+    rc = fn(C.byref(source), int(clip_bytes), int(mb_w), int(mb_h), C.byref(n))
+    if rc:
+        raise PcamvError(f"pcamv_gpu_source_check failed: {rc}")
+    return n.value
+
+
+def _host_clip(clip):
+    """a clip in host memory as the library reads it: its bytes, not a conversion of something else"""
+    clip = np.asarray(clip)
+    if clip.dtype != np.uint8 or clip.ndim != 1 or (clip.size > 1 and clip.strides[0] != 1):
+        raise PcamvError("the clip is a one-dimensional contiguous uint8 array")
+    return clip
+
+
+def source_picture(source, clip, picture, mb_w=None, mb_h=None):
+    """pcamv_gpu_source_picture, the definition of the source feed without a GPU: picture `picture` of `clip` (a uint8 array; exactly its
+    bytes may be read) as the three planes of the coded size, padded; raises for a descriptor or an index the library refuses"""
+    mb_w, mb_h = (source.mb_size[0] if mb_w is None else mb_w), (source.mb_size[1] if mb_h is None else mb_h)
+    clip = _host_clip(clip)
+    planes = [np.zeros((16 * mb_h >> s, 16 * mb_w >> s), np.uint8) for s in (0, 1, 1)] if 0 < mb_w <= 65536 and 0 < mb_h <= 65536 else [np.zeros((1, 1), np.uint8)] * 3
+    out = (C.c_void_p * 3)(*[a.ctypes.data for a in planes])
+    fn = load_library().pcamv_gpu_source_picture
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64, C.c_int, C.c_int, C.c_void_p]
+    rc = fn(C.byref(source), C.c_void_p(clip.ctypes.data), clip.size, int(picture), int(mb_w), int(mb_h), out)
+    if rc:
+        raise PcamvError(f"pcamv_gpu_source_picture failed: {rc}")
+    return tuple(planes)
+
+
+def stream_picture_size(stream):
+    """(width, height) of the pictures of an Annex B byte stream, from its first SPS: the coded size less the cropping (a host call)"""
+    data = bytes(stream)
+    units, _, _ = annexb_index(data)
+    for u in units:
+        if int(u["nal_header"]) & 31 == 7:
+            rc, sps = parse_sps(nal_to_rbsp(data[int(u["off"]):int(u["off"]) + int(u["len"])])[0])
+            if rc:
+                raise PcamvError(f"stream_picture_size: the stream's first SPS does not parse ({rc})")
+            return 16 * sps.mb_w - 2 * (sps.crop_left + sps.crop_right), 16 * sps.mb_h - 2 * (sps.crop_top + sps.crop_bottom)
+    raise PcamvError("stream_picture_size: the stream has no SPS")
+
+
+def crop_planes(planes, width, height):
+    """decoded or fetched planes (Y, U, V of a coded size) cut down to a picture of width x height"""
+    y, u, v = planes
+    return y[:height, :width], u[:height // 2, :width // 2], v[:height // 2, :width // 2]
 
 
 def features():
@@ -903,6 +998,22 @@ class Encoder:
     def upload_fenc(self, y, u, v):
         keep, ptrs, strides = self._planes(y, u, v)
         self._chk(self.lib.pcamv_gpu_upload_fenc(self.ctx, ptrs, strides), "upload_fenc")
+
+    def upload_picture(self, source, clip, picture=0):
+        """pcamv_gpu_upload_picture: picture `picture` of a host clip (a uint8 array) under `source`, padded to the context's size by the
+        rule of source_picture, as upload_fenc; the clip is taken as source_picture takes it (one-dimensional, contiguous, uint8)"""
+        clip = _host_clip(clip)
+        fn = self.lib.pcamv_gpu_upload_picture
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64]
+        self._chk(fn(self.ctx, C.byref(source), C.c_void_p(clip.ctypes.data), clip.size, int(picture)), "upload_picture")
+
+    def fetch_fenc(self):
+        """pcamv_gpu_debug_fetch_fenc: (the context's own source planes, whole; whether the guard bytes behind them are intact); synchronises"""
+        planes = [np.zeros((self.h >> s, self.w >> s), np.uint8) for s in (0, 1, 1)]
+        arr = (C.c_void_p * 3)(*[a.ctypes.data for a in planes])
+        intact = C.c_int()
+        self._chk(self.lib.pcamv_gpu_debug_fetch_fenc(self.ctx, arr, C.byref(intact)), "debug_fetch_fenc")
+        return tuple(planes), bool(intact.value)
 
     def set_ref(self, y, u, v, prev_mv=None, prev_ref=None):
         keep, ptrs, strides = self._planes(y, u, v)
@@ -1489,6 +1600,27 @@ class Batch:
         """the controllers' states, one record of RATE_STATE_DTYPE per context; synchronises"""
         out = np.zeros(len(self.encs), RATE_STATE_DTYPE)
         self._rate_chk(self.lib.pcamv_gpu_batch_rate_tell(self.b, _p(out)), "batch_rate_tell")
+        return out
+
+    def feed(self, clip, source, picture, stream=0):
+        """pcamv_gpu_batch_feed_device: context i's source becomes picture picture[i] of `clip` (a contiguous uint8 device tensor) under
+        `source`, padded to whole macroblocks, in one launch on `stream`; `picture` is a contiguous int64 device tensor, one index per
+        context.  Both are borrowed until the queued work has run; no host sync.  An index outside the clip: feed_status().
+        Whatever writes `picture` or the clip (the torch add that moves the indices on) must be queued on `stream`, and so must the calls
+        that read the source behind the feed; with stream=0 the feed runs on a context's own non-blocking stream: synchronise first"""
+        if not _is_device_tensor(clip) or not clip.is_cuda or clip.element_size() != 1 or clip.is_floating_point() or not clip.is_contiguous():
+            raise PcamvError("the clip is a contiguous uint8 device tensor")
+        if (not _is_device_tensor(picture) or not picture.is_cuda or picture.element_size() != 8 or picture.is_floating_point() or not picture.is_contiguous() or
+                picture.numel() != len(self.encs)):
+            raise PcamvError("the picture indices are a contiguous int64 device tensor, one per context")
+        fn = self.lib.pcamv_gpu_batch_feed_device
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._rate_chk(fn(self.b, C.c_void_p(clip.data_ptr()), clip.numel(), C.byref(source), C.c_void_p(picture.data_ptr()), C.c_void_p(stream or None)), "batch_feed_device")
+
+    def feed_status(self):
+        """per context: 0, or -1 (EINVAL) where the last feed's index lay outside the clip (that context kept its planes); synchronises"""
+        out = np.zeros(len(self.encs), np.int32)
+        self._rate_chk(self.lib.pcamv_gpu_batch_feed_status(self.b, _p(out)), "batch_feed_status")
         return out
 
     def set_closed_loop(self, on=True):
